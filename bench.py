@@ -6,10 +6,13 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-A "step" is one lockstep pass of the hot path over the whole batch: one Game.step() on every table (T env-steps).
-Table state is resident in HBM before the timed region starts; agents run in-kernel (Philox), finished games
-auto-reset.  Rank 0 prints ONE JSON line.  torch is used only for torch.distributed (barrier / max / sum across the
-one-process-per-GPU ranks); the product path itself is plain HIP behind a ctypes C ABI.
+A "step" is one lockstep pass of the hot path over the whole batch: one Game.step() on every table (T env-steps);
+--steps is the number of timed steps, ms_per_step the time of one.  Table state is resident in HBM before the timed
+region starts; agents run in-kernel (Philox), finished games auto-reset.  Rank 0 prints ONE JSON line.  A plain run
+measures the headline figure alone; --full adds the stand-alone evaluator, the other workloads and the CPU baseline.
+--dump-outputs DIR writes what the timed rollout computed (same arguments, same inputs: builds compare output for output).
+torch is used only for torch.distributed (barrier / max / sum across the one-process-per-GPU ranks); the product path
+itself is plain HIP behind a ctypes C ABI.
 """
 import argparse
 import json
@@ -465,10 +468,38 @@ def env_mode(args, ctx, device):
         print(json.dumps(env_line(res, ctx)))
 
 
+DUMP_LIMIT = 64 << 20     # bytes: --dump-outputs writes at most this much
+
+
+def write_outputs(game, counters, out_dir, table_id_base=0):
+    """--dump-outputs: what a caller of the rollout receives after its last timed step -- the counters rollout() returns and the
+    table state the VecGame getters return -- as float64 <name>.npy files (every value is an integer or a binary64 amount: the
+    cast is exact).  tables.npy holds the global ids of the rows; beyond DUMP_LIMIT the rows are a fixed seeded sample of tables."""
+    import numpy as np
+    rank, kick = game.hand_rankings
+    hand_serial, step_serial = game._serials()
+    state = {"credits": game.credits, "bets": game.bets, "pending_bets": game.pending_bets, "payoffs": game.payoffs,
+             "player_states": game.player_states, "cards": game.deck, "hand_rank": rank, "hand_kickers": kick,
+             "active_player": game.active_player, "turn": game.turn, "dealer_idx": game.dealer_idx, "hand": game.hand,
+             "minimum_raise_value": game.minimum_raise_value, "hand_serial": hand_serial, "step_serial": step_serial}
+    T = game.num_tables
+    row_bytes = 8 * (1 + sum(a.size // T for a in state.values()))             # (+1: tables.npy)
+    rows = min(T, (DUMP_LIMIT - (64 << 10)) // row_bytes)                         # (64 KiB: the files' headers and counters.npy)
+    idx = np.arange(T) if rows == T else np.sort(np.random.default_rng(0).choice(T, rows, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "counters.npy"),
+            np.array([counters[k] for k in ("steps", "hands", "evals", "games")], np.float64))
+    np.save(os.path.join(out_dir, "tables.npy"), (idx + table_id_base).astype(np.float64))
+    for name, a in state.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[idx], dtype=np.float64))
+
+
 def rollout_workload(ctx, device, tables, players, policy_name, K, warmup, chunk=4096, reps=0, min_steps=524288, samples=7,
-                     fused=True, coalesce=-1):
+                     fused=True, coalesce=-1, total=None, dump_dir=None):
     """The fused rollout of one configuration: `samples` timed samples of reps x K steps per table, each bracketed by HIP
-    events on the handle's stream and completed by a sync; the device counters prove the steps were executed."""
+    events on the handle's stream and completed by a sync; the device counters prove the steps were executed.
+    total: the samples share exactly `total` steps per table instead (the headline: --steps is the number of timed steps), in
+    calls of up to `chunk` steps.  dump_dir: write_outputs() of what the rollout leaves after its last timed step."""
     import pokerl_amd
     from pokerl_amd.hipmem import DeviceEvent
     policy = 0 if policy_name == "random" else 1
@@ -478,14 +509,21 @@ def rollout_workload(ctx, device, tables, players, policy_name, K, warmup, chunk
     game.reset()
     if coalesce >= 0:
         game.set_coalesce(coalesce)
-    K = max(1, K)
-    if reps <= 0:   # auto: as many blocks as make a sample >= min_steps steps (unfused: one block -- K launches -- per sample)
-        reps = max(1, -(-min_steps // K)) if fused else 1
+    if total is None:
+        K = max(1, K)
+        if reps <= 0:   # auto: as many blocks as make a sample >= min_steps steps (unfused: one block -- K launches -- per sample)
+            reps = max(1, -(-min_steps // K)) if fused else 1
+        plan = [[K] * reps] * max(1, samples)        # per sample: the blocks it is made of
+    else:
+        n = max(1, min(samples, total))
+        plan = [[total // n + (1 if i < total % n else 0)] for i in range(n)]
+        K, reps = max(p[0] for p in plan), 1
+    sample_steps = [sum(p) for p in plan]
 
-    def block():  # K steps on every table; launches are asynchronous and may defer their stragglers to the next launch
+    def block(k_block):  # k_block steps on every table; launches are asynchronous and may defer their stragglers to the next launch
         done = 0
-        while done < K:
-            k = min(chunk, K - done)
+        while done < k_block:
+            k = min(chunk, k_block - done)
             game.rollout(k, policy, True, fused, counters=False)
             done += k
 
@@ -498,25 +536,28 @@ def rollout_workload(ctx, device, tables, players, policy_name, K, warmup, chunk
     ev0, ev1 = DeviceEvent(), DeviceEvent()
     stats_warm = game.launch_stats(reset=True)           # launches so far (reset + warm-up): a profiler sees those too
     sample_s, sample_dev_ms, sample_stats = [], [], []
-    for _ in range(max(1, samples)):
+    for blocks in plan:
         ctx.barrier(); game.sync()
         game.record_event(ev0.handle)                    # HIP events on the stream the kernel is launched on
         t0 = time.perf_counter()
-        for _ in range(reps):
-            block()
+        for k_block in blocks:
+            block(k_block)
         game.record_event(ev1.handle)                    # completes every deferred / host-held step first, then records
-        game.sync(); ctx.barrier()   # exactly reps*K steps per table are inside
+        game.sync(); ctx.barrier()   # exactly sum(blocks) steps per table are inside
         sample_s.append(ctx.aggregate(0, time.perf_counter() - t0)[1])   # MAX over ranks
         sample_dev_ms.append(DeviceEvent.elapsed_ms(ev0, ev1))
         sample_stats.append(game.launch_stats(reset=True))
     stats = dict(launches=sum(x["launches"] for x in sample_stats), steps=sum(x["steps"] for x in sample_stats),
                  min=min(x["min"] for x in sample_stats), max=max(x["max"] for x in sample_stats))
     c = game.rollout(0, policy, True, fused, counters=True)
-    assert c["steps"] == n_local * K * reps * len(sample_s), (c, n_local, K, reps)
-    assert stats["steps"] == K * reps * len(sample_s), (stats, K, reps)
-    med = sorted(range(len(sample_s)), key=lambda i: sample_s[i])[len(sample_s) // 2]   # the MEDIAN sample: value, ms_per_step and kernel_ms are all its
+    assert c["steps"] == n_local * sum(sample_steps), (c, n_local, sample_steps)
+    assert stats["steps"] == sum(sample_steps), (stats, sample_steps)
+    if dump_dir is not None and ctx.rank == 0:
+        write_outputs(game, c, dump_dir, base)
+    # the MEDIAN sample by time per step: value, ms_per_step and kernel_ms are all its
+    med = sorted(range(len(sample_s)), key=lambda i: sample_s[i] / sample_steps[i])[len(sample_s) // 2]
     seconds = sample_s[med]
-    total_steps = ctx.aggregate(n_local * K * reps, 0.0)[0]
+    total_steps = ctx.aggregate(n_local * sample_steps[med], 0.0)[0]
     scale = 1.0 / (sum(sample_s))   # counters cover all samples
     hands, evals, games = ctx.sum_list([c["hands"], c["evals"], c["games"]])
     # roofline leg: the timed region itself, bracketed by HIP events on the handle's stream; the dominant kernel is the only
@@ -526,7 +567,8 @@ def rollout_workload(ctx, device, tables, players, policy_name, K, warmup, chunk
     kern_steps = sample_stats[med]["steps"] / float(launches)        # mean Game.step()s per table per launch
     game.close()
     return dict(tables=tables, players=players, policy=policy_name, K=K, warmup=warmup, chunk=chunk, reps=reps, fused=fused,
-                n_local=n_local, seconds=seconds, total_steps=total_steps, sample_s=sample_s, sample_dev_ms=sample_dev_ms,
+                n_local=n_local, seconds=seconds, steps_per_sample=sample_steps[med], timed_steps=sum(sample_steps),
+                total_steps=total_steps, sample_s=sample_s, sample_dev_ms=sample_dev_ms,
                 stats=stats, stats_warm=stats_warm, launches=launches, ms_launch=ms_launch, kern_steps=kern_steps,
                 hand_evals_per_s=evals * scale, hands_per_s=hands * scale, games_per_s=games * scale)
 
@@ -788,7 +830,6 @@ def step_line(res, name):
 
 # ---------------------------------------------------------------------------------------------- the ONE stdout line
 LINE_LIMIT = 4096        # the driver keeps the last ~8 KB of stdout: the line must fit with room to spare
-DETAIL_FILE = os.path.join(ROOT, "bench_detail.json")   # everything else: notes, per-sample arrays, the full roofline blocks
 
 
 def _sig(x, digits=5):
@@ -830,9 +871,9 @@ def _short_leg(x):
     return out
 
 
-def compact_line(full):
+def compact_line(full, detail=None):
     """The driver-facing line (<= LINE_LIMIT bytes) out of the full result: the contract's keys, `roofline`, `cpu_baseline`, the
-    evaluator and one short entry per extra leg.  Prose and arrays stay in DETAIL_FILE."""
+    evaluator and one short entry per extra leg.  Prose and arrays stay in the full result (`detail`: the file --detail wrote it to)."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "reps", "samples", "timed_steps_per_table", "timed_s", "lib")
     line = {k: _sig(full[k]) for k in keep if k in full}     # (the self-check keys are absent from results of earlier rounds)
@@ -857,7 +898,7 @@ def compact_line(full):
         line["extra_workloads"] = [_short_leg(x) for x in full["extra_workloads"]]
     if "dist" in full:
         line["dist"] = full["dist"]
-    line["detail"] = os.path.basename(DETAIL_FILE)
+    line["detail"] = detail
     text = json.dumps(line, separators=(",", ":"))
     if len(text) >= LINE_LIMIT and "extra_workloads" in line:       # never observed; the contract keys come first
         line["extra_workloads"] = [{"name": x["name"], "value": x.get("value"), "frac": x.get("frac")} for x in line["extra_workloads"]]
@@ -942,19 +983,24 @@ def pk_lib_info():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=4096, help="K: Game.step()s per table in one timed block")
+    ap.add_argument("--steps", type=int, default=7 * 524288,
+                    help="timed Game.step()s per table, all samples together (the default: seven samples of 524 288 steps, ~1.1 s "
+                         "of GPU work each at 65 536 x 6)")
     ap.add_argument("--warmup", type=int, default=512)
     ap.add_argument("--tables", type=int, default=65536, help="tables per GPU (weak scaling)")
     ap.add_argument("--players", type=int, default=6)
     ap.add_argument("--policy", choices=["random", "allin"], default="random")
-    ap.add_argument("--chunk", type=int, default=4096, help="at most this many steps per fused launch")
-    ap.add_argument("--reps", type=int, default=0,
-                    help="blocks of --steps per timed sample (0 = as many as make a sample >= --min-steps steps, so that a "
-                         "short --steps is not one launch-latency sample)")
-    ap.add_argument("--min-steps", type=int, default=524288,
-                    help="a timed sample runs at least this many steps per table (~1.1 s of GPU work at 65 536 x 6: seven "
-                         "samples keep the GPU busy for ~8 s of a ~16 s run)")
-    ap.add_argument("--samples", type=int, default=7, help="timed samples; the MEDIAN is reported")
+    ap.add_argument("--chunk", type=int, default=4096, help="steps per asynchronous rollout call (at most this many per fused launch)")
+    ap.add_argument("--samples", type=int, default=7, help="timed samples the --steps are split into; the MEDIAN is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure, also run the stand-alone evaluator, the extra_workloads legs (the other "
+                         "BASELINE configs, Game.step, PokerGameEnv) and the CPU baseline")
+    ap.add_argument("--detail", metavar="FILE", default=None,
+                    help="also write the full result (notes, per-sample arrays, the full roofline block of every leg) to FILE as JSON; "
+                         "nothing is written into the source tree")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the rollout leaves to a caller (counters and table state, float64) "
+                         "as DIR/<name>.npy, at most 64 MB (rank 0's tables)")
     ap.add_argument("--unfused", action="store_true", help="one launch per step (state round-trips HBM every step)")
     ap.add_argument("--mode", choices=["game", "env", "step"], default="game")
     ap.add_argument("--step-replay", action="store_true", help="--mode step: the step kernel alone on replayed (pre-picked) actions")
@@ -970,15 +1016,19 @@ def main():
                     help="--mode env --env-async: sub-batches INSIDE each handle (pk_set_env_batches): a call launches one "
                          "range of the handle's tables and delivers the range launched longest ago")
     ap.add_argument("--full-line", action="store_true",
-                    help="print the FULL result (what bench_detail.json holds) on stdout instead of the compact line: for the profiling "
+                    help="print the FULL result (what --detail writes) on stdout instead of the compact line: for the profiling "
                          "tools under tools/, never for the driver (it keeps only the last ~8 KB of stdout)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-evaluator", action="store_true", help="skip the stand-alone evaluator kernel leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_workloads legs (the other BASELINE configs, PokerGameEnv)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-evaluator", action="store_true", help="--full without the stand-alone evaluator kernel leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra_workloads legs (the other BASELINE configs, PokerGameEnv)")
     ap.add_argument("--coalesce", type=int, default=-1,
                     help="host-side merging of asynchronous rollout calls into launches of up to this many steps "
                          "(pk_set_coalesce; -1: the library default 1024, 0: one launch per call)")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.mode != "game":
+        ap.error("--dump-outputs writes what the headline rollout computed (--mode game)")
+    if args.steps < 1 or args.samples < 1 or args.chunk < 1:
+        ap.error("--steps, --samples and --chunk must be positive")
 
     ctx = DistContext()
     if ctx.world != max(1, args.gpus) and ctx.rank == 0:
@@ -1000,23 +1050,24 @@ def main():
         return
     policy = 0 if args.policy == "random" else 1
     fused = not args.unfused
-    w = rollout_workload(ctx, device, args.tables, args.players, args.policy, args.steps, args.warmup, args.chunk,
-                         args.reps, args.min_steps, args.samples, fused, args.coalesce)
-    K, reps = w["K"], w["reps"]
+    w = rollout_workload(ctx, device, args.tables, args.players, args.policy, args.chunk, args.warmup, args.chunk,
+                         samples=args.samples, fused=fused, coalesce=args.coalesce, total=args.steps, dump_dir=args.dump_outputs)
     dist_block = ctx.describe(device, w["n_local"])      # (collective: every rank takes part)
     ctx.barrier()
     if ctx.rank == 0:
         cfg_idx = baseline_config_index(args.tables, args.players, args.policy, ctx.world)
         out = {
             "metric": "env-steps/sec (whole node) + showdown hand-evals/sec, %s tables %d-max" % ("{:,}".format(args.tables).replace(",", " "), args.players),
-            "value": w["total_steps"] / w["seconds"], "unit": "env-steps/s", "n_gpus": ctx.world, "steps": K,
-            "warmup": args.warmup, "ms_per_step": w["seconds"] / (K * reps) * 1e3, "higher_is_better": True,
+            "value": w["total_steps"] / w["seconds"], "unit": "env-steps/s", "n_gpus": ctx.world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": w["seconds"] / w["steps_per_sample"] * 1e3, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "reps": reps, "samples": len(w["sample_s"]), "sample_seconds": w["sample_s"], "sample_device_ms": w["sample_dev_ms"],
+            "samples": len(w["sample_s"]), "sample_seconds": w["sample_s"], "sample_device_ms": w["sample_dev_ms"],
             # self-check: ms_per_step (of the median sample) x timed_steps_per_table ~ timed_s (all samples) <= the run's wall clock
-            "timed_steps_per_table": K * reps * len(w["sample_s"]), "timed_s": sum(w["sample_s"]), "lib": pk_lib_info(),
-            "timing": "each sample = %d block(s) of %d steps per table, launched back to back and completed by a sync inside "
-                      "the timed region; value = steps of one sample / MEDIAN sample time (MAX over ranks per sample)" % (reps, K),
+            "timed_steps_per_table": w["timed_steps"], "timed_s": sum(w["sample_s"]), "lib": pk_lib_info(),
+            "timing": "the %d timed steps per table = %d sample(s) of ~%d steps, each launched back to back in calls of up to %d "
+                      "steps and completed by a sync inside the timed region; value = steps of one sample / its time, of the "
+                      "MEDIAN sample by time per step (MAX over ranks per sample)"
+                      % (args.steps, len(w["sample_s"]), w["steps_per_sample"], args.chunk),
             "config": {"workload": "%d tables/GPU x %d GPU(s), num_players=%d, %s agents in-kernel (Philox4x32-10), "
                                    "start_credits=100 blinds 1/2, auto-reset; %s"
                                    % (args.tables, ctx.world, args.players, args.policy,
@@ -1027,20 +1078,21 @@ def main():
             "hand_evals_per_s": w["hand_evals_per_s"], "hands_per_s": w["hands_per_s"], "games_per_s": w["games_per_s"],
             "roofline": rollout_roofline(w, ctx.world),
         }
-        if not args.no_evaluator:
+        if args.full and not args.no_evaluator:
             out["evaluator"] = evaluator_leg(device)
-        if not args.no_extra and ctx.world == 1 and fused:
+        if args.full and not args.no_extra and ctx.world == 1 and fused:
             try:    # the headline line must survive whatever happens to a secondary leg
                 out["extra_workloads"] = extra_workloads(ctx, device)
             except Exception as e:   # noqa: BLE001
                 out["extra_workloads"] = [{"name": "extra_workloads", "error": "%s: %s" % (type(e).__name__, e)}]
-        if not args.no_cpu_baseline and ctx.world == 1:
+        if args.full and not args.no_cpu_baseline and ctx.world == 1:
             out["cpu_baseline"] = cpu_baseline(args.players, policy)
         if dist_block is not None:
             out["dist"] = dist_block
-        with open(DETAIL_FILE, "w") as f:      # everything: notes, per-sample arrays, the full roofline block of every leg
-            json.dump(out, f, indent=1)
-        print(json.dumps(out) if args.full_line else compact_line(out))   # ONE line of < 4 KB (the driver keeps the last ~8 KB of stdout)
+        if args.detail:
+            with open(args.detail, "w") as f:      # everything: notes, per-sample arrays, the full roofline block of every leg
+                json.dump(out, f, indent=1)
+        print(json.dumps(out) if args.full_line else compact_line(out, args.detail))   # ONE line of < 4 KB (the driver keeps the last ~8 KB of stdout)
     ctx.close()
 
 

@@ -724,13 +724,13 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     env = dict(os.environ, PK_BENCH_BACKEND="gloo", PK_BENCH_SAME_DEVICE="1", MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--tables", "8192", "--steps", "256", "--warmup", "64", "--chunk", "64", "--min-steps", "1024"],
+                          "--gpus", "2", "--tables", "8192", "--steps", "7168", "--warmup", "64", "--chunk", "64"],
                          capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     r = json.loads(line)
     assert len(line) < 4096
-    assert r["n_gpus"] == 2 and r["scaling"] == "weak" and r["steps"] == 256
+    assert r["n_gpus"] == 2 and r["scaling"] == "weak" and r["steps"] == 7168 and r["timed_steps_per_table"] == 7168
     assert r["value"] > 0 and abs(r["value"] - 2 * 8192 * 256 / (r["ms_per_step"] * 256 / 1e3)) / r["value"] < 1e-3
     assert "cpu_baseline" not in r and r["roofline"]["frac"] > 0
     # the `dist` block: the collective library saw both ranks, each with its shard (value = units of ALL ranks / MAX seconds, above)
@@ -951,20 +951,19 @@ def test_empty_and_minimal_inputs(HB, O):
     assert h.rollout(300, 0)[0] == 300
 
 
-def test_bench_json_contract():
-    """`python bench.py` prints exactly ONE JSON line on stdout -- under 4 KB, so that it fits the tail of stdout the driver keeps --
-    with every field the driver's contract names; everything else (notes, per-sample arrays, the full roofline block of every leg) is
-    in bench_detail.json next to bench.py."""
+def test_bench_json_contract(tmp_path):
+    """`python bench.py --full` prints exactly ONE JSON line on stdout -- under 4 KB, so that it fits the tail of stdout the driver keeps --
+    with every field the driver's contract names and the --full legs; everything else (notes, per-sample arrays, the full roofline block of
+    every leg) is in the file --detail names."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PK_BENCH_CPU_BUDGET="1", PK_BENCH_EVAL_LOG2="22")
-    detail_path = os.path.join(root, "bench_detail.json")
-    if os.path.exists(detail_path):
-        os.remove(detail_path)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "256", "--warmup", "64"],
+    detail_path = str(tmp_path / "bench_detail.json")
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--steps", str(256 * 2048 * 7), "--warmup", "64",
+                          "--chunk", "256", "--detail", detail_path],
                          capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -975,7 +974,7 @@ def test_bench_json_contract():
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "evaluator", "extra_workloads", "detail"):
         assert k in c, k
     assert c["metric"] == "env-steps/sec (whole node) + showdown hand-evals/sec, 65 536 tables 6-max"      # BASELINE.json's metric
-    assert c["n_gpus"] == 1 and c["steps"] == 256 and c["warmup"] == 64 and c["higher_is_better"] is True
+    assert c["n_gpus"] == 1 and c["steps"] == 256 * 2048 * 7 and c["warmup"] == 64 and c["higher_is_better"] is True
     assert c["scaling"] == "weak" and c["vs_baseline"] is None and c["dtype"] == "f64" and c["data"] == "synthetic"
     assert "workload" in c["config"] and "model" not in c["config"] and "BASELINE configs[2]" in c["config"]["workload"]
     assert c["config"]["kernel"].startswith("k_rollout_tab<6>") and "dist" not in c      # (256-step launches: the table-evaluator variant)
@@ -999,20 +998,20 @@ def test_bench_json_contract():
     # the line checks itself: ms_per_step (median sample) x the steps every table made inside the timed samples = the timed
     # seconds (all samples), which fit inside this run's wall clock; `lib` names the kernel sources the figures were measured on
     from pokerl_amd import _lib as L
-    assert c["timed_steps_per_table"] == c["steps"] * c["reps"] * c["samples"] == c["config"]["launch_stats"]["steps"]
+    assert c["timed_steps_per_table"] == c["steps"] == c["config"]["launch_stats"]["steps"] and c["samples"] == 7
     assert abs(c["ms_per_step"] * 1e-3 * c["timed_steps_per_table"] - c["timed_s"]) < 0.15 * c["timed_s"], (c["ms_per_step"], c["timed_steps_per_table"], c["timed_s"])
     assert c["lib"] == L.lib().pk_build_info().decode() and c["lib"].startswith("abi=6 src=")
     assert isinstance(crf["profile_stale"], bool)
     assert abs(cx[1]["hand_evals_per_s"] / cx[1]["value"] - 1.0) < 1e-3       # configs[4]: one in-game evaluation per env-step
 
     # ---- the detail file: what the line held up to round 4
-    assert c["detail"] == "bench_detail.json"
+    assert c["detail"] == detail_path
     r = json.load(open(detail_path))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in r, k
     assert abs(r["value"] - 65536 * 256 / (r["ms_per_step"] * 256 / 1e3)) / r["value"] < 1e-6 and abs(r["value"] - c["value"]) / r["value"] < 1e-4
-    assert r["reps"] == 2048 and r["samples"] == 7 and len(r["sample_seconds"]) == 7   # 2 048 blocks of 256 steps = 524 288 per sample
+    assert r["samples"] == 7 and len(r["sample_seconds"]) == 7 and r["timed_steps_per_table"] == 256 * 2048 * 7   # 2 048 calls of 256 steps = 524 288 per sample
     rf = r["roofline"]
     # the binding roofline leads: VALU issue, from the committed rocprofv3 PMC summary of this workload x this run's launch time
     assert rf["bound"] == "valu-issue" and rf["unit"] == "wave-instr/s" and rf["peak"] == 256 * 4 * 2.4e9 / 2
@@ -1068,6 +1067,60 @@ def test_bench_json_contract():
     assert rf["profile_stale"] == (src.get("source_hash") != L.source_hash()) == crf["profile_stale"]
     for short, full in zip(cx, xs):
         assert bool(short.get("profile_stale", False)) == bool(full["roofline"].get("profile_stale", False)), short["name"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path, O):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` measures the headline figure alone -- exactly N timed steps per table, none of
+    the --full legs -- and --dump-outputs writes what the timed rollout left: the same files from run to run, and the CPU oracle's
+    state after W + N steps of the same tables."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(d, *extra):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "300", "--warmup", "40",
+                              "--dump-outputs", str(d)] + list(extra), capture_output=True, text=True, timeout=300, cwd=root)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+
+    def files(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    def tree():
+        return sorted(f for f in os.listdir(root) if f != "__pycache__")
+
+    before = tree()
+    c = run(tmp_path / "a")
+    assert c["detail"] is None and tree() == before       # the run writes nothing into the source tree
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype", "config"):
+        assert k in c, k
+    assert not {"cpu_baseline", "evaluator", "extra_workloads"} & set(c)
+    assert c["metric"] == "env-steps/sec (whole node) + showdown hand-evals/sec, 65 536 tables 6-max" and c["unit"] == "env-steps/s"
+    assert c["steps"] == 300 and c["warmup"] == 40 and c["timed_steps_per_table"] == 300 == c["config"]["launch_stats"]["steps"]
+    assert abs(c["value"] - 65536 / (c["ms_per_step"] / 1e3)) / c["value"] < 1e-3 and c["hand_evals_per_s"] > 0
+    a = files(tmp_path / "a")
+    assert sum(os.path.getsize(os.path.join(tmp_path / "a", f)) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert a["credits"].shape == (65536, 6) and np.array_equal(a["tables"], np.arange(65536)) and a["counters"][0] == 65536 * 300
+    run(tmp_path / "b")
+    b = files(tmp_path / "b")
+    assert sorted(a) == sorted(b) and all(a[k].tobytes() == b[k].tobytes() for k in a)
+
+    run(tmp_path / "c", "--tables", "2048")
+    d = files(tmp_path / "c")
+    o = O.OracleGame(2048, 6)
+    o.reset()
+    co, err = o.rollout(340, 0, True)
+    snap = o.snapshot()
+    assert err == 0 and d["counters"][0] == 2048 * 300 and co[0] == 2048 * 340
+    for name, key in [("credits", "credits"), ("bets", "bets"), ("pending_bets", "pending"), ("payoffs", "payoffs"),
+                      ("player_states", "states"), ("cards", "cards"), ("hand_rank", "srank"), ("hand_kickers", "skick"),
+                      ("active_player", "active"), ("turn", "turn"), ("dealer_idx", "dealer"), ("hand", "hand"),
+                      ("minimum_raise_value", "min_raise"), ("hand_serial", "hand_serial"), ("step_serial", "step_serial")]:
+        assert np.array_equal(d[name], snap[key].astype(np.float64)), name
 
 
 @pytest.mark.parametrize("N,policy", [(6, 0), (9, 1), (2, 0), (10, 0)])

@@ -231,6 +231,48 @@ def test_bench_line_is_compact():
     assert len(bench.compact_line(full)) < bench.LINE_LIMIT
 
 
+def test_bench_dump_outputs_fit_and_sample_by_seed(tmp_path):
+    """--dump-outputs: every getter's array as float64, one row per table; a batch too large for 64 MB is written as a fixed, seeded
+    sample of tables (tables.npy: their global ids), the same from run to run.  --dump-outputs belongs to the headline rollout."""
+    import bench
+
+    class Game:      # the getters write_outputs reads, with the shapes and dtypes of VecGame's
+        def __init__(self, T, N):
+            r = np.random.default_rng(T)
+            self.num_tables = T
+            f = lambda *s: r.integers(0, 200, s).astype(np.float64)
+            u = lambda dt, *s: r.integers(0, 50, s).astype(dt)
+            self.credits, self.bets, self.pending_bets, self.payoffs = f(T, N), f(T, N), f(T, N), f(T, N)
+            self.player_states, self.deck, self.hand_rankings = u(np.uint8, T, N), u(np.uint8, T, 5 + 2 * N), (u(np.uint8, T, N), u(np.uint32, T, N))
+            self.active_player, self.turn, self.dealer_idx, self.hand = (u(np.int32, T) for _ in range(4))
+            self.minimum_raise_value = f(T)
+            self.serials = (u(np.uint64, T), u(np.uint64, T))
+
+        def _serials(self):
+            return self.serials
+
+    counters = dict(steps=6 * 300, hands=7, evals=8, games=9)
+    g = Game(1000, 6)
+    bench.write_outputs(g, counters, str(tmp_path / "small"), table_id_base=5000)
+    d = {f[:-4]: np.load(str(tmp_path / "small" / f)) for f in os.listdir(str(tmp_path / "small"))}
+    assert all(x.dtype == np.float64 for x in d.values()) and d["counters"].tolist() == [1800, 7, 8, 9]
+    assert np.array_equal(d["tables"], 5000 + np.arange(1000)) and np.array_equal(d["credits"], g.credits)
+    assert np.array_equal(d["cards"], g.deck) and np.array_equal(d["hand_kickers"], g.hand_rankings[1]) and np.array_equal(d["step_serial"], g.serials[1])
+    big = Game(160000, 16)         # 1 256 B per table: 200 MB in all
+    for name in ("x", "y"):
+        bench.write_outputs(big, counters, str(tmp_path / name))
+    sizes = [os.path.getsize(str(tmp_path / "x" / f)) for f in os.listdir(str(tmp_path / "x"))]
+    assert 60 << 20 < sum(sizes) <= bench.DUMP_LIMIT == 64 << 20
+    x = {f: np.load(str(tmp_path / "x" / f)) for f in os.listdir(str(tmp_path / "x"))}
+    y = {f: np.load(str(tmp_path / "y" / f)) for f in os.listdir(str(tmp_path / "y"))}
+    assert all(x[f].tobytes() == y[f].tobytes() for f in x)
+    rows = x["tables.npy"].astype(np.int64)
+    assert len(rows) < 160000 and np.all(np.diff(rows) > 0) and np.array_equal(x["payoffs.npy"], big.payoffs[rows])
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "env", "--dump-outputs", str(tmp_path / "z")],
+                         capture_output=True, text=True, timeout=60)
+    assert out.returncode == 2 and "--dump-outputs" in out.stderr and not os.path.exists(str(tmp_path / "z"))
+
+
 def test_source_hash_ignores_comments_and_is_embedded():
     """pokerl_amd/build.py source_hash(): over the kernel sources without comments / white space + the compiler flags; the built library
     reports the hash it was built from (pk_build_info) and the summaries under profiles/ that were made in round 6 or later carry one."""

@@ -8,5 +8,5 @@ for lib in "" pokerl_amd/libpokerl_hip_dev6.so; do
   python bench.py --mode env --steps 300 --warmup 30 2>/dev/null | tail -1 | python -c "import json,sys; r=json.loads(sys.stdin.read()); print('  env.step sync           %.4f G env.step/s  %.1f us/launch' % (r['value']/1e9, r['roofline']['kernel_ms']*1e3))"
   python bench.py --mode env --steps 2000 --warmup 200 --env-async 8 2>/dev/null | tail -1 | python -c "import json,sys; r=json.loads(sys.stdin.read()); print('  env.step async8         %.4f G env.step/s  %.1f us/launch' % (r['value']/1e9, r['roofline']['kernel_ms']*1e3))"
   done
-  python bench.py --full-line --unfused --steps 512 --warmup 64 --no-cpu-baseline --no-evaluator --samples 3 2>/dev/null | tail -1 | python -c "import json,sys; r=json.loads(sys.stdin.read()); print('  rollout unfused (k_rollout_single) %.3f G' % (r['value']/1e9))"
+  python bench.py --full-line --unfused --steps 1536 --warmup 64 --samples 3 2>/dev/null | tail -1 | python -c "import json,sys; r=json.loads(sys.stdin.read()); print('  rollout unfused (k_rollout_single) %.3f G' % (r['value']/1e9))"
 done

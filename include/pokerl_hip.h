@@ -456,6 +456,60 @@ int pk_wait_event(pk_handle *h, void *event);
 int pk_record_event(pk_handle *h, void *event);
 /* Completes deferred rollout steps and waits until everything requested so far has finished. */
 int pk_sync(pk_handle *h);
+
+/* ---- Snapshots: save, restore and clone tables (copy.deepcopy / pickle of a Game, checkpoints, search over copies).
+ *
+ * A snapshot is a position-independent byte blob of m table RECORDS.  It holds no pointers: it can be written to disk or moved to another
+ * device or process running the same library build.  Layout (pk_snapshot_bytes(N, m) bytes):
+ *   header, 256 bytes: u32 magic "PKSN", u32 format version (1), u32 N, u32 0, u64 m, f64 start_credits[16] (seats >= N: 0),
+ *                      f64 big_blind, f64 small_blind, zero padding;
+ *   records, FIELD-MAJOR: each field an array [rows][m] that starts 256-byte aligned (offset of the next = previous + round_up(bytes, 256)):
+ *     credits, bets, pending_bets, payoffs  f64 [N][m]     min_raise  f64 [m]     seat_states  u64 [m]     hand_serial, step_serial  u64 [m]
+ *     cursors  u32 [m]     hand  i32 [m]     cards  u32 [ceil((5+2N)/4)][m]     show  u32 [N][m]     valid, terr  u8 [m]
+ *   (the fields of the handle's own table state, table-major along m: one lane per table reads and writes coalesced words on both sides).
+ * A record is everything a caller can observe of a table or that decides its future.  Not in a record: the deferred-launch and in-flight
+ * bookkeeping (zero for an idle table; a load or clone writes zeros there), counters, the seed key and the table id.
+ * FUTURE RANDOMNESS BELONGS TO THE DESTINATION: its seed key and its table id table_id_base + t.  A record carries the table's serials, so
+ *   - a table restored into the same slot of the same handle, or of a handle with the same seed and table_id_base, continues bit-identically;
+ *   - a table cloned into another slot continues its CURRENT hand identically under the same actions; its next decks and random-agent draws
+ *     are those of the new table id.
+ * Every entry point below completes deferred rollout work first, returns PK_E_BUSY while steps of pk_step_async_d / pk_env_step_async_d /
+ * pk_env_step_begin are in flight (on either handle of a clone; nothing written), treats m == 0 as a no-op and is ordered on the handle's
+ * stream.  `tables` / `tables_d` (int32 [m], NULL = tables 0 .. m-1) name the tables.  Refused with PK_E_INVALID_ARG, the reason in
+ * pk_last_error and NOTHING written: a table index out of range; a destination named twice (sources may repeat); handles on different
+ * devices; N or the money configuration (start credits, blinds) differing between blob / source and destination; a bad magic or version; a
+ * load whose m differs from the blob's; an observer outside {-2, -1, 0 .. N-1}.  A call that takes an index array, and every load, checks on
+ * the device and reads one refusal word back before it writes (the call waits for its stream up to there).
+ * Blobs in device memory must be 8-byte aligned. */
+#define PK_OBSERVER_NONE (-1)   /* clone: an exact copy */
+#define PK_OBSERVER_ACTIVE (-2) /* clone: redeal from the point of view of each source table's active player */
+/* Bytes of a blob of m records at N seats; 0 for N outside [PK_MIN_PLAYERS, PK_MAX_PLAYERS].  Needs no device. */
+size_t pk_snapshot_bytes(int num_players, size_t m);
+/* Save m tables into blob_d (device memory, asynchronous without an index array). */
+int pk_save_tables_d(pk_handle *h, const int32_t *tables_d, size_t m, void *blob_d);
+/* Restore m records of blob_d into the named tables.  Every record is checked on the device BEFORE any write, and the whole call is
+ * refused if one fails -- a blob from this library always passes; a corrupted one must never make a later kernel index out of bounds:
+ * cursor nibbles (active, dealer, sb, bb) < N, turn <= 4 (a finished game may stay at 4, game.py:561-564), in-flight bits 20..31 zero; the
+ * four 16-bit seat masks use bits < N only and are pairwise disjoint; every card byte a Card.value and the 5+2N cards distinct -- or,
+ * for a table never dealt (created, not reset yet), all 5+2N bytes zero at turn 0; all money finite; valid < 128.  A clone copies the
+ * zero deck of a never-dealt table as it is (there is nothing hidden to redeal). */
+int pk_load_tables_d(pk_handle *h, const int32_t *tables_d, size_t m, const void *blob_d);
+/* The same through host memory (tables and blob), synchronous. */
+int pk_save_tables(pk_handle *h, const int32_t *tables, size_t m, void *blob);
+int pk_load_tables(pk_handle *h, const int32_t *tables, size_t m, const void *blob);
+/* Table src_tables_d[i] of `src` -> table dst_tables_d[i] of `dst`, on dst's stream (after src's queued work; src's later work waits for
+ * the clone's reads).  dst == src and overlapping index sets are allowed: the result is that of all reads before any write.
+ * observer PK_OBSERVER_NONE: an exact copy.  observer = a seat p (0 .. N-1), or PK_OBSERVER_ACTIVE (p = each source table's active
+ * player): a REDEAL of the cards p cannot see, so that a search over the copies does not know the future board or the opponents' cards.
+ * p sees the board deck[0:nb] (nb = 0 at turn 0, else min(turn + 2, 5): game.py:266-278) and its hole cards deck[5+2p : 7+2p]; they stay.
+ * The hidden slots -- board nb..4, then the two hole cards of every other seat in ascending seat order, folded and broken seats included --
+ * are refilled by a uniform draw without replacement from the P = 52 - nb - 2 cards p has not seen (the deck's RNG spec with its own
+ * stream): Philox4x32-10 with the DESTINATION's key, counter (dst table id, nonce lo, 'RDL0' + b, nonce hi), 64-bit words
+ * X[2b] = w0 | w1 << 32, X[2b+1] = w2 | w3 << 32, chained bounded draws c_i = (x * (P - i)) >> 64 (x = X[i / 9] when i % 9 == 0, then
+ * x = low 64 bits of the product), card i = the c_i-th not yet drawn unseen card in canonical order (value[k] = ((k%4)<<4) | (k/4)).
+ * Money, cursors, serials, show, valid and terr are copied unchanged.  Both handles need the same N and money configuration. */
+int pk_clone_tables_d(pk_handle *dst, const int32_t *dst_tables_d, pk_handle *src, const int32_t *src_tables_d, size_t m, int observer,
+                      uint64_t nonce);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

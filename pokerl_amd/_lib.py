@@ -19,6 +19,7 @@ POLICY_EXTERNAL = 15
 ABI_VERSION = 6
 NUM_COUNTERS = 4
 MIN_PLAYERS, MAX_PLAYERS = 2, 16
+OBSERVER_NONE, OBSERVER_ACTIVE = -1, -2   # pk_clone_tables_d: an exact copy / redeal from each source table's active player
 
 # every symbol include/pokerl_hip.h declares (tests check the library exports each one)
 SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "pk_destroy", "pk_num_tables",
@@ -31,7 +32,8 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_pick_actions_d", "pk_flush", "pk_get_owed", "pk_env_step_fused_d", "pk_env_step_async_d", "pk_set_tuning", "pk_get_stream", "pk_set_stream", "pk_wait_event",
            "pk_record_event", "pk_use_own_stream", "pk_set_coalesce", "pk_get_launch_stats", "pk_env_step_multi_d", "pk_env_end_multi_d", "pk_get_f64_d", "pk_set_env_batches", "pk_env_last_range",
            "pk_get_obs_packed", "pk_get_obs_packed_d", "pk_set_env_obs_packed", "pk_host_alloc", "pk_host_free", "pk_check_actions",
-           "pk_env_step_begin", "pk_env_step_end", "pk_reset_d", "pk_step_auto_d", "pk_stream_pool_drain", "pk_step_async_d", "pk_set_step_obs", "pk_build_info"]
+           "pk_env_step_begin", "pk_env_step_end", "pk_reset_d", "pk_step_auto_d", "pk_stream_pool_drain", "pk_step_async_d", "pk_set_step_obs", "pk_build_info",
+           "pk_snapshot_bytes", "pk_save_tables_d", "pk_load_tables_d", "pk_save_tables", "pk_load_tables", "pk_clone_tables_d"]
 
 
 class PokerlHipError(RuntimeError):
@@ -124,9 +126,14 @@ def lib():
     L.pk_wait_event.argtypes = [_vp, _vp]
     L.pk_record_event.argtypes = [_vp, _vp]
     L.pk_time_rollout.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _vp]
+    L.pk_snapshot_bytes.argtypes = [C.c_int, C.c_size_t]
+    for name in ("pk_save_tables_d", "pk_load_tables_d", "pk_save_tables", "pk_load_tables"):
+        getattr(L, name).argtypes = [_vp, _vp, C.c_size_t, _vp]
+    L.pk_clone_tables_d.argtypes = [_vp, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_uint64]
     for name in SYMBOLS:
-        if name not in ("pk_last_error", "pk_build_info"):
+        if name not in ("pk_last_error", "pk_build_info", "pk_snapshot_bytes"):
             getattr(L, name).restype = C.c_int
+    L.pk_snapshot_bytes.restype = C.c_size_t
     if L.pk_abi_version() != ABI_VERSION:
         raise PokerlHipError("libpokerl_hip.so ABI version mismatch")
     _lib = L

@@ -12,6 +12,7 @@
 
 #include "pk_device.hpp"
 #include "pk_kernels.hpp"
+#include "pk_snapshot.hpp"
 
 using namespace pk;
 
@@ -84,6 +85,13 @@ struct pk_handle {
     uint8_t *env_obs_packed = nullptr;   // pk_set_env_obs_packed: device buffer [T][PK_OBS_PACKED_BYTES(N)] or NULL
     double *step_obs = nullptr;          // pk_set_step_obs: device buffers the Game.step kernels write the row of the player to act into, or NULL
     uint8_t *step_obs_packed = nullptr;
+    // snapshots (pk_save_tables_d ...), allocated on first use: the refusal word the check kernels write, one count per table for the
+    // duplicate / overlap checks of destination indices, a grow-only staging buffer (host-memory calls, overlapping clones) and the event
+    // that orders a clone between two handles' streams
+    uint32_t *snap_word = nullptr, *snap_mark = nullptr;
+    void *snap_stage = nullptr;
+    size_t snap_stage_bytes = 0;
+    hipEvent_t snap_ev = nullptr;
     std::string err;
     int fail(int code, const char *what, hipError_t e = hipSuccess) {
         err = what;
@@ -593,6 +601,10 @@ int pk_destroy(pk_handle *h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->arena) (void)hipFree(h->arena);
     if (h->d_obs_packed) (void)hipFree(h->d_obs_packed);
+    if (h->snap_word) (void)hipFree(h->snap_word);
+    if (h->snap_mark) (void)hipFree(h->snap_mark);
+    if (h->snap_stage) (void)hipFree(h->snap_stage);
+    if (h->snap_ev) (void)hipEventDestroy(h->snap_ev);
     if (h->h_pinned) (void)hipHostFree(h->h_pinned);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -1363,6 +1375,224 @@ int pk_sync(pk_handle *h) {
     if (!in_flight(h)) FLUSH(h);     // env steps in flight stay in flight: only wait for the launches made so far
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int b = 0; b < h->env_batches && h->env_batches > 1; ++b) HIPCHK(h, hipStreamSynchronize(h->env_streams[b]));
+    return PK_OK;
+}
+
+// ---- snapshots (pokerl_hip.h "Snapshots"; kernels: pk_snapshot.hip)
+static int snap_prepare(pk_handle *h) {   // the refusal word, the per-table marks and the event, on first use; the device is current
+    if (!h->snap_word) HIPCHK(h, hipMalloc(&h->snap_word, 256));
+    if (!h->snap_mark) HIPCHK(h, hipMalloc(&h->snap_mark, (size_t)h->T * 4));
+    if (!h->snap_ev) HIPCHK(h, hipEventCreateWithFlags(&h->snap_ev, hipEventDisableTiming));
+    return PK_OK;
+}
+static int snap_staging(pk_handle *h, size_t bytes, char **out) {   // grow-only; a buffer in use by queued work is waited for before it is freed
+    if (bytes > h->snap_stage_bytes) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->snap_stage) (void)hipFree(h->snap_stage);
+        h->snap_stage = nullptr; h->snap_stage_bytes = 0;
+        const hipError_t e = hipMalloc(&h->snap_stage, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); h->snap_stage = nullptr; return h->fail(PK_E_OOM, "snapshot staging buffer", e); }
+        h->snap_stage_bytes = bytes;
+    }
+    *out = (char *)h->snap_stage;
+    return PK_OK;
+}
+static SnapHeader snap_header_of(const pk_handle *h, size_t m) {
+    SnapHeader hd{};
+    hd.magic = SNAP_MAGIC; hd.version = SNAP_VERSION; hd.num_players = (uint32_t)h->N; hd.m = m;
+    for (int i = 0; i < PK_MAX_PLAYERS; ++i) hd.start_credits[i] = h->S.start_credits[i];
+    hd.big_blind = h->S.big_blind; hd.small_blind = h->S.small_blind;
+    return hd;
+}
+static bool snap_same_money(const pk_handle *a, const SnapHeader &b) {   // (start credits of unused seats are 0 on both sides)
+    bool same = a->S.big_blind == b.big_blind && a->S.small_blind == b.small_blind;
+    for (int i = 0; i < PK_MAX_PLAYERS; ++i) same = same && a->S.start_credits[i] == b.start_credits[i];
+    return same;
+}
+// Reads the refusal word the check kernels queued on h->stream (waits for the stream); non-zero refusal bits fail the call.
+static int snap_verdict(pk_handle *h, const char *call, uint32_t *word_out) {
+    uint32_t w = 0;
+    HIPCHK(h, hipMemcpyAsync(&w, h->snap_word, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (word_out) *word_out = w;
+    if (!(w & ~SNAP_OVERLAP)) return PK_OK;
+    std::string s = std::string(call) + ": refused, nothing written:";
+    if (w & SNAP_BAD_SRC_INDEX) s += " a source table index is out of range;";
+    if (w & SNAP_BAD_DST_INDEX) s += " a destination table index is out of range;";
+    if (w & SNAP_DUP_DST) s += " a destination table is named twice;";
+    if (w & SNAP_BAD_CURSOR) s += " a record's cursors are invalid (seat nibble >= N, turn > 4 or in-flight bits set);";
+    if (w & SNAP_BAD_SEATS) s += " a record's seat masks use seats >= N or overlap;";
+    if (w & SNAP_BAD_CARD) s += " a record holds a byte that is no card, or a card twice;";
+    if (w & SNAP_BAD_MONEY) s += " a record holds money that is inf or NaN;";
+    if (w & SNAP_BAD_VALID) s += " a record's valid-action mask has bit 7 set;";
+    return h->fail(PK_E_INVALID_ARG, s.c_str());
+}
+// Checks an index array on the device: in range, and (dst) no table twice.
+static int snap_check_tables(pk_handle *h, const int32_t *tables_d, size_t m, bool dst) {
+    if (!tables_d) return PK_OK;
+    if (dst) HIPCHK(h, hipMemsetAsync(h->snap_mark, 0, (size_t)h->T * 4, h->stream));
+    HIPCHK(h, snap_check_idx(h->stream, tables_d, m, h->T, dst ? h->snap_mark : nullptr, 0, dst ? SNAP_BAD_DST_INDEX : SNAP_BAD_SRC_INDEX,
+                             h->snap_word));
+    return PK_OK;
+}
+static int snap_save(pk_handle *h, const int32_t *tables_d, size_t m, void *blob_d, const char *call) {
+    if (!tables_d && m > (size_t)h->T) return h->fail(PK_E_INVALID_ARG, (std::string(call) + ": tables NULL and m > the handle's tables").c_str());
+    if ((uintptr_t)blob_d & 7) return h->fail(PK_E_INVALID_ARG, (std::string(call) + ": blob must be 8-byte aligned").c_str());
+    if (tables_d) {
+        int rc = snap_prepare(h);
+        if (rc) return rc;
+        HIPCHK(h, hipMemsetAsync(h->snap_word, 0, 4, h->stream));
+        if ((rc = snap_check_tables(h, tables_d, m, false))) return rc;
+        if ((rc = snap_verdict(h, call, nullptr))) return rc;
+    }
+    SnapView blob;
+    SnapPads pads;
+    snap_layout(h->N, m, (char *)blob_d, &blob, &pads);
+    HIPCHK(h, snap_copy(h->stream, SNAP_KIND_SAVE, snap_view_of_state(h->S), tables_d, blob, nullptr, h->N, m, Redeal{PK_OBSERVER_NONE, 0, 0, 0, 0},
+                        snap_header_of(h, m), blob_d, pads));
+    return PK_OK;
+}
+static int snap_load(pk_handle *h, const int32_t *tables_d, size_t m, const void *blob_d, const char *call) {
+    const std::string c(call);
+    if ((uintptr_t)blob_d & 7) return h->fail(PK_E_INVALID_ARG, (c + ": blob must be 8-byte aligned").c_str());
+    SnapHeader hd{};
+    HIPCHK(h, hipMemcpyAsync(&hd, blob_d, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (hd.magic != SNAP_MAGIC || hd.version != SNAP_VERSION) return h->fail(PK_E_INVALID_ARG, (c + ": not a snapshot of this format (magic / version)").c_str());
+    if (hd.num_players != (uint32_t)h->N) return h->fail(PK_E_INVALID_ARG, (c + ": the blob holds tables of another number of seats").c_str());
+    if (!snap_same_money(h, hd)) return h->fail(PK_E_INVALID_ARG, (c + ": the blob's start credits or blinds differ from the handle's").c_str());
+    if (hd.m != m) return h->fail(PK_E_INVALID_ARG, (c + ": m differs from the blob's record count").c_str());
+    if (m > (size_t)h->T) return h->fail(PK_E_INVALID_ARG, (c + ": more records than the handle has tables").c_str());
+    int rc = snap_prepare(h);
+    if (rc) return rc;
+    SnapView blob;
+    snap_layout(h->N, m, (char *)const_cast<void *>(blob_d), &blob);
+    HIPCHK(h, hipMemsetAsync(h->snap_word, 0, 4, h->stream));
+    if ((rc = snap_check_tables(h, tables_d, m, true))) return rc;
+    HIPCHK(h, snap_check_records(h->stream, blob, h->N, m, h->snap_word));
+    if ((rc = snap_verdict(h, call, nullptr))) return rc;
+    HIPCHK(h, snap_copy(h->stream, SNAP_KIND_LOAD, blob, nullptr, snap_view_of_state(h->S), tables_d, h->N, m, Redeal{PK_OBSERVER_NONE, 0, 0, 0, 0},
+                        SnapHeader{}, nullptr, SnapPads{}));
+    return PK_OK;
+}
+
+size_t pk_snapshot_bytes(int num_players, size_t m) {
+    if (num_players < PK_MIN_PLAYERS || num_players > PK_MAX_PLAYERS) return 0;
+    return snap_layout(num_players, m, nullptr, nullptr);
+}
+
+int pk_save_tables_d(pk_handle *h, const int32_t *tables_d, size_t m, void *blob_d) {
+    if (!h || !blob_d) return h ? h->fail(PK_E_INVALID_ARG, "pk_save_tables_d: NULL blob") : PK_E_INVALID_ARG;
+    ON_DEVICE(h);
+    FLUSH(h);
+    if (m == 0) return PK_OK;
+    return snap_save(h, tables_d, m, blob_d, "pk_save_tables_d");
+}
+
+int pk_load_tables_d(pk_handle *h, const int32_t *tables_d, size_t m, const void *blob_d) {
+    if (!h || !blob_d) return h ? h->fail(PK_E_INVALID_ARG, "pk_load_tables_d: NULL blob") : PK_E_INVALID_ARG;
+    ON_DEVICE(h);
+    FLUSH(h);
+    if (m == 0) return PK_OK;
+    return snap_load(h, tables_d, m, blob_d, "pk_load_tables_d");
+}
+
+int pk_save_tables(pk_handle *h, const int32_t *tables, size_t m, void *blob) {
+    if (!h || !blob) return h ? h->fail(PK_E_INVALID_ARG, "pk_save_tables: NULL blob") : PK_E_INVALID_ARG;
+    ON_DEVICE(h);
+    FLUSH(h);
+    if (m == 0) return PK_OK;
+    if (!tables && m > (size_t)h->T) return h->fail(PK_E_INVALID_ARG, "pk_save_tables: tables NULL and m > the handle's tables");   // (before staging)
+    const size_t idx_bytes = tables ? snap_align(m * 4) : 0, bytes = pk_snapshot_bytes(h->N, m);
+    char *stage = nullptr;
+    int rc = snap_staging(h, idx_bytes + bytes, &stage);
+    if (rc) return rc;
+    if (tables) HIPCHK(h, hipMemcpyAsync(stage, tables, m * 4, hipMemcpyHostToDevice, h->stream));
+    if ((rc = snap_save(h, tables ? (const int32_t *)stage : nullptr, m, stage + idx_bytes, "pk_save_tables"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(blob, stage + idx_bytes, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PK_OK;
+}
+
+int pk_load_tables(pk_handle *h, const int32_t *tables, size_t m, const void *blob) {
+    if (!h || !blob) return h ? h->fail(PK_E_INVALID_ARG, "pk_load_tables: NULL blob") : PK_E_INVALID_ARG;
+    ON_DEVICE(h);
+    FLUSH(h);
+    if (m == 0) return PK_OK;
+    // the header first, from host memory: it says how many bytes the caller's blob holds
+    SnapHeader hd;
+    memcpy(&hd, blob, sizeof(hd));
+    if (hd.magic != SNAP_MAGIC || hd.version != SNAP_VERSION) return h->fail(PK_E_INVALID_ARG, "pk_load_tables: not a snapshot of this format (magic / version)");
+    if (hd.num_players != (uint32_t)h->N) return h->fail(PK_E_INVALID_ARG, "pk_load_tables: the blob holds tables of another number of seats");
+    if (hd.m != m) return h->fail(PK_E_INVALID_ARG, "pk_load_tables: m differs from the blob's record count");
+    if (m > (size_t)h->T) return h->fail(PK_E_INVALID_ARG, "pk_load_tables: more records than the handle has tables");
+    const size_t idx_bytes = tables ? snap_align(m * 4) : 0, bytes = pk_snapshot_bytes(h->N, m);
+    char *stage = nullptr;
+    int rc = snap_staging(h, idx_bytes + bytes, &stage);
+    if (rc) return rc;
+    if (tables) HIPCHK(h, hipMemcpyAsync(stage, tables, m * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(stage + idx_bytes, blob, bytes, hipMemcpyHostToDevice, h->stream));
+    if ((rc = snap_load(h, tables ? (const int32_t *)stage : nullptr, m, stage + idx_bytes, "pk_load_tables"))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PK_OK;
+}
+
+int pk_clone_tables_d(pk_handle *dst, const int32_t *dst_tables_d, pk_handle *src, const int32_t *src_tables_d, size_t m, int observer,
+                      uint64_t nonce) {
+    if (!dst || !src) {
+        if (dst) return dst->fail(PK_E_INVALID_ARG, "pk_clone_tables_d: NULL source handle");
+        g_err = "pk_clone_tables_d: NULL destination handle";
+        return PK_E_INVALID_ARG;
+    }
+    if (dst->device != src->device) return dst->fail(PK_E_INVALID_ARG, "pk_clone_tables_d: the handles are on different devices (save / load through a blob instead)");
+    if (dst->N != src->N) return dst->fail(PK_E_INVALID_ARG, "pk_clone_tables_d: the handles have different numbers of seats");
+    if (!snap_same_money(dst, snap_header_of(src, 0))) return dst->fail(PK_E_INVALID_ARG, "pk_clone_tables_d: the handles' start credits or blinds differ");
+    if (observer < PK_OBSERVER_ACTIVE || observer >= dst->N) return dst->fail(PK_E_INVALID_ARG, "pk_clone_tables_d: observer must be -2, -1 or a seat");
+    ON_DEVICE(dst);
+    if (src != dst) {
+        const int rc = flush(src);
+        if (rc) return dst->fail(rc, src->err.c_str());
+    }
+    FLUSH(dst);
+    if (m == 0) return PK_OK;
+    if (m > (size_t)dst->T) return dst->fail(PK_E_INVALID_ARG, "pk_clone_tables_d: more destinations than the handle has tables");
+    if (!src_tables_d && m > (size_t)src->T) return dst->fail(PK_E_INVALID_ARG, "pk_clone_tables_d: src_tables_d NULL and m > the source's tables");
+    int rc = snap_prepare(dst);
+    if (rc) return rc;
+    if (src != dst) {   // the clone reads what src's stream has queued so far
+        HIPCHK(dst, hipEventRecord(dst->snap_ev, src->stream));
+        HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->snap_ev, 0));
+    }
+    // Destinations: in range, none twice (marks).  Sources: in range; within one handle also whether one of them is a destination -- then
+    // the reads are staged through a blob first, so that the result is that of all reads before any write.
+    const bool marks = dst_tables_d || src == dst;   // (tables 0 .. m-1 of another handle need neither check)
+    HIPCHK(dst, hipMemsetAsync(dst->snap_word, 0, 4, dst->stream));
+    if (marks) {
+        HIPCHK(dst, hipMemsetAsync(dst->snap_mark, 0, (size_t)dst->T * 4, dst->stream));
+        HIPCHK(dst, snap_check_idx(dst->stream, dst_tables_d, m, dst->T, dst->snap_mark, 0, SNAP_BAD_DST_INDEX, dst->snap_word));
+    }
+    HIPCHK(dst, snap_check_idx(dst->stream, src_tables_d, m, src->T, src == dst ? dst->snap_mark : nullptr, 1, SNAP_BAD_SRC_INDEX, dst->snap_word));
+    uint32_t word = 0;
+    if ((rc = snap_verdict(dst, "pk_clone_tables_d", &word))) return rc;
+    const Redeal rd{observer, dst->S.key0, dst->S.key1, dst->S.table_id_base, nonce};
+    if (word & SNAP_OVERLAP) {
+        char *stage = nullptr;
+        if ((rc = snap_staging(dst, pk_snapshot_bytes(dst->N, m), &stage))) return rc;
+        SnapView blob;
+        SnapPads pads;
+        snap_layout(dst->N, m, stage, &blob, &pads);
+        HIPCHK(dst, snap_copy(dst->stream, SNAP_KIND_SAVE, snap_view_of_state(src->S), src_tables_d, blob, nullptr, dst->N, m, rd, snap_header_of(src, m), stage,
+                              pads));
+        HIPCHK(dst, snap_copy(dst->stream, SNAP_KIND_CLONE, blob, nullptr, snap_view_of_state(dst->S), dst_tables_d, dst->N, m, rd, SnapHeader{}, nullptr,
+                              SnapPads{}));
+    } else {
+        HIPCHK(dst, snap_copy(dst->stream, SNAP_KIND_CLONE, snap_view_of_state(src->S), src_tables_d, snap_view_of_state(dst->S), dst_tables_d, dst->N, m, rd,
+                              SnapHeader{}, nullptr, SnapPads{}));
+    }
+    if (src != dst) {   // src's later work waits for the clone's reads
+        HIPCHK(dst, hipEventRecord(dst->snap_ev, dst->stream));
+        HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->snap_ev, 0));
+    }
     return PK_OK;
 }
 

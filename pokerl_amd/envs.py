@@ -15,7 +15,9 @@ class VecPokerGameEnv:
         """`PokerGameEnv(agents, **game_config)` (game_env.py:13-18) for num_tables tables.  agents: the reference's list
         with one agent per OPPONENT seat (seat 1 first) -- in-kernel agents (pokerl_amd.agents.RandomAgent / AllInAgent /
         CallAgent or a Policy value) and / or host callables, see pokerl_amd/agents.py -- or, as a shorthand, ONE Policy
-        that every opponent plays."""
+        that every opponent plays.
+        The env has no snapshot API of its own: its tables are those of `self.game`, a VecGame, whose save / load / clone_tables /
+        copy.deepcopy / pickle work on them between env steps (not while steps are in flight)."""
         self.game = VecGame(num_tables, **game_config)  # game_env.py:16
         self.player_agent = 0                           # game_env.py:18
         self._pin, self._sent, self._in_flight = {}, None, False    # send() / recv(): pinned arrays, what send() asked for, a send awaits its recv

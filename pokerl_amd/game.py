@@ -14,6 +14,11 @@ from .enums import PokerMoves
 DEFAULT_SEED = 0x706F6B65726C  # 'pokerl'
 
 
+def snapshot_nbytes(num_players, m):
+    """Bytes of a snapshot blob of m table records at num_players seats (pk_snapshot_bytes); 0 for a seat count the ABI does not take."""
+    return int(L.lib().pk_snapshot_bytes(int(num_players), int(m)))
+
+
 class VecGame:
     """`Game(**config)` (pokerl/game.py:242-264) for `num_tables` tables.
 
@@ -263,6 +268,114 @@ class VecGame:
             return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.uint64), (self.num_tables,)))
         hs, ss = arr(hand_serial), arr(step_serial)
         L.check(self._lib.pk_set_serials(self._h, L.ptr(hs), L.ptr(ss)), self._h)
+
+    # ------------------------------------------------------------------ snapshots: save / load / clone tables (pokerl_hip.h "Snapshots")
+    # A snapshot is a position-independent byte blob of table records (snapshot_nbytes(N, m) bytes).  Future randomness belongs to the
+    # DESTINATION (its seed and table ids): a table restored into the same slot of a handle with the same seed and table_id_base continues
+    # bit-identically; a table cloned into another slot plays its current hand on identically, then deals the decks of its new table id.
+    def _config(self):
+        sc = self.start_credits
+        return dict(num_players=self.num_players, start_credits=sc if isinstance(sc, (int, float, np.integer, np.floating)) else list(np.asarray(sc, np.float64)),
+                    big_blind=self.big_blind, small_blind=self.small_blind, dealer=self.dealer, seed=self.seed, device=self.device,
+                    table_id_base=self.table_id_base)
+
+    def _tables(self, tables, what='tables'):
+        if tables is None:
+            return None
+        a = np.asarray(tables).reshape(-1)
+        if a.dtype.kind not in 'iu':
+            raise TypeError('%s must be integers' % what)
+        if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):   # a cast would wrap to another table
+            raise IndexError('%s: table index out of range' % what)
+        return np.ascontiguousarray(a, np.int32)
+
+    def save(self, tables=None):
+        """The records of `tables` (all tables if None, in order) as a uint8 blob (pk_save_tables)."""
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        blob = np.zeros(snapshot_nbytes(self.num_players, m), np.uint8)
+        L.check(self._lib.pk_save_tables(self._h, L.ptr(t), m, L.ptr(blob)), self._h)
+        return blob
+
+    def load(self, blob, tables=None):
+        """Restores the blob's records into `tables` (tables 0 .. m-1 if None); the records are checked on the device first and a blob
+        that fails is refused as a whole (pk_load_tables).  Deferred and in-flight bookkeeping of the restored tables is cleared."""
+        blob = np.ascontiguousarray(blob, np.uint8).reshape(-1)
+        if blob.nbytes < 256:
+            raise ValueError('not a snapshot blob (shorter than its header)')
+        m = int(blob[16:24].view(np.uint64)[0])              # header: magic, version, N, 0, m
+        t = self._tables(tables)
+        if t is not None:
+            m = len(t)
+        if blob.nbytes < snapshot_nbytes(self.num_players, m):
+            raise ValueError('blob too short for %d records of %d seats' % (m, self.num_players))
+        L.check(self._lib.pk_load_tables(self._h, L.ptr(t), m, L.ptr(blob)), self._h)
+
+    def save_d(self, blob_d, tables_d=None, m=None):
+        """pk_save_tables_d: m records (default: every table, or tables_d's length must be given as m) into the device buffer blob_d of
+        snapshot_nbytes(N, m) bytes; asynchronous on the handle's stream unless tables_d is given (its indices are checked first)."""
+        m = self.num_tables if m is None else int(m)
+        L.check(self._lib.pk_save_tables_d(self._h, self._dptr(tables_d), m, self._dptr(blob_d)), self._h)
+
+    def load_d(self, blob_d, tables_d=None, m=None):
+        """pk_load_tables_d: restores m records of the device blob blob_d (m defaults to every table)."""
+        m = self.num_tables if m is None else int(m)
+        L.check(self._lib.pk_load_tables_d(self._h, self._dptr(tables_d), m, self._dptr(blob_d)), self._h)
+
+    @staticmethod
+    def _observer(observer):
+        if observer is None:
+            return L.OBSERVER_NONE
+        if observer == 'active':
+            return L.OBSERVER_ACTIVE
+        return int(observer)
+
+    def clone_tables_d(self, dst_tables_d, src_tables_d, m, src=None, observer=None, nonce=0):
+        """pk_clone_tables_d on device index arrays (int32 [m], None = 0 .. m-1): table src_tables_d[i] of `src` (default: this game)
+        -> table dst_tables_d[i] of this game.  observer None: an exact copy; a seat or 'active' (= OBSERVER_ACTIVE): redeal the cards that
+        seat cannot see (see pokerl_hip.h), drawn from this game's seed, the destination table id and `nonce`."""
+        src = self if src is None else src
+        L.check(self._lib.pk_clone_tables_d(self._h, self._dptr(dst_tables_d), src._h, self._dptr(src_tables_d), int(m),
+                                            self._observer(observer), int(nonce) & 0xFFFFFFFFFFFFFFFF), self._h)
+
+    def clone_tables(self, dst_tables, src_tables, src=None, observer=None, nonce=0):
+        """clone_tables_d on host index arrays (src_tables broadcasts: [0] fans one table out to every destination); synchronous."""
+        from .hipmem import DeviceBuffer
+        src = self if src is None else src
+        d = self._tables(dst_tables, 'dst_tables')
+        m = self.num_tables if d is None else len(d)
+        s = self._tables(src_tables, 'src_tables')
+        if s is not None:
+            s = np.ascontiguousarray(np.broadcast_to(s, (m,)) if s.size == 1 else s, np.int32)
+            if len(s) != m:
+                raise ValueError('src_tables and dst_tables differ in length')
+        bufs = [None if a is None else DeviceBuffer(max(a.nbytes, 4), self.device).upload(a) for a in (d, s)]
+        try:
+            self.clone_tables_d(bufs[0], bufs[1], m, src=src, observer=observer, nonce=nonce)
+            self.sync()
+            if src is not self:
+                src.sync()
+        finally:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+
+    def __deepcopy__(self, memo):
+        """A new handle with the same configuration (seed and table ids included) holding a copy of every table: it continues
+        bit-identically to this game under the same actions, and stepping one leaves the other untouched.  Only the construction
+        config and the tables are copied (also by pickle): runtime settings of this handle -- its stream (set_stream), coalescing,
+        tuning, env sub-batches, set_step_obs / packed-observation buffers -- start at their defaults in the copy."""
+        g = VecGame(self.num_tables, **self._config())
+        g.load(self.save())
+        return g
+
+    def __getstate__(self):
+        return dict(num_tables=self.num_tables, config=self._config(), blob=self.save())
+
+    def __setstate__(self, state):
+        """Unpickling creates a handle on the pickled `device` and loads the tables."""
+        self.__init__(state['num_tables'], **state['config'])
+        self.load(state['blob'])
 
     # ------------------------------------------------------------------ state reads (Game attributes)
     def _f64(self, field):

@@ -4,6 +4,8 @@
 `num_tables = 1`: every value still comes from the HIP kernels, nothing is computed here.  (One table per launch is a
 latency-bound way to use a GPU: batch with VecGame when throughput matters.)
 """
+import copy
+
 import numpy as np
 
 from .enums import PlayerState
@@ -26,6 +28,15 @@ class Game:
 
     def close(self):
         self._v.close()
+
+    # ---- copy.deepcopy / pickle (a reference Game is a plain Python object: both work on it): through the table's snapshot
+    def __deepcopy__(self, memo):
+        """A standalone Game on a handle of its own, holding a copy of this table: it continues bit-identically under the same
+        actions (same seed and table id), and stepping it leaves this game untouched.  Also for `env.game`."""
+        return _game_of(copy.deepcopy(self._v, memo))
+
+    def __reduce__(self):
+        return (_game_of, (self._v,))
 
     # ---- attributes of game.py:251-264 (read fresh from the device on every access)
     credits = property(lambda self: self._v.credits[0])
@@ -87,6 +98,17 @@ class Game:
             raise NotImplementedError                                             # :646, :700
         over, hand, turn = self._v.step(np.array([action], np.int64))
         return bool(over[0]), bool(hand[0]), bool(turn[0])
+
+
+def _game_of(vec_game):
+    """A Game over an existing one-table VecGame (copy.deepcopy and unpickling)."""
+    g = Game.__new__(Game)
+    g.logger = None
+    g._v = vec_game
+    g.num_players = vec_game.num_players
+    g.start_credits = vec_game.start_credits
+    g.big_blind, g.small_blind = vec_game.big_blind, vec_game.small_blind
+    return g
 
 
 class PokerGameEnv:

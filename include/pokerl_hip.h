@@ -227,8 +227,8 @@ int pk_time_eval7_d(int device, const uint64_t *hands_d, size_t m, uint32_t *out
  * canonical deck indices (pokerl/cards.py:77 order) are (a, b), in lexicographic order; out holds C(51-b, 5) words.
  * fast == 1: the 7-distinct-card evaluator the showdown kernels use; fast == 0: the general one behind pk_eval_hands;
  * fast == 2: the table-driven 7-distinct-card evaluator of pk_eval7_d (cards of hand i rotated by i inside the packed word);
- * fast == 3: the register evaluator that backed pk_eval_hands(_d) up to ABI 4 and still does under PK_EVAL_HANDS_TAB=0 (a bitmask fast path
- * for 3..7 distinct cards, the reference's scan for hands that repeat a card or hold fewer than three);
+ * fast == 3: the register evaluator that backed pk_eval_hands(_d) up to ABI 4 and still does when the evaluator table cannot be allocated
+ * (a bitmask fast path for 3..7 distinct cards, the reference's scan for hands that repeat a card or hold fewer than three);
  * fast == 4: the table path pk_eval_hands(_d) takes (eval_tab_n, cards rotated as for fast == 2). */
 int pk_eval7_prefix(int device, int a, int b, int fast, uint32_t *out, size_t *count_out);
 

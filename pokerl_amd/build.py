@@ -14,7 +14,7 @@ HEADERS = [os.path.join(CSRC, "pk_device.hpp"), os.path.join(CSRC, "pk_kernels.h
 #   scheduler should chase ILP, not occupancy: +10 % on k_rollout<6> (19.6 -> 21.6 G env-steps/s).
 # -fno-honor-nans: money is never NaN, so `x > m ? x : m` may become v_max_f64 (-4 % VALU); signed zeros stay honoured.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-ffp-contract=off", "-fno-fast-math", "-fno-honor-nans", "-mllvm", "-amdgpu-sched-strategy=max-ilp", "-fPIC", "-shared",
-         "-fgpu-rdc=0" if False else "-Wall", "-Wno-unused-function"]
+         "-Wall", "-Wno-unused-function"]
 
 
 SEATS = list(range(2, 17))   # one object per seat count (pk_tables.hip -DPK_SEATS=N), PK_MIN_PLAYERS .. PK_MAX_PLAYERS

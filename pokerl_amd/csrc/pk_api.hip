@@ -2,12 +2,14 @@
 // no torch types.  Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC (see pokerl_amd/build.py).
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "pk_device.hpp"
@@ -18,9 +20,22 @@ using namespace pk;
 
 // ================================================================================================ host side
 static thread_local std::string g_err;
+// The error of a call without a handle (pk_last_error(NULL)): `what`, and the HIP error if there is one.
+static int g_fail(int code, const char *what, hipError_t e = hipSuccess) {
+    g_err = what;
+    if (e != hipSuccess) { g_err += ": "; g_err += hipGetErrorString(e); }
+    return code;
+}
+// An integer knob from the environment: its value if it is set and lies in [lo, hi], otherwise `fallback`.
+static int env_int(const char *name, int lo, int hi, int fallback) {
+    const char *s = getenv(name);
+    if (!s) return fallback;
+    const int v = atoi(s);
+    return v >= lo && v <= hi ? v : fallback;
+}
 
 struct pk_handle {
-    int device = 0, T = 0, N = 0, block = 64, dealer = 0;
+    int device = 0, T = 0, N = 0, dealer = 0;
     int tpb = 64;   // tables per wavefront (Hot::tpb)
     int env_tpb = 64;  // ... of the PokerGameEnv kernels (hot_env): see pk_create; knob PK_ENV_TPB
     Hot hot_env{};
@@ -94,9 +109,8 @@ struct pk_handle {
     hipEvent_t snap_ev = nullptr;
     std::string err;
     int fail(int code, const char *what, hipError_t e = hipSuccess) {
-        err = what;
-        if (e != hipSuccess) { err += ": "; err += hipGetErrorString(e); }
-        g_err = err;
+        g_fail(code, what, e);
+        err = g_err;
         return code;
     }
 };
@@ -132,74 +146,40 @@ struct DeviceGuard {
 #endif
 #define PK_FOR_SEATS_LE10(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10)
 #define PK_FOR_SEATS_GT10(X) X(11) X(12) X(13) X(14) X(15) X(16)
+#define PK_FOR_SEATS_LE6(X) X(2) X(3) X(4) X(5) X(6)
 static_assert(PK_MIN_PLAYERS == 2 && PK_MAX_PLAYERS == 16, "the lists above name the seat counts");
 #define PK_DECLARE_ALL(N) PK_TABLE_KERNELS(PK_DECLARE_KERNEL, N)
 #define PK_DECLARE_ALL_LE10(N) PK_TABLE_KERNELS_LE10(PK_DECLARE_KERNEL, N)
 #define PK_DECLARE_ALL_LE6(N) PK_TABLE_KERNELS_LE6(PK_DECLARE_KERNEL, N)
-#define PK_FOR_SEATS_LE6(X) X(2) X(3) X(4) X(5) X(6)
 PK_FOR_SEATS_LE10(PK_DECLARE_ALL)
 PK_FOR_SEATS_GT10(PK_DECLARE_ALL)
 PK_FOR_SEATS_LE10(PK_DECLARE_ALL_LE10)
 PK_FOR_SEATS_LE6(PK_DECLARE_ALL_LE6)
-static inline bool seat_count_built(int n) {
-#define PK_SEAT_CASE(N) if (n == N) return PK_SEAT_ENABLED(N);
-    PK_FOR_SEATS_LE10(PK_SEAT_CASE)
-    PK_FOR_SEATS_GT10(PK_SEAT_CASE)
-#undef PK_SEAT_CASE
-    return false;
-}
-#define DISPATCH_N_ON(h, strm, KERNEL, grid, ...) \
-    do { \
-        dim3 g_((grid)), b_((h)->block); \
-        hipStream_t strm_ = (strm); \
-        switch ((h)->N) { \
-            case 2: if constexpr (PK_SEAT_ENABLED(2)) hipLaunchKernelGGL(KERNEL<2>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 3: if constexpr (PK_SEAT_ENABLED(3)) hipLaunchKernelGGL(KERNEL<3>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 4: if constexpr (PK_SEAT_ENABLED(4)) hipLaunchKernelGGL(KERNEL<4>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 5: if constexpr (PK_SEAT_ENABLED(5)) hipLaunchKernelGGL(KERNEL<5>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 6: if constexpr (PK_SEAT_ENABLED(6)) hipLaunchKernelGGL(KERNEL<6>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 7: if constexpr (PK_SEAT_ENABLED(7)) hipLaunchKernelGGL(KERNEL<7>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 8: if constexpr (PK_SEAT_ENABLED(8)) hipLaunchKernelGGL(KERNEL<8>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 9: if constexpr (PK_SEAT_ENABLED(9)) hipLaunchKernelGGL(KERNEL<9>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 10: if constexpr (PK_SEAT_ENABLED(10)) hipLaunchKernelGGL(KERNEL<10>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 11: if constexpr (PK_SEAT_ENABLED(11)) hipLaunchKernelGGL(KERNEL<11>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 12: if constexpr (PK_SEAT_ENABLED(12)) hipLaunchKernelGGL(KERNEL<12>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 13: if constexpr (PK_SEAT_ENABLED(13)) hipLaunchKernelGGL(KERNEL<13>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 14: if constexpr (PK_SEAT_ENABLED(14)) hipLaunchKernelGGL(KERNEL<14>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 15: if constexpr (PK_SEAT_ENABLED(15)) hipLaunchKernelGGL(KERNEL<15>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-            case 16: if constexpr (PK_SEAT_ENABLED(16)) hipLaunchKernelGGL(KERNEL<16>, g_, b_, 0, strm_, __VA_ARGS__); break; \
-        } \
-    } while (0)
-#define DISPATCH_N(h, KERNEL, grid, ...) DISPATCH_N_ON(h, (h)->stream, KERNEL, grid, __VA_ARGS__)
-// ... for the kernels that exist for up to ten seats only (the 168-register variants: beyond ten seats they would spill)
-#define DISPATCH_N_LE10(h, KERNEL, grid, ...) \
-    do { \
-        dim3 g_((grid)), b_((h)->block); \
-        switch ((h)->N) { \
-            case 2: if constexpr (PK_SEAT_ENABLED(2)) hipLaunchKernelGGL(KERNEL<2>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 3: if constexpr (PK_SEAT_ENABLED(3)) hipLaunchKernelGGL(KERNEL<3>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 4: if constexpr (PK_SEAT_ENABLED(4)) hipLaunchKernelGGL(KERNEL<4>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 5: if constexpr (PK_SEAT_ENABLED(5)) hipLaunchKernelGGL(KERNEL<5>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 6: if constexpr (PK_SEAT_ENABLED(6)) hipLaunchKernelGGL(KERNEL<6>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 7: if constexpr (PK_SEAT_ENABLED(7)) hipLaunchKernelGGL(KERNEL<7>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 8: if constexpr (PK_SEAT_ENABLED(8)) hipLaunchKernelGGL(KERNEL<8>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 9: if constexpr (PK_SEAT_ENABLED(9)) hipLaunchKernelGGL(KERNEL<9>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 10: if constexpr (PK_SEAT_ENABLED(10)) hipLaunchKernelGGL(KERNEL<10>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-        } \
-    } while (0)
 
-// ... and up to six (k_rollout_tab)
-#define DISPATCH_N_LE6(h, KERNEL, grid, ...) \
-    do { \
-        dim3 g_((grid)), b_((h)->block); \
-        switch ((h)->N) { \
-            case 2: if constexpr (PK_SEAT_ENABLED(2)) hipLaunchKernelGGL(KERNEL<2>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 3: if constexpr (PK_SEAT_ENABLED(3)) hipLaunchKernelGGL(KERNEL<3>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 4: if constexpr (PK_SEAT_ENABLED(4)) hipLaunchKernelGGL(KERNEL<4>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 5: if constexpr (PK_SEAT_ENABLED(5)) hipLaunchKernelGGL(KERNEL<5>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-            case 6: if constexpr (PK_SEAT_ENABLED(6)) hipLaunchKernelGGL(KERNEL<6>, g_, b_, 0, (h)->stream, __VA_ARGS__); break; \
-        } \
-    } while (0)
+// The seat-count dispatch: calls launch(std::integral_constant<int, N>{}) for N == n if this build holds seat count n and n <= MAX
+// (16; 10 for the 168-register kernels, which would spill beyond ten seats; 6 for k_rollout_tab).  false: no kernel, nothing launched.
+// Only the seat counts the walk reaches are named, so a kernel that does not exist for a seat count is never referenced.
+template <int MAX = PK_MAX_PLAYERS, int N = PK_MIN_PLAYERS, typename F>
+static bool seat_dispatch(int n, F &&launch) {
+    if constexpr (N > MAX) {
+        return false;
+    } else {
+        if constexpr (PK_SEAT_ENABLED(N)) {
+            if (n == N) { launch(std::integral_constant<int, N>{}); return true; }
+        }
+        return seat_dispatch<MAX, N + 1>(n, launch);
+    }
+}
+// The launch of KERNEL<N> that seat_dispatch calls: one wavefront per workgroup
+#define SEAT_KERNEL(KERNEL, grid, stream, ...) \
+    [&](auto n_) { hipLaunchKernelGGL(KERNEL<decltype(n_)::value>, dim3(grid), dim3(PK_TABLE_BLOCK), 0, (stream), __VA_ARGS__); }
+// ... for the handle's seat count, checked
+template <int MAX = PK_MAX_PLAYERS, typename F>
+static int seat_launch(pk_handle *h, F &&launch) {
+    if (!seat_dispatch<MAX>(h->N, launch)) return h->fail(PK_E_INVALID_ARG, "no kernel for this seat count in this build of the library");
+    HIPCHK(h, hipGetLastError());
+    return PK_OK;
+}
 
 #define PK_STR_(x) #x
 #define PK_STR(x) PK_STR_(x)
@@ -224,23 +204,25 @@ static inline int obs_grid(int T) { return (T + OBS_BLOCK - 1) / OBS_BLOCK; }
 // wave have work left (endk == 1: runs to completion).
 static int launch_rollout(pk_handle *h, int k_steps, int policy, int auto_reset, int endk) {
     const int slack = endk <= 1 ? PK_WAVE : ((PK_WAVE - endk) * h->tpb) / PK_WAVE;   // lanes allowed to idle before a launch ends
-#define ROLLOUT_ARGS (const State *)h->d_S, h->hot, k_steps, auto_reset, scaled_park(h, policy == PK_POLICY_RANDOM ? 28 : 32), slack, h->pending ? 0 : 1
-    if (policy == PK_POLICY_RANDOM && k_steps == 1 && endk <= 1 && !h->occ3) DISPATCH_N(h, k_rollout_single, table_grid(h), ROLLOUT_ARGS);
-    else if (policy == PK_POLICY_CALL) DISPATCH_N(h, k_rollout_call, table_grid(h), ROLLOUT_ARGS);
+    const int park = scaled_park(h, policy == PK_POLICY_RANDOM ? 28 : 32), clear_terr = h->pending ? 0 : 1;
+#define ROLLOUT(KERNEL) SEAT_KERNEL(KERNEL, table_grid(h), h->stream, (const State *)h->d_S, h->hot, k_steps, auto_reset, park, slack, clear_terr)
+    int rc;
+    if (policy == PK_POLICY_RANDOM && k_steps == 1 && endk <= 1 && !h->occ3) rc = seat_launch(h, ROLLOUT(k_rollout_single));
+    else if (policy == PK_POLICY_CALL) rc = seat_launch(h, ROLLOUT(k_rollout_call));
     else if (!h->occ3) {
         // k_rollout_tab: the showdown hands ranked by the table-driven evaluator -- where its 40 KB of LDS per wave cost no occupancy (at most one
         // wave per SIMD: 1 024 workgroups) and the launch is long enough to pay for staging the table (~1.5 us); knob PK_ROLLOUT_TAB (min steps, 0 = off)
         const bool tab_ok = h->S.evtab && h->tab_min_steps > 0 && k_steps >= h->tab_min_steps && table_grid(h) <= 1024;
-        if (policy == PK_POLICY_RANDOM && h->N <= 6 && tab_ok) DISPATCH_N_LE6(h, k_rollout_tab, table_grid(h), ROLLOUT_ARGS);
-        else if (policy == PK_POLICY_ALLIN && h->N <= 10 && tab_ok) DISPATCH_N_LE10(h, k_rollout_allin_tab, table_grid(h), ROLLOUT_ARGS);   // (no action ring in LDS: up to ten seats)
-        else if (policy == PK_POLICY_RANDOM) DISPATCH_N(h, k_rollout, table_grid(h), ROLLOUT_ARGS);
-        else DISPATCH_N(h, k_rollout_allin, table_grid(h), ROLLOUT_ARGS);
+        if (policy == PK_POLICY_RANDOM && h->N <= 6 && tab_ok) rc = seat_launch<6>(h, ROLLOUT(k_rollout_tab));
+        else if (policy == PK_POLICY_ALLIN && h->N <= 10 && tab_ok) rc = seat_launch<10>(h, ROLLOUT(k_rollout_allin_tab));   // (no action ring in LDS: up to ten seats)
+        else if (policy == PK_POLICY_RANDOM) rc = seat_launch(h, ROLLOUT(k_rollout));
+        else rc = seat_launch(h, ROLLOUT(k_rollout_allin));
     } else {
-        if (policy == PK_POLICY_RANDOM) DISPATCH_N_LE10(h, k_rollout_occ3, table_grid(h), ROLLOUT_ARGS);
-        else DISPATCH_N_LE10(h, k_rollout_occ3_allin, table_grid(h), ROLLOUT_ARGS);
+        if (policy == PK_POLICY_RANDOM) rc = seat_launch<10>(h, ROLLOUT(k_rollout_occ3));
+        else rc = seat_launch<10>(h, ROLLOUT(k_rollout_occ3_allin));
     }
-#undef ROLLOUT_ARGS
-    HIPCHK(h, hipGetLastError());
+#undef ROLLOUT
+    if (rc) return rc;
     h->pending = slack < PK_WAVE;
     h->pend_policy = policy; h->pend_auto = auto_reset;
     h->st_launches += 1; h->st_steps += (uint64_t)k_steps;
@@ -319,26 +301,36 @@ static std::vector<hipStream_t> g_stream_pool[PK_MAX_DEVICES][2];   // [device][
 // (one hipMemcpy or one torch kernel brings it to life) and whatever else the process has created -- with normal-priority streams a
 // process that had merely made one hipMemcpy before creating the handle ran 524 288 x 6 in three sub-batches at 2.57 G env.step/s
 // against 3.66 G (tools/env_queue_scenarios.py).  env PK_ENV_STREAM_PRIO=0: off.
-// How the pool notices a device reset WITHOUT touching a pooled (then dangling) stream handle: a small device allocation made when the first stream
-// of a device is pooled.  hipMemGetAddressRange looks an ADDRESS up in the runtime's allocation map -- no dereference of a dead object -- and
-// after a reset the canary is gone from it (or, should the application have re-allocated that very address in the meantime, would have to
-// come back with the same odd size: not impossible, so pk_stream_pool_drain before hipDeviceReset remains the rule; this is the seat belt).
-static void *g_pool_canary[PK_MAX_DEVICES];
-static const size_t POOL_CANARY_BYTES = 4096 + 272;
-static bool pool_alive(int device) {   // caller holds g_stream_mu and has the device current
-    void *c = g_pool_canary[device];
-    if (!c) return false;
+static int pool_class(bool sub_batch) {
+    static const bool prio = env_int("PK_ENV_STREAM_PRIO", INT_MIN, INT_MAX, 1) != 0;
+    return (sub_batch && prio) ? 1 : 0;
+}
+// A per-device cache of device memory (the stream pool's canary, the judger's scratch arena, the evaluator table) outlives its allocation when the
+// application resets the device: a kernel launched on such a pointer would fault, a pooled stream handle dangles.  The seat belt: look the ADDRESS
+// up before trusting it -- hipMemGetAddressRange looks it up in the runtime's allocation map, no dereference of a dead object.  The allocator hands
+// the same addresses out again after a reset (measured: the evaluator table's address came back as the next handle's arena), so base AND size must
+// match -- and every cached allocation has an odd size (PK_ODD_BYTES more than it needs) that no caller is likely to ask for.  Not impossible, so
+// pk_stream_pool_drain before hipDeviceReset remains the rule.
+#define PK_ODD_BYTES 272
+static bool dev_alloc_alive(const void *p, size_t bytes) {
+    if (!p) return false;
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
-    const hipError_t e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)c);
+    const hipError_t e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
     if (e != hipSuccess) (void)hipGetLastError();
-    const bool ok = e == hipSuccess && (void *)base == c && size == POOL_CANARY_BYTES;
+    return e == hipSuccess && (const void *)base == p && size == bytes;
+}
+// How the pool notices a device reset WITHOUT touching a pooled (then dangling) stream handle: a small device allocation made when the first stream
+// of a device is pooled.
+static void *g_pool_canary[PK_MAX_DEVICES];
+static const size_t POOL_CANARY_BYTES = 4096 + PK_ODD_BYTES;
+static bool pool_alive(int device) {   // caller holds g_stream_mu and has the device current
+    const bool ok = dev_alloc_alive(g_pool_canary[device], POOL_CANARY_BYTES);
     if (!ok) g_pool_canary[device] = nullptr;          // (not freed: it no longer exists)
     return ok;
 }
 static hipError_t stream_acquire(int device, hipStream_t *out, bool sub_batch = false) {   // the device is current
-    static const bool prio = !(getenv("PK_ENV_STREAM_PRIO") && atoi(getenv("PK_ENV_STREAM_PRIO")) == 0);
-    const int cls = (sub_batch && prio) ? 1 : 0;
+    const int cls = pool_class(sub_batch);
     if (device >= 0 && device < PK_MAX_DEVICES) {
         std::lock_guard<std::mutex> lock(g_stream_mu);
         auto &pool = g_stream_pool[device][cls];
@@ -364,14 +356,13 @@ static void stream_release(int device, hipStream_t s, bool sub_batch = false) { 
         (void)hipGetLastError(); (void)hipStreamDestroy(s); (void)hipGetLastError();
         return;
     }
-    static const bool prio = !(getenv("PK_ENV_STREAM_PRIO") && atoi(getenv("PK_ENV_STREAM_PRIO")) == 0);
     if (device >= 0 && device < PK_MAX_DEVICES) {
         std::lock_guard<std::mutex> lock(g_stream_mu);
         if (!g_pool_canary[device]) {                  // the pool's reset detector (pool_alive); without one the stream is not pooled
             for (int c = 0; c < 2; ++c) g_stream_pool[device][c].clear();    // (whatever was pooled under an earlier, vanished canary is stale)
             if (hipMalloc(&g_pool_canary[device], POOL_CANARY_BYTES) != hipSuccess) { (void)hipGetLastError(); g_pool_canary[device] = nullptr; (void)hipStreamDestroy(s); return; }
         }
-        g_stream_pool[device][(sub_batch && prio) ? 1 : 0].push_back(s);
+        g_stream_pool[device][pool_class(sub_batch)].push_back(s);
     } else (void)hipStreamDestroy(s);
 }
 
@@ -401,12 +392,21 @@ static int drain_stream_pool(int device) {
     return n;
 }
 
-static int check_device_any() {
+// Is there a HIP device at all (PK_E_NO_DEVICE), and is `device` one of them and below `limit` (PK_E_INVALID_ARG)?  Device 0: any device.
+static int check_device(const char *call, int device, int limit = INT_MAX) {
     int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) { g_err = "no HIP device available; this library has no CPU fallback"; return PK_E_NO_DEVICE; }
+    const hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+        return g_fail(PK_E_NO_DEVICE, (std::string(call) + ": no HIP device available (" + (e != hipSuccess ? hipGetErrorString(e) : "0 devices") +
+                                       "); this library has no CPU fallback").c_str());
+    if (device < 0 || device >= ndev || device >= limit) return g_fail(PK_E_INVALID_ARG, (std::string(call) + ": device index out of range").c_str());
     return PK_OK;
 }
+// ON_DEVICE of the calls without a handle: the device check, then `device` current until the call returns
+#define ON_DEVICE_INDEX(call, device, limit)                                     \
+    if (int rc_ = check_device(call, device, limit)) return rc_;                 \
+    DeviceGuard guard_(device);                                                  \
+    if (!guard_.ok) return g_fail(PK_E_HIP, call ": hipSetDevice failed")
 
 // The argument block of the PokerGameEnv.step kernels (pk_kernels.hpp EnvKernArgs): common fields; callers set the rest.
 static EnvKernArgs env_args(const pk_handle *h, const int32_t *actions_d, int seat0_policy, uint64_t seatpol, int auto_reset,
@@ -455,7 +455,7 @@ int pk_create(pk_handle **out, int device, int num_tables, int num_players, cons
                 "rule the reference pins: DESIGN.md section 8, docs/history.md section 9)";
         return PK_E_INVALID_ARG;
     }
-    if (!seat_count_built(num_players)) { g_err = "pk_create: this development build of the library holds one seat count only (PK_ONLY_SEATS)"; return PK_E_INVALID_ARG; }
+    if (!seat_dispatch(num_players, [](auto) {})) { g_err = "pk_create: this development build of the library holds one seat count only (PK_ONLY_SEATS)"; return PK_E_INVALID_ARG; }
     {   // Money must be finite: the library is built with -fno-honor-nans (v_max_f64 / v_min_f64 for np.max / np.minimum), and an
         // infinite stack turns into NaN at the first all-in (inf - inf), where numpy and the device would disagree silently.
         bool finite = std::isfinite(big_blind) && std::isfinite(small_blind);
@@ -463,41 +463,32 @@ int pk_create(pk_handle **out, int device, int num_tables, int num_players, cons
         else finite = finite && std::isfinite(start_credit_scalar);
         if (!finite) { g_err = "pk_create: start_credits, big_blind and small_blind must be finite (no inf / NaN)"; return PK_E_INVALID_ARG; }
     }
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        g_err = std::string("pk_create: no HIP device available (") + (e != hipSuccess ? hipGetErrorString(e) : "0 devices") +
-                "); this library has no CPU fallback";
-        return PK_E_NO_DEVICE;
-    }
-    if (device < 0 || device >= ndev) { g_err = "pk_create: device index out of range"; return PK_E_INVALID_ARG; }
+    if (int rc = check_device("pk_create", device)) return rc;
     pk_handle *h = new pk_handle();
     h->device = device; h->T = num_tables; h->N = num_players; h->dealer = dealer;
-    h->block = PK_TABLE_BLOCK;
     {   // small batches: spread the tables over all 1 024 SIMDs of the chip (power of two, 1..64 tables per wave)
         int tpb = 64;
         while (tpb > 1 && (long)num_tables <= 1024L * (tpb / 2)) tpb /= 2;
-        if (const char *pk = getenv("PK_TPB")) { int v = atoi(pk); if (v >= 1 && v <= 64) tpb = v; }
-        h->tpb = tpb;
+        h->tpb = env_int("PK_TPB", 1, 64, tpb);
         // k_rollout_occ3 (registers capped at 168: three waves per SIMD) only where it was measured to pay: six seats
         // (k_rollout<6> needs 171 registers -- profiles/r04_resource_usage.txt --, the capped build 162 without a spill) as soon as a SIMD gets a
         // third wave, i.e. beyond 131 072 tables; seven seats from 262 144 tables (+6..10 %), eight from 524 288 (+5..7 %).
         // Up to five seats k_rollout fits 168 registers by itself; at nine and ten seats the cap spills to scratch and
         // loses 10..35 % at every batch size.
-        h->occ3 = (num_players == 6 && num_tables > 131072) || (num_players == 7 && num_tables >= 262144) ||
-                  (num_players == 8 && num_tables >= 524288);
-        if (const char *pk = getenv("PK_OCC3")) h->occ3 = atoi(pk) != 0 && num_players <= 10;
+        const bool occ3 = (num_players == 6 && num_tables > 131072) || (num_players == 7 && num_tables >= 262144) ||
+                          (num_players == 8 && num_tables >= 524288);
+        h->occ3 = env_int("PK_OCC3", INT_MIN, INT_MAX, occ3) != 0 && num_players <= 10;
     }
     {   // The env kernels are bound by the tail of the slowest table of a wave (a busted seat 0 waits for the end of the game),
         // not by issue slots: half-populated waves halve that tail and bring a second wave to each SIMD
-        // (profiles/r03_env_tpb_sweep.txt)
-        h->env_tpb = h->tpb;
-        if (const char *pk = getenv("PK_ENV_TPB")) { int v = atoi(pk); if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) h->env_tpb = v; }
+        // (profiles/r03_env_tpb_sweep.txt); knob PK_ENV_TPB: a power of two
+        const int v = env_int("PK_ENV_TPB", 1, 64, h->tpb);
+        h->env_tpb = (v & (v - 1)) == 0 ? v : h->tpb;
     }
-    if (const char *pk = getenv("PK_ROLLOUT_TAB")) { int v = atoi(pk); if (v >= 0) h->tab_min_steps = v; }
-    if (const char *pk = getenv("PK_PARK")) { int v = atoi(pk); if (v >= 1 && v <= 64) h->park = v; }
-    if (const char *pk = getenv("PK_ENDK")) { int v = atoi(pk); if (v >= 1 && v <= 64) h->endk = v; }
-    if (const char *pk = getenv("PK_COALESCE")) { int v = atoi(pk); if (v >= 0 && v <= (1 << 20)) h->coalesce = v; }
+    h->tab_min_steps = env_int("PK_ROLLOUT_TAB", 0, INT_MAX, h->tab_min_steps);
+    h->park = env_int("PK_PARK", 1, 64, h->park);
+    h->endk = env_int("PK_ENDK", 1, 64, h->endk);
+    h->coalesce = env_int("PK_COALESCE", 0, 1 << 20, h->coalesce);
     auto bail = [&](int code) { g_err = h->err; pk_destroy(h); return code; };
     DeviceGuard guard(device);
     if (!guard.ok) return bail(h->fail(PK_E_HIP, "hipSetDevice"));
@@ -550,7 +541,7 @@ int pk_create(pk_handle **out, int device, int num_tables, int num_players, cons
         return off;
     };
     const size_t total = layout(nullptr);
-    e = hipMalloc(&h->arena, total);
+    const hipError_t e = hipMalloc(&h->arena, total);
     if (e != hipSuccess) return bail(h->fail(PK_E_OOM, "hipMalloc(table state)", e));
     if (hipMemsetAsync(h->arena, 0, total, h->stream) != hipSuccess) return bail(h->fail(PK_E_HIP, "hipMemset"));
     if (layout((char *)h->arena) != total) return bail(h->fail(PK_E_HIP, "arena layout changed between its two passes"));
@@ -587,8 +578,7 @@ int pk_create(pk_handle **out, int device, int num_tables, int num_players, cons
             hipMemcpyAsync(S.valid, valid.data(), T, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess)
             return bail(h->fail(PK_E_HIP, "initial state upload"));
-        DISPATCH_N(h, k_make_fresh, 1, h->hot, d_fresh);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+        if (seat_launch(h, SEAT_KERNEL(k_make_fresh, 1, h->stream, h->hot, d_fresh)) || hipStreamSynchronize(h->stream) != hipSuccess)
             return bail(h->fail(PK_E_HIP, "k_make_fresh"));
     }
     *out = h;
@@ -699,8 +689,7 @@ int pk_reset(pk_handle *h, const uint8_t *mask, int dealer) {
     int rc = upload_mask(h, mask, &dmask);
     if (rc) return rc;
     int d = ((dealer % h->N) + h->N) % h->N;
-    DISPATCH_N(h, k_reset, table_grid(h), h->S, h->hot, dmask, 0xff, d);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = seat_launch(h, SEAT_KERNEL(k_reset, table_grid(h), h->stream, h->S, h->hot, dmask, 0xff, d)))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return PK_OK;
 }
@@ -711,18 +700,14 @@ int pk_reset_d(pk_handle *h, const uint8_t *mask_d, int mask_bits, int dealer) {
     ON_DEVICE(h);
     FLUSH(h);
     int d = ((dealer % h->N) + h->N) % h->N;
-    DISPATCH_N(h, k_reset, table_grid(h), h->S, h->hot, mask_d, mask_bits & 0xff, d);
-    HIPCHK(h, hipGetLastError());
-    return PK_OK;
+    return seat_launch(h, SEAT_KERNEL(k_reset, table_grid(h), h->stream, h->S, h->hot, mask_d, mask_bits & 0xff, d));
 }
 
 static int launch_step(pk_handle *h, const int32_t *actions_d, uint8_t *flags_d, uint8_t *terr_d, int auto_reset) {
     ON_DEVICE(h);
     FLUSH(h);
     const StepKernArgs ka{(const State *)h->d_S, h->hot, actions_d, flags_d, terr_d, scaled_park(h, 28), auto_reset ? 1 : 0, nullptr, 0, h->step_obs, h->step_obs_packed};
-    DISPATCH_N(h, k_step, table_grid(h), ka);
-    HIPCHK(h, hipGetLastError());
-    return PK_OK;
+    return seat_launch(h, SEAT_KERNEL(k_step, table_grid(h), h->stream, ka));
 }
 int pk_step_d(pk_handle *h, const int32_t *actions_d, uint8_t *flags_d, uint8_t *terr_d) {
     if (!h || !actions_d || !flags_d) return h ? h->fail(PK_E_INVALID_ARG, "pk_step_d: NULL buffer") : PK_E_INVALID_ARG;
@@ -743,8 +728,7 @@ int pk_step_async_d(pk_handle *h, const int32_t *actions_d, uint8_t *flags_d, ui
     } else FLUSH(h);
     const StepKernArgs ka{(const State *)h->d_S, h->hot, actions_d, flags_d, terr_d, scaled_park(h, 28), auto_reset ? 1 : 0, ready_d, max_hands > 0 ? max_hands : 0,
                           h->step_obs, h->step_obs_packed};
-    DISPATCH_N(h, k_step_async, table_grid(h), ka);
-    HIPCHK(h, hipGetLastError());
+    if (int rc = seat_launch(h, SEAT_KERNEL(k_step_async, table_grid(h), h->stream, ka))) return rc;
     h->step_pending = max_hands > 0;
     h->step_auto = auto_reset ? 1 : 0;
     return PK_OK;
@@ -773,30 +757,36 @@ int pk_step(pk_handle *h, const int32_t *actions, uint8_t *flags, uint8_t *terr)
 
 static int bad_player(const pk_handle *h, int player) { return player >= h->N; }
 
+// The launches of the getters that have a host form (export_to_host into h->d_export) and a device form (FLUSH_READER, the caller's buffer)
+static void launch_valid_actions(pk_handle *h, int player, uint8_t *out) {
+    hipLaunchKernelGGL(k_export_valid, dim3(flat_grid((size_t)h->T * PK_NUM_MOVES)), dim3(256), 0, h->stream, h->S, h->N, player, out);
+}
+static void launch_f64(pk_handle *h, int field, double *out) {
+    const double *src = field == PK_F_CREDITS ? h->S.credits : field == PK_F_BETS ? h->S.bets : field == PK_F_PENDING_BETS ? h->S.pending : h->S.payoffs;
+    hipLaunchKernelGGL(k_export_f64, dim3(flat_grid((size_t)h->T * h->N)), dim3(256), 0, h->stream, src, h->T, h->N, out);
+}
+static void launch_obs(pk_handle *h, int player, double *out) {
+    hipLaunchKernelGGL(k_obs, dim3(obs_grid(h->T)), dim3(OBS_BLOCK), 0, h->stream, h->S, h->N, player, out);
+}
+static void launch_obs_packed(pk_handle *h, int player, uint8_t *out) {
+    hipLaunchKernelGGL(k_obs_packed, dim3(obs_grid(h->T)), dim3(OBS_BLOCK), 0, h->stream, h->S, h->N, player, out);
+}
+
 int pk_get_valid_actions(pk_handle *h, int player, uint8_t *out) {
     if (!h || !out || bad_player(h, player)) return h ? h->fail(PK_E_INVALID_ARG, "pk_get_valid_actions: bad argument") : PK_E_INVALID_ARG;
-    size_t n = (size_t)h->T * PK_NUM_MOVES;
-    return export_to_host(h, out, n, [&] {
-        hipLaunchKernelGGL(k_export_valid, dim3(flat_grid(n)), dim3(256), 0, h->stream, h->S, h->N, player, (uint8_t *)h->d_export);
-    });
+    return export_to_host(h, out, (size_t)h->T * PK_NUM_MOVES, [&] { launch_valid_actions(h, player, (uint8_t *)h->d_export); });
 }
 
 int pk_get_f64(pk_handle *h, int field, double *out) {
     if (!h || !out || field < 0 || field > 3) return h ? h->fail(PK_E_INVALID_ARG, "pk_get_f64: bad field") : PK_E_INVALID_ARG;
-    const double *src = field == PK_F_CREDITS ? h->S.credits : field == PK_F_BETS ? h->S.bets : field == PK_F_PENDING_BETS ? h->S.pending : h->S.payoffs;
-    size_t n = (size_t)h->T * h->N;
-    return export_to_host(h, out, n * 8, [&] {
-        hipLaunchKernelGGL(k_export_f64, dim3(flat_grid(n)), dim3(256), 0, h->stream, src, h->T, h->N, (double *)h->d_export);
-    });
+    return export_to_host(h, out, (size_t)h->T * h->N * 8, [&] { launch_f64(h, field, (double *)h->d_export); });
 }
 
 int pk_get_f64_d(pk_handle *h, int field, double *out_d) {
     if (!h || !out_d || field < 0 || field > 3) return h ? h->fail(PK_E_INVALID_ARG, "pk_get_f64_d: bad argument") : PK_E_INVALID_ARG;
     ON_DEVICE(h);
     FLUSH_READER(h);
-    const double *src = field == PK_F_CREDITS ? h->S.credits : field == PK_F_BETS ? h->S.bets : field == PK_F_PENDING_BETS ? h->S.pending : h->S.payoffs;
-    size_t n = (size_t)h->T * h->N;
-    hipLaunchKernelGGL(k_export_f64, dim3(flat_grid(n)), dim3(256), 0, h->stream, src, h->T, h->N, out_d);
+    launch_f64(h, field, out_d);
     HIPCHK(h, hipGetLastError());
     return PK_OK;
 }
@@ -879,34 +869,28 @@ int pk_get_hand_ranks(pk_handle *h, uint8_t *rank, uint32_t *kick) {
 
 int pk_get_obs(pk_handle *h, int player, double *out) {
     if (!h || !out || bad_player(h, player)) return h ? h->fail(PK_E_INVALID_ARG, "pk_get_obs: bad argument") : PK_E_INVALID_ARG;
-    size_t bytes = (size_t)h->T * PK_OBS_DIM(h->N) * 8;
-    return export_to_host(h, out, bytes, [&] {
-        hipLaunchKernelGGL(k_obs, dim3(obs_grid(h->T)), dim3(OBS_BLOCK), 0, h->stream, h->S, h->N, player, (double *)h->d_export);
-    });
+    return export_to_host(h, out, (size_t)h->T * PK_OBS_DIM(h->N) * 8, [&] { launch_obs(h, player, (double *)h->d_export); });
 }
 
 int pk_get_obs_d(pk_handle *h, int player, double *out_d) {
     if (!h || !out_d || bad_player(h, player)) return h ? h->fail(PK_E_INVALID_ARG, "pk_get_obs_d: bad argument") : PK_E_INVALID_ARG;
     ON_DEVICE(h);
     FLUSH_READER(h);
-    hipLaunchKernelGGL(k_obs, dim3(obs_grid(h->T)), dim3(OBS_BLOCK), 0, h->stream, h->S, h->N, player, out_d);
+    launch_obs(h, player, out_d);
     HIPCHK(h, hipGetLastError());
     return PK_OK;
 }
 
 int pk_get_obs_packed(pk_handle *h, int player, uint8_t *out) {
     if (!h || !out || bad_player(h, player)) return h ? h->fail(PK_E_INVALID_ARG, "pk_get_obs_packed: bad argument") : PK_E_INVALID_ARG;
-    size_t bytes = (size_t)h->T * PK_OBS_PACKED_BYTES(h->N);
-    return export_to_host(h, out, bytes, [&] {
-        hipLaunchKernelGGL(k_obs_packed, dim3(obs_grid(h->T)), dim3(OBS_BLOCK), 0, h->stream, h->S, h->N, player, (uint8_t *)h->d_export);
-    });
+    return export_to_host(h, out, (size_t)h->T * PK_OBS_PACKED_BYTES(h->N), [&] { launch_obs_packed(h, player, (uint8_t *)h->d_export); });
 }
 
 int pk_get_obs_packed_d(pk_handle *h, int player, uint8_t *out_d) {
     if (!h || !out_d || bad_player(h, player) || ((uintptr_t)out_d & 7)) return h ? h->fail(PK_E_INVALID_ARG, "pk_get_obs_packed_d: bad argument (out_d must be 8-byte aligned)") : PK_E_INVALID_ARG;
     ON_DEVICE(h);
     FLUSH_READER(h);
-    hipLaunchKernelGGL(k_obs_packed, dim3(obs_grid(h->T)), dim3(OBS_BLOCK), 0, h->stream, h->S, h->N, player, out_d);
+    launch_obs_packed(h, player, out_d);
     HIPCHK(h, hipGetLastError());
     return PK_OK;
 }
@@ -928,10 +912,9 @@ int pk_set_step_obs(pk_handle *h, double *obs_d, uint8_t *obs_packed_d) {
 int pk_host_alloc(void **out, size_t bytes) {
     if (!out || bytes == 0) { g_err = "pk_host_alloc: bad argument"; return PK_E_INVALID_ARG; }
     *out = nullptr;
-    int rc = check_device_any();
-    if (rc) return rc;
+    if (int rc = check_device("pk_host_alloc", 0)) return rc;
     hipError_t e = hipHostMalloc(out, bytes, hipHostMallocPortable);
-    if (e != hipSuccess) { g_err = std::string("pk_host_alloc: ") + hipGetErrorString(e); *out = nullptr; return PK_E_OOM; }
+    if (e != hipSuccess) { *out = nullptr; return g_fail(PK_E_OOM, "pk_host_alloc", e); }
     return PK_OK;
 }
 
@@ -964,8 +947,7 @@ int pk_get_valid_actions_d(pk_handle *h, int player, uint8_t *out_d) {
     if (!h || !out_d || bad_player(h, player)) return h ? h->fail(PK_E_INVALID_ARG, "pk_get_valid_actions_d: bad argument") : PK_E_INVALID_ARG;
     ON_DEVICE(h);
     FLUSH_READER(h);
-    size_t n = (size_t)h->T * PK_NUM_MOVES;
-    hipLaunchKernelGGL(k_export_valid, dim3(flat_grid(n)), dim3(256), 0, h->stream, h->S, h->N, player, out_d);
+    launch_valid_actions(h, player, out_d);
     HIPCHK(h, hipGetLastError());
     return PK_OK;
 }
@@ -975,9 +957,7 @@ int pk_env_reset_d(pk_handle *h, const uint8_t *mask_d, int opp_policy) {
     ON_DEVICE(h);
     FLUSH(h);
     const EnvResetKernArgs ka{(const State *)h->d_S, h->hot_env, mask_d, uniform_seats(opp_policy), env_park(h)};
-    DISPATCH_N(h, k_env_reset, env_grid(h), ka);
-    HIPCHK(h, hipGetLastError());
-    return PK_OK;
+    return seat_launch(h, SEAT_KERNEL(k_env_reset, env_grid(h), h->stream, ka));
 }
 
 int pk_env_step_d(pk_handle *h, const int32_t *actions_d, int opp_policy, double *reward_d, uint8_t *done_d,
@@ -987,9 +967,7 @@ int pk_env_step_d(pk_handle *h, const int32_t *actions_d, int opp_policy, double
     ON_DEVICE(h);
     FLUSH(h);
     const EnvKernArgs ka = env_args(h, actions_d, -1, uniform_seats(opp_policy), 0, reward_d, done_d, hand_d, terr_d, nullptr);
-    DISPATCH_N(h, k_env_step, env_grid(h), ka);
-    HIPCHK(h, hipGetLastError());
-    return PK_OK;
+    return seat_launch(h, SEAT_KERNEL(k_env_step, env_grid(h), h->stream, ka));
 }
 
 int pk_env_step_fused_d(pk_handle *h, const int32_t *actions_d, int seat0_policy, int opp_policy, int auto_reset,
@@ -1000,9 +978,7 @@ int pk_env_step_fused_d(pk_handle *h, const int32_t *actions_d, int seat0_policy
     ON_DEVICE(h);
     FLUSH(h);
     const EnvKernArgs ka = with_packed(h, env_args(h, actions_d, actions_d ? -1 : seat0_policy, uniform_seats(opp_policy), auto_reset ? 1 : 0, reward_d, done_d, hand_d, terr_d, obs_d));
-    DISPATCH_N(h, k_env_step, env_grid(h), ka);
-    HIPCHK(h, hipGetLastError());
-    return PK_OK;
+    return seat_launch(h, SEAT_KERNEL(k_env_step, env_grid(h), h->stream, ka));
 }
 
 int pk_env_step_async_d(pk_handle *h, const int32_t *actions_d, int seat0_policy, int opp_policy, int auto_reset, int max_passes,
@@ -1023,8 +999,7 @@ int pk_env_step_async_d(pk_handle *h, const int32_t *actions_d, int seat0_policy
     if (h->env_batches <= 1) {
         EnvKernArgs ka = with_packed(h, env_args(h, actions_d, actions_d ? -1 : seat0_policy, uniform_seats(opp_policy), au, reward_d, done_d, hand_d, terr_d, obs_d));
         ka.A.ready = ready_d; ka.A.max_passes = mp;
-        DISPATCH_N(h, k_env_step_async, env_grid(h), ka);
-        HIPCHK(h, hipGetLastError());
+        if ((rc = seat_launch(h, SEAT_KERNEL(k_env_step_async, env_grid(h), h->stream, ka)))) return rc;
         h->env_last_begin = 0; h->env_last_end = h->T; h->env_last_fresh = 0;
     } else {
         // the caller's writes so far (actions of the range about to be launched) order before the launch(es) below
@@ -1040,8 +1015,7 @@ int pk_env_step_async_d(pk_handle *h, const int32_t *actions_d, int seat0_policy
             if (caller_busy) HIPCHK(h, hipStreamWaitEvent(h->env_streams[b], h->env_in, 0));
             EnvKernArgs ka = with_packed(h, env_args(h, actions_d, actions_d ? -1 : seat0_policy, uniform_seats(opp_policy), au, reward_d, done_d, hand_d, terr_d, obs_d));
             ka.A.ready = ready_d; ka.A.max_passes = passes; ka.A.t0 = t0; ka.A.tend = tend;
-            DISPATCH_N_ON(h, h->env_streams[b], k_env_step_async, (tend - t0 + h->env_tpb - 1) / h->env_tpb, ka);
-            HIPCHK(h, hipGetLastError());
+            if (int rc_ = seat_launch(h, SEAT_KERNEL(k_env_step_async, (tend - t0 + h->env_tpb - 1) / h->env_tpb, h->env_streams[b], ka))) return rc_;
             HIPCHK(h, hipEventRecord(h->env_done[b], h->env_streams[b]));
             return PK_OK;
         };
@@ -1061,12 +1035,8 @@ int pk_env_step_async_d(pk_handle *h, const int32_t *actions_d, int seat0_policy
             // stream is a barrier packet parked at the head of its hardware queue: when that queue happens to share a pipe of the
             // command processor with one of the range queues (which queues share depends on how many the process created before),
             // the parked barrier holds that range's dispatches back -- the same call sequence ran at 1.5 G env.step/s in a process
-            // that had used another PokerGameEnv handle before, 3.6 G in a fresh one.  env PK_ENV_HOST_WAIT=0: the device-side wait.
-            static const bool host_wait = !(getenv("PK_ENV_HOST_WAIT") && atoi(getenv("PK_ENV_HOST_WAIT")) == 0);
-            if (h->env_launched[d]) {
-                if (host_wait) HIPCHK(h, hipEventSynchronize(h->env_done[d]));
-                else HIPCHK(h, hipStreamWaitEvent(h->stream, h->env_done[d], 0));
-            }
+            // that had used another PokerGameEnv handle before, 3.6 G in a fresh one.
+            if (h->env_launched[d]) HIPCHK(h, hipEventSynchronize(h->env_done[d]));
             h->env_last_begin = d * h->env_range;
             h->env_last_end = (h->env_last_begin + h->env_range < h->T) ? h->env_last_begin + h->env_range : h->T;
             h->env_next = d;
@@ -1135,8 +1105,7 @@ int pk_env_step_multi_d(pk_handle *h, const int32_t *actions_d, const uint8_t *r
     const int pol0 = PK_SEAT_POLICY(seat_policies, 0);
     EnvKernArgs ka = with_packed(h, env_args(h, actions_d, pol0 == PK_POLICY_EXTERNAL ? -1 : pol0, seat_policies, au, reward_d, done_d, hand_d, terr_d, obs_d));
     ka.A.ready = ready_d; ka.A.max_passes = max_passes > 0 ? max_passes : 0; ka.A.reset_req = reset_d; ka.A.who = who_d;
-    DISPATCH_N(h, k_env_step_multi, env_grid(h), ka);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = seat_launch(h, SEAT_KERNEL(k_env_step_multi, env_grid(h), h->stream, ka)))) return rc;
     // a table may be waiting for the caller's action for an external seat even after a drain: in flight until pk_env_end_multi_d
     h->env_pending = max_passes > 0 || ext;
     h->env_multi = true; h->env_seats = seat_policies; h->env_auto = au;
@@ -1153,8 +1122,7 @@ int pk_env_end_multi_d(pk_handle *h) {
     // Outputs of steps that return during this drain go to the handle's own staging buffers, i.e. are dropped.
     EnvKernArgs ka = env_args(h, nullptr, pol0 == PK_POLICY_EXTERNAL ? -1 : pol0, h->env_seats, h->env_auto, h->d_reward, h->d_done, h->d_handf, h->d_terr, nullptr);
     ka.A.ready = h->d_flags; ka.A.who = h->d_mask; ka.A.abandon = 1; ka.A.obs_packed = nullptr;
-    DISPATCH_N(h, k_env_step_multi, env_grid(h), ka);
-    HIPCHK(h, hipGetLastError());
+    if (int rc = seat_launch(h, SEAT_KERNEL(k_env_step_multi, env_grid(h), h->stream, ka))) return rc;
     h->env_pending = false; h->env_multi = false;
     return PK_OK;
 }
@@ -1163,9 +1131,7 @@ int pk_pick_actions_d(pk_handle *h, int policy, int32_t *actions_d) {
     if (!h || !actions_d || bad_policy(policy)) return h ? h->fail(PK_E_INVALID_ARG, "pk_pick_actions_d: bad argument") : PK_E_INVALID_ARG;
     ON_DEVICE(h);
     FLUSH_READER(h);
-    DISPATCH_N(h, k_pick, table_grid(h), h->S, h->hot, policy, actions_d);
-    HIPCHK(h, hipGetLastError());
-    return PK_OK;
+    return seat_launch(h, SEAT_KERNEL(k_pick, table_grid(h), h->stream, h->S, h->hot, policy, actions_d));
 }
 
 int pk_pick_actions(pk_handle *h, int policy, int32_t *actions) {
@@ -1333,8 +1299,7 @@ int pk_env_step_begin(pk_handle *h, const int32_t *actions, int opp_policy, int 
     EnvKernArgs ka = env_args(h, h->d_actions, -1, uniform_seats(opp_policy), auto_reset ? 1 : 0, h->d_reward, h->d_done, h->d_handf, h->d_terr,
                               obs ? (double *)h->d_export : nullptr);
     ka.A.obs_packed = obs_packed ? h->d_obs_packed : nullptr;
-    DISPATCH_N(h, k_env_step, env_grid(h), ka);
-    HIPCHK(h, hipGetLastError());
+    if (int rc = seat_launch(h, SEAT_KERNEL(k_env_step, env_grid(h), h->stream, ka))) return rc;
     // Busy from HERE on: if one of the copies below fails to queue, the earlier ones are already queued into the caller's buffers, and
     // pk_env_step_end is the caller's sanctioned way to wait for them (round 5 set the flag after the last copy: ADVICE r05).
     h->host_step = true;      // until pk_env_step_end: every entry point that reads or changes tables (another begin included) is PK_E_BUSY
@@ -1597,32 +1562,9 @@ int pk_clone_tables_d(pk_handle *dst, const int32_t *dst_tables_d, pk_handle *sr
 }
 
 // ---- standalone judger ops (no handle)
-struct tmp_handle { std::string err; int fail(int code, const char *what, hipError_t e) { err = what; err += ": "; err += hipGetErrorString(e); g_err = err; return code; } };
-
-static int check_device(int device) {
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) { g_err = "no HIP device available; this library has no CPU fallback"; return PK_E_NO_DEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "device index out of range"; return PK_E_INVALID_ARG; }
-    return PK_OK;
-}
-
 // Grow-only device scratch of the host-buffer judger calls, one per device: no hipMalloc / hipFree per call.
 static std::mutex g_scratch_mu;
 static struct { void *p; size_t cap; } g_scratch[PK_MAX_DEVICES];
-// A per-device cache of device memory (the judger's scratch arena, the evaluator table) outlives its allocation when the application resets the
-// device: a kernel launched on such a pointer would fault.  Same seat belt as the stream pool's canary: look the ADDRESS up before trusting it.
-// The allocator hands the same addresses out again after a reset (measured: the evaluator table's address came back as the next handle's arena),
-// so base AND size must match -- and every cached allocation has an odd size (PK_ODD_BYTES more than it needs) that no caller is likely to ask for.
-#define PK_ODD_BYTES 272
-static bool dev_alloc_alive(const void *p, size_t bytes) {
-    if (!p) return false;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    const hipError_t e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
-    if (e != hipSuccess) (void)hipGetLastError();
-    return e == hipSuccess && (const void *)base == p && size == bytes;
-}
 static void *scratch(int device, size_t bytes) {  // caller holds g_scratch_mu and has the device current
     auto &s = g_scratch[device];
     if (s.p && !dev_alloc_alive(s.p, s.cap + PK_ODD_BYTES)) { s.p = nullptr; s.cap = 0; }      // (the device was reset: the arena is gone, not freed)
@@ -1636,16 +1578,13 @@ static void *scratch(int device, size_t bytes) {  // caller holds g_scratch_mu a
     return s.p;
 }
 
-// pk_eval_hands(_d)'s launch: the table path (k_eval_hands_tab); the register evaluator if the table could not be allocated or
-// env PK_EVAL_HANDS_TAB=0 (A/B knob).  tab: eval7_table(device), fetched by the caller BEFORE it takes g_scratch_mu.
+// pk_eval_hands(_d)'s launch: the table path (k_eval_hands_tab); the register evaluator if the table could not be allocated.
+// tab: eval7_table(device), fetched by the caller BEFORE it takes g_scratch_mu.
 static void launch_eval_hands(const uint32_t *tab, const uint8_t *cards_d, const uint8_t *ncards_d, size_t m, uint8_t *rank_d, uint32_t *kick_d,
                               uint8_t *nkick_d, hipStream_t stream) {
-    static const bool use_tab = !(getenv("PK_EVAL_HANDS_TAB") && atoi(getenv("PK_EVAL_HANDS_TAB")) == 0);
-    if (tab && use_tab) {
-        static const int grid_env = getenv("PK_EVAL_HANDS_GRID") ? atoi(getenv("PK_EVAL_HANDS_GRID")) : 256 * 8;
-        static const int grid_max = grid_env < 1 ? 1 : grid_env;              // (a knob value of 0 or below: one workgroup, never an empty or a wrapped-around grid)
+    if (tab) {
         const size_t chunks = (m + EVAL_TAB_BLOCK - 1) / EVAL_TAB_BLOCK;      // every workgroup copies the 32 KB table: no more of them than have hands
-        const unsigned grid = (unsigned)(chunks < (size_t)grid_max ? chunks : (size_t)grid_max);   // four resident per CU (LDS), two rounds; grid-stride over the rest
+        const unsigned grid = (unsigned)(chunks < 256 * 8 ? chunks : 256 * 8);   // four resident per CU (LDS), two rounds; grid-stride over the rest
         if (ncards_d) hipLaunchKernelGGL(k_eval_hands_tab<true>, dim3(grid), dim3(EVAL_TAB_BLOCK), 0, stream, cards_d, ncards_d, m, rank_d, kick_d, nkick_d, tab);
         else hipLaunchKernelGGL(k_eval_hands_tab<false>, dim3(grid), dim3(EVAL_TAB_BLOCK), 0, stream, cards_d, ncards_d, m, rank_d, kick_d, nkick_d, tab);
     } else {
@@ -1655,32 +1594,24 @@ static void launch_eval_hands(const uint32_t *tab, const uint8_t *cards_d, const
 
 int pk_eval_hands_d(int device, const uint8_t *cards_d, const uint8_t *ncards_d, size_t m, uint8_t *rank_d, uint32_t *kick_d,
                     uint8_t *nkick_d, void *stream) {
-    if (!cards_d || !rank_d || !kick_d) { g_err = "pk_eval_hands_d: NULL buffer"; return PK_E_INVALID_ARG; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) { g_err = "hipSetDevice failed"; return PK_E_HIP; }
+    if (!cards_d || !rank_d || !kick_d) return g_fail(PK_E_INVALID_ARG, "pk_eval_hands_d: NULL buffer");
+    ON_DEVICE_INDEX("pk_eval_hands_d", device, INT_MAX);
     if (m == 0) return PK_OK;
     launch_eval_hands(eval7_table(device, (hipStream_t)stream), cards_d, ncards_d, m, rank_d, kick_d, nkick_d, (hipStream_t)stream);   // (a first call builds the table on the CALLER's stream)
-    if (hipGetLastError() != hipSuccess) { g_err = "pk_eval_hands_d: launch failed"; return PK_E_HIP; }
+    if (hipGetLastError() != hipSuccess) return g_fail(PK_E_HIP, "pk_eval_hands_d: launch failed");
     return PK_OK;
 }
 
 int pk_eval_hands(int device, const uint8_t *cards, const uint8_t *ncards, size_t m, uint8_t *rank, uint32_t *kick,
                   uint8_t *nkick) {
-    if (!cards || !rank || !kick) { g_err = "pk_eval_hands: NULL buffer"; return PK_E_INVALID_ARG; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    if (device >= PK_MAX_DEVICES) { g_err = "pk_eval_hands: device index beyond PK_MAX_DEVICES"; return PK_E_INVALID_ARG; }
-    DeviceGuard guard(device);
-    if (!guard.ok) { g_err = "hipSetDevice failed"; return PK_E_HIP; }
+    if (!cards || !rank || !kick) return g_fail(PK_E_INVALID_ARG, "pk_eval_hands: NULL buffer");
+    ON_DEVICE_INDEX("pk_eval_hands", device, PK_MAX_DEVICES);
     if (m == 0) return PK_OK;
-    tmp_handle th;
     const uint32_t *tab = eval7_table(device);   // (takes g_scratch_mu itself)
     std::lock_guard<std::mutex> lock(g_scratch_mu);
     size_t off_n = m * 7, off_r = off_n + m, off_nk = off_r + m, off_k = (off_nk + m + 3) & ~(size_t)3, total = off_k + m * 4;
     uint8_t *d = (uint8_t *)scratch(device, total);
-    if (!d) { g_err = "pk_eval_hands: out of device memory"; return PK_E_OOM; }
+    if (!d) return g_fail(PK_E_OOM, "pk_eval_hands: out of device memory");
     hipError_t e = hipMemcpyAsync(d, cards, m * 7, hipMemcpyHostToDevice, 0);
     if (e == hipSuccess && ncards) e = hipMemcpyAsync(d + off_n, ncards, m, hipMemcpyHostToDevice, 0);
     if (e == hipSuccess) {
@@ -1691,24 +1622,19 @@ int pk_eval_hands(int device, const uint8_t *cards, const uint8_t *ncards, size_
     if (e == hipSuccess) e = hipMemcpyAsync(kick, d + off_k, m * 4, hipMemcpyDeviceToHost, 0);
     if (e == hipSuccess && nkick) e = hipMemcpyAsync(nkick, d + off_nk, m, hipMemcpyDeviceToHost, 0);
     if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (e != hipSuccess) return th.fail(PK_E_HIP, "pk_eval_hands", e);
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_eval_hands", e);
     return PK_OK;
 }
 
 int pk_compare_rankings(int device, const uint8_t *rank, const uint32_t *kick, int n, size_t m, uint8_t *onehot) {
-    if (!rank || !kick || !onehot || n < 1 || n > 32) { g_err = "pk_compare_rankings: bad argument (1 <= n <= 32)"; return PK_E_INVALID_ARG; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    if (device >= PK_MAX_DEVICES) { g_err = "pk_compare_rankings: device index beyond PK_MAX_DEVICES"; return PK_E_INVALID_ARG; }
-    DeviceGuard guard(device);
-    if (!guard.ok) { g_err = "hipSetDevice failed"; return PK_E_HIP; }
+    if (!rank || !kick || !onehot || n < 1 || n > 32) return g_fail(PK_E_INVALID_ARG, "pk_compare_rankings: bad argument (1 <= n <= 32)");
+    ON_DEVICE_INDEX("pk_compare_rankings", device, PK_MAX_DEVICES);
     if (m == 0) return PK_OK;
-    tmp_handle th;
     std::lock_guard<std::mutex> lock(g_scratch_mu);
     size_t cnt = m * (size_t)n;
     size_t off_r = cnt * 4, off_o = off_r + cnt, total = off_o + cnt;
     uint8_t *d = (uint8_t *)scratch(device, total);
-    if (!d) { g_err = "pk_compare_rankings: out of device memory"; return PK_E_OOM; }
+    if (!d) return g_fail(PK_E_OOM, "pk_compare_rankings: out of device memory");
     hipError_t e = hipMemcpyAsync(d, kick, cnt * 4, hipMemcpyHostToDevice, 0);
     if (e == hipSuccess) e = hipMemcpyAsync(d + off_r, rank, cnt, hipMemcpyHostToDevice, 0);
     if (e == hipSuccess) {
@@ -1717,7 +1643,7 @@ int pk_compare_rankings(int device, const uint8_t *rank, const uint32_t *kick, i
     }
     if (e == hipSuccess) e = hipMemcpyAsync(onehot, d + off_o, cnt, hipMemcpyDeviceToHost, 0);
     if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (e != hipSuccess) return th.fail(PK_E_HIP, "pk_compare_rankings", e);
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_compare_rankings", e);
     return PK_OK;
 }
 
@@ -1740,21 +1666,12 @@ static const uint32_t *eval7_table(int device, hipStream_t stream) {   // the de
 static int launch_eval7(int device, const uint64_t *hands_d, size_t m, uint32_t *out_d, int distinct) {
     const unsigned grid = 256 * 16;  // 16 workgroups per CU, grid-stride over the rest
     const bool vec = (((uintptr_t)hands_d & 15) | ((uintptr_t)out_d & 7)) == 0;  // 16-byte loads / 8-byte stores need it
-    static const bool no_tab = getenv("PK_EVAL7_NOTAB") != nullptr;   // A/B knob: the register-only evaluator of the table kernels
-    const uint32_t *tab = (distinct && !no_tab) ? eval7_table(device) : nullptr;
+    const uint32_t *tab = distinct ? eval7_table(device) : nullptr;
     if (tab) {   // four 512-thread workgroups per CU (LDS: 4 x 32 KB), two rounds of them
-        // A/B knob (bit 0 clear: software prefetch of the next hands; bit 1 clear: both hands' lookups issued before either is used):
-        // all four within 1.5 % of each other at 2^28 hands; the plain form is the default
-        static const int variant = getenv("PK_EVAL7_VARIANT") ? atoi(getenv("PK_EVAL7_VARIANT")) : 3;
-        static const int grid_env = getenv("PK_EVAL7_GRID") ? atoi(getenv("PK_EVAL7_GRID")) : 256 * 32;
-        static const int grid_max = grid_env < 1 ? 1 : grid_env;
         const size_t want = (m / 2 + 511) / 512;     // every workgroup copies the 32 KB table: no more of them than have hands
-        const unsigned gridx = (unsigned)(want < 1 ? 1 : (want < (size_t)grid_max ? want : (size_t)grid_max));
-        if (vec && variant == 1) hipLaunchKernelGGL((k_eval7_tab_stream<true, 1>), dim3(gridx), dim3(512), 0, 0, hands_d, m, out_d, tab);
-        else if (vec && variant == 2) hipLaunchKernelGGL((k_eval7_tab_stream<true, 2>), dim3(gridx), dim3(512), 0, 0, hands_d, m, out_d, tab);
-        else if (vec && variant == 0) hipLaunchKernelGGL((k_eval7_tab_stream<true, 0>), dim3(gridx), dim3(512), 0, 0, hands_d, m, out_d, tab);
-        else if (vec) hipLaunchKernelGGL((k_eval7_tab_stream<true, 3>), dim3(gridx), dim3(512), 0, 0, hands_d, m, out_d, tab);
-        else hipLaunchKernelGGL((k_eval7_tab_stream<false, 3>), dim3(gridx), dim3(512), 0, 0, hands_d, m, out_d, tab);
+        const unsigned gridx = (unsigned)(want < 1 ? 1 : (want < 256 * 32 ? want : 256 * 32));
+        if (vec) hipLaunchKernelGGL(k_eval7_tab_stream<true>, dim3(gridx), dim3(512), 0, 0, hands_d, m, out_d, tab);
+        else hipLaunchKernelGGL(k_eval7_tab_stream<false>, dim3(gridx), dim3(512), 0, 0, hands_d, m, out_d, tab);
     } else if (distinct) {
         if (vec) hipLaunchKernelGGL((k_eval7_stream<true, true>), dim3(grid), dim3(256), 0, 0, hands_d, m, out_d);
         else hipLaunchKernelGGL((k_eval7_stream<true, false>), dim3(grid), dim3(256), 0, 0, hands_d, m, out_d);
@@ -1766,38 +1683,29 @@ static int launch_eval7(int device, const uint64_t *hands_d, size_t m, uint32_t 
 }
 
 int pk_eval7_d(int device, const uint64_t *hands_d, size_t m, uint32_t *out_d, int distinct) {
-    if (!hands_d || !out_d || ((uintptr_t)hands_d & 7) || ((uintptr_t)out_d & 3)) { g_err = "pk_eval7_d: NULL or misaligned buffer"; return PK_E_INVALID_ARG; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) { g_err = "hipSetDevice failed"; return PK_E_HIP; }
+    if (!hands_d || !out_d || ((uintptr_t)hands_d & 7) || ((uintptr_t)out_d & 3)) return g_fail(PK_E_INVALID_ARG, "pk_eval7_d: NULL or misaligned buffer");
+    ON_DEVICE_INDEX("pk_eval7_d", device, INT_MAX);
     if (m == 0) return PK_OK;
-    if (launch_eval7(device, hands_d, m, out_d, distinct) != PK_OK || hipDeviceSynchronize() != hipSuccess) { g_err = "pk_eval7_d: launch failed"; return PK_E_HIP; }
+    if (launch_eval7(device, hands_d, m, out_d, distinct) != PK_OK || hipDeviceSynchronize() != hipSuccess) return g_fail(PK_E_HIP, "pk_eval7_d: launch failed");
     return PK_OK;
 }
 
 int pk_make_hands_d(int device, uint64_t seed, size_t m, uint64_t *hands_d) {
-    if (!hands_d) { g_err = "pk_make_hands_d: NULL buffer"; return PK_E_INVALID_ARG; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) { g_err = "hipSetDevice failed"; return PK_E_HIP; }
+    if (!hands_d) return g_fail(PK_E_INVALID_ARG, "pk_make_hands_d: NULL buffer");
+    ON_DEVICE_INDEX("pk_make_hands_d", device, INT_MAX);
     if (m == 0) return PK_OK;
     Hot H{};
     H.key0 = (uint32_t)seed; H.key1 = (uint32_t)(seed >> 32);
     hipLaunchKernelGGL(k_make_hands, dim3(256 * 16), dim3(256), 0, 0, H, m, hands_d);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { g_err = "pk_make_hands_d: launch failed"; return PK_E_HIP; }
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return g_fail(PK_E_HIP, "pk_make_hands_d: launch failed");
     return PK_OK;
 }
 
 int pk_time_eval7_d(int device, const uint64_t *hands_d, size_t m, uint32_t *out_d, int distinct, int reps, double *ms_per_pass) {
-    if (!hands_d || !out_d || !ms_per_pass || reps < 1) { g_err = "pk_time_eval7_d: bad argument"; return PK_E_INVALID_ARG; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    DeviceGuard guard(device);
-    if (!guard.ok) { g_err = "hipSetDevice failed"; return PK_E_HIP; }
+    if (!hands_d || !out_d || !ms_per_pass || reps < 1) return g_fail(PK_E_INVALID_ARG, "pk_time_eval7_d: bad argument");
+    ON_DEVICE_INDEX("pk_time_eval7_d", device, INT_MAX);
     hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { g_err = "hipEventCreate failed"; return PK_E_HIP; }
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return g_fail(PK_E_HIP, "hipEventCreate failed");
     launch_eval7(device, hands_d, m, out_d, distinct);  // warm (instruction cache, clocks)
     (void)hipEventRecord(e0, 0);
     for (int r = 0; r < reps; ++r) launch_eval7(device, hands_d, m, out_d, distinct);
@@ -1806,7 +1714,7 @@ int pk_time_eval7_d(int device, const uint64_t *hands_d, size_t m, uint32_t *out
     float ms = 0.f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (e != hipSuccess) { g_err = std::string("pk_time_eval7_d: ") + hipGetErrorString(e); return PK_E_HIP; }
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_time_eval7_d", e);
     *ms_per_pass = (double)ms / reps;
     return PK_OK;
 }
@@ -1814,26 +1722,21 @@ int pk_time_eval7_d(int device, const uint64_t *hands_d, size_t m, uint32_t *out
 // Test hook (declared in pokerl_hip.h as part of the judger surface): values rank<<20|kick of all 7-card hands whose
 // two lowest canonical indices are (a, b), lexicographic order.  out holds C(51-b, 5) words.
 int pk_eval7_prefix(int device, int a, int b, int fast, uint32_t *out, size_t *count_out) {
-    if (!out || a < 0 || b <= a || b > 51) { g_err = "pk_eval7_prefix: bad argument"; return PK_E_INVALID_ARG; }
-    int rc = check_device(device);
-    if (rc) return rc;
-    if (device >= PK_MAX_DEVICES) { g_err = "pk_eval7_prefix: device index beyond PK_MAX_DEVICES"; return PK_E_INVALID_ARG; }
-    DeviceGuard guard(device);
-    if (!guard.ok) { g_err = "hipSetDevice failed"; return PK_E_HIP; }
+    if (!out || a < 0 || b <= a || b > 51) return g_fail(PK_E_INVALID_ARG, "pk_eval7_prefix: bad argument");
+    ON_DEVICE_INDEX("pk_eval7_prefix", device, PK_MAX_DEVICES);
     int n = 51 - b;
     size_t count = n >= 5 ? (size_t)n * (n - 1) * (n - 2) * (n - 3) * (n - 4) / 120 : 0;
     if (count_out) *count_out = count;
     if (!count) return PK_OK;
-    tmp_handle th;
     const uint32_t *tab = (fast == 2 || fast == 4) ? eval7_table(device) : nullptr;   // (takes g_scratch_mu itself)
-    if ((fast == 2 || fast == 4) && !tab) { g_err = "pk_eval7_prefix: out of device memory"; return PK_E_OOM; }
+    if ((fast == 2 || fast == 4) && !tab) return g_fail(PK_E_OOM, "pk_eval7_prefix: out of device memory");
     std::lock_guard<std::mutex> lock(g_scratch_mu);
     uint32_t *d = (uint32_t *)scratch(device, count * 4);
-    if (!d) { g_err = "pk_eval7_prefix: out of device memory"; return PK_E_OOM; }
+    if (!d) return g_fail(PK_E_OOM, "pk_eval7_prefix: out of device memory");
     hipLaunchKernelGGL(k_eval7_prefix, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, a, b, fast, (uint32_t)count, d, tab);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out, d, count * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return th.fail(PK_E_HIP, "pk_eval7_prefix", e);
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_eval7_prefix", e);
     return PK_OK;
 }
 

@@ -1053,27 +1053,20 @@ __global__ void k_make_eval7_tab(uint32_t *tab) {
 }
 // Streaming evaluator for 7 DISTINCT cards, table-driven (eval7_tab): 512-thread workgroups, four per CU (4 x 32 KB of LDS),
 // eight waves per SIMD under the 64-register cap; same two-hands-per-lane 16-byte loads / 8-byte stores as above.
-template <bool VEC, int VARIANT>
+template <bool VEC>
 __global__ void __launch_bounds__(512, 8) k_eval7_tab_stream(const uint64_t *__restrict__ hands, size_t m, uint32_t *__restrict__ out, const uint32_t *__restrict__ tab) {
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += 512) reinterpret_cast<uint4 *>(T)[i] = reinterpret_cast<const uint4 *>(tab)[i];
     __syncthreads();
     const size_t pairs = VEC ? m / 2 : 0, stride = (size_t)gridDim.x * blockDim.x;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    constexpr bool PREFETCH = (VARIANT & 1) == 0, TWO_PHASE = (VARIANT & 2) == 0;
     uint4 w = i < pairs ? reinterpret_cast<const uint4 *>(hands)[i] : uint4{0, 0, 0, 0};
     for (; i < pairs; i += stride) {
-        const size_t nx = i + stride;                       // the next iteration's hands are in flight while these are evaluated
-        uint4 wn = uint4{0, 0, 0, 0};
-        if (PREFETCH) { if (nx < pairs) wn = reinterpret_cast<const uint4 *>(hands)[nx]; }
+        const size_t nx = i + stride;
         uint2 r;
-        if (TWO_PHASE) {
-            const Eval7Front f0 = eval7_tab_front(w.x, w.y, T), f1 = eval7_tab_front(w.z, w.w, T);   // ten lookups issued ...
-            r.x = eval7_tab_back(f0, T); r.y = eval7_tab_back(f1, T);                                // ... before the first is used
-        } else { r.x = eval7_tab(w.x, w.y, T); r.y = eval7_tab(w.z, w.w, T); }
+        r.x = eval7_tab(w.x, w.y, T); r.y = eval7_tab(w.z, w.w, T);
         reinterpret_cast<uint2 *>(out)[i] = r;
-        if (PREFETCH) w = wn;
-        else if (nx < pairs) w = reinterpret_cast<const uint4 *>(hands)[nx];
+        if (nx < pairs) w = reinterpret_cast<const uint4 *>(hands)[nx];
     }
     if constexpr (VEC) {
         if ((m & 1) && blockIdx.x == 0 && threadIdx.x == 0) out[m - 1] = eval7_tab((uint32_t)hands[m - 1], (uint32_t)(hands[m - 1] >> 32), T);

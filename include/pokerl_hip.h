@@ -510,6 +510,47 @@ int pk_load_tables(pk_handle *h, const int32_t *tables, size_t m, const void *bl
  * Money, cursors, serials, show, valid and terr are copied unchanged.  Both handles need the same N and money configuration. */
 int pk_clone_tables_d(pk_handle *dst, const int32_t *dst_tables_d, pk_handle *src, const int32_t *src_tables_d, size_t m, int observer,
                       uint64_t nonce);
+/* ---- Showdown equity: "if the cards still to come were dealt now, how often does each seat win?" -- every board enumerated on the device,
+ * exact integer counts.
+ *
+ * A SPOT is N seats (the num_players of the call, 2 .. 16), two hole-card bytes per seat (Card.value; 0xFF = unknown / not dealt, allowed only
+ * at a seat that is not live), nb = 0 .. 5 known board cards and a 16-bit live mask (bit p: seat p takes part in the showdown; bits >= N are
+ * ignored).  Dead cards = the nb board cards and every hole card that is not 0xFF, live or not.  Pool = the 52 cards minus the dead ones,
+ * P of them; boards = all C(P, 5 - nb) completions.  On each board v[p] = eval_hand(board + hole[p]) for a live seat and eval_hand([]) =
+ * (NONE, []) for the others -- the list Game.end_hand builds (game.py:488-490) -- and the winners are compare_rankings(v) (judger.py:111-158
+ * INCLUDING its line-148 behaviour: who takes the main pot as the reference judges it, which is not always who wins at poker).
+ * Per spot and seat, nw = the number of winners of a board:
+ *   win[p]   u32  boards on which p is the only winner          tie[p]  u32  boards on which p wins and nw > 1
+ *   share[p] u64  sum over the boards p wins of PK_EQ_SHARE_UNIT / nw  (720720 = lcm(1 .. 16): exact; sum over p = 720720 * boards)
+ *   boards   u32  C(P, 5 - nb)                                    status  u8   PK_EQ_* bits, 0 = evaluated
+ * equity[p] = share[p] / (720720 * boards).  A spot with a non-zero status gets all-zero counts and boards = 0; it never fails the call or
+ * disturbs another spot.  Any of win / tie / share / boards / status may be NULL (not wanted).  m == 0 is a no-op; m < 2^31, and
+ * a call whose worst-case task count (every spot pre-flop: 33 per spot in the explicit form from 256 spots on) does not fit 32 bits -- about
+ * 130 M spots -- is refused with PK_E_INVALID_ARG: split the batch.  device < PK_MAX_DEVICES.
+ * STREAMS: the device form runs on the stream it is given, asynchronously (its work space is a grow-only buffer the library keeps per
+ * stream, for the 8 most recently used streams of a device); the host forms are synchronous -- the handle-less one on a pooled non-blocking stream, the table one on the handle's stream.
+ * None of them touches the legacy default stream unless the caller passes it (stream == NULL) explicitly.
+ * TABLE FORM: spot i is table tables[i] of the handle (NULL: table i; indices may repeat): board = deck[0:nb] with nb = 0 at turn 0, else
+ * min(turn + 2, 5); hole cards = deck[5+2p : 7+2p] of EVERY seat (all 2N are dead, folded and broken seats included); live = the seats that are
+ * ACTIVE, CALLED or ALL_IN.  The future board cards the deck already holds are unknown: they are in the pool.  It reads the handle's state and
+ * writes nothing to it, completes deferred rollout work first like the getters, and runs on the handle's stream.  A table created but never
+ * reset has an all-zero deck and reports PK_EQ_DUP_CARD. */
+#define PK_EQ_SHARE_UNIT 720720u
+#define PK_EQ_BAD_CARD 1u    /* a byte that is no card; 0xFF in the board or at a live seat */
+#define PK_EQ_DUP_CARD 2u    /* a card twice */
+#define PK_EQ_NO_LIVE 4u     /* no live seat */
+#define PK_EQ_BAD_NBOARD 8u  /* nb > 5 */
+#define PK_EQ_IN_FLIGHT 16u  /* table form: the table's step is in flight (the asynchronous Game.step entry point) */
+#define PK_EQ_BAD_TABLE 32u  /* table form: the table index is out of range (nothing is read) */
+/* holes_d u8 [m][N][2], board_d u8 [m][5] (the first nboard_d[i] used), nboard_d u8 [m], live_d u16 [m]; outputs [m][N] / [m]. */
+int pk_equity_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
+                const uint16_t *live_d, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *boards_d, uint8_t *status_d, void *stream);
+int pk_equity(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
+              uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards, uint8_t *status);
+int pk_table_equity_d(pk_handle *h, const int32_t *tables_d, size_t m, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *boards_d,
+                      uint8_t *status_d);
+int pk_table_equity(pk_handle *h, const int32_t *tables, size_t m, uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards,
+                    uint8_t *status);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

@@ -14,6 +14,7 @@
 
 #include "pk_device.hpp"
 #include "pk_kernels.hpp"
+#include "pk_equity.hpp"
 #include "pk_snapshot.hpp"
 
 using namespace pk;
@@ -1737,6 +1738,184 @@ int pk_eval7_prefix(int device, int a, int b, int fast, uint32_t *out, size_t *c
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out, d, count * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_eval7_prefix", e);
+    return PK_OK;
+}
+
+// ---- showdown equity (pokerl_hip.h "Showdown equity"; kernels: pk_equity.hip)
+static bool eq_bad_seats(int n) { return n < PK_MIN_PLAYERS || n > PK_MAX_PLAYERS; }
+static const size_t EQ_MAX_SPOTS = (size_t)1 << 31;
+// The device counts a call's tasks in 32 bits: a call whose worst case (every spot pre-flop) does not fit is refused, not wrapped.
+static bool eq_too_many_tasks(size_t m, int pool_max) { return eq_task_cap(m, eq_lpt(m), pool_max) > EQ_TASKS_MAX; }
+#define EQ_TASKS_MSG ": too many spots for one call (the worst-case task count must fit 32 bits: split the batch)"
+
+// Work space of the device form, which runs asynchronously on the CALLER's stream: one grow-only hipMalloc'ed buffer per (device, stream),
+// reused by the next call on that stream -- stream order makes that safe -- and at most EQ_WS_STREAMS of them per device (the least
+// recently used one is freed for a new stream; hipFree waits for the device, so work still queued on it is not cut short).  NOT the
+// stream-ordered allocator: with hipMallocAsync / hipFreeAsync every call that followed a synchronisation got a fresh mapping, and on
+// such a mapping the enumeration kernel found the task count still zero -- every third call of a 4 096-spot loop returned all-zero
+// counts (measured, ROCm 7.2).
+static const int EQ_WS_STREAMS = 8;
+struct EqStreamWs { hipStream_t stream; void *p; size_t cap; uint64_t used; };
+static std::mutex g_eq_ws_mu;
+static std::vector<EqStreamWs> g_eq_ws[PK_MAX_DEVICES];
+static uint64_t g_eq_ws_clock;
+static void *eq_stream_ws(int device, hipStream_t st, size_t bytes) {   // the device is current and < PK_MAX_DEVICES
+    std::lock_guard<std::mutex> lock(g_eq_ws_mu);
+    auto &v = g_eq_ws[device];
+    for (size_t i = 0; i < v.size();)            // (buffers that vanished with a device reset are forgotten, not freed)
+        if (!dev_alloc_alive(v[i].p, v[i].cap + PK_ODD_BYTES)) v.erase(v.begin() + i); else ++i;
+    EqStreamWs *hit = nullptr;
+    for (auto &x : v) if (x.stream == st) hit = &x;
+    if (hit && hit->cap >= bytes) { hit->used = ++g_eq_ws_clock; return hit->p; }
+    if (hit) {                                   // too small: the calls queued on it so far must finish before it goes
+        if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+        (void)hipFree(hit->p);
+        v.erase(v.begin() + (hit - v.data()));
+    } else if ((int)v.size() >= EQ_WS_STREAMS) {
+        size_t lru = 0;
+        for (size_t i = 1; i < v.size(); ++i) if (v[i].used < v[lru].used) lru = i;
+        (void)hipFree(v[lru].p);
+        v.erase(v.begin() + lru);
+    }
+    const size_t cap = bytes < (1u << 20) ? (1u << 20) : bytes + bytes / 4;
+    void *p = nullptr;
+    if (hipMalloc(&p, cap + PK_ODD_BYTES) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    v.push_back(EqStreamWs{st, p, cap, ++g_eq_ws_clock});
+    return p;
+}
+
+int pk_equity_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
+                const uint16_t *live_d, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *boards_d, uint8_t *status_d, void *stream) {
+    if (eq_bad_seats(num_players) || m >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, "pk_equity_d: num_players outside 2 .. 16, or m >= 2^31");
+    if (m && (!holes_d || !board_d || !nboard_d || !live_d)) return g_fail(PK_E_INVALID_ARG, "pk_equity_d: NULL input buffer");
+    if (eq_too_many_tasks(m, 50)) return g_fail(PK_E_INVALID_ARG, "pk_equity_d" EQ_TASKS_MSG);
+    ON_DEVICE_INDEX("pk_equity_d", device, PK_MAX_DEVICES);   // (the evaluator table is kept per device index below PK_MAX_DEVICES)
+    if (m == 0) return PK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t *tab = eval7_table(device, st);   // (a first call builds the table on the CALLER's stream)
+    if (!tab) return g_fail(PK_E_OOM, "pk_equity_d: out of device memory (evaluator table)");
+    const int lpt = eq_lpt(m);
+    void *ws = eq_stream_ws(device, st, eq_layout(num_players, m, lpt, 50, nullptr, nullptr));
+    if (!ws) return g_fail(PK_E_OOM, "pk_equity_d: out of device memory (work space)");
+    EqWork w;
+    eq_layout(num_players, m, lpt, 50, (char *)ws, &w);
+    const EqSpots spots{holes_d, board_d, nboard_d, live_d};
+    const hipError_t e = eq_launch(st, tab, &spots, nullptr, num_players, m, EqOut{win_d, tie_d, share_d, boards_d, status_d}, w, lpt);
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_d: launch failed", e);
+    return PK_OK;
+}
+
+// Device staging of a host-array call: the count outputs that are wanted, 256-byte aligned, after `in_bytes` of inputs
+struct EqStage {
+    size_t win, tie, share, boards, status, work, total;
+    EqStage(size_t in_bytes, int N, size_t m, size_t work_bytes) {
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        size_t off = al(in_bytes);
+        share = off; off += al(m * N * 8);
+        win = off; off += al(m * N * 4);
+        tie = off; off += al(m * N * 4);
+        boards = off; off += al(m * 4);
+        status = off; off += al(m);
+        work = off; total = off + work_bytes;
+    }
+};
+static hipError_t eq_fetch(hipStream_t st, const char *d, const EqStage &g, int N, size_t m, uint32_t *win, uint32_t *tie, uint64_t *share,
+                           uint32_t *boards, uint8_t *status) {
+    hipError_t e = hipSuccess;
+    if (e == hipSuccess && win) e = hipMemcpyAsync(win, d + g.win, m * N * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && tie) e = hipMemcpyAsync(tie, d + g.tie, m * N * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && share) e = hipMemcpyAsync(share, d + g.share, m * N * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && boards) e = hipMemcpyAsync(boards, d + g.boards, m * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && status) e = hipMemcpyAsync(status, d + g.status, m, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e;
+}
+static EqOut eq_staged_out(char *d, const EqStage &g, const uint32_t *win, const uint32_t *tie, const uint64_t *share, const uint32_t *boards,
+                           const uint8_t *status) {
+    return EqOut{win ? (uint32_t *)(d + g.win) : nullptr, tie ? (uint32_t *)(d + g.tie) : nullptr, share ? (uint64_t *)(d + g.share) : nullptr,
+                 boards ? (uint32_t *)(d + g.boards) : nullptr, status ? (uint8_t *)(d + g.status) : nullptr};
+}
+
+int pk_equity(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
+              uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards, uint8_t *status) {
+    if (eq_bad_seats(num_players) || m >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, "pk_equity: num_players outside 2 .. 16, or m >= 2^31");
+    if (m && (!holes || !board || !nboard || !live)) return g_fail(PK_E_INVALID_ARG, "pk_equity: NULL input buffer");
+    if (eq_too_many_tasks(m, 50)) return g_fail(PK_E_INVALID_ARG, "pk_equity" EQ_TASKS_MSG);
+    ON_DEVICE_INDEX("pk_equity", device, PK_MAX_DEVICES);
+    if (m == 0) return PK_OK;
+    const int N = num_players, lpt = eq_lpt(m);
+    hipStream_t st = nullptr;
+    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity: no stream"); }
+    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
+    int rc = PK_OK;
+    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity: out of device memory (evaluator table)");
+    else {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        const size_t off_b = m * N * 2, off_n = off_b + m * 5, off_l = (off_n + m + 1) & ~(size_t)1;
+        const EqStage g(off_l + m * 2, N, m, eq_layout(N, m, lpt, 50, nullptr, nullptr));
+        char *d = (char *)scratch(device, g.total);
+        if (!d) rc = g_fail(PK_E_OOM, "pk_equity: out of device memory");
+        else {
+            hipError_t e = hipMemcpyAsync(d, holes, m * N * 2, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(d + off_b, board, m * 5, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(d + off_n, nboard, m, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(d + off_l, live, m * 2, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) {
+                EqWork w;
+                eq_layout(N, m, lpt, 50, d + g.work, &w);
+                const EqSpots spots{(const uint8_t *)d, (const uint8_t *)d + off_b, (const uint8_t *)d + off_n, (const uint16_t *)(d + off_l)};
+                e = eq_launch(st, tab, &spots, nullptr, N, m, eq_staged_out(d, g, win, tie, share, boards, status), w, lpt);
+            }
+            if (e == hipSuccess) e = eq_fetch(st, d, g, N, m, win, tie, share, boards, status);
+            else (void)hipStreamSynchronize(st);
+            if (e != hipSuccess) rc = g_fail(PK_E_HIP, "pk_equity", e);
+        }
+    }
+    stream_release(device, st);
+    return rc;
+}
+
+// The table form reads the handle's own state on the handle's stream; its work space is the handle's grow-only staging buffer.
+static int table_equity(pk_handle *h, const int32_t *tables_d, size_t m, const EqOut &out, char *work) {
+    const uint32_t *tab = eval7_table(h->device, h->stream);
+    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity: out of device memory (evaluator table)");
+    const int lpt = eq_lpt(m);
+    EqWork w;
+    eq_layout(h->N, m, lpt, 52 - 2 * h->N, work, &w);
+    const EqTables t{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T};
+    HIPCHK(h, eq_launch(h->stream, tab, nullptr, &t, h->N, m, out, w, lpt));
+    return PK_OK;
+}
+
+int pk_table_equity_d(pk_handle *h, const int32_t *tables_d, size_t m, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *boards_d,
+                      uint8_t *status_d) {
+    if (!h) return PK_E_INVALID_ARG;
+    if (m >= EQ_MAX_SPOTS) return h->fail(PK_E_INVALID_ARG, "pk_table_equity_d: m >= 2^31");
+    if (eq_too_many_tasks(m, 52 - 2 * h->N)) return h->fail(PK_E_INVALID_ARG, "pk_table_equity_d" EQ_TASKS_MSG);
+    ON_DEVICE(h);
+    FLUSH_READER(h);
+    if (m == 0) return PK_OK;
+    char *stage = nullptr;
+    const int rc = snap_staging(h, eq_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, nullptr, nullptr), &stage);
+    if (rc) return rc;
+    return table_equity(h, tables_d, m, EqOut{win_d, tie_d, share_d, boards_d, status_d}, stage);
+}
+
+int pk_table_equity(pk_handle *h, const int32_t *tables, size_t m, uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards,
+                    uint8_t *status) {
+    if (!h) return PK_E_INVALID_ARG;
+    if (m >= EQ_MAX_SPOTS) return h->fail(PK_E_INVALID_ARG, "pk_table_equity: m >= 2^31");
+    if (eq_too_many_tasks(m, 52 - 2 * h->N)) return h->fail(PK_E_INVALID_ARG, "pk_table_equity" EQ_TASKS_MSG);
+    ON_DEVICE(h);
+    FLUSH_READER(h);
+    if (m == 0) return PK_OK;
+    const EqStage g(tables ? m * 4 : 0, h->N, m, eq_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, nullptr, nullptr));
+    char *d = nullptr;
+    int rc = snap_staging(h, g.total, &d);
+    if (rc) return rc;
+    if (tables) HIPCHK(h, hipMemcpyAsync(d, tables, m * 4, hipMemcpyHostToDevice, h->stream));
+    if ((rc = table_equity(h, tables ? (const int32_t *)d : nullptr, m, eq_staged_out(d, g, win, tie, share, boards, status), d + g.work))) return rc;
+    HIPCHK(h, eq_fetch(h->stream, d, g, h->N, m, win, tie, share, boards, status));
     return PK_OK;
 }
 

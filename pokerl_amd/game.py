@@ -360,6 +360,27 @@ class VecGame:
                 if b is not None:
                     b.free()
 
+    def equity(self, tables=None):
+        """Showdown equity of `tables` (all tables if None; indices may repeat) as they stand: every completion of the board enumerated on
+        the device (pk_table_equity; definition: pokerl_hip.h "Showdown equity").  Board = the community cards dealt so far, hole cards =
+        every seat's (all dead), live = the seats still in the hand; the future board cards the deck holds are unknown.  Returns a
+        judger.Equity of [m, N] / [m] arrays; a table that cannot be evaluated (never reset, step in flight) has a non-zero status."""
+        from .judger import Equity
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        n = self.num_players
+        win, tie, share = np.zeros((m, n), np.uint32), np.zeros((m, n), np.uint32), np.zeros((m, n), np.uint64)
+        boards, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        L.check(self._lib.pk_table_equity(self._h, L.ptr(t), m, L.ptr(win), L.ptr(tie), L.ptr(share), L.ptr(boards), L.ptr(status)), self._h)
+        return Equity(win, tie, share, boards, status)
+
+    def equity_d(self, m=None, tables_d=None, win_d=None, tie_d=None, share_d=None, boards_d=None, status_d=None):
+        """pk_table_equity_d: the same into device buffers (uint32 [m, N] win / tie, uint64 [m, N] share, uint32 [m] boards, uint8 [m]
+        status; any may be None), asynchronous on the handle's stream.  m defaults to every table."""
+        m = self.num_tables if m is None else int(m)
+        L.check(self._lib.pk_table_equity_d(self._h, self._dptr(tables_d), m, self._dptr(win_d), self._dptr(tie_d), self._dptr(share_d),
+                                            self._dptr(boards_d), self._dptr(status_d)), self._h)
+
     def __deepcopy__(self, memo):
         """A new handle with the same configuration (seed and table ids included) holding a copy of every table: it continues
         bit-identically to this game under the same actions, and stepping one leaves the other untouched.  Only the construction

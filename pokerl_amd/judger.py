@@ -109,3 +109,110 @@ def time_eval7_stream(hands_d, m, out_d, distinct=True, reps=5, device=0):
     ms = C.c_double(0.0)
     L.check(L.lib().pk_time_eval7_d(int(device), hands_d, int(m), out_d, int(bool(distinct)), int(reps), C.byref(ms)))
     return ms.value
+
+
+# ---------------------------------------------------------------------------------------------- showdown equity
+# "If the cards still to come were dealt now, how often does each seat win?" -- every board enumerated on the device (pk_equity; the
+# definition: include/pokerl_hip.h "Showdown equity").  Winners are the reference's compare_rankings, line 148 included.
+UNKNOWN_CARD = 0xFF
+_EQ_STATUS = [(L.EQ_BAD_CARD, 'a byte that is no card (or an unknown card in the board or at a live seat)'), (L.EQ_DUP_CARD, 'a card twice'),
+              (L.EQ_NO_LIVE, 'no live seat'), (L.EQ_BAD_NBOARD, 'more than five board cards'),
+              (L.EQ_IN_FLIGHT, "the table's step is in flight"), (L.EQ_BAD_TABLE, 'table index out of range')]
+
+
+def equity_status_text(status):
+    return '; '.join(t for bit, t in _EQ_STATUS if int(status) & bit) or 'ok'
+
+
+class Equity:
+    """Counts of one spot or of a batch ([N] or [m, N] arrays; `boards`, `status` scalars or [m]): win = boards a seat wins alone, tie = boards
+    it wins with others, share = sum of 720720 / (number of winners) over the boards it wins.  `equity` = share / (720720 * boards) in float64
+    (0 where a spot was refused: status != 0)."""
+
+    def __init__(self, win, tie, share, boards, status):
+        self.win, self.tie, self.share, self.boards, self.status = win, tie, share, boards, status
+
+    @property
+    def equity(self):
+        b = np.asarray(self.boards, np.float64)[..., None] * float(L.EQ_SHARE_UNIT)
+        return np.divide(np.asarray(self.share, np.float64), b, out=np.zeros(np.shape(self.share), np.float64), where=b > 0)
+
+    def __getitem__(self, i):
+        return Equity(self.win[i], self.tie[i], self.share[i], self.boards[i], self.status[i])
+
+    def __repr__(self):
+        return 'Equity(boards=%r, status=%r, win=%r, tie=%r, equity=%r)' % (self.boards, self.status, self.win, self.tie, self.equity)
+
+
+def showdown_equity_batch(holes, board, nboard, live, device=0):
+    """pk_equity on host arrays: holes uint8 [m, N, 2] Card.value (0xFF = unknown, at seats that are not live only), board uint8 [m, 5] (the
+    first nboard[i] used), nboard uint8 [m], live uint16 [m] seat masks -> Equity of [m, N] / [m] arrays.  A bad spot is reported through
+    its `status` (PK_EQ_* bits) with all-zero counts; the others are unaffected."""
+    holes = np.ascontiguousarray(holes, np.uint8)
+    if holes.ndim != 3 or holes.shape[2] != 2 or not (L.MIN_PLAYERS <= holes.shape[1] <= L.MAX_PLAYERS):
+        raise ValueError('holes must have shape [m, N, 2] with 2 <= N <= 16')
+    m, n = holes.shape[:2]
+    board = np.ascontiguousarray(board, np.uint8)
+    nboard = np.ascontiguousarray(nboard, np.uint8)
+    live = np.ascontiguousarray(live, np.uint16)
+    if board.shape != (m, 5) or nboard.shape != (m,) or live.shape != (m,):
+        raise ValueError('board must have shape [m, 5], nboard and live shape [m]')
+    win, tie = np.zeros((m, n), np.uint32), np.zeros((m, n), np.uint32)
+    share = np.zeros((m, n), np.uint64)
+    boards, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+    L.check(L.lib().pk_equity(int(device), n, m, L.ptr(holes), L.ptr(board), L.ptr(nboard), L.ptr(live), L.ptr(win), L.ptr(tie), L.ptr(share),
+                              L.ptr(boards), L.ptr(status)))
+    return Equity(win, tie, share, boards, status)
+
+
+def showdown_equity_d(num_players, m, holes_d, board_d, nboard_d, live_d, win_d=None, tie_d=None, share_d=None, boards_d=None, status_d=None,
+                      device=0, stream=None):
+    """pk_equity_d: the same on device-resident buffers (device pointers as ints / c_void_p; outputs may be None), asynchronous on `stream`."""
+    L.check(L.lib().pk_equity_d(int(device), int(num_players), int(m), holes_d, board_d, nboard_d, live_d, win_d, tie_d, share_d, boards_d,
+                                status_d, stream))
+
+
+def _card(c):
+    try:
+        return card_value(c)
+    except (AssertionError, KeyError, IndexError) as e:
+        raise ValueError('not a card: %r' % (c,)) from e
+
+
+def showdown_equity(hands, board=(), live=None, device=0):
+    """One spot.  hands: per seat two cards (Card-likes / 'RS' strings / Card.value ints), or None for a seat whose cards are unknown (it
+    cannot be live); board: 0 .. 5 known cards; live: the seats that show down (iterable of seat numbers or a bit mask; default: every seat
+    with cards).  Returns an Equity with [N] arrays; raises ValueError for an invalid spot."""
+    hands = list(hands)
+    n = len(hands)
+    if not (L.MIN_PLAYERS <= n <= L.MAX_PLAYERS):
+        raise ValueError('between 2 and 16 seats')
+    board = list(board)
+    if len(board) > 5:
+        raise ValueError('at most five board cards')
+    holes = np.full((1, n, 2), UNKNOWN_CARD, np.uint8)
+    for p, h in enumerate(hands):
+        if h is None:
+            continue
+        h = list(h)
+        if len(h) != 2:
+            raise ValueError('seat %d: two hole cards (or None)' % p)
+        holes[0, p] = [_card(c) for c in h]
+    b = np.zeros((1, 5), np.uint8)
+    b[0, :len(board)] = [_card(c) for c in board]
+    if live is None:
+        mask = sum(1 << p for p, h in enumerate(hands) if h is not None)
+    elif isinstance(live, (int, np.integer)):
+        mask = int(live)
+    else:
+        mask = 0
+        for p in live:
+            if not 0 <= int(p) < n:
+                raise ValueError('live seat %r out of range' % (p,))
+            mask |= 1 << int(p)
+    if mask < 0 or mask >> n:
+        raise ValueError('live mask names seats >= %d' % n)
+    r = showdown_equity_batch(holes, b, np.array([len(board)], np.uint8), np.array([mask], np.uint16), device)[0]
+    if r.status:
+        raise ValueError('invalid spot: ' + equity_status_text(r.status))
+    return r

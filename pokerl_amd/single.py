@@ -91,6 +91,14 @@ class Game:
     def reset(self, **config):                                                    # :397-412
         self._v.reset(**config)
 
+    def equity(self):
+        """Showdown equity of the table as it stands (VecGame.equity): a judger.Equity with [N] arrays.  Not in the reference."""
+        r = self._v.equity()[0]
+        if r.status:
+            from .judger import equity_status_text
+            raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
+        return r
+
     def step(self, action):                                                       # :621-700
         """Returns (game_over, hand_over, turn_over); raises the reference's ValueError / NotImplementedError /
         AssertionError in the reference's situations."""

@@ -35,6 +35,91 @@ static int env_int(const char *name, int lo, int hi, int fallback) {
     return v >= lo && v <= hi ? v : fallback;
 }
 
+// A per-device cache of device memory (the stream pool's canary, the judger's scratch arena, the evaluator table) outlives its allocation when the
+// application resets the device: a kernel launched on such a pointer would fault, a pooled stream handle dangles.  The seat belt: look the ADDRESS
+// up before trusting it -- hipMemGetAddressRange looks it up in the runtime's allocation map, no dereference of a dead object.  The allocator hands
+// the same addresses out again after a reset (measured: the evaluator table's address came back as the next handle's arena), so base AND size must
+// match -- and every cached allocation has an odd size (PK_ODD_BYTES more than it needs) that no caller is likely to ask for.  Not impossible, so
+// pk_stream_pool_drain before hipDeviceReset remains the rule.
+#define PK_ODD_BYTES 272
+namespace {   // (helpers of this file: no symbols of theirs in the library)
+// A grow-only device buffer that outlives the call: THE way to device memory besides a handle's arena.  Each user keeps its own lock,
+// stream and head-room rule (`grow_to`: the capacity to allocate when `bytes` do not fit).
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    hipError_t err = hipSuccess;   // of the last allocation
+    // `queued`: the stream whose work may still use the old buffer -- waited for before that is freed.  cache: a per-device cache (above),
+    // forgotten and not freed once the device was reset.  NULL: out of memory (the sticky HIP error cleared), and the buffer is empty.
+    void *reserve(size_t bytes, size_t grow_to, hipStream_t queued, bool cache = false) {
+        if (cache && !alive()) *this = DevBuf{};
+        if (p && cap >= bytes) return p;
+        if (p && hipStreamSynchronize(queued) != hipSuccess) (void)hipGetLastError();
+        drop();
+        err = hipMalloc(&p, grow_to + (cache ? PK_ODD_BYTES : 0));
+        if (err != hipSuccess) { (void)hipGetLastError(); p = nullptr; return nullptr; }
+        cap = grow_to;
+        return p;
+    }
+    bool alive() const {   // a per-device cache: it is allocated, and the allocation still exists
+        if (!p) return false;
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        const hipError_t e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
+        if (e != hipSuccess) (void)hipGetLastError();
+        return e == hipSuccess && (const void *)base == p && size == cap + PK_ODD_BYTES;
+    }
+    void drop() {   // frees without waiting for a stream (hipFree waits for the device)
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+};
+// the head room of the per-device caches: at least 1 MiB, else 1/div more than asked for
+static inline size_t with_headroom(size_t bytes, int div) { return bytes < (1u << 20) ? (1u << 20) : bytes + bytes / div; }
+// Staging of a call on host arrays in ONE device buffer: name the pieces (each 256-byte aligned), reserve `total` bytes, set `base`, then
+// upload(), launch on at<T>(piece), download() -- or run(), which is the three.  An optional array the caller left out (in / out with a
+// NULL host pointer) gets no piece: at() gives the kernel NULL for it, and nothing is copied.
+struct Stage {
+    struct Piece { size_t off, bytes; const void *src; void *dst; };
+    std::vector<Piece> pieces;
+    size_t total = 0;
+    char *base = nullptr;
+    int add(size_t bytes, const void *src = nullptr, void *dst = nullptr) {   // src: host array to upload from, dst: to download into
+        pieces.push_back(Piece{total, bytes, src, dst});
+        total += (bytes + 255) & ~(size_t)255;
+        return (int)pieces.size() - 1;
+    }
+    int in(const void *host, size_t bytes) { return host ? add(bytes, host) : -1; }
+    int out(void *host, size_t bytes) { return host ? add(bytes, nullptr, host) : -1; }
+    template <typename T> T *at(int piece) const { return piece < 0 ? nullptr : (T *)(base + pieces[(size_t)piece].off); }
+    // The copies are queued on `stream` up to the first HIP error; download() then waits for the stream.
+    hipError_t upload(hipStream_t stream) const {
+        hipError_t e = hipSuccess;
+        for (const Piece &c : pieces)
+            if (e == hipSuccess && c.src) e = hipMemcpyAsync(base + c.off, c.src, c.bytes, hipMemcpyHostToDevice, stream);
+        return e;
+    }
+    hipError_t download(hipStream_t stream) const {
+        hipError_t e = hipSuccess;
+        for (const Piece &c : pieces)
+            if (e == hipSuccess && c.dst) e = hipMemcpyAsync(c.dst, base + c.off, c.bytes, hipMemcpyDeviceToHost, stream);
+        return e == hipSuccess ? hipStreamSynchronize(stream) : e;
+    }
+    template <typename F> hipError_t run(hipStream_t stream, F launch) const {   // launch(): queues the kernels, returns their HIP error
+        hipError_t e = upload(stream);
+        if (e == hipSuccess) e = launch();
+        return e == hipSuccess ? download(stream) : e;
+    }
+};
+// The count outputs an equity call on host arrays wants, as pieces of its staging
+struct EqStagedOut {
+    int win, tie, share, boards, status;
+    EqStagedOut(Stage &g, int N, size_t m, uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards, uint8_t *status)
+        : win(g.out(win, m * N * 4)), tie(g.out(tie, m * N * 4)), share(g.out(share, m * N * 8)), boards(g.out(boards, m * 4)), status(g.out(status, m)) {}
+    EqOut at(const Stage &g) const { return EqOut{g.at<uint32_t>(win), g.at<uint32_t>(tie), g.at<uint64_t>(share), g.at<uint32_t>(boards), g.at<uint8_t>(status)}; }
+};
+}  // namespace
+
 struct pk_handle {
     int device = 0, T = 0, N = 0, dealer = 0;
     int tpb = 64;   // tables per wavefront (Hot::tpb)
@@ -97,7 +182,7 @@ struct pk_handle {
     void *d_export = nullptr;
     size_t export_bytes = 0;
     uint8_t *h_pinned = nullptr;  // [T] pinned: per-table error bytes of pk_step / pk_env_step
-    uint8_t *d_obs_packed = nullptr;     // [T][PK_OBS_PACKED_BYTES(N)]: device staging of pk_env_step_begin (allocated on first use)
+    DevBuf d_obs_packed;                 // [T][PK_OBS_PACKED_BYTES(N)]: device staging of pk_env_step_begin (allocated on first use)
     uint8_t *env_obs_packed = nullptr;   // pk_set_env_obs_packed: device buffer [T][PK_OBS_PACKED_BYTES(N)] or NULL
     double *step_obs = nullptr;          // pk_set_step_obs: device buffers the Game.step kernels write the row of the player to act into, or NULL
     uint8_t *step_obs_packed = nullptr;
@@ -105,8 +190,7 @@ struct pk_handle {
     // duplicate / overlap checks of destination indices, a grow-only staging buffer (host-memory calls, overlapping clones) and the event
     // that orders a clone between two handles' streams
     uint32_t *snap_word = nullptr, *snap_mark = nullptr;
-    void *snap_stage = nullptr;
-    size_t snap_stage_bytes = 0;
+    DevBuf snap_stage;
     hipEvent_t snap_ev = nullptr;
     std::string err;
     int fail(int code, const char *what, hipError_t e = hipSuccess) {
@@ -306,28 +390,12 @@ static int pool_class(bool sub_batch) {
     static const bool prio = env_int("PK_ENV_STREAM_PRIO", INT_MIN, INT_MAX, 1) != 0;
     return (sub_batch && prio) ? 1 : 0;
 }
-// A per-device cache of device memory (the stream pool's canary, the judger's scratch arena, the evaluator table) outlives its allocation when the
-// application resets the device: a kernel launched on such a pointer would fault, a pooled stream handle dangles.  The seat belt: look the ADDRESS
-// up before trusting it -- hipMemGetAddressRange looks it up in the runtime's allocation map, no dereference of a dead object.  The allocator hands
-// the same addresses out again after a reset (measured: the evaluator table's address came back as the next handle's arena), so base AND size must
-// match -- and every cached allocation has an odd size (PK_ODD_BYTES more than it needs) that no caller is likely to ask for.  Not impossible, so
-// pk_stream_pool_drain before hipDeviceReset remains the rule.
-#define PK_ODD_BYTES 272
-static bool dev_alloc_alive(const void *p, size_t bytes) {
-    if (!p) return false;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    const hipError_t e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
-    if (e != hipSuccess) (void)hipGetLastError();
-    return e == hipSuccess && (const void *)base == p && size == bytes;
-}
 // How the pool notices a device reset WITHOUT touching a pooled (then dangling) stream handle: a small device allocation made when the first stream
 // of a device is pooled.
-static void *g_pool_canary[PK_MAX_DEVICES];
-static const size_t POOL_CANARY_BYTES = 4096 + PK_ODD_BYTES;
+static DevBuf g_pool_canary[PK_MAX_DEVICES];
 static bool pool_alive(int device) {   // caller holds g_stream_mu and has the device current
-    const bool ok = dev_alloc_alive(g_pool_canary[device], POOL_CANARY_BYTES);
-    if (!ok) g_pool_canary[device] = nullptr;          // (not freed: it no longer exists)
+    const bool ok = g_pool_canary[device].alive();
+    if (!ok) g_pool_canary[device] = DevBuf{};          // (not freed: it no longer exists)
     return ok;
 }
 static hipError_t stream_acquire(int device, hipStream_t *out, bool sub_batch = false) {   // the device is current
@@ -359,9 +427,9 @@ static void stream_release(int device, hipStream_t s, bool sub_batch = false) { 
     }
     if (device >= 0 && device < PK_MAX_DEVICES) {
         std::lock_guard<std::mutex> lock(g_stream_mu);
-        if (!g_pool_canary[device]) {                  // the pool's reset detector (pool_alive); without one the stream is not pooled
+        if (!g_pool_canary[device].p) {                // the pool's reset detector (pool_alive); without one the stream is not pooled
             for (int c = 0; c < 2; ++c) g_stream_pool[device][c].clear();    // (whatever was pooled under an earlier, vanished canary is stale)
-            if (hipMalloc(&g_pool_canary[device], POOL_CANARY_BYTES) != hipSuccess) { (void)hipGetLastError(); g_pool_canary[device] = nullptr; (void)hipStreamDestroy(s); return; }
+            if (!g_pool_canary[device].reserve(4096, 4096, s, true)) { (void)hipStreamDestroy(s); return; }
         }
         g_stream_pool[device][pool_class(sub_batch)].push_back(s);
     } else (void)hipStreamDestroy(s);
@@ -383,11 +451,11 @@ static int drain_stream_pool(int device) {
             (void)hipGetLastError();
             pool.clear();
         }
-        if (g_pool_canary[d] && g_stream_pool[d][0].empty() && g_stream_pool[d][1].empty()) {
+        if (g_pool_canary[d].p && g_stream_pool[d][0].empty() && g_stream_pool[d][1].empty()) {
             DeviceGuard guard(d);
-            if (guard.ok && pool_alive(d)) (void)hipFree(g_pool_canary[d]);
+            if (guard.ok && pool_alive(d)) g_pool_canary[d].drop();
             (void)hipGetLastError();
-            g_pool_canary[d] = nullptr;
+            g_pool_canary[d] = DevBuf{};
         }
     }
     return n;
@@ -591,10 +659,10 @@ int pk_destroy(pk_handle *h) {
     DeviceGuard guard(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->arena) (void)hipFree(h->arena);
-    if (h->d_obs_packed) (void)hipFree(h->d_obs_packed);
+    h->d_obs_packed.drop();
     if (h->snap_word) (void)hipFree(h->snap_word);
     if (h->snap_mark) (void)hipFree(h->snap_mark);
-    if (h->snap_stage) (void)hipFree(h->snap_stage);
+    h->snap_stage.drop();
     if (h->snap_ev) (void)hipEventDestroy(h->snap_ev);
     if (h->h_pinned) (void)hipHostFree(h->h_pinned);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1293,13 +1361,12 @@ int pk_env_step_begin(pk_handle *h, const int32_t *actions, int opp_policy, int 
     FLUSH(h);
     const size_t T = (size_t)h->T, D = (size_t)PK_OBS_DIM(h->N), PB = (size_t)PK_OBS_PACKED_BYTES(h->N);
     if (obs && T * D * 8 > h->export_bytes) return h->fail(PK_E_INVALID_ARG, "export buffer too small");
-    if (obs_packed && !h->d_obs_packed) {
-        HIPCHK(h, hipMalloc((void **)&h->d_obs_packed, T * PB));
-    }
+    uint8_t *d_packed = obs_packed ? (uint8_t *)h->d_obs_packed.reserve(T * PB, T * PB, h->stream) : nullptr;
+    if (obs_packed && !d_packed) return h->fail(PK_E_HIP, "hipMalloc((void **)&h->d_obs_packed, T * PB)", h->d_obs_packed.err);
     HIPCHK(h, hipMemcpyAsync(h->d_actions, actions, T * 4, hipMemcpyHostToDevice, h->stream));
     EnvKernArgs ka = env_args(h, h->d_actions, -1, uniform_seats(opp_policy), auto_reset ? 1 : 0, h->d_reward, h->d_done, h->d_handf, h->d_terr,
                               obs ? (double *)h->d_export : nullptr);
-    ka.A.obs_packed = obs_packed ? h->d_obs_packed : nullptr;
+    ka.A.obs_packed = d_packed;
     if (int rc = seat_launch(h, SEAT_KERNEL(k_env_step, env_grid(h), h->stream, ka))) return rc;
     // Busy from HERE on: if one of the copies below fails to queue, the earlier ones are already queued into the caller's buffers, and
     // pk_env_step_end is the caller's sanctioned way to wait for them (round 5 set the flag after the last copy: ADVICE r05).
@@ -1309,7 +1376,7 @@ int pk_env_step_begin(pk_handle *h, const int32_t *actions, int opp_policy, int 
     HIPCHK(h, hipMemcpyAsync(hand, h->d_handf, T, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(terr, h->d_terr, T, hipMemcpyDeviceToHost, h->stream));
     if (obs) HIPCHK(h, hipMemcpyAsync(obs, h->d_export, T * D * 8, hipMemcpyDeviceToHost, h->stream));
-    if (obs_packed) HIPCHK(h, hipMemcpyAsync(obs_packed, h->d_obs_packed, T * PB, hipMemcpyDeviceToHost, h->stream));
+    if (obs_packed) HIPCHK(h, hipMemcpyAsync(obs_packed, d_packed, T * PB, hipMemcpyDeviceToHost, h->stream));
     return PK_OK;
 }
 
@@ -1351,17 +1418,9 @@ static int snap_prepare(pk_handle *h) {   // the refusal word, the per-table mar
     if (!h->snap_ev) HIPCHK(h, hipEventCreateWithFlags(&h->snap_ev, hipEventDisableTiming));
     return PK_OK;
 }
-static int snap_staging(pk_handle *h, size_t bytes, char **out) {   // grow-only; a buffer in use by queued work is waited for before it is freed
-    if (bytes > h->snap_stage_bytes) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->snap_stage) (void)hipFree(h->snap_stage);
-        h->snap_stage = nullptr; h->snap_stage_bytes = 0;
-        const hipError_t e = hipMalloc(&h->snap_stage, bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); h->snap_stage = nullptr; return h->fail(PK_E_OOM, "snapshot staging buffer", e); }
-        h->snap_stage_bytes = bytes;
-    }
-    *out = (char *)h->snap_stage;
-    return PK_OK;
+static int snap_staging(pk_handle *h, size_t bytes, char **out) {   // grow-only, exactly as large as the largest call so far
+    *out = (char *)h->snap_stage.reserve(bytes, bytes, h->stream);
+    return *out ? PK_OK : h->fail(PK_E_OOM, "snapshot staging buffer", h->snap_stage.err);
 }
 static SnapHeader snap_header_of(const pk_handle *h, size_t m) {
     SnapHeader hd{};
@@ -1418,17 +1477,18 @@ static int snap_save(pk_handle *h, const int32_t *tables_d, size_t m, void *blob
                         snap_header_of(h, m), blob_d, pads));
     return PK_OK;
 }
-static int snap_load(pk_handle *h, const int32_t *tables_d, size_t m, const void *blob_d, const char *call) {
+// May the blob that starts with `hd` be loaded into m tables of h?
+static int snap_check_header(pk_handle *h, const SnapHeader &hd, size_t m, const char *call) {
     const std::string c(call);
-    if ((uintptr_t)blob_d & 7) return h->fail(PK_E_INVALID_ARG, (c + ": blob must be 8-byte aligned").c_str());
-    SnapHeader hd{};
-    HIPCHK(h, hipMemcpyAsync(&hd, blob_d, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
     if (hd.magic != SNAP_MAGIC || hd.version != SNAP_VERSION) return h->fail(PK_E_INVALID_ARG, (c + ": not a snapshot of this format (magic / version)").c_str());
     if (hd.num_players != (uint32_t)h->N) return h->fail(PK_E_INVALID_ARG, (c + ": the blob holds tables of another number of seats").c_str());
     if (!snap_same_money(h, hd)) return h->fail(PK_E_INVALID_ARG, (c + ": the blob's start credits or blinds differ from the handle's").c_str());
     if (hd.m != m) return h->fail(PK_E_INVALID_ARG, (c + ": m differs from the blob's record count").c_str());
     if (m > (size_t)h->T) return h->fail(PK_E_INVALID_ARG, (c + ": more records than the handle has tables").c_str());
+    return PK_OK;
+}
+// (the caller has checked the blob's header: snap_check_header)
+static int snap_load(pk_handle *h, const int32_t *tables_d, size_t m, const void *blob_d, const char *call) {
     int rc = snap_prepare(h);
     if (rc) return rc;
     SnapView blob;
@@ -1447,58 +1507,53 @@ size_t pk_snapshot_bytes(int num_players, size_t m) {
     return snap_layout(num_players, m, nullptr, nullptr);
 }
 
+// The opening of the four save / load entry points (m == 0: nothing to do, once the handle has been flushed)
+#define SNAP_ENTER(h, blob, m, call)                                                                      \
+    if (!(h) || !(blob)) return (h) ? (h)->fail(PK_E_INVALID_ARG, call ": NULL blob") : PK_E_INVALID_ARG; \
+    ON_DEVICE(h);                                                                                         \
+    FLUSH(h);                                                                                             \
+    if ((m) == 0) return PK_OK
+
 int pk_save_tables_d(pk_handle *h, const int32_t *tables_d, size_t m, void *blob_d) {
-    if (!h || !blob_d) return h ? h->fail(PK_E_INVALID_ARG, "pk_save_tables_d: NULL blob") : PK_E_INVALID_ARG;
-    ON_DEVICE(h);
-    FLUSH(h);
-    if (m == 0) return PK_OK;
+    SNAP_ENTER(h, blob_d, m, "pk_save_tables_d");
     return snap_save(h, tables_d, m, blob_d, "pk_save_tables_d");
 }
 
 int pk_load_tables_d(pk_handle *h, const int32_t *tables_d, size_t m, const void *blob_d) {
-    if (!h || !blob_d) return h ? h->fail(PK_E_INVALID_ARG, "pk_load_tables_d: NULL blob") : PK_E_INVALID_ARG;
-    ON_DEVICE(h);
-    FLUSH(h);
-    if (m == 0) return PK_OK;
+    SNAP_ENTER(h, blob_d, m, "pk_load_tables_d");
+    if ((uintptr_t)blob_d & 7) return h->fail(PK_E_INVALID_ARG, "pk_load_tables_d: blob must be 8-byte aligned");
+    SnapHeader hd{};
+    HIPCHK(h, hipMemcpyAsync(&hd, blob_d, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (int rc = snap_check_header(h, hd, m, "pk_load_tables_d")) return rc;
     return snap_load(h, tables_d, m, blob_d, "pk_load_tables_d");
 }
 
 int pk_save_tables(pk_handle *h, const int32_t *tables, size_t m, void *blob) {
-    if (!h || !blob) return h ? h->fail(PK_E_INVALID_ARG, "pk_save_tables: NULL blob") : PK_E_INVALID_ARG;
-    ON_DEVICE(h);
-    FLUSH(h);
-    if (m == 0) return PK_OK;
+    SNAP_ENTER(h, blob, m, "pk_save_tables");
     if (!tables && m > (size_t)h->T) return h->fail(PK_E_INVALID_ARG, "pk_save_tables: tables NULL and m > the handle's tables");   // (before staging)
-    const size_t idx_bytes = tables ? snap_align(m * 4) : 0, bytes = pk_snapshot_bytes(h->N, m);
-    char *stage = nullptr;
-    int rc = snap_staging(h, idx_bytes + bytes, &stage);
+    Stage g;
+    const int idx = g.in(tables, m * 4), rec = g.out(blob, pk_snapshot_bytes(h->N, m));
+    int rc = snap_staging(h, g.total, &g.base);
     if (rc) return rc;
-    if (tables) HIPCHK(h, hipMemcpyAsync(stage, tables, m * 4, hipMemcpyHostToDevice, h->stream));
-    if ((rc = snap_save(h, tables ? (const int32_t *)stage : nullptr, m, stage + idx_bytes, "pk_save_tables"))) return rc;
-    HIPCHK(h, hipMemcpyAsync(blob, stage + idx_bytes, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, g.upload(h->stream));
+    if ((rc = snap_save(h, g.at<int32_t>(idx), m, g.at<char>(rec), "pk_save_tables"))) return rc;
+    HIPCHK(h, g.download(h->stream));
     return PK_OK;
 }
 
 int pk_load_tables(pk_handle *h, const int32_t *tables, size_t m, const void *blob) {
-    if (!h || !blob) return h ? h->fail(PK_E_INVALID_ARG, "pk_load_tables: NULL blob") : PK_E_INVALID_ARG;
-    ON_DEVICE(h);
-    FLUSH(h);
-    if (m == 0) return PK_OK;
+    SNAP_ENTER(h, blob, m, "pk_load_tables");
     // the header first, from host memory: it says how many bytes the caller's blob holds
     SnapHeader hd;
     memcpy(&hd, blob, sizeof(hd));
-    if (hd.magic != SNAP_MAGIC || hd.version != SNAP_VERSION) return h->fail(PK_E_INVALID_ARG, "pk_load_tables: not a snapshot of this format (magic / version)");
-    if (hd.num_players != (uint32_t)h->N) return h->fail(PK_E_INVALID_ARG, "pk_load_tables: the blob holds tables of another number of seats");
-    if (hd.m != m) return h->fail(PK_E_INVALID_ARG, "pk_load_tables: m differs from the blob's record count");
-    if (m > (size_t)h->T) return h->fail(PK_E_INVALID_ARG, "pk_load_tables: more records than the handle has tables");
-    const size_t idx_bytes = tables ? snap_align(m * 4) : 0, bytes = pk_snapshot_bytes(h->N, m);
-    char *stage = nullptr;
-    int rc = snap_staging(h, idx_bytes + bytes, &stage);
+    int rc = snap_check_header(h, hd, m, "pk_load_tables");
     if (rc) return rc;
-    if (tables) HIPCHK(h, hipMemcpyAsync(stage, tables, m * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(stage + idx_bytes, blob, bytes, hipMemcpyHostToDevice, h->stream));
-    if ((rc = snap_load(h, tables ? (const int32_t *)stage : nullptr, m, stage + idx_bytes, "pk_load_tables"))) return rc;
+    Stage g;
+    const int idx = g.in(tables, m * 4), rec = g.in(blob, pk_snapshot_bytes(h->N, m));
+    if ((rc = snap_staging(h, g.total, &g.base))) return rc;
+    HIPCHK(h, g.upload(h->stream));
+    if ((rc = snap_load(h, g.at<int32_t>(idx), m, g.at<char>(rec), "pk_load_tables"))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return PK_OK;
 }
@@ -1565,19 +1620,9 @@ int pk_clone_tables_d(pk_handle *dst, const int32_t *dst_tables_d, pk_handle *sr
 // ---- standalone judger ops (no handle)
 // Grow-only device scratch of the host-buffer judger calls, one per device: no hipMalloc / hipFree per call.
 static std::mutex g_scratch_mu;
-static struct { void *p; size_t cap; } g_scratch[PK_MAX_DEVICES];
-static void *scratch(int device, size_t bytes) {  // caller holds g_scratch_mu and has the device current
-    auto &s = g_scratch[device];
-    if (s.p && !dev_alloc_alive(s.p, s.cap + PK_ODD_BYTES)) { s.p = nullptr; s.cap = 0; }      // (the device was reset: the arena is gone, not freed)
-    if (s.cap < bytes) {
-        if (s.p) (void)hipFree(s.p);
-        s.p = nullptr; s.cap = 0;
-        size_t want = bytes < (1u << 20) ? (1u << 20) : bytes + bytes / 2;
-        if (hipMalloc(&s.p, want + PK_ODD_BYTES) != hipSuccess) { (void)hipGetLastError(); s.p = nullptr; return nullptr; }
-        s.cap = want;
-    }
-    return s.p;
-}
+static DevBuf g_scratch[PK_MAX_DEVICES];
+// Caller holds g_scratch_mu, has the device current and waits for its own work on `stream` before it lets go of the lock.
+static char *scratch(int device, size_t bytes, hipStream_t stream) { return (char *)g_scratch[device].reserve(bytes, with_headroom(bytes, 2), stream, true); }
 
 // pk_eval_hands(_d)'s launch: the table path (k_eval_hands_tab); the register evaluator if the table could not be allocated.
 // tab: eval7_table(device), fetched by the caller BEFORE it takes g_scratch_mu.
@@ -1610,21 +1655,11 @@ int pk_eval_hands(int device, const uint8_t *cards, const uint8_t *ncards, size_
     if (m == 0) return PK_OK;
     const uint32_t *tab = eval7_table(device);   // (takes g_scratch_mu itself)
     std::lock_guard<std::mutex> lock(g_scratch_mu);
-    size_t off_n = m * 7, off_r = off_n + m, off_nk = off_r + m, off_k = (off_nk + m + 3) & ~(size_t)3, total = off_k + m * 4;
-    uint8_t *d = (uint8_t *)scratch(device, total);
-    if (!d) return g_fail(PK_E_OOM, "pk_eval_hands: out of device memory");
-    hipError_t e = hipMemcpyAsync(d, cards, m * 7, hipMemcpyHostToDevice, 0);
-    if (e == hipSuccess && ncards) e = hipMemcpyAsync(d + off_n, ncards, m, hipMemcpyHostToDevice, 0);
-    if (e == hipSuccess) {
-        launch_eval_hands(tab, d, ncards ? d + off_n : nullptr, m, d + off_r, (uint32_t *)(d + off_k), d + off_nk, 0);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(rank, d + off_r, m, hipMemcpyDeviceToHost, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(kick, d + off_k, m * 4, hipMemcpyDeviceToHost, 0);
-    if (e == hipSuccess && nkick) e = hipMemcpyAsync(nkick, d + off_nk, m, hipMemcpyDeviceToHost, 0);
-    if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_eval_hands", e);
-    return PK_OK;
+    Stage g;
+    const int c = g.in(cards, m * 7), nc = g.in(ncards, m), r = g.out(rank, m), k = g.out(kick, m * 4), nk = g.out(nkick, m);
+    if (!(g.base = scratch(device, g.total, 0))) return g_fail(PK_E_OOM, "pk_eval_hands: out of device memory");
+    const hipError_t e = g.run(0, [&] { launch_eval_hands(tab, g.at<uint8_t>(c), g.at<uint8_t>(nc), m, g.at<uint8_t>(r), g.at<uint32_t>(k), g.at<uint8_t>(nk), 0); return hipGetLastError(); });
+    return e == hipSuccess ? PK_OK : g_fail(PK_E_HIP, "pk_eval_hands", e);
 }
 
 int pk_compare_rankings(int device, const uint8_t *rank, const uint32_t *kick, int n, size_t m, uint8_t *onehot) {
@@ -1632,36 +1667,31 @@ int pk_compare_rankings(int device, const uint8_t *rank, const uint32_t *kick, i
     ON_DEVICE_INDEX("pk_compare_rankings", device, PK_MAX_DEVICES);
     if (m == 0) return PK_OK;
     std::lock_guard<std::mutex> lock(g_scratch_mu);
-    size_t cnt = m * (size_t)n;
-    size_t off_r = cnt * 4, off_o = off_r + cnt, total = off_o + cnt;
-    uint8_t *d = (uint8_t *)scratch(device, total);
-    if (!d) return g_fail(PK_E_OOM, "pk_compare_rankings: out of device memory");
-    hipError_t e = hipMemcpyAsync(d, kick, cnt * 4, hipMemcpyHostToDevice, 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + off_r, rank, cnt, hipMemcpyHostToDevice, 0);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_compare, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, d + off_r, (const uint32_t *)d, n, m, d + off_o);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(onehot, d + off_o, cnt, hipMemcpyDeviceToHost, 0);
-    if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_compare_rankings", e);
-    return PK_OK;
+    const size_t cnt = m * (size_t)n;
+    Stage g;
+    const int k = g.in(kick, cnt * 4), r = g.in(rank, cnt), o = g.out(onehot, cnt);
+    if (!(g.base = scratch(device, g.total, 0))) return g_fail(PK_E_OOM, "pk_compare_rankings: out of device memory");
+    const hipError_t e = g.run(0, [&] {
+        hipLaunchKernelGGL(k_compare, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, g.at<uint8_t>(r), (const uint32_t *)g.at<uint32_t>(k), n, m, g.at<uint8_t>(o));
+        return hipGetLastError();
+    });
+    return e == hipSuccess ? PK_OK : g_fail(PK_E_HIP, "pk_compare_rankings", e);
 }
 
 // The 32 KB table of the table-driven evaluator (eval7_tab), one per device, built on first use.
-static uint32_t *g_eval_tab[PK_MAX_DEVICES];
+static DevBuf g_eval_tab[PK_MAX_DEVICES];
 static const uint32_t *eval7_table(int device, hipStream_t stream) {   // the device is current
     if (device < 0 || device >= PK_MAX_DEVICES) return nullptr;
     std::lock_guard<std::mutex> lock(g_scratch_mu);
-    if (g_eval_tab[device] && !dev_alloc_alive(g_eval_tab[device], EVAL7_TAB_WORDS * 4 + PK_ODD_BYTES)) g_eval_tab[device] = nullptr;   // (the device was reset: build it again)
-    if (!g_eval_tab[device]) {
-        uint32_t *p = nullptr;
-        if (hipMalloc((void **)&p, EVAL7_TAB_WORDS * 4 + PK_ODD_BYTES) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    DevBuf &t = g_eval_tab[device];
+    if (!t.alive()) {   // (not yet there, or the device was reset: build it)
+        t = DevBuf{};
+        uint32_t *p = (uint32_t *)t.reserve(EVAL7_TAB_WORDS * 4, EVAL7_TAB_WORDS * 4, stream, true);
+        if (!p) return nullptr;
         hipLaunchKernelGGL(k_make_eval7_tab, dim3(EVAL7_TAB_WORDS / 256), dim3(256), 0, stream, p);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { (void)hipFree(p); return nullptr; }
-        g_eval_tab[device] = p;
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { t.drop(); return nullptr; }
     }
-    return g_eval_tab[device];
+    return (const uint32_t *)t.p;
 }
 
 static int launch_eval7(int device, const uint64_t *hands_d, size_t m, uint32_t *out_d, int distinct) {
@@ -1705,8 +1735,11 @@ int pk_make_hands_d(int device, uint64_t seed, size_t m, uint64_t *hands_d) {
 int pk_time_eval7_d(int device, const uint64_t *hands_d, size_t m, uint32_t *out_d, int distinct, int reps, double *ms_per_pass) {
     if (!hands_d || !out_d || !ms_per_pass || reps < 1) return g_fail(PK_E_INVALID_ARG, "pk_time_eval7_d: bad argument");
     ON_DEVICE_INDEX("pk_time_eval7_d", device, INT_MAX);
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return g_fail(PK_E_HIP, "hipEventCreate failed");
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+        if (e0) (void)hipEventDestroy(e0);
+        return g_fail(PK_E_HIP, "hipEventCreate failed");
+    }
     launch_eval7(device, hands_d, m, out_d, distinct);  // warm (instruction cache, clocks)
     (void)hipEventRecord(e0, 0);
     for (int r = 0; r < reps; ++r) launch_eval7(device, hands_d, m, out_d, distinct);
@@ -1732,7 +1765,7 @@ int pk_eval7_prefix(int device, int a, int b, int fast, uint32_t *out, size_t *c
     const uint32_t *tab = (fast == 2 || fast == 4) ? eval7_table(device) : nullptr;   // (takes g_scratch_mu itself)
     if ((fast == 2 || fast == 4) && !tab) return g_fail(PK_E_OOM, "pk_eval7_prefix: out of device memory");
     std::lock_guard<std::mutex> lock(g_scratch_mu);
-    uint32_t *d = (uint32_t *)scratch(device, count * 4);
+    uint32_t *d = (uint32_t *)scratch(device, count * 4, 0);
     if (!d) return g_fail(PK_E_OOM, "pk_eval7_prefix: out of device memory");
     hipLaunchKernelGGL(k_eval7_prefix, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, 0, a, b, fast, (uint32_t)count, d, tab);
     hipError_t e = hipGetLastError();
@@ -1755,40 +1788,40 @@ static bool eq_too_many_tasks(size_t m, int pool_max) { return eq_task_cap(m, eq
 // such a mapping the enumeration kernel found the task count still zero -- every third call of a 4 096-spot loop returned all-zero
 // counts (measured, ROCm 7.2).
 static const int EQ_WS_STREAMS = 8;
-struct EqStreamWs { hipStream_t stream; void *p; size_t cap; uint64_t used; };
+struct EqStreamWs { hipStream_t stream; DevBuf buf; uint64_t used; };
 static std::mutex g_eq_ws_mu;
 static std::vector<EqStreamWs> g_eq_ws[PK_MAX_DEVICES];
 static uint64_t g_eq_ws_clock;
 static void *eq_stream_ws(int device, hipStream_t st, size_t bytes) {   // the device is current and < PK_MAX_DEVICES
     std::lock_guard<std::mutex> lock(g_eq_ws_mu);
     auto &v = g_eq_ws[device];
-    for (size_t i = 0; i < v.size();)            // (buffers that vanished with a device reset are forgotten, not freed)
-        if (!dev_alloc_alive(v[i].p, v[i].cap + PK_ODD_BYTES)) v.erase(v.begin() + i); else ++i;
+    for (size_t i = 0; i < v.size();)            // (other streams' buffers that vanished with a device reset are forgotten, not freed; reserve sees to this stream's)
+        if (v[i].stream != st && !v[i].buf.alive()) v.erase(v.begin() + i); else ++i;
     EqStreamWs *hit = nullptr;
     for (auto &x : v) if (x.stream == st) hit = &x;
-    if (hit && hit->cap >= bytes) { hit->used = ++g_eq_ws_clock; return hit->p; }
-    if (hit) {                                   // too small: the calls queued on it so far must finish before it goes
-        if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
-        (void)hipFree(hit->p);
-        v.erase(v.begin() + (hit - v.data()));
-    } else if ((int)v.size() >= EQ_WS_STREAMS) {
-        size_t lru = 0;
-        for (size_t i = 1; i < v.size(); ++i) if (v[i].used < v[lru].used) lru = i;
-        (void)hipFree(v[lru].p);
-        v.erase(v.begin() + lru);
+    if (!hit) {
+        if ((int)v.size() >= EQ_WS_STREAMS) {
+            size_t lru = 0;
+            for (size_t i = 1; i < v.size(); ++i) if (v[i].used < v[lru].used) lru = i;
+            v[lru].buf.drop();
+            v.erase(v.begin() + lru);
+        }
+        v.push_back(EqStreamWs{st, DevBuf{}, 0});
+        hit = &v.back();
     }
-    const size_t cap = bytes < (1u << 20) ? (1u << 20) : bytes + bytes / 4;
-    void *p = nullptr;
-    if (hipMalloc(&p, cap + PK_ODD_BYTES) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    v.push_back(EqStreamWs{st, p, cap, ++g_eq_ws_clock});
-    return p;
+    hit->used = ++g_eq_ws_clock;
+    return hit->buf.reserve(bytes, with_headroom(bytes, 4), st, true);   // (too small: the calls queued on it so far finish before it goes)
 }
+
+// The argument checks the two explicit forms share (made before the device is looked at)
+#define EQ_CHECK_SPOTS(call, num_players, m, inputs)                                                                                                             \
+    if (eq_bad_seats(num_players) || (m) >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, call ": num_players outside 2 .. 16, or m >= 2^31");                   \
+    if ((m) && !(inputs)) return g_fail(PK_E_INVALID_ARG, call ": NULL input buffer");                                                                           \
+    if (eq_too_many_tasks(m, 50)) return g_fail(PK_E_INVALID_ARG, call EQ_TASKS_MSG)
 
 int pk_equity_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
                 const uint16_t *live_d, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *boards_d, uint8_t *status_d, void *stream) {
-    if (eq_bad_seats(num_players) || m >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, "pk_equity_d: num_players outside 2 .. 16, or m >= 2^31");
-    if (m && (!holes_d || !board_d || !nboard_d || !live_d)) return g_fail(PK_E_INVALID_ARG, "pk_equity_d: NULL input buffer");
-    if (eq_too_many_tasks(m, 50)) return g_fail(PK_E_INVALID_ARG, "pk_equity_d" EQ_TASKS_MSG);
+    EQ_CHECK_SPOTS("pk_equity_d", num_players, m, holes_d && board_d && nboard_d && live_d);
     ON_DEVICE_INDEX("pk_equity_d", device, PK_MAX_DEVICES);   // (the evaluator table is kept per device index below PK_MAX_DEVICES)
     if (m == 0) return PK_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -1805,42 +1838,9 @@ int pk_equity_d(int device, int num_players, size_t m, const uint8_t *holes_d, c
     return PK_OK;
 }
 
-// Device staging of a host-array call: the count outputs that are wanted, 256-byte aligned, after `in_bytes` of inputs
-struct EqStage {
-    size_t win, tie, share, boards, status, work, total;
-    EqStage(size_t in_bytes, int N, size_t m, size_t work_bytes) {
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        size_t off = al(in_bytes);
-        share = off; off += al(m * N * 8);
-        win = off; off += al(m * N * 4);
-        tie = off; off += al(m * N * 4);
-        boards = off; off += al(m * 4);
-        status = off; off += al(m);
-        work = off; total = off + work_bytes;
-    }
-};
-static hipError_t eq_fetch(hipStream_t st, const char *d, const EqStage &g, int N, size_t m, uint32_t *win, uint32_t *tie, uint64_t *share,
-                           uint32_t *boards, uint8_t *status) {
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess && win) e = hipMemcpyAsync(win, d + g.win, m * N * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && tie) e = hipMemcpyAsync(tie, d + g.tie, m * N * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && share) e = hipMemcpyAsync(share, d + g.share, m * N * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && boards) e = hipMemcpyAsync(boards, d + g.boards, m * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && status) e = hipMemcpyAsync(status, d + g.status, m, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    return e;
-}
-static EqOut eq_staged_out(char *d, const EqStage &g, const uint32_t *win, const uint32_t *tie, const uint64_t *share, const uint32_t *boards,
-                           const uint8_t *status) {
-    return EqOut{win ? (uint32_t *)(d + g.win) : nullptr, tie ? (uint32_t *)(d + g.tie) : nullptr, share ? (uint64_t *)(d + g.share) : nullptr,
-                 boards ? (uint32_t *)(d + g.boards) : nullptr, status ? (uint8_t *)(d + g.status) : nullptr};
-}
-
 int pk_equity(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
               uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards, uint8_t *status) {
-    if (eq_bad_seats(num_players) || m >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, "pk_equity: num_players outside 2 .. 16, or m >= 2^31");
-    if (m && (!holes || !board || !nboard || !live)) return g_fail(PK_E_INVALID_ARG, "pk_equity: NULL input buffer");
-    if (eq_too_many_tasks(m, 50)) return g_fail(PK_E_INVALID_ARG, "pk_equity" EQ_TASKS_MSG);
+    EQ_CHECK_SPOTS("pk_equity", num_players, m, holes && board && nboard && live);
     ON_DEVICE_INDEX("pk_equity", device, PK_MAX_DEVICES);
     if (m == 0) return PK_OK;
     const int N = num_players, lpt = eq_lpt(m);
@@ -1851,24 +1851,19 @@ int pk_equity(int device, int num_players, size_t m, const uint8_t *holes, const
     if (!tab) rc = g_fail(PK_E_OOM, "pk_equity: out of device memory (evaluator table)");
     else {
         std::lock_guard<std::mutex> lock(g_scratch_mu);
-        const size_t off_b = m * N * 2, off_n = off_b + m * 5, off_l = (off_n + m + 1) & ~(size_t)1;
-        const EqStage g(off_l + m * 2, N, m, eq_layout(N, m, lpt, 50, nullptr, nullptr));
-        char *d = (char *)scratch(device, g.total);
-        if (!d) rc = g_fail(PK_E_OOM, "pk_equity: out of device memory");
+        Stage g;
+        const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2);
+        const EqStagedOut out(g, N, m, win, tie, share, boards, status);
+        const int work = g.add(eq_layout(N, m, lpt, 50, nullptr, nullptr));
+        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity: out of device memory");
         else {
-            hipError_t e = hipMemcpyAsync(d, holes, m * N * 2, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(d + off_b, board, m * 5, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(d + off_n, nboard, m, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(d + off_l, live, m * 2, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) {
+            const hipError_t e = g.run(st, [&] {
                 EqWork w;
-                eq_layout(N, m, lpt, 50, d + g.work, &w);
-                const EqSpots spots{(const uint8_t *)d, (const uint8_t *)d + off_b, (const uint8_t *)d + off_n, (const uint16_t *)(d + off_l)};
-                e = eq_launch(st, tab, &spots, nullptr, N, m, eq_staged_out(d, g, win, tie, share, boards, status), w, lpt);
-            }
-            if (e == hipSuccess) e = eq_fetch(st, d, g, N, m, win, tie, share, boards, status);
-            else (void)hipStreamSynchronize(st);
-            if (e != hipSuccess) rc = g_fail(PK_E_HIP, "pk_equity", e);
+                eq_layout(N, m, lpt, 50, g.at<char>(work), &w);
+                const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
+                return eq_launch(st, tab, &spots, nullptr, N, m, out.at(g), w, lpt);
+            });
+            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity", e); }   // (the lock is held until what was queued is done)
         }
     }
     stream_release(device, st);
@@ -1886,36 +1881,35 @@ static int table_equity(pk_handle *h, const int32_t *tables_d, size_t m, const E
     HIPCHK(h, eq_launch(h->stream, tab, nullptr, &t, h->N, m, out, w, lpt));
     return PK_OK;
 }
+// The opening of the two table forms (m == 0: nothing to do, once the handle has been flushed)
+#define EQ_TABLE_ENTER(h, m, call)                                                                             \
+    if (!(h)) return PK_E_INVALID_ARG;                                                                         \
+    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                           \
+    if (eq_too_many_tasks(m, 52 - 2 * (h)->N)) return (h)->fail(PK_E_INVALID_ARG, call EQ_TASKS_MSG);          \
+    ON_DEVICE(h);                                                                                              \
+    FLUSH_READER(h);                                                                                           \
+    if ((m) == 0) return PK_OK
 
 int pk_table_equity_d(pk_handle *h, const int32_t *tables_d, size_t m, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *boards_d,
                       uint8_t *status_d) {
-    if (!h) return PK_E_INVALID_ARG;
-    if (m >= EQ_MAX_SPOTS) return h->fail(PK_E_INVALID_ARG, "pk_table_equity_d: m >= 2^31");
-    if (eq_too_many_tasks(m, 52 - 2 * h->N)) return h->fail(PK_E_INVALID_ARG, "pk_table_equity_d" EQ_TASKS_MSG);
-    ON_DEVICE(h);
-    FLUSH_READER(h);
-    if (m == 0) return PK_OK;
-    char *stage = nullptr;
-    const int rc = snap_staging(h, eq_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, nullptr, nullptr), &stage);
-    if (rc) return rc;
-    return table_equity(h, tables_d, m, EqOut{win_d, tie_d, share_d, boards_d, status_d}, stage);
+    EQ_TABLE_ENTER(h, m, "pk_table_equity_d");
+    char *work = nullptr;
+    if (int rc = snap_staging(h, eq_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, nullptr, nullptr), &work)) return rc;
+    return table_equity(h, tables_d, m, EqOut{win_d, tie_d, share_d, boards_d, status_d}, work);
 }
 
 int pk_table_equity(pk_handle *h, const int32_t *tables, size_t m, uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards,
                     uint8_t *status) {
-    if (!h) return PK_E_INVALID_ARG;
-    if (m >= EQ_MAX_SPOTS) return h->fail(PK_E_INVALID_ARG, "pk_table_equity: m >= 2^31");
-    if (eq_too_many_tasks(m, 52 - 2 * h->N)) return h->fail(PK_E_INVALID_ARG, "pk_table_equity" EQ_TASKS_MSG);
-    ON_DEVICE(h);
-    FLUSH_READER(h);
-    if (m == 0) return PK_OK;
-    const EqStage g(tables ? m * 4 : 0, h->N, m, eq_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, nullptr, nullptr));
-    char *d = nullptr;
-    int rc = snap_staging(h, g.total, &d);
+    EQ_TABLE_ENTER(h, m, "pk_table_equity");
+    Stage g;
+    const int idx = g.in(tables, m * 4);
+    const EqStagedOut out(g, h->N, m, win, tie, share, boards, status);
+    const int work = g.add(eq_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, nullptr, nullptr));
+    int rc = snap_staging(h, g.total, &g.base);
     if (rc) return rc;
-    if (tables) HIPCHK(h, hipMemcpyAsync(d, tables, m * 4, hipMemcpyHostToDevice, h->stream));
-    if ((rc = table_equity(h, tables ? (const int32_t *)d : nullptr, m, eq_staged_out(d, g, win, tie, share, boards, status), d + g.work))) return rc;
-    HIPCHK(h, eq_fetch(h->stream, d, g, h->N, m, win, tie, share, boards, status));
+    HIPCHK(h, g.upload(h->stream));
+    if ((rc = table_equity(h, g.at<int32_t>(idx), m, out.at(g), g.at<char>(work)))) return rc;
+    HIPCHK(h, g.download(h->stream));
     return PK_OK;
 }
 

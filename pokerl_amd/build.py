@@ -6,7 +6,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpokerl_hip.so")
-HEADERS = [os.path.join(CSRC, "pk_device.hpp"), os.path.join(CSRC, "pk_kernels.hpp"), os.path.join(CSRC, "pk_snapshot.hpp"), os.path.join(CSRC, "pk_equity.hpp"),
+HEADERS = [os.path.join(CSRC, "pk_device.hpp"), os.path.join(CSRC, "pk_table_kernels.hpp"), os.path.join(CSRC, "pk_util_kernels.hpp"), os.path.join(CSRC, "pk_snapshot.hpp"), os.path.join(CSRC, "pk_equity.hpp"),
            os.path.join(os.path.dirname(HERE), "include", "pokerl_hip.h")]
 # -ffp-contract=off: numpy never fuses multiply-add, so neither may we (bit-exact f64 money).
 # -amdgpu-sched-strategy=max-ilp: the table kernels run ONE wave per SIMD (65 536 tables = 1 024 waves), where issue is bound
@@ -81,7 +81,7 @@ def _compile(job):
     return obj
 
 
-def build_variant(out, defines=(), seats=None, tag="", verbose=False, jobs=None, table_defines=()):
+def build_variant(out, defines=(), seats=None, tag="", verbose=False, jobs=None):
     """Compiles pk_api.hip and one pk_tables.hip object per seat count IN PARALLEL (the table kernels of one seat count take
     10-40 s of hipcc each; in one translation unit the library took three minutes), then links them.  seats: None = all of
     SEATS; one seat count = a development library that holds that seat count only (-DPK_ONLY_SEATS), built in seconds."""
@@ -101,7 +101,7 @@ def build_variant(out, defines=(), seats=None, tag="", verbose=False, jobs=None,
             ("pk_snapshot.hip", os.path.join(OBJ, "pk_snapshot%s.o" % tag), defines, verbose),
             ("pk_equity.hip", os.path.join(OBJ, "pk_equity%s.o" % tag), defines, verbose)]
     # widest tables first: they take longest to compile
-    work += [("pk_tables.hip", os.path.join(OBJ, "pk_tables_%d%s.o" % (n, tag)), defines + list(table_defines) + ["-DPK_SEATS=%d" % n], verbose)
+    work += [("pk_tables.hip", os.path.join(OBJ, "pk_tables_%d%s.o" % (n, tag)), defines + ["-DPK_SEATS=%d" % n], verbose)
              for n in sorted(seats, reverse=True)]
     jobs = jobs or int(os.environ.get("PK_BUILD_JOBS", "0")) or min(8, os.cpu_count() or 1)
     with ThreadPoolExecutor(jobs) as ex:

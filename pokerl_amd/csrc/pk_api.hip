@@ -1,4 +1,4 @@
-// pk_api.hip -- host side of the C ABI (include/pokerl_hip.h) of libpokerl_hip.so; kernels: pk_kernels.hpp.  gfx950 only; plain HIP runtime,
+// pk_api.hip -- host side of the C ABI (include/pokerl_hip.h) of libpokerl_hip.so; kernels: pk_table_kernels.hpp, pk_util_kernels.hpp.  gfx950 only; plain HIP runtime,
 // no torch types.  Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC (see pokerl_amd/build.py).
 #include <hip/hip_runtime.h>
 
@@ -13,7 +13,8 @@
 #include <vector>
 
 #include "pk_device.hpp"
-#include "pk_kernels.hpp"
+#include "pk_table_kernels.hpp"
+#include "pk_util_kernels.hpp"
 #include "pk_equity.hpp"
 #include "pk_snapshot.hpp"
 
@@ -477,7 +478,7 @@ static int check_device(const char *call, int device, int limit = INT_MAX) {
     DeviceGuard guard_(device);                                                  \
     if (!guard_.ok) return g_fail(PK_E_HIP, call ": hipSetDevice failed")
 
-// The argument block of the PokerGameEnv.step kernels (pk_kernels.hpp EnvKernArgs): common fields; callers set the rest.
+// The argument block of the PokerGameEnv.step kernels (pk_table_kernels.hpp EnvKernArgs): common fields; callers set the rest.
 static EnvKernArgs env_args(const pk_handle *h, const int32_t *actions_d, int seat0_policy, uint64_t seatpol, int auto_reset,
                             double *reward_d, uint8_t *done_d, uint8_t *hand_d, uint8_t *terr_d, double *obs_d) {
     EnvKernArgs ka{};

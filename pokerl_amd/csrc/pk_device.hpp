@@ -53,6 +53,68 @@ struct State {
     int T;
 };
 
+// ---------------------------------------------------------------------------------------------- the packed State words
+// The bit layout of State::cursors, ::seat_states and ::cards, the community-card rule and the valid-action arithmetic: written HERE ONLY.
+enum : int { LS_DONE = 0, LS_SCAN = 1, LS_POT = 2, LS_END = 3 };   // lane states of the step machine: see "the table" below
+__device__ __forceinline__ uint32_t nib(uint32_t x, int i) { return (x >> (4 * i)) & 0xf; }   // nibble i of x
+struct Cursor {   // State::cursors
+    uint32_t w;
+    __device__ __forceinline__ uint32_t active() const { return nib(w, 0); }
+    __device__ __forceinline__ uint32_t dealer() const { return nib(w, 1); }
+    __device__ __forceinline__ uint32_t sb() const { return nib(w, 2); }   // small / big blind seat
+    __device__ __forceinline__ uint32_t bb() const { return nib(w, 3); }
+    __device__ __forceinline__ uint32_t turn() const { return nib(w, 4); }
+    __device__ __forceinline__ uint32_t current() const { return nib(w, 5); }   // from here on: a step left in flight across launches (all-zero bits = idle table)
+    __device__ __forceinline__ uint32_t lstate() const { return (w >> 24) & 3; }
+    __device__ __forceinline__ uint32_t foldout() const { return (w >> 26) & 1; }
+    __device__ __forceinline__ uint32_t stepped() const { return (w >> 27) & 1; }
+    __device__ __forceinline__ uint32_t flags() const { return (w >> 28) & 7; }
+    __device__ __forceinline__ bool in_flight() const { return (w >> 20) != 0; }
+    __device__ __forceinline__ static uint32_t pack(int active, int dealer, int sb, int bb, int turn, int current, int lstate, bool foldout, uint32_t stepped, uint32_t flags) {
+        const uint32_t inflight = ((uint32_t)current << 20) | ((uint32_t)lstate << 24) | ((uint32_t)foldout << 26) | (stepped << 27) | (flags << 28);
+        return (uint32_t)active | ((uint32_t)dealer << 4) | ((uint32_t)sb << 8) | ((uint32_t)bb << 12) | ((uint32_t)turn << 16) | (lstate == LS_DONE ? 0u : inflight);
+    }
+};
+struct SeatStates {   // State::seat_states
+    uint64_t w;
+    __device__ __forceinline__ uint32_t active() const { return (uint32_t)w & 0xffff; }
+    __device__ __forceinline__ uint32_t called() const { return (uint32_t)(w >> 16) & 0xffff; }
+    __device__ __forceinline__ uint32_t allin() const { return (uint32_t)(w >> 32) & 0xffff; }
+    __device__ __forceinline__ uint32_t broken() const { return (uint32_t)(w >> 48) & 0xffff; }
+    __device__ __forceinline__ uint8_t state_of(int p) const {   // player_states[p]
+        uint8_t st = PS_FOLDED;
+        if ((w >> p) & 1) st = PS_ACTIVE;
+        if ((w >> (16 + p)) & 1) st = PS_CALLED;
+        if ((w >> (32 + p)) & 1) st = PS_ALL_IN;
+        if ((w >> (48 + p)) & 1) st = PS_BROKEN;
+        return st;
+    }
+    __device__ __forceinline__ static uint64_t pack(uint64_t active, uint64_t called, uint64_t allin, uint64_t broken) { return active | (called << 16) | (allin << 32) | (broken << 48); }
+};
+// Card i of a deck of packed words: byte i % 4 of `word`, its word i / 4 ...
+__device__ __forceinline__ uint32_t card_byte(uint32_t word, int i) { return (word >> (8 * (i & 3))) & 0xff; }
+// ... for table t of State::cards ([W][T])
+__device__ __forceinline__ uint32_t card_byte(const uint32_t *cards, size_t T, int t, int i) { return card_byte(cards[(size_t)(i >> 2) * T + t], i); }
+// Community card c is face up in betting round `turn`, game.py:278
+__device__ __forceinline__ bool community_visible(int turn, int c) { return turn != 0 && c < turn + 2; }
+// First 8 bytes of a packed observation row (pokerl_hip.h PK_OBS_PACKED_BYTES): seat, turn, valid mask, hole cards, flop.
+__device__ __forceinline__ uint64_t obs_packed_header0(uint32_t who, uint32_t turn, uint32_t vmask, uint32_t h0, uint32_t h1, uint32_t c0, uint32_t c1, uint32_t c2) {
+    return (uint64_t)(who | (turn << 8) | ((vmask & 0x7fu) << 16) | (h0 << 24)) | ((uint64_t)(h1 | (c0 << 8) | (c1 << 16) | (c2 << 24)) << 32);
+}
+// Game.get_valid_actions as a bitmask, game.py:367-376, for credit = credits[player], high_bet = np.max(pending_bets) (:365-366); the f64
+// expressions and their order are part of the bit-exactness contract.
+__device__ __forceinline__ uint32_t valid_bits(double credit, double high_bet, double min_raise) {
+    uint32_t mask = (1u << MV_FOLD) | (1u << MV_ALL_IN);                           // :367
+    double d = credit - high_bet;
+    double rv0 = 0.1 * d, rv1 = 0.25 * d, rv2 = 0.5 * d;                           // :370
+    mask |= (rv0 > min_raise && (high_bet + rv0) < credit) ? (1u << 3) : 0;        // :371
+    mask |= (rv1 > min_raise && (high_bet + rv1) < credit) ? (1u << 4) : 0;
+    mask |= (rv2 > min_raise && (high_bet + rv2) < credit) ? (1u << 5) : 0;
+    mask |= (high_bet == 0.0) ? (1u << MV_CHECK) : 0;                              // :375
+    mask |= (high_bet < credit) ? (1u << MV_CALL) : 0;                             // :376
+    return mask;
+}
+
 // The few scalars the step machine needs inside its loop, passed BY VALUE (kernel-argument SGPRs); the array bases of
 // State are taken by pointer and s_load-ed only where a table is loaded / stored.  (All of State by value kept ~35 SGPR
 // pairs live across the loop and spilled 66 SGPRs into VGPR lanes; all of it by pointer made the compiler re-issue
@@ -204,7 +266,7 @@ __device__ inline uint32_t eval_hand(const uint32_t (&c)[7], int n, int &nk) {
             uint32_t rr = rk[idx], sr = sk[idx] & 0xf, ss = sk[idx] >> 4;
             if (ss == (flush & 0xf)) {                                             // :52
                 flush += 0x100;
-                if (sr + (both >> 8) == ((both >> 4) & 0xf)) both += 0x100;        // :56
+                if (sr + (both >> 8) == nib(both, 1)) both += 0x100;               // :56
                 else both = 0x100 | (sr << 4) | ss;                                // :57
             } else if ((flush >> 8) < 5) { both = flush = 0x100 | (sr << 4) | ss; flush_start = idx; }  // :58
             if (rr == (kind & 0xf)) kind += 0x10;                                  // :61
@@ -225,7 +287,7 @@ __device__ inline uint32_t eval_hand(const uint32_t (&c)[7], int n, int &nk) {
         else if (numakind == 3) { three |= kr << (4 * n3); ++n3; }
         else if (numakind == 4) { four |= kr << (4 * n4); ++n4; }
     }
-    if ((both >> 8) == 4 && ((both >> 4) & 0xf) == 4) {                            // :83-85  (CardRank.FIVE == 4)
+    if ((both >> 8) == 4 && nib(both, 1) == 4) {                                   // :83-85  (CardRank.FIVE == 4)
         bool ace = false;
 #pragma unroll
         for (int i = 0; i < 7; ++i) ace = ace || (i < n && sk[i] == (((both & 0xf) << 4) | 13));
@@ -244,9 +306,9 @@ __device__ inline uint32_t eval_hand(const uint32_t (&c)[7], int n, int &nk) {
         cnt += k;
     };
     uint32_t kick = 0;
-    if ((both >> 8) >= 5) { nk = 1; return ((uint32_t)HR_SF << 20) | ((both >> 4) & 0xf); }                 // :90
+    if ((both >> 8) >= 5) { nk = 1; return ((uint32_t)HR_SF << 20) | nib(both, 1); }                        // :90
     if (n4) { kick = four & 0xf; nk = 1; others(four & 0xf, 99, 1, kick, nk); return ((uint32_t)HR_POKER << 20) | kick; }  // :91
-    if (n3 > 1) { nk = 2; return ((uint32_t)HR_FULL << 20) | ((three & 0xf) << 4) | ((three >> 4) & 0xf); }  // :92
+    if (n3 > 1) { nk = 2; return ((uint32_t)HR_FULL << 20) | ((three & 0xf) << 4) | nib(three, 1); }         // :92
     if (n3 && n2) { nk = 2; return ((uint32_t)HR_FULL << 20) | ((three & 0xf) << 4) | (two & 0xf); }          // :93
     if ((flush >> 8) >= 5) {                                                                                  // :94
 #pragma unroll
@@ -260,7 +322,7 @@ __device__ inline uint32_t eval_hand(const uint32_t (&c)[7], int n, int &nk) {
     if ((straight >> 4) >= 5) { nk = 1; return ((uint32_t)HR_STRAIGHT << 20) | (straight & 0xf); }            // :95
     if (n3) { kick = three & 0xf; nk = 1; others(three & 0xf, 99, 2, kick, nk); return ((uint32_t)HR_TRIS << 20) | kick; }  // :96
     if (n2 > 1) {                                                                                             // :97
-        uint32_t t0 = two & 0xf, t1 = (two >> 4) & 0xf;
+        uint32_t t0 = two & 0xf, t1 = nib(two, 1);
         kick = (t0 << 4) | t1; nk = 2; others(t0, t1, 1, kick, nk);
         return ((uint32_t)HR_TWO_PAIR << 20) | kick;
     }
@@ -475,8 +537,8 @@ __device__ __forceinline__ Eval7Front eval7_tab_front(uint32_t lo, uint32_t hi, 
 // eval_hand on EVERY 3-, 4-, 5-, 6- and 7-card subset of the deck (value and count: tools/host_sim `evalntab`).
 template <bool SEVEN, bool NK>   // NK: len(kickers) is wanted
 __device__ __forceinline__ uint32_t eval_tab_back(const Eval7Front &f, const uint32_t *T, int &nk) {
-    const uint32_t p1 = (f.e_p >> 16) & 15u, p12 = (f.e_p >> 12) & 0xffu, p2 = p12 & 15u, p3 = (f.e_p >> 8) & 15u;
-    const uint32_t t1 = (f.e_t >> 16) & 15u, t2 = (f.e_t >> 12) & 15u, q1 = (f.e_q >> 16) & 15u;
+    const uint32_t p1 = nib(f.e_p, 4), p12 = (f.e_p >> 12) & 0xffu, p2 = p12 & 15u, p3 = nib(f.e_p, 2);
+    const uint32_t t1 = nib(f.e_t, 4), t2 = nib(f.e_t, 3), q1 = nib(f.e_q, 4);
     const uint32_t st = (f.e_um >> 20) & 15u;
     // an empty mask's entry is 0, so "the family exists" is "its first rank is not 0"
     uint32_t W = 1u << 24;                                                                     // :99 HIGH, tail = top five of um
@@ -596,8 +658,7 @@ __device__ __forceinline__ bool distinct_valid_cards(const uint32_t (&c)[7], int
 //            showdowns end with) for the showdowns that arrive and the ones still in the loop together, instead of
 //            iterating until the slowest arrival is done: that took 3.8 wave-iterations of the ~300-instruction body
 //            with 14 of 64 lanes active, a third of all instructions of the kernel.  Never survives a kernel: the
-//            complete kernels run until nothing is parked, k_rollout takes it back to LS_END when it ends early.
-enum : int { LS_DONE = 0, LS_SCAN = 1, LS_POT = 2, LS_END = 3 };
+//            complete kernels run until nothing is parked, k_rollout takes it back to LS_END when it ends early.  (Values: beside Cursor.)
 #ifndef PK_WAVE
 #define PK_WAVE 64  // lanes per wavefront on gfx950 (tools/host_sim builds this header with 1)
 #endif
@@ -824,8 +885,8 @@ __device__ __forceinline__ int seat_policy(uint64_t seatpol, int p) { return (in
 // Rounds 1-5 wrote __syncthreads() here: the compiler drops its s_barrier for a one-wave workgroup but keeps its fences -- a full s_waitcnt (every
 // LDS and global access drained) and no scheduling across it.  Round 6: a compiler-only barrier (no memory operation moves across it, nothing is
 // emitted; the reads' own s_waitcnt is placed at their first use): k_rollout_tab<6> 30.84 -> 31.13 G on one box (profiles/r06_tab_variants.txt).
-// -DPK_HEAVY_SYNC brings the old form back.  NOT valid for workgroups of several waves (there are none among the table kernels: static_assert below).
-#if defined(PK_HOST_SIM) || defined(PK_HEAVY_SYNC)
+// NOT valid for workgroups of several waves (there are none among the table kernels: static_assert beside PK_TABLE_BLOCK).
+#ifdef PK_HOST_SIM
 #define PK_QSYNC() __syncthreads()
 #else
 #define PK_QSYNC() __builtin_amdgcn_wave_barrier()
@@ -838,9 +899,6 @@ struct Table {
     static constexpr uint32_t FULL = (1u << N) - 1;
     double credits[N], bets[N], pending[N], payoffs[N];
     double min_raise;
-#ifdef PK_CARRY_HB
-    double hb;                   // np.max(pending_bets) carried across the step instead of recomputed (experiment, round 6: see valid_mask)
-#endif
     uint32_t st_active, st_called, st_allin, st_broken;  // seat bitmasks; FOLDED = in none of them
     int active, dealer, sb, bb, turn, hand;
     uint64_t hand_serial, step_serial;
@@ -872,23 +930,19 @@ struct Table {
             pending[p] = g_pending[(size_t)p * T + t]; payoffs[p] = PAYOFFS ? g_payoffs[(size_t)p * T + t] : 0.0;
          PK_END
         pay_dirty = false;
-#ifdef PK_CARRY_HB
-        hb = vmax<N>(pending);
-#endif
         min_raise = as_global(S.min_raise)[t];
-        uint64_t ss = as_global(S.seat_states)[t];
-        st_active = (uint32_t)ss & 0xffff; st_called = (uint32_t)(ss >> 16) & 0xffff;
-        st_allin = (uint32_t)(ss >> 32) & 0xffff; st_broken = (uint32_t)(ss >> 48) & 0xffff;
-        uint32_t cur = as_global(S.cursors)[t];
-        active = cur & 0xf; dealer = (cur >> 4) & 0xf; sb = (cur >> 8) & 0xf; bb = (cur >> 12) & 0xf; turn = (cur >> 16) & 0xf;
+        const SeatStates ss{as_global(S.seat_states)[t]};
+        st_active = ss.active(); st_called = ss.called(); st_allin = ss.allin(); st_broken = ss.broken();
+        const Cursor cur{as_global(S.cursors)[t]};
+        active = cur.active(); dealer = cur.dealer(); sb = cur.sb(); bb = cur.bb(); turn = cur.turn();
         hand = as_global(S.hand)[t];
         hand_serial = as_global(S.hand_serial)[t]; step_serial = as_global(S.step_serial)[t];
         const auto g_cards = as_global(S.cards);
         PK_FOR(w, W) cards[w] = g_cards[(size_t)w * T + t]; PK_END
         // A step left in flight by a deferred rollout launch (all-zero bits = idle table; only k_rollout ever finds
         // anything else: the host flushes deferred work before every other kernel).
-        current = (cur >> 20) & 0xf; lstate = (cur >> 24) & 3; foldout = (cur >> 26) & 1; stepped = (cur >> 27) & 1;
-        flags = (cur >> 28) & 7; hands_this_step = 0; terr = 0;
+        current = cur.current(); lstate = cur.lstate(); foldout = cur.foldout(); stepped = cur.stepped();
+        flags = cur.flags(); hands_this_step = 0; terr = 0;
         PK_FOR(p, N) pot_wb[p] = 0.0; pot_hv[p] = NONE_V; PK_END
         pot_todo = 0; pot_npw = 0;
         evals = 0; games = 0; hands = 0; seen = 0; showed = false;
@@ -898,9 +952,6 @@ struct Table {
     __device__ __forceinline__ void blank() {
         PK_FOR(p, N) credits[p] = bets[p] = pending[p] = payoffs[p] = 0.0;  PK_END
         min_raise = 0.0; st_active = st_called = st_allin = 0; st_broken = FULL;
-#ifdef PK_CARRY_HB
-        hb = 0.0;
-#endif
         active = dealer = sb = bb = turn = hand = 0; hand_serial = step_serial = 0;
         PK_FOR(w, W) cards[w] = 0; PK_END
         PK_FOR(p, N) pot_wb[p] = 0.0; pot_hv[p] = NONE_V; PK_END
@@ -921,10 +972,8 @@ struct Table {
          PK_END
         if (!PAYOFFS && pay_dirty) { PK_FOR(p, N) g_payoffs[(size_t)p * T + t] = payoffs[p]; PK_END }
         as_global(S.min_raise)[t] = min_raise;
-        as_global(S.seat_states)[t] = (uint64_t)st_active | ((uint64_t)st_called << 16) | ((uint64_t)st_allin << 32) | ((uint64_t)st_broken << 48);
-        const uint32_t inflight = ((uint32_t)current << 20) | ((uint32_t)lstate << 24) | ((uint32_t)foldout << 26) | (stepped << 27) | (flags << 28);
-        as_global(S.cursors)[t] = (uint32_t)active | ((uint32_t)dealer << 4) | ((uint32_t)sb << 8) | ((uint32_t)bb << 12) | ((uint32_t)turn << 16) |
-                                  (lstate == LS_DONE ? 0u : inflight);
+        as_global(S.seat_states)[t] = SeatStates::pack(st_active, st_called, st_allin, st_broken);
+        as_global(S.cursors)[t] = Cursor::pack(active, dealer, sb, bb, turn, current, lstate, foldout, stepped, flags);   // (a step in flight: with its machine state)
         as_global(S.hand)[t] = hand;
         as_global(S.hand_serial)[t] = hand_serial; as_global(S.step_serial)[t] = step_serial;
         const auto g_cards = as_global(S.cards);
@@ -952,24 +1001,8 @@ struct Table {
 
     // Game.get_valid_actions(active player) as a bitmask, game.py:339-383.  high_bet is returned for the step.
     __device__ __forceinline__ uint32_t valid_mask(double &high_bet) const {
-#ifdef PK_CARRY_HB
-        high_bet = hb;
-#ifdef PK_HOST_SIM
-        if (hb != vmax<N>(pending)) { printf("CARRIED HIGH BET %.17g != np.max(pending_bets) %.17g\n", hb, vmax<N>(pending)); abort(); }
-#endif
-#else
         high_bet = vmax<N>(pending);                                               // :365
-#endif
-        double credit = sel<N>(credits, active);                                   // :366
-        uint32_t mask = (1u << MV_FOLD) | (1u << MV_ALL_IN);                       // :367
-        double d = credit - high_bet;
-        double rv0 = 0.1 * d, rv1 = 0.25 * d, rv2 = 0.5 * d;                       // :370
-        mask |= (rv0 > min_raise && (high_bet + rv0) < credit) ? (1u << 3) : 0;    // :371
-        mask |= (rv1 > min_raise && (high_bet + rv1) < credit) ? (1u << 4) : 0;
-        mask |= (rv2 > min_raise && (high_bet + rv2) < credit) ? (1u << 5) : 0;
-        mask |= (high_bet == 0.0) ? (1u << MV_CHECK) : 0;                          // :375
-        mask |= (high_bet < credit) ? (1u << MV_CALL) : 0;                         // :376
-        return mask;
+        return valid_bits(sel<N>(credits, active), high_bet, min_raise);           // :366
     }
 
     // Deck of this hand (RNG spec: DESIGN.md, "RNG specification") -> cards[]; replaces random.shuffle(self.deck), game.py:424.
@@ -1027,7 +1060,7 @@ struct Table {
             cards[w] = ((idx & 0x03030303u) << 4) | ((idx >> 2) & 0x0f0f0f0fu);
         PK_END
     }
-    __device__ __forceinline__ uint32_t card(int i) const { return (cards[i >> 2] >> (8 * (i & 3))) & 0xff; }  // compile-time i
+    __device__ __forceinline__ uint32_t card(int i) const { return card_byte(cards[i >> 2], i); }  // compile-time i
 
     // Game.setup_hand minus the shuffle, game.py:414-451
     __device__ __forceinline__ void setup_state(const Hot &S) {
@@ -1050,9 +1083,6 @@ struct Table {
          PK_END
         st_active &= ~over; st_called &= ~over; st_broken &= ~over; st_allin |= over;
         min_raise = vmax<N>(pending);                                              // :446
-#ifdef PK_CARRY_HB
-        hb = min_raise;
-#endif
         hands_this_step += 1;
     }
     // Game.reset minus the shuffle, game.py:397-412
@@ -1091,9 +1121,6 @@ struct Table {
     __device__ __forceinline__ void load_fresh(const Fresh &f) {
         PK_FOR(p, N) credits[p] = f.credits[p]; bets[p] = 0.0; pending[p] = f.pending[p]; PK_END
         min_raise = f.min_raise;
-#ifdef PK_CARRY_HB
-        hb = f.min_raise;
-#endif
         st_active = f.st_active; st_called = f.st_called; st_allin = f.st_allin; st_broken = f.st_broken;
         active = f.active; dealer = f.dealer; sb = f.sb; bb = f.bb;
         hand = 1; turn = 0;
@@ -1117,9 +1144,6 @@ struct Table {
         st_active |= raises ? st_called : 0;                                       // :683 CALLED -> ACTIVE
         st_called = raises ? 0 : st_called;
         min_raise = raises ? bet_value - high_bet : min_raise;                     // :687
-#ifdef PK_CARRY_HB
-        hb = raises ? bet_value : hb;        // (a bet that is no raise never exceeds the high bet; the acting seat's own earlier bet is never the sole maximum it undercuts)
-#endif
         st_active &= ~b; st_called &= ~b; st_allin &= ~b; st_broken &= ~b;         // player_states[a] = ...
         st_allin |= (action == MV_ALL_IN) ? b : 0;                                 // :671
         st_called |= (action != MV_FOLD && action != MV_ALL_IN) ? b : 0;           // :660, :667 (FOLD: in no mask, :657)
@@ -1170,9 +1194,6 @@ struct Table {
     __device__ __forceinline__ void next_turns() {
         PK_FOR(p, N) bets[p] = bets[p] + pending[p]; credits[p] = credits[p] - pending[p]; pending[p] = 0.0; PK_END  // :554-557
         min_raise = 0.0;                                                           // :558
-#ifdef PK_CARRY_HB
-        hb = 0.0;
-#endif
         turn += 1;                                                                 // :561
         const bool more = turn < 4;                                                // :566-576, as selects (one basic block)
         const bool merge = more && __popc(st_called) > 1;
@@ -1222,9 +1243,6 @@ struct Table {
                 pending[p] = 0.0; payoffs[p] = 0.0;
              PK_END
             min_raise = 0.0;
-#ifdef PK_CARRY_HB
-            hb = 0.0;
-#endif
             uint32_t pw = (st_active | st_called | st_allin) & FULL;               // :471 (not BROKEN, not FOLDED)
             const int npw = __popc(pw);                                            // :472
             nowin = npw <= 0;                                                      // :473
@@ -1246,7 +1264,7 @@ struct Table {
         //      seat 0 waiting for the end of its game): no queue, no barrier -- the lane's cards travel by v_readlane, lane p evaluates
         //      seat p's hand, the rankings travel back the same way.  Same function on the same cards as the queue below.
         bool lone = false;
-#if PK_WAVE >= 16 && !defined(PK_NO_LONE)   // (PK_NO_LONE: A/B builds without the lone-table paths)
+#if PK_WAVE >= 16
         if constexpr (LONE) {
             const unsigned long long eb = __ballot(e);
             lone = __popcll(eb) == 1;                                              // wave-uniform
@@ -1435,7 +1453,7 @@ struct Table {
             // lanes, the price of one -- kept in LDS for the hands this table's step may roll on (each further hand of the tail then
             // takes its deck from the stock: a deal is a third of a lone end_block).  A deck is a pure function of (table id, hand
             // serial), so a stocked deck IS the deck the table would have dealt.
-#if PK_WAVE >= 16 && !defined(PK_NO_LONE)
+#if PK_WAVE >= 16
             const unsigned long long db = LONE ? __ballot(need_deal) : 0ull;
             if (LONE && __popcll(db) == 1) {
                 const int dl = __ffsll((long long)db) - 1;

@@ -69,9 +69,10 @@ __global__ void __launch_bounds__(EQ_PREP_BLOCK) k_equity_prep(EqPrepArgs a) {
             const int64_t t = a.t.tables ? (int64_t)a.t.tables[i] : (int64_t)i;
             if (t < 0 || t >= (int64_t)a.t.T) { status |= PK_EQ_BAD_TABLE; readable = false; }
             else {
-                const uint32_t cur = a.t.cursors[t];
-                if (cur >> 20) status |= PK_EQ_IN_FLIGHT;
-                const int turn = (int)((cur >> 16) & 15u);
+                // (Cursor::in_flight(), SeatStates' masks, card_byte() by hand: through them this kernel is scheduled differently; its code is kept as it is)
+                const Cursor cur{a.t.cursors[t]};
+                if (cur.w >> 20) status |= PK_EQ_IN_FLIGHT;
+                const int turn = (int)cur.turn();
                 nb = turn == 0 ? 0 : (turn + 2 < 5 ? turn + 2 : 5);                 // game.py:266-278
                 const uint64_t ss = a.t.seat_states[t];
                 live = (uint32_t)(ss | (ss >> 16) | (ss >> 32)) & 0xffffu & seats;   // ACTIVE | CALLED | ALL_IN
@@ -182,7 +183,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
         const uint64_t known = eq_uniform(d[0]), avail = eq_uniform(d[1]), meta = eq_uniform(d[2]);
         uint64_t hole[N];
         PK_FOR(p, N) hole[p] = eq_uniform(d[3 + p]); PK_END
-        const uint32_t boards = (uint32_t)meta, live = (uint32_t)(meta >> 32) & 0xffffu, k = (uint32_t)(meta >> 48) & 0xffu, P = (uint32_t)(meta >> 56);
+        const uint32_t boards = (uint32_t)meta, mhi = (uint32_t)(meta >> 32), live = mhi & 0xffffu, k = (mhi >> 16) & 0xffu, P = mhi >> 24;
         // this task's boards [start, end) of the spot's, and this lane's [s, s + cnt) of those
         const uint32_t per_max = 64u * (uint32_t)lpt_max, nch = (boards + per_max - 1) / per_max, per = (boards + nch - 1) / nch;
         const uint32_t start = chunk * per, end = min(boards, start + per), nt = end > start ? end - start : 0u;

@@ -40,8 +40,8 @@ __device__ __forceinline__ uint32_t select_bit(uint64_t m, uint32_t k) {
 // canonical order.  Positions are compile-time constants (PK_FOR): the deck never leaves registers.
 __device__ __forceinline__ void redeal(uint32_t (&cw)[SNAP_MAX_WORDS], int N, uint32_t cursors, const Redeal &rd, uint32_t table_id) {
     const int K = 5 + 2 * N;
-    const int turn = (int)((cursors >> 16) & 15u);
-    const int p = rd.observer >= 0 ? rd.observer : (int)(cursors & 15u);
+    const int turn = (int)Cursor{cursors}.turn(), active = (int)Cursor{cursors}.active();
+    const int p = rd.observer >= 0 ? rd.observer : active;
     const int nb = turn == 0 ? 0 : (turn + 2 < 5 ? turn + 2 : 5);   // game.py:266-278
     const int h0 = 5 + 2 * p;
     uint64_t seen = 0;
@@ -159,11 +159,12 @@ __global__ void __launch_bounds__(SNAP_BLOCK) k_snap_check(SnapView v, int N, si
     if (i >= m) return;
     const size_t st = v.stride;
     uint32_t r = 0;
-    const uint32_t cur = v.cursors[i], n = (uint32_t)N;
-    if ((cur & 15u) >= n || ((cur >> 4) & 15u) >= n || ((cur >> 8) & 15u) >= n || ((cur >> 12) & 15u) >= n || ((cur >> 16) & 15u) > 4u || (cur >> 20) != 0)
+    const Cursor cur{v.cursors[i]};   // (its fields by hand below: through the getters this kernel's branches come out in another order; its code is kept as it is)
+    const uint32_t n = (uint32_t)N;
+    if ((cur.w & 15u) >= n || ((cur.w >> 4) & 15u) >= n || ((cur.w >> 8) & 15u) >= n || ((cur.w >> 12) & 15u) >= n || ((cur.w >> 16) & 15u) > 4u || (cur.w >> 20) != 0)
         r |= SNAP_BAD_CURSOR;
-    const uint64_t ss = v.seat_states[i];
-    const uint32_t sa = (uint32_t)ss & 0xffffu, sc = (uint32_t)(ss >> 16) & 0xffffu, sl = (uint32_t)(ss >> 32) & 0xffffu, sb = (uint32_t)(ss >> 48);
+    const SeatStates ss{v.seat_states[i]};
+    const uint32_t sa = ss.active(), sc = ss.called(), sl = ss.allin(), sb = ss.broken();
     const uint32_t seats = (1u << n) - 1u;
     if (((sa | sc | sl | sb) & ~seats) || (sa & sc) || (sa & sl) || (sa & sb) || (sc & sl) || (sc & sb) || (sl & sb)) r |= SNAP_BAD_SEATS;
     const int K = 5 + 2 * N, W = (K + 3) / 4;
@@ -182,7 +183,7 @@ __global__ void __launch_bounds__(SNAP_BLOCK) k_snap_check(SnapView v, int N, si
         }
     }
     // a table that was never dealt (created, not reset yet: pk_create leaves its deck zero) holds 5+2N zero bytes at turn 0
-    const bool never_dealt = any == 0 && ((cur >> 16) & 15u) == 0;
+    const bool never_dealt = any == 0 && cur.turn() == 0;
     if (!never_dealt && (!cards_ok || __popcll(bits) != K)) r |= SNAP_BAD_CARD;
     bool money_ok = finite_bits(v.min_raise[i]);
     for (int p = 0; p < N; ++p)

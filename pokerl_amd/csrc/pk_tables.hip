@@ -1,8 +1,7 @@
 // pk_tables.hip -- the table kernels of libpokerl_hip.so for ONE seat count (-DPK_SEATS=N): explicit instantiations of the
-// templates in pk_kernels.hpp.  One object per seat count, compiled in parallel (pokerl_amd/build.py); pk_api.hip declares
+// templates in pk_table_kernels.hpp.  One object per seat count, compiled in parallel (pokerl_amd/build.py); pk_api.hip declares
 // the same instantiations `extern template` and launches them.  gfx950 only.
-#define PK_TABLES_ONLY
-#include "pk_kernels.hpp"
+#include "pk_table_kernels.hpp"
 
 #ifndef PK_SEATS
 #error "compile with -DPK_SEATS=<number of seats>"

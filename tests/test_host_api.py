@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol():
 
 
 # The table kernels that DO use scratch memory, and why: the 168-register variants of the fused rollout (three waves per SIMD) spill at eight to
-# ten seats -- measured to pay at eight seats from 524 288 tables on (pk_create picks it there; never at nine / ten): pk_kernels.hpp, PK_OCC_CAP.
+# ten seats -- measured to pay at eight seats from 524 288 tables on (pk_create picks it there; never at nine / ten): pk_table_kernels.hpp, PK_OCC_CAP.
 SCRATCH_ALLOWED = {"k_rollout_occ3<8>", "k_rollout_occ3<9>", "k_rollout_occ3<10>", "k_rollout_occ3_allin<8>", "k_rollout_occ3_allin<9>", "k_rollout_occ3_allin<10>"}
 
 

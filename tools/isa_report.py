@@ -14,6 +14,13 @@ FULL_RATE = re.compile(r"^v_(add|sub|subrev|and|or|xor|xnor|not|mov)_(u32|i32|b3
                        r"^v_(add|sub|subrev|addc|subb|subbrev)_co(_ci)?_u32(_e32|_e64|_sdwa|_dpp)?$|"
                        r"^v_cmpx?_\w+_(u32|i32)(_e32|_e64|_sdwa)?$|^v_accvgpr")
 
+def split_asm(s):
+    """hipcc's device assembly cut per symbol: ({kernel: its body and kernel descriptor}, {data object: its definition})."""
+    parts = re.split(r"\n(_Z\w+):\s*; @", s)
+    desc = dict(re.findall(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", s, re.S))
+    funcs = {parts[i]: parts[i + 1].split(".Lfunc_end")[0] + desc.get(parts[i], "") for i in range(1, len(parts), 2)}
+    return funcs, dict(re.findall(r"\.type\t(\S+),@object[^\n]*\n(.*?)\t\.size\t\1,", s, re.S))
+
 def report(n):
     with tempfile.TemporaryDirectory() as td:
         asm = os.path.join(td, "t.s")
@@ -32,11 +39,8 @@ def report(n):
         if m and cur:
             usage[cur][m.group(1).strip()] = m.group(2)
     out = {}
-    parts = re.split(r"\n(_Z\w+):\s*; @", s)
-    for i in range(1, len(parts), 2):
-        mangled = parts[i]
+    for mangled, body in split_asm(s)[0].items():
         name = re.sub(r"\(.*", "", subprocess.run(["c++filt", mangled], capture_output=True, text=True).stdout.strip()).replace("void ", "")
-        body = parts[i + 1].split(".Lfunc_end")[0]
         ops = re.findall(r"\n\s+([a-z_0-9]+)[ \n]", body)
         valu = [o for o in ops if o.startswith("v_") and not o.startswith(("v_readlane", "v_writelane", "v_readfirstlane"))]
         hist = {}

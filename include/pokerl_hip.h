@@ -200,7 +200,14 @@ int pk_get_hand_ranks(pk_handle *h, uint8_t *rank, uint32_t *kick);
  * (any m >= 1) before capturing or timing.
  * Multiset semantics: duplicate cards are legal, as in the reference's own tests (those hands, hands of fewer than three cards and
  * hands with a byte that is no card -- suit > 3 or rank nibble > 12 -- take the reference's sort-and-scan; 3..7 DISTINCT cards a
- * table-driven evaluator that equals it on every subset of the deck: tools/host_sim `evalntab`, GPU digest fast = 4). */
+ * table-driven evaluator that equals it on every subset of the deck: tools/host_sim `evalntab`, GPU digest fast = 4).
+ * Pinned on the device against the imported reference: every hand of 0..7 distinct cards and the hands that repeat cards
+ * (tests/test_hip_evaln.py, tests/golden/evaln_digest.json; seven cards: eval7_digest.json).
+ * A byte that is no card (the reference refuses to construct one, cards.py:58-59) is READ as suit = bits 4..5 and rank nibble as it
+ * is: the result is eval_hand's on (byte & 0x3F) with Card.rank = (value & 0xf) or 13 applied to it -- nibbles 0 and 13 both rank as
+ * the ace, 14 and 15 as two ranks above it; bits 6..7 are ignored -- with ONE exception: a hand that holds a rank above the ace
+ * (nibble 14 or 15) never scores the plain five-high straight of judger.py:86-88, because the scan looks for that straight's ace at the
+ * head of the rank-sorted hand.  The oracle states this reading as orc_eval_hands_bytes; tested for every byte value in every position. */
 int pk_eval_hands(int device, const uint8_t *cards, const uint8_t *ncards, size_t m, uint8_t *rank, uint32_t *kick,
                   uint8_t *nkick);
 /* Same op on device-resident buffers, asynchronous on `stream` (a hipStream_t; NULL = the default stream): the

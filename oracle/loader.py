@@ -64,6 +64,7 @@ def lib():
     L.orc_get_cards.argtypes = [C.c_void_p, _u8p]
     L.orc_get_showdown.argtypes = [C.c_void_p, _u8p, _u32p]
     L.orc_eval_hands.argtypes = [_u8p, C.c_void_p, C.c_size_t, _u8p, _u32p, _u8p]
+    L.orc_eval_hands_bytes.argtypes = L.orc_eval_hands.argtypes
     L.orc_compare_rankings.argtypes = [_u8p, _u32p, C.c_int, _u8p]
     L.orc_compare_rankings.restype = C.c_int
     L.orc_philox4x32_10.argtypes = [_u32p, _u32p, _u32p]
@@ -198,7 +199,8 @@ class OracleGame:
                     valid=self.valid_actions(), hand_serial=hs, step_serial=ss)
 
 
-def eval_hands(cards, ncards=None):
+def eval_hands(cards, ncards=None, any_bytes=False):
+    """any_bytes: orc_eval_hands_bytes, pk_eval_hands' documented reading of bytes that are no card."""
     cards = np.ascontiguousarray(cards, np.uint8).reshape(-1, 7)
     m = cards.shape[0]
     rank = np.zeros(m, np.uint8)
@@ -209,7 +211,7 @@ def eval_hands(cards, ncards=None):
     else:
         ncards = np.ascontiguousarray(ncards, np.uint8)
         p = ncards.ctypes.data_as(C.c_void_p)
-    lib().orc_eval_hands(cards, p, m, rank, kick, nk)
+    (lib().orc_eval_hands_bytes if any_bytes else lib().orc_eval_hands)(cards, p, m, rank, kick, nk)
     return rank, kick, nk
 
 

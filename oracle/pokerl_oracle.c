@@ -160,7 +160,10 @@ static int others(const uint8_t *rank_sorted, int n, int ex0, int ex1, int count
     return k;
 }
 
-static void eval_hand(const uint8_t *hand, int n, ranking_t *out) { /* judger.py:7-99 */
+/* ace_at_head: 0 = the reference.  1 = the DEVICE scan's plain-wheel test (pk_device.hpp eval_hand: `rk[0] == 13`), which looks for the ace
+ * at the head of the rank-sorted hand instead of anywhere in it.  The same thing for cards (no rank exceeds the ace's); it differs only
+ * where a byte that is no card carries rank nibble 14 or 15 (orc_eval_hands_bytes). */
+static void eval_hand_ex(const uint8_t *hand, int n, ranking_t *out, int ace_at_head) { /* judger.py:7-99 */
     out->nk = 0;
     if (n == 0) { out->rank = HR_NONE; return; }                                  /* :30 */
     if (n == 1) { out->rank = HR_HIGH; out->kick[0] = card_rank(hand[0]); out->nk = 1; return; } /* :31 */
@@ -207,6 +210,7 @@ static void eval_hand(const uint8_t *hand, int n, ranking_t *out) { /* judger.py
     } else if ((straight >> 4) == 4 && (straight & 0xf) == RANK_FIVE) {            /* :86-88 */
         int ace = 0;
         for (int i = 0; i < n; ++i) if (card_rank(hand[i]) == RANK_ACE) ace = 1;
+        if (ace_at_head) ace = card_rank(rank_sorted[0]) == RANK_ACE;
         if (ace) { out->rank = HR_STRAIGHT; out->kick[0] = RANK_FIVE; out->nk = 1; return; }
     }
     if ((both >> 8) >= 5) { out->rank = HR_SF; out->kick[0] = (both >> 4) & 0xf; out->nk = 1; }          /* :90 */
@@ -221,6 +225,25 @@ static void eval_hand(const uint8_t *hand, int n, ranking_t *out) { /* judger.py
     else if (n2 > 1) { out->rank = HR_TWO_PAIR; out->kick[0] = two[0]; out->kick[1] = two[1]; out->nk = 2 + others(rank_sorted, n, two[0], two[1], 1, out->kick + 2); } /* :97 */
     else if (n2) { out->rank = HR_PAIR; out->kick[0] = two[0]; out->nk = 1 + others(rank_sorted, n, two[0], -1, 3, out->kick + 1); } /* :98 */
     else { out->rank = HR_HIGH; for (int i = 0; i < 5 && i < n; ++i) out->kick[out->nk++] = card_rank(rank_sorted[i]); } /* :99 */
+}
+
+static void eval_hand(const uint8_t *hand, int n, ranking_t *out) { eval_hand_ex(hand, n, out, 0); }
+
+/* What pk_eval_hands(_d) returns for ARBITRARY bytes (include/pokerl_hip.h at pk_eval_hands): every used byte read as suit = bits 4..5 and
+ * rank nibble as it is (byte & 0x3F; nibbles 0 and 13 both rank as the ace, 14 and 15 above it), evaluated as the reference does, except that
+ * a hand holding a rank above the ace never scores the plain five-high straight of judger.py:86-88 (the device finds the ace at the head of
+ * the sorted hand).  Equal to orc_eval_hands wherever every used byte is a card. */
+void orc_eval_hands_bytes(const uint8_t *cards, const uint8_t *ncards, size_t m, uint8_t *rank, uint32_t *kick, uint8_t *nkick) {
+    for (size_t i = 0; i < m; ++i) {
+        ranking_t r;
+        uint8_t h[7];
+        int n = ncards ? ncards[i] : 7;
+        for (int j = 0; j < 7; ++j) h[j] = cards[7 * i + j] & 0x3f;
+        eval_hand_ex(h, n, &r, 1);
+        rank[i] = (uint8_t)r.rank;
+        kick[i] = kickers_value(&r);
+        if (nkick) nkick[i] = (uint8_t)r.nk;
+    }
 }
 
 void orc_eval_hands(const uint8_t *cards, const uint8_t *ncards, size_t m, uint8_t *rank, uint32_t *kick, uint8_t *nkick) {

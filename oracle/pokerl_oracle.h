@@ -80,6 +80,8 @@ void orc_get_showdown(const orc_game *g, uint8_t *rank, uint32_t *kick /* [T][N]
 /* judger.eval_hand on M hands of ncards[i] (0..7) cards (Card.value bytes, row stride 7). judger.py:7-99
  * kick = get_kickers_value(kickers) (judger.py:101-109), nkick = len(kickers). */
 void orc_eval_hands(const uint8_t *cards, const uint8_t *ncards, size_t m, uint8_t *rank, uint32_t *kick, uint8_t *nkick);
+/* pk_eval_hands' documented reading of arbitrary bytes (see the definition); equals orc_eval_hands where every used byte is a card */
+void orc_eval_hands_bytes(const uint8_t *cards, const uint8_t *ncards, size_t m, uint8_t *rank, uint32_t *kick, uint8_t *nkick);
 /* judger.compare_rankings on one list. judger.py:111-158. Returns number of winners. */
 int orc_compare_rankings(const uint8_t *rank, const uint32_t *kick, int n, uint8_t *onehot);
 

@@ -931,6 +931,11 @@ def test_streaming_evaluator(HB, O):
         C.CDLL("libamdhip64.so").hipDeviceSynchronize()
         got.append((d_r.download(np.uint8, 2048), d_k.download(np.uint32, 2048), d_nk.download(np.uint8, 2048)))
     assert all(np.array_equal(a, b) for a, b in zip(*got))
+    # ... and what the scan reads in such a byte is the documented reading (suit = bits 4..5, rank nibble as it is, no plain five-high
+    # straight under a rank above the ace: include/pokerl_hip.h at pk_eval_hands, orc_eval_hands_bytes; every byte value in every
+    # position: tests/test_hip_evaln.py)
+    want = O.eval_hands(odd, any_bytes=True)
+    assert all(np.array_equal(w, g) for run in got for w, g in zip(want, run))
 
 
 def test_empty_and_minimal_inputs(HB, O):

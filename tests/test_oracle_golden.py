@@ -1,10 +1,12 @@
 """CPU oracle (oracle/pokerl_oracle.c) pinned against vectors captured from the imported reference."""
 import json
+import math
 import os
 
 import numpy as np
 import pytest
 
+import evaln_spec as S
 import golden_util as GU
 from oracle import loader as O
 from oracle import rng_spec as R
@@ -170,6 +172,53 @@ def test_eval7_exhaustive_digest_vs_reference():
     assert counts.tolist() == gold["category_counts"]
     assert ["%016x" % int(x) for x in per_first] == gold["per_first_card"]
     assert "%016x" % (int(per_first.astype(object).sum()) % (1 << 64)) == gold["digest"]
+
+
+@pytest.mark.parametrize("k", list(S.DISTINCT_K))
+def test_evaln_exhaustive_digest_vs_reference(k):
+    """Every hand of k = 0 .. 6 distinct cards (23 251 684 in all): the C oracle reproduces the digests, the per-first-card
+    digests and the category / len(kickers) counts computed from the imported reference (tests/golden/evaln_digest.json, made
+    by tests/golden/make_evaln_digest.py; the definition: tests/evaln_spec.py)."""
+    gold = GU.load_json("evaln_digest")["distinct"][str(k)]
+    got = S.digest_distinct(k, O.eval_hands)
+    assert got["hands"] == gold["hands"] == math.comb(52, k)
+    for field in ("category_counts", "nkick_counts", "per_first_card", "digest"):
+        assert got[field] == gold[field], field
+
+
+@pytest.mark.parametrize("name", S.MULTISET_NAMES)
+def test_evaln_multiset_digest_vs_reference(name):
+    """Hands that repeat cards -- every ordered pair and triple of cards, and the generated sets of 4 .. 7 cards drawn from
+    twelve -- against the reference's digests; and what tests/test_hip_evaln.py relies on for its second layout: the oracle
+    returns the same for the rotated hands with real cards in the unused slots."""
+    gold = GU.load_json("evaln_digest")["multiset"][name]
+    k, cards = S.multiset_set(name)
+    got = S.digest_multiset(name, k, cards, O.eval_hands)
+    assert got == gold
+    if name.startswith("gen"):
+        assert got["repeat_share"] >= 0.5
+    nc = np.full(len(cards), k, np.uint8)
+    for a, b in zip(O.eval_hands(cards, nc), O.eval_hands(S.scrambled(cards, k), nc)):
+        assert np.array_equal(a, b)
+    # the device's reading of arbitrary bytes (orc_eval_hands_bytes) is the reference's wherever the bytes are cards
+    for a, b in zip(O.eval_hands(cards, nc), O.eval_hands(S.scrambled(cards, k), nc, any_bytes=True)):
+        assert np.array_equal(a, b)
+
+
+def test_evaln_distinct_cards_in_any_order():
+    """The reference reads a hand's order only where cards tie under its sort keys (stable sorts, judger.py:38-39), and distinct
+    cards never tie under the suit key while the rank-sorted list is read by rank alone: every hand of up to five distinct cards
+    in every rotation, with real cards in the unused slots (evaln_spec.scrambled's layout, shifted so that each hand meets each
+    of its k rotations), returns what it returns in ascending order."""
+    for k in range(1, 6):
+        for a in range(52):
+            cards, _ = S.hands_of_first(k, a)
+            nc = np.full(len(cards), k, np.uint8)
+            want = O.eval_hands(cards, nc)
+            for shift in range(k):
+                rot = S.scrambled(np.roll(cards, shift, axis=0), k)
+                got = O.eval_hands(rot, nc)
+                assert all(np.array_equal(np.roll(w, shift), g) for w, g in zip(want, got)), (k, a, shift)
 
 
 @pytest.mark.parametrize("name", GU.ALIAS_SETS)

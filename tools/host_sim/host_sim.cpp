@@ -253,7 +253,65 @@ static int check_evaln(int nmax, const uint32_t *tab = nullptr) {   // tab: chec
     return bad != 0;
 }
 
+// What pk_eval_hands returns for a byte that is no card, stated through the oracle: k_eval_hands_tab's dispatch (table / eval_small / scan)
+// and the register dispatch (eval_hand_any) equal orc_eval_hands_bytes -- suit = bits 4..5, rank nibble as it is (0 and 13 both read as
+// the ace, 14 / 15 as ranks above it), and no plain five-high straight for a hand that holds a rank above the ace, because the scan looks
+// for the ace at the head of the sorted hand -- for EVERY byte value in EVERY used position of hands of 1 .. 7 cards, and on `fuzz` hands
+// of 0 .. 7 arbitrary bytes (the GPU twin, on 3-, 5- and 7-card hands: tests/test_hip_evaln.py).  Also counts how often the plain
+// reading, orc_eval_hands on byte & 0x3F, would have differed.
+static int check_noncard(const uint32_t *tab, long long fuzz) {
+    const uint32_t base[4][7] = {{0x01, 0x02, 0x03, 0x04, 0x1c, 0x2b, 0x35}, {0x3c, 0x2c, 0x1c, 0x0b, 0x1b, 0x2a, 0x00}, {0x10, 0x1c, 0x1b, 0x1a, 0x19, 0x25, 0x36},
+                                 {0x00, 0x11, 0x22, 0x33, 0x04, 0x1c, 0x2b}};
+    long long bad = 0, total = 0, plain_differs = 0;
+    auto one = [&](const uint32_t (&c)[7], int n, const char *what) {
+        uint8_t raw[7], masked[7];
+        uint64_t w = 0, bits;
+        for (int i = 0; i < 7; ++i) { raw[i] = (uint8_t)c[i]; masked[i] = (uint8_t)(c[i] & 0x3f); w |= (uint64_t)c[i] << (8 * i); }
+        uint8_t nc = (uint8_t)n, orank, onk, prank, pnk;
+        uint32_t okick, pkick;
+        orc_eval_hands_bytes(raw, &nc, 1, &orank, &okick, &onk);
+        orc_eval_hands(masked, &nc, 1, &prank, &pkick, &pnk);
+        plain_differs += prank != orank || pkick != okick || pnk != onk;
+        const uint32_t want = ((uint32_t)orank << 20) | okick;
+        int nk = -1, nk2 = -1;
+        const uint32_t v = tab_bits_of(w, n, bits) ? eval_tab_bits(bits, tab, nk) : (n < 3 ? eval_small(w, n, nk) : eval_hand(c, n, nk));
+        const uint32_t v2 = eval_hand_any(c, n, nk2);
+        ++total;
+        if (v != want || nk != (int)onk || v2 != want || nk2 != (int)onk) {
+            if (bad++ < 5) printf("noncard MISMATCH (%s) n %d bytes %02x %02x %02x %02x %02x %02x %02x: oracle %08x/%d kernel %08x/%d register %08x/%d\n", what, n,
+                                  c[0], c[1], c[2], c[3], c[4], c[5], c[6], want, onk, v, nk, v2, nk2);
+        }
+    };
+    for (int k = 0; k < 4; ++k)
+        for (int n = 1; n <= 7; ++n)
+            for (int pos = 0; pos < n; ++pos)
+                for (uint32_t byte = 0; byte < 256; ++byte) {
+                    uint32_t c[7];
+                    for (int i = 0; i < 7; ++i) c[i] = i == pos ? byte : base[k][i];
+                    one(c, n, "one byte");
+                }
+    uint64_t r = 0x9E3779B97F4A7C15ull;
+    auto next = [&]() { r ^= r << 13; r ^= r >> 7; r ^= r << 17; return r; };
+    for (long long i = 0; i < fuzz; ++i) {      // arbitrary bytes; every other hand from a narrow window so that runs, flushes and repeats happen
+        uint32_t c[7];
+        const uint64_t a = next(), b = next();
+        const bool narrow = (a >> 60) & 1;
+        for (int j = 0; j < 7; ++j) {
+            const uint32_t x = (uint32_t)(b >> (8 * j)) & 0xff;
+            c[j] = narrow ? ((x & 0xc0 & (uint32_t)(a >> 8)) | (x & 0x10) | ((((uint32_t)a & 15) + (x & 7)) & 15)) : x;
+        }
+        one(c, (int)((a >> 56) & 7), "fuzz");
+    }
+    printf("noncard: %lld hands, %lld mismatching (the plain reading, the oracle on byte & 0x3F, differs on %lld)\n", total, bad, plain_differs);
+    return bad != 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "noncard")) {
+        std::vector<uint32_t> tab(EVAL7_TAB_WORDS);
+        for (int m = 0; m < EVAL7_TAB_WORDS; ++m) tab[m] = eval7_tab_entry((uint32_t)m);
+        return check_noncard(tab.data(), argc > 2 ? atoll(argv[2]) : 4000000);
+    }
     if (argc > 1 && !strcmp(argv[1], "evaln")) return check_evaln(argc > 2 ? atoi(argv[2]) : 7);
     if (argc > 1 && !strcmp(argv[1], "evalntab")) {
         std::vector<uint32_t> tab(EVAL7_TAB_WORDS);

@@ -558,6 +558,42 @@ int pk_table_equity_d(pk_handle *h, const int32_t *tables_d, size_t m, uint32_t 
                       uint8_t *status_d);
 int pk_table_equity(pk_handle *h, const int32_t *tables, size_t m, uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards,
                     uint8_t *status);
+/* ---- Sampled showdown equity: the same question for a seat that does NOT know the other hands -- the hidden cards are drawn, S samples per
+ * spot, on the device; the counts are exact integers and bit-identical to a restatement of this definition.
+ *
+ * A SPOT is as above with one difference: a 0xFF hole byte at a LIVE seat is legal and means HIDDEN (each byte on its own: a seat may show one
+ * card).  Dead cards = the nb board cards and every hole byte that is a card, live or not; a 0xFF at a seat that is not live is "not known" as
+ * above (that card is simply in the pool).  Pool = the 52 cards minus the dead ones, P of them, in canonical order value[k] = ((k%4)<<4) | (k/4).
+ * Hidden slots, in this order: board positions nb .. 4, then the hidden hole bytes by ascending seat, byte 0 before byte 1 -- D of them
+ * (D <= 37 <= P always).  STATUS: the PK_EQ_* bits above; PK_EQ_BAD_CARD is "a byte that is no card, or 0xFF in the board".  A spot with a
+ * non-zero status gets all-zero counts and samples = 0 and disturbs nothing else.
+ * SAMPLE s (0 .. S-1) of a spot with stream id `id` (u32) is the redeal's draw (pk_clone_tables_d) on its own stream: Philox4x32-10 under
+ * `key`, counter (id, s, 'EQS0' + b, nonce) with 'EQS0' = 0x45515330 and block b = 0, 1, 2; 64-bit words X[2b] = w0 | w1 << 32,
+ * X[2b+1] = w2 | w3 << 32; chained bounded draws c_i = (x * (P - i)) >> 64 (x = X[i / 9] when i % 9 == 0, then x = the low 64 bits of the
+ * product); hidden slot i receives the c_i-th not yet drawn pool card.  Then v[p] = eval_hand(board + hole[p]) for a live seat and (NONE, [])
+ * for the others, and the winners are compare_rankings(v), exactly as above.  Outputs per spot and seat over the S samples: win, tie (u32),
+ * share (u64, units of 720720 / nw); per spot samples (u32: S, or 0 where status != 0) and status (u8).  Any output may be NULL; m == 0 is a
+ * no-op.  S = 1 .. 2^24 per call, nonce any u32; a spot's counts depend on (spot, key, nonce, id, S) only -- not on the batch it travels in --
+ * and COUNTS OF CALLS WITH DIFFERENT NONCES ADD EXACTLY: that is the way to more samples (and to a running estimate).
+ * Refused with PK_E_INVALID_ARG (pk_last_error names the function): N outside 2 .. 16, samples 0 or > 2^24, m * ceil(samples / 64) not
+ * fitting 32 bits, an observer outside {-2, -1, 0 .. N-1}.
+ * EXPLICIT FORM: key = (seed lo, seed hi) as pk_create's seed; id = ids[i] where the optional ids array (u32 [m]) is given, else i.
+ * TABLE FORM: the handle's key, id = table_id_base + table index (independent of sharding); nb, board and live seats as pk_table_equity.
+ * observer = a seat p (0 .. N-1) or PK_OBSERVER_ACTIVE (each table's active seat): p's two hole cards are known; every other seat's are
+ * hidden if the seat is live and, if it is not, NOT dead (p never saw a folded hand: those cards are in the pool).  PK_OBSERVER_NONE: all 2N
+ * hole cards known and dead as in pk_table_equity, only the board is sampled.  Like pk_table_equity the call completes deferred rollout work,
+ * reads only, runs on the handle's stream, and reports PK_EQ_IN_FLIGHT / PK_EQ_BAD_TABLE / PK_EQ_DUP_CARD (a table never dealt) per table.
+ * STREAMS and work space: as pk_equity (the device form asynchronous on the stream it is given, the host forms synchronous). */
+int pk_equity_sampled_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
+                        const uint16_t *live_d, const uint32_t *ids_d /* NULL: i */, uint32_t samples, uint64_t seed, uint32_t nonce,
+                        uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *samples_d, uint8_t *status_d, void *stream);
+int pk_equity_sampled(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard,
+                      const uint16_t *live, const uint32_t *ids /* NULL: i */, uint32_t samples, uint64_t seed, uint32_t nonce, uint32_t *win,
+                      uint32_t *tie, uint64_t *share, uint32_t *samples_out, uint8_t *status);
+int pk_table_equity_sampled_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce,
+                              uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *samples_d, uint8_t *status_d);
+int pk_table_equity_sampled(pk_handle *h, const int32_t *tables, size_t m, int observer, uint32_t samples, uint32_t nonce, uint32_t *win,
+                            uint32_t *tie, uint64_t *share, uint32_t *samples_out, uint8_t *status);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

@@ -4,7 +4,8 @@ from .enums import CardRank, CardSuit, HandRanking, PlayerState, PokerMoves, Pol
 from .game import VecGame, snapshot_nbytes
 from .envs import VecPokerGameEnv, VecPokerGameEnvPool
 from .agents import AllInAgent, CallAgent, PokerAgent, RandomAgent
-from .judger import Equity, compare_hands, compare_rankings, eval_hand, eval_hands, showdown_equity, showdown_equity_batch
+from .judger import (Equity, SampledEquity, compare_hands, compare_rankings, eval_hand, eval_hands, sampled_equity, sampled_equity_batch,
+                     showdown_equity, showdown_equity_batch)
 from .sharding import gather_f64, shard_tables
 from .single import Game, PokerGameEnv
 from .state_view import Card, StateView, packed_dtype, unpack_obs
@@ -14,4 +15,5 @@ from ._lib import OBSERVER_ACTIVE, OBSERVER_NONE, PokerlHipError, device_count
 __all__ = ['Game', 'PokerGameEnv', 'VecGame', 'VecPokerGameEnv', 'VecPokerGameEnvPool', 'eval_hand', 'eval_hands', 'compare_rankings', 'compare_hands',
            'shard_tables', 'gather_f64', 'Card', 'StateView', 'HandRanking', 'PokerMoves', 'PlayerState', 'CardRank', 'CardSuit', 'Policy',
            'PokerlHipError', 'device_count', 'packed_dtype', 'unpack_obs', 'pinned_empty', 'PokerAgent', 'RandomAgent', 'AllInAgent', 'CallAgent',
-           'snapshot_nbytes', 'OBSERVER_NONE', 'OBSERVER_ACTIVE', 'Equity', 'showdown_equity', 'showdown_equity_batch']
+           'snapshot_nbytes', 'OBSERVER_NONE', 'OBSERVER_ACTIVE', 'Equity', 'showdown_equity', 'showdown_equity_batch',
+           'SampledEquity', 'sampled_equity', 'sampled_equity_batch']

@@ -22,6 +22,7 @@ MIN_PLAYERS, MAX_PLAYERS = 2, 16
 EQ_SHARE_UNIT = 720720   # lcm(1 .. 16): a board's pot share of one of nw winners is EQ_SHARE_UNIT / nw (pk_equity)
 EQ_BAD_CARD, EQ_DUP_CARD, EQ_NO_LIVE, EQ_BAD_NBOARD, EQ_IN_FLIGHT, EQ_BAD_TABLE = 1, 2, 4, 8, 16, 32   # PK_EQ_* status bits
 OBSERVER_NONE, OBSERVER_ACTIVE = -1, -2   # pk_clone_tables_d: an exact copy / redeal from each source table's active player
+EQS_SAMPLES_MAX = 1 << 24   # pk_equity_sampled: samples per call and spot at most
 
 # every symbol include/pokerl_hip.h declares (tests check the library exports each one)
 SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "pk_destroy", "pk_num_tables",
@@ -36,7 +37,8 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_get_obs_packed", "pk_get_obs_packed_d", "pk_set_env_obs_packed", "pk_host_alloc", "pk_host_free", "pk_check_actions",
            "pk_env_step_begin", "pk_env_step_end", "pk_reset_d", "pk_step_auto_d", "pk_stream_pool_drain", "pk_step_async_d", "pk_set_step_obs", "pk_build_info",
            "pk_snapshot_bytes", "pk_save_tables_d", "pk_load_tables_d", "pk_save_tables", "pk_load_tables", "pk_clone_tables_d",
-           "pk_equity_d", "pk_equity", "pk_table_equity_d", "pk_table_equity"]
+           "pk_equity_d", "pk_equity", "pk_table_equity_d", "pk_table_equity",
+           "pk_equity_sampled_d", "pk_equity_sampled", "pk_table_equity_sampled_d", "pk_table_equity_sampled"]
 
 
 class PokerlHipError(RuntimeError):
@@ -137,6 +139,10 @@ def lib():
     L.pk_equity.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 9
     L.pk_table_equity_d.argtypes = [_vp, _vp, C.c_size_t] + [_vp] * 5
     L.pk_table_equity.argtypes = [_vp, _vp, C.c_size_t] + [_vp] * 5
+    L.pk_equity_sampled_d.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_uint32, C.c_uint64, C.c_uint32] + [_vp] * 6
+    L.pk_equity_sampled.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_uint32, C.c_uint64, C.c_uint32] + [_vp] * 5
+    L.pk_table_equity_sampled_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32] + [_vp] * 5
+    L.pk_table_equity_sampled.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32] + [_vp] * 5
     for name in SYMBOLS:
         if name not in ("pk_last_error", "pk_build_info", "pk_snapshot_bytes"):
             getattr(L, name).restype = C.c_int

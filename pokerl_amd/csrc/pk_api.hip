@@ -16,6 +16,7 @@
 #include "pk_table_kernels.hpp"
 #include "pk_util_kernels.hpp"
 #include "pk_equity.hpp"
+#include "pk_equity_sampled.hpp"
 #include "pk_snapshot.hpp"
 
 using namespace pk;
@@ -1910,6 +1911,111 @@ int pk_table_equity(pk_handle *h, const int32_t *tables, size_t m, uint32_t *win
     if (rc) return rc;
     HIPCHK(h, g.upload(h->stream));
     if ((rc = table_equity(h, g.at<int32_t>(idx), m, out.at(g), g.at<char>(work)))) return rc;
+    HIPCHK(h, g.download(h->stream));
+    return PK_OK;
+}
+
+// ---- sampled showdown equity (pokerl_hip.h "Sampled showdown equity"; kernels: pk_equity_sampled.hip).  Work space (the descriptors) as above.
+static bool eqs_bad_samples(uint32_t samples) { return samples == 0 || samples > EQS_SAMPLES_MAX; }
+static EqsOut eqs_out(const EqOut &o) { return EqsOut{o.win, o.tie, o.share, o.boards, o.status}; }
+static EqsStream eqs_seed_stream(uint64_t seed, uint32_t nonce, uint32_t samples, const uint32_t *ids) {
+    return EqsStream{(uint32_t)seed, (uint32_t)(seed >> 32), nonce, samples, 0u, ids};
+}
+#define EQS_CHECK_SPOTS(call, num_players, m, samples, inputs)                                                                                    \
+    if (eq_bad_seats(num_players) || (m) >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, call ": num_players outside 2 .. 16, or m >= 2^31");    \
+    if (eqs_bad_samples(samples)) return g_fail(PK_E_INVALID_ARG, call ": samples outside 1 .. 2^24");                                            \
+    if ((m) && !(inputs)) return g_fail(PK_E_INVALID_ARG, call ": NULL input buffer");                                                            \
+    if (eqs_task_bound(m, samples) > EQ_TASKS_MAX) return g_fail(PK_E_INVALID_ARG, call ": m * ceil(samples / 64) must fit 32 bits: split the batch")
+
+int pk_equity_sampled_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
+                        const uint16_t *live_d, const uint32_t *ids_d, uint32_t samples, uint64_t seed, uint32_t nonce, uint32_t *win_d,
+                        uint32_t *tie_d, uint64_t *share_d, uint32_t *samples_d, uint8_t *status_d, void *stream) {
+    EQS_CHECK_SPOTS("pk_equity_sampled_d", num_players, m, samples, holes_d && board_d && nboard_d && live_d);
+    ON_DEVICE_INDEX("pk_equity_sampled_d", device, PK_MAX_DEVICES);
+    if (m == 0) return PK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t *tab = eval7_table(device, st);
+    if (!tab) return g_fail(PK_E_OOM, "pk_equity_sampled_d: out of device memory (evaluator table)");
+    void *ws = eq_stream_ws(device, st, eqs_work_bytes(num_players, m));
+    if (!ws) return g_fail(PK_E_OOM, "pk_equity_sampled_d: out of device memory (work space)");
+    const EqSpots spots{holes_d, board_d, nboard_d, live_d};
+    const hipError_t e = eqs_launch(st, tab, &spots, nullptr, PK_OBSERVER_NONE, eqs_seed_stream(seed, nonce, samples, ids_d), num_players, m,
+                                    EqsOut{win_d, tie_d, share_d, samples_d, status_d}, (uint64_t *)ws);
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_sampled_d: launch failed", e);
+    return PK_OK;
+}
+
+int pk_equity_sampled(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard,
+                      const uint16_t *live, const uint32_t *ids, uint32_t samples, uint64_t seed, uint32_t nonce, uint32_t *win, uint32_t *tie,
+                      uint64_t *share, uint32_t *samples_out, uint8_t *status) {
+    EQS_CHECK_SPOTS("pk_equity_sampled", num_players, m, samples, holes && board && nboard && live);
+    ON_DEVICE_INDEX("pk_equity_sampled", device, PK_MAX_DEVICES);
+    if (m == 0) return PK_OK;
+    const int N = num_players;
+    hipStream_t st = nullptr;
+    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity_sampled: no stream"); }
+    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
+    int rc = PK_OK;
+    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity_sampled: out of device memory (evaluator table)");
+    else {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        Stage g;
+        const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), id = g.in(ids, m * 4);
+        const EqStagedOut out(g, N, m, win, tie, share, samples_out, status);
+        const int work = g.add(eqs_work_bytes(N, m));
+        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity_sampled: out of device memory");
+        else {
+            const hipError_t e = g.run(st, [&] {
+                const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
+                return eqs_launch(st, tab, &spots, nullptr, PK_OBSERVER_NONE, eqs_seed_stream(seed, nonce, samples, g.at<uint32_t>(id)), N, m,
+                                  eqs_out(out.at(g)), g.at<uint64_t>(work));
+            });
+            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity_sampled", e); }   // (the lock is held until what was queued is done)
+        }
+    }
+    stream_release(device, st);
+    return rc;
+}
+
+// The table form: the handle's own state on the handle's stream, as `observer` sees it; the handle's key, stream id = table_id_base + table
+static int table_equity_sampled(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce, const EqsOut &out,
+                                char *work) {
+    const uint32_t *tab = eval7_table(h->device, h->stream);
+    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity_sampled: out of device memory (evaluator table)");
+    const EqTables t{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T};
+    const EqsStream rng{h->S.key0, h->S.key1, nonce, samples, h->S.table_id_base, nullptr};
+    HIPCHK(h, eqs_launch(h->stream, tab, nullptr, &t, observer, rng, h->N, m, out, (uint64_t *)work));
+    return PK_OK;
+}
+#define EQS_TABLE_ENTER(h, m, observer, samples, call)                                                                                       \
+    if (!(h)) return PK_E_INVALID_ARG;                                                                                                       \
+    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                                                         \
+    if (eqs_bad_samples(samples)) return (h)->fail(PK_E_INVALID_ARG, call ": samples outside 1 .. 2^24");                                    \
+    if ((observer) < PK_OBSERVER_ACTIVE || (observer) >= (h)->N) return (h)->fail(PK_E_INVALID_ARG, call ": observer outside {-2, -1, 0 .. N-1}"); \
+    if (eqs_task_bound(m, samples) > EQ_TASKS_MAX) return (h)->fail(PK_E_INVALID_ARG, call ": m * ceil(samples / 64) must fit 32 bits: split the batch"); \
+    ON_DEVICE(h);                                                                                                                            \
+    FLUSH_READER(h);                                                                                                                         \
+    if ((m) == 0) return PK_OK
+
+int pk_table_equity_sampled_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce, uint32_t *win_d,
+                              uint32_t *tie_d, uint64_t *share_d, uint32_t *samples_d, uint8_t *status_d) {
+    EQS_TABLE_ENTER(h, m, observer, samples, "pk_table_equity_sampled_d");
+    char *work = nullptr;
+    if (int rc = snap_staging(h, eqs_work_bytes(h->N, m), &work)) return rc;
+    return table_equity_sampled(h, tables_d, m, observer, samples, nonce, EqsOut{win_d, tie_d, share_d, samples_d, status_d}, work);
+}
+
+int pk_table_equity_sampled(pk_handle *h, const int32_t *tables, size_t m, int observer, uint32_t samples, uint32_t nonce, uint32_t *win,
+                            uint32_t *tie, uint64_t *share, uint32_t *samples_out, uint8_t *status) {
+    EQS_TABLE_ENTER(h, m, observer, samples, "pk_table_equity_sampled");
+    Stage g;
+    const int idx = g.in(tables, m * 4);
+    const EqStagedOut out(g, h->N, m, win, tie, share, samples_out, status);
+    const int work = g.add(eqs_work_bytes(h->N, m));
+    int rc = snap_staging(h, g.total, &g.base);
+    if (rc) return rc;
+    HIPCHK(h, g.upload(h->stream));
+    if ((rc = table_equity_sampled(h, g.at<int32_t>(idx), m, observer, samples, nonce, eqs_out(out.at(g)), g.at<char>(work)))) return rc;
     HIPCHK(h, g.download(h->stream));
     return PK_OK;
 }

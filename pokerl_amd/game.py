@@ -381,6 +381,42 @@ class VecGame:
         L.check(self._lib.pk_table_equity_d(self._h, self._dptr(tables_d), m, self._dptr(win_d), self._dptr(tie_d), self._dptr(share_d),
                                             self._dptr(boards_d), self._dptr(status_d)), self._h)
 
+    def _equity_observer(self, observer):
+        """observer of equity_sampled: a seat, OBSERVER_ACTIVE / 'active', or OBSERVER_NONE / None; ValueError otherwise (before any call)."""
+        o = self._observer(observer)
+        if not (L.OBSERVER_ACTIVE <= o < self.num_players):
+            raise ValueError('observer must be a seat 0 .. %d, OBSERVER_ACTIVE or OBSERVER_NONE' % (self.num_players - 1))
+        return o
+
+    def equity_sampled(self, tables=None, observer=L.OBSERVER_ACTIVE, samples=1024, nonce=0):
+        """Sampled showdown equity of `tables` (all tables if None; indices may repeat) as `observer` sees them (pk_table_equity_sampled;
+        definition: pokerl_hip.h "Sampled showdown equity"): a seat or OBSERVER_ACTIVE (each table's active seat) knows the board so far and
+        its own two cards -- the other live seats' cards and the board to come are drawn `samples` times, folded hands are in the pool;
+        OBSERVER_NONE knows every hole card and only the board is drawn.  The stream is the handle's seed, table id and `nonce`: the result
+        does not depend on sharding, and counts of calls with different nonces add.  Returns a judger.SampledEquity of [m, N] / [m] arrays."""
+        from .judger import SampledEquity, check_samples
+        o = self._equity_observer(observer)
+        samples, nonce = check_samples(samples, nonce)
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        n = self.num_players
+        win, tie, share = np.zeros((m, n), np.uint32), np.zeros((m, n), np.uint32), np.zeros((m, n), np.uint64)
+        count, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        L.check(self._lib.pk_table_equity_sampled(self._h, L.ptr(t), m, o, samples, nonce, L.ptr(win), L.ptr(tie), L.ptr(share), L.ptr(count),
+                                                  L.ptr(status)), self._h)
+        return SampledEquity(win, tie, share, count, status)
+
+    def equity_sampled_d(self, m=None, tables_d=None, observer=L.OBSERVER_ACTIVE, samples=1024, nonce=0, win_d=None, tie_d=None, share_d=None,
+                         samples_d=None, status_d=None):
+        """pk_table_equity_sampled_d: the same into device buffers (uint32 [m, N] win / tie, uint64 [m, N] share, uint32 [m] samples, uint8 [m]
+        status; any may be None), asynchronous on the handle's stream.  m defaults to every table."""
+        from .judger import check_samples
+        o = self._equity_observer(observer)
+        samples, nonce = check_samples(samples, nonce)
+        m = self.num_tables if m is None else int(m)
+        L.check(self._lib.pk_table_equity_sampled_d(self._h, self._dptr(tables_d), m, o, samples, nonce, self._dptr(win_d), self._dptr(tie_d),
+                                                    self._dptr(share_d), self._dptr(samples_d), self._dptr(status_d)), self._h)
+
     def __deepcopy__(self, memo):
         """A new handle with the same configuration (seed and table ids included) holding a copy of every table: it continues
         bit-identically to this game under the same actions, and stepping one leaves the other untouched.  Only the construction

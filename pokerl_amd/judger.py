@@ -216,3 +216,122 @@ def showdown_equity(hands, board=(), live=None, device=0):
     if r.status:
         raise ValueError('invalid spot: ' + equity_status_text(r.status))
     return r
+
+
+# ---------------------------------------------------------------------------------------------- sampled showdown equity
+# The same question for a seat that does not know the other hands: hidden cards are DRAWN on the device, `samples` times per spot, on a fixed
+# counter-based stream (pk_equity_sampled; the definition: include/pokerl_hip.h "Sampled showdown equity").
+DEFAULT_SEED = 0x706F6B65726C
+
+
+class SampledEquity:
+    """Counts of one spot or of a batch over `samples` samples ([N] or [m, N] arrays; `samples`, `status` scalars or [m]): as Equity, with
+    samples in place of boards.  `equity` = share / (720720 * samples); `stderr` = the binomial standard error of (win + tie) / samples per
+    seat (0 where a spot was refused).  Counts of calls with different nonces add exactly."""
+
+    def __init__(self, win, tie, share, samples, status):
+        self.win, self.tie, self.share, self.samples, self.status = win, tie, share, samples, status
+
+    @property
+    def equity(self):
+        b = np.asarray(self.samples, np.float64)[..., None] * float(L.EQ_SHARE_UNIT)
+        return np.divide(np.asarray(self.share, np.float64), b, out=np.zeros(np.shape(self.share), np.float64), where=b > 0)
+
+    @property
+    def stderr(self):
+        s = np.broadcast_to(np.asarray(self.samples, np.float64)[..., None], np.shape(self.win))
+        p = np.divide(np.asarray(self.win, np.float64) + np.asarray(self.tie, np.float64), s, out=np.zeros(np.shape(self.win), np.float64), where=s > 0)
+        return np.sqrt(np.divide(p * (1.0 - p), s, out=np.zeros(np.shape(self.win), np.float64), where=s > 0))
+
+    def __getitem__(self, i):
+        return SampledEquity(self.win[i], self.tie[i], self.share[i], self.samples[i], self.status[i])
+
+    def __repr__(self):
+        return 'SampledEquity(samples=%r, status=%r, win=%r, tie=%r, equity=%r)' % (self.samples, self.status, self.win, self.tie, self.equity)
+
+
+def check_samples(samples, nonce=0):
+    """The (samples, nonce) of a sampled-equity call as ints; ValueError outside 1 .. 2^24 / 0 .. 2^32 - 1 (before any device call)."""
+    samples, nonce = int(samples), int(nonce)
+    if not 1 <= samples <= L.EQS_SAMPLES_MAX:
+        raise ValueError('samples must be 1 .. 2^24 per call (more: further calls with other nonces; the counts add)')
+    if not 0 <= nonce <= 0xFFFFFFFF:
+        raise ValueError('nonce must fit 32 bits')
+    return samples, nonce
+
+
+def sampled_equity_batch(holes, board, nboard, live, samples=4096, seed=DEFAULT_SEED, nonce=0, ids=None, device=0):
+    """pk_equity_sampled on host arrays: as showdown_equity_batch, but a 0xFF hole byte at a live seat is HIDDEN and drawn anew in each of the
+    `samples` samples.  ids uint32 [m]: the spots' stream ids (default: the spot index).  Returns a SampledEquity of [m, N] / [m] arrays."""
+    holes = np.ascontiguousarray(holes, np.uint8)
+    if holes.ndim != 3 or holes.shape[2] != 2 or not (L.MIN_PLAYERS <= holes.shape[1] <= L.MAX_PLAYERS):
+        raise ValueError('holes must have shape [m, N, 2] with 2 <= N <= 16')
+    m, n = holes.shape[:2]
+    board = np.ascontiguousarray(board, np.uint8)
+    nboard = np.ascontiguousarray(nboard, np.uint8)
+    live = np.ascontiguousarray(live, np.uint16)
+    if board.shape != (m, 5) or nboard.shape != (m,) or live.shape != (m,):
+        raise ValueError('board must have shape [m, 5], nboard and live shape [m]')
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, np.uint32)
+        if ids.shape != (m,):
+            raise ValueError('ids must have shape [m]')
+    samples, nonce = check_samples(samples, nonce)
+    if m * ((samples + 63) // 64) > 0xFFFFFFFF:
+        raise ValueError('m * ceil(samples / 64) must fit 32 bits: split the batch')
+    win, tie = np.zeros((m, n), np.uint32), np.zeros((m, n), np.uint32)
+    share = np.zeros((m, n), np.uint64)
+    count, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+    L.check(L.lib().pk_equity_sampled(int(device), n, m, L.ptr(holes), L.ptr(board), L.ptr(nboard), L.ptr(live), L.ptr(ids), samples,
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, nonce, L.ptr(win), L.ptr(tie), L.ptr(share), L.ptr(count), L.ptr(status)))
+    return SampledEquity(win, tie, share, count, status)
+
+
+def sampled_equity_d(num_players, m, holes_d, board_d, nboard_d, live_d, samples, ids_d=None, seed=DEFAULT_SEED, nonce=0, win_d=None, tie_d=None,
+                     share_d=None, samples_d=None, status_d=None, device=0, stream=None):
+    """pk_equity_sampled_d: the same on device-resident buffers (device pointers as ints / c_void_p; ids_d and the outputs may be None),
+    asynchronous on `stream`."""
+    samples, nonce = check_samples(samples, nonce)
+    if not (L.MIN_PLAYERS <= int(num_players) <= L.MAX_PLAYERS):
+        raise ValueError('between 2 and 16 seats')
+    L.check(L.lib().pk_equity_sampled_d(int(device), int(num_players), int(m), holes_d, board_d, nboard_d, live_d, ids_d, samples,
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, nonce, win_d, tie_d, share_d, samples_d, status_d, stream))
+
+
+def sampled_equity(hands, board=(), live=None, samples=4096, seed=DEFAULT_SEED, nonce=0, device=0):
+    """One spot.  hands: per seat two cards (Card-likes / 'RS' strings / Card.value ints), either of which may be None = hidden, or None for
+    a seat with both cards hidden; board: 0 .. 5 known cards; live: the seats that show down (iterable of seat numbers or a bit mask; default:
+    EVERY seat -- a hidden hand is drawn).  Returns a SampledEquity with [N] arrays; raises ValueError for an invalid spot."""
+    hands = list(hands)
+    n = len(hands)
+    if not (L.MIN_PLAYERS <= n <= L.MAX_PLAYERS):
+        raise ValueError('between 2 and 16 seats')
+    board = list(board)
+    if len(board) > 5:
+        raise ValueError('at most five board cards')
+    holes = np.full((1, n, 2), UNKNOWN_CARD, np.uint8)
+    for p, h in enumerate(hands):
+        if h is None:
+            continue
+        h = list(h)
+        if len(h) != 2:
+            raise ValueError('seat %d: two hole cards (each a card or None), or None' % p)
+        holes[0, p] = [UNKNOWN_CARD if c is None else _card(c) for c in h]
+    b = np.zeros((1, 5), np.uint8)
+    b[0, :len(board)] = [_card(c) for c in board]
+    if live is None:
+        mask = (1 << n) - 1
+    elif isinstance(live, (int, np.integer)):
+        mask = int(live)
+    else:
+        mask = 0
+        for p in live:
+            if not 0 <= int(p) < n:
+                raise ValueError('live seat %r out of range' % (p,))
+            mask |= 1 << int(p)
+    if mask < 0 or mask >> n:
+        raise ValueError('live mask names seats >= %d' % n)
+    r = sampled_equity_batch(holes, b, np.array([len(board)], np.uint8), np.array([mask], np.uint16), samples, seed, nonce, device=device)[0]
+    if r.status:
+        raise ValueError('invalid spot: ' + equity_status_text(r.status))
+    return r

@@ -99,6 +99,16 @@ class Game:
             raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
         return r
 
+    def equity_sampled(self, observer=None, samples=1024, nonce=0):
+        """Sampled showdown equity of the table as `observer` sees it (VecGame.equity_sampled; None = the active seat): a
+        judger.SampledEquity with [N] arrays.  Not in the reference."""
+        from ._lib import OBSERVER_ACTIVE
+        r = self._v.equity_sampled(observer=OBSERVER_ACTIVE if observer is None else observer, samples=samples, nonce=nonce)[0]
+        if r.status:
+            from .judger import equity_status_text
+            raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
+        return r
+
     def step(self, action):                                                       # :621-700
         """Returns (game_over, hand_over, turn_over); raises the reference's ValueError / NotImplementedError /
         AssertionError in the reference's situations."""

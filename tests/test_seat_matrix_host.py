@@ -1,0 +1,152 @@
+"""CPU pre-flight of tests/test_hip_seat_matrix.py, with the oracle alone: the oracle half of every (seat count, configuration) ends within
+its step budget and below the caps, contains what the configuration is there for, and the comparators of tests/seat_matrix.py reject a
+one-bit change -- so a GPU case cannot pass by comparing nothing.  The figures are printed per (N, configuration) (pytest -s shows them)."""
+import numpy as np
+import pytest
+
+import seat_matrix as M
+
+T_LAST = M.T_MATRIX - 1     # a lane of the ragged wavefront
+CAP_SHARE = 0.05        # ladder / top_seat: at most this share of the tables may run into PK_TERR_HAND_CAP / _ENV_CAP; default: none
+
+
+def cap_limit(kind, T):
+    return 0 if kind == "default" else int(CAP_SHARE * T)
+
+
+@pytest.mark.parametrize("N", M.SEATS)
+@pytest.mark.parametrize("kind", M.KINDS)
+def test_caps_and_content(kind, N):
+    cfg = M.matrix_config(kind, N)
+    T = cfg["T"]
+    # ---- lockstep Game.step: the trace ends (it is a bounded loop over a terminating oracle), caps, side pots
+    capped, paid, resets, over_seen = np.zeros(T, bool), 0, 0, 0
+    for tr in M.game_step_trace(cfg, M.K_GAME, before=True):
+        assert not (tr["eo"] & 2).any(), (tr["s"], "game.py:473: the bounded twin would stop here and compare nothing further")
+        capped |= (tr["eo"] & M.CAPS) != 0
+        resets += int(tr["over"].sum())
+        over_seen += int(M.oracle_views(tr["pre"])[2].sum())
+        paid = max(paid, int(M.seats_paid(tr).max()))
+    fig = dict(game_capped=int(capped.sum()), game_resets=resets, seats_paid=paid, game_over_seen=over_seen)
+    assert capped.sum() <= cap_limit(kind, T), fig
+    assert not any((tr["eo"] & 2).any() for tr in M.game_step_trace(M.matrix_config(kind, N, 1), M.K_GAME)), "game.py:473 at one table"
+    # ---- the same agents' rollout: finished games and showdowns from the counters
+    o = M.oracle_of(cfg)
+    o.reset(dealer=cfg["dealer"])
+    c, err = o.rollout(M.K_GAME, cfg["policy"], True)
+    fig.update(games=int(c[3]), showdowns=int(c[2]))
+    if kind == "default":
+        assert err == 0 and c[3] >= 1 and c[2] >= 1, fig
+    if kind == "ladder":
+        assert paid >= min(N, 4), fig                # side pots formed: that many seats RECEIVED different non-zero amounts in one hand
+        assert over_seen > 0, fig                    # ... and pot / high_bet / game_over are read on finished games
+    # ---- PokerGameEnv.step, one opponent policy and one per seat
+    for T_env in (T, M.T_BATCHES, 1):
+        ecfg = M.matrix_config(kind, N, T_env)
+        st = M.env_want(ecfg, 1 if kind == "ladder" else 0, M.K_ENV)[4]
+        assert st["capped"] <= cap_limit(kind, T_env), (T_env, st["capped"])
+        if T_env == T:
+            fig.update(env_capped=st["capped"], env_done=st["done"])
+            assert st["done"] > 0, fig
+    pols, external = M.multi_seats(cfg)
+    st = M.multi_want(cfg, pols, M.K_MULTI)[1]
+    fig.update(multi_capped=st["capped"])
+    assert st["capped"] <= cap_limit(kind, T), fig
+    for T1 in (1,):
+        c1 = M.matrix_config(kind, N, T1)
+        assert M.multi_want(c1, pols, M.K_MULTI)[1]["capped"] == 0 and M.env_want(c1, 0, M.K_ENV)[4]["capped"] == 0
+    if kind == "top_seat":
+        assert N - 1 in external and (N == 2 or pols[0] != pols[N - 2])
+        y = M.multi_yields(cfg, pols, external, M.K_MULTI)        # (also: the twin replay ends in the oracle's own state)
+        fig.update(yields_to_top_seat=y[N - 1])
+        assert y[N - 1] >= 1, fig
+        ik = M.in_kernel_seats(cfg)
+        assert M.env_want(cfg, ik, M.K_MULTI, seat0=0)[4]["capped"] <= cap_limit(kind, T) and (N == 2 or ik[0] != ik[N - 2])
+    # ---- call-agent rollout, and the tables the snapshot / equity families start from
+    o = M.oracle_of(cfg)
+    o.reset(dealer=cfg["dealer"])
+    c, err = o.rollout(M.k_call(N), 2, True)
+    assert err == 0 and c[0] == T * M.k_call(N) and c[1] > 0, c
+    snap = M.played_oracle(cfg, M.K_PLAYED, M.extra_call(kind, N)).snapshot()
+    fig.update(past_the_flop=int((snap["turn"] >= 1).sum()))
+    assert len(M.equity_tables(snap["turn"])) == M.EQUITY_FIRST, fig
+    print("seat matrix %-8s N=%2d: capped share %.3f (game) %.3f (env) %.3f (multi) | %s"
+          % (kind, N, fig["game_capped"] / T, fig["env_capped"] / T, fig["multi_capped"] / T, fig))
+
+
+def test_the_top_seat_configuration_wraps_the_table_ids():
+    cfg = M.matrix_config("top_seat", 16)
+    assert cfg["base"] + cfg["T"] > 2 ** 32 > cfg["base"] and cfg["top"] == 15
+    assert M.T_MATRIX % 64 == 37 and M.T_MATRIX // 64 == 2 and M.T_BATCHES == 3 * 64 + 5
+
+
+# ------------------------------------------------------------------ the comparators reject a one-bit change
+def _flip_low_bit(x):
+    x.view(np.uint64)[...] ^= np.uint64(1)
+
+
+def test_comparators_reject_one_bit():
+    cfg = M.matrix_config("default", 6)
+    want, rows, acts, o, _ = M.env_want(cfg, 0, 6)
+    k = next(i for i, w in enumerate(want) if w[0].any())
+    good = tuple(x.copy() for x in want[k])
+    M.assert_delivered(good, want[k], "unchanged")
+    t = int(np.argmax(want[k][0] != 0))
+    bad = tuple(x.copy() for x in want[k])
+    _flip_low_bit(bad[0][t:t + 1])                              # the low mantissa bit of one delivered reward
+    assert bad[0][t] != want[k][0][t] and abs(bad[0][t] - want[k][0][t]) < 1e-12
+    with pytest.raises(AssertionError, match="reward"):
+        M.assert_delivered(bad, want[k], "reward bit")
+    bad = tuple(x.copy() for x in want[k])
+    bad[3][T_LAST] ^= 1                                         # one terr byte
+    with pytest.raises(AssertionError, match="terr"):
+        M.assert_delivered(bad, want[k], "terr byte")
+    # ... of the [K, T] form the bounded drivers index, too
+    W = [np.stack([w[i] for w in want]) for i in range(4)]
+    idx, cnt = np.arange(cfg["T"]), np.full(cfg["T"], k)
+    got = [x[cnt, idx].copy() for x in W]
+    M.assert_delivered(tuple(got), tuple(x[cnt, idx] for x in W), "unchanged, indexed")
+    _flip_low_bit(got[0][t:t + 1])
+    with pytest.raises(AssertionError, match="reward"):
+        M.assert_delivered(tuple(got), tuple(x[cnt, idx] for x in W), "reward bit, indexed")
+    # observation rows: one element of the dense row, one byte of the packed row
+    dense, packed = M.oracle_rows(o.snapshot(), cfg["N"])
+    mask = np.ones(cfg["T"], bool)
+    assert M.assert_rows(dense.copy(), packed.copy(), dense, packed, mask, "unchanged") == 2 * cfg["T"]
+    d = dense.copy()
+    _flip_low_bit(d[T_LAST, 17:18])                             # (a stack: its low mantissa bit)
+    with pytest.raises(AssertionError, match="dense row"):
+        M.assert_rows(d, None, dense, packed, mask, "row element")
+    mask_off = mask.copy()
+    mask_off[T_LAST] = False
+    M.assert_rows(d, None, dense, packed, mask_off, "row element of a table outside the mask")
+    p = packed.copy()
+    p[T_LAST, 2] ^= 1
+    with pytest.raises(AssertionError, match="packed row"):
+        M.assert_rows(None, p, dense, packed, mask, "packed byte")
+    # flags / terr of Game.step
+    tr = next(M.game_step_trace(cfg, 1))
+    M.assert_flags(tr["fo"].copy(), tr["eo"].copy(), tr["fo"], tr["eo"], False, "unchanged")
+    te = tr["eo"].copy()
+    te[T_LAST] ^= 1
+    with pytest.raises(AssertionError, match="flags / terr"):
+        M.assert_flags(tr["fo"].copy(), te, tr["fo"], tr["eo"], False, "terr byte")
+
+
+def test_oracle_rows_are_the_host_mirror_s_rows():
+    """oracle_rows restates the row layouts: its packed rows unpack (pokerl_amd.unpack_obs) to its dense rows, and a StateView built from a
+    dense row reads the oracle's fields."""
+    from pokerl_amd.state_view import StateView, packed_dtype, unpack_obs
+    for kind, N in (("default", 2), ("ladder", 9), ("top_seat", 16)):
+        cfg = M.matrix_config(kind, N)
+        snap = M.played_oracle(cfg, 25, 5).snapshot()
+        dense, packed = M.oracle_rows(snap, N)
+        assert packed.shape[1] == packed_dtype(N).itemsize
+        assert unpack_obs(packed, N).tobytes() == dense.tobytes()
+        for t in (0, 64, T_LAST):
+            sv = StateView(dense[t], N)
+            nvis = 0 if snap["turn"][t] == 0 else snap["turn"][t] + 2
+            assert sv.player == snap["active"][t] and sv.turn == snap["turn"][t] and sv.minimum_raise_value == snap["min_raise"][t]
+            assert [c.value for c in sv.community_cards] == snap["cards"][t, :nvis].tolist()
+            assert [c.value for c in sv.player_cards] == snap["cards"][t, 5 + 2 * sv.player:7 + 2 * sv.player].tolist()
+            assert sv.credits.tobytes() == snap["credits"][t].tobytes() and sv.pending_bets.tobytes() == snap["pending"][t].tobytes()

@@ -1,7 +1,9 @@
 // pk_table_kernels.hpp -- the per-seat-count __global__ kernel templates of libpokerl_hip.so: everything pk_tables.hip instantiates and pk_api.hip
 // launches (the state machine they run: pk_device.hpp; the kernels that are no templates: pk_util_kernels.hpp).  gfx950 only.
 #pragma once
+#ifndef PK_HOST_SIM  // tools/host_sim (dev-only CPU builds of the kernel bodies) supplies shims instead
 #include <hip/hip_runtime.h>
+#endif
 
 #include "pk_device.hpp"
 
@@ -152,10 +154,14 @@ __device__ __forceinline__ void rollout_body(const State *__restrict__ Sp, const
     constexpr int policy = POLICY;
     const auto &S = *as_global(Sp);
     using LDS = std::conditional_t<TAB, LdsTab<N, POLICY == PK_POLICY_RANDOM>, Lds<N>>;
-    __shared__ LDS lds;
+    PK_SHARED_OBJECT(LDS, lds);
     if constexpr (TAB) {     // the workgroup's copy of the evaluator's table: 32 x (16-byte load + 16-byte LDS write) per lane, eight loads in flight
         static_assert(ONE_PASS && POLICY != PK_POLICY_EXTERNAL, "k_rollout_tab is a fused-rollout kernel");
+#ifdef PK_HOST_SIM
+        struct alignas(16) u32x4 { uint32_t v[4]; };
+#else
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+#endif
         const auto g_tab = (PK_GLOBAL const u32x4 *)as_global(S.evtab);
         const int lane0 = threadIdx.x & (PK_WAVE - 1);
 #pragma unroll 1
@@ -172,6 +178,7 @@ __device__ __forceinline__ void rollout_body(const State *__restrict__ Sp, const
     const uint32_t table_id = H.table_id_base + (uint32_t)t;
     Table<N> tb;
     uint32_t owed = 0;
+    if constexpr (TAB) { if constexpr (LDS::PAIRS) Table<N>::seed_dummy(lds); }   // (before stage_fresh's barrier)
     Table<N>::stage_fresh(lds, H.fresh);
     if constexpr (!TAB || POLICY == PK_POLICY_RANDOM) stage_nth(lds);      // (the table variant of the all-in agents has no such table: LdsTab<N, false>)
     constexpr bool EXTERNAL = POLICY == PK_POLICY_EXTERNAL;
@@ -195,7 +202,7 @@ __device__ __forceinline__ void rollout_body(const State *__restrict__ Sp, const
     }
     int nend = 0;
     uint32_t late = (live ? 1u : 0u) | (ext_ok ? 2u : 0u);   // the epilogue's lane predicates travel through the loop in ONE VGPR
-    if (EXTERNAL) asm volatile("" : "+v"(late));               // (as lane masks: an SGPR pair each, live across the loop; see env_step_body)
+    if (EXTERNAL) PK_PIN_VGPR(late);                           // (as lane masks: an SGPR pair each, live across the loop; see env_step_body)
     // lanes that can work at all in this launch; the launch ends once more than `slack` of them have run out of work
     // (slack >= 64: never, i.e. run to completion)
     const int cap = __popcll(__ballot(live && (owed > 0 || tb.lstate == LS_END)));
@@ -268,7 +275,7 @@ __device__ __forceinline__ void rollout_body(const State *__restrict__ Sp, const
     // side pots restart from the unchanged committed bets), so the next launch redoes it together with its own arrivals.
     if (tb.lstate == LS_POT) { tb.lstate = LS_END; tb.evals -= (uint32_t)__popc((tb.st_called | tb.st_allin) & Table<N>::FULL); }
     if (EXTERNAL) {
-        asm volatile("" : "+v"(late));
+        PK_PIN_VGPR(late);
         const bool ext_ok_l = late & 2u;
         if (late & 1u) {
             const auto flags_out = as_global(ext->flags), terr_out = as_global(ext->terr);

@@ -129,6 +129,11 @@ int pk_create(pk_handle **out, int device, int num_tables, int num_players, cons
 int pk_destroy(pk_handle *h);
 int pk_num_tables(const pk_handle *h);
 int pk_num_players(const pk_handle *h);
+/* How pk_create laid the tables out over wavefronts (read-only; fixed for the handle's life).  tables_per_wave: a power of two, 1 .. 64 --
+ * small batches are spread over the chip: 64 halved while num_tables <= 1024 * (tables_per_wave / 2), so 1 up to 1 024 tables and 64 only
+ * above 32 768 (knob: env PK_TPB); a wave's lanes >= tables_per_wave are dead.  env_tables_per_wave: the same of the PokerGameEnv kernels
+ * (env PK_ENV_TPB, a power of two; default tables_per_wave).  Results do not depend on either.  NULL arguments: PK_E_INVALID_ARG. */
+int pk_get_wave_shape(pk_handle *h, int *tables_per_wave, int *env_tables_per_wave);
 
 /* Game.reset(dealer=...), pokerl/game.py:397-412, on tables with mask[t] != 0 (mask NULL = all tables). */
 int pk_reset(pk_handle *h, const uint8_t *mask, int dealer);

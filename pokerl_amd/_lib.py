@@ -38,7 +38,7 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_env_step_begin", "pk_env_step_end", "pk_reset_d", "pk_step_auto_d", "pk_stream_pool_drain", "pk_step_async_d", "pk_set_step_obs", "pk_build_info",
            "pk_snapshot_bytes", "pk_save_tables_d", "pk_load_tables_d", "pk_save_tables", "pk_load_tables", "pk_clone_tables_d",
            "pk_equity_d", "pk_equity", "pk_table_equity_d", "pk_table_equity",
-           "pk_equity_sampled_d", "pk_equity_sampled", "pk_table_equity_sampled_d", "pk_table_equity_sampled"]
+           "pk_equity_sampled_d", "pk_equity_sampled", "pk_table_equity_sampled_d", "pk_table_equity_sampled", "pk_get_wave_shape"]
 
 
 class PokerlHipError(RuntimeError):
@@ -68,6 +68,7 @@ def lib():
     L.pk_destroy.argtypes = [_vp]
     L.pk_num_tables.argtypes = [_vp]
     L.pk_num_players.argtypes = [_vp]
+    L.pk_get_wave_shape.argtypes = [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.pk_reset.argtypes = [_vp, _vp, C.c_int]
     L.pk_reset_d.argtypes = [_vp, _vp, C.c_int, C.c_int]
     L.pk_step.argtypes = [_vp, _vp, _vp, _vp]

@@ -687,6 +687,11 @@ int pk_stream_pool_drain(int device) {
 
 int pk_num_tables(const pk_handle *h) { return h ? h->T : PK_E_INVALID_ARG; }
 int pk_num_players(const pk_handle *h) { return h ? h->N : PK_E_INVALID_ARG; }
+int pk_get_wave_shape(pk_handle *h, int *tables_per_wave, int *env_tables_per_wave) {
+    if (!h || !tables_per_wave || !env_tables_per_wave) return h ? h->fail(PK_E_INVALID_ARG, "pk_get_wave_shape: NULL argument") : PK_E_INVALID_ARG;
+    *tables_per_wave = h->tpb; *env_tables_per_wave = h->env_tpb;
+    return PK_OK;
+}
 
 // ---- stream control: how a caller with its own stream (a learner on the same GPU) orders its work against ours
 int pk_get_stream(pk_handle *h, void **stream_out) {

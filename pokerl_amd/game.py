@@ -253,6 +253,14 @@ class VecGame:
     def record_event(self, event):
         L.check(self._lib.pk_record_event(self._h, C.c_void_p(event) if isinstance(event, int) else event), self._h)
 
+    @property
+    def wave_shape(self):
+        """(tables per wavefront, ... of the PokerGameEnv kernels) as pk_create laid this handle out (pk_get_wave_shape): powers of two, 64
+        only above 32 768 tables unless PK_TPB / PK_ENV_TPB say otherwise.  Results do not depend on it."""
+        a, b = C.c_int(), C.c_int()
+        L.check(self._lib.pk_get_wave_shape(self._h, C.byref(a), C.byref(b)), self._h)
+        return a.value, b.value
+
     # ------------------------------------------------------------------ RNG-spec serials (checkpoint / resume)
     def _serials(self):
         hs = np.zeros(self.num_tables, np.uint64)

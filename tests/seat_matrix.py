@@ -11,13 +11,22 @@ from oracle import loader as O
 from oracle import rng_spec as R
 
 SEATS = list(range(2, 17))
-T_MATRIX = 165                 # two full wavefronts and a ragged one of 37 lanes
-T_BATCHES = 3 * 64 + 5         # B = 2 sub-batches: a range is whole waves
+T_MATRIX = 165                 # 64 + 64 + 37 lanes ONLY at 64 tables per wave (shape "full"); pk_create's own choice at this size is one table per wave
+T_BATCHES = 3 * 64 + 5         # B = 2 sub-batches: a range is whole 64-table blocks (batch_ranges)
 CAPS = O.ERR_HAND_CAP | O.ERR_ENV_CAP
 PS_BROKEN = 4
 KINDS = ("default", "ladder", "top_seat")
+RESUMED = "resumed"            # the fourth configuration: default, with the RNG streams resumed just below 2^32 (matrix_config)
+ALL_KINDS = KINDS + (RESUMED,)
+RESUMED_SEATS = (2, 6, 9, 13, 16)
+RESUMED_SERIALS = (2 ** 32 - 2, 2 ** 35 - 5)     # (hand_serial, step_serial): the action-block index step_serial >> 3 is 2^32 - 1
+# How pk_create lays the tables out over wavefronts (PK_TPB; None: its own rule, tpb_rule).  spread: what a caller gets -- one table per wave at
+# the matrix's sizes.  full: waves of 64, 64 and 37 live lanes.  part: twenty waves of 8 live lanes and one of 5, lanes >= 8 dead inside the wave --
+# the shape every caller between 1 025 and 32 768 tables gets.
+WAVE_SHAPES = {"spread": None, "full": 64, "part": 8}
 # steps per family in the matrix (a case is to take a few seconds); tests/test_seat_matrix_host.py checks the caps at the same budgets
 K_GAME, K_ENV, K_MULTI, K_PLAYED = 40, 15, 15, 40
+K_ROLLOUT = 48                 # the fused rollout family: launches of 16, 25 and 7 steps -- the first two long enough for k_rollout_tab / k_rollout_allin_tab
 BUDGETS = (1, 3)               # hand ends / Game.steps per launch of the bounded forms
 
 
@@ -26,16 +35,69 @@ def k_call(N):
     return max(40, 6 * N)
 
 
+def k_of(family, kind, N):
+    """Steps of `family` (a driver's name) in configuration `kind`.  The resumed configuration needs three tables in four to end two hands
+    inside the run, so that hand_serial 2^32 is dealt; tests/test_seat_matrix_host.py holds the oracle half to that at these very K, and they
+    suffice as they are (random agents end a hand within a few steps) -- a family that missed it would get a longer K for RESUMED here."""
+    return {"game_step": K_GAME, "game_step_async": K_GAME, "env_step": K_ENV, "rollout": K_ROLLOUT, "rollout_call": k_call(N)}[family]
+
+
+# ------------------------------------------------------------------ wave shapes
+def tpb_rule(T):
+    """Tables per wavefront as pk_create picks them without a knob (include/pokerl_hip.h, pk_get_wave_shape), restated: 64 halved while the
+    batch fits 1 024 waves of half as many -- 1 up to 1 024 tables, 64 only above 32 768."""
+    tpb = 64
+    while tpb > 1 and T <= 1024 * (tpb // 2):
+        tpb //= 2
+    return tpb
+
+
+def use_shape(monkeypatch, shape):
+    """Sets the environment a handle created from now on reads its wave shape from; PK_ENV_TPB goes, so that the env kernels follow PK_TPB."""
+    if WAVE_SHAPES[shape] is None:
+        monkeypatch.delenv("PK_TPB", raising=False)
+    else:
+        monkeypatch.setenv("PK_TPB", str(WAVE_SHAPES[shape]))
+    monkeypatch.delenv("PK_ENV_TPB", raising=False)
+
+
+def shape_demand(cfg):
+    """(tables per wave, ... of the env kernels) that cfg's shape demands of every handle made for it."""
+    tpb = WAVE_SHAPES[cfg["shape"]] or tpb_rule(cfg["T"])
+    return tpb, tpb
+
+
+def assert_shape(g, cfg):
+    """Every handle a driver makes: the shape the case names is the shape that runs (a case must not silently run one table per wave).
+    Configurations that name no shape (the fuzz tools') claim none."""
+    if cfg.get("shape") is not None:
+        assert g.wave_shape == shape_demand(cfg), (where_of(cfg), "wave shape", g.wave_shape, shape_demand(cfg))
+    return g
+
+
+def batch_ranges(T, B):
+    """The contiguous table ranges pk_set_env_batches(h, B) cuts T tables into, by the rule its header states: ceil(T / B) tables rounded up
+    to whole 64-table blocks per range, as many ranges as that takes (fewer than B for a small batch)."""
+    size = -(-(-(-T // B)) // 64) * 64
+    return [(b, min(b + size, T)) for b in range(0, T, size)]
+
+
 # ------------------------------------------------------------------ configurations
-def matrix_config(kind, N, T=T_MATRIX):
-    """The matrix's three configurations at N seats.  default: stacks 100, blinds 2 / 1, random agents.  ladder: per-seat stacks 5 (p + 1),
+def matrix_config(kind, N, T=T_MATRIX, shape="spread"):
+    """The matrix's configurations at N seats.  default: stacks 100, blinds 2 / 1, random agents.  ladder: per-seat stacks 5 (p + 1),
     all-in agents, first dealer N - 1 -- every hand an N-way showdown with up to N - 1 side-pot levels.  top_seat: table ids that wrap
-    inside the batch, and seat N - 1 wherever a family takes a seat."""
-    cfg = dict(kind=kind, T=T, N=N, start=100, bb=2, sb=1, seed=0x5EA7 * 1000003 + 7919 * N + KINDS.index(kind), base=0, dealer=0, policy=0, top=None)
+    inside the batch, and seat N - 1 wherever a family takes a seat.  resumed: default with the serials set to RESUMED_SERIALS before the
+    first reset -- that reset deals hand_serial 2^32 - 2, the first hand end 2^32 - 1 (a lone table's stock of four decks then spans the
+    carry into the high counter word), the second 2^32; the action-block index crosses 2^32 after five Game.steps.
+    `shape`: the wave shape the drivers demand of every handle (WAVE_SHAPES; the caller sets it with use_shape)."""
+    cfg = dict(kind=kind, T=T, N=N, start=100, bb=2, sb=1, seed=0x5EA7 * 1000003 + 7919 * N + ALL_KINDS.index(kind), base=0, dealer=0, policy=0, top=None,
+               shape=shape, serials=None)
     if kind == "ladder":
         cfg.update(start=[5.0 * (p + 1) for p in range(N)], policy=1, dealer=N - 1)
     elif kind == "top_seat":
         cfg.update(base=2 ** 32 - 100, top=N - 1)
+    elif kind == RESUMED:
+        cfg.update(serials=RESUMED_SERIALS)
     elif kind != "default":
         raise ValueError(kind)
     return cfg
@@ -65,15 +127,40 @@ def in_kernel_seats(cfg):
 
 
 def where_of(cfg, what=""):
-    return "%s N=%d T=%d %s" % (cfg["kind"] if "kind" in cfg else "cfg", cfg["N"], cfg["T"], what)
+    return "%s N=%d T=%d %s%s" % (cfg["kind"] if "kind" in cfg else "cfg", cfg["N"], cfg["T"], "shape=%s " % cfg["shape"] if cfg.get("shape") else "", what)
 
 
 def oracle_of(cfg):
-    return O.OracleGame(cfg["T"], cfg["N"], cfg["start"], cfg["bb"], cfg["sb"], seed=cfg["seed"], table_id_base=cfg["base"])
+    o = O.OracleGame(cfg["T"], cfg["N"], cfg["start"], cfg["bb"], cfg["sb"], seed=cfg["seed"], table_id_base=cfg["base"])
+    if cfg.get("serials"):
+        o.set_serials(*cfg["serials"])
+    return o
 
 
 def backend_of(HB, cfg):
-    return HB(cfg["T"], cfg["N"], cfg["start"], cfg["bb"], cfg["sb"], seed=cfg["seed"], table_id_base=cfg["base"])
+    h = HB(cfg["T"], cfg["N"], cfg["start"], cfg["bb"], cfg["sb"], seed=cfg["seed"], table_id_base=cfg["base"])
+    assert_shape(h.g, cfg)
+    if cfg.get("serials"):
+        h.set_serials(*cfg["serials"])
+    return h
+
+
+def env_of(agents, cfg):
+    """A VecPokerGameEnv of cfg's tables (opponents: one policy or a list of agents), its shape asserted, its serials set before the first reset."""
+    import pokerl_amd
+    env = pokerl_amd.VecPokerGameEnv(agents, **env_kwargs(cfg))
+    assert_shape(env.game, cfg)
+    if cfg.get("serials"):
+        env.game.set_serials(*cfg["serials"])
+    return env
+
+
+def crossed(snap0, snap1):
+    """A resumed run between two oracle snapshots: (every table's action-block index step_serial >> 3 starts below 2^32 and ends at or above
+    it, the number of tables whose hand_serial ends above 2^32 -- the deal of serial 2^32 itself has happened there)."""
+    b0, b1 = np.asarray(snap0["step_serial"], np.uint64) >> np.uint64(3), np.asarray(snap1["step_serial"], np.uint64) >> np.uint64(3)
+    return bool((b0 < 2 ** 32).all() and (b1 >= 2 ** 32).all() and (np.asarray(snap0["hand_serial"], np.uint64) < 2 ** 32).all()), \
+        int((np.asarray(snap1["hand_serial"], np.uint64) > 2 ** 32).sum())
 
 
 def env_kwargs(cfg):
@@ -370,7 +457,6 @@ def env_step(cfg, opp, K, passes, B=1, exact_batches=True):
     call (pk_env_step_fused_d: seat 0 in-kernel, reset and observation row in the launch), and bounded launches (pk_env_step_async_d with
     `passes` Game.steps per launch; B > 1: in sub-batches, pk_set_env_batches) whose per-table delivered (reward, done, hand, terr, row)
     sequence must be the fused call's.  Returns counts."""
-    import pokerl_amd
     from pokerl_amd import _lib as L
     from pokerl_amd.hipmem import DeviceBuffer
     lib = L.lib()
@@ -383,7 +469,7 @@ def env_step(cfg, opp, K, passes, B=1, exact_batches=True):
                    obs.download(np.float64, T * D).reshape(T, D))
     st = dict(delivered=0, sub=0, launches=0)
     # ---- the host form: pk_env_step, then pk_env_reset of the episodes that ended (errors of that reset stay in the handle)
-    env = pokerl_amd.VecPokerGameEnv(opp, **env_kwargs(cfg))
+    env = env_of(opp, cfg)
     env.reset()
     for k in range(K):
         ob, r, d, h, e = env.step(acts[k], strict=False)
@@ -396,7 +482,7 @@ def env_step(cfg, opp, K, passes, B=1, exact_batches=True):
     GU.assert_snap(_env_snapshot(env), o.snapshot(), where + " pk_env_step")
     env.close()
     # ---- fused
-    env = pokerl_amd.VecPokerGameEnv(opp, **env_kwargs(cfg))
+    env = env_of(opp, cfg)
     g = env.game
     env.reset()
     sync = []
@@ -410,12 +496,14 @@ def env_step(cfg, opp, K, passes, B=1, exact_batches=True):
     GU.assert_snap(_env_snapshot(env), o.snapshot(), where + " fused")
     env.close()
     # ---- bounded launches of the same tables
-    env = pokerl_amd.VecPokerGameEnv(opp, **env_kwargs(cfg))
+    env = env_of(opp, cfg)
     g = env.game
     env.reset()
     nb = env.set_env_batches(B) if B > 1 else 1
-    if B > 1 and exact_batches:                      # (a small batch is cut into fewer ranges than asked for: a range is whole waves)
+    ranges = batch_ranges(T, B)                      # the split the header's rule gives, under any wave shape (not read back from the handle)
+    if B > 1 and exact_batches:                      # (a small batch is cut into fewer ranges than asked for: a range is whole 64-table blocks)
         assert nb == B and env.last_range()[1] % 64 == 0, (where, nb, env.last_range())
+        assert nb == len(ranges) and env.last_range() == ranges[0] + (True,), (where, nb, env.last_range(), ranges)
     st["sub"] = int(nb > 1)
     W = [np.stack([s[i] for s in sync]) for i in range(5)]
     count = np.zeros(T, np.int64)
@@ -429,6 +517,7 @@ def env_step(cfg, opp, K, passes, B=1, exact_batches=True):
         r = ready.download(np.uint8, T) != 0
         if nb > 1:                                   # one range was launched; outputs are complete inside the DELIVERED range only
             db, de, fresh = env.last_range()
+            assert not exact_batches or (db, de) in ranges, (where, (db, de), ranges)
             if fresh:
                 continue
             inside = np.zeros(T, bool)
@@ -534,7 +623,7 @@ def env_multi(cfg, pols, external, K, passes, cap=6000):
     W, _ = multi_want(cfg, pols, K)
     agents = [(lambda st: 0) if s in external else [pokerl_amd.RandomAgent(), pokerl_amd.AllInAgent(), pokerl_amd.CallAgent()][pols[s - 1]]
               for s in range(1, N)]
-    env = pokerl_amd.VecPokerGameEnv(agents, **env_kwargs(cfg))
+    env = env_of(agents, cfg)
     g = env.game
     rew, done, hand, terr, obs, who, ready, act, rst = bufs = [DeviceBuffer(n) for n in (T * 8, T, T, T, T * D * 8, T, T, T * 4, T)]
     count = np.full(T, -1, np.int64)                  # -1: the delivery of the initial reset is still to come
@@ -585,7 +674,7 @@ def env_in_kernel_seats(cfg, pols, K):
     import pokerl_amd
     where = where_of(cfg, "in-kernel pols=%s" % (pols,))
     agents = [[pokerl_amd.RandomAgent(), pokerl_amd.AllInAgent(), pokerl_amd.CallAgent()][p] for p in pols]
-    env = pokerl_amd.VecPokerGameEnv(agents, **env_kwargs(cfg))
+    env = env_of(agents, cfg)
     o = oracle_of(cfg)
     env.reset(); o.env_reset(None, list(pols))
     for k in range(K):
@@ -633,7 +722,7 @@ def rollout_then_lockstep(HB, cfg, K, lock=6, split=True):
     GU.assert_snap(h.snapshot(), o.snapshot(), where + " reset")
     co, _ = o.rollout(K, policy, True)
     if split:
-        k1 = K // 3
+        k1 = K // 3                                                  # (K >= 48: both deferred launches are >= 16 steps, which k_rollout_tab / _allin_tab take up to 6 / 10 seats)
         h.g.rollout(k1, policy, True, True, counters=False)          # deferred launches of mixed lengths ...
         h.g.rollout(K - k1 - 7, policy, True, True, counters=False)
         ch = h.rollout(7, policy, True)                              # ... and a completing one
@@ -698,6 +787,7 @@ def snapshots(HB, cfg, K, extra_call=0, observer="active", nonce=5):
     # the redeal first (it reads the handle as it stands)
     seed2, base2 = 0xABCDEF12345, 2 ** 32 - 7
     d = pokerl_amd.VecGame(T, num_players=N, start_credits=cfg["start"], big_blind=cfg["bb"], small_blind=cfg["sb"], seed=seed2, table_id_base=base2)
+    assert_shape(d, cfg)
     d.reset()
     rng = np.random.default_rng(N)
     perm = rng.permutation(T).astype(np.int32)

@@ -1,10 +1,19 @@
 """Every table-kernel family at every seat count 2 .. 16 (one template instantiation of pk_tables.hip each) against the CPU oracle, through
-the shared drivers of tests/seat_matrix.py: one case per (seat count, family), so a failure names the instantiation.
+the shared drivers of tests/seat_matrix.py: one case per (seat count, family, wave shape), so a failure names the instantiation and the shape.
 
-Shapes: 165 tables (two full wavefronts and a ragged one of 37 lanes), one table for the step and env families, 197 tables in two
-sub-batches.  Configurations per case: default, ladder (N-way showdowns with up to N - 1 side-pot levels) and top_seat (table ids that
+Wave shapes (seat_matrix.WAVE_SHAPES): pk_create spreads a small batch over the chip -- 64 tables per wave halved while the batch fits 1 024
+waves of half as many -- so the matrix's 165 tables run ONE table per wave (`spread`: 63 dead lanes, no cross-lane code sees two live lanes)
+unless PK_TPB says otherwise.  `full` (PK_TPB=64) makes them two full wavefronts and a ragged one of 37 lanes; `part` (PK_TPB=8) twenty
+waves of 8 live lanes and one of 5, the other lanes dead inside the wave -- what a caller between 1 025 and 32 768 tables gets.  Every driver
+asserts VecGame.wave_shape on every handle it makes, so a case cannot silently run narrow.  The ids of the `spread` cases are the ones the
+matrix had before it knew shapes ("N-family"); every other id ends in its shape.
+
+Batches: 165 tables, one table for the step and env families (under `spread` only: it is the same launch under any shape), 197 tables in
+two sub-batches.  Configurations per case: default, ladder (N-way showdowns with up to N - 1 side-pot levels) and top_seat (table ids that
 wrap inside the batch, seat N - 1 wherever the family takes a seat) -- seat_matrix.matrix_config; tests/test_seat_matrix_host.py shows on the
-CPU that each of them contains what it is there for and stays below the caps."""
+CPU that each of them contains what it is there for and stays below the caps.  A fourth configuration, resumed (RNG streams resumed so that
+hand_serial and the action-block index step_serial >> 3 both cross 2^32 inside the run), has cases of its own: full waves (plus the lone
+table of game_step and env_step, whose deals come from a stock of four decks) at 2, 6, 9, 13 and 16 seats."""
 import pytest
 
 import seat_matrix as M
@@ -19,70 +28,121 @@ def HB():
     return HipBackend
 
 
-def game_step(HB, N):
-    for kind in M.KINDS:
-        for T in (M.T_MATRIX, 1):
-            st = M.game_step(HB, M.matrix_config(kind, N, T), M.K_GAME)
-            assert st["rows"] == 3 * T * M.K_GAME and st["views"] == 6 * T * M.K_GAME, (kind, T, st)
+def game_step(HB, N, shape="spread", kinds=M.KINDS):
+    for kind in kinds:
+        K = M.k_of("game_step", kind, N)
+        for T in (M.T_MATRIX, 1) if shape == "spread" or kind == M.RESUMED else (M.T_MATRIX,):
+            st = M.game_step(HB, M.matrix_config(kind, N, T, shape), K)
+            assert st["rows"] == 3 * T * K and st["views"] == 6 * T * K, (kind, T, st)
 
 
-def game_step_async(HB, N):
-    for kind in M.KINDS:
-        for T, budget in [(M.T_MATRIX, b) for b in M.BUDGETS] + [(1, M.BUDGETS[-1])]:
-            st = M.game_step_async(HB, M.matrix_config(kind, N, T), M.K_GAME, max_hands=budget)
+def game_step_async(HB, N, shape="spread", kinds=M.KINDS):
+    for kind in kinds:
+        K = M.k_of("game_step_async", kind, N)
+        for T, budget in [(M.T_MATRIX, b) for b in M.BUDGETS] + [(1, M.BUDGETS[-1])] * (shape == "spread"):
+            st = M.game_step_async(HB, M.matrix_config(kind, N, T, shape), K, max_hands=budget)
             # (the pre-flight shows that no matrix configuration meets game.py:473, so the twin runs to the drain and its state is compared)
             assert st["drained"] and st["async_steps"] > 0 and st["rows"] == st["async_steps"], (kind, T, budget, st)
 
 
-def env_step(HB, N):
-    for kind in M.KINDS:
+def env_step(HB, N, shape="spread", kinds=M.KINDS):
+    for kind in kinds:
+        K = M.k_of("env_step", kind, N)
         opp = 1 if kind == "ladder" else 0
-        for T, passes in [(M.T_MATRIX, b) for b in M.BUDGETS] + [(1, M.BUDGETS[-1])]:
-            st = M.env_step(M.matrix_config(kind, N, T), opp, M.K_ENV, passes)
-            assert st["delivered"] == T * M.K_ENV, (kind, T, st)
+        for T, passes in [(M.T_MATRIX, b) for b in M.BUDGETS] + [(1, M.BUDGETS[-1])] * (shape == "spread" or kind == M.RESUMED):
+            st = M.env_step(M.matrix_config(kind, N, T, shape), opp, K, passes)
+            assert st["delivered"] == T * K, (kind, T, st)
 
 
-def env_batches(HB, N):
-    for kind in M.KINDS:
-        st = M.env_step(M.matrix_config(kind, N, M.T_BATCHES), 1 if kind == "ladder" else 0, M.K_ENV, 3, B=2)
+def env_batches(HB, N, shape="spread", kinds=M.KINDS):
+    for kind in kinds:
+        st = M.env_step(M.matrix_config(kind, N, M.T_BATCHES, shape), 1 if kind == "ladder" else 0, M.K_ENV, 3, B=2)
         assert st["sub"] == 1 and st["delivered"] == M.T_BATCHES * M.K_ENV, (kind, st)
 
 
-def env_multi(HB, N):
-    for kind in M.KINDS:
-        for T, passes in [(M.T_MATRIX, b) for b in M.BUDGETS] + [(1, M.BUDGETS[0])]:
-            cfg = M.matrix_config(kind, N, T)
+def env_multi(HB, N, shape="spread", kinds=M.KINDS):
+    for kind in kinds:
+        for T, passes in [(M.T_MATRIX, b) for b in M.BUDGETS] + [(1, M.BUDGETS[0])] * (shape == "spread"):
+            cfg = M.matrix_config(kind, N, T, shape)
             pols, external = M.multi_seats(cfg)
             st = M.env_multi(cfg, pols, external, M.K_MULTI, passes)
             assert st["delivered"] == T * M.K_MULTI, (kind, T, st)
             if kind == "top_seat" and T > 1:
                 assert st["yields_by_seat"][N - 1] > 0, (kind, st)       # the top nibble was played by the caller
-    cfg = M.matrix_config("top_seat", N)
+    cfg = M.matrix_config("top_seat", N, shape=shape)
     M.env_in_kernel_seats(cfg, M.in_kernel_seats(cfg), M.K_MULTI)
 
 
-def rollout_call(HB, N):
-    for kind in M.KINDS:
-        c = M.rollout_call(HB, M.matrix_config(kind, N), M.k_call(N))
-        assert c[0] == M.T_MATRIX * M.k_call(N) and c[1] > 0, (kind, c)
+def rollout_call(HB, N, shape="spread", kinds=M.KINDS):
+    for kind in kinds:
+        K = M.k_of("rollout_call", kind, N)
+        c = M.rollout_call(HB, M.matrix_config(kind, N, shape=shape), K)
+        assert c[0] == M.T_MATRIX * K and c[1] > 0, (kind, c)
 
 
-def snapshots(HB, N):
-    for kind in M.KINDS:
-        M.snapshots(HB, M.matrix_config(kind, N), M.K_PLAYED, extra_call=M.extra_call(kind, N), observer=N - 1 if kind == "top_seat" else "active")
+def rollout(HB, N, shape="spread", kinds=M.KINDS):
+    """The fused rollout of the configuration's own agents (random; all-in for the ladder) in deferred launches of K // 3 and K - K // 3 - 7
+    steps (16 and 25 at K = 48) and a completing one of 7, then ten lockstep steps.  Launches of at least 16 steps are k_rollout_tab up to six
+    seats and k_rollout_allin_tab up to ten; k_rollout / k_rollout_allin beyond."""
+    for kind in kinds:
+        K = M.k_of("rollout", kind, N)
+        assert K >= 48 and K // 3 >= 16 and K - K // 3 - 7 >= 16
+        assert M.rollout_then_lockstep(HB, M.matrix_config(kind, N, shape=shape), K, lock=10, split=True) == M.T_MATRIX * (K + 10)
 
 
-def equity(HB, N):
-    for kind in M.KINDS:
-        st = M.equity(HB, M.matrix_config(kind, N), M.K_PLAYED, extra_call=M.extra_call(kind, N),
+def snapshots(HB, N, shape="spread", kinds=M.KINDS):
+    for kind in kinds:
+        M.snapshots(HB, M.matrix_config(kind, N, shape=shape), M.K_PLAYED, extra_call=M.extra_call(kind, N), observer=N - 1 if kind == "top_seat" else "active")
+
+
+def equity(HB, N, shape="spread", kinds=M.KINDS):
+    for kind in kinds:
+        st = M.equity(HB, M.matrix_config(kind, N, shape=shape), M.K_PLAYED, extra_call=M.extra_call(kind, N),
                       observer={"default": -2, "ladder": -1, "top_seat": N - 1}[kind])
         assert st["tables"] == M.EQUITY_FIRST and st["samples"] == 65 * M.EQUITY_FIRST, (kind, st)
 
 
 FAMILIES = [game_step, game_step_async, env_step, env_batches, env_multi, rollout_call, snapshots, equity]
+PART_FAMILIES = [rollout, game_step, env_step]
+RESUMED_FAMILIES = [rollout, rollout_call, game_step, game_step_async, env_step]
 
 
-@pytest.mark.parametrize("family", FAMILIES, ids=lambda f: f.__name__)
-@pytest.mark.parametrize("N", M.SEATS)
-def test_family_at_every_seat_count(HB, N, family):
-    family(HB, N)
+def _cases():
+    """(id, N, family, shape, configurations), by seat count as before."""
+    for N in M.SEATS:
+        for f in FAMILIES:
+            yield "%d-%s" % (N, f.__name__), N, f, "spread", M.KINDS
+        yield "%d-rollout-spread" % N, N, rollout, "spread", M.KINDS
+        for f in FAMILIES + [rollout]:
+            yield "%d-%s-full" % (N, f.__name__), N, f, "full", M.KINDS
+        for f in PART_FAMILIES:
+            yield "%d-%s-part" % (N, f.__name__), N, f, "part", M.KINDS
+        if N in M.RESUMED_SEATS:
+            for f in RESUMED_FAMILIES:
+                yield "%d-%s-full-resumed" % (N, f.__name__), N, f, "full", (M.RESUMED,)
+
+
+CASES = list(_cases())
+
+
+@pytest.mark.parametrize("N,family,shape,kinds", [c[1:] for c in CASES], ids=[c[0] for c in CASES])
+def test_family_at_every_seat_count(HB, monkeypatch, N, family, shape, kinds):
+    M.use_shape(monkeypatch, shape)
+    family(HB, N, shape, kinds)
+
+
+def test_wave_shape_accessor(HB, monkeypatch):
+    """pk_get_wave_shape / VecGame.wave_shape: pk_create's rule without a knob, PK_TPB and PK_ENV_TPB with one (the env kernels follow
+    PK_TPB unless PK_ENV_TPB names a power of two), NULL arguments refused with the outputs untouched."""
+    import ctypes as C
+    from pokerl_amd import _lib as L
+    for tpb, env_tpb, T, want in ((None, None, 1025, (2, 2)), (None, None, 1024, (1, 1)), ("64", None, 5, (64, 64)), ("8", "4", 165, (8, 4)), ("8", "3", 165, (8, 8)),
+                                  (None, "16", 165, (1, 16))):
+        for name, v in (("PK_TPB", tpb), ("PK_ENV_TPB", env_tpb)):
+            monkeypatch.delenv(name, raising=False) if v is None else monkeypatch.setenv(name, v)
+        h = HB(T, 3)
+        assert h.g.wave_shape == want and h.env.game.wave_shape == want, (tpb, env_tpb, T, h.g.wave_shape, want)
+        a = C.c_int(-7)
+        for args in ((h.g._h, None, C.byref(a)), (h.g._h, C.byref(a), None), (None, C.byref(a), C.byref(a))):
+            assert L.lib().pk_get_wave_shape(*args) == L.PK_E_INVALID_ARG and a.value == -7, args
+        h.g.close()

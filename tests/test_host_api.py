@@ -93,6 +93,14 @@ def test_create_refuses_bad_arguments_before_looking_for_a_device():
         pokerl_amd.VecGame(4, num_players=L.MAX_PLAYERS + 1)
 
 
+def test_wave_shape_refuses_null_without_a_device():
+    """pk_get_wave_shape: a NULL handle is PK_E_INVALID_ARG and writes nothing (with a handle: tests/test_hip_seat_matrix.py)."""
+    import ctypes as C
+    from pokerl_amd import _lib as L
+    a, b = C.c_int(-7), C.c_int(-7)
+    assert L.lib().pk_get_wave_shape(None, C.byref(a), C.byref(b)) == L.PK_E_INVALID_ARG and (a.value, b.value) == (-7, -7)
+
+
 def test_packed_observation_rows_unpack_to_the_dense_layout():
     """state_view.packed_dtype / unpack_obs: the host side of PK_OBS_PACKED_BYTES (the device side is a -m gpu test)."""
     from pokerl_amd import packed_dtype, unpack_obs

@@ -6,22 +6,72 @@ import pytest
 
 import seat_matrix as M
 
-T_LAST = M.T_MATRIX - 1     # a lane of the ragged wavefront
-CAP_SHARE = 0.05        # ladder / top_seat: at most this share of the tables may run into PK_TERR_HAND_CAP / _ENV_CAP; default: none
+T_LAST = M.T_MATRIX - 1     # a lane of the ragged wavefront (at 64 tables per wave)
+CAP_SHARE = 0.05        # ladder / top_seat: at most this share of the tables may run into PK_TERR_HAND_CAP / _ENV_CAP; default and resumed: none
+CROSS_SHARE = 0.75      # resumed: at least this share of the tables deals hand_serial 2^32 in every family's run
 
 
 def cap_limit(kind, T):
-    return 0 if kind == "default" else int(CAP_SHARE * T)
+    return 0 if kind in ("default", M.RESUMED) else int(CAP_SHARE * T)
 
 
-@pytest.mark.parametrize("N", M.SEATS)
-@pytest.mark.parametrize("kind", M.KINDS)
+def resumed_runs(N, T):
+    """The oracle halves of the resumed families as the drivers of tests/seat_matrix.py run them, at the matrix's step counts: per family
+    (snapshot before the first reset -- an env's first reset already plays the opponents in front of seat 0 --, snapshot at the end of the run)."""
+    cfg = M.matrix_config(M.RESUMED, N, T)
+    start = M.oracle_of(cfg).snapshot()
+    *_, last = M.game_step_trace(cfg, M.k_of("game_step", M.RESUMED, N))
+    yield "game_step", start, last["o"].snapshot()
+    if T > 1:
+        *_, last = M.game_step_trace(cfg, M.k_of("game_step_async", M.RESUMED, N))
+        yield "game_step_async", start, last["o"].snapshot()
+    yield "env_step", start, M.env_want(cfg, 0, M.k_of("env_step", M.RESUMED, N))[3].snapshot()
+    if T > 1:
+        o = M.oracle_of(cfg)
+        o.reset(dealer=cfg["dealer"])
+        o.rollout(M.k_of("rollout", M.RESUMED, N), cfg["policy"], True)          # (rollout_then_lockstep goes on for ten lockstep steps)
+        yield "rollout", start, o.snapshot()
+        o = M.oracle_of(cfg)
+        o.reset(dealer=cfg["dealer"])
+        o.rollout(M.k_of("rollout_call", M.RESUMED, N) + 7 + 45, 2, True)         # (rollout_call: fused, one step per launch, five deferred calls)
+        yield "rollout_call", start, o.snapshot()
+
+
+@pytest.mark.parametrize("N", M.RESUMED_SEATS)
+def test_resumed_runs_cross_both_boundaries(N):
+    """The resumed configuration is there for the 64-bit serials: in the oracle half of every family that runs it, every table's
+    action-block index step_serial >> 3 starts below 2^32 and ends at or above it, and at least CROSS_SHARE of the tables end two hands, so
+    that hand_serial 2^32 - 1 and 2^32 are both dealt (hand_serial ends ABOVE 2^32).  The lone table of the step and env families crosses both."""
+    for T in (M.T_MATRIX, 1):
+        fig = {}
+        for family, snap0, snap1 in resumed_runs(N, T):
+            assert (snap0["hand_serial"] == 2 ** 32 - 2).all() and (snap0["step_serial"] >> np.uint64(3) == 2 ** 32 - 1).all(), family
+            blocks, hands = M.crossed(snap0, snap1)
+            fig[family] = hands
+            assert blocks, (family, T, "the action-block index does not cross 2^32 on every table")
+            assert hands >= (CROSS_SHARE * T if T > 1 else 1), (family, T, hands, "tables that dealt hand_serial 2^32")
+        print("seat matrix resumed  N=%2d T=%3d: tables that dealt hand_serial 2^32: %s" % (N, T, fig))
+
+
+def test_tpb_rule_edges():
+    """pk_create's rule for tables per wave, restated in seat_matrix.tpb_rule (the `spread` cases hold every handle to it): 1 up to 1 024
+    tables, doubling with the batch, 64 only above 32 768 -- so no small shape fills a wave by itself."""
+    assert [M.tpb_rule(T) for T in (1, 1024, 1025, 32768, 32769)] == [1, 1, 2, 32, 64]
+    assert [M.tpb_rule(T) for T in (M.T_MATRIX, M.T_BATCHES, 2048, 2049, 16384, 16385, 1 << 20)] == [1, 1, 2, 4, 16, 32, 64]
+    assert M.shape_demand(M.matrix_config("default", 6)) == (1, 1) and M.shape_demand(M.matrix_config("default", 6, shape="full")) == (64, 64)
+    assert M.shape_demand(M.matrix_config("default", 6, 1, "part")) == (8, 8)
+    assert M.batch_ranges(M.T_BATCHES, 2) == [(0, 128), (128, 197)] and M.batch_ranges(M.T_MATRIX, 8) == [(0, 64), (64, 128), (128, 165)]
+
+
+@pytest.mark.parametrize("kind,N", [(kind, N) for kind in M.KINDS for N in M.SEATS] + [(M.RESUMED, N) for N in M.RESUMED_SEATS],
+                         ids=lambda v: str(v))      # (the resumed configuration has cases at RESUMED_SEATS only)
 def test_caps_and_content(kind, N):
     cfg = M.matrix_config(kind, N)
     T = cfg["T"]
+    K_GAME, K_ENV = M.k_of("game_step", kind, N), M.k_of("env_step", kind, N)
     # ---- lockstep Game.step: the trace ends (it is a bounded loop over a terminating oracle), caps, side pots
     capped, paid, resets, over_seen = np.zeros(T, bool), 0, 0, 0
-    for tr in M.game_step_trace(cfg, M.K_GAME, before=True):
+    for tr in M.game_step_trace(cfg, K_GAME, before=True):
         assert not (tr["eo"] & 2).any(), (tr["s"], "game.py:473: the bounded twin would stop here and compare nothing further")
         capped |= (tr["eo"] & M.CAPS) != 0
         resets += int(tr["over"].sum())
@@ -29,13 +79,13 @@ def test_caps_and_content(kind, N):
         paid = max(paid, int(M.seats_paid(tr).max()))
     fig = dict(game_capped=int(capped.sum()), game_resets=resets, seats_paid=paid, game_over_seen=over_seen)
     assert capped.sum() <= cap_limit(kind, T), fig
-    assert not any((tr["eo"] & 2).any() for tr in M.game_step_trace(M.matrix_config(kind, N, 1), M.K_GAME)), "game.py:473 at one table"
+    assert not any((tr["eo"] & 2).any() for tr in M.game_step_trace(M.matrix_config(kind, N, 1), K_GAME)), "game.py:473 at one table"
     # ---- the same agents' rollout: finished games and showdowns from the counters
     o = M.oracle_of(cfg)
     o.reset(dealer=cfg["dealer"])
-    c, err = o.rollout(M.K_GAME, cfg["policy"], True)
+    c, err = o.rollout(K_GAME, cfg["policy"], True)
     fig.update(games=int(c[3]), showdowns=int(c[2]))
-    if kind == "default":
+    if kind in ("default", M.RESUMED):
         assert err == 0 and c[3] >= 1 and c[2] >= 1, fig
     if kind == "ladder":
         assert paid >= min(N, 4), fig                # side pots formed: that many seats RECEIVED different non-zero amounts in one hand
@@ -43,7 +93,7 @@ def test_caps_and_content(kind, N):
     # ---- PokerGameEnv.step, one opponent policy and one per seat
     for T_env in (T, M.T_BATCHES, 1):
         ecfg = M.matrix_config(kind, N, T_env)
-        st = M.env_want(ecfg, 1 if kind == "ladder" else 0, M.K_ENV)[4]
+        st = M.env_want(ecfg, 1 if kind == "ladder" else 0, K_ENV)[4]
         assert st["capped"] <= cap_limit(kind, T_env), (T_env, st["capped"])
         if T_env == T:
             fig.update(env_capped=st["capped"], env_done=st["done"])
@@ -54,7 +104,7 @@ def test_caps_and_content(kind, N):
     assert st["capped"] <= cap_limit(kind, T), fig
     for T1 in (1,):
         c1 = M.matrix_config(kind, N, T1)
-        assert M.multi_want(c1, pols, M.K_MULTI)[1]["capped"] == 0 and M.env_want(c1, 0, M.K_ENV)[4]["capped"] == 0
+        assert M.multi_want(c1, pols, M.K_MULTI)[1]["capped"] == 0 and M.env_want(c1, 0, K_ENV)[4]["capped"] == 0
     if kind == "top_seat":
         assert N - 1 in external and (N == 2 or pols[0] != pols[N - 2])
         y = M.multi_yields(cfg, pols, external, M.K_MULTI)        # (also: the twin replay ends in the oracle's own state)
@@ -65,8 +115,8 @@ def test_caps_and_content(kind, N):
     # ---- call-agent rollout, and the tables the snapshot / equity families start from
     o = M.oracle_of(cfg)
     o.reset(dealer=cfg["dealer"])
-    c, err = o.rollout(M.k_call(N), 2, True)
-    assert err == 0 and c[0] == T * M.k_call(N) and c[1] > 0, c
+    c, err = o.rollout(M.k_of("rollout_call", kind, N), 2, True)
+    assert err == 0 and c[0] == T * M.k_of("rollout_call", kind, N) and c[1] > 0, c
     snap = M.played_oracle(cfg, M.K_PLAYED, M.extra_call(kind, N)).snapshot()
     fig.update(past_the_flop=int((snap["turn"] >= 1).sum()))
     assert len(M.equity_tables(snap["turn"])) == M.EQUITY_FIRST, fig

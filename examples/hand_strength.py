@@ -4,6 +4,9 @@
 device, never read.  Everything stays in HBM: the observation rows (pk_set_step_obs), the equity counts, the actions.  A network would
 read `obs` and `share` (equity = share / (720720 * samples)); here the library's in-kernel random pick stands in for it.  A new nonce per
 step gives independent draws; the counts of the steps a spot stays unchanged could be added up for a tighter estimate.
+Where the flop is out, the EXACT strength of the same seat against one hidden hand (pk_table_equity_range, every holding and every board
+enumerated) is printed beside it.  The two answer different questions -- every live opponent with the pot split among all winners, against
+one opponent with a tie counted as a half -- and are the same quantity only heads-up.
 
     python examples/hand_strength.py [tables=65536] [steps=200] [samples=256]
 """
@@ -46,6 +49,11 @@ eq = share.download(np.uint64, T * N).reshape(T, N)[np.arange(T), game.active_pl
 print("%d tables x %d steps, each with a %d-sample equity of the acting seat, in %.3f s (%.1f us per step of the whole batch); "
       "acting seats' equity now: mean %.3f, 10th / 90th percentile %.3f / %.3f"
       % (T, steps, S, dt, dt / steps * 1e6, eq.mean(), np.percentile(eq, 10), np.percentile(eq, 90)))
+exact = game.equity_range(observer='active')                   # post-flop tables only: the others report PK_EQ_PREFLOP
+post = exact.status == 0
+if post.any():
+    print("the %d tables past the flop: sampled equity against every live opponent, mean %.3f; exact strength against ONE hidden hand, mean %.3f"
+          % (int(post.sum()), eq[post].mean(), exact.strength[post].mean()))
 game.set_step_obs(None, None)
 for b in (actions, flags, terr, obs, share, status):
     b.free()

@@ -588,7 +588,8 @@ int pk_table_equity(pk_handle *h, const int32_t *tables, size_t m, uint32_t *win
  * hidden if the seat is live and, if it is not, NOT dead (p never saw a folded hand: those cards are in the pool).  PK_OBSERVER_NONE: all 2N
  * hole cards known and dead as in pk_table_equity, only the board is sampled.  Like pk_table_equity the call completes deferred rollout work,
  * reads only, runs on the handle's stream, and reports PK_EQ_IN_FLIGHT / PK_EQ_BAD_TABLE / PK_EQ_DUP_CARD (a table never dealt) per table.
- * STREAMS and work space: as pk_equity (the device form asynchronous on the stream it is given, the host forms synchronous). */
+ * STREAMS and work space: as pk_equity (the device form asynchronous on the stream it is given, the host forms synchronous).
+ * The EXACT post-flop answer against one hidden opponent, per holding and under a range, is pk_equity_range below. */
 int pk_equity_sampled_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
                         const uint16_t *live_d, const uint32_t *ids_d /* NULL: i */, uint32_t samples, uint64_t seed, uint32_t nonce,
                         uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *samples_d, uint8_t *status_d, void *stream);
@@ -599,6 +600,48 @@ int pk_table_equity_sampled_d(pk_handle *h, const int32_t *tables_d, size_t m, i
                               uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *samples_d, uint8_t *status_d);
 int pk_table_equity_sampled(pk_handle *h, const int32_t *tables, size_t m, int observer, uint32_t samples, uint32_t nonce, uint32_t *win,
                             uint32_t *tie, uint64_t *share, uint32_t *samples_out, uint8_t *status);
+/* ---- Range equity: exact hand strength against ONE hidden hand -- the hero's result against every holding the hidden opponent can have, per
+ * holding and reduced by a range of weights.  POST-FLOP ONLY: pre-flop a hidden hand is 2 * 10^9 boards per spot and
+ * the pre-flop hero-versus-holding table is a constant nobody needs recomputed; such a spot reports PK_EQ_PREFLOP.
+ *
+ * A SPOT is hero u8[2] (Card.value bytes), board u8[5] with nb = 3, 4 or 5 known cards, and dead u64: bit k = the card of canonical index
+ * k = rank0 * 4 + suit is known to be out of play (a shown folded hand, say; 0 = none).  Dead cards = hero + board[0:nb] + `dead`; pool = the
+ * other cards, P of them, in canonical order value[k] = ((k%4)<<4) | (k/4).
+ * A HOLDING is an unordered pair of cards with canonical indices a < b; its index is h = b (b - 1) / 2 + a, 0 .. 1325 (PK_EQ_HOLDINGS),
+ * fixed and independent of the spot.  It is VALID when both cards are in the pool.
+ * COUNTS: for a valid holding every completion of the board from the pool minus the holding is enumerated -- boards = C(P - 2, 5 - nb) of
+ * them, the same for every valid holding of a spot; on each, v = [eval_hand(board + hero), eval_hand(board + holding)] and the winners are
+ * compare_rankings(v) as above (the hero is index 0).  win[h] u32 = boards the hero wins alone, tie[h] u32 = boards both win; losses are
+ * boards - win - tie, the hero's share is 720720 * win + 360360 * tie (not stored).  Invalid holdings get zeros.
+ * RANGE: weights u16 [1326] is optional -- one vector for every spot of the call (weights_per_spot = 0) or one per spot ([m][1326],
+ * weights_per_spot = 1); NULL = every weight 1.  agg u64 [3] per spot = sum w[h] win[h], sum w[h] tie[h], boards * sum over the valid h of
+ * w[h]; hand strength = (agg[0] + agg[1] / 2) / agg[2], formed by the caller in binary64 (the largest aggregate, 65 535 * 990 * 1 081, fits
+ * 64 bits with room).
+ * STATUS (u8; a non-zero status gives all-zero outputs and boards = 0, never fails the call, and disturbs no neighbour): PK_EQ_BAD_CARD a
+ * byte that is no card, 0xFF anywhere, or a `dead` bit >= 52; PK_EQ_DUP_CARD a card twice among hero and board, or a hero / board card that is
+ * also in `dead`; PK_EQ_BAD_NBOARD nb > 5; PK_EQ_PREFLOP nb < 3; PK_EQ_SMALL_POOL P < (5 - nb) + 2 (nb <= 5); the table form also
+ * PK_EQ_IN_FLIGHT, PK_EQ_BAD_TABLE and PK_EQ_DUP_CARD for a table never dealt, as pk_table_equity.
+ * Any output may be NULL (not wanted); m == 0 is a no-op; m < 2^31; device < PK_MAX_DEVICES.
+ * TABLE FORM: observer = a seat p (0 .. N-1) or PK_OBSERVER_ACTIVE (each table's active seat); PK_OBSERVER_NONE is refused with
+ * PK_E_INVALID_ARG.  Spot = p's two hole cards plus the board so far (nb as pk_table_equity); dead = 0: p has seen no folded hand, and the
+ * board cards the deck already holds for later streets are in the pool.  The question is the same at any seat count -- "against ONE hidden
+ * hand" -- and does not look at who is live.  Like the other table forms it completes deferred rollout work, reads only, and runs on the
+ * handle's stream.
+ * STREAMS and work space: as pk_equity (the device form asynchronous on the stream it is given, the host forms synchronous). */
+#define PK_EQ_HOLDINGS 1326
+#define PK_EQ_PREFLOP 64u      /* range equity: nb < 3 (out of scope: see above) */
+#define PK_EQ_SMALL_POOL 128u  /* range equity: fewer pool cards than the board to come plus one holding */
+int pk_equity_range_d(int device, size_t m, const uint8_t *hero_d /*[m][2]*/, const uint8_t *board_d /*[m][5]*/, const uint8_t *nboard_d,
+                      const uint64_t *dead_d /*NULL: none*/, const uint16_t *weights_d /*NULL: 1*/, int weights_per_spot,
+                      uint64_t *agg_d /*[m][3]*/, uint32_t *win_d /*[m][1326]*/, uint32_t *tie_d, uint32_t *boards_d, uint8_t *status_d,
+                      void *stream);
+int pk_equity_range(int device, size_t m, const uint8_t *hero, const uint8_t *board, const uint8_t *nboard, const uint64_t *dead,
+                    const uint16_t *weights, int weights_per_spot, uint64_t *agg, uint32_t *win, uint32_t *tie, uint32_t *boards,
+                    uint8_t *status);
+int pk_table_equity_range_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, const uint16_t *weights_d, int weights_per_spot,
+                            uint64_t *agg_d, uint32_t *win_d, uint32_t *tie_d, uint32_t *boards_d, uint8_t *status_d);
+int pk_table_equity_range(pk_handle *h, const int32_t *tables, size_t m, int observer, const uint16_t *weights, int weights_per_spot,
+                          uint64_t *agg, uint32_t *win, uint32_t *tie, uint32_t *boards, uint8_t *status);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

@@ -22,6 +22,8 @@ MIN_PLAYERS, MAX_PLAYERS = 2, 16
 EQ_SHARE_UNIT = 720720   # lcm(1 .. 16): a board's pot share of one of nw winners is EQ_SHARE_UNIT / nw (pk_equity)
 EQ_BAD_CARD, EQ_DUP_CARD, EQ_NO_LIVE, EQ_BAD_NBOARD, EQ_IN_FLIGHT, EQ_BAD_TABLE = 1, 2, 4, 8, 16, 32   # PK_EQ_* status bits
 OBSERVER_NONE, OBSERVER_ACTIVE = -1, -2   # pk_clone_tables_d: an exact copy / redeal from each source table's active player
+EQ_PREFLOP, EQ_SMALL_POOL = 64, 128   # ... of pk_equity_range: nb < 3 / fewer pool cards than the board to come plus one holding
+EQ_HOLDINGS = 1326   # PK_EQ_HOLDINGS: unordered pairs of the 52 cards, h = b (b - 1) / 2 + a over canonical indices a < b
 EQS_SAMPLES_MAX = 1 << 24   # pk_equity_sampled: samples per call and spot at most
 
 # every symbol include/pokerl_hip.h declares (tests check the library exports each one)
@@ -38,11 +40,12 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_env_step_begin", "pk_env_step_end", "pk_reset_d", "pk_step_auto_d", "pk_stream_pool_drain", "pk_step_async_d", "pk_set_step_obs", "pk_build_info",
            "pk_snapshot_bytes", "pk_save_tables_d", "pk_load_tables_d", "pk_save_tables", "pk_load_tables", "pk_clone_tables_d",
            "pk_equity_d", "pk_equity", "pk_table_equity_d", "pk_table_equity",
-           "pk_equity_sampled_d", "pk_equity_sampled", "pk_table_equity_sampled_d", "pk_table_equity_sampled", "pk_get_wave_shape"]
+           "pk_equity_sampled_d", "pk_equity_sampled", "pk_table_equity_sampled_d", "pk_table_equity_sampled", "pk_get_wave_shape",
+           "pk_equity_range_d", "pk_equity_range", "pk_table_equity_range_d", "pk_table_equity_range"]
 
 
 class PokerlHipError(RuntimeError):
-    pass
+    code = None     # the library's PK_E_* return code where check() raised it
 
 
 _lib = None
@@ -144,6 +147,10 @@ def lib():
     L.pk_equity_sampled.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_uint32, C.c_uint64, C.c_uint32] + [_vp] * 5
     L.pk_table_equity_sampled_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32] + [_vp] * 5
     L.pk_table_equity_sampled.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32] + [_vp] * 5
+    L.pk_equity_range_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_int] + [_vp] * 6
+    L.pk_equity_range.argtypes = [C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_int] + [_vp] * 5
+    L.pk_table_equity_range_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int] + [_vp] * 5
+    L.pk_table_equity_range.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int] + [_vp] * 5
     for name in SYMBOLS:
         if name not in ("pk_last_error", "pk_build_info", "pk_snapshot_bytes"):
             getattr(L, name).restype = C.c_int
@@ -162,7 +169,9 @@ def check(rc, handle=None, allow_table_errors=False):
     if rc == PK_OK or (allow_table_errors and rc == PK_E_TABLE):
         return rc
     msg = lib().pk_last_error(handle)
-    raise PokerlHipError("libpokerl_hip: error %d: %s" % (rc, msg.decode() if msg else "?"))
+    err = PokerlHipError("libpokerl_hip: error %d: %s" % (rc, msg.decode() if msg else "?"))
+    err.code = rc
+    raise err
 
 
 def source_hash():

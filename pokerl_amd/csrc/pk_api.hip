@@ -17,6 +17,7 @@
 #include "pk_util_kernels.hpp"
 #include "pk_equity.hpp"
 #include "pk_equity_sampled.hpp"
+#include "pk_equity_range.hpp"
 #include "pk_snapshot.hpp"
 
 using namespace pk;
@@ -119,6 +120,14 @@ struct EqStagedOut {
     EqStagedOut(Stage &g, int N, size_t m, uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards, uint8_t *status)
         : win(g.out(win, m * N * 4)), tie(g.out(tie, m * N * 4)), share(g.out(share, m * N * 8)), boards(g.out(boards, m * 4)), status(g.out(status, m)) {}
     EqOut at(const Stage &g) const { return EqOut{g.at<uint32_t>(win), g.at<uint32_t>(tie), g.at<uint64_t>(share), g.at<uint32_t>(boards), g.at<uint8_t>(status)}; }
+};
+// ... and a range-equity call
+struct EqrStagedOut {
+    int agg, win, tie, boards, status;
+    EqrStagedOut(Stage &g, size_t m, uint64_t *agg, uint32_t *win, uint32_t *tie, uint32_t *boards, uint8_t *status)
+        : agg(g.out(agg, m * 3 * 8)), win(g.out(win, m * EQR_HOLDINGS * 4)), tie(g.out(tie, m * EQR_HOLDINGS * 4)), boards(g.out(boards, m * 4)),
+          status(g.out(status, m)) {}
+    EqrOut at(const Stage &g) const { return EqrOut{g.at<uint64_t>(agg), g.at<uint32_t>(win), g.at<uint32_t>(tie), g.at<uint32_t>(boards), g.at<uint8_t>(status)}; }
 };
 }  // namespace
 
@@ -2021,6 +2030,102 @@ int pk_table_equity_sampled(pk_handle *h, const int32_t *tables, size_t m, int o
     if (rc) return rc;
     HIPCHK(h, g.upload(h->stream));
     if ((rc = table_equity_sampled(h, g.at<int32_t>(idx), m, observer, samples, nonce, eqs_out(out.at(g)), g.at<char>(work)))) return rc;
+    HIPCHK(h, g.download(h->stream));
+    return PK_OK;
+}
+
+// ---- range equity (pokerl_hip.h "Range equity"; kernels: pk_equity_range.hip).  Work space (the descriptors) as above.
+static size_t eqr_weight_bytes(size_t m, int per_spot) { return (per_spot ? m : (size_t)1) * EQR_HOLDINGS * 2; }
+#define EQR_CHECK_SPOTS(call, m, inputs)                                                     \
+    if ((m) >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, call ": m >= 2^31");            \
+    if ((m) && !(inputs)) return g_fail(PK_E_INVALID_ARG, call ": NULL input buffer")
+
+int pk_equity_range_d(int device, size_t m, const uint8_t *hero_d, const uint8_t *board_d, const uint8_t *nboard_d, const uint64_t *dead_d,
+                      const uint16_t *weights_d, int weights_per_spot, uint64_t *agg_d, uint32_t *win_d, uint32_t *tie_d, uint32_t *boards_d,
+                      uint8_t *status_d, void *stream) {
+    EQR_CHECK_SPOTS("pk_equity_range_d", m, hero_d && board_d && nboard_d);
+    ON_DEVICE_INDEX("pk_equity_range_d", device, PK_MAX_DEVICES);
+    if (m == 0) return PK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t *tab = eval7_table(device, st);   // (a first call builds the table on the CALLER's stream)
+    if (!tab) return g_fail(PK_E_OOM, "pk_equity_range_d: out of device memory (evaluator table)");
+    void *ws = eq_stream_ws(device, st, eqr_work_bytes(m));
+    if (!ws) return g_fail(PK_E_OOM, "pk_equity_range_d: out of device memory (work space)");
+    const EqrSpots spots{hero_d, board_d, nboard_d, dead_d};
+    const hipError_t e = eqr_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{weights_d, weights_per_spot != 0}, m,
+                                    EqrOut{agg_d, win_d, tie_d, boards_d, status_d}, (uint64_t *)ws);
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_range_d: launch failed", e);
+    return PK_OK;
+}
+
+int pk_equity_range(int device, size_t m, const uint8_t *hero, const uint8_t *board, const uint8_t *nboard, const uint64_t *dead,
+                    const uint16_t *weights, int weights_per_spot, uint64_t *agg, uint32_t *win, uint32_t *tie, uint32_t *boards,
+                    uint8_t *status) {
+    EQR_CHECK_SPOTS("pk_equity_range", m, hero && board && nboard);
+    ON_DEVICE_INDEX("pk_equity_range", device, PK_MAX_DEVICES);
+    if (m == 0) return PK_OK;
+    hipStream_t st = nullptr;
+    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity_range: no stream"); }
+    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
+    int rc = PK_OK;
+    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity_range: out of device memory (evaluator table)");
+    else {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        Stage g;
+        const int he = g.in(hero, m * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
+        const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+        const EqrStagedOut out(g, m, agg, win, tie, boards, status);
+        const int work = g.add(eqr_work_bytes(m));
+        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity_range: out of device memory");
+        else {
+            const hipError_t e = g.run(st, [&] {
+                const EqrSpots spots{g.at<uint8_t>(he), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
+                return eqr_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, out.at(g),
+                                  g.at<uint64_t>(work));
+            });
+            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity_range", e); }   // (the lock is held until what was queued is done)
+        }
+    }
+    stream_release(device, st);
+    return rc;
+}
+
+// The table form: the handle's own state on the handle's stream, as `observer` sees it
+static int table_equity_range(pk_handle *h, const int32_t *tables_d, size_t m, int observer, const EqrWeights &weights, const EqrOut &out, char *work) {
+    const uint32_t *tab = eval7_table(h->device, h->stream);
+    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity_range: out of device memory (evaluator table)");
+    const EqTables t{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T};
+    HIPCHK(h, eqr_launch(h->stream, tab, nullptr, &t, h->N, observer, weights, m, out, (uint64_t *)work));
+    return PK_OK;
+}
+#define EQR_TABLE_ENTER(h, m, observer, call)                                                                                                \
+    if (!(h)) return PK_E_INVALID_ARG;                                                                                                       \
+    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                                                         \
+    if ((observer) != PK_OBSERVER_ACTIVE && ((observer) < 0 || (observer) >= (h)->N))                                                        \
+        return (h)->fail(PK_E_INVALID_ARG, call ": observer outside {-2, 0 .. N-1} (a hidden hand needs somebody to be hidden from)");       \
+    ON_DEVICE(h);                                                                                                                            \
+    FLUSH_READER(h);                                                                                                                         \
+    if ((m) == 0) return PK_OK
+
+int pk_table_equity_range_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, const uint16_t *weights_d, int weights_per_spot,
+                            uint64_t *agg_d, uint32_t *win_d, uint32_t *tie_d, uint32_t *boards_d, uint8_t *status_d) {
+    EQR_TABLE_ENTER(h, m, observer, "pk_table_equity_range_d");
+    char *work = nullptr;
+    if (int rc = snap_staging(h, eqr_work_bytes(m), &work)) return rc;
+    return table_equity_range(h, tables_d, m, observer, EqrWeights{weights_d, weights_per_spot != 0}, EqrOut{agg_d, win_d, tie_d, boards_d, status_d}, work);
+}
+
+int pk_table_equity_range(pk_handle *h, const int32_t *tables, size_t m, int observer, const uint16_t *weights, int weights_per_spot,
+                          uint64_t *agg, uint32_t *win, uint32_t *tie, uint32_t *boards, uint8_t *status) {
+    EQR_TABLE_ENTER(h, m, observer, "pk_table_equity_range");
+    Stage g;
+    const int idx = g.in(tables, m * 4), we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const EqrStagedOut out(g, m, agg, win, tie, boards, status);
+    const int work = g.add(eqr_work_bytes(m));
+    int rc = snap_staging(h, g.total, &g.base);
+    if (rc) return rc;
+    HIPCHK(h, g.upload(h->stream));
+    if ((rc = table_equity_range(h, g.at<int32_t>(idx), m, observer, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, out.at(g), g.at<char>(work)))) return rc;
     HIPCHK(h, g.download(h->stream));
     return PK_OK;
 }

@@ -425,6 +425,60 @@ class VecGame:
         L.check(self._lib.pk_table_equity_sampled_d(self._h, self._dptr(tables_d), m, o, samples, nonce, self._dptr(win_d), self._dptr(tie_d),
                                                     self._dptr(share_d), self._dptr(samples_d), self._dptr(status_d)), self._h)
 
+    def _range_observer(self, observer):
+        """observer of equity_range: a seat or OBSERVER_ACTIVE / 'active'; ValueError otherwise (before any call)."""
+        o = self._observer(observer)
+        if o != L.OBSERVER_ACTIVE and not (0 <= o < self.num_players):
+            raise ValueError('observer must be a seat 0 .. %d or OBSERVER_ACTIVE' % (self.num_players - 1))
+        return o
+
+    def equity_range(self, observer='active', weights=None, tables=None, per_holding=False):
+        """Exact hand strength of `observer` (a seat, or 'active' / OBSERVER_ACTIVE: each table's active seat) against ONE hidden hand at
+        `tables` (all tables if None; indices may repeat), post-flop (pk_table_equity_range; definition: pokerl_hip.h "Range equity"): the
+        observer's two cards and the board so far against every holding of the other cards, every completion of the board enumerated.
+        weights: None (uniform), uint16 [1326] (one range) or [m, 1326] over judger.holding_index.  Returns a judger.RangeEquity: agg [m, 3]
+        and `strength` [m] always, win / tie [m, 1326] and `valid` with per_holding=True (`valid` is None while asynchronous steps are in
+        flight: it is formed from the getters).  A table that cannot be evaluated (pre-flop, never
+        reset, step in flight) has a non-zero status and strength 0."""
+        from .judger import RangeEquity, range_weights, valid_holdings
+        o = self._range_observer(observer)
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        w, per_spot = range_weights(weights, m)
+        win = np.zeros((m, L.EQ_HOLDINGS), np.uint32) if per_holding else None
+        tie = np.zeros((m, L.EQ_HOLDINGS), np.uint32) if per_holding else None
+        agg, boards, status = np.zeros((m, 3), np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        L.check(self._lib.pk_table_equity_range(self._h, L.ptr(t), m, o, L.ptr(w), per_spot, L.ptr(agg), L.ptr(win), L.ptr(tie), L.ptr(boards),
+                                                L.ptr(status)), self._h)
+        valid = None
+        if per_holding and not status.all():    # (from the getters, which refuse with PK_E_BUSY while asynchronous steps are in flight: no mask then)
+            try:
+                deck, turn, active = self.deck, self.turn, self.active_player
+            except L.PokerlHipError as e:
+                if e.code != L.PK_E_BUSY:       # (any other failure of a getter is the caller's to see)
+                    raise
+                deck = None
+            if deck is not None:
+                idx = np.arange(self.num_tables) if t is None else t
+                sel = idx[status == 0]
+                who = active[sel].astype(np.int64) if o == L.OBSERVER_ACTIVE else np.full(len(sel), o, np.int64)
+                hero = np.stack([deck[sel, 5 + 2 * who], deck[sel, 6 + 2 * who]], axis=1)
+                valid = np.zeros((m, L.EQ_HOLDINGS), bool)
+                valid[status == 0] = valid_holdings(hero, deck[sel, :5], np.minimum(turn[sel] + 2, 5))
+        elif per_holding:
+            valid = np.zeros((m, L.EQ_HOLDINGS), bool)
+        return RangeEquity(win, tie, boards, status, agg, valid)
+
+    def equity_range_d(self, m=None, tables_d=None, observer='active', weights_d=None, weights_per_spot=False, agg_d=None, win_d=None, tie_d=None,
+                       boards_d=None, status_d=None):
+        """pk_table_equity_range_d: the same into device buffers (uint64 [m, 3] agg, uint32 [m, 1326] win / tie, uint32 [m] boards, uint8 [m]
+        status; any may be None; weights_d uint16 [1326] or [m, 1326] or None), asynchronous on the handle's stream.  m defaults to every table."""
+        o = self._range_observer(observer)
+        m = self.num_tables if m is None else int(m)
+        L.check(self._lib.pk_table_equity_range_d(self._h, self._dptr(tables_d), m, o, self._dptr(weights_d), int(bool(weights_per_spot)),
+                                                  self._dptr(agg_d), self._dptr(win_d), self._dptr(tie_d), self._dptr(boards_d), self._dptr(status_d)),
+                self._h)
+
     def __deepcopy__(self, memo):
         """A new handle with the same configuration (seed and table ids included) holding a copy of every table: it continues
         bit-identically to this game under the same actions, and stepping one leaves the other untouched.  Only the construction

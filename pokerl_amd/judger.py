@@ -117,7 +117,9 @@ def time_eval7_stream(hands_d, m, out_d, distinct=True, reps=5, device=0):
 UNKNOWN_CARD = 0xFF
 _EQ_STATUS = [(L.EQ_BAD_CARD, 'a byte that is no card (or an unknown card in the board or at a live seat)'), (L.EQ_DUP_CARD, 'a card twice'),
               (L.EQ_NO_LIVE, 'no live seat'), (L.EQ_BAD_NBOARD, 'more than five board cards'),
-              (L.EQ_IN_FLIGHT, "the table's step is in flight"), (L.EQ_BAD_TABLE, 'table index out of range')]
+              (L.EQ_IN_FLIGHT, "the table's step is in flight"), (L.EQ_BAD_TABLE, 'table index out of range'),
+              (L.EQ_PREFLOP, 'fewer than three board cards (range equity is post-flop only)'),
+              (L.EQ_SMALL_POOL, 'too few cards left for the board to come and one holding')]
 
 
 def equity_status_text(status):
@@ -332,6 +334,157 @@ def sampled_equity(hands, board=(), live=None, samples=4096, seed=DEFAULT_SEED, 
     if mask < 0 or mask >> n:
         raise ValueError('live mask names seats >= %d' % n)
     r = sampled_equity_batch(holes, b, np.array([len(board)], np.uint8), np.array([mask], np.uint16), samples, seed, nonce, device=device)[0]
+    if r.status:
+        raise ValueError('invalid spot: ' + equity_status_text(r.status))
+    return r
+
+
+# ---------------------------------------------------------------------------------------------- range equity
+# Exact hand strength against ONE hidden hand, post-flop: the hero's win / tie counts against every holding the opponent can have, and their
+# sum under a range of weights (pk_equity_range; the definition: include/pokerl_hip.h "Range equity").
+_CANON = [((k % 4) << 4) | (k // 4) for k in range(52)]                # canonical index k = rank0 * 4 + suit -> Card.value (cards.py:77)
+HOLDINGS = np.array([[_CANON[a], _CANON[b]] for b in range(52) for a in range(b)], np.uint8)   # [1326][2]: holding h = b (b - 1) / 2 + a
+HOLDINGS.setflags(write=False)
+
+
+def _canon_index(c):
+    v = _card(c)
+    return (v & 15) * 4 + (v >> 4)
+
+
+def holding_index(c0, c1):
+    """The index 0 .. 1325 of the holding {c0, c1} (Card-likes / 'RS' strings / Card.value ints; either order): h = b (b - 1) / 2 + a over
+    the canonical indices a < b.  HOLDINGS[h] names its two cards."""
+    a, b = sorted((_canon_index(c0), _canon_index(c1)))
+    if a == b:
+        raise ValueError('a holding is two different cards')
+    return b * (b - 1) // 2 + a
+
+
+def dead_mask(cards):
+    """The `dead` word of a range-equity spot: bit k = the card of canonical index k is out of play."""
+    mask = 0
+    for c in cards:
+        mask |= 1 << _canon_index(c)
+    return mask
+
+
+class RangeEquity:
+    """Counts of one spot or of a batch against every holding of ONE hidden hand ([1326] or [m, 1326] arrays win / tie, or None where only
+    the aggregates were asked for; `boards`, `status` scalars or [m]; agg [3] or [m, 3]): win / tie = boards the hero wins alone / splits
+    against that holding, of `boards` completions each; agg = (sum w win, sum w tie, boards * sum of w over the valid holdings).
+    `valid` = the holdings both of whose cards are in the pool; `equity` = (win + tie / 2) / boards per holding; `strength` =
+    (agg[0] + agg[1] / 2) / agg[2] in float64 (0 where a spot was refused or the range is empty)."""
+
+    def __init__(self, win, tie, boards, status, agg, valid=None):
+        self.win, self.tie, self.boards, self.status, self.agg, self.valid = win, tie, boards, status, agg, valid
+
+    @property
+    def equity(self):
+        if self.win is None:
+            raise ValueError('the per-holding counts were not asked for (per_holding=False)')
+        b = np.asarray(self.boards, np.float64)[..., None]
+        num = np.asarray(self.win, np.float64) + 0.5 * np.asarray(self.tie, np.float64)
+        return np.divide(num, b, out=np.zeros(np.shape(self.win), np.float64), where=b > 0)
+
+    @property
+    def strength(self):
+        a = np.asarray(self.agg, np.float64)
+        num, den = a[..., 0] + 0.5 * a[..., 1], a[..., 2]
+        return np.divide(num, den, out=np.zeros(np.shape(den), np.float64), where=den > 0)[()]
+
+    def __getitem__(self, i):
+        return RangeEquity(None if self.win is None else self.win[i], None if self.tie is None else self.tie[i], self.boards[i], self.status[i],
+                           self.agg[i], None if self.valid is None else self.valid[i])
+
+    def __repr__(self):
+        return 'RangeEquity(boards=%r, status=%r, strength=%r)' % (self.boards, self.status, self.strength)
+
+
+def range_weights(weights, m):
+    """(array or None, weights_per_spot) of a range-equity call: None = every weight 1, uint16 [1326] = one range for every spot, [m, 1326] =
+    one per spot; ValueError for another shape or a weight outside 0 .. 65535 (before any device call)."""
+    if weights is None:
+        return None, 0
+    w = np.asarray(weights)
+    if w.dtype.kind not in 'iub' or w.shape not in ((L.EQ_HOLDINGS,), (m, L.EQ_HOLDINGS)):
+        raise ValueError('weights must be integers of shape [1326] or [m, 1326]')
+    if w.size and (w.min() < 0 or w.max() > 0xFFFF):
+        raise ValueError('weights must fit 16 bits')
+    return np.ascontiguousarray(w, np.uint16), int(w.ndim == 2)
+
+
+def valid_holdings(hero, board, nboard, dead=None):
+    """bool [m, 1326]: the holdings both of whose cards are in the pool of each spot (host arithmetic on the inputs; refused spots are not
+    looked at here -- mask with status == 0)."""
+    hero, board = np.asarray(hero, np.uint8), np.asarray(board, np.uint8)
+    m = hero.shape[0]
+    canon = lambda v: (v.astype(np.int64) & 15) * 4 + (v.astype(np.int64) >> 4)
+    out = np.zeros((m, 52), bool)
+    rows = np.arange(m)
+    for v in (hero[:, 0], hero[:, 1]):
+        out[rows, np.clip(canon(v), 0, 51)] = True
+    nb = np.minimum(np.asarray(nboard, np.int64), 5)
+    for j in range(5):
+        sel = nb > j
+        out[rows[sel], np.clip(canon(board[sel, j]), 0, 51)] = True
+    if dead is not None:
+        out |= ((np.asarray(dead, np.uint64)[:, None] >> np.arange(52, dtype=np.uint64)) & np.uint64(1)).astype(bool)
+    a = np.array([a for b in range(52) for a in range(b)])
+    b = np.array([b for b in range(52) for a in range(b)])
+    return ~out[:, a] & ~out[:, b]
+
+
+def range_equity_batch(hero, board, nboard, dead=None, weights=None, per_holding=True, device=0):
+    """pk_equity_range on host arrays: hero uint8 [m, 2] Card.value, board uint8 [m, 5] (the first nboard[i] = 3, 4 or 5 used), nboard uint8
+    [m], dead uint64 [m] masks over canonical card indices (None: none), weights None / uint16 [1326] / [m, 1326] -> RangeEquity.  A bad
+    spot is reported through its `status` (PK_EQ_* bits) with all-zero outputs; the others are unaffected."""
+    hero = np.ascontiguousarray(hero, np.uint8)
+    if hero.ndim != 2 or hero.shape[1] != 2:
+        raise ValueError('hero must have shape [m, 2]')
+    m = hero.shape[0]
+    board = np.ascontiguousarray(board, np.uint8)
+    nboard = np.ascontiguousarray(nboard, np.uint8)
+    if board.shape != (m, 5) or nboard.shape != (m,):
+        raise ValueError('board must have shape [m, 5], nboard shape [m]')
+    if dead is not None:
+        dead = np.ascontiguousarray(dead, np.uint64)
+        if dead.shape != (m,):
+            raise ValueError('dead must have shape [m]')
+    w, per_spot = range_weights(weights, m)
+    win = np.zeros((m, L.EQ_HOLDINGS), np.uint32) if per_holding else None
+    tie = np.zeros((m, L.EQ_HOLDINGS), np.uint32) if per_holding else None
+    agg, boards, status = np.zeros((m, 3), np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+    L.check(L.lib().pk_equity_range(int(device), m, L.ptr(hero), L.ptr(board), L.ptr(nboard), L.ptr(dead), L.ptr(w), per_spot, L.ptr(agg),
+                                    L.ptr(win), L.ptr(tie), L.ptr(boards), L.ptr(status)))
+    valid = valid_holdings(hero, board, nboard, dead) & (status == 0)[:, None]
+    return RangeEquity(win, tie, boards, status, agg, valid)
+
+
+def range_equity_d(m, hero_d, board_d, nboard_d, dead_d=None, weights_d=None, weights_per_spot=False, agg_d=None, win_d=None, tie_d=None,
+                   boards_d=None, status_d=None, device=0, stream=None):
+    """pk_equity_range_d: the same on device-resident buffers (device pointers as ints / c_void_p; dead_d, weights_d and the outputs may be
+    None), asynchronous on `stream`."""
+    L.check(L.lib().pk_equity_range_d(int(device), int(m), hero_d, board_d, nboard_d, dead_d, weights_d, int(bool(weights_per_spot)), agg_d,
+                                      win_d, tie_d, boards_d, status_d, stream))
+
+
+def range_equity(hero, board, dead=(), weights=None, device=0):
+    """One spot.  hero: two cards (Card-likes / 'RS' strings / Card.value ints); board: 3 .. 5 known cards; dead: cards known to be out of
+    play; weights: None or [1326] integers 0 .. 65535 over holding_index.  Returns a RangeEquity with [1326] arrays and the scalar
+    `strength`; raises ValueError for an invalid spot."""
+    hero, board = list(hero), list(board)
+    if len(hero) != 2:
+        raise ValueError('the hero holds two cards')
+    if not 3 <= len(board) <= 5:
+        raise ValueError('three to five board cards (range equity is post-flop only)')
+    h = np.array([[_card(c) for c in hero]], np.uint8)
+    b = np.zeros((1, 5), np.uint8)
+    b[0, :len(board)] = [_card(c) for c in board]
+    d = np.array([dead_mask(dead)], np.uint64)
+    if weights is not None and np.ndim(weights) != 1:
+        raise ValueError('weights must have shape [1326]')
+    r = range_equity_batch(h, b, np.array([len(board)], np.uint8), d, weights, device=device)[0]
     if r.status:
         raise ValueError('invalid spot: ' + equity_status_text(r.status))
     return r

@@ -109,6 +109,16 @@ class Game:
             raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
         return r
 
+    def equity_range(self, observer=None, weights=None):
+        """Exact hand strength of `observer` (None = the active seat) against one hidden hand, post-flop (VecGame.equity_range): a
+        judger.RangeEquity with [1326] arrays and the scalar `strength`.  Not in the reference."""
+        from ._lib import OBSERVER_ACTIVE
+        r = self._v.equity_range(observer=OBSERVER_ACTIVE if observer is None else observer, weights=weights, per_holding=True)[0]
+        if r.status:
+            from .judger import equity_status_text
+            raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
+        return r
+
     def step(self, action):                                                       # :621-700
         """Returns (game_over, hand_over, turn_over); raises the reference's ValueError / NotImplementedError /
         AssertionError in the reference's situations."""

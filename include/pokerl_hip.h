@@ -642,6 +642,39 @@ int pk_table_equity_range_d(pk_handle *h, const int32_t *tables_d, size_t m, int
                             uint64_t *agg_d, uint32_t *win_d, uint32_t *tie_d, uint32_t *boards_d, uint8_t *status_d);
 int pk_table_equity_range(pk_handle *h, const int32_t *tables, size_t m, int observer, const uint16_t *weights, int weights_per_spot,
                           uint64_t *agg, uint32_t *win, uint32_t *tie, uint32_t *boards, uint8_t *status);
+/* ---- Range vs range: the exact result of EVERY holding the hero can have on a public board against a weighted opponent range -- the
+ * terminal-node evaluation of a solver.  POST-FLOP ONLY, as range equity.
+ *
+ * A SPOT is board u8[5] with nb = 3, 4 or 5 known cards and dead u64 (bit k = the card of canonical index k is out of play); there is NO hero.
+ * Dead cards = board[0:nb] + `dead`; the pool is the other P cards in canonical order, as above; k = 5 - nb.  A holding (the fixed index
+ * h = b (b - 1) / 2 + a above) is VALID when both its cards are in the pool.
+ * WEIGHTS: weights u16 [1326] is the opponent's range -- one vector for the call (weights_per_spot = 0) or one per spot ([m][1326]); NULL = all 1.
+ * OUTPUTS, three u64 per spot and hero holding h ([m][1326] each; invalid holdings get zeros): take every valid villain holding h' that
+ * shares no card with h and every one of the C(P - 4, k) completions of the board from the pool minus h and h'; on each,
+ * winners = compare_rankings([eval_hand(board + h), eval_hand(board + h')]) exactly as above, the hero at index 0.  Then
+ *   win[h] = sum of w[h'] * (boards the hero wins alone)      tie[h] = sum of w[h'] * (boards both win)
+ *   tot[h] = C(P - 4, k) * (sum of w[h'] over the valid h' that share no card with h)
+ * and per spot boards u32 = C(P - 4, k), status u8.  Strength[h] = (win + tie / 2) / tot is formed by the caller in binary64 (nan where
+ * tot = 0).  The largest value is 65 535 * 1 081 * 990 ~ 7.0e10: u64 holds it; one completion's partial sum, at most 65 535 * 1 081, fits u32.
+ * IDENTITY: row h of a spot is the agg[3] that pk_equity_range returns for hero = h with the same board, `dead` and weights.
+ * STATUS: the PK_EQ_* bits of range equity, except that there is no hero to be a bad or duplicate card, and PK_EQ_SMALL_POOL is P < k + 4
+ * (the pool must hold the board to come and TWO holdings).  A non-zero status gives all-zero outputs and boards = 0, never fails the call and
+ * disturbs no neighbour.
+ * Any output may be NULL; asking for boards / status alone runs only the preparation kernel.  m == 0 is a no-op; m < 2^31;
+ * device < PK_MAX_DEVICES.
+ * TABLE FORM: board = the table's board so far (nb as pk_table_equity), dead = 0; no hole card is read and there is no observer.  It
+ * completes deferred rollout work, reads only, runs on the handle's stream, and reports PK_EQ_IN_FLIGHT / PK_EQ_BAD_TABLE; a table at turn
+ * 0, one never dealt included, is PK_EQ_PREFLOP.
+ * STREAMS and work space: as pk_equity_range. */
+int pk_equity_rvr_d(int device, size_t m, const uint8_t *board_d /*[m][5]*/, const uint8_t *nboard_d, const uint64_t *dead_d /*NULL: none*/,
+                    const uint16_t *weights_d /*NULL: 1*/, int weights_per_spot, uint64_t *win_d /*[m][1326]*/, uint64_t *tie_d, uint64_t *tot_d,
+                    uint32_t *boards_d, uint8_t *status_d, void *stream);
+int pk_equity_rvr(int device, size_t m, const uint8_t *board, const uint8_t *nboard, const uint64_t *dead, const uint16_t *weights,
+                  int weights_per_spot, uint64_t *win, uint64_t *tie, uint64_t *tot, uint32_t *boards, uint8_t *status);
+int pk_table_equity_rvr_d(pk_handle *h, const int32_t *tables_d, size_t m, const uint16_t *weights_d, int weights_per_spot, uint64_t *win_d,
+                          uint64_t *tie_d, uint64_t *tot_d, uint32_t *boards_d, uint8_t *status_d);
+int pk_table_equity_rvr(pk_handle *h, const int32_t *tables, size_t m, const uint16_t *weights, int weights_per_spot, uint64_t *win, uint64_t *tie,
+                        uint64_t *tot, uint32_t *boards, uint8_t *status);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

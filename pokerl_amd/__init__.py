@@ -7,6 +7,7 @@ from .agents import AllInAgent, CallAgent, PokerAgent, RandomAgent
 from .judger import (Equity, SampledEquity, compare_hands, compare_rankings, eval_hand, eval_hands, sampled_equity, sampled_equity_batch,
                      showdown_equity, showdown_equity_batch)
 from .judger import HOLDINGS, RangeEquity, holding_index, range_equity, range_equity_batch, range_equity_d
+from .judger import RangeVsRange, range_vs_range, range_vs_range_batch, range_vs_range_d
 from .sharding import gather_f64, shard_tables
 from .single import Game, PokerGameEnv
 from .state_view import Card, StateView, packed_dtype, unpack_obs
@@ -18,4 +19,5 @@ __all__ = ['Game', 'PokerGameEnv', 'VecGame', 'VecPokerGameEnv', 'VecPokerGameEn
            'PokerlHipError', 'device_count', 'packed_dtype', 'unpack_obs', 'pinned_empty', 'PokerAgent', 'RandomAgent', 'AllInAgent', 'CallAgent',
            'snapshot_nbytes', 'OBSERVER_NONE', 'OBSERVER_ACTIVE', 'Equity', 'showdown_equity', 'showdown_equity_batch',
            'SampledEquity', 'sampled_equity', 'sampled_equity_batch',
-           'HOLDINGS', 'RangeEquity', 'holding_index', 'range_equity', 'range_equity_batch', 'range_equity_d']
+           'HOLDINGS', 'RangeEquity', 'holding_index', 'range_equity', 'range_equity_batch', 'range_equity_d',
+           'RangeVsRange', 'range_vs_range', 'range_vs_range_batch', 'range_vs_range_d']

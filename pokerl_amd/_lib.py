@@ -41,7 +41,8 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_snapshot_bytes", "pk_save_tables_d", "pk_load_tables_d", "pk_save_tables", "pk_load_tables", "pk_clone_tables_d",
            "pk_equity_d", "pk_equity", "pk_table_equity_d", "pk_table_equity",
            "pk_equity_sampled_d", "pk_equity_sampled", "pk_table_equity_sampled_d", "pk_table_equity_sampled", "pk_get_wave_shape",
-           "pk_equity_range_d", "pk_equity_range", "pk_table_equity_range_d", "pk_table_equity_range"]
+           "pk_equity_range_d", "pk_equity_range", "pk_table_equity_range_d", "pk_table_equity_range",
+           "pk_equity_rvr_d", "pk_equity_rvr", "pk_table_equity_rvr_d", "pk_table_equity_rvr"]
 
 
 class PokerlHipError(RuntimeError):
@@ -151,6 +152,10 @@ def lib():
     L.pk_equity_range.argtypes = [C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_int] + [_vp] * 5
     L.pk_table_equity_range_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int] + [_vp] * 5
     L.pk_table_equity_range.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int] + [_vp] * 5
+    L.pk_equity_rvr_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 4 + [C.c_int] + [_vp] * 6
+    L.pk_equity_rvr.argtypes = [C.c_int, C.c_size_t] + [_vp] * 4 + [C.c_int] + [_vp] * 5
+    L.pk_table_equity_rvr_d.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_int] + [_vp] * 5
+    L.pk_table_equity_rvr.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_int] + [_vp] * 5
     for name in SYMBOLS:
         if name not in ("pk_last_error", "pk_build_info", "pk_snapshot_bytes"):
             getattr(L, name).restype = C.c_int

@@ -479,6 +479,43 @@ class VecGame:
                                                   self._dptr(agg_d), self._dptr(win_d), self._dptr(tie_d), self._dptr(boards_d), self._dptr(status_d)),
                 self._h)
 
+    def equity_rvr(self, weights=None, tables=None):
+        """Range against range on the PUBLIC board of `tables` (all tables if None; indices may repeat), post-flop (pk_table_equity_rvr;
+        definition: pokerl_hip.h "Range vs range"): for every holding the hero can have, the weight of the opponent's range it beats, ties
+        and meets, every completion of the board enumerated.  No hole card is read.  weights: None (uniform), uint16 [1326] (one range) or
+        [m, 1326] over judger.holding_index.  Returns a judger.RangeVsRange with uint64 [m, 1326] win / tie / tot (`valid` is None while
+        asynchronous steps are in flight: it is formed from the getters).  A table that cannot be evaluated (pre-flop, step in flight) has a
+        non-zero status and zeros."""
+        from .judger import RangeVsRange, range_weights, rvr_valid_holdings
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        w, per_spot = range_weights(weights, m)
+        win, tie, tot = (np.zeros((m, L.EQ_HOLDINGS), np.uint64) for _ in range(3))
+        boards, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        L.check(self._lib.pk_table_equity_rvr(self._h, L.ptr(t), m, L.ptr(w), per_spot, L.ptr(win), L.ptr(tie), L.ptr(tot), L.ptr(boards),
+                                              L.ptr(status)), self._h)
+        valid = np.zeros((m, L.EQ_HOLDINGS), bool)
+        if not status.all():    # (from the getters, which refuse with PK_E_BUSY while asynchronous steps are in flight: no mask then)
+            try:
+                deck, turn = self.deck, self.turn
+                idx = np.arange(self.num_tables) if t is None else t
+                sel = idx[status == 0]
+                valid[status == 0] = rvr_valid_holdings(deck[sel, :5], np.minimum(turn[sel] + 2, 5))
+            except L.PokerlHipError as e:
+                if e.code != L.PK_E_BUSY:       # (any other failure of a getter is the caller's to see)
+                    raise
+                valid = None
+        return RangeVsRange(win, tie, tot, boards, status, valid)
+
+    def equity_rvr_d(self, m=None, tables_d=None, weights_d=None, weights_per_spot=False, win_d=None, tie_d=None, tot_d=None, boards_d=None,
+                     status_d=None):
+        """pk_table_equity_rvr_d: the same into device buffers (uint64 [m, 1326] win / tie / tot, uint32 [m] boards, uint8 [m] status; any may
+        be None; weights_d uint16 [1326] or [m, 1326] or None), asynchronous on the handle's stream.  m defaults to every table."""
+        m = self.num_tables if m is None else int(m)
+        L.check(self._lib.pk_table_equity_rvr_d(self._h, self._dptr(tables_d), m, self._dptr(weights_d), int(bool(weights_per_spot)),
+                                                self._dptr(win_d), self._dptr(tie_d), self._dptr(tot_d), self._dptr(boards_d), self._dptr(status_d)),
+                self._h)
+
     def __deepcopy__(self, memo):
         """A new handle with the same configuration (seed and table ids included) holding a copy of every table: it continues
         bit-identically to this game under the same actions, and stepping one leaves the other untouched.  Only the construction

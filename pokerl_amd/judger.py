@@ -488,3 +488,110 @@ def range_equity(hero, board, dead=(), weights=None, device=0):
     if r.status:
         raise ValueError('invalid spot: ' + equity_status_text(r.status))
     return r
+
+
+# ---------------------------------------------------------------------------------------------- range vs range
+# The same three numbers for EVERY holding the hero can have on a public board, against a weighted opponent range: the terminal-node
+# evaluation of a solver (pk_equity_rvr; the definition: include/pokerl_hip.h "Range vs range").
+class RangeVsRange:
+    """Sums of one spot or of a batch ([1326] or [m, 1326] uint64 arrays; `boards`, `status` scalars or [m]): for hero holding h, win / tie =
+    the weight of (villain holding, completion) pairs the hero wins alone / splits, tot = the weight of all of them; `valid` = the holdings
+    both of whose cards are in the pool.  `strength` = (win + tie / 2) / tot per holding in float64 (nan where tot = 0);
+    `against(hero_weights)` = the one range-against-range number."""
+
+    def __init__(self, win, tie, tot, boards, status, valid=None):
+        self.win, self.tie, self.tot, self.boards, self.status, self.valid = win, tie, tot, boards, status, valid
+
+    @property
+    def strength(self):
+        num = np.asarray(self.win, np.float64) + 0.5 * np.asarray(self.tie, np.float64)
+        den = np.asarray(self.tot, np.float64)
+        return np.divide(num, den, out=np.full(np.shape(den), np.nan, np.float64), where=den > 0)
+
+    def against(self, hero_weights=None):
+        """sum u[h] (win[h] + tie[h] / 2) / sum u[h] tot[h] over the hero's range u ([1326] integers; None = ones): the sums in Python
+        integers, the quotient in float64 (nan where the denominator is 0).  One spot -> float, a batch -> [m] float64."""
+        u = [1] * L.EQ_HOLDINGS if hero_weights is None else [int(x) for x in np.asarray(hero_weights).reshape(-1)]
+        if len(u) != L.EQ_HOLDINGS or min(u) < 0:
+            raise ValueError('hero_weights must be 1326 non-negative integers')
+
+        def one(win, tie, tot):
+            num2 = sum(x * (2 * int(w) + int(t)) for x, w, t in zip(u, win, tie))
+            den = sum(x * int(t) for x, t in zip(u, tot))
+            return num2 / (2 * den) if den else float('nan')
+        if np.ndim(self.win) == 1:
+            return one(self.win, self.tie, self.tot)
+        return np.array([one(w, t, d) for w, t, d in zip(self.win, self.tie, self.tot)], np.float64)
+
+    def __getitem__(self, i):
+        return RangeVsRange(self.win[i], self.tie[i], self.tot[i], self.boards[i], self.status[i], None if self.valid is None else self.valid[i])
+
+    def __repr__(self):
+        return 'RangeVsRange(boards=%r, status=%r)' % (self.boards, self.status)
+
+
+def range_vs_range_batch(board, nboard, dead=None, weights=None, device=0):
+    """pk_equity_rvr on host arrays: board uint8 [m, 5] Card.value (the first nboard[i] = 3, 4 or 5 used), nboard uint8 [m], dead uint64 [m]
+    masks over canonical card indices (None: none), weights None / uint16 [1326] / [m, 1326] (the opponent's range) -> RangeVsRange.  A bad
+    spot is reported through its `status` (PK_EQ_* bits) with all-zero outputs; the others are unaffected."""
+    board = np.ascontiguousarray(board, np.uint8)
+    if board.ndim != 2 or board.shape[1] != 5:
+        raise ValueError('board must have shape [m, 5]')
+    m = board.shape[0]
+    nboard = np.ascontiguousarray(nboard, np.uint8)
+    if nboard.shape != (m,):
+        raise ValueError('nboard must have shape [m]')
+    if dead is not None:
+        dead = np.ascontiguousarray(dead, np.uint64)
+        if dead.shape != (m,):
+            raise ValueError('dead must have shape [m]')
+    w, per_spot = range_weights(weights, m)
+    win, tie, tot = (np.zeros((m, L.EQ_HOLDINGS), np.uint64) for _ in range(3))
+    boards, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+    L.check(L.lib().pk_equity_rvr(int(device), m, L.ptr(board), L.ptr(nboard), L.ptr(dead), L.ptr(w), per_spot, L.ptr(win), L.ptr(tie),
+                                  L.ptr(tot), L.ptr(boards), L.ptr(status)))
+    return RangeVsRange(win, tie, tot, boards, status, rvr_valid_holdings(board, nboard, dead) & (status == 0)[:, None])
+
+
+def rvr_valid_holdings(board, nboard, dead=None):
+    """bool [m, 1326]: the holdings both of whose cards are in the pool of each range-vs-range spot (valid_holdings without a hero)."""
+    board = np.asarray(board, np.uint8)
+    m = board.shape[0]
+    canon = lambda v: (v.astype(np.int64) & 15) * 4 + (v.astype(np.int64) >> 4)
+    out = np.zeros((m, 52), bool)
+    rows = np.arange(m)
+    nb = np.minimum(np.asarray(nboard, np.int64), 5)
+    for j in range(5):
+        sel = nb > j
+        out[rows[sel], np.clip(canon(board[sel, j]), 0, 51)] = True
+    if dead is not None:
+        out |= ((np.asarray(dead, np.uint64)[:, None] >> np.arange(52, dtype=np.uint64)) & np.uint64(1)).astype(bool)
+    a = np.array([a for b in range(52) for a in range(b)])
+    b = np.array([b for b in range(52) for a in range(b)])
+    return ~out[:, a] & ~out[:, b]
+
+
+def range_vs_range_d(m, board_d, nboard_d, dead_d=None, weights_d=None, weights_per_spot=False, win_d=None, tie_d=None, tot_d=None,
+                     boards_d=None, status_d=None, device=0, stream=None):
+    """pk_equity_rvr_d: the same on device-resident buffers (device pointers as ints / c_void_p; dead_d, weights_d and the outputs may be
+    None; win / tie / tot are uint64 [m, 1326]), asynchronous on `stream`."""
+    L.check(L.lib().pk_equity_rvr_d(int(device), int(m), board_d, nboard_d, dead_d, weights_d, int(bool(weights_per_spot)), win_d, tie_d,
+                                    tot_d, boards_d, status_d, stream))
+
+
+def range_vs_range(board, dead=(), weights=None, device=0):
+    """One spot.  board: 3 .. 5 known cards (Card-likes / 'RS' strings / Card.value ints); dead: cards known to be out of play; weights:
+    None or [1326] integers 0 .. 65535 over holding_index, the opponent's range.  Returns a RangeVsRange with [1326] arrays; raises
+    ValueError for an invalid spot."""
+    board = list(board)
+    if not 3 <= len(board) <= 5:
+        raise ValueError('invalid spot: ' + equity_status_text(L.EQ_PREFLOP) if len(board) < 3 else 'three to five board cards')
+    b = np.zeros((1, 5), np.uint8)
+    b[0, :len(board)] = [_card(c) for c in board]
+    d = np.array([dead_mask(dead)], np.uint64)
+    if weights is not None and np.ndim(weights) != 1:
+        raise ValueError('weights must have shape [1326]')
+    r = range_vs_range_batch(b, np.array([len(board)], np.uint8), d, weights, device=device)[0]
+    if r.status:
+        raise ValueError('invalid spot: ' + equity_status_text(r.status))
+    return r

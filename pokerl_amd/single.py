@@ -119,6 +119,15 @@ class Game:
             raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
         return r
 
+    def equity_rvr(self, weights=None):
+        """Range against range on the public board, post-flop (VecGame.equity_rvr): a judger.RangeVsRange with [1326] arrays -- every
+        holding the hero can have against the opponent's range `weights`.  Not in the reference."""
+        r = self._v.equity_rvr(weights=weights)[0]
+        if r.status:
+            from .judger import equity_status_text
+            raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
+        return r
+
     def step(self, action):                                                       # :621-700
         """Returns (game_over, hand_over, turn_over); raises the reference's ValueError / NotImplementedError /
         AssertionError in the reference's situations."""

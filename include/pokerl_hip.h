@@ -675,6 +675,41 @@ int pk_table_equity_rvr_d(pk_handle *h, const int32_t *tables_d, size_t m, const
                           uint64_t *tie_d, uint64_t *tot_d, uint32_t *boards_d, uint8_t *status_d);
 int pk_table_equity_rvr(pk_handle *h, const int32_t *tables, size_t m, const uint16_t *weights, int weights_per_spot, uint64_t *win, uint64_t *tie,
                         uint64_t *tot, uint32_t *boards, uint8_t *status);
+/* ---- Strength histograms: for EVERY holding the hero can have on a public board, how its RIVER strength against a weighted opponent range
+ * is distributed over the completions of the board -- the input of distribution-aware card abstraction and a "hand potential" feature
+ * (DESIGN.md section 3.5).  POST-FLOP ONLY, as range equity.
+ *
+ * SPOT, WEIGHTS, STATUS, TABLE FORM, STREAMS and work space are exactly those of range vs range above: board u8[5] with nb = 3, 4 or 5 known
+ * cards, dead u64, no hero; weights u16 [1326] shared or per spot, NULL = all 1; a holding is VALID when both its cards are in the pool of
+ * P cards; k = 5 - nb; the PK_EQ_* bits with PK_EQ_SMALL_POOL = P < k + 4.  The same spot gets the same status from both families.
+ * NBINS: one per call, 1 .. PK_EQ_HIST_MAX_BINS; anything else is PK_E_INVALID_ARG before any launch.
+ * PER valid hero holding h and per completion c -- one of the C(P - 2, k) sets of k cards from the pool minus h: let V(h, c) be the valid
+ * holdings that share no card with h or c (never empty: P >= k + 4).  On board + c every h' in V has
+ * winners = compare_rankings([eval_hand(board + c + h), eval_hand(board + c + h')]) exactly as above, the hero at index 0, and
+ *   below = sum of w[h'] where the hero wins alone     equal = sum of w[h'] where both win     den = sum of w[h'] over V.
+ * If den = 0 (the range has no weight left after card removal) void[h] += 1; otherwise, in integers,
+ *   bin = min(nbins - 1, floor(nbins * (2 below + equal) / (2 den)))     hist[h][bin] += 1
+ * so strength exactly j / nbins lands in bin j and strength 1 in the last bin.  Every product fits 32 bits:
+ * 32 * 2 * 65 535 * C(45, 2) = 4 152 297 600 < 2^32 (990 = the most villain holdings that can be live at once).
+ * OUTPUTS: hist u16 [m][1326][nbins], void u16 [m][1326] (the largest count is C(47, 2) = 1 081), completions u32 [m] = C(P - 2, k) -- the
+ * completions ONE holding meets, NOT the `boards` = C(P - 4, k) of range vs range, which counts per pair of holdings -- and status u8 [m].
+ * Invalid holdings and refused spots are all zeros (completions = 0); every entry is written, the caller clears nothing.
+ * INVARIANT: for a valid h, sum over b of hist[h][b] + void[h] = completions.
+ * IDENTITY: for a completion c, the river spot (board + c, the same dead, the same weights) has the same pool minus c, and row h of its
+ * pk_equity_rvr is (win, tie, tot) = (below, equal, den) for every h that shares no card with c: a spot's histogram is the sum over its
+ * completions of the one-hot bins of those river rows.  At nb = 5 there is one completion: a single count of 1 per valid holding.
+ * Any output may be NULL; asking for completions / status alone runs only the one-lane-per-spot kernels.  m == 0 is a no-op; m < 2^31;
+ * device < PK_MAX_DEVICES. */
+#define PK_EQ_HIST_MAX_BINS 32
+int pk_equity_hist_d(int device, size_t m, const uint8_t *board_d /*[m][5]*/, const uint8_t *nboard_d, const uint64_t *dead_d /*NULL: none*/,
+                     const uint16_t *weights_d /*NULL: 1*/, int weights_per_spot, int nbins, uint16_t *hist_d /*[m][1326][nbins]*/,
+                     uint16_t *void_d /*[m][1326]*/, uint32_t *completions_d, uint8_t *status_d, void *stream);
+int pk_equity_hist(int device, size_t m, const uint8_t *board, const uint8_t *nboard, const uint64_t *dead, const uint16_t *weights,
+                   int weights_per_spot, int nbins, uint16_t *hist, uint16_t *void_, uint32_t *completions, uint8_t *status);
+int pk_table_equity_hist_d(pk_handle *h, const int32_t *tables_d, size_t m, const uint16_t *weights_d, int weights_per_spot, int nbins,
+                           uint16_t *hist_d, uint16_t *void_d, uint32_t *completions_d, uint8_t *status_d);
+int pk_table_equity_hist(pk_handle *h, const int32_t *tables, size_t m, const uint16_t *weights, int weights_per_spot, int nbins, uint16_t *hist,
+                         uint16_t *void_, uint32_t *completions, uint8_t *status);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

@@ -23,6 +23,7 @@ EQ_SHARE_UNIT = 720720   # lcm(1 .. 16): a board's pot share of one of nw winner
 EQ_BAD_CARD, EQ_DUP_CARD, EQ_NO_LIVE, EQ_BAD_NBOARD, EQ_IN_FLIGHT, EQ_BAD_TABLE = 1, 2, 4, 8, 16, 32   # PK_EQ_* status bits
 OBSERVER_NONE, OBSERVER_ACTIVE = -1, -2   # pk_clone_tables_d: an exact copy / redeal from each source table's active player
 EQ_PREFLOP, EQ_SMALL_POOL = 64, 128   # ... of pk_equity_range: nb < 3 / fewer pool cards than the board to come plus one holding
+EQ_HIST_MAX_BINS = 32   # PK_EQ_HIST_MAX_BINS: the most bins of a strength histogram
 EQ_HOLDINGS = 1326   # PK_EQ_HOLDINGS: unordered pairs of the 52 cards, h = b (b - 1) / 2 + a over canonical indices a < b
 EQS_SAMPLES_MAX = 1 << 24   # pk_equity_sampled: samples per call and spot at most
 
@@ -42,7 +43,8 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_equity_d", "pk_equity", "pk_table_equity_d", "pk_table_equity",
            "pk_equity_sampled_d", "pk_equity_sampled", "pk_table_equity_sampled_d", "pk_table_equity_sampled", "pk_get_wave_shape",
            "pk_equity_range_d", "pk_equity_range", "pk_table_equity_range_d", "pk_table_equity_range",
-           "pk_equity_rvr_d", "pk_equity_rvr", "pk_table_equity_rvr_d", "pk_table_equity_rvr"]
+           "pk_equity_rvr_d", "pk_equity_rvr", "pk_table_equity_rvr_d", "pk_table_equity_rvr",
+           "pk_equity_hist_d", "pk_equity_hist", "pk_table_equity_hist_d", "pk_table_equity_hist"]
 
 
 class PokerlHipError(RuntimeError):
@@ -156,6 +158,10 @@ def lib():
     L.pk_equity_rvr.argtypes = [C.c_int, C.c_size_t] + [_vp] * 4 + [C.c_int] + [_vp] * 5
     L.pk_table_equity_rvr_d.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_int] + [_vp] * 5
     L.pk_table_equity_rvr.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_int] + [_vp] * 5
+    L.pk_equity_hist_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 4 + [C.c_int, C.c_int] + [_vp] * 5
+    L.pk_equity_hist.argtypes = [C.c_int, C.c_size_t] + [_vp] * 4 + [C.c_int, C.c_int] + [_vp] * 4
+    L.pk_table_equity_hist_d.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_int, C.c_int] + [_vp] * 4
+    L.pk_table_equity_hist.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_int, C.c_int] + [_vp] * 4
     for name in SYMBOLS:
         if name not in ("pk_last_error", "pk_build_info", "pk_snapshot_bytes"):
             getattr(L, name).restype = C.c_int

@@ -19,6 +19,7 @@
 #include "pk_equity_sampled.hpp"
 #include "pk_equity_range.hpp"
 #include "pk_equity_rvr.hpp"
+#include "pk_equity_hist.hpp"
 #include "pk_snapshot.hpp"
 
 using namespace pk;
@@ -137,6 +138,14 @@ struct RvrStagedOut {
         : win(g.out(win, m * RVR_HOLDINGS * 8)), tie(g.out(tie, m * RVR_HOLDINGS * 8)), tot(g.out(tot, m * RVR_HOLDINGS * 8)), boards(g.out(boards, m * 4)),
           status(g.out(status, m)) {}
     RvrOut at(const Stage &g) const { return RvrOut{g.at<uint64_t>(win), g.at<uint64_t>(tie), g.at<uint64_t>(tot), g.at<uint32_t>(boards), g.at<uint8_t>(status)}; }
+};
+// ... and a strength-histogram call
+struct HistStagedOut {
+    int hist, void_, completions, status;
+    HistStagedOut(Stage &g, size_t m, int nbins, uint16_t *hist, uint16_t *void_, uint32_t *completions, uint8_t *status)
+        : hist(g.out(hist, m * RVR_HOLDINGS * (size_t)nbins * 2)), void_(g.out(void_, m * RVR_HOLDINGS * 2)), completions(g.out(completions, m * 4)),
+          status(g.out(status, m)) {}
+    HistOut at(const Stage &g) const { return HistOut{g.at<uint16_t>(hist), g.at<uint16_t>(void_), g.at<uint32_t>(completions), g.at<uint8_t>(status)}; }
 };
 }  // namespace
 
@@ -2222,6 +2231,99 @@ int pk_table_equity_rvr(pk_handle *h, const int32_t *tables, size_t m, const uin
     if (rc) return rc;
     HIPCHK(h, g.upload(h->stream));
     if ((rc = table_equity_rvr(h, g.at<int32_t>(idx), m, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, out.at(g), g.at<char>(work)))) return rc;
+    HIPCHK(h, g.download(h->stream));
+    return PK_OK;
+}
+
+// ---- strength histograms (pokerl_hip.h "Strength histograms"; kernels: pk_equity_hist.hip).  Spots, weights and work space as range vs range.
+static_assert(HIST_MAX_BINS == PK_EQ_HIST_MAX_BINS, "pk_equity_hist.hpp and the ABI header agree");
+#define HIST_CHECK_BINS(call, nbins) \
+    if ((nbins) < 1 || (nbins) > PK_EQ_HIST_MAX_BINS) return g_fail(PK_E_INVALID_ARG, call ": nbins must be 1 .. PK_EQ_HIST_MAX_BINS (32)")
+
+int pk_equity_hist_d(int device, size_t m, const uint8_t *board_d, const uint8_t *nboard_d, const uint64_t *dead_d, const uint16_t *weights_d,
+                     int weights_per_spot, int nbins, uint16_t *hist_d, uint16_t *void_d, uint32_t *completions_d, uint8_t *status_d, void *stream) {
+    EQR_CHECK_SPOTS("pk_equity_hist_d", m, board_d && nboard_d);
+    HIST_CHECK_BINS("pk_equity_hist_d", nbins);
+    ON_DEVICE_INDEX("pk_equity_hist_d", device, PK_MAX_DEVICES);
+    if (m == 0) return PK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t *tab = eval7_table(device, st);   // (a first call builds the table on the CALLER's stream)
+    if (!tab) return g_fail(PK_E_OOM, "pk_equity_hist_d: out of device memory (evaluator table)");
+    void *ws = eq_stream_ws(device, st, rvr_work_bytes(m));
+    if (!ws) return g_fail(PK_E_OOM, "pk_equity_hist_d: out of device memory (work space)");
+    const RvrSpots spots{board_d, nboard_d, dead_d};
+    const hipError_t e = hist_launch(st, tab, &spots, nullptr, RvrWeights{weights_d, weights_per_spot != 0}, m, nbins,
+                                     HistOut{hist_d, void_d, completions_d, status_d}, (uint64_t *)ws);
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_hist_d: launch failed", e);
+    return PK_OK;
+}
+
+int pk_equity_hist(int device, size_t m, const uint8_t *board, const uint8_t *nboard, const uint64_t *dead, const uint16_t *weights,
+                   int weights_per_spot, int nbins, uint16_t *hist, uint16_t *void_, uint32_t *completions, uint8_t *status) {
+    EQR_CHECK_SPOTS("pk_equity_hist", m, board && nboard);
+    HIST_CHECK_BINS("pk_equity_hist", nbins);
+    ON_DEVICE_INDEX("pk_equity_hist", device, PK_MAX_DEVICES);
+    if (m == 0) return PK_OK;
+    hipStream_t st = nullptr;
+    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity_hist: no stream"); }
+    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
+    int rc = PK_OK;
+    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity_hist: out of device memory (evaluator table)");
+    else {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        Stage g;
+        const int bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
+        const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+        const HistStagedOut out(g, m, nbins, hist, void_, completions, status);
+        const int work = g.add(rvr_work_bytes(m));
+        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity_hist: out of device memory");
+        else {
+            const hipError_t e = g.run(st, [&] {
+                const RvrSpots spots{g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
+                return hist_launch(st, tab, &spots, nullptr, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, nbins, out.at(g), g.at<uint64_t>(work));
+            });
+            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity_hist", e); }   // (the lock is held until what was queued is done)
+        }
+    }
+    stream_release(device, st);
+    return rc;
+}
+
+// The table form: the public board of the handle's own tables on the handle's stream (no hole card is read: there is no observer)
+static int table_equity_hist(pk_handle *h, const int32_t *tables_d, size_t m, const RvrWeights &weights, int nbins, const HistOut &out, char *work) {
+    const uint32_t *tab = eval7_table(h->device, h->stream);
+    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity_hist: out of device memory (evaluator table)");
+    const EqTables t{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T};
+    HIPCHK(h, hist_launch(h->stream, tab, nullptr, &t, weights, m, nbins, out, (uint64_t *)work));
+    return PK_OK;
+}
+#define HIST_TABLE_ENTER(h, m, nbins, call)                                                                                      \
+    if (!(h)) return PK_E_INVALID_ARG;                                                                                           \
+    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                                             \
+    if ((nbins) < 1 || (nbins) > PK_EQ_HIST_MAX_BINS) return (h)->fail(PK_E_INVALID_ARG, call ": nbins must be 1 .. PK_EQ_HIST_MAX_BINS (32)"); \
+    ON_DEVICE(h);                                                                                                                \
+    FLUSH_READER(h);                                                                                                             \
+    if ((m) == 0) return PK_OK
+
+int pk_table_equity_hist_d(pk_handle *h, const int32_t *tables_d, size_t m, const uint16_t *weights_d, int weights_per_spot, int nbins,
+                           uint16_t *hist_d, uint16_t *void_d, uint32_t *completions_d, uint8_t *status_d) {
+    HIST_TABLE_ENTER(h, m, nbins, "pk_table_equity_hist_d");
+    char *work = nullptr;
+    if (int rc = snap_staging(h, rvr_work_bytes(m), &work)) return rc;
+    return table_equity_hist(h, tables_d, m, RvrWeights{weights_d, weights_per_spot != 0}, nbins, HistOut{hist_d, void_d, completions_d, status_d}, work);
+}
+
+int pk_table_equity_hist(pk_handle *h, const int32_t *tables, size_t m, const uint16_t *weights, int weights_per_spot, int nbins, uint16_t *hist,
+                         uint16_t *void_, uint32_t *completions, uint8_t *status) {
+    HIST_TABLE_ENTER(h, m, nbins, "pk_table_equity_hist");
+    Stage g;
+    const int idx = g.in(tables, m * 4), we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const HistStagedOut out(g, m, nbins, hist, void_, completions, status);
+    const int work = g.add(rvr_work_bytes(m));
+    int rc = snap_staging(h, g.total, &g.base);
+    if (rc) return rc;
+    HIPCHK(h, g.upload(h->stream));
+    if ((rc = table_equity_hist(h, g.at<int32_t>(idx), m, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, nbins, out.at(g), g.at<char>(work)))) return rc;
     HIPCHK(h, g.download(h->stream));
     return PK_OK;
 }

@@ -293,9 +293,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
 
 namespace pk {
 
-hipError_t rvr_launch(hipStream_t stream, const uint32_t *tab, const RvrSpots *spots, const EqTables *tables, const RvrWeights &weights, size_t m,
-                      const RvrOut &out, uint64_t *desc) {
-    if (m == 0) return hipSuccess;
+hipError_t rvr_prep_launch(hipStream_t stream, const RvrSpots *spots, const EqTables *tables, size_t m, const RvrOut &out, uint64_t *desc) {
     RvrPrepArgs a{};
     if (spots) a.s = *spots;
     if (tables) a.t = *tables;
@@ -303,7 +301,13 @@ hipError_t rvr_launch(hipStream_t stream, const uint32_t *tab, const RvrSpots *s
     const dim3 pgrid((unsigned)((m + RVR_PREP_BLOCK - 1) / RVR_PREP_BLOCK));
     if (tables) hipLaunchKernelGGL(k_rvr_prep<true>, pgrid, dim3(RVR_PREP_BLOCK), 0, stream, a);
     else hipLaunchKernelGGL(k_rvr_prep<false>, pgrid, dim3(RVR_PREP_BLOCK), 0, stream, a);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t rvr_launch(hipStream_t stream, const uint32_t *tab, const RvrSpots *spots, const EqTables *tables, const RvrWeights &weights, size_t m,
+                      const RvrOut &out, uint64_t *desc) {
+    if (m == 0) return hipSuccess;
+    const hipError_t e = rvr_prep_launch(stream, spots, tables, m, out, desc);
     if (e != hipSuccess || !(out.win || out.tie || out.tot)) return e;   // (boards / status alone: the preparation kernel has written them)
     // one workgroup per spot at a time (each stages the 32 KB table); the grid is persistent beyond two workgroups per CU
     const unsigned grid = (unsigned)(m < (size_t)RVR_GRID_MAX ? m : (size_t)RVR_GRID_MAX);

@@ -43,5 +43,8 @@ struct RvrWeights {
 // persistent kernel.  tab: the evaluator table (eval7_table); `tables` non-NULL selects the table form.
 hipError_t rvr_launch(hipStream_t stream, const uint32_t *tab, const RvrSpots *spots, const EqTables *tables, const RvrWeights &weights, size_t m,
                       const RvrOut &out, uint64_t *desc);
+// The preparation kernel alone (m > 0): descriptors + boards / status (the win / tie / tot of `out` are not looked at).  The strength
+// histograms (pk_equity_hist.hip) check their spots with it too: the same spot gets the same status from both families.
+hipError_t rvr_prep_launch(hipStream_t stream, const RvrSpots *spots, const EqTables *tables, size_t m, const RvrOut &out, uint64_t *desc);
 
 }  // namespace pk

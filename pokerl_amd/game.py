@@ -516,6 +516,46 @@ class VecGame:
                                                 self._dptr(win_d), self._dptr(tie_d), self._dptr(tot_d), self._dptr(boards_d), self._dptr(status_d)),
                 self._h)
 
+    def equity_hist(self, weights=None, tables=None, bins=10):
+        """Strength histograms on the PUBLIC board of `tables` (all tables if None; indices may repeat), post-flop (pk_table_equity_hist;
+        definition: pokerl_hip.h "Strength histograms"): for every holding the hero can have, the distribution of its river strength against
+        the opponent's range over the completions of the board, in `bins` (1 .. 32) equal parts of [0, 1].  No hole card is read.  weights:
+        None (uniform), uint16 [1326] (one range) or [m, 1326] over judger.holding_index.  Returns a judger.StrengthHistogram with uint16
+        [m, 1326, bins] hist and [m, 1326] void (`valid` is None while asynchronous steps are in flight: it is formed from the getters).  A
+        table that cannot be evaluated (pre-flop, step in flight) has a non-zero status and zeros."""
+        from .judger import StrengthHistogram, check_bins, range_weights, rvr_valid_holdings
+        bins = check_bins(bins)
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        w, per_spot = range_weights(weights, m)
+        hist, void = np.zeros((m, L.EQ_HOLDINGS, bins), np.uint16), np.zeros((m, L.EQ_HOLDINGS), np.uint16)
+        completions, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        L.check(self._lib.pk_table_equity_hist(self._h, L.ptr(t), m, L.ptr(w), per_spot, bins, L.ptr(hist), L.ptr(void), L.ptr(completions),
+                                               L.ptr(status)), self._h)
+        valid = np.zeros((m, L.EQ_HOLDINGS), bool)
+        if not status.all():    # (from the getters, which refuse with PK_E_BUSY while asynchronous steps are in flight: no mask then)
+            try:
+                deck, turn = self.deck, self.turn
+                idx = np.arange(self.num_tables) if t is None else t
+                sel = idx[status == 0]
+                valid[status == 0] = rvr_valid_holdings(deck[sel, :5], np.minimum(turn[sel] + 2, 5))
+            except L.PokerlHipError as e:
+                if e.code != L.PK_E_BUSY:       # (any other failure of a getter is the caller's to see)
+                    raise
+                valid = None
+        return StrengthHistogram(hist, void, completions, status, valid)
+
+    def equity_hist_d(self, m=None, tables_d=None, weights_d=None, weights_per_spot=False, bins=10, hist_d=None, void_d=None, completions_d=None,
+                      status_d=None):
+        """pk_table_equity_hist_d: the same into device buffers (uint16 [m, 1326, bins] hist, uint16 [m, 1326] void, uint32 [m] completions,
+        uint8 [m] status; any may be None; weights_d uint16 [1326] or [m, 1326] or None), asynchronous on the handle's stream.  m defaults
+        to every table."""
+        from .judger import check_bins
+        m = self.num_tables if m is None else int(m)
+        L.check(self._lib.pk_table_equity_hist_d(self._h, self._dptr(tables_d), m, self._dptr(weights_d), int(bool(weights_per_spot)),
+                                                 check_bins(bins), self._dptr(hist_d), self._dptr(void_d), self._dptr(completions_d),
+                                                 self._dptr(status_d)), self._h)
+
     def __deepcopy__(self, memo):
         """A new handle with the same configuration (seed and table ids included) holding a copy of every table: it continues
         bit-identically to this game under the same actions, and stepping one leaves the other untouched.  Only the construction

@@ -595,3 +595,109 @@ def range_vs_range(board, dead=(), weights=None, device=0):
     if r.status:
         raise ValueError('invalid spot: ' + equity_status_text(r.status))
     return r
+
+
+# ---------------------------------------------------------------------------------------------- strength histograms
+# For EVERY holding the hero can have on a public board: how its river strength against a weighted opponent range is distributed over the
+# completions of the board (pk_equity_hist; the definition: include/pokerl_hip.h "Strength histograms").
+def check_bins(bins):
+    """bins as an int 1 .. PK_EQ_HIST_MAX_BINS; ValueError otherwise (before any device call)."""
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= L.EQ_HIST_MAX_BINS:
+        raise ValueError('bins must be an integer 1 .. %d' % L.EQ_HIST_MAX_BINS)
+    return int(bins)
+
+
+class StrengthHistogram:
+    """Counts of one spot or of a batch: hist uint16 [1326, bins] or [m, 1326, bins] -- completions of the board on which holding h's river
+    strength (below + equal / 2) / den falls into each of `bins` equal parts of [0, 1] --, void uint16 [1326] or [m, 1326] -- completions on
+    which the opponent's range has no weight left --, `completions` = C(P - 2, k) and `status` scalars or [m]; `valid` = the holdings both
+    of whose cards are in the pool.  For a valid h: hist[h].sum() + void[h] == completions.  `pdf` = hist / hist.sum(-1) in float64 (nan
+    where nothing was counted), `cdf` its running sum."""
+
+    def __init__(self, hist, void, completions, status, valid=None):
+        self.hist, self.void, self.completions, self.status, self.valid = hist, void, completions, status, valid
+
+    @property
+    def bins(self):
+        return np.shape(self.hist)[-1]
+
+    @property
+    def pdf(self):
+        h = np.asarray(self.hist, np.float64)
+        n = h.sum(axis=-1, keepdims=True)
+        return np.divide(h, n, out=np.full(h.shape, np.nan, np.float64), where=n > 0)
+
+    @property
+    def cdf(self):
+        return np.cumsum(self.pdf, axis=-1)
+
+    def __getitem__(self, i):
+        return StrengthHistogram(self.hist[i], self.void[i], self.completions[i], self.status[i], None if self.valid is None else self.valid[i])
+
+    def __repr__(self):
+        return 'StrengthHistogram(bins=%r, completions=%r, status=%r)' % (self.bins, self.completions, self.status)
+
+
+def histogram_emd(a, b):
+    """The 1-D earth mover's distance of two strength histograms in BIN units: the L1 distance of their CDFs, sum over bins of |cdf_a -
+    cdf_b|.  a, b: count or probability arrays [..., bins] (each normalised by its own sum; broadcast against each other), float64 out;
+    nan where either has no mass.  Divide by bins for units of strength."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    if a.ndim < 1 or b.ndim < 1 or a.shape[-1] != b.shape[-1]:
+        raise ValueError('histograms must have the same number of bins')
+
+    def cdf(x):
+        n = x.sum(axis=-1, keepdims=True)
+        return np.cumsum(np.divide(x, n, out=np.full(x.shape, np.nan, np.float64), where=n > 0), axis=-1)
+    return np.abs(cdf(a) - cdf(b)).sum(axis=-1)
+
+
+def strength_histogram_batch(board, nboard, dead=None, weights=None, bins=10, device=0):
+    """pk_equity_hist on host arrays: board uint8 [m, 5] Card.value (the first nboard[i] = 3, 4 or 5 used), nboard uint8 [m], dead uint64 [m]
+    masks over canonical card indices (None: none), weights None / uint16 [1326] / [m, 1326] (the opponent's range), bins 1 .. 32 ->
+    StrengthHistogram.  A bad spot is reported through its `status` (PK_EQ_* bits) with all-zero outputs; the others are unaffected."""
+    bins = check_bins(bins)
+    board = np.ascontiguousarray(board, np.uint8)
+    if board.ndim != 2 or board.shape[1] != 5:
+        raise ValueError('board must have shape [m, 5]')
+    m = board.shape[0]
+    nboard = np.ascontiguousarray(nboard, np.uint8)
+    if nboard.shape != (m,):
+        raise ValueError('nboard must have shape [m]')
+    if dead is not None:
+        dead = np.ascontiguousarray(dead, np.uint64)
+        if dead.shape != (m,):
+            raise ValueError('dead must have shape [m]')
+    w, per_spot = range_weights(weights, m)
+    hist, void = np.zeros((m, L.EQ_HOLDINGS, bins), np.uint16), np.zeros((m, L.EQ_HOLDINGS), np.uint16)
+    completions, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+    L.check(L.lib().pk_equity_hist(int(device), m, L.ptr(board), L.ptr(nboard), L.ptr(dead), L.ptr(w), per_spot, bins, L.ptr(hist), L.ptr(void),
+                                   L.ptr(completions), L.ptr(status)))
+    return StrengthHistogram(hist, void, completions, status, rvr_valid_holdings(board, nboard, dead) & (status == 0)[:, None])
+
+
+def strength_histogram_d(m, board_d, nboard_d, dead_d=None, weights_d=None, weights_per_spot=False, bins=10, hist_d=None, void_d=None,
+                         completions_d=None, status_d=None, device=0, stream=None):
+    """pk_equity_hist_d: the same on device-resident buffers (device pointers as ints / c_void_p; dead_d, weights_d and the outputs may be
+    None; hist is uint16 [m, 1326, bins], void uint16 [m, 1326]), asynchronous on `stream`."""
+    L.check(L.lib().pk_equity_hist_d(int(device), int(m), board_d, nboard_d, dead_d, weights_d, int(bool(weights_per_spot)), check_bins(bins),
+                                     hist_d, void_d, completions_d, status_d, stream))
+
+
+def strength_histogram(board, dead=(), weights=None, bins=10, device=0):
+    """One spot.  board: 3 .. 5 known cards (Card-likes / 'RS' strings / Card.value ints); dead: cards known to be out of play; weights:
+    None or [1326] integers 0 .. 65535 over holding_index, the opponent's range; bins 1 .. 32.  Returns a StrengthHistogram with
+    [1326, bins] / [1326] arrays; raises ValueError for an invalid spot."""
+    bins = check_bins(bins)
+    board = list(board)
+    if not 3 <= len(board) <= 5:
+        raise ValueError('invalid spot: ' + equity_status_text(L.EQ_PREFLOP) if len(board) < 3 else 'three to five board cards')
+    b = np.zeros((1, 5), np.uint8)
+    b[0, :len(board)] = [_card(c) for c in board]
+    d = np.array([dead_mask(dead)], np.uint64)
+    if weights is not None and np.ndim(weights) != 1:
+        raise ValueError('weights must have shape [1326]')
+    r = strength_histogram_batch(b, np.array([len(board)], np.uint8), d, weights, bins, device=device)[0]
+    if r.status:
+        raise ValueError('invalid spot: ' + equity_status_text(r.status))
+    return r

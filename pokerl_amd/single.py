@@ -128,6 +128,15 @@ class Game:
             raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
         return r
 
+    def equity_hist(self, weights=None, bins=10):
+        """Strength histograms on the public board, post-flop (VecGame.equity_hist): a judger.StrengthHistogram with [1326, bins] hist --
+        the distribution of every holding's river strength against the opponent's range `weights`.  Not in the reference."""
+        r = self._v.equity_hist(weights=weights, bins=bins)[0]
+        if r.status:
+            from .judger import equity_status_text
+            raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
+        return r
+
     def step(self, action):                                                       # :621-700
         """Returns (game_over, hand_over, turn_over); raises the reference's ValueError / NotImplementedError /
         AssertionError in the reference's situations."""

@@ -162,11 +162,11 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
     const uint32_t listed = W.ctrl->ntasks;
     const uint32_t ntasks = listed < W.task_cap ? listed : (uint32_t)W.task_cap;
     if (blockIdx.x * EQ_WAVES >= ntasks) return;                 // (the whole workgroup: before the table is staged)
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQ_BLOCK) reinterpret_cast<uint4 *>(T)[i] = reinterpret_cast<const uint4 *>(tab)[i];
-    if (threadIdx.x < 32) wt[threadIdx.x] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
+    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQ_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
+    if (threadIdx.x < 32) wt[PK_IDX(threadIdx.x, 32, "wt")] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, wave = eq_uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
-    uint64_t *mypool = pool[wave];
+    uint64_t *mypool = pool[PK_IDX(wave, EQ_WAVES, "pool")];
     // Tasks are taken in runs of `take` consecutive ones: a wavefront's first run is its own number, the next ones come from the counter,
     // fetched one run ahead.  One task per run while there are few (a lone pre-flop spot must spread over every CU); four once there are
     // eight per wavefront -- 65 536 one-task spots would otherwise queue 65 536 atomics on ONE address.
@@ -192,7 +192,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
         // the pool: card j (canonical order) of the cards not dead, as its bit in the suit-lane layout
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         if (lane < 52u && ((avail >> lane) & 1ull))
-            mypool[__popcll(avail & ((1ull << lane) - 1ull))] = 4ull << (((lane & 3u) << 4) | (lane >> 2));
+            mypool[PK_IDX(__popcll(avail & ((1ull << lane) - 1ull)), 64, "mypool")] = 4ull << (((lane & 3u) << 4) | (lane >> 2));
         if (lane == EQ_FROZEN) mypool[EQ_FROZEN] = 0;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -218,11 +218,11 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
             if (f <= 3) c3 = level(std::integral_constant<int, 1>{});
             if (f <= 4) j = x + r;
         }
-        uint64_t base = known | mypool[c0] | mypool[c1] | mypool[c2] | mypool[c3];
+        uint64_t base = known | mypool[PK_IDX(c0, 64, "mypool")] | mypool[PK_IDX(c1, 64, "mypool")] | mypool[PK_IDX(c2, 64, "mypool")] | mypool[PK_IDX(c3, 64, "mypool")];
         uint32_t sole[N], inw[N], sh[N];
         PK_FOR(p, N) sole[p] = 0; inw[p] = 0; sh[p] = 0; PK_END
         for (uint32_t n = 0; n < cnt; ++n) {
-            const uint64_t bits = base | mypool[j & 63u];
+            const uint64_t bits = base | mypool[PK_IDX(j, 64, "mypool") & 63u];
             uint32_t v[N];
             PK_FOR(p, N)
                 v[p] = NONE_V;                                                        // eval_hand([]) of a seat that does not show down
@@ -230,7 +230,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
             PK_END
             int nw;
             const uint32_t win = compare_rankings<N>(v, nw);
-            const uint32_t w = wt[nw];
+            const uint32_t w = wt[PK_IDX(nw, 32, "wt")];
             PK_FOR(p, N)
                 if ((live >> p) & 1u) {
                     const bool in = (win >> p) & 1u;
@@ -248,7 +248,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
                 else if ((int)c0 < lim0) { ++c0; c1 = c0 + 1; c2 = c1 + 1; c3 = c2 + 1; }
                 else { c3 = EQ_FROZEN - 1; }                                          // (past the spot's last board: never evaluated)
                 j = c3 + 1;
-                base = known | mypool[c0 & 63u] | mypool[c1 & 63u] | mypool[c2 & 63u] | mypool[c3 & 63u];
+                base = known | mypool[PK_IDX(c0, 64, "mypool") & 63u] | mypool[PK_IDX(c1, 64, "mypool") & 63u] | mypool[PK_IDX(c2, 64, "mypool") & 63u] | mypool[PK_IDX(c3, 64, "mypool") & 63u];
             }
         }
         // per seat: the wavefront's sums, then one atomic per output from lane 0

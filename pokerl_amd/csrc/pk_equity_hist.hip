@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
     __shared__ uint64_t pool[64];                     // card j of the pool (canonical order) as its bit in the suit-lane layout
     __shared__ uint32_t canon[64];                    // ... and its canonical index
     __shared__ uint32_t wsum[RVR_WAVES];
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += RVR_BLOCK) reinterpret_cast<uint4 *>(T)[i] = reinterpret_cast<const uint4 *>(tab)[i];
+    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += RVR_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = hist_uniform(tid >> 6);
     const uint32_t row_words = (uint32_t)RVR_HOLDINGS * nbins;                // u16 entries of one spot's rows: at most 42 432
     for (uint32_t spot = blockIdx.x; spot < m; spot += gridDim.x) {
@@ -80,8 +80,8 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
         if (boards) {                                 // (a refused spot: zeros)
             if (tid < 52u && ((avail >> tid) & 1ull)) {
                 const uint32_t s = (uint32_t)__popcll(avail & ((1ull << tid) - 1ull));
-                pool[s] = 4ull << (((tid & 3u) << 4) | (tid >> 2));
-                canon[s] = tid;
+                pool[PK_IDX(s, 64, "pool")] = 4ull << (((tid & 3u) << 4) | (tid >> 2));
+                canon[PK_IDX(s, 64, "canon")] = tid;
             }
             if (tid == HIST_NONE) { pool[HIST_NONE] = 0; canon[HIST_NONE] = 0; }
             __syncthreads();                          // (... and the zeros above are in place before any lane counts in its rows)
@@ -164,12 +164,12 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
                     const uint32_t y = __shfl_up(inc, off);
                     inc += lane >= (uint32_t)off ? y : 0u;
                 }
-                if (lane == 63u) wsum[wave] = inc;
+                if (lane == 63u) wsum[PK_IDX(wave, RVR_WAVES, "wsum")] = inc;
                 __syncthreads();
                 uint32_t run = inc - mine, live = 0;  // live: the weight of every holding in play on this completion
 #pragma unroll
                 for (int w = 0; w < RVR_WAVES; ++w) {
-                    const uint32_t s = wsum[w];
+                    const uint32_t s = wsum[PK_IDX(w, RVR_WAVES, "wsum")];
                     run += (uint32_t)w < wave ? s : 0u;
                     live += s;
                 }
@@ -203,7 +203,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
                         if (x == ha[j] || x == hb[j]) continue;
                         const uint32_t tx = hist_tri(x);
                         const uint32_t p0 = PK_IDX(hist_pair(ha[j], ta, x, tx), RVR_POOL_HOLDINGS, "pair"), p1 = PK_IDX(hist_pair(hb[j], tb, x, tx), RVR_POOL_HOLDINGS, "pair");
-                        const uint32_t k0 = keyw[p0], k1 = keyw[p1], w0 = wp[p0], w1 = wp[p1];
+                        const uint32_t k0 = keyw[p0], k1 = keyw[p1], w0 = wp[p0], w1 = wp[p1];   // (p0, p1: checked above)
                         below -= (k0 < kh ? w0 : 0u) + (k1 < kh ? w1 : 0u);
                         equal -= (k0 == kh ? w0 : 0u) + (k1 == kh ? w1 : 0u);
                         den -= (k0 != HIST_SENT ? w0 : 0u) + (k1 != HIST_SENT ? w1 : 0u);

@@ -128,8 +128,8 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
     __shared__ uint32_t hero_w[EQR_COMPLETIONS];  // the hero's ranking word per completion of the board
     __shared__ uint32_t cwin[EQR_HOLDINGS], ctie[EQR_HOLDINGS];
     __shared__ uint64_t red[EQR_WAVES][3];
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQR_BLOCK) reinterpret_cast<uint4 *>(T)[i] = reinterpret_cast<const uint4 *>(tab)[i];
-    for (int h = threadIdx.x; h < EQR_HOLDINGS; h += EQR_BLOCK) { cwin[h] = 0; ctie[h] = 0; }
+    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQR_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
+    for (int h = threadIdx.x; h < EQR_HOLDINGS; h += EQR_BLOCK) { cwin[PK_IDX(h, EQR_HOLDINGS, "cwin")] = 0; ctie[PK_IDX(h, EQR_HOLDINGS, "ctie")] = 0; }
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = eqr_uniform(tid >> 6);
     for (uint32_t spot = blockIdx.x; spot < m; spot += gridDim.x) {
         __syncthreads();                          // (the table and the cleared counters; the spot before: its pool, hero words and sums are done with)
@@ -139,8 +139,8 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
         if (boards) {                             // (a refused spot: its counters stay zero)
             if (tid < 52u && ((avail >> tid) & 1ull)) {
                 const uint32_t slot = (uint32_t)__popcll(avail & ((1ull << tid) - 1ull));
-                pool[slot] = 4ull << (((tid & 3u) << 4) | (tid >> 2));
-                canon[slot] = tid;
+                pool[PK_IDX(slot, 64, "pool")] = 4ull << (((tid & 3u) << 4) | (tid >> 2));
+                canon[PK_IDX(slot, 64, "canon")] = tid;
             }
             if (tid == EQR_FROZEN) { pool[EQR_FROZEN] = 0; canon[EQR_FROZEN] = 0; }
             __syncthreads();
@@ -148,9 +148,9 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
             const uint32_t ncomp = eqr_binom2(P, k);
             for (uint32_t c = tid; c < ncomp; c += EQR_BLOCK) {
                 uint64_t bits = known | hero;
-                if (k == 2u) { uint32_t ci, cj; eqr_unpair(c, ci, cj); bits |= pool[ci & 63u] | pool[cj & 63u]; }
-                else if (k == 1u) bits |= pool[c & 63u];
-                hero_w[c] = eval7_tab_back(eval7_tab_front_bits(bits, T), T);
+                if (k == 2u) { uint32_t ci, cj; eqr_unpair(c, ci, cj); bits |= pool[PK_IDX(ci, 64, "pool") & 63u] | pool[PK_IDX(cj, 64, "pool") & 63u]; }
+                else if (k == 1u) bits |= pool[PK_IDX(c, 64, "pool") & 63u];
+                hero_w[PK_IDX(c, EQR_COMPLETIONS, "hero_w")] = eval7_tab_back(eval7_tab_front_bits(bits, T), T);
             }
             __syncthreads();
             // ---- villain pass: the sets S of s = k + 2 pool cards, lexicographic; this lane's [s0, s0 + cnt)
@@ -179,11 +179,11 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
                 c2 = level(std::integral_constant<int, 1>{});
                 j = x + r;
             }
-            uint64_t base = known | pool[c0 & 63u] | pool[c1 & 63u] | pool[c2 & 63u];
-            uint32_t n0 = canon[c0 & 63u], n1 = canon[c1 & 63u], n2 = canon[c2 & 63u];
+            uint64_t base = known | pool[PK_IDX(c0, 64, "pool") & 63u] | pool[PK_IDX(c1, 64, "pool") & 63u] | pool[PK_IDX(c2, 64, "pool") & 63u];
+            uint32_t n0 = canon[PK_IDX(c0, 64, "canon") & 63u], n1 = canon[PK_IDX(c1, 64, "canon") & 63u], n2 = canon[PK_IDX(c2, 64, "canon") & 63u];
             for (uint32_t n = 0; n < cnt; ++n) {
-                const uint32_t nj = canon[j & 63u];
-                const uint32_t vil = eval7_tab_back(eval7_tab_front_bits(base | pool[j & 63u], T), T);
+                const uint32_t nj = canon[PK_IDX(j, 64, "canon") & 63u];
+                const uint32_t vil = eval7_tab_back(eval7_tab_front_bits(base | pool[PK_IDX(j, 64, "pool") & 63u], T), T);
                 // one split: levels x < y are the villain's hole cards (canonical nx < ny), levels u < v the board to come
                 auto split = [&](int x, uint32_t nx, uint32_t ny, uint32_t lu, uint32_t lv) {
                     if (x < f) return;                                                   // (uniform: a level that does not exist)
@@ -209,8 +209,8 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
                     else if ((int)c0 < lim0) { ++c0; c1 = c0 + 1; c2 = c1 + 1; }
                     else { c2 = EQR_FROZEN - 1; }                                        // (past the spot's last set: never evaluated)
                     j = c2 + 1;
-                    base = known | pool[c0 & 63u] | pool[c1 & 63u] | pool[c2 & 63u];
-                    n0 = canon[c0 & 63u]; n1 = canon[c1 & 63u]; n2 = canon[c2 & 63u];
+                    base = known | pool[PK_IDX(c0, 64, "pool") & 63u] | pool[PK_IDX(c1, 64, "pool") & 63u] | pool[PK_IDX(c2, 64, "pool") & 63u];
+                    n0 = canon[PK_IDX(c0, 64, "canon") & 63u]; n1 = canon[PK_IDX(c1, 64, "canon") & 63u]; n2 = canon[PK_IDX(c2, 64, "canon") & 63u];
                 }
             }
             __syncthreads();
@@ -219,7 +219,7 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
         const uint16_t *wv = wts.w ? wts.w + (wts.per_spot ? (size_t)spot * EQR_HOLDINGS : 0) : nullptr;
         uint64_t a0 = 0, a1 = 0, a2 = 0;
         for (uint32_t h = tid; h < (uint32_t)EQR_HOLDINGS; h += EQR_BLOCK) {
-            const uint32_t w = cwin[h], t = ctie[h];
+            const uint32_t w = cwin[PK_IDX(h, EQR_HOLDINGS, "cwin")], t = ctie[PK_IDX(h, EQR_HOLDINGS, "ctie")];
             cwin[h] = 0; ctie[h] = 0;
             if (out.win) out.win[(size_t)spot * EQR_HOLDINGS + h] = w;
             if (out.tie) out.tie[(size_t)spot * EQR_HOLDINGS + h] = t;
@@ -233,11 +233,11 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
         }
         if (out.agg) {
             a0 = eqr_wave_sum(a0); a1 = eqr_wave_sum(a1); a2 = eqr_wave_sum(a2);
-            if (lane == 0) { red[wave][0] = a0; red[wave][1] = a1; red[wave][2] = a2; }
+            if (lane == 0) { red[PK_IDX(wave, EQR_WAVES, "red")][0] = a0; red[wave][1] = a1; red[wave][2] = a2; }
             __syncthreads();
             if (tid == 0) {
                 uint64_t r0 = 0, r1 = 0, r2 = 0;
-                for (int wv_ = 0; wv_ < EQR_WAVES; ++wv_) { r0 += red[wv_][0]; r1 += red[wv_][1]; r2 += red[wv_][2]; }
+                for (int wv_ = 0; wv_ < EQR_WAVES; ++wv_) { r0 += red[PK_IDX(wv_, EQR_WAVES, "red")][0]; r1 += red[wv_][1]; r2 += red[wv_][2]; }
                 out.agg[(size_t)spot * 3] = r0;
                 out.agg[(size_t)spot * 3 + 1] = r1;
                 out.agg[(size_t)spot * 3 + 2] = (uint64_t)boards * r2;

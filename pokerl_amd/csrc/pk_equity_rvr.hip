@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
     __shared__ uint64_t pool[64];                     // card j of the pool (canonical order) as its bit in the suit-lane layout
     __shared__ uint32_t canon[64];                    // ... and its canonical index
     __shared__ uint32_t wsum[RVR_WAVES];
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += RVR_BLOCK) reinterpret_cast<uint4 *>(T)[i] = reinterpret_cast<const uint4 *>(tab)[i];
+    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += RVR_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = rvr_uniform(tid >> 6);
     for (uint32_t spot = blockIdx.x; spot < m; spot += gridDim.x) {
         __syncthreads();                              // (the table; the spot before: its pool, weights, keys and sums are done with)
@@ -127,8 +127,8 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
         if (boards) {                                 // (a refused spot: zeros)
             if (tid < 52u && ((avail >> tid) & 1ull)) {
                 const uint32_t s = (uint32_t)__popcll(avail & ((1ull << tid) - 1ull));
-                pool[s] = 4ull << (((tid & 3u) << 4) | (tid >> 2));
-                canon[s] = tid;
+                pool[PK_IDX(s, 64, "pool")] = 4ull << (((tid & 3u) << 4) | (tid >> 2));
+                canon[PK_IDX(s, 64, "canon")] = tid;
             }
             if (tid == RVR_NONE) { pool[RVR_NONE] = 0; canon[RVR_NONE] = 0; }
             __syncthreads();
@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
             for (uint32_t i = nh + tid; i < npad; i += RVR_BLOCK) slot[PK_IDX(i, RVR_SLOTS, "slot")] = ~0ull;   // (stay all ones: every sorted position >= nreal is)
 #pragma unroll
             for (int off = 32; off >= 1; off >>= 1) wmine += __shfl_xor(wmine, off);
-            if (lane == 0) wsum[wave] = wmine;
+            if (lane == 0) wsum[PK_IDX(wave, RVR_WAVES, "wsum")] = wmine;
             // ... the holdings this lane OWNS (h = tid + 512 j of the fixed index space) as pool slots ha < hb; hph: their pool holding
             uint32_t ha[RVR_PER_LANE], hb[RVR_PER_LANE], hph[RVR_PER_LANE];
             bool hvalid[RVR_PER_LANE];
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
             __syncthreads();
             uint32_t wall = 0;
 #pragma unroll
-            for (int w = 0; w < RVR_WAVES; ++w) wall += wsum[w];
+            for (int w = 0; w < RVR_WAVES; ++w) wall += wsum[PK_IDX(w, RVR_WAVES, "wsum")];
             // tot[h] = boards * (the weight of the valid holdings that share no card with h)
 #pragma unroll
             for (int j = 0; j < RVR_PER_LANE; ++j) {
@@ -233,11 +233,11 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
                     const uint32_t y = __shfl_up(inc, off);
                     inc += lane >= (uint32_t)off ? y : 0u;
                 }
-                if (lane == 63u) wsum[wave] = inc;
+                if (lane == 63u) wsum[PK_IDX(wave, RVR_WAVES, "wsum")] = inc;
                 __syncthreads();
                 uint32_t run = inc - mine;
 #pragma unroll
-                for (int w = 0; w < RVR_WAVES; ++w) run += (uint32_t)w < wave ? wsum[w] : 0u;
+                for (int w = 0; w < RVR_WAVES; ++w) run += (uint32_t)w < wave ? wsum[PK_IDX(w, RVR_WAVES, "wsum")] : 0u;
 #pragma unroll
                 for (int j = 0; j < RVR_PER_LANE; ++j) {
                     pre[PK_IDX(tid * RVR_PER_LANE + (uint32_t)j, RVR_PREFIX, "pre")] = run;
@@ -266,7 +266,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
                         if (x == ha[j] || x == hb[j]) continue;
                         const uint32_t tx = rvr_tri(x);
                         const uint32_t p0 = PK_IDX(rvr_pair(ha[j], ta, x, tx), RVR_POOL_HOLDINGS, "pair"), p1 = PK_IDX(rvr_pair(hb[j], tb, x, tx), RVR_POOL_HOLDINGS, "pair");
-                        const uint32_t k0 = keyw[p0], k1 = keyw[p1], w0 = wp[p0], w1 = wp[p1];
+                        const uint32_t k0 = keyw[p0], k1 = keyw[p1], w0 = wp[p0], w1 = wp[p1];   // (p0, p1: checked above)
                         below -= (k0 < kh ? w0 : 0u) + (k1 < kh ? w1 : 0u);
                         equal -= (k0 == kh ? w0 : 0u) + (k1 == kh ? w1 : 0u);
                     }

@@ -143,8 +143,8 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqs_min_waves<N>()) k_eqs(const uint
                                                                      EqsStream rng, uint32_t ntasks, uint32_t nch, uint32_t per) {
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     __shared__ uint32_t wt[32];
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQ_BLOCK) reinterpret_cast<uint4 *>(T)[i] = reinterpret_cast<const uint4 *>(tab)[i];
-    if (threadIdx.x < 32) wt[threadIdx.x] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
+    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQ_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
+    if (threadIdx.x < 32) wt[PK_IDX(threadIdx.x, 32, "wt")] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, wave = eqs_uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
     const uint32_t S = rng.samples;
@@ -211,7 +211,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqs_min_waves<N>()) k_eqs(const uint
             PK_END
             int nw;
             const uint32_t win = compare_rankings<N>(v, nw);
-            const uint32_t wsh = wt[nw];
+            const uint32_t wsh = wt[PK_IDX(nw, 32, "wt")];
             PK_FOR(p, N)
                 if ((live >> p) & 1u) {
                     const bool in = (win >> p) & 1u;

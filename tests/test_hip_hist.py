@@ -98,7 +98,10 @@ def test_every_fixture_spot_equals_the_reference(PK):
 
 # The shapes at which each mechanism can break: the full river and turn pools; on the flop P = 6 (the minimum: one villain per hero and
 # completion), 7, 11 and 12 (C(P, 2) = 55 and 66: either side of the 64-slot sort pad), 16.
-SHAPES = {"river": (5, (47,)), "turn": (4, (48, 48)), "flop": (3, (6, 7, 11, 12, 16))}
+# river-bounds / turn-bounds: the pools on either side of each size of the sort, npad = 64 | 128 | 256 | 512 | 1 024 | 2 048 by nh = C(P, 2)
+# (32 | 33 and 45 | 46 also give a lane its second and third holding); the turn's 45 | 46 in a case of their own (P completions each in the spec).
+SHAPES = {"river": (5, (47,)), "turn": (4, (48, 48)), "flop": (3, (6, 7, 11, 12, 16)),
+          "river-bounds": (5, (11, 12, 16, 17, 23, 24, 32, 33, 45, 46)), "turn-bounds": (4, (11, 12, 16, 17, 23, 24, 32, 33)), "turn-top": (4, (45, 46))}
 RANGES = ("random", "top", "null", "zero")
 _spec = {}
 
@@ -116,7 +119,7 @@ def spec_of(name):
     return _spec[name]
 
 
-@pytest.mark.parametrize("name", ["river", "flop", "turn"])
+@pytest.mark.parametrize("name", ["river", "flop", "turn", "river-bounds", "turn-bounds", "turn-top"])
 def test_random_spots_equal_the_spec(PK, name):
     board, nboard, dead, shared, spec = spec_of(name)
     nb, pools = SHAPES[name]

@@ -89,15 +89,17 @@ def test_every_fixture_spot_equals_the_reference(PK):
 
 # Pools by the number n = C(P - k, 2) of holdings one completion leaves in play: the smallest pools (n = 6, 10) and the pools around the
 # sort's edges -- n = 496, 528, 561 about 512 and 990, 1 035, 1 081 about 1 024 -- where the padded sort size and the number of holdings and
-# sorted positions a lane serves change.
-REST = {5: (4, 5, 32, 33, 34, 45, 46, 47), 4: (4, 5, 32, 33), 3: (4, 5, 11, 12)}
+# sorted positions a lane serves change.  The sort itself is padded by the POOL's holdings nh = C(P, 2): P = 11 | 12, 16 | 17, 23 | 24, 32 | 33,
+# 45 | 46 lie across npad = 64 | 128 | 256 | 512 | 1 024 | 2 048 -- on the river (rest = P) every pair, on the turn (rest = P - 1) the pairs up to
+# 32 | 33 twice each, and 45 | 46 once each in a case of their own ("4-top": 45 completions of 900 000 pairwise decisions each in the spec).
+REST = {5: (4, 5, 11, 12, 16, 17, 23, 24, 32, 33, 34, 45, 46, 47), 4: (4, 5, 10, 11, 15, 16, 22, 23, 31, 32, 33), 3: (4, 5, 11, 12)}
 
 
-@pytest.mark.parametrize("nb", [5, 4, 3])
-def test_random_spots_equal_the_spec(PK, nb):
+@pytest.mark.parametrize("nb,rests,each", [(5, REST[5], 2), (4, REST[4], 2), (3, REST[3], 2), (4, (44, 45), 1)], ids=["5", "4", "3", "4-top"])
+def test_random_spots_equal_the_spec(PK, nb, rests, each):
     rng = np.random.default_rng(3000 + nb)
     k = 5 - nb
-    pools = [rest + k for rest in REST[nb] for _ in range(2)]
+    pools = [rest + k for rest in rests for _ in range(each)]
     m = len(pools)
     board, nboard, dead = VS.random_boards(rng, m, nb, lambda i: pools[i])
     shared = random_weights(rng)
@@ -111,8 +113,9 @@ def test_random_spots_equal_the_spec(PK, nb):
     none = device_rvr(board, nboard, dead)
     assert_equal(none, want(2), "random nb=%d, NULL weights" % nb)
     assert_equal(device_rvr(board, nboard, dead, np.ones(H, np.uint16)), none, "NULL weights are all ones")
-    assert none["valid"][:2].sum(axis=1).tolist() == [math.comb(k + 4, 2)] * 2 and none["boards"][:2].tolist() == [1, 1]   # the smallest pool
-    assert (none["tot"][:2][none["valid"][:2]] == math.comb(k + 2, 2)).all()
+    if rests[0] == 4:
+        assert none["valid"][:2].sum(axis=1).tolist() == [math.comb(k + 4, 2)] * 2 and none["boards"][:2].tolist() == [1, 1]   # the smallest pool
+        assert (none["tot"][:2][none["valid"][:2]] == math.comb(k + 2, 2)).all()
     if nb == 5:                                                   # the largest value there is on a river: 65 535 * 990 per holding
         assert (top["tot"][-1][top["valid"][-1]] == 65535 * 990).all()
 

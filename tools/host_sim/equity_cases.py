@@ -1,0 +1,533 @@
+#!/usr/bin/env python3
+"""Dev-only: the cases of tools/host_sim/equity_sim.cpp -- the equity kernels run on the CPU as 8-wave workgroups (wg_shim.h) -- and their
+expected values.  This module writes a case file, runs the driver on it, reads every output array back and compares it, by exact integer
+equality, with the numpy specs of tests/ (equity_spec, equity_sampled_spec, equity_range_spec, rvr_spec, hist_spec: themselves pinned to the
+reference's fixtures by the host tests).  Nothing expected comes from a kernel.  tests/test_equity_sim_host.py runs the cases marked quick on a
+plain build; tools/host_sim/sanitize_equity.sh runs all of them on the ASan + UBSan and the TSan build.
+
+The shapes are the smallest at which each mechanism of the kernels can break (docs/history.md lists them with their reasons):
+  k_rvr / k_hist   nh = C(P, 2) pool holdings: P = 11|12, 16|17, 23|24, 32|33, 45|46 lie across each size of the sort (npad 64 .. 2048; 32|33 and
+                   45|46 also give a lane its second and third holding), 47 is the full river pool, k + 4 the smallest; river and turn spots
+                   (1 and P completions), flop spots at P = 6, 7 (the pair-order walk); every weight form, a dead range, a range dead on some
+                   completions; bins 1, 7, 32; each output NULL in turn; a grid of 1 with spots of falling size (stale LDS); a refused spot
+                   between good ones;
+  k_eqr            nb = 3, 4, 5; the smallest pool; sets below 512 and no multiple of 512; a grid of 1 (the counters cleared for the next spot);
+                   agg NULL and not; every weight form; a refused spot in between;
+  k_equity<N>      N = 2, 3, 9, 16; nb = 0 .. 5; folded seats, a lone live seat; grids of 1 and 2 with more tasks than waves; 64+ one-task
+                   spots on a grid of 1 (take = 4); refused spots inside the batch;
+  k_eqs<N>         N = 2, 6, 16; hidden hole cards up to 37 draws (three Philox blocks); samples 1, 63, 64, 65 and several tasks per spot; two nonces;
+  preparation      every status bit, the explicit and the table form; table indices -1, T and 2^31 - 1 (nothing is read: ASan's to check).
+
+  equity_cases.py --exe <equity_sim> [--exe <another build>] [--quick] [--only <substring>] [--list] [--keep <dir>]
+"""
+import argparse
+import math
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import equity_range_spec as RS          # noqa: E402
+import equity_sampled_spec as SS        # noqa: E402
+import equity_spec as ES                # noqa: E402
+import hist_spec as HS                  # noqa: E402
+import rvr_spec as VS                   # noqa: E402
+from oracle import rng_spec as R        # noqa: E402
+
+HOLDINGS = 1326
+IN_FLIGHT, BAD_TABLE = 16, 32
+DTYPES = {"u8": np.uint8, "u16": np.uint16, "u32": np.uint32, "u64": np.uint64, "i32": np.int32}
+OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("win", "tie", "share", "samples", "status"),
+           "range": ("agg", "win", "tie", "boards", "status"), "rvr": ("win", "tie", "tot", "boards", "status"),
+           "hist": ("hist", "void", "completions", "status")}
+
+
+class Case:
+    """name, family, the driver's input arrays {name: (dtype, values)}, the outputs wanted, expect() -> {output: array}, quick."""
+
+    def __init__(self, name, family, arrays, expect, outputs=None, quick=False):
+        self.name, self.family, self.arrays, self.expect, self.quick = name, family, arrays, expect, quick
+        self.outputs = tuple(OUTPUTS[family] if outputs is None else outputs)
+        self._want = None
+
+    def expected(self):
+        if self._want is None:                                        # (once, however many builds run the case)
+            self._want = self.expect()
+        return self._want
+
+    def write(self, path):
+        with open(path, "w") as f:
+            f.write("family %s\noutputs %s\n" % (self.family, " ".join(self.outputs)))
+            for key, (dt, val) in self.arrays.items():
+                if val is None:
+                    continue
+                v = np.asarray(val).astype(DTYPES[dt]).reshape(-1)
+                f.write("%s %s %d\n%s\n" % (key, dt, v.size, " ".join(str(int(x)) for x in v.tolist())))
+
+
+def read_outputs(path):
+    out = {}
+    with open(path) as f:
+        while True:
+            head = f.readline().split()
+            if not head:
+                return out
+            vals = f.readline().split()
+            assert len(vals) == int(head[2]), (head, len(vals))
+            out[head[0]] = np.array([int(x) for x in vals], dtype=np.uint64).astype(DTYPES[head[1]])
+
+
+def run_case(exe, case, workdir, timeout=1800):
+    """Runs the driver on one case -> (list of mismatch strings, seconds of the driver, its stdout + stderr)."""
+    cpath, opath = os.path.join(workdir, case.name + ".case"), os.path.join(workdir, case.name + ".out")
+    case.write(cpath)
+    if os.path.exists(opath):
+        os.remove(opath)
+    t0 = time.time()
+    r = subprocess.run([exe, cpath, opath], capture_output=True, text=True, timeout=timeout)
+    sec = time.time() - t0
+    log = r.stdout + r.stderr
+    if r.returncode != 0:
+        return ["the driver exited with status %d" % r.returncode], sec, log
+    got, want, bad = read_outputs(opath), case.expected(), []
+    if sorted(got) != sorted(case.outputs):
+        bad.append("outputs written: %s, wanted: %s" % (sorted(got), sorted(case.outputs)))
+    for key in case.outputs:
+        if key not in got:
+            continue
+        w = np.asarray(want[key]).reshape(-1)
+        g = got[key]
+        if g.size != w.size:
+            bad.append("%s: %d entries, the spec has %d" % (key, g.size, w.size))
+            continue
+        ne = np.nonzero(g.astype(np.uint64) != w.astype(np.uint64))[0]
+        if ne.size:
+            i = int(ne[0])
+            bad.append("%s: %d of %d entries differ, the first at %d: kernel %d, spec %d" % (key, ne.size, g.size, i, int(g[i]), int(w[i])))
+    return bad, sec, log
+
+
+# ---------------------------------------------------------------------------------------------------------------- spots
+def card(c):
+    return ES.CANON[c]
+
+
+def dead_mask(cards):
+    m = 0
+    for c in cards:
+        m |= 1 << int(c)
+    return m
+
+
+def board_spots(seed, shapes):
+    """[(nb, P)] -> board [m, 5], nboard [m], dead [m]: random valid spots whose pool has P cards."""
+    rng = np.random.default_rng(seed)
+    bs, ns, ds = [], [], []
+    for nb, pool in shapes:
+        b, n, d = VS.random_boards(rng, 1, nb, pool=pool)
+        bs.append(b[0]); ns.append(n[0]); ds.append(d[0])
+    return np.array(bs, np.uint8), np.array(ns, np.uint8), np.array(ds, np.uint64)
+
+
+def hero_spots(seed, shapes):
+    rng = np.random.default_rng(seed)
+    hs, bs, ns, ds = [], [], [], []
+    for nb, pool in shapes:
+        h, b, n, d = RS.random_spots(rng, 1, nb, pool=pool)
+        hs.append(h[0]); bs.append(b[0]); ns.append(n[0]); ds.append(d[0])
+    return np.array(hs, np.uint8), np.array(bs, np.uint8), np.array(ns, np.uint8), np.array(ds, np.uint64)
+
+
+def weights_for(seed, m, form):
+    """form: None, 'shared' [1326], 'spot' [m, 1326], 'zero' (shared, all zero); a third of the entries zero, the largest 65 535."""
+    if form is None:
+        return None, 0
+    if form == "zero":
+        return np.zeros(HOLDINGS, np.uint16), 0
+    rng = np.random.default_rng(seed)
+    shape = (m, HOLDINGS) if form == "spot" else (HOLDINGS,)
+    w = rng.integers(0, 200, shape).astype(np.uint16)
+    w[rng.random(shape) < 0.33] = 0
+    w.reshape(-1)[::97] = 65535
+    return w, 1 if form == "spot" else 0
+
+
+def pack_tables(deck, turn, active, states, inflight):
+    """A handle's arrays by hand: deck uint8 [T, 5 + 2N], turn / active [T], states [T, N] (PlayerState: 0 folded 1 active 2 called 3 all in),
+    inflight [T] (the step-in-flight bits of the cursor) -> cards [W][T] words, cursors [T], seat_states [T]."""
+    deck = np.asarray(deck, np.uint8)
+    t, k = deck.shape
+    w = (k + 3) // 4
+    padded = np.full((t, 4 * w), 0xFF, np.uint32)
+    padded[:, :k] = deck
+    words = (padded[:, 0::4] | (padded[:, 1::4] << 8) | (padded[:, 2::4] << 16) | (padded[:, 3::4] << 24)).astype(np.uint32)   # [T, W]
+    n = states.shape[1]
+    cursors = np.array([int(active[i]) | (0 << 4) | (((0 + 1) % n) << 8) | (((0 + 2) % n) << 12) | (int(turn[i]) << 16) | (int(inflight[i]) << 20) for i in range(t)], np.uint32)
+    ss = np.zeros(t, np.uint64)
+    for i in range(t):
+        v = 0
+        for p in range(n):
+            if states[i, p] in (1, 2, 3):
+                v |= 1 << (16 * (int(states[i, p]) - 1) + p)
+        ss[i] = v
+    return words.T.copy(), cursors, ss
+
+
+def table_world(seed, n, t, turns=(1, 2, 3, 0)):
+    """t hand-built tables of n seats: the betting rounds `turns` in turn, one step in flight (table 2), folded seats, -> dict."""
+    rng = np.random.default_rng(seed)
+    deck = np.array([[card(c) for c in rng.permutation(52)[:5 + 2 * n]] for _ in range(t)], np.uint8)
+    turn = np.array([turns[i % len(turns)] for i in range(t)])        # (1 2 3 0: flop, turn, river, pre-flop)
+    active = np.array([i % n for i in range(t)])
+    states = np.ones((t, n), np.int64)
+    for i in range(t):
+        states[i, (i + 1) % n] = (0, 2, 3)[i % 3]                     # a folded, a called, an all-in seat
+    inflight = np.zeros(t, np.int64)
+    inflight[2 % t] = 0x13
+    cards, cursors, ss = pack_tables(deck, turn, active, states, inflight)
+    # the spots: every table once, and the three indices no table has
+    tables = np.array(list(range(t)) + [-1, t, 2 ** 31 - 1, 0], np.int32)
+    return dict(deck=deck, turn=turn, active=active, states=states, inflight=inflight, cards=cards, cursors=cursors, ss=ss, tables=tables, T=t, N=n)
+
+
+def table_arrays(w):
+    return {"T": ("u32", [w["T"]]), "N": ("u32", [w["N"]]), "cards": ("u32", w["cards"]), "cursors": ("u32", w["cursors"]),
+            "seat_states": ("u64", w["ss"]), "tables": ("i32", w["tables"])}
+
+
+def table_expect(w, per_table, zero_keys, count_key):
+    """The table form's expected outputs from per_table (the spec's batch result over ALL T tables, as explicit spots): spot i is table
+    tables[i]; a bad index is BAD_TABLE alone and zeros; a step in flight adds IN_FLIGHT and zeroes the spot's results."""
+    tabs = w["tables"]
+    out = {}
+    for key, arr in per_table.items():
+        out[key] = np.zeros((len(tabs),) + arr.shape[1:], arr.dtype)
+    for i, t in enumerate(tabs.tolist()):
+        if t < 0 or t >= w["T"]:
+            out["status"][i] = BAD_TABLE
+            continue
+        for key in per_table:
+            out[key][i] = per_table[key][t]
+        if w["inflight"][t]:
+            out["status"][i] |= IN_FLIGHT
+            for key in zero_keys + (count_key,):
+                out[key][i] = 0
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- rvr / hist
+def rvr_like(name, family, shapes, seed, grid, wform=None, bins=None, outputs=None, quick=False, edit=None, wedit=None):
+    board, nboard, dead = board_spots(seed, shapes)
+    if edit:
+        edit(board, nboard, dead)
+    m = len(shapes)
+    w, per_spot = weights_for(seed + 1, m, wform)
+    if wedit:
+        w = wedit(w, board, nboard, dead)
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [grid]), "board": ("u8", board), "nboard": ("u8", nboard), "dead": ("u64", dead),
+              "weights": ("u16", w), "per_spot": ("u32", [per_spot])}
+    if family == "hist":
+        arrays["bins"] = ("u32", [bins])
+
+    def expect():
+        if family == "rvr":
+            return VS.batch_rvr(board, nboard, dead, w)
+        r = HS.batch_hist(board, nboard, dead, w, bins)
+        return dict(r, void=r["void"])
+    return Case(name, family, arrays, expect, outputs, quick)
+
+
+def range_dead_on_some(w, board, nboard, dead):
+    """Shared weights that live on ONE holding only: every completion that holds one of its cards leaves the range dead (hist: void)."""
+    gone = VS.check_spot([int(x) for x in board[0]], int(nboard[0]), int(dead[0]))[1]
+    pool = [c for c in range(52) if c not in gone]
+    a, b = pool[1], pool[3]
+    w = np.zeros(HOLDINGS, np.uint16)
+    w[b * (b - 1) // 2 + a] = 7
+    return w
+
+
+def break_middle(board, nboard, dead):
+    board[1, 1] = board[1, 0]                                         # the spot in the middle: a card twice -> refused
+
+
+RIVER_DOWN = [(5, p) for p in (47, 46, 45, 33, 32, 24, 23, 17, 16, 12, 11, 4)]
+TURN_SMALL = [(4, p) for p in (24, 23, 17, 16, 12, 11, 5)]
+
+
+def rvr_hist_cases():
+    cs = []
+    for fam, bins in (("rvr", None), ("hist", 7)):
+        # every boundary of the sort on river spots, the largest first on ONE workgroup: each spot starts from the LDS the larger one left
+        cs.append(rvr_like(fam + "-river-bounds-grid1", fam, RIVER_DOWN, 11, 1, None, bins, quick=True))
+        cs.append(rvr_like(fam + "-river-bounds-shared-w", fam, RIVER_DOWN[::-1], 12, 3, "shared", bins))
+        # turn spots (P completions each) across npad 64|128, 128|256, 256|512 and the smallest pool, falling sizes on one workgroup
+        cs.append(rvr_like(fam + "-turn-small-grid1-spot-w", fam, TURN_SMALL, 13, 1, "spot", bins, quick=True))
+        cs.append(rvr_like(fam + "-turn-32-33", fam, [(4, 33), (4, 32)], 14, 1, "shared", bins))
+        cs.append(rvr_like(fam + "-turn-45-46-47", fam, [(4, 47), (4, 46), (4, 45)], 15, 3, "spot", bins))
+        # flop spots: the pair-order walk of ci / cj, 15 and 21 completions
+        cs.append(rvr_like(fam + "-flop-6-7", fam, [(3, 7), (3, 6)], 16, 1, "shared", bins, quick=True))
+        cs.append(rvr_like(fam + "-zero-weights", fam, [(4, 12), (5, 17)], 17, 2, "zero", bins))
+        cs.append(rvr_like(fam + "-range-dies", fam, [(4, 12)], 18, 1, "shared", bins, wedit=range_dead_on_some, quick=True))
+        cs.append(rvr_like(fam + "-refused-between", fam, [(5, 24), (4, 12), (5, 11)], 19, 1, None, bins, edit=break_middle, quick=True))
+        for o in OUTPUTS[fam]:
+            cs.append(rvr_like(fam + "-no-" + o, fam, [(5, 12), (4, 11)], 20, 1, "shared", bins, outputs=[x for x in OUTPUTS[fam] if x != o]))
+        cs.append(status_case(fam, bins))
+        cs.append(table_case(fam, bins))
+    cs.append(rvr_like("hist-bins1", "hist", [(5, 33), (4, 12), (3, 6)], 21, 1, "shared", 1, quick=True))
+    cs.append(rvr_like("hist-bins32", "hist", [(5, 33), (4, 12), (3, 6)], 22, 1, "spot", 32, quick=True))
+    return cs
+
+
+def status_case(fam, bins):
+    """Every status bit of k_rvr_prep's explicit form, with a good spot at each end (boards / status / completions AND the rows: zeros)."""
+    shapes = [(5, 12), (5, 12), (5, 12), (5, 12), (2, 20), (4, 12), (5, 12), (3, 12), (5, 11)]
+
+    def edit(board, nboard, dead):
+        board[1, 2] = 0x0D                                            # rank nibble 13: no card
+        board[2, 3] = board[2, 0]                                     # a card twice
+        nboard[3] = 6                                                 # no board size
+        # [4]: nb = 2, pre-flop
+        dead[5] = np.uint64(dead_mask([c for c in range(52) if card(c) not in [int(x) for x in board[5, :4]]][:44]))   # P = 4 < k + 4 = 5
+        dead[6] = np.uint64(int(dead[6]) | (1 << 52))                 # a bit no card has
+        dead[7] = np.uint64(int(dead[7]) | (1 << VS.canon_index(int(board[7, 0]))))   # a board card is also `dead`
+    return rvr_like(fam + "-status-bits", fam, shapes, 23, 2, None, bins, edit=edit, quick=True)
+
+
+def table_case(fam, bins):
+    w = table_world(24, 2, 5, turns=(3, 0, 3))                        # river and pre-flop tables (a full-pool flop is 1 176 completions)
+    arrays = dict(table_arrays(w), m=("u32", [len(w["tables"])]), grid=("u32", [2]))
+    if fam == "hist":
+        arrays["bins"] = ("u32", [bins])
+
+    def expect():
+        board, nboard = VS.table_boards(w["deck"], w["turn"])
+        if fam == "rvr":
+            r = VS.batch_rvr(board, nboard)
+            return table_expect(w, {k: r[k] for k in OUTPUTS["rvr"]}, ("win", "tie", "tot"), "boards")
+        r = HS.batch_hist(board, nboard, None, None, bins)
+        return table_expect(w, {k: r[k] for k in OUTPUTS["hist"]}, ("hist", "void"), "completions")
+    return Case(fam + "-table-form", fam, arrays, expect, quick=(fam == "rvr"))
+
+
+# ---------------------------------------------------------------------------------------------------------------- range
+def range_case(name, shapes, seed, grid, wform=None, outputs=None, quick=False, edit=None):
+    hero, board, nboard, dead = hero_spots(seed, shapes)
+    if edit:
+        edit(hero, board, nboard, dead)
+    m = len(shapes)
+    w, per_spot = weights_for(seed + 1, m, wform)
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [grid]), "hero": ("u8", hero), "board": ("u8", board), "nboard": ("u8", nboard),
+              "dead": ("u64", dead), "weights": ("u16", w), "per_spot": ("u32", [per_spot])}
+    return Case(name, "range", arrays, lambda: RS.batch_range(hero, board, nboard, dead, w), outputs, quick)
+
+
+def range_cases():
+    cs = []
+    # nb = 5, 4, 3 at the smallest pool (k + 2), k + 4, sets below 512 (C(12, 4) = 495) and no multiple of 512 (C(20, 3) = 1140, C(33, 2) = 528)
+    small = [(5, 33), (5, 6), (5, 4), (5, 2), (4, 20), (4, 7), (4, 5), (4, 3), (3, 20), (3, 12), (3, 8), (3, 6), (3, 4)]
+    cs.append(range_case("range-bounds-grid1", small, 31, 1, None, quick=True))
+    cs.append(range_case("range-bounds-shared-w", small[::-1], 32, 3, "shared"))
+    cs.append(range_case("range-full-pools", [(3, 47), (4, 46), (5, 45)], 33, 2, "spot"))
+    # one workgroup, three spots, the largest first: the counters cleared for the next spot; without agg, and with per-spot weights
+    cs.append(range_case("range-grid1-no-agg", [(4, 30), (3, 12), (5, 20)], 34, 1, "shared", outputs=("win", "tie", "boards", "status"), quick=True))
+    cs.append(range_case("range-grid1-spot-w", [(4, 30), (3, 12), (5, 20)], 35, 1, "spot", quick=True))
+    cs.append(range_case("range-agg-only", [(4, 12), (5, 20)], 36, 1, "shared", outputs=("agg",)))
+
+    def middle(hero, board, nboard, dead):
+        hero[1, 1] = board[1, 0]                                      # the hero holds a board card -> refused
+    cs.append(range_case("range-refused-between", [(4, 20), (4, 12), (5, 11)], 37, 1, "shared", edit=middle, quick=True))
+
+    def bits(hero, board, nboard, dead):
+        hero[1, 0] = 0x4A                                             # suit 4: no card
+        board[2, 2] = hero[2, 0]
+        nboard[3] = 7
+        # [4]: nb = 0, pre-flop
+        used = [VS.canon_index(int(x)) for x in list(hero[5]) + list(board[5, :3])]
+        dead[5] = np.uint64(dead_mask([c for c in range(52) if c not in used][:44]))      # P = 3 < k + 2 = 4
+        dead[6] = np.uint64(1 << 63)
+    cs.append(range_case("range-status-bits", [(5, 12), (5, 12), (5, 12), (5, 12), (0, 30), (3, 12), (5, 12), (4, 11)], 38, 2, None, edit=bits, quick=True))
+    for observer, who in ((1, lambda w: np.full(w["T"], 1)), (-2, lambda w: w["active"])):
+        w = table_world(39, 3, 5)
+        arrays = dict(table_arrays(w), m=("u32", [len(w["tables"])]), grid=("u32", [2]), observer=("i32", [observer]))
+
+        def expect(w=w, who=who):
+            hero, board, nboard = RS.table_spots(w["deck"], w["turn"], who(w))
+            r = RS.batch_range(hero, board, nboard)
+            return table_expect(w, {k: r[k] for k in OUTPUTS["range"]}, ("agg", "win", "tie"), "boards")
+        cs.append(Case("range-table-form-observer%d" % observer, "range", arrays, expect, quick=(observer == -2)))
+    return cs
+
+
+# ---------------------------------------------------------------------------------------------------------------- equity / sampled
+def eq_lpt(m):
+    return 16 if m < 16 else (64 if m < 256 else 1024)               # pk::eq_lpt
+
+
+def seat_spots(seed, n, specs):
+    """specs: [(nb, live mask or None = every seat, seats whose cards are unknown)] -> holes [m, n, 2], board, nboard, live."""
+    rng = np.random.default_rng(seed)
+    m = len(specs)
+    holes, board = np.zeros((m, n, 2), np.uint8), np.zeros((m, 5), np.uint8)
+    nboard, live = np.zeros(m, np.uint8), np.zeros(m, np.uint16)
+    for i, (nb, lv, unknown) in enumerate(specs):
+        vals = np.array([card(c) for c in rng.permutation(52)], np.uint8)
+        board[i], holes[i], nboard[i] = vals[:5], vals[5:5 + 2 * n].reshape(n, 2), nb
+        live[i] = (1 << n) - 1 if lv is None else lv
+        for p in unknown:
+            holes[i, p] = ES.UNKNOWN
+    return holes, board, nboard, live
+
+
+def equity_case(name, n, specs, seed, grid, outputs=None, quick=False, edit=None):
+    holes, board, nboard, live = seat_spots(seed, n, specs)
+    if edit:
+        edit(holes, board, nboard, live)
+    m = len(specs)
+    arrays = {"N": ("u32", [n]), "m": ("u32", [m]), "grid": ("u32", [grid]), "lpt": ("u32", [eq_lpt(m)]), "pool_max": ("u32", [50]),
+              "holes": ("u8", holes), "board": ("u8", board), "nboard": ("u8", nboard), "live": ("u16", live)}
+    return Case(name, "equity", arrays, lambda: ES.batch_equity(holes, board, nboard, live), outputs, quick)
+
+
+def equity_cases():
+    cs = []
+    # N = 2: nb = 2 is a spot of 15 tasks (C(46, 3) = 15 180 boards, 1 024 per task): more tasks than the 8 or 16 waves -> the counter path;
+    # a folded seat with unknown cards, a lone live seat
+    two = [(2, None, ()), (3, None, ()), (4, None, ()), (5, None, ()), (2, 0b01, (1,)), (3, 0b10, ()), (5, 0b10, (0,))]
+    cs.append(equity_case("equity-N2-grid1", 2, two, 41, 1, quick=True))
+    cs.append(equity_case("equity-N2-grid2", 2, two, 42, 2))
+    cs.append(equity_case("equity-N3", 3, [(2, None, ()), (3, 0b101, (1,)), (4, 0b110, ()), (5, None, ()), (4, 0b010, (0, 2))], 43, 1, quick=True))
+    cs.append(equity_case("equity-N9", 9, [(1, None, ()), (3, 0b101010101, (1, 3)), (5, None, ()), (4, 0b000010000, ()), (2, 0b111000111, ())], 44, 2))
+    cs.append(equity_case("equity-N16", 16, [(0, None, ()), (1, 0xF0F0, ()), (2, None, ()), (5, 0x8001, ()), (3, 0x0100, ())], 45, 2))
+    cs.append(equity_case("equity-N16-quick", 16, [(2, None, ()), (5, 0x8001, ()), (1, 0xF0F0, ())], 46, 1, quick=True))
+
+    # 72 river spots of one task each on one workgroup: 68 tasks >= 8 per wave -> runs of four; four refused spots inside the batch
+    def some_bad(holes, board, nboard, live):
+        holes[5, 0, 0] = board[5, 1]
+        live[20] = 0
+        nboard[41] = 9
+        holes[63, 1, 1] = 0x3D
+    cs.append(equity_case("equity-take4", 2, [(5, None, ())] * 72, 47, 1, edit=some_bad, quick=True))
+    cs.append(equity_case("equity-take4-N3-turn", 3, [(4, None, ())] * 70, 48, 1))
+    for o in ("win", "tie", "share", "boards", "status"):
+        cs.append(equity_case("equity-no-" + o, 3, [(4, None, ()), (5, 0b011, (2,))], 49, 1, outputs=[x for x in OUTPUTS["equity"] if x != o]))
+
+    def bits(holes, board, nboard, live):
+        holes[1, 0, 0] = 0x1F                                         # rank nibble 15
+        holes[2, 1, 1] = board[2, 2]
+        live[3] = 0
+        nboard[4] = 6
+        holes[5, 1] = ES.UNKNOWN                                      # a LIVE seat's cards must be known
+    cs.append(equity_case("equity-status-bits", 2, [(5, None, ())] * 7, 50, 1, edit=bits, quick=True))
+    for n in (2, 9):
+        w = table_world(51 + n, n, 5, turns=(1, 2, 3, 0) if n == 9 else (1, 2, 3))   # (pre-flop at two seats is 1.7 million boards)
+        arrays = dict(table_arrays(w), m=("u32", [len(w["tables"])]), grid=("u32", [2]), lpt=("u32", [16]), pool_max=("u32", [52 - 2 * n]))
+
+        def expect(w=w):
+            holes, board, nboard, live = ES.table_spots(w["deck"], w["states"], w["turn"])
+            r = ES.batch_equity(holes, board, nboard, live)
+            return table_expect(w, {k: r[k] for k in OUTPUTS["equity"]}, ("win", "tie", "share"), "boards")
+        cs.append(Case("equity-table-form-N%d" % n, "equity", arrays, expect, quick=(n == 2)))
+    return cs
+
+
+def sampled_case(name, n, specs, seed, grid, samples, nonce=0, ids=None, lpt=None, quick=False, edit=None):
+    holes, board, nboard, live = seat_spots(seed, n, specs)
+    if edit:
+        edit(holes, board, nboard, live)
+    m = len(specs)
+    key = R.seed_key(SS.DEFAULT_SEED + seed)
+    arrays = {"N": ("u32", [n]), "m": ("u32", [m]), "grid": ("u32", [grid]), "samples": ("u32", [samples]), "nonce": ("u32", [nonce]),
+              "key0": ("u32", [key[0]]), "key1": ("u32", [key[1]]), "ids": ("u32", ids), "lpt": ("u32", None if lpt is None else [lpt]),
+              "holes": ("u8", holes), "board": ("u8", board), "nboard": ("u8", nboard), "live": ("u16", live)}
+    return Case(name, "sampled", arrays, lambda: SS.batch_equity(holes, board, nboard, live, samples, nonce=nonce, ids=ids, key=key), None, quick)
+
+
+def sampled_cases():
+    cs = []
+    # hidden hole cards: a seat's both, one byte, nobody's; a folded seat whose cards are simply in the pool
+    two = [(3, None, (1,)), (0, None, (0, 1)), (5, None, ()), (4, 0b01, (1,)), (2, None, ())]
+
+    def one_byte(holes, board, nboard, live):
+        holes[4, 0, 1] = ES.UNKNOWN
+    for s in (1, 63, 64, 65):
+        cs.append(sampled_case("sampled-N2-S%d" % s, 2, two, 61, 1, s, edit=one_byte, quick=(s in (1, 65))))
+    # several tasks per spot (512 samples per task at the smallest lpt), more tasks than waves on one workgroup; two nonces over the same spots
+    for nonce in (0, 1):
+        cs.append(sampled_case("sampled-N2-S1200-nonce%d" % nonce, 2, two, 61, 1, 1200, nonce=nonce, ids=[7, 7, 9, 2 ** 32 - 1, 0], edit=one_byte, quick=(nonce == 1)))
+    six = [(3, None, (1, 2, 3, 4, 5)), (0, 0b101101, (0, 1, 2, 3, 4, 5)), (5, None, (2,)), (4, 0b000100, (2,))]
+    cs.append(sampled_case("sampled-N6", 6, six, 62, 2, 200, quick=True))
+    # 16 seats, everything hidden: 32 + k draws -- pre-flop 37, the third Philox block; the flop 34, the second
+    all16 = tuple(range(16))
+    cs.append(sampled_case("sampled-N16", 16, [(0, None, all16), (3, None, all16), (5, 0x00FF, all16), (4, None, ())], 63, 1, 130, quick=True))
+
+    def bits(holes, board, nboard, live):
+        holes[1, 0, 0] = 0x0E
+        holes[2, 1, 1] = board[2, 2]
+        live[3] = 0
+        nboard[4] = 6
+    cs.append(sampled_case("sampled-status-bits", 2, [(5, None, ())] * 6, 64, 1, 64, edit=bits, quick=True))
+    for observer in (-1, -2, 1):
+        w = table_world(65, 6, 5)
+        key = R.seed_key(SS.DEFAULT_SEED)
+        arrays = dict(table_arrays(w), m=("u32", [len(w["tables"])]), grid=("u32", [1]), samples=("u32", [65]), nonce=("u32", [3]), key0=("u32", [key[0]]),
+                      key1=("u32", [key[1]]), id_base=("u32", [1000]), observer=("i32", [observer]))
+
+        def expect(w=w, observer=observer, key=key):
+            holes, board, nboard, live = SS.table_spots(w["deck"], w["states"], w["turn"], w["active"], observer)
+            r = SS.batch_equity(holes, board, nboard, live, 65, nonce=3, ids=[1000 + t for t in range(w["T"])], key=key)
+            return table_expect(w, {k: r[k] for k in OUTPUTS["sampled"]}, ("win", "tie", "share"), "samples")
+        cs.append(Case("sampled-table-form-observer%d" % observer, "sampled", arrays, expect, quick=(observer == -2)))
+    return cs
+
+
+def all_cases():
+    cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--exe", action="append", help="the driver; given several times, every case runs on each build")
+    ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--only", default="")
+    ap.add_argument("--list", action="store_true")
+    ap.add_argument("--keep")
+    a = ap.parse_args()
+    cases = [c for c in all_cases() if (c.quick or not a.quick) and a.only in c.name]
+    if a.list:
+        for c in cases:
+            print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))
+        return 0
+    if not a.exe:
+        ap.error("--exe")
+    work = a.keep or tempfile.mkdtemp(prefix="equity_sim_")
+    os.makedirs(work, exist_ok=True)
+    failed, total = 0, [0.0] * len(a.exe)
+    for c in cases:
+        for k, exe in enumerate(a.exe):
+            bad, sec, log = run_case(exe, c, work)
+            total[k] += sec
+            stats = [ln for ln in log.splitlines() if ln.startswith("equity_sim:")]
+            print("%-34s %-18s %s  %7.2f s  %s" % (c.name, os.path.basename(exe), "FAILED" if bad else "== spec", sec, stats[-1].split(" done: ")[-1] if stats and not bad else ""))
+            if bad:
+                failed += 1
+                for b in bad:
+                    print("    " + b)
+                print("    " + "\n    ".join(log.splitlines()[-30:]))
+            sys.stdout.flush()
+    print("%d cases x %d builds, %d failed; in the driver: %s" % (len(cases), len(a.exe), failed, ", ".join("%s %.1f s" % (os.path.basename(e), t) for e, t in zip(a.exe, total))))
+    return 1 if failed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

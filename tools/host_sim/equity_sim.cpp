@@ -1,0 +1,311 @@
+// Dev-only: the REAL equity kernels -- k_equity<N>, k_eqs<N>, k_eqr, k_rvr, k_hist and their one-lane-per-spot preparation kernels, the text of
+// pokerl_amd/csrc/pk_equity*.hip -- run on the CPU as workgroups of 8 waves x 64 lanes (wg_shim.h: a fibre per lane, every collective and
+// barrier a checked rendezvous, garbage LDS before every workgroup, PK_IDX active).  One case per run: the case file names the family, the
+// spots, the weights / bins / samples, the grid and which outputs are wanted; the preparation kernel runs, then the main kernel, and every
+// output array goes to the out file.  Expected values are NOT computed here: tools/host_sim/equity_cases.py writes the case files and compares
+// the outputs with the numpy specs of tests/.  Every input, work and output array is an allocation of exactly its size (ASan bounds it); work
+// and output arrays start from a non-zero pattern (device memory is not zeroed, and the kernels promise to write every entry).
+//   g++ -std=c++20 -O1 -ffp-contract=off -DPK_HOST_SIM -I tools/host_sim/stub -include tools/host_sim/wg_shim.h tools/host_sim/equity_sim.cpp
+//   equity_sim <case file> <out file>
+// Case file: lines "name dtype count" (dtype u8 u16 u32 u64 i32) each followed by a line of `count` decimal values, and
+// "family <name>" / "outputs <name> ..." lines.  Out file: the same array format.
+// -DPK_ES_ONLY=1 .. 5: a build of ONE family (equity, sampled, range, rvr, hist), so that a test can compile the five side by side.
+#ifndef PK_ES_ONLY
+#define PK_ES_ONLY 0
+#endif
+#define PK_ES_HAS(n) (PK_ES_ONLY == 0 || PK_ES_ONLY == (n))
+#if PK_ES_HAS(1)
+#include "../../pokerl_amd/csrc/pk_equity.hip"
+#endif
+#if PK_ES_HAS(2)
+#include "../../pokerl_amd/csrc/pk_equity_sampled.hip"
+#endif
+#if PK_ES_HAS(3)
+#include "../../pokerl_amd/csrc/pk_equity_range.hip"
+#endif
+#if PK_ES_HAS(4) || PK_ES_HAS(5)
+#include "../../pokerl_amd/csrc/pk_equity_rvr.hip"      // (the histograms check their spots with k_rvr_prep)
+#endif
+#if PK_ES_HAS(5)
+#include "../../pokerl_amd/csrc/pk_equity_hist.hip"
+#endif
+
+#include <chrono>
+#include <climits>
+#include <fstream>
+#include <map>
+#include <memory>
+#include <sstream>
+
+namespace {
+
+[[noreturn]] void die(const std::string &what) { fprintf(stderr, "equity_sim: %s\n", what.c_str()); exit(2); }
+
+struct Buf {
+    std::string dtype;
+    size_t count = 0, width = 0;
+    void *p = nullptr;
+    Buf(const std::string &dt, size_t n, int fill) : dtype(dt), count(n) {
+        width = dt == "u8" ? 1 : (dt == "u16" ? 2 : (dt == "u32" || dt == "i32" ? 4 : (dt == "u64" ? 8 : 0)));
+        if (!width) die("dtype " + dt);
+        p = malloc(n * width ? n * width : 1);                       // exactly its size
+        memset(p, fill, n * width);
+    }
+    ~Buf() { free(p); }
+    Buf(const Buf &) = delete;
+    void set(size_t i, unsigned long long v) {
+        if (width == 1) ((uint8_t *)p)[i] = (uint8_t)v; else if (width == 2) ((uint16_t *)p)[i] = (uint16_t)v;
+        else if (width == 4) ((uint32_t *)p)[i] = (uint32_t)v; else ((uint64_t *)p)[i] = v;
+    }
+    unsigned long long get(size_t i) const {
+        return width == 1 ? ((uint8_t *)p)[i] : (width == 2 ? ((uint16_t *)p)[i] : (width == 4 ? ((uint32_t *)p)[i] : ((uint64_t *)p)[i]));
+    }
+};
+
+struct Case {
+    std::string family;
+    std::vector<std::string> outputs;
+    std::map<std::string, std::unique_ptr<Buf>> in;
+    std::vector<std::pair<std::string, std::unique_ptr<Buf>>> out;
+
+    explicit Case(const char *path) {
+        std::ifstream f(path);
+        if (!f) die(std::string("cannot read ") + path);
+        std::string line;
+        while (std::getline(f, line)) {
+            std::istringstream h(line);
+            std::string name, dt;
+            if (!(h >> name)) continue;
+            if (name == "family") { h >> family; continue; }
+            if (name == "outputs") { std::string o; while (h >> o) outputs.push_back(o); continue; }
+            size_t n;
+            if (!(h >> dt >> n)) die("bad header line: " + line);
+            auto b = std::make_unique<Buf>(dt, n, 0);
+            if (!std::getline(f, line)) die("no values for " + name);
+            std::istringstream v(line);
+            for (size_t i = 0; i < n; ++i) {
+                std::string tok;
+                if (!(v >> tok)) die("too few values for " + name);
+                b->set(i, dt == "i32" ? (unsigned long long)(long long)std::stoll(tok) : std::stoull(tok));
+            }
+            in[name] = std::move(b);
+        }
+    }
+    template <typename T> const T *arr(const char *name, size_t want) const {
+        auto it = in.find(name);
+        if (it == in.end()) return nullptr;
+        if (it->second->width != sizeof(T) || it->second->count != want) die(std::string(name) + ": " + std::to_string(it->second->count) + " x " + it->second->dtype + ", the kernel reads " + std::to_string(want) + " elements of " + std::to_string(sizeof(T)) + " bytes");
+        return (const T *)it->second->p;
+    }
+    template <typename T> const T *need(const char *name, size_t want) const {
+        const T *p = arr<T>(name, want);
+        if (!p) die(std::string("the case has no ") + name);
+        return p;
+    }
+    long long num(const char *name, long long dflt = LLONG_MIN) const {
+        auto it = in.find(name);
+        if (it == in.end()) { if (dflt == LLONG_MIN) die(std::string("the case has no ") + name); return dflt; }
+        return it->second->dtype == "i32" ? (long long)(int32_t)it->second->get(0) : (long long)it->second->get(0);
+    }
+    // an output array: NULL unless the case wants it; starts from 0xA5 bytes
+    template <typename T> T *output(const char *name, const char *dt, size_t n) {
+        if (std::find(outputs.begin(), outputs.end(), name) == outputs.end()) return nullptr;
+        out.emplace_back(name, std::make_unique<Buf>(dt, n, 0xA5));
+        return (T *)out.back().second->p;
+    }
+    void write(const char *path) const {
+        FILE *f = fopen(path, "w");
+        if (!f) die(std::string("cannot write ") + path);
+        for (const auto &o : out) {
+            fprintf(f, "%s %s %zu\n", o.first.c_str(), o.second->dtype.c_str(), o.second->count);
+            for (size_t i = 0; i < o.second->count; ++i) fprintf(f, i ? " %llu" : "%llu", o.second->get(i));
+            fprintf(f, "\n");
+        }
+        fclose(f);
+    }
+};
+
+// a work array of the call (descriptors, task list): exactly its size, 0x5A bytes
+template <typename T> struct Work {
+    T *p; size_t n;
+    explicit Work(size_t n_) : p((T *)malloc(n_ * sizeof(T) ? n_ * sizeof(T) : 1)), n(n_) { memset((void *)p, 0x5A, n * sizeof(T)); }
+    ~Work() { free(p); }
+    Work(const Work &) = delete;
+};
+
+// the table form's arrays (a handle's own state, hand-built by the case): cards [W][T] words, seat_states [T], cursors [T], tables [m] or none
+bool table_form(const Case &c, int N, size_t m, EqTables &t) {
+    if (c.in.find("cursors") == c.in.end()) return false;
+    const int T = (int)c.num("T"), W = (5 + 2 * N + 3) / 4;
+    t.T = T;
+    t.cards = c.need<uint32_t>("cards", (size_t)W * T);
+    t.seat_states = c.need<uint64_t>("seat_states", (size_t)T);
+    t.cursors = c.need<uint32_t>("cursors", (size_t)T);
+    t.tables = c.arr<int32_t>("tables", m);
+    return true;
+}
+unsigned prep_grid(size_t m, unsigned block) { return (unsigned)((m + block - 1) / block); }
+
+#if PK_ES_HAS(1)
+template <int N>
+void run_equity(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const int lpt = (int)c.num("lpt"), pool_max = (int)c.num("pool_max");
+    const unsigned grid = (unsigned)c.num("grid");
+    EqPrepArgs a{};
+    const bool tbl = table_form(c, N, m, a.t);
+    if (!tbl) { a.s.holes = c.need<uint8_t>("holes", m * N * 2); a.s.board = c.need<uint8_t>("board", m * 5); a.s.nboard = c.need<uint8_t>("nboard", m); a.s.live = c.need<uint16_t>("live", m); }
+    EqOut out{c.output<uint32_t>("win", "u32", m * N), c.output<uint32_t>("tie", "u32", m * N), c.output<uint64_t>("share", "u64", m * N),
+              c.output<uint32_t>("boards", "u32", m), c.output<uint8_t>("status", "u8", m)};
+    Work<EqCtrl> ctrl(1);
+    memset(ctrl.p, 0, sizeof(EqCtrl));                               // (eq_launch's hipMemsetAsync)
+    Work<uint64_t> desc(m * (size_t)(3 + N));
+    Work<uint2> tasks(pk::eq_task_cap(m, lpt, pool_max));
+    const EqWork w{ctrl.p, desc.p, tasks.p, tasks.n};
+    a.out = out; a.w = w; a.N = N; a.lpt = lpt; a.m = m;
+    if (tbl) pk_sim::launch(prep_grid(m, EQ_PREP_BLOCK), EQ_PREP_BLOCK, [&] { k_equity_prep<true>(a); });
+    else pk_sim::launch(prep_grid(m, EQ_PREP_BLOCK), EQ_PREP_BLOCK, [&] { k_equity_prep<false>(a); });
+    printf("tasks %u take %u\n", ctrl.p->ntasks, ctrl.p->ntasks >= 8u * grid * EQ_WAVES ? 4u : 1u);
+    pk_sim::launch(grid, EQ_BLOCK, [&] { k_equity<N>(tab, w, out, lpt); });
+}
+
+#endif
+
+#if PK_ES_HAS(2)
+template <int N>
+void run_sampled(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    EqsPrepArgs a{};
+    const bool tbl = table_form(c, N, m, a.t);
+    if (!tbl) { a.s.holes = c.need<uint8_t>("holes", m * N * 2); a.s.board = c.need<uint8_t>("board", m * 5); a.s.nboard = c.need<uint8_t>("nboard", m); a.s.live = c.need<uint16_t>("live", m); }
+    EqsStream rng{(uint32_t)c.num("key0"), (uint32_t)c.num("key1"), (uint32_t)c.num("nonce"), (uint32_t)c.num("samples"), (uint32_t)c.num("id_base", 0), c.arr<uint32_t>("ids", m)};
+    EqsOut out{};
+    out.win = c.output<uint32_t>("win", "u32", m * N); out.tie = c.output<uint32_t>("tie", "u32", m * N); out.share = c.output<uint64_t>("share", "u64", m * N);
+    out.samples = c.output<uint32_t>("samples", "u32", m); out.status = c.output<uint8_t>("status", "u8", m);
+    Work<uint64_t> desc(m * (size_t)eqs_desc_words(N));
+    a.rng = rng; a.out = out; a.desc = desc.p; a.N = N; a.observer = (int)c.num("observer", PK_OBSERVER_NONE); a.m = m;
+    if (tbl) pk_sim::launch(prep_grid(m, EQS_PREP_BLOCK), EQS_PREP_BLOCK, [&] { k_eqs_prep<true>(a); });
+    else pk_sim::launch(prep_grid(m, EQS_PREP_BLOCK), EQS_PREP_BLOCK, [&] { k_eqs_prep<false>(a); });
+    const long long lpt_case = c.num("lpt", 0);
+    const uint32_t S = rng.samples, per = 64u * (uint32_t)(lpt_case ? lpt_case : pk::eqs_lpt(m, S)), nch = (S + per - 1) / per, ntasks = (uint32_t)m * nch;
+    printf("tasks %u (%u per spot)\n", ntasks, nch);
+    const uint64_t *dp = desc.p;
+    pk_sim::launch(grid, EQ_BLOCK, [&] { k_eqs<N>(tab, dp, out, rng, ntasks, nch, per); });
+}
+
+#endif
+
+#if PK_ES_HAS(3)
+void run_range(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const int N = (int)c.num("N", 2);
+    EqrPrepArgs a{};
+    const bool tbl = table_form(c, N, m, a.t);
+    if (!tbl) { a.s.hero = c.need<uint8_t>("hero", m * 2); a.s.board = c.need<uint8_t>("board", m * 5); a.s.nboard = c.need<uint8_t>("nboard", m); a.s.dead = c.arr<uint64_t>("dead", m); }
+    const int per_spot = (int)c.num("per_spot", 0);
+    const EqrWeights wts{c.arr<uint16_t>("weights", per_spot ? m * EQR_HOLDINGS : (size_t)EQR_HOLDINGS), per_spot};
+    EqrOut out{};
+    out.agg = c.output<uint64_t>("agg", "u64", m * 3); out.win = c.output<uint32_t>("win", "u32", m * EQR_HOLDINGS); out.tie = c.output<uint32_t>("tie", "u32", m * EQR_HOLDINGS);
+    out.boards = c.output<uint32_t>("boards", "u32", m); out.status = c.output<uint8_t>("status", "u8", m);
+    Work<uint64_t> desc(m * EQR_DESC_WORDS);
+    a.out = out; a.desc = desc.p; a.N = N; a.observer = (int)c.num("observer", 0); a.m = m;
+    if (tbl) pk_sim::launch(prep_grid(m, EQR_PREP_BLOCK), EQR_PREP_BLOCK, [&] { k_eqr_prep<true>(a); });
+    else pk_sim::launch(prep_grid(m, EQR_PREP_BLOCK), EQR_PREP_BLOCK, [&] { k_eqr_prep<false>(a); });
+    const uint64_t *dp = desc.p;
+    if (out.agg || out.win || out.tie) pk_sim::launch(grid, EQR_BLOCK, [&] { k_eqr(tab, dp, wts, out, (uint32_t)m); });
+}
+
+#endif
+
+#if PK_ES_HAS(4) || PK_ES_HAS(5)
+// k_rvr_prep for range vs range and the histograms alike
+void run_rvr_prep(Case &c, size_t m, const RvrOut &out, uint64_t *desc) {
+    RvrPrepArgs a{};
+    const bool tbl = table_form(c, (int)c.num("N", 2), m, a.t);
+    if (!tbl) { a.s.board = c.need<uint8_t>("board", m * 5); a.s.nboard = c.need<uint8_t>("nboard", m); a.s.dead = c.arr<uint64_t>("dead", m); }
+    a.out = out; a.desc = desc; a.m = m;
+    if (tbl) pk_sim::launch(prep_grid(m, RVR_PREP_BLOCK), RVR_PREP_BLOCK, [&] { k_rvr_prep<true>(a); });
+    else pk_sim::launch(prep_grid(m, RVR_PREP_BLOCK), RVR_PREP_BLOCK, [&] { k_rvr_prep<false>(a); });
+}
+
+#endif
+
+#if PK_ES_HAS(4)
+void run_rvr(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const int per_spot = (int)c.num("per_spot", 0);
+    const RvrWeights wts{c.arr<uint16_t>("weights", per_spot ? m * RVR_HOLDINGS : (size_t)RVR_HOLDINGS), per_spot};
+    RvrOut out{};
+    out.win = c.output<uint64_t>("win", "u64", m * RVR_HOLDINGS); out.tie = c.output<uint64_t>("tie", "u64", m * RVR_HOLDINGS); out.tot = c.output<uint64_t>("tot", "u64", m * RVR_HOLDINGS);
+    out.boards = c.output<uint32_t>("boards", "u32", m); out.status = c.output<uint8_t>("status", "u8", m);
+    Work<uint64_t> desc(m * RVR_DESC_WORDS);
+    run_rvr_prep(c, m, out, desc.p);
+    const uint64_t *dp = desc.p;
+    if (out.win || out.tie || out.tot) pk_sim::launch(grid, RVR_BLOCK, [&] { k_rvr(tab, dp, wts, out, (uint32_t)m); });
+}
+
+#endif
+
+#if PK_ES_HAS(5)
+void run_hist(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const uint32_t bins = (uint32_t)c.num("bins");
+    const int per_spot = (int)c.num("per_spot", 0);
+    const RvrWeights wts{c.arr<uint16_t>("weights", per_spot ? m * RVR_HOLDINGS : (size_t)RVR_HOLDINGS), per_spot};
+    HistOut out{};
+    out.hist = c.output<uint16_t>("hist", "u16", m * RVR_HOLDINGS * bins); out.void_ = c.output<uint16_t>("void", "u16", m * RVR_HOLDINGS);
+    out.completions = c.output<uint32_t>("completions", "u32", m); out.status = c.output<uint8_t>("status", "u8", m);
+    Work<uint64_t> desc(m * RVR_DESC_WORDS);
+    run_rvr_prep(c, m, RvrOut{nullptr, nullptr, nullptr, nullptr, out.status}, desc.p);
+    const uint64_t *dp = desc.p;
+    if (out.completions) pk_sim::launch(prep_grid(m, HIST_COUNTS_BLOCK), HIST_COUNTS_BLOCK, [&] { k_hist_counts(dp, out.completions, m); });
+    if (out.hist || out.void_) pk_sim::launch(grid, RVR_BLOCK, [&] { k_hist(tab, dp, wts, out, bins, (uint32_t)m); });
+}
+#endif
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    if (argc != 3) die("usage: equity_sim <case file> <out file>");
+    Case c(argv[1]);
+    // the function-local __shared__ arrays of the five main kernels (the preparation kernels have none)
+    const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj"});
+    Work<uint32_t> tab(EVAL7_TAB_WORDS);
+    for (int i = 0; i < EVAL7_TAB_WORDS; ++i) tab.p[i] = eval7_tab_entry((uint32_t)i);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int N = (int)c.num("N", 2);
+    bool ran = false;
+    (void)N;
+#if PK_ES_HAS(1)
+    if (c.family == "equity") {
+        if (N == 2) run_equity<2>(c, tab.p); else if (N == 3) run_equity<3>(c, tab.p); else if (N == 9) run_equity<9>(c, tab.p); else if (N == 16) run_equity<16>(c, tab.p);
+        else die("k_equity<N>: this build has N = 2, 3, 9, 16");
+        ran = true;
+    }
+#endif
+#if PK_ES_HAS(2)
+    if (c.family == "sampled") {
+        if (N == 2) run_sampled<2>(c, tab.p); else if (N == 6) run_sampled<6>(c, tab.p); else if (N == 16) run_sampled<16>(c, tab.p);
+        else die("k_eqs<N>: this build has N = 2, 6, 16");
+        ran = true;
+    }
+#endif
+#if PK_ES_HAS(3)
+    if (c.family == "range") { run_range(c, tab.p); ran = true; }
+#endif
+#if PK_ES_HAS(4)
+    if (c.family == "rvr") { run_rvr(c, tab.p); ran = true; }
+#endif
+#if PK_ES_HAS(5)
+    if (c.family == "hist") { run_hist(c, tab.p); ran = true; }
+#endif
+    if (!ran) die("family " + c.family + ": not in this build");
+    c.write(argv[2]);
+    printf("equity_sim: %s done: %zu LDS bytes in %zu arrays refilled per workgroup, %llu __syncthreads, %llu wave collectives  [%.2f s]\n", c.family.c_str(), lds,
+           pk_sim::g_lds.size(), pk_sim::g.barriers, pk_sim::g.rendezvous, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return 0;
+}

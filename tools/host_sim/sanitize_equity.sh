@@ -1,0 +1,32 @@
+#!/bin/bash
+# Dev-only: the 8-wave CPU build of the equity kernels (equity_sim.cpp on wg_shim.h) under ASan + UBSan and under TSan, EVERY case of
+# equity_cases.py on both builds, each compared with the numpy specs; exits 0 only if every case on both builds does.  Stand-alone programs, run
+# directly; the two builds are compiled side by side (2 jobs, never more than 16).
+#   tools/host_sim/sanitize_equity.sh [out-dir] [equity_cases.py options, e.g. --only rvr]      (default out-dir /tmp/equity_sim_san)
+set -e -o pipefail
+cd "$(dirname "$0")/../.."
+OUT=${1:-/tmp/equity_sim_san}
+shift || true
+JOBS=${PK_BUILD_JOBS:-$(n=$(nproc); echo $(( n < 16 ? n : 16 )))}
+mkdir -p "$OUT"
+CXX="g++ -std=c++20 -O1 -g -ffp-contract=off -fno-omit-frame-pointer -DPK_HOST_SIM -I tools/host_sim/stub -include tools/host_sim/wg_shim.h"
+t0=$SECONDS
+printf '%s\n' "asan -fsanitize=address,undefined -fno-sanitize-recover=undefined" "tsan -fsanitize=thread" | xargs -P "$JOBS" -L 1 sh -c \
+    "$CXX \$1 \$2 tools/host_sim/equity_sim.cpp -o $OUT/equity_sim_\$0 2>$OUT/build_\$0.log" \
+    || { for f in "$OUT"/build_*.log; do [ -s "$f" ] && { echo "== $f"; cat "$f"; }; done; echo "build FAILED"; exit 1; }
+$CXX -fsanitize=address,undefined -fno-sanitize-recover=undefined tools/host_sim/wg_shim_selftest.cpp -o "$OUT/selftest_asan"
+$CXX -fsanitize=thread tools/host_sim/wg_shim_selftest.cpp -o "$OUT/selftest_tsan"
+echo "build asan + tsan: $((SECONDS - t0)) s ($JOBS jobs at most)"
+g++ --version | head -1
+export UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 ASAN_OPTIONS=detect_leaks=1 TSAN_OPTIONS=halt_on_error=1:second_deadlock_stack=1
+# the shim against itself: clean on both builds; a missing barrier between waves must be a race TSan reports (that run is MEANT to fail)
+"$OUT/selftest_asan" ok
+"$OUT/selftest_tsan" ok
+for mode in race race-ahead; do
+    if "$OUT/selftest_tsan" $mode >"$OUT/selftest_$mode.log" 2>&1; then echo "wg_shim_selftest $mode: TSan reported NO race"; exit 1; fi
+    grep -q "ThreadSanitizer: data race" "$OUT/selftest_$mode.log" || { cat "$OUT/selftest_$mode.log"; exit 1; }
+    echo "wg_shim_selftest $mode: TSan reports the race (as it must)"
+done
+t0=$SECONDS
+python3 tools/host_sim/equity_cases.py --exe "$OUT/equity_sim_asan" --exe "$OUT/equity_sim_tsan" --keep "$OUT/cases" "$@"
+echo "run asan + tsan: $((SECONDS - t0)) s"

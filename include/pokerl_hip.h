@@ -600,6 +600,52 @@ int pk_table_equity_sampled_d(pk_handle *h, const int32_t *tables_d, size_t m, i
                               uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *samples_d, uint8_t *status_d);
 int pk_table_equity_sampled(pk_handle *h, const int32_t *tables, size_t m, int observer, uint32_t samples, uint32_t nonce, uint32_t *win,
                             uint32_t *tie, uint64_t *share, uint32_t *samples_out, uint8_t *status);
+/* ---- Ranged sampled equity: sampled showdown equity where every hidden seat draws its HOLDING from a weighted range -- any seat count, any
+ * street.  Everything not stated here is "Sampled showdown equity" above.
+ *
+ * A SPOT is as there, except that a live seat shows both hole cards or hides both (0xFF 0xFF): a live seat with exactly one 0xFF is refused
+ * with PK_EQ_BAD_CARD (a weighted draw of half a holding is not defined).  Dead cards = the nb board cards and every hole byte that is a card,
+ * live or not; a 0xFF at a seat that is not live is in the pool; P = 52 - dead.  Hidden seats in ascending seat order, j = 0 .. H-1; always
+ * P - 2H >= 15 >= 5 - nb.
+ * RANGES: per call one table weights u16 [R][1326], 0 <= R <= PK_EQW_MAX_RANGES, over the holding index h = b (b - 1) / 2 + a of range equity
+ * below.  Per spot, range_of u16 [N] names each seat's row (the explicit form: [m][N]); PK_EQW_UNIFORM (0xFFFF) = every weight 1; range_of == NULL = every hidden seat uniform.  An
+ * entry is read only where the seat is hidden; there a value >= R other than 0xFFFF gives the spot PK_EQ_BAD_CARD (the u8 status word has no
+ * bit left: a row that does not exist is reported as a bad input byte).  cum_r[h] = sum of w_r[0 .. h] (u32), T_r = cum_r[1325] < 2^27; the
+ * uniform row has cum[h] = h + 1, T = 1326.
+ * ATTEMPT s (0 .. S-1) of a spot with stream id `id`: Philox4x32-10 under `key`, counter (id, s, 'EQW0' + b, nonce) with 'EQW0' = 0x45515730,
+ * blocks b = 0 .. ceil((H + 1) / 2) - 1, words X[2b] = w0 | w1 << 32, X[2b+1] = w2 | w3 << 32.
+ *   1. hidden seat j draws u_j = (X[j] * T_j) >> 64; its holding h_j = the number of h with cum[h] <= u_j.
+ *   2. the attempt is REJECTED if some T_j = 0, a drawn holding contains a dead card, or two drawn holdings share a card.  The accepted joint
+ *      law is proportional to the product of w_j[h_j] over holdings disjoint from each other and from the dead cards.
+ *   3. an accepted attempt draws the 5 - nb board cards from the P' = P - 2H pool cards left, canonical order, by the chained rule from the ONE
+ *      word x = X[H]: c_i = (x * (P' - i)) >> 64, x = the low 64 bits; slot nb + i receives the c_i-th card not yet drawn.
+ *   4. v[p] = eval_hand(board + hole[p]) for a live seat, (NONE, []) otherwise; winners = compare_rankings(v) as in "Showdown equity".
+ * OUTPUTS over the ACCEPTED attempts: win, tie u32 [m][N], share u64 [m][N] (units of 720720 / nw), per spot accepted u32 and status u8.
+ * equity = share / (720720 * accepted), formed by the caller (nan at accepted = 0).  A range with no weight left is NOT an error: status 0,
+ * accepted 0.  A non-zero status gives zeros and disturbs no neighbour.  S = 1 .. 2^24, m * ceil(S / 64) must fit 32 bits, counts of calls
+ * with different nonces add exactly (accepted included), a spot's counts depend on (spot, ranges, key, nonce, id, S) only.
+ * Refused with PK_E_INVALID_ARG: what pk_equity_sampled refuses, num_ranges > PK_EQW_MAX_RANGES, num_ranges > 0 with weights NULL, and in the
+ * table form observer PK_OBSERVER_NONE (nothing would be hidden).
+ * TABLE FORM: the spot is exactly pk_table_equity_sampled's for a seat or PK_OBSERVER_ACTIVE (folded seats are not dead and not read);
+ * range_of is u16 [N] by seat for all tables (range_per_table = 0) or [m][N] (1); the observer's own entry is ignored.  Key, id, deferred
+ * rollout work, read-only, the handle's stream, PK_EQ_IN_FLIGHT / PK_EQ_BAD_TABLE / PK_EQ_DUP_CARD: as pk_table_equity_sampled.
+ * STREAMS and work space: as pk_equity_sampled; the work space also holds the u32 [R][1326] cumulative sums. */
+#define PK_EQW_MAX_RANGES 16
+#define PK_EQW_UNIFORM 0xFFFFu
+int pk_equity_ranged_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
+                       const uint16_t *live_d, const uint32_t *ids_d /* NULL: i */, uint32_t samples, uint64_t seed, uint32_t nonce,
+                       const uint16_t *weights_d /*[R][1326]*/, uint32_t num_ranges, const uint16_t *range_of_d /*[m][N], NULL: uniform*/,
+                       uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *accepted_d, uint8_t *status_d, void *stream);
+int pk_equity_ranged(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard,
+                     const uint16_t *live, const uint32_t *ids /* NULL: i */, uint32_t samples, uint64_t seed, uint32_t nonce,
+                     const uint16_t *weights, uint32_t num_ranges, const uint16_t *range_of, uint32_t *win, uint32_t *tie, uint64_t *share,
+                     uint32_t *accepted, uint8_t *status);
+int pk_table_equity_ranged_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce,
+                             const uint16_t *weights_d, uint32_t num_ranges, const uint16_t *range_of_d, int range_per_table, uint32_t *win_d,
+                             uint32_t *tie_d, uint64_t *share_d, uint32_t *accepted_d, uint8_t *status_d);
+int pk_table_equity_ranged(pk_handle *h, const int32_t *tables, size_t m, int observer, uint32_t samples, uint32_t nonce,
+                           const uint16_t *weights, uint32_t num_ranges, const uint16_t *range_of, int range_per_table, uint32_t *win,
+                           uint32_t *tie, uint64_t *share, uint32_t *accepted, uint8_t *status);
 /* ---- Range equity: exact hand strength against ONE hidden hand -- the hero's result against every holding the hidden opponent can have, per
  * holding and reduced by a range of weights.  POST-FLOP ONLY: pre-flop a hidden hand is 2 * 10^9 boards per spot and
  * the pre-flop hero-versus-holding table is a constant nobody needs recomputed; such a spot reports PK_EQ_PREFLOP.

@@ -9,6 +9,7 @@ from .judger import (Equity, SampledEquity, compare_hands, compare_rankings, eva
 from .judger import HOLDINGS, RangeEquity, holding_index, range_equity, range_equity_batch, range_equity_d
 from .judger import RangeVsRange, range_vs_range, range_vs_range_batch, range_vs_range_d
 from .judger import StrengthHistogram, histogram_emd, strength_histogram, strength_histogram_batch, strength_histogram_d
+from .judger import RangedEquity, ranged_equity, ranged_equity_batch, ranged_equity_d
 from .sharding import gather_f64, shard_tables
 from .single import Game, PokerGameEnv
 from .state_view import Card, StateView, packed_dtype, unpack_obs
@@ -22,4 +23,5 @@ __all__ = ['Game', 'PokerGameEnv', 'VecGame', 'VecPokerGameEnv', 'VecPokerGameEn
            'SampledEquity', 'sampled_equity', 'sampled_equity_batch',
            'HOLDINGS', 'RangeEquity', 'holding_index', 'range_equity', 'range_equity_batch', 'range_equity_d',
            'RangeVsRange', 'range_vs_range', 'range_vs_range_batch', 'range_vs_range_d',
-           'StrengthHistogram', 'histogram_emd', 'strength_histogram', 'strength_histogram_batch', 'strength_histogram_d']
+           'StrengthHistogram', 'histogram_emd', 'strength_histogram', 'strength_histogram_batch', 'strength_histogram_d',
+           'RangedEquity', 'ranged_equity', 'ranged_equity_batch', 'ranged_equity_d']

@@ -26,6 +26,7 @@ EQ_PREFLOP, EQ_SMALL_POOL = 64, 128   # ... of pk_equity_range: nb < 3 / fewer p
 EQ_HIST_MAX_BINS = 32   # PK_EQ_HIST_MAX_BINS: the most bins of a strength histogram
 EQ_HOLDINGS = 1326   # PK_EQ_HOLDINGS: unordered pairs of the 52 cards, h = b (b - 1) / 2 + a over canonical indices a < b
 EQS_SAMPLES_MAX = 1 << 24   # pk_equity_sampled: samples per call and spot at most
+EQW_MAX_RANGES, EQW_UNIFORM = 16, 0xFFFF   # pk_equity_ranged: rows of a call's weight table at most / the range_of entry "every weight 1"
 
 # every symbol include/pokerl_hip.h declares (tests check the library exports each one)
 SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "pk_destroy", "pk_num_tables",
@@ -44,7 +45,8 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_equity_sampled_d", "pk_equity_sampled", "pk_table_equity_sampled_d", "pk_table_equity_sampled", "pk_get_wave_shape",
            "pk_equity_range_d", "pk_equity_range", "pk_table_equity_range_d", "pk_table_equity_range",
            "pk_equity_rvr_d", "pk_equity_rvr", "pk_table_equity_rvr_d", "pk_table_equity_rvr",
-           "pk_equity_hist_d", "pk_equity_hist", "pk_table_equity_hist_d", "pk_table_equity_hist"]
+           "pk_equity_hist_d", "pk_equity_hist", "pk_table_equity_hist_d", "pk_table_equity_hist",
+           "pk_equity_ranged_d", "pk_equity_ranged", "pk_table_equity_ranged_d", "pk_table_equity_ranged"]
 
 
 class PokerlHipError(RuntimeError):
@@ -150,6 +152,10 @@ def lib():
     L.pk_equity_sampled.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_uint32, C.c_uint64, C.c_uint32] + [_vp] * 5
     L.pk_table_equity_sampled_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32] + [_vp] * 5
     L.pk_table_equity_sampled.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32] + [_vp] * 5
+    L.pk_equity_ranged_d.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_uint32, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp] + [_vp] * 6
+    L.pk_equity_ranged.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_uint32, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp] + [_vp] * 5
+    L.pk_table_equity_ranged_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_int] + [_vp] * 5
+    L.pk_table_equity_ranged.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_int] + [_vp] * 5
     L.pk_equity_range_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_int] + [_vp] * 6
     L.pk_equity_range.argtypes = [C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_int] + [_vp] * 5
     L.pk_table_equity_range_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int] + [_vp] * 5

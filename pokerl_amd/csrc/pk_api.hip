@@ -17,6 +17,7 @@
 #include "pk_util_kernels.hpp"
 #include "pk_equity.hpp"
 #include "pk_equity_sampled.hpp"
+#include "pk_equity_ranged.hpp"
 #include "pk_equity_range.hpp"
 #include "pk_equity_rvr.hpp"
 #include "pk_equity_hist.hpp"
@@ -2048,6 +2049,120 @@ int pk_table_equity_sampled(pk_handle *h, const int32_t *tables, size_t m, int o
     if (rc) return rc;
     HIPCHK(h, g.upload(h->stream));
     if ((rc = table_equity_sampled(h, g.at<int32_t>(idx), m, observer, samples, nonce, eqs_out(out.at(g)), g.at<char>(work)))) return rc;
+    HIPCHK(h, g.download(h->stream));
+    return PK_OK;
+}
+
+// ---- ranged sampled equity (pokerl_hip.h "Ranged sampled equity"; kernels: pk_equity_ranged.hip).  Work space: the cumulative sums of the
+// call's range rows, then the descriptors -- the per-(device, stream) buffer, the judger arena or the handle's staging buffer, as above.
+static EqwOut eqw_out(const EqOut &o) { return EqwOut{o.win, o.tie, o.share, o.boards, o.status}; }
+#define EQW_CHECK_RANGES(fail, call, weights, num_ranges)                                                                                          \
+    if ((num_ranges) > (uint32_t)EQW_MAX_RANGES) return fail(PK_E_INVALID_ARG, call ": num_ranges above PK_EQW_MAX_RANGES (16)");                  \
+    if ((num_ranges) && !(weights)) return fail(PK_E_INVALID_ARG, call ": NULL weights with num_ranges > 0")
+
+int pk_equity_ranged_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
+                       const uint16_t *live_d, const uint32_t *ids_d, uint32_t samples, uint64_t seed, uint32_t nonce, const uint16_t *weights_d,
+                       uint32_t num_ranges, const uint16_t *range_of_d, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *accepted_d,
+                       uint8_t *status_d, void *stream) {
+    EQS_CHECK_SPOTS("pk_equity_ranged_d", num_players, m, samples, holes_d && board_d && nboard_d && live_d);
+    EQW_CHECK_RANGES(g_fail, "pk_equity_ranged_d", weights_d, num_ranges);
+    ON_DEVICE_INDEX("pk_equity_ranged_d", device, PK_MAX_DEVICES);
+    if (m == 0) return PK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t *tab = eval7_table(device, st);
+    if (!tab) return g_fail(PK_E_OOM, "pk_equity_ranged_d: out of device memory (evaluator table)");
+    void *ws = eq_stream_ws(device, st, eqw_work_bytes(num_players, m, num_ranges));
+    if (!ws) return g_fail(PK_E_OOM, "pk_equity_ranged_d: out of device memory (work space)");
+    const EqSpots spots{holes_d, board_d, nboard_d, live_d};
+    const hipError_t e = eqw_launch(st, tab, &spots, nullptr, PK_OBSERVER_ACTIVE, eqs_seed_stream(seed, nonce, samples, ids_d),
+                                    EqwRanges{weights_d, num_ranges, range_of_d, 1}, num_players, m,
+                                    EqwOut{win_d, tie_d, share_d, accepted_d, status_d}, (char *)ws);
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_ranged_d: launch failed", e);
+    return PK_OK;
+}
+
+int pk_equity_ranged(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
+                     const uint32_t *ids, uint32_t samples, uint64_t seed, uint32_t nonce, const uint16_t *weights, uint32_t num_ranges,
+                     const uint16_t *range_of, uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *accepted, uint8_t *status) {
+    EQS_CHECK_SPOTS("pk_equity_ranged", num_players, m, samples, holes && board && nboard && live);
+    EQW_CHECK_RANGES(g_fail, "pk_equity_ranged", weights, num_ranges);
+    ON_DEVICE_INDEX("pk_equity_ranged", device, PK_MAX_DEVICES);
+    if (m == 0) return PK_OK;
+    const int N = num_players;
+    hipStream_t st = nullptr;
+    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity_ranged: no stream"); }
+    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
+    int rc = PK_OK;
+    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity_ranged: out of device memory (evaluator table)");
+    else {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        Stage g;
+        const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), id = g.in(ids, m * 4);
+        const int wt = g.in(num_ranges ? weights : nullptr, (size_t)num_ranges * EQW_HOLDINGS * 2), ro = g.in(range_of, m * (size_t)N * 2);
+        const EqStagedOut out(g, N, m, win, tie, share, accepted, status);
+        const int work = g.add(eqw_work_bytes(N, m, num_ranges));
+        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity_ranged: out of device memory");
+        else {
+            const hipError_t e = g.run(st, [&] {
+                const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
+                return eqw_launch(st, tab, &spots, nullptr, PK_OBSERVER_ACTIVE, eqs_seed_stream(seed, nonce, samples, g.at<uint32_t>(id)),
+                                  EqwRanges{g.at<uint16_t>(wt), num_ranges, g.at<uint16_t>(ro), 1}, N, m, eqw_out(out.at(g)), g.at<char>(work));
+            });
+            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity_ranged", e); }   // (the lock is held until what was queued is done)
+        }
+    }
+    stream_release(device, st);
+    return rc;
+}
+
+// The table form: the handle's own state on the handle's stream, as `observer` sees it; the handle's key, stream id = table_id_base + table
+static int table_equity_ranged(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce, const EqwRanges &ranges,
+                               const EqwOut &out, char *work) {
+    const uint32_t *tab = eval7_table(h->device, h->stream);
+    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity_ranged: out of device memory (evaluator table)");
+    const EqTables t{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T};
+    const EqsStream rng{h->S.key0, h->S.key1, nonce, samples, h->S.table_id_base, nullptr};
+    HIPCHK(h, eqw_launch(h->stream, tab, nullptr, &t, observer, rng, ranges, h->N, m, out, work));
+    return PK_OK;
+}
+#define EQW_TABLE_ENTER(h, m, observer, samples, weights, num_ranges, call)                                                                  \
+    if (!(h)) return PK_E_INVALID_ARG;                                                                                                       \
+    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                                                         \
+    if (eqs_bad_samples(samples)) return (h)->fail(PK_E_INVALID_ARG, call ": samples outside 1 .. 2^24");                                    \
+    if ((observer) == PK_OBSERVER_NONE || (observer) < PK_OBSERVER_ACTIVE || (observer) >= (h)->N)                                           \
+        return (h)->fail(PK_E_INVALID_ARG, call ": observer outside {-2, 0 .. N-1} (PK_OBSERVER_NONE: nothing would be hidden)");            \
+    EQW_CHECK_RANGES((h)->fail, call, weights, num_ranges);                                                                                  \
+    if (eqs_task_bound(m, samples) > EQ_TASKS_MAX) return (h)->fail(PK_E_INVALID_ARG, call ": m * ceil(samples / 64) must fit 32 bits: split the batch"); \
+    ON_DEVICE(h);                                                                                                                            \
+    FLUSH_READER(h);                                                                                                                         \
+    if ((m) == 0) return PK_OK
+
+int pk_table_equity_ranged_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce, const uint16_t *weights_d,
+                             uint32_t num_ranges, const uint16_t *range_of_d, int range_per_table, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d,
+                             uint32_t *accepted_d, uint8_t *status_d) {
+    EQW_TABLE_ENTER(h, m, observer, samples, weights_d, num_ranges, "pk_table_equity_ranged_d");
+    char *work = nullptr;
+    if (int rc = snap_staging(h, eqw_work_bytes(h->N, m, num_ranges), &work)) return rc;
+    return table_equity_ranged(h, tables_d, m, observer, samples, nonce, EqwRanges{weights_d, num_ranges, range_of_d, range_per_table ? 1 : 0},
+                               EqwOut{win_d, tie_d, share_d, accepted_d, status_d}, work);
+}
+
+int pk_table_equity_ranged(pk_handle *h, const int32_t *tables, size_t m, int observer, uint32_t samples, uint32_t nonce, const uint16_t *weights,
+                           uint32_t num_ranges, const uint16_t *range_of, int range_per_table, uint32_t *win, uint32_t *tie, uint64_t *share,
+                           uint32_t *accepted, uint8_t *status) {
+    EQW_TABLE_ENTER(h, m, observer, samples, weights, num_ranges, "pk_table_equity_ranged");
+    Stage g;
+    const int idx = g.in(tables, m * 4);
+    const int wt = g.in(num_ranges ? weights : nullptr, (size_t)num_ranges * EQW_HOLDINGS * 2);
+    const int ro = g.in(range_of, (range_per_table ? m : (size_t)1) * (size_t)h->N * 2);
+    const EqStagedOut out(g, h->N, m, win, tie, share, accepted, status);
+    const int work = g.add(eqw_work_bytes(h->N, m, num_ranges));
+    int rc = snap_staging(h, g.total, &g.base);
+    if (rc) return rc;
+    HIPCHK(h, g.upload(h->stream));
+    if ((rc = table_equity_ranged(h, g.at<int32_t>(idx), m, observer, samples, nonce,
+                                  EqwRanges{g.at<uint16_t>(wt), num_ranges, g.at<uint16_t>(ro), range_per_table ? 1 : 0}, eqw_out(out.at(g)), g.at<char>(work))))
+        return rc;
     HIPCHK(h, g.download(h->stream));
     return PK_OK;
 }

@@ -425,6 +425,40 @@ class VecGame:
         L.check(self._lib.pk_table_equity_sampled_d(self._h, self._dptr(tables_d), m, o, samples, nonce, self._dptr(win_d), self._dptr(tie_d),
                                                     self._dptr(share_d), self._dptr(samples_d), self._dptr(status_d)), self._h)
 
+    def equity_ranged(self, tables=None, observer=L.OBSERVER_ACTIVE, ranges=None, range_of=None, samples=1024, nonce=0):
+        """Sampled showdown equity of `tables` (all tables if None; indices may repeat) as `observer` (a seat or OBSERVER_ACTIVE) sees them,
+        where every other live seat draws its holding from a weighted range (pk_table_equity_ranged; definition: pokerl_hip.h "Ranged
+        sampled equity").  ranges: uint16 [1326] or [R, 1326], R <= 16; range_of: the row of each SEAT, [N] for all tables or [m, N] per
+        table (0xFFFF = uniform; None: uniform, or the one row where ranges is a single vector); the observer's own entry is ignored.  The
+        stream is the handle's seed, table id and `nonce`, as equity_sampled.  Returns a judger.RangedEquity of [m, N] / [m] arrays."""
+        from .judger import RangedEquity, check_ranges, check_samples
+        o = self._range_observer(observer)
+        samples, nonce = check_samples(samples, nonce)
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        n = self.num_players
+        w, r, ro, per = check_ranges(ranges, range_of, n, m)
+        win, tie, share = np.zeros((m, n), np.uint32), np.zeros((m, n), np.uint32), np.zeros((m, n), np.uint64)
+        count, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        L.check(self._lib.pk_table_equity_ranged(self._h, L.ptr(t), m, o, samples, nonce, L.ptr(w), r, L.ptr(ro), int(per), L.ptr(win), L.ptr(tie),
+                                                 L.ptr(share), L.ptr(count), L.ptr(status)), self._h)
+        return RangedEquity(win, tie, share, count, status, samples)
+
+    def equity_ranged_d(self, m=None, tables_d=None, observer=L.OBSERVER_ACTIVE, weights_d=None, num_ranges=0, range_of_d=None,
+                        range_per_table=False, samples=1024, nonce=0, win_d=None, tie_d=None, share_d=None, accepted_d=None, status_d=None):
+        """pk_table_equity_ranged_d: the same on device buffers (weights_d uint16 [num_ranges, 1326], range_of_d uint16 [N] or [m, N]; outputs
+        uint32 [m, N] win / tie, uint64 [m, N] share, uint32 [m] accepted, uint8 [m] status; any may be None), asynchronous on the handle's
+        stream.  m defaults to every table."""
+        from .judger import check_samples
+        o = self._range_observer(observer)
+        samples, nonce = check_samples(samples, nonce)
+        if not 0 <= int(num_ranges) <= L.EQW_MAX_RANGES:
+            raise ValueError('at most %d ranges per call' % L.EQW_MAX_RANGES)
+        m = self.num_tables if m is None else int(m)
+        L.check(self._lib.pk_table_equity_ranged_d(self._h, self._dptr(tables_d), m, o, samples, nonce, self._dptr(weights_d), int(num_ranges),
+                                                   self._dptr(range_of_d), int(bool(range_per_table)), self._dptr(win_d), self._dptr(tie_d),
+                                                   self._dptr(share_d), self._dptr(accepted_d), self._dptr(status_d)), self._h)
+
     def _range_observer(self, observer):
         """observer of equity_range: a seat or OBSERVER_ACTIVE / 'active'; ValueError otherwise (before any call)."""
         o = self._observer(observer)

@@ -339,6 +339,154 @@ def sampled_equity(hands, board=(), live=None, samples=4096, seed=DEFAULT_SEED, 
     return r
 
 
+# ---------------------------------------------------------------------------------------------- ranged sampled equity
+# Sampled equity where every hidden seat draws its HOLDING from a weighted range -- any seat count, any street (pk_equity_ranged; the
+# definition: include/pokerl_hip.h "Ranged sampled equity").  Attempts whose holdings collide are rejected, so the
+# counts are over the ACCEPTED attempts.
+class RangedEquity:
+    """Counts of one spot or of a batch over the accepted attempts ([N] or [m, N] arrays; `accepted`, `status` scalars or [m]; `samples` =
+    the attempts asked for).  `equity` = share / (720720 * accepted), nan where nothing was accepted; `acceptance` = accepted / samples.
+    Counts of calls with different nonces add exactly, `accepted` included."""
+
+    def __init__(self, win, tie, share, accepted, status, samples):
+        self.win, self.tie, self.share, self.accepted, self.status, self.samples = win, tie, share, accepted, status, samples
+
+    @property
+    def equity(self):
+        b = np.asarray(self.accepted, np.float64)[..., None] * float(L.EQ_SHARE_UNIT)
+        return np.divide(np.asarray(self.share, np.float64), b, out=np.full(np.shape(self.share), np.nan, np.float64), where=b > 0)
+
+    @property
+    def acceptance(self):
+        return np.asarray(self.accepted, np.float64) / float(self.samples)
+
+    def __getitem__(self, i):
+        return RangedEquity(self.win[i], self.tie[i], self.share[i], self.accepted[i], self.status[i], self.samples)
+
+    def __repr__(self):
+        return 'RangedEquity(accepted=%r of %r, status=%r, win=%r, tie=%r, equity=%r)' % (self.accepted, self.samples, self.status, self.win,
+                                                                                          self.tie, self.equity)
+
+
+def check_ranges(ranges, range_of, n, m, shared_ok=True):
+    """(weights uint16 [R, 1326] or None, R, range_of uint16 or None, per_spot) of a ranged-equity call; ValueError for a wrong shape or more
+    than 16 rows -- before any device call.  ranges: None, one [1326] vector or [R, 1326]; range_of: None (every hidden seat uniform; with
+    ONE row: every seat that row), [n] for every spot, or [m, n].  shared_ok False: an [n] vector is repeated to [m, n].  An entry that
+    names no row is not refused here: where its seat is hidden the SPOT reports EQ_BAD_CARD."""
+    w, r = None, 0
+    if ranges is not None:
+        w = np.ascontiguousarray(ranges, np.uint16)
+        if w.ndim == 1:
+            w = w.reshape(1, -1)
+        if w.ndim != 2 or w.shape[1] != L.EQ_HOLDINGS:
+            raise ValueError('ranges must have shape [1326] or [R, 1326]')
+        r = w.shape[0]
+        if r > L.EQW_MAX_RANGES:
+            raise ValueError('at most %d ranges per call' % L.EQW_MAX_RANGES)
+        if r == 0:
+            w = None
+    if range_of is None:
+        ro = np.zeros(n, np.int64) if r == 1 else None
+    else:
+        ro = np.asarray(range_of)
+        if ro.shape not in ((n,), (m, n)):
+            raise ValueError('range_of must have shape [N] or [m, N]')
+        if ((ro < 0) | (ro > 0xFFFF)).any():
+            raise ValueError('range_of entries must fit 16 bits')
+    per_spot = False
+    if ro is not None:
+        if ro.shape == (m, n) and (ro.ndim == 2):
+            per_spot = True
+        elif not shared_ok:
+            ro, per_spot = np.broadcast_to(ro, (m, n)), True
+        ro = np.ascontiguousarray(ro, np.uint16)
+    return w, r, ro, per_spot
+
+
+def ranged_equity_batch(holes, board, nboard, live, ranges=None, range_of=None, samples=4096, seed=DEFAULT_SEED, nonce=0, ids=None, device=0):
+    """pk_equity_ranged on host arrays: as sampled_equity_batch, but a live seat hides both cards or none, and a hidden seat p draws its
+    holding from row range_of[i, p] of `ranges` (uint16 [1326] or [R, 1326]; 0xFFFF or range_of None: uniform; an [N] vector serves every
+    spot).  Returns a RangedEquity of [m, N] / [m] arrays."""
+    holes = np.ascontiguousarray(holes, np.uint8)
+    if holes.ndim != 3 or holes.shape[2] != 2 or not (L.MIN_PLAYERS <= holes.shape[1] <= L.MAX_PLAYERS):
+        raise ValueError('holes must have shape [m, N, 2] with 2 <= N <= 16')
+    m, n = holes.shape[:2]
+    board = np.ascontiguousarray(board, np.uint8)
+    nboard = np.ascontiguousarray(nboard, np.uint8)
+    live = np.ascontiguousarray(live, np.uint16)
+    if board.shape != (m, 5) or nboard.shape != (m,) or live.shape != (m,):
+        raise ValueError('board must have shape [m, 5], nboard and live shape [m]')
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, np.uint32)
+        if ids.shape != (m,):
+            raise ValueError('ids must have shape [m]')
+    samples, nonce = check_samples(samples, nonce)
+    if m * ((samples + 63) // 64) > 0xFFFFFFFF:
+        raise ValueError('m * ceil(samples / 64) must fit 32 bits: split the batch')
+    w, r, ro, _ = check_ranges(ranges, range_of, n, m, shared_ok=False)
+    win, tie = np.zeros((m, n), np.uint32), np.zeros((m, n), np.uint32)
+    share = np.zeros((m, n), np.uint64)
+    count, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+    L.check(L.lib().pk_equity_ranged(int(device), n, m, L.ptr(holes), L.ptr(board), L.ptr(nboard), L.ptr(live), L.ptr(ids), samples,
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, nonce, L.ptr(w), r, L.ptr(ro), L.ptr(win), L.ptr(tie), L.ptr(share),
+                                     L.ptr(count), L.ptr(status)))
+    return RangedEquity(win, tie, share, count, status, samples)
+
+
+def ranged_equity_d(num_players, m, holes_d, board_d, nboard_d, live_d, samples, weights_d=None, num_ranges=0, range_of_d=None, ids_d=None,
+                    seed=DEFAULT_SEED, nonce=0, win_d=None, tie_d=None, share_d=None, accepted_d=None, status_d=None, device=0, stream=None):
+    """pk_equity_ranged_d: the same on device-resident buffers (device pointers as ints / c_void_p; weights_d uint16 [num_ranges, 1326],
+    range_of_d uint16 [m, N]; ids_d, range_of_d and the outputs may be None), asynchronous on `stream`."""
+    samples, nonce = check_samples(samples, nonce)
+    if not (L.MIN_PLAYERS <= int(num_players) <= L.MAX_PLAYERS):
+        raise ValueError('between 2 and 16 seats')
+    if not 0 <= int(num_ranges) <= L.EQW_MAX_RANGES:
+        raise ValueError('at most %d ranges per call' % L.EQW_MAX_RANGES)
+    L.check(L.lib().pk_equity_ranged_d(int(device), int(num_players), int(m), holes_d, board_d, nboard_d, live_d, ids_d, samples,
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, nonce, weights_d, int(num_ranges), range_of_d, win_d, tie_d, share_d,
+                                       accepted_d, status_d, stream))
+
+
+def ranged_equity(hands, board=(), live=None, ranges=None, range_of=None, samples=4096, seed=DEFAULT_SEED, nonce=0, device=0):
+    """One spot.  hands: per seat two cards (Card-likes / 'RS' strings / Card.value ints) or None = hidden: that seat draws its holding from
+    row range_of[seat] of `ranges`; board: 0 .. 5 known cards; live: the seats that show down (iterable of seat numbers or a bit mask;
+    default: EVERY seat).  Returns a RangedEquity with [N] arrays; raises ValueError for an invalid spot."""
+    hands = list(hands)
+    n = len(hands)
+    if not (L.MIN_PLAYERS <= n <= L.MAX_PLAYERS):
+        raise ValueError('between 2 and 16 seats')
+    board = list(board)
+    if len(board) > 5:
+        raise ValueError('at most five board cards')
+    holes = np.full((1, n, 2), UNKNOWN_CARD, np.uint8)
+    for p, h in enumerate(hands):
+        if h is None:
+            continue
+        h = list(h)
+        if len(h) != 2 or any(c is None for c in h):
+            raise ValueError('seat %d: two hole cards, or None for a hidden hand' % p)
+        holes[0, p] = [_card(c) for c in h]
+    b = np.zeros((1, 5), np.uint8)
+    b[0, :len(board)] = [_card(c) for c in board]
+    if live is None:
+        mask = (1 << n) - 1
+    elif isinstance(live, (int, np.integer)):
+        mask = int(live)
+    else:
+        mask = 0
+        for p in live:
+            if not 0 <= int(p) < n:
+                raise ValueError('live seat %r out of range' % (p,))
+            mask |= 1 << int(p)
+    if mask < 0 or mask >> n:
+        raise ValueError('live mask names seats >= %d' % n)
+    r = ranged_equity_batch(holes, b, np.array([len(board)], np.uint8), np.array([mask], np.uint16), ranges, range_of, samples, seed, nonce,
+                            device=device)[0]
+    if r.status:
+        raise ValueError('invalid spot: ' + equity_status_text(r.status))
+    return r
+
+
 # ---------------------------------------------------------------------------------------------- range equity
 # Exact hand strength against ONE hidden hand, post-flop: the hero's win / tie counts against every holding the opponent can have, and their
 # sum under a range of weights (pk_equity_range; the definition: include/pokerl_hip.h "Range equity", DESIGN.md section 3.3).

@@ -109,6 +109,17 @@ class Game:
             raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
         return r
 
+    def equity_ranged(self, observer=None, ranges=None, range_of=None, samples=1024, nonce=0):
+        """Sampled showdown equity of the table as `observer` sees it (None = the active seat) with every other live seat's holding drawn
+        from a weighted range (VecGame.equity_ranged): a judger.RangedEquity with [N] arrays.  Not in the reference."""
+        from ._lib import OBSERVER_ACTIVE
+        r = self._v.equity_ranged(observer=OBSERVER_ACTIVE if observer is None else observer, ranges=ranges, range_of=range_of, samples=samples,
+                                  nonce=nonce)[0]
+        if r.status:
+            from .judger import equity_status_text
+            raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
+        return r
+
     def equity_range(self, observer=None, weights=None):
         """Exact hand strength of `observer` (None = the active seat) against one hidden hand, post-flop (VecGame.equity_range): a
         judger.RangeEquity with [1326] arrays and the scalar `strength`.  Not in the reference."""

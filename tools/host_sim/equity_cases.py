@@ -16,6 +16,9 @@ The shapes are the smallest at which each mechanism of the kernels can break (do
   k_equity<N>      N = 2, 3, 9, 16; nb = 0 .. 5; folded seats, a lone live seat; grids of 1 and 2 with more tasks than waves; 64+ one-task
                    spots on a grid of 1 (take = 4); refused spots inside the batch;
   k_eqs<N>         N = 2, 6, 16; hidden hole cards up to 37 draws (three Philox blocks); samples 1, 63, 64, 65 and several tasks per spot; two nonces;
+  k_eqw<N, RC>     (ranged_cases, run beside all_cases by this program and by tests/test_equity_ranged_sim_host.py) N = 2, 3, 6, 16; the three LDS
+                   size classes (R = 0, 4, 16); H = 1 .. 16 hidden seats (1 .. 9 Philox blocks); dense, sparse, one-holding and dead ranges; attempts
+                   1, 65 and several tasks per spot on a grid of 1; a refused spot between good ones; the three new refusals; the table form;
   preparation      every status bit, the explicit and the table form; table indices -1, T and 2^31 - 1 (nothing is read: ASan's to check).
 
   equity_cases.py --exe <equity_sim> [--exe <another build>] [--quick] [--only <substring>] [--list] [--keep <dir>]
@@ -36,6 +39,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 import equity_range_spec as RS          # noqa: E402
+import equity_ranged_spec as WS         # noqa: E402
 import equity_sampled_spec as SS        # noqa: E402
 import equity_spec as ES                # noqa: E402
 import hist_spec as HS                  # noqa: E402
@@ -47,7 +51,7 @@ IN_FLIGHT, BAD_TABLE = 16, 32
 DTYPES = {"u8": np.uint8, "u16": np.uint16, "u32": np.uint32, "u64": np.uint64, "i32": np.int32}
 OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("win", "tie", "share", "samples", "status"),
            "range": ("agg", "win", "tie", "boards", "status"), "rvr": ("win", "tie", "tot", "boards", "status"),
-           "hist": ("hist", "void", "completions", "status")}
+           "hist": ("hist", "void", "completions", "status"), "ranged": ("win", "tie", "share", "accepted", "status")}
 
 
 class Case:
@@ -489,6 +493,116 @@ def sampled_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- ranged
+def ranged_case(name, n, specs, seed, grid, samples, weights=None, range_of=None, nonce=0, ids=None, lpt=None, quick=False, edit=None):
+    """specs as seat_spots; range_of [m, n] (None: every hidden seat uniform); weights [R, 1326] or None."""
+    holes, board, nboard, live = seat_spots(seed, n, specs)
+    m = len(specs)
+    ro = None if range_of is None else np.array(range_of, np.uint16).reshape(m, n)
+    if edit:
+        edit(holes, board, nboard, live, ro)
+    key = R.seed_key(WS.DEFAULT_SEED + seed)
+    w = None if weights is None else np.asarray(weights, np.uint16).reshape(-1, HOLDINGS)
+    arrays = {"N": ("u32", [n]), "m": ("u32", [m]), "grid": ("u32", [grid]), "samples": ("u32", [samples]), "nonce": ("u32", [nonce]),
+              "key0": ("u32", [key[0]]), "key1": ("u32", [key[1]]), "ids": ("u32", ids), "lpt": ("u32", None if lpt is None else [lpt]),
+              "R": ("u32", [0 if w is None else len(w)]), "weights": ("u16", w), "range_of": ("u16", ro),
+              "holes": ("u8", holes), "board": ("u8", board), "nboard": ("u8", nboard), "live": ("u16", live)}
+    return Case(name, "ranged", arrays,
+                lambda: WS.batch_equity(holes, board, nboard, live, samples, w, ro, per_spot=True, nonce=nonce, ids=ids, key=key), None, quick)
+
+
+def ranged_cases():
+    """The cases of k_eqw_cdf / k_eqw_prep / k_eqw<N, RC>; NOT part of all_cases() (tests/test_equity_sim_host.py pins that set)."""
+    cs = []
+    rng = np.random.default_rng(71)
+    four = WS.random_ranges(rng)                                      # dense, ~40 holdings, one holding, all zero
+    U = WS.UNIFORM
+    # two seats: hero against one hidden hand on every street, each row and the uniform one; a dead range (accepted 0, status 0); nothing
+    # hidden; a folded hidden seat (its 0xFF is simply in the pool)
+    two = [(4, None, (1,)), (0, None, (1,)), (3, None, (1,)), (5, None, (0,)), (5, None, (1,)), (2, None, ()), (4, 0b01, (1,)), (0, None, (0, 1))]
+    ro2 = [[U, 0], [U, 1], [U, U], [2, U], [U, 3], [0, 0], [0, 9], [1, 0]]
+    for s in (1, 65):
+        cs.append(ranged_case("ranged-N2-S%d-grid1" % s, 2, two, 72, 1, s, four, ro2, quick=True))
+    # several tasks per spot (512 attempts per task at the smallest lpt) on ONE workgroup, whose LDS the tasks before have used; two nonces
+    for nonce in (0, 1):
+        cs.append(ranged_case("ranged-N2-S1200-grid1-nonce%d" % nonce, 2, two[:4], 72, 1, 1200, four, ro2[:4], nonce=nonce, ids=[7, 7, 9, 2 ** 32 - 1],
+                              quick=(nonce == 0)))
+    # R = 0: no cumulative row in LDS at all (size class 0), range_of NULL
+    cs.append(ranged_case("ranged-N3-R0", 3, [(0, None, (1, 2)), (3, None, (0, 1, 2)), (5, 0b011, (1,))], 73, 1, 100, quick=True))
+    # six seats, the observer shown: H = 5, a mix of rows; a refused spot between good ones (a card twice)
+    six = [(0, None, (1, 2, 3, 4, 5)), (3, None, (1, 2, 3, 4, 5)), (4, 0b101101, (0, 2, 3, 5)), (5, None, (2,))]
+    ro6 = [[U, 0, 1, U, 0, 1], [U, 0, 0, 0, 0, 0], [1, U, 0, 0, U, U], [U, U, 1, U, U, U]]
+
+    def twice(holes, board, nboard, live, ro):
+        holes[1, 0, 1] = board[1, 0]
+    cs.append(ranged_case("ranged-N6", 6, six, 74, 2, 200, four, ro6, quick=True))
+    cs.append(ranged_case("ranged-N6-refused-between", 6, six[:3], 74, 1, 70, four, ro6[:3], edit=twice, quick=True))
+    # sixteen seats, everything hidden: H = 16, 17 words, 9 Philox blocks; sixteen rows, every one used (size class 16).  Row r lives on the
+    # three holdings among the cards 3r .. 3r + 2, so sixteen holdings never collide and pre-flop every attempt is accepted; with the rows
+    # handed out the other way round as well, with board cards dead (some rows lose holdings), and H = 15 with dense rows (nearly all rejected)
+    sixteen = np.zeros((16, HOLDINGS), np.uint16)
+    for r in range(16):
+        for a, b in ((3 * r, 3 * r + 1), (3 * r, 3 * r + 2), (3 * r + 1, 3 * r + 2)):
+            sixteen[r, b * (b - 1) // 2 + a] = int(rng.integers(1, 65536))
+    all16 = tuple(range(16))
+    cs.append(ranged_case("ranged-N16-H16-R16", 16, [(0, None, all16), (0, None, all16), (3, None, all16), (5, 0x00FF, all16)], 75, 1, 130, sixteen,
+                          [list(range(16)), list(range(15, -1, -1)), list(range(16)), [U] * 8 + list(range(8))], quick=True))
+    dense = np.zeros((9, HOLDINGS), np.uint16)
+    for r in range(9):
+        dense[r] = rng.integers(0, 300, HOLDINGS) * (rng.random(HOLDINGS) < 0.6)
+    cs.append(ranged_case("ranged-N16-H15-R9-dense", 16, [(3, None, all16[1:])], 78, 1, 70, dense, [[r % 9 for r in range(16)]]))
+
+    # the refusals: a half-hidden live seat, a row >= R at a hidden seat (and the same entry at a shown seat: ignored), a card twice, nb = 6, no
+    # live seat, a byte that is no card -- good spots at both ends
+    def bits(holes, board, nboard, live, ro):
+        holes[1, 1, 1] = ES.UNKNOWN                                   # seat 1 shows one card
+        ro[2, 1] = 4                                                  # R = 4: no such row, seat 1 hidden
+        ro[3, 0] = 4                                                  # ... seat 0 shown: not read
+        holes[4, 0, 1] = board[4, 2]
+        nboard[5] = 6
+        live[6] = 0
+        holes[7, 0, 0] = 0x0E
+    status_specs = [(5, None, (1,)), (5, None, ()), (4, None, (1,)), (4, None, (1,)), (5, None, (1,)), (5, None, (1,)), (5, None, (1,)), (3, None, (1,)), (5, None, (1,))]
+    cs.append(ranged_case("ranged-status-bits", 2, status_specs, 76, 1, 64, four, [[U, 0]] * 9, edit=bits, quick=True))
+    for observer, per in ((-2, 0), (1, 1)):
+        w = table_world(77, 6, 5)
+        key = R.seed_key(WS.DEFAULT_SEED)
+        m = len(w["tables"])
+        ro = np.array([[0, 1, U, 0, 1, 2]] * (m if per else 1), np.uint16)
+        if per:
+            ro[1] = [1, 1, 1, 1, 1, 1]
+        arrays = dict(table_arrays(w), m=("u32", [m]), grid=("u32", [1]), samples=("u32", [65]), nonce=("u32", [3]), key0=("u32", [key[0]]),
+                      key1=("u32", [key[1]]), id_base=("u32", [1000]), observer=("i32", [observer]), R=("u32", [4]), weights=("u16", four),
+                      range_of=("u16", ro), per_spot=("u32", [per]))
+
+        def expect(w=w, observer=observer, key=key, ro=ro, per=per):
+            holes, board, nboard, live = WS.table_spots(w["deck"], w["states"], w["turn"], w["active"], observer)
+            tabs = w["tables"].tolist()
+            # range_of goes by SPOT: evaluate per spot, then pick (a shared vector: by table is the same)
+            if not per:
+                r = WS.batch_equity(holes, board, nboard, live, 65, four, ro[0], nonce=3, ids=[1000 + t for t in range(w["T"])], key=key)
+                return table_expect(w, {k: r[k] for k in OUTPUTS["ranged"]}, ("win", "tie", "share"), "accepted")
+            good = [(i, t) for i, t in enumerate(tabs) if 0 <= t < w["T"]]
+            idx = [t for _, t in good]
+            r = WS.batch_equity(holes[idx], board[idx], nboard[idx], live[idx], 65, four, ro[[i for i, _ in good]], per_spot=True, nonce=3,
+                                ids=[1000 + t for t in idx], key=key)
+            out = {k: np.zeros((len(tabs),) + r[k].shape[1:], r[k].dtype) for k in OUTPUTS["ranged"]}
+            for i, t in enumerate(tabs):
+                if not 0 <= t < w["T"]:
+                    out["status"][i] = BAD_TABLE
+            for j, (i, t) in enumerate(good):
+                for k in out:
+                    out[k][i] = r[k][j]
+                if w["inflight"][t]:
+                    out["status"][i] |= IN_FLIGHT
+                    for k in ("win", "tie", "share", "accepted"):
+                        out[k][i] = 0
+            return out
+        cs.append(Case("ranged-table-form-observer%d" % observer, "ranged", arrays, expect, quick=True))
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -503,7 +617,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

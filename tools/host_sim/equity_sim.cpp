@@ -1,4 +1,4 @@
-// Dev-only: the REAL equity kernels -- k_equity<N>, k_eqs<N>, k_eqr, k_rvr, k_hist and their one-lane-per-spot preparation kernels, the text of
+// Dev-only: the REAL equity kernels -- k_equity<N>, k_eqs<N>, k_eqr, k_rvr, k_hist, k_eqw<N, RC> and their preparation kernels, the text of
 // pokerl_amd/csrc/pk_equity*.hip -- run on the CPU as workgroups of 8 waves x 64 lanes (wg_shim.h: a fibre per lane, every collective and
 // barrier a checked rendezvous, garbage LDS before every workgroup, PK_IDX active).  One case per run: the case file names the family, the
 // spots, the weights / bins / samples, the grid and which outputs are wanted; the preparation kernel runs, then the main kernel, and every
@@ -9,7 +9,7 @@
 //   equity_sim <case file> <out file>
 // Case file: lines "name dtype count" (dtype u8 u16 u32 u64 i32) each followed by a line of `count` decimal values, and
 // "family <name>" / "outputs <name> ..." lines.  Out file: the same array format.
-// -DPK_ES_ONLY=1 .. 5: a build of ONE family (equity, sampled, range, rvr, hist), so that a test can compile the five side by side.
+// -DPK_ES_ONLY=1 .. 6: a build of ONE family (equity, sampled, range, rvr, hist, ranged), so that a test can compile them side by side.
 #ifndef PK_ES_ONLY
 #define PK_ES_ONLY 0
 #endif
@@ -28,6 +28,12 @@
 #endif
 #if PK_ES_HAS(5)
 #include "../../pokerl_amd/csrc/pk_equity_hist.hip"
+#endif
+#if PK_ES_HAS(6)
+#if !PK_ES_HAS(2)
+#include "../../pokerl_amd/csrc/pk_equity_sampled.hip"  // (the ranged family splits its tasks with pk::eqs_lpt)
+#endif
+#include "../../pokerl_amd/csrc/pk_equity_ranged.hip"
 #endif
 
 #include <chrono>
@@ -267,13 +273,51 @@ void run_hist(Case &c, const uint32_t *tab) {
 }
 #endif
 
+
+#if PK_ES_HAS(6)
+// k_eqw_cdf, k_eqw_prep, k_eqw<N, RC>: RC is the size class of the case's R, as eqw_launch picks it
+template <int N, int RC>
+void run_ranged_class(const uint32_t *tab, const uint32_t *cum, const uint64_t *desc, const EqwOut &out, const EqsStream &rng, uint32_t R, unsigned grid,
+                      uint32_t ntasks, uint32_t nch, uint32_t per) {
+    pk_sim::launch(grid, EQ_BLOCK, [&] { k_eqw<N, RC>(tab, cum, desc, out, rng, R, ntasks, nch, per); });
+}
+template <int N>
+void run_ranged(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const uint32_t R = (uint32_t)c.num("R", 0);
+    EqwPrepArgs a{};
+    const bool tbl = table_form(c, N, m, a.t);
+    if (!tbl) { a.s.holes = c.need<uint8_t>("holes", m * N * 2); a.s.board = c.need<uint8_t>("board", m * 5); a.s.nboard = c.need<uint8_t>("nboard", m); a.s.live = c.need<uint16_t>("live", m); }
+    const int per_spot = (int)c.num("per_spot", tbl ? 0 : 1);
+    const EqwRanges ranges{R ? c.need<uint16_t>("weights", (size_t)R * EQW_HOLDINGS) : nullptr, R, c.arr<uint16_t>("range_of", (per_spot ? m : (size_t)1) * N), per_spot};
+    EqsStream rng{(uint32_t)c.num("key0"), (uint32_t)c.num("key1"), (uint32_t)c.num("nonce"), (uint32_t)c.num("samples"), (uint32_t)c.num("id_base", 0), c.arr<uint32_t>("ids", m)};
+    EqwOut out{};
+    out.win = c.output<uint32_t>("win", "u32", m * N); out.tie = c.output<uint32_t>("tie", "u32", m * N); out.share = c.output<uint64_t>("share", "u64", m * N);
+    out.accepted = c.output<uint32_t>("accepted", "u32", m); out.status = c.output<uint8_t>("status", "u8", m);
+    Work<uint32_t> cum((size_t)R * EQW_HOLDINGS);
+    Work<uint64_t> desc(m * (size_t)eqw_desc_words(N));
+    if (R) pk_sim::launch(R, 64, [&] { k_eqw_cdf(ranges.weights, cum.p, R); });
+    a.rng = rng; a.r = ranges; a.out = out; a.desc = desc.p; a.N = N; a.observer = (int)c.num("observer", PK_OBSERVER_ACTIVE); a.m = m;
+    if (tbl) pk_sim::launch(prep_grid(m, EQW_PREP_BLOCK), EQW_PREP_BLOCK, [&] { k_eqw_prep<true>(a); });
+    else pk_sim::launch(prep_grid(m, EQW_PREP_BLOCK), EQW_PREP_BLOCK, [&] { k_eqw_prep<false>(a); });
+    const long long lpt_case = c.num("lpt", 0);
+    const uint32_t S = rng.samples, per = 64u * (uint32_t)(lpt_case ? lpt_case : pk::eqs_lpt(m, S)), nch = (S + per - 1) / per, ntasks = (uint32_t)m * nch;
+    const int rc = pk::eqw_class(R);
+    printf("tasks %u (%u per spot), size class %d\n", ntasks, nch, rc);
+    if (rc == 0) run_ranged_class<N, 0>(tab, cum.p, desc.p, out, rng, R, grid, ntasks, nch, per);
+    else if (rc == 8) run_ranged_class<N, 8>(tab, cum.p, desc.p, out, rng, R, grid, ntasks, nch, per);
+    else run_ranged_class<N, 16>(tab, cum.p, desc.p, out, rng, R, grid, ntasks, nch, per);
+}
+#endif
+
 }  // namespace
 
 int main(int argc, char **argv) {
     if (argc != 3) die("usage: equity_sim <case file> <out file>");
     Case c(argv[1]);
-    // the function-local __shared__ arrays of the five main kernels (the preparation kernels have none)
-    const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj"});
+    // the function-local __shared__ arrays of the six main kernels (the preparation kernels have none)
+    const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "5k_eqwILi"});
     Work<uint32_t> tab(EVAL7_TAB_WORDS);
     for (int i = 0; i < EVAL7_TAB_WORDS; ++i) tab.p[i] = eval7_tab_entry((uint32_t)i);
     const auto t0 = std::chrono::steady_clock::now();
@@ -302,6 +346,13 @@ int main(int argc, char **argv) {
 #endif
 #if PK_ES_HAS(5)
     if (c.family == "hist") { run_hist(c, tab.p); ran = true; }
+#endif
+#if PK_ES_HAS(6)
+    if (c.family == "ranged") {
+        if (N == 2) run_ranged<2>(c, tab.p); else if (N == 3) run_ranged<3>(c, tab.p); else if (N == 6) run_ranged<6>(c, tab.p); else if (N == 16) run_ranged<16>(c, tab.p);
+        else die("k_eqw<N, RC>: this build has N = 2, 3, 6, 16");
+        ran = true;
+    }
 #endif
     if (!ran) die("family " + c.family + ": not in this build");
     c.write(argv[2]);

@@ -11,6 +11,8 @@ from pokerl_amd import build
 from isa_report import split_asm
 
 def symbols(tree, src, flags):
+    if not os.path.exists(os.path.join(tree, "pokerl_amd", "csrc", src)):       # a translation unit <git-rev> does not have yet: all its symbols are new
+        return None
     r = subprocess.run([build.hipcc()] + flags + ["--cuda-device-only", "-S", os.path.join(tree, "pokerl_amd", "csrc", src), "-o", "-"], capture_output=True, text=True)
     if r.returncode:
         sys.exit(r.stderr)
@@ -27,6 +29,9 @@ if __name__ == "__main__":
         res = list(ex.map(lambda j: symbols(j[0], j[2], j[3]), [(tree,) + u for u in units for tree in (old, ROOT)]))
     compared = same = 0
     for (unit, _, _), a, b in zip(units, res[0::2], res[1::2]):
+        if a is None:
+            print("%-32s %3d symbols, new: %s does not have it" % (unit, len(b), rev))
+            continue
         differ = sorted(k for k in a.keys() & b.keys() if a[k] != b[k])
         compared += len(a.keys() | b.keys()); same += len(a.keys() & b.keys()) - len(differ)
         print("%-32s %3d symbols, %3d identical" % (unit, len(a.keys() | b.keys()), len(a.keys() & b.keys()) - len(differ)))

@@ -69,6 +69,8 @@ def lib():
     L.orc_compare_rankings.restype = C.c_int
     L.orc_philox4x32_10.argtypes = [_u32p, _u32p, _u32p]
     L.orc_deck.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, _u8p]
+    L.orc_pick_action.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint, C.c_int]
+    L.orc_pick_action.restype = C.c_int
     L.orc_eval7_digest.argtypes = [C.c_int, C.c_int, _u64p, _u64p]
     L.orc_eval7_prefix.argtypes = [C.c_int, C.c_int, _u32p]
     L.orc_eval7_prefix.restype = C.c_size_t

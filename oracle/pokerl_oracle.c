@@ -82,6 +82,7 @@ void orc_deck(uint64_t seed, uint32_t table_id, uint64_t hand_serial, uint8_t ou
 static int pick_action(uint64_t seed, const table_t *t, int policy, unsigned mask) {
     if (policy == 1) return MV_ALL_IN;
     if (policy == 2) return ((mask >> MV_CALL) & 1) ? MV_CALL : (((mask >> MV_CHECK) & 1) ? MV_CHECK : MV_ALL_IN); /* call agent, rng_spec.py */
+    if (policy == 14) { unsigned m2 = mask & 0x3Eu; mask = m2 ? m2 : (mask & 0x7Eu); } /* deep caller (test infrastructure only), rng_spec.py */
     uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)}, o[4];
     uint64_t q = t->step_serial >> 3;
     int j = (int)(t->step_serial & 7);
@@ -93,6 +94,15 @@ static int pick_action(uint64_t seed, const table_t *t, int policy, unsigned mas
     for (int a = 0; a < MV_NUM; ++a)
         if ((mask >> a) & 1) { if (k == 0) return a; --k; }
     return -1;
+}
+
+/* the agents' rule on a caller-given (table id, step serial, valid mask): what tests hold rng_spec.pick_action to */
+int orc_pick_action(uint64_t seed, uint32_t table_id, uint64_t step_serial, unsigned mask, int policy) {
+    table_t t;
+    memset(&t, 0, sizeof t);
+    t.table_id = table_id;
+    t.step_serial = step_serial;
+    return pick_action(seed, &t, policy, mask);
 }
 
 /* ------------------------------------------------------------------ numpy reductions */

@@ -45,7 +45,7 @@ void orc_valid_actions(const orc_game *g, uint8_t *mask);
 /* the same for seat `player` of every table (player < 0: the active player), get_valid_actions(player) game.py:339-383 */
 void orc_valid_actions_for(const orc_game *g, int player, uint8_t *mask);
 
-/* Synthetic agents of rng_spec.py: policy 0 random, 1 all-in, 2 call. Writes the action each table would take now. */
+/* Synthetic agents of rng_spec.py: policy 0 random, 1 all-in, 2 call, 14 the deep caller (test infrastructure). Writes the action each table would take now. */
 void orc_pick_actions(const orc_game *g, int policy, int32_t *actions);
 
 /* K lockstep steps with in-library agents; auto_reset != 0 resets finished games (dealer 0).
@@ -94,6 +94,8 @@ size_t orc_eval7_prefix(int a, int b, uint32_t *out);
 /* Spec helpers exposed for tests */
 void orc_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 void orc_deck(uint64_t seed, uint32_t table_id, uint64_t hand_serial, uint8_t out[52]);
+/* policy 0 random, 1 all-in, 2 call, 14 the deep caller of rng_spec.py (test infrastructure); -1 on an empty mask */
+int orc_pick_action(uint64_t seed, uint32_t table_id, uint64_t step_serial, unsigned mask, int policy);
 double orc_np_sum(const double *a, int n);
 
 #ifdef __cplusplus

@@ -32,6 +32,12 @@ RNG seeds" is defined by THIS counter-based spec instead:
       call agent   (policy 2): CALL (2) if it is valid, else CHECK (1) if it is valid, else ALL_IN (6) -- the passive
       "calling station"; CALL is invalid exactly when high_bet >= credit (game.py:376), CHECK when high_bet != 0 (:375).
 
+  deep caller (policy 14, POLICY_DEEP): TEST INFRASTRUCTURE ONLY -- a never-fold caller that drives hands to late streets with raises and
+      side pots; the product refuses the code (it is no PK_POLICY_*).  reduced = valid_mask & 0b0111110 (FOLD and ALL_IN dropped); if that
+      is empty, reduced = valid_mask & 0b1111110 (FOLD dropped only).  The action is the random agent's own draw over `reduced`: same
+      Philox block, same step_serial, n = popcount(reduced).  A pure function of (seed, table id, step_serial, valid mask), so a caller
+      computes it from what the product exposes.
+
   per-seat agents (PokerGameEnv with a list of agents, envs/game_env.py:13-18): seat p plays policy nibble
   (seat_policies >> 4p) & 15 of a 64-bit word; 15 = the caller supplies that seat's actions.
 
@@ -52,6 +58,7 @@ DEFAULT_SEED = 0x706F6B65726C  # 'pokerl'
 POLICY_RANDOM = 0
 POLICY_ALLIN = 1
 POLICY_CALL = 2
+POLICY_DEEP = 14       # test infrastructure only: no product entry point accepts it
 POLICY_EXTERNAL = 15
 
 
@@ -113,12 +120,21 @@ def deck_permutation(seed, table_id, hand_serial, ndraws=52):
     return perm + remaining
 
 
+def deep_mask(valid_mask_bits):
+    """The mask POLICY_DEEP draws from: no FOLD and no ALL_IN; ALL_IN only where nothing else is left."""
+    return (valid_mask_bits & 0b0111110) or (valid_mask_bits & 0b1111110)
+
+
 def pick_action(seed, table_id, step_serial, valid_mask_bits, policy=POLICY_RANDOM):
     """Action of the synthetic agents. valid_mask_bits: bit a set iff action a valid."""
     if policy == POLICY_ALLIN:
         return 6
     if policy == POLICY_CALL:
         return 2 if (valid_mask_bits >> 2) & 1 else (1 if (valid_mask_bits >> 1) & 1 else 6)
+    if policy == POLICY_DEEP:
+        valid_mask_bits = deep_mask(valid_mask_bits)
+    elif policy != POLICY_RANDOM:
+        raise ValueError("no synthetic agent has policy %r" % (policy,))
     q, j = step_serial >> 3, step_serial & 7
     w = philox4x32_10((table_id & MASK32, q & MASK32, STREAM_ACTION, (q >> 32) & MASK32), seed_key(seed))
     r = (w[j >> 1] >> (16 * (j & 1))) & 0xFFFF

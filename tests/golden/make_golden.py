@@ -124,6 +124,25 @@ class Table:
             return out
 
         self.game.step = counted_step
+        # content counters (the deep sets' meta): showdowns at the river among three or more seats, hands that pay three or more amounts
+        self.river_showdowns_3way, self.hands_paying_3_amounts, self._ending = 0, 0, None
+        real_end, real_setup = self.game.end_hand, self.game.setup_hand
+
+        def counted_end():
+            g = self.game
+            live = int(np.sum((g.player_states != PlayerState.BROKEN) & (g.player_states != PlayerState.FOLDED)))
+            self.river_showdowns_3way += int(g.turn == 4 and live >= 3)      # (next_turn has counted the river's end, game.py:561-564)
+            self._ending = g.bets + g.pending_bets                           # what every seat has put in, before game.py:457
+            real_end()
+
+        def counted_setup():
+            if self._ending is not None:        # called by end_hand (game.py:539): payoffs are net of the seats' own bets (game.py:531)
+                got = self.game.payoffs + self._ending
+                self.hands_paying_3_amounts += int(len(set(got[got != 0].tolist())) >= 3)
+                self._ending = None
+            real_setup()
+
+        self.game.end_hand, self.game.setup_hand = counted_end, counted_setup
 
     def _absorb_showdowns(self):
         # every showdown evaluates exactly num_players hands in seat order (game.py:488-489)
@@ -302,11 +321,16 @@ def game_trajectory(n, policy, seed, tables, steps, table_id_base=0, cfg=None, f
     if digest_every:
         meta["digest_every"] = digest_every
         meta["digests"] = digests
+    meta.update(_content(ts))
     if hand_cap:
         meta["hand_cap"] = hand_cap
         meta["reference_hands_in_its_longest_step"] = max_hands_in_step
     out["meta"] = np.array(json.dumps(meta))
     return out
+
+
+def _content(ts):
+    return dict(river_showdowns_3way=sum(t.river_showdowns_3way for t in ts), hands_paying_3_amounts=sum(t.hands_paying_3_amounts for t in ts))
 
 
 # --------------------------------------------------------------------------- PokerGameEnv trajectories
@@ -362,6 +386,7 @@ def env_trajectory(n, policy, opp_policy, seed, tables, steps, table_id_base=0, 
     out["reset_idx"] = np.array(reset_idx, np.int32).reshape(-1, 2)
     meta = dict(kind="env", n=n, policy=policy, opp_policy=opp_policy, seed=seed, tables=tables,
                 steps=steps, table_id_base=table_id_base, cfg=cfg)
+    meta.update(_content(ts))
     out["meta"] = np.array(json.dumps(meta))
     return out
 
@@ -573,6 +598,27 @@ DIGEST_SETS = {
     "digest_n15_random": (15, R.POLICY_RANDOM, SEED, 16, 800, 0, None),
     "digest_n16_random": (16, R.POLICY_RANDOM, SEED, 16, 800, 0, None),
 }
+# Deep hands: the never-fold caller of rng_spec.py (POLICY_DEEP, test infrastructure) on per-seat fractional stacks -- raises on several
+# streets, short stacks all-in on different streets, multi-way river showdowns that pay several different amounts.  First dealer N - 1,
+# table ids that wrap 2^32 inside the set.  (n, seed, tables, steps)
+def deep_cfg(n, reverse=False):
+    return dict(start_credits=[7.5 * (p + 1) + 0.25 * (p % 3) for p in range(n)][::-1 if reverse else 1], big_blind=2, small_blind=1)
+
+
+DEEP_BASE = 2 ** 32 - 3
+DEEP_GAME_SETS = {"game_n%d_deep" % n: (n, 0xDEE9 + n, 6 if n <= 9 else 4, 200 if n <= 9 else 250) for n in (2, 3, 6, 9, 13, 16)}
+# seat 0 deep against call agents: every hand an N-way river showdown raised on every street; and against a different agent per seat.
+# PokerGameEnv.step never returns early for a seat 0 that goes broke while an OPPONENT's step ends the hand (game_env.py:49-52 then plays
+# the opponents until the game is over), and call agents alone need thousands of hands for that: the product ends such a step with
+# PK_TERR_ENV_CAP, a documented divergence no fixture can hold.  So seeds and lengths are chosen (by scanning with the oracle) such
+# that no env.step of the set plays 8 192 Game.steps, and at sixteen seats the stacks are dealt in REVERSE seat order (seat 0 the deepest):
+# with seat 0 the shortest of sixteen no seed gives more than three such steps.  (n, opponents, seed, tables, steps, stacks reversed)
+DEEP_ENV_SETS = {
+    "env_n4_deep_vs_call": (4, R.POLICY_CALL, 0xDEE9 + 104, 6, 150, False),
+    "env_n9_deep_vs_call": (9, R.POLICY_CALL, 0xDEE9 + 109 + 72000, 4, 110, False),
+    "env_n16_deep_vs_call": (16, R.POLICY_CALL, 0xDEE9 + 116 + 11000, 4, 85, True),
+    "env_n6_deep_vs_mixed": (6, [R.POLICY_CALL, R.POLICY_RANDOM, R.POLICY_CALL, R.POLICY_ALLIN, R.POLICY_CALL], 0xDEE9 + 206, 6, 150, False),
+}
 ENV_SETS = {
     "env_n4_random": (4, R.POLICY_RANDOM, R.POLICY_RANDOM, SEED, 8, 200, 0, None),
     "env_n6_random": (6, R.POLICY_RANDOM, R.POLICY_RANDOM, SEED, 6, 200, 0, None),
@@ -623,6 +669,24 @@ def main():
             out = game_trajectory(n, pol, seed, tables, steps, base, cfg)
             np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
             print(name, "resets:", len(out["reset_idx"]), "hands:", int(out["post_hand_serial"].max()))
+    for name, (n, seed, tables, steps) in DEEP_GAME_SETS.items():
+        if want(name):
+            out = game_trajectory(n, R.POLICY_DEEP, seed, tables, steps, DEEP_BASE, deep_cfg(n), dealer=n - 1)
+            meta = json.loads(str(out["meta"]))
+            assert meta["river_showdowns_3way"] > 0 or n == 2, meta
+            assert meta["hands_paying_3_amounts"] > 0 or n == 2, meta
+            assert not out["errs"].any() and not (out["actions"] == 0).any()
+            np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
+            print(name, "resets:", len(out["reset_idx"]), "hands:", int(out["post_hand_serial"].max()), "river showdowns 3+-way:",
+                  meta["river_showdowns_3way"], "hands paying 3+ amounts:", meta["hands_paying_3_amounts"])
+    for name, (n, opp, seed, tables, steps, reverse) in DEEP_ENV_SETS.items():
+        if want(name):
+            out = env_trajectory(n, R.POLICY_DEEP, opp, seed, tables, steps, DEEP_BASE, deep_cfg(n, reverse))
+            meta = json.loads(str(out["meta"]))
+            assert meta["river_showdowns_3way"] > 0 and meta["hands_paying_3_amounts"] > 0, meta
+            np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
+            print(name, "episodes:", int(out["done"].sum()), "river showdowns 3+-way:", meta["river_showdowns_3way"],
+                  "hands paying 3+ amounts:", meta["hands_paying_3_amounts"])
     for name, (n, pol, seed, tables, steps, base, cfg, dealer) in ODD_SETS.items():
         if want(name):
             out = game_trajectory(n, pol, seed, tables, steps, base, cfg, dealer=dealer)

@@ -156,7 +156,8 @@ GAME_SETS = ["game_n2_random", "game_n6_random", "game_n9_random", "game_n6_alli
              "game_n5_zero_blinds", "game_n4_sb_gt_bb_fractional", "game_n7_blinds_gt_stacks", "game_n8_mixed_allin",
              "game_n6_serial_hi", "game_n8_argsort_tie", "game_n9_argsort_tie", "game_n6_hand_cap",
              "game_n12_random", "game_n15_random", "game_n14_mixed_allin",
-             "game_n16_random", "game_n16_mixed_allin", "game_n16_argsort_tie"]
+             "game_n16_random", "game_n16_mixed_allin", "game_n16_argsort_tie",
+             "game_n2_deep", "game_n3_deep", "game_n6_deep", "game_n9_deep", "game_n13_deep", "game_n16_deep"]   # the never-fold caller, rng_spec POLICY_DEEP
 DIGEST_SETS = ["digest_n2_random", "digest_n6_random", "digest_n9_random", "digest_n9_allin", "digest_n6_shard1",
                "digest_n6_shard7", "digest_n15_random", "digest_n16_random"]
 VIEW_SETS = ["views_n6_random", "views_n3_percredits", "views_n13_random", "views_n16_random"]
@@ -164,4 +165,5 @@ ALIAS_SETS = ["views_alias_n6_random", "views_alias_n3_percredits"]   # a StateV
 ENV_SETS = ["env_n4_random", "env_n6_random", "env_n6_vs_allin", "env_n2_random", "env_n5_percredits",
             "env_n9_random_hi_base", "env_n3_big_blinds_vs_allin", "env_n3_vs_call", "env_n4_mixed_opponents",
             "env_n6_mixed_percredits", "env_n2_call_vs_call", "env_n11_random", "env_n12_mixed_opponents",
-            "env_n16_mixed_opponents"]
+            "env_n16_mixed_opponents",
+            "env_n4_deep_vs_call", "env_n9_deep_vs_call", "env_n16_deep_vs_call", "env_n6_deep_vs_mixed"]         # seat 0 the never-fold caller

@@ -2,6 +2,7 @@
 import numpy as np
 
 import pokerl_amd
+from oracle import rng_spec as R
 from pokerl_amd import _lib as L
 
 
@@ -12,6 +13,7 @@ class HipBackend:
                                               table_id_base=table_id_base)
         self.g = self.env.game
         self.T, self.N = tables, n
+        self.seed, self.base = seed, table_id_base
 
     @classmethod
     def from_meta(cls, meta):
@@ -32,7 +34,18 @@ class HipBackend:
         return flags, terr
 
     def pick_actions(self, policy):
+        if policy == R.POLICY_DEEP:
+            return self.deep_actions()
         return self.g.pick_actions(policy)
+
+    def deep_actions(self):
+        """The never-fold caller of rng_spec.py (POLICY_DEEP: test infrastructure, the product knows no such policy), computed on the host
+        from the handle's own valid_actions and step_serial getters -- so a replay that holds these picks to recorded actions checks both
+        getters on the states the caller reaches."""
+        onehot, _ = self.g.get_valid_actions()
+        serial = self.g.step_serial
+        bits = (np.asarray(onehot) != 0).astype(np.int64) @ (1 << np.arange(7, dtype=np.int64))
+        return np.array([R.pick_action(self.seed, (self.base + t) % 2 ** 32, int(serial[t]), int(bits[t]), R.POLICY_DEEP) for t in range(self.T)], np.int32)
 
     def env_reset(self, mask=None, opp_policy=0):
         self.env.opp_policy = opp_policy

@@ -17,7 +17,9 @@ CAPS = O.ERR_HAND_CAP | O.ERR_ENV_CAP
 PS_BROKEN = 4
 KINDS = ("default", "ladder", "top_seat")
 RESUMED = "resumed"            # the fourth configuration: default, with the RNG streams resumed just below 2^32 (matrix_config)
-ALL_KINDS = KINDS + (RESUMED,)
+DEEP = "deep"                  # the fifth configuration: the never-fold caller of rng_spec.py (POLICY_DEEP) on per-seat fractional stacks (matrix_config)
+ALL_KINDS = KINDS + (RESUMED, DEEP)
+DEEP_SHAPE_SEATS = (2, 6, 9, 13, 16)             # seat counts at which the deep game_step / env_step cases also run under `spread` and `part`
 RESUMED_SEATS = (2, 6, 9, 13, 16)
 RESUMED_SERIALS = (2 ** 32 - 2, 2 ** 35 - 5)     # (hand_serial, step_serial): the action-block index step_serial >> 3 is 2^32 - 1
 # How pk_create lays the tables out over wavefronts (PK_TPB; None: its own rule, tpb_rule).  spread: what a caller gets -- one table per wave at
@@ -27,6 +29,8 @@ WAVE_SHAPES = {"spread": None, "full": 64, "part": 8}
 # steps per family in the matrix (a case is to take a few seconds); tests/test_seat_matrix_host.py checks the caps at the same budgets
 K_GAME, K_ENV, K_MULTI, K_PLAYED = 40, 15, 15, 40
 K_ROLLOUT = 48                 # the fused rollout family: launches of 16, 25 and 7 steps -- the first two long enough for k_rollout_tab / k_rollout_allin_tab
+K_DEEP_GAME = 60               # lockstep steps of the deep configuration's game_step families
+K_DEEP = 30                    # lockstep deep steps before the rollout_from_deep, snapshot and equity families take over
 BUDGETS = (1, 3)               # hand ends / Game.steps per launch of the bounded forms
 
 
@@ -39,6 +43,13 @@ def k_of(family, kind, N):
     """Steps of `family` (a driver's name) in configuration `kind`.  The resumed configuration needs three tables in four to end two hands
     inside the run, so that hand_serial 2^32 is dealt; tests/test_seat_matrix_host.py holds the oracle half to that at these very K, and they
     suffice as they are (random agents end a hand within a few steps) -- a family that missed it would get a longer K for RESUMED here."""
+    if kind == DEEP:
+        # game_step: long enough for 40 river hand ends among three or more seats and 40 hands that pay three or more amounts at every seat
+        # count (the pre-flight's floors).  env_step: PokerGameEnv.step never returns for a seat 0 that goes broke while an opponent's step
+        # ends the hand with two or more call agents left (game_env.py:49-52; the product ends it with PK_TERR_ENV_CAP after 8 192 steps), and
+        # from eight seats on the first such step comes after six env.steps of the deep configuration's tables.
+        return {"game_step": K_DEEP_GAME, "game_step_async": K_DEEP_GAME, "env_step": K_ENV if N <= 7 else 6,
+                "played": K_DEEP, "rollout": K_ROLLOUT}[family]
     return {"game_step": K_GAME, "game_step_async": K_GAME, "env_step": K_ENV, "rollout": K_ROLLOUT, "rollout_call": k_call(N)}[family]
 
 
@@ -89,6 +100,9 @@ def matrix_config(kind, N, T=T_MATRIX, shape="spread"):
     inside the batch, and seat N - 1 wherever a family takes a seat.  resumed: default with the serials set to RESUMED_SERIALS before the
     first reset -- that reset deals hand_serial 2^32 - 2, the first hand end 2^32 - 1 (a lone table's stock of four decks then spans the
     carry into the high counter word), the second 2^32; the action-block index crosses 2^32 after five Game.steps.
+    deep: per-seat stacks 7.5 (p + 1) + 0.25 (p % 3), the never-fold caller POLICY_DEEP (test infrastructure: the device is handed the
+    oracle's actions wherever another configuration lets it pick), first dealer N - 1, table ids that wrap inside the batch -- raises on
+    every street, short stacks all-in on different streets, multi-way river showdowns that pay several different amounts.
     `shape`: the wave shape the drivers demand of every handle (WAVE_SHAPES; the caller sets it with use_shape)."""
     cfg = dict(kind=kind, T=T, N=N, start=100, bb=2, sb=1, seed=0x5EA7 * 1000003 + 7919 * N + ALL_KINDS.index(kind), base=0, dealer=0, policy=0, top=None,
                shape=shape, serials=None)
@@ -98,9 +112,37 @@ def matrix_config(kind, N, T=T_MATRIX, shape="spread"):
         cfg.update(base=2 ** 32 - 100, top=N - 1)
     elif kind == RESUMED:
         cfg.update(serials=RESUMED_SERIALS)
+    elif kind == DEEP:
+        cfg.update(start=deep_stacks(N), policy=R.POLICY_DEEP, dealer=N - 1, base=2 ** 32 - 100)
     elif kind != "default":
         raise ValueError(kind)
     return cfg
+
+
+def deep_stacks(N):
+    return [7.5 * (p + 1) + 0.25 * (p % 3) for p in range(N)]
+
+
+def env_config(kind, N, T=T_MATRIX, shape="spread"):
+    """matrix_config for the env families.  deep: the same stacks dealt in REVERSE seat order, seat 0 the deepest -- with seat 0 the
+    shortest stack against call agents it is broke within three env.steps at eight or more seats, which the env never returns from
+    (k_of); the deepest seat lasts six."""
+    cfg = matrix_config(kind, N, T, shape)
+    if kind == DEEP:
+        cfg["start"] = cfg["start"][::-1]
+    return cfg
+
+
+def is_deep(cfg):
+    return cfg["policy"] == R.POLICY_DEEP
+
+
+def device_picks(g, buf, cfg, a):
+    """The actions of this step in a device buffer: the in-kernel agent's own pick, or -- the deep caller is no product policy -- the oracle's."""
+    if is_deep(cfg):
+        buf.upload(np.ascontiguousarray(a, np.int32))
+    else:
+        g.pick_actions_d(buf, cfg["policy"])
 
 
 def multi_seats(cfg):
@@ -114,6 +156,14 @@ def multi_seats(cfg):
         pols[N - 2] = 1
         return pols, sorted({1, N - 1} if N > 2 else {1})
     return pols, list(range(2, N, 3)) or [1]
+
+
+def deep_multi_seats(N, mixed):
+    """(policy per opponent seat, caller-played seats) of the deep configuration's multi-agent cases: every seat the deep caller, played by
+    the CALLER (the product knows no such policy; the oracle plays nibble 14) -- or, `mixed`, in-kernel call agents at the odd seats, from
+    eight seats on at seat 1 alone: two call agents left over by the deep seats, with seat 0 broke, never end their game (k_of)."""
+    pols = [2 if mixed and s % 2 and (N <= 7 or s == 1) else R.POLICY_DEEP for s in range(1, N)]
+    return pols, [s for s in range(1, N) if pols[s - 1] == R.POLICY_DEEP]
 
 
 def in_kernel_seats(cfg):
@@ -315,8 +365,8 @@ def game_step(HB, cfg, K, snap_every=40, views_every=1):
     for tr in game_step_trace(cfg, K):
         s, a, fo, eo, over, o = tr["s"], tr["a"], tr["fo"], tr["eo"], tr["over"], tr["o"]
         where = where_of(cfg, "step %d" % s)
-        ha.g.pick_actions_d(act_a, policy); ha.g.step_d(act_a, fl_a, te_a, auto_reset=True)
-        hb.g.pick_actions_d(act_b, policy); hb.g.step_d(act_b, fl_b, te_b)
+        device_picks(ha.g, act_a, cfg, a); ha.g.step_d(act_a, fl_a, te_a, auto_reset=True)
+        device_picks(hb.g, act_b, cfg, a); hb.g.step_d(act_b, fl_b, te_b)
         ha.g.sync(); hb.g.sync()
         assert np.array_equal(act_a.download(np.int32, T), a) and np.array_equal(act_b.download(np.int32, T), a), (where, "in-kernel agent picks")
         assert_flags(fl_b.download(np.uint8, T), te_b.download(np.uint8, T), fo, eo, False, where + " (step_d)")
@@ -390,7 +440,7 @@ def game_step_async(HB, cfg, K, max_hands=1):
         if off or (tr["eo"] & 2).any():
             off = True
             break
-        hc.g.pick_actions_d(act_c, policy); hc.g.sync()
+        device_picks(hc.g, act_c, cfg, oc.pick_actions(policy) if is_deep(cfg) else None); hc.g.sync()      # (deep: idle tables get the twin's next action)
         off = call(act_c.download(np.int32, T), max_hands, where_of(cfg, "step %d" % tr["s"]))
     act_c.upload(np.full(T, -1, np.int32))                # drain: idle tables get "no step"
     if not off:
@@ -464,7 +514,9 @@ def env_step(cfg, opp, K, passes, B=1, exact_batches=True):
     D = 17 + 3 * N
     where = where_of(cfg, "opp=%s K=%d passes=%d sub-batches=%d" % (opp, K, passes, B))
     want, rows, acts, o, wstats = env_want(cfg, opp, K)
-    rew, done, hand, terr, obs, ready = bufs = [DeviceBuffer(n) for n in (T * 8, T, T, T, T * D * 8, T)]
+    rew, done, hand, terr, obs, ready, act = bufs = [DeviceBuffer(n) for n in (T * 8, T, T, T, T * D * 8, T, T * 4)]
+    deep = is_deep(cfg)                              # seat 0's actions are uploaded (actions_d non-NULL) instead of picked in the kernel
+    A = np.stack(acts).astype(np.int32)
     out = lambda: (rew.download(np.float64, T), done.download(np.uint8, T), hand.download(np.uint8, T), terr.download(np.uint8, T),
                    obs.download(np.float64, T * D).reshape(T, D))
     st = dict(delivered=0, sub=0, launches=0)
@@ -487,7 +539,9 @@ def env_step(cfg, opp, K, passes, B=1, exact_batches=True):
     env.reset()
     sync = []
     for k in range(K):
-        L.check(lib.pk_env_step_fused_d(g._h, None, seat0, env.opp_policy, 1, rew.ptr, done.ptr, hand.ptr, terr.ptr, obs.ptr), g._h)
+        if deep:
+            act.upload(A[k])
+        L.check(lib.pk_env_step_fused_d(g._h, act.ptr if deep else None, 0 if deep else seat0, env.opp_policy, 1, rew.ptr, done.ptr, hand.ptr, terr.ptr, obs.ptr), g._h)
         g.sync()
         w = out()
         assert_delivered(w[:4], want[k], where + " fused %d" % k)
@@ -512,7 +566,9 @@ def env_step(cfg, opp, K, passes, B=1, exact_batches=True):
         # (a table whose seat 0 is broke with the game not over plays up to PK_ENV_STEP_CAP = 8 192 opponent steps per env.step: with a
         #  budget of `passes` Game.steps per launch that is ~8 192 / passes launches for ONE env.step -- slow, not stuck)
         assert st["launches"] < max(200, 2 * 8192 // passes + 50) * K * nb, (where, "no progress")
-        env.step_async_d(None, rew.ptr, done.ptr, hand.ptr, terr.ptr, obs.ptr, ready.ptr, max_passes=passes, seat0_policy=seat0)
+        if deep:                                     # action count[t] of the table's own sequence; -1 once it has delivered its K steps
+            act.upload(np.where(count < K, A[np.minimum(count, K - 1), np.arange(T)], -1).astype(np.int32))
+        env.step_async_d(act.ptr if deep else None, rew.ptr, done.ptr, hand.ptr, terr.ptr, obs.ptr, ready.ptr, max_passes=passes, seat0_policy=0 if deep else seat0)
         g.sync()
         r = ready.download(np.uint8, T) != 0
         if nb > 1:                                   # one range was launched; outputs are complete inside the DELIVERED range only
@@ -527,10 +583,17 @@ def env_step(cfg, opp, K, passes, B=1, exact_batches=True):
         w = out()
         assert_delivered(tuple(x[idx] for x in w), tuple(x[count[idx], idx] for x in W), where + " bounded launch %d" % st["launches"])
         st["delivered"] += len(idx)
+        if deep:                                     # a table past its K steps was given -1: back at once, untouched, and not counted
+            past = r & (count >= K)
+            assert (w[3][past] == L.TERR_INVALID_ACTION).all(), (where, "a table given no action", np.nonzero(past)[0][:4].tolist())
         count[r] += 1
-    env.step_async_d(None, rew.ptr, done.ptr, hand.ptr, terr.ptr, obs.ptr, ready.ptr, max_passes=0, seat0_policy=seat0)
+    if deep:
+        act.upload(np.full(T, -1, np.int32))
+    env.step_async_d(act.ptr if deep else None, rew.ptr, done.ptr, hand.ptr, terr.ptr, obs.ptr, ready.ptr, max_passes=0, seat0_policy=0 if deep else seat0)
     g.sync()
     assert (ready.download(np.uint8, T) != 0).all(), where
+    if deep:                                         # every table has made exactly its K env.steps: the oracle's state
+        GU.assert_snap(_env_snapshot(env), o.snapshot(), where + " bounded, drained")
     env.close()
     for b in bufs:
         b.free()
@@ -547,7 +610,7 @@ def _env_snapshot(env):
 # ------------------------------------------------------------------ 3. one agent per seat, some seats played by the caller
 def multi_want(cfg, pols, K):
     """env_want with one policy per opponent seat, stacked: ([K, T] reward, done, hand, terr), stats."""
-    want, _, _, _, stats = env_want(cfg, list(pols), K, seat0=0)
+    want, _, _, _, stats = env_want(cfg, list(pols), K, seat0=cfg["policy"] if is_deep(cfg) else 0)
     return [np.stack([w[i] for w in want]) for i in range(4)], stats
 
 
@@ -621,6 +684,7 @@ def env_multi(cfg, pols, external, K, passes, cap=6000):
     D = 17 + 3 * N
     where = where_of(cfg, "pols=%s external=%s K=%d passes=%d" % (pols, external, K, passes))
     W, _ = multi_want(cfg, pols, K)
+    seat0 = cfg["policy"] if is_deep(cfg) else 0
     agents = [(lambda st: 0) if s in external else [pokerl_amd.RandomAgent(), pokerl_amd.AllInAgent(), pokerl_amd.CallAgent()][pols[s - 1]]
               for s in range(1, N)]
     env = env_of(agents, cfg)
@@ -659,7 +723,7 @@ def env_multi(cfg, pols, external, K, passes, cap=6000):
         serial = g.step_serial
         bits = (rows[:, 3:10] > 0).astype(np.uint32) @ (1 << np.arange(7, dtype=np.uint32))
         for t in np.nonzero((r == 1) | (r == 2))[0]:
-            pol = 0 if r[t] == 1 else pols[int(w[t]) - 1]
+            pol = seat0 if r[t] == 1 else pols[int(w[t]) - 1]
             a[t] = R.pick_action(seed, base + int(t), int(serial[t]), int(bits[t]), pol)
     env.end_multi()
     env.close()
@@ -713,8 +777,9 @@ def rollout_call(HB, cfg, K):
     return co
 
 
-def rollout_then_lockstep(HB, cfg, K, lock=6, split=True):
-    """Fused rollout (deferred launches of mixed lengths when `split`) and a few lockstep steps against the oracle."""
+def rollout_then_lockstep(HB, cfg, K, lock=6, split=True, lock_policy=None):
+    """Fused rollout (deferred launches of mixed lengths when `split`) and a few lockstep steps against the oracle.  lock_policy: the agent
+    of the lockstep part where it is not the rollout's (R.POLICY_DEEP: the never-fold caller; the backend takes the oracle's actions)."""
     policy = cfg["policy"]
     o, h = oracle_of(cfg), backend_of(HB, cfg)
     o.reset(dealer=cfg["dealer"]); h.reset(dealer=cfg["dealer"])
@@ -731,7 +796,7 @@ def rollout_then_lockstep(HB, cfg, K, lock=6, split=True):
     assert co.tolist() == ch.tolist(), where
     GU.assert_snap(h.snapshot(), o.snapshot(), where + " rollout")
     for s in range(lock):
-        a = o.pick_actions(policy)
+        a = o.pick_actions(policy if lock_policy is None else lock_policy)
         fo, eo = o.step(a)
         fh, eh = h.step(a)
         assert np.array_equal(fo, fh) and np.array_equal(eo, eh), where
@@ -743,11 +808,67 @@ def rollout_then_lockstep(HB, cfg, K, lock=6, split=True):
     return cfg["T"] * (K + lock)
 
 
-def played(HB, cfg, K, extra_call=0):
-    """(backend, oracle) after reset, a K-step rollout of the configuration's agents and `extra_call` steps of the call agents (which
-    bring tables past the flop where the configuration's own agents end every hand at once), state compared."""
+def deep_lockstep(h, o, cfg, K):
+    """K lockstep steps of the deep caller on a backend (pk_step_d with the oracle's actions uploaded, pk_reset_d of finished games; None:
+    the oracle alone) and the oracle, flags and terr compared at every step, every state byte at the end.  Returns the tables standing
+    past the flop with three or more seats in the hand."""
+    T = cfg["T"]
+    if h is not None:
+        from pokerl_amd import _lib as L
+        from pokerl_amd.hipmem import DeviceBuffer
+        act, fl, te = bufs = [DeviceBuffer(n) for n in (T * 4, T, T)]
+    for s in range(K):
+        a = o.pick_actions(cfg["policy"])
+        fo, eo = o.step(a)
+        assert not (eo & 2).any(), where_of(cfg, "deep lockstep step %d: game.py:473" % s)
+        over = over_of(fo, eo)
+        if over.any():
+            o.reset(mask=over)
+        if h is not None:
+            act.upload(a)
+            h.g.step_d(act, fl, te); h.g.sync()
+            assert_flags(fl.download(np.uint8, T), te.download(np.uint8, T), fo, eo, False, where_of(cfg, "deep lockstep step %d" % s))
+            h.g.reset_d(fl, L.FLAG_GAME_OVER)
+            if (eo & 4).any():
+                h.g.reset_d(te, L.TERR_HAND_CAP)
+    snap = o.snapshot()
+    if h is not None:
+        for b in bufs:
+            b.free()
+        GU.assert_snap(h.snapshot(), snap, where_of(cfg, "after %d deep lockstep steps" % K))
+    return int(((snap["turn"] >= 1) & (np.isin(snap["states"], (1, 2, 3)).sum(axis=1) >= 3)).sum())
+
+
+def rollout_from_deep(HB, cfg, K, K_roll=K_ROLLOUT):
+    """K lockstep deep steps, then the fused rollout of the CALL agents for K_roll steps in deferred launches (16 / 25 / 7 at 48): the rollout
+    kernels (k_rollout_call, and the table-evaluator variants where the seat count selects them) finish hands whose pots were built over
+    several streets, with all-in and broke seats.  Counters and every state byte against the oracle.  Returns (tables mid-hand past the
+    flop among three or more seats when the rollout starts, the counters)."""
     o, h = oracle_of(cfg), backend_of(HB, cfg)
     o.reset(dealer=cfg["dealer"]); h.reset(dealer=cfg["dealer"])
+    where = where_of(cfg, "rollout from deep tables")
+    deep_tables = deep_lockstep(h, o, cfg, K)
+    co, err = o.rollout(K_roll, 2, True)
+    assert err == 0, where
+    k1 = K_roll // 3
+    h.g.rollout(k1, 2, True, True, counters=False)
+    h.g.rollout(K_roll - k1 - 7, 2, True, True, counters=False)
+    ch = h.rollout(7, 2, True)
+    assert co.tolist() == ch.tolist(), (where, co.tolist(), ch.tolist())
+    GU.assert_snap(h.snapshot(), o.snapshot(), where)
+    h.g.close()
+    return deep_tables, co
+
+
+def played(HB, cfg, K, extra_call=0):
+    """(backend, oracle) after reset, a K-step rollout of the configuration's agents and `extra_call` steps of the call agents (which
+    bring tables past the flop where the configuration's own agents end every hand at once), state compared.  deep: K lockstep steps of
+    the deep caller instead (deep_lockstep) -- tables mid-hand past the flop with all-in and broke seats."""
+    o, h = oracle_of(cfg), backend_of(HB, cfg)
+    o.reset(dealer=cfg["dealer"]); h.reset(dealer=cfg["dealer"])
+    if is_deep(cfg):
+        deep_lockstep(h, o, cfg, K)
+        return h, o
     played_oracle(cfg, K, extra_call, o)
     h.rollout(K, cfg["policy"], True)
     if extra_call:
@@ -760,6 +881,9 @@ def played_oracle(cfg, K, extra_call=0, o=None):
     if o is None:
         o = oracle_of(cfg)
         o.reset(dealer=cfg["dealer"])
+    if is_deep(cfg):
+        deep_lockstep(None, o, cfg, K)
+        return o
     o.rollout(K, cfg["policy"], True)
     if extra_call:
         o.rollout(extra_call, 2, True)

@@ -746,6 +746,13 @@ def test_bad_arguments_are_reported_not_fatal(HB):
     g = pokerl_amd.VecGame(4, num_players=2)
     assert lib.pk_get_f64(g._h, 9, None) == L.PK_E_INVALID_ARG
     assert lib.pk_rollout(g._h, 5, 7, 1, 1, None) == L.PK_E_INVALID_ARG     # unknown policy
+    # 14 is the test suites' own never-fold caller (oracle/rng_spec.py POLICY_DEEP): no product policy -- refused, nothing changed
+    g.reset()
+    before = g.save()
+    picks = np.full(4, -7, np.int32)
+    assert lib.pk_pick_actions(g._h, 14, L.ptr(picks)) == L.PK_E_INVALID_ARG and (picks == -7).all()
+    assert lib.pk_rollout(g._h, 5, 14, 1, 1, None) == L.PK_E_INVALID_ARG
+    assert np.array_equal(g.save(), before)
     with pytest.raises(ValueError):
         g.reset(mask=np.ones(3, np.uint8))
 
@@ -870,10 +877,11 @@ def test_random_configurations_vs_oracle(HB, O):
     """Seeded fuzz over odd configurations (zero / fractional blinds, small blind above big blind, blinds larger than
     the stacks, per-seat stacks from 0.5 to 1e6, every N, table ids anywhere in 2^32, any first dealer): fused rollout
     and a few lockstep steps against the oracle (which tests/golden/fuzz_oracle_vs_reference.py checks against the
-    imported reference on the same kind of configurations)."""
+    imported reference on the same kind of configurations).  In one configuration in three the lockstep part is played by the never-fold
+    caller of oracle/rng_spec.py (POLICY_DEEP; drawn from a generator of its own: the configurations are the ones of before)."""
     import random
     import seat_matrix as M
-    rng = random.Random(99)
+    rng, deep_rng = random.Random(99), random.Random(1999)
     stacks = [0.5, 1, 2, 3, 5, 10, 37.5, 100, 1000, 1e6]
     blinds = [0, 0.25, 0.5, 1, 2, 3, 7.5, 40]
     # configurations 0 .. 41 are the 42 of before (same seed stream, N = 2 .. 15); three appended ones bring seat count 16 in
@@ -884,7 +892,7 @@ def test_random_configurations_vs_oracle(HB, O):
         seed, base, dealer = rng.getrandbits(63), rng.getrandbits(32) & 0xFFFFF000, rng.randrange(N)
         T = rng.choice([65, 128, 300])
         cfg = dict(kind="cfg %d" % i, T=T, N=N, start=start, bb=bb, sb=sb, seed=seed, base=base, dealer=dealer, policy=policy)
-        M.rollout_then_lockstep(HB, cfg, 120, lock=10, split=False)
+        M.rollout_then_lockstep(HB, cfg, 120, lock=10, split=False, lock_policy=M.R.POLICY_DEEP if deep_rng.random() < 1 / 3 else None)
 
 
 def test_streaming_evaluator(HB, O):

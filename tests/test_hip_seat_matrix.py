@@ -13,7 +13,11 @@ two sub-batches.  Configurations per case: default, ladder (N-way showdowns with
 wrap inside the batch, seat N - 1 wherever the family takes a seat) -- seat_matrix.matrix_config; tests/test_seat_matrix_host.py shows on the
 CPU that each of them contains what it is there for and stays below the caps.  A fourth configuration, resumed (RNG streams resumed so that
 hand_serial and the action-block index step_serial >> 3 both cross 2^32 inside the run), has cases of its own: full waves (plus the lone
-table of game_step and env_step, whose deals come from a stock of four decks) at 2, 6, 9, 13 and 16 seats."""
+table of game_step and env_step, whose deals come from a stock of four decks) at 2, 6, 9, 13 and 16 seats.  A fifth, deep (the never-fold
+caller of oracle/rng_spec.py on per-seat fractional stacks: raises on every street, all-ins on different streets, multi-way river
+showdowns that pay several amounts; the device is handed the oracle's actions), runs every family at every seat count on full waves,
+game_step and env_step also under `spread` and `part` at 2, 6, 9, 13 and 16 seats, and rollout_from_deep: the call agents' fused rollout
+finishing such hands."""
 import pytest
 
 import seat_matrix as M
@@ -45,22 +49,38 @@ def game_step_async(HB, N, shape="spread", kinds=M.KINDS):
             assert st["drained"] and st["async_steps"] > 0 and st["rows"] == st["async_steps"], (kind, T, budget, st)
 
 
+def env_opps(kind, N):
+    """The opponents' policy of the env families, one run each.  deep: call agents (every hand an N-way river showdown raised on every
+    street), and random agents up to six seats (more of them fold too often to see late streets)."""
+    return {"ladder": (1,), M.DEEP: (2, 0) if N <= 6 else (2,)}.get(kind, (0,))
+
+
 def env_step(HB, N, shape="spread", kinds=M.KINDS):
     for kind in kinds:
         K = M.k_of("env_step", kind, N)
-        opp = 1 if kind == "ladder" else 0
-        for T, passes in [(M.T_MATRIX, b) for b in M.BUDGETS] + [(1, M.BUDGETS[-1])] * (shape == "spread" or kind == M.RESUMED):
-            st = M.env_step(M.matrix_config(kind, N, T, shape), opp, K, passes)
-            assert st["delivered"] == T * K, (kind, T, st)
+        for opp in env_opps(kind, N):
+            for T, passes in [(M.T_MATRIX, b) for b in M.BUDGETS] + [(1, M.BUDGETS[-1])] * (shape == "spread" or kind == M.RESUMED):
+                st = M.env_step(M.env_config(kind, N, T, shape), opp, K, passes)
+                assert st["delivered"] == T * K, (kind, T, st)
 
 
 def env_batches(HB, N, shape="spread", kinds=M.KINDS):
     for kind in kinds:
-        st = M.env_step(M.matrix_config(kind, N, M.T_BATCHES, shape), 1 if kind == "ladder" else 0, M.K_ENV, 3, B=2)
-        assert st["sub"] == 1 and st["delivered"] == M.T_BATCHES * M.K_ENV, (kind, st)
+        K = M.k_of("env_step", kind, N)
+        for opp in env_opps(kind, N):
+            st = M.env_step(M.env_config(kind, N, M.T_BATCHES, shape), opp, K, 3, B=2)
+            assert st["sub"] == 1 and st["delivered"] == M.T_BATCHES * K, (kind, st)
 
 
 def env_multi(HB, N, shape="spread", kinds=M.KINDS):
+    if kinds == (M.DEEP,):
+        for mixed in (False, True):             # every seat played by the caller by the deep rule; then in-kernel call agents among them
+            for T, passes in [(M.T_MATRIX, b) for b in M.BUDGETS] + [(1, M.BUDGETS[0])] * (shape == "spread"):
+                cfg = M.matrix_config(M.DEEP, N, T, shape)
+                pols, external = M.deep_multi_seats(N, mixed)
+                st = M.env_multi(cfg, pols, external, M.K_MULTI, passes)
+                assert st["delivered"] == T * M.K_MULTI and (not external or st["yields"] > 0), (mixed, T, st)
+        return
     for kind in kinds:
         for T, passes in [(M.T_MATRIX, b) for b in M.BUDGETS] + [(1, M.BUDGETS[0])] * (shape == "spread"):
             cfg = M.matrix_config(kind, N, T, shape)
@@ -90,21 +110,35 @@ def rollout(HB, N, shape="spread", kinds=M.KINDS):
         assert M.rollout_then_lockstep(HB, M.matrix_config(kind, N, shape=shape), K, lock=10, split=True) == M.T_MATRIX * (K + 10)
 
 
+def rollout_from_deep(HB, N, shape="spread", kinds=(M.DEEP,)):
+    """K_DEEP lockstep steps of the deep caller, then the call agents' fused rollout (launches of 16, 25 and 7 steps) finishes the hands."""
+    for kind in kinds:
+        deep_tables, c = M.rollout_from_deep(HB, M.matrix_config(kind, N, shape=shape), M.k_of("played", kind, N))
+        assert deep_tables > 0 or N == 2, (kind, deep_tables)
+        assert c[0] == M.T_MATRIX * M.K_ROLLOUT and c[1] > 0 and c[2] > 0, (kind, c)
+
+
+def played_k(kind, N):
+    return M.k_of("played", kind, N) if kind == M.DEEP else M.K_PLAYED
+
+
 def snapshots(HB, N, shape="spread", kinds=M.KINDS):
     for kind in kinds:
-        M.snapshots(HB, M.matrix_config(kind, N, shape=shape), M.K_PLAYED, extra_call=M.extra_call(kind, N), observer=N - 1 if kind == "top_seat" else "active")
+        M.snapshots(HB, M.matrix_config(kind, N, shape=shape), played_k(kind, N), extra_call=M.extra_call(kind, N), observer=N - 1 if kind == "top_seat" else "active")
 
 
 def equity(HB, N, shape="spread", kinds=M.KINDS):
     for kind in kinds:
-        st = M.equity(HB, M.matrix_config(kind, N, shape=shape), M.K_PLAYED, extra_call=M.extra_call(kind, N),
-                      observer={"default": -2, "ladder": -1, "top_seat": N - 1}[kind])
+        st = M.equity(HB, M.matrix_config(kind, N, shape=shape), played_k(kind, N), extra_call=M.extra_call(kind, N),
+                      observer={"default": -2, "ladder": -1, "top_seat": N - 1, M.DEEP: -2}[kind])
         assert st["tables"] == M.EQUITY_FIRST and st["samples"] == 65 * M.EQUITY_FIRST, (kind, st)
 
 
 FAMILIES = [game_step, game_step_async, env_step, env_batches, env_multi, rollout_call, snapshots, equity]
 PART_FAMILIES = [rollout, game_step, env_step]
 RESUMED_FAMILIES = [rollout, rollout_call, game_step, game_step_async, env_step]
+DEEP_FAMILIES = [game_step, game_step_async, env_step, env_batches, env_multi, rollout_from_deep, snapshots, equity]
+DEEP_SHAPE_FAMILIES = [game_step, env_step]
 
 
 def _cases():
@@ -120,6 +154,12 @@ def _cases():
         if N in M.RESUMED_SEATS:
             for f in RESUMED_FAMILIES:
                 yield "%d-%s-full-resumed" % (N, f.__name__), N, f, "full", (M.RESUMED,)
+        for f in DEEP_FAMILIES:
+            yield "%d-%s-full-deep" % (N, f.__name__), N, f, "full", (M.DEEP,)
+        if N in M.DEEP_SHAPE_SEATS:
+            for shape in ("spread", "part"):
+                for f in DEEP_SHAPE_FAMILIES:
+                    yield "%d-%s-%s-deep" % (N, f.__name__, shape), N, f, shape, (M.DEEP,)
 
 
 CASES = list(_cases())

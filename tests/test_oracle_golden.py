@@ -48,6 +48,34 @@ def test_deck_spec_c_vs_python():
             assert R.deck_permutation(seed, tid, hs, ndraws=k)[:k] == perm[:k]
 
 
+def test_deep_policy_c_vs_python():
+    """POLICY_DEEP (rng_spec.py: the never-fold caller the deep fixtures and the deep matrix configuration are played by) in its C and
+    Python forms: every non-empty valid mask, serials from zero, around the 2^32 boundary of the action-block index step_serial >> 3
+    (step_serial 2^35) and around step_serial 2^32, table ids at both ends.  The pick is never FOLD, ALL_IN only where the mask leaves
+    nothing else, and it is the random agent's own draw over the reduced mask."""
+    L = O.lib()
+    serials = list(range(40)) + list(range(2 ** 35 - 24, 2 ** 35 + 24)) + list(range(2 ** 32 - 12, 2 ** 32 + 12)) + [2 ** 64 - 1, 2 ** 63 + 5]
+    checked = 0
+    for seed, tid in ((R.DEFAULT_SEED, 0), (2 ** 63 + 5, 2 ** 32 - 1), (7, 65537)):
+        for s in serials[::1 if tid == 0 else 3]:
+            with pytest.raises(AssertionError):                           # FOLD alone (no game state offers it): nothing to draw from, in both forms
+                R.pick_action(seed, tid, s, 1, R.POLICY_DEEP)
+            assert L.orc_pick_action(seed, tid, s, 1, R.POLICY_DEEP) == -1
+            for mask in range(2, 128):
+                a = R.pick_action(seed, tid, s, mask, R.POLICY_DEEP)
+                assert L.orc_pick_action(seed, tid, s, mask, R.POLICY_DEEP) == a, (seed, tid, s, mask)
+                reduced = R.deep_mask(mask)
+                assert a != 0 and (reduced >> a) & 1 and (a != 6 or not mask & 0b0111110), (mask, a)
+                assert a == R.pick_action(seed, tid, s, reduced, R.POLICY_RANDOM) == L.orc_pick_action(seed, tid, s, reduced, R.POLICY_RANDOM)
+                checked += 1
+    assert checked == 126 * 190
+    for pol in (R.POLICY_RANDOM, R.POLICY_ALLIN, R.POLICY_CALL):          # the existing agents through the same entry point
+        for mask in range(1, 128):
+            assert L.orc_pick_action(R.DEFAULT_SEED, 3, 2 ** 35 - 1, mask, pol) == R.pick_action(R.DEFAULT_SEED, 3, 2 ** 35 - 1, mask, pol)
+    with pytest.raises(ValueError):
+        R.pick_action(R.DEFAULT_SEED, 0, 0, 0x7f, 13)
+
+
 def test_np_sum_order_matches_numpy():
     L = O.lib()
     rng = np.random.default_rng(5)

@@ -124,6 +124,65 @@ def test_caps_and_content(kind, N):
           % (kind, N, fig["game_capped"] / T, fig["env_capped"] / T, fig["multi_capped"] / T, fig))
 
 
+DEEP_FLOOR = 40         # deep: river hand ends among three or more seats, and hands that pay three or more amounts, in the game_step run
+
+
+@pytest.mark.parametrize("N", M.SEATS)
+def test_deep_caps_and_content(N):
+    """The deep configuration (the never-fold caller of rng_spec.py) is there for hands the other agents do not produce: in the oracle
+    half of its game_step run at least DEEP_FLOOR hand ends come at the river among three or more live seats (N = 2: at the river), at
+    least DEEP_FLOOR hands pay three or more distinct amounts (N >= 3), and one raise after the flop falls per ten tables; no table of
+    any family's run -- a lone table included -- meets a cap or game.py:473; the env families deliver finished episodes and hand ends
+    with a non-zero reward; the multi-agent runs end below the caps; the rollout, snapshot and equity families start from tables past
+    the flop."""
+    cfg = M.matrix_config(M.DEEP, N)
+    T = cfg["T"]
+    assert cfg["base"] + T > 2 ** 32 > cfg["base"] and cfg["dealer"] == N - 1 and len(set(cfg["start"])) == N
+    K_GAME = M.k_of("game_step", M.DEEP, N)
+    fig = dict(river_3way=0, paid_3=0, max_paid=0, raises_after_flop=0, allin_after_flop=0, game_resets=0, ends_by_street=[0, 0, 0, 0])
+    for tr in M.game_step_trace(cfg, K_GAME, before=True):
+        assert not tr["eo"].any(), (tr["s"], "a cap, an invalid action or game.py:473 in the game_step run")
+        assert not (tr["a"] == 0).any(), "the deep caller folded"
+        was, ended = tr["was"], (tr["fo"] & 2) != 0
+        live = np.isin(was["states"], (1, 2, 3)).sum(axis=1)                   # seats in the hand: active, called or all-in
+        fig["river_3way"] += int((ended & (was["turn"] == 3) & (live >= min(N, 3))).sum())
+        for street in range(4):
+            fig["ends_by_street"][street] += int((ended & (was["turn"] == street)).sum())
+        paid = M.seats_paid(tr)
+        fig["paid_3"] += int((paid >= 3).sum()); fig["max_paid"] = max(fig["max_paid"], int(paid.max()))
+        fig["raises_after_flop"] += int((np.isin(tr["a"], (3, 4, 5)) & (was["turn"] >= 1)).sum())
+        fig["allin_after_flop"] += int(((tr["a"] == 6) & (was["turn"] >= 1)).sum())
+        fig["game_resets"] += int(tr["over"].sum())
+    assert fig["river_3way"] >= DEEP_FLOOR and (N == 2 or fig["paid_3"] >= DEEP_FLOOR) and 10 * fig["raises_after_flop"] >= T, fig
+    assert not any(tr["eo"].any() for tr in M.game_step_trace(M.matrix_config(M.DEEP, N, 1), K_GAME)), "a cap or game.py:473 at one table"
+    # ---- PokerGameEnv.step: seat 0 deep against call agents (random agents too up to six seats), 165 / 197 tables and a lone one
+    K_ENV = M.k_of("env_step", M.DEEP, N)
+    for opp in (2, 0) if N <= 6 else (2,):
+        for T_env in (T, M.T_BATCHES, 1):
+            want, _, acts, _, st = M.env_want(M.env_config(M.DEEP, N, T_env), opp, K_ENV)
+            assert st["capped"] == 0 and not any(e.any() for e in st["step_terr"]), (opp, T_env, st["capped"])
+            if T_env == T:
+                rewarded = sum(int(((w[2] != 0) & (w[0] != 0)).sum()) for w in want)
+                fig["env_done_vs_%d" % opp], fig["env_rewarded_hands_vs_%d" % opp] = st["done"], rewarded
+                assert st["done"] > 0 and rewarded > 0 and not any((a == 0).any() for a in acts), fig
+    # ---- one agent per seat: every seat the deep caller, and in-kernel call agents among them
+    for mixed in (False, True):
+        pols, external = M.deep_multi_seats(N, mixed)
+        assert all(p in (2, 14) for p in pols) and (mixed or len(external) == N - 1)
+        for T1 in (T, 1):
+            st = M.multi_want(M.matrix_config(M.DEEP, N, T1), pols, M.K_MULTI)[1]
+            assert st["capped"] == 0, (mixed, T1, st["capped"])
+    # ---- the tables the rollout_from_deep, snapshot and equity families start from, and the call agents' rollout from there
+    o = M.played_oracle(cfg, M.k_of("played", M.DEEP, N))
+    snap = o.snapshot()
+    fig.update(past_the_flop=int((snap["turn"] >= 1).sum()), allin_or_broke_seats=int(np.isin(snap["states"], (3, M.PS_BROKEN)).any(axis=1).sum()))
+    assert len(M.equity_tables(snap["turn"])) == M.EQUITY_FIRST and fig["allin_or_broke_seats"] > 0, fig
+    c, err = o.rollout(M.K_ROLLOUT, 2, True)
+    fig.update(rollout_hands=int(c[1]), rollout_showdown_evals=int(c[2]))
+    assert err == 0 and c[0] == T * M.K_ROLLOUT and c[1] > 0 and c[2] > 0, fig
+    print("seat matrix deep     N=%2d: %s" % (N, fig))
+
+
 def test_the_top_seat_configuration_wraps_the_table_ids():
     cfg = M.matrix_config("top_seat", 16)
     assert cfg["base"] + cfg["T"] > 2 ** 32 > cfg["base"] and cfg["top"] == 15
@@ -159,6 +218,16 @@ def test_comparators_reject_one_bit():
     _flip_low_bit(got[0][t:t + 1])
     with pytest.raises(AssertionError, match="reward"):
         M.assert_delivered(tuple(got), tuple(x[cnt, idx] for x in W), "reward bit, indexed")
+    # a deep trace: the low mantissa bit of a reward delivered at the end of a hand raised on every street (a fractional amount)
+    dcfg = M.env_config(M.DEEP, 9)
+    dwant = M.env_want(dcfg, 2, M.k_of("env_step", M.DEEP, 9))[0]
+    k, t = next((k, int(np.argmax(w[0] != np.round(w[0])))) for k, w in enumerate(dwant) if (w[0] != np.round(w[0])).any())
+    bad = tuple(x.copy() for x in dwant[k])
+    M.assert_delivered(bad, dwant[k], "deep, unchanged")
+    _flip_low_bit(bad[0][t:t + 1])
+    assert dwant[k][2][t] and bad[0][t] != dwant[k][0][t] and abs(bad[0][t] - dwant[k][0][t]) < 1e-12
+    with pytest.raises(AssertionError, match="reward"):
+        M.assert_delivered(bad, dwant[k], "deep reward bit")
     # observation rows: one element of the dense row, one byte of the packed row
     dense, packed = M.oracle_rows(o.snapshot(), cfg["N"])
     mask = np.ones(cfg["T"], bool)

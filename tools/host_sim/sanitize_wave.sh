@@ -1,6 +1,6 @@
 #!/bin/bash
 # Dev-only: the 64-lane CPU build of the table kernels' bodies (wave_sim.cpp on wave_shim.h) under ASan + UBSan and under TSan, every
-# configuration of the driver, both must exit 0.  One translation unit per family and seat group, at most 16 compiles at once.
+# configuration of the driver and the step families' deep variant, all must exit 0.  One translation unit per family and seat group, at most 16 compiles at once.
 #   tools/host_sim/sanitize_wave.sh [out-dir]        (default /tmp/wave_sim_san; prints build and run times)
 set -e -o pipefail
 cd "$(dirname "$0")/../.."
@@ -20,6 +20,7 @@ build() {   # name, sanitizer flags
 run() {
     local name=$1 t0=$SECONDS
     "$OUT/wave_sim_$name"
+    "$OUT/wave_sim_$name" --deep --steps 120      # the step families on the never-fold caller's actions (deep hands)
     echo "run $name: $((SECONDS - t0)) s"
 }
 build asan "-fsanitize=address,undefined -fno-sanitize-recover=undefined"

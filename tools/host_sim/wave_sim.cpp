@@ -6,7 +6,9 @@
 // follows the flush that completes them.)  Built plain by tests/test_wave_sim_host.py and under ASan + UBSan and TSan by sanitize_wave.sh.
 //   g++ -std=c++20 -O1 -pthread -ffp-contract=off -DPK_HOST_SIM -include tools/host_sim/wave_shim.h -DPK_WS_PART=100 -DPK_WS_MAIN \
 //       tools/host_sim/wave_sim.cpp oracle/pokerl_oracle.c
-//   wave_sim [family [N]] [--quick] [--steps K]       families: rollout allin call tab allin_tab single step step_async
+//   wave_sim [family [N]] [--quick] [--steps K] [--deep]      families: rollout allin call tab allin_tab single step step_async
+//   --deep (step, step_async): the actions of the oracle's never-fold caller (oracle/rng_spec.py POLICY_DEEP, policy 14 of orc_pick_actions) on
+//   per-seat fractional stacks -- raises on every street, all-ins on different streets, multi-way river showdowns with side pots; 60 steps
 // One translation unit per family and seat group (-DPK_WS_PART=1..11; 100: the three instantiations of the suite's test), main with -DPK_WS_MAIN.
 #define HIP_INCLUDE_HIP_HIP_RUNTIME_H
 #include "../../pokerl_amd/csrc/pk_table_kernels.hpp"
@@ -17,7 +19,7 @@ extern "C" {
 
 enum Family : int { F_ROLLOUT, F_ALLIN, F_CALL, F_TAB, F_ALLIN_TAB, F_SINGLE, F_STEP, F_STEP_ASYNC };
 static const char *const kFamilyName[] = {"rollout", "allin", "call", "tab", "allin_tab", "single", "step", "step_async"};
-struct Opts { bool quick = false; int steps = 0; };
+struct Opts { bool quick = false; int steps = 0; bool deep = false; };
 struct Case { int family, n; int (*fn)(const Opts &); };
 std::vector<Case> &registry();
 #ifdef PK_WS_MAIN
@@ -49,6 +51,12 @@ static Cfg rolling_cfg(int n) {
     static const double stacks[] = {3, 5, 10, 37.5, 2, 5, 3, 10};
     Cfg c; for (int p = 0; p < 16; ++p) c.start[p] = stacks[(p + n) % 8];
     c.bb = 40; c.sb = 7.5; c.base = 77; c.seed = 0x5EEDull + (uint64_t)n; c.name = "blinds above the stacks";
+    return c;
+}
+// the deep configuration of tests/seat_matrix.py: stacks 7.5 (p + 1) + 0.25 (p % 3), blinds 2 / 1, table ids that wrap 2^32 inside the batch
+static Cfg deep_cfg(int n) {
+    Cfg c; for (int p = 0; p < 16; ++p) c.start[p] = 7.5 * (p + 1) + 0.25 * (p % 3);
+    c.bb = 2; c.sb = 1; c.base = 0xffffff9cu; c.seed = 0xDEE9ull + (uint64_t)n; c.name = "deep caller, per-seat fractional stacks";
     return c;
 }
 static Cfg equal_cfg(int n) {
@@ -213,15 +221,24 @@ static int run_rollout(int T, const Cfg &cfg, int K, int park, bool split) {
 // Game.step with the caller's actions (the oracle's random agent's, one table in 23 an invalid one); finished games are reset as a caller does.
 // ASYNC: every step is a bounded launch (max_end = 1) followed by a drain (actions == NULL) that completes what stayed in flight.
 template <int N, int FAM>
-static int run_step(int T, const Cfg &cfg, int K, int park, long *inflight) {
+static int run_step(int T, const Cfg &cfg, int K, int park, long *inflight, bool deep = false, long *river = nullptr) {
     Sim<N, FAM> s(T, cfg);
     Arr<uint8_t> of(T), oe(T), m(T);
+    Arr<int32_t> ocur(6 * (size_t)T);
+    Arr<uint8_t> ostates((size_t)T * N);
     char where[96];
     int bad = 0;
     for (int k = 0; k < K && !bad; ++k) {
-        orc_pick_actions(s.o, 0, s.actions.p);
+        orc_pick_actions(s.o, deep ? 14 : 0, s.actions.p);
+        if (river) { orc_get_cursors(s.o, ocur.p); orc_get_states(s.o, ostates.p); }
         for (int t = 0; t < T; ++t) if ((t + 3 * k) % 23 == 5) s.actions[t] = (k & 1) ? PK_NUM_MOVES : -1;
         orc_step(s.o, s.actions.p, of.p, oe.p);
+        if (river)      // hand ends at the river among three or more seats still in the hand (two at a two-seat table)
+            for (int t = 0; t < T; ++t) {
+                int live = 0;
+                for (int p = 0; p < N; ++p) live += ostates[(size_t)t * N + p] >= 1 && ostates[(size_t)t * N + p] <= 3;
+                *river += (of[t] & 2) && ocur[6 * t + 1] == 3 && live >= (N < 3 ? N : 3);
+            }
         if (FAM == F_STEP) s.launch_step(s.actions.p, s.flags.p, s.terr_out.p, nullptr, park, 0);
         else {
             // the bounded launch; one more bounded launch that steps nothing (an invalid action for every table: the ones whose step has returned come
@@ -253,11 +270,32 @@ static int run_step(int T, const Cfg &cfg, int K, int park, long *inflight) {
 template <int N, int FAM>
 static int run_case(const Opts &op) {
     constexpr bool allin = FAM == F_ALLIN || FAM == F_ALLIN_TAB, stepf = FAM == F_STEP || FAM == F_STEP_ASYNC;
-    const int K = op.steps > 0 ? op.steps : (stepf || FAM == F_SINGLE ? 24 : 48);
+    const int K = op.steps > 0 ? op.steps : (stepf && op.deep ? 60 : (stepf || FAM == F_SINGLE ? 24 : 48));
     int bad = 0, runs = 0;
     long inflight = 0;
     const auto t0 = std::chrono::steady_clock::now();
     std::string ran;
+    if (op.deep) {
+        if constexpr (stepf) {
+            long river = 0;
+            const Cfg cfg = deep_cfg(N);
+            for (int T : {64 * 3 + 7, 1})
+                for (int park : {1, 28, 64}) {
+                    if (op.quick && !(T > 1 && park == 28)) continue;
+                    const int b = run_step<N, FAM>(T, cfg, K, park, &inflight, true, &river);
+                    if (b) printf("  ^ %s, T=%d park=%d K=%d\n", cfg.name, T, park, K);
+                    bad += b; ++runs;
+                }
+            if (river == 0) { printf("%s N=%d deep: no hand ended at the river among three or more seats: nothing deep was compared\n", kFamilyName[FAM], N); ++bad; }
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            if (!bad) printf("%s N=%d deep: %d runs (%s; %d steps; %ld multi-way river hand ends): wave-sim == oracle  [%.1f s]\n", kFamilyName[FAM], N, runs, cfg.name, K, river, sec);
+            else printf("%s N=%d deep: %d mismatches\n", kFamilyName[FAM], N, bad);
+            fflush(stdout);
+            return bad != 0;
+        } else {
+            return 0;      // (the rollout families play the product's own agents: nothing deep to run)
+        }
+    }
     for (int ci = 0; ci < (op.quick ? 1 : (stepf ? 3 : 2)); ++ci) {
         // quick (the suite's test): the configuration that matters most for the family -- equal stacks for the all-in agents (all-showdown queues)
         const Cfg cfg = ci == 2 ? rolling_cfg(N) : ((op.quick ? allin : ci == 1) ? equal_cfg(N) : fuzz_cfg(N));
@@ -324,6 +362,7 @@ int main(int argc, char **argv) {
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--quick") op.quick = true;
+        else if (a == "--deep") op.deep = true;
         else if (a == "--steps" && i + 1 < argc) op.steps = atoi(argv[++i]);
         else if (fam.empty()) fam = a;
         else n = atoi(argv[i]);
@@ -331,7 +370,7 @@ int main(int argc, char **argv) {
     std::sort(registry().begin(), registry().end(), [](const Case &a, const Case &b) { return a.family != b.family ? a.family < b.family : a.n < b.n; });
     int rc = 0, ran = 0;
     for (const Case &c : registry())
-        if ((fam.empty() || fam == kFamilyName[c.family]) && (n == 0 || n == c.n)) { rc |= c.fn(op); ++ran; }
+        if ((fam.empty() || fam == kFamilyName[c.family]) && (n == 0 || n == c.n) && (!op.deep || c.family == F_STEP || c.family == F_STEP_ASYNC)) { rc |= c.fn(op); ++ran; }
     if (!ran) { fprintf(stderr, "wave_sim: no such case in this build\n"); return 2; }
     printf(rc ? "wave_sim: FAILED\n" : "wave_sim: %d cases == oracle\n", ran);
     return rc;

@@ -531,6 +531,8 @@ int pk_clone_tables_d(pk_handle *dst, const int32_t *dst_tables_d, pk_handle *sr
  * P of them; boards = all C(P, 5 - nb) completions.  On each board v[p] = eval_hand(board + hole[p]) for a live seat and eval_hand([]) =
  * (NONE, []) for the others -- the list Game.end_hand builds (game.py:488-490) -- and the winners are compare_rankings(v) (judger.py:111-158
  * INCLUDING its line-148 behaviour: who takes the main pot as the reference judges it, which is not always who wins at poker).
+ * This is the FIRST comparison end_hand makes -- main-pot equity.  It is an all-in EV only while every live seat has bet the same; with
+ * unequal stacks the pot is paid out in levels: "Showdown EV" below (pk_equity_ev) gives the expected payoff in chips.
  * Per spot and seat, nw = the number of winners of a board:
  *   win[p]   u32  boards on which p is the only winner          tie[p]  u32  boards on which p wins and nw > 1
  *   share[p] u64  sum over the boards p wins of PK_EQ_SHARE_UNIT / nw  (720720 = lcm(1 .. 16): exact; sum over p = 720720 * boards)
@@ -756,6 +758,49 @@ int pk_table_equity_hist_d(pk_handle *h, const int32_t *tables_d, size_t m, cons
                            uint16_t *hist_d, uint16_t *void_d, uint32_t *completions_d, uint8_t *status_d);
 int pk_table_equity_hist(pk_handle *h, const int32_t *tables, size_t m, const uint16_t *weights, int weights_per_spot, int nbins, uint16_t *hist,
                          uint16_t *void_, uint32_t *completions, uint8_t *status);
+/* ---- Showdown EV: "if the cards still to come were dealt now, what does each seat expect to be paid, in chips?" -- the side pots of
+ * Game.end_hand (game.py:494-531) enumerated over every board on the device, exact.  pk_equity above answers only the
+ * first comparison of end_hand (who wins when every live seat is compared); with unequal stacks the pot is paid out in LEVELS, each judged
+ * after the lower bettors' hands have been taken out of the comparison.
+ *
+ * A SPOT is a "Showdown equity" spot plus bets f64 [N]: what each seat has committed to the pot this hand -- seats that are not live
+ * included (a folded seat's money is in the pot).  Dead cards, pool, boards and v[p] per board are exactly those of "Showdown equity".
+ * LEVELS depend on bets and live only, never on the board:
+ *     order = [p for p in stable_argsort(bets) if live[p]];  work = copy(bets);  remain = set(order)
+ *     for i, s in enumerate(order):
+ *         if all(work <= 0): break
+ *         if len(remain) == 1:  level i: seat s, amount = np.sum(work), LAST;  break                  (the "last stand", game.py:500-505)
+ *         mb = clip(work, 0, work[s]);  level i: seat s, amount = np.sum(mb), remain as it is now
+ *         remain.remove(s);  work -= mb
+ * (np.sum in numpy's association order).  A level that is not reached does not exist: level_seat 0xFF, amount 0.
+ * PER BOARD and level i that is not LAST: W_i = compare_rankings(v with every seat outside remain_i set to (NONE, [])), line 148 as it is
+ * -- W_i is NOT W_0 restricted to remain_i: the first hand of the best rank class fixes best_kicker, so taking that hand out changes
+ * who wins among the rest.
+ *   share      u64 [m][N][N]  level-major: share[i][p] = sum of 720720 / |W_i| over the boards with p in W_i; 0 for a level whose amount is 0 or
+ *                             that does not exist; for the LAST level 720720 * boards at the level's seat, 0 elsewhere
+ *   level_seat u8  [m][N]     the seat visited at level i (0xFF: no such level)        amount  f64 [m][N]
+ *   boards     u32 [m]        status  u8 [m]  (the PK_EQ_* bits of "Showdown equity" plus PK_EQ_BAD_BET)
+ *   ev         f64 [m][N]     acc = +0.0;  for i ascending: acc = acc + (amount[i] * (double)share[i][p]) / (720720.0 * (double)boards);
+ *                             ev[p] = acc - bets[p] -- every operation rounded on its own, nothing fused: bit-identical to that formula
+ *                             evaluated in binary64 anywhere.  On a complete board with money of integer value every product is exact and
+ *                             ev equals the payoffs Game.end_hand writes, bit for bit.
+ * A spot with a non-zero status gets zeros everywhere, boards = 0 and level_seat = 0xFF; it disturbs nothing else.  Any output except
+ * `status` may be NULL.  m, device, STREAMS and work space: as pk_equity (the work space also holds the levels, and the share counters
+ * when share is NULL); the task bound counts ceil((N - 1) / L) groups of levels per spot (L = 3 up to eight seats, 2 beyond).
+ * TABLE FORM: cards, nb and live seats as pk_table_equity (an ACTIVE seat counts as one that shows down: "nobody bets further");
+ * bets = bets + pending_bets per seat, one binary64 addition each -- the commit end_hand makes (game.py:457).  Completes deferred rollout
+ * work, reads only, runs on the handle's stream; PK_EQ_IN_FLIGHT / PK_EQ_BAD_TABLE / PK_EQ_DUP_CARD per table as pk_table_equity. */
+#define PK_EQ_BAD_BET 64u    /* showdown EV: a bet that is negative, NaN or infinite (the value of PK_EQ_PREFLOP, which no EV call reports) */
+/* holes_d, board_d, nboard_d, live_d as pk_equity_d; bets_d f64 [m][N]. */
+int pk_equity_ev_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
+                   const uint16_t *live_d, const double *bets_d, uint64_t *share_d, uint8_t *level_seat_d, double *amount_d, double *ev_d,
+                   uint32_t *boards_d, uint8_t *status_d, void *stream);
+int pk_equity_ev(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
+                 const double *bets, uint64_t *share, uint8_t *level_seat, double *amount, double *ev, uint32_t *boards, uint8_t *status);
+int pk_table_equity_ev_d(pk_handle *h, const int32_t *tables_d, size_t m, uint64_t *share_d, uint8_t *level_seat_d, double *amount_d, double *ev_d,
+                         uint32_t *boards_d, uint8_t *status_d);
+int pk_table_equity_ev(pk_handle *h, const int32_t *tables, size_t m, uint64_t *share, uint8_t *level_seat, double *amount, double *ev,
+                       uint32_t *boards, uint8_t *status);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

@@ -10,6 +10,7 @@ from .judger import HOLDINGS, RangeEquity, holding_index, range_equity, range_eq
 from .judger import RangeVsRange, range_vs_range, range_vs_range_batch, range_vs_range_d
 from .judger import StrengthHistogram, histogram_emd, strength_histogram, strength_histogram_batch, strength_histogram_d
 from .judger import RangedEquity, ranged_equity, ranged_equity_batch, ranged_equity_d
+from .judger import ShowdownEV, showdown_ev, showdown_ev_batch, showdown_ev_d
 from .sharding import gather_f64, shard_tables
 from .single import Game, PokerGameEnv
 from .state_view import Card, StateView, packed_dtype, unpack_obs
@@ -24,4 +25,5 @@ __all__ = ['Game', 'PokerGameEnv', 'VecGame', 'VecPokerGameEnv', 'VecPokerGameEn
            'HOLDINGS', 'RangeEquity', 'holding_index', 'range_equity', 'range_equity_batch', 'range_equity_d',
            'RangeVsRange', 'range_vs_range', 'range_vs_range_batch', 'range_vs_range_d',
            'StrengthHistogram', 'histogram_emd', 'strength_histogram', 'strength_histogram_batch', 'strength_histogram_d',
-           'RangedEquity', 'ranged_equity', 'ranged_equity_batch', 'ranged_equity_d']
+           'RangedEquity', 'ranged_equity', 'ranged_equity_batch', 'ranged_equity_d',
+           'ShowdownEV', 'showdown_ev', 'showdown_ev_batch', 'showdown_ev_d']

@@ -23,6 +23,7 @@ EQ_SHARE_UNIT = 720720   # lcm(1 .. 16): a board's pot share of one of nw winner
 EQ_BAD_CARD, EQ_DUP_CARD, EQ_NO_LIVE, EQ_BAD_NBOARD, EQ_IN_FLIGHT, EQ_BAD_TABLE = 1, 2, 4, 8, 16, 32   # PK_EQ_* status bits
 OBSERVER_NONE, OBSERVER_ACTIVE = -1, -2   # pk_clone_tables_d: an exact copy / redeal from each source table's active player
 EQ_PREFLOP, EQ_SMALL_POOL = 64, 128   # ... of pk_equity_range: nb < 3 / fewer pool cards than the board to come plus one holding
+EQ_BAD_BET = 64   # ... of pk_equity_ev: a bet that is negative, NaN or infinite (the value of EQ_PREFLOP, which no EV call reports)
 EQ_HIST_MAX_BINS = 32   # PK_EQ_HIST_MAX_BINS: the most bins of a strength histogram
 EQ_HOLDINGS = 1326   # PK_EQ_HOLDINGS: unordered pairs of the 52 cards, h = b (b - 1) / 2 + a over canonical indices a < b
 EQS_SAMPLES_MAX = 1 << 24   # pk_equity_sampled: samples per call and spot at most
@@ -46,7 +47,8 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_equity_range_d", "pk_equity_range", "pk_table_equity_range_d", "pk_table_equity_range",
            "pk_equity_rvr_d", "pk_equity_rvr", "pk_table_equity_rvr_d", "pk_table_equity_rvr",
            "pk_equity_hist_d", "pk_equity_hist", "pk_table_equity_hist_d", "pk_table_equity_hist",
-           "pk_equity_ranged_d", "pk_equity_ranged", "pk_table_equity_ranged_d", "pk_table_equity_ranged"]
+           "pk_equity_ranged_d", "pk_equity_ranged", "pk_table_equity_ranged_d", "pk_table_equity_ranged",
+           "pk_equity_ev_d", "pk_equity_ev", "pk_table_equity_ev_d", "pk_table_equity_ev"]
 
 
 class PokerlHipError(RuntimeError):
@@ -148,6 +150,10 @@ def lib():
     L.pk_equity.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 9
     L.pk_table_equity_d.argtypes = [_vp, _vp, C.c_size_t] + [_vp] * 5
     L.pk_table_equity.argtypes = [_vp, _vp, C.c_size_t] + [_vp] * 5
+    L.pk_equity_ev_d.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 12
+    L.pk_equity_ev.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 11
+    L.pk_table_equity_ev_d.argtypes = [_vp, _vp, C.c_size_t] + [_vp] * 6
+    L.pk_table_equity_ev.argtypes = [_vp, _vp, C.c_size_t] + [_vp] * 6
     L.pk_equity_sampled_d.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_uint32, C.c_uint64, C.c_uint32] + [_vp] * 6
     L.pk_equity_sampled.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_uint32, C.c_uint64, C.c_uint32] + [_vp] * 5
     L.pk_table_equity_sampled_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32] + [_vp] * 5

@@ -16,6 +16,7 @@
 #include "pk_table_kernels.hpp"
 #include "pk_util_kernels.hpp"
 #include "pk_equity.hpp"
+#include "pk_equity_ev.hpp"
 #include "pk_equity_sampled.hpp"
 #include "pk_equity_ranged.hpp"
 #include "pk_equity_range.hpp"
@@ -1944,6 +1945,117 @@ int pk_table_equity(pk_handle *h, const int32_t *tables, size_t m, uint32_t *win
     if (rc) return rc;
     HIPCHK(h, g.upload(h->stream));
     if ((rc = table_equity(h, g.at<int32_t>(idx), m, out.at(g), g.at<char>(work)))) return rc;
+    HIPCHK(h, g.download(h->stream));
+    return PK_OK;
+}
+
+// ---- showdown EV in chips (pokerl_hip.h "Showdown EV"; kernels: pk_equity_ev.hip).  Streams and work space as showdown equity; the work space
+// also holds the level table, the bets, the amounts and -- when the caller does not ask for `share` -- the share counters.
+static bool ev_too_many_tasks(int N, size_t m, int pool_max) { return ev_task_cap(N, m, eq_lpt(m), pool_max) > EQ_TASKS_MAX; }
+struct EvStagedOut {
+    int share, level_seat, amount, ev, boards, status;
+    EvStagedOut(Stage &g, int N, size_t m, uint64_t *share, uint8_t *level_seat, double *amount, double *ev, uint32_t *boards, uint8_t *status)
+        : share(g.out(share, m * N * N * 8)), level_seat(g.out(level_seat, m * N)), amount(g.out(amount, m * N * 8)), ev(g.out(ev, m * N * 8)),
+          boards(g.out(boards, m * 4)), status(g.out(status, m)) {}
+    EvOut at(const Stage &g) const {
+        return EvOut{g.at<uint64_t>(share), g.at<uint8_t>(level_seat), g.at<double>(amount), g.at<double>(ev), g.at<uint32_t>(boards), g.at<uint8_t>(status)};
+    }
+};
+#define EV_CHECK_SPOTS(call, num_players, m, inputs, status)                                                                                                     \
+    if (eq_bad_seats(num_players) || (m) >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, call ": num_players outside 2 .. 16, or m >= 2^31");                   \
+    if ((m) && !((inputs) && (status))) return g_fail(PK_E_INVALID_ARG, call ": NULL input buffer or NULL status");                                              \
+    if (ev_too_many_tasks(num_players, m, 50)) return g_fail(PK_E_INVALID_ARG, call EQ_TASKS_MSG)
+
+int pk_equity_ev_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
+                   const uint16_t *live_d, const double *bets_d, uint64_t *share_d, uint8_t *level_seat_d, double *amount_d, double *ev_d,
+                   uint32_t *boards_d, uint8_t *status_d, void *stream) {
+    EV_CHECK_SPOTS("pk_equity_ev_d", num_players, m, holes_d && board_d && nboard_d && live_d && bets_d, status_d);
+    ON_DEVICE_INDEX("pk_equity_ev_d", device, PK_MAX_DEVICES);
+    if (m == 0) return PK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t *tab = eval7_table(device, st);   // (a first call builds the table on the CALLER's stream)
+    if (!tab) return g_fail(PK_E_OOM, "pk_equity_ev_d: out of device memory (evaluator table)");
+    const int lpt = eq_lpt(m);
+    void *ws = eq_stream_ws(device, st, ev_layout(num_players, m, lpt, 50, !share_d, nullptr, nullptr));
+    if (!ws) return g_fail(PK_E_OOM, "pk_equity_ev_d: out of device memory (work space)");
+    EvWork w;
+    ev_layout(num_players, m, lpt, 50, !share_d, (char *)ws, &w);
+    const EqSpots spots{holes_d, board_d, nboard_d, live_d};
+    const hipError_t e = ev_launch(st, tab, &spots, bets_d, nullptr, num_players, m, EvOut{share_d, level_seat_d, amount_d, ev_d, boards_d, status_d}, w, lpt);
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_ev_d: launch failed", e);
+    return PK_OK;
+}
+
+int pk_equity_ev(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
+                 const double *bets, uint64_t *share, uint8_t *level_seat, double *amount, double *ev, uint32_t *boards, uint8_t *status) {
+    EV_CHECK_SPOTS("pk_equity_ev", num_players, m, holes && board && nboard && live && bets, status);
+    ON_DEVICE_INDEX("pk_equity_ev", device, PK_MAX_DEVICES);
+    if (m == 0) return PK_OK;
+    const int N = num_players, lpt = eq_lpt(m);
+    hipStream_t st = nullptr;
+    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity_ev: no stream"); }
+    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
+    int rc = PK_OK;
+    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity_ev: out of device memory (evaluator table)");
+    else {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        Stage g;
+        const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), be = g.in(bets, m * N * 8);
+        const EvStagedOut out(g, N, m, share, level_seat, amount, ev, boards, status);
+        const int work = g.add(ev_layout(N, m, lpt, 50, !share, nullptr, nullptr));
+        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity_ev: out of device memory");
+        else {
+            const hipError_t e = g.run(st, [&] {
+                EvWork w;
+                ev_layout(N, m, lpt, 50, !share, g.at<char>(work), &w);
+                const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
+                return ev_launch(st, tab, &spots, g.at<double>(be), nullptr, N, m, out.at(g), w, lpt);
+            });
+            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity_ev", e); }   // (the lock is held until what was queued is done)
+        }
+    }
+    stream_release(device, st);
+    return rc;
+}
+
+static int table_equity_ev(pk_handle *h, const int32_t *tables_d, size_t m, const EvOut &out, char *work) {
+    const uint32_t *tab = eval7_table(h->device, h->stream);
+    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity_ev: out of device memory (evaluator table)");
+    const int lpt = eq_lpt(m);
+    EvWork w;
+    ev_layout(h->N, m, lpt, 52 - 2 * h->N, !out.share, work, &w);
+    const EvTables t{EqTables{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T}, h->S.bets, h->S.pending};
+    HIPCHK(h, ev_launch(h->stream, tab, nullptr, nullptr, &t, h->N, m, out, w, lpt));
+    return PK_OK;
+}
+#define EV_TABLE_ENTER(h, m, status, call)                                                                     \
+    if (!(h)) return PK_E_INVALID_ARG;                                                                         \
+    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                           \
+    if ((m) && !(status)) return (h)->fail(PK_E_INVALID_ARG, call ": NULL status");                            \
+    if (ev_too_many_tasks((h)->N, m, 52 - 2 * (h)->N)) return (h)->fail(PK_E_INVALID_ARG, call EQ_TASKS_MSG);  \
+    ON_DEVICE(h);                                                                                              \
+    FLUSH_READER(h);                                                                                           \
+    if ((m) == 0) return PK_OK
+
+int pk_table_equity_ev_d(pk_handle *h, const int32_t *tables_d, size_t m, uint64_t *share_d, uint8_t *level_seat_d, double *amount_d, double *ev_d,
+                         uint32_t *boards_d, uint8_t *status_d) {
+    EV_TABLE_ENTER(h, m, status_d, "pk_table_equity_ev_d");
+    char *work = nullptr;
+    if (int rc = snap_staging(h, ev_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, !share_d, nullptr, nullptr), &work)) return rc;
+    return table_equity_ev(h, tables_d, m, EvOut{share_d, level_seat_d, amount_d, ev_d, boards_d, status_d}, work);
+}
+
+int pk_table_equity_ev(pk_handle *h, const int32_t *tables, size_t m, uint64_t *share, uint8_t *level_seat, double *amount, double *ev,
+                       uint32_t *boards, uint8_t *status) {
+    EV_TABLE_ENTER(h, m, status, "pk_table_equity_ev");
+    Stage g;
+    const int idx = g.in(tables, m * 4);
+    const EvStagedOut out(g, h->N, m, share, level_seat, amount, ev, boards, status);
+    const int work = g.add(ev_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, !share, nullptr, nullptr));
+    int rc = snap_staging(h, g.total, &g.base);
+    if (rc) return rc;
+    HIPCHK(h, g.upload(h->stream));
+    if ((rc = table_equity_ev(h, g.at<int32_t>(idx), m, out.at(g), g.at<char>(work)))) return rc;
     HIPCHK(h, g.download(h->stream));
     return PK_OK;
 }

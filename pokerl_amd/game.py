@@ -389,6 +389,40 @@ class VecGame:
         L.check(self._lib.pk_table_equity_d(self._h, self._dptr(tables_d), m, self._dptr(win_d), self._dptr(tie_d), self._dptr(share_d),
                                             self._dptr(boards_d), self._dptr(status_d)), self._h)
 
+    def equity_ev(self, tables=None):
+        """Showdown EV in chips of `tables` (all tables if None; indices may repeat) as they stand: the side pots of end_hand over every
+        completion of the board (pk_table_equity_ev; definition: pokerl_hip.h "Showdown EV").  Cards and live seats as equity(); an ACTIVE
+        seat counts as one that shows down ("nobody bets further"), bets = bets + pending_bets.  Returns a judger.ShowdownEV of [m, N] /
+        [m, N, N] / [m] arrays; a table that cannot be evaluated (never reset, step in flight, index out of range) has a non-zero status
+        (`bets` and `payout` are None while asynchronous steps are in flight: they are formed from the getters)."""
+        from .judger import NO_LEVEL, ShowdownEV
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        n = self.num_players
+        share = np.zeros((m, n, n), np.uint64)
+        level_seat = np.full((m, n), NO_LEVEL, np.uint8)
+        amount, ev = np.zeros((m, n), np.float64), np.zeros((m, n), np.float64)
+        boards, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        L.check(self._lib.pk_table_equity_ev(self._h, L.ptr(t), m, L.ptr(share), L.ptr(level_seat), L.ptr(amount), L.ptr(ev), L.ptr(boards),
+                                             L.ptr(status)), self._h)
+        try:                            # (`bets` is formed from the getters, which refuse with PK_E_BUSY while asynchronous steps are in flight)
+            bets = self.bets + self.pending_bets
+            if t is not None:
+                ok = (t >= 0) & (t < self.num_tables)
+                bets = np.where(ok[:, None], bets[np.where(ok, t, 0)], 0.0)
+        except L.PokerlHipError as e:
+            if e.code != L.PK_E_BUSY:       # (any other failure of a getter is the caller's to see)
+                raise
+            bets = None
+        return ShowdownEV(ev, share, level_seat, amount, boards, status, bets)
+
+    def equity_ev_d(self, status_d, m=None, tables_d=None, share_d=None, level_seat_d=None, amount_d=None, ev_d=None, boards_d=None):
+        """pk_table_equity_ev_d: the same into device buffers (uint64 [m, N, N] share, uint8 [m, N] level_seat, float64 [m, N] amount / ev,
+        uint32 [m] boards, uint8 [m] status; any but status_d may be None), asynchronous on the handle's stream.  m defaults to every table."""
+        m = self.num_tables if m is None else int(m)
+        L.check(self._lib.pk_table_equity_ev_d(self._h, self._dptr(tables_d), m, self._dptr(share_d), self._dptr(level_seat_d), self._dptr(amount_d),
+                                               self._dptr(ev_d), self._dptr(boards_d), self._dptr(status_d)), self._h)
+
     def _equity_observer(self, observer):
         """observer of equity_sampled: a seat, OBSERVER_ACTIVE / 'active', or OBSERVER_NONE / None; ValueError otherwise (before any call)."""
         o = self._observer(observer)

@@ -220,6 +220,130 @@ def showdown_equity(hands, board=(), live=None, device=0):
     return r
 
 
+# ---------------------------------------------------------------------------------------------- showdown EV in chips
+# "If the cards still to come were dealt now, what does each seat expect to be paid?" -- the side pots of Game.end_hand (game.py:494-531)
+# over every board (pk_equity_ev; the definition: include/pokerl_hip.h "Showdown EV").  With equal bets this is
+# pot * equity - bet; with unequal stacks the pot is paid out in levels and main-pot equity gives the wrong number.
+NO_LEVEL = 0xFF
+_EV_STATUS = [(bit, t) for bit, t in _EQ_STATUS if bit < L.EQ_BAD_BET] + [(L.EQ_BAD_BET, 'a bet that is negative, NaN or infinite')]
+
+
+def ev_status_text(status):
+    return '; '.join(t for bit, t in _EV_STATUS if int(status) & bit) or 'ok'
+
+
+class ShowdownEV:
+    """Expected payoffs of one spot or of a batch ([N] / [N, N] or [m, N] / [m, N, N] arrays; `boards`, `status` scalars or [m]):
+    ev = expected payoff minus what the seat has put in (what Game.end_hand writes to `payoffs`, averaged over the boards), share[i][p] = sum
+    of 720720 / (number of winners) over the boards seat p wins pot level i, level_seat[i] / amount[i] = the seat visited at level i (0xFF:
+    no such level) and the chips that level pays, bets = the bets of the spot."""
+
+    def __init__(self, ev, share, level_seat, amount, boards, status, bets):
+        self.ev, self.share, self.level_seat, self.amount, self.boards, self.status, self.bets = ev, share, level_seat, amount, boards, status, bets
+
+    @property
+    def payout(self):
+        """ev + bets: what a seat expects to take out of the pot (0 where a spot was refused)."""
+        if self.bets is None:
+            return None
+        ok = np.asarray(self.status)[..., None] == 0
+        return np.where(ok, np.asarray(self.ev) + np.asarray(self.bets), 0.0)
+
+    @property
+    def levels(self):
+        """(seat, amount) pairs of the levels that exist, in visiting order (a batch: one list per spot)."""
+        seat, amount = np.asarray(self.level_seat), np.asarray(self.amount)
+        if seat.ndim == 1:
+            return [(int(s), float(a)) for s, a in zip(seat, amount) if s != NO_LEVEL]
+        return [[(int(s), float(a)) for s, a in zip(ss, aa) if s != NO_LEVEL] for ss, aa in zip(seat, amount)]
+
+    def __getitem__(self, i):
+        return ShowdownEV(self.ev[i], self.share[i], self.level_seat[i], self.amount[i], self.boards[i], self.status[i],
+                          None if self.bets is None else self.bets[i])
+
+    def __repr__(self):
+        return 'ShowdownEV(boards=%r, status=%r, ev=%r, levels=%r)' % (self.boards, self.status, self.ev, self.levels)
+
+
+def showdown_ev_batch(holes, board, nboard, live, bets, device=0):
+    """pk_equity_ev on host arrays: the spots of showdown_equity_batch plus bets float64 [m, N] (what each seat has committed, folded seats
+    included) -> ShowdownEV of [m, N] / [m, N, N] / [m] arrays.  A bad spot is reported through its `status` (PK_EQ_* bits, PK_EQ_BAD_BET
+    among them) with zeros everywhere; the others are unaffected."""
+    holes = np.ascontiguousarray(holes, np.uint8)
+    if holes.ndim != 3 or holes.shape[2] != 2 or not (L.MIN_PLAYERS <= holes.shape[1] <= L.MAX_PLAYERS):
+        raise ValueError('holes must have shape [m, N, 2] with 2 <= N <= 16')
+    m, n = holes.shape[:2]
+    board = np.ascontiguousarray(board, np.uint8)
+    nboard = np.ascontiguousarray(nboard, np.uint8)
+    live = np.ascontiguousarray(live, np.uint16)
+    bets = np.ascontiguousarray(bets, np.float64)
+    if board.shape != (m, 5) or nboard.shape != (m,) or live.shape != (m,) or bets.shape != (m, n):
+        raise ValueError('board must have shape [m, 5], nboard and live shape [m], bets shape [m, N]')
+    share = np.zeros((m, n, n), np.uint64)
+    level_seat = np.full((m, n), NO_LEVEL, np.uint8)
+    amount, ev = np.zeros((m, n), np.float64), np.zeros((m, n), np.float64)
+    boards, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+    L.check(L.lib().pk_equity_ev(int(device), n, m, L.ptr(holes), L.ptr(board), L.ptr(nboard), L.ptr(live), L.ptr(bets), L.ptr(share),
+                                 L.ptr(level_seat), L.ptr(amount), L.ptr(ev), L.ptr(boards), L.ptr(status)))
+    return ShowdownEV(ev, share, level_seat, amount, boards, status, bets)
+
+
+def showdown_ev_d(num_players, m, holes_d, board_d, nboard_d, live_d, bets_d, status_d, share_d=None, level_seat_d=None, amount_d=None, ev_d=None,
+                  boards_d=None, device=0, stream=None):
+    """pk_equity_ev_d: the same on device-resident buffers (device pointers as ints / c_void_p; every output but status_d may be None),
+    asynchronous on `stream`."""
+    L.check(L.lib().pk_equity_ev_d(int(device), int(num_players), int(m), holes_d, board_d, nboard_d, live_d, bets_d, share_d, level_seat_d,
+                                   amount_d, ev_d, boards_d, status_d, stream))
+
+
+def showdown_ev(hands, board=(), live=None, bets=None, device=0):
+    """One spot: showdown_equity's arguments plus bets, one number per seat (what the seat has committed to the pot; a folded seat's money
+    counts).  Returns a ShowdownEV with [N] / [N, N] arrays; raises ValueError for an invalid spot."""
+    hands = list(hands)
+    n = len(hands)
+    if not (L.MIN_PLAYERS <= n <= L.MAX_PLAYERS):
+        raise ValueError('between 2 and 16 seats')
+    if bets is None:
+        raise ValueError('bets: one number per seat')
+    try:
+        b = np.array([float(x) for x in bets], np.float64)
+    except TypeError as e:
+        raise ValueError('bets: one number per seat') from e
+    if b.shape != (n,):
+        raise ValueError('bets: one number per seat')
+    if not np.all(np.isfinite(b)) or np.any(b < 0):
+        raise ValueError('bets must be finite and not negative')
+    board = list(board)
+    if len(board) > 5:
+        raise ValueError('at most five board cards')
+    holes = np.full((1, n, 2), UNKNOWN_CARD, np.uint8)
+    for p, h in enumerate(hands):
+        if h is None:
+            continue
+        h = list(h)
+        if len(h) != 2:
+            raise ValueError('seat %d: two hole cards (or None)' % p)
+        holes[0, p] = [_card(c) for c in h]
+    bd = np.zeros((1, 5), np.uint8)
+    bd[0, :len(board)] = [_card(c) for c in board]
+    if live is None:
+        mask = sum(1 << p for p, h in enumerate(hands) if h is not None)
+    elif isinstance(live, (int, np.integer)):
+        mask = int(live)
+    else:
+        mask = 0
+        for p in live:
+            if not 0 <= int(p) < n:
+                raise ValueError('live seat %r out of range' % (p,))
+            mask |= 1 << int(p)
+    if mask < 0 or mask >> n:
+        raise ValueError('live mask names seats >= %d' % n)
+    r = showdown_ev_batch(holes, bd, np.array([len(board)], np.uint8), np.array([mask], np.uint16), b[None, :], device)[0]
+    if r.status:
+        raise ValueError('invalid spot: ' + ev_status_text(r.status))
+    return r
+
+
 # ---------------------------------------------------------------------------------------------- sampled showdown equity
 # The same question for a seat that does not know the other hands: hidden cards are DRAWN on the device, `samples` times per spot, on a fixed
 # counter-based stream (pk_equity_sampled; the definition: include/pokerl_hip.h "Sampled showdown equity", DESIGN.md section 3.2).

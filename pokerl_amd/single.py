@@ -99,6 +99,14 @@ class Game:
             raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
         return r
 
+    def equity_ev(self):
+        """Showdown EV in chips of the table as it stands (VecGame.equity_ev): a judger.ShowdownEV with [N] arrays.  Not in the reference."""
+        r = self._v.equity_ev()[0]
+        if r.status:
+            from .judger import ev_status_text
+            raise ValueError('the table cannot be evaluated: ' + ev_status_text(r.status))
+        return r
+
     def equity_sampled(self, observer=None, samples=1024, nonce=0):
         """Sampled showdown equity of the table as `observer` sees it (VecGame.equity_sampled; None = the active seat): a
         judger.SampledEquity with [N] arrays.  Not in the reference."""

@@ -19,6 +19,11 @@ The shapes are the smallest at which each mechanism of the kernels can break (do
   k_eqw<N, RC>     (ranged_cases, run beside all_cases by this program and by tests/test_equity_ranged_sim_host.py) N = 2, 3, 6, 16; the three LDS
                    size classes (R = 0, 4, 16); H = 1 .. 16 hidden seats (1 .. 9 Philox blocks); dense, sparse, one-holding and dead ranges; attempts
                    1, 65 and several tasks per spot on a grid of 1; a refused spot between good ones; the three new refusals; the table form;
+  k_ev<N>          (ev_cases, run beside all_cases by this program and by tests/test_equity_ev_sim_host.py) N = 2, 3, 5, 9, 16; a grid of 1 with
+                   spots of falling size and different levels (stale LDS, stale level tables); a refused spot (a bad bet, a bad card) between
+                   valid ones; five live seats on a ladder -- four levels to compare, the smallest spot that needs a second group of levels;
+                   ladders at 9 and 16 seats; dead money, a live seat with bet 0, one live seat, all bets 0; each output NULL in turn; the
+                   table form with bets + pending_bets.  f64 arrays travel as their bit patterns: amount and ev are compared bit for bit;
   preparation      every status bit, the explicit and the table form; table indices -1, T and 2^31 - 1 (nothing is read: ASan's to check).
 
   equity_cases.py --exe <equity_sim> [--exe <another build>] [--quick] [--only <substring>] [--list] [--keep <dir>]
@@ -42,6 +47,7 @@ import equity_range_spec as RS          # noqa: E402
 import equity_ranged_spec as WS         # noqa: E402
 import equity_sampled_spec as SS        # noqa: E402
 import equity_spec as ES                # noqa: E402
+import ev_spec as EV                    # noqa: E402
 import hist_spec as HS                  # noqa: E402
 import rvr_spec as VS                   # noqa: E402
 from oracle import rng_spec as R        # noqa: E402
@@ -51,7 +57,8 @@ IN_FLIGHT, BAD_TABLE = 16, 32
 DTYPES = {"u8": np.uint8, "u16": np.uint16, "u32": np.uint32, "u64": np.uint64, "i32": np.int32}
 OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("win", "tie", "share", "samples", "status"),
            "range": ("agg", "win", "tie", "boards", "status"), "rvr": ("win", "tie", "tot", "boards", "status"),
-           "hist": ("hist", "void", "completions", "status"), "ranged": ("win", "tie", "share", "accepted", "status")}
+           "hist": ("hist", "void", "completions", "status"), "ranged": ("win", "tie", "share", "accepted", "status"),
+           "ev": ("share", "level_seat", "amount", "ev", "boards", "status")}
 
 
 class Case:
@@ -603,6 +610,75 @@ def ranged_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- ev
+def f64_bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def ev_expect(r):
+    return dict(r, amount=f64_bits(r["amount"]), ev=f64_bits(r["ev"]))
+
+
+def ev_case(name, n, specs, bets, seed, grid, outputs=None, quick=False, edit=None):
+    """specs as seat_spots; bets [m][n] (a short row is padded with its last value)."""
+    holes, board, nboard, live = seat_spots(seed, n, specs)
+    m = len(specs)
+    b = np.array([list(row) + [row[-1]] * (n - len(row)) for row in bets], np.float64)
+    assert b.shape == (m, n)
+    if edit:
+        edit(holes, board, nboard, live, b)
+    arrays = {"N": ("u32", [n]), "m": ("u32", [m]), "grid": ("u32", [grid]), "lpt": ("u32", [eq_lpt(m)]), "pool_max": ("u32", [50]),
+              "holes": ("u8", holes), "board": ("u8", board), "nboard": ("u8", nboard), "live": ("u16", live), "bets": ("u64", f64_bits(b))}
+    return Case(name, "ev", arrays, lambda: ev_expect(EV.batch_ev(holes, board, nboard, live, b)), outputs, quick)
+
+
+def ev_cases():
+    cs = []
+    ladder = lambda n: [5.0 * (p + 1) for p in range(n)]
+    # a grid of 1, spots of falling size with different levels: what a spot leaves in LDS and in the level table must not reach the next
+    two = [(2, None, ()), (3, None, ()), (4, None, ()), (5, None, ()), (3, 0b01, (1,)), (5, 0b10, (0,)), (4, None, ())]
+    cs.append(ev_case("ev-N2-grid1", 2, two, [[10, 37], [20, 20], [50, 5], [0, 10], [10, 37], [5, 5], [0, 0]], 71, 1, quick=True))
+    cs.append(ev_case("ev-N2-grid2", 2, two, [[10, 37], [20, 20], [50, 5], [0, 10], [10, 37], [5, 5], [0, 0]], 72, 2))
+    three = [(3, None, ()), (4, 0b101, (1,)), (5, None, ()), (4, None, ()), (5, 0b010, (0, 2)), (4, 0b110, ())]
+    cs.append(ev_case("ev-N3-grid1", 3, three, [[30, 10, 20], [10, 50, 10], [10, 10, 10], [0, 10, 10], [5, 7, 9], [50, 20, 20]], 73, 1, quick=True))
+
+    # a refused spot between two valid ones: a bad bet, a duplicate card, no live seat, a NaN, an infinity
+    def refuse(holes, board, nboard, live, b):
+        b[1, 2] = -1.0
+        holes[3, 0, 0] = board[3, 1]
+        live[5] = 0
+        b[7, 0] = np.nan
+        b[7, 1] = np.inf
+    cs.append(ev_case("ev-N3-refused-between", 3, [(4, None, ())] * 9, [ladder(3)] * 9, 74, 1, edit=refuse, quick=True))
+    # five live seats on a ladder: four levels to compare = two groups of three; then fewer levels in the same slots
+    five = [(4, None, ()), (5, None, ()), (4, 0b10111, ()), (5, 0b00100, ()), (4, None, ())]
+    cs.append(ev_case("ev-N5-two-groups", 5, five, [ladder(5), ladder(5)[::-1], [50, 5, 5, 50, 20], ladder(5), [10] * 5], 75, 1, quick=True))
+    cs.append(ev_case("ev-N9-ladder", 9, [(3, None, ()), (5, 0b101010101, (1, 3)), (4, None, ())], [ladder(9), ladder(9), [0, 5, 5, 37, 37, 50, 10, 20, 20]], 76, 2))
+    cs.append(ev_case("ev-N16-ladder", 16, [(3, None, ()), (5, 0x8001, ()), (4, 0xF0F0, ())], [ladder(16)] * 3, 77, 2))
+    cs.append(ev_case("ev-N16-quick", 16, [(4, None, ()), (5, 0xF0F0, ())], [ladder(16), ladder(16)[::-1]], 78, 1, quick=True))
+    # 72 river spots of one task each on one workgroup: runs of four
+    cs.append(ev_case("ev-take4", 2, [(5, None, ())] * 72, [[10, 37], [5, 5], [20, 0]] * 24, 79, 1, quick=True))
+    for o in ("share", "level_seat", "amount", "ev", "boards"):
+        cs.append(ev_case("ev-no-" + o, 3, [(4, None, ()), (5, 0b011, (2,))], [[30, 10, 20], [10, 5, 50]], 80, 1, outputs=[x for x in OUTPUTS["ev"] if x != o], quick=(o == "share")))
+    for n in (3, 9):
+        w = table_world(81 + n, n, 5, turns=(1, 2, 3))
+        rng = np.random.default_rng(90 + n)
+        tb = rng.choice([0.0, 5.0, 10.0, 20.0, 37.5], (w["T"], n))
+        tp = rng.choice([0.0, 0.0, 2.5, 10.0], (w["T"], n))
+        arrays = dict(table_arrays(w), m=("u32", [len(w["tables"])]), grid=("u32", [2]), lpt=("u32", [16]), pool_max=("u32", [52 - 2 * n]),
+                      bets=("u64", f64_bits(tb.T.copy())), pending=("u64", f64_bits(tp.T.copy())))
+
+        def expect(w=w, tb=tb, tp=tp):
+            holes, board, nboard, live = ES.table_spots(w["deck"], w["states"], w["turn"])
+            r = EV.batch_ev(holes, board, nboard, live, tb + tp)
+            out = table_expect(w, {k: r[k] for k in OUTPUTS["ev"]}, ("share", "amount", "ev", "level_seat"), "boards")
+            out["level_seat"][out["status"] != 0] = EV.NO_LEVEL
+            return ev_expect(out)
+        cs.append(Case("ev-table-form-N%d" % n, "ev", arrays, expect, quick=(n == 3)))
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -617,7 +693,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

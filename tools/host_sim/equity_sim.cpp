@@ -9,7 +9,8 @@
 //   equity_sim <case file> <out file>
 // Case file: lines "name dtype count" (dtype u8 u16 u32 u64 i32) each followed by a line of `count` decimal values, and
 // "family <name>" / "outputs <name> ..." lines.  Out file: the same array format.
-// -DPK_ES_ONLY=1 .. 6: a build of ONE family (equity, sampled, range, rvr, hist, ranged), so that a test can compile them side by side.
+// -DPK_ES_ONLY=1 .. 7: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev), so that a test can compile them side by side.
+// f64 arrays (the bets, amounts and ev of the ev family) travel as their bit patterns, dtype u64.
 #ifndef PK_ES_ONLY
 #define PK_ES_ONLY 0
 #endif
@@ -34,6 +35,10 @@
 #include "../../pokerl_amd/csrc/pk_equity_sampled.hip"  // (the ranged family splits its tasks with pk::eqs_lpt)
 #endif
 #include "../../pokerl_amd/csrc/pk_equity_ranged.hip"
+#endif
+
+#if PK_ES_HAS(7)
+#include "../../pokerl_amd/csrc/pk_equity_ev.hip"
 #endif
 
 #include <chrono>
@@ -311,13 +316,47 @@ void run_ranged(Case &c, const uint32_t *tab) {
 }
 #endif
 
+#if PK_ES_HAS(7)
+// k_ev_prep<N, TABLE>, k_ev<N>, k_ev_finish; the share counters are the caller's array, or a work array when the case does not want them
+template <int N>
+void run_ev(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const int lpt = (int)c.num("lpt"), pool_max = (int)c.num("pool_max");
+    const unsigned grid = (unsigned)c.num("grid");
+    EvPrepArgs a{};
+    const bool tbl = table_form(c, N, m, a.t.t);
+    if (tbl) { a.t.bets = (const double *)c.need<uint64_t>("bets", (size_t)N * a.t.t.T); a.t.pending = (const double *)c.need<uint64_t>("pending", (size_t)N * a.t.t.T); }
+    else {
+        a.s.holes = c.need<uint8_t>("holes", m * N * 2); a.s.board = c.need<uint8_t>("board", m * 5); a.s.nboard = c.need<uint8_t>("nboard", m); a.s.live = c.need<uint16_t>("live", m);
+        a.bets = (const double *)c.need<uint64_t>("bets", m * N);
+    }
+    EvOut out{c.output<uint64_t>("share", "u64", m * N * N), c.output<uint8_t>("level_seat", "u8", m * N), (double *)c.output<uint64_t>("amount", "u64", m * N),
+              (double *)c.output<uint64_t>("ev", "u64", m * N), c.output<uint32_t>("boards", "u32", m), c.output<uint8_t>("status", "u8", m)};
+    if (!out.status) die("the ev family needs the status output");
+    Work<EqCtrl> ctrl(1);
+    memset(ctrl.p, 0, sizeof(EqCtrl));                               // (ev_launch's hipMemsetAsync)
+    Work<uint64_t> desc(m * (size_t)(3 + N));
+    Work<uint32_t> levels(m * N);
+    Work<double> wbets(m * N), wamount(m * N);
+    Work<uint64_t> wshare(out.share ? 0 : m * N * N);
+    Work<uint2> tasks(pk::ev_task_cap(N, m, lpt, pool_max));
+    const EvWork w{EqWork{ctrl.p, desc.p, tasks.p, tasks.n}, levels.p, wbets.p, wamount.p, out.share ? out.share : wshare.p};
+    a.out = out; a.w = w; a.lpt = lpt; a.m = m;
+    if (tbl) pk_sim::launch(prep_grid(m, EV_PREP_BLOCK), EV_PREP_BLOCK, [&] { k_ev_prep<N, true>(a); });
+    else pk_sim::launch(prep_grid(m, EV_PREP_BLOCK), EV_PREP_BLOCK, [&] { k_ev_prep<N, false>(a); });
+    printf("tasks %u take %u groups of %d levels\n", ctrl.p->ntasks, ctrl.p->ntasks >= 8u * grid * EQ_WAVES ? 4u : 1u, pk::ev_group(N));
+    pk_sim::launch(grid, EQ_BLOCK, [&] { k_ev<N>(tab, w, lpt); });
+    pk_sim::launch(prep_grid(m * N, EV_FINISH_BLOCK), EV_FINISH_BLOCK, [&] { k_ev_finish(w, out.ev, N, m); });
+}
+#endif
+
 }  // namespace
 
 int main(int argc, char **argv) {
     if (argc != 3) die("usage: equity_sim <case file> <out file>");
     Case c(argv[1]);
-    // the function-local __shared__ arrays of the six main kernels (the preparation kernels have none)
-    const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "5k_eqwILi"});
+    // the function-local __shared__ arrays of the seven main kernels (the preparation kernels have none)
+    const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "5k_eqwILi", "4k_evILi"});
     Work<uint32_t> tab(EVAL7_TAB_WORDS);
     for (int i = 0; i < EVAL7_TAB_WORDS; ++i) tab.p[i] = eval7_tab_entry((uint32_t)i);
     const auto t0 = std::chrono::steady_clock::now();
@@ -351,6 +390,13 @@ int main(int argc, char **argv) {
     if (c.family == "ranged") {
         if (N == 2) run_ranged<2>(c, tab.p); else if (N == 3) run_ranged<3>(c, tab.p); else if (N == 6) run_ranged<6>(c, tab.p); else if (N == 16) run_ranged<16>(c, tab.p);
         else die("k_eqw<N, RC>: this build has N = 2, 3, 6, 16");
+        ran = true;
+    }
+#endif
+#if PK_ES_HAS(7)
+    if (c.family == "ev") {
+        if (N == 2) run_ev<2>(c, tab.p); else if (N == 3) run_ev<3>(c, tab.p); else if (N == 5) run_ev<5>(c, tab.p); else if (N == 9) run_ev<9>(c, tab.p); else if (N == 16) run_ev<16>(c, tab.p);
+        else die("k_ev<N>: this build has N = 2, 3, 5, 9, 16");
         ran = true;
     }
 #endif

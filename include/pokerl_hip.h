@@ -801,6 +801,53 @@ int pk_table_equity_ev_d(pk_handle *h, const int32_t *tables_d, size_t m, uint64
                          uint32_t *boards_d, uint8_t *status_d);
 int pk_table_equity_ev(pk_handle *h, const int32_t *tables, size_t m, uint64_t *share, uint8_t *level_seat, double *amount, double *ev,
                        uint32_t *boards, uint8_t *status);
+/* ---- Histogram clustering: bucket strength histograms on the device -- exact k-means under the earth mover's distance (DESIGN.md section
+ * 3.8).  Everything is an integer; the device equals the numpy restatement tests/hist_cluster_spec.py bit for bit.
+ *
+ * POINTS: hist u16 [n][nbins], any rows -- for example an [m][1326][nbins] output of pk_equity_hist_d viewed flat; nbins 1 ..
+ * PK_EQ_HIST_MAX_BINS, n 1 .. 2^31 - 1.  The mass of row i is m_i = sum over b of hist[i][b]; a row with m_i = 0 is EMPTY (invalid holdings
+ * and refused spots are exactly these rows): label PK_CL_NONE, distance 0, it takes part in nothing.
+ * QUANTISED CDF: q[i][b] = floor(65535 * (hist[i][0] + ... + hist[i][b]) / m_i) as u16 (a 64-bit division, once per row and bin);
+ * q[i][nbins - 1] = 65535 always.
+ * DISTANCE: d(i, c) = sum over b of |q[i][b] - C[c][b]|, a u32 of at most 32 * 65535; d / 65535 is the earth mover's distance in bin units
+ * (histogram_emd's unit).  Against a centroid that is another row's q: |d / 65535 - histogram_emd| < nbins / 65535.
+ * CENTROIDS: C u16 [K][nbins], K 1 .. PK_CL_MAX_K.
+ * ASSIGN: label[i] = the SMALLEST c among those that minimise d(i, c); dist[i] = that d.
+ * UPDATE: n_c = rows with label c, S_c[b] = sum of q[i][b] over them (u64); C[c][b] = floor((S_c[b] + floor(n_c / 2)) / n_c); a cluster with
+ * n_c = 0 keeps its centroid.
+ * ONE ITERATION t = assign, then update from those labels; inertia[t] = sum of dist, changed[t] = labels that differ from the iteration
+ * before (the first iteration counts every non-empty row).  pk_hist_cluster runs EXACTLY `iters` iterations (1 .. 1024) and then one final
+ * assign -- inertia[iters] is its sum --, so the returned labels belong to the returned centroids.  changed = 0 is a fixed point: later
+ * iterations change nothing.  Inertia is NOT monotone (the mean does not minimise L1, and the centroids are rounded).
+ * SEEDING (k-means++ with LINEAR weights, exact): rounds j = 0 .. K - 1.  Round 0: w_i = 1 for a non-empty row, 0 for an empty one; later
+ * rounds: w_i = the smallest d(i, .) to the centroids chosen so far.  W = sum of w_i (fits u64 for every legal n);  r = (x * W) >> 64 with
+ * x = w0 | w1 << 32 of the Philox4x32-10 block with key (seed & 0xffffffff, seed >> 32) -- as pk_create -- and counter (j, 0, 'CLS0' =
+ * 0x434C5330, nonce); the chosen row is the smallest i whose inclusive prefix sum of w exceeds r, and its q becomes C[j].  W = 0 (every
+ * non-empty row coincides with a centroid): the lowest-index non-empty row.
+ * ERRORS, PK_E_INVALID_ARG before any launch: nbins, K, iters or n out of range, a NULL array that is needed; for seeding and clustering,
+ * whose centroids come from rows, also K > n, and in their host forms K larger than the number of non-empty rows (they see the rows).
+ * ASSIGN takes any n >= 1 with any K: one histogram against 4 096 centroids is its ordinary use.  The _d forms of seeding and clustering
+ * run asynchronously and cannot see the rows: THE CALLER MUST GUARANTEE AT LEAST ONE NON-EMPTY ROW.  With fewer non-empty rows than K the
+ * W = 0 rule repeats a row; with none pk_hist_cluster_seed_d still returns PK_OK and leaves centroids_d UNWRITTEN -- pk_hist_cluster_d
+ * would then iterate on whatever that buffer held.
+ * label u16 [n], dist u32 [n] (NULL: not wanted), inertia u64 [iters + 1], changed u32 [iters] (either NULL: not wanted).  The _d forms run
+ * asynchronously on `stream`; work space (q, the packed centroids, the seeding's distances and partial sums, the update's sums and counts)
+ * is the grow-only per-(device, stream) buffer of pk_equity_d.  The host forms are synchronous on a pooled stream.  Launches: seeding 1 + 2 K,
+ * assign 3, clustering 2 + 3 iters + 1.  NOT HERE: per-row multiplicities, squared distances, k-medians, a table form. */
+#define PK_CL_MAX_K 4096
+#define PK_CL_NONE 0xFFFFu
+int pk_hist_cluster_seed_d(int device, size_t n, int nbins, const uint16_t *hist_d, int K, uint64_t seed, uint32_t nonce,
+                           uint16_t *centroids_d /*[K][nbins]*/, void *stream);
+int pk_hist_cluster_assign_d(int device, size_t n, int nbins, const uint16_t *hist_d, int K, const uint16_t *centroids_d, uint16_t *label_d,
+                             uint32_t *dist_d /*NULL ok*/, void *stream);
+int pk_hist_cluster_d(int device, size_t n, int nbins, const uint16_t *hist_d, int K, uint16_t *centroids_d /*in: seeds, out: result*/, int iters,
+                      uint16_t *label_d, uint32_t *dist_d, uint64_t *inertia_d /*[iters+1], last = final assign*/, uint32_t *changed_d /*[iters]*/,
+                      void *stream);
+int pk_hist_cluster_seed(int device, size_t n, int nbins, const uint16_t *hist, int K, uint64_t seed, uint32_t nonce, uint16_t *centroids);
+int pk_hist_cluster_assign(int device, size_t n, int nbins, const uint16_t *hist, int K, const uint16_t *centroids, uint16_t *label,
+                           uint32_t *dist);
+int pk_hist_cluster(int device, size_t n, int nbins, const uint16_t *hist, int K, uint16_t *centroids, int iters, uint16_t *label,
+                    uint32_t *dist, uint64_t *inertia, uint32_t *changed);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

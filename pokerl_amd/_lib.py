@@ -26,6 +26,7 @@ EQ_PREFLOP, EQ_SMALL_POOL = 64, 128   # ... of pk_equity_range: nb < 3 / fewer p
 EQ_BAD_BET = 64   # ... of pk_equity_ev: a bet that is negative, NaN or infinite (the value of EQ_PREFLOP, which no EV call reports)
 EQ_HIST_MAX_BINS = 32   # PK_EQ_HIST_MAX_BINS: the most bins of a strength histogram
 EQ_HOLDINGS = 1326   # PK_EQ_HOLDINGS: unordered pairs of the 52 cards, h = b (b - 1) / 2 + a over canonical indices a < b
+CL_MAX_K, CL_NONE, CL_MAX_ITERS = 4096, 0xFFFF, 1024   # PK_CL_MAX_K, PK_CL_NONE; iterations of one pk_hist_cluster call at most
 EQS_SAMPLES_MAX = 1 << 24   # pk_equity_sampled: samples per call and spot at most
 EQW_MAX_RANGES, EQW_UNIFORM = 16, 0xFFFF   # pk_equity_ranged: rows of a call's weight table at most / the range_of entry "every weight 1"
 
@@ -48,7 +49,8 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_equity_rvr_d", "pk_equity_rvr", "pk_table_equity_rvr_d", "pk_table_equity_rvr",
            "pk_equity_hist_d", "pk_equity_hist", "pk_table_equity_hist_d", "pk_table_equity_hist",
            "pk_equity_ranged_d", "pk_equity_ranged", "pk_table_equity_ranged_d", "pk_table_equity_ranged",
-           "pk_equity_ev_d", "pk_equity_ev", "pk_table_equity_ev_d", "pk_table_equity_ev"]
+           "pk_equity_ev_d", "pk_equity_ev", "pk_table_equity_ev_d", "pk_table_equity_ev",
+           "pk_hist_cluster_seed_d", "pk_hist_cluster_assign_d", "pk_hist_cluster_d", "pk_hist_cluster_seed", "pk_hist_cluster_assign", "pk_hist_cluster"]
 
 
 class PokerlHipError(RuntimeError):
@@ -174,6 +176,12 @@ def lib():
     L.pk_equity_hist.argtypes = [C.c_int, C.c_size_t] + [_vp] * 4 + [C.c_int, C.c_int] + [_vp] * 4
     L.pk_table_equity_hist_d.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_int, C.c_int] + [_vp] * 4
     L.pk_table_equity_hist.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_int, C.c_int] + [_vp] * 4
+    L.pk_hist_cluster_seed_d.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, C.c_uint64, C.c_uint32, _vp, _vp]
+    L.pk_hist_cluster_seed.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, C.c_uint64, C.c_uint32, _vp]
+    L.pk_hist_cluster_assign_d.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]
+    L.pk_hist_cluster_assign.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, _vp, _vp, _vp]
+    L.pk_hist_cluster_d.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, _vp, C.c_int] + [_vp] * 5
+    L.pk_hist_cluster.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, _vp, C.c_int] + [_vp] * 4
     for name in SYMBOLS:
         if name not in ("pk_last_error", "pk_build_info", "pk_snapshot_bytes"):
             getattr(L, name).restype = C.c_int

@@ -22,6 +22,7 @@
 #include "pk_equity_range.hpp"
 #include "pk_equity_rvr.hpp"
 #include "pk_equity_hist.hpp"
+#include "pk_hist_cluster.hpp"
 #include "pk_snapshot.hpp"
 
 using namespace pk;
@@ -2553,6 +2554,130 @@ int pk_table_equity_hist(pk_handle *h, const int32_t *tables, size_t m, const ui
     if ((rc = table_equity_hist(h, g.at<int32_t>(idx), m, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, nbins, out.at(g), g.at<char>(work)))) return rc;
     HIPCHK(h, g.download(h->stream));
     return PK_OK;
+}
+
+
+// ---- histogram clustering (pokerl_hip.h "Histogram clustering"; kernels: pk_hist_cluster.hip).  Work space: the per-(device, stream) buffer.
+static_assert(CL_MAX_K == PK_CL_MAX_K && CL_NONE == PK_CL_NONE && CL_MAX_BINS == PK_EQ_HIST_MAX_BINS, "pk_hist_cluster.hpp and the ABI header agree");
+#define CL_CHECK(call, n, nbins, K, arrays)                                                                                                        \
+    if ((nbins) < 1 || (nbins) > PK_EQ_HIST_MAX_BINS) return g_fail(PK_E_INVALID_ARG, call ": nbins must be 1 .. PK_EQ_HIST_MAX_BINS (32)");       \
+    if ((n) < 1 || (n) >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, call ": n must be 1 .. 2^31 - 1");                                         \
+    if ((K) < 1 || (K) > PK_CL_MAX_K) return g_fail(PK_E_INVALID_ARG, call ": K must be 1 .. PK_CL_MAX_K (4096)");                                 \
+    if (!(arrays)) return g_fail(PK_E_INVALID_ARG, call ": NULL array")
+// seeding and clustering take their centroids from rows: K rows at least (assign labels any number of rows with any K)
+#define CL_CHECK_K_ROWS(call, n, K) \
+    if ((size_t)(K) > (n)) return g_fail(PK_E_INVALID_ARG, call ": K is larger than the number of rows")
+#define CL_CHECK_ITERS(call, iters) \
+    if ((iters) < 1 || (iters) > CL_MAX_ITERS) return g_fail(PK_E_INVALID_ARG, call ": iters must be 1 .. 1024")
+// the host forms see the rows: K non-empty ones at least
+static bool cl_enough_rows(size_t n, int nbins, const uint16_t *hist, int K) {
+    size_t live = 0;
+    for (size_t i = 0; i < n && live < (size_t)K; ++i) {
+        uint32_t mass = 0;
+        for (int b = 0; b < nbins; ++b) mass += hist[i * (size_t)nbins + b];
+        live += mass != 0;
+    }
+    return live >= (size_t)K;
+}
+#define CL_CHECK_ROWS(call, n, nbins, hist, K) \
+    if (!cl_enough_rows(n, nbins, hist, K)) return g_fail(PK_E_INVALID_ARG, call ": K is larger than the number of non-empty rows")
+
+int pk_hist_cluster_seed_d(int device, size_t n, int nbins, const uint16_t *hist_d, int K, uint64_t seed, uint32_t nonce, uint16_t *centroids_d,
+                           void *stream) {
+    CL_CHECK("pk_hist_cluster_seed_d", n, nbins, K, hist_d && centroids_d);
+    CL_CHECK_K_ROWS("pk_hist_cluster_seed_d", n, K);
+    ON_DEVICE_INDEX("pk_hist_cluster_seed_d", device, PK_MAX_DEVICES);
+    hipStream_t st = (hipStream_t)stream;
+    void *ws = eq_stream_ws(device, st, cl_work_bytes(n, nbins, K, true, false));
+    if (!ws) return g_fail(PK_E_OOM, "pk_hist_cluster_seed_d: out of device memory (work space)");
+    const hipError_t e = cl_seed_launch(st, n, nbins, hist_d, K, (uint32_t)seed, (uint32_t)(seed >> 32), nonce, centroids_d, cl_work(ws, n, nbins, K, true, false));
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_hist_cluster_seed_d: launch failed", e);
+    return PK_OK;
+}
+
+int pk_hist_cluster_assign_d(int device, size_t n, int nbins, const uint16_t *hist_d, int K, const uint16_t *centroids_d, uint16_t *label_d,
+                             uint32_t *dist_d, void *stream) {
+    CL_CHECK("pk_hist_cluster_assign_d", n, nbins, K, hist_d && centroids_d && label_d);
+    ON_DEVICE_INDEX("pk_hist_cluster_assign_d", device, PK_MAX_DEVICES);
+    hipStream_t st = (hipStream_t)stream;
+    void *ws = eq_stream_ws(device, st, cl_work_bytes(n, nbins, K, false, false));
+    if (!ws) return g_fail(PK_E_OOM, "pk_hist_cluster_assign_d: out of device memory (work space)");
+    const hipError_t e = cl_assign_launch(st, n, nbins, hist_d, K, centroids_d, label_d, dist_d, cl_work(ws, n, nbins, K, false, false));
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_hist_cluster_assign_d: launch failed", e);
+    return PK_OK;
+}
+
+int pk_hist_cluster_d(int device, size_t n, int nbins, const uint16_t *hist_d, int K, uint16_t *centroids_d, int iters, uint16_t *label_d,
+                      uint32_t *dist_d, uint64_t *inertia_d, uint32_t *changed_d, void *stream) {
+    CL_CHECK("pk_hist_cluster_d", n, nbins, K, hist_d && centroids_d && label_d);
+    CL_CHECK_K_ROWS("pk_hist_cluster_d", n, K);
+    CL_CHECK_ITERS("pk_hist_cluster_d", iters);
+    ON_DEVICE_INDEX("pk_hist_cluster_d", device, PK_MAX_DEVICES);
+    hipStream_t st = (hipStream_t)stream;
+    void *ws = eq_stream_ws(device, st, cl_work_bytes(n, nbins, K, false, true));
+    if (!ws) return g_fail(PK_E_OOM, "pk_hist_cluster_d: out of device memory (work space)");
+    const hipError_t e = cl_cluster_launch(st, n, nbins, hist_d, K, centroids_d, iters, label_d, dist_d, inertia_d, changed_d, cl_work(ws, n, nbins, K, false, true));
+    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_hist_cluster_d: launch failed", e);
+    return PK_OK;
+}
+
+// The host forms: one staging buffer (inputs, outputs, work space) on a pooled stream; launch(g, work) queues the kernels
+extern "C++" {
+template <typename F>
+static int cl_host_call(const char *call, int device, Stage &g, size_t work_bytes, F launch) {
+    hipStream_t st = nullptr;
+    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, (std::string(call) + ": no stream").c_str()); }
+    int rc = PK_OK;
+    {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        const int work = g.add(work_bytes);
+        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, (std::string(call) + ": out of device memory").c_str());
+        else {
+            const hipError_t e = g.run(st, [&] { return launch(st, g.at<char>(work)); });
+            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, call, e); }   // (the lock is held until what was queued is done)
+        }
+    }
+    stream_release(device, st);
+    return rc;
+}
+}  // extern "C++" (a template)
+
+int pk_hist_cluster_seed(int device, size_t n, int nbins, const uint16_t *hist, int K, uint64_t seed, uint32_t nonce, uint16_t *centroids) {
+    CL_CHECK("pk_hist_cluster_seed", n, nbins, K, hist && centroids);
+    CL_CHECK_K_ROWS("pk_hist_cluster_seed", n, K);
+    CL_CHECK_ROWS("pk_hist_cluster_seed", n, nbins, hist, K);
+    ON_DEVICE_INDEX("pk_hist_cluster_seed", device, PK_MAX_DEVICES);
+    Stage g;
+    const int hi = g.in(hist, n * (size_t)nbins * 2), ce = g.out(centroids, (size_t)K * nbins * 2);
+    return cl_host_call("pk_hist_cluster_seed", device, g, cl_work_bytes(n, nbins, K, true, false), [&](hipStream_t st, char *work) {
+        return cl_seed_launch(st, n, nbins, g.at<uint16_t>(hi), K, (uint32_t)seed, (uint32_t)(seed >> 32), nonce, g.at<uint16_t>(ce), cl_work(work, n, nbins, K, true, false));
+    });
+}
+
+int pk_hist_cluster_assign(int device, size_t n, int nbins, const uint16_t *hist, int K, const uint16_t *centroids, uint16_t *label, uint32_t *dist) {
+    CL_CHECK("pk_hist_cluster_assign", n, nbins, K, hist && centroids && label);
+    ON_DEVICE_INDEX("pk_hist_cluster_assign", device, PK_MAX_DEVICES);
+    Stage g;
+    const int hi = g.in(hist, n * (size_t)nbins * 2), ce = g.in(centroids, (size_t)K * nbins * 2), la = g.out(label, n * 2), di = g.out(dist, n * 4);
+    return cl_host_call("pk_hist_cluster_assign", device, g, cl_work_bytes(n, nbins, K, false, false), [&](hipStream_t st, char *work) {
+        return cl_assign_launch(st, n, nbins, g.at<uint16_t>(hi), K, g.at<uint16_t>(ce), g.at<uint16_t>(la), g.at<uint32_t>(di), cl_work(work, n, nbins, K, false, false));
+    });
+}
+
+int pk_hist_cluster(int device, size_t n, int nbins, const uint16_t *hist, int K, uint16_t *centroids, int iters, uint16_t *label, uint32_t *dist,
+                    uint64_t *inertia, uint32_t *changed) {
+    CL_CHECK("pk_hist_cluster", n, nbins, K, hist && centroids && label);
+    CL_CHECK_K_ROWS("pk_hist_cluster", n, K);
+    CL_CHECK_ITERS("pk_hist_cluster", iters);
+    CL_CHECK_ROWS("pk_hist_cluster", n, nbins, hist, K);
+    ON_DEVICE_INDEX("pk_hist_cluster", device, PK_MAX_DEVICES);
+    Stage g;
+    const int hi = g.in(hist, n * (size_t)nbins * 2), ce = g.add((size_t)K * nbins * 2, centroids, centroids), la = g.out(label, n * 2), di = g.out(dist, n * 4);
+    const int in = g.out(inertia, (size_t)(iters + 1) * 8), ch = g.out(changed, (size_t)iters * 4);
+    return cl_host_call("pk_hist_cluster", device, g, cl_work_bytes(n, nbins, K, false, true), [&](hipStream_t st, char *work) {
+        return cl_cluster_launch(st, n, nbins, g.at<uint16_t>(hi), K, g.at<uint16_t>(ce), iters, g.at<uint16_t>(la), g.at<uint32_t>(di), g.at<uint64_t>(in),
+                                 g.at<uint32_t>(ch), cl_work(work, n, nbins, K, false, true));
+    });
 }
 
 }  // extern "C"

@@ -906,6 +906,11 @@ class StrengthHistogram:
     def __getitem__(self, i):
         return StrengthHistogram(self.hist[i], self.void[i], self.completions[i], self.status[i], None if self.valid is None else self.valid[i])
 
+    def cluster(self, k, iters=20, seed=DEFAULT_SEED, nonce=0, init=None, device=0):
+        """cluster_histograms over every row of `hist`: labels come back in the shape of `hist` without its last axis ([1326] or [m, 1326]),
+        PK_CL_NONE (0xFFFF) at the invalid holdings and refused spots, whose rows are empty."""
+        return cluster_histograms(self.hist, k, iters=iters, seed=seed, nonce=nonce, init=init, device=device)
+
     def __repr__(self):
         return 'StrengthHistogram(bins=%r, completions=%r, status=%r)' % (self.bins, self.completions, self.status)
 
@@ -973,3 +978,139 @@ def strength_histogram(board, dead=(), weights=None, bins=10, device=0):
     if r.status:
         raise ValueError('invalid spot: ' + equity_status_text(r.status))
     return r
+
+
+# ---------------------------------------------------------------------------------------------- histogram clustering
+# Buckets of strength histograms: exact k-means under the earth mover's distance on the device (pk_hist_cluster; the definition:
+# include/pokerl_hip.h "Histogram clustering").  Every quantity is an integer.
+CL_NONE = L.CL_NONE      # the label of an empty row (an invalid holding, a refused spot)
+
+
+def _cl_rows(hist):
+    """hist [..., bins] counts -> (uint16 [n, bins] C-contiguous, the leading shape); ValueError otherwise (before any device call)."""
+    a = np.asarray(hist)
+    if a.ndim < 2 or not 1 <= a.shape[-1] <= L.EQ_HIST_MAX_BINS:
+        raise ValueError('hist must have shape [..., bins] with bins 1 .. %d' % L.EQ_HIST_MAX_BINS)
+    if a.dtype != np.uint16:
+        if a.dtype.kind not in 'iu' or (a.size and (a.min() < 0 or a.max() > 65535)):
+            raise ValueError('hist must hold integers 0 .. 65535')
+    lead = a.shape[:-1]
+    flat = np.ascontiguousarray(a.reshape(-1, a.shape[-1]), np.uint16)
+    if not 1 <= flat.shape[0] < 2 ** 31:
+        raise ValueError('hist must have 1 .. 2^31 - 1 rows')
+    return flat, lead
+
+
+def _cl_int(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError('%s must be an integer %d .. %d' % (name, lo, hi))
+    return int(v)
+
+
+def _cl_k(k, flat):
+    k = _cl_int('k', k, 1, L.CL_MAX_K)
+    live = int(np.count_nonzero(flat.any(axis=1)))
+    if k > live:
+        raise ValueError('k = %d is larger than the number of non-empty rows (%d)' % (k, live))
+    return k
+
+
+def _cl_centroids(centroids, bins, name='centroids'):
+    c = np.asarray(centroids)
+    if c.ndim != 2 or c.shape[1] != bins or not 1 <= c.shape[0] <= L.CL_MAX_K:
+        raise ValueError('%s must have shape [k, %d] with k 1 .. %d' % (name, bins, L.CL_MAX_K))
+    if c.dtype != np.uint16 and (c.dtype.kind not in 'iu' or c.min() < 0 or c.max() > 65535):
+        raise ValueError('%s must hold integers 0 .. 65535 (quantised CDFs)' % name)
+    return np.ascontiguousarray(c, np.uint16)
+
+
+class HistogramClusters:
+    """The result of cluster_histograms: centroids uint16 [k, bins] (quantised CDFs, 65535 = 1), labels uint16 [...] (PK_CL_NONE = 0xFFFF for an
+    empty row) and dist uint32 [...] in the leading shape of the input, inertia uint64 [iterations run + 1] (the last entry belongs to the
+    returned labels), changed uint32 [iterations run].  `emd` = dist / 65535, the earth mover's distance to the row's centroid in bins
+    (histogram_emd's unit).  assign(hist) labels further rows with the learned centroids."""
+
+    def __init__(self, centroids, labels, dist, inertia, changed, device=0):
+        self.centroids, self.labels, self.dist, self.inertia, self.changed, self.device = centroids, labels, dist, inertia, changed, device
+
+    @property
+    def k(self):
+        return self.centroids.shape[0]
+
+    @property
+    def bins(self):
+        return self.centroids.shape[1]
+
+    @property
+    def emd(self):
+        return np.asarray(self.dist, np.float64) / 65535.0
+
+    def assign(self, hist):
+        """(labels, dist) of the rows of hist [..., bins] under these centroids."""
+        return assign_histograms(hist, self.centroids, device=self.device)
+
+    def __repr__(self):
+        return 'HistogramClusters(k=%d, bins=%d, iterations=%d, inertia=%d)' % (self.k, self.bins, len(self.changed), int(self.inertia[-1]))
+
+
+def seed_histogram_centroids(hist, k, seed=DEFAULT_SEED, nonce=0, device=0):
+    """pk_hist_cluster_seed on host arrays: exact k-means++ with linear weights -> centroids uint16 [k, bins]."""
+    flat, _ = _cl_rows(hist)
+    k = _cl_k(k, flat)
+    seed, nonce = _cl_int('seed', seed, 0, 2 ** 64 - 1), _cl_int('nonce', nonce, 0, 2 ** 32 - 1)
+    cen = np.zeros((k, flat.shape[1]), np.uint16)
+    L.check(L.lib().pk_hist_cluster_seed(int(device), flat.shape[0], flat.shape[1], L.ptr(flat), k, seed, nonce, L.ptr(cen)))
+    return cen
+
+
+def assign_histograms(hist, centroids, device=0):
+    """pk_hist_cluster_assign on host arrays -> (labels uint16, dist uint32) in the leading shape of hist: the nearest centroid (the smallest
+    index among equals) and the distance to it; PK_CL_NONE and 0 for an empty row.  Any number of rows against any number of centroids."""
+    flat, lead = _cl_rows(hist)
+    cen = _cl_centroids(centroids, flat.shape[1])
+    label, dist = np.zeros(flat.shape[0], np.uint16), np.zeros(flat.shape[0], np.uint32)
+    L.check(L.lib().pk_hist_cluster_assign(int(device), flat.shape[0], flat.shape[1], L.ptr(flat), cen.shape[0], L.ptr(cen), L.ptr(label), L.ptr(dist)))
+    return label.reshape(lead), dist.reshape(lead)
+
+
+def cluster_histograms(hist, k, iters=20, seed=DEFAULT_SEED, nonce=0, init=None, device=0):
+    """Buckets the rows of hist [..., bins] into k clusters: seeds (seed_histogram_centroids; `init`: a [k, bins] uint16 centroid array to
+    start from instead), then ONE pk_hist_cluster call of `iters` iterations: ALL `iters` ARE ALWAYS PAID FOR on the device, also by a run
+    that settles early.  An iteration that changes no label is a fixed point -- the iterations after it are no-ops --, so `inertia` and
+    `changed` are cut there: the result is that of stopping.  -> HistogramClusters."""
+    flat, lead = _cl_rows(hist)
+    k = _cl_k(k, flat)
+    iters = _cl_int('iters', iters, 1, L.CL_MAX_ITERS)
+    if init is None:
+        cen = seed_histogram_centroids(flat, k, seed=seed, nonce=nonce, device=device)
+    else:
+        cen = _cl_centroids(init, flat.shape[1], 'init').copy()
+        if cen.shape[0] != k:
+            raise ValueError('init must have shape [k, bins]')
+    n = flat.shape[0]
+    label, dist = np.zeros(n, np.uint16), np.zeros(n, np.uint32)
+    inertia, changed = np.zeros(iters + 1, np.uint64), np.zeros(iters, np.uint32)
+    L.check(L.lib().pk_hist_cluster(int(device), n, flat.shape[1], L.ptr(flat), k, L.ptr(cen), iters, L.ptr(label), L.ptr(dist), L.ptr(inertia),
+                                    L.ptr(changed)))
+    still = np.flatnonzero(changed == 0)
+    ran = int(still[0]) + 1 if still.size else iters
+    return HistogramClusters(cen, label.reshape(lead), dist.reshape(lead), np.concatenate([inertia[:ran], inertia[-1:]]), changed[:ran], device)
+
+
+def seed_histogram_centroids_d(n, bins, hist_d, k, centroids_d, seed=DEFAULT_SEED, nonce=0, device=0, stream=None):
+    """pk_hist_cluster_seed_d: seeding on device-resident buffers (device pointers as ints / c_void_p), asynchronous on `stream`."""
+    L.check(L.lib().pk_hist_cluster_seed_d(int(device), int(n), check_bins(bins), hist_d, _cl_int('k', k, 1, L.CL_MAX_K),
+                                           _cl_int('seed', seed, 0, 2 ** 64 - 1), _cl_int('nonce', nonce, 0, 2 ** 32 - 1), centroids_d, stream))
+
+
+def assign_histograms_d(n, bins, hist_d, k, centroids_d, label_d, dist_d=None, device=0, stream=None):
+    """pk_hist_cluster_assign_d: hist uint16 [n, bins], centroids uint16 [k, bins] -> label uint16 [n], dist uint32 [n] (None: not wanted)."""
+    L.check(L.lib().pk_hist_cluster_assign_d(int(device), int(n), check_bins(bins), hist_d, _cl_int('k', k, 1, L.CL_MAX_K), centroids_d, label_d, dist_d,
+                                             stream))
+
+
+def cluster_histograms_d(n, bins, hist_d, k, centroids_d, iters, label_d, dist_d=None, inertia_d=None, changed_d=None, device=0, stream=None):
+    """pk_hist_cluster_d: EXACTLY `iters` iterations from the centroids in centroids_d (in: seeds, out: result) and one final assign;
+    inertia uint64 [iters + 1], changed uint32 [iters] (None: not wanted).  Asynchronous on `stream`."""
+    L.check(L.lib().pk_hist_cluster_d(int(device), int(n), check_bins(bins), hist_d, _cl_int('k', k, 1, L.CL_MAX_K), centroids_d,
+                                      _cl_int('iters', iters, 1, L.CL_MAX_ITERS), label_d, dist_d, inertia_d, changed_d, stream))

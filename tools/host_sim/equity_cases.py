@@ -24,6 +24,9 @@ The shapes are the smallest at which each mechanism of the kernels can break (do
                    valid ones; five live seats on a ladder -- four levels to compare, the smallest spot that needs a second group of levels;
                    ladders at 9 and 16 seats; dead money, a live seat with bet 0, one live seat, all bets 0; each output NULL in turn; the
                    table form with bets + pending_bets.  f64 arrays travel as their bit patterns: amount and ev are compared bit for bit;
+  k_cl_*           (cluster_cases, run beside all_cases by this program and by tests/test_hist_cluster_sim_host.py) quantise / assign / update /
+                   finalise / seed as pk::cl_*_launch queues them; 1, 2, 7, 10 and 32 bins; a grid of 1 (every workgroup strides), an unaligned
+                   histogram pointer, empty rows as whole waves, constructed ties, both update kernels, seeding over several chunks and tiles.
   preparation      every status bit, the explicit and the table form; table indices -1, T and 2^31 - 1 (nothing is read: ASan's to check).
 
   equity_cases.py --exe <equity_sim> [--exe <another build>] [--quick] [--only <substring>] [--list] [--keep <dir>]
@@ -48,6 +51,7 @@ import equity_ranged_spec as WS         # noqa: E402
 import equity_sampled_spec as SS        # noqa: E402
 import equity_spec as ES                # noqa: E402
 import ev_spec as EV                    # noqa: E402
+import hist_cluster_spec as CS          # noqa: E402
 import hist_spec as HS                  # noqa: E402
 import rvr_spec as VS                   # noqa: E402
 from oracle import rng_spec as R        # noqa: E402
@@ -58,7 +62,8 @@ DTYPES = {"u8": np.uint8, "u16": np.uint16, "u32": np.uint32, "u64": np.uint64, 
 OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("win", "tie", "share", "samples", "status"),
            "range": ("agg", "win", "tie", "boards", "status"), "rvr": ("win", "tie", "tot", "boards", "status"),
            "hist": ("hist", "void", "completions", "status"), "ranged": ("win", "tie", "share", "accepted", "status"),
-           "ev": ("share", "level_seat", "amount", "ev", "boards", "status")}
+           "ev": ("share", "level_seat", "amount", "ev", "boards", "status"),
+           "cluster": ("centroids_out", "label", "dist", "inertia", "changed")}
 
 
 class Case:
@@ -679,6 +684,98 @@ def ev_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- histogram clustering
+def cluster_case(name, op, hist, K, grid, centroids=None, iters=None, seed=None, nonce=0, chunk=None, lds=None, skew=0, quick=False):
+    """op 0: seeding -> centroids; 1: assign -> label, dist; 2: `iters` iterations and the final assign.  Expected: tests/hist_cluster_spec.py."""
+    hist = np.ascontiguousarray(hist, np.uint16)
+    n, nbins = hist.shape
+    arrays = {"n": ("u32", [n]), "nbins": ("u32", [nbins]), "K": ("u32", [K]), "op": ("u32", [op]), "grid": ("u32", [grid]),
+              "skew": ("u32", [skew]), "hist": ("u16", np.concatenate([np.full(skew, 0xABCD, np.uint16), hist.reshape(-1)]))}
+    if chunk is not None:
+        arrays["chunk"] = ("u32", [chunk])
+    if lds is not None:
+        arrays["lds"] = ("u32", [lds])
+    if op == 0:
+        arrays.update(key0=("u32", [seed & 0xFFFFFFFF]), key1=("u32", [seed >> 32]), nonce=("u32", [nonce]))
+
+        def expect():
+            q, empty = CS.quant(hist)
+            return {"centroids": CS.seed(q, empty, K, seed, nonce)[0]}
+        return Case(name, "cluster", arrays, expect, ("centroids",), quick)
+    centroids = np.ascontiguousarray(centroids, np.uint16)
+    assert centroids.shape == (K, nbins)
+    arrays["centroids"] = ("u16", centroids)
+    if op == 1:
+        def expect():
+            q, empty = CS.quant(hist)
+            label, dist = CS.assign(q, empty, centroids)
+            return {"label": label, "dist": dist}
+        return Case(name, "cluster", arrays, expect, ("label", "dist"), quick)
+    arrays["iters"] = ("u32", [iters])
+
+    def expect():
+        q, empty = CS.quant(hist)
+        r = CS.iterate(q, empty, centroids, iters)
+        return {"centroids_out": r["centroids"], "label": r["labels"], "dist": r["dist"], "inertia": r["inertia"], "changed": r["changed"]}
+    return Case(name, "cluster", arrays, expect, None, quick)
+
+
+def cluster_rows(seed, n, nbins, empties=()):
+    rng = np.random.default_rng(seed)
+    hist = CS.latent_rows(rng, n, nbins, mass=46, shapes=5, empty_frac=0.1)
+    for a, b in empties:
+        hist[a:b] = 0
+    return hist
+
+
+def cluster_centroids(seed, hist, K):
+    """K centroids near the data: the q of random non-empty rows, some nudged (kept non-decreasing)."""
+    rng = np.random.default_rng(seed)
+    q, empty = CS.quant(hist)
+    C = q[rng.choice(np.flatnonzero(~empty), K)].astype(np.int64)
+    C[::2] = np.sort(np.clip(C[::2] + rng.integers(-900, 900, C[::2].shape), 0, 65535), axis=1)
+    return C.astype(np.uint16)
+
+
+def cluster_cases():
+    cs = []
+    for nbins in (1, 2, 7, 10, 32):
+        # 300 rows = two workgroups' worth on a grid of 1: the workgroup strides; empty rows first, last and as a whole wave; an unaligned pointer
+        hist = cluster_rows(200 + nbins, 300, nbins, empties=((0, 3), (64, 128), (297, 300)))
+        cs.append(cluster_case("cluster-assign-b%d" % nbins, 1, hist, 5, 1, centroids=cluster_centroids(1, hist, 5), skew=(nbins % 3), quick=True))
+        cs.append(cluster_case("cluster-iterate-b%d" % nbins, 2, hist, 6, 2, centroids=cluster_centroids(2, hist, 6), iters=3, quick=nbins in (7, 32)))
+    # assign takes any K: one row and 63 rows against 2, 3 (one more than the kernel's unroll of two) and more centroids than rows
+    wide = cluster_rows(209, 400, 10)
+    for n, K in ((1, 2), (1, 3), (1, 70), (63, 2), (63, 3), (63, 70)):
+        few = wide[wide.any(axis=1)][:n] if n == 1 else wide[:n]
+        cs.append(cluster_case("cluster-assign-n%d-K%d" % (n, K), 1, few, K, 1, centroids=cluster_centroids(10 + K, wide, K), quick=True))
+    hist = cluster_rows(210, 700, 7, empties=((640, 700),))
+    cs.append(cluster_case("cluster-iterate-global-sums", 2, hist, 9, 2, centroids=cluster_centroids(3, hist, 9), iters=2, lds=0, quick=True))
+    cs.append(cluster_case("cluster-iterate-K1", 2, hist[:65], 1, 1, centroids=cluster_centroids(4, hist, 1), iters=2, quick=True))
+    # ties: duplicated rows, two identical centroids (the smaller index wins, the larger stays empty and keeps its centroid), a row midway
+    t = np.zeros((70, 4), np.uint16)
+    t[:, 3] = 4
+    t[::3] = [4, 0, 0, 0]
+    t[1::3] = [0, 0, 0, 4]
+    t[2::3] = [2, 0, 0, 2]                                            # q = (32767, 32767, 32767, 65535): between the two below
+    t[5] = 0
+    tc = np.array([[65535, 65535, 65535, 65535], [0, 0, 0, 65535], [0, 0, 0, 65535], [65534, 65535, 65535, 65535]], np.uint16)
+    cs.append(cluster_case("cluster-ties-assign", 1, t, 4, 1, centroids=tc, quick=True))
+    cs.append(cluster_case("cluster-ties-iterate", 2, t, 4, 1, centroids=tc, iters=2, quick=True))
+    # seeding: three chunks of one tile, two chunks of two tiles, one row; K = 1, 2, 33
+    for K, chunk in ((1, 256), (2, 256), (33, 256), (5, 512)):
+        cs.append(cluster_case("cluster-seed-K%d-chunk%d" % (K, chunk), 0, hist, K, 2, seed=R.DEFAULT_SEED + K, nonce=K, chunk=chunk, quick=K != 2))
+    cs.append(cluster_case("cluster-seed-one-row", 0, hist[:1], 1, 1, seed=7, quick=True))
+    same = np.zeros((300, 10), np.uint16)
+    same[:] = [1, 0, 3, 0, 0, 9, 0, 0, 2, 1]
+    same[:70] = 0
+    same[200:264] = 0
+    cs.append(cluster_case("cluster-seed-identical-rows", 0, same, 3, 1, seed=11, nonce=2, quick=True))   # W = 0 from round 1 on
+    cs.append(cluster_case("cluster-iterate-identical-rows", 2, same, 3, 1, centroids=np.tile(CS.quant(same)[0][70], (3, 1)), iters=1, quick=True))
+    assert len({c.name for c in cs}) == len(cs) and all(c.name.startswith("cluster-") for c in cs)
+    return cs
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -693,7 +790,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + cluster_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

@@ -9,7 +9,9 @@
 //   equity_sim <case file> <out file>
 // Case file: lines "name dtype count" (dtype u8 u16 u32 u64 i32) each followed by a line of `count` decimal values, and
 // "family <name>" / "outputs <name> ..." lines.  Out file: the same array format.
-// -DPK_ES_ONLY=1 .. 7: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev), so that a test can compile them side by side.
+// -DPK_ES_ONLY=1 .. 8: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster), so that a test can compile them side by side.
+// The cluster family (pk_hist_cluster.hip) has no preparation kernel: the driver queues its kernels in the order of pk::cl_seed_launch /
+// cl_assign_launch / cl_cluster_launch (`op` 0 / 1 / 2), with the case's grid, seeding chunk and choice of the update kernel.
 // f64 arrays (the bets, amounts and ev of the ev family) travel as their bit patterns, dtype u64.
 #ifndef PK_ES_ONLY
 #define PK_ES_ONLY 0
@@ -39,6 +41,11 @@
 
 #if PK_ES_HAS(7)
 #include "../../pokerl_amd/csrc/pk_equity_ev.hip"
+#endif
+
+#if PK_ES_HAS(8)
+#include "../../pokerl_amd/csrc/pk_equity.hpp"          // (EqTables, which the driver's table_form names)
+#include "../../pokerl_amd/csrc/pk_hist_cluster.hip"
 #endif
 
 #include <chrono>
@@ -350,13 +357,88 @@ void run_ev(Case &c, const uint32_t *tab) {
 }
 #endif
 
+#if PK_ES_HAS(8)
+template <int P = 1, typename F>
+void cl_with_pairs(int pairs, F f) {
+    if constexpr (P <= CL_ROW_DWORDS) {
+        if (pairs == P) f(std::integral_constant<int, P>{}); else cl_with_pairs<P + 1>(pairs, f);
+    } else die("pairs outside 1 .. 16");
+}
+void run_cluster(Case &c) {
+    const size_t n = (size_t)c.num("n");
+    const int nbins = (int)c.num("nbins"), K = (int)c.num("K"), op = (int)c.num("op"), pairs = pk::cl_pairs(nbins);
+    const unsigned grid = (unsigned)c.num("grid");
+    const size_t skew = (size_t)c.num("skew", 0);                    // u16 entries before the first row: an array that is not 16-byte aligned
+    const uint16_t *hist = c.need<uint16_t>("hist", n * nbins + skew) + skew;
+    Work<uint32_t> q(n * pairs), cp((size_t)K * CL_ROW_DWORDS);
+    pk_sim::launch(grid, CL_BLOCK, [&] { k_cl_quant(hist, q.p, (uint32_t)nbins, (uint64_t)n); });
+    const uint32_t *qp = q.p, *cpp = cp.p;
+    auto assign = [&](uint16_t *label, uint32_t *dist, int mode, uint32_t *changed, uint64_t *inertia) {
+        cl_with_pairs(pairs, [&](auto pc) {
+            pk_sim::launch(grid, CL_BLOCK, [&] { k_cl_assign<decltype(pc)::value>(qp, cpp, (uint32_t)K, (uint64_t)n, label, dist, mode, changed, (cl_u64 *)inertia); });
+        });
+    };
+    if (op == 0) {
+        const uint64_t chunk = (uint64_t)c.num("chunk", (long long)pk::cl_chunk_rows(n));
+        if (chunk == 0 || chunk % CL_BLOCK) die("chunk: a multiple of the workgroup's width");
+        const uint32_t nchunks = (uint32_t)((n + chunk - 1) / chunk);
+        Work<uint32_t> mind(n);
+        Work<uint64_t> part(nchunks), rows(nchunks);
+        uint16_t *cen = c.output<uint16_t>("centroids", "u16", (size_t)K * nbins);
+        if (!cen) die("seeding needs the centroids output");
+        const uint32_t key0 = (uint32_t)c.num("key0"), key1 = (uint32_t)c.num("key1"), nonce = (uint32_t)c.num("nonce");
+        for (int j = 0; j < K; ++j) {
+            const uint32_t *newest = j ? cp.p + (size_t)(j - 1) * CL_ROW_DWORDS : nullptr;
+            uint64_t *out = j ? part.p : rows.p;
+            const int mode = j == 0 ? 0 : (j == 1 ? 1 : 2);
+            cl_with_pairs(pairs, [&](auto pc) {
+                pk_sim::launch(nchunks, CL_BLOCK, [&] { k_cl_seed_dist<decltype(pc)::value>(qp, newest, mind.p, out, (uint64_t)n, chunk, mode); });
+            });
+            pk_sim::launch(1, CL_BLOCK, [&] { k_cl_seed_pick(qp, mind.p, part.p, rows.p, nchunks, chunk, (uint64_t)n, (uint32_t)j, key0, key1, nonce, (uint32_t)nbins, cen, cp.p); });
+        }
+        return;
+    }
+    const uint16_t *cin = c.need<uint16_t>("centroids", (size_t)K * nbins);
+    uint16_t *label = c.output<uint16_t>("label", "u16", n);
+    uint32_t *dist = c.output<uint32_t>("dist", "u32", n);
+    if (!label) die("assign and cluster need the label output");
+    if (op == 1) {
+        pk_sim::launch((unsigned)((K * CL_ROW_DWORDS + CL_BLOCK - 1) / CL_BLOCK), CL_BLOCK, [&] { k_cl_pack(cin, cp.p, (uint32_t)nbins, (uint32_t)K); });
+        assign(label, dist, 0, nullptr, nullptr);
+        return;
+    }
+    const int iters = (int)c.num("iters");
+    uint16_t *cen = c.output<uint16_t>("centroids_out", "u16", (size_t)K * nbins);
+    uint64_t *inertia = c.output<uint64_t>("inertia", "u64", (size_t)iters + 1);
+    uint32_t *changed = c.output<uint32_t>("changed", "u32", (size_t)iters);
+    if (!cen) die("cluster needs the centroids_out output");
+    memcpy(cen, cin, (size_t)K * nbins * 2);                         // (in: seeds, out: result)
+    Work<uint64_t> sums((size_t)K * nbins);
+    Work<uint32_t> counts((size_t)K);
+    memset(sums.p, 0, sums.n * 8); memset(counts.p, 0, counts.n * 4);   // (cl_cluster_launch's fills)
+    if (inertia) memset(inertia, 0, ((size_t)iters + 1) * 8);
+    if (changed) memset(changed, 0, (size_t)iters * 4);
+    const bool lds = c.num("lds", (size_t)K * nbins <= (size_t)CL_LDS_SUMS) != 0;
+    if (lds && (size_t)K * nbins > (size_t)CL_LDS_SUMS) die("lds: K * nbins does not fit");
+    pk_sim::launch((unsigned)((K * CL_ROW_DWORDS + CL_BLOCK - 1) / CL_BLOCK), CL_BLOCK, [&] { k_cl_pack(cin, cp.p, (uint32_t)nbins, (uint32_t)K); });
+    for (int t = 0; t < iters; ++t) {
+        assign(label, nullptr, t == 0 ? 1 : 2, changed ? changed + t : nullptr, inertia ? inertia + t : nullptr);
+        if (lds) pk_sim::launch(grid, CL_BLOCK, [&] { k_cl_update<true>(qp, label, (uint32_t)nbins, (uint32_t)K, (uint64_t)n, (cl_u64 *)sums.p, counts.p); });
+        else pk_sim::launch(grid, CL_BLOCK, [&] { k_cl_update<false>(qp, label, (uint32_t)nbins, (uint32_t)K, (uint64_t)n, (cl_u64 *)sums.p, counts.p); });
+        pk_sim::launch((unsigned)((K + CL_BLOCK - 1) / CL_BLOCK), CL_BLOCK, [&] { k_cl_finalise((cl_u64 *)sums.p, counts.p, cen, cp.p, (uint32_t)nbins, (uint32_t)K); });
+    }
+    assign(label, dist, 0, nullptr, inertia ? inertia + iters : nullptr);
+}
+#endif
+
 }  // namespace
 
 int main(int argc, char **argv) {
     if (argc != 3) die("usage: equity_sim <case file> <out file>");
     Case c(argv[1]);
-    // the function-local __shared__ arrays of the seven main kernels (the preparation kernels have none)
-    const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "5k_eqwILi", "4k_evILi"});
+    // the function-local __shared__ arrays of the main kernels (the preparation kernels have none)
+    const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "5k_eqwILi", "4k_evILi", "10k_cl_quant", "11k_cl_assign",
+                                        "11k_cl_update", "14k_cl_seed_dist", "14k_cl_seed_pick"});
     Work<uint32_t> tab(EVAL7_TAB_WORDS);
     for (int i = 0; i < EVAL7_TAB_WORDS; ++i) tab.p[i] = eval7_tab_entry((uint32_t)i);
     const auto t0 = std::chrono::steady_clock::now();
@@ -399,6 +481,9 @@ int main(int argc, char **argv) {
         else die("k_ev<N>: this build has N = 2, 3, 5, 9, 16");
         ran = true;
     }
+#endif
+#if PK_ES_HAS(8)
+    if (c.family == "cluster") { run_cluster(c); ran = true; }
 #endif
     if (!ran) die("family " + c.family + ": not in this build");
     c.write(argv[2]);

@@ -50,6 +50,11 @@ struct MaxU32 { static constexpr const char *label = "v_max_u32";
     static __device__ __forceinline__ void dep(unsigned &a, unsigned b) { asm volatile("v_max_u32 %0, %0, %1" : "+v"(a) : "v"(b)); } };
 struct Bcnt { static constexpr const char *label = "v_bcnt_u32_b32";
     static __device__ __forceinline__ void dep(unsigned &a, unsigned b) { asm volatile("v_bcnt_u32_b32 %0, %0, %1" : "+v"(a) : "v"(b)); } };
+// the histogram clustering's inner instruction (pk_hist_cluster.hip): the accumulator chain, with the centroid operand in a VGPR and in an SGPR
+struct SadU16 { static constexpr const char *label = "v_sad_u16";
+    static __device__ __forceinline__ void dep(unsigned &a, unsigned b) { asm volatile("v_sad_u16 %0, %1, %1, %0" : "+v"(a) : "v"(b)); } };
+struct SadU16S { static constexpr const char *label = "v_sad_u16 (sgpr operand)";
+    static __device__ __forceinline__ void dep(unsigned &a, unsigned b) { asm volatile("v_sad_u16 %0, %1, %2, %0" : "+v"(a) : "v"(b), "s"(0x12345678u)); } };
 
 template <typename OP, int ILP>
 __global__ void __launch_bounds__(256) k32(int iters, unsigned *sink) {
@@ -148,7 +153,7 @@ int main() {
 #define R32(OP) row(OP::label, k32<OP, 1>, s32, 1); row(OP::label, k32<OP, 8>, s32, 8);
 #define R64(OP) row(OP::label, k64<OP, 1>, s64, 1); row(OP::label, k64<OP, 8>, s64, 8);
     R32(AddU32) R32(XorB32) R32(AndB32) R32(Cndmask) R32(CndmaskSgpr) R32(CmpCnd) R32(CmpCndS) R32(LshlRev) R32(Bcnt) R32(MulU24) R32(MulLo) R32(MulHi)
-    R32(Bfe) R32(Perm) R32(Or3) R32(Max3) R32(MaxU32) R32(Bitop3) R32(LshlOr) R32(Ffbh)
+    R32(Bfe) R32(Perm) R32(Or3) R32(Max3) R32(MaxU32) R32(Bitop3) R32(LshlOr) R32(Ffbh) R32(SadU16) R32(SadU16S)
     R64(AddF64) R64(MulF64) R64(FmaF64) R64(CmpF64) R64(Mad64) R64(Lshl64) R64(LshlAdd64) R64(MaxF64)
     {   // the real clock, and the lone wave's issue cost in real shader cycles
         unsigned long long *d, h[512];

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpokerl_hip.so")
 HEADERS = [os.path.join(CSRC, "pk_device.hpp"), os.path.join(CSRC, "pk_table_kernels.hpp"), os.path.join(CSRC, "pk_util_kernels.hpp"), os.path.join(CSRC, "pk_snapshot.hpp"), os.path.join(CSRC, "pk_equity.hpp"),
-           os.path.join(CSRC, "pk_equity_sampled.hpp"), os.path.join(CSRC, "pk_equity_range.hpp"), os.path.join(CSRC, "pk_equity_rvr.hpp"),
+           os.path.join(CSRC, "pk_equity_common.hpp"), os.path.join(CSRC, "pk_equity_sampled.hpp"), os.path.join(CSRC, "pk_equity_range.hpp"), os.path.join(CSRC, "pk_equity_rvr.hpp"),
            os.path.join(CSRC, "pk_equity_hist.hpp"), os.path.join(CSRC, "pk_equity_ranged.hpp"), os.path.join(CSRC, "pk_equity_ev.hpp"), os.path.join(CSRC, "pk_hist_cluster.hpp"),
            os.path.join(os.path.dirname(HERE), "include", "pokerl_hip.h")]
 # -ffp-contract=off: numpy never fuses multiply-add, so neither may we (bit-exact f64 money).

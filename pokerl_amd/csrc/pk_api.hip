@@ -507,7 +507,7 @@ static int check_device(const char *call, int device, int limit = INT_MAX) {
 #define ON_DEVICE_INDEX(call, device, limit)                                     \
     if (int rc_ = check_device(call, device, limit)) return rc_;                 \
     DeviceGuard guard_(device);                                                  \
-    if (!guard_.ok) return g_fail(PK_E_HIP, call ": hipSetDevice failed")
+    if (!guard_.ok) return g_fail(PK_E_HIP, (std::string(call) + ": hipSetDevice failed").c_str())
 
 // The argument block of the PokerGameEnv.step kernels (pk_table_kernels.hpp EnvKernArgs): common fields; callers set the rest.
 static EnvKernArgs env_args(const pk_handle *h, const int32_t *actions_d, int seat0_policy, uint64_t seatpol, int auto_reset,
@@ -1811,16 +1811,9 @@ int pk_eval7_prefix(int device, int a, int b, int fast, uint32_t *out, size_t *c
     return PK_OK;
 }
 
-// ---- showdown equity (pokerl_hip.h "Showdown equity"; kernels: pk_equity.hip)
-static bool eq_bad_seats(int n) { return n < PK_MIN_PLAYERS || n > PK_MAX_PLAYERS; }
-static const size_t EQ_MAX_SPOTS = (size_t)1 << 31;
-// The device counts a call's tasks in 32 bits: a call whose worst case (every spot pre-flop) does not fit is refused, not wrapped.
-static bool eq_too_many_tasks(size_t m, int pool_max) { return eq_task_cap(m, eq_lpt(m), pool_max) > EQ_TASKS_MAX; }
-#define EQ_TASKS_MSG ": too many spots for one call (the worst-case task count must fit 32 bits: split the batch)"
-
-// Work space of the device form, which runs asynchronously on the CALLER's stream: one grow-only hipMalloc'ed buffer per (device, stream),
-// reused by the next call on that stream -- stream order makes that safe -- and at most EQ_WS_STREAMS of them per device (the least
-// recently used one is freed for a new stream; hipFree waits for the device, so work still queued on it is not cut short).  NOT the
+// ---- the equity family's work space of the device forms, which run asynchronously on the CALLER's stream: one grow-only hipMalloc'ed buffer
+// per (device, stream), reused by the next call on that stream -- stream order makes that safe -- and at most EQ_WS_STREAMS of them per device
+// (the least recently used one is freed for a new stream; hipFree waits for the device, so work still queued on it is not cut short).  NOT the
 // stream-ordered allocator: with hipMallocAsync / hipFreeAsync every call that followed a synchronisation got a fresh mapping, and on
 // such a mapping the enumeration kernel found the task count still zero -- every third call of a 4 096-spot loop returned all-zero
 // counts (measured, ROCm 7.2).
@@ -1850,109 +1843,197 @@ static void *eq_stream_ws(int device, hipStream_t st, size_t bytes) {   // the d
     return hit->buf.reserve(bytes, with_headroom(bytes, 4), st, true);   // (too small: the calls queued on it so far finish before it goes)
 }
 
-// The argument checks the two explicit forms share (made before the device is looked at)
-#define EQ_CHECK_SPOTS(call, num_players, m, inputs)                                                                                                             \
-    if (eq_bad_seats(num_players) || (m) >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, call ": num_players outside 2 .. 16, or m >= 2^31");                   \
-    if ((m) && !(inputs)) return g_fail(PK_E_INVALID_ARG, call ": NULL input buffer");                                                                           \
-    if (eq_too_many_tasks(m, 50)) return g_fail(PK_E_INVALID_ARG, call EQ_TASKS_MSG)
+// ---- showdown equity (pokerl_hip.h "Showdown equity"; kernels: pk_equity.hip) and, after it, the rest of the equity family.  Every family
+// comes in the same four forms, and each form is written ONCE here: an entry point checks its arguments, names its
+// staging pieces and its work-space size, and hands a lambda that queues its kernels to the form's skeleton.
+extern "C++" {   // (templates)
+static int eq_fail(int code, const char *call, const char *what, hipError_t e = hipSuccess) { return g_fail(code, (std::string(call) + what).c_str(), e); }
 
-int pk_equity_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
-                const uint16_t *live_d, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *boards_d, uint8_t *status_d, void *stream) {
-    EQ_CHECK_SPOTS("pk_equity_d", num_players, m, holes_d && board_d && nboard_d && live_d);
-    ON_DEVICE_INDEX("pk_equity_d", device, PK_MAX_DEVICES);   // (the evaluator table is kept per device index below PK_MAX_DEVICES)
+// The device form: asynchronous on the CALLER's stream, every array in device memory; the work space is that stream's (above).
+// launch(st, tab, work) queues the kernels; tab is NULL for a family that does not evaluate hands (need_table false).
+template <typename F>
+static int eq_call_d(const char *call, int device, void *stream, size_t m, bool need_table, size_t work_bytes, F launch) {
+    ON_DEVICE_INDEX(call, device, PK_MAX_DEVICES);   // (the evaluator table is kept per device index below PK_MAX_DEVICES)
     if (m == 0) return PK_OK;
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t *tab = eval7_table(device, st);   // (a first call builds the table on the CALLER's stream)
-    if (!tab) return g_fail(PK_E_OOM, "pk_equity_d: out of device memory (evaluator table)");
-    const int lpt = eq_lpt(m);
-    void *ws = eq_stream_ws(device, st, eq_layout(num_players, m, lpt, 50, nullptr, nullptr));
-    if (!ws) return g_fail(PK_E_OOM, "pk_equity_d: out of device memory (work space)");
-    EqWork w;
-    eq_layout(num_players, m, lpt, 50, (char *)ws, &w);
-    const EqSpots spots{holes_d, board_d, nboard_d, live_d};
-    const hipError_t e = eq_launch(st, tab, &spots, nullptr, num_players, m, EqOut{win_d, tie_d, share_d, boards_d, status_d}, w, lpt);
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_d: launch failed", e);
+    const uint32_t *tab = need_table ? eval7_table(device, st) : nullptr;   // (a first call builds the table on the CALLER's stream)
+    if (need_table && !tab) return eq_fail(PK_E_OOM, call, ": out of device memory (evaluator table)");
+    char *work = (char *)eq_stream_ws(device, st, work_bytes);
+    if (!work) return eq_fail(PK_E_OOM, call, ": out of device memory (work space)");
+    const hipError_t e = launch(st, tab, work);
+    if (e != hipSuccess) return eq_fail(PK_E_HIP, call, ": launch failed", e);
     return PK_OK;
 }
 
-int pk_equity(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
-              uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards, uint8_t *status) {
-    EQ_CHECK_SPOTS("pk_equity", num_players, m, holes && board && nboard && live);
-    ON_DEVICE_INDEX("pk_equity", device, PK_MAX_DEVICES);
+// The host form: the caller's host arrays, staged in ONE buffer (g's pieces: inputs, outputs, then the work space) of the judger arena on a
+// pooled stream; returns when the outputs are in the caller's arrays.  launch(st, tab, work) as above, on g.at<T>(piece).
+template <typename F>
+static int eq_call_host(const char *call, int device, size_t m, bool need_table, Stage &g, size_t work_bytes, F launch) {
+    ON_DEVICE_INDEX(call, device, PK_MAX_DEVICES);
     if (m == 0) return PK_OK;
-    const int N = num_players, lpt = eq_lpt(m);
     hipStream_t st = nullptr;
-    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity: no stream"); }
-    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
+    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return eq_fail(PK_E_HIP, call, ": no stream"); }
+    const uint32_t *tab = need_table ? eval7_table(device, st) : nullptr;   // (takes g_scratch_mu itself)
     int rc = PK_OK;
-    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity: out of device memory (evaluator table)");
+    if (need_table && !tab) rc = eq_fail(PK_E_OOM, call, ": out of device memory (evaluator table)");
     else {
         std::lock_guard<std::mutex> lock(g_scratch_mu);
-        Stage g;
-        const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2);
-        const EqStagedOut out(g, N, m, win, tie, share, boards, status);
-        const int work = g.add(eq_layout(N, m, lpt, 50, nullptr, nullptr));
-        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity: out of device memory");
+        const int work = g.add(work_bytes);
+        if (!(g.base = scratch(device, g.total, st))) rc = eq_fail(PK_E_OOM, call, ": out of device memory");
         else {
-            const hipError_t e = g.run(st, [&] {
-                EqWork w;
-                eq_layout(N, m, lpt, 50, g.at<char>(work), &w);
-                const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
-                return eq_launch(st, tab, &spots, nullptr, N, m, out.at(g), w, lpt);
-            });
-            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity", e); }   // (the lock is held until what was queued is done)
+            const hipError_t e = g.run(st, [&] { return launch(st, tab, g.at<char>(work)); });
+            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, call, e); }   // (the lock is held until what was queued is done)
         }
     }
     stream_release(device, st);
     return rc;
 }
 
-// The table form reads the handle's own state on the handle's stream; its work space is the handle's grow-only staging buffer.
-static int table_equity(pk_handle *h, const int32_t *tables_d, size_t m, const EqOut &out, char *work) {
+// The two table forms read the handle's own state on the handle's stream; their work space is the handle's grow-only staging buffer.  What
+// they share once that is there: the evaluator table, the handle's state as EqTables, launch(tab, tables, work).
+template <typename F>
+static int eq_table_launch(pk_handle *h, const char *call, const int32_t *tables_d, char *work, F launch) {
     const uint32_t *tab = eval7_table(h->device, h->stream);
-    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity: out of device memory (evaluator table)");
-    const int lpt = eq_lpt(m);
-    EqWork w;
-    eq_layout(h->N, m, lpt, 52 - 2 * h->N, work, &w);
+    if (!tab) {
+        std::string family(call);                    // (this text has always named the family, without the device form's _d)
+        if (family.size() > 2 && family.compare(family.size() - 2, 2, "_d") == 0) family.resize(family.size() - 2);
+        return h->fail(PK_E_OOM, (family + ": out of device memory (evaluator table)").c_str());
+    }
     const EqTables t{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T};
-    HIPCHK(h, eq_launch(h->stream, tab, nullptr, &t, h->N, m, out, w, lpt));
+    const hipError_t e = launch(tab, t, work);
+    if (e != hipSuccess) return h->fail(PK_E_HIP, (std::string(call) + ": launch failed").c_str(), e);
     return PK_OK;
 }
-// The opening of the two table forms (m == 0: nothing to do, once the handle has been flushed)
-#define EQ_TABLE_ENTER(h, m, call)                                                                             \
-    if (!(h)) return PK_E_INVALID_ARG;                                                                         \
-    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                           \
-    if (eq_too_many_tasks(m, 52 - 2 * (h)->N)) return (h)->fail(PK_E_INVALID_ARG, call EQ_TASKS_MSG);          \
-    ON_DEVICE(h);                                                                                              \
-    FLUSH_READER(h);                                                                                           \
-    if ((m) == 0) return PK_OK
+// The device form: tables_d and the outputs in device memory, asynchronous on the handle's stream (m == 0: nothing to do, once the handle has
+// been flushed)
+template <typename F>
+static int eq_table_call_d(pk_handle *h, const char *call, const int32_t *tables_d, size_t m, size_t work_bytes, F launch) {
+    ON_DEVICE(h);
+    FLUSH_READER(h);
+    if (m == 0) return PK_OK;
+    char *work = nullptr;
+    if (int rc = snap_staging(h, work_bytes, &work)) return rc;
+    return eq_table_launch(h, call, tables_d, work, launch);
+}
+// The host form: g's pieces (inputs, outputs), then the table indices and the work space, staged as the host form above stages them
+template <typename F>
+static int eq_table_call(pk_handle *h, const char *call, const int32_t *tables, size_t m, Stage &g, size_t work_bytes, F launch) {
+    ON_DEVICE(h);
+    FLUSH_READER(h);
+    if (m == 0) return PK_OK;
+    const int idx = g.in(tables, m * 4), work = g.add(work_bytes);
+    if (int rc = snap_staging(h, g.total, &g.base)) return rc;
+    HIPCHK(h, g.upload(h->stream));
+    if (int rc = eq_table_launch(h, call, g.at<int32_t>(idx), g.at<char>(work), launch)) return rc;
+    HIPCHK(h, g.download(h->stream));
+    return PK_OK;
+}
+}  // extern "C++"
+
+// The argument checks, made before the device is looked at.  Each gives the text its refusal ends in, or NULL; a family's check asks them in
+// the order its entry points always have.  EQ_REFUSE returns PK_E_INVALID_ARG with "<call><text>" (fail: g_fail, or the handle's).
+#define EQ_REFUSE(fail, call, check) \
+    if (const char *why_ = (check)) return fail(PK_E_INVALID_ARG, (std::string(call) + why_).c_str())
+static const size_t EQ_MAX_SPOTS = (size_t)1 << 31;
+static const char *eq_bad_m(size_t m) { return m >= EQ_MAX_SPOTS ? ": m >= 2^31" : nullptr; }
+static const char *eq_bad_spots(int num_players, size_t m) {
+    return num_players < PK_MIN_PLAYERS || num_players > PK_MAX_PLAYERS || m >= EQ_MAX_SPOTS ? ": num_players outside 2 .. 16, or m >= 2^31" : nullptr;
+}
+static const char *eq_null(size_t m, bool given, const char *text = ": NULL input buffer") { return m && !given ? text : nullptr; }
+// The device counts a call's tasks in 32 bits: a call whose worst case (every spot pre-flop) does not fit is refused, not wrapped.
+static const char *eq_bad_tasks(size_t worst_case) {
+    return worst_case > EQ_TASKS_MAX ? ": too many spots for one call (the worst-case task count must fit 32 bits: split the batch)" : nullptr;
+}
+static const char *eqs_bad_samples(uint32_t samples) { return samples == 0 || samples > EQS_SAMPLES_MAX ? ": samples outside 1 .. 2^24" : nullptr; }
+static const char *eqs_bad_tasks(size_t m, uint32_t samples) {
+    return eqs_task_bound(m, samples) > EQ_TASKS_MAX ? ": m * ceil(samples / 64) must fit 32 bits: split the batch" : nullptr;
+}
+static const char *eqw_bad_ranges(const uint16_t *weights, uint32_t num_ranges) {
+    if (num_ranges > (uint32_t)EQW_MAX_RANGES) return ": num_ranges above PK_EQW_MAX_RANGES (16)";
+    return num_ranges && !weights ? ": NULL weights with num_ranges > 0" : nullptr;
+}
+static const char *hist_bad_bins(int nbins) { return nbins < 1 || nbins > PK_EQ_HIST_MAX_BINS ? ": nbins must be 1 .. PK_EQ_HIST_MAX_BINS (32)" : nullptr; }
+// whose eyes a table form looks through: a seat, the active player, or -- for sampled equity alone -- nobody's
+static bool eq_observes(int observer, int N) { return observer == PK_OBSERVER_ACTIVE || (observer >= 0 && observer < N); }
+static const char *eqs_bad_observer(int observer, int N) {
+    return observer != PK_OBSERVER_NONE && !eq_observes(observer, N) ? ": observer outside {-2, -1, 0 .. N-1}" : nullptr;
+}
+static const char *eqw_bad_observer(int observer, int N) {
+    return !eq_observes(observer, N) ? ": observer outside {-2, 0 .. N-1} (PK_OBSERVER_NONE: nothing would be hidden)" : nullptr;
+}
+static const char *eqr_bad_observer(int observer, int N) {
+    return !eq_observes(observer, N) ? ": observer outside {-2, 0 .. N-1} (a hidden hand needs somebody to be hidden from)" : nullptr;
+}
+
+static const char *eq_check(int num_players, size_t m, bool inputs) {
+    if (const char *why = eq_bad_spots(num_players, m)) return why;
+    if (const char *why = eq_null(m, inputs)) return why;
+    return eq_bad_tasks(eq_task_cap(m, eq_lpt(m), 50));
+}
+static const char *eq_table_check(const pk_handle *h, size_t m) {
+    if (const char *why = eq_bad_m(m)) return why;
+    return eq_bad_tasks(eq_task_cap(m, eq_lpt(m), 52 - 2 * h->N));
+}
+
+int pk_equity_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
+                const uint16_t *live_d, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *boards_d, uint8_t *status_d, void *stream) {
+    const char *call = "pk_equity_d";
+    EQ_REFUSE(g_fail, call, eq_check(num_players, m, holes_d && board_d && nboard_d && live_d));
+    const int N = num_players, lpt = eq_lpt(m);
+    return eq_call_d(call, device, stream, m, true, eq_layout(N, m, lpt, 50, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        EqWork w;
+        eq_layout(N, m, lpt, 50, work, &w);
+        const EqSpots spots{holes_d, board_d, nboard_d, live_d};
+        return eq_launch(st, tab, &spots, nullptr, N, m, EqOut{win_d, tie_d, share_d, boards_d, status_d}, w, lpt);
+    });
+}
+
+int pk_equity(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
+              uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards, uint8_t *status) {
+    const char *call = "pk_equity";
+    EQ_REFUSE(g_fail, call, eq_check(num_players, m, holes && board && nboard && live));
+    const int N = num_players, lpt = eq_lpt(m);
+    Stage g;
+    const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2);
+    const EqStagedOut out(g, N, m, win, tie, share, boards, status);
+    return eq_call_host(call, device, m, true, g, eq_layout(N, m, lpt, 50, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        EqWork w;
+        eq_layout(N, m, lpt, 50, work, &w);
+        const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
+        return eq_launch(st, tab, &spots, nullptr, N, m, out.at(g), w, lpt);
+    });
+}
 
 int pk_table_equity_d(pk_handle *h, const int32_t *tables_d, size_t m, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *boards_d,
                       uint8_t *status_d) {
-    EQ_TABLE_ENTER(h, m, "pk_table_equity_d");
-    char *work = nullptr;
-    if (int rc = snap_staging(h, eq_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, nullptr, nullptr), &work)) return rc;
-    return table_equity(h, tables_d, m, EqOut{win_d, tie_d, share_d, boards_d, status_d}, work);
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_d";
+    EQ_REFUSE(h->fail, call, eq_table_check(h, m));
+    const int N = h->N, lpt = eq_lpt(m), pool = 52 - 2 * N;
+    return eq_table_call_d(h, call, tables_d, m, eq_layout(N, m, lpt, pool, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        EqWork w;
+        eq_layout(N, m, lpt, pool, work, &w);
+        return eq_launch(h->stream, tab, nullptr, &t, N, m, EqOut{win_d, tie_d, share_d, boards_d, status_d}, w, lpt);
+    });
 }
 
 int pk_table_equity(pk_handle *h, const int32_t *tables, size_t m, uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *boards,
                     uint8_t *status) {
-    EQ_TABLE_ENTER(h, m, "pk_table_equity");
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity";
+    EQ_REFUSE(h->fail, call, eq_table_check(h, m));
+    const int N = h->N, lpt = eq_lpt(m), pool = 52 - 2 * N;
     Stage g;
-    const int idx = g.in(tables, m * 4);
-    const EqStagedOut out(g, h->N, m, win, tie, share, boards, status);
-    const int work = g.add(eq_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, nullptr, nullptr));
-    int rc = snap_staging(h, g.total, &g.base);
-    if (rc) return rc;
-    HIPCHK(h, g.upload(h->stream));
-    if ((rc = table_equity(h, g.at<int32_t>(idx), m, out.at(g), g.at<char>(work)))) return rc;
-    HIPCHK(h, g.download(h->stream));
-    return PK_OK;
+    const EqStagedOut out(g, N, m, win, tie, share, boards, status);
+    return eq_table_call(h, call, tables, m, g, eq_layout(N, m, lpt, pool, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        EqWork w;
+        eq_layout(N, m, lpt, pool, work, &w);
+        return eq_launch(h->stream, tab, nullptr, &t, N, m, out.at(g), w, lpt);
+    });
 }
 
-// ---- showdown EV in chips (pokerl_hip.h "Showdown EV"; kernels: pk_equity_ev.hip).  Streams and work space as showdown equity; the work space
-// also holds the level table, the bets, the amounts and -- when the caller does not ask for `share` -- the share counters.
-static bool ev_too_many_tasks(int N, size_t m, int pool_max) { return ev_task_cap(N, m, eq_lpt(m), pool_max) > EQ_TASKS_MAX; }
+// ---- showdown EV in chips (pokerl_hip.h "Showdown EV"; kernels: pk_equity_ev.hip).  The work space also holds the level table, the bets, the
+// amounts and -- when the caller does not ask for `share` -- the share counters.
 struct EvStagedOut {
     int share, level_seat, amount, ev, boards, status;
     EvStagedOut(Stage &g, int N, size_t m, uint64_t *share, uint8_t *level_seat, double *amount, double *ev, uint32_t *boards, uint8_t *status)
@@ -1962,719 +2043,487 @@ struct EvStagedOut {
         return EvOut{g.at<uint64_t>(share), g.at<uint8_t>(level_seat), g.at<double>(amount), g.at<double>(ev), g.at<uint32_t>(boards), g.at<uint8_t>(status)};
     }
 };
-#define EV_CHECK_SPOTS(call, num_players, m, inputs, status)                                                                                                     \
-    if (eq_bad_seats(num_players) || (m) >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, call ": num_players outside 2 .. 16, or m >= 2^31");                   \
-    if ((m) && !((inputs) && (status))) return g_fail(PK_E_INVALID_ARG, call ": NULL input buffer or NULL status");                                              \
-    if (ev_too_many_tasks(num_players, m, 50)) return g_fail(PK_E_INVALID_ARG, call EQ_TASKS_MSG)
+static const char *ev_check(int num_players, size_t m, bool inputs_and_status) {
+    if (const char *why = eq_bad_spots(num_players, m)) return why;
+    if (const char *why = eq_null(m, inputs_and_status, ": NULL input buffer or NULL status")) return why;
+    return eq_bad_tasks(ev_task_cap(num_players, m, eq_lpt(m), 50));
+}
+static const char *ev_table_check(const pk_handle *h, size_t m, const uint8_t *status) {
+    if (const char *why = eq_bad_m(m)) return why;
+    if (const char *why = eq_null(m, status, ": NULL status")) return why;
+    return eq_bad_tasks(ev_task_cap(h->N, m, eq_lpt(m), 52 - 2 * h->N));
+}
 
 int pk_equity_ev_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
                    const uint16_t *live_d, const double *bets_d, uint64_t *share_d, uint8_t *level_seat_d, double *amount_d, double *ev_d,
                    uint32_t *boards_d, uint8_t *status_d, void *stream) {
-    EV_CHECK_SPOTS("pk_equity_ev_d", num_players, m, holes_d && board_d && nboard_d && live_d && bets_d, status_d);
-    ON_DEVICE_INDEX("pk_equity_ev_d", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t *tab = eval7_table(device, st);   // (a first call builds the table on the CALLER's stream)
-    if (!tab) return g_fail(PK_E_OOM, "pk_equity_ev_d: out of device memory (evaluator table)");
-    const int lpt = eq_lpt(m);
-    void *ws = eq_stream_ws(device, st, ev_layout(num_players, m, lpt, 50, !share_d, nullptr, nullptr));
-    if (!ws) return g_fail(PK_E_OOM, "pk_equity_ev_d: out of device memory (work space)");
-    EvWork w;
-    ev_layout(num_players, m, lpt, 50, !share_d, (char *)ws, &w);
-    const EqSpots spots{holes_d, board_d, nboard_d, live_d};
-    const hipError_t e = ev_launch(st, tab, &spots, bets_d, nullptr, num_players, m, EvOut{share_d, level_seat_d, amount_d, ev_d, boards_d, status_d}, w, lpt);
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_ev_d: launch failed", e);
-    return PK_OK;
+    const char *call = "pk_equity_ev_d";
+    EQ_REFUSE(g_fail, call, ev_check(num_players, m, holes_d && board_d && nboard_d && live_d && bets_d && status_d));
+    const int N = num_players, lpt = eq_lpt(m);
+    return eq_call_d(call, device, stream, m, true, ev_layout(N, m, lpt, 50, !share_d, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        EvWork w;
+        ev_layout(N, m, lpt, 50, !share_d, work, &w);
+        const EqSpots spots{holes_d, board_d, nboard_d, live_d};
+        return ev_launch(st, tab, &spots, bets_d, nullptr, N, m, EvOut{share_d, level_seat_d, amount_d, ev_d, boards_d, status_d}, w, lpt);
+    });
 }
 
 int pk_equity_ev(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
                  const double *bets, uint64_t *share, uint8_t *level_seat, double *amount, double *ev, uint32_t *boards, uint8_t *status) {
-    EV_CHECK_SPOTS("pk_equity_ev", num_players, m, holes && board && nboard && live && bets, status);
-    ON_DEVICE_INDEX("pk_equity_ev", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
+    const char *call = "pk_equity_ev";
+    EQ_REFUSE(g_fail, call, ev_check(num_players, m, holes && board && nboard && live && bets && status));
     const int N = num_players, lpt = eq_lpt(m);
-    hipStream_t st = nullptr;
-    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity_ev: no stream"); }
-    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
-    int rc = PK_OK;
-    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity_ev: out of device memory (evaluator table)");
-    else {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        Stage g;
-        const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), be = g.in(bets, m * N * 8);
-        const EvStagedOut out(g, N, m, share, level_seat, amount, ev, boards, status);
-        const int work = g.add(ev_layout(N, m, lpt, 50, !share, nullptr, nullptr));
-        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity_ev: out of device memory");
-        else {
-            const hipError_t e = g.run(st, [&] {
-                EvWork w;
-                ev_layout(N, m, lpt, 50, !share, g.at<char>(work), &w);
-                const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
-                return ev_launch(st, tab, &spots, g.at<double>(be), nullptr, N, m, out.at(g), w, lpt);
-            });
-            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity_ev", e); }   // (the lock is held until what was queued is done)
-        }
-    }
-    stream_release(device, st);
-    return rc;
+    Stage g;
+    const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), be = g.in(bets, m * N * 8);
+    const EvStagedOut out(g, N, m, share, level_seat, amount, ev, boards, status);
+    return eq_call_host(call, device, m, true, g, ev_layout(N, m, lpt, 50, !share, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        EvWork w;
+        ev_layout(N, m, lpt, 50, !share, work, &w);
+        const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
+        return ev_launch(st, tab, &spots, g.at<double>(be), nullptr, N, m, out.at(g), w, lpt);
+    });
 }
-
-static int table_equity_ev(pk_handle *h, const int32_t *tables_d, size_t m, const EvOut &out, char *work) {
-    const uint32_t *tab = eval7_table(h->device, h->stream);
-    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity_ev: out of device memory (evaluator table)");
-    const int lpt = eq_lpt(m);
-    EvWork w;
-    ev_layout(h->N, m, lpt, 52 - 2 * h->N, !out.share, work, &w);
-    const EvTables t{EqTables{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T}, h->S.bets, h->S.pending};
-    HIPCHK(h, ev_launch(h->stream, tab, nullptr, nullptr, &t, h->N, m, out, w, lpt));
-    return PK_OK;
-}
-#define EV_TABLE_ENTER(h, m, status, call)                                                                     \
-    if (!(h)) return PK_E_INVALID_ARG;                                                                         \
-    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                           \
-    if ((m) && !(status)) return (h)->fail(PK_E_INVALID_ARG, call ": NULL status");                            \
-    if (ev_too_many_tasks((h)->N, m, 52 - 2 * (h)->N)) return (h)->fail(PK_E_INVALID_ARG, call EQ_TASKS_MSG);  \
-    ON_DEVICE(h);                                                                                              \
-    FLUSH_READER(h);                                                                                           \
-    if ((m) == 0) return PK_OK
 
 int pk_table_equity_ev_d(pk_handle *h, const int32_t *tables_d, size_t m, uint64_t *share_d, uint8_t *level_seat_d, double *amount_d, double *ev_d,
                          uint32_t *boards_d, uint8_t *status_d) {
-    EV_TABLE_ENTER(h, m, status_d, "pk_table_equity_ev_d");
-    char *work = nullptr;
-    if (int rc = snap_staging(h, ev_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, !share_d, nullptr, nullptr), &work)) return rc;
-    return table_equity_ev(h, tables_d, m, EvOut{share_d, level_seat_d, amount_d, ev_d, boards_d, status_d}, work);
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_ev_d";
+    EQ_REFUSE(h->fail, call, ev_table_check(h, m, status_d));
+    const int N = h->N, lpt = eq_lpt(m), pool = 52 - 2 * N;
+    return eq_table_call_d(h, call, tables_d, m, ev_layout(N, m, lpt, pool, !share_d, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        EvWork w;
+        ev_layout(N, m, lpt, pool, !share_d, work, &w);
+        const EvTables et{t, h->S.bets, h->S.pending};     // (the handle's bets and pending chips beside the tables)
+        return ev_launch(h->stream, tab, nullptr, nullptr, &et, N, m, EvOut{share_d, level_seat_d, amount_d, ev_d, boards_d, status_d}, w, lpt);
+    });
 }
 
 int pk_table_equity_ev(pk_handle *h, const int32_t *tables, size_t m, uint64_t *share, uint8_t *level_seat, double *amount, double *ev,
                        uint32_t *boards, uint8_t *status) {
-    EV_TABLE_ENTER(h, m, status, "pk_table_equity_ev");
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_ev";
+    EQ_REFUSE(h->fail, call, ev_table_check(h, m, status));
+    const int N = h->N, lpt = eq_lpt(m), pool = 52 - 2 * N;
     Stage g;
-    const int idx = g.in(tables, m * 4);
-    const EvStagedOut out(g, h->N, m, share, level_seat, amount, ev, boards, status);
-    const int work = g.add(ev_layout(h->N, m, eq_lpt(m), 52 - 2 * h->N, !share, nullptr, nullptr));
-    int rc = snap_staging(h, g.total, &g.base);
-    if (rc) return rc;
-    HIPCHK(h, g.upload(h->stream));
-    if ((rc = table_equity_ev(h, g.at<int32_t>(idx), m, out.at(g), g.at<char>(work)))) return rc;
-    HIPCHK(h, g.download(h->stream));
-    return PK_OK;
+    const EvStagedOut out(g, N, m, share, level_seat, amount, ev, boards, status);
+    return eq_table_call(h, call, tables, m, g, ev_layout(N, m, lpt, pool, !share, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        EvWork w;
+        ev_layout(N, m, lpt, pool, !share, work, &w);
+        const EvTables et{t, h->S.bets, h->S.pending};
+        return ev_launch(h->stream, tab, nullptr, nullptr, &et, N, m, out.at(g), w, lpt);
+    });
 }
 
-// ---- sampled showdown equity (pokerl_hip.h "Sampled showdown equity"; kernels: pk_equity_sampled.hip).  Work space (the descriptors) as above.
-static bool eqs_bad_samples(uint32_t samples) { return samples == 0 || samples > EQS_SAMPLES_MAX; }
+// ---- sampled showdown equity (pokerl_hip.h "Sampled showdown equity"; kernels: pk_equity_sampled.hip).  Work space: the descriptors.
 static EqsOut eqs_out(const EqOut &o) { return EqsOut{o.win, o.tie, o.share, o.boards, o.status}; }
 static EqsStream eqs_seed_stream(uint64_t seed, uint32_t nonce, uint32_t samples, const uint32_t *ids) {
     return EqsStream{(uint32_t)seed, (uint32_t)(seed >> 32), nonce, samples, 0u, ids};
 }
-#define EQS_CHECK_SPOTS(call, num_players, m, samples, inputs)                                                                                    \
-    if (eq_bad_seats(num_players) || (m) >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, call ": num_players outside 2 .. 16, or m >= 2^31");    \
-    if (eqs_bad_samples(samples)) return g_fail(PK_E_INVALID_ARG, call ": samples outside 1 .. 2^24");                                            \
-    if ((m) && !(inputs)) return g_fail(PK_E_INVALID_ARG, call ": NULL input buffer");                                                            \
-    if (eqs_task_bound(m, samples) > EQ_TASKS_MAX) return g_fail(PK_E_INVALID_ARG, call ": m * ceil(samples / 64) must fit 32 bits: split the batch")
+// The table forms draw with the handle's key, stream id = table_id_base + table
+static EqsStream eqs_table_stream(const pk_handle *h, uint32_t nonce, uint32_t samples) {
+    return EqsStream{h->S.key0, h->S.key1, nonce, samples, h->S.table_id_base, nullptr};
+}
+static const char *eqs_check(int num_players, size_t m, uint32_t samples, bool inputs) {
+    if (const char *why = eq_bad_spots(num_players, m)) return why;
+    if (const char *why = eqs_bad_samples(samples)) return why;
+    if (const char *why = eq_null(m, inputs)) return why;
+    return eqs_bad_tasks(m, samples);
+}
+static const char *eqs_table_check(const pk_handle *h, size_t m, int observer, uint32_t samples) {
+    if (const char *why = eq_bad_m(m)) return why;
+    if (const char *why = eqs_bad_samples(samples)) return why;
+    if (const char *why = eqs_bad_observer(observer, h->N)) return why;
+    return eqs_bad_tasks(m, samples);
+}
 
 int pk_equity_sampled_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
                         const uint16_t *live_d, const uint32_t *ids_d, uint32_t samples, uint64_t seed, uint32_t nonce, uint32_t *win_d,
                         uint32_t *tie_d, uint64_t *share_d, uint32_t *samples_d, uint8_t *status_d, void *stream) {
-    EQS_CHECK_SPOTS("pk_equity_sampled_d", num_players, m, samples, holes_d && board_d && nboard_d && live_d);
-    ON_DEVICE_INDEX("pk_equity_sampled_d", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t *tab = eval7_table(device, st);
-    if (!tab) return g_fail(PK_E_OOM, "pk_equity_sampled_d: out of device memory (evaluator table)");
-    void *ws = eq_stream_ws(device, st, eqs_work_bytes(num_players, m));
-    if (!ws) return g_fail(PK_E_OOM, "pk_equity_sampled_d: out of device memory (work space)");
-    const EqSpots spots{holes_d, board_d, nboard_d, live_d};
-    const hipError_t e = eqs_launch(st, tab, &spots, nullptr, PK_OBSERVER_NONE, eqs_seed_stream(seed, nonce, samples, ids_d), num_players, m,
-                                    EqsOut{win_d, tie_d, share_d, samples_d, status_d}, (uint64_t *)ws);
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_sampled_d: launch failed", e);
-    return PK_OK;
+    const char *call = "pk_equity_sampled_d";
+    EQ_REFUSE(g_fail, call, eqs_check(num_players, m, samples, holes_d && board_d && nboard_d && live_d));
+    return eq_call_d(call, device, stream, m, true, eqs_work_bytes(num_players, m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const EqSpots spots{holes_d, board_d, nboard_d, live_d};
+        return eqs_launch(st, tab, &spots, nullptr, PK_OBSERVER_NONE, eqs_seed_stream(seed, nonce, samples, ids_d), num_players, m,
+                          EqsOut{win_d, tie_d, share_d, samples_d, status_d}, (uint64_t *)work);
+    });
 }
 
 int pk_equity_sampled(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard,
                       const uint16_t *live, const uint32_t *ids, uint32_t samples, uint64_t seed, uint32_t nonce, uint32_t *win, uint32_t *tie,
                       uint64_t *share, uint32_t *samples_out, uint8_t *status) {
-    EQS_CHECK_SPOTS("pk_equity_sampled", num_players, m, samples, holes && board && nboard && live);
-    ON_DEVICE_INDEX("pk_equity_sampled", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
+    const char *call = "pk_equity_sampled";
+    EQ_REFUSE(g_fail, call, eqs_check(num_players, m, samples, holes && board && nboard && live));
     const int N = num_players;
-    hipStream_t st = nullptr;
-    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity_sampled: no stream"); }
-    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
-    int rc = PK_OK;
-    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity_sampled: out of device memory (evaluator table)");
-    else {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        Stage g;
-        const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), id = g.in(ids, m * 4);
-        const EqStagedOut out(g, N, m, win, tie, share, samples_out, status);
-        const int work = g.add(eqs_work_bytes(N, m));
-        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity_sampled: out of device memory");
-        else {
-            const hipError_t e = g.run(st, [&] {
-                const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
-                return eqs_launch(st, tab, &spots, nullptr, PK_OBSERVER_NONE, eqs_seed_stream(seed, nonce, samples, g.at<uint32_t>(id)), N, m,
-                                  eqs_out(out.at(g)), g.at<uint64_t>(work));
-            });
-            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity_sampled", e); }   // (the lock is held until what was queued is done)
-        }
-    }
-    stream_release(device, st);
-    return rc;
+    Stage g;
+    const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), id = g.in(ids, m * 4);
+    const EqStagedOut out(g, N, m, win, tie, share, samples_out, status);
+    return eq_call_host(call, device, m, true, g, eqs_work_bytes(N, m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
+        return eqs_launch(st, tab, &spots, nullptr, PK_OBSERVER_NONE, eqs_seed_stream(seed, nonce, samples, g.at<uint32_t>(id)), N, m,
+                          eqs_out(out.at(g)), (uint64_t *)work);
+    });
 }
 
-// The table form: the handle's own state on the handle's stream, as `observer` sees it; the handle's key, stream id = table_id_base + table
-static int table_equity_sampled(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce, const EqsOut &out,
-                                char *work) {
-    const uint32_t *tab = eval7_table(h->device, h->stream);
-    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity_sampled: out of device memory (evaluator table)");
-    const EqTables t{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T};
-    const EqsStream rng{h->S.key0, h->S.key1, nonce, samples, h->S.table_id_base, nullptr};
-    HIPCHK(h, eqs_launch(h->stream, tab, nullptr, &t, observer, rng, h->N, m, out, (uint64_t *)work));
-    return PK_OK;
-}
-#define EQS_TABLE_ENTER(h, m, observer, samples, call)                                                                                       \
-    if (!(h)) return PK_E_INVALID_ARG;                                                                                                       \
-    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                                                         \
-    if (eqs_bad_samples(samples)) return (h)->fail(PK_E_INVALID_ARG, call ": samples outside 1 .. 2^24");                                    \
-    if ((observer) < PK_OBSERVER_ACTIVE || (observer) >= (h)->N) return (h)->fail(PK_E_INVALID_ARG, call ": observer outside {-2, -1, 0 .. N-1}"); \
-    if (eqs_task_bound(m, samples) > EQ_TASKS_MAX) return (h)->fail(PK_E_INVALID_ARG, call ": m * ceil(samples / 64) must fit 32 bits: split the batch"); \
-    ON_DEVICE(h);                                                                                                                            \
-    FLUSH_READER(h);                                                                                                                         \
-    if ((m) == 0) return PK_OK
-
+// The table forms: the handle's own state as `observer` sees it
 int pk_table_equity_sampled_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce, uint32_t *win_d,
                               uint32_t *tie_d, uint64_t *share_d, uint32_t *samples_d, uint8_t *status_d) {
-    EQS_TABLE_ENTER(h, m, observer, samples, "pk_table_equity_sampled_d");
-    char *work = nullptr;
-    if (int rc = snap_staging(h, eqs_work_bytes(h->N, m), &work)) return rc;
-    return table_equity_sampled(h, tables_d, m, observer, samples, nonce, EqsOut{win_d, tie_d, share_d, samples_d, status_d}, work);
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_sampled_d";
+    EQ_REFUSE(h->fail, call, eqs_table_check(h, m, observer, samples));
+    return eq_table_call_d(h, call, tables_d, m, eqs_work_bytes(h->N, m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return eqs_launch(h->stream, tab, nullptr, &t, observer, eqs_table_stream(h, nonce, samples), h->N, m,
+                          EqsOut{win_d, tie_d, share_d, samples_d, status_d}, (uint64_t *)work);
+    });
 }
 
 int pk_table_equity_sampled(pk_handle *h, const int32_t *tables, size_t m, int observer, uint32_t samples, uint32_t nonce, uint32_t *win,
                             uint32_t *tie, uint64_t *share, uint32_t *samples_out, uint8_t *status) {
-    EQS_TABLE_ENTER(h, m, observer, samples, "pk_table_equity_sampled");
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_sampled";
+    EQ_REFUSE(h->fail, call, eqs_table_check(h, m, observer, samples));
     Stage g;
-    const int idx = g.in(tables, m * 4);
     const EqStagedOut out(g, h->N, m, win, tie, share, samples_out, status);
-    const int work = g.add(eqs_work_bytes(h->N, m));
-    int rc = snap_staging(h, g.total, &g.base);
-    if (rc) return rc;
-    HIPCHK(h, g.upload(h->stream));
-    if ((rc = table_equity_sampled(h, g.at<int32_t>(idx), m, observer, samples, nonce, eqs_out(out.at(g)), g.at<char>(work)))) return rc;
-    HIPCHK(h, g.download(h->stream));
-    return PK_OK;
+    return eq_table_call(h, call, tables, m, g, eqs_work_bytes(h->N, m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return eqs_launch(h->stream, tab, nullptr, &t, observer, eqs_table_stream(h, nonce, samples), h->N, m, eqs_out(out.at(g)), (uint64_t *)work);
+    });
 }
 
 // ---- ranged sampled equity (pokerl_hip.h "Ranged sampled equity"; kernels: pk_equity_ranged.hip).  Work space: the cumulative sums of the
-// call's range rows, then the descriptors -- the per-(device, stream) buffer, the judger arena or the handle's staging buffer, as above.
+// call's range rows, then the descriptors.
 static EqwOut eqw_out(const EqOut &o) { return EqwOut{o.win, o.tie, o.share, o.boards, o.status}; }
-#define EQW_CHECK_RANGES(fail, call, weights, num_ranges)                                                                                          \
-    if ((num_ranges) > (uint32_t)EQW_MAX_RANGES) return fail(PK_E_INVALID_ARG, call ": num_ranges above PK_EQW_MAX_RANGES (16)");                  \
-    if ((num_ranges) && !(weights)) return fail(PK_E_INVALID_ARG, call ": NULL weights with num_ranges > 0")
+static const char *eqw_check(int num_players, size_t m, uint32_t samples, bool inputs, const uint16_t *weights, uint32_t num_ranges) {
+    if (const char *why = eqs_check(num_players, m, samples, inputs)) return why;
+    return eqw_bad_ranges(weights, num_ranges);
+}
+static const char *eqw_table_check(const pk_handle *h, size_t m, int observer, uint32_t samples, const uint16_t *weights, uint32_t num_ranges) {
+    if (const char *why = eq_bad_m(m)) return why;
+    if (const char *why = eqs_bad_samples(samples)) return why;
+    if (const char *why = eqw_bad_observer(observer, h->N)) return why;
+    if (const char *why = eqw_bad_ranges(weights, num_ranges)) return why;
+    return eqs_bad_tasks(m, samples);
+}
 
 int pk_equity_ranged_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
                        const uint16_t *live_d, const uint32_t *ids_d, uint32_t samples, uint64_t seed, uint32_t nonce, const uint16_t *weights_d,
                        uint32_t num_ranges, const uint16_t *range_of_d, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d, uint32_t *accepted_d,
                        uint8_t *status_d, void *stream) {
-    EQS_CHECK_SPOTS("pk_equity_ranged_d", num_players, m, samples, holes_d && board_d && nboard_d && live_d);
-    EQW_CHECK_RANGES(g_fail, "pk_equity_ranged_d", weights_d, num_ranges);
-    ON_DEVICE_INDEX("pk_equity_ranged_d", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t *tab = eval7_table(device, st);
-    if (!tab) return g_fail(PK_E_OOM, "pk_equity_ranged_d: out of device memory (evaluator table)");
-    void *ws = eq_stream_ws(device, st, eqw_work_bytes(num_players, m, num_ranges));
-    if (!ws) return g_fail(PK_E_OOM, "pk_equity_ranged_d: out of device memory (work space)");
-    const EqSpots spots{holes_d, board_d, nboard_d, live_d};
-    const hipError_t e = eqw_launch(st, tab, &spots, nullptr, PK_OBSERVER_ACTIVE, eqs_seed_stream(seed, nonce, samples, ids_d),
-                                    EqwRanges{weights_d, num_ranges, range_of_d, 1}, num_players, m,
-                                    EqwOut{win_d, tie_d, share_d, accepted_d, status_d}, (char *)ws);
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_ranged_d: launch failed", e);
-    return PK_OK;
+    const char *call = "pk_equity_ranged_d";
+    EQ_REFUSE(g_fail, call, eqw_check(num_players, m, samples, holes_d && board_d && nboard_d && live_d, weights_d, num_ranges));
+    return eq_call_d(call, device, stream, m, true, eqw_work_bytes(num_players, m, num_ranges), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const EqSpots spots{holes_d, board_d, nboard_d, live_d};
+        return eqw_launch(st, tab, &spots, nullptr, PK_OBSERVER_ACTIVE, eqs_seed_stream(seed, nonce, samples, ids_d),
+                          EqwRanges{weights_d, num_ranges, range_of_d, 1}, num_players, m, EqwOut{win_d, tie_d, share_d, accepted_d, status_d}, work);
+    });
 }
 
 int pk_equity_ranged(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
                      const uint32_t *ids, uint32_t samples, uint64_t seed, uint32_t nonce, const uint16_t *weights, uint32_t num_ranges,
                      const uint16_t *range_of, uint32_t *win, uint32_t *tie, uint64_t *share, uint32_t *accepted, uint8_t *status) {
-    EQS_CHECK_SPOTS("pk_equity_ranged", num_players, m, samples, holes && board && nboard && live);
-    EQW_CHECK_RANGES(g_fail, "pk_equity_ranged", weights, num_ranges);
-    ON_DEVICE_INDEX("pk_equity_ranged", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
+    const char *call = "pk_equity_ranged";
+    EQ_REFUSE(g_fail, call, eqw_check(num_players, m, samples, holes && board && nboard && live, weights, num_ranges));
     const int N = num_players;
-    hipStream_t st = nullptr;
-    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity_ranged: no stream"); }
-    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
-    int rc = PK_OK;
-    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity_ranged: out of device memory (evaluator table)");
-    else {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        Stage g;
-        const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), id = g.in(ids, m * 4);
-        const int wt = g.in(num_ranges ? weights : nullptr, (size_t)num_ranges * EQW_HOLDINGS * 2), ro = g.in(range_of, m * (size_t)N * 2);
-        const EqStagedOut out(g, N, m, win, tie, share, accepted, status);
-        const int work = g.add(eqw_work_bytes(N, m, num_ranges));
-        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity_ranged: out of device memory");
-        else {
-            const hipError_t e = g.run(st, [&] {
-                const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
-                return eqw_launch(st, tab, &spots, nullptr, PK_OBSERVER_ACTIVE, eqs_seed_stream(seed, nonce, samples, g.at<uint32_t>(id)),
-                                  EqwRanges{g.at<uint16_t>(wt), num_ranges, g.at<uint16_t>(ro), 1}, N, m, eqw_out(out.at(g)), g.at<char>(work));
-            });
-            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity_ranged", e); }   // (the lock is held until what was queued is done)
-        }
-    }
-    stream_release(device, st);
-    return rc;
+    Stage g;
+    const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), id = g.in(ids, m * 4);
+    const int wt = g.in(num_ranges ? weights : nullptr, (size_t)num_ranges * EQW_HOLDINGS * 2), ro = g.in(range_of, m * (size_t)N * 2);
+    const EqStagedOut out(g, N, m, win, tie, share, accepted, status);
+    return eq_call_host(call, device, m, true, g, eqw_work_bytes(N, m, num_ranges), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
+        return eqw_launch(st, tab, &spots, nullptr, PK_OBSERVER_ACTIVE, eqs_seed_stream(seed, nonce, samples, g.at<uint32_t>(id)),
+                          EqwRanges{g.at<uint16_t>(wt), num_ranges, g.at<uint16_t>(ro), 1}, N, m, eqw_out(out.at(g)), work);
+    });
 }
 
-// The table form: the handle's own state on the handle's stream, as `observer` sees it; the handle's key, stream id = table_id_base + table
-static int table_equity_ranged(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce, const EqwRanges &ranges,
-                               const EqwOut &out, char *work) {
-    const uint32_t *tab = eval7_table(h->device, h->stream);
-    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity_ranged: out of device memory (evaluator table)");
-    const EqTables t{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T};
-    const EqsStream rng{h->S.key0, h->S.key1, nonce, samples, h->S.table_id_base, nullptr};
-    HIPCHK(h, eqw_launch(h->stream, tab, nullptr, &t, observer, rng, ranges, h->N, m, out, work));
-    return PK_OK;
-}
-#define EQW_TABLE_ENTER(h, m, observer, samples, weights, num_ranges, call)                                                                  \
-    if (!(h)) return PK_E_INVALID_ARG;                                                                                                       \
-    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                                                         \
-    if (eqs_bad_samples(samples)) return (h)->fail(PK_E_INVALID_ARG, call ": samples outside 1 .. 2^24");                                    \
-    if ((observer) == PK_OBSERVER_NONE || (observer) < PK_OBSERVER_ACTIVE || (observer) >= (h)->N)                                           \
-        return (h)->fail(PK_E_INVALID_ARG, call ": observer outside {-2, 0 .. N-1} (PK_OBSERVER_NONE: nothing would be hidden)");            \
-    EQW_CHECK_RANGES((h)->fail, call, weights, num_ranges);                                                                                  \
-    if (eqs_task_bound(m, samples) > EQ_TASKS_MAX) return (h)->fail(PK_E_INVALID_ARG, call ": m * ceil(samples / 64) must fit 32 bits: split the batch"); \
-    ON_DEVICE(h);                                                                                                                            \
-    FLUSH_READER(h);                                                                                                                         \
-    if ((m) == 0) return PK_OK
-
+// The table forms: the handle's own state as `observer` sees it
 int pk_table_equity_ranged_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce, const uint16_t *weights_d,
                              uint32_t num_ranges, const uint16_t *range_of_d, int range_per_table, uint32_t *win_d, uint32_t *tie_d, uint64_t *share_d,
                              uint32_t *accepted_d, uint8_t *status_d) {
-    EQW_TABLE_ENTER(h, m, observer, samples, weights_d, num_ranges, "pk_table_equity_ranged_d");
-    char *work = nullptr;
-    if (int rc = snap_staging(h, eqw_work_bytes(h->N, m, num_ranges), &work)) return rc;
-    return table_equity_ranged(h, tables_d, m, observer, samples, nonce, EqwRanges{weights_d, num_ranges, range_of_d, range_per_table ? 1 : 0},
-                               EqwOut{win_d, tie_d, share_d, accepted_d, status_d}, work);
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_ranged_d";
+    EQ_REFUSE(h->fail, call, eqw_table_check(h, m, observer, samples, weights_d, num_ranges));
+    return eq_table_call_d(h, call, tables_d, m, eqw_work_bytes(h->N, m, num_ranges), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return eqw_launch(h->stream, tab, nullptr, &t, observer, eqs_table_stream(h, nonce, samples),
+                          EqwRanges{weights_d, num_ranges, range_of_d, range_per_table ? 1 : 0}, h->N, m,
+                          EqwOut{win_d, tie_d, share_d, accepted_d, status_d}, work);
+    });
 }
 
 int pk_table_equity_ranged(pk_handle *h, const int32_t *tables, size_t m, int observer, uint32_t samples, uint32_t nonce, const uint16_t *weights,
                            uint32_t num_ranges, const uint16_t *range_of, int range_per_table, uint32_t *win, uint32_t *tie, uint64_t *share,
                            uint32_t *accepted, uint8_t *status) {
-    EQW_TABLE_ENTER(h, m, observer, samples, weights, num_ranges, "pk_table_equity_ranged");
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_ranged";
+    EQ_REFUSE(h->fail, call, eqw_table_check(h, m, observer, samples, weights, num_ranges));
     Stage g;
-    const int idx = g.in(tables, m * 4);
     const int wt = g.in(num_ranges ? weights : nullptr, (size_t)num_ranges * EQW_HOLDINGS * 2);
     const int ro = g.in(range_of, (range_per_table ? m : (size_t)1) * (size_t)h->N * 2);
     const EqStagedOut out(g, h->N, m, win, tie, share, accepted, status);
-    const int work = g.add(eqw_work_bytes(h->N, m, num_ranges));
-    int rc = snap_staging(h, g.total, &g.base);
-    if (rc) return rc;
-    HIPCHK(h, g.upload(h->stream));
-    if ((rc = table_equity_ranged(h, g.at<int32_t>(idx), m, observer, samples, nonce,
-                                  EqwRanges{g.at<uint16_t>(wt), num_ranges, g.at<uint16_t>(ro), range_per_table ? 1 : 0}, eqw_out(out.at(g)), g.at<char>(work))))
-        return rc;
-    HIPCHK(h, g.download(h->stream));
-    return PK_OK;
+    return eq_table_call(h, call, tables, m, g, eqw_work_bytes(h->N, m, num_ranges), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return eqw_launch(h->stream, tab, nullptr, &t, observer, eqs_table_stream(h, nonce, samples),
+                          EqwRanges{g.at<uint16_t>(wt), num_ranges, g.at<uint16_t>(ro), range_per_table ? 1 : 0}, h->N, m, eqw_out(out.at(g)), work);
+    });
 }
 
-// ---- range equity (pokerl_hip.h "Range equity"; kernels: pk_equity_range.hip).  Work space (the descriptors) as above.
+// ---- range equity (pokerl_hip.h "Range equity"; kernels: pk_equity_range.hip).  Work space: the descriptors.
 static size_t eqr_weight_bytes(size_t m, int per_spot) { return (per_spot ? m : (size_t)1) * EQR_HOLDINGS * 2; }
-#define EQR_CHECK_SPOTS(call, m, inputs)                                                     \
-    if ((m) >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, call ": m >= 2^31");            \
-    if ((m) && !(inputs)) return g_fail(PK_E_INVALID_ARG, call ": NULL input buffer")
+static const char *eqr_check(size_t m, bool inputs) {   // (range equity, range vs range and the histograms: no seat count, no task list)
+    if (const char *why = eq_bad_m(m)) return why;
+    return eq_null(m, inputs);
+}
+static const char *eqr_table_check(const pk_handle *h, size_t m, int observer) {
+    if (const char *why = eq_bad_m(m)) return why;
+    return eqr_bad_observer(observer, h->N);
+}
 
 int pk_equity_range_d(int device, size_t m, const uint8_t *hero_d, const uint8_t *board_d, const uint8_t *nboard_d, const uint64_t *dead_d,
                       const uint16_t *weights_d, int weights_per_spot, uint64_t *agg_d, uint32_t *win_d, uint32_t *tie_d, uint32_t *boards_d,
                       uint8_t *status_d, void *stream) {
-    EQR_CHECK_SPOTS("pk_equity_range_d", m, hero_d && board_d && nboard_d);
-    ON_DEVICE_INDEX("pk_equity_range_d", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t *tab = eval7_table(device, st);   // (a first call builds the table on the CALLER's stream)
-    if (!tab) return g_fail(PK_E_OOM, "pk_equity_range_d: out of device memory (evaluator table)");
-    void *ws = eq_stream_ws(device, st, eqr_work_bytes(m));
-    if (!ws) return g_fail(PK_E_OOM, "pk_equity_range_d: out of device memory (work space)");
-    const EqrSpots spots{hero_d, board_d, nboard_d, dead_d};
-    const hipError_t e = eqr_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{weights_d, weights_per_spot != 0}, m,
-                                    EqrOut{agg_d, win_d, tie_d, boards_d, status_d}, (uint64_t *)ws);
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_range_d: launch failed", e);
-    return PK_OK;
+    const char *call = "pk_equity_range_d";
+    EQ_REFUSE(g_fail, call, eqr_check(m, hero_d && board_d && nboard_d));
+    return eq_call_d(call, device, stream, m, true, eqr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const EqrSpots spots{hero_d, board_d, nboard_d, dead_d};
+        return eqr_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{weights_d, weights_per_spot != 0}, m,
+                          EqrOut{agg_d, win_d, tie_d, boards_d, status_d}, (uint64_t *)work);
+    });
 }
 
 int pk_equity_range(int device, size_t m, const uint8_t *hero, const uint8_t *board, const uint8_t *nboard, const uint64_t *dead,
                     const uint16_t *weights, int weights_per_spot, uint64_t *agg, uint32_t *win, uint32_t *tie, uint32_t *boards,
                     uint8_t *status) {
-    EQR_CHECK_SPOTS("pk_equity_range", m, hero && board && nboard);
-    ON_DEVICE_INDEX("pk_equity_range", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
-    hipStream_t st = nullptr;
-    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity_range: no stream"); }
-    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
-    int rc = PK_OK;
-    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity_range: out of device memory (evaluator table)");
-    else {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        Stage g;
-        const int he = g.in(hero, m * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
-        const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
-        const EqrStagedOut out(g, m, agg, win, tie, boards, status);
-        const int work = g.add(eqr_work_bytes(m));
-        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity_range: out of device memory");
-        else {
-            const hipError_t e = g.run(st, [&] {
-                const EqrSpots spots{g.at<uint8_t>(he), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
-                return eqr_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, out.at(g),
-                                  g.at<uint64_t>(work));
-            });
-            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity_range", e); }   // (the lock is held until what was queued is done)
-        }
-    }
-    stream_release(device, st);
-    return rc;
+    const char *call = "pk_equity_range";
+    EQ_REFUSE(g_fail, call, eqr_check(m, hero && board && nboard));
+    Stage g;
+    const int he = g.in(hero, m * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
+    const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const EqrStagedOut out(g, m, agg, win, tie, boards, status);
+    return eq_call_host(call, device, m, true, g, eqr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const EqrSpots spots{g.at<uint8_t>(he), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
+        return eqr_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, out.at(g),
+                          (uint64_t *)work);
+    });
 }
 
-// The table form: the handle's own state on the handle's stream, as `observer` sees it
-static int table_equity_range(pk_handle *h, const int32_t *tables_d, size_t m, int observer, const EqrWeights &weights, const EqrOut &out, char *work) {
-    const uint32_t *tab = eval7_table(h->device, h->stream);
-    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity_range: out of device memory (evaluator table)");
-    const EqTables t{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T};
-    HIPCHK(h, eqr_launch(h->stream, tab, nullptr, &t, h->N, observer, weights, m, out, (uint64_t *)work));
-    return PK_OK;
-}
-#define EQR_TABLE_ENTER(h, m, observer, call)                                                                                                \
-    if (!(h)) return PK_E_INVALID_ARG;                                                                                                       \
-    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                                                         \
-    if ((observer) != PK_OBSERVER_ACTIVE && ((observer) < 0 || (observer) >= (h)->N))                                                        \
-        return (h)->fail(PK_E_INVALID_ARG, call ": observer outside {-2, 0 .. N-1} (a hidden hand needs somebody to be hidden from)");       \
-    ON_DEVICE(h);                                                                                                                            \
-    FLUSH_READER(h);                                                                                                                         \
-    if ((m) == 0) return PK_OK
-
+// The table forms: the handle's own state as `observer` sees it
 int pk_table_equity_range_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, const uint16_t *weights_d, int weights_per_spot,
                             uint64_t *agg_d, uint32_t *win_d, uint32_t *tie_d, uint32_t *boards_d, uint8_t *status_d) {
-    EQR_TABLE_ENTER(h, m, observer, "pk_table_equity_range_d");
-    char *work = nullptr;
-    if (int rc = snap_staging(h, eqr_work_bytes(m), &work)) return rc;
-    return table_equity_range(h, tables_d, m, observer, EqrWeights{weights_d, weights_per_spot != 0}, EqrOut{agg_d, win_d, tie_d, boards_d, status_d}, work);
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_range_d";
+    EQ_REFUSE(h->fail, call, eqr_table_check(h, m, observer));
+    return eq_table_call_d(h, call, tables_d, m, eqr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return eqr_launch(h->stream, tab, nullptr, &t, h->N, observer, EqrWeights{weights_d, weights_per_spot != 0}, m,
+                          EqrOut{agg_d, win_d, tie_d, boards_d, status_d}, (uint64_t *)work);
+    });
 }
 
 int pk_table_equity_range(pk_handle *h, const int32_t *tables, size_t m, int observer, const uint16_t *weights, int weights_per_spot,
                           uint64_t *agg, uint32_t *win, uint32_t *tie, uint32_t *boards, uint8_t *status) {
-    EQR_TABLE_ENTER(h, m, observer, "pk_table_equity_range");
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_range";
+    EQ_REFUSE(h->fail, call, eqr_table_check(h, m, observer));
     Stage g;
-    const int idx = g.in(tables, m * 4), we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
     const EqrStagedOut out(g, m, agg, win, tie, boards, status);
-    const int work = g.add(eqr_work_bytes(m));
-    int rc = snap_staging(h, g.total, &g.base);
-    if (rc) return rc;
-    HIPCHK(h, g.upload(h->stream));
-    if ((rc = table_equity_range(h, g.at<int32_t>(idx), m, observer, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, out.at(g), g.at<char>(work)))) return rc;
-    HIPCHK(h, g.download(h->stream));
-    return PK_OK;
+    return eq_table_call(h, call, tables, m, g, eqr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return eqr_launch(h->stream, tab, nullptr, &t, h->N, observer, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, out.at(g), (uint64_t *)work);
+    });
 }
 
-
-// ---- range against range (pokerl_hip.h "Range vs range"; kernels: pk_equity_rvr.hip).  Work space (the descriptors) as above.
+// ---- range against range (pokerl_hip.h "Range vs range"; kernels: pk_equity_rvr.hip).  Work space: the descriptors.  The table forms read
+// the public board of the handle's own tables (no hole card is read: there is no observer).
 int pk_equity_rvr_d(int device, size_t m, const uint8_t *board_d, const uint8_t *nboard_d, const uint64_t *dead_d, const uint16_t *weights_d,
                     int weights_per_spot, uint64_t *win_d, uint64_t *tie_d, uint64_t *tot_d, uint32_t *boards_d, uint8_t *status_d, void *stream) {
-    EQR_CHECK_SPOTS("pk_equity_rvr_d", m, board_d && nboard_d);
-    ON_DEVICE_INDEX("pk_equity_rvr_d", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t *tab = eval7_table(device, st);   // (a first call builds the table on the CALLER's stream)
-    if (!tab) return g_fail(PK_E_OOM, "pk_equity_rvr_d: out of device memory (evaluator table)");
-    void *ws = eq_stream_ws(device, st, rvr_work_bytes(m));
-    if (!ws) return g_fail(PK_E_OOM, "pk_equity_rvr_d: out of device memory (work space)");
-    const RvrSpots spots{board_d, nboard_d, dead_d};
-    const hipError_t e = rvr_launch(st, tab, &spots, nullptr, RvrWeights{weights_d, weights_per_spot != 0}, m,
-                                    RvrOut{win_d, tie_d, tot_d, boards_d, status_d}, (uint64_t *)ws);
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_rvr_d: launch failed", e);
-    return PK_OK;
+    const char *call = "pk_equity_rvr_d";
+    EQ_REFUSE(g_fail, call, eqr_check(m, board_d && nboard_d));
+    return eq_call_d(call, device, stream, m, true, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const RvrSpots spots{board_d, nboard_d, dead_d};
+        return rvr_launch(st, tab, &spots, nullptr, RvrWeights{weights_d, weights_per_spot != 0}, m, RvrOut{win_d, tie_d, tot_d, boards_d, status_d},
+                          (uint64_t *)work);
+    });
 }
 
 int pk_equity_rvr(int device, size_t m, const uint8_t *board, const uint8_t *nboard, const uint64_t *dead, const uint16_t *weights,
                   int weights_per_spot, uint64_t *win, uint64_t *tie, uint64_t *tot, uint32_t *boards, uint8_t *status) {
-    EQR_CHECK_SPOTS("pk_equity_rvr", m, board && nboard);
-    ON_DEVICE_INDEX("pk_equity_rvr", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
-    hipStream_t st = nullptr;
-    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity_rvr: no stream"); }
-    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
-    int rc = PK_OK;
-    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity_rvr: out of device memory (evaluator table)");
-    else {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        Stage g;
-        const int bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
-        const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
-        const RvrStagedOut out(g, m, win, tie, tot, boards, status);
-        const int work = g.add(rvr_work_bytes(m));
-        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity_rvr: out of device memory");
-        else {
-            const hipError_t e = g.run(st, [&] {
-                const RvrSpots spots{g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
-                return rvr_launch(st, tab, &spots, nullptr, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, out.at(g), g.at<uint64_t>(work));
-            });
-            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity_rvr", e); }   // (the lock is held until what was queued is done)
-        }
-    }
-    stream_release(device, st);
-    return rc;
+    const char *call = "pk_equity_rvr";
+    EQ_REFUSE(g_fail, call, eqr_check(m, board && nboard));
+    Stage g;
+    const int bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
+    const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const RvrStagedOut out(g, m, win, tie, tot, boards, status);
+    return eq_call_host(call, device, m, true, g, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const RvrSpots spots{g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
+        return rvr_launch(st, tab, &spots, nullptr, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, out.at(g), (uint64_t *)work);
+    });
 }
-
-// The table form: the public board of the handle's own tables on the handle's stream (no hole card is read: there is no observer)
-static int table_equity_rvr(pk_handle *h, const int32_t *tables_d, size_t m, const RvrWeights &weights, const RvrOut &out, char *work) {
-    const uint32_t *tab = eval7_table(h->device, h->stream);
-    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity_rvr: out of device memory (evaluator table)");
-    const EqTables t{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T};
-    HIPCHK(h, rvr_launch(h->stream, tab, nullptr, &t, weights, m, out, (uint64_t *)work));
-    return PK_OK;
-}
-#define RVR_TABLE_ENTER(h, m, call)                                                                  \
-    if (!(h)) return PK_E_INVALID_ARG;                                                               \
-    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                 \
-    ON_DEVICE(h);                                                                                    \
-    FLUSH_READER(h);                                                                                 \
-    if ((m) == 0) return PK_OK
 
 int pk_table_equity_rvr_d(pk_handle *h, const int32_t *tables_d, size_t m, const uint16_t *weights_d, int weights_per_spot, uint64_t *win_d,
                           uint64_t *tie_d, uint64_t *tot_d, uint32_t *boards_d, uint8_t *status_d) {
-    RVR_TABLE_ENTER(h, m, "pk_table_equity_rvr_d");
-    char *work = nullptr;
-    if (int rc = snap_staging(h, rvr_work_bytes(m), &work)) return rc;
-    return table_equity_rvr(h, tables_d, m, RvrWeights{weights_d, weights_per_spot != 0}, RvrOut{win_d, tie_d, tot_d, boards_d, status_d}, work);
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_rvr_d";
+    EQ_REFUSE(h->fail, call, eq_bad_m(m));
+    return eq_table_call_d(h, call, tables_d, m, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return rvr_launch(h->stream, tab, nullptr, &t, RvrWeights{weights_d, weights_per_spot != 0}, m, RvrOut{win_d, tie_d, tot_d, boards_d, status_d},
+                          (uint64_t *)work);
+    });
 }
 
 int pk_table_equity_rvr(pk_handle *h, const int32_t *tables, size_t m, const uint16_t *weights, int weights_per_spot, uint64_t *win, uint64_t *tie,
                         uint64_t *tot, uint32_t *boards, uint8_t *status) {
-    RVR_TABLE_ENTER(h, m, "pk_table_equity_rvr");
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_rvr";
+    EQ_REFUSE(h->fail, call, eq_bad_m(m));
     Stage g;
-    const int idx = g.in(tables, m * 4), we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
     const RvrStagedOut out(g, m, win, tie, tot, boards, status);
-    const int work = g.add(rvr_work_bytes(m));
-    int rc = snap_staging(h, g.total, &g.base);
-    if (rc) return rc;
-    HIPCHK(h, g.upload(h->stream));
-    if ((rc = table_equity_rvr(h, g.at<int32_t>(idx), m, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, out.at(g), g.at<char>(work)))) return rc;
-    HIPCHK(h, g.download(h->stream));
-    return PK_OK;
+    return eq_table_call(h, call, tables, m, g, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return rvr_launch(h->stream, tab, nullptr, &t, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, out.at(g), (uint64_t *)work);
+    });
 }
 
 // ---- strength histograms (pokerl_hip.h "Strength histograms"; kernels: pk_equity_hist.hip).  Spots, weights and work space as range vs range.
 static_assert(HIST_MAX_BINS == PK_EQ_HIST_MAX_BINS, "pk_equity_hist.hpp and the ABI header agree");
-#define HIST_CHECK_BINS(call, nbins) \
-    if ((nbins) < 1 || (nbins) > PK_EQ_HIST_MAX_BINS) return g_fail(PK_E_INVALID_ARG, call ": nbins must be 1 .. PK_EQ_HIST_MAX_BINS (32)")
+static const char *hist_check(size_t m, bool inputs, int nbins) {
+    if (const char *why = eqr_check(m, inputs)) return why;
+    return hist_bad_bins(nbins);
+}
+static const char *hist_table_check(size_t m, int nbins) {
+    if (const char *why = eq_bad_m(m)) return why;
+    return hist_bad_bins(nbins);
+}
 
 int pk_equity_hist_d(int device, size_t m, const uint8_t *board_d, const uint8_t *nboard_d, const uint64_t *dead_d, const uint16_t *weights_d,
                      int weights_per_spot, int nbins, uint16_t *hist_d, uint16_t *void_d, uint32_t *completions_d, uint8_t *status_d, void *stream) {
-    EQR_CHECK_SPOTS("pk_equity_hist_d", m, board_d && nboard_d);
-    HIST_CHECK_BINS("pk_equity_hist_d", nbins);
-    ON_DEVICE_INDEX("pk_equity_hist_d", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t *tab = eval7_table(device, st);   // (a first call builds the table on the CALLER's stream)
-    if (!tab) return g_fail(PK_E_OOM, "pk_equity_hist_d: out of device memory (evaluator table)");
-    void *ws = eq_stream_ws(device, st, rvr_work_bytes(m));
-    if (!ws) return g_fail(PK_E_OOM, "pk_equity_hist_d: out of device memory (work space)");
-    const RvrSpots spots{board_d, nboard_d, dead_d};
-    const hipError_t e = hist_launch(st, tab, &spots, nullptr, RvrWeights{weights_d, weights_per_spot != 0}, m, nbins,
-                                     HistOut{hist_d, void_d, completions_d, status_d}, (uint64_t *)ws);
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_equity_hist_d: launch failed", e);
-    return PK_OK;
+    const char *call = "pk_equity_hist_d";
+    EQ_REFUSE(g_fail, call, hist_check(m, board_d && nboard_d, nbins));
+    return eq_call_d(call, device, stream, m, true, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const RvrSpots spots{board_d, nboard_d, dead_d};
+        return hist_launch(st, tab, &spots, nullptr, RvrWeights{weights_d, weights_per_spot != 0}, m, nbins,
+                           HistOut{hist_d, void_d, completions_d, status_d}, (uint64_t *)work);
+    });
 }
 
 int pk_equity_hist(int device, size_t m, const uint8_t *board, const uint8_t *nboard, const uint64_t *dead, const uint16_t *weights,
                    int weights_per_spot, int nbins, uint16_t *hist, uint16_t *void_, uint32_t *completions, uint8_t *status) {
-    EQR_CHECK_SPOTS("pk_equity_hist", m, board && nboard);
-    HIST_CHECK_BINS("pk_equity_hist", nbins);
-    ON_DEVICE_INDEX("pk_equity_hist", device, PK_MAX_DEVICES);
-    if (m == 0) return PK_OK;
-    hipStream_t st = nullptr;
-    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, "pk_equity_hist: no stream"); }
-    const uint32_t *tab = eval7_table(device, st);   // (takes g_scratch_mu itself)
-    int rc = PK_OK;
-    if (!tab) rc = g_fail(PK_E_OOM, "pk_equity_hist: out of device memory (evaluator table)");
-    else {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        Stage g;
-        const int bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
-        const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
-        const HistStagedOut out(g, m, nbins, hist, void_, completions, status);
-        const int work = g.add(rvr_work_bytes(m));
-        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, "pk_equity_hist: out of device memory");
-        else {
-            const hipError_t e = g.run(st, [&] {
-                const RvrSpots spots{g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
-                return hist_launch(st, tab, &spots, nullptr, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, nbins, out.at(g), g.at<uint64_t>(work));
-            });
-            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, "pk_equity_hist", e); }   // (the lock is held until what was queued is done)
-        }
-    }
-    stream_release(device, st);
-    return rc;
+    const char *call = "pk_equity_hist";
+    EQ_REFUSE(g_fail, call, hist_check(m, board && nboard, nbins));
+    Stage g;
+    const int bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
+    const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const HistStagedOut out(g, m, nbins, hist, void_, completions, status);
+    return eq_call_host(call, device, m, true, g, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const RvrSpots spots{g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
+        return hist_launch(st, tab, &spots, nullptr, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, nbins, out.at(g), (uint64_t *)work);
+    });
 }
-
-// The table form: the public board of the handle's own tables on the handle's stream (no hole card is read: there is no observer)
-static int table_equity_hist(pk_handle *h, const int32_t *tables_d, size_t m, const RvrWeights &weights, int nbins, const HistOut &out, char *work) {
-    const uint32_t *tab = eval7_table(h->device, h->stream);
-    if (!tab) return h->fail(PK_E_OOM, "pk_table_equity_hist: out of device memory (evaluator table)");
-    const EqTables t{h->S.cards, h->S.seat_states, h->S.cursors, tables_d, h->T};
-    HIPCHK(h, hist_launch(h->stream, tab, nullptr, &t, weights, m, nbins, out, (uint64_t *)work));
-    return PK_OK;
-}
-#define HIST_TABLE_ENTER(h, m, nbins, call)                                                                                      \
-    if (!(h)) return PK_E_INVALID_ARG;                                                                                           \
-    if ((m) >= EQ_MAX_SPOTS) return (h)->fail(PK_E_INVALID_ARG, call ": m >= 2^31");                                             \
-    if ((nbins) < 1 || (nbins) > PK_EQ_HIST_MAX_BINS) return (h)->fail(PK_E_INVALID_ARG, call ": nbins must be 1 .. PK_EQ_HIST_MAX_BINS (32)"); \
-    ON_DEVICE(h);                                                                                                                \
-    FLUSH_READER(h);                                                                                                             \
-    if ((m) == 0) return PK_OK
 
 int pk_table_equity_hist_d(pk_handle *h, const int32_t *tables_d, size_t m, const uint16_t *weights_d, int weights_per_spot, int nbins,
                            uint16_t *hist_d, uint16_t *void_d, uint32_t *completions_d, uint8_t *status_d) {
-    HIST_TABLE_ENTER(h, m, nbins, "pk_table_equity_hist_d");
-    char *work = nullptr;
-    if (int rc = snap_staging(h, rvr_work_bytes(m), &work)) return rc;
-    return table_equity_hist(h, tables_d, m, RvrWeights{weights_d, weights_per_spot != 0}, nbins, HistOut{hist_d, void_d, completions_d, status_d}, work);
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_hist_d";
+    EQ_REFUSE(h->fail, call, hist_table_check(m, nbins));
+    return eq_table_call_d(h, call, tables_d, m, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return hist_launch(h->stream, tab, nullptr, &t, RvrWeights{weights_d, weights_per_spot != 0}, m, nbins,
+                           HistOut{hist_d, void_d, completions_d, status_d}, (uint64_t *)work);
+    });
 }
 
 int pk_table_equity_hist(pk_handle *h, const int32_t *tables, size_t m, const uint16_t *weights, int weights_per_spot, int nbins, uint16_t *hist,
                          uint16_t *void_, uint32_t *completions, uint8_t *status) {
-    HIST_TABLE_ENTER(h, m, nbins, "pk_table_equity_hist");
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_hist";
+    EQ_REFUSE(h->fail, call, hist_table_check(m, nbins));
     Stage g;
-    const int idx = g.in(tables, m * 4), we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
     const HistStagedOut out(g, m, nbins, hist, void_, completions, status);
-    const int work = g.add(rvr_work_bytes(m));
-    int rc = snap_staging(h, g.total, &g.base);
-    if (rc) return rc;
-    HIPCHK(h, g.upload(h->stream));
-    if ((rc = table_equity_hist(h, g.at<int32_t>(idx), m, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, nbins, out.at(g), g.at<char>(work)))) return rc;
-    HIPCHK(h, g.download(h->stream));
-    return PK_OK;
+    return eq_table_call(h, call, tables, m, g, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return hist_launch(h->stream, tab, nullptr, &t, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, nbins, out.at(g), (uint64_t *)work);
+    });
 }
 
-
-// ---- histogram clustering (pokerl_hip.h "Histogram clustering"; kernels: pk_hist_cluster.hip).  Work space: the per-(device, stream) buffer.
+// ---- histogram clustering (pokerl_hip.h "Histogram clustering"; kernels: pk_hist_cluster.hip).  The device and the host form of the family
+// (n >= 1 rows stand where the spots do), no evaluator table.
 static_assert(CL_MAX_K == PK_CL_MAX_K && CL_NONE == PK_CL_NONE && CL_MAX_BINS == PK_EQ_HIST_MAX_BINS, "pk_hist_cluster.hpp and the ABI header agree");
-#define CL_CHECK(call, n, nbins, K, arrays)                                                                                                        \
-    if ((nbins) < 1 || (nbins) > PK_EQ_HIST_MAX_BINS) return g_fail(PK_E_INVALID_ARG, call ": nbins must be 1 .. PK_EQ_HIST_MAX_BINS (32)");       \
-    if ((n) < 1 || (n) >= EQ_MAX_SPOTS) return g_fail(PK_E_INVALID_ARG, call ": n must be 1 .. 2^31 - 1");                                         \
-    if ((K) < 1 || (K) > PK_CL_MAX_K) return g_fail(PK_E_INVALID_ARG, call ": K must be 1 .. PK_CL_MAX_K (4096)");                                 \
-    if (!(arrays)) return g_fail(PK_E_INVALID_ARG, call ": NULL array")
+static const char *cl_check(size_t n, int nbins, int K, bool arrays) {
+    if (const char *why = hist_bad_bins(nbins)) return why;
+    if (n < 1 || n >= EQ_MAX_SPOTS) return ": n must be 1 .. 2^31 - 1";
+    if (K < 1 || K > PK_CL_MAX_K) return ": K must be 1 .. PK_CL_MAX_K (4096)";
+    return arrays ? nullptr : ": NULL array";
+}
 // seeding and clustering take their centroids from rows: K rows at least (assign labels any number of rows with any K)
-#define CL_CHECK_K_ROWS(call, n, K) \
-    if ((size_t)(K) > (n)) return g_fail(PK_E_INVALID_ARG, call ": K is larger than the number of rows")
-#define CL_CHECK_ITERS(call, iters) \
-    if ((iters) < 1 || (iters) > CL_MAX_ITERS) return g_fail(PK_E_INVALID_ARG, call ": iters must be 1 .. 1024")
+static const char *cl_bad_k_rows(size_t n, int K) { return (size_t)K > n ? ": K is larger than the number of rows" : nullptr; }
+static const char *cl_bad_iters(int iters) { return iters < 1 || iters > CL_MAX_ITERS ? ": iters must be 1 .. 1024" : nullptr; }
 // the host forms see the rows: K non-empty ones at least
-static bool cl_enough_rows(size_t n, int nbins, const uint16_t *hist, int K) {
+static const char *cl_bad_rows(size_t n, int nbins, const uint16_t *hist, int K) {
     size_t live = 0;
     for (size_t i = 0; i < n && live < (size_t)K; ++i) {
         uint32_t mass = 0;
         for (int b = 0; b < nbins; ++b) mass += hist[i * (size_t)nbins + b];
         live += mass != 0;
     }
-    return live >= (size_t)K;
+    return live < (size_t)K ? ": K is larger than the number of non-empty rows" : nullptr;
 }
-#define CL_CHECK_ROWS(call, n, nbins, hist, K) \
-    if (!cl_enough_rows(n, nbins, hist, K)) return g_fail(PK_E_INVALID_ARG, call ": K is larger than the number of non-empty rows")
 
 int pk_hist_cluster_seed_d(int device, size_t n, int nbins, const uint16_t *hist_d, int K, uint64_t seed, uint32_t nonce, uint16_t *centroids_d,
                            void *stream) {
-    CL_CHECK("pk_hist_cluster_seed_d", n, nbins, K, hist_d && centroids_d);
-    CL_CHECK_K_ROWS("pk_hist_cluster_seed_d", n, K);
-    ON_DEVICE_INDEX("pk_hist_cluster_seed_d", device, PK_MAX_DEVICES);
-    hipStream_t st = (hipStream_t)stream;
-    void *ws = eq_stream_ws(device, st, cl_work_bytes(n, nbins, K, true, false));
-    if (!ws) return g_fail(PK_E_OOM, "pk_hist_cluster_seed_d: out of device memory (work space)");
-    const hipError_t e = cl_seed_launch(st, n, nbins, hist_d, K, (uint32_t)seed, (uint32_t)(seed >> 32), nonce, centroids_d, cl_work(ws, n, nbins, K, true, false));
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_hist_cluster_seed_d: launch failed", e);
-    return PK_OK;
+    const char *call = "pk_hist_cluster_seed_d";
+    EQ_REFUSE(g_fail, call, cl_check(n, nbins, K, hist_d && centroids_d));
+    EQ_REFUSE(g_fail, call, cl_bad_k_rows(n, K));
+    return eq_call_d(call, device, stream, n, false, cl_work_bytes(n, nbins, K, true, false), [&](hipStream_t st, const uint32_t *, char *work) {
+        return cl_seed_launch(st, n, nbins, hist_d, K, (uint32_t)seed, (uint32_t)(seed >> 32), nonce, centroids_d, cl_work(work, n, nbins, K, true, false));
+    });
 }
 
 int pk_hist_cluster_assign_d(int device, size_t n, int nbins, const uint16_t *hist_d, int K, const uint16_t *centroids_d, uint16_t *label_d,
                              uint32_t *dist_d, void *stream) {
-    CL_CHECK("pk_hist_cluster_assign_d", n, nbins, K, hist_d && centroids_d && label_d);
-    ON_DEVICE_INDEX("pk_hist_cluster_assign_d", device, PK_MAX_DEVICES);
-    hipStream_t st = (hipStream_t)stream;
-    void *ws = eq_stream_ws(device, st, cl_work_bytes(n, nbins, K, false, false));
-    if (!ws) return g_fail(PK_E_OOM, "pk_hist_cluster_assign_d: out of device memory (work space)");
-    const hipError_t e = cl_assign_launch(st, n, nbins, hist_d, K, centroids_d, label_d, dist_d, cl_work(ws, n, nbins, K, false, false));
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_hist_cluster_assign_d: launch failed", e);
-    return PK_OK;
+    const char *call = "pk_hist_cluster_assign_d";
+    EQ_REFUSE(g_fail, call, cl_check(n, nbins, K, hist_d && centroids_d && label_d));
+    return eq_call_d(call, device, stream, n, false, cl_work_bytes(n, nbins, K, false, false), [&](hipStream_t st, const uint32_t *, char *work) {
+        return cl_assign_launch(st, n, nbins, hist_d, K, centroids_d, label_d, dist_d, cl_work(work, n, nbins, K, false, false));
+    });
 }
 
 int pk_hist_cluster_d(int device, size_t n, int nbins, const uint16_t *hist_d, int K, uint16_t *centroids_d, int iters, uint16_t *label_d,
                       uint32_t *dist_d, uint64_t *inertia_d, uint32_t *changed_d, void *stream) {
-    CL_CHECK("pk_hist_cluster_d", n, nbins, K, hist_d && centroids_d && label_d);
-    CL_CHECK_K_ROWS("pk_hist_cluster_d", n, K);
-    CL_CHECK_ITERS("pk_hist_cluster_d", iters);
-    ON_DEVICE_INDEX("pk_hist_cluster_d", device, PK_MAX_DEVICES);
-    hipStream_t st = (hipStream_t)stream;
-    void *ws = eq_stream_ws(device, st, cl_work_bytes(n, nbins, K, false, true));
-    if (!ws) return g_fail(PK_E_OOM, "pk_hist_cluster_d: out of device memory (work space)");
-    const hipError_t e = cl_cluster_launch(st, n, nbins, hist_d, K, centroids_d, iters, label_d, dist_d, inertia_d, changed_d, cl_work(ws, n, nbins, K, false, true));
-    if (e != hipSuccess) return g_fail(PK_E_HIP, "pk_hist_cluster_d: launch failed", e);
-    return PK_OK;
+    const char *call = "pk_hist_cluster_d";
+    EQ_REFUSE(g_fail, call, cl_check(n, nbins, K, hist_d && centroids_d && label_d));
+    EQ_REFUSE(g_fail, call, cl_bad_k_rows(n, K));
+    EQ_REFUSE(g_fail, call, cl_bad_iters(iters));
+    return eq_call_d(call, device, stream, n, false, cl_work_bytes(n, nbins, K, false, true), [&](hipStream_t st, const uint32_t *, char *work) {
+        return cl_cluster_launch(st, n, nbins, hist_d, K, centroids_d, iters, label_d, dist_d, inertia_d, changed_d, cl_work(work, n, nbins, K, false, true));
+    });
 }
-
-// The host forms: one staging buffer (inputs, outputs, work space) on a pooled stream; launch(g, work) queues the kernels
-extern "C++" {
-template <typename F>
-static int cl_host_call(const char *call, int device, Stage &g, size_t work_bytes, F launch) {
-    hipStream_t st = nullptr;
-    if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return g_fail(PK_E_HIP, (std::string(call) + ": no stream").c_str()); }
-    int rc = PK_OK;
-    {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        const int work = g.add(work_bytes);
-        if (!(g.base = scratch(device, g.total, st))) rc = g_fail(PK_E_OOM, (std::string(call) + ": out of device memory").c_str());
-        else {
-            const hipError_t e = g.run(st, [&] { return launch(st, g.at<char>(work)); });
-            if (e != hipSuccess) { (void)hipStreamSynchronize(st); rc = g_fail(PK_E_HIP, call, e); }   // (the lock is held until what was queued is done)
-        }
-    }
-    stream_release(device, st);
-    return rc;
-}
-}  // extern "C++" (a template)
 
 int pk_hist_cluster_seed(int device, size_t n, int nbins, const uint16_t *hist, int K, uint64_t seed, uint32_t nonce, uint16_t *centroids) {
-    CL_CHECK("pk_hist_cluster_seed", n, nbins, K, hist && centroids);
-    CL_CHECK_K_ROWS("pk_hist_cluster_seed", n, K);
-    CL_CHECK_ROWS("pk_hist_cluster_seed", n, nbins, hist, K);
-    ON_DEVICE_INDEX("pk_hist_cluster_seed", device, PK_MAX_DEVICES);
+    const char *call = "pk_hist_cluster_seed";
+    EQ_REFUSE(g_fail, call, cl_check(n, nbins, K, hist && centroids));
+    EQ_REFUSE(g_fail, call, cl_bad_k_rows(n, K));
+    EQ_REFUSE(g_fail, call, cl_bad_rows(n, nbins, hist, K));
     Stage g;
     const int hi = g.in(hist, n * (size_t)nbins * 2), ce = g.out(centroids, (size_t)K * nbins * 2);
-    return cl_host_call("pk_hist_cluster_seed", device, g, cl_work_bytes(n, nbins, K, true, false), [&](hipStream_t st, char *work) {
+    return eq_call_host(call, device, n, false, g, cl_work_bytes(n, nbins, K, true, false), [&](hipStream_t st, const uint32_t *, char *work) {
         return cl_seed_launch(st, n, nbins, g.at<uint16_t>(hi), K, (uint32_t)seed, (uint32_t)(seed >> 32), nonce, g.at<uint16_t>(ce), cl_work(work, n, nbins, K, true, false));
     });
 }
 
 int pk_hist_cluster_assign(int device, size_t n, int nbins, const uint16_t *hist, int K, const uint16_t *centroids, uint16_t *label, uint32_t *dist) {
-    CL_CHECK("pk_hist_cluster_assign", n, nbins, K, hist && centroids && label);
-    ON_DEVICE_INDEX("pk_hist_cluster_assign", device, PK_MAX_DEVICES);
+    const char *call = "pk_hist_cluster_assign";
+    EQ_REFUSE(g_fail, call, cl_check(n, nbins, K, hist && centroids && label));
     Stage g;
     const int hi = g.in(hist, n * (size_t)nbins * 2), ce = g.in(centroids, (size_t)K * nbins * 2), la = g.out(label, n * 2), di = g.out(dist, n * 4);
-    return cl_host_call("pk_hist_cluster_assign", device, g, cl_work_bytes(n, nbins, K, false, false), [&](hipStream_t st, char *work) {
+    return eq_call_host(call, device, n, false, g, cl_work_bytes(n, nbins, K, false, false), [&](hipStream_t st, const uint32_t *, char *work) {
         return cl_assign_launch(st, n, nbins, g.at<uint16_t>(hi), K, g.at<uint16_t>(ce), g.at<uint16_t>(la), g.at<uint32_t>(di), cl_work(work, n, nbins, K, false, false));
     });
 }
 
 int pk_hist_cluster(int device, size_t n, int nbins, const uint16_t *hist, int K, uint16_t *centroids, int iters, uint16_t *label, uint32_t *dist,
                     uint64_t *inertia, uint32_t *changed) {
-    CL_CHECK("pk_hist_cluster", n, nbins, K, hist && centroids && label);
-    CL_CHECK_K_ROWS("pk_hist_cluster", n, K);
-    CL_CHECK_ITERS("pk_hist_cluster", iters);
-    CL_CHECK_ROWS("pk_hist_cluster", n, nbins, hist, K);
-    ON_DEVICE_INDEX("pk_hist_cluster", device, PK_MAX_DEVICES);
+    const char *call = "pk_hist_cluster";
+    EQ_REFUSE(g_fail, call, cl_check(n, nbins, K, hist && centroids && label));
+    EQ_REFUSE(g_fail, call, cl_bad_k_rows(n, K));
+    EQ_REFUSE(g_fail, call, cl_bad_iters(iters));
+    EQ_REFUSE(g_fail, call, cl_bad_rows(n, nbins, hist, K));
     Stage g;
     const int hi = g.in(hist, n * (size_t)nbins * 2), ce = g.add((size_t)K * nbins * 2, centroids, centroids), la = g.out(label, n * 2), di = g.out(dist, n * 4);
     const int in = g.out(inertia, (size_t)(iters + 1) * 8), ch = g.out(changed, (size_t)iters * 4);
-    return cl_host_call("pk_hist_cluster", device, g, cl_work_bytes(n, nbins, K, false, true), [&](hipStream_t st, char *work) {
+    return eq_call_host(call, device, n, false, g, cl_work_bytes(n, nbins, K, false, true), [&](hipStream_t st, const uint32_t *, char *work) {
         return cl_cluster_launch(st, n, nbins, g.at<uint16_t>(hi), K, g.at<uint16_t>(ce), iters, g.at<uint16_t>(la), g.at<uint32_t>(di), g.at<uint64_t>(in),
                                  g.at<uint32_t>(ch), cl_work(work, n, nbins, K, false, true));
     });

@@ -12,6 +12,7 @@
 // Ordinary vector stores and atomics only; no scratch memory (tests/test_equity_host.py reads the code objects).
 #include <hip/hip_runtime.h>
 
+#include "pk_equity_common.hpp"
 #include "pk_equity.hpp"
 
 using namespace pk;
@@ -130,26 +131,6 @@ __global__ void __launch_bounds__(EQ_PREP_BLOCK) k_equity_prep(EqPrepArgs a) {
         if (first + c < a.w.task_cap) a.w.tasks[first + c] = make_uint2((uint32_t)tid, c);
 }
 
-__device__ __forceinline__ uint32_t eq_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t eq_uniform(uint64_t x) { return (uint64_t)eq_uniform((uint32_t)x) | ((uint64_t)eq_uniform((uint32_t)(x >> 32)) << 32); }
-__device__ __forceinline__ uint32_t eq_wave_sum(uint32_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-__device__ __forceinline__ uint64_t eq_wave_sum(uint64_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-// C(n, J) for the unranking, J a compile-time 1 .. 4 (n <= 51); 0 where n < J
-template <int J>
-__device__ __forceinline__ uint32_t eq_binom_c(uint32_t n) {
-    if constexpr (J == 1) return n;
-    else if constexpr (J == 2) return n * (n - 1u) / 2u;                     // (n = 0: 0 * 0xffffffff = 0)
-    else if constexpr (J == 3) return n < 3u ? 0u : n * (n - 1u) * (n - 2u) / 6u;
-    else return n < 4u ? 0u : n * (n - 1u) * (n - 2u) * (n - 3u) / 24u;
-}
 
 // registers per lane: eight waves per SIMD (64) up to three seats, four (128) up to eight, two beyond -- no spill at any seat count
 template <int N> constexpr int eq_min_waves() { return N <= 3 ? 8 : (N <= 8 ? 4 : 2); }
@@ -165,7 +146,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
     for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQ_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
     if (threadIdx.x < 32) wt[PK_IDX(threadIdx.x, 32, "wt")] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
     __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = eq_uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
+    const uint32_t lane = threadIdx.x & 63u, wave = uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
     uint64_t *mypool = pool[PK_IDX(wave, EQ_WAVES, "pool")];
     // Tasks are taken in runs of `take` consecutive ones: a wavefront's first run is its own number, the next ones come from the counter,
     // fetched one run ahead.  One task per run while there are few (a lone pre-flop spot must spread over every CU); four once there are
@@ -178,11 +159,11 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
             if (lane == 0) fetched = atomicAdd(&W.ctrl->next, 1u);
         }
         const uint2 task = W.tasks[t];
-        const uint32_t spot = eq_uniform(task.x), chunk = eq_uniform(task.y);
+        const uint32_t spot = uniform(task.x), chunk = uniform(task.y);
         const uint64_t *d = W.desc + (size_t)spot * (3 + N);
-        const uint64_t known = eq_uniform(d[0]), avail = eq_uniform(d[1]), meta = eq_uniform(d[2]);
+        const uint64_t known = uniform(d[0]), avail = uniform(d[1]), meta = uniform(d[2]);
         uint64_t hole[N];
-        PK_FOR(p, N) hole[p] = eq_uniform(d[3 + p]); PK_END
+        PK_FOR(p, N) hole[p] = uniform(d[3 + p]); PK_END
         const uint32_t boards = (uint32_t)meta, mhi = (uint32_t)(meta >> 32), live = mhi & 0xffffu, k = (mhi >> 16) & 0xffu, P = mhi >> 24;
         // this task's boards [start, end) of the spot's, and this lane's [s, s + cnt) of those
         const uint32_t per_max = 64u * (uint32_t)lpt_max, nch = (boards + per_max - 1) / per_max, per = (boards + nch - 1) / nch;
@@ -206,7 +187,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
             auto level = [&](auto jc) {
                 constexpr int J = decltype(jc)::value;
                 while (x < P) {
-                    const uint32_t c = eq_binom_c<J>(P - 1u - x);
+                    const uint32_t c = binom_c<J>(P - 1u - x);
                     if (r < c) break;
                     r -= c; ++x;
                 }
@@ -254,8 +235,8 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
         // per seat: the wavefront's sums, then one atomic per output from lane 0
         PK_FOR(p, N)
             if ((live >> p) & 1u) {
-                const uint32_t ws = eq_wave_sum(sole[p]), wi = eq_wave_sum(inw[p]);
-                const uint64_t wsh = eq_wave_sum((uint64_t)sh[p]);
+                const uint32_t ws = wave_sum(sole[p]), wi = wave_sum(inw[p]);
+                const uint64_t wsh = wave_sum((uint64_t)sh[p]);
                 if (lane == 0) {
                     const size_t o = (size_t)spot * N + p;
                     if (out.win && ws) atomicAdd(&out.win[o], ws);
@@ -264,7 +245,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
                 }
             }
         PK_END
-        if (--left == 0) { t = (eq_uniform(fetched) + nwaves) * take; left = take; }
+        if (--left == 0) { t = (uniform(fetched) + nwaves) * take; left = take; }
         else ++t;
     }
 }

@@ -12,6 +12,7 @@
 // Ordinary vector stores and atomics only; no scratch memory (tests/test_equity_ev_host.py reads the code objects).
 #include <hip/hip_runtime.h>
 
+#include "pk_equity_common.hpp"
 #include "pk_equity_ev.hpp"
 
 using namespace pk;
@@ -186,21 +187,6 @@ __global__ void __launch_bounds__(EV_PREP_BLOCK) k_ev_prep(EvPrepArgs a) {
                 if (slot < a.w.eq.task_cap) a.w.eq.tasks[slot] = make_uint2((uint32_t)tid, c | (g << 24));
 }
 
-__device__ __forceinline__ uint32_t ev_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t ev_uniform(uint64_t x) { return (uint64_t)ev_uniform((uint32_t)x) | ((uint64_t)ev_uniform((uint32_t)(x >> 32)) << 32); }
-__device__ __forceinline__ uint64_t ev_wave_sum(uint64_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-// C(n, J) for the unranking, J a compile-time 1 .. 4 (n <= 51); 0 where n < J
-template <int J>
-__device__ __forceinline__ uint32_t ev_binom_c(uint32_t n) {
-    if constexpr (J == 1) return n;
-    else if constexpr (J == 2) return n * (n - 1u) / 2u;                     // (n = 0: 0 * 0xffffffff = 0)
-    else if constexpr (J == 3) return n < 3u ? 0u : n * (n - 1u) * (n - 2u) / 6u;
-    else return n < 4u ? 0u : n * (n - 1u) * (n - 2u) * (n - 3u) / 24u;
-}
 
 // registers per lane: as k_equity<N> -- its 3 N counters are this kernel's ev_group(N) * N
 template <int N> constexpr int ev_min_waves() { return N <= 3 ? 8 : (N <= 8 ? 4 : 2); }
@@ -217,7 +203,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, ev_min_waves<N>()) k_ev(const uint32
     for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQ_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
     if (threadIdx.x < 32) wt[PK_IDX(threadIdx.x, 32, "wt")] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
     __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = ev_uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
+    const uint32_t lane = threadIdx.x & 63u, wave = uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
     uint64_t *mypool = pool[PK_IDX(wave, EQ_WAVES, "pool")];
     // tasks are taken in runs, as k_equity takes them
     const uint32_t take = ntasks >= 8u * nwaves ? 4u : 1u;
@@ -228,16 +214,16 @@ __global__ void __launch_bounds__(EQ_BLOCK, ev_min_waves<N>()) k_ev(const uint32
             if (lane == 0) fetched = atomicAdd(&W.eq.ctrl->next, 1u);
         }
         const uint2 task = W.eq.tasks[t];
-        const uint32_t spot = ev_uniform(task.x), ty = ev_uniform(task.y), chunk = ty & 0xffffffu, first = (ty >> 24) * (uint32_t)G;
+        const uint32_t spot = uniform(task.x), ty = uniform(task.y), chunk = ty & 0xffffffu, first = (ty >> 24) * (uint32_t)G;
         const uint64_t *d = W.eq.desc + (size_t)spot * (3 + N);
-        const uint64_t known = ev_uniform(d[0]), avail = ev_uniform(d[1]), meta = ev_uniform(d[2]);
+        const uint64_t known = uniform(d[0]), avail = uniform(d[1]), meta = uniform(d[2]);
         uint64_t hole[N];
-        PK_FOR(p, N) hole[p] = ev_uniform(d[3 + p]); PK_END
+        PK_FOR(p, N) hole[p] = uniform(d[3 + p]); PK_END
         // the levels of this task's group: remain mask and flags, scalars (0: no level here)
         uint32_t lv[G];
         PK_FOR(c, G)
             lv[c] = 0;
-            if (first + c < (uint32_t)N) lv[c] = ev_uniform(W.levels[(size_t)spot * N + first + c]);
+            if (first + c < (uint32_t)N) lv[c] = uniform(W.levels[(size_t)spot * N + first + c]);
         PK_END
         const uint32_t boards = (uint32_t)meta, mhi = (uint32_t)(meta >> 32), live = mhi & 0xffffu, k = (mhi >> 16) & 0xffu, P = mhi >> 24;
         // this task's boards [start, end) of the spot's, and this lane's [s, s + cnt) of those
@@ -262,7 +248,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, ev_min_waves<N>()) k_ev(const uint32
             auto level = [&](auto jc) {
                 constexpr int J = decltype(jc)::value;
                 while (x < P) {
-                    const uint32_t c = ev_binom_c<J>(P - 1u - x);
+                    const uint32_t c = binom_c<J>(P - 1u - x);
                     if (r < c) break;
                     r -= c; ++x;
                 }
@@ -311,14 +297,14 @@ __global__ void __launch_bounds__(EQ_BLOCK, ev_min_waves<N>()) k_ev(const uint32
             if (lv[c] & EV_COMPARE) {
                 PK_FOR(p, N)
                     if ((lv[c] >> p) & 1u) {
-                        const uint64_t wsh = ev_wave_sum((uint64_t)sh[c][p]);
+                        const uint64_t wsh = wave_sum((uint64_t)sh[c][p]);
                         if (lane == 0 && wsh)
                             atomicAdd(reinterpret_cast<unsigned long long *>(&W.share[((size_t)spot * N + first + c) * N + p]), (unsigned long long)wsh);
                     }
                 PK_END
             }
         PK_END
-        if (--left == 0) { t = (ev_uniform(fetched) + nwaves) * take; left = take; }
+        if (--left == 0) { t = (uniform(fetched) + nwaves) * take; left = take; }
         else ++t;
     }
 }

@@ -18,6 +18,7 @@
 // Ordinary vector loads / stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_hist_host.py reads the code objects).
 #include <hip/hip_runtime.h>
 
+#include "pk_equity_common.hpp"
 #include "pk_equity_hist.hpp"
 
 using namespace pk;
@@ -25,31 +26,15 @@ using namespace pk;
 constexpr uint32_t HIST_NONE = 63;            // pool slot that holds no card: a completion card that does not exist (k < 2)
 constexpr uint32_t HIST_SENT = 0xFFFFFFFFu;   // the key of a holding that is out of play on this completion: above every real key (24 bits)
 
-__device__ __forceinline__ uint32_t hist_binom2(uint32_t n, uint32_t k) { return k == 0 ? 1u : (k == 1 ? n : n * (n - 1u) / 2u); }   // C(n, k), k <= 2
 
 __global__ void __launch_bounds__(HIST_COUNTS_BLOCK) k_hist_counts(const uint64_t *__restrict__ desc, uint32_t *__restrict__ completions, size_t m) {
     const size_t i = (size_t)blockIdx.x * HIST_COUNTS_BLOCK + threadIdx.x;
     if (i >= m) return;
     const uint64_t meta = desc[i * (size_t)RVR_DESC_WORDS + 2];
     const uint32_t boards = (uint32_t)meta, k = (uint32_t)(meta >> 48) & 0xffu, P = (uint32_t)(meta >> 56);
-    completions[i] = boards ? hist_binom2(P - 2u, k) : 0u;                      // (boards != 0: the spot is good, P >= k + 4)
+    completions[i] = boards ? binom2(P - 2u, k) : 0u;                      // (boards != 0: the spot is good, P >= k + 4)
 }
 
-__device__ __forceinline__ uint32_t hist_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t hist_uniform(uint64_t x) { return (uint64_t)hist_uniform((uint32_t)x) | ((uint64_t)hist_uniform((uint32_t)(x >> 32)) << 32); }
-__device__ __forceinline__ uint32_t hist_tri(uint32_t n) { return n * (n - 1u) / 2u; }   // (n = 0: 0 * 0xffffffff = 0)
-// t = b (b - 1) / 2 + a with a < b -> (a, b); t < 2^20
-__device__ __forceinline__ void hist_unpair(uint32_t t, uint32_t &a, uint32_t &b) {
-    b = (uint32_t)((1.0f + sqrtf(1.0f + 8.0f * (float)t)) * 0.5f);
-    b = b < 1u ? 1u : b;
-    while (hist_tri(b) > t) --b;
-    while (hist_tri(b + 1u) <= t) ++b;
-    a = t - hist_tri(b);
-}
-// the index of the pair {a, x}, a != x
-__device__ __forceinline__ uint32_t hist_pair(uint32_t a, uint32_t tri_a, uint32_t x, uint32_t tri_x) { return x < a ? tri_a + x : tri_x + a; }
-// The two-seat order: the hero beats exactly the words whose key is SMALLER, and ties exactly the equal key.
-__device__ __forceinline__ uint32_t hist_key(uint32_t word) { return ((15u - (word >> 20)) << 20) | (word & 0xFFFFFu); }
 
 // registers per lane: four waves per SIMD (two 512-thread workgroups per CU, what the group segment allows) cap a lane at 128 registers
 __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, RvrWeights wts, HistOut out,
@@ -63,12 +48,12 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
     __shared__ uint32_t canon[64];                    // ... and its canonical index
     __shared__ uint32_t wsum[RVR_WAVES];
     for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += RVR_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = hist_uniform(tid >> 6);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
     const uint32_t row_words = (uint32_t)RVR_HOLDINGS * nbins;                // u16 entries of one spot's rows: at most 42 432
     for (uint32_t spot = blockIdx.x; spot < m; spot += gridDim.x) {
         __syncthreads();                              // (the table; the spot before: its pool, weights, keys and sums are done with)
         const uint64_t *d = desc + (size_t)spot * RVR_DESC_WORDS;
-        const uint64_t known = hist_uniform(d[0]), avail = hist_uniform(d[1]), meta = hist_uniform(d[2]);
+        const uint64_t known = uniform(d[0]), avail = uniform(d[1]), meta = uniform(d[2]);
         const uint32_t boards = (uint32_t)meta, k = (uint32_t)(meta >> 48) & 0xffu, P = (uint32_t)(meta >> 56);
         uint16_t *rows = out.hist ? out.hist + (size_t)spot * row_words : nullptr;
         // ---- every entry of the spot's rows is written: zeros first, by the whole workgroup (a refused spot, an invalid holding: they stay)
@@ -85,7 +70,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
             }
             if (tid == HIST_NONE) { pool[HIST_NONE] = 0; canon[HIST_NONE] = 0; }
             __syncthreads();                          // (... and the zeros above are in place before any lane counts in its rows)
-            const uint32_t nh = hist_tri(P), nreal = hist_tri(P - k);   // pool holdings; those a completion leaves in play
+            const uint32_t nh = tri(P), nreal = tri(P - k);   // pool holdings; those a completion leaves in play
             uint32_t npad = 64;
             while (npad < nh) npad <<= 1;                             // (> nh: C(P, 2) is no power of two for P >= 3, so a pad slot always exists)
             // ---- per spot: the pool holdings this lane ranks (ea < eb pool slots), the weights by pool holding, the pad slots
@@ -97,9 +82,9 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
                 const uint32_t ph = tid + (uint32_t)j * RVR_BLOCK;
                 ea[j] = HIST_NONE; eb[j] = HIST_NONE; ebits[j] = 0;
                 if (ph < nh) {
-                    hist_unpair(ph, ea[j], eb[j]);
+                    unpair(ph, ea[j], eb[j]);
                     ebits[j] = pool[PK_IDX(ea[j], 64, "pool")] | pool[PK_IDX(eb[j], 64, "pool")];
-                    const uint32_t gh = hist_tri(canon[PK_IDX(eb[j], 64, "canon")]) + canon[PK_IDX(ea[j], 64, "canon")];
+                    const uint32_t gh = tri(canon[PK_IDX(eb[j], 64, "canon")]) + canon[PK_IDX(ea[j], 64, "canon")];
                     const uint32_t w = wv ? (uint32_t)wv[PK_IDX(gh, RVR_HOLDINGS, "weights")] : 1u;
                     wp[PK_IDX(ph, RVR_POOL_HOLDINGS, "wp")] = (uint16_t)w;
                 }
@@ -112,14 +97,14 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
             for (int j = 0; j < RVR_PER_LANE; ++j) {
                 const uint32_t h = tid + (uint32_t)j * RVR_BLOCK;
                 uint32_t ca = 0, cb = 1;
-                if (h < (uint32_t)RVR_HOLDINGS) hist_unpair(h, ca, cb);
+                if (h < (uint32_t)RVR_HOLDINGS) unpair(h, ca, cb);
                 hvalid[j] = h < (uint32_t)RVR_HOLDINGS && ((avail >> ca) & (avail >> cb) & 1ull);
                 ha[j] = (uint32_t)__popcll(avail & ((1ull << ca) - 1ull));
                 hb[j] = (uint32_t)__popcll(avail & ((1ull << cb) - 1ull));
-                hph[j] = hvalid[j] ? hist_tri(hb[j]) + ha[j] : 0u;
+                hph[j] = hvalid[j] ? tri(hb[j]) + ha[j] : 0u;
             }
             // ---- the completions: {ci < cj} in pair order (k = 2), {c} (k = 1), {} (k = 0)
-            const uint32_t ncomp = hist_binom2(P, k);
+            const uint32_t ncomp = binom2(P, k);
             uint32_t ci = 0, cj = 1;
             for (uint32_t c = 0; c < ncomp; ++c) {
                 const uint32_t x0 = k == 2u ? ci : (k == 1u ? c : HIST_NONE), x1 = k == 2u ? cj : HIST_NONE;
@@ -131,7 +116,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
                     if (ph < nh) {
                         const bool gone = ea[j] == x0 || ea[j] == x1 || eb[j] == x0 || eb[j] == x1;
                         uint32_t key = HIST_SENT;
-                        if (!gone) key = hist_key(eval7_tab_back(eval7_tab_front_bits(board | ebits[j], T), T));
+                        if (!gone) key = order_key(eval7_tab_back(eval7_tab_front_bits(board | ebits[j], T), T));
                         keyw[PK_IDX(ph, RVR_POOL_HOLDINGS, "keyw")] = key;
                         slot[PK_IDX(ph, RVR_SLOTS, "slot")] = gone ? ~0ull : (((uint64_t)key << 11) | ph);
                     }
@@ -198,11 +183,11 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
                     const uint32_t wh = wp[PK_IDX(hph[j], RVR_POOL_HOLDINGS, "wp")];
                     equal -= wh;
                     den -= wh;
-                    const uint32_t ta = hist_tri(ha[j]), tb = hist_tri(hb[j]);
+                    const uint32_t ta = tri(ha[j]), tb = tri(hb[j]);
                     for (uint32_t x = 0; x < P; ++x) {
                         if (x == ha[j] || x == hb[j]) continue;
-                        const uint32_t tx = hist_tri(x);
-                        const uint32_t p0 = PK_IDX(hist_pair(ha[j], ta, x, tx), RVR_POOL_HOLDINGS, "pair"), p1 = PK_IDX(hist_pair(hb[j], tb, x, tx), RVR_POOL_HOLDINGS, "pair");
+                        const uint32_t tx = tri(x);
+                        const uint32_t p0 = PK_IDX(pair(ha[j], ta, x, tx), RVR_POOL_HOLDINGS, "pair"), p1 = PK_IDX(pair(hb[j], tb, x, tx), RVR_POOL_HOLDINGS, "pair");
                         const uint32_t k0 = keyw[p0], k1 = keyw[p1], w0 = wp[p0], w1 = wp[p1];   // (p0, p1: checked above)
                         below -= (k0 < kh ? w0 : 0u) + (k1 < kh ? w1 : 0u);
                         equal -= (k0 == kh ? w0 : 0u) + (k1 == kh ? w1 : 0u);

@@ -18,6 +18,7 @@
 // Ordinary vector stores and LDS atomics only; no scratch memory (tests/test_equity_range_host.py reads the code objects).
 #include <hip/hip_runtime.h>
 
+#include "pk_equity_common.hpp"
 #include "pk_equity_range.hpp"
 
 using namespace pk;
@@ -34,8 +35,6 @@ struct EqrPrepArgs {
     size_t m;
 };
 
-// C(n, k), 0 <= k <= 2
-__device__ __forceinline__ uint32_t eqr_binom2(uint32_t n, uint32_t k) { return k == 0 ? 1u : (k == 1 ? n : n * (n - 1u) / 2u); }
 
 template <bool TABLE>
 __global__ void __launch_bounds__(EQR_PREP_BLOCK) k_eqr_prep(EqrPrepArgs a) {
@@ -86,7 +85,7 @@ __global__ void __launch_bounds__(EQR_PREP_BLOCK) k_eqr_prep(EqrPrepArgs a) {
     }
     const uint32_t P = 52u - (uint32_t)__popcll(dead), k = (uint32_t)(5 - nb);
     if (counted && P < k + 2u) status |= PK_EQ_SMALL_POOL;
-    const uint32_t boards = status ? 0u : eqr_binom2(P - 2u, k);
+    const uint32_t boards = status ? 0u : binom2(P - 2u, k);
     d[0] = known;
     d[1] = hero;
     d[2] = ~dead & 0x000FFFFFFFFFFFFFull;
@@ -95,29 +94,6 @@ __global__ void __launch_bounds__(EQR_PREP_BLOCK) k_eqr_prep(EqrPrepArgs a) {
     if (a.out.status) a.out.status[i] = (uint8_t)status;
 }
 
-__device__ __forceinline__ uint32_t eqr_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t eqr_uniform(uint64_t x) { return (uint64_t)eqr_uniform((uint32_t)x) | ((uint64_t)eqr_uniform((uint32_t)(x >> 32)) << 32); }
-__device__ __forceinline__ uint64_t eqr_wave_sum(uint64_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-__device__ __forceinline__ uint32_t eqr_tri(uint32_t n) { return n * (n - 1u) / 2u; }   // (n = 0: 0 * 0xffffffff = 0)
-// t = b (b - 1) / 2 + a with a < b (a holding index, a completion's pair index) -> (a, b); t < 2^20
-__device__ __forceinline__ void eqr_unpair(uint32_t t, uint32_t &a, uint32_t &b) {
-    b = (uint32_t)((1.0f + sqrtf(1.0f + 8.0f * (float)t)) * 0.5f);
-    b = b < 1u ? 1u : b;
-    while (eqr_tri(b) > t) --b;
-    while (eqr_tri(b + 1u) <= t) ++b;
-    a = t - eqr_tri(b);
-}
-// C(n, J) for the unranking, J a compile-time 1 .. 3 (n <= 46); 0 where n < J
-template <int J>
-__device__ __forceinline__ uint32_t eqr_binom_c(uint32_t n) {
-    if constexpr (J == 1) return n;
-    else if constexpr (J == 2) return n * (n - 1u) / 2u;
-    else return n < 3u ? 0u : n * (n - 1u) * (n - 2u) / 6u;
-}
 
 // registers per lane: six waves per SIMD (three 512-thread workgroups per CU, what the group segment allows) caps a lane at 80 registers; the kernel uses 72, no spill
 __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, EqrWeights wts, EqrOut out,
@@ -130,11 +106,11 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
     __shared__ uint64_t red[EQR_WAVES][3];
     for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQR_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
     for (int h = threadIdx.x; h < EQR_HOLDINGS; h += EQR_BLOCK) { cwin[PK_IDX(h, EQR_HOLDINGS, "cwin")] = 0; ctie[PK_IDX(h, EQR_HOLDINGS, "ctie")] = 0; }
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = eqr_uniform(tid >> 6);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
     for (uint32_t spot = blockIdx.x; spot < m; spot += gridDim.x) {
         __syncthreads();                          // (the table and the cleared counters; the spot before: its pool, hero words and sums are done with)
         const uint64_t *d = desc + (size_t)spot * EQR_DESC_WORDS;
-        const uint64_t known = eqr_uniform(d[0]), hero = eqr_uniform(d[1]), avail = eqr_uniform(d[2]), meta = eqr_uniform(d[3]);
+        const uint64_t known = uniform(d[0]), hero = uniform(d[1]), avail = uniform(d[2]), meta = uniform(d[3]);
         const uint32_t boards = (uint32_t)meta, k = (uint32_t)(meta >> 48) & 0xffu, P = (uint32_t)(meta >> 56);
         if (boards) {                             // (a refused spot: its counters stay zero)
             if (tid < 52u && ((avail >> tid) & 1ull)) {
@@ -145,17 +121,17 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
             if (tid == EQR_FROZEN) { pool[EQR_FROZEN] = 0; canon[EQR_FROZEN] = 0; }
             __syncthreads();
             // ---- hero pass: completion {i < j} at j (j - 1) / 2 + i, {i} at i, {} at 0
-            const uint32_t ncomp = eqr_binom2(P, k);
+            const uint32_t ncomp = binom2(P, k);
             for (uint32_t c = tid; c < ncomp; c += EQR_BLOCK) {
                 uint64_t bits = known | hero;
-                if (k == 2u) { uint32_t ci, cj; eqr_unpair(c, ci, cj); bits |= pool[PK_IDX(ci, 64, "pool") & 63u] | pool[PK_IDX(cj, 64, "pool") & 63u]; }
+                if (k == 2u) { uint32_t ci, cj; unpair(c, ci, cj); bits |= pool[PK_IDX(ci, 64, "pool") & 63u] | pool[PK_IDX(cj, 64, "pool") & 63u]; }
                 else if (k == 1u) bits |= pool[PK_IDX(c, 64, "pool") & 63u];
                 hero_w[PK_IDX(c, EQR_COMPLETIONS, "hero_w")] = eval7_tab_back(eval7_tab_front_bits(bits, T), T);
             }
             __syncthreads();
             // ---- villain pass: the sets S of s = k + 2 pool cards, lexicographic; this lane's [s0, s0 + cnt)
             const uint32_t s = k + 2u;
-            const uint32_t nsets = s == 2u ? eqr_binom_c<2>(P) : (s == 3u ? eqr_binom_c<3>(P) : (uint32_t)((uint64_t)eqr_binom_c<3>(P) * (P - 3u) / 4u));
+            const uint32_t nsets = s == 2u ? binom_c<2>(P) : (s == 3u ? binom_c<3>(P) : (uint32_t)((uint64_t)binom_c<3>(P) * (P - 3u) / 4u));
             const uint32_t per = (nsets + EQR_BLOCK - 1u) / EQR_BLOCK, s0 = tid * per;
             const uint32_t cnt = s0 < nsets ? min(per, nsets - s0) : 0u;
             // combination levels 0 .. 3 (ascending pool indices c0 < c1 < c2 < j), the first f = 4 - s of them frozen on the empty slot;
@@ -168,7 +144,7 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
                 auto level = [&](auto jc) {
                     constexpr int J = decltype(jc)::value;
                     while (x < P) {
-                        const uint32_t c = eqr_binom_c<J>(P - 1u - x);
+                        const uint32_t c = binom_c<J>(P - 1u - x);
                         if (r < c) break;
                         r -= c; ++x;
                     }
@@ -187,11 +163,11 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
                 // one split: levels x < y are the villain's hole cards (canonical nx < ny), levels u < v the board to come
                 auto split = [&](int x, uint32_t nx, uint32_t ny, uint32_t lu, uint32_t lv) {
                     if (x < f) return;                                                   // (uniform: a level that does not exist)
-                    const uint32_t comp = k == 2u ? eqr_tri(lv) + lu : (k == 1u ? lv : 0u);
+                    const uint32_t comp = k == 2u ? tri(lv) + lu : (k == 1u ? lv : 0u);
                     const uint32_t v[2] = {hero_w[PK_IDX(comp, EQR_COMPLETIONS, "hero_w")], vil};
                     int nw;
                     const uint32_t win = compare_rankings<2>(v, nw);
-                    const uint32_t h = PK_IDX(eqr_tri(ny) + nx, EQR_HOLDINGS, "holding");
+                    const uint32_t h = PK_IDX(tri(ny) + nx, EQR_HOLDINGS, "holding");
                     if (win == 1u) atomicAdd(&cwin[h], 1u);
                     else if (win == 3u) atomicAdd(&ctie[h], 1u);
                 };
@@ -226,13 +202,13 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
             if (out.agg) {
                 const uint64_t wt = wv ? (uint64_t)wv[h] : 1ull;
                 uint32_t ca, cb;
-                eqr_unpair(h, ca, cb);
+                unpair(h, ca, cb);
                 const bool valid = boards && ((avail >> ca) & (avail >> cb) & 1ull);
                 a0 += wt * w; a1 += wt * t; a2 += valid ? wt : 0ull;
             }
         }
         if (out.agg) {
-            a0 = eqr_wave_sum(a0); a1 = eqr_wave_sum(a1); a2 = eqr_wave_sum(a2);
+            a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
             if (lane == 0) { red[PK_IDX(wave, EQR_WAVES, "red")][0] = a0; red[wave][1] = a1; red[wave][2] = a2; }
             __syncthreads();
             if (tid == 0) {

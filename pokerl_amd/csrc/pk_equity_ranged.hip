@@ -13,6 +13,7 @@
 // -DPK_EQW_CLASS=0 | 8 | 16: an object file with the sampling kernels of ONE size class (class 0 carries the shared kernels and eqw_launch).
 #include <hip/hip_runtime.h>
 
+#include "pk_equity_common.hpp"
 #include "pk_equity_ranged.hpp"
 
 using namespace pk;
@@ -151,35 +152,6 @@ __global__ void __launch_bounds__(EQW_PREP_BLOCK) k_eqw_prep(EqwPrepArgs a) {
 }
 #endif  // EQW_SHARED_PART
 
-__device__ __forceinline__ uint32_t eqw_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t eqw_uniform(uint64_t x) { return (uint64_t)eqw_uniform((uint32_t)x) | ((uint64_t)eqw_uniform((uint32_t)(x >> 32)) << 32); }
-__device__ __forceinline__ uint32_t eqw_wave_sum(uint32_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-__device__ __forceinline__ uint64_t eqw_wave_sum(uint64_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-// Index of the c-th (0-based) set bit of m, c < popcount(m): k_eqs's popcount bisection, 32 -> 1 bits.  Registers only.
-__device__ __forceinline__ uint32_t eqw_select(uint64_t m, uint32_t c) {
-    const uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
-    uint32_t p = (uint32_t)__popc(lo);
-    bool up = c >= p;
-    uint32_t w = up ? hi : lo, base = up ? 32u : 0u;
-    c -= up ? p : 0u;
-#pragma unroll
-    for (uint32_t sh = 16; sh >= 1; sh >>= 1) {
-        p = (uint32_t)__popc(w & ((1u << sh) - 1u));
-        up = c >= p;
-        c -= up ? p : 0u;
-        w = up ? w >> sh : w;
-        base += up ? sh : 0u;
-    }
-    return base;
-}
 // The number of h with row[h] <= u over a non-decreasing row of 1326 sums: 11 dependent LDS reads, no branch.  u < row[1325]: the result <= 1325.
 __device__ __forceinline__ uint32_t eqw_search(const uint32_t *row, uint32_t u) {
     uint32_t pos = 0;
@@ -219,19 +191,19 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqw_min_waves<N>()) k_eqw(const uint
     }
     if (threadIdx.x < 32) wt[PK_IDX(threadIdx.x, 32, "wt")] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
     __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = eqw_uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
+    const uint32_t lane = threadIdx.x & 63u, wave = uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
     const uint32_t S = rng.samples;
     // every task costs about the same, so the tasks are dealt round robin: no counter
     for (uint32_t t = blockIdx.x * EQ_WAVES + wave; t < ntasks; t += nwaves) {
         const uint32_t spot = t / nch, chunk = t - spot * nch;
         const uint64_t *d = desc + (size_t)spot * eqw_desc_words(N);
-        const uint64_t m3 = eqw_uniform(d[3]);
+        const uint64_t m3 = uniform(d[3]);
         if (!(m3 >> 32)) continue;                                   // a refused spot: no attempts
-        const uint64_t known = eqw_uniform(d[0]), avail = eqw_uniform(d[1]), meta = eqw_uniform(d[2]);
+        const uint64_t known = uniform(d[0]), avail = uniform(d[1]), meta = uniform(d[2]);
         uint64_t rw[(N + 3) / 4];
-        PK_FOR(q, (N + 3) / 4) rw[q] = eqw_uniform(d[4 + q]); PK_END
+        PK_FOR(q, (N + 3) / 4) rw[q] = uniform(d[4 + q]); PK_END
         uint64_t hole[N];
-        PK_FOR(p, N) hole[p] = eqw_uniform(d[8 + p]); PK_END
+        PK_FOR(p, N) hole[p] = uniform(d[8 + p]); PK_END
         const uint32_t hid = (uint32_t)meta & 0xffffu, mhi = (uint32_t)(meta >> 32), live = mhi & 0xffffu, k = (mhi >> 16) & 0xffu, P = mhi >> 24;
         const uint32_t id = (uint32_t)m3, H = (uint32_t)__builtin_popcount(hid), Pb = P - 2u * H;
         // per hidden seat: the row's first word in CUM (EQW_UNIFORM: none) and its total T_j; a range with no weight left accepts nothing
@@ -243,7 +215,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqw_min_waves<N>()) k_eqw(const uint
                 const uint32_t row = (uint32_t)(rw[p / 4] >> (16 * (p % 4))) & 0xffffu;
                 tot[p] = (uint32_t)EQW_HOLDINGS;
                 if constexpr (RC > 0) {
-                    if (row != EQW_UNIFORM) tot[p] = eqw_uniform(CUM[PK_IDX(row * (uint32_t)EQW_HOLDINGS + (uint32_t)EQW_HOLDINGS - 1u, CUM_WORDS, "CUM total")]);
+                    if (row != EQW_UNIFORM) tot[p] = uniform(CUM[PK_IDX(row * (uint32_t)EQW_HOLDINGS + (uint32_t)EQW_HOLDINGS - 1u, CUM_WORDS, "CUM total")]);
                 }
                 none = none || tot[p] == 0u;
             }
@@ -295,7 +267,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqw_min_waves<N>()) k_eqw(const uint
                             const uint32_t left = Pb - (uint32_t)j;
                             const uint64_t a = (uint64_t)xlo * left, b = (uint64_t)xhi * left + (a >> 32);
                             xlo = (uint32_t)a; xhi = (uint32_t)b;
-                            const uint32_t c = eqw_select(rem, (uint32_t)(b >> 32));
+                            const uint32_t c = select(rem, (uint32_t)(b >> 32));
                             rem &= ~(1ull << c);
                             bits |= eqw_card_bit(c);
                         }
@@ -326,8 +298,8 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqw_min_waves<N>()) k_eqw(const uint
         // per seat: the wavefront's sums, then one atomic per output from lane 0; one more for the accepted attempts
         PK_FOR(p, N)
             if ((live >> p) & 1u) {
-                const uint32_t ws = eqw_wave_sum(sole[p]), wi = eqw_wave_sum(inw[p]);
-                const uint64_t wsh = eqw_wave_sum((uint64_t)sh[p]);
+                const uint32_t ws = wave_sum(sole[p]), wi = wave_sum(inw[p]);
+                const uint64_t wsh = wave_sum((uint64_t)sh[p]);
                 if (lane == 0) {
                     const size_t o = (size_t)spot * N + p;
                     if (out.win && ws) atomicAdd(&out.win[o], ws);
@@ -336,7 +308,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqw_min_waves<N>()) k_eqw(const uint
                 }
             }
         PK_END
-        const uint32_t wacc = eqw_wave_sum(acc);
+        const uint32_t wacc = wave_sum(acc);
         if (lane == 0 && out.accepted && wacc) atomicAdd(&out.accepted[spot], wacc);
     }
 }

@@ -18,6 +18,7 @@
 // Ordinary vector stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_rvr_host.py reads the code objects).
 #include <hip/hip_runtime.h>
 
+#include "pk_equity_common.hpp"
 #include "pk_equity_rvr.hpp"
 
 using namespace pk;
@@ -34,8 +35,6 @@ struct RvrPrepArgs {
     size_t m;
 };
 
-// C(n, k), 0 <= k <= 2
-__device__ __forceinline__ uint32_t rvr_binom2(uint32_t n, uint32_t k) { return k == 0 ? 1u : (k == 1 ? n : n * (n - 1u) / 2u); }
 
 template <bool TABLE>
 __global__ void __launch_bounds__(RVR_PREP_BLOCK) k_rvr_prep(RvrPrepArgs a) {
@@ -78,7 +77,7 @@ __global__ void __launch_bounds__(RVR_PREP_BLOCK) k_rvr_prep(RvrPrepArgs a) {
     }
     const uint32_t P = 52u - (uint32_t)__popcll(dead), k = (uint32_t)(5 - nb);
     if (counted && P < k + 4u) status |= PK_EQ_SMALL_POOL;                      // the board to come and TWO holdings
-    const uint32_t boards = status ? 0u : rvr_binom2(P - 4u, k);
+    const uint32_t boards = status ? 0u : binom2(P - 4u, k);
     d[0] = known;
     d[1] = ~dead & 0x000FFFFFFFFFFFFFull;
     d[2] = (uint64_t)boards | ((uint64_t)k << 48) | ((uint64_t)P << 56);
@@ -86,22 +85,6 @@ __global__ void __launch_bounds__(RVR_PREP_BLOCK) k_rvr_prep(RvrPrepArgs a) {
     if (a.out.status) a.out.status[i] = (uint8_t)status;
 }
 
-__device__ __forceinline__ uint32_t rvr_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t rvr_uniform(uint64_t x) { return (uint64_t)rvr_uniform((uint32_t)x) | ((uint64_t)rvr_uniform((uint32_t)(x >> 32)) << 32); }
-__device__ __forceinline__ uint32_t rvr_tri(uint32_t n) { return n * (n - 1u) / 2u; }   // (n = 0: 0 * 0xffffffff = 0)
-// t = b (b - 1) / 2 + a with a < b -> (a, b); t < 2^20
-__device__ __forceinline__ void rvr_unpair(uint32_t t, uint32_t &a, uint32_t &b) {
-    b = (uint32_t)((1.0f + sqrtf(1.0f + 8.0f * (float)t)) * 0.5f);
-    b = b < 1u ? 1u : b;
-    while (rvr_tri(b) > t) --b;
-    while (rvr_tri(b + 1u) <= t) ++b;
-    a = t - rvr_tri(b);
-}
-// the index of the pair {a, x}, a != x
-__device__ __forceinline__ uint32_t rvr_pair(uint32_t a, uint32_t tri_a, uint32_t x, uint32_t tri_x) { return x < a ? tri_a + x : tri_x + a; }
-// The two-seat order: compare_rankings<2> on ranking words rank << 20 | kickers lets the lower rank number win, then the
-// larger kickers value, and ties equal words.  So the hero beats exactly the words whose key is SMALLER, and ties exactly the equal key.
-__device__ __forceinline__ uint32_t rvr_key(uint32_t word) { return ((15u - (word >> 20)) << 20) | (word & 0xFFFFFu); }
 
 // registers per lane: four waves per SIMD (two 512-thread workgroups per CU, what the group segment allows) cap a lane at 128 registers
 __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, RvrWeights wts, RvrOut out,
@@ -115,11 +98,11 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
     __shared__ uint32_t canon[64];                    // ... and its canonical index
     __shared__ uint32_t wsum[RVR_WAVES];
     for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += RVR_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = rvr_uniform(tid >> 6);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
     for (uint32_t spot = blockIdx.x; spot < m; spot += gridDim.x) {
         __syncthreads();                              // (the table; the spot before: its pool, weights, keys and sums are done with)
         const uint64_t *d = desc + (size_t)spot * RVR_DESC_WORDS;
-        const uint64_t known = rvr_uniform(d[0]), avail = rvr_uniform(d[1]), meta = rvr_uniform(d[2]);
+        const uint64_t known = uniform(d[0]), avail = uniform(d[1]), meta = uniform(d[2]);
         const uint32_t boards = (uint32_t)meta, k = (uint32_t)(meta >> 48) & 0xffu, P = (uint32_t)(meta >> 56);
         uint64_t win[RVR_PER_LANE], tie[RVR_PER_LANE], tot[RVR_PER_LANE];
 #pragma unroll
@@ -132,7 +115,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
             }
             if (tid == RVR_NONE) { pool[RVR_NONE] = 0; canon[RVR_NONE] = 0; }
             __syncthreads();
-            const uint32_t nh = rvr_tri(P), nreal = rvr_tri(P - k);   // pool holdings; those a completion leaves in play
+            const uint32_t nh = tri(P), nreal = tri(P - k);   // pool holdings; those a completion leaves in play
             uint32_t npad = 64;
             while (npad < nh) npad <<= 1;                             // (> nh: C(P, 2) is no power of two for P >= 3, so a pad slot always exists)
             // ---- per spot: the pool holdings this lane ranks (ea < eb pool slots), the weights by pool holding, the pad slots
@@ -144,9 +127,9 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
                 const uint32_t ph = tid + (uint32_t)j * RVR_BLOCK;
                 ea[j] = RVR_NONE; eb[j] = RVR_NONE; ebits[j] = 0;
                 if (ph < nh) {
-                    rvr_unpair(ph, ea[j], eb[j]);
+                    unpair(ph, ea[j], eb[j]);
                     ebits[j] = pool[PK_IDX(ea[j], 64, "pool")] | pool[PK_IDX(eb[j], 64, "pool")];
-                    const uint32_t gh = rvr_tri(canon[PK_IDX(eb[j], 64, "canon")]) + canon[PK_IDX(ea[j], 64, "canon")];
+                    const uint32_t gh = tri(canon[PK_IDX(eb[j], 64, "canon")]) + canon[PK_IDX(ea[j], 64, "canon")];
                     const uint32_t w = wv ? (uint32_t)wv[PK_IDX(gh, RVR_HOLDINGS, "weights")] : 1u;
                     wp[PK_IDX(ph, RVR_POOL_HOLDINGS, "wp")] = (uint16_t)w;
                     wmine += w;
@@ -163,11 +146,11 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
             for (int j = 0; j < RVR_PER_LANE; ++j) {
                 const uint32_t h = tid + (uint32_t)j * RVR_BLOCK;
                 uint32_t ca = 0, cb = 1;
-                if (h < (uint32_t)RVR_HOLDINGS) rvr_unpair(h, ca, cb);
+                if (h < (uint32_t)RVR_HOLDINGS) unpair(h, ca, cb);
                 hvalid[j] = h < (uint32_t)RVR_HOLDINGS && ((avail >> ca) & (avail >> cb) & 1ull);
                 ha[j] = (uint32_t)__popcll(avail & ((1ull << ca) - 1ull));
                 hb[j] = (uint32_t)__popcll(avail & ((1ull << cb) - 1ull));
-                hph[j] = hvalid[j] ? rvr_tri(hb[j]) + ha[j] : 0u;
+                hph[j] = hvalid[j] ? tri(hb[j]) + ha[j] : 0u;
             }
             __syncthreads();
             uint32_t wall = 0;
@@ -178,17 +161,17 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
             for (int j = 0; j < RVR_PER_LANE; ++j) {
                 if (!hvalid[j]) continue;
                 uint32_t conf = wp[PK_IDX(hph[j], RVR_POOL_HOLDINGS, "wp")];
-                const uint32_t ta = rvr_tri(ha[j]), tb = rvr_tri(hb[j]);
+                const uint32_t ta = tri(ha[j]), tb = tri(hb[j]);
                 for (uint32_t x = 0; x < P; ++x) {
                     if (x == ha[j] || x == hb[j]) continue;
-                    const uint32_t tx = rvr_tri(x);
-                    conf += (uint32_t)wp[PK_IDX(rvr_pair(ha[j], ta, x, tx), RVR_POOL_HOLDINGS, "wp")] +
-                            (uint32_t)wp[PK_IDX(rvr_pair(hb[j], tb, x, tx), RVR_POOL_HOLDINGS, "wp")];
+                    const uint32_t tx = tri(x);
+                    conf += (uint32_t)wp[PK_IDX(pair(ha[j], ta, x, tx), RVR_POOL_HOLDINGS, "wp")] +
+                            (uint32_t)wp[PK_IDX(pair(hb[j], tb, x, tx), RVR_POOL_HOLDINGS, "wp")];
                 }
                 tot[j] = (uint64_t)boards * (uint64_t)(wall - conf);
             }
             // ---- the completions: {ci < cj} in pair order (k = 2), {c} (k = 1), {} (k = 0)
-            const uint32_t ncomp = rvr_binom2(P, k);
+            const uint32_t ncomp = binom2(P, k);
             uint32_t ci = 0, cj = 1;
             for (uint32_t c = 0; c < ncomp; ++c) {
                 const uint32_t x0 = k == 2u ? ci : (k == 1u ? c : RVR_NONE), x1 = k == 2u ? cj : RVR_NONE;
@@ -200,7 +183,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
                     if (ph < nh) {
                         const bool gone = ea[j] == x0 || ea[j] == x1 || eb[j] == x0 || eb[j] == x1;
                         uint32_t key = RVR_SENT;
-                        if (!gone) key = rvr_key(eval7_tab_back(eval7_tab_front_bits(board | ebits[j], T), T));
+                        if (!gone) key = order_key(eval7_tab_back(eval7_tab_front_bits(board | ebits[j], T), T));
                         keyw[PK_IDX(ph, RVR_POOL_HOLDINGS, "keyw")] = key;
                         slot[PK_IDX(ph, RVR_SLOTS, "slot")] = gone ? ~0ull : (((uint64_t)key << 11) | ph);
                     }
@@ -261,11 +244,11 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
                     uint32_t below = below0, equal = pre[PK_IDX(ub, RVR_PREFIX, "pre")] - below0;
                     // card removal: h itself, and every holding {ha, x}, {hb, x}
                     equal -= wp[PK_IDX(hph[j], RVR_POOL_HOLDINGS, "wp")];
-                    const uint32_t ta = rvr_tri(ha[j]), tb = rvr_tri(hb[j]);
+                    const uint32_t ta = tri(ha[j]), tb = tri(hb[j]);
                     for (uint32_t x = 0; x < P; ++x) {
                         if (x == ha[j] || x == hb[j]) continue;
-                        const uint32_t tx = rvr_tri(x);
-                        const uint32_t p0 = PK_IDX(rvr_pair(ha[j], ta, x, tx), RVR_POOL_HOLDINGS, "pair"), p1 = PK_IDX(rvr_pair(hb[j], tb, x, tx), RVR_POOL_HOLDINGS, "pair");
+                        const uint32_t tx = tri(x);
+                        const uint32_t p0 = PK_IDX(pair(ha[j], ta, x, tx), RVR_POOL_HOLDINGS, "pair"), p1 = PK_IDX(pair(hb[j], tb, x, tx), RVR_POOL_HOLDINGS, "pair");
                         const uint32_t k0 = keyw[p0], k1 = keyw[p1], w0 = wp[p0], w1 = wp[p1];   // (p0, p1: checked above)
                         below -= (k0 < kh ? w0 : 0u) + (k1 < kh ? w1 : 0u);
                         equal -= (k0 == kh ? w0 : 0u) + (k1 == kh ? w1 : 0u);

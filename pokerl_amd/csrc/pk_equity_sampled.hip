@@ -11,6 +11,7 @@
 // Ordinary vector stores and atomics only; no scratch memory (tests/test_equity_sampled_host.py reads the code objects).
 #include <hip/hip_runtime.h>
 
+#include "pk_equity_common.hpp"
 #include "pk_equity_sampled.hpp"
 
 using namespace pk;
@@ -105,35 +106,6 @@ __global__ void __launch_bounds__(EQS_PREP_BLOCK) k_eqs_prep(EqsPrepArgs a) {
     if (a.out.status) a.out.status[i] = (uint8_t)status;
 }
 
-__device__ __forceinline__ uint32_t eqs_uniform(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t eqs_uniform(uint64_t x) { return (uint64_t)eqs_uniform((uint32_t)x) | ((uint64_t)eqs_uniform((uint32_t)(x >> 32)) << 32); }
-__device__ __forceinline__ uint32_t eqs_wave_sum(uint32_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-__device__ __forceinline__ uint64_t eqs_wave_sum(uint64_t x) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-// Index of the c-th (0-based) set bit of m, c < popcount(m): popcount bisection, 32 -> 1 bits.  Registers only.
-__device__ __forceinline__ uint32_t eqs_select(uint64_t m, uint32_t c) {
-    const uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
-    uint32_t p = (uint32_t)__popc(lo);
-    bool up = c >= p;
-    uint32_t w = up ? hi : lo, base = up ? 32u : 0u;
-    c -= up ? p : 0u;
-#pragma unroll
-    for (uint32_t sh = 16; sh >= 1; sh >>= 1) {
-        p = (uint32_t)__popc(w & ((1u << sh) - 1u));
-        up = c >= p;
-        c -= up ? p : 0u;
-        w = up ? w >> sh : w;
-        base += up ? sh : 0u;
-    }
-    return base;
-}
 
 // registers per lane: the caps of k_equity<N> (eight waves per SIMD up to three seats, four up to eight, two beyond) -- no spill at any seat count
 template <int N> constexpr int eqs_min_waves() { return N <= 3 ? 8 : (N <= 8 ? 4 : 2); }
@@ -146,17 +118,17 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqs_min_waves<N>()) k_eqs(const uint
     for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQ_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
     if (threadIdx.x < 32) wt[PK_IDX(threadIdx.x, 32, "wt")] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
     __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = eqs_uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
+    const uint32_t lane = threadIdx.x & 63u, wave = uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
     const uint32_t S = rng.samples;
     // every task costs the same, so the tasks are dealt round robin: no counter
     for (uint32_t t = blockIdx.x * EQ_WAVES + wave; t < ntasks; t += nwaves) {
         const uint32_t spot = t / nch, chunk = t - spot * nch;
         const uint64_t *d = desc + (size_t)spot * eqs_desc_words(N);
-        const uint64_t m3 = eqs_uniform(d[3]);
+        const uint64_t m3 = uniform(d[3]);
         if (!(m3 >> 32)) continue;                                   // a refused spot: no samples
-        const uint64_t known = eqs_uniform(d[0]), avail = eqs_uniform(d[1]), meta = eqs_uniform(d[2]);
+        const uint64_t known = uniform(d[0]), avail = uniform(d[1]), meta = uniform(d[2]);
         uint64_t hole[N];
-        PK_FOR(p, N) hole[p] = eqs_uniform(d[4 + p]); PK_END
+        PK_FOR(p, N) hole[p] = uniform(d[4 + p]); PK_END
         const uint32_t hidden = (uint32_t)meta, mhi = (uint32_t)(meta >> 32), live = mhi & 0xffffu, k = (mhi >> 16) & 0xffu, P = mhi >> 24;
         const uint32_t id = (uint32_t)m3, D = k + (uint32_t)__builtin_popcount(hidden);
         // this task's samples [start, end) of the spot's, and this lane's [s, s + cnt) of those
@@ -192,7 +164,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqs_min_waves<N>()) k_eqs(const uint
                 const uint32_t left = P - i;                                       // chained multiply-high: c = (x * left) >> 64, x = the low 64 bits
                 const uint64_t a = (uint64_t)xlo * left, b = (uint64_t)xhi * left + (a >> 32);
                 xlo = (uint32_t)a; xhi = (uint32_t)b;
-                const uint32_t c = eqs_select(rem, (uint32_t)(b >> 32));
+                const uint32_t c = select(rem, (uint32_t)(b >> 32));
                 rem &= ~(1ull << c);
                 return 4ull << (((c & 3u) << 4) | (c >> 2));
             };
@@ -224,8 +196,8 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqs_min_waves<N>()) k_eqs(const uint
         // per seat: the wavefront's sums, then one atomic per output from lane 0
         PK_FOR(p, N)
             if ((live >> p) & 1u) {
-                const uint32_t ws = eqs_wave_sum(sole[p]), wi = eqs_wave_sum(inw[p]);
-                const uint64_t wsh = eqs_wave_sum((uint64_t)sh[p]);
+                const uint32_t ws = wave_sum(sole[p]), wi = wave_sum(inw[p]);
+                const uint64_t wsh = wave_sum((uint64_t)sh[p]);
                 if (lane == 0) {
                     const size_t o = (size_t)spot * N + p;
                     if (out.win && ws) atomicAdd(&out.win[o], ws);

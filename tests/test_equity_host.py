@@ -118,6 +118,21 @@ def test_null_arguments_are_refused_without_a_device(lib):
     assert L.pk_equity_d(64, 2, 1, lib.ptr(one), lib.ptr(one), lib.ptr(one), lib.ptr(one), None, None, None, None, None, None) != lib.PK_OK
 
 
+def test_refusals_are_the_recorded_ones(lib):
+    """Every bad-argument call of the equity family (34 entry points) recorded in golden/equity_refusals.json, replayed: the return code and
+    the pk_last_error(NULL) text, both exactly.  All of them are refused before any device is looked at."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_equity_refusals as MR
+    with open(os.path.join(ROOT, "tests", "golden", "equity_refusals.json")) as f:
+        ref = json.load(f)
+    calls = [(c["fn"], c["args"]) for c in ref["calls"]]
+    assert calls == [tuple(c) for c in MR.cases()]                              # (the fixture is what the script would record today)
+    assert len({fn for fn, _ in calls}) == 34 and all(c["rc"] == lib.PK_E_INVALID_ARG for c in ref["calls"])
+    got = MR.run(lib, calls, ref["mark"])
+    for c, (rc, err) in zip(ref["calls"], got):
+        assert (rc, err) == (c["rc"], c["error"]), (c["fn"], c["args"])
+
+
 def test_python_helpers_validate_before_any_device_call(lib):
     from pokerl_amd import judger as J
     with pytest.raises(ValueError):

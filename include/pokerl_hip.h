@@ -758,6 +758,50 @@ int pk_table_equity_hist_d(pk_handle *h, const int32_t *tables_d, size_t m, cons
                            uint16_t *hist_d, uint16_t *void_d, uint32_t *completions_d, uint8_t *status_d);
 int pk_table_equity_hist(pk_handle *h, const int32_t *tables, size_t m, const uint16_t *weights, int weights_per_spot, int nbins, uint16_t *hist,
                          uint16_t *void_, uint32_t *completions, uint8_t *status);
+/* ---- Hero strength histogram: the strength histogram of ONE seat's holding, and optionally its bucket -- "which bucket is the hand of the
+ * seat to act in, on each of my tables?" (DESIGN.md section 3.9).  It is row h of "Strength histograms" above for the one holding that is
+ * wanted, at the cost of one "Range equity" spot.  POST-FLOP ONLY, as range equity.
+ *
+ * SPOT, WEIGHTS, STATUS, TABLE FORM, STREAMS: exactly those of "Range equity" above: hero u8[2], board u8[5] with nb = 3, 4 or 5 known cards,
+ * dead u64; dead cards = hero + board[0:nb] + `dead`, the pool is the other P cards in canonical order, k = 5 - nb; weights u16 [1326] shared
+ * or per spot (weights_per_spot), NULL = all 1; PK_EQ_PREFLOP for nb < 3 and PK_EQ_SMALL_POOL for P < k + 2, so the same spot gets the same
+ * status from pk_equity_range and from this family.
+ * NBINS: one per call, 1 .. PK_EQ_HIST_MAX_BINS; anything else is PK_E_INVALID_ARG before any launch.
+ * PER completion c of the board -- one of the C(P, k) sets of k cards from the pool: let V(c) be the valid holdings (both cards in the pool)
+ * that share no card with c.  On board + c every h' in V has winners = compare_rankings([eval_hand(board + c + hero),
+ * eval_hand(board + c + h')]) exactly as above, the hero at index 0, and
+ *   below = sum of w[h'] where the hero wins alone     equal = sum of w[h'] where both win     den = sum of w[h'] over V.
+ * If den = 0, void += 1; otherwise, in integers, bin = min(nbins - 1, floor(nbins * (2 below + equal) / (2 den))) and hist[bin] += 1: the
+ * rule of "Strength histograms" word for word; every product fits 32 bits by its bound, and below, equal, den <= 65 535 * 990 fit u32.
+ * OUTPUTS (any may be NULL; every entry is written, the caller clears nothing): hist u16 [m][nbins], void u16 [m], completions u32 [m] =
+ * C(P, k), status u8 [m].  A refused spot is all zeros.
+ * INVARIANT: sum over b of hist[b] + void = completions.
+ * IDENTITY: the outputs equal row h = holding index of the hero of pk_equity_hist on the same board, the same `dead` (WITHOUT the hero's
+ * cards) and the same weights; that form's completions = C(P' - 2, k) with P' = P + 2 is the same number, and its PK_EQ_SMALL_POOL rule
+ * P' < k + 4 the same inequality.
+ * BUCKET STAGE (optional, in the same call): K = 0 is none; else K 1 .. PK_CL_MAX_K and centroids u16 [K][nbins] give label u16 [m] and
+ * dist u32 [m], each exactly what pk_hist_cluster_assign returns for the m rows hist[m][nbins] of this call against those centroids (the
+ * quantised CDF, the L1 distance and the smallest-index rule of "Histogram clustering" below).  An empty row -- a refused spot, pre-flop, or
+ * every completion void -- gives PK_CL_NONE and distance 0.  label or dist may be asked for with hist NULL: the rows then live in the work
+ * space.  K > 0 with NULL centroids is PK_E_INVALID_ARG, and so is K = 0 with a non-NULL label or dist, and K outside 0 .. PK_CL_MAX_K.
+ * m == 0 is a no-op; m < 2^31; device < PK_MAX_DEVICES.  Asking for completions / status alone runs only the one-lane-per-spot kernels.
+ * TABLE FORM: as pk_table_equity_range: observer = a seat or PK_OBSERVER_ACTIVE (PK_OBSERVER_NONE is refused); spot = that seat's hole cards
+ * plus the board so far, dead = 0; reports PK_EQ_IN_FLIGHT, PK_EQ_BAD_TABLE, and PK_EQ_PREFLOP at turn 0; completes deferred rollout work,
+ * reads only, runs on the handle's stream.
+ * NOT HERE: pre-flop, the per-completion raw terms as an output, the bucket inside the step kernels' observation rows, multiway hidden hands. */
+int pk_equity_hist_hero_d(int device, size_t m, const uint8_t *hero_d /*[m][2]*/, const uint8_t *board_d /*[m][5]*/, const uint8_t *nboard_d,
+                          const uint64_t *dead_d /*NULL: none*/, const uint16_t *weights_d /*NULL: 1*/, int weights_per_spot, int nbins,
+                          uint16_t *hist_d /*[m][nbins]*/, uint16_t *void_d /*[m]*/, uint32_t *completions_d, uint8_t *status_d, int K /*0: no bucket*/,
+                          const uint16_t *centroids_d /*[K][nbins]*/, uint16_t *label_d /*[m]*/, uint32_t *dist_d /*[m]*/, void *stream);
+int pk_equity_hist_hero(int device, size_t m, const uint8_t *hero, const uint8_t *board, const uint8_t *nboard, const uint64_t *dead,
+                        const uint16_t *weights, int weights_per_spot, int nbins, uint16_t *hist, uint16_t *void_, uint32_t *completions,
+                        uint8_t *status, int K, const uint16_t *centroids, uint16_t *label, uint32_t *dist);
+int pk_table_equity_hist_hero_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, const uint16_t *weights_d, int weights_per_spot,
+                                int nbins, uint16_t *hist_d, uint16_t *void_d, uint32_t *completions_d, uint8_t *status_d, int K,
+                                const uint16_t *centroids_d, uint16_t *label_d, uint32_t *dist_d);
+int pk_table_equity_hist_hero(pk_handle *h, const int32_t *tables, size_t m, int observer, const uint16_t *weights, int weights_per_spot, int nbins,
+                              uint16_t *hist, uint16_t *void_, uint32_t *completions, uint8_t *status, int K, const uint16_t *centroids,
+                              uint16_t *label, uint32_t *dist);
 /* ---- Showdown EV: "if the cards still to come were dealt now, what does each seat expect to be paid, in chips?" -- the side pots of
  * Game.end_hand (game.py:494-531) enumerated over every board on the device, exact.  pk_equity above answers only the
  * first comparison of end_hand (who wins when every live seat is compared); with unequal stacks the pot is paid out in LEVELS, each judged

@@ -9,6 +9,7 @@ from .judger import (Equity, SampledEquity, compare_hands, compare_rankings, eva
 from .judger import HOLDINGS, RangeEquity, holding_index, range_equity, range_equity_batch, range_equity_d
 from .judger import RangeVsRange, range_vs_range, range_vs_range_batch, range_vs_range_d
 from .judger import StrengthHistogram, histogram_emd, strength_histogram, strength_histogram_batch, strength_histogram_d
+from .judger import HeroHistogram, hero_histogram, hero_histogram_batch, hero_histogram_d
 from .judger import (HistogramClusters, assign_histograms, assign_histograms_d, cluster_histograms, cluster_histograms_d,
                      seed_histogram_centroids, seed_histogram_centroids_d)
 from .judger import RangedEquity, ranged_equity, ranged_equity_batch, ranged_equity_d
@@ -27,6 +28,7 @@ __all__ = ['Game', 'PokerGameEnv', 'VecGame', 'VecPokerGameEnv', 'VecPokerGameEn
            'HOLDINGS', 'RangeEquity', 'holding_index', 'range_equity', 'range_equity_batch', 'range_equity_d',
            'RangeVsRange', 'range_vs_range', 'range_vs_range_batch', 'range_vs_range_d',
            'StrengthHistogram', 'histogram_emd', 'strength_histogram', 'strength_histogram_batch', 'strength_histogram_d',
+           'HeroHistogram', 'hero_histogram', 'hero_histogram_batch', 'hero_histogram_d',
            'HistogramClusters', 'cluster_histograms', 'assign_histograms', 'seed_histogram_centroids', 'cluster_histograms_d',
            'assign_histograms_d', 'seed_histogram_centroids_d',
            'RangedEquity', 'ranged_equity', 'ranged_equity_batch', 'ranged_equity_d',

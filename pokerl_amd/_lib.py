@@ -48,6 +48,7 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_equity_range_d", "pk_equity_range", "pk_table_equity_range_d", "pk_table_equity_range",
            "pk_equity_rvr_d", "pk_equity_rvr", "pk_table_equity_rvr_d", "pk_table_equity_rvr",
            "pk_equity_hist_d", "pk_equity_hist", "pk_table_equity_hist_d", "pk_table_equity_hist",
+           "pk_equity_hist_hero_d", "pk_equity_hist_hero", "pk_table_equity_hist_hero_d", "pk_table_equity_hist_hero",
            "pk_equity_ranged_d", "pk_equity_ranged", "pk_table_equity_ranged_d", "pk_table_equity_ranged",
            "pk_equity_ev_d", "pk_equity_ev", "pk_table_equity_ev_d", "pk_table_equity_ev",
            "pk_hist_cluster_seed_d", "pk_hist_cluster_assign_d", "pk_hist_cluster_d", "pk_hist_cluster_seed", "pk_hist_cluster_assign", "pk_hist_cluster"]
@@ -176,6 +177,10 @@ def lib():
     L.pk_equity_hist.argtypes = [C.c_int, C.c_size_t] + [_vp] * 4 + [C.c_int, C.c_int] + [_vp] * 4
     L.pk_table_equity_hist_d.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_int, C.c_int] + [_vp] * 4
     L.pk_table_equity_hist.argtypes = [_vp, _vp, C.c_size_t, _vp, C.c_int, C.c_int] + [_vp] * 4
+    L.pk_equity_hist_hero_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_int, C.c_int] + [_vp] * 4 + [C.c_int] + [_vp] * 4
+    L.pk_equity_hist_hero.argtypes = [C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_int, C.c_int] + [_vp] * 4 + [C.c_int] + [_vp] * 3
+    L.pk_table_equity_hist_hero_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 4 + [C.c_int] + [_vp] * 3
+    L.pk_table_equity_hist_hero.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int, C.c_int] + [_vp] * 4 + [C.c_int] + [_vp] * 3
     L.pk_hist_cluster_seed_d.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, C.c_uint64, C.c_uint32, _vp, _vp]
     L.pk_hist_cluster_seed.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, C.c_uint64, C.c_uint32, _vp]
     L.pk_hist_cluster_assign_d.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]

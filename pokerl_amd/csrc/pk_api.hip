@@ -22,6 +22,7 @@
 #include "pk_equity_range.hpp"
 #include "pk_equity_rvr.hpp"
 #include "pk_equity_hist.hpp"
+#include "pk_equity_hist_hero.hpp"
 #include "pk_hist_cluster.hpp"
 #include "pk_snapshot.hpp"
 
@@ -149,6 +150,16 @@ struct HistStagedOut {
         : hist(g.out(hist, m * RVR_HOLDINGS * (size_t)nbins * 2)), void_(g.out(void_, m * RVR_HOLDINGS * 2)), completions(g.out(completions, m * 4)),
           status(g.out(status, m)) {}
     HistOut at(const Stage &g) const { return HistOut{g.at<uint16_t>(hist), g.at<uint16_t>(void_), g.at<uint32_t>(completions), g.at<uint8_t>(status)}; }
+};
+// ... and a hero-histogram call, with the bucket stage's centroids, labels and distances
+struct HeroHistStaged {
+    int hist, void_, completions, status, centroids, label, dist, K;
+    HeroHistStaged(Stage &g, size_t m, int nbins, uint16_t *hist, uint16_t *void_, uint32_t *completions, uint8_t *status, int K, const uint16_t *centroids,
+                   uint16_t *label, uint32_t *dist)
+        : hist(g.out(hist, m * (size_t)nbins * 2)), void_(g.out(void_, m * 2)), completions(g.out(completions, m * 4)), status(g.out(status, m)),
+          centroids(K > 0 ? g.in(centroids, (size_t)K * nbins * 2) : -1), label(g.out(label, m * 2)), dist(g.out(dist, m * 4)), K(K) {}
+    HeroHistOut at(const Stage &g) const { return HeroHistOut{g.at<uint16_t>(hist), g.at<uint16_t>(void_), g.at<uint32_t>(completions), g.at<uint8_t>(status)}; }
+    HeroHistBucket bucket(const Stage &g) const { return HeroHistBucket{K, g.at<uint16_t>(centroids), g.at<uint16_t>(label), g.at<uint32_t>(dist)}; }
 };
 }  // namespace
 
@@ -2435,6 +2446,85 @@ int pk_table_equity_hist(pk_handle *h, const int32_t *tables, size_t m, const ui
     const HistStagedOut out(g, m, nbins, hist, void_, completions, status);
     return eq_table_call(h, call, tables, m, g, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return hist_launch(h->stream, tab, nullptr, &t, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, nbins, out.at(g), (uint64_t *)work);
+    });
+}
+
+// ---- hero strength histogram (pokerl_hip.h "Hero strength histogram"; kernels: pk_equity_hist_hero.hip).  Spots, weights and observer as range
+// equity; the optional bucket stage is the clustering family's assign on the rows of the call.  Work space: pk::hh_work_bytes.
+static_assert(HH_MAX_BINS == PK_EQ_HIST_MAX_BINS, "pk_equity_hist_hero.hpp and the ABI header agree");
+static const char *hh_bad_bucket(int K, const void *centroids, const void *label, const void *dist) {
+    if (K < 0 || K > PK_CL_MAX_K) return ": K must be 0 (no bucket stage) or 1 .. PK_CL_MAX_K (4096)";
+    if (K > 0 && !centroids) return ": NULL centroids with K > 0";
+    return K == 0 && (label || dist) ? ": label / dist asked for with K = 0 (no centroids to measure against)" : nullptr;
+}
+static const char *hh_check(size_t m, bool inputs, int nbins, int K, const void *centroids, const void *label, const void *dist) {
+    if (const char *why = eqr_check(m, inputs)) return why;
+    if (const char *why = hist_bad_bins(nbins)) return why;
+    return hh_bad_bucket(K, centroids, label, dist);
+}
+static const char *hh_table_check(const pk_handle *h, size_t m, int observer, int nbins, int K, const void *centroids, const void *label, const void *dist) {
+    if (const char *why = eqr_table_check(h, m, observer)) return why;
+    if (const char *why = hist_bad_bins(nbins)) return why;
+    return hh_bad_bucket(K, centroids, label, dist);
+}
+
+int pk_equity_hist_hero_d(int device, size_t m, const uint8_t *hero_d, const uint8_t *board_d, const uint8_t *nboard_d, const uint64_t *dead_d,
+                          const uint16_t *weights_d, int weights_per_spot, int nbins, uint16_t *hist_d, uint16_t *void_d, uint32_t *completions_d,
+                          uint8_t *status_d, int K, const uint16_t *centroids_d, uint16_t *label_d, uint32_t *dist_d, void *stream) {
+    const char *call = "pk_equity_hist_hero_d";
+    EQ_REFUSE(g_fail, call, hh_check(m, hero_d && board_d && nboard_d, nbins, K, centroids_d, label_d, dist_d));
+    const HeroHistOut out{hist_d, void_d, completions_d, status_d};
+    const HeroHistBucket bk{K, centroids_d, label_d, dist_d};
+    return eq_call_d(call, device, stream, m, true, hh_work_bytes(m, nbins, out, bk), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const EqrSpots spots{hero_d, board_d, nboard_d, dead_d};
+        return hh_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{weights_d, weights_per_spot != 0}, m, nbins, out, bk, work);
+    });
+}
+
+int pk_equity_hist_hero(int device, size_t m, const uint8_t *hero, const uint8_t *board, const uint8_t *nboard, const uint64_t *dead,
+                        const uint16_t *weights, int weights_per_spot, int nbins, uint16_t *hist, uint16_t *void_, uint32_t *completions,
+                        uint8_t *status, int K, const uint16_t *centroids, uint16_t *label, uint32_t *dist) {
+    const char *call = "pk_equity_hist_hero";
+    EQ_REFUSE(g_fail, call, hh_check(m, hero && board && nboard, nbins, K, centroids, label, dist));
+    Stage g;
+    const int he = g.in(hero, m * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
+    const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const HeroHistStaged io(g, m, nbins, hist, void_, completions, status, K, centroids, label, dist);
+    const size_t bytes = hh_work_bytes(m, nbins, HeroHistOut{hist, void_, completions, status}, HeroHistBucket{K, centroids, label, dist});
+    return eq_call_host(call, device, m, true, g, bytes, [&](hipStream_t st, const uint32_t *tab, char *work) {
+        const EqrSpots spots{g.at<uint8_t>(he), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
+        return hh_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, nbins, io.at(g),
+                         io.bucket(g), work);
+    });
+}
+
+// The table forms: the handle's own state as `observer` sees it
+int pk_table_equity_hist_hero_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, const uint16_t *weights_d, int weights_per_spot, int nbins,
+                                uint16_t *hist_d, uint16_t *void_d, uint32_t *completions_d, uint8_t *status_d, int K, const uint16_t *centroids_d,
+                                uint16_t *label_d, uint32_t *dist_d) {
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_hist_hero_d";
+    EQ_REFUSE(h->fail, call, hh_table_check(h, m, observer, nbins, K, centroids_d, label_d, dist_d));
+    const HeroHistOut out{hist_d, void_d, completions_d, status_d};
+    const HeroHistBucket bk{K, centroids_d, label_d, dist_d};
+    return eq_table_call_d(h, call, tables_d, m, hh_work_bytes(m, nbins, out, bk), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return hh_launch(h->stream, tab, nullptr, &t, h->N, observer, EqrWeights{weights_d, weights_per_spot != 0}, m, nbins, out, bk, work);
+    });
+}
+
+int pk_table_equity_hist_hero(pk_handle *h, const int32_t *tables, size_t m, int observer, const uint16_t *weights, int weights_per_spot, int nbins,
+                              uint16_t *hist, uint16_t *void_, uint32_t *completions, uint8_t *status, int K, const uint16_t *centroids, uint16_t *label,
+                              uint32_t *dist) {
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_equity_hist_hero";
+    EQ_REFUSE(h->fail, call, hh_table_check(h, m, observer, nbins, K, centroids, label, dist));
+    Stage g;
+    const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const HeroHistStaged io(g, m, nbins, hist, void_, completions, status, K, centroids, label, dist);
+    const size_t bytes = hh_work_bytes(m, nbins, HeroHistOut{hist, void_, completions, status}, HeroHistBucket{K, centroids, label, dist});
+    return eq_table_call(h, call, tables, m, g, bytes, [&](const uint32_t *tab, const EqTables &t, char *work) {
+        return hh_launch(h->stream, tab, nullptr, &t, h->N, observer, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, nbins, io.at(g), io.bucket(g),
+                         work);
     });
 }
 

@@ -224,9 +224,8 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
 
 namespace pk {
 
-hipError_t eqr_launch(hipStream_t stream, const uint32_t *tab, const EqrSpots *spots, const EqTables *tables, int N, int observer,
-                      const EqrWeights &weights, size_t m, const EqrOut &out, uint64_t *desc) {
-    if (m == 0) return hipSuccess;
+hipError_t eqr_prep_launch(hipStream_t stream, const EqrSpots *spots, const EqTables *tables, int N, int observer, size_t m, const EqrOut &out,
+                           uint64_t *desc) {
     EqrPrepArgs a{};
     if (spots) a.s = *spots;
     if (tables) a.t = *tables;
@@ -234,7 +233,13 @@ hipError_t eqr_launch(hipStream_t stream, const uint32_t *tab, const EqrSpots *s
     const dim3 pgrid((unsigned)((m + EQR_PREP_BLOCK - 1) / EQR_PREP_BLOCK));
     if (tables) hipLaunchKernelGGL(k_eqr_prep<true>, pgrid, dim3(EQR_PREP_BLOCK), 0, stream, a);
     else hipLaunchKernelGGL(k_eqr_prep<false>, pgrid, dim3(EQR_PREP_BLOCK), 0, stream, a);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t eqr_launch(hipStream_t stream, const uint32_t *tab, const EqrSpots *spots, const EqTables *tables, int N, int observer,
+                      const EqrWeights &weights, size_t m, const EqrOut &out, uint64_t *desc) {
+    if (m == 0) return hipSuccess;
+    const hipError_t e = eqr_prep_launch(stream, spots, tables, N, observer, m, out, desc);
     if (e != hipSuccess || !(out.agg || out.win || out.tie)) return e;   // (boards / status alone: the preparation kernel has written them)
     // one workgroup per spot at a time (each stages the 32 KB table); the grid is persistent beyond three workgroups per CU
     const unsigned grid = (unsigned)(m < (size_t)EQR_GRID_MAX ? m : (size_t)EQR_GRID_MAX);

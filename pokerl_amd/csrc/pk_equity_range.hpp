@@ -38,5 +38,9 @@ struct EqrWeights {
 // tab: the evaluator table (eval7_table); `tables` non-NULL selects the table form (observer: a seat or PK_OBSERVER_ACTIVE).
 hipError_t eqr_launch(hipStream_t stream, const uint32_t *tab, const EqrSpots *spots, const EqTables *tables, int N, int observer,
                       const EqrWeights &weights, size_t m, const EqrOut &out, uint64_t *desc);
+// The first half alone, for the hero histograms (pk_equity_hist_hero.hip), whose spot is this one: k_eqr_prep on `stream` -- the descriptors,
+// and out.boards / out.status where they are given (the other outputs are not looked at).
+hipError_t eqr_prep_launch(hipStream_t stream, const EqrSpots *spots, const EqTables *tables, int N, int observer, size_t m, const EqrOut &out,
+                           uint64_t *desc);
 
 }  // namespace pk

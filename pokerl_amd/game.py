@@ -624,6 +624,60 @@ class VecGame:
                                                  check_bins(bins), self._dptr(hist_d), self._dptr(void_d), self._dptr(completions_d),
                                                  self._dptr(status_d)), self._h)
 
+    def equity_hist_hero(self, observer='active', weights=None, tables=None, bins=10, centroids=None):
+        """The strength histogram of ONE seat's holding at `tables` (all tables if None; indices may repeat), post-flop
+        (pk_table_equity_hist_hero; definition: pokerl_hip.h "Hero strength histogram"): the distribution of the river strength of
+        `observer` (a seat, or 'active' / OBSERVER_ACTIVE: each table's active seat) against the opponent's range over the completions of
+        the board, in `bins` (1 .. 32) equal parts of [0, 1] -- the row of equity_hist for that seat's hand, at the cost of equity_range.
+        weights: None (uniform), uint16 [1326] (one range) or [m, 1326] over judger.holding_index.  centroids: None, or uint16 [k, bins]
+        (cluster_histograms(...).centroids): the result then carries each table's bucket `label` and `dist` from the same call.  Returns a
+        judger.HeroHistogram with uint16 [m, bins] hist.  A table that cannot be evaluated (pre-flop, never reset, step in flight) has a
+        non-zero status, zeros, and label PK_CL_NONE."""
+        from .judger import HeroHistogram, hero_bucket_args, range_weights
+        o = self._range_observer(observer)
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        w, per_spot = range_weights(weights, m)
+        bins, cen, k, label, dist = hero_bucket_args(bins, centroids, m)
+        hist, void = np.zeros((m, bins), np.uint16), np.zeros(m, np.uint16)
+        completions, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        L.check(self._lib.pk_table_equity_hist_hero(self._h, L.ptr(t), m, o, L.ptr(w), per_spot, bins, L.ptr(hist), L.ptr(void), L.ptr(completions),
+                                                    L.ptr(status), k, L.ptr(cen), L.ptr(label), L.ptr(dist)), self._h)
+        return HeroHistogram(hist, void, completions, status, label, dist)
+
+    def equity_hist_hero_d(self, m=None, tables_d=None, observer='active', weights_d=None, weights_per_spot=False, bins=10, hist_d=None, void_d=None,
+                           completions_d=None, status_d=None, k=0, centroids_d=None, label_d=None, dist_d=None):
+        """pk_table_equity_hist_hero_d: the same into device buffers (uint16 [m, bins] hist, uint16 [m] void, uint32 [m] completions, uint8
+        [m] status, and with k > 0 and centroids_d uint16 [k, bins]: uint16 [m] label, uint32 [m] dist; any output may be None; weights_d
+        uint16 [1326] or [m, 1326] or None), asynchronous on the handle's stream.  m defaults to every table."""
+        from .judger import _cl_int, check_bins
+        o = self._range_observer(observer)
+        m = self.num_tables if m is None else int(m)
+        k = _cl_int('k', k, 0, L.CL_MAX_K)
+        if k and centroids_d is None:
+            raise ValueError('k > 0 needs centroids_d')
+        if not k and (label_d is not None or dist_d is not None):
+            raise ValueError('label_d / dist_d need k > 0 and centroids_d')
+        L.check(self._lib.pk_table_equity_hist_hero_d(self._h, self._dptr(tables_d), m, o, self._dptr(weights_d), int(bool(weights_per_spot)),
+                                                      check_bins(bins), self._dptr(hist_d), self._dptr(void_d), self._dptr(completions_d),
+                                                      self._dptr(status_d), k, self._dptr(centroids_d), self._dptr(label_d), self._dptr(dist_d)),
+                self._h)
+
+    def bucket(self, centroids, observer='active', weights=None, tables=None):
+        """The bucket of `observer`'s hand at `tables` -> uint16 [m]: the label of equity_hist_hero(..., bins=centroids.shape[1],
+        centroids=centroids), asked for alone (the histograms stay on the device).  PK_CL_NONE (0xFFFF) where a table cannot be evaluated."""
+        from .judger import hero_bucket_args, range_weights
+        o = self._range_observer(observer)
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        w, per_spot = range_weights(weights, m)
+        if centroids is None or np.ndim(centroids) != 2:
+            raise ValueError('centroids must have shape [k, bins]')
+        bins, cen, k, label, _ = hero_bucket_args(int(np.shape(centroids)[1]), centroids, m)
+        L.check(self._lib.pk_table_equity_hist_hero(self._h, L.ptr(t), m, o, L.ptr(w), per_spot, bins, None, None, None, None, k, L.ptr(cen),
+                                                    L.ptr(label), None), self._h)
+        return label
+
     def __deepcopy__(self, memo):
         """A new handle with the same configuration (seed and table ids included) holding a copy of every table: it continues
         bit-identically to this game under the same actions, and stepping one leaves the other untouched.  Only the construction

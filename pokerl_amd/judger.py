@@ -980,6 +980,117 @@ def strength_histogram(board, dead=(), weights=None, bins=10, device=0):
     return r
 
 
+# ---------------------------------------------------------------------------------------------- hero strength histogram
+# The strength histogram of ONE holding -- row holding_index(hero) of the histograms above at the cost of one range-equity spot -- and,
+# with centroids, its bucket in the same call (pk_equity_hist_hero; the definition: include/pokerl_hip.h "Hero strength histogram",
+# DESIGN.md section 3.9).
+class HeroHistogram:
+    """Counts of one spot or of a batch: hist uint16 [bins] or [m, bins] -- completions of the board on which the hero's river strength
+    (below + equal / 2) / den falls into each of `bins` equal parts of [0, 1] --, void -- completions on which the opponent's range has no
+    weight left --, `completions` = C(P, k) and `status`, scalars or [m]: hist.sum(-1) + void == completions.  `pdf` = hist / hist.sum(-1) in
+    float64 (nan where nothing was counted), `cdf` its running sum.  With centroids: `label` uint16 (PK_CL_NONE = 0xFFFF for an empty row),
+    `dist` uint32 and `emd` = dist / 65535, the earth mover's distance to the bucket's centroid in bins; None without."""
+
+    def __init__(self, hist, void, completions, status, label=None, dist=None):
+        self.hist, self.void, self.completions, self.status, self.label, self.dist = hist, void, completions, status, label, dist
+
+    @property
+    def bins(self):
+        return np.shape(self.hist)[-1]
+
+    @property
+    def pdf(self):
+        h = np.asarray(self.hist, np.float64)
+        n = h.sum(axis=-1, keepdims=True)
+        return np.divide(h, n, out=np.full(h.shape, np.nan, np.float64), where=n > 0)
+
+    @property
+    def cdf(self):
+        return np.cumsum(self.pdf, axis=-1)
+
+    @property
+    def emd(self):
+        return None if self.dist is None else np.asarray(self.dist, np.float64) / 65535.0
+
+    def __getitem__(self, i):
+        return HeroHistogram(self.hist[i], self.void[i], self.completions[i], self.status[i], None if self.label is None else self.label[i],
+                             None if self.dist is None else self.dist[i])
+
+    def __repr__(self):
+        return 'HeroHistogram(bins=%r, completions=%r, status=%r, label=%r)' % (self.bins, self.completions, self.status, self.label)
+
+
+def hero_bucket_args(bins, centroids, m):
+    """(bins, centroids or None, K, label or None, dist or None) of a hero-histogram call; ValueError before any device call."""
+    bins = check_bins(bins)
+    if centroids is None:
+        return bins, None, 0, None, None
+    cen = _cl_centroids(centroids, bins)
+    return bins, cen, cen.shape[0], np.zeros(m, np.uint16), np.zeros(m, np.uint32)
+
+
+def hero_histogram_batch(hero, board, nboard, dead=None, weights=None, bins=10, centroids=None, device=0):
+    """pk_equity_hist_hero on host arrays: hero uint8 [m, 2] Card.value, board uint8 [m, 5] (the first nboard[i] = 3, 4 or 5 used), nboard
+    uint8 [m], dead uint64 [m] masks over canonical card indices (None: none), weights None / uint16 [1326] / [m, 1326] (the opponent's
+    range), bins 1 .. 32, centroids None or uint16 [k, bins] (cluster_histograms(...).centroids) -> HeroHistogram.  A bad spot is reported
+    through its `status` (PK_EQ_* bits) with all-zero outputs and label PK_CL_NONE; the others are unaffected."""
+    hero = np.ascontiguousarray(hero, np.uint8)
+    if hero.ndim != 2 or hero.shape[1] != 2:
+        raise ValueError('hero must have shape [m, 2]')
+    m = hero.shape[0]
+    board = np.ascontiguousarray(board, np.uint8)
+    nboard = np.ascontiguousarray(nboard, np.uint8)
+    if board.shape != (m, 5) or nboard.shape != (m,):
+        raise ValueError('board must have shape [m, 5], nboard shape [m]')
+    if dead is not None:
+        dead = np.ascontiguousarray(dead, np.uint64)
+        if dead.shape != (m,):
+            raise ValueError('dead must have shape [m]')
+    w, per_spot = range_weights(weights, m)
+    bins, cen, k, label, dist = hero_bucket_args(bins, centroids, m)
+    hist, void = np.zeros((m, bins), np.uint16), np.zeros(m, np.uint16)
+    completions, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+    L.check(L.lib().pk_equity_hist_hero(int(device), m, L.ptr(hero), L.ptr(board), L.ptr(nboard), L.ptr(dead), L.ptr(w), per_spot, bins,
+                                        L.ptr(hist), L.ptr(void), L.ptr(completions), L.ptr(status), k, L.ptr(cen), L.ptr(label), L.ptr(dist)))
+    return HeroHistogram(hist, void, completions, status, label, dist)
+
+
+def hero_histogram_d(m, hero_d, board_d, nboard_d, dead_d=None, weights_d=None, weights_per_spot=False, bins=10, hist_d=None, void_d=None,
+                     completions_d=None, status_d=None, k=0, centroids_d=None, label_d=None, dist_d=None, device=0, stream=None):
+    """pk_equity_hist_hero_d: the same on device-resident buffers (device pointers as ints / c_void_p; dead_d, weights_d and the outputs may
+    be None; hist is uint16 [m, bins]; k = 0: no bucket stage, else centroids_d uint16 [k, bins] and label_d uint16 [m] / dist_d uint32 [m]),
+    asynchronous on `stream`."""
+    k = _cl_int('k', k, 0, L.CL_MAX_K)
+    if k and centroids_d is None:
+        raise ValueError('k > 0 needs centroids_d')
+    if not k and (label_d is not None or dist_d is not None):
+        raise ValueError('label_d / dist_d need k > 0 and centroids_d')
+    L.check(L.lib().pk_equity_hist_hero_d(int(device), int(m), hero_d, board_d, nboard_d, dead_d, weights_d, int(bool(weights_per_spot)),
+                                          check_bins(bins), hist_d, void_d, completions_d, status_d, k, centroids_d, label_d, dist_d, stream))
+
+
+def hero_histogram(hero, board, dead=(), weights=None, bins=10, centroids=None, device=0):
+    """One spot.  hero: two cards (Card-likes / 'RS' strings / Card.value ints); board: 3 .. 5 known cards; dead: cards known to be out of
+    play; weights: None or [1326] integers 0 .. 65535 over holding_index, the opponent's range; bins 1 .. 32; centroids: None or uint16
+    [k, bins].  Returns a HeroHistogram with a [bins] hist and scalars; raises ValueError for an invalid spot."""
+    bins = check_bins(bins)
+    hero, board = list(hero), list(board)
+    if len(hero) != 2:
+        raise ValueError('the hero holds two cards')
+    if not 3 <= len(board) <= 5:
+        raise ValueError('invalid spot: ' + equity_status_text(L.EQ_PREFLOP) if len(board) < 3 else 'three to five board cards')
+    h = np.array([[_card(c) for c in hero]], np.uint8)
+    b = np.zeros((1, 5), np.uint8)
+    b[0, :len(board)] = [_card(c) for c in board]
+    d = np.array([dead_mask(dead)], np.uint64)
+    if weights is not None and np.ndim(weights) != 1:
+        raise ValueError('weights must have shape [1326]')
+    r = hero_histogram_batch(h, b, np.array([len(board)], np.uint8), d, weights, bins, centroids, device=device)[0]
+    if r.status:
+        raise ValueError('invalid spot: ' + equity_status_text(r.status))
+    return r
+
+
 # ---------------------------------------------------------------------------------------------- histogram clustering
 # Buckets of strength histograms: exact k-means under the earth mover's distance on the device (pk_hist_cluster; the definition:
 # include/pokerl_hip.h "Histogram clustering", DESIGN.md section 3.8).  Every quantity is an integer.

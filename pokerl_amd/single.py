@@ -156,6 +156,21 @@ class Game:
             raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
         return r
 
+    def equity_hist_hero(self, observer=None, weights=None, bins=10, centroids=None):
+        """The strength histogram of `observer`'s hand (None = the active seat), post-flop (VecGame.equity_hist_hero): a
+        judger.HeroHistogram with a [bins] hist and, with centroids, its bucket `label` / `dist`.  Not in the reference."""
+        from ._lib import OBSERVER_ACTIVE
+        r = self._v.equity_hist_hero(observer=OBSERVER_ACTIVE if observer is None else observer, weights=weights, bins=bins, centroids=centroids)[0]
+        if r.status:
+            from .judger import equity_status_text
+            raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
+        return r
+
+    def bucket(self, centroids, observer=None, weights=None):
+        """The bucket of `observer`'s hand (None = the active seat) under `centroids` uint16 [k, bins], post-flop: an int.  Not in the
+        reference."""
+        return int(self.equity_hist_hero(observer=observer, weights=weights, bins=int(np.shape(centroids)[-1]), centroids=centroids).label)
+
     def step(self, action):                                                       # :621-700
         """Returns (game_over, hand_over, turn_over); raises the reference's ValueError / NotImplementedError /
         AssertionError in the reference's situations."""

@@ -27,6 +27,10 @@ The shapes are the smallest at which each mechanism of the kernels can break (do
   k_cl_*           (cluster_cases, run beside all_cases by this program and by tests/test_hist_cluster_sim_host.py) quantise / assign / update /
                    finalise / seed as pk::cl_*_launch queues them; 1, 2, 7, 10 and 32 bins; a grid of 1 (every workgroup strides), an unaligned
                    histogram pointer, empty rows as whole waves, constructed ties, both update kernels, seeding over several chunks and tiles.
+  k_hero_hist      (hero_hist_cases, run beside all_cases by this program and by tests/test_hero_hist_sim_host.py) k_eqr's shapes: nb = 3, 4, 5;
+                   the smallest pool; sets below 512 and no multiple of 512; a river spot (one completion); a grid of 1 with spots of falling
+                   size (the counters cleared for the next spot, stale LDS); every weight form, a dead range (every completion void); bins 1,
+                   7, 10, 32; each output NULL in turn; a refused spot between good ones; the table form.
   preparation      every status bit, the explicit and the table form; table indices -1, T and 2^31 - 1 (nothing is read: ASan's to check).
 
   equity_cases.py --exe <equity_sim> [--exe <another build>] [--quick] [--only <substring>] [--list] [--keep <dir>]
@@ -51,6 +55,7 @@ import equity_ranged_spec as WS         # noqa: E402
 import equity_sampled_spec as SS        # noqa: E402
 import equity_spec as ES                # noqa: E402
 import ev_spec as EV                    # noqa: E402
+import hero_hist_spec as HHS             # noqa: E402
 import hist_cluster_spec as CS          # noqa: E402
 import hist_spec as HS                  # noqa: E402
 import rvr_spec as VS                   # noqa: E402
@@ -63,7 +68,8 @@ OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("w
            "range": ("agg", "win", "tie", "boards", "status"), "rvr": ("win", "tie", "tot", "boards", "status"),
            "hist": ("hist", "void", "completions", "status"), "ranged": ("win", "tie", "share", "accepted", "status"),
            "ev": ("share", "level_seat", "amount", "ev", "boards", "status"),
-           "cluster": ("centroids_out", "label", "dist", "inertia", "changed")}
+           "cluster": ("centroids_out", "label", "dist", "inertia", "changed"),
+           "herohist": ("hist", "void", "completions", "status")}
 
 
 class Case:
@@ -776,6 +782,61 @@ def cluster_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- hero histograms
+def hero_hist_case(name, shapes, seed, grid, bins, wform=None, outputs=None, quick=False, edit=None):
+    hero, board, nboard, dead = hero_spots(seed, shapes)
+    if edit:
+        edit(hero, board, nboard, dead)
+    m = len(shapes)
+    w, per_spot = weights_for(seed + 1, m, wform)
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [grid]), "bins": ("u32", [bins]), "hero": ("u8", hero), "board": ("u8", board), "nboard": ("u8", nboard),
+              "dead": ("u64", dead), "weights": ("u16", w), "per_spot": ("u32", [per_spot])}
+    return Case(name, "herohist", arrays, lambda: HHS.batch_hero_hist(hero, board, nboard, dead, w, bins), outputs, quick)
+
+
+def hero_hist_cases():
+    """The cases of k_hero_hist: a list of its own (all_cases() and cluster_cases() are counted by their tests)."""
+    cs = []
+    # nb = 5, 4, 3 at the smallest pool (k + 2), sets below 512 (C(12, 4) = 495) and no multiple of 512 (C(20, 3) = 1140, C(33, 2) = 528), river spots
+    # (one completion); ONE workgroup, the largest first: the counters cleared for the next spot
+    small = [(5, 33), (5, 6), (5, 2), (4, 20), (4, 7), (4, 3), (3, 12), (3, 8), (3, 4)]
+    cs.append(hero_hist_case("herohist-bounds-grid1", small, 51, 1, 7, None, quick=True))
+    cs.append(hero_hist_case("herohist-bounds-shared-w", small[::-1], 52, 3, 10, "shared"))
+    cs.append(hero_hist_case("herohist-full-pools", [(3, 47), (4, 46), (5, 45)], 53, 2, 10, "spot"))
+    cs.append(hero_hist_case("herohist-grid1-spot-w", [(4, 30), (3, 12), (5, 20)], 54, 1, 10, "spot", quick=True))
+    cs.append(hero_hist_case("herohist-two-spots-grid1", [(3, 10), (3, 9)], 55, 1, 32, "shared", quick=True))
+    cs.append(hero_hist_case("herohist-river-alone", [(5, 47)], 56, 1, 2, "shared", quick=True))
+    cs.append(hero_hist_case("herohist-zero-weights", [(4, 12), (5, 17), (3, 7)], 57, 2, 7, "zero", quick=True))
+    cs.append(hero_hist_case("herohist-bins1", [(5, 33), (4, 12), (3, 6)], 58, 1, 1, "shared", quick=True))
+
+    def middle(hero, board, nboard, dead):
+        hero[1, 1] = board[1, 0]                                      # the hero holds a board card -> refused
+    cs.append(hero_hist_case("herohist-refused-between", [(4, 20), (4, 12), (5, 11)], 59, 1, 7, "shared", edit=middle, quick=True))
+    for o in OUTPUTS["herohist"]:
+        cs.append(hero_hist_case("herohist-no-" + o, [(5, 12), (4, 11)], 60, 1, 7, "shared", outputs=[x for x in OUTPUTS["herohist"] if x != o]))
+
+    def bits(hero, board, nboard, dead):
+        hero[1, 0] = 0x4A                                             # suit 4: no card
+        board[2, 2] = hero[2, 0]
+        nboard[3] = 7
+        # [4]: nb = 0, pre-flop
+        used = [VS.canon_index(int(x)) for x in list(hero[5]) + list(board[5, :3])]
+        dead[5] = np.uint64(dead_mask([c for c in range(52) if c not in used][:44]))      # P = 3 < k + 2 = 4
+        dead[6] = np.uint64(1 << 63)
+    cs.append(hero_hist_case("herohist-status-bits", [(5, 12), (5, 12), (5, 12), (5, 12), (0, 30), (3, 12), (5, 12), (4, 11)], 61, 2, 7, None, edit=bits, quick=True))
+    for observer, who in ((1, lambda w: np.full(w["T"], 1)), (-2, lambda w: w["active"])):
+        w = table_world(62, 3, 5, turns=(3, 0, 2))                    # river, pre-flop and turn tables (a full-pool flop is 178 365 sets)
+        arrays = dict(table_arrays(w), m=("u32", [len(w["tables"])]), grid=("u32", [2]), bins=("u32", [10]), observer=("i32", [observer]))
+
+        def expect(w=w, who=who):
+            hero, board, nboard = RS.table_spots(w["deck"], w["turn"], who(w))
+            r = HHS.batch_hero_hist(hero, board, nboard, None, None, 10)
+            return table_expect(w, {k: r[k] for k in OUTPUTS["herohist"]}, ("hist", "void"), "completions")
+        cs.append(Case("herohist-table-form-observer%d" % observer, "herohist", arrays, expect, quick=(observer == -2)))
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -790,7 +851,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + cluster_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + cluster_cases() + hero_hist_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

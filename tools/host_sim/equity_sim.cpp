@@ -1,4 +1,4 @@
-// Dev-only: the REAL equity kernels -- k_equity<N>, k_eqs<N>, k_eqr, k_rvr, k_hist, k_eqw<N, RC> and their preparation kernels, the text of
+// Dev-only: the REAL equity kernels -- k_equity<N>, k_eqs<N>, k_eqr, k_rvr, k_hist, k_hero_hist, k_eqw<N, RC> and their preparation kernels, the text of
 // pokerl_amd/csrc/pk_equity*.hip -- run on the CPU as workgroups of 8 waves x 64 lanes (wg_shim.h: a fibre per lane, every collective and
 // barrier a checked rendezvous, garbage LDS before every workgroup, PK_IDX active).  One case per run: the case file names the family, the
 // spots, the weights / bins / samples, the grid and which outputs are wanted; the preparation kernel runs, then the main kernel, and every
@@ -9,7 +9,8 @@
 //   equity_sim <case file> <out file>
 // Case file: lines "name dtype count" (dtype u8 u16 u32 u64 i32) each followed by a line of `count` decimal values, and
 // "family <name>" / "outputs <name> ..." lines.  Out file: the same array format.
-// -DPK_ES_ONLY=1 .. 8: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster), so that a test can compile them side by side.
+// -DPK_ES_ONLY=1 .. 9: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist), so that a test can compile them side by side.
+// The herohist family (pk_equity_hist_hero.hip) checks its spots with k_eqr_prep; its optional bucket stage is the cluster family's assign and is not run here.
 // The cluster family (pk_hist_cluster.hip) has no preparation kernel: the driver queues its kernels in the order of pk::cl_seed_launch /
 // cl_assign_launch / cl_cluster_launch (`op` 0 / 1 / 2), with the case's grid, seeding chunk and choice of the update kernel.
 // f64 arrays (the bets, amounts and ev of the ev family) travel as their bit patterns, dtype u64.
@@ -23,8 +24,8 @@
 #if PK_ES_HAS(2)
 #include "../../pokerl_amd/csrc/pk_equity_sampled.hip"
 #endif
-#if PK_ES_HAS(3)
-#include "../../pokerl_amd/csrc/pk_equity_range.hip"
+#if PK_ES_HAS(3) || PK_ES_HAS(9)
+#include "../../pokerl_amd/csrc/pk_equity_range.hip"     // (the hero histograms check their spots with k_eqr_prep)
 #endif
 #if PK_ES_HAS(4) || PK_ES_HAS(5)
 #include "../../pokerl_amd/csrc/pk_equity_rvr.hip"      // (the histograms check their spots with k_rvr_prep)
@@ -43,9 +44,13 @@
 #include "../../pokerl_amd/csrc/pk_equity_ev.hip"
 #endif
 
-#if PK_ES_HAS(8)
+#if PK_ES_HAS(8) || PK_ES_HAS(9)
 #include "../../pokerl_amd/csrc/pk_equity.hpp"          // (EqTables, which the driver's table_form names)
-#include "../../pokerl_amd/csrc/pk_hist_cluster.hip"
+#include "../../pokerl_amd/csrc/pk_hist_cluster.hip"    // (pk::hh_launch names pk::cl_assign_launch)
+#endif
+
+#if PK_ES_HAS(9)
+#include "../../pokerl_amd/csrc/pk_equity_hist_hero.hip"
 #endif
 
 #include <chrono>
@@ -286,6 +291,31 @@ void run_hist(Case &c, const uint32_t *tab) {
 #endif
 
 
+#if PK_ES_HAS(9)
+// k_eqr_prep (status alone), k_hero_hist_counts, k_hero_hist
+void run_hero_hist(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const uint32_t bins = (uint32_t)c.num("bins");
+    const int N = (int)c.num("N", 2);
+    EqrPrepArgs a{};
+    const bool tbl = table_form(c, N, m, a.t);
+    if (!tbl) { a.s.hero = c.need<uint8_t>("hero", m * 2); a.s.board = c.need<uint8_t>("board", m * 5); a.s.nboard = c.need<uint8_t>("nboard", m); a.s.dead = c.arr<uint64_t>("dead", m); }
+    const int per_spot = (int)c.num("per_spot", 0);
+    const EqrWeights wts{c.arr<uint16_t>("weights", per_spot ? m * EQR_HOLDINGS : (size_t)EQR_HOLDINGS), per_spot};
+    HeroHistOut out{};
+    out.hist = c.output<uint16_t>("hist", "u16", m * bins); out.void_ = c.output<uint16_t>("void", "u16", m);
+    out.completions = c.output<uint32_t>("completions", "u32", m); out.status = c.output<uint8_t>("status", "u8", m);
+    Work<uint64_t> desc(m * EQR_DESC_WORDS);
+    a.out = EqrOut{nullptr, nullptr, nullptr, nullptr, out.status}; a.desc = desc.p; a.N = N; a.observer = (int)c.num("observer", 0); a.m = m;
+    if (tbl) pk_sim::launch(prep_grid(m, EQR_PREP_BLOCK), EQR_PREP_BLOCK, [&] { k_eqr_prep<true>(a); });
+    else pk_sim::launch(prep_grid(m, EQR_PREP_BLOCK), EQR_PREP_BLOCK, [&] { k_eqr_prep<false>(a); });
+    const uint64_t *dp = desc.p;
+    if (out.completions) pk_sim::launch(prep_grid(m, HH_COUNTS_BLOCK), HH_COUNTS_BLOCK, [&] { k_hero_hist_counts(dp, out.completions, m); });
+    if (out.hist || out.void_) pk_sim::launch(grid, HH_BLOCK, [&] { k_hero_hist(tab, dp, wts, out, bins, (uint32_t)m); });
+}
+#endif
+
 #if PK_ES_HAS(6)
 // k_eqw_cdf, k_eqw_prep, k_eqw<N, RC>: RC is the size class of the case's R, as eqw_launch picks it
 template <int N, int RC>
@@ -437,7 +467,7 @@ int main(int argc, char **argv) {
     if (argc != 3) die("usage: equity_sim <case file> <out file>");
     Case c(argv[1]);
     // the function-local __shared__ arrays of the main kernels (the preparation kernels have none)
-    const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "5k_eqwILi", "4k_evILi", "10k_cl_quant", "11k_cl_assign",
+    const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "11k_hero_histPKj", "5k_eqwILi", "4k_evILi", "10k_cl_quant", "11k_cl_assign",
                                         "11k_cl_update", "14k_cl_seed_dist", "14k_cl_seed_pick"});
     Work<uint32_t> tab(EVAL7_TAB_WORDS);
     for (int i = 0; i < EVAL7_TAB_WORDS; ++i) tab.p[i] = eval7_tab_entry((uint32_t)i);
@@ -484,6 +514,9 @@ int main(int argc, char **argv) {
 #endif
 #if PK_ES_HAS(8)
     if (c.family == "cluster") { run_cluster(c); ran = true; }
+#endif
+#if PK_ES_HAS(9)
+    if (c.family == "herohist") { run_hero_hist(c, tab.p); ran = true; }
 #endif
     if (!ran) die("family " + c.family + ": not in this build");
     c.write(argv[2]);

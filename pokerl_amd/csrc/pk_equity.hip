@@ -18,7 +18,6 @@
 using namespace pk;
 
 #define EQ_PREP_BLOCK 256
-constexpr uint32_t EQ_FROZEN = 63;   // pool slot that holds no card: the index of a combination level that does not exist (k < 5)
 
 struct EqPrepArgs {
     EqSpots s;
@@ -28,14 +27,6 @@ struct EqPrepArgs {
     int N, lpt;
     size_t m;
 };
-
-// C(n, k), 0 <= k <= 5, n <= 52: exact at every step (r * (n - j) is a multiple of j + 1)
-__host__ __device__ inline uint32_t eq_binom(uint32_t n, uint32_t k) {
-    if (k > n) return 0;
-    uint32_t r = 1;
-    for (uint32_t j = 0; j < k; ++j) r = r * (n - j) / (j + 1);
-    return r;
-}
 
 template <bool TABLE>
 __global__ void __launch_bounds__(EQ_PREP_BLOCK) k_equity_prep(EqPrepArgs a) {
@@ -143,8 +134,8 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
     const uint32_t listed = W.ctrl->ntasks;
     const uint32_t ntasks = listed < W.task_cap ? listed : (uint32_t)W.task_cap;
     if (blockIdx.x * EQ_WAVES >= ntasks) return;                 // (the whole workgroup: before the table is staged)
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQ_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
-    if (threadIdx.x < 32) wt[PK_IDX(threadIdx.x, 32, "wt")] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
+    stage_eval7_tab<EQ_BLOCK>(T, tab);
+    fill_share_weights(wt);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, wave = uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
     uint64_t *mypool = pool[PK_IDX(wave, EQ_WAVES, "pool")];
@@ -170,18 +161,12 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
         const uint32_t start = chunk * per, end = min(boards, start + per), nt = end > start ? end - start : 0u;
         const uint32_t l = (nt + 63u) / 64u, s = start + lane * l;
         const uint32_t cnt = s < end ? min(l, end - s) : 0u;
-        // the pool: card j (canonical order) of the cards not dead, as its bit in the suit-lane layout
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (lane < 52u && ((avail >> lane) & 1ull))
-            mypool[PK_IDX(__popcll(avail & ((1ull << lane) - 1ull)), 64, "mypool")] = 4ull << (((lane & 3u) << 4) | (lane >> 2));
-        if (lane == EQ_FROZEN) mypool[EQ_FROZEN] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        eq_fill_wave_pool(mypool, avail, lane);
         // combination levels 0 .. 4 (ascending pool indices c0 < c1 < c2 < c3 < j), the first 5 - k of them frozen on the empty slot;
         // lim[t]: the highest index level t may still be raised FROM (-1: never)
         const int f = 5 - (int)k;
         const int lim0 = f <= 0 ? (int)P - 5 : -1, lim1 = f <= 1 ? (int)P - 4 : -1, lim2 = f <= 2 ? (int)P - 3 : -1, lim3 = f <= 3 ? (int)P - 2 : -1;
-        uint32_t c0 = EQ_FROZEN, c1 = EQ_FROZEN, c2 = EQ_FROZEN, c3 = EQ_FROZEN, j = EQ_FROZEN;
+        uint32_t c0 = COMB_FROZEN, c1 = COMB_FROZEN, c2 = COMB_FROZEN, c3 = COMB_FROZEN, j = COMB_FROZEN;
         if (cnt) {     // unrank board index s (lexicographic): C(P - 1 - x, levels left) boards start with x at a level
             uint32_t r = s, x = 0;
             auto level = [&](auto jc) {
@@ -227,7 +212,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eq_min_waves<N>()) k_equity(const ui
                 else if ((int)c2 < lim2) { ++c2; c3 = c2 + 1; }
                 else if ((int)c1 < lim1) { ++c1; c2 = c1 + 1; c3 = c2 + 1; }
                 else if ((int)c0 < lim0) { ++c0; c1 = c0 + 1; c2 = c1 + 1; c3 = c2 + 1; }
-                else { c3 = EQ_FROZEN - 1; }                                          // (past the spot's last board: never evaluated)
+                else { c3 = COMB_FROZEN - 1; }                                          // (past the spot's last board: never evaluated)
                 j = c3 + 1;
                 base = known | mypool[PK_IDX(c0, 64, "mypool") & 63u] | mypool[PK_IDX(c1, 64, "mypool") & 63u] | mypool[PK_IDX(c2, 64, "mypool") & 63u] | mypool[PK_IDX(c3, 64, "mypool") & 63u];
             }
@@ -270,12 +255,6 @@ size_t eq_layout(int N, size_t m, int lpt, int pool_max, char *base, EqWork *w) 
     if (w) *w = r;
     return off;
 }
-
-#ifdef PK_ONLY_SEATS
-#define EQ_SEAT_ENABLED(N) ((N) == (PK_ONLY_SEATS))
-#else
-#define EQ_SEAT_ENABLED(N) 1
-#endif
 
 template <int N>
 static bool eq_dispatch(int n, hipStream_t stream, unsigned grid, const uint32_t *tab, const EqWork &w, const EqOut &out, int lpt) {

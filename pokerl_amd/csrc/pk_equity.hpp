@@ -1,11 +1,13 @@
 // pk_equity.hpp -- showdown equity by exhaustive board enumeration (include/pokerl_hip.h "Showdown equity"): what the
-// host entry points (pk_api.hip) and the kernels (pk_equity.hip) share.  The existing table kernels do not include it.
+// host entry points (pk_api.hip) and the kernels (pk_equity.hip) share, and the device pieces k_equity<N> shares with k_ev<N>
+// (pk_equity_ev.hip).  The existing table kernels do not include it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "pk_device.hpp"
+#include "pk_equity_common.hpp"
 
 namespace pk {
 
@@ -55,6 +57,26 @@ struct EqTables {         // the table form: a handle's own state (read only)
     const int32_t *tables;   // NULL: spot i is table i
     int T;
 };
+
+// C(n, k), 0 <= k <= 5, n <= 52: exact at every step (r * (n - j) is a multiple of j + 1)
+__host__ __device__ inline uint32_t eq_binom(uint32_t n, uint32_t k) {
+    if (k > n) return 0;
+    uint32_t r = 1;
+    for (uint32_t j = 0; j < k; ++j) r = r * (n - j) / (j + 1);
+    return r;
+}
+
+// ---- what the persistent enumeration kernels (k_equity<N>, k_ev<N>) share on the device
+// The wavefront's pool: card j (canonical order) of the cards not dead, as its bit in the suit-lane layout; the empty slot holds none.
+// The wavefront alone reads and writes mypool, between fences: the task before is done with it, the lanes see what the others wrote.
+__device__ __forceinline__ void eq_fill_wave_pool(uint64_t *mypool, uint64_t avail, uint32_t lane) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    if (lane < 52u && ((avail >> lane) & 1ull))
+        mypool[PK_IDX(__popcll(avail & ((1ull << lane) - 1ull)), 64, "mypool")] = card_bit(lane);
+    if (lane == COMB_FROZEN) mypool[COMB_FROZEN] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
 
 // Queues the whole call on `stream`: control block reset, descriptors + zeroed outputs + task list (one lane per spot), then the
 // persistent enumeration kernel.  tab: the evaluator table (eval7_table); `tables` non-NULL selects the table form.

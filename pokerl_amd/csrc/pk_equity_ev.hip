@@ -19,7 +19,6 @@ using namespace pk;
 
 #define EV_PREP_BLOCK 256
 #define EV_FINISH_BLOCK 256
-constexpr uint32_t EV_FROZEN = 63;   // pool slot that holds no card (pk_equity.hip: EQ_FROZEN)
 
 struct EvPrepArgs {
     EqSpots s;
@@ -30,13 +29,6 @@ struct EvPrepArgs {
     int lpt;
     size_t m;
 };
-
-__host__ __device__ inline uint32_t ev_binom(uint32_t n, uint32_t k) {   // C(n, k), 0 <= k <= 5, n <= 52 (pk_equity.hip: eq_binom)
-    if (k > n) return 0;
-    uint32_t r = 1;
-    for (uint32_t j = 0; j < k; ++j) r = r * (n - j) / (j + 1);
-    return r;
-}
 
 // negative (not -0.0), infinite or NaN: read from the bits -- the build does not honour NaNs in comparisons (build.py)
 __device__ __forceinline__ bool ev_bad_bet(double b) {
@@ -116,7 +108,7 @@ __global__ void __launch_bounds__(EV_PREP_BLOCK) k_ev_prep(EvPrepArgs a) {
         PK_FOR(p, N) bad = bad || ev_bad_bet(bets[p]); PK_END
         if (bad) status |= PK_EQ_BAD_BET;
         const uint32_t P = 52u - (uint32_t)__popcll(dead), k = (uint32_t)(5 - nb);
-        const uint32_t boards = status ? 0u : ev_binom(P, k);
+        const uint32_t boards = status ? 0u : eq_binom(P, k);
         d[0] = known;
         d[1] = ~dead & 0x000FFFFFFFFFFFFFull;
         d[2] = (uint64_t)boards | ((uint64_t)live << 32) | ((uint64_t)k << 48) | ((uint64_t)P << 56);
@@ -200,8 +192,8 @@ __global__ void __launch_bounds__(EQ_BLOCK, ev_min_waves<N>()) k_ev(const uint32
     const uint32_t listed = W.eq.ctrl->ntasks;
     const uint32_t ntasks = listed < W.eq.task_cap ? listed : (uint32_t)W.eq.task_cap;
     if (blockIdx.x * EQ_WAVES >= ntasks) return;                 // (the whole workgroup: before the table is staged)
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQ_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
-    if (threadIdx.x < 32) wt[PK_IDX(threadIdx.x, 32, "wt")] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
+    stage_eval7_tab<EQ_BLOCK>(T, tab);
+    fill_share_weights(wt);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, wave = uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
     uint64_t *mypool = pool[PK_IDX(wave, EQ_WAVES, "pool")];
@@ -231,18 +223,12 @@ __global__ void __launch_bounds__(EQ_BLOCK, ev_min_waves<N>()) k_ev(const uint32
         const uint32_t start = chunk * per, end = min(boards, start + per), nt = end > start ? end - start : 0u;
         const uint32_t l = (nt + 63u) / 64u, s = start + lane * l;
         const uint32_t cnt = s < end ? min(l, end - s) : 0u;
-        // the pool: card j (canonical order) of the cards not dead, as its bit in the suit-lane layout
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (lane < 52u && ((avail >> lane) & 1ull))
-            mypool[PK_IDX(__popcll(avail & ((1ull << lane) - 1ull)), 64, "mypool")] = 4ull << (((lane & 3u) << 4) | (lane >> 2));
-        if (lane == EV_FROZEN) mypool[EV_FROZEN] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        eq_fill_wave_pool(mypool, avail, lane);
         // combination levels 0 .. 4 (ascending pool indices c0 < c1 < c2 < c3 < j), the first 5 - k of them frozen on the empty slot;
         // lim[t]: the highest index level t may still be raised FROM (-1: never)
         const int f = 5 - (int)k;
         const int lim0 = f <= 0 ? (int)P - 5 : -1, lim1 = f <= 1 ? (int)P - 4 : -1, lim2 = f <= 2 ? (int)P - 3 : -1, lim3 = f <= 3 ? (int)P - 2 : -1;
-        uint32_t c0 = EV_FROZEN, c1 = EV_FROZEN, c2 = EV_FROZEN, c3 = EV_FROZEN, j = EV_FROZEN;
+        uint32_t c0 = COMB_FROZEN, c1 = COMB_FROZEN, c2 = COMB_FROZEN, c3 = COMB_FROZEN, j = COMB_FROZEN;
         if (cnt) {     // unrank board index s (lexicographic): C(P - 1 - x, levels left) boards start with x at a level
             uint32_t r = s, x = 0;
             auto level = [&](auto jc) {
@@ -287,7 +273,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, ev_min_waves<N>()) k_ev(const uint32
                 else if ((int)c2 < lim2) { ++c2; c3 = c2 + 1; }
                 else if ((int)c1 < lim1) { ++c1; c2 = c1 + 1; c3 = c2 + 1; }
                 else if ((int)c0 < lim0) { ++c0; c1 = c0 + 1; c2 = c1 + 1; c3 = c2 + 1; }
-                else { c3 = EV_FROZEN - 1; }                                          // (past the spot's last board: never evaluated)
+                else { c3 = COMB_FROZEN - 1; }                                          // (past the spot's last board: never evaluated)
                 j = c3 + 1;
                 base = known | mypool[PK_IDX(c0, 64, "mypool") & 63u] | mypool[PK_IDX(c1, 64, "mypool") & 63u] | mypool[PK_IDX(c2, 64, "mypool") & 63u] | mypool[PK_IDX(c3, 64, "mypool") & 63u];
             }
@@ -336,7 +322,7 @@ __global__ void __launch_bounds__(EV_FINISH_BLOCK) k_ev_finish(EvWork W, double 
 namespace pk {
 
 size_t ev_task_cap(int N, size_t m, int lpt, int pool_max) {
-    return m * (((size_t)ev_binom((uint32_t)pool_max, 5) + 64 * (size_t)lpt - 1) / (64 * (size_t)lpt)) * (size_t)ev_groups_max(N);
+    return m * (((size_t)eq_binom((uint32_t)pool_max, 5) + 64 * (size_t)lpt - 1) / (64 * (size_t)lpt)) * (size_t)ev_groups_max(N);
 }
 
 size_t ev_layout(int N, size_t m, int lpt, int pool_max, bool own_share, char *base, EvWork *w) {
@@ -356,18 +342,12 @@ size_t ev_layout(int N, size_t m, int lpt, int pool_max, bool own_share, char *b
     return off;
 }
 
-#ifdef PK_ONLY_SEATS
-#define EV_SEAT_ENABLED(N) ((N) == (PK_ONLY_SEATS))
-#else
-#define EV_SEAT_ENABLED(N) 1
-#endif
-
 template <int N>
 static bool ev_dispatch(int n, hipStream_t stream, bool table, unsigned pgrid, const EvPrepArgs &a, unsigned grid, const uint32_t *tab) {
     if constexpr (N > PK_MAX_PLAYERS) return false;
     else {
         if (n == N) {
-            if constexpr (EV_SEAT_ENABLED(N)) {
+            if constexpr (EQ_SEAT_ENABLED(N)) {
                 if (table) hipLaunchKernelGGL((k_ev_prep<N, true>), dim3(pgrid), dim3(EV_PREP_BLOCK), 0, stream, a);
                 else hipLaunchKernelGGL((k_ev_prep<N, false>), dim3(pgrid), dim3(EV_PREP_BLOCK), 0, stream, a);
                 hipLaunchKernelGGL(k_ev<N>, dim3(grid), dim3(EQ_BLOCK), 0, stream, tab, a.w, a.lpt);

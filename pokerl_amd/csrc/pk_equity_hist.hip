@@ -23,8 +23,6 @@
 
 using namespace pk;
 
-constexpr uint32_t HIST_NONE = 63;            // pool slot that holds no card: a completion card that does not exist (k < 2)
-constexpr uint32_t HIST_SENT = 0xFFFFFFFFu;   // the key of a holding that is out of play on this completion: above every real key (24 bits)
 
 
 __global__ void __launch_bounds__(HIST_COUNTS_BLOCK) k_hist_counts(const uint64_t *__restrict__ desc, uint32_t *__restrict__ completions, size_t m) {
@@ -42,12 +40,12 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     __shared__ uint64_t slot[RVR_SLOTS];              // key << 11 | pool holding, sorted per completion; all ones = no holding
     __shared__ uint32_t pre[RVR_PREFIX];              // pre[i]: the weight of sorted positions 0 .. i - 1
-    __shared__ uint32_t keyw[RVR_POOL_HOLDINGS];      // this completion's key per pool holding (HIST_SENT: shares a card with the completion)
+    __shared__ uint32_t keyw[RVR_POOL_HOLDINGS];      // this completion's key per pool holding (RVR_SENT: shares a card with the completion)
     __shared__ uint16_t wp[RVR_POOL_HOLDINGS];        // the spot's weights per pool holding
     __shared__ uint64_t pool[64];                     // card j of the pool (canonical order) as its bit in the suit-lane layout
     __shared__ uint32_t canon[64];                    // ... and its canonical index
     __shared__ uint32_t wsum[RVR_WAVES];
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += RVR_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
+    stage_eval7_tab<RVR_BLOCK>(T, tab);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
     const uint32_t row_words = (uint32_t)RVR_HOLDINGS * nbins;                // u16 entries of one spot's rows: at most 42 432
     for (uint32_t spot = blockIdx.x; spot < m; spot += gridDim.x) {
@@ -63,12 +61,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
 #pragma unroll
         for (int j = 0; j < RVR_PER_LANE; ++j) voidc[j] = 0;
         if (boards) {                                 // (a refused spot: zeros)
-            if (tid < 52u && ((avail >> tid) & 1ull)) {
-                const uint32_t s = (uint32_t)__popcll(avail & ((1ull << tid) - 1ull));
-                pool[PK_IDX(s, 64, "pool")] = 4ull << (((tid & 3u) << 4) | (tid >> 2));
-                canon[PK_IDX(s, 64, "canon")] = tid;
-            }
-            if (tid == HIST_NONE) { pool[HIST_NONE] = 0; canon[HIST_NONE] = 0; }
+            fill_pool(pool, canon, avail, tid);
             __syncthreads();                          // (... and the zeros above are in place before any lane counts in its rows)
             const uint32_t nh = tri(P), nreal = tri(P - k);   // pool holdings; those a completion leaves in play
             uint32_t npad = 64;
@@ -80,7 +73,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
 #pragma unroll
             for (int j = 0; j < RVR_PER_LANE; ++j) {
                 const uint32_t ph = tid + (uint32_t)j * RVR_BLOCK;
-                ea[j] = HIST_NONE; eb[j] = HIST_NONE; ebits[j] = 0;
+                ea[j] = RVR_NONE; eb[j] = RVR_NONE; ebits[j] = 0;
                 if (ph < nh) {
                     unpair(ph, ea[j], eb[j]);
                     ebits[j] = pool[PK_IDX(ea[j], 64, "pool")] | pool[PK_IDX(eb[j], 64, "pool")];
@@ -107,7 +100,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
             const uint32_t ncomp = binom2(P, k);
             uint32_t ci = 0, cj = 1;
             for (uint32_t c = 0; c < ncomp; ++c) {
-                const uint32_t x0 = k == 2u ? ci : (k == 1u ? c : HIST_NONE), x1 = k == 2u ? cj : HIST_NONE;
+                const uint32_t x0 = k == 2u ? ci : (k == 1u ? c : RVR_NONE), x1 = k == 2u ? cj : RVR_NONE;
                 const uint64_t board = known | pool[PK_IDX(x0, 64, "pool")] | pool[PK_IDX(x1, 64, "pool")];
                 // rank
 #pragma unroll
@@ -115,7 +108,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
                     const uint32_t ph = tid + (uint32_t)j * RVR_BLOCK;
                     if (ph < nh) {
                         const bool gone = ea[j] == x0 || ea[j] == x1 || eb[j] == x0 || eb[j] == x1;
-                        uint32_t key = HIST_SENT;
+                        uint32_t key = RVR_SENT;
                         if (!gone) key = order_key(eval7_tab_back(eval7_tab_front_bits(board | ebits[j], T), T));
                         keyw[PK_IDX(ph, RVR_POOL_HOLDINGS, "keyw")] = key;
                         slot[PK_IDX(ph, RVR_SLOTS, "slot")] = gone ? ~0ull : (((uint64_t)key << 11) | ph);
@@ -169,7 +162,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
                 for (int j = 0; j < RVR_PER_LANE; ++j) {
                     if (!hvalid[j]) continue;
                     const uint32_t kh = keyw[PK_IDX(hph[j], RVR_POOL_HOLDINGS, "keyw")];
-                    if (kh == HIST_SENT) continue;                                  // (h shares a card with this completion)
+                    if (kh == RVR_SENT) continue;                                  // (h shares a card with this completion)
                     uint32_t lb = 0, ub = 0;                                        // sorted positions with a key < kh, <= kh
                     for (uint32_t step = npad >> 1; step > 0; step >>= 1) {
                         const uint32_t kl = (uint32_t)(slot[PK_IDX(lb + step - 1u, RVR_SLOTS, "slot")] >> 11);
@@ -191,7 +184,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_hist(const uint32_t *__restric
                         const uint32_t k0 = keyw[p0], k1 = keyw[p1], w0 = wp[p0], w1 = wp[p1];   // (p0, p1: checked above)
                         below -= (k0 < kh ? w0 : 0u) + (k1 < kh ? w1 : 0u);
                         equal -= (k0 == kh ? w0 : 0u) + (k1 == kh ? w1 : 0u);
-                        den -= (k0 != HIST_SENT ? w0 : 0u) + (k1 != HIST_SENT ? w1 : 0u);
+                        den -= (k0 != RVR_SENT ? w0 : 0u) + (k1 != RVR_SENT ? w1 : 0u);
                     }
                     if (den == 0u) { ++voidc[j]; continue; }
                     // nbins (2 below + equal) <= 32 * 2 * 65 535 * 990 < 2^32; 2 below + equal <= 2 den, so the quotient is at most nbins

@@ -4,7 +4,8 @@
 // kernel (k_eqr_prep through pk::eqr_prep_launch: the same descriptor, the same status).  Two kernels here (k_hero_hist*, not k_hist_hero*:
 // the names that begin with k_hist are the public form's, and tests/test_hist_host.py counts them):
 //   k_hero_hist_counts  one lane per spot: completions = C(P, k) from the descriptor (0 for a refused spot);
-//   k_hero_hist         k_eqr's shape, COPIED (k_eqr itself is untouched): a persistent grid of 512-thread workgroups, the 32 KB rank-mask table
+//   k_hero_hist         k_eqr's shape, and its hero and villain passes themselves (pk_equity_range.hpp: eqr_hero_pass, eqr_villain_pass with another
+//                       callable): a persistent grid of 512-thread workgroups, the 32 KB rank-mask table
 //                       of eval7_tab in LDS (staged once per workgroup), ONE SPOT PER WORKGROUP at a time, spots dealt round robin.  Per spot:
 //                         weights       the spot's weight vector into LDS in the fixed 1 326 index space, 0 at the holdings that are not valid;
 //                                       on the way the weight of the holdings that hold each card, W[card] (LDS atomics, 2 per holding);
@@ -30,7 +31,6 @@
 
 using namespace pk;
 
-constexpr uint32_t HH_FROZEN = 63;   // pool slot that holds no card: the index of a combination level that does not exist (k < 2)
 constexpr int HH_CARDS = 52;
 static_assert(HH_MAX_BINS + 1 <= 64 && HH_CARDS + 1 <= 64, "one wave clears the counters");
 
@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(HH_BLOCK, 6) k_hero_hist(const uint32_t *__res
     __shared__ uint16_t wt[EQR_HOLDINGS];         // the spot's weights; 0 at a holding that is not valid
     __shared__ uint32_t wcard[64];                // [c < 52] the weight of the valid holdings that hold card c; [52] the weight of all of them
     __shared__ uint32_t cnt[64];                  // [b < nbins] the histogram, [nbins] void
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += HH_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
+    stage_eval7_tab<HH_BLOCK>(T, tab);
     for (int c = threadIdx.x; c < EQR_COMPLETIONS; c += HH_BLOCK) { below[PK_IDX(c, EQR_COMPLETIONS, "below")] = 0; equal[PK_IDX(c, EQR_COMPLETIONS, "equal")] = 0; }
     if (threadIdx.x < 64u) { wcard[threadIdx.x] = 0; cnt[threadIdx.x] = 0; }
     const uint32_t tid = threadIdx.x, wave = uniform(tid >> 6);
@@ -65,12 +65,7 @@ __global__ void __launch_bounds__(HH_BLOCK, 6) k_hero_hist(const uint32_t *__res
         const uint64_t known = uniform(d[0]), hero = uniform(d[1]), avail = uniform(d[2]), meta = uniform(d[3]);
         const uint32_t boards = (uint32_t)meta, k = (uint32_t)(meta >> 48) & 0xffu, P = (uint32_t)(meta >> 56);
         if (boards) {                             // (a refused spot: its counters stay zero)
-            if (tid < 52u && ((avail >> tid) & 1ull)) {
-                const uint32_t slot = (uint32_t)__popcll(avail & ((1ull << tid) - 1ull));
-                pool[PK_IDX(slot, 64, "pool")] = 4ull << (((tid & 3u) << 4) | (tid >> 2));
-                canon[PK_IDX(slot, 64, "canon")] = tid;
-            }
-            if (tid == HH_FROZEN) { pool[HH_FROZEN] = 0; canon[HH_FROZEN] = 0; }
+            fill_pool(pool, canon, avail, tid);
             // ---- weights: the fixed index space, 0 where a card of the holding is not in the pool; the per-card sums
             const uint16_t *wv = wts.w ? wts.w + (wts.per_spot ? (size_t)spot * EQR_HOLDINGS : 0) : nullptr;
             for (uint32_t h = tid; h < (uint32_t)EQR_HOLDINGS; h += HH_BLOCK) {
@@ -82,80 +77,21 @@ __global__ void __launch_bounds__(HH_BLOCK, 6) k_hero_hist(const uint32_t *__res
                 if (w) { atomicAdd(&wcard[PK_IDX(ca, HH_CARDS, "wcard")], w); atomicAdd(&wcard[PK_IDX(cb, HH_CARDS, "wcard")], w); }   // (at most 51 * 65 535 each)
             }
             __syncthreads();
-            // ---- hero pass: completion {i < j} at j (j - 1) / 2 + i, {i} at i, {} at 0
+            // ---- hero pass: the hero's word per completion; one wave adds the W[card] up
             const uint32_t ncomp = binom2(P, k);
-            for (uint32_t c = tid; c < ncomp; c += HH_BLOCK) {
-                uint64_t bits = known | hero;
-                if (k == 2u) { uint32_t ci, cj; unpair(c, ci, cj); bits |= pool[PK_IDX(ci, 64, "pool") & 63u] | pool[PK_IDX(cj, 64, "pool") & 63u]; }
-                else if (k == 1u) bits |= pool[PK_IDX(c, 64, "pool") & 63u];
-                hero_w[PK_IDX(c, EQR_COMPLETIONS, "hero_w")] = eval7_tab_back(eval7_tab_front_bits(bits, T), T);
-            }
+            eqr_hero_pass(T, pool, hero_w, known | hero, k, ncomp, tid);
             if (wave == HH_WAVES - 1) {           // every holding is in two cards' sums: total = half their sum, at most 65 535 * 1 326
                 const uint32_t c = tid & 63u;
                 const uint32_t s = wave_sum(c < (uint32_t)HH_CARDS ? wcard[c] : 0u);
                 if (c == 0u) wcard[HH_CARDS] = s >> 1;
             }
             __syncthreads();
-            // ---- villain pass: the sets S of s = k + 2 pool cards, lexicographic; this lane's [s0, s0 + cnt)
-            const uint32_t s = k + 2u;
-            const uint32_t nsets = s == 2u ? binom_c<2>(P) : (s == 3u ? binom_c<3>(P) : (uint32_t)((uint64_t)binom_c<3>(P) * (P - 3u) / 4u));
-            const uint32_t per = (nsets + HH_BLOCK - 1u) / HH_BLOCK, s0 = tid * per;
-            const uint32_t nmine = s0 < nsets ? min(per, nsets - s0) : 0u;
-            // combination levels 0 .. 3 (ascending pool indices c0 < c1 < c2 < j), the first f = 4 - s of them frozen on the empty slot;
-            // lim[t]: the highest index level t may still be raised FROM (-1: never)
-            const int f = 4 - (int)s;
-            const int lim0 = f <= 0 ? (int)P - 4 : -1, lim1 = f <= 1 ? (int)P - 3 : -1, lim2 = (int)P - 2;
-            uint32_t c0 = HH_FROZEN, c1 = HH_FROZEN, c2 = HH_FROZEN, j = HH_FROZEN;
-            if (nmine) {   // unrank set index s0: C(P - 1 - x, levels left) sets start with x at a level
-                uint32_t r = s0, x = 0;
-                auto level = [&](auto jc) {
-                    constexpr int J = decltype(jc)::value;
-                    while (x < P) {
-                        const uint32_t c = binom_c<J>(P - 1u - x);
-                        if (r < c) break;
-                        r -= c; ++x;
-                    }
-                    return x++;
-                };
-                if (f <= 0) c0 = level(std::integral_constant<int, 3>{});
-                if (f <= 1) c1 = level(std::integral_constant<int, 2>{});
-                c2 = level(std::integral_constant<int, 1>{});
-                j = x + r;
-            }
-            uint64_t base = known | pool[PK_IDX(c0, 64, "pool") & 63u] | pool[PK_IDX(c1, 64, "pool") & 63u] | pool[PK_IDX(c2, 64, "pool") & 63u];
-            uint32_t n0 = canon[PK_IDX(c0, 64, "canon") & 63u], n1 = canon[PK_IDX(c1, 64, "canon") & 63u], n2 = canon[PK_IDX(c2, 64, "canon") & 63u];
-            for (uint32_t n = 0; n < nmine; ++n) {
-                const uint32_t nj = canon[PK_IDX(j, 64, "canon") & 63u];
-                const uint32_t vil = eval7_tab_back(eval7_tab_front_bits(base | pool[PK_IDX(j, 64, "pool") & 63u], T), T);
-                // one split: levels x < y are the villain's hole cards (canonical nx < ny), levels u < v the board to come
-                auto split = [&](int x, uint32_t nx, uint32_t ny, uint32_t lu, uint32_t lv) {
-                    if (x < f) return;                                                   // (uniform: a level that does not exist)
-                    const uint32_t comp = PK_IDX(k == 2u ? tri(lv) + lu : (k == 1u ? lv : 0u), EQR_COMPLETIONS, "completion");
-                    const uint32_t v[2] = {hero_w[comp], vil};
-                    int nw;
-                    const uint32_t win = compare_rankings<2>(v, nw);
-                    const uint32_t w = wt[PK_IDX(tri(ny) + nx, EQR_HOLDINGS, "holding")];
-                    if (win == 1u) atomicAdd(&below[comp], w);
-                    else if (win == 3u) atomicAdd(&equal[comp], w);
-                };
-                split(0, n0, n1, c2, j);
-                split(0, n0, n2, c1, j);
-                split(0, n0, nj, c1, c2);
-                split(1, n1, n2, c0, j);
-                split(1, n1, nj, c0, c2);
-                split(2, n2, nj, c0, c1);
-                // next set: the last card moves on; when it runs out, the deepest level that can still rise does, and the ones after it follow
-                ++j;
-                if (j >= P) {
-                    if ((int)c2 < lim2) { ++c2; }
-                    else if ((int)c1 < lim1) { ++c1; c2 = c1 + 1; }
-                    else if ((int)c0 < lim0) { ++c0; c1 = c0 + 1; c2 = c1 + 1; }
-                    else { c2 = HH_FROZEN - 1; }                                         // (past the spot's last set: never evaluated)
-                    j = c2 + 1;
-                    base = known | pool[PK_IDX(c0, 64, "pool") & 63u] | pool[PK_IDX(c1, 64, "pool") & 63u] | pool[PK_IDX(c2, 64, "pool") & 63u];
-                    n0 = canon[PK_IDX(c0, 64, "canon") & 63u]; n1 = canon[PK_IDX(c1, 64, "canon") & 63u]; n2 = canon[PK_IDX(c2, 64, "canon") & 63u];
-                }
-            }
+            // ---- villain pass: a split adds its HOLDING's weight to the counters of its COMPLETION
+            eqr_villain_pass(T, pool, canon, hero_w, known, k, P, tid, [&](uint32_t comp, uint32_t h, uint32_t win) {
+                const uint32_t w = wt[h];
+                if (win == 1u) atomicAdd(&below[comp], w);
+                else if (win == 3u) atomicAdd(&equal[comp], w);
+            });
             __syncthreads();
             // ---- bin pass: one lane per completion; den = the weight of the valid holdings that share no card with it
             const uint32_t total = wcard[HH_CARDS];

@@ -13,6 +13,7 @@
 //                                once, then stepped), evaluate board | S ONCE, and for each of the C(k + 2, 2) splits look the hero's word of
 //                                that completion up, decide with compare_rankings<2> and add to the LDS counters of that split's holding
 //                                (two u32 per holding in the fixed 1 326 index space, LDS atomics).  One loop serves nb = 3, 4, 5;
+//                                The two passes are functions of pk_equity_range.hpp, shared with k_hero_hist (pk_equity_hist_hero.hip);
 //                  output        all 1 326 win / tie entries from LDS, coalesced, zeros included (no memset); the weighted sums reduced
 //                                over the workgroup in 64 bits and written by one lane; the counters cleared for the next spot.
 // Ordinary vector stores and LDS atomics only; no scratch memory (tests/test_equity_range_host.py reads the code objects).
@@ -24,7 +25,6 @@
 using namespace pk;
 
 #define EQR_PREP_BLOCK 256
-constexpr uint32_t EQR_FROZEN = 63;   // pool slot that holds no card: the index of a combination level that does not exist (k < 2)
 
 struct EqrPrepArgs {
     EqrSpots s;
@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
     __shared__ uint32_t hero_w[EQR_COMPLETIONS];  // the hero's ranking word per completion of the board
     __shared__ uint32_t cwin[EQR_HOLDINGS], ctie[EQR_HOLDINGS];
     __shared__ uint64_t red[EQR_WAVES][3];
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQR_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
+    stage_eval7_tab<EQR_BLOCK>(T, tab);
     for (int h = threadIdx.x; h < EQR_HOLDINGS; h += EQR_BLOCK) { cwin[PK_IDX(h, EQR_HOLDINGS, "cwin")] = 0; ctie[PK_IDX(h, EQR_HOLDINGS, "ctie")] = 0; }
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
     for (uint32_t spot = blockIdx.x; spot < m; spot += gridDim.x) {
@@ -113,82 +113,15 @@ __global__ void __launch_bounds__(EQR_BLOCK, 6) k_eqr(const uint32_t *__restrict
         const uint64_t known = uniform(d[0]), hero = uniform(d[1]), avail = uniform(d[2]), meta = uniform(d[3]);
         const uint32_t boards = (uint32_t)meta, k = (uint32_t)(meta >> 48) & 0xffu, P = (uint32_t)(meta >> 56);
         if (boards) {                             // (a refused spot: its counters stay zero)
-            if (tid < 52u && ((avail >> tid) & 1ull)) {
-                const uint32_t slot = (uint32_t)__popcll(avail & ((1ull << tid) - 1ull));
-                pool[PK_IDX(slot, 64, "pool")] = 4ull << (((tid & 3u) << 4) | (tid >> 2));
-                canon[PK_IDX(slot, 64, "canon")] = tid;
-            }
-            if (tid == EQR_FROZEN) { pool[EQR_FROZEN] = 0; canon[EQR_FROZEN] = 0; }
+            fill_pool(pool, canon, avail, tid);
             __syncthreads();
-            // ---- hero pass: completion {i < j} at j (j - 1) / 2 + i, {i} at i, {} at 0
-            const uint32_t ncomp = binom2(P, k);
-            for (uint32_t c = tid; c < ncomp; c += EQR_BLOCK) {
-                uint64_t bits = known | hero;
-                if (k == 2u) { uint32_t ci, cj; unpair(c, ci, cj); bits |= pool[PK_IDX(ci, 64, "pool") & 63u] | pool[PK_IDX(cj, 64, "pool") & 63u]; }
-                else if (k == 1u) bits |= pool[PK_IDX(c, 64, "pool") & 63u];
-                hero_w[PK_IDX(c, EQR_COMPLETIONS, "hero_w")] = eval7_tab_back(eval7_tab_front_bits(bits, T), T);
-            }
+            eqr_hero_pass(T, pool, hero_w, known | hero, k, binom2(P, k), tid);
             __syncthreads();
-            // ---- villain pass: the sets S of s = k + 2 pool cards, lexicographic; this lane's [s0, s0 + cnt)
-            const uint32_t s = k + 2u;
-            const uint32_t nsets = s == 2u ? binom_c<2>(P) : (s == 3u ? binom_c<3>(P) : (uint32_t)((uint64_t)binom_c<3>(P) * (P - 3u) / 4u));
-            const uint32_t per = (nsets + EQR_BLOCK - 1u) / EQR_BLOCK, s0 = tid * per;
-            const uint32_t cnt = s0 < nsets ? min(per, nsets - s0) : 0u;
-            // combination levels 0 .. 3 (ascending pool indices c0 < c1 < c2 < j), the first f = 4 - s of them frozen on the empty slot;
-            // lim[t]: the highest index level t may still be raised FROM (-1: never)
-            const int f = 4 - (int)s;
-            const int lim0 = f <= 0 ? (int)P - 4 : -1, lim1 = f <= 1 ? (int)P - 3 : -1, lim2 = (int)P - 2;
-            uint32_t c0 = EQR_FROZEN, c1 = EQR_FROZEN, c2 = EQR_FROZEN, j = EQR_FROZEN;
-            if (cnt) {     // unrank set index s0: C(P - 1 - x, levels left) sets start with x at a level
-                uint32_t r = s0, x = 0;
-                auto level = [&](auto jc) {
-                    constexpr int J = decltype(jc)::value;
-                    while (x < P) {
-                        const uint32_t c = binom_c<J>(P - 1u - x);
-                        if (r < c) break;
-                        r -= c; ++x;
-                    }
-                    return x++;
-                };
-                if (f <= 0) c0 = level(std::integral_constant<int, 3>{});
-                if (f <= 1) c1 = level(std::integral_constant<int, 2>{});
-                c2 = level(std::integral_constant<int, 1>{});
-                j = x + r;
-            }
-            uint64_t base = known | pool[PK_IDX(c0, 64, "pool") & 63u] | pool[PK_IDX(c1, 64, "pool") & 63u] | pool[PK_IDX(c2, 64, "pool") & 63u];
-            uint32_t n0 = canon[PK_IDX(c0, 64, "canon") & 63u], n1 = canon[PK_IDX(c1, 64, "canon") & 63u], n2 = canon[PK_IDX(c2, 64, "canon") & 63u];
-            for (uint32_t n = 0; n < cnt; ++n) {
-                const uint32_t nj = canon[PK_IDX(j, 64, "canon") & 63u];
-                const uint32_t vil = eval7_tab_back(eval7_tab_front_bits(base | pool[PK_IDX(j, 64, "pool") & 63u], T), T);
-                // one split: levels x < y are the villain's hole cards (canonical nx < ny), levels u < v the board to come
-                auto split = [&](int x, uint32_t nx, uint32_t ny, uint32_t lu, uint32_t lv) {
-                    if (x < f) return;                                                   // (uniform: a level that does not exist)
-                    const uint32_t comp = k == 2u ? tri(lv) + lu : (k == 1u ? lv : 0u);
-                    const uint32_t v[2] = {hero_w[PK_IDX(comp, EQR_COMPLETIONS, "hero_w")], vil};
-                    int nw;
-                    const uint32_t win = compare_rankings<2>(v, nw);
-                    const uint32_t h = PK_IDX(tri(ny) + nx, EQR_HOLDINGS, "holding");
-                    if (win == 1u) atomicAdd(&cwin[h], 1u);
-                    else if (win == 3u) atomicAdd(&ctie[h], 1u);
-                };
-                split(0, n0, n1, c2, j);
-                split(0, n0, n2, c1, j);
-                split(0, n0, nj, c1, c2);
-                split(1, n1, n2, c0, j);
-                split(1, n1, nj, c0, c2);
-                split(2, n2, nj, c0, c1);
-                // next set: the last card moves on; when it runs out, the deepest level that can still rise does, and the ones after it follow
-                ++j;
-                if (j >= P) {
-                    if ((int)c2 < lim2) { ++c2; }
-                    else if ((int)c1 < lim1) { ++c1; c2 = c1 + 1; }
-                    else if ((int)c0 < lim0) { ++c0; c1 = c0 + 1; c2 = c1 + 1; }
-                    else { c2 = EQR_FROZEN - 1; }                                        // (past the spot's last set: never evaluated)
-                    j = c2 + 1;
-                    base = known | pool[PK_IDX(c0, 64, "pool") & 63u] | pool[PK_IDX(c1, 64, "pool") & 63u] | pool[PK_IDX(c2, 64, "pool") & 63u];
-                    n0 = canon[PK_IDX(c0, 64, "canon") & 63u]; n1 = canon[PK_IDX(c1, 64, "canon") & 63u]; n2 = canon[PK_IDX(c2, 64, "canon") & 63u];
-                }
-            }
+            // the villain pass: a split counts for its holding
+            eqr_villain_pass(T, pool, canon, hero_w, known, k, P, tid, [&](uint32_t, uint32_t h, uint32_t win) {
+                if (win == 1u) atomicAdd(&cwin[h], 1u);
+                else if (win == 3u) atomicAdd(&ctie[h], 1u);
+            });
             __syncthreads();
         }
         // ---- output: every holding's counters (zeros included), the weighted sums, and the counters cleared for the next spot

@@ -179,7 +179,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqw_min_waves<N>()) k_eqw(const uint
     __shared__ uint32_t CUM[CUM_WORDS];
     __shared__ uint16_t HC[EQW_HOLDINGS];                             // holding h -> its cards' canonical indices a | b << 8
     __shared__ uint32_t wt[32];
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQ_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
+    stage_eval7_tab<EQ_BLOCK>(T, tab);
     if constexpr (RC > 0) {
         const uint32_t words = (R < (uint32_t)RC ? R : (uint32_t)RC) * EQW_HOLDINGS;
         for (uint32_t i = threadIdx.x; i < words; i += EQ_BLOCK) CUM[PK_IDX(i, CUM_WORDS, "CUM")] = cum[i];
@@ -189,7 +189,7 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqw_min_waves<N>()) k_eqw(const uint
         while (b * (b + 1u) / 2u <= h) ++b;
         HC[PK_IDX(h, EQW_HOLDINGS, "HC")] = (uint16_t)((h - b * (b - 1u) / 2u) | (b << 8));
     }
-    if (threadIdx.x < 32) wt[PK_IDX(threadIdx.x, 32, "wt")] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
+    fill_share_weights(wt);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, wave = uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
     const uint32_t S = rng.samples;
@@ -315,19 +315,13 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqw_min_waves<N>()) k_eqw(const uint
 
 namespace pk {
 
-#ifdef PK_ONLY_SEATS
-#define EQW_SEAT_ENABLED(N) ((N) == (PK_ONLY_SEATS))
-#else
-#define EQW_SEAT_ENABLED(N) 1
-#endif
-
 template <int N, int RC>
 static bool eqw_dispatch(int n, hipStream_t stream, unsigned grid, const uint32_t *tab, const uint32_t *cum, const uint64_t *desc, const EqwOut &out,
                          const EqsStream &rng, uint32_t R, uint32_t ntasks, uint32_t nch, uint32_t per) {
     if constexpr (N > PK_MAX_PLAYERS) return false;
     else {
         if (n == N) {
-            if constexpr (EQW_SEAT_ENABLED(N)) {
+            if constexpr (EQ_SEAT_ENABLED(N)) {
                 hipLaunchKernelGGL((k_eqw<N, RC>), dim3(grid), dim3(EQ_BLOCK), 0, stream, tab, cum, desc, out, rng, R, ntasks, nch, per);
                 return true;
             } else return false;

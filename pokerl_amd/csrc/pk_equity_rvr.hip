@@ -24,8 +24,6 @@
 using namespace pk;
 
 #define RVR_PREP_BLOCK 256
-constexpr uint32_t RVR_NONE = 63;             // pool slot that holds no card: a completion card that does not exist (k < 2)
-constexpr uint32_t RVR_SENT = 0xFFFFFFFFu;    // the key of a holding that is out of play on this completion: above every real key (24 bits)
 
 struct RvrPrepArgs {
     RvrSpots s;
@@ -97,7 +95,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
     __shared__ uint64_t pool[64];                     // card j of the pool (canonical order) as its bit in the suit-lane layout
     __shared__ uint32_t canon[64];                    // ... and its canonical index
     __shared__ uint32_t wsum[RVR_WAVES];
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += RVR_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
+    stage_eval7_tab<RVR_BLOCK>(T, tab);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
     for (uint32_t spot = blockIdx.x; spot < m; spot += gridDim.x) {
         __syncthreads();                              // (the table; the spot before: its pool, weights, keys and sums are done with)
@@ -108,12 +106,7 @@ __global__ void __launch_bounds__(RVR_BLOCK, 4) k_rvr(const uint32_t *__restrict
 #pragma unroll
         for (int j = 0; j < RVR_PER_LANE; ++j) { win[j] = 0; tie[j] = 0; tot[j] = 0; }
         if (boards) {                                 // (a refused spot: zeros)
-            if (tid < 52u && ((avail >> tid) & 1ull)) {
-                const uint32_t s = (uint32_t)__popcll(avail & ((1ull << tid) - 1ull));
-                pool[PK_IDX(s, 64, "pool")] = 4ull << (((tid & 3u) << 4) | (tid >> 2));
-                canon[PK_IDX(s, 64, "canon")] = tid;
-            }
-            if (tid == RVR_NONE) { pool[RVR_NONE] = 0; canon[RVR_NONE] = 0; }
+            fill_pool(pool, canon, avail, tid);
             __syncthreads();
             const uint32_t nh = tri(P), nreal = tri(P - k);   // pool holdings; those a completion leaves in play
             uint32_t npad = 64;

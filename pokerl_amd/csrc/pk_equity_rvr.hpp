@@ -39,6 +39,11 @@ struct RvrWeights {
     int per_spot;            // 0: one vector [1326] for the call, 1: [m][1326]
 };
 
+// What the two kernels of this spot (k_rvr, and k_hist of pk_equity_hist.hip) both name:
+constexpr uint32_t RVR_NONE = 63;             // pool slot that holds no card: a completion card that does not exist (k < 2)
+constexpr uint32_t RVR_SENT = 0xFFFFFFFFu;    // the key of a holding that is out of play on this completion: above every real key (24 bits)
+static_assert(RVR_NONE == COMB_FROZEN, "pk::fill_pool empties that slot");
+
 // Queues the whole call on `stream`: descriptors + boards / status (one lane per spot), then -- where win, tie or tot is wanted -- the
 // persistent kernel.  tab: the evaluator table (eval7_table); `tables` non-NULL selects the table form.
 hipError_t rvr_launch(hipStream_t stream, const uint32_t *tab, const RvrSpots *spots, const EqTables *tables, const RvrWeights &weights, size_t m,

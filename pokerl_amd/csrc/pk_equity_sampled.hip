@@ -115,8 +115,8 @@ __global__ void __launch_bounds__(EQ_BLOCK, eqs_min_waves<N>()) k_eqs(const uint
                                                                      EqsStream rng, uint32_t ntasks, uint32_t nch, uint32_t per) {
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     __shared__ uint32_t wt[32];
-    for (int i = threadIdx.x; i < EVAL7_TAB_WORDS / 4; i += EQ_BLOCK) reinterpret_cast<uint4 *>(T)[PK_IDX(i, EVAL7_TAB_WORDS / 4, "T")] = reinterpret_cast<const uint4 *>(tab)[i];
-    if (threadIdx.x < 32) wt[PK_IDX(threadIdx.x, 32, "wt")] = (threadIdx.x >= 1 && threadIdx.x <= 16) ? EQ_SHARE_UNIT / threadIdx.x : 0u;
+    stage_eval7_tab<EQ_BLOCK>(T, tab);
+    fill_share_weights(wt);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u, wave = uniform(threadIdx.x >> 6), nwaves = gridDim.x * EQ_WAVES;
     const uint32_t S = rng.samples;
@@ -217,19 +217,13 @@ int eqs_lpt(size_t m, uint32_t samples) {
     return (int)(lpt < (uint64_t)EQS_LPT_MIN ? (uint64_t)EQS_LPT_MIN : (lpt > (uint64_t)EQS_LPT_MAX ? (uint64_t)EQS_LPT_MAX : lpt));
 }
 
-#ifdef PK_ONLY_SEATS
-#define EQS_SEAT_ENABLED(N) ((N) == (PK_ONLY_SEATS))
-#else
-#define EQS_SEAT_ENABLED(N) 1
-#endif
-
 template <int N>
 static bool eqs_dispatch(int n, hipStream_t stream, unsigned grid, const uint32_t *tab, const uint64_t *desc, const EqsOut &out, const EqsStream &rng,
                          uint32_t ntasks, uint32_t nch, uint32_t per) {
     if constexpr (N > PK_MAX_PLAYERS) return false;
     else {
         if (n == N) {
-            if constexpr (EQS_SEAT_ENABLED(N)) {
+            if constexpr (EQ_SEAT_ENABLED(N)) {
                 hipLaunchKernelGGL(k_eqs<N>, dim3(grid), dim3(EQ_BLOCK), 0, stream, tab, desc, out, rng, ntasks, nch, per);
                 return true;
             } else return false;

@@ -9,7 +9,7 @@ before: host-enumerated 7-card hands of ALL the leg's tables through pk_eval7_d 
 evaluator's DEVICE time is set against the new call (host enumeration, every copy and the whole comparison pass excluded: flattering the
 old way); the comparison pass is timed separately on `--old-tables` tables as the host call a caller has, copies included.
 
-    python tools/equity_bench.py [--samples 5] [--skip-1m]
+    python tools/equity_bench.py [--samples 5] [--skip-1m] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -18,7 +18,8 @@ import json
 import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import pokerl_amd  # noqa: E402
 from pokerl_amd import _lib as L  # noqa: E402
@@ -117,6 +118,7 @@ def main():
     ap.add_argument("--samples", type=int, default=5)
     ap.add_argument("--old-tables", type=int, default=1024)
     ap.add_argument("--skip-1m", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "equity_bench.json"))
     args = ap.parse_args()
     if pokerl_amd.device_count() < 1:
         sys.exit("equity_bench: no MI355X visible (no fallback)")
@@ -193,7 +195,10 @@ def main():
             b.free()
         g.close()
     hip.hipStreamDestroy(stream)
-    print(json.dumps(res))
+    line = json.dumps(res)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@ call by call in one process, with pk_equity_d / pk_table_equity_d on the same sp
 call makes one per pot level.  Per leg: microseconds per call of both (HIP events on the call's stream, every shape warmed up, median of
 `--samples`, the samples kept), their ratio, and the levels per spot (existing / compared).  No threshold: the ratio is a finding.
 
-    python tools/equity_ev_bench.py [--samples 5]
+    python tools/equity_ev_bench.py [--samples 5] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -13,7 +13,8 @@ import json
 import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import pokerl_amd  # noqa: E402
 from pokerl_amd import _lib as L  # noqa: E402
@@ -64,6 +65,7 @@ def leg(ev, eq, level_seat, amount, boards, live):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "equity_ev_bench.json"))
     args = ap.parse_args()
     if pokerl_amd.device_count() < 1:
         sys.exit("equity_ev_bench: no MI355X visible (no fallback)")
@@ -121,7 +123,10 @@ def main():
         b.free()
     g.close()
     hip.hipStreamDestroy(stream)
-    print(json.dumps(res))
+    line = json.dumps(res)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
 
 
 if __name__ == "__main__":

@@ -697,6 +697,26 @@ __device__ __forceinline__ uint32_t lane_read(uint32_t v, int lane) { return (ui
 __device__ __forceinline__ uint64_t lane_read64(uint64_t v, int lane) { return (uint64_t)lane_read((uint32_t)v, lane) | ((uint64_t)lane_read((uint32_t)(v >> 32), lane) << 32); }
 __device__ __forceinline__ bool wave_uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }   // b holds the same value in every lane
 #endif
+// Exclusive prefix sum of x over the lanes of the wave (lane l: the sum of x over the lanes below l) and the wave's total.  Wave-uniform control
+// flow, every lane active.  Six v_add_u32 with a DPP operand: a Hillis-Steele scan inside each row of 16 lanes (row_shr:1 / 2 / 4 / 8, zeros
+// shifted in), then lane 15 of rows 0 and 2 into rows 1 and 3 (row_bcast:15), then lane 31 into rows 2 and 3 (row_bcast:31).
+__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t x, uint32_t &total) {
+#if PK_WAVE >= 16
+    static_assert(PK_WAVE == 64, "four rows of 16 lanes");
+    int s = (int)x;
+    s += __builtin_amdgcn_update_dpp(0, s, 0x111, 0xf, 0xf, true);     // row_shr:1
+    s += __builtin_amdgcn_update_dpp(0, s, 0x112, 0xf, 0xf, true);     // row_shr:2
+    s += __builtin_amdgcn_update_dpp(0, s, 0x114, 0xf, 0xf, true);     // row_shr:4
+    s += __builtin_amdgcn_update_dpp(0, s, 0x118, 0xf, 0xf, true);     // row_shr:8
+    s += __builtin_amdgcn_update_dpp(0, s, 0x142, 0xa, 0xf, false);    // row_bcast:15 row_mask:0xa
+    s += __builtin_amdgcn_update_dpp(0, s, 0x143, 0xc, 0xf, false);    // row_bcast:31 row_mask:0xc
+    total = lane_read((uint32_t)s, PK_WAVE - 1);
+    return (uint32_t)s - x;
+#else
+    total = x;
+    return 0u;
+#endif
+}
 
 // Diagnostic build only (-DPK_PROFILE, libpokerl_hip_prof.so; never the shipped library): per-wave cycle stamps
 // (s_memtime) around the blocks of the step machine, summed into State::prof.  Shares, not run times, are read from it.
@@ -851,12 +871,12 @@ struct ActionRing {
         }
     }
     template <typename LDS>
-    __device__ __forceinline__ static uint32_t peek(const LDS &lds, uint64_t step_serial) {
-        const uint32_t s = (uint32_t)step_serial;
+    __device__ __forceinline__ static uint32_t peek(const LDS &lds, uint32_t step_serial) {   // (the serial's low word: a 64-bit parameter had its
+        const uint32_t s = step_serial;                                                          //  bit 0 tested with a 64-bit compare)
         return lds.act[((s >> 3) & 1) * 4 + ((s & 7) >> 1)][threadIdx.x & (PK_WAVE - 1)];
     }
-    __device__ __forceinline__ static uint32_t half_of(uint32_t word, uint64_t step_serial) {
-        return ((uint32_t)step_serial & 1) ? (word >> 16) : (word & 0xffffu);
+    __device__ __forceinline__ static uint32_t half_of(uint32_t word, uint32_t step_serial) {
+        return (step_serial & 1) ? (word >> 16) : (word & 0xffffu);
     }
 };
 // The same through the workgroup's LDS table (k_rollout): one byte read instead of a six-step select chain.
@@ -1173,6 +1193,9 @@ struct Table {
 
     // Game.step up to the call of next_player (game.py:656-699) for an action already checked against the mask.
     // Branch-free: every lane of the wave takes a different action, so the three arms are merged into selects.
+    // MONEY_IN_SEAT: `pending[a] = bet` compares the seats with a seat index that is -1 where no money moves -- one select in place of a lane-mask
+    // AND per seat.  For rollout_body's kernels (k_rollout_tab<6> +0.6 %); the PokerGameEnv kernels keep the ANDs (synchronous env.step -1.7 % with it).
+    template <bool MONEY_IN_SEAT = false>
     __device__ __forceinline__ void begin_step(const Hot &S, int action, double high_bet) {
         const int a = active;
         const uint32_t b = 1u << a;
@@ -1191,7 +1214,8 @@ struct Table {
         st_active &= ~b; st_called &= ~b; st_allin &= ~b; st_broken &= ~b;         // player_states[a] = ...
         st_allin |= (action == MV_ALL_IN) ? b : 0;                                 // :671
         st_called |= (action != MV_FOLD && action != MV_ALL_IN) ? b : 0;           // :660, :667 (FOLD: in no mask, :657)
-        PK_FOR(p, N) pending[p] = (money && p == a) ? bet_value : pending[p]; PK_END  // :696
+        const int a_m = (!MONEY_IN_SEAT || money) ? a : -1;
+        PK_FOR(p, N) pending[p] = ((MONEY_IN_SEAT || money) && p == a_m) ? bet_value : pending[p]; PK_END  // :696
         // next_player's entry (game.py:598-605,616-619)
         const bool many = __popc((st_active | st_called | st_allin) & FULL) > 1;
         current = a;
@@ -1339,13 +1363,12 @@ struct Table {
         }
 #endif
         // ---- showdown hands of all arriving lanes -> LDS queue -> one hand per lane (game.py:488-489)
+        // A lane's showdown seats take consecutive slots from the lane's base: ONE prefix sum over the lanes of popc(showdown), and per seat the
+        // seats below it (p is a compile-time constant).  The rankings come back through the same slots, so no result depends on the queue's order.
         uint32_t total = 0, my_base[N];
         if (!lone) {
-        PK_FOR(p, N)
-            unsigned long long bal = __ballot((showdown >> p) & 1);
-            my_base[p] = total + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-            total += (uint32_t)__popcll(bal);
-         PK_END
+            const uint32_t lane_base = wave_excl_scan((uint32_t)__popc(showdown), total);
+            PK_FOR(p, N) my_base[p] = lane_base + (uint32_t)__popc(showdown & ((1u << p) - 1u)); PK_END
         }
         if (lone) {
         } else if (total) {  // wave-uniform
@@ -1407,6 +1430,8 @@ struct Table {
         PK_FOR(p, N) pot_wb[p] = sd ? bets[p] : pot_wb[p]; PK_END                  // :485 (selects: one basic block)
         pot_todo = sd ? showdown : pot_todo;                                       // :495-496 argsort(bets) filtered, stable
         showed = showed || sd;
+        // (These three as plain assignments under the `if (sd)` below: five MORE instructions in k_rollout_tab<6>'s end_block, and k_rollout_occ3<7>
+        //  spills two registers to scratch memory -- docs/history.md, "Fewer issue slots per betting pass".)
         if (sd) { PK_FOR(p, N) lds.show[p][PK_IDX(lane, 64, "lds.show")] = pot_hv[p]; PK_END }             // (an unconditional write to a scratch row: slower)
         // ---- the side-pot loop (:498-525) for the arriving showdowns and the ones still in it: per call ONE pass of
         //      the general body plus, if that leaves a single potential winner, the closing pass of :500-505.

@@ -184,8 +184,9 @@ __device__ __forceinline__ void rollout_body(const State *__restrict__ Sp, const
     constexpr bool EXTERNAL = POLICY == PK_POLICY_EXTERNAL;
     constexpr bool PAY = PASSES != 1;        // the single-step kernels (k_step, k_rollout_single) move the payoffs only where a hand ended
     if (live) { tb.template load<PAY>(S, t); tb.hands_this_step = (int)as_global(S.mid)[t]; owed = as_global(S.owed)[t] + (uint32_t)K; } else tb.blank();
-    uint32_t steps = 0;
-    bool alive = live;
+    // No `alive` predicate and no step counter in the loop: a lane that can make no further step owes nothing (owed == 0: a lane without a
+    // table, a refused action, a table `retire` found in error), so `owed > 0` is the whole test; and the good retirements of a launch are
+    // (owed at load + K) - (owed at exit), reconstructed in the epilogue from `owed_base`, which a table in error corrects where it zeroes `owed`.
     ActionRing ring;
     double high_bet;
     int ext_action = -1;
@@ -198,7 +199,6 @@ __device__ __forceinline__ void rollout_body(const State *__restrict__ Sp, const
         const bool carried = BOUNDED && live && tb.stepped;                        // a step of an earlier launch is in flight: its action was taken then
         ext_ok = carried || (live && ext_action >= 0 && ext_action < PK_NUM_MOVES && ((vm >> ext_action) & 1));
         owed = ext_ok ? 1u : 0u;                                                   // (the host has flushed: nothing was owed)
-        alive = ext_ok;
     }
     int nend = 0;
     uint32_t late = (live ? 1u : 0u) | (ext_ok ? 2u : 0u);   // the epilogue's lane predicates travel through the loop in ONE VGPR
@@ -208,17 +208,18 @@ __device__ __forceinline__ void rollout_body(const State *__restrict__ Sp, const
     const int cap = __popcll(__ballot(live && (owed > 0 || tb.lstate == LS_END)));
     const int quit = max(1, cap - slack);
     PK_PROF(tb.prof.start();)
-    auto retire = [&]() {  // a lane whose Game.step() has returned (selects, not branches: nearly every lane, every pass)
-        const bool r = tb.stepped && tb.lstate == LS_DONE;
-        const bool bad = r && tb.terr != 0;            // table keeps its (reference-identical) state; reported through terr
-        const bool good = r && tb.terr == 0;
-        tb.step_serial += (r && !(tb.terr & PK_TERR_NO_WINNER)) ? 1u : 0u;   // finish_step()
-        tb.stepped = r ? 0u : tb.stepped;
-        owed = bad ? 0u : owed - (r ? 1u : 0u);
-        alive = alive && !bad;
-        steps += good ? 1u : 0u;
-        tb.games += good ? (tb.flags & PK_FLAG_GAME_OVER) : 0u;
-    };
+    uint32_t owed_base = owed;
+    static_assert(PK_TERR_NO_WINNER == 2 && PK_FLAG_GAME_OVER == 1, "retire()'s bit arithmetic");
+    auto retire = [&]() {  // a lane whose Game.step() has returned (nearly every lane, every pass): the predicates travel as 0 / 1 VALUES that are
+                           // added, not as lane masks that are ANDed and then selected on (two mask operations here; there were seven)
+        const uint32_t r = tb.lstate == LS_DONE ? tb.stepped : 0u;      // (stepped is 0 or 1)
+        const uint32_t good = tb.terr == 0 ? r : 0u;
+        tb.step_serial += r & ~(tb.terr >> 1);                          // finish_step(): not after PK_TERR_NO_WINNER
+        tb.stepped -= r;
+        owed -= r;
+        tb.games += good & tb.flags;
+        if (r != good) { owed_base -= owed + 1u; owed = 0u; }           // in error (rare): the table keeps its (reference-identical) state, reported through
+    };                                                                  // terr, and owes nothing more; its count of good steps freezes here
 // Which of the betting passes also run cursor_tail() (next_turn for the lanes whose seat walk failed: ~75 instructions for
 // ~1 lane in 5).  Every other pass: the block runs half as often over twice the lanes, a lane waits at most one pass
 // (29.7 vs 28.6 G at 65 536 x 6; last pass only 28.7, passes 0+3 29.1, six passes with three tails 29.2).  The LAST
@@ -235,20 +236,20 @@ __device__ __forceinline__ void rollout_body(const State *__restrict__ Sp, const
         // conditionally executed blocks), and parks a full s_waitcnt right behind the first LDS read of every betting
         // pass: the action ring's latency was exposed three passes out of four.
         if (policy == PK_POLICY_RANDOM) __builtin_amdgcn_s_waitcnt(0);   // (the all-in kernel has no LDS read in its passes)
-        if constexpr (policy == PK_POLICY_RANDOM) ring.ensure(lds, H, table_id, tb.step_serial, alive && owed > 0, NPASS);   // wave-uniform
+        if constexpr (policy == PK_POLICY_RANDOM) ring.ensure(lds, H, table_id, tb.step_serial, owed > 0, NPASS);   // wave-uniform
 #pragma unroll
         for (int pass = 0; pass < NPASS; ++pass) {
-            const bool go = alive && tb.lstate == LS_DONE && owed > 0;
+            const bool go = tb.lstate == LS_DONE && owed > 0;
             uint32_t word = 0;
-            if constexpr (policy == PK_POLICY_RANDOM) word = ActionRing::peek(lds, tb.step_serial);
+            if constexpr (policy == PK_POLICY_RANDOM) word = ActionRing::peek(lds, (uint32_t)tb.step_serial);
             if (go) {
                 uint32_t mask = tb.valid_mask(high_bet);
                 int act;
                 if constexpr (EXTERNAL) act = ext_action;
                 else if constexpr (policy == PK_POLICY_ALLIN) act = (int)MV_ALL_IN;
                 else if constexpr (policy == PK_POLICY_CALL) act = call_action(mask);
-                else act = action_from_draw_lds(lds, ActionRing::half_of(word, tb.step_serial), mask);
-                tb.begin_step(H, act, high_bet);
+                else act = action_from_draw_lds(lds, ActionRing::half_of(word, (uint32_t)tb.step_serial), mask);
+                tb.template begin_step<true>(H, act, high_bet);
             }
             PK_PROF(tb.prof.lap(PF_ACTION);)
             tb.scan_first();      // every lane in LS_SCAN: the steps just begun and the ones end_block carried into a new hand
@@ -259,7 +260,7 @@ __device__ __forceinline__ void rollout_body(const State *__restrict__ Sp, const
         }
         // showdowns waiting in their side-pot loop (LS_POT) count towards `park` like arrivals (weights 0 and 1/2 measured no better)
         const int parked = __popcll(__ballot(tb.parked()));
-        const int runnable = __popcll(__ballot(alive && tb.lstate == LS_DONE && owed > 0));
+        const int runnable = __popcll(__ballot(tb.lstate == LS_DONE && owed > 0));
         if (parked + runnable < quit) break;
         if (parked >= park || runnable == 0) {
             if constexpr (BOUNDED) {   // the budget is used up: what is parked stays in flight -- unless a step is rolling hand after hand
@@ -318,7 +319,7 @@ __device__ __forceinline__ void rollout_body(const State *__restrict__ Sp, const
         const auto g_terr = as_global(S.terr);
         g_terr[t] = (uint8_t)((clear_terr ? 0 : g_terr[t]) | tb.terr | tb.seen);
     }
-    wave_add_counters(S, steps, tb.hands, tb.evals, tb.games);  // every lane takes part in the shuffles
+    wave_add_counters(S, owed_base - owed, tb.hands, tb.evals, tb.games);  // every lane takes part in the shuffles
     PK_PROF(tb.prof.flush(S.prof);)
 }
 
@@ -646,7 +647,7 @@ __device__ __forceinline__ void env_step_body() {
 #pragma unroll
         for (int pass = 0; pass < EP; ++pass) {
             const bool open = !(ASYNC && max_passes > 0 && passes + pass >= max_passes);
-            const uint32_t word = draws ? ActionRing::peek(lds, tb.step_serial) : 0u;
+            const uint32_t word = draws ? ActionRing::peek(lds, (uint32_t)tb.step_serial) : 0u;
             if (open && phase != PH_END && phase != PH_RESET && tb.lstate == LS_DONE && !yielded) {   // begin this lane's next Game.step()
                 const uint32_t vm = tb.valid_mask(high_bet);
                 // self.agents[active_player] (:25, :43, :51); seat 0's own step (:35) takes the caller's action when supplied
@@ -655,7 +656,7 @@ __device__ __forceinline__ void env_step_body() {
                 const bool begin = !supplied || phase == PH_SEAT0 || have_ext;     // an external seat without an action: yield
                 // every agent's move computed, then selected: as a chain of conditionals around the LDS lookup of the random
                 // agent's move the compiler made this four nested branches per pass
-                const int a_rand = draws ? action_from_draw_lds(lds, ActionRing::half_of(word, tb.step_serial), vm) : 0;
+                const int a_rand = draws ? action_from_draw_lds(lds, ActionRing::half_of(word, (uint32_t)tb.step_serial), vm) : 0;
                 const int a_call = call_action(vm);
                 int a = pol == PK_POLICY_ALLIN ? (int)MV_ALL_IN : (pol == PK_POLICY_CALL ? a_call : a_rand);
                 a = supplied ? action : a;

@@ -62,10 +62,10 @@ using std::min;
 #define PK_SIM_LDS_GARBAGE 0x2D
 
 namespace pk_sim {
-enum Kind : uint32_t { K_BALLOT = 1, K_READLANE = 2, K_READFIRST = 3, K_SHFL = 4, K_BARRIER = 5 };
+enum Kind : uint32_t { K_BALLOT = 1, K_READLANE = 2, K_READFIRST = 3, K_SHFL = 4, K_BARRIER = 5, K_DPP = 6 };
 inline const char *kind_name(uint32_t k) {
-    static const char *n[] = {"?", "__ballot/__any", "readlane", "readfirstlane", "__shfl_down", "barrier (__syncthreads / PK_QSYNC)"};
-    return n[k <= 5 ? k : 0];
+    static const char *n[] = {"?", "__ballot/__any", "readlane", "readfirstlane", "__shfl_down", "barrier (__syncthreads / PK_QSYNC)", "update_dpp"};
+    return n[k <= 6 ? k : 0];
 }
 struct Wave {
     std::atomic<uint64_t> live{0}, pending{0}, arrived[2], val[2][64], hb{0};
@@ -231,6 +231,22 @@ static inline unsigned __shfl_down(unsigned v, int off, int width, PK_SIM_SITE) 
     const int par = pk_sim::meet(pk_sim::K_SHFL, v, file, line), src = pk_sim::t_lane + off;
     const uint64_t am = pk_sim::g_wave.arrived[par].load(PK_SIM_MO);
     return (src < 64 && ((am >> src) & 1)) ? (unsigned)pk_sim::g_wave.val[par][src].load(PK_SIM_MO) : v;
+}
+// v_mov_b32_dpp for the controls wave_excl_scan (pk_device.hpp) uses: row_shr:1..15 (0x111..0x11f: the lane n below in the same row of 16),
+// row_bcast:15 (0x142: lane 15 of the row below) and row_bcast:31 (0x143: lane 31, for rows 2 and 3).  A lane whose row or bank the masks
+// leave out keeps `old`; so does one whose source is out of range or not active, unless bound_ctrl asks for 0.  Any other control aborts.
+static inline int __builtin_amdgcn_update_dpp(int old, int src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl, PK_SIM_SITE) {
+    const int par = pk_sim::meet(pk_sim::K_DPP, (uint32_t)src, file, line), l = pk_sim::t_lane;
+    const uint64_t am = pk_sim::g_wave.arrived[par].load(PK_SIM_MO);
+    int from = -1;
+    bool in_range = true;
+    if (ctrl >= 0x111 && ctrl <= 0x11f) { from = l - (ctrl - 0x110); in_range = (l & 15) >= ctrl - 0x110; }
+    else if (ctrl == 0x142) { from = (l & ~15) - 1; in_range = l >= 16; }
+    else if (ctrl == 0x143) { from = 31; in_range = l >= 32; }
+    else { fprintf(stderr, "wave_sim: update_dpp control 0x%x is not implemented\n", ctrl); abort(); }
+    if (!((row_mask >> (l >> 4)) & 1) || !((bank_mask >> ((l >> 2) & 3)) & 1)) return old;
+    if (!in_range || !((am >> from) & 1)) return bound_ctrl ? 0 : old;
+    return (int)(uint32_t)pk_sim::g_wave.val[par][from].load(PK_SIM_MO);
 }
 // lanes below this one among the mask's bits (v_mbcnt_lo / _hi_u32_b32)
 static inline unsigned __builtin_amdgcn_mbcnt_lo(unsigned mask, unsigned v) {

@@ -418,6 +418,19 @@ template <typename T> static inline T __shfl(T v, int src, int width = 64, PK_SI
 template <typename T> static inline T __shfl_up(T v, unsigned off, int width = 64, PK_SIM_SITE) { (void)width; return pk_sim::shfl(v, (pk_sim::cur_lane() & 63) - (int)off, file, line); }
 template <typename T> static inline T __shfl_down(T v, unsigned off, int width = 64, PK_SIM_SITE) { (void)width; return pk_sim::shfl(v, (pk_sim::cur_lane() & 63) + (int)off, file, line); }
 template <typename T> static inline T __shfl_xor(T v, int mask, int width = 64, PK_SIM_SITE) { (void)width; return pk_sim::shfl(v, ((pk_sim::cur_lane() & 63) ^ mask) & 63, file, line); }
+// v_mov_b32_dpp for the controls pk::wave_excl_scan (pk_device.hpp) uses, as in wave_shim.h: row_shr:1..15, row_bcast:15, row_bcast:31
+static inline int __builtin_amdgcn_update_dpp(int old, int src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl, PK_SIM_SITE) {
+    const int w = pk_sim::meet(pk_sim::K_SHFL, (uint32_t)src, file, line), l = pk_sim::cur_lane() & 63;
+    int from = -1;
+    bool in_range = true;
+    if (ctrl >= 0x111 && ctrl <= 0x11f) { from = l - (ctrl - 0x110); in_range = (l & 15) >= ctrl - 0x110; }
+    else if (ctrl == 0x142) { from = (l & ~15) - 1; in_range = l >= 16; }
+    else if (ctrl == 0x143) { from = 31; in_range = l >= 32; }
+    else { fprintf(stderr, "wg_sim: update_dpp control 0x%x is not implemented\n", ctrl); abort(); }
+    if (!((row_mask >> (l >> 4)) & 1) || !((bank_mask >> ((l >> 2) & 3)) & 1)) return old;
+    if (!in_range || !((pk_sim::wave_mask(w) >> from) & 1)) return bound_ctrl ? 0 : old;
+    return (int)(uint32_t)pk_sim::wave_val(w, from);
+}
 // lanes below this one among the mask's bits (v_mbcnt_lo / _hi_u32_b32)
 static inline unsigned __builtin_amdgcn_mbcnt_lo(unsigned mask, unsigned v) {
     const int l = pk_sim::cur_lane() & 63;

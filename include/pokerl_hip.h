@@ -892,6 +892,58 @@ int pk_hist_cluster_assign(int device, size_t n, int nbins, const uint16_t *hist
                            uint32_t *dist);
 int pk_hist_cluster(int device, size_t n, int nbins, const uint16_t *hist, int K, uint16_t *centroids, int iters, uint16_t *label,
                     uint32_t *dist, uint64_t *inertia, uint32_t *changed);
+/* ---- Pre-flop matchups: the exact result of every ordered pair of holdings over every five-card board, counted on the device, and the
+ * pre-flop forms of range equity and range vs range that read it.  Every other hidden-hand family refuses nb < 3
+ * (PK_EQ_PREFLOP) and keeps doing so; these entry points are the pre-flop capability.
+ *
+ * Cards by canonical index k = rank0 * 4 + suit, value[k] = ((k%4)<<4) | (k/4); holdings h = b (b - 1) / 2 + a over a < b, 0 .. 1325, as
+ * above.  The two-seat result is decided by the ORDER KEY of section 3.4 (larger key wins, equal keys tie): exactly the winners of
+ * compare_rankings([eval_hand(board + h), eval_hand(board + o)]).  BOARDS are the 5-subsets of the canonical indices 0 .. 51 in
+ * lexicographic order (itertools.combinations(range(52), 5)); a board's rank r runs over 0 .. 2 598 959 (PK_PREFLOP_ALL_BOARDS).
+ * PARTIAL COUNTS over the board range [first, first + n), for every ordered pair (h, o) of holdings that share no card:
+ *   win[h][o] = boards b of the range with b disjoint from h and o on which h wins alone,   tie[h][o] = such boards on which both win;
+ * pairs that share a card, the diagonal included, get 0.  Both are u32 [1326][1326]; either may be NULL.  accumulate != 0 ADDS the counts to
+ * what the arrays hold; otherwise the arrays are overwritten, zeros included (no memset is needed).  Counts over disjoint ranges add exactly.
+ * first + n > PK_PREFLOP_ALL_BOARDS is PK_E_INVALID_ARG; n = 0 writes nothing.  The evaluator's suit quirks are carried by the keys: no
+ * suit symmetry is assumed anywhere, and the table is NOT invariant under a renaming of suits.
+ * THE MATCHUP TABLE is the partial count over all boards.  For disjoint (h, o): win[h][o] + tie[h][o] + win[o][h] = 1 712 304
+ * (PK_PREFLOP_BOARDS = C(48, 5)); tie[h][o] = tie[o][h]; (win[h][o], tie[h][o]) are win[0], tie[0] of pk_equity on the two-seat spot [h, o],
+ * nb = 0, live = 3, bit for bit.  It is built once per device on first use, on the stream of the call that needs it (as the evaluator
+ * table is), and stays resident: 2 x 7.03 MB (the build's own key work space, 92 MB at the default chunk, is freed when the table stands).
+ * pk_preflop_matchups copies it out (either output may be NULL).  A call of the two families below that asks for boards / status alone
+ * neither reads nor builds it.
+ * PRE-FLOP RANGE EQUITY is range equity with nb = 0, dead = 0.  A spot is hero u8[2]; per spot win / tie u32 [1326] = row
+ * holding_index(hero) of the table, agg u64 [3] = sum w[o] win[o], sum w[o] tie[o], boards * sum of w[o] over the o that share no card with
+ * the hero, boards u32 = 1 712 304 (0 when refused), status u8: PK_EQ_BAD_CARD a byte that is no card (0xFF too), PK_EQ_DUP_CARD the same
+ * card twice; the table form also PK_EQ_IN_FLIGHT, PK_EQ_BAD_TABLE and PK_EQ_DUP_CARD for a table never dealt.  A non-zero status gives
+ * all-zero outputs, never fails the call and disturbs no neighbour.  Weights as range equity (u16 [1326] shared or [m][1326], NULL = ones);
+ * the largest aggregate, 65 535 * 1 225 * 1 712 304 ~ 1.4e14, fits u64.  TABLE FORM: observer = a seat or PK_OBSERVER_ACTIVE
+ * (PK_OBSERVER_NONE is refused); the spot is the observer's two hole cards AT WHATEVER TURN THE TABLE RESTS -- the board is not read: the
+ * starting-hand strength, a feature that stays meaningful later in the hand.
+ * PRE-FLOP RANGE VS RANGE: a spot is one weight row u16 [1326] (weights NULL: every row all ones); per spot and hero holding h, u64 [m][1326]:
+ *   win[h] = sum w[o] M.win[h][o],   tie[h] = sum w[o] M.tie[h][o],   tot[h] = 1 712 304 * (sum of w[o] over the o that share no card with h).
+ * Row h equals the agg of pre-flop range equity for hero = h with the same weights.  There is no table form (no board, no observer).
+ * Any output may be NULL; a call with no spot writes nothing; m < 2^31; device < PK_MAX_DEVICES.  STREAMS and work space: as pk_equity; the
+ * count pass's work space (the keys of one chunk of boards, PK_PFM_CHUNK = 1 .. 65 536 boards, default 16 384) is a grow-only piece of
+ * it; no launch ranks more boards than one chunk. */
+#define PK_PREFLOP_BOARDS 1712304u
+#define PK_PREFLOP_ALL_BOARDS 2598960u
+int pk_preflop_count_d(int device, uint32_t first, uint32_t n, int accumulate, uint32_t *win_d /*[1326][1326]*/, uint32_t *tie_d, void *stream);
+int pk_preflop_count(int device, uint32_t first, uint32_t n, int accumulate, uint32_t *win, uint32_t *tie);
+int pk_preflop_matchups_d(int device, uint32_t *win_d /*[1326][1326]*/, uint32_t *tie_d, void *stream);
+int pk_preflop_matchups(int device, uint32_t *win, uint32_t *tie);
+int pk_equity_preflop_d(int device, size_t m, const uint8_t *hero_d /*[m][2]*/, const uint16_t *weights_d /*NULL: 1*/, int weights_per_spot,
+                        uint64_t *agg_d /*[m][3]*/, uint32_t *win_d /*[m][1326]*/, uint32_t *tie_d, uint32_t *boards_d, uint8_t *status_d,
+                        void *stream);
+int pk_equity_preflop(int device, size_t m, const uint8_t *hero, const uint16_t *weights, int weights_per_spot, uint64_t *agg, uint32_t *win,
+                      uint32_t *tie, uint32_t *boards, uint8_t *status);
+int pk_table_equity_preflop_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, const uint16_t *weights_d, int weights_per_spot,
+                              uint64_t *agg_d, uint32_t *win_d, uint32_t *tie_d, uint32_t *boards_d, uint8_t *status_d);
+int pk_table_equity_preflop(pk_handle *h, const int32_t *tables, size_t m, int observer, const uint16_t *weights, int weights_per_spot,
+                            uint64_t *agg, uint32_t *win, uint32_t *tie, uint32_t *boards, uint8_t *status);
+int pk_equity_rvr_preflop_d(int device, size_t m, const uint16_t *weights_d /*[m][1326]; NULL: 1*/, uint64_t *win_d /*[m][1326]*/, uint64_t *tie_d,
+                            uint64_t *tot_d, void *stream);
+int pk_equity_rvr_preflop(int device, size_t m, const uint16_t *weights, uint64_t *win, uint64_t *tie, uint64_t *tot);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

@@ -8,6 +8,8 @@ from .judger import (Equity, SampledEquity, compare_hands, compare_rankings, eva
                      showdown_equity, showdown_equity_batch)
 from .judger import HOLDINGS, RangeEquity, holding_index, range_equity, range_equity_batch, range_equity_d
 from .judger import RangeVsRange, range_vs_range, range_vs_range_batch, range_vs_range_d
+from .judger import (PreflopMatchups, preflop_counts, preflop_counts_d, preflop_equity, preflop_equity_batch, preflop_equity_d, preflop_matchups,
+                     preflop_matchups_d, preflop_range_vs_range, preflop_range_vs_range_batch, preflop_range_vs_range_d)
 from .judger import StrengthHistogram, histogram_emd, strength_histogram, strength_histogram_batch, strength_histogram_d
 from .judger import HeroHistogram, hero_histogram, hero_histogram_batch, hero_histogram_d
 from .judger import (HistogramClusters, assign_histograms, assign_histograms_d, cluster_histograms, cluster_histograms_d,
@@ -32,4 +34,7 @@ __all__ = ['Game', 'PokerGameEnv', 'VecGame', 'VecPokerGameEnv', 'VecPokerGameEn
            'HistogramClusters', 'cluster_histograms', 'assign_histograms', 'seed_histogram_centroids', 'cluster_histograms_d',
            'assign_histograms_d', 'seed_histogram_centroids_d',
            'RangedEquity', 'ranged_equity', 'ranged_equity_batch', 'ranged_equity_d',
-           'ShowdownEV', 'showdown_ev', 'showdown_ev_batch', 'showdown_ev_d']
+           'ShowdownEV', 'showdown_ev', 'showdown_ev_batch', 'showdown_ev_d',
+           'PreflopMatchups', 'preflop_matchups', 'preflop_matchups_d', 'preflop_counts', 'preflop_counts_d',
+           'preflop_equity', 'preflop_equity_batch', 'preflop_equity_d',
+           'preflop_range_vs_range', 'preflop_range_vs_range_batch', 'preflop_range_vs_range_d']

@@ -27,6 +27,7 @@ EQ_BAD_BET = 64   # ... of pk_equity_ev: a bet that is negative, NaN or infinite
 EQ_HIST_MAX_BINS = 32   # PK_EQ_HIST_MAX_BINS: the most bins of a strength histogram
 EQ_HOLDINGS = 1326   # PK_EQ_HOLDINGS: unordered pairs of the 52 cards, h = b (b - 1) / 2 + a over canonical indices a < b
 CL_MAX_K, CL_NONE, CL_MAX_ITERS = 4096, 0xFFFF, 1024   # PK_CL_MAX_K, PK_CL_NONE; iterations of one pk_hist_cluster call at most
+PREFLOP_BOARDS, PREFLOP_ALL_BOARDS = 1712304, 2598960   # PK_PREFLOP_BOARDS = C(48, 5): boards of one pre-flop matchup; PK_PREFLOP_ALL_BOARDS = C(52, 5)
 EQS_SAMPLES_MAX = 1 << 24   # pk_equity_sampled: samples per call and spot at most
 EQW_MAX_RANGES, EQW_UNIFORM = 16, 0xFFFF   # pk_equity_ranged: rows of a call's weight table at most / the range_of entry "every weight 1"
 
@@ -51,7 +52,10 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_equity_hist_hero_d", "pk_equity_hist_hero", "pk_table_equity_hist_hero_d", "pk_table_equity_hist_hero",
            "pk_equity_ranged_d", "pk_equity_ranged", "pk_table_equity_ranged_d", "pk_table_equity_ranged",
            "pk_equity_ev_d", "pk_equity_ev", "pk_table_equity_ev_d", "pk_table_equity_ev",
-           "pk_hist_cluster_seed_d", "pk_hist_cluster_assign_d", "pk_hist_cluster_d", "pk_hist_cluster_seed", "pk_hist_cluster_assign", "pk_hist_cluster"]
+           "pk_hist_cluster_seed_d", "pk_hist_cluster_assign_d", "pk_hist_cluster_d", "pk_hist_cluster_seed", "pk_hist_cluster_assign", "pk_hist_cluster",
+           "pk_preflop_count_d", "pk_preflop_count", "pk_preflop_matchups_d", "pk_preflop_matchups",
+           "pk_equity_preflop_d", "pk_equity_preflop", "pk_table_equity_preflop_d", "pk_table_equity_preflop",
+           "pk_equity_rvr_preflop_d", "pk_equity_rvr_preflop"]
 
 
 class PokerlHipError(RuntimeError):
@@ -187,6 +191,16 @@ def lib():
     L.pk_hist_cluster_assign.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, _vp, _vp, _vp]
     L.pk_hist_cluster_d.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, _vp, C.c_int] + [_vp] * 5
     L.pk_hist_cluster.argtypes = [C.c_int, C.c_size_t, C.c_int, _vp, C.c_int, _vp, C.c_int] + [_vp] * 4
+    L.pk_preflop_count_d.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_int, _vp, _vp, _vp]
+    L.pk_preflop_count.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_int, _vp, _vp]
+    L.pk_preflop_matchups_d.argtypes = [C.c_int, _vp, _vp, _vp]
+    L.pk_preflop_matchups.argtypes = [C.c_int, _vp, _vp]
+    L.pk_equity_preflop_d.argtypes = [C.c_int, C.c_size_t, _vp, _vp, C.c_int] + [_vp] * 6
+    L.pk_equity_preflop.argtypes = [C.c_int, C.c_size_t, _vp, _vp, C.c_int] + [_vp] * 5
+    L.pk_table_equity_preflop_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int] + [_vp] * 5
+    L.pk_table_equity_preflop.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int] + [_vp] * 5
+    L.pk_equity_rvr_preflop_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 5
+    L.pk_equity_rvr_preflop.argtypes = [C.c_int, C.c_size_t] + [_vp] * 4
     for name in SYMBOLS:
         if name not in ("pk_last_error", "pk_build_info", "pk_snapshot_bytes"):
             getattr(L, name).restype = C.c_int

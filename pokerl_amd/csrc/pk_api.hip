@@ -24,6 +24,7 @@
 #include "pk_equity_hist.hpp"
 #include "pk_equity_hist_hero.hpp"
 #include "pk_hist_cluster.hpp"
+#include "pk_preflop.hpp"
 #include "pk_snapshot.hpp"
 
 using namespace pk;
@@ -1857,18 +1858,27 @@ static void *eq_stream_ws(int device, hipStream_t st, size_t bytes) {   // the d
 // ---- showdown equity (pokerl_hip.h "Showdown equity"; kernels: pk_equity.hip) and, after it, the rest of the equity family.  Every family
 // comes in the same four forms, and each form is written ONCE here: an entry point checks its arguments, names its
 // staging pieces and its work-space size, and hands a lambda that queues its kernels to the form's skeleton.
+// The per-device table a family's kernels read, handed to its launch as `tab`: none, the evaluator table, or the pre-flop matchup
+// table (pfm_table, further down: win [1326][1326], then tie).  A first call builds it on the CALLER's stream.
+enum { EQ_TAB_NONE = 0, EQ_TAB_EVAL = 1, EQ_TAB_PREFLOP = 2 };
+static const uint32_t *pfm_table(int device, hipStream_t stream);
+static const uint32_t *eq_resident(int need, int device, hipStream_t st) {
+    return need == EQ_TAB_PREFLOP ? pfm_table(device, st) : (need ? eval7_table(device, st) : nullptr);
+}
+static const char *eq_resident_text(int need) { return need == EQ_TAB_PREFLOP ? ": out of device memory (pre-flop matchup table)" : ": out of device memory (evaluator table)"; }
+
 extern "C++" {   // (templates)
 static int eq_fail(int code, const char *call, const char *what, hipError_t e = hipSuccess) { return g_fail(code, (std::string(call) + what).c_str(), e); }
 
 // The device form: asynchronous on the CALLER's stream, every array in device memory; the work space is that stream's (above).
-// launch(st, tab, work) queues the kernels; tab is NULL for a family that does not evaluate hands (need_table false).
+// launch(st, tab, work) queues the kernels; tab is the table need_table names (EQ_TAB_*), NULL for EQ_TAB_NONE.
 template <typename F>
-static int eq_call_d(const char *call, int device, void *stream, size_t m, bool need_table, size_t work_bytes, F launch) {
+static int eq_call_d(const char *call, int device, void *stream, size_t m, int need_table, size_t work_bytes, F launch) {
     ON_DEVICE_INDEX(call, device, PK_MAX_DEVICES);   // (the evaluator table is kept per device index below PK_MAX_DEVICES)
     if (m == 0) return PK_OK;
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t *tab = need_table ? eval7_table(device, st) : nullptr;   // (a first call builds the table on the CALLER's stream)
-    if (need_table && !tab) return eq_fail(PK_E_OOM, call, ": out of device memory (evaluator table)");
+    const uint32_t *tab = eq_resident(need_table, device, st);   // (a first call builds the table on the CALLER's stream)
+    if (need_table && !tab) return eq_fail(PK_E_OOM, call, eq_resident_text(need_table));
     char *work = (char *)eq_stream_ws(device, st, work_bytes);
     if (!work) return eq_fail(PK_E_OOM, call, ": out of device memory (work space)");
     const hipError_t e = launch(st, tab, work);
@@ -1879,14 +1889,14 @@ static int eq_call_d(const char *call, int device, void *stream, size_t m, bool 
 // The host form: the caller's host arrays, staged in ONE buffer (g's pieces: inputs, outputs, then the work space) of the judger arena on a
 // pooled stream; returns when the outputs are in the caller's arrays.  launch(st, tab, work) as above, on g.at<T>(piece).
 template <typename F>
-static int eq_call_host(const char *call, int device, size_t m, bool need_table, Stage &g, size_t work_bytes, F launch) {
+static int eq_call_host(const char *call, int device, size_t m, int need_table, Stage &g, size_t work_bytes, F launch) {
     ON_DEVICE_INDEX(call, device, PK_MAX_DEVICES);
     if (m == 0) return PK_OK;
     hipStream_t st = nullptr;
     if (stream_acquire(device, &st) != hipSuccess) { (void)hipGetLastError(); return eq_fail(PK_E_HIP, call, ": no stream"); }
-    const uint32_t *tab = need_table ? eval7_table(device, st) : nullptr;   // (takes g_scratch_mu itself)
+    const uint32_t *tab = eq_resident(need_table, device, st);   // (takes g_scratch_mu itself)
     int rc = PK_OK;
-    if (need_table && !tab) rc = eq_fail(PK_E_OOM, call, ": out of device memory (evaluator table)");
+    if (need_table && !tab) rc = eq_fail(PK_E_OOM, call, eq_resident_text(need_table));
     else {
         std::lock_guard<std::mutex> lock(g_scratch_mu);
         const int work = g.add(work_bytes);
@@ -1901,11 +1911,12 @@ static int eq_call_host(const char *call, int device, size_t m, bool need_table,
 }
 
 // The two table forms read the handle's own state on the handle's stream; their work space is the handle's grow-only staging buffer.  What
-// they share once that is there: the evaluator table, the handle's state as EqTables, launch(tab, tables, work).
+// they share once that is there: the table need_table names (EQ_TAB_*), the handle's state as EqTables, launch(tab, tables, work).
 template <typename F>
-static int eq_table_launch(pk_handle *h, const char *call, const int32_t *tables_d, char *work, F launch) {
-    const uint32_t *tab = eval7_table(h->device, h->stream);
-    if (!tab) {
+static int eq_table_launch(pk_handle *h, const char *call, const int32_t *tables_d, int need_table, char *work, F launch) {
+    const uint32_t *tab = eq_resident(need_table, h->device, h->stream);
+    if (!tab && need_table == EQ_TAB_PREFLOP) return h->fail(PK_E_OOM, (std::string(call) + eq_resident_text(need_table)).c_str());
+    if (!tab && need_table) {
         std::string family(call);                    // (this text has always named the family, without the device form's _d)
         if (family.size() > 2 && family.compare(family.size() - 2, 2, "_d") == 0) family.resize(family.size() - 2);
         return h->fail(PK_E_OOM, (family + ": out of device memory (evaluator table)").c_str());
@@ -1918,24 +1929,24 @@ static int eq_table_launch(pk_handle *h, const char *call, const int32_t *tables
 // The device form: tables_d and the outputs in device memory, asynchronous on the handle's stream (m == 0: nothing to do, once the handle has
 // been flushed)
 template <typename F>
-static int eq_table_call_d(pk_handle *h, const char *call, const int32_t *tables_d, size_t m, size_t work_bytes, F launch) {
+static int eq_table_call_d(pk_handle *h, const char *call, const int32_t *tables_d, size_t m, int need_table, size_t work_bytes, F launch) {
     ON_DEVICE(h);
     FLUSH_READER(h);
     if (m == 0) return PK_OK;
     char *work = nullptr;
     if (int rc = snap_staging(h, work_bytes, &work)) return rc;
-    return eq_table_launch(h, call, tables_d, work, launch);
+    return eq_table_launch(h, call, tables_d, need_table, work, launch);
 }
 // The host form: g's pieces (inputs, outputs), then the table indices and the work space, staged as the host form above stages them
 template <typename F>
-static int eq_table_call(pk_handle *h, const char *call, const int32_t *tables, size_t m, Stage &g, size_t work_bytes, F launch) {
+static int eq_table_call(pk_handle *h, const char *call, const int32_t *tables, size_t m, int need_table, Stage &g, size_t work_bytes, F launch) {
     ON_DEVICE(h);
     FLUSH_READER(h);
     if (m == 0) return PK_OK;
     const int idx = g.in(tables, m * 4), work = g.add(work_bytes);
     if (int rc = snap_staging(h, g.total, &g.base)) return rc;
     HIPCHK(h, g.upload(h->stream));
-    if (int rc = eq_table_launch(h, call, g.at<int32_t>(idx), g.at<char>(work), launch)) return rc;
+    if (int rc = eq_table_launch(h, call, g.at<int32_t>(idx), need_table, g.at<char>(work), launch)) return rc;
     HIPCHK(h, g.download(h->stream));
     return PK_OK;
 }
@@ -1991,7 +2002,7 @@ int pk_equity_d(int device, int num_players, size_t m, const uint8_t *holes_d, c
     const char *call = "pk_equity_d";
     EQ_REFUSE(g_fail, call, eq_check(num_players, m, holes_d && board_d && nboard_d && live_d));
     const int N = num_players, lpt = eq_lpt(m);
-    return eq_call_d(call, device, stream, m, true, eq_layout(N, m, lpt, 50, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, eq_layout(N, m, lpt, 50, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
         EqWork w;
         eq_layout(N, m, lpt, 50, work, &w);
         const EqSpots spots{holes_d, board_d, nboard_d, live_d};
@@ -2007,7 +2018,7 @@ int pk_equity(int device, int num_players, size_t m, const uint8_t *holes, const
     Stage g;
     const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2);
     const EqStagedOut out(g, N, m, win, tie, share, boards, status);
-    return eq_call_host(call, device, m, true, g, eq_layout(N, m, lpt, 50, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, eq_layout(N, m, lpt, 50, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
         EqWork w;
         eq_layout(N, m, lpt, 50, work, &w);
         const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
@@ -2021,7 +2032,7 @@ int pk_table_equity_d(pk_handle *h, const int32_t *tables_d, size_t m, uint32_t 
     const char *call = "pk_table_equity_d";
     EQ_REFUSE(h->fail, call, eq_table_check(h, m));
     const int N = h->N, lpt = eq_lpt(m), pool = 52 - 2 * N;
-    return eq_table_call_d(h, call, tables_d, m, eq_layout(N, m, lpt, pool, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call_d(h, call, tables_d, m, EQ_TAB_EVAL, eq_layout(N, m, lpt, pool, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
         EqWork w;
         eq_layout(N, m, lpt, pool, work, &w);
         return eq_launch(h->stream, tab, nullptr, &t, N, m, EqOut{win_d, tie_d, share_d, boards_d, status_d}, w, lpt);
@@ -2036,7 +2047,7 @@ int pk_table_equity(pk_handle *h, const int32_t *tables, size_t m, uint32_t *win
     const int N = h->N, lpt = eq_lpt(m), pool = 52 - 2 * N;
     Stage g;
     const EqStagedOut out(g, N, m, win, tie, share, boards, status);
-    return eq_table_call(h, call, tables, m, g, eq_layout(N, m, lpt, pool, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call(h, call, tables, m, EQ_TAB_EVAL, g, eq_layout(N, m, lpt, pool, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
         EqWork w;
         eq_layout(N, m, lpt, pool, work, &w);
         return eq_launch(h->stream, tab, nullptr, &t, N, m, out.at(g), w, lpt);
@@ -2071,7 +2082,7 @@ int pk_equity_ev_d(int device, int num_players, size_t m, const uint8_t *holes_d
     const char *call = "pk_equity_ev_d";
     EQ_REFUSE(g_fail, call, ev_check(num_players, m, holes_d && board_d && nboard_d && live_d && bets_d && status_d));
     const int N = num_players, lpt = eq_lpt(m);
-    return eq_call_d(call, device, stream, m, true, ev_layout(N, m, lpt, 50, !share_d, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, ev_layout(N, m, lpt, 50, !share_d, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
         EvWork w;
         ev_layout(N, m, lpt, 50, !share_d, work, &w);
         const EqSpots spots{holes_d, board_d, nboard_d, live_d};
@@ -2087,7 +2098,7 @@ int pk_equity_ev(int device, int num_players, size_t m, const uint8_t *holes, co
     Stage g;
     const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), be = g.in(bets, m * N * 8);
     const EvStagedOut out(g, N, m, share, level_seat, amount, ev, boards, status);
-    return eq_call_host(call, device, m, true, g, ev_layout(N, m, lpt, 50, !share, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, ev_layout(N, m, lpt, 50, !share, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
         EvWork w;
         ev_layout(N, m, lpt, 50, !share, work, &w);
         const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
@@ -2101,7 +2112,7 @@ int pk_table_equity_ev_d(pk_handle *h, const int32_t *tables_d, size_t m, uint64
     const char *call = "pk_table_equity_ev_d";
     EQ_REFUSE(h->fail, call, ev_table_check(h, m, status_d));
     const int N = h->N, lpt = eq_lpt(m), pool = 52 - 2 * N;
-    return eq_table_call_d(h, call, tables_d, m, ev_layout(N, m, lpt, pool, !share_d, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call_d(h, call, tables_d, m, EQ_TAB_EVAL, ev_layout(N, m, lpt, pool, !share_d, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
         EvWork w;
         ev_layout(N, m, lpt, pool, !share_d, work, &w);
         const EvTables et{t, h->S.bets, h->S.pending};     // (the handle's bets and pending chips beside the tables)
@@ -2117,7 +2128,7 @@ int pk_table_equity_ev(pk_handle *h, const int32_t *tables, size_t m, uint64_t *
     const int N = h->N, lpt = eq_lpt(m), pool = 52 - 2 * N;
     Stage g;
     const EvStagedOut out(g, N, m, share, level_seat, amount, ev, boards, status);
-    return eq_table_call(h, call, tables, m, g, ev_layout(N, m, lpt, pool, !share, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call(h, call, tables, m, EQ_TAB_EVAL, g, ev_layout(N, m, lpt, pool, !share, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
         EvWork w;
         ev_layout(N, m, lpt, pool, !share, work, &w);
         const EvTables et{t, h->S.bets, h->S.pending};
@@ -2152,7 +2163,7 @@ int pk_equity_sampled_d(int device, int num_players, size_t m, const uint8_t *ho
                         uint32_t *tie_d, uint64_t *share_d, uint32_t *samples_d, uint8_t *status_d, void *stream) {
     const char *call = "pk_equity_sampled_d";
     EQ_REFUSE(g_fail, call, eqs_check(num_players, m, samples, holes_d && board_d && nboard_d && live_d));
-    return eq_call_d(call, device, stream, m, true, eqs_work_bytes(num_players, m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, eqs_work_bytes(num_players, m), [&](hipStream_t st, const uint32_t *tab, char *work) {
         const EqSpots spots{holes_d, board_d, nboard_d, live_d};
         return eqs_launch(st, tab, &spots, nullptr, PK_OBSERVER_NONE, eqs_seed_stream(seed, nonce, samples, ids_d), num_players, m,
                           EqsOut{win_d, tie_d, share_d, samples_d, status_d}, (uint64_t *)work);
@@ -2168,7 +2179,7 @@ int pk_equity_sampled(int device, int num_players, size_t m, const uint8_t *hole
     Stage g;
     const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), id = g.in(ids, m * 4);
     const EqStagedOut out(g, N, m, win, tie, share, samples_out, status);
-    return eq_call_host(call, device, m, true, g, eqs_work_bytes(N, m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, eqs_work_bytes(N, m), [&](hipStream_t st, const uint32_t *tab, char *work) {
         const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
         return eqs_launch(st, tab, &spots, nullptr, PK_OBSERVER_NONE, eqs_seed_stream(seed, nonce, samples, g.at<uint32_t>(id)), N, m,
                           eqs_out(out.at(g)), (uint64_t *)work);
@@ -2181,7 +2192,7 @@ int pk_table_equity_sampled_d(pk_handle *h, const int32_t *tables_d, size_t m, i
     if (!h) return PK_E_INVALID_ARG;
     const char *call = "pk_table_equity_sampled_d";
     EQ_REFUSE(h->fail, call, eqs_table_check(h, m, observer, samples));
-    return eq_table_call_d(h, call, tables_d, m, eqs_work_bytes(h->N, m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call_d(h, call, tables_d, m, EQ_TAB_EVAL, eqs_work_bytes(h->N, m), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return eqs_launch(h->stream, tab, nullptr, &t, observer, eqs_table_stream(h, nonce, samples), h->N, m,
                           EqsOut{win_d, tie_d, share_d, samples_d, status_d}, (uint64_t *)work);
     });
@@ -2194,7 +2205,7 @@ int pk_table_equity_sampled(pk_handle *h, const int32_t *tables, size_t m, int o
     EQ_REFUSE(h->fail, call, eqs_table_check(h, m, observer, samples));
     Stage g;
     const EqStagedOut out(g, h->N, m, win, tie, share, samples_out, status);
-    return eq_table_call(h, call, tables, m, g, eqs_work_bytes(h->N, m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call(h, call, tables, m, EQ_TAB_EVAL, g, eqs_work_bytes(h->N, m), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return eqs_launch(h->stream, tab, nullptr, &t, observer, eqs_table_stream(h, nonce, samples), h->N, m, eqs_out(out.at(g)), (uint64_t *)work);
     });
 }
@@ -2220,7 +2231,7 @@ int pk_equity_ranged_d(int device, int num_players, size_t m, const uint8_t *hol
                        uint8_t *status_d, void *stream) {
     const char *call = "pk_equity_ranged_d";
     EQ_REFUSE(g_fail, call, eqw_check(num_players, m, samples, holes_d && board_d && nboard_d && live_d, weights_d, num_ranges));
-    return eq_call_d(call, device, stream, m, true, eqw_work_bytes(num_players, m, num_ranges), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, eqw_work_bytes(num_players, m, num_ranges), [&](hipStream_t st, const uint32_t *tab, char *work) {
         const EqSpots spots{holes_d, board_d, nboard_d, live_d};
         return eqw_launch(st, tab, &spots, nullptr, PK_OBSERVER_ACTIVE, eqs_seed_stream(seed, nonce, samples, ids_d),
                           EqwRanges{weights_d, num_ranges, range_of_d, 1}, num_players, m, EqwOut{win_d, tie_d, share_d, accepted_d, status_d}, work);
@@ -2237,7 +2248,7 @@ int pk_equity_ranged(int device, int num_players, size_t m, const uint8_t *holes
     const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), id = g.in(ids, m * 4);
     const int wt = g.in(num_ranges ? weights : nullptr, (size_t)num_ranges * EQW_HOLDINGS * 2), ro = g.in(range_of, m * (size_t)N * 2);
     const EqStagedOut out(g, N, m, win, tie, share, accepted, status);
-    return eq_call_host(call, device, m, true, g, eqw_work_bytes(N, m, num_ranges), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, eqw_work_bytes(N, m, num_ranges), [&](hipStream_t st, const uint32_t *tab, char *work) {
         const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
         return eqw_launch(st, tab, &spots, nullptr, PK_OBSERVER_ACTIVE, eqs_seed_stream(seed, nonce, samples, g.at<uint32_t>(id)),
                           EqwRanges{g.at<uint16_t>(wt), num_ranges, g.at<uint16_t>(ro), 1}, N, m, eqw_out(out.at(g)), work);
@@ -2251,7 +2262,7 @@ int pk_table_equity_ranged_d(pk_handle *h, const int32_t *tables_d, size_t m, in
     if (!h) return PK_E_INVALID_ARG;
     const char *call = "pk_table_equity_ranged_d";
     EQ_REFUSE(h->fail, call, eqw_table_check(h, m, observer, samples, weights_d, num_ranges));
-    return eq_table_call_d(h, call, tables_d, m, eqw_work_bytes(h->N, m, num_ranges), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call_d(h, call, tables_d, m, EQ_TAB_EVAL, eqw_work_bytes(h->N, m, num_ranges), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return eqw_launch(h->stream, tab, nullptr, &t, observer, eqs_table_stream(h, nonce, samples),
                           EqwRanges{weights_d, num_ranges, range_of_d, range_per_table ? 1 : 0}, h->N, m,
                           EqwOut{win_d, tie_d, share_d, accepted_d, status_d}, work);
@@ -2268,7 +2279,7 @@ int pk_table_equity_ranged(pk_handle *h, const int32_t *tables, size_t m, int ob
     const int wt = g.in(num_ranges ? weights : nullptr, (size_t)num_ranges * EQW_HOLDINGS * 2);
     const int ro = g.in(range_of, (range_per_table ? m : (size_t)1) * (size_t)h->N * 2);
     const EqStagedOut out(g, h->N, m, win, tie, share, accepted, status);
-    return eq_table_call(h, call, tables, m, g, eqw_work_bytes(h->N, m, num_ranges), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call(h, call, tables, m, EQ_TAB_EVAL, g, eqw_work_bytes(h->N, m, num_ranges), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return eqw_launch(h->stream, tab, nullptr, &t, observer, eqs_table_stream(h, nonce, samples),
                           EqwRanges{g.at<uint16_t>(wt), num_ranges, g.at<uint16_t>(ro), range_per_table ? 1 : 0}, h->N, m, eqw_out(out.at(g)), work);
     });
@@ -2290,7 +2301,7 @@ int pk_equity_range_d(int device, size_t m, const uint8_t *hero_d, const uint8_t
                       uint8_t *status_d, void *stream) {
     const char *call = "pk_equity_range_d";
     EQ_REFUSE(g_fail, call, eqr_check(m, hero_d && board_d && nboard_d));
-    return eq_call_d(call, device, stream, m, true, eqr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, eqr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
         const EqrSpots spots{hero_d, board_d, nboard_d, dead_d};
         return eqr_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{weights_d, weights_per_spot != 0}, m,
                           EqrOut{agg_d, win_d, tie_d, boards_d, status_d}, (uint64_t *)work);
@@ -2306,7 +2317,7 @@ int pk_equity_range(int device, size_t m, const uint8_t *hero, const uint8_t *bo
     const int he = g.in(hero, m * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
     const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
     const EqrStagedOut out(g, m, agg, win, tie, boards, status);
-    return eq_call_host(call, device, m, true, g, eqr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, eqr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
         const EqrSpots spots{g.at<uint8_t>(he), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
         return eqr_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, out.at(g),
                           (uint64_t *)work);
@@ -2319,7 +2330,7 @@ int pk_table_equity_range_d(pk_handle *h, const int32_t *tables_d, size_t m, int
     if (!h) return PK_E_INVALID_ARG;
     const char *call = "pk_table_equity_range_d";
     EQ_REFUSE(h->fail, call, eqr_table_check(h, m, observer));
-    return eq_table_call_d(h, call, tables_d, m, eqr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call_d(h, call, tables_d, m, EQ_TAB_EVAL, eqr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return eqr_launch(h->stream, tab, nullptr, &t, h->N, observer, EqrWeights{weights_d, weights_per_spot != 0}, m,
                           EqrOut{agg_d, win_d, tie_d, boards_d, status_d}, (uint64_t *)work);
     });
@@ -2333,7 +2344,7 @@ int pk_table_equity_range(pk_handle *h, const int32_t *tables, size_t m, int obs
     Stage g;
     const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
     const EqrStagedOut out(g, m, agg, win, tie, boards, status);
-    return eq_table_call(h, call, tables, m, g, eqr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call(h, call, tables, m, EQ_TAB_EVAL, g, eqr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return eqr_launch(h->stream, tab, nullptr, &t, h->N, observer, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, out.at(g), (uint64_t *)work);
     });
 }
@@ -2344,7 +2355,7 @@ int pk_equity_rvr_d(int device, size_t m, const uint8_t *board_d, const uint8_t 
                     int weights_per_spot, uint64_t *win_d, uint64_t *tie_d, uint64_t *tot_d, uint32_t *boards_d, uint8_t *status_d, void *stream) {
     const char *call = "pk_equity_rvr_d";
     EQ_REFUSE(g_fail, call, eqr_check(m, board_d && nboard_d));
-    return eq_call_d(call, device, stream, m, true, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
         const RvrSpots spots{board_d, nboard_d, dead_d};
         return rvr_launch(st, tab, &spots, nullptr, RvrWeights{weights_d, weights_per_spot != 0}, m, RvrOut{win_d, tie_d, tot_d, boards_d, status_d},
                           (uint64_t *)work);
@@ -2359,7 +2370,7 @@ int pk_equity_rvr(int device, size_t m, const uint8_t *board, const uint8_t *nbo
     const int bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
     const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
     const RvrStagedOut out(g, m, win, tie, tot, boards, status);
-    return eq_call_host(call, device, m, true, g, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
         const RvrSpots spots{g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
         return rvr_launch(st, tab, &spots, nullptr, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, out.at(g), (uint64_t *)work);
     });
@@ -2370,7 +2381,7 @@ int pk_table_equity_rvr_d(pk_handle *h, const int32_t *tables_d, size_t m, const
     if (!h) return PK_E_INVALID_ARG;
     const char *call = "pk_table_equity_rvr_d";
     EQ_REFUSE(h->fail, call, eq_bad_m(m));
-    return eq_table_call_d(h, call, tables_d, m, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call_d(h, call, tables_d, m, EQ_TAB_EVAL, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return rvr_launch(h->stream, tab, nullptr, &t, RvrWeights{weights_d, weights_per_spot != 0}, m, RvrOut{win_d, tie_d, tot_d, boards_d, status_d},
                           (uint64_t *)work);
     });
@@ -2384,7 +2395,7 @@ int pk_table_equity_rvr(pk_handle *h, const int32_t *tables, size_t m, const uin
     Stage g;
     const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
     const RvrStagedOut out(g, m, win, tie, tot, boards, status);
-    return eq_table_call(h, call, tables, m, g, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call(h, call, tables, m, EQ_TAB_EVAL, g, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return rvr_launch(h->stream, tab, nullptr, &t, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, out.at(g), (uint64_t *)work);
     });
 }
@@ -2404,7 +2415,7 @@ int pk_equity_hist_d(int device, size_t m, const uint8_t *board_d, const uint8_t
                      int weights_per_spot, int nbins, uint16_t *hist_d, uint16_t *void_d, uint32_t *completions_d, uint8_t *status_d, void *stream) {
     const char *call = "pk_equity_hist_d";
     EQ_REFUSE(g_fail, call, hist_check(m, board_d && nboard_d, nbins));
-    return eq_call_d(call, device, stream, m, true, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
         const RvrSpots spots{board_d, nboard_d, dead_d};
         return hist_launch(st, tab, &spots, nullptr, RvrWeights{weights_d, weights_per_spot != 0}, m, nbins,
                            HistOut{hist_d, void_d, completions_d, status_d}, (uint64_t *)work);
@@ -2419,7 +2430,7 @@ int pk_equity_hist(int device, size_t m, const uint8_t *board, const uint8_t *nb
     const int bo = g.in(board, m * 5), nb = g.in(nboard, m), de = g.in(dead, m * 8);
     const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
     const HistStagedOut out(g, m, nbins, hist, void_, completions, status);
-    return eq_call_host(call, device, m, true, g, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, rvr_work_bytes(m), [&](hipStream_t st, const uint32_t *tab, char *work) {
         const RvrSpots spots{g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
         return hist_launch(st, tab, &spots, nullptr, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, nbins, out.at(g), (uint64_t *)work);
     });
@@ -2430,7 +2441,7 @@ int pk_table_equity_hist_d(pk_handle *h, const int32_t *tables_d, size_t m, cons
     if (!h) return PK_E_INVALID_ARG;
     const char *call = "pk_table_equity_hist_d";
     EQ_REFUSE(h->fail, call, hist_table_check(m, nbins));
-    return eq_table_call_d(h, call, tables_d, m, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call_d(h, call, tables_d, m, EQ_TAB_EVAL, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return hist_launch(h->stream, tab, nullptr, &t, RvrWeights{weights_d, weights_per_spot != 0}, m, nbins,
                            HistOut{hist_d, void_d, completions_d, status_d}, (uint64_t *)work);
     });
@@ -2444,7 +2455,7 @@ int pk_table_equity_hist(pk_handle *h, const int32_t *tables, size_t m, const ui
     Stage g;
     const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
     const HistStagedOut out(g, m, nbins, hist, void_, completions, status);
-    return eq_table_call(h, call, tables, m, g, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call(h, call, tables, m, EQ_TAB_EVAL, g, rvr_work_bytes(m), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return hist_launch(h->stream, tab, nullptr, &t, RvrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, nbins, out.at(g), (uint64_t *)work);
     });
 }
@@ -2475,7 +2486,7 @@ int pk_equity_hist_hero_d(int device, size_t m, const uint8_t *hero_d, const uin
     EQ_REFUSE(g_fail, call, hh_check(m, hero_d && board_d && nboard_d, nbins, K, centroids_d, label_d, dist_d));
     const HeroHistOut out{hist_d, void_d, completions_d, status_d};
     const HeroHistBucket bk{K, centroids_d, label_d, dist_d};
-    return eq_call_d(call, device, stream, m, true, hh_work_bytes(m, nbins, out, bk), [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, hh_work_bytes(m, nbins, out, bk), [&](hipStream_t st, const uint32_t *tab, char *work) {
         const EqrSpots spots{hero_d, board_d, nboard_d, dead_d};
         return hh_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{weights_d, weights_per_spot != 0}, m, nbins, out, bk, work);
     });
@@ -2491,7 +2502,7 @@ int pk_equity_hist_hero(int device, size_t m, const uint8_t *hero, const uint8_t
     const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
     const HeroHistStaged io(g, m, nbins, hist, void_, completions, status, K, centroids, label, dist);
     const size_t bytes = hh_work_bytes(m, nbins, HeroHistOut{hist, void_, completions, status}, HeroHistBucket{K, centroids, label, dist});
-    return eq_call_host(call, device, m, true, g, bytes, [&](hipStream_t st, const uint32_t *tab, char *work) {
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, bytes, [&](hipStream_t st, const uint32_t *tab, char *work) {
         const EqrSpots spots{g.at<uint8_t>(he), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint64_t>(de)};
         return hh_launch(st, tab, &spots, nullptr, 0, PK_OBSERVER_NONE, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, nbins, io.at(g),
                          io.bucket(g), work);
@@ -2507,7 +2518,7 @@ int pk_table_equity_hist_hero_d(pk_handle *h, const int32_t *tables_d, size_t m,
     EQ_REFUSE(h->fail, call, hh_table_check(h, m, observer, nbins, K, centroids_d, label_d, dist_d));
     const HeroHistOut out{hist_d, void_d, completions_d, status_d};
     const HeroHistBucket bk{K, centroids_d, label_d, dist_d};
-    return eq_table_call_d(h, call, tables_d, m, hh_work_bytes(m, nbins, out, bk), [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call_d(h, call, tables_d, m, EQ_TAB_EVAL, hh_work_bytes(m, nbins, out, bk), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return hh_launch(h->stream, tab, nullptr, &t, h->N, observer, EqrWeights{weights_d, weights_per_spot != 0}, m, nbins, out, bk, work);
     });
 }
@@ -2522,7 +2533,7 @@ int pk_table_equity_hist_hero(pk_handle *h, const int32_t *tables, size_t m, int
     const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
     const HeroHistStaged io(g, m, nbins, hist, void_, completions, status, K, centroids, label, dist);
     const size_t bytes = hh_work_bytes(m, nbins, HeroHistOut{hist, void_, completions, status}, HeroHistBucket{K, centroids, label, dist});
-    return eq_table_call(h, call, tables, m, g, bytes, [&](const uint32_t *tab, const EqTables &t, char *work) {
+    return eq_table_call(h, call, tables, m, EQ_TAB_EVAL, g, bytes, [&](const uint32_t *tab, const EqTables &t, char *work) {
         return hh_launch(h->stream, tab, nullptr, &t, h->N, observer, EqrWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m, nbins, io.at(g), io.bucket(g),
                          work);
     });
@@ -2556,7 +2567,7 @@ int pk_hist_cluster_seed_d(int device, size_t n, int nbins, const uint16_t *hist
     const char *call = "pk_hist_cluster_seed_d";
     EQ_REFUSE(g_fail, call, cl_check(n, nbins, K, hist_d && centroids_d));
     EQ_REFUSE(g_fail, call, cl_bad_k_rows(n, K));
-    return eq_call_d(call, device, stream, n, false, cl_work_bytes(n, nbins, K, true, false), [&](hipStream_t st, const uint32_t *, char *work) {
+    return eq_call_d(call, device, stream, n, EQ_TAB_NONE, cl_work_bytes(n, nbins, K, true, false), [&](hipStream_t st, const uint32_t *, char *work) {
         return cl_seed_launch(st, n, nbins, hist_d, K, (uint32_t)seed, (uint32_t)(seed >> 32), nonce, centroids_d, cl_work(work, n, nbins, K, true, false));
     });
 }
@@ -2565,7 +2576,7 @@ int pk_hist_cluster_assign_d(int device, size_t n, int nbins, const uint16_t *hi
                              uint32_t *dist_d, void *stream) {
     const char *call = "pk_hist_cluster_assign_d";
     EQ_REFUSE(g_fail, call, cl_check(n, nbins, K, hist_d && centroids_d && label_d));
-    return eq_call_d(call, device, stream, n, false, cl_work_bytes(n, nbins, K, false, false), [&](hipStream_t st, const uint32_t *, char *work) {
+    return eq_call_d(call, device, stream, n, EQ_TAB_NONE, cl_work_bytes(n, nbins, K, false, false), [&](hipStream_t st, const uint32_t *, char *work) {
         return cl_assign_launch(st, n, nbins, hist_d, K, centroids_d, label_d, dist_d, cl_work(work, n, nbins, K, false, false));
     });
 }
@@ -2576,7 +2587,7 @@ int pk_hist_cluster_d(int device, size_t n, int nbins, const uint16_t *hist_d, i
     EQ_REFUSE(g_fail, call, cl_check(n, nbins, K, hist_d && centroids_d && label_d));
     EQ_REFUSE(g_fail, call, cl_bad_k_rows(n, K));
     EQ_REFUSE(g_fail, call, cl_bad_iters(iters));
-    return eq_call_d(call, device, stream, n, false, cl_work_bytes(n, nbins, K, false, true), [&](hipStream_t st, const uint32_t *, char *work) {
+    return eq_call_d(call, device, stream, n, EQ_TAB_NONE, cl_work_bytes(n, nbins, K, false, true), [&](hipStream_t st, const uint32_t *, char *work) {
         return cl_cluster_launch(st, n, nbins, hist_d, K, centroids_d, iters, label_d, dist_d, inertia_d, changed_d, cl_work(work, n, nbins, K, false, true));
     });
 }
@@ -2588,7 +2599,7 @@ int pk_hist_cluster_seed(int device, size_t n, int nbins, const uint16_t *hist, 
     EQ_REFUSE(g_fail, call, cl_bad_rows(n, nbins, hist, K));
     Stage g;
     const int hi = g.in(hist, n * (size_t)nbins * 2), ce = g.out(centroids, (size_t)K * nbins * 2);
-    return eq_call_host(call, device, n, false, g, cl_work_bytes(n, nbins, K, true, false), [&](hipStream_t st, const uint32_t *, char *work) {
+    return eq_call_host(call, device, n, EQ_TAB_NONE, g, cl_work_bytes(n, nbins, K, true, false), [&](hipStream_t st, const uint32_t *, char *work) {
         return cl_seed_launch(st, n, nbins, g.at<uint16_t>(hi), K, (uint32_t)seed, (uint32_t)(seed >> 32), nonce, g.at<uint16_t>(ce), cl_work(work, n, nbins, K, true, false));
     });
 }
@@ -2598,7 +2609,7 @@ int pk_hist_cluster_assign(int device, size_t n, int nbins, const uint16_t *hist
     EQ_REFUSE(g_fail, call, cl_check(n, nbins, K, hist && centroids && label));
     Stage g;
     const int hi = g.in(hist, n * (size_t)nbins * 2), ce = g.in(centroids, (size_t)K * nbins * 2), la = g.out(label, n * 2), di = g.out(dist, n * 4);
-    return eq_call_host(call, device, n, false, g, cl_work_bytes(n, nbins, K, false, false), [&](hipStream_t st, const uint32_t *, char *work) {
+    return eq_call_host(call, device, n, EQ_TAB_NONE, g, cl_work_bytes(n, nbins, K, false, false), [&](hipStream_t st, const uint32_t *, char *work) {
         return cl_assign_launch(st, n, nbins, g.at<uint16_t>(hi), K, g.at<uint16_t>(ce), g.at<uint16_t>(la), g.at<uint32_t>(di), cl_work(work, n, nbins, K, false, false));
     });
 }
@@ -2613,9 +2624,161 @@ int pk_hist_cluster(int device, size_t n, int nbins, const uint16_t *hist, int K
     Stage g;
     const int hi = g.in(hist, n * (size_t)nbins * 2), ce = g.add((size_t)K * nbins * 2, centroids, centroids), la = g.out(label, n * 2), di = g.out(dist, n * 4);
     const int in = g.out(inertia, (size_t)(iters + 1) * 8), ch = g.out(changed, (size_t)iters * 4);
-    return eq_call_host(call, device, n, false, g, cl_work_bytes(n, nbins, K, false, true), [&](hipStream_t st, const uint32_t *, char *work) {
+    return eq_call_host(call, device, n, EQ_TAB_NONE, g, cl_work_bytes(n, nbins, K, false, true), [&](hipStream_t st, const uint32_t *, char *work) {
         return cl_cluster_launch(st, n, nbins, g.at<uint16_t>(hi), K, g.at<uint16_t>(ce), iters, g.at<uint16_t>(la), g.at<uint32_t>(di), g.at<uint64_t>(in),
                                  g.at<uint32_t>(ch), cl_work(work, n, nbins, K, false, true));
+    });
+}
+
+// ---- pre-flop matchups (pokerl_hip.h "Pre-flop matchups"; kernels: pk_preflop.hip).  The count pass's work space: the keys of one chunk of
+// boards (knob PK_PFM_CHUNK, boards).  The readers' work space: one holding index per spot.
+static uint32_t pfm_chunk() { return (uint32_t)env_int("PK_PFM_CHUNK", 1, PFM_CHUNK_MAX, PFM_CHUNK_DEFAULT); }
+// The matchup table, one per device, built on first use on `stream` (the device is current): the partial count over all boards.  The
+// build's key work space is allocated for the build and freed after it: only the table stays.
+static std::mutex g_pfm_mu;
+static DevBuf g_pfm_tab[PK_MAX_DEVICES];
+static const uint32_t *pfm_table(int device, hipStream_t stream) {
+    if (device < 0 || device >= PK_MAX_DEVICES) return nullptr;
+    std::lock_guard<std::mutex> lock(g_pfm_mu);
+    DevBuf &t = g_pfm_tab[device];
+    if (!t.alive()) {   // (not yet there, or the device was reset: build it)
+        t = DevBuf{};
+        const uint32_t *tab = eval7_table(device, stream);
+        if (!tab) return nullptr;
+        const uint32_t chunk = pfm_chunk();
+        DevBuf keys;                                 // (the build's own: 92 MB at the default chunk, freed once the table stands)
+        uint32_t *kp = (uint32_t *)keys.reserve(pfm_keys_bytes(chunk), pfm_keys_bytes(chunk), stream);
+        uint32_t *p = kp ? (uint32_t *)t.reserve(2 * PFM_CELLS * 4, 2 * PFM_CELLS * 4, stream, true) : nullptr;
+        const bool ok = p && pfm_count_launch(stream, tab, 0, PFM_BOARDS, 0, chunk, kp, p, p + PFM_CELLS) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+        keys.drop();
+        if (!ok) {
+            (void)hipGetLastError();
+            t.drop();
+            return nullptr;
+        }
+    }
+    return (const uint32_t *)t.p;
+}
+
+static const char *pfm_count_check(uint32_t first, uint32_t n) {
+    return (uint64_t)first + n > (uint64_t)PFM_BOARDS ? ": first + n above PK_PREFLOP_ALL_BOARDS (2 598 960)" : nullptr;
+}
+
+int pk_preflop_count_d(int device, uint32_t first, uint32_t n, int accumulate, uint32_t *win_d, uint32_t *tie_d, void *stream) {
+    const char *call = "pk_preflop_count_d";
+    EQ_REFUSE(g_fail, call, pfm_count_check(first, n));
+    const uint32_t chunk = pfm_chunk();
+    return eq_call_d(call, device, stream, n, EQ_TAB_EVAL, pfm_keys_bytes(chunk), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return pfm_count_launch(st, tab, first, n, accumulate, chunk, (uint32_t *)work, win_d, tie_d);
+    });
+}
+
+int pk_preflop_count(int device, uint32_t first, uint32_t n, int accumulate, uint32_t *win, uint32_t *tie) {
+    const char *call = "pk_preflop_count";
+    EQ_REFUSE(g_fail, call, pfm_count_check(first, n));
+    const uint32_t chunk = pfm_chunk();
+    Stage g;   // (an accumulating call uploads what the arrays hold)
+    const int wi = win ? g.add(PFM_CELLS * 4, accumulate ? win : nullptr, win) : -1, ti = tie ? g.add(PFM_CELLS * 4, accumulate ? tie : nullptr, tie) : -1;
+    return eq_call_host(call, device, n, EQ_TAB_EVAL, g, pfm_keys_bytes(chunk), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return pfm_count_launch(st, tab, first, n, accumulate, chunk, (uint32_t *)work, g.at<uint32_t>(wi), g.at<uint32_t>(ti));
+    });
+}
+
+int pk_preflop_matchups_d(int device, uint32_t *win_d, uint32_t *tie_d, void *stream) {
+    const char *call = "pk_preflop_matchups_d";
+    return eq_call_d(call, device, stream, (win_d || tie_d) ? 1 : 0, EQ_TAB_PREFLOP, 0, [&](hipStream_t st, const uint32_t *M, char *) {
+        hipError_t e = hipSuccess;
+        if (win_d) e = hipMemcpyAsync(win_d, M, PFM_CELLS * 4, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess && tie_d) e = hipMemcpyAsync(tie_d, M + PFM_CELLS, PFM_CELLS * 4, hipMemcpyDeviceToDevice, st);
+        return e;
+    });
+}
+
+int pk_preflop_matchups(int device, uint32_t *win, uint32_t *tie) {
+    const char *call = "pk_preflop_matchups";
+    Stage g;
+    const int wi = g.out(win, PFM_CELLS * 4), ti = g.out(tie, PFM_CELLS * 4);
+    return eq_call_host(call, device, (win || tie) ? 1 : 0, EQ_TAB_PREFLOP, g, 0, [&](hipStream_t st, const uint32_t *M, char *) {
+        hipError_t e = hipSuccess;
+        if (win) e = hipMemcpyAsync(g.at<uint32_t>(wi), M, PFM_CELLS * 4, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess && tie) e = hipMemcpyAsync(g.at<uint32_t>(ti), M + PFM_CELLS, PFM_CELLS * 4, hipMemcpyDeviceToDevice, st);
+        return e;
+    });
+}
+
+// boards / status alone are the preparation kernel's: such a call neither reads nor builds the table
+static int pfm_hero_needs(const void *agg, const void *win, const void *tie) { return agg || win || tie ? EQ_TAB_PREFLOP : EQ_TAB_NONE; }
+static const char *pfm_hero_check(size_t m, bool inputs) {
+    if (const char *why = eq_bad_m(m)) return why;
+    return eq_null(m, inputs);
+}
+
+int pk_equity_preflop_d(int device, size_t m, const uint8_t *hero_d, const uint16_t *weights_d, int weights_per_spot, uint64_t *agg_d, uint32_t *win_d,
+                        uint32_t *tie_d, uint32_t *boards_d, uint8_t *status_d, void *stream) {
+    const char *call = "pk_equity_preflop_d";
+    EQ_REFUSE(g_fail, call, pfm_hero_check(m, hero_d != nullptr));
+    return eq_call_d(call, device, stream, m, pfm_hero_needs(agg_d, win_d, tie_d), pfm_desc_bytes(m), [&](hipStream_t st, const uint32_t *M, char *work) {
+        return pfm_hero_launch(st, M, hero_d, nullptr, 0, PK_OBSERVER_NONE, PfmWeights{weights_d, weights_per_spot != 0}, m,
+                               PfmOut{agg_d, win_d, tie_d, boards_d, status_d}, (uint32_t *)work);
+    });
+}
+
+int pk_equity_preflop(int device, size_t m, const uint8_t *hero, const uint16_t *weights, int weights_per_spot, uint64_t *agg, uint32_t *win,
+                      uint32_t *tie, uint32_t *boards, uint8_t *status) {
+    const char *call = "pk_equity_preflop";
+    EQ_REFUSE(g_fail, call, pfm_hero_check(m, hero != nullptr));
+    Stage g;
+    const int he = g.in(hero, m * 2), we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const EqrStagedOut out(g, m, agg, win, tie, boards, status);
+    return eq_call_host(call, device, m, pfm_hero_needs(agg, win, tie), g, pfm_desc_bytes(m), [&](hipStream_t st, const uint32_t *M, char *work) {
+        const EqrOut o = out.at(g);
+        return pfm_hero_launch(st, M, g.at<uint8_t>(he), nullptr, 0, PK_OBSERVER_NONE, PfmWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m,
+                               PfmOut{o.agg, o.win, o.tie, o.boards, o.status}, (uint32_t *)work);
+    });
+}
+
+int pk_table_equity_preflop_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, const uint16_t *weights_d, int weights_per_spot,
+                              uint64_t *agg_d, uint32_t *win_d, uint32_t *tie_d, uint32_t *boards_d, uint8_t *status_d) {
+    const char *call = "pk_table_equity_preflop_d";
+    if (!h) return g_fail(PK_E_INVALID_ARG, "pk_table_equity_preflop_d: NULL handle");
+    EQ_REFUSE(h->fail, call, eqr_table_check(h, m, observer));
+    return eq_table_call_d(h, call, tables_d, m, pfm_hero_needs(agg_d, win_d, tie_d), pfm_desc_bytes(m), [&](const uint32_t *M, const EqTables &t, char *work) {
+        return pfm_hero_launch(h->stream, M, nullptr, &t, h->N, observer, PfmWeights{weights_d, weights_per_spot != 0}, m,
+                               PfmOut{agg_d, win_d, tie_d, boards_d, status_d}, (uint32_t *)work);
+    });
+}
+
+int pk_table_equity_preflop(pk_handle *h, const int32_t *tables, size_t m, int observer, const uint16_t *weights, int weights_per_spot, uint64_t *agg,
+                            uint32_t *win, uint32_t *tie, uint32_t *boards, uint8_t *status) {
+    const char *call = "pk_table_equity_preflop";
+    if (!h) return g_fail(PK_E_INVALID_ARG, "pk_table_equity_preflop: NULL handle");
+    EQ_REFUSE(h->fail, call, eqr_table_check(h, m, observer));
+    Stage g;
+    const int we = g.in(weights, eqr_weight_bytes(m, weights_per_spot));
+    const EqrStagedOut out(g, m, agg, win, tie, boards, status);
+    return eq_table_call(h, call, tables, m, pfm_hero_needs(agg, win, tie), g, pfm_desc_bytes(m), [&](const uint32_t *M, const EqTables &t, char *work) {
+        const EqrOut o = out.at(g);
+        return pfm_hero_launch(h->stream, M, nullptr, &t, h->N, observer, PfmWeights{g.at<uint16_t>(we), weights_per_spot != 0}, m,
+                               PfmOut{o.agg, o.win, o.tie, o.boards, o.status}, (uint32_t *)work);
+    });
+}
+
+int pk_equity_rvr_preflop_d(int device, size_t m, const uint16_t *weights_d, uint64_t *win_d, uint64_t *tie_d, uint64_t *tot_d, void *stream) {
+    const char *call = "pk_equity_rvr_preflop_d";
+    EQ_REFUSE(g_fail, call, eq_bad_m(m));
+    return eq_call_d(call, device, stream, m, EQ_TAB_PREFLOP, 0, [&](hipStream_t st, const uint32_t *M, char *) {
+        return pfm_rvr_launch(st, M, weights_d, m, win_d, tie_d, tot_d);
+    });
+}
+
+int pk_equity_rvr_preflop(int device, size_t m, const uint16_t *weights, uint64_t *win, uint64_t *tie, uint64_t *tot) {
+    const char *call = "pk_equity_rvr_preflop";
+    EQ_REFUSE(g_fail, call, eq_bad_m(m));
+    Stage g;
+    const int we = g.in(weights, m * PFM_HOLDINGS * 2);
+    const int wi = g.out(win, m * PFM_HOLDINGS * 8), ti = g.out(tie, m * PFM_HOLDINGS * 8), to = g.out(tot, m * PFM_HOLDINGS * 8);
+    return eq_call_host(call, device, m, EQ_TAB_PREFLOP, g, 0, [&](hipStream_t st, const uint32_t *M, char *) {
+        return pfm_rvr_launch(st, M, g.at<uint16_t>(we), m, g.at<uint64_t>(wi), g.at<uint64_t>(ti), g.at<uint64_t>(to));
     });
 }
 

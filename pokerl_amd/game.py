@@ -547,6 +547,53 @@ class VecGame:
                                                   self._dptr(agg_d), self._dptr(win_d), self._dptr(tie_d), self._dptr(boards_d), self._dptr(status_d)),
                 self._h)
 
+    def equity_preflop(self, observer='active', weights=None, tables=None, per_holding=False):
+        """Exact STARTING-HAND strength of `observer` (a seat, or 'active' / OBSERVER_ACTIVE: each table's active seat) against ONE hidden hand
+        at `tables` (all tables if None; indices may repeat): the observer's two hole cards against every holding of the other fifty cards
+        over every five-card board (pk_table_equity_preflop; definition: pokerl_hip.h "Pre-flop matchups").  The board is NOT read, at
+        whatever turn a table rests: a caller who wants "pre-flop here, post-flop there" passes `tables` to this call and to equity_range.
+        weights: None (uniform), uint16 [1326] (one range) or [m, 1326] over judger.holding_index.  Returns a judger.RangeEquity: agg [m, 3]
+        and `strength` [m] always, win / tie [m, 1326] and `valid` with per_holding=True (`valid` is None while asynchronous steps are in
+        flight: it is formed from the getters).  A table that cannot be evaluated (never reset, step in flight, index out of range) has a
+        non-zero status and strength 0."""
+        from .judger import RangeEquity, preflop_valid_holdings, range_weights
+        o = self._range_observer(observer)
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        w, per_spot = range_weights(weights, m)
+        win = np.zeros((m, L.EQ_HOLDINGS), np.uint32) if per_holding else None
+        tie = np.zeros((m, L.EQ_HOLDINGS), np.uint32) if per_holding else None
+        agg, boards, status = np.zeros((m, 3), np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        L.check(self._lib.pk_table_equity_preflop(self._h, L.ptr(t), m, o, L.ptr(w), per_spot, L.ptr(agg), L.ptr(win), L.ptr(tie), L.ptr(boards),
+                                                  L.ptr(status)), self._h)
+        valid = None
+        if per_holding and not status.all():    # (from the getters, which refuse with PK_E_BUSY while asynchronous steps are in flight: no mask then)
+            try:
+                deck, active = self.deck, self.active_player
+            except L.PokerlHipError as e:
+                if e.code != L.PK_E_BUSY:       # (any other failure of a getter is the caller's to see)
+                    raise
+                deck = None
+            if deck is not None:
+                idx = np.arange(self.num_tables) if t is None else t
+                sel = idx[status == 0]
+                who = active[sel].astype(np.int64) if o == L.OBSERVER_ACTIVE else np.full(len(sel), o, np.int64)
+                valid = np.zeros((m, L.EQ_HOLDINGS), bool)
+                valid[status == 0] = preflop_valid_holdings(np.stack([deck[sel, 5 + 2 * who], deck[sel, 6 + 2 * who]], axis=1))
+        elif per_holding:
+            valid = np.zeros((m, L.EQ_HOLDINGS), bool)
+        return RangeEquity(win, tie, boards, status, agg, valid)
+
+    def equity_preflop_d(self, m=None, tables_d=None, observer='active', weights_d=None, weights_per_spot=False, agg_d=None, win_d=None, tie_d=None,
+                         boards_d=None, status_d=None):
+        """pk_table_equity_preflop_d: the same into device buffers (uint64 [m, 3] agg, uint32 [m, 1326] win / tie, uint32 [m] boards, uint8 [m]
+        status; any may be None; weights_d uint16 [1326] or [m, 1326] or None), asynchronous on the handle's stream.  m defaults to every table."""
+        o = self._range_observer(observer)
+        m = self.num_tables if m is None else int(m)
+        L.check(self._lib.pk_table_equity_preflop_d(self._h, self._dptr(tables_d), m, o, self._dptr(weights_d), int(bool(weights_per_spot)),
+                                                    self._dptr(agg_d), self._dptr(win_d), self._dptr(tie_d), self._dptr(boards_d), self._dptr(status_d)),
+                self._h)
+
     def equity_rvr(self, weights=None, tables=None):
         """Range against range on the PUBLIC board of `tables` (all tables if None; indices may repeat), post-flop (pk_table_equity_rvr;
         definition: pokerl_hip.h "Range vs range"): for every holding the hero can have, the weight of the opponent's range it beats, ties

@@ -869,6 +869,149 @@ def range_vs_range(board, dead=(), weights=None, device=0):
     return r
 
 
+# ---------------------------------------------------------------------------------------------- pre-flop matchups
+# The pre-flop forms of the two families above: every ordered pair of holdings over every five-card board, counted once per device and kept
+# resident (pk_preflop_*; the definition: include/pokerl_hip.h "Pre-flop matchups").
+class PreflopMatchups:
+    """The matchup table: uint32 [1326, 1326] win / tie over judger.holding_index -- win[h, o] = boards (of `boards` = 1 712 304) on which h
+    wins alone against o, tie[h, o] = boards both win; 0 where the two share a card.  `equity` = (win + tie / 2) / boards in float64, nan
+    where the pair shares a card.  The evaluator's suit quirks are in it: it is not invariant under a renaming of suits."""
+    boards = L.PREFLOP_BOARDS
+
+    def __init__(self, win, tie):
+        self.win, self.tie = win, tie
+
+    @property
+    def shared(self):
+        """bool [1326, 1326]: the two holdings share a card (the diagonal included)."""
+        a, b = HOLDINGS[:, 0].astype(np.int64), HOLDINGS[:, 1].astype(np.int64)
+        m = (np.uint64(1) << a.astype(np.uint64)) | (np.uint64(1) << b.astype(np.uint64))     # (Card.value < 64: one bit per card)
+        return (m[:, None] & m[None, :]) != 0
+
+    @property
+    def equity(self):
+        e = (self.win.astype(np.float64) + 0.5 * self.tie.astype(np.float64)) / float(self.boards)
+        e[self.shared] = np.nan
+        return e
+
+    def __repr__(self):
+        return 'PreflopMatchups(boards=%d)' % self.boards
+
+
+def preflop_counts(first, n, win=None, tie=None, device=0):
+    """pk_preflop_count: the partial counts over the boards of rank first .. first + n - 1 (itertools.combinations(range(52), 5) order over
+    the canonical card indices) as uint32 [1326, 1326] (win, tie).  With win / tie given (C-contiguous uint32 [1326, 1326]) the counts are
+    ADDED to them in place; otherwise fresh arrays are returned.  Counts over disjoint ranges add exactly."""
+    first, n = int(first), int(n)
+    if first < 0 or n < 0 or first + n > L.PREFLOP_ALL_BOARDS:
+        raise ValueError('the board range must lie in 0 .. %d' % L.PREFLOP_ALL_BOARDS)
+    if (win is None) != (tie is None):
+        raise ValueError('give both win and tie, or neither')
+    accumulate = win is not None
+    if accumulate:
+        for a in (win, tie):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.uint32 and a.shape == (L.EQ_HOLDINGS, L.EQ_HOLDINGS) and a.flags.c_contiguous):
+                raise ValueError('win / tie must be C-contiguous uint32 [1326, 1326] arrays')
+    else:
+        win, tie = np.zeros((L.EQ_HOLDINGS, L.EQ_HOLDINGS), np.uint32), np.zeros((L.EQ_HOLDINGS, L.EQ_HOLDINGS), np.uint32)
+    L.check(L.lib().pk_preflop_count(int(device), first, n, int(accumulate), L.ptr(win), L.ptr(tie)))
+    return win, tie
+
+
+def preflop_counts_d(first, n, win_d, tie_d, accumulate=False, device=0, stream=None):
+    """pk_preflop_count_d: the same into device buffers (uint32 [1326, 1326]; either may be None), asynchronous on `stream`."""
+    L.check(L.lib().pk_preflop_count_d(int(device), int(first), int(n), int(bool(accumulate)), win_d, tie_d, stream))
+
+
+def preflop_matchups(device=0):
+    """The matchup table of `device` as a PreflopMatchups (pk_preflop_matchups): built on the device on first use -- every holding ranked
+    once per board, every pair compared on every board -- and resident from then on; a later call only copies it."""
+    win, tie = np.empty((L.EQ_HOLDINGS, L.EQ_HOLDINGS), np.uint32), np.empty((L.EQ_HOLDINGS, L.EQ_HOLDINGS), np.uint32)
+    L.check(L.lib().pk_preflop_matchups(int(device), L.ptr(win), L.ptr(tie)))
+    return PreflopMatchups(win, tie)
+
+
+def preflop_matchups_d(win_d, tie_d, device=0, stream=None):
+    """pk_preflop_matchups_d: the table into device buffers (uint32 [1326, 1326]; either may be None), asynchronous on `stream`."""
+    L.check(L.lib().pk_preflop_matchups_d(int(device), win_d, tie_d, stream))
+
+
+def preflop_valid_holdings(hero):
+    """bool [m, 1326]: the holdings that share no card with each spot's hero (host arithmetic; mask with status == 0)."""
+    hero = np.asarray(hero, np.uint8)
+    return (HOLDINGS[None, :, :, None] != hero[:, None, None, :]).all(axis=(2, 3))
+
+
+def preflop_equity_batch(hero, weights=None, per_holding=True, device=0):
+    """pk_equity_preflop on host arrays: hero uint8 [m, 2] Card.value, weights None / uint16 [1326] / [m, 1326] -> RangeEquity (boards =
+    1 712 304): the hero's starting hand against ONE hidden hand, no board.  A bad spot is reported through its `status` (PK_EQ_BAD_CARD /
+    PK_EQ_DUP_CARD) with all-zero outputs; the others are unaffected."""
+    hero = np.ascontiguousarray(hero, np.uint8)
+    if hero.ndim != 2 or hero.shape[1] != 2:
+        raise ValueError('hero must have shape [m, 2]')
+    m = hero.shape[0]
+    w, per_spot = range_weights(weights, m)
+    win = np.zeros((m, L.EQ_HOLDINGS), np.uint32) if per_holding else None
+    tie = np.zeros((m, L.EQ_HOLDINGS), np.uint32) if per_holding else None
+    agg, boards, status = np.zeros((m, 3), np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+    L.check(L.lib().pk_equity_preflop(int(device), m, L.ptr(hero), L.ptr(w), per_spot, L.ptr(agg), L.ptr(win), L.ptr(tie), L.ptr(boards),
+                                      L.ptr(status)))
+    return RangeEquity(win, tie, boards, status, agg, preflop_valid_holdings(hero) & (status == 0)[:, None])
+
+
+def preflop_equity_d(m, hero_d, weights_d=None, weights_per_spot=False, agg_d=None, win_d=None, tie_d=None, boards_d=None, status_d=None,
+                     device=0, stream=None):
+    """pk_equity_preflop_d: the same on device-resident buffers (device pointers as ints / c_void_p; weights_d and the outputs may be
+    None), asynchronous on `stream`."""
+    L.check(L.lib().pk_equity_preflop_d(int(device), int(m), hero_d, weights_d, int(bool(weights_per_spot)), agg_d, win_d, tie_d, boards_d,
+                                        status_d, stream))
+
+
+def preflop_equity(hero, weights=None, device=0):
+    """One starting hand.  hero: two cards (Card-likes / 'RS' strings / Card.value ints); weights: None or [1326] integers 0 .. 65535 over
+    holding_index.  Returns a RangeEquity with [1326] arrays and the scalar `strength`; raises ValueError for an invalid spot."""
+    hero = list(hero)
+    if len(hero) != 2:
+        raise ValueError('the hero holds two cards')
+    if weights is not None and np.ndim(weights) != 1:
+        raise ValueError('weights must have shape [1326]')
+    r = preflop_equity_batch(np.array([[_card(c) for c in hero]], np.uint8), weights, device=device)[0]
+    if r.status:
+        raise ValueError('invalid spot: ' + equity_status_text(r.status))
+    return r
+
+
+def preflop_range_vs_range_batch(weights, device=0):
+    """pk_equity_rvr_preflop on host arrays: weights uint16 [m, 1326], one opponent range per spot -> RangeVsRange with uint64 [m, 1326]
+    win / tie / tot (boards = 1 712 304, status 0, every holding valid): every starting hand against each range, no board."""
+    w = np.asarray(weights)
+    if w.dtype.kind not in 'iub' or w.ndim != 2 or w.shape[1] != L.EQ_HOLDINGS:
+        raise ValueError('weights must be integers of shape [m, 1326]')
+    if w.size and (w.min() < 0 or w.max() > 0xFFFF):
+        raise ValueError('weights must fit 16 bits')
+    w = np.ascontiguousarray(w, np.uint16)
+    m = w.shape[0]
+    win, tie, tot = (np.zeros((m, L.EQ_HOLDINGS), np.uint64) for _ in range(3))
+    L.check(L.lib().pk_equity_rvr_preflop(int(device), m, L.ptr(w), L.ptr(win), L.ptr(tie), L.ptr(tot)))
+    return RangeVsRange(win, tie, tot, np.full(m, L.PREFLOP_BOARDS, np.uint32), np.zeros(m, np.uint8), np.ones((m, L.EQ_HOLDINGS), bool))
+
+
+def preflop_range_vs_range_d(m, weights_d=None, win_d=None, tie_d=None, tot_d=None, device=0, stream=None):
+    """pk_equity_rvr_preflop_d: the same on device-resident buffers (weights_d uint16 [m, 1326] or None = ones; win / tie / tot uint64
+    [m, 1326], any may be None), asynchronous on `stream`."""
+    L.check(L.lib().pk_equity_rvr_preflop_d(int(device), int(m), weights_d, win_d, tie_d, tot_d, stream))
+
+
+def preflop_range_vs_range(weights=None, device=0):
+    """One opponent range (None: uniform; or [1326] integers 0 .. 65535 over holding_index) -> a RangeVsRange with [1326] arrays: the
+    pre-flop strength of every starting hand against it (`.strength`, `.against(hero_weights)`)."""
+    if weights is None:
+        weights = np.ones(L.EQ_HOLDINGS, np.uint16)
+    if np.ndim(weights) != 1:
+        raise ValueError('weights must have shape [1326]')
+    return preflop_range_vs_range_batch(np.asarray(weights)[None, :], device=device)[0]
+
+
 # ---------------------------------------------------------------------------------------------- strength histograms
 # For EVERY holding the hero can have on a public board: how its river strength against a weighted opponent range is distributed over the
 # completions of the board (pk_equity_hist; the definition: include/pokerl_hip.h "Strength histograms", DESIGN.md section 3.5).

@@ -138,6 +138,16 @@ class Game:
             raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
         return r
 
+    def equity_preflop(self, observer=None, weights=None):
+        """Exact starting-hand strength of `observer` (None = the active seat) against one hidden hand, the board not read
+        (VecGame.equity_preflop): a judger.RangeEquity with [1326] arrays and the scalar `strength`.  Not in the reference."""
+        from ._lib import OBSERVER_ACTIVE
+        r = self._v.equity_preflop(observer=OBSERVER_ACTIVE if observer is None else observer, weights=weights, per_holding=True)[0]
+        if r.status:
+            from .judger import equity_status_text
+            raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
+        return r
+
     def equity_rvr(self, weights=None):
         """Range against range on the public board, post-flop (VecGame.equity_rvr): a judger.RangeVsRange with [1326] arrays -- every
         holding the hero can have against the opponent's range `weights`.  Not in the reference."""

@@ -58,6 +58,7 @@ import ev_spec as EV                    # noqa: E402
 import hero_hist_spec as HHS             # noqa: E402
 import hist_cluster_spec as CS          # noqa: E402
 import hist_spec as HS                  # noqa: E402
+import preflop_spec as PS               # noqa: E402
 import rvr_spec as VS                   # noqa: E402
 from oracle import rng_spec as R        # noqa: E402
 
@@ -69,7 +70,8 @@ OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("w
            "hist": ("hist", "void", "completions", "status"), "ranged": ("win", "tie", "share", "accepted", "status"),
            "ev": ("share", "level_seat", "amount", "ev", "boards", "status"),
            "cluster": ("centroids_out", "label", "dist", "inertia", "changed"),
-           "herohist": ("hist", "void", "completions", "status")}
+           "herohist": ("hist", "void", "completions", "status"), "preflop": ("win", "tie"),
+           "pfhero": ("agg", "win", "tie", "boards", "status"), "pfrvr": ("win", "tie", "tot")}
 
 
 class Case:
@@ -837,6 +839,115 @@ def hero_hist_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- pre-flop partial counts
+OUT_FILL = 0xA5A5A5A5       # what the driver's output arrays hold before the launch
+
+
+def preflop_case(name, first, n, chunk, accumulate=0, outputs=None, quick=False):
+    arrays = {"first": ("u32", [first]), "n": ("u32", [n]), "chunk": ("u32", [chunk]), "accumulate": ("u32", [accumulate])}
+
+    def expect():
+        win, tie = PS.counts(first, n)
+        if accumulate:                                                # (added to what the arrays held, modulo 2^32)
+            win, tie = win + np.uint32(OUT_FILL), tie + np.uint32(OUT_FILL)
+        return {"win": win, "tie": tie}
+    return Case(name, "preflop", arrays, expect, outputs, quick)
+
+
+def preflop_cases():
+    """The cases of k_pfm_rank + k_pfm_count: a list of its own.  Boards from rank 1 000 000 on hold middling cards; from 0 on, the lowest."""
+    cs = [preflop_case("preflop-one-board-first", 0, 1, 64, quick=True),
+          preflop_case("preflop-one-board-last", PS.ALL_BOARDS - 1, 1, 64, quick=True),
+          # 100 boards in chunks of 40: a storing launch of one slice (32 boards), then 40 and a ragged 28; two slices per chunk, the second ragged
+          preflop_case("preflop-100-boards-chunk40", 1000003, 100, 40, quick=True),
+          preflop_case("preflop-accumulate-33-boards", 17, 33, 32, accumulate=1, quick=True),
+          preflop_case("preflop-win-alone", 2000000, 5, 64, outputs=("win",)),
+          preflop_case("preflop-tie-alone", 2000000, 5, 64, outputs=("tie",)),
+          # a chunk below one run of boards: the storing launch is capped at the chunk (the key work space holds exactly one chunk)
+          preflop_case("preflop-40-boards-chunk5", 1234567, 40, 5, quick=True),
+          preflop_case("preflop-accumulate-chunk1", 99, 3, 1, accumulate=1),
+          preflop_case("preflop-300-boards-chunk128", 2598960 - 300, 300, 128)]
+    cs += preflop_reader_cases()
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
+_pf_table = []
+
+
+def preflop_table():
+    """The table the driver hands the readers (equity_sim.cpp fill_table): a fixed pattern, win and tie uint32 [1326, 1326]."""
+    if not _pf_table:
+        i = np.arange(HOLDINGS * HOLDINGS, dtype=np.uint64)
+        win = (((i * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)) >> np.uint64(11)).astype(np.uint32)
+        tie = (((i * np.uint64(40503) + np.uint64(7)) & np.uint64(0xFFFFFFFF)) & np.uint64(1023)).astype(np.uint32)
+        _pf_table.append((win.reshape(HOLDINGS, HOLDINGS), tie.reshape(HOLDINGS, HOLDINGS)))
+    return _pf_table[0]
+
+
+def pf_hero_expect(hero, w, per_spot):
+    win, tie = preflop_table()
+    m = len(hero)
+    out = dict(agg=np.zeros((m, 3), np.uint64), win=np.zeros((m, HOLDINGS), np.uint32), tie=np.zeros((m, HOLDINGS), np.uint32),
+               boards=np.zeros(m, np.uint32), status=np.zeros(m, np.uint8))
+    for i in range(m):
+        r = PS.hero_equity(win, tie, hero[i], None if w is None else (w[i] if per_spot else w))
+        for k in out:
+            out[k][i] = r[k]
+    return out
+
+
+def pf_hero_case(name, m, seed, grid, wform=None, outputs=None, quick=False, edit=None):
+    rng = np.random.default_rng(seed)
+    hero = np.array([[card(c) for c in rng.permutation(52)[:2]] for _ in range(m)], np.uint8)
+    if edit:
+        edit(hero)
+    w, per_spot = weights_for(seed + 1, m, wform)
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [grid]), "hero": ("u8", hero), "weights": ("u16", w), "per_spot": ("u32", [per_spot])}
+    return Case(name, "pfhero", arrays, lambda: pf_hero_expect(hero, w, per_spot), outputs, quick)
+
+
+def preflop_reader_cases():
+    """k_pfm_prep + k_pfm_hero (family pfhero) and k_pfm_rvr (family pfrvr) on the fixed table."""
+    cs = []
+
+    def ends(hero):
+        hero[0], hero[1] = [card(0), card(1)], [card(51), card(50)]      # holdings 0 and 1325
+
+    def bits(hero):
+        hero[1] = [0x4A, 0x01]                                        # suit 4: no card
+        hero[2] = [0x05, 0xFF]
+        hero[4] = [0x21, 0x21]                                        # the same card twice
+    # ONE workgroup takes every spot in turn: the sums of the spot before are read before the next one's are written
+    cs.append(pf_hero_case("pfhero-grid1-five-spots", 5, 71, 1, "shared", quick=True, edit=ends))
+    cs.append(pf_hero_case("pfhero-spot-weights-grid2", 5, 72, 2, "spot", quick=True))
+    cs.append(pf_hero_case("pfhero-no-weights-refused-between", 6, 73, 4, None, quick=True, edit=bits))
+    cs.append(pf_hero_case("pfhero-zero-weights", 2, 74, 2, "zero"))
+    cs.append(pf_hero_case("pfhero-status-alone", 6, 73, 4, None, outputs=("status",), quick=True, edit=bits))
+    for o in OUTPUTS["pfhero"]:
+        cs.append(pf_hero_case("pfhero-no-" + o, 3, 75, 1, "shared", outputs=[x for x in OUTPUTS["pfhero"] if x != o]))
+    for observer, who in ((1, lambda w: np.full(w["T"], 1)), (-2, lambda w: w["active"])):
+        w = table_world(76, 3, 6)                                     # tables at every turn: the board is not read
+        arrays = dict(table_arrays(w), m=("u32", [len(w["tables"])]), grid=("u32", [2]), observer=("i32", [observer]))
+
+        def expect(w=w, who=who):
+            seat = np.asarray(who(w), np.int64)
+            rows = np.arange(w["T"])
+            hero = np.stack([w["deck"][rows, 5 + 2 * seat], w["deck"][rows, 6 + 2 * seat]], axis=1)
+            return table_expect(w, pf_hero_expect(hero, None, 0), ("agg", "win", "tie"), "boards")
+        cs.append(Case("pfhero-table-form-observer%d" % observer, "pfhero", arrays, expect, quick=(observer == -2)))
+    for name, m, wform, quick in (("pfrvr-two-rows", 2, "spot", True), ("pfrvr-no-weights", 1, None, False)):
+        w, _ = weights_for(77, m, wform)
+        arrays = {"m": ("u32", [m]), "weights": ("u16", w)}
+
+        def expect(w=w, m=m):
+            win, tie = preflop_table()
+            rw, rt, tot = PS.rvr(win, tie, np.ones((m, HOLDINGS), np.uint16) if w is None else w)
+            return {"win": rw, "tie": rt, "tot": tot}
+        cs.append(Case(name, "pfrvr", arrays, expect, quick=quick))
+    return cs
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -851,7 +962,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + cluster_cases() + hero_hist_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

@@ -1,5 +1,5 @@
 // Dev-only: the REAL equity kernels -- k_equity<N>, k_eqs<N>, k_eqr, k_rvr, k_hist, k_hero_hist, k_eqw<N, RC> and their preparation kernels, the text of
-// pokerl_amd/csrc/pk_equity*.hip -- run on the CPU as workgroups of 8 waves x 64 lanes (wg_shim.h: a fibre per lane, every collective and
+// pokerl_amd/csrc/pk_equity*.hip, and k_pfm_rank / k_pfm_count of pk_preflop.hip -- run on the CPU as workgroups of 8 waves x 64 lanes (wg_shim.h: a fibre per lane, every collective and
 // barrier a checked rendezvous, garbage LDS before every workgroup, PK_IDX active).  One case per run: the case file names the family, the
 // spots, the weights / bins / samples, the grid and which outputs are wanted; the preparation kernel runs, then the main kernel, and every
 // output array goes to the out file.  Expected values are NOT computed here: tools/host_sim/equity_cases.py writes the case files and compares
@@ -9,7 +9,11 @@
 //   equity_sim <case file> <out file>
 // Case file: lines "name dtype count" (dtype u8 u16 u32 u64 i32) each followed by a line of `count` decimal values, and
 // "family <name>" / "outputs <name> ..." lines.  Out file: the same array format.
-// -DPK_ES_ONLY=1 .. 9: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist), so that a test can compile them side by side.
+// -DPK_ES_ONLY=1 .. 10: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist, preflop), so that a test can compile them side by side.
+// The preflop family (pk_preflop.hip) is the partial count: the driver queues k_pfm_rank and k_pfm_count chunk by chunk in the order of
+// pk::pfm_count_launch, with the case's board range, chunk and `accumulate` (the outputs start from 0xA5 bytes: an accumulating case adds to them).
+// Its readers are the families pfhero (k_pfm_prep, k_pfm_hero) and pfrvr (k_pfm_rvr) of the same build; the table they read is a fixed pattern
+// (fill_table; equity_cases.py preflop_table restates it), not a counted one: what the readers do with the numbers is what is checked.
 // The herohist family (pk_equity_hist_hero.hip) checks its spots with k_eqr_prep; its optional bucket stage is the cluster family's assign and is not run here.
 // The cluster family (pk_hist_cluster.hip) has no preparation kernel: the driver queues its kernels in the order of pk::cl_seed_launch /
 // cl_assign_launch / cl_cluster_launch (`op` 0 / 1 / 2), with the case's grid, seeding chunk and choice of the update kernel.
@@ -53,6 +57,9 @@
 #include "../../pokerl_amd/csrc/pk_equity_hist_hero.hip"
 #endif
 
+#if PK_ES_HAS(10)
+#include "../../pokerl_amd/csrc/pk_preflop.hip"
+#endif
 #include <chrono>
 #include <climits>
 #include <fstream>
@@ -461,6 +468,82 @@ void run_cluster(Case &c) {
 }
 #endif
 
+#if PK_ES_HAS(10)
+// k_pfm_rank, k_pfm_count<STORE>: the launches of pk::pfm_count_launch
+void run_preflop(Case &c, const uint32_t *tab) {
+    const uint32_t first = (uint32_t)c.num("first"), n = (uint32_t)c.num("n"), chunk = (uint32_t)c.num("chunk");
+    const int accumulate = (int)c.num("accumulate", 0);
+    uint32_t *win = c.output<uint32_t>("win", "u32", PFM_CELLS), *tie = c.output<uint32_t>("tie", "u32", PFM_CELLS);
+    // the key work space holds ONE chunk.  Under ASan it is exactly that; otherwise a run of untouched rows follows it and is looked at
+    // afterwards, so that a launch that ranks more boards than a chunk is caught by any build
+#if defined(__SANITIZE_ADDRESS__)
+    const size_t guard = 0;
+#else
+    const size_t guard = (size_t)PFM_RUN * PFM_STRIDE;
+#endif
+    const size_t nkeys = (size_t)chunk * PFM_STRIDE;
+    Work<uint32_t> keys(nkeys + guard);
+    const uint32_t slice = pk::pfm_slice_boards(chunk);
+    bool store = accumulate == 0;
+    unsigned launches = 0;
+    for (uint32_t pos = first, end = first + n; pos < end;) {
+        const uint32_t cap = store && slice < chunk ? slice : chunk, cn = end - pos < cap ? end - pos : cap;
+        uint32_t *kp = keys.p;
+        pk_sim::launch((cn + PFM_RANK_BOARDS - 1) / PFM_RANK_BOARDS, PFM_RANK_BLOCK, [&] { k_pfm_rank(tab, pos, cn, kp); });
+        const unsigned grid = PFM_STRIPS * PFM_STRIPS * ((cn + slice - 1) / slice);
+        if (store) pk_sim::launch(grid, PFM_COUNT_BLOCK, [&] { k_pfm_count<true>(kp, cn, slice, win, tie); });
+        else pk_sim::launch(grid, PFM_COUNT_BLOCK, [&] { k_pfm_count<false>(kp, cn, slice, win, tie); });
+        store = false;
+        pos += cn;
+        ++launches;
+    }
+    for (size_t i = 0; i < guard; ++i)
+        if (keys.p[nkeys + i] != 0x5A5A5A5Au) die("the key work space of one chunk was overrun at word " + std::to_string(nkeys + i));
+    printf("chunks %u (slice %u boards)\n", launches, slice);
+}
+
+// the readers' table: win, then tie, a fixed pattern
+void fill_table(uint32_t *M) {
+    for (size_t i = 0; i < PFM_CELLS; ++i) {
+        M[i] = ((uint32_t)i * 2654435761u) >> 11;
+        M[PFM_CELLS + i] = ((uint32_t)i * 40503u + 7u) & 1023u;
+    }
+}
+
+// k_pfm_prep<TABLE>, k_pfm_hero
+void run_preflop_hero(Case &c) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const int N = (int)c.num("N", 2);
+    PfmPrepArgs a{};
+    const bool tbl = table_form(c, N, m, a.t);
+    if (!tbl) a.hero = c.need<uint8_t>("hero", m * 2);
+    const int per_spot = (int)c.num("per_spot", 0);
+    const PfmWeights wts{c.arr<uint16_t>("weights", per_spot ? m * PFM_HOLDINGS : (size_t)PFM_HOLDINGS), per_spot};
+    PfmOut out{};
+    out.agg = c.output<uint64_t>("agg", "u64", m * 3); out.win = c.output<uint32_t>("win", "u32", m * PFM_HOLDINGS); out.tie = c.output<uint32_t>("tie", "u32", m * PFM_HOLDINGS);
+    out.boards = c.output<uint32_t>("boards", "u32", m); out.status = c.output<uint8_t>("status", "u8", m);
+    Work<uint32_t> desc(m), M(2 * PFM_CELLS);
+    fill_table(M.p);
+    a.out = out; a.desc = desc.p; a.N = N; a.observer = (int)c.num("observer", 0); a.m = m;
+    if (tbl) pk_sim::launch(prep_grid(m, PFM_PREP_BLOCK), PFM_PREP_BLOCK, [&] { k_pfm_prep<true>(a); });
+    else pk_sim::launch(prep_grid(m, PFM_PREP_BLOCK), PFM_PREP_BLOCK, [&] { k_pfm_prep<false>(a); });
+    const uint32_t *dp = desc.p, *mp = M.p;
+    if (out.agg || out.win || out.tie) pk_sim::launch(grid, PFM_READ_BLOCK, [&] { k_pfm_hero(mp, dp, wts, out, (uint32_t)m); });
+}
+
+// k_pfm_rvr: the grid is the kernel's own, PFM_RVR_ROWS rows per workgroup
+void run_preflop_rvr(Case &c) {
+    const size_t m = (size_t)c.num("m");
+    const uint16_t *w = c.arr<uint16_t>("weights", m * PFM_HOLDINGS);
+    uint64_t *win = c.output<uint64_t>("win", "u64", m * PFM_HOLDINGS), *tie = c.output<uint64_t>("tie", "u64", m * PFM_HOLDINGS), *tot = c.output<uint64_t>("tot", "u64", m * PFM_HOLDINGS);
+    Work<uint32_t> M(2 * PFM_CELLS);
+    fill_table(M.p);
+    const uint32_t *mp = M.p;
+    pk_sim::launch(PFM_HOLDINGS / PFM_RVR_ROWS, PFM_READ_BLOCK, [&] { k_pfm_rvr(mp, w, (uint32_t)m, win, tie, tot); });
+}
+#endif
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -468,7 +551,7 @@ int main(int argc, char **argv) {
     Case c(argv[1]);
     // the function-local __shared__ arrays of the main kernels (the preparation kernels have none)
     const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "11k_hero_histPKj", "5k_eqwILi", "4k_evILi", "10k_cl_quant", "11k_cl_assign",
-                                        "11k_cl_update", "14k_cl_seed_dist", "14k_cl_seed_pick"});
+                                        "11k_cl_update", "14k_cl_seed_dist", "14k_cl_seed_pick", "10k_pfm_rank", "11k_pfm_count", "10k_pfm_hero", "9k_pfm_rvr"});
     Work<uint32_t> tab(EVAL7_TAB_WORDS);
     for (int i = 0; i < EVAL7_TAB_WORDS; ++i) tab.p[i] = eval7_tab_entry((uint32_t)i);
     const auto t0 = std::chrono::steady_clock::now();
@@ -517,6 +600,11 @@ int main(int argc, char **argv) {
 #endif
 #if PK_ES_HAS(9)
     if (c.family == "herohist") { run_hero_hist(c, tab.p); ran = true; }
+#endif
+#if PK_ES_HAS(10)
+    if (c.family == "preflop") { run_preflop(c, tab.p); ran = true; }
+    if (c.family == "pfhero") { run_preflop_hero(c); ran = true; }
+    if (c.family == "pfrvr") { run_preflop_rvr(c); ran = true; }
 #endif
     if (!ran) die("family " + c.family + ": not in this build");
     c.write(argv[2]);

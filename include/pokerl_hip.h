@@ -845,6 +845,50 @@ int pk_table_equity_ev_d(pk_handle *h, const int32_t *tables_d, size_t m, uint64
                          uint32_t *boards_d, uint8_t *status_d);
 int pk_table_equity_ev(pk_handle *h, const int32_t *tables, size_t m, uint64_t *share, uint8_t *level_seat, double *amount, double *ev,
                        uint32_t *boards, uint8_t *status);
+/* ---- Ranged showdown EV: "with what I believe about their hands, what am I paid in chips if I call?" -- the side pots of "Showdown EV"
+ * over attempts in which every hidden seat draws its holding from a weighted range, as in "Ranged sampled equity" (DESIGN.md section 3.11).
+ * Everything not stated here is "Ranged sampled equity" for cards, ranges, attempts and streams, and "Showdown EV" for bets, levels and ev.
+ *
+ * A SPOT is a "Ranged sampled equity" spot (a live seat shows both hole cards or hides both; weights u16 [R][1326], R <= PK_EQW_MAX_RANGES,
+ * range_of u16 per seat) plus bets f64 [N]: what each seat has put into the pot this hand, seats that are not live included.
+ * STATUS: the bits of "Ranged sampled equity" plus PK_EQ_BAD_BET (64, free in that family) for a bet that is negative, NaN or infinite, read
+ * from its bits (-0.0 is a zero, and is read as +0.0).  A refused spot gets zeros everywhere, level_seat = 0xFF, accepted = 0, and disturbs no neighbour.
+ * LEVELS: exactly the loop of "Showdown EV", on bets and live only: the same level_seat u8 [m][N] and amount f64 [m][N].
+ * ATTEMPT s of a spot is the attempt of "Ranged sampled equity", verbatim: stream 'EQW0' with the same key, id, nonce and S, the holdings by
+ * cumulative search, rejection, the board from word X[H].  For the same arguments the set of accepted attempts, their cards and `accepted`
+ * equal those of pk_equity_ranged.
+ * PER ACCEPTED ATTEMPT: v[p] = eval_hand(board + hole[p]) for live seats; for every level i that is not LAST and whose amount is > 0:
+ * W_i = compare_rankings(v with every seat outside remain_i set to (NONE, [])), share[i][p] += 720720 / |W_i| for p in W_i.  The LAST level
+ * gets 720720 * accepted at its seat.  A level with amount 0, or that does not exist, stays 0.
+ *   share      u64 [m][N][N]  level-major          level_seat u8 [m][N]     amount f64 [m][N]
+ *   accepted   u32 [m]                             status     u8 [m]
+ *   ev         f64 [m][N]     acc = +0.0;  for i ascending: acc = acc + (amount[i] * (double)share[i][p]) / (720720.0 * (double)accepted);
+ *                             ev[p] = acc - bets[p] -- every operation rounded on its own.  With accepted == 0 the ev row is +0.0: status 0,
+ *                             no estimate, the caller reads `accepted`.
+ * `status` may not be NULL; every other output may.  S = 1 .. 2^24; m * ceil(S / 64) * G must fit 32 bits, G = ceil((N - 1) / L) groups of
+ * levels (L = 3 up to eight seats, 2 beyond): otherwise PK_E_INVALID_ARG.  num_ranges > PK_EQW_MAX_RANGES, or > 0 with weights NULL:
+ * PK_E_INVALID_ARG before any launch.  share and accepted of calls with different nonces add exactly; ev of the sum is the formula applied to
+ * the summed counts (formed by the caller).
+ * TABLE FORM: observer is a seat or PK_OBSERVER_ACTIVE (PK_OBSERVER_NONE: PK_E_INVALID_ARG); cards and live seats are exactly
+ * pk_table_equity_ranged's spot for that observer (folded seats are not dead and not read); bets = bets + pending_bets per seat, one binary64
+ * addition each, as pk_table_equity_ev; range_of u16 [N], or [m][N] with range_per_table.  Completes deferred rollout work, reads only, runs on
+ * the handle's stream; PK_EQ_IN_FLIGHT / PK_EQ_BAD_TABLE / PK_EQ_DUP_CARD per table; PK_EQ_BAD_BET can be met through the negative-credit
+ * quirk of "Showdown EV".  STREAMS and work space: as pk_equity_ranged; the work space also holds the levels, the bets, the amounts, and
+ * share / accepted when they are NULL. */
+int pk_ev_ranged_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
+                   const uint16_t *live_d, const double *bets_d /*[m][N]*/, const uint32_t *ids_d /* NULL: i */, uint32_t samples, uint64_t seed,
+                   uint32_t nonce, const uint16_t *weights_d /*[R][1326]*/, uint32_t num_ranges, const uint16_t *range_of_d /*[m][N], NULL: uniform*/,
+                   uint64_t *share_d, uint8_t *level_seat_d, double *amount_d, double *ev_d, uint32_t *accepted_d, uint8_t *status_d, void *stream);
+int pk_ev_ranged(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
+                 const double *bets, const uint32_t *ids /* NULL: i */, uint32_t samples, uint64_t seed, uint32_t nonce, const uint16_t *weights,
+                 uint32_t num_ranges, const uint16_t *range_of, uint64_t *share, uint8_t *level_seat, double *amount, double *ev, uint32_t *accepted,
+                 uint8_t *status);
+int pk_table_ev_ranged_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce, const uint16_t *weights_d,
+                         uint32_t num_ranges, const uint16_t *range_of_d, int range_per_table, uint64_t *share_d, uint8_t *level_seat_d,
+                         double *amount_d, double *ev_d, uint32_t *accepted_d, uint8_t *status_d);
+int pk_table_ev_ranged(pk_handle *h, const int32_t *tables, size_t m, int observer, uint32_t samples, uint32_t nonce, const uint16_t *weights,
+                       uint32_t num_ranges, const uint16_t *range_of, int range_per_table, uint64_t *share, uint8_t *level_seat, double *amount,
+                       double *ev, uint32_t *accepted, uint8_t *status);
 /* ---- Histogram clustering: bucket strength histograms on the device -- exact k-means under the earth mover's distance (DESIGN.md section
  * 3.8).  Everything is an integer; the device equals the numpy restatement tests/hist_cluster_spec.py bit for bit.
  *

@@ -52,6 +52,7 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_equity_hist_hero_d", "pk_equity_hist_hero", "pk_table_equity_hist_hero_d", "pk_table_equity_hist_hero",
            "pk_equity_ranged_d", "pk_equity_ranged", "pk_table_equity_ranged_d", "pk_table_equity_ranged",
            "pk_equity_ev_d", "pk_equity_ev", "pk_table_equity_ev_d", "pk_table_equity_ev",
+           "pk_ev_ranged_d", "pk_ev_ranged", "pk_table_ev_ranged_d", "pk_table_ev_ranged",
            "pk_hist_cluster_seed_d", "pk_hist_cluster_assign_d", "pk_hist_cluster_d", "pk_hist_cluster_seed", "pk_hist_cluster_assign", "pk_hist_cluster",
            "pk_preflop_count_d", "pk_preflop_count", "pk_preflop_matchups_d", "pk_preflop_matchups",
            "pk_equity_preflop_d", "pk_equity_preflop", "pk_table_equity_preflop_d", "pk_table_equity_preflop",
@@ -169,6 +170,10 @@ def lib():
     L.pk_equity_ranged.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_uint32, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp] + [_vp] * 5
     L.pk_table_equity_ranged_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_int] + [_vp] * 5
     L.pk_table_equity_ranged.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_int] + [_vp] * 5
+    L.pk_ev_ranged_d.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 6 + [C.c_uint32, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp] + [_vp] * 7
+    L.pk_ev_ranged.argtypes = [C.c_int, C.c_int, C.c_size_t] + [_vp] * 6 + [C.c_uint32, C.c_uint64, C.c_uint32, _vp, C.c_uint32, _vp] + [_vp] * 6
+    L.pk_table_ev_ranged_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_int] + [_vp] * 6
+    L.pk_table_ev_ranged.argtypes = [_vp, _vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_int] + [_vp] * 6
     L.pk_equity_range_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_int] + [_vp] * 6
     L.pk_equity_range.argtypes = [C.c_int, C.c_size_t] + [_vp] * 5 + [C.c_int] + [_vp] * 5
     L.pk_table_equity_range_d.argtypes = [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_int] + [_vp] * 5

@@ -19,6 +19,7 @@
 #include "pk_equity_ev.hpp"
 #include "pk_equity_sampled.hpp"
 #include "pk_equity_ranged.hpp"
+#include "pk_ev_ranged.hpp"
 #include "pk_equity_range.hpp"
 #include "pk_equity_rvr.hpp"
 #include "pk_equity_hist.hpp"
@@ -2282,6 +2283,111 @@ int pk_table_equity_ranged(pk_handle *h, const int32_t *tables, size_t m, int ob
     return eq_table_call(h, call, tables, m, EQ_TAB_EVAL, g, eqw_work_bytes(h->N, m, num_ranges), [&](const uint32_t *tab, const EqTables &t, char *work) {
         return eqw_launch(h->stream, tab, nullptr, &t, observer, eqs_table_stream(h, nonce, samples),
                           EqwRanges{g.at<uint16_t>(wt), num_ranges, g.at<uint16_t>(ro), range_per_table ? 1 : 0}, h->N, m, eqw_out(out.at(g)), work);
+    });
+}
+
+// ---- ranged showdown EV in chips (pokerl_hip.h "Ranged showdown EV"; kernels: pk_ev_ranged.hip).  Work space: the ranged family's (cumulative
+// sums, descriptors), then the level table, the bets, the amounts and -- when the caller does not ask for them -- `share` and `accepted`.
+struct EvwStagedOut {
+    int share, level_seat, amount, ev, accepted, status;
+    EvwStagedOut(Stage &g, int N, size_t m, uint64_t *share, uint8_t *level_seat, double *amount, double *ev, uint32_t *accepted, uint8_t *status)
+        : share(g.out(share, m * N * N * 8)), level_seat(g.out(level_seat, m * N)), amount(g.out(amount, m * N * 8)), ev(g.out(ev, m * N * 8)),
+          accepted(g.out(accepted, m * 4)), status(g.out(status, m)) {}
+    EvwOut at(const Stage &g) const {
+        return EvwOut{g.at<uint64_t>(share), g.at<uint8_t>(level_seat), g.at<double>(amount), g.at<double>(ev), g.at<uint32_t>(accepted), g.at<uint8_t>(status)};
+    }
+};
+static const char *evw_bad_tasks(int N, size_t m, uint32_t samples) {
+    return evw_task_bound(N, m, samples) > EQ_TASKS_MAX ? ": m * ceil(samples / 64) * (groups of levels) must fit 32 bits: split the batch" : nullptr;
+}
+static const char *evw_check(int num_players, size_t m, uint32_t samples, bool inputs_and_status, const uint16_t *weights, uint32_t num_ranges) {
+    if (const char *why = eq_bad_spots(num_players, m)) return why;
+    if (const char *why = eqs_bad_samples(samples)) return why;
+    if (const char *why = eqw_bad_ranges(weights, num_ranges)) return why;
+    if (const char *why = eq_null(m, inputs_and_status, ": NULL input buffer or NULL status")) return why;
+    return evw_bad_tasks(num_players, m, samples);
+}
+static const char *evw_table_check(const pk_handle *h, size_t m, int observer, uint32_t samples, const uint16_t *weights, uint32_t num_ranges,
+                                   const uint8_t *status) {
+    if (const char *why = eq_bad_m(m)) return why;
+    if (const char *why = eqs_bad_samples(samples)) return why;
+    if (const char *why = eqw_bad_observer(observer, h->N)) return why;
+    if (const char *why = eqw_bad_ranges(weights, num_ranges)) return why;
+    if (const char *why = eq_null(m, status, ": NULL status")) return why;
+    return evw_bad_tasks(h->N, m, samples);
+}
+
+int pk_ev_ranged_d(int device, int num_players, size_t m, const uint8_t *holes_d, const uint8_t *board_d, const uint8_t *nboard_d,
+                   const uint16_t *live_d, const double *bets_d, const uint32_t *ids_d, uint32_t samples, uint64_t seed, uint32_t nonce,
+                   const uint16_t *weights_d, uint32_t num_ranges, const uint16_t *range_of_d, uint64_t *share_d, uint8_t *level_seat_d,
+                   double *amount_d, double *ev_d, uint32_t *accepted_d, uint8_t *status_d, void *stream) {
+    const char *call = "pk_ev_ranged_d";
+    EQ_REFUSE(g_fail, call, evw_check(num_players, m, samples, holes_d && board_d && nboard_d && live_d && bets_d && status_d, weights_d, num_ranges));
+    const int N = num_players;
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, evw_layout(N, m, num_ranges, !share_d, !accepted_d, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        EvwWork w;
+        evw_layout(N, m, num_ranges, !share_d, !accepted_d, work, &w);
+        const EqSpots spots{holes_d, board_d, nboard_d, live_d};
+        return evw_launch(st, tab, &spots, bets_d, nullptr, PK_OBSERVER_ACTIVE, eqs_seed_stream(seed, nonce, samples, ids_d),
+                          EqwRanges{weights_d, num_ranges, range_of_d, 1}, N, m, EvwOut{share_d, level_seat_d, amount_d, ev_d, accepted_d, status_d}, w);
+    });
+}
+
+int pk_ev_ranged(int device, int num_players, size_t m, const uint8_t *holes, const uint8_t *board, const uint8_t *nboard, const uint16_t *live,
+                 const double *bets, const uint32_t *ids, uint32_t samples, uint64_t seed, uint32_t nonce, const uint16_t *weights,
+                 uint32_t num_ranges, const uint16_t *range_of, uint64_t *share, uint8_t *level_seat, double *amount, double *ev, uint32_t *accepted,
+                 uint8_t *status) {
+    const char *call = "pk_ev_ranged";
+    EQ_REFUSE(g_fail, call, evw_check(num_players, m, samples, holes && board && nboard && live && bets && status, weights, num_ranges));
+    const int N = num_players;
+    Stage g;
+    const int ho = g.in(holes, m * N * 2), bo = g.in(board, m * 5), nb = g.in(nboard, m), lv = g.in(live, m * 2), be = g.in(bets, m * N * 8), id = g.in(ids, m * 4);
+    const int wt = g.in(num_ranges ? weights : nullptr, (size_t)num_ranges * EQW_HOLDINGS * 2), ro = g.in(range_of, m * (size_t)N * 2);
+    const EvwStagedOut out(g, N, m, share, level_seat, amount, ev, accepted, status);
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, evw_layout(N, m, num_ranges, !share, !accepted, nullptr, nullptr), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        EvwWork w;
+        evw_layout(N, m, num_ranges, !share, !accepted, work, &w);
+        const EqSpots spots{g.at<uint8_t>(ho), g.at<uint8_t>(bo), g.at<uint8_t>(nb), g.at<uint16_t>(lv)};
+        return evw_launch(st, tab, &spots, g.at<double>(be), nullptr, PK_OBSERVER_ACTIVE, eqs_seed_stream(seed, nonce, samples, g.at<uint32_t>(id)),
+                          EqwRanges{g.at<uint16_t>(wt), num_ranges, g.at<uint16_t>(ro), 1}, N, m, out.at(g), w);
+    });
+}
+
+// The table forms: the handle's own state as `observer` sees it, bets = bets + pending_bets
+int pk_table_ev_ranged_d(pk_handle *h, const int32_t *tables_d, size_t m, int observer, uint32_t samples, uint32_t nonce, const uint16_t *weights_d,
+                         uint32_t num_ranges, const uint16_t *range_of_d, int range_per_table, uint64_t *share_d, uint8_t *level_seat_d,
+                         double *amount_d, double *ev_d, uint32_t *accepted_d, uint8_t *status_d) {
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_ev_ranged_d";
+    EQ_REFUSE(h->fail, call, evw_table_check(h, m, observer, samples, weights_d, num_ranges, status_d));
+    const int N = h->N;
+    return eq_table_call_d(h, call, tables_d, m, EQ_TAB_EVAL, evw_layout(N, m, num_ranges, !share_d, !accepted_d, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        EvwWork w;
+        evw_layout(N, m, num_ranges, !share_d, !accepted_d, work, &w);
+        const EvTables et{t, h->S.bets, h->S.pending};     // (the handle's bets and pending chips beside the tables)
+        return evw_launch(h->stream, tab, nullptr, nullptr, &et, observer, eqs_table_stream(h, nonce, samples),
+                          EqwRanges{weights_d, num_ranges, range_of_d, range_per_table ? 1 : 0}, N, m,
+                          EvwOut{share_d, level_seat_d, amount_d, ev_d, accepted_d, status_d}, w);
+    });
+}
+
+int pk_table_ev_ranged(pk_handle *h, const int32_t *tables, size_t m, int observer, uint32_t samples, uint32_t nonce, const uint16_t *weights,
+                       uint32_t num_ranges, const uint16_t *range_of, int range_per_table, uint64_t *share, uint8_t *level_seat, double *amount,
+                       double *ev, uint32_t *accepted, uint8_t *status) {
+    if (!h) return PK_E_INVALID_ARG;
+    const char *call = "pk_table_ev_ranged";
+    EQ_REFUSE(h->fail, call, evw_table_check(h, m, observer, samples, weights, num_ranges, status));
+    const int N = h->N;
+    Stage g;
+    const int wt = g.in(num_ranges ? weights : nullptr, (size_t)num_ranges * EQW_HOLDINGS * 2);
+    const int ro = g.in(range_of, (range_per_table ? m : (size_t)1) * (size_t)N * 2);
+    const EvwStagedOut out(g, N, m, share, level_seat, amount, ev, accepted, status);
+    return eq_table_call(h, call, tables, m, EQ_TAB_EVAL, g, evw_layout(N, m, num_ranges, !share, !accepted, nullptr, nullptr), [&](const uint32_t *tab, const EqTables &t, char *work) {
+        EvwWork w;
+        evw_layout(N, m, num_ranges, !share, !accepted, work, &w);
+        const EvTables et{t, h->S.bets, h->S.pending};
+        return evw_launch(h->stream, tab, nullptr, nullptr, &et, observer, eqs_table_stream(h, nonce, samples),
+                          EqwRanges{g.at<uint16_t>(wt), num_ranges, g.at<uint16_t>(ro), range_per_table ? 1 : 0}, N, m, out.at(g), w);
     });
 }
 

@@ -352,6 +352,11 @@ extern template bool eqw_run_class<16>(int, hipStream_t, unsigned, const uint32_
 #endif
 
 #if EQW_SHARED_PART
+hipError_t eqw_launch_cdf(hipStream_t stream, const uint16_t *weights, uint32_t *cum, uint32_t R) {
+    if (R) hipLaunchKernelGGL(k_eqw_cdf, dim3(R), dim3(64), 0, stream, weights, cum, R);
+    return hipGetLastError();
+}
+
 hipError_t eqw_launch(hipStream_t stream, const uint32_t *tab, const EqSpots *spots, const EqTables *tables, int observer, const EqsStream &rng,
                       const EqwRanges &ranges, int N, size_t m, const EqwOut &out, char *work) {
     if (m == 0) return hipSuccess;

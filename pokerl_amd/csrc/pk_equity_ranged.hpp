@@ -52,6 +52,8 @@ struct EqwRanges {        // weights u16 [R][1326]; range_of u16 [m][N] (per_spo
 // The task split is the sampled family's (eqs_lpt).  `tables` non-NULL selects the table form, whose `observer` is a seat or PK_OBSERVER_ACTIVE.
 hipError_t eqw_launch(hipStream_t stream, const uint32_t *tab, const EqSpots *spots, const EqTables *tables, int observer, const EqsStream &rng,
                       const EqwRanges &ranges, int N, size_t m, const EqwOut &out, char *work);
+// k_eqw_cdf alone, for another family that draws from the same rows (pk_ev_ranged.hip): cum u32 [R][1326]; R = 0 queues nothing
+hipError_t eqw_launch_cdf(hipStream_t stream, const uint16_t *weights, uint32_t *cum, uint32_t R);
 // the sampling kernel of one LDS size class (each class is an object file of its own: pokerl_amd/build.py)
 template <int RC>
 bool eqw_run_class(int n, hipStream_t stream, unsigned grid, const uint32_t *tab, const uint32_t *cum, const uint64_t *desc, const EqwOut &out,

@@ -493,6 +493,53 @@ class VecGame:
                                                    self._dptr(range_of_d), int(bool(range_per_table)), self._dptr(win_d), self._dptr(tie_d),
                                                    self._dptr(share_d), self._dptr(accepted_d), self._dptr(status_d)), self._h)
 
+    def ev_ranged(self, tables=None, observer=L.OBSERVER_ACTIVE, ranges=None, range_of=None, samples=1024, nonce=0):
+        """Showdown EV in chips of `tables` (all tables if None; indices may repeat) as `observer` (a seat or OBSERVER_ACTIVE) sees them,
+        where every other live seat draws its holding from a weighted range: the side pots of equity_ev over the attempts of equity_ranged
+        (pk_table_ev_ranged; definition: pokerl_hip.h "Ranged showdown EV").  ranges, range_of, samples, nonce as equity_ranged; bets = bets +
+        pending_bets as equity_ev.  Returns a judger.RangedEV of [m, N] / [m, N, N] / [m] arrays (`bets` and `payout` are None while
+        asynchronous steps are in flight: they are formed from the getters)."""
+        from .judger import NO_LEVEL, RangedEV, check_ranges, check_samples
+        o = self._range_observer(observer)
+        samples, nonce = check_samples(samples, nonce)
+        t = self._tables(tables)
+        m = self.num_tables if t is None else len(t)
+        n = self.num_players
+        w, r, ro, per = check_ranges(ranges, range_of, n, m)
+        share = np.zeros((m, n, n), np.uint64)
+        level_seat = np.full((m, n), NO_LEVEL, np.uint8)
+        amount, ev = np.zeros((m, n), np.float64), np.zeros((m, n), np.float64)
+        count, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        L.check(self._lib.pk_table_ev_ranged(self._h, L.ptr(t), m, o, samples, nonce, L.ptr(w), r, L.ptr(ro), int(per), L.ptr(share),
+                                             L.ptr(level_seat), L.ptr(amount), L.ptr(ev), L.ptr(count), L.ptr(status)), self._h)
+        try:                            # (`bets` is formed from the getters, which refuse with PK_E_BUSY while asynchronous steps are in flight)
+            bets = self.bets + self.pending_bets
+            if t is not None:
+                ok = (t >= 0) & (t < self.num_tables)
+                bets = np.where(ok[:, None], bets[np.where(ok, t, 0)], 0.0)
+        except L.PokerlHipError as e:
+            if e.code != L.PK_E_BUSY:
+                raise
+            bets = None
+        return RangedEV(ev, share, level_seat, amount, count, status, bets, samples)
+
+    def ev_ranged_d(self, status_d, m=None, tables_d=None, observer=L.OBSERVER_ACTIVE, weights_d=None, num_ranges=0, range_of_d=None,
+                    range_per_table=False, samples=1024, nonce=0, share_d=None, level_seat_d=None, amount_d=None, ev_d=None, accepted_d=None):
+        """pk_table_ev_ranged_d: the same on device buffers (weights_d uint16 [num_ranges, 1326], range_of_d uint16 [N] or [m, N]; outputs
+        uint64 [m, N, N] share, uint8 [m, N] level_seat, float64 [m, N] amount / ev, uint32 [m] accepted, uint8 [m] status; any but status_d
+        may be None), asynchronous on the handle's stream.  m defaults to every table."""
+        from .judger import check_samples
+        o = self._range_observer(observer)
+        samples, nonce = check_samples(samples, nonce)
+        if not 0 <= int(num_ranges) <= L.EQW_MAX_RANGES:
+            raise ValueError('at most %d ranges per call' % L.EQW_MAX_RANGES)
+        if status_d is None:
+            raise ValueError('status_d is required')
+        m = self.num_tables if m is None else int(m)
+        L.check(self._lib.pk_table_ev_ranged_d(self._h, self._dptr(tables_d), m, o, samples, nonce, self._dptr(weights_d), int(num_ranges),
+                                               self._dptr(range_of_d), int(bool(range_per_table)), self._dptr(share_d), self._dptr(level_seat_d),
+                                               self._dptr(amount_d), self._dptr(ev_d), self._dptr(accepted_d), self._dptr(status_d)), self._h)
+
     def _range_observer(self, observer):
         """observer of equity_range: a seat or OBSERVER_ACTIVE / 'active'; ValueError otherwise (before any call)."""
         o = self._observer(observer)

@@ -611,6 +611,187 @@ def ranged_equity(hands, board=(), live=None, ranges=None, range_of=None, sample
     return r
 
 
+# ---------------------------------------------------------------------------------------------- ranged showdown EV
+# Showdown EV in chips where every hidden seat draws its holding from a weighted range: the side pots of showdown_ev over the attempts of
+# ranged_equity (pk_ev_ranged; the definition: include/pokerl_hip.h "Ranged showdown EV").  "With what I believe
+# about their hands, what am I paid in chips if I call?"
+def ranged_ev_status_text(status):
+    return ev_status_text(status)           # (the same bits: PK_EQ_BAD_BET in the place of PK_EQ_PREFLOP)
+
+
+def ranged_ev_formula(amount, share, accepted, bets):
+    """ev [N] of one spot by the stated formula in binary64: acc = +0.0; for i ascending: acc = acc + (amount[i] * float(share[i][p])) /
+    (720720.0 * float(accepted)); ev[p] = acc - bets[p].  accepted == 0: all +0.0."""
+    n = len(bets)
+    ev = np.zeros(n, np.float64)
+    if int(accepted) == 0:
+        return ev
+    den = np.float64(L.EQ_SHARE_UNIT) * np.float64(int(accepted))
+    for p in range(n):
+        acc = np.float64(0.0)
+        for i in range(n):
+            acc = acc + (np.float64(amount[i]) * np.float64(int(share[i][p]))) / den
+        ev[p] = acc - np.float64(bets[p])
+    return ev
+
+
+class RangedEV:
+    """Expected payoffs of one spot or of a batch over the ACCEPTED attempts ([N] / [N, N] or [m, N] / [m, N, N] arrays; `accepted`, `status`
+    scalars or [m]; `samples` = the attempts asked for): ev, share, level_seat, amount as ShowdownEV with `accepted` in the place of `boards`.
+    accepted == 0 with status 0 (a range with no weight left): ev is all +0.0 and is no estimate."""
+
+    def __init__(self, ev, share, level_seat, amount, accepted, status, bets, samples):
+        self.ev, self.share, self.level_seat, self.amount, self.accepted, self.status, self.bets, self.samples = (
+            ev, share, level_seat, amount, accepted, status, bets, samples)
+
+    @property
+    def payout(self):
+        """ev + bets: what a seat expects to take out of the pot (0 where a spot was refused or nothing was accepted)."""
+        if self.bets is None:
+            return None
+        ok = ((np.asarray(self.status) == 0) & (np.asarray(self.accepted) > 0))[..., None]
+        return np.where(ok, np.asarray(self.ev) + np.asarray(self.bets), 0.0)
+
+    @property
+    def levels(self):
+        """(seat, amount) pairs of the levels that exist, in visiting order (a batch: one list per spot)."""
+        seat, amount = np.asarray(self.level_seat), np.asarray(self.amount)
+        if seat.ndim == 1:
+            return [(int(s), float(a)) for s, a in zip(seat, amount) if s != NO_LEVEL]
+        return [[(int(s), float(a)) for s, a in zip(ss, aa) if s != NO_LEVEL] for ss, aa in zip(seat, amount)]
+
+    @property
+    def acceptance(self):
+        return np.asarray(self.accepted, np.float64) / float(self.samples)
+
+    def __getitem__(self, i):
+        return RangedEV(self.ev[i], self.share[i], self.level_seat[i], self.amount[i], self.accepted[i], self.status[i],
+                        None if self.bets is None else self.bets[i], self.samples)
+
+    def merged(self, other):
+        """The result of both calls together: two results of the SAME spots drawn with different nonces.  share and accepted add exactly; ev
+        is re-formed on the host by the formula on the sums."""
+        if self.bets is None or other.bets is None:
+            raise ValueError('merged needs the bets of both results')
+        a, b = (np.asarray(x.level_seat) for x in (self, other))
+        if a.shape != b.shape or not np.array_equal(a, b) or not np.array_equal(np.asarray(self.status), np.asarray(other.status)) or \
+                not np.array_equal(np.asarray(self.amount, np.float64).view(np.uint64), np.asarray(other.amount, np.float64).view(np.uint64)):
+            raise ValueError('merged: the two results are not of the same spots')
+        share = np.asarray(self.share, np.uint64) + np.asarray(other.share, np.uint64)
+        acc = np.asarray(self.accepted, np.uint64) + np.asarray(other.accepted, np.uint64)
+        bets = np.asarray(self.bets, np.float64)
+        if a.ndim == 1:
+            ev = ranged_ev_formula(self.amount, share, acc, bets)
+        else:
+            ev = np.array([ranged_ev_formula(self.amount[i], share[i], acc[i], bets[i]) for i in range(a.shape[0])], np.float64).reshape(a.shape)
+        return RangedEV(ev, share, self.level_seat, self.amount, acc, self.status, self.bets, self.samples + other.samples)
+
+    def __repr__(self):
+        return 'RangedEV(accepted=%r of %r, status=%r, ev=%r, levels=%r)' % (self.accepted, self.samples, self.status, self.ev, self.levels)
+
+
+def ranged_ev_batch(holes, board, nboard, live, bets, ranges=None, range_of=None, samples=1024, seed=DEFAULT_SEED, nonce=0, ids=None, device=0):
+    """pk_ev_ranged on host arrays: the spots, ranges and stream of ranged_equity_batch plus bets float64 [m, N] (what each seat has committed,
+    folded seats included) -> RangedEV of [m, N] / [m, N, N] / [m] arrays.  A bad spot is reported through its `status` (PK_EQ_* bits,
+    PK_EQ_BAD_BET among them) with zeros everywhere; the others are unaffected."""
+    holes = np.ascontiguousarray(holes, np.uint8)
+    if holes.ndim != 3 or holes.shape[2] != 2 or not (L.MIN_PLAYERS <= holes.shape[1] <= L.MAX_PLAYERS):
+        raise ValueError('holes must have shape [m, N, 2] with 2 <= N <= 16')
+    m, n = holes.shape[:2]
+    board = np.ascontiguousarray(board, np.uint8)
+    nboard = np.ascontiguousarray(nboard, np.uint8)
+    live = np.ascontiguousarray(live, np.uint16)
+    if bets is None:
+        raise ValueError('bets: float64 [m, N]')
+    bets = np.ascontiguousarray(bets, np.float64)
+    if board.shape != (m, 5) or nboard.shape != (m,) or live.shape != (m,) or bets.shape != (m, n):
+        raise ValueError('board must have shape [m, 5], nboard and live shape [m], bets shape [m, N]')
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, np.uint32)
+        if ids.shape != (m,):
+            raise ValueError('ids must have shape [m]')
+    samples, nonce = check_samples(samples, nonce)
+    groups = (n - 1 + (3 if n <= 8 else 2) - 1) // (3 if n <= 8 else 2)
+    if m * ((samples + 63) // 64) * groups > 0xFFFFFFFF:
+        raise ValueError('m * ceil(samples / 64) * (groups of levels) must fit 32 bits: split the batch')
+    w, r, ro, _ = check_ranges(ranges, range_of, n, m, shared_ok=False)
+    share = np.zeros((m, n, n), np.uint64)
+    level_seat = np.full((m, n), NO_LEVEL, np.uint8)
+    amount, ev = np.zeros((m, n), np.float64), np.zeros((m, n), np.float64)
+    count, status = np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+    L.check(L.lib().pk_ev_ranged(int(device), n, m, L.ptr(holes), L.ptr(board), L.ptr(nboard), L.ptr(live), L.ptr(bets), L.ptr(ids), samples,
+                                 int(seed) & 0xFFFFFFFFFFFFFFFF, nonce, L.ptr(w), r, L.ptr(ro), L.ptr(share), L.ptr(level_seat), L.ptr(amount),
+                                 L.ptr(ev), L.ptr(count), L.ptr(status)))
+    return RangedEV(ev, share, level_seat, amount, count, status, bets, samples)
+
+
+def ranged_ev_d(num_players, m, holes_d, board_d, nboard_d, live_d, bets_d, samples, status_d, weights_d=None, num_ranges=0, range_of_d=None,
+                ids_d=None, seed=DEFAULT_SEED, nonce=0, share_d=None, level_seat_d=None, amount_d=None, ev_d=None, accepted_d=None, device=0,
+                stream=None):
+    """pk_ev_ranged_d: the same on device-resident buffers (device pointers as ints / c_void_p; bets_d float64 [m, N], weights_d uint16
+    [num_ranges, 1326], range_of_d uint16 [m, N]; ids_d, range_of_d and every output but status_d may be None), asynchronous on `stream`."""
+    samples, nonce = check_samples(samples, nonce)
+    if not (L.MIN_PLAYERS <= int(num_players) <= L.MAX_PLAYERS):
+        raise ValueError('between 2 and 16 seats')
+    if not 0 <= int(num_ranges) <= L.EQW_MAX_RANGES:
+        raise ValueError('at most %d ranges per call' % L.EQW_MAX_RANGES)
+    if bets_d is None or status_d is None:
+        raise ValueError('bets_d and status_d are required')
+    L.check(L.lib().pk_ev_ranged_d(int(device), int(num_players), int(m), holes_d, board_d, nboard_d, live_d, bets_d, ids_d, samples,
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF, nonce, weights_d, int(num_ranges), range_of_d, share_d, level_seat_d, amount_d,
+                                   ev_d, accepted_d, status_d, stream))
+
+
+def ranged_ev(hands, board=None, live=None, bets=None, ranges=None, range_of=None, samples=1024, seed=DEFAULT_SEED, nonce=0, device=0):
+    """One spot: ranged_equity's arguments (hands: per seat two cards or None = hidden, drawn from row range_of[seat] of `ranges`) plus bets,
+    one number per seat (what the seat has committed to the pot; a folded seat's money counts).  Returns a RangedEV with [N] / [N, N] arrays;
+    raises ValueError for an invalid spot."""
+    hands = list(hands)
+    n = len(hands)
+    if not (L.MIN_PLAYERS <= n <= L.MAX_PLAYERS):
+        raise ValueError('between 2 and 16 seats')
+    if bets is None:
+        raise ValueError('bets: one number per seat')
+    try:
+        bt = np.array([float(x) for x in bets], np.float64)
+    except TypeError as e:
+        raise ValueError('bets: one number per seat') from e
+    if bt.shape != (n,):
+        raise ValueError('bets: one number per seat')
+    if not np.all(np.isfinite(bt)) or np.any(bt < 0):
+        raise ValueError('bets must be finite and not negative')
+    board = [] if board is None else list(board)
+    if len(board) > 5:
+        raise ValueError('at most five board cards')
+    holes = np.full((1, n, 2), UNKNOWN_CARD, np.uint8)
+    for p, h in enumerate(hands):
+        if h is None:
+            continue
+        h = list(h)
+        if len(h) != 2 or any(c is None for c in h):
+            raise ValueError('seat %d: two hole cards, or None for a hidden hand' % p)
+        holes[0, p] = [_card(c) for c in h]
+    b = np.zeros((1, 5), np.uint8)
+    b[0, :len(board)] = [_card(c) for c in board]
+    if live is None:
+        mask = (1 << n) - 1
+    elif isinstance(live, (int, np.integer)):
+        mask = int(live)
+    else:
+        mask = 0
+        for p in live:
+            if not 0 <= int(p) < n:
+                raise ValueError('live seat %r out of range' % (p,))
+            mask |= 1 << int(p)
+    if mask < 0 or mask >> n:
+        raise ValueError('live mask names seats >= %d' % n)
+    r = ranged_ev_batch(holes, b, np.array([len(board)], np.uint8), np.array([mask], np.uint16), bt[None, :], ranges, range_of, samples, seed,
+                        nonce, device=device)[0]
+    if r.status:
+        raise ValueError('invalid spot: ' + ranged_ev_status_text(r.status))
+    return r
+
+
 # ---------------------------------------------------------------------------------------------- range equity
 # Exact hand strength against ONE hidden hand, post-flop: the hero's win / tie counts against every holding the opponent can have, and their
 # sum under a range of weights (pk_equity_range; the definition: include/pokerl_hip.h "Range equity", DESIGN.md section 3.3).

@@ -128,6 +128,17 @@ class Game:
             raise ValueError('the table cannot be evaluated: ' + equity_status_text(r.status))
         return r
 
+    def ev_ranged(self, observer=None, ranges=None, range_of=None, samples=1024, nonce=0):
+        """Showdown EV in chips of the table as `observer` sees it (None = the active seat) with every other live seat's holding drawn from
+        a weighted range (VecGame.ev_ranged): a judger.RangedEV with [N] / [N, N] arrays.  Not in the reference."""
+        from ._lib import OBSERVER_ACTIVE
+        r = self._v.ev_ranged(observer=OBSERVER_ACTIVE if observer is None else observer, ranges=ranges, range_of=range_of, samples=samples,
+                              nonce=nonce)[0]
+        if r.status:
+            from .judger import ranged_ev_status_text
+            raise ValueError('the table cannot be evaluated: ' + ranged_ev_status_text(r.status))
+        return r
+
     def equity_range(self, observer=None, weights=None):
         """Exact hand strength of `observer` (None = the active seat) against one hidden hand, post-flop (VecGame.equity_range): a
         judger.RangeEquity with [1326] arrays and the scalar `strength`.  Not in the reference."""

@@ -59,6 +59,7 @@ import hero_hist_spec as HHS             # noqa: E402
 import hist_cluster_spec as CS          # noqa: E402
 import hist_spec as HS                  # noqa: E402
 import preflop_spec as PS               # noqa: E402
+import ranged_ev_spec as XS             # noqa: E402
 import rvr_spec as VS                   # noqa: E402
 from oracle import rng_spec as R        # noqa: E402
 
@@ -69,6 +70,7 @@ OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("w
            "range": ("agg", "win", "tie", "boards", "status"), "rvr": ("win", "tie", "tot", "boards", "status"),
            "hist": ("hist", "void", "completions", "status"), "ranged": ("win", "tie", "share", "accepted", "status"),
            "ev": ("share", "level_seat", "amount", "ev", "boards", "status"),
+           "rangedev": ("share", "level_seat", "amount", "ev", "accepted", "status"),
            "cluster": ("centroids_out", "label", "dist", "inertia", "changed"),
            "herohist": ("hist", "void", "completions", "status"), "preflop": ("win", "tie"),
            "pfhero": ("agg", "win", "tie", "boards", "status"), "pfrvr": ("win", "tie", "tot")}
@@ -692,6 +694,128 @@ def ev_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- ranged ev
+def ranged_ev_case(name, n, specs, bets, seed, grid, samples, weights=None, range_of=None, nonce=0, ids=None, lpt=None, outputs=None, quick=False,
+                   edit=None):
+    """specs as seat_spots; bets [m][n] (a short row is padded with its last value); range_of [m, n] (None: every hidden seat uniform);
+    weights [R, 1326] or None."""
+    holes, board, nboard, live = seat_spots(seed, n, specs)
+    m = len(specs)
+    b = np.array([list(row) + [row[-1]] * (n - len(row)) for row in bets], np.float64)
+    assert b.shape == (m, n)
+    ro = None if range_of is None else np.array(range_of, np.uint16).reshape(m, n)
+    if edit:
+        edit(holes, board, nboard, live, ro, b)
+    key = R.seed_key(WS.DEFAULT_SEED + seed)
+    w = None if weights is None else np.asarray(weights, np.uint16).reshape(-1, HOLDINGS)
+    arrays = {"N": ("u32", [n]), "m": ("u32", [m]), "grid": ("u32", [grid]), "samples": ("u32", [samples]), "nonce": ("u32", [nonce]),
+              "key0": ("u32", [key[0]]), "key1": ("u32", [key[1]]), "ids": ("u32", ids), "lpt": ("u32", None if lpt is None else [lpt]),
+              "R": ("u32", [0 if w is None else len(w)]), "weights": ("u16", w), "range_of": ("u16", ro),
+              "holes": ("u8", holes), "board": ("u8", board), "nboard": ("u8", nboard), "live": ("u16", live), "bets": ("u64", f64_bits(b))}
+    return Case(name, "rangedev", arrays,
+                lambda: ev_expect(XS.batch_ev(holes, board, nboard, live, b, samples, w, ro, per_spot=True, nonce=nonce, ids=ids, key=key)), outputs, quick)
+
+
+def ranged_ev_cases():
+    """The cases of k_evw_prep<N, TABLE> / k_evw<N, RC> / k_evw_finish (family "rangedev", names evw-...: `--only ranged` and `--only ev-` do not
+    pick them up); NOT part of all_cases()."""
+    cs = []
+    rng = np.random.default_rng(71)
+    four = WS.random_ranges(rng)                                      # dense, ~40 holdings, one holding, all zero
+    U = WS.UNIFORM
+    ladder = lambda n: [5.0 * (p + 1) for p in range(n)]
+    # a grid of 1, spots with different levels after each other: what a spot leaves in LDS and in the level table must not reach the next;
+    # every street, each row and the uniform one, nothing hidden, a folded hidden seat, all bets zero
+    two = [(4, None, (1,)), (0, None, (1,)), (3, None, (1,)), (5, None, (0,)), (5, None, (1,)), (2, None, ()), (4, 0b01, (1,)), (0, None, (0, 1))]
+    ro2 = [[U, 0], [U, 1], [U, U], [2, U], [U, 3], [0, 0], [0, 9], [1, 0]]
+    bets2 = [[10, 37], [20, 20], [50, 5], [0, 10], [10, 37], [5, 5], [10, 37], [0, 0]]
+    cs.append(ranged_ev_case("evw-N2-S65-grid1", 2, two, bets2, 72, 1, 65, four, ro2, quick=True))
+    three = [(3, None, (1, 2)), (4, 0b101, (1, 2)), (5, None, (2,)), (0, None, (0, 1, 2)), (5, 0b010, (0, 2)), (4, 0b110, (1, 2))]
+    ro3 = [[U, 0, 1], [U, 0, 0], [U, U, 1], [0, U, 1], [U, 0, U], [1, 0, U]]
+    cs.append(ranged_ev_case("evw-N3-grid1", 3, three, [[30, 10, 20], [10, 50, 10], [10, 10, 10], [0, 10, 10], [5, 7, 9], [50, 20, 20]], 73, 1, 100, four, ro3,
+                             quick=True))
+    # S = 200: one chunk, a ragged run of lanes; S = 1 200: several chunks (512 attempts a chunk at the smallest lpt) on ONE workgroup, two nonces
+    cs.append(ranged_ev_case("evw-N3-S200", 3, three[:3], [[30, 10, 20], [10, 50, 10], [20, 20, 5]], 73, 2, 200, four, ro3[:3], quick=True))
+    for nonce in (0, 1):
+        cs.append(ranged_ev_case("evw-N3-S1200-grid1-nonce%d" % nonce, 3, three[:3], [[30, 10, 20], [10, 50, 10], [20, 20, 5]], 73, 1, 1200, four, ro3[:3],
+                                 nonce=nonce, ids=[7, 7, 2 ** 32 - 1], quick=(nonce == 0)))
+    # R = 0: no cumulative row in LDS at all (size class 0), range_of NULL
+    cs.append(ranged_ev_case("evw-N3-R0", 3, [(0, None, (1, 2)), (3, None, (0, 1, 2)), (5, 0b011, (1,))], [[30, 10, 20], [5, 5, 5], [10, 50, 10]], 74, 1, 100,
+                             quick=True))
+    # an all-zero range at a hidden seat: accepted 0, status 0 -- group 0 still runs, nothing is evaluated; the levels are still reported
+    cs.append(ranged_ev_case("evw-N3-dead-range", 3, [(4, None, (1, 2)), (4, None, (1, 2)), (4, None, (1, 2))], [[30, 10, 20]] * 3, 75, 1, 70, four,
+                             [[U, 0, 1], [U, 3, 0], [U, 0, 1]], quick=True))
+
+    # a refused spot between valid ones: a bad bet, a half-hidden live seat (BAD_CARD), a NaN with an infinity, no live seat
+    def refuse(holes, board, nboard, live, ro, b):
+        b[1, 2] = -1.0
+        holes[3, 1, 1] = [c for c in ES.CANON if c not in set(holes[3].reshape(-1).tolist()) | set(board[3].tolist())][0]
+        live[5] = 0
+        b[7, 0] = np.nan
+        b[7, 1] = np.inf
+        b[8, 0] = -0.0                                                # -0.0 is a zero
+    cs.append(ranged_ev_case("evw-N3-refused-between", 3, [(4, None, (1, 2))] * 9, [ladder(3)] * 9, 76, 1, 70, four, [[U, 0, 1]] * 9, edit=refuse, quick=True))
+    # five live seats on a ladder with two hidden seats: four levels to compare = two groups of three; then fewer levels in the same slots
+    five = [(4, None, (1, 3)), (5, None, (0, 4)), (4, 0b10111, (1, 2)), (5, 0b00100, (2,)), (3, None, (1, 3))]
+    ro5 = [[U, 0, U, 1, U], [1, U, U, U, 0], [U, 0, U, U, U], [U, U, 1, U, U], [U, 0, U, 0, U]]
+    cs.append(ranged_ev_case("evw-N5-two-groups", 5, five, [ladder(5), ladder(5)[::-1], [50, 5, 5, 50, 20], ladder(5), [10] * 5], 77, 1, 100, four, ro5, quick=True))
+    # nine seats with size class 16, sixteen seats on a ladder: two-level groups, four and eight of them.  Row r lives on the three holdings among
+    # the cards 3r .. 3r + 2, so the drawn holdings never collide with each other
+    sixteen = np.zeros((16, HOLDINGS), np.uint16)
+    for r in range(16):
+        for a, b in ((3 * r, 3 * r + 1), (3 * r, 3 * r + 2), (3 * r + 1, 3 * r + 2)):
+            sixteen[r, b * (b - 1) // 2 + a] = int(rng.integers(1, 65536))
+    all9, all16 = tuple(range(9)), tuple(range(16))
+    cs.append(ranged_ev_case("evw-N9-R16", 9, [(0, None, all9), (3, 0b101010111, all9)], [ladder(9), [0, 5, 5, 37, 37, 50, 10, 20, 20]], 78, 1, 66, sixteen,
+                             [list(range(9)), [15, 14, 13, U, 11, 10, 9, 8, 7]], quick=True))
+    cs.append(ranged_ev_case("evw-N16-ladder", 16, [(0, None, all16), (3, 0xF0F7, all16)], [ladder(16), ladder(16)[::-1]], 79, 1, 66, sixteen,
+                             [list(range(16)), list(range(15, -1, -1))], quick=True))
+    cs.append(ranged_ev_case("evw-N16-ladder-grid2", 16, [(0, None, all16), (4, None, all16), (5, 0x8001, all16)], [ladder(16)] * 3, 80, 2, 130, sixteen,
+                             [list(range(16))] * 3))
+    for o in ("share", "level_seat", "amount", "ev", "accepted"):
+        cs.append(ranged_ev_case("evw-no-" + o, 3, three[:2], [[30, 10, 20], [10, 5, 50]], 81, 1, 70, four, ro3[:2],
+                                 outputs=[x for x in OUTPUTS["rangedev"] if x != o], quick=(o in ("share", "accepted"))))
+    for observer, per in ((-2, 0), (1, 1)):
+        w = table_world(82, 3, 5)
+        key = R.seed_key(WS.DEFAULT_SEED)
+        m = len(w["tables"])
+        ro = np.array([[0, 1, U]] * (m if per else 1), np.uint16)
+        if per:
+            ro[1] = [1, 1, 1]
+        trng = np.random.default_rng(90)
+        tb = trng.choice([0.0, 5.0, 10.0, 20.0, 37.5], (w["T"], 3))
+        tp = trng.choice([0.0, 0.0, 2.5, 10.0], (w["T"], 3))
+        arrays = dict(table_arrays(w), m=("u32", [m]), grid=("u32", [1]), samples=("u32", [65]), nonce=("u32", [3]), key0=("u32", [key[0]]),
+                      key1=("u32", [key[1]]), id_base=("u32", [1000]), observer=("i32", [observer]), R=("u32", [4]), weights=("u16", four),
+                      range_of=("u16", ro), per_spot=("u32", [per]), bets=("u64", f64_bits(tb.T.copy())), pending=("u64", f64_bits(tp.T.copy())))
+
+        def expect(w=w, observer=observer, key=key, ro=ro, per=per, tb=tb, tp=tp):
+            holes, board, nboard, live, bets = XS.table_spots(w["deck"], w["states"], w["turn"], w["active"], observer, tb, tp)
+            tabs = w["tables"].tolist()
+            good = [(i, t) for i, t in enumerate(tabs) if 0 <= t < w["T"]]      # range_of goes by SPOT: evaluate per spot
+            idx = [t for _, t in good]
+            rows = ro[[i for i, _ in good]] if per else np.tile(ro[0], (len(good), 1))
+            r = XS.batch_ev(holes[idx], board[idx], nboard[idx], live[idx], bets[idx], 65, four, rows, per_spot=True, nonce=3,
+                            ids=[1000 + t for t in idx], key=key)
+            out = {k: np.zeros((len(tabs),) + r[k].shape[1:], r[k].dtype) for k in OUTPUTS["rangedev"]}
+            out["level_seat"][:] = XS.NO_LEVEL
+            for i, t in enumerate(tabs):
+                if not 0 <= t < w["T"]:
+                    out["status"][i] = BAD_TABLE
+            for j, (i, t) in enumerate(good):
+                for k in out:
+                    out[k][i] = r[k][j]
+                if w["inflight"][t]:
+                    out["status"][i] |= IN_FLIGHT
+                    for k in ("share", "amount", "ev", "accepted"):
+                        out[k][i] = 0
+                    out["level_seat"][i] = XS.NO_LEVEL
+            return ev_expect(out)
+        cs.append(Case("evw-table-form-observer%d" % observer, "rangedev", arrays, expect, quick=True))
+    assert len({c.name for c in cs}) == len(cs) and all(c.name.startswith("evw-") for c in cs)
+    return cs
+
+
 # ---------------------------------------------------------------------------------------------------------------- histogram clustering
 def cluster_case(name, op, hist, K, grid, centroids=None, iters=None, seed=None, nonce=0, chunk=None, lds=None, skew=0, quick=False):
     """op 0: seeding -> centroids; 1: assign -> label, dist; 2: `iters` iterations and the final assign.  Expected: tests/hist_cluster_spec.py."""
@@ -962,7 +1086,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

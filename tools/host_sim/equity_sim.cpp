@@ -9,7 +9,7 @@
 //   equity_sim <case file> <out file>
 // Case file: lines "name dtype count" (dtype u8 u16 u32 u64 i32) each followed by a line of `count` decimal values, and
 // "family <name>" / "outputs <name> ..." lines.  Out file: the same array format.
-// -DPK_ES_ONLY=1 .. 10: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist, preflop), so that a test can compile them side by side.
+// -DPK_ES_ONLY=1 .. 11: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist, preflop, rangedev), so that a test can compile them side by side.
 // The preflop family (pk_preflop.hip) is the partial count: the driver queues k_pfm_rank and k_pfm_count chunk by chunk in the order of
 // pk::pfm_count_launch, with the case's board range, chunk and `accumulate` (the outputs start from 0xA5 bytes: an accumulating case adds to them).
 // Its readers are the families pfhero (k_pfm_prep, k_pfm_hero) and pfrvr (k_pfm_rvr) of the same build; the table they read is a fixed pattern
@@ -37,15 +37,19 @@
 #if PK_ES_HAS(5)
 #include "../../pokerl_amd/csrc/pk_equity_hist.hip"
 #endif
-#if PK_ES_HAS(6)
+#if PK_ES_HAS(6) || PK_ES_HAS(11)
 #if !PK_ES_HAS(2)
-#include "../../pokerl_amd/csrc/pk_equity_sampled.hip"  // (the ranged family splits its tasks with pk::eqs_lpt)
+#include "../../pokerl_amd/csrc/pk_equity_sampled.hip"  // (the ranged families split their tasks with pk::eqs_lpt)
 #endif
-#include "../../pokerl_amd/csrc/pk_equity_ranged.hip"
+#include "../../pokerl_amd/csrc/pk_equity_ranged.hip"   // (the ranged EV sums its rows with k_eqw_cdf)
 #endif
 
 #if PK_ES_HAS(7)
 #include "../../pokerl_amd/csrc/pk_equity_ev.hip"
+#endif
+
+#if PK_ES_HAS(11)
+#include "../../pokerl_amd/csrc/pk_ev_ranged.hip"
 #endif
 
 #if PK_ES_HAS(8) || PK_ES_HAS(9)
@@ -394,6 +398,54 @@ void run_ev(Case &c, const uint32_t *tab) {
 }
 #endif
 
+#if PK_ES_HAS(11)
+// k_eqw_cdf, k_evw_prep<N, TABLE>, k_evw<N, RC>, k_evw_finish: RC is the size class of the case's R, as evw_launch picks it; `share` and
+// `accepted` are the caller's arrays, or work arrays when the case does not want them
+template <int N, int RC>
+void run_rangedev_class(const uint32_t *tab, const EvwWork &w, const EqsStream &rng, uint32_t R, unsigned grid, uint32_t ntasks, uint32_t nch, uint32_t per) {
+    pk_sim::launch(grid, EQ_BLOCK, [&] { k_evw<N, RC>(tab, w, rng, R, ntasks, nch, per); });
+}
+template <int N>
+void run_rangedev(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const uint32_t R = (uint32_t)c.num("R", 0);
+    EvwPrepArgs a{};
+    const bool tbl = table_form(c, N, m, a.t.t);
+    if (tbl) { a.t.bets = (const double *)c.need<uint64_t>("bets", (size_t)N * a.t.t.T); a.t.pending = (const double *)c.need<uint64_t>("pending", (size_t)N * a.t.t.T); }
+    else {
+        a.s.holes = c.need<uint8_t>("holes", m * N * 2); a.s.board = c.need<uint8_t>("board", m * 5); a.s.nboard = c.need<uint8_t>("nboard", m); a.s.live = c.need<uint16_t>("live", m);
+        a.bets = (const double *)c.need<uint64_t>("bets", m * N);
+    }
+    const int per_spot = (int)c.num("per_spot", tbl ? 0 : 1);
+    const EqwRanges ranges{R ? c.need<uint16_t>("weights", (size_t)R * EQW_HOLDINGS) : nullptr, R, c.arr<uint16_t>("range_of", (per_spot ? m : (size_t)1) * N), per_spot};
+    EqsStream rng{(uint32_t)c.num("key0"), (uint32_t)c.num("key1"), (uint32_t)c.num("nonce"), (uint32_t)c.num("samples"), (uint32_t)c.num("id_base", 0), c.arr<uint32_t>("ids", m)};
+    EvwOut out{c.output<uint64_t>("share", "u64", m * N * N), c.output<uint8_t>("level_seat", "u8", m * N), (double *)c.output<uint64_t>("amount", "u64", m * N),
+               (double *)c.output<uint64_t>("ev", "u64", m * N), c.output<uint32_t>("accepted", "u32", m), c.output<uint8_t>("status", "u8", m)};
+    if (!out.status) die("the rangedev family needs the status output");
+    Work<uint32_t> cum((size_t)R * EQW_HOLDINGS);
+    Work<uint64_t> desc(m * (size_t)eqw_desc_words(N));
+    Work<uint32_t> levels(m * N);
+    Work<double> wbets(m * N), wamount(m * N);
+    Work<uint64_t> wshare(out.share ? 0 : m * N * N);
+    Work<uint32_t> waccepted(out.accepted ? 0 : m);
+    const EvwWork w{cum.p, desc.p, levels.p, wbets.p, wamount.p, out.share ? out.share : wshare.p, out.accepted ? out.accepted : waccepted.p};
+    if (R) pk_sim::launch(R, 64, [&] { k_eqw_cdf(ranges.weights, cum.p, R); });
+    a.rng = rng; a.r = ranges; a.out = out; a.w = w; a.observer = (int)c.num("observer", PK_OBSERVER_ACTIVE); a.m = m;
+    if (tbl) pk_sim::launch(prep_grid(m, EVW_PREP_BLOCK), EVW_PREP_BLOCK, [&] { k_evw_prep<N, true>(a); });
+    else pk_sim::launch(prep_grid(m, EVW_PREP_BLOCK), EVW_PREP_BLOCK, [&] { k_evw_prep<N, false>(a); });
+    const long long lpt_case = c.num("lpt", 0);
+    const uint32_t S = rng.samples, per = 64u * (uint32_t)(lpt_case ? lpt_case : pk::eqs_lpt(m, S)), nch = (S + per - 1) / per;
+    const uint32_t ntasks = (uint32_t)m * nch * (uint32_t)pk::ev_groups_max(N);
+    const int rc = pk::eqw_class(R);
+    printf("tasks %u (%u chunks x %d groups of %d levels per spot), size class %d\n", ntasks, nch, pk::ev_groups_max(N), pk::ev_group(N), rc);
+    if (rc == 0) run_rangedev_class<N, 0>(tab, w, rng, R, grid, ntasks, nch, per);
+    else if (rc == 8) run_rangedev_class<N, 8>(tab, w, rng, R, grid, ntasks, nch, per);
+    else run_rangedev_class<N, 16>(tab, w, rng, R, grid, ntasks, nch, per);
+    pk_sim::launch(prep_grid(m * N, EVW_FINISH_BLOCK), EVW_FINISH_BLOCK, [&] { k_evw_finish(w, out.ev, N, m); });
+}
+#endif
+
 #if PK_ES_HAS(8)
 template <int P = 1, typename F>
 void cl_with_pairs(int pairs, F f) {
@@ -550,7 +602,7 @@ int main(int argc, char **argv) {
     if (argc != 3) die("usage: equity_sim <case file> <out file>");
     Case c(argv[1]);
     // the function-local __shared__ arrays of the main kernels (the preparation kernels have none)
-    const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "11k_hero_histPKj", "5k_eqwILi", "4k_evILi", "10k_cl_quant", "11k_cl_assign",
+    const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "11k_hero_histPKj", "5k_eqwILi", "4k_evILi", "5k_evwILi", "10k_cl_quant", "11k_cl_assign",
                                         "11k_cl_update", "14k_cl_seed_dist", "14k_cl_seed_pick", "10k_pfm_rank", "11k_pfm_count", "10k_pfm_hero", "9k_pfm_rvr"});
     Work<uint32_t> tab(EVAL7_TAB_WORDS);
     for (int i = 0; i < EVAL7_TAB_WORDS; ++i) tab.p[i] = eval7_tab_entry((uint32_t)i);
@@ -592,6 +644,14 @@ int main(int argc, char **argv) {
     if (c.family == "ev") {
         if (N == 2) run_ev<2>(c, tab.p); else if (N == 3) run_ev<3>(c, tab.p); else if (N == 5) run_ev<5>(c, tab.p); else if (N == 9) run_ev<9>(c, tab.p); else if (N == 16) run_ev<16>(c, tab.p);
         else die("k_ev<N>: this build has N = 2, 3, 5, 9, 16");
+        ran = true;
+    }
+#endif
+#if PK_ES_HAS(11)
+    if (c.family == "rangedev") {
+        if (N == 2) run_rangedev<2>(c, tab.p); else if (N == 3) run_rangedev<3>(c, tab.p); else if (N == 5) run_rangedev<5>(c, tab.p); else if (N == 9) run_rangedev<9>(c, tab.p);
+        else if (N == 16) run_rangedev<16>(c, tab.p);
+        else die("k_evw<N, RC>: this build has N = 2, 3, 5, 9, 16");
         ran = true;
     }
 #endif

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Which GPU kernels does the working tree compile differently from <git-rev>?  Both trees' device code -- every translation unit of build.SOURCES as
-build.py compiles it: pk_tables.hip per seat count, pk_equity_ranged.hip per LDS size class (build.EQW_CLASSES), every other unit once -- goes to
+build.py compiles it: pk_tables.hip per seat count, pk_equity_ranged.hip and pk_ev_ranged.hip per LDS size class (build.EQW_CLASSES), every other unit once -- goes to
 assembly with the library's build flags and is compared per kernel (body and kernel descriptor) and per device constant object (g_nth,
 g_env_transitions); function order, local label numbers and the __hip_cuid_* symbol do not count.  Exit status 1 on a difference.
 usage: tools/isa_diff.py <git-rev> [N ...]      (default N = every seat count)"""
@@ -24,7 +24,8 @@ if __name__ == "__main__":
     rev, seats = sys.argv[1], [int(a) for a in sys.argv[2:]] or build.SEATS
     units = [("pk_tables.hip -DPK_SEATS=%d" % n, "pk_tables.hip", build.table_flags(n) + ["-DPK_SEATS=%d" % n]) for n in sorted(seats, reverse=True)]
     units += [("pk_equity_ranged.hip -DPK_EQW_CLASS=%d" % rc, "pk_equity_ranged.hip", build.COMPILE_FLAGS + ["-DPK_EQW_CLASS=%d" % rc]) for rc in build.EQW_CLASSES]
-    units += [(s, s, build.COMPILE_FLAGS) for s in build.SOURCES if s not in ("pk_tables.hip", "pk_equity_ranged.hip")]
+    units += [("pk_ev_ranged.hip -DPK_EVW_CLASS=%d" % rc, "pk_ev_ranged.hip", build.COMPILE_FLAGS + ["-DPK_EVW_CLASS=%d" % rc]) for rc in build.EQW_CLASSES]
+    units += [(s, s, build.COMPILE_FLAGS) for s in build.SOURCES if s not in ("pk_tables.hip", "pk_equity_ranged.hip", "pk_ev_ranged.hip")]
     with tempfile.TemporaryDirectory() as old, ThreadPoolExecutor(int(os.environ.get("PK_BUILD_JOBS", "0")) or min(8, os.cpu_count() or 1)) as ex:
         tar = subprocess.run(["git", "-C", ROOT, "archive", rev, "pokerl_amd/csrc", "include"], check=True, capture_output=True).stdout
         subprocess.run(["tar", "-x", "-C", old], input=tar, check=True)

@@ -988,6 +988,53 @@ int pk_table_equity_preflop(pk_handle *h, const int32_t *tables, size_t m, int o
 int pk_equity_rvr_preflop_d(int device, size_t m, const uint16_t *weights_d /*[m][1326]; NULL: 1*/, uint64_t *win_d /*[m][1326]*/, uint64_t *tie_d,
                             uint64_t *tot_d, void *stream);
 int pk_equity_rvr_preflop(int device, size_t m, const uint16_t *weights, uint64_t *win, uint64_t *tie, uint64_t *tot);
+
+/* ---- River solver: heads-up CFR+ over a caller's betting tree on a complete board, exact integers (the numpy
+ * restatement: tests/river_solver_spec.py).  No result depends on the order of a sum, so the output is the same bytes whatever the grid.
+ * PLAYERS AND RANGES: two players, five board cards, an optional `dead` mask as in range vs range.  Player 0 acts first.  ranges u16
+ * [m][2][1326] over the holding index.  A holding with a board or dead card is INVALID: its weight is ignored and every output at it is 0.
+ * P = pool cards <= 47.
+ * TREE: one per call, shared by the m spots, in HOST memory in every form (it travels with the launch).  n nodes, 1 <= n <= 64; kind u8 [n]:
+ * 0 / 1 = player 0 / 1 to act, 2 / 3 = player 0 / 1 has folded, 4 = showdown; child u8 [n][4]: a decision node's 1 .. 4 children packed
+ * first, then 0xFF; put u32 [n][2]: chips each player has put in since the subgame's root; pot u32: chips in the middle at the root.
+ * D = number of decision nodes; the d-th decision node in index order is row d of `strategy`.  Refused with PK_E_INVALID_ARG before any
+ * device is looked at: the root is not a decision node; a child index <= its parent or >= n; a non-root node without exactly one parent; a
+ * terminal with a child; a decision node without one; a showdown with put[0] != put[1]; pot + max put > 8191; iters outside 1 .. 4096; a NULL
+ * pointer where one is required (board, ranges, kind, child, put, status).
+ * UNITS: ONE = 32768 (Q15).  Root reach r_p[0][h] = w_p[h] << 4 for valid h, else 0.  Utilities are in half-chips x opponent reach.
+ * q = 1 - p throughout.
+ * STRATEGY FROM NON-NEGATIVE INTEGERS X[a] (the regrets, and at the end the average accumulators) at a node with nact actions: mx = max X;
+ * if mx = 0, sigma_a = ONE / nact (floor) for a >= 1; otherwise sh = max(0, bitlen(mx) - 31), X' = X >> sh, S = sum X', sigma_a =
+ * (X'_a << 15) / S (floor) for a >= 1; in both cases sigma_0 = ONE - sum_{a >= 1} sigma_a.
+ * ONE TREE PASS WITH STRATEGIES sigma.  DOWN, in index order, at a decision node n of actor p: r_p[c_a][h] = (r_p[n][h] sigma[n][a][h])
+ * >> 15, and r_q is copied.  TERMINALS: sums over the valid h' that share no card with h; `compare` is the two-seat decision of range vs
+ * range.  S_q(h) = sum r_q[n][h']; W_q(h), T_q(h), L_q(h) = the same sum over the h' that h beats, ties, loses to.  Fold by f:
+ * u_f[h] = -2 put[f] S_q(h) and u_{1-f}[h] = 2 (pot + put[f]) S_q(h).  Showdown, c = put[0]: u_p[h] = 2 (pot + c) W_q(h) + pot T_q(h)
+ * - 2 c L_q(h).  UP, in reverse index order, at a decision node of actor p: u_p[n][h] = floor(sum_a sigma[n][a][h] u_p[c_a][h] / 32768),
+ * the sum first and the floor once; u_q[n][h] = sum_a u_q[c_a][h].
+ * ITERATIONS t = 1 .. iters, both players updated from the same pass (simultaneous CFR+): sigma from the regrets R (which start at 0), one
+ * pass, then at every decision node n of actor p, action a, valid h: R[n][a][h] = max(0, R[n][a][h] + u_p[c_a][h] - u_p[n][h]) and
+ * A[n][a][h] += t r_p[c_a][h].
+ * OUTPUTS, each optional except status: strategy u16 [m][D][4][1326] = the strategy rule applied to A (unused action slots and invalid holdings 0; a
+ * valid holding of weight 0, like any holding whose accumulators are all 0, gets the uniform row); value i64 [m][2][1326] = u_p[root] of one
+ * pass in which every node plays `strategy`; br i64 [m][2][1326] = for each p, u_p[root] of a pass with `strategy` in which p's reach is
+ * copied unchanged at p's own nodes, u_p[n][h] = max_a u_p[c_a][h] there, and everything of q is ignored; status u8 [m]: PK_EQ_BAD_CARD
+ * (a `dead` bit >= 52 too), PK_EQ_DUP_CARD, PK_EQ_SMALL_POOL for P < 4.  A refused spot gives all-zero outputs and disturbs no neighbour;
+ * a call with no spot writes nothing.
+ * BOUNDS: reaches < 2^20 and their sums < 2^31; |u| < 2^45, so |sigma u| < 2^60; |R| < 2^58 after 4096 iterations; A < 2^44.  Everything
+ * fits int64_t.  STREAMS and work space: as pk_equity; the work space is the descriptors plus a slice per RESIDENT workgroup (at most 256):
+ * 47 872 bytes per tree node.  There is no table form: a tree carries absolute chips. */
+#define PK_RS_MAX_NODES 64
+#define PK_RS_MAX_ITERS 4096
+#define PK_RS_MAX_CHIPS 8191u
+#define PK_RS_ONE 32768u
+int pk_solve_river_d(int device, size_t m, const uint8_t *board_d /*[m][5]*/, const uint64_t *dead_d /*[m]; NULL: none*/,
+                     const uint16_t *ranges_d /*[m][2][1326]*/, uint32_t n, const uint8_t *kind /*[n], host*/, const uint8_t *child /*[n][4], host*/,
+                     const uint32_t *put /*[n][2], host*/, uint32_t pot, uint32_t iters, uint16_t *strategy_d /*[m][D][4][1326]*/,
+                     int64_t *value_d /*[m][2][1326]*/, int64_t *br_d, uint8_t *status_d, void *stream);
+int pk_solve_river(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t n, const uint8_t *kind,
+                   const uint8_t *child, const uint32_t *put, uint32_t pot, uint32_t iters, uint16_t *strategy, int64_t *value, int64_t *br,
+                   uint8_t *status);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

@@ -22,6 +22,7 @@
 #include "pk_ev_ranged.hpp"
 #include "pk_equity_range.hpp"
 #include "pk_equity_rvr.hpp"
+#include "pk_river_solver.hpp"
 #include "pk_equity_hist.hpp"
 #include "pk_equity_hist_hero.hpp"
 #include "pk_hist_cluster.hpp"
@@ -2885,6 +2886,82 @@ int pk_equity_rvr_preflop(int device, size_t m, const uint16_t *weights, uint64_
     const int wi = g.out(win, m * PFM_HOLDINGS * 8), ti = g.out(tie, m * PFM_HOLDINGS * 8), to = g.out(tot, m * PFM_HOLDINGS * 8);
     return eq_call_host(call, device, m, EQ_TAB_PREFLOP, g, 0, [&](hipStream_t st, const uint32_t *M, char *) {
         return pfm_rvr_launch(st, M, g.at<uint16_t>(we), m, g.at<uint64_t>(wi), g.at<uint64_t>(ti), g.at<uint64_t>(to));
+    });
+}
+
+// ---- the river solver (pokerl_hip.h "River solver"; kernels: pk_river_solver.hip).  The tree is checked and packed on the host and travels
+// with the launch; the work space is the descriptors plus a slice per resident workgroup.  There is no table form.
+static_assert(RS_HOLDINGS == PK_EQ_HOLDINGS, "pk_river_solver.hpp and the ABI header agree");
+// The tree check: the refusal's text, or NULL with `t` filled (nact and row derived)
+static const char *rs_check_tree(uint32_t n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, uint32_t pot, RsTree &t) {
+    if (n < 1u || n > (uint32_t)RS_MAX_NODES) return ": n outside 1 .. 64";
+    t = RsTree{};
+    t.n = n; t.pot = pot;
+    uint32_t parents[RS_MAX_NODES] = {0}, rows = 0;
+    for (uint32_t v = 0; v < n; ++v) {
+        if (kind[v] > RS_SHOWDOWN) return ": a node kind outside 0 .. 4";
+        if (v == 0 && kind[v] > RS_P1) return ": the root is not a decision node";
+        t.kind[v] = kind[v];
+        t.put[v][0] = put[v * 2]; t.put[v][1] = put[v * 2 + 1];
+        const uint32_t top = put[v * 2] > put[v * 2 + 1] ? put[v * 2] : put[v * 2 + 1];
+        if (pot > RS_MAX_CHIPS || top > RS_MAX_CHIPS || pot + top > RS_MAX_CHIPS) return ": pot + max put > 8191";
+        if (kind[v] == RS_SHOWDOWN && put[v * 2] != put[v * 2 + 1]) return ": a showdown has put[0] != put[1]";
+        uint32_t nact = 0;
+        bool ended = false;
+        for (int a = 0; a < 4; ++a) {
+            const uint32_t c = child[v * 4 + a];
+            t.child[v][a] = (uint8_t)c;
+            if (c == 0xFFu) { ended = true; continue; }
+            if (kind[v] > RS_P1) return ": a terminal has a child";
+            if (ended) return ": a node's children are not packed first";
+            if (c <= v || c >= n) return ": a child index is <= its parent or >= n";
+            ++parents[c];
+            ++nact;
+        }
+        if (kind[v] <= RS_P1 && nact == 0u) return ": a decision node has no child";
+        t.nact[v] = (uint8_t)nact;
+        if (kind[v] <= RS_P1) t.row[v] = (uint8_t)rows++;
+    }
+    for (uint32_t v = 1; v < n; ++v)
+        if (parents[v] != 1u) return ": a non-root node does not have exactly one parent";
+    return nullptr;
+}
+static const char *rs_check(size_t m, bool pointers, uint32_t iters, uint32_t n, const uint8_t *kind, const uint8_t *child, const uint32_t *put,
+                            uint32_t pot, RsTree &t) {
+    if (const char *why = eq_bad_m(m)) return why;
+    if ((m && !pointers) || !kind || !child || !put) return ": NULL where a pointer is required (board, ranges, kind, child, put, status)";
+    if (iters < 1u || iters > (uint32_t)RS_MAX_ITERS) return ": iters outside 1 .. 4096";
+    return rs_check_tree(n, kind, child, put, pot, t);
+}
+
+int pk_solve_river_d(int device, size_t m, const uint8_t *board_d, const uint64_t *dead_d, const uint16_t *ranges_d, uint32_t n, const uint8_t *kind,
+                     const uint8_t *child, const uint32_t *put, uint32_t pot, uint32_t iters, uint16_t *strategy_d, int64_t *value_d, int64_t *br_d,
+                     uint8_t *status_d, void *stream) {
+    const char *call = "pk_solve_river_d";
+    RsTree t;
+    EQ_REFUSE(g_fail, call, rs_check(m, board_d && ranges_d && status_d, iters, n, kind, child, put, pot, t));
+    const bool solve = strategy_d || value_d || br_d;
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, rs_work_bytes(m, n, solve), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return rs_launch(st, tab, RsSpots{board_d, dead_d, ranges_d}, t, iters, m, RsOut{strategy_d, value_d, br_d, status_d}, work);
+    });
+}
+
+int pk_solve_river(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t n, const uint8_t *kind,
+                   const uint8_t *child, const uint32_t *put, uint32_t pot, uint32_t iters, uint16_t *strategy, int64_t *value, int64_t *br,
+                   uint8_t *status) {
+    const char *call = "pk_solve_river";
+    RsTree t;
+    EQ_REFUSE(g_fail, call, rs_check(m, board && ranges && status, iters, n, kind, child, put, pot, t));
+    size_t D = 0;
+    for (uint32_t v = 0; v < n; ++v) D += t.kind[v] <= RS_P1;
+    const bool solve = strategy || value || br;
+    Stage g;
+    const int bo = g.in(board, m * 5), de = g.in(dead, m * 8), ra = g.in(ranges, m * 2 * RS_HOLDINGS * 2);
+    const int sg = g.out(strategy, m * D * 4 * RS_HOLDINGS * 2), va = g.out(value, m * 2 * RS_HOLDINGS * 8), be = g.out(br, m * 2 * RS_HOLDINGS * 8);
+    const int su = g.out(status, m);
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, rs_work_bytes(m, n, solve), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return rs_launch(st, tab, RsSpots{g.at<uint8_t>(bo), g.at<uint64_t>(de), g.at<uint16_t>(ra)}, t, iters, m,
+                         RsOut{g.at<uint16_t>(sg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
     });
 }
 

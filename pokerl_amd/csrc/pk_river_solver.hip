@@ -1,0 +1,451 @@
+// pk_river_solver.hip -- the river subgame solver (include/pokerl_hip.h "River solver"): simultaneous CFR+ for two
+// players over a caller's betting tree, in 64-bit integers whose sums do not depend on their order.  Two kernels:
+//   k_rs_prep       one lane per spot: checks the five board cards and the dead mask, writes the spot's descriptor (range vs range's, k = 0)
+//                   and its status;
+//   k_river_solve   a persistent grid of 512-thread workgroups, the evaluator table and the tree in LDS (staged once per workgroup), ONE
+//                   SPOT PER WORKGROUP at a time.  Per spot the pool's holdings are ranked and sorted ONCE (k_rvr's rank and order stage at
+//                   k = 0); from then on a lane OWNS the holdings at sorted positions i = tid, tid + 512, tid + 1024: their regrets,
+//                   average accumulators, reaches, probabilities and values, all in the workgroup's slice of the global work space, every
+//                   word of which is read and written by its owner alone.  Only a terminal node couples lanes: both players' reaches
+//                   go to LDS in sorted order as ONE 64-bit word (player 0 low, player 1 high: neither half of any sum reaches 2^31),
+//                   a workgroup prefix sum follows, and a lane reads the weight below, equal to and above each of its holdings at the
+//                   bounds it found once per spot; the 2 (P - 2) holdings that share a card with it, and itself, are taken back out by their
+//                   own sorted positions (card removal by the holder's keys, as k_rvr's combine).
+//                   The final passes (the average strategy, its values, the best responses) run in the same launch.  A best-response
+//                   pass of p needs only q's reaches, which are those of the value pass: one walk down serves all three, and the walk up
+//                   carries the maximum beside the value.
+// Ordinary vector stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_river_solver_host.py reads the code object).
+#include <hip/hip_runtime.h>
+
+#include "pk_equity_common.hpp"
+#include "pk_river_solver.hpp"
+
+using namespace pk;
+
+#define RS_PREP_BLOCK 256
+
+struct RsPrepArgs {
+    RsSpots s;
+    uint8_t *status;
+    uint64_t *desc;
+    size_t m;
+};
+
+__global__ void __launch_bounds__(RS_PREP_BLOCK) k_rs_prep(RsPrepArgs a) {
+    const size_t i = (size_t)blockIdx.x * RS_PREP_BLOCK + threadIdx.x;
+    if (i >= a.m) return;
+    uint64_t *d = a.desc + i * (size_t)RS_DESC_WORDS;
+    uint32_t status = 0;
+    uint64_t dead = 0, known = 0;
+    for (int j = 0; j < 5; ++j) {
+        const uint32_t c = a.s.board[i * 5 + j];
+        if (c >= 0x40u || (c & 15u) >= 13u) { status |= PK_EQ_BAD_CARD; continue; }
+        const uint64_t bit = 1ull << ((c & 15u) * 4u + (c >> 4));              // canonical index (cards.py:77)
+        status |= (dead & bit) ? (uint32_t)PK_EQ_DUP_CARD : 0u;
+        dead |= bit;
+        known |= 4ull << c;
+    }
+    const uint64_t out_of_play = a.s.dead ? a.s.dead[i] : 0ull;
+    if (out_of_play >> 52) status |= PK_EQ_BAD_CARD;
+    const uint64_t dd = out_of_play & 0x000FFFFFFFFFFFFFull;
+    if (dd & dead) status |= PK_EQ_DUP_CARD;
+    dead |= dd;
+    const uint32_t P = 52u - (uint32_t)__popcll(dead);
+    if (P < 4u) status |= PK_EQ_SMALL_POOL;                                    // TWO holdings that share no card
+    d[0] = known;
+    d[1] = ~dead & 0x000FFFFFFFFFFFFFull;
+    d[2] = (uint64_t)(status ? 0u : 1u) | ((uint64_t)P << 56);
+    if (a.status) a.status[i] = (uint8_t)status;
+}
+
+namespace {
+
+// floor(num / den), num < 2^46, 0 < den < 2^33: the double quotient is within one of it
+__device__ __forceinline__ uint32_t rs_div(uint64_t num, uint64_t den) {
+    uint64_t q = (uint64_t)((double)num / (double)den);
+    if (q * den > num) --q;
+    else if ((q + 1u) * den <= num) ++q;
+    return (uint32_t)q;
+}
+
+// The strategy rule: X[0 .. nact) non-negative -> sig[0 .. nact) summing to RS_ONE (the slots from nact on: 0)
+__device__ __forceinline__ void rs_sigma(const int64_t (&X)[4], uint32_t nact, uint32_t (&sig)[4]) {
+    uint64_t mx = 0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) mx = ((uint32_t)a < nact && (uint64_t)X[a] > mx) ? (uint64_t)X[a] : mx;
+    const uint32_t hi = (uint32_t)(mx >> 32), bl = hi ? 64u - (uint32_t)__clz((int)hi) : 32u - (uint32_t)__clz((int)(uint32_t)mx), sh = bl > 31u ? bl - 31u : 0u;
+    uint64_t S = 0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) S += (uint32_t)a < nact ? (uint64_t)X[a] >> sh : 0ull;
+    const uint32_t even = RS_ONE / nact;
+    uint32_t rest = RS_ONE;
+    sig[0] = 0;
+#pragma unroll
+    for (int a = 1; a < 4; ++a) {
+        sig[a] = 0;
+        if ((uint32_t)a < nact) sig[a] = mx ? rs_div(((uint64_t)X[a] >> sh) << 15, S) : even;
+        rest -= sig[a];
+    }
+    sig[0] = rest;
+}
+
+}  // namespace
+
+// registers: one workgroup per CU is two waves per SIMD
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_river_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, RsTree tree, RsSpots spots,
+                                                             RsOut out, char *ws, uint32_t iters, uint32_t m) {
+    __shared__ uint32_t T[EVAL7_TAB_WORDS];
+    __shared__ uint64_t slot[RS_SLOTS];               // key << 11 | pool holding, sorted once per spot; all ones = no holding.  After the
+                                                      // sort the same memory holds rs and posof (below)
+    __shared__ uint64_t pre[RS_PREFIX];               // pre[i]: both players' reach at sorted positions 0 .. i - 1
+    __shared__ uint64_t pool[64];                     // card j of the pool (canonical order) as its bit in the suit-lane layout
+    __shared__ uint32_t canon[64];                    // ... and its canonical index
+    __shared__ uint64_t wsum[RS_WAVES];
+    __shared__ RsTree tr;
+    uint64_t *const rs = slot;                                                   // [RS_SORTED] a terminal's reaches in sorted order
+    uint16_t *const posof = reinterpret_cast<uint16_t *>(slot + RS_SORTED);      // [RS_SORTED] pool holding -> its sorted position
+    static_assert(RS_SORTED * 8 + RS_SORTED * 2 <= RS_SLOTS * 8, "rs and posof fit the sort slots");
+    stage_eval7_tab<RS_BLOCK>(T, tab);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
+    for (uint32_t w = tid; w < (uint32_t)(sizeof(RsTree) / 4); w += RS_BLOCK)
+        reinterpret_cast<uint32_t *>(&tr)[PK_IDX(w, sizeof(RsTree) / 4, "tree")] = reinterpret_cast<const uint32_t *>(&tree)[w];
+    __syncthreads();
+    const uint32_t n = uniform(tr.n), pot = uniform(tr.pot);
+    uint32_t D = 0;
+    for (uint32_t v = 0; v < n; ++v) D += tr.kind[PK_IDX(v, RS_MAX_NODES, "kind")] <= RS_P1 ? 1u : 0u;
+    D = uniform(D);
+    // the workgroup's slice of the work space, every array [n][RS_SORTED]
+    char *const base = ws + (size_t)blockIdx.x * rs_group_bytes(n);
+    const size_t plane = (size_t)n * RS_SORTED;
+    int64_t *const R = reinterpret_cast<int64_t *>(base), *const A = R + plane, *const U0 = A + plane, *const U1 = U0 + plane;
+    uint64_t *const RR = reinterpret_cast<uint64_t *>(U1 + plane);
+    uint32_t *const SG = reinterpret_cast<uint32_t *>(RR + plane);
+    auto at = [&](uint32_t node, uint32_t i) -> size_t { return (size_t)PK_IDX(node, n, "node") * RS_SORTED + PK_IDX(i, RS_SORTED, "position"); };
+    // a decision node's children (every lane of the wave asks together: the answer is wave-uniform); the slots past nact: node 0, never used
+    auto kids = [&](uint32_t node, uint32_t nact, uint32_t (&ch)[4]) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) ch[a] = (uint32_t)a < nact ? uniform((uint32_t)tr.child[PK_IDX(node, RS_MAX_NODES, "child")][a]) : 0u;
+    };
+
+    for (uint32_t spot = blockIdx.x; spot < m; spot += gridDim.x) {
+        __syncthreads();                              // (the table and the tree; the spot before: its pool and positions are done with)
+        const uint64_t *d = desc + (size_t)spot * RS_DESC_WORDS;
+        const uint64_t known = uniform(d[0]), meta = uniform(d[2]);
+        const bool good = ((uint32_t)meta & 1u) != 0u;
+        const uint64_t avail = good ? uniform(d[1]) : 0ull;     // (a refused spot: no holding is valid, every output is 0)
+        const uint32_t P = (uint32_t)(meta >> 56);
+        // ---- zeros: every output at the holdings that are not in the pool, by the lanes of the fixed index h = tid + 512 j
+        for (uint32_t h = tid; h < (uint32_t)RS_HOLDINGS; h += RS_BLOCK) {
+            uint32_t ca = 0, cb = 1;
+            unpair(h, ca, cb);
+            if ((avail >> ca) & (avail >> cb) & 1ull) continue;
+            for (uint32_t p = 0; p < 2u; ++p) {
+                if (out.value) out.value[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
+                if (out.br) out.br[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
+            }
+            if (out.strategy)
+                for (uint32_t r = 0; r < D * 4u; ++r) out.strategy[((size_t)spot * D * 4 + r) * RS_HOLDINGS + h] = 0;
+        }
+        if (!good) continue;
+        fill_pool(pool, canon, avail, tid);
+        __syncthreads();
+        const uint32_t nh = tri(P);
+        uint32_t npad = 64;
+        while (npad < nh) npad <<= 1;                 // (> nh: C(P, 2) is no power of two for P >= 3, so a pad slot always exists)
+        // ---- rank: every pool holding once, on the complete board
+        for (uint32_t ph = tid; ph < npad; ph += RS_BLOCK) {
+            uint64_t s = ~0ull;
+            if (ph < nh) {
+                uint32_t ea, eb;
+                unpair(ph, ea, eb);
+                const uint64_t bits = known | pool[PK_IDX(ea, 64, "pool")] | pool[PK_IDX(eb, 64, "pool")];
+                s = ((uint64_t)order_key(eval7_tab_back(eval7_tab_front_bits(bits, T), T)) << 11) | ph;
+            }
+            slot[PK_IDX(ph, RS_SLOTS, "slot")] = s;
+        }
+        __syncthreads();
+        // ---- order: bitonic sort of slot[0 .. npad), ascending
+        for (uint32_t kk = 2; kk <= npad; kk <<= 1) {
+            for (uint32_t jj = kk >> 1; jj > 0; jj >>= 1) {
+                for (uint32_t t = tid; t < (npad >> 1); t += RS_BLOCK) {
+                    const uint32_t lo = ((t & ~(jj - 1u)) << 1) | (t & (jj - 1u)), hi = lo | jj;
+                    const uint64_t a = slot[PK_IDX(lo, RS_SLOTS, "slot")], b = slot[PK_IDX(hi, RS_SLOTS, "slot")];
+                    const bool up = (lo & kk) == 0u;
+                    if ((a > b) == up) { slot[PK_IDX(lo, RS_SLOTS, "slot")] = b; slot[PK_IDX(hi, RS_SLOTS, "slot")] = a; }
+                }
+                __syncthreads();
+            }
+        }
+        // ---- the positions this lane owns: the holding there (pool slots ha < hb, fixed index gh) and the bounds of its key
+        uint32_t ha[RS_PER_LANE], hb[RS_PER_LANE], gh[RS_PER_LANE], lb[RS_PER_LANE], ub[RS_PER_LANE], hph[RS_PER_LANE];
+#pragma unroll
+        for (int j = 0; j < RS_PER_LANE; ++j) {
+            const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+            ha[j] = 0; hb[j] = 1; gh[j] = 0; lb[j] = 0; ub[j] = 0; hph[j] = 0;
+            if (i < nh) {
+                const uint64_t s = slot[PK_IDX(i, RS_SLOTS, "slot")];
+                const uint32_t kh = (uint32_t)(s >> 11);
+                hph[j] = (uint32_t)s & 2047u;
+                unpair(hph[j], ha[j], hb[j]);
+                gh[j] = tri(canon[PK_IDX(hb[j], 64, "canon")]) + canon[PK_IDX(ha[j], 64, "canon")];
+                uint32_t l = 0, u = 0;                                          // sorted positions with a key < kh, <= kh
+                for (uint32_t step = npad >> 1; step > 0; step >>= 1) {
+                    const uint32_t kl = (uint32_t)(slot[PK_IDX(l + step - 1u, RS_SLOTS, "slot")] >> 11);
+                    const uint32_t ku = (uint32_t)(slot[PK_IDX(u + step - 1u, RS_SLOTS, "slot")] >> 11);
+                    l += kl < kh ? step : 0u;
+                    u += ku <= kh ? step : 0u;
+                }
+                lb[j] = l; ub[j] = u;
+            }
+        }
+        __syncthreads();                              // (the slots have been read: their memory becomes rs and posof)
+#pragma unroll
+        for (int j = 0; j < RS_PER_LANE; ++j) {
+            const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+            if (i < nh) posof[PK_IDX(hph[j], RS_SORTED, "posof")] = (uint16_t)i;
+        }
+        // ---- the root's reaches; regrets and accumulators start at 0
+        const uint16_t *w0 = spots.ranges + (size_t)spot * 2 * RS_HOLDINGS, *w1 = w0 + RS_HOLDINGS;
+#pragma unroll
+        for (int j = 0; j < RS_PER_LANE; ++j) {
+            const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+            if (i >= nh) continue;
+            RR[at(0, i)] = ((uint64_t)w0[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 4) | ((uint64_t)w1[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 36);
+            for (uint32_t v = 1; v < n; ++v) { R[at(v, i)] = 0; A[at(v, i)] = 0; }
+        }
+        __syncthreads();                              // (posof)
+
+        // A terminal node: both players' values of every holding from the opponent's reaches (every lane of the workgroup comes here)
+        auto terminal = [&](uint32_t node, uint32_t kind) {
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                if (i < nh) rs[PK_IDX(i, RS_SORTED, "rs")] = RR[at(node, i)];
+            }
+            __syncthreads();
+            // exclusive prefix sum in sorted order: three positions per lane, a wave scan, the waves' totals
+            uint64_t v[RS_PER_LANE], mine = 0;
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid * RS_PER_LANE + (uint32_t)j;
+                v[j] = i < nh ? rs[PK_IDX(i, RS_SORTED, "rs")] : 0ull;
+                mine += v[j];
+            }
+            uint64_t inc = mine;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint64_t y = __shfl_up(inc, off);
+                inc += lane >= (uint32_t)off ? y : 0ull;
+            }
+            if (lane == 63u) wsum[PK_IDX(wave, RS_WAVES, "wsum")] = inc;
+            __syncthreads();
+            uint64_t run = inc - mine, all = 0;
+#pragma unroll
+            for (int w = 0; w < RS_WAVES; ++w) {
+                const uint64_t s = wsum[PK_IDX(w, RS_WAVES, "wsum")];
+                run += (uint32_t)w < wave ? s : 0ull;
+                all += s;
+            }
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid * RS_PER_LANE + (uint32_t)j;
+                if (i < (uint32_t)RS_PREFIX) pre[PK_IDX(i, RS_PREFIX, "pre")] = run;
+                run += v[j];
+            }
+            __syncthreads();
+            const uint32_t f = kind - RS_FOLD0, pf = tr.put[PK_IDX(node, RS_MAX_NODES, "put")][f & 1u], c = tr.put[PK_IDX(node, RS_MAX_NODES, "put")][0];
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                if (i >= nh) continue;
+                const uint64_t below0 = pre[PK_IDX(lb[j], RS_PREFIX, "pre")], self = rs[PK_IDX(i, RS_SORTED, "rs")];
+                uint64_t below = below0, equal = pre[PK_IDX(ub[j], RS_PREFIX, "pre")] - below0 - self, conf = self;
+                // card removal: every holding {ha, x}, {hb, x}, by its own sorted position
+                const uint32_t ta = tri(ha[j]), tb = tri(hb[j]);
+                // (no branch in the loop, so that the loads of several x are in flight together: x = ha or hb looks h itself up and counts 0)
+#pragma unroll 4
+                for (uint32_t x = 0; x < P; ++x) {
+                    const bool own = x == ha[j] || x == hb[j];
+                    const uint32_t tx = tri(x);
+                    const uint32_t i0 = own ? hph[j] : pair(ha[j], ta, x, tx), i1 = own ? hph[j] : pair(hb[j], tb, x, tx);
+                    const uint32_t p0 = posof[PK_IDX(i0, RS_SORTED, "posof")], p1 = posof[PK_IDX(i1, RS_SORTED, "posof")];
+                    const uint64_t r0 = own ? 0ull : rs[PK_IDX(p0, RS_SORTED, "rs")], r1 = own ? 0ull : rs[PK_IDX(p1, RS_SORTED, "rs")];
+                    conf += r0 + r1;
+                    below -= (p0 < lb[j] ? r0 : 0ull) + (p1 < lb[j] ? r1 : 0ull);
+                    equal -= ((p0 >= lb[j] && p0 < ub[j]) ? r0 : 0ull) + ((p1 >= lb[j] && p1 < ub[j]) ? r1 : 0ull);
+                }
+                const uint64_t S = all - conf, above = S - below - equal;
+                int64_t u0, u1;                       // player 0 meets player 1's reach (the high halves), player 1 the low ones
+                if (kind == RS_SHOWDOWN) {
+                    u0 = (int64_t)(2u * (pot + c)) * (int64_t)(below >> 32) + (int64_t)pot * (int64_t)(equal >> 32) - (int64_t)(2u * c) * (int64_t)(above >> 32);
+                    u1 = (int64_t)(2u * (pot + c)) * (int64_t)(uint32_t)below + (int64_t)pot * (int64_t)(uint32_t)equal - (int64_t)(2u * c) * (int64_t)(uint32_t)above;
+                } else {
+                    const int64_t lose = -(int64_t)(2u * pf), gain = (int64_t)(2u * (pot + pf));
+                    u0 = (f == 0u ? lose : gain) * (int64_t)(S >> 32);
+                    u1 = (f == 1u ? lose : gain) * (int64_t)(uint32_t)S;
+                }
+                U0[at(node, i)] = u0;
+                U1[at(node, i)] = u1;
+            }
+            __syncthreads();                          // (rs, pre and the totals are rewritten by the next terminal)
+        };
+
+        // One walk down: reaches, and every terminal's values.  FROM_R: the probabilities come from the regrets and are kept in SG;
+        // otherwise SG is played as it stands.
+        auto down = [&](bool from_r) {
+            for (uint32_t node = 0; node < n; ++node) {
+                const uint32_t kind = uniform((uint32_t)tr.kind[PK_IDX(node, RS_MAX_NODES, "kind")]);
+                if (kind > RS_P1) { terminal(node, kind); continue; }
+                const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, RS_MAX_NODES, "nact")]);
+                uint32_t ch[4];
+                kids(node, nact, ch);
+#pragma unroll
+                for (int j = 0; j < RS_PER_LANE; ++j) {
+                    const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                    if (i >= nh) continue;
+                    uint32_t sig[4];
+                    if (from_r) {
+                        int64_t X[4];
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) X[a] = (uint32_t)a < nact ? R[at(ch[a], i)] : 0;
+                        rs_sigma(X, nact, sig);
+                    }
+                    const uint64_t rr = RR[at(node, i)];
+                    const uint32_t r0 = (uint32_t)rr, r1 = (uint32_t)(rr >> 32);
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        if ((uint32_t)a >= nact) continue;
+                        const size_t e = at(ch[a], i);
+                        if (from_r) SG[e] = sig[a]; else sig[a] = SG[e];
+                        const uint32_t mine = (uint32_t)(((uint64_t)(kind == RS_P0 ? r0 : r1) * sig[a]) >> 15);
+                        RR[e] = kind == RS_P0 ? ((uint64_t)mine | ((uint64_t)r1 << 32)) : ((uint64_t)r0 | ((uint64_t)mine << 32));
+                    }
+                }
+            }
+        };
+
+        // ---- the iterations: one walk down, then the walk up with the regret and accumulator updates of each decision node
+        for (uint32_t t = 1; t <= iters; ++t) {
+            down(true);
+            for (uint32_t node = n; node-- > 0u;) {
+                const uint32_t kind = uniform((uint32_t)tr.kind[PK_IDX(node, RS_MAX_NODES, "kind")]);
+                if (kind > RS_P1) continue;
+                const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, RS_MAX_NODES, "nact")]);
+                int64_t *const Up = kind == RS_P0 ? U0 : U1, *const Uq = kind == RS_P0 ? U1 : U0;
+                uint32_t ch[4];
+                kids(node, nact, ch);
+#pragma unroll
+                for (int j = 0; j < RS_PER_LANE; ++j) {
+                    const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                    if (i >= nh) continue;
+                    int64_t up[4], acc = 0, uq = 0;
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        up[a] = 0;
+                        if ((uint32_t)a >= nact) continue;
+                        const size_t e = at(ch[a], i);
+                        up[a] = Up[e];
+                        acc += (int64_t)SG[e] * up[a];
+                        uq += Uq[e];
+                    }
+                    const int64_t un = acc >> 15;     // (the sum first, the floor once)
+                    Up[at(node, i)] = un;
+                    Uq[at(node, i)] = uq;
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        if ((uint32_t)a >= nact) continue;
+                        const size_t e = at(ch[a], i);
+                        const int64_t r = R[e] + up[a] - un;
+                        R[e] = r > 0 ? r : 0;
+                        const uint64_t rr = RR[e];
+                        A[e] += (int64_t)((uint64_t)t * (uint64_t)(kind == RS_P0 ? (uint32_t)rr : (uint32_t)(rr >> 32)));
+                    }
+                }
+            }
+        }
+
+        // ---- the average strategy: the rule applied to the accumulators; it stays in SG for the last walk
+        for (uint32_t node = 0; node < n; ++node) {
+            const uint32_t kind = uniform((uint32_t)tr.kind[PK_IDX(node, RS_MAX_NODES, "kind")]);
+            if (kind > RS_P1) continue;
+            const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, RS_MAX_NODES, "nact")]), row = uniform((uint32_t)tr.row[PK_IDX(node, RS_MAX_NODES, "row")]);
+            uint32_t ch[4];
+            kids(node, nact, ch);
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                if (i >= nh) continue;
+                int64_t X[4];
+                uint32_t sig[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) X[a] = (uint32_t)a < nact ? A[at(ch[a], i)] : 0;
+                rs_sigma(X, nact, sig);
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    if ((uint32_t)a < nact) SG[at(ch[a], i)] = sig[a];
+                    if (out.strategy) out.strategy[(((size_t)spot * D + row) * 4 + (uint32_t)a) * RS_HOLDINGS + gh[j]] = (uint16_t)sig[a];
+                }
+            }
+        }
+        if (!(out.value || out.br)) continue;
+        // ---- its values and the best responses against it: the walk up carries, beside each player's value, the value of the player
+        // who plays the maximum at its own nodes (B0 / B1, in the memory of R / A; a terminal's is its value)
+        down(false);
+        for (uint32_t node = n; node-- > 0u;) {
+            const uint32_t kind = uniform((uint32_t)tr.kind[PK_IDX(node, RS_MAX_NODES, "kind")]);
+            if (kind > RS_P1) continue;
+            const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, RS_MAX_NODES, "nact")]);
+            int64_t *const Up = kind == RS_P0 ? U0 : U1, *const Uq = kind == RS_P0 ? U1 : U0;
+            int64_t *const Bp = kind == RS_P0 ? R : A, *const Bq = kind == RS_P0 ? A : R;
+            uint32_t ch[4];
+            bool leaf[4];
+            kids(node, nact, ch);
+#pragma unroll
+            for (int a = 0; a < 4; ++a) leaf[a] = uniform((uint32_t)tr.kind[PK_IDX(ch[a], RS_MAX_NODES, "kind")]) > RS_P1;
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                if (i >= nh) continue;
+                int64_t acc = 0, uq = 0, bp = 0, bq = 0;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    if ((uint32_t)a >= nact) continue;
+                    const size_t e = at(ch[a], i);
+                    const int64_t up = Up[e], uqa = Uq[e], bpa = leaf[a] ? up : Bp[e], bqa = leaf[a] ? uqa : Bq[e];
+                    acc += (int64_t)SG[e] * up;
+                    uq += uqa;
+                    bp = (a == 0 || bpa > bp) ? bpa : bp;
+                    bq += bqa;
+                }
+                Up[at(node, i)] = acc >> 15;
+                Uq[at(node, i)] = uq;
+                Bp[at(node, i)] = bp;
+                Bq[at(node, i)] = bq;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < RS_PER_LANE; ++j) {
+            const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+            if (i >= nh) continue;
+            const size_t o = (size_t)spot * 2 * RS_HOLDINGS + gh[j];
+            if (out.value) { out.value[o] = U0[at(0, i)]; out.value[o + RS_HOLDINGS] = U1[at(0, i)]; }
+            if (out.br) { out.br[o] = R[at(0, i)]; out.br[o + RS_HOLDINGS] = A[at(0, i)]; }
+        }
+    }
+}
+
+namespace pk {
+
+hipError_t rs_launch(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTree &tree, uint32_t iters, size_t m, const RsOut &out,
+                     char *work) {
+    if (m == 0) return hipSuccess;
+    const RsPrepArgs a{spots, out.status, (uint64_t *)work, m};
+    hipLaunchKernelGGL(k_rs_prep, dim3((unsigned)((m + RS_PREP_BLOCK - 1) / RS_PREP_BLOCK)), dim3(RS_PREP_BLOCK), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !(out.strategy || out.value || out.br)) return e;   // (status alone: the preparation kernel has written it)
+    hipLaunchKernelGGL(k_river_solve, dim3(rs_grid(m)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, tree, spots, out, work + rs_desc_bytes(m),
+                       iters, (uint32_t)m);
+    return hipGetLastError();
+}
+
+}  // namespace pk

@@ -1,0 +1,63 @@
+// pk_river_solver.hpp -- the river subgame solver: heads-up CFR+ over a caller's betting tree, one subgame per workgroup, in integers
+// (include/pokerl_hip.h "River solver"): what the host entry points (pk_api.hip) and the kernels
+// (pk_river_solver.hip) share.  The table kernels do not include it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "pk_equity.hpp"
+
+namespace pk {
+
+constexpr int RS_HOLDINGS = PK_EQ_HOLDINGS;              // C(52, 2): the fixed holding index of the ranges and of every output
+constexpr int RS_BLOCK = 512, RS_WAVES = RS_BLOCK / 64;
+constexpr int RS_PER_LANE = 3;                           // sorted positions a lane owns: i = tid, tid + 512, tid + 1024
+constexpr int RS_GRID_MAX = 256;                         // persistent grid: one 512-thread workgroup per CU (its work space is megabytes)
+constexpr int RS_MAX_NODES = PK_RS_MAX_NODES, RS_MAX_ITERS = PK_RS_MAX_ITERS;
+constexpr uint32_t RS_MAX_CHIPS = PK_RS_MAX_CHIPS;
+constexpr uint32_t RS_ONE = PK_RS_ONE;                   // a probability of 1 (Q15)
+constexpr int RS_POOL_HOLDINGS = 1081;                   // C(47, 2): holdings of the largest pool (five board cards are always gone)
+constexpr int RS_SORTED = 1088;                          // ... padded: sorted positions per node of the work space and of the LDS arrays
+constexpr int RS_PREFIX = RS_SORTED + 8;                 // exclusive prefix sums: positions 0 .. nh inclusive
+constexpr int RS_SLOTS = 2048;                           // sort slots: the next power of two
+constexpr int RS_DESC_WORDS = 3;                         // a spot's descriptor: as range vs range's (pk_equity_rvr.hpp), k = 0
+static_assert(RS_BLOCK * RS_PER_LANE >= RS_POOL_HOLDINGS && RS_SORTED >= RS_POOL_HOLDINGS && RS_SORTED % 8 == 0, "a lane owns at most RS_PER_LANE positions");
+
+enum { RS_P0 = 0, RS_P1 = 1, RS_FOLD0 = 2, RS_FOLD1 = 3, RS_SHOWDOWN = 4 };
+
+// The tree as the kernel takes it (by value: it travels with the launch, so the caller's host arrays are done with when the call returns).
+// nact and row are derived by the host check: a decision node's number of children, and its row of `strategy`.
+struct RsTree {
+    uint32_t n, pot;
+    uint32_t put[RS_MAX_NODES][2];
+    uint8_t kind[RS_MAX_NODES], nact[RS_MAX_NODES], row[RS_MAX_NODES];
+    uint8_t child[RS_MAX_NODES][4];
+};
+static_assert(sizeof(RsTree) % 4 == 0 && sizeof(RsTree) <= 1024, "copied into LDS as 32-bit words");
+
+struct RsSpots {
+    const uint8_t *board;      // [m][5]
+    const uint64_t *dead;      // [m], NULL: none
+    const uint16_t *ranges;    // [m][2][1326]
+};
+struct RsOut {                 // any may be NULL
+    uint16_t *strategy;        // [m][D][4][1326]
+    int64_t *value, *br;       // [m][2][1326]
+    uint8_t *status;           // [m]
+};
+
+// Work space: the m descriptors, then -- sized by the grid, never by m -- per workgroup and per (node, sorted position): the regret and the
+// average accumulator of the edge INTO the node, both players' values, both players' reaches (one 64-bit word) and the edge's probability.
+constexpr size_t RS_NODE_BYTES = (size_t)RS_SORTED * (5 * 8 + 4);
+constexpr unsigned rs_grid(size_t m) { return (unsigned)(m < (size_t)RS_GRID_MAX ? m : (size_t)RS_GRID_MAX); }
+constexpr size_t rs_desc_bytes(size_t m) { return (m * RS_DESC_WORDS * sizeof(uint64_t) + 255) & ~(size_t)255; }
+constexpr size_t rs_group_bytes(uint32_t n) { return (size_t)n * RS_NODE_BYTES; }
+constexpr size_t rs_work_bytes(size_t m, uint32_t n, bool solve) { return rs_desc_bytes(m) + (solve ? (size_t)rs_grid(m) * rs_group_bytes(n) : 0); }
+
+// Queues the whole call on `stream`: descriptors + status (one lane per spot), then -- where strategy, value or br is wanted -- the
+// persistent kernel.  tab: the evaluator table (eval7_table).  The tree has passed the host check (pk_api.hip rs_check_tree).
+hipError_t rs_launch(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTree &tree, uint32_t iters, size_t m, const RsOut &out,
+                     char *work);
+
+}  // namespace pk

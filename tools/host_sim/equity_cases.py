@@ -59,6 +59,7 @@ import hero_hist_spec as HHS             # noqa: E402
 import hist_cluster_spec as CS          # noqa: E402
 import hist_spec as HS                  # noqa: E402
 import preflop_spec as PS               # noqa: E402
+import river_solver_spec as RVS         # noqa: E402
 import ranged_ev_spec as XS             # noqa: E402
 import rvr_spec as VS                   # noqa: E402
 from oracle import rng_spec as R        # noqa: E402
@@ -73,7 +74,8 @@ OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("w
            "rangedev": ("share", "level_seat", "amount", "ev", "accepted", "status"),
            "cluster": ("centroids_out", "label", "dist", "inertia", "changed"),
            "herohist": ("hist", "void", "completions", "status"), "preflop": ("win", "tie"),
-           "pfhero": ("agg", "win", "tie", "boards", "status"), "pfrvr": ("win", "tie", "tot")}
+           "pfhero": ("agg", "win", "tie", "boards", "status"), "pfrvr": ("win", "tie", "tot"),
+           "riversolve": ("strategy", "value", "br", "status")}
 
 
 class Case:
@@ -1072,6 +1074,65 @@ def preflop_reader_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- river solver
+def river_case(name, pools, tree, iters, seed, grid=1, outputs=None, quick=True, edit=None, redit=None):
+    """k_rs_prep + k_river_solve against tests/river_solver_spec.py; int64 value / br are compared as their bit patterns."""
+    board, _, dead = board_spots(seed, [(5, p) for p in pools])
+    m = len(pools)
+    rng = np.random.default_rng(seed + 1)
+    ranges = rng.integers(0, 65536, (m, 2, HOLDINGS)).astype(np.uint16)
+    for row in ranges.reshape(-1, HOLDINGS):
+        row[rng.integers(0, HOLDINGS, 200)] = 0
+        row[rng.integers(0, HOLDINGS, 100)] = 65535
+    if edit:
+        edit(board, dead)
+    if redit:
+        redit(ranges)
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [grid]), "iters": ("u32", [iters]), "n": ("u32", [tree.n]), "pot": ("u32", [tree.pot]),
+              "kind": ("u8", tree.kind), "child": ("u8", tree.child), "put": ("u32", tree.put), "board": ("u8", board), "dead": ("u64", dead),
+              "ranges": ("u16", ranges)}
+
+    def expect():
+        r = RVS.solve_batch(board, ranges, tree, iters, dead)
+        return dict(strategy=r["strategy"], value=r["value"].view(np.uint64), br=r["br"].view(np.uint64), status=r["status"])
+    return Case(name, "riversolve", arrays, expect, outputs, quick)
+
+
+def river_cases():
+    """Every case at a grid of 1: one workgroup takes the spots in turn, so stale LDS or work space of the spot before would show."""
+    from pokerl_amd.solver import RiverTree, river_tree
+    small, default = river_tree(100, 50), river_tree(100, 400)
+    FF = 0xFF
+    forced = RiverTree([0, 1, 4], [[1, FF, FF, FF], [2, FF, FF, FF], [FF] * 4], [[0, 0]] * 3, 77)
+    four = RiverTree([0, 4, 1, 1, 1, 3, 4, 3, 4, 3, 4], [[1, 2, 3, 4], [FF] * 4, [5, 6, FF, FF], [7, 8, FF, FF], [9, 10, FF, FF]] + [[FF] * 4] * 6,
+                     [[0, 0], [0, 0], [50, 0], [100, 0], [200, 0], [50, 0], [50, 50], [100, 0], [100, 100], [200, 0], [200, 200]], 100)
+
+    def royal_board(board, dead):                                     # ten to ace of one suit, the rest of that suit dead: the board plays
+        board[:] = np.array([8, 9, 10, 11, 12], np.uint8)             # for everyone, every pair of holdings ties
+        for i in range(len(dead)):
+            d = (int(dead[i]) & ~sum(1 << (r * 4) for r in range(8, 13))) | sum(1 << (r * 4) for r in range(8))
+            dead[i] = np.uint64(d)
+
+    def break_middle_board(board, dead):
+        board[1, 1] = board[1, 0]
+
+    def zero_one(ranges):
+        ranges[0, 1] = 0
+        ranges[1, 0] = 0
+    cs = [river_case("rsolve-pools-grid1", (4, 9, 33, 46), small, 2, 31),
+          river_case("rsolve-default-tree-iters1", (9, 12), default, 1, 32),
+          river_case("rsolve-default-tree-iters3", (6, 17), default, 3, 33),
+          river_case("rsolve-forced-and-four", (5, 24), forced, 2, 34),
+          river_case("rsolve-four-actions", (11, 32), four, 2, 35),
+          river_case("rsolve-refused-between", (12, 9, 11), small, 2, 36, edit=break_middle_board),
+          river_case("rsolve-all-ties", (10, 14), small, 3, 37, edit=royal_board),
+          river_case("rsolve-one-range-zero", (12, 16), default, 2, 38, redit=zero_one),
+          river_case("rsolve-grid2-status-only", (9, 9, 9), small, 1, 39, grid=2, outputs=("status",), edit=break_middle_board),
+          river_case("rsolve-no-strategy", (7, 8), small, 2, 40, outputs=("value", "br", "status"))]
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -1086,7 +1147,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""Timings of the river solver (pk_solve_river_d) on one MI355X, printed as ONE JSON line and written to profiles/river_solver_bench.json
+(stamped with the library's source hash).  Legs: m = 512 and 4 096 full-pool river subgames (random boards, random ranges with zeros and
+65 535s), the default tree river_tree(100, 400), 256 iterations, all outputs.  Per leg: milliseconds per call (a HIP event pair on the
+call's stream and the host's clock, every shape warmed up, median of `--samples`), solves per second, and the call's work-space bytes
+(the descriptors plus one slice per resident workgroup).  For scale, --spec-iters N times N iterations of the numpy restatement
+(tests/river_solver_spec.py) of ONE of the same subgames on the host and reports seconds per iteration.
+
+    python tools/river_solver_bench.py [--samples 3] [--m 512 4096] [--iters 256] [--spec-iters 4]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import numpy as np  # noqa: E402
+import pokerl_amd  # noqa: E402
+from pokerl_amd import _lib as L  # noqa: E402
+from pokerl_amd import hipmem, solver  # noqa: E402
+from pokerl_amd.hipmem import DeviceBuffer  # noqa: E402
+from equity_bench import CANON, time_stream  # noqa: E402
+import kernel_meta  # noqa: E402
+
+H = L.EQ_HOLDINGS
+NODE_BYTES = 1088 * 44      # pk::RS_NODE_BYTES: a workgroup's work space per tree node
+
+
+def work_bytes(m, n):
+    """pk::rs_work_bytes"""
+    return ((m * 24 + 255) & ~255) + min(m, solver.GRID_MAX) * n * NODE_BYTES
+
+
+def subgames(rng, m):
+    board = np.zeros((m, 5), np.uint8)
+    for i in range(m):
+        board[i] = [CANON[c] for c in rng.permutation(52)[:5]]
+    ranges = rng.integers(0, 65536, (m, 2, H)).astype(np.uint16)
+    for row in ranges.reshape(-1, H):
+        row[rng.integers(0, H, 200)] = 0
+        row[rng.integers(0, H, 100)] = 65535
+    return board, ranges
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", type=int, default=3)
+    ap.add_argument("--m", type=int, nargs="+", default=[512, 4096])
+    ap.add_argument("--iters", type=int, default=256)
+    ap.add_argument("--spec-iters", type=int, default=0)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "river_solver_bench.json"))
+    args = ap.parse_args()
+    if pokerl_amd.device_count() < 1:
+        sys.exit("river_solver_bench: no MI355X visible (no fallback)")
+    hip = hipmem._lib()
+    stream = C.c_void_p()
+    assert hip.hipStreamCreateWithFlags(C.byref(stream), 1) == 0
+    rng = np.random.default_rng(0)
+    tree = solver.river_tree(100, 400)
+    D = len(tree.decision_nodes)
+    meta = kernel_meta.kernels(L.LIB_PATH)["k_river_solve"]
+    res = dict(tool="river_solver_bench", src=L.source_hash(), samples=args.samples, iters=args.iters, tree_nodes=tree.n, decision_nodes=D, legs={},
+               k_river_solve=dict(vgprs=meta["vgprs"], sgprs=meta["sgprs"], lds=meta["lds"], scratch=meta["private_segment"], block=512, grid_max=solver.GRID_MAX))
+    board, ranges = subgames(rng, max(args.m))
+    for m in args.m:
+        ins = [DeviceBuffer(x.nbytes).upload(x) for x in (np.ascontiguousarray(board[:m]), np.ascontiguousarray(ranges[:m]))]
+        strategy, value, br, status = DeviceBuffer(m * D * 4 * H * 2), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m)
+
+        def run():
+            solver.solve_river_d(m, ins[0].ptr, ins[1].ptr, tree, args.iters, strategy_d=strategy.ptr, value_d=value.ptr, br_d=br.ptr, status_d=status.ptr,
+                                 stream=stream)
+
+        us, each, wall, odd = time_stream(run, stream, args.samples, warmup=1)
+        assert not status.download(np.uint8, m).any()
+        v, b = value.download(np.int64, m * 2 * H), br.download(np.int64, m * 2 * H)
+        assert (b >= v).all() and v.any()
+        res["legs"]["m_%d" % m] = dict(ms_per_call=round(us * 1e-3, 3), samples_ms=[round(x * 1e-3, 3) for x in each], host_clock_ms=round(wall * 1e-3, 3),
+                                       event_anomalies=odd, solves_per_s=round(m / (us * 1e-6), 1), iterations_per_s=round(m * args.iters / (us * 1e-6), 0),
+                                       work_space_bytes=work_bytes(m, tree.n))
+        for x in ins + [strategy, value, br, status]:
+            x.free()
+    if args.spec_iters > 0:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import river_solver_spec as RS
+        RS.solve_spot([int(x) for x in board[0]], ranges[0], tree, 1)                       # (warm: the pairwise matrices' code paths)
+        t0 = time.perf_counter()
+        RS.solve_spot([int(x) for x in board[0]], ranges[0], tree, 1)
+        t1 = time.perf_counter()
+        RS.solve_spot([int(x) for x in board[0]], ranges[0], tree, 1 + args.spec_iters)
+        t2 = time.perf_counter()
+        per_iter = ((t2 - t1) - (t1 - t0)) / args.spec_iters
+        res["numpy_spec_on_the_host"] = dict(seconds_per_iteration=round(per_iter, 4), seconds_per_solve_extrapolated=round(per_iter * args.iters + (t1 - t0), 2),
+                                             note="one subgame, int64 numpy on one host core; not the device's yardstick, only a sense of scale")
+    hip.hipStreamDestroy(stream)
+    line = json.dumps(res)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()

@@ -9,6 +9,7 @@ import pytest
 
 import equity_ranged_spec as WS
 import equity_spec as ES
+from equity_seat_matrix import disjoint_rows
 
 pytestmark = pytest.mark.gpu
 KEYS = WS.KEYS
@@ -98,10 +99,7 @@ def test_word_count_edges(PK, hidden):
     """H hidden seats pre-flop at S = 128: H + 1 64-bit words (odd and even counts), 1 .. 9 Philox blocks.  Disjoint three-holding rows, so
     that sixteen drawn holdings do not collide; one seat uniform where there is room."""
     n = max(hidden, 2)
-    w = np.zeros((16, WS.HOLDINGS), np.uint16)
-    for r in range(16):
-        for a, b in ((3 * r, 3 * r + 1), (3 * r, 3 * r + 2), (3 * r + 1, 3 * r + 2)):
-            w[r, b * (b - 1) // 2 + a] = 1 + 1000 * r + a
+    w = disjoint_rows()
     holes = np.full((2, n, 2), 0xFF, np.uint8)
     if hidden < n:
         holes[:, 0] = [ES.CANON[50], ES.CANON[51]]
@@ -124,10 +122,7 @@ def test_range_count_edges(PK, four):
     ro = np.zeros((8, 6), np.uint16)
     got = device_ranged(holes, board, nboard, live, 100, one, nonce=1)                   # one vector: every hidden seat draws from it
     assert_equal(got, spec(holes, board, nboard, live, 100, one, ro, nonce=1), "R = 1")
-    w = np.zeros((16, WS.HOLDINGS), np.uint16)
-    for r in range(16):
-        for a, b in ((3 * r, 3 * r + 1), (3 * r, 3 * r + 2), (3 * r + 1, 3 * r + 2)):
-            w[r, b * (b - 1) // 2 + a] = int(rng.integers(1, 65536))
+    w = disjoint_rows(rng)
     h16 = np.full((3, 16, 2), 0xFF, np.uint8)
     b16 = np.array([[ES.CANON[48], ES.CANON[49], ES.CANON[50], ES.CANON[51], 0]] * 3, np.uint8)
     nb16, lv16 = np.array([0, 3, 4], np.uint8), np.full(3, 0xFFFF, np.uint16)

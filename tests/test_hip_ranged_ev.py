@@ -13,6 +13,7 @@ import equity_ranged_spec as WS
 import equity_spec as ES
 import ev_witness as W
 import ranged_ev_spec as XS
+from equity_seat_matrix import disjoint_rows
 
 pytestmark = pytest.mark.gpu
 KEYS = XS.KEYS
@@ -76,15 +77,6 @@ def mixed_rows(rng, m, n):
 
 def pattern_bets(n, live):
     return np.array([XS.bet_patterns(n, live[i], i) for i in range(len(live))], np.float64)
-
-
-def disjoint_rows(rng=None):
-    """Sixteen rows of three holdings each over cards 3 r .. 3 r + 2: sixteen drawn holdings never collide."""
-    w = np.zeros((16, WS.HOLDINGS), np.uint16)
-    for r in range(16):
-        for a, b in ((3 * r, 3 * r + 1), (3 * r, 3 * r + 2), (3 * r + 1, 3 * r + 2)):
-            w[r, b * (b - 1) // 2 + a] = 1 + 1000 * r + a if rng is None else int(rng.integers(1, 65536))
-    return w
 
 
 @pytest.mark.parametrize("n", [2, 3, 6, 9, 16])

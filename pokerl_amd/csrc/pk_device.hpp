@@ -211,6 +211,7 @@ __device__ __forceinline__ uint32_t rep4(uint32_t x) {
 //   PK_PIN_VGPR(x)          the empty asm that makes x a VGPR of its own
 //   PK_IDX(i, n, what)      an array index; the CPU builds check i < n (ASan's redzones cannot see a read 32 KB past a member)
 //   PK_SHARED_OBJECT(T, x)  the workgroup's LDS object; the 64-lane CPU build supplies one heap allocation of sizeof(T) per wave
+//   PK_RING_COUNT(k, n)     nothing, unless the build defines it: wave_shim.h counts what ActionRing::ensure does (wave_sim --ring-stats)
 //   PK_DUMMY_STORE(d, l, v) a queue store; where d holds, several lanes may aim it at ONE dummy slot (LdsTab): whichever lands last wins, a relaxed
 //                           atomic for TSan; a store into a real slot stays a plain one, so that two lanes given the same slot are a reported race
 #ifdef PK_HOST_SIM
@@ -235,9 +236,14 @@ static inline I pk_sim_idx(I i, unsigned long long n, const char *what, const ch
 #define PK_SHARED_OBJECT(T, x) __shared__ T x
 #define PK_DUMMY_STORE(dummy, l, v) l = v
 #endif
+#ifndef PK_RING_COUNT
+#define PK_RING_COUNT(k, n)
+#endif
 template <typename T>
 __device__ __forceinline__ PK_GLOBAL T *as_global(T *p) { return (PK_GLOBAL T *)p; }   // (keep the result's TYPE: `auto g = as_global(p)`;
                                                                                        //  cast back to a flat pointer and the optimiser folds the pair away)
+// (`hi ^ c ^ k` stays two v_xor_b32: as one v_bitop3_b32, truth table 0x96, a block has 15 instructions fewer and k_rollout_tab<6> is no faster --
+//  `c ^ k` does not wait for the multiply, so the second xor only filled a slot the dependent chain leaves empty; docs/history.md, "Second slot diet".)
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -853,12 +859,15 @@ struct ActionRing {
         if (!primed || (int32_t)(filled - q) < 0) filled = q;
         primed = true;
         const int have = (int)(filled - q) * 8 - (int)((uint32_t)step_serial & 7);   // draws of this lane held in LDS
+        if (lane == 0) PK_RING_COUNT(0, 1);
         if (__any(may && have < ahead)) {
 #pragma unroll 1
             for (int r = 0; r < 2; ++r) {
                 const bool fill = (int32_t)(filled - q) < 2;
                 if (!__any(fill)) break;
+                if (lane == 0) PK_RING_COUNT(1, 1);
                 if (fill) {
+                    PK_RING_COUNT(2, 1);
                     const uint64_t b = qfull + (uint64_t)(filled - q);
                     uint32_t w[4];
                     philox4x32_10(table_id, (uint32_t)b, STREAM_ACTION, (uint32_t)(b >> 32), S.key0, S.key1, w);
@@ -1441,8 +1450,15 @@ struct Table {
 #ifdef PK_PROFILE_COUNTS
             prof.count_wave(S.prof, PF_N_SIDEPOT, PF_N_SIDEPOT_LANES);
 #endif
-            bool left = false;                                                     // any bet still > 0 (:499)
-            PK_FOR(p, N) left = left || !(pot_wb[p] <= 0.0); PK_END
+            // any bet still > 0 (:499).  FAST_MASKS (the fused rollout kernels): the test on the LARGEST bet -- N - 1 v_max_f64 and one compare
+            // where a test per seat is N compares and N - 1 lane-mask ORs (money is finite and never NaN; a largest bet of -0.0 or +0.0 fails
+            // the test like each of its seats).  The step and env kernels keep the per-seat form: Game.step lost 0.3 ... 0.7 % with the other.
+            constexpr bool FAST_MASKS = ONE_PASS;
+            auto any_left = [&]() {
+                if constexpr (FAST_MASKS) return !(vmax<N>(pot_wb) <= 0.0);
+                else { bool l = false; PK_FOR(p, N) l = l || !(pot_wb[p] <= 0.0); PK_END return l; }
+            };
+            bool left = any_left();
             if (pot_todo != 0 && left && pot_npw != 1) {                           // a general pass (:507-525)
                 int player = 0; double best = 0.0, max_bet = 0.0; bool have = false;
                 PK_FOR(p, N)                                                       // next seat in ascending ORIGINAL-bet order
@@ -1461,13 +1477,12 @@ struct Table {
                 // (s*0.0)/k == +0.0 for the rest (s >= 0), which leaves a non-negative payoff unchanged bit for bit.
                 double share = (nw == 2) ? s * 0.5 : s;                           // s / 2 == s * 0.5 exactly
                 if (nw > 2) share = s / (double)nw;                                // real division only for 3+-way ties
-                left = false;
                 PK_FOR(p, N)
                     payoffs[p] = ((win >> p) & 1) ? payoffs[p] + share : payoffs[p];
                     pot_hv[p] = (p == player) ? NONE_V : pot_hv[p];                // :522
                     pot_wb[p] = pot_wb[p] - mb[p];                                 // :523
-                    left = left || !(pot_wb[p] <= 0.0);
                 PK_END
+                left = any_left();
                 pot_npw -= 1;                                                      // :525
             }
             // what the next pass of the loop would do: stop (:498, :499), hand everything left to the last potential
@@ -1502,8 +1517,19 @@ struct Table {
                 // is over (:610) -- or if it never could: (a) dead table -- every seat's credits are exactly 0 and no
                 // seat is ACTIVE, so each further hand is a zero-chip showdown that re-creates this very state;
                 // (b) backstop: PK_HAND_CAP hands inside one step.  (Selects: one basic block up to the deal.)
+                // any credits != 0.0.  The fused rollout kernels: the OR of the seats' words with the sign bit masked (-0.0 == 0.0) and ONE compare,
+                // not a compare and a lane-mask OR per seat (the step and env kernels keep those, see `left` above)
                 bool chips = false;
-                PK_FOR(p, N) chips = chips || credits[p] != 0.0; PK_END
+                if constexpr (ONE_PASS) {
+                    uint32_t chips_hi = 0, chips_lo = 0;
+                    PK_FOR(p, N)
+                        const uint64_t cw = (uint64_t)__double_as_longlong(credits[p]);
+                        chips_hi |= (uint32_t)(cw >> 32); chips_lo |= (uint32_t)cw;
+                    PK_END
+                    chips = ((chips_hi & 0x7fffffffu) | chips_lo) != 0;
+                } else {
+                    PK_FOR(p, N) chips = chips || credits[p] != 0.0; PK_END
+                }
                 const bool dead = !chips && st_active == 0;
                 const bool capped = !foldout && !go && (dead || hands_this_step > PK_HAND_CAP);
                 flags = (go ? PK_FLAG_GAME_OVER : 0) | PK_FLAG_HAND_OVER | (foldout ? 0 : PK_FLAG_TURN_OVER);

@@ -76,6 +76,10 @@ struct Wave {
     int block = 0;
 };
 inline Wave g_wave;
+// wave_sim --ring-stats: what ActionRing::ensure did (PK_RING_COUNT in pk_device.hpp): [0] calls (= loop iterations of rollout_body), [1] Philox
+// passes, [2] lanes filled by them; counted by one lane per wave ([0], [1]) or by every filling lane ([2])
+inline std::atomic<uint64_t> ring_count[3];
+#define PK_RING_COUNT(k, n) pk_sim::ring_count[k].fetch_add((n), std::memory_order_relaxed)
 inline thread_local int t_lane = -1;
 inline void cfence() { std::atomic_signal_fence(std::memory_order_seq_cst); }
 inline int timeout_ms() {

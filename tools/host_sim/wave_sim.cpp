@@ -9,6 +9,9 @@
 //   wave_sim [family [N]] [--quick] [--steps K] [--deep]      families: rollout allin call tab allin_tab single step step_async
 //   --deep (step, step_async): the actions of the oracle's never-fold caller (oracle/rng_spec.py POLICY_DEEP, policy 14 of orc_pick_actions) on
 //   per-seat fractional stacks -- raises on every street, all-ins on different streets, multi-way river showdowns with side pots; 60 steps
+//   --ring-stats (the random-agent rollout families): three complete launches of --steps (default 1 024) steps on 192 tables -- three waves of 64
+//   live lanes -- with the headline's stacks and blinds (100, 2 / 1) and parking threshold (28); prints the Philox passes of ActionRing::ensure per
+//   loop iteration and the lanes each pass filled.  The step machine is deterministic: the counts are the device's.
 // One translation unit per family and seat group (-DPK_WS_PART=1..11; 100: the three instantiations of the suite's test), main with -DPK_WS_MAIN.
 #define HIP_INCLUDE_HIP_HIP_RUNTIME_H
 #include "../../pokerl_amd/csrc/pk_table_kernels.hpp"
@@ -19,7 +22,7 @@ extern "C" {
 
 enum Family : int { F_ROLLOUT, F_ALLIN, F_CALL, F_TAB, F_ALLIN_TAB, F_SINGLE, F_STEP, F_STEP_ASYNC };
 static const char *const kFamilyName[] = {"rollout", "allin", "call", "tab", "allin_tab", "single", "step", "step_async"};
-struct Opts { bool quick = false; int steps = 0; bool deep = false; };
+struct Opts { bool quick = false; int steps = 0; bool deep = false; bool ring = false; };
 struct Case { int family, n; int (*fn)(const Opts &); };
 std::vector<Case> &registry();
 #ifdef PK_WS_MAIN
@@ -275,6 +278,22 @@ static int run_case(const Opts &op) {
     long inflight = 0;
     const auto t0 = std::chrono::steady_clock::now();
     std::string ran;
+    if (op.ring) {
+        if constexpr (FAM == F_ROLLOUT || FAM == F_TAB) {
+            const int Kr = op.steps > 0 ? op.steps : 1024;
+            Sim<N, FAM> s(192, equal_cfg(N));
+            for (auto &c : pk_sim::ring_count) c.store(0);
+            for (int i = 0; i < 3 && !bad; ++i) {
+                s.launch_rollout(Kr, 28, PK_WAVE, 1);
+                s.orc_err = orc_rollout(s.o, Kr, Sim<N, FAM>::POLICY, 1, s.oc4);
+                bad = s.compare("ring-stats", true);
+            }
+            const double it = (double)pk_sim::ring_count[0].load(), ps = (double)pk_sim::ring_count[1].load(), ln = (double)pk_sim::ring_count[2].load();
+            printf("%s N=%d ring-stats: 3 launches of %d steps, 192 tables, park 28: %.0f loop iterations, %.0f Philox passes = %.3f per iteration, %.1f lanes filled per pass, "
+                   "%.3f wave-steps per iteration%s\n", kFamilyName[FAM], N, Kr, it, ps, ps / it, ps > 0 ? ln / ps : 0.0, 3.0 * Kr * 3 / it, bad ? ": MISMATCH" : ": wave-sim == oracle");
+        }
+        return bad != 0;
+    }
     if (op.deep) {
         if constexpr (stepf) {
             long river = 0;
@@ -363,6 +382,7 @@ int main(int argc, char **argv) {
         const std::string a = argv[i];
         if (a == "--quick") op.quick = true;
         else if (a == "--deep") op.deep = true;
+        else if (a == "--ring-stats") op.ring = true;
         else if (a == "--steps" && i + 1 < argc) op.steps = atoi(argv[++i]);
         else if (fam.empty()) fam = a;
         else n = atoi(argv[i]);

@@ -1035,6 +1035,48 @@ int pk_solve_river_d(int device, size_t m, const uint8_t *board_d /*[m][5]*/, co
 int pk_solve_river(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t n, const uint8_t *kind,
                    const uint8_t *child, const uint32_t *put, uint32_t pot, uint32_t iters, uint16_t *strategy, int64_t *value, int64_t *br,
                    uint8_t *status);
+
+/* ---- Turn solver: heads-up CFR+ on a FOUR-card board through the river card, exact integers (the numpy
+ * restatement: tests/turn_solver_spec.py).  The river solver's definition holds wherever nothing is said here; no result depends on the
+ * order of a sum, so the output is the same bytes whatever the grid.
+ * SPOT: board u8 [m][4], optional dead u64 [m], ranges u16 [m][2][1326].  P = 52 - 4 - |dead| pool cards <= 48: at most 1128 valid
+ * holdings.  status: PK_EQ_BAD_CARD, PK_EQ_DUP_CARD, PK_EQ_SMALL_POOL for P < 5 (two disjoint holdings and one river card).
+ * TREE: as the river solver's, n <= 128, plus kind 5 = CHANCE (the river card is dealt): exactly one child, put[0] == put[1] at it, no
+ * chance node below a chance node.  Nodes not below a chance node are TURN-LEVEL, the others RIVER-LEVEL.  A showdown must be river-level
+ * (an all-in call on the turn is a chance node whose child is a showdown); folds may be at either level.  D_t / D_r = the number of
+ * turn-level / river-level decision nodes, each counted in index order.  Refused as the river solver's trees are, and: n outside 1 .. 128;
+ * a node kind outside 0 .. 5; a chance node without exactly one child; a chance node below a chance node; a turn-level showdown; a chance
+ * node with put[0] != put[1].
+ * UNITS: ONE = 32768.  Root reach r_p[0][h] = w_p[h] << 1 (NOT << 4: see BOUNDS).  At a chance node, for each river card c of the pool, the
+ * child gets r_p[h] at the holdings without c and 0 at the others, for both players; everything below it under c is the river solver's
+ * pass on the board + c.  On the way up u_p[chance][h] = sum over c not in h of u_p[child under c][h]: a plain sum, never an average.  Two
+ * disjoint holdings always leave exactly P - 4 river cards, so every utility is in half-chips x opponent reach x (P - 4), and a TURN-LEVEL
+ * fold by f is scaled to agree: u_f[h] = -2 put[f] (P - 4) S_q(h), u_{1-f}[h] = 2 (pot + put[f]) (P - 4) S_q(h).
+ * ITERATIONS: the river solver's rule, regret and accumulator updates; a river-level decision node has its R and A PER RIVER CARD.  A
+ * best-response pass of p takes the maximum per river card below the chance node, then sums.
+ * OUTPUTS, each optional except status: strategy u16 [m][D_t][4][1326]; river_strategy u16 [m][D_r][52][4][1326], indexed by the river
+ * card's canonical index, 0 for cards outside the pool and for holdings with the card (551 616 bytes per river-level decision node and
+ * spot); value, br i64 [m][2][1326]; status u8 [m].  A refused spot gives all-zero outputs and disturbs no neighbour; a call with no spot
+ * writes nothing.
+ * BOUNDS: a reach < 2^17 (65535 << 1); a sum of reaches < 1128 * 2^17 < 2^27.2; a terminal's |u| <= 2 * 8191 * that < 2^41.2; at the
+ * chance node, 44 river cards: |u| < 2^46.7; |sum sigma u| < 2^61.7 (x ONE; the sigma of a node sum to ONE, so the sum is no larger than
+ * ONE times the largest |u|); a regret grows by at most 2 max|u| < 2^47.7 an iteration, so |R| < 2^59.7 after 4096; A <= sum t * reach <
+ * 2^23 * 2^17 = 2^40 < 2^41.  Everything fits int64_t; with << 4 the sigma u sum would not.  The packed prefix sums keep both players'
+ * sums of reaches below 2^32 each.
+ * STREAMS and work space: as pk_equity; the work space is the descriptors plus a slice per RESIDENT workgroup, sized for P = 48 whatever the
+ * spots: 423 936 bytes of per-card tables, 50 688 bytes per turn-level node and 866 048 bytes per river-level node; the grid is
+ * min(m, 256, 4 GiB / slice). */
+#define PK_TS_MAX_NODES 128
+int pk_solve_turn_d(int device, size_t m, const uint8_t *board_d /*[m][4]*/, const uint64_t *dead_d /*[m]; NULL: none*/,
+                    const uint16_t *ranges_d /*[m][2][1326]*/, uint32_t n, const uint8_t *kind /*[n], host*/, const uint8_t *child /*[n][4], host*/,
+                    const uint32_t *put /*[n][2], host*/, uint32_t pot, uint32_t iters, uint16_t *strategy_d /*[m][D_t][4][1326]*/,
+                    uint16_t *river_strategy_d /*[m][D_r][52][4][1326]*/, int64_t *value_d /*[m][2][1326]*/, int64_t *br_d, uint8_t *status_d,
+                    void *stream);
+int pk_solve_turn(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t n, const uint8_t *kind,
+                  const uint8_t *child, const uint32_t *put, uint32_t pot, uint32_t iters, uint16_t *strategy, uint16_t *river_strategy,
+                  int64_t *value, int64_t *br, uint8_t *status);
+/* The grid pk_solve_turn uses for m spots of a tree with nt turn-level and nr river-level nodes (no output depends on it). */
+unsigned pk_turn_grid(size_t m, uint32_t nt, uint32_t nr);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

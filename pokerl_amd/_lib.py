@@ -57,7 +57,7 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_preflop_count_d", "pk_preflop_count", "pk_preflop_matchups_d", "pk_preflop_matchups",
            "pk_equity_preflop_d", "pk_equity_preflop", "pk_table_equity_preflop_d", "pk_table_equity_preflop",
            "pk_equity_rvr_preflop_d", "pk_equity_rvr_preflop",
-           "pk_solve_river_d", "pk_solve_river"]
+           "pk_solve_river_d", "pk_solve_river", "pk_solve_turn_d", "pk_solve_turn", "pk_turn_grid"]
 
 
 class PokerlHipError(RuntimeError):
@@ -209,6 +209,9 @@ def lib():
     L.pk_equity_rvr_preflop.argtypes = [C.c_int, C.c_size_t] + [_vp] * 4
     L.pk_solve_river_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 3 + [C.c_uint32, C.c_uint32] + [_vp] * 5
     L.pk_solve_river.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 3 + [C.c_uint32, C.c_uint32] + [_vp] * 4
+    L.pk_solve_turn_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 3 + [C.c_uint32, C.c_uint32] + [_vp] * 6
+    L.pk_solve_turn.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 3 + [C.c_uint32, C.c_uint32] + [_vp] * 5
+    L.pk_turn_grid.argtypes = [C.c_size_t, C.c_uint32, C.c_uint32]
     for name in SYMBOLS:
         if name not in ("pk_last_error", "pk_build_info", "pk_snapshot_bytes"):
             getattr(L, name).restype = C.c_int

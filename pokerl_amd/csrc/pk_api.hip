@@ -23,6 +23,7 @@
 #include "pk_equity_range.hpp"
 #include "pk_equity_rvr.hpp"
 #include "pk_river_solver.hpp"
+#include "pk_turn_solver.hpp"
 #include "pk_equity_hist.hpp"
 #include "pk_equity_hist_hero.hpp"
 #include "pk_hist_cluster.hpp"
@@ -2962,6 +2963,95 @@ int pk_solve_river(int device, size_t m, const uint8_t *board, const uint64_t *d
     return eq_call_host(call, device, m, EQ_TAB_EVAL, g, rs_work_bytes(m, n, solve), [&](hipStream_t st, const uint32_t *tab, char *work) {
         return rs_launch(st, tab, RsSpots{g.at<uint8_t>(bo), g.at<uint64_t>(de), g.at<uint16_t>(ra)}, t, iters, m,
                          RsOut{g.at<uint16_t>(sg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
+    });
+}
+
+// ---- the turn solver (pokerl_hip.h "Turn solver"; kernels: pk_turn_solver.hip).  As the river solver: the tree is checked and packed on
+// the host and travels with the launch (TsTree fits the kernel-argument space beside the other arguments; the static_assert of
+// pk_turn_solver.hpp holds it there); the work space is the descriptors plus a slice per resident workgroup.
+// The tree check: the refusal's text, or NULL with `t` filled (nact, row, river and idx derived)
+static const char *ts_check_tree(uint32_t n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, uint32_t pot, TsTree &t) {
+    if (n < 1u || n > (uint32_t)TS_MAX_NODES) return ": n outside 1 .. 128";
+    t = TsTree{};
+    t.n = n; t.pot = pot;
+    uint32_t parents[TS_MAX_NODES] = {0}, rows[2] = {0, 0};
+    for (uint32_t v = 0; v < n; ++v) {
+        if (kind[v] > TS_CHANCE) return ": a node kind outside 0 .. 5";
+        if (v == 0 && kind[v] > RS_P1) return ": the root is not a decision node";
+        t.kind[v] = kind[v];
+        t.put[v][0] = put[v * 2]; t.put[v][1] = put[v * 2 + 1];
+        const uint32_t top = put[v * 2] > put[v * 2 + 1] ? put[v * 2] : put[v * 2 + 1];
+        if (pot > RS_MAX_CHIPS || top > RS_MAX_CHIPS || pot + top > RS_MAX_CHIPS) return ": pot + max put > 8191";
+        if (kind[v] == RS_SHOWDOWN && put[v * 2] != put[v * 2 + 1]) return ": a showdown has put[0] != put[1]";
+        if (kind[v] == TS_CHANCE && put[v * 2] != put[v * 2 + 1]) return ": a chance node has put[0] != put[1]";
+        const bool terminal = kind[v] > RS_P1 && kind[v] != TS_CHANCE;
+        uint32_t nact = 0;
+        bool ended = false;
+        for (int a = 0; a < 4; ++a) {
+            const uint32_t c = child[v * 4 + a];
+            t.child[v][a] = (uint8_t)c;
+            if (c == 0xFFu) { ended = true; continue; }
+            if (terminal) return ": a terminal has a child";
+            if (ended) return ": a node's children are not packed first";
+            if (c <= v || c >= n) return ": a child index is <= its parent or >= n";
+            ++parents[c];
+            ++nact;
+        }
+        if (kind[v] <= RS_P1 && nact == 0u) return ": a decision node has no child";
+        if (kind[v] == TS_CHANCE && nact != 1u) return ": a chance node does not have exactly one child";
+        t.nact[v] = (uint8_t)nact;
+    }
+    for (uint32_t v = 1; v < n; ++v)
+        if (parents[v] != 1u) return ": a non-root node does not have exactly one parent";
+    // the levels (every parent comes before its children), then what is counted per level
+    for (uint32_t v = 0; v < n; ++v) {
+        if (kind[v] == TS_CHANCE && t.river[v]) return ": a chance node below a chance node";
+        if (kind[v] == RS_SHOWDOWN && !t.river[v]) return ": a turn-level showdown";
+        for (uint32_t a = 0; a < t.nact[v]; ++a) t.river[t.child[v][a]] = (uint8_t)(t.river[v] || kind[v] == TS_CHANCE);
+        uint32_t &count = t.river[v] ? t.nr : t.nt;
+        t.idx[v] = (uint8_t)count++;
+        if (kind[v] <= RS_P1) t.row[v] = (uint8_t)rows[t.river[v]]++;
+    }
+    return nullptr;
+}
+static const char *ts_check(size_t m, bool pointers, uint32_t iters, uint32_t n, const uint8_t *kind, const uint8_t *child, const uint32_t *put,
+                            uint32_t pot, TsTree &t) {
+    if (const char *why = eq_bad_m(m)) return why;
+    if ((m && !pointers) || !kind || !child || !put) return ": NULL where a pointer is required (board, ranges, kind, child, put, status)";
+    if (iters < 1u || iters > (uint32_t)RS_MAX_ITERS) return ": iters outside 1 .. 4096";
+    return ts_check_tree(n, kind, child, put, pot, t);
+}
+
+unsigned pk_turn_grid(size_t m, uint32_t nt, uint32_t nr) { return ts_grid(m, nt, nr); }
+
+int pk_solve_turn_d(int device, size_t m, const uint8_t *board_d, const uint64_t *dead_d, const uint16_t *ranges_d, uint32_t n, const uint8_t *kind,
+                    const uint8_t *child, const uint32_t *put, uint32_t pot, uint32_t iters, uint16_t *strategy_d, uint16_t *river_strategy_d,
+                    int64_t *value_d, int64_t *br_d, uint8_t *status_d, void *stream) {
+    const char *call = "pk_solve_turn_d";
+    TsTree t;
+    EQ_REFUSE(g_fail, call, ts_check(m, board_d && ranges_d && status_d, iters, n, kind, child, put, pot, t));
+    const bool solve = strategy_d || river_strategy_d || value_d || br_d;
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, ts_work_bytes(m, t.nt, t.nr, solve), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return ts_launch(st, tab, TsSpots{board_d, dead_d, ranges_d}, t, iters, m, TsOut{strategy_d, river_strategy_d, value_d, br_d, status_d}, work);
+    });
+}
+
+int pk_solve_turn(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t n, const uint8_t *kind,
+                  const uint8_t *child, const uint32_t *put, uint32_t pot, uint32_t iters, uint16_t *strategy, uint16_t *river_strategy,
+                  int64_t *value, int64_t *br, uint8_t *status) {
+    const char *call = "pk_solve_turn";
+    TsTree t;
+    EQ_REFUSE(g_fail, call, ts_check(m, board && ranges && status, iters, n, kind, child, put, pot, t));
+    size_t Dt = 0, Dr = 0;
+    for (uint32_t v = 0; v < n; ++v) (t.river[v] ? Dr : Dt) += t.kind[v] <= RS_P1;
+    const bool solve = strategy || river_strategy || value || br;
+    Stage g;
+    const int bo = g.in(board, m * 4), de = g.in(dead, m * 8), ra = g.in(ranges, m * 2 * RS_HOLDINGS * 2);
+    const int sg = g.out(strategy, m * Dt * 4 * RS_HOLDINGS * 2), rg = g.out(river_strategy, m * Dr * 52 * 4 * RS_HOLDINGS * 2);
+    const int va = g.out(value, m * 2 * RS_HOLDINGS * 8), be = g.out(br, m * 2 * RS_HOLDINGS * 8), su = g.out(status, m);
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, ts_work_bytes(m, t.nt, t.nr, solve), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return ts_launch(st, tab, TsSpots{g.at<uint8_t>(bo), g.at<uint64_t>(de), g.at<uint16_t>(ra)}, t, iters, m,
+                         TsOut{g.at<uint16_t>(sg), g.at<uint16_t>(rg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
     });
 }
 

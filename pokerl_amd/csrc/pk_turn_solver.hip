@@ -1,0 +1,626 @@
+// pk_turn_solver.hip -- the turn subgame solver (include/pokerl_hip.h "Turn solver"): simultaneous CFR+ for two
+// players on a FOUR-card board, through the river card, in 64-bit integers whose sums do not depend on their order.  Two kernels:
+//   k_ts_prep       one lane per spot: checks the four board cards and the dead mask, writes the spot's descriptor and its status;
+//   k_turn_solve    k_river_solve's structure (pk_river_solver.hip) with a card loop around the river-level pass: a persistent grid of
+//                   512-thread workgroups, ONE SPOT PER WORKGROUP at a time.  Once per spot and river card the holdings of the pool without
+//                   that card are ranked on the five cards and sorted; what the card's passes need stays in the work space: per sorted
+//                   position its turn slot and the bounds [lb, ub) of its key, per turn slot its position.  TURN-LEVEL arrays are indexed
+//                   by the spot's fixed turn slot (the pair index of the holding's two pool slots), a lane owns slots tid, tid + 512,
+//                   tid + 1024; RIVER-LEVEL arrays by the card's sorted position, a lane owns positions tid, tid + 512, tid + 1024.
+//                   An iteration walks down the turn-level nodes, then for each river card -- one after the other, a barrier between
+//                   them -- gathers the reaches at every chance node through the card's table, walks the river-level nodes down,
+//                   evaluates their terminals as k_river_solve does (one 64-bit prefix sum for both players, card removal by the
+//                   holder's own positions), walks up with the regret update fused in, and the owner of each position adds its root
+//                   value into the chance node's value at its turn slot (positions map to distinct slots: no atomics); then it walks up
+//                   the turn-level nodes.  A turn-level fold needs no order: the total minus the two per-card sums plus the own reach.
+//                   Regrets and accumulators of river-level nodes are kept per card; values, reaches and probabilities of river-level
+//                   nodes are rewritten by every card's pass.  The final passes run in the same launch.
+// Ordinary vector stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_turn_solver_host.py reads the code object).
+#include <hip/hip_runtime.h>
+
+#include "pk_equity_common.hpp"
+#include "pk_solver_common.hpp"
+#include "pk_turn_solver.hpp"
+
+using namespace pk;
+
+#define TS_PREP_BLOCK 256
+
+struct TsPrepArgs {
+    TsSpots s;
+    uint8_t *status;
+    uint64_t *desc;
+    size_t m;
+};
+
+__global__ void __launch_bounds__(TS_PREP_BLOCK) k_ts_prep(TsPrepArgs a) {
+    const size_t i = (size_t)blockIdx.x * TS_PREP_BLOCK + threadIdx.x;
+    if (i >= a.m) return;
+    uint64_t *d = a.desc + i * (size_t)RS_DESC_WORDS;
+    uint32_t status = 0;
+    uint64_t dead = 0, known = 0;
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t c = a.s.board[i * 4 + j];
+        if (c >= 0x40u || (c & 15u) >= 13u) { status |= PK_EQ_BAD_CARD; continue; }
+        const uint64_t bit = 1ull << ((c & 15u) * 4u + (c >> 4));              // canonical index (cards.py:77)
+        status |= (dead & bit) ? (uint32_t)PK_EQ_DUP_CARD : 0u;
+        dead |= bit;
+        known |= 4ull << c;
+    }
+    const uint64_t out_of_play = a.s.dead ? a.s.dead[i] : 0ull;
+    if (out_of_play >> 52) status |= PK_EQ_BAD_CARD;
+    const uint64_t dd = out_of_play & 0x000FFFFFFFFFFFFFull;
+    if (dd & dead) status |= PK_EQ_DUP_CARD;
+    dead |= dd;
+    const uint32_t P = 52u - (uint32_t)__popcll(dead);
+    if (P < 5u) status |= PK_EQ_SMALL_POOL;                                    // two holdings that share no card, and a river card
+    d[0] = known;
+    d[1] = ~dead & 0x000FFFFFFFFFFFFFull;
+    d[2] = (uint64_t)(status ? 0u : 1u) | ((uint64_t)P << 56);
+    if (a.status) a.status[i] = (uint8_t)status;
+}
+
+namespace {
+
+// the arrays of one level of the tree as a pass sees them: [node of the level][stride], cnt entries of a node in use
+struct TsLevel {
+    int64_t *R, *A, *U0, *U1;
+    uint64_t *RR;
+    uint32_t *SG;
+    uint32_t stride, cnt;
+};
+
+}  // namespace
+
+// registers: one workgroup per CU is two waves per SIMD
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_turn_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, TsTree tree, TsSpots spots,
+                                                            TsOut out, char *ws, uint32_t iters, uint32_t m) {
+    __shared__ uint32_t T[EVAL7_TAB_WORDS];
+    __shared__ uint64_t slot[RS_SLOTS];               // key << 11 | turn slot, sorted once per spot and card; all ones = no holding.  Between
+                                                      // the sorts the same memory holds rs and posof, or a turn-level fold's reaches
+    __shared__ uint64_t pre[RS_PREFIX];               // pre[i]: both players' reach at sorted positions 0 .. i - 1; a turn-level fold: per-card sums
+    __shared__ uint64_t pool[64];                     // card j of the pool (canonical order) as its bit in the suit-lane layout
+    __shared__ uint32_t canon[64];                    // ... and its canonical index
+    __shared__ uint64_t wsum[RS_WAVES];
+    __shared__ TsTree tr;
+    uint64_t *const rs = slot;                                                   // [RS_SORTED] a terminal's reaches in sorted order
+    uint16_t *const posof = reinterpret_cast<uint16_t *>(slot + RS_SORTED);      // [TS_TURN] turn slot -> its sorted position under the card
+    static_assert(RS_SORTED * 8 + TS_TURN * 2 <= RS_SLOTS * 8 && TS_TURN <= RS_SLOTS && RS_PREFIX >= 64, "rs and posof, or a fold's reaches, fit the sort slots");
+    stage_eval7_tab<RS_BLOCK>(T, tab);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
+    for (uint32_t w = tid; w < (uint32_t)(sizeof(TsTree) / 4); w += RS_BLOCK)
+        reinterpret_cast<uint32_t *>(&tr)[PK_IDX(w, sizeof(TsTree) / 4, "tree")] = reinterpret_cast<const uint32_t *>(&tree)[w];
+    __syncthreads();
+    const uint32_t n = uniform(tr.n), pot = uniform(tr.pot), nt = uniform(tr.nt), nr = uniform(tr.nr);
+    uint32_t Dt = 0, Dr = 0;
+    for (uint32_t v = 0; v < n; ++v) {
+        const bool dec = tr.kind[PK_IDX(v, TS_MAX_NODES, "kind")] <= RS_P1, riv = tr.river[PK_IDX(v, TS_MAX_NODES, "river")] != 0;
+        Dt += (dec && !riv) ? 1u : 0u;
+        Dr += (dec && riv) ? 1u : 0u;
+    }
+    Dt = uniform(Dt); Dr = uniform(Dr);
+    // the workgroup's slice of the work space (pk_turn_solver.hpp): 64-bit arrays first
+    char *const base = ws + (size_t)blockIdx.x * ts_group_bytes(nt, nr);
+    const size_t tplane = (size_t)nt * TS_TURN, rplane = (size_t)nr * RS_SORTED;
+    int64_t *const Rt = reinterpret_cast<int64_t *>(base), *const At = Rt + tplane, *const U0t = At + tplane, *const U1t = U0t + tplane;
+    uint64_t *const RRt = reinterpret_cast<uint64_t *>(U1t + tplane);
+    int64_t *const Rr = reinterpret_cast<int64_t *>(RRt + tplane), *const Ar = Rr + rplane * TS_CARDS;         // [card][river node][position]
+    int64_t *const U0r = Ar + rplane * TS_CARDS, *const U1r = U0r + rplane;
+    uint64_t *const RRr = reinterpret_cast<uint64_t *>(U1r + rplane);
+    uint32_t *const SGt = reinterpret_cast<uint32_t *>(RRr + rplane), *const SGr = SGt + tplane;
+    uint32_t *const bounds = SGr + rplane;                                       // [card][position] lb | ub << 16
+    uint16_t *const slotof = reinterpret_cast<uint16_t *>(bounds + (size_t)TS_CARDS * RS_SORTED);              // [card][position] -> turn slot
+    uint16_t *const posofg = slotof + (size_t)TS_CARDS * RS_SORTED;             // [card][turn slot] -> position
+    const TsLevel Lt{Rt, At, U0t, U1t, RRt, SGt, (uint32_t)TS_TURN, 0u};
+    auto idx = [&](uint32_t node) -> uint32_t { return uniform((uint32_t)tr.idx[PK_IDX(node, TS_MAX_NODES, "idx")]); };
+    // where a node's entries begin in its level's arrays (wave-uniform: asked outside the code that depends on the lane), and entry i there
+    auto row_of = [&](const TsLevel &L, uint32_t node) -> size_t { return (size_t)idx(node) * L.stride; };
+    auto at = [&](const TsLevel &L, size_t row, uint32_t i) -> size_t { return row + PK_IDX(i, L.stride, "entry"); };
+    auto tab_at = [&](uint32_t c, uint32_t i) -> size_t { return (size_t)PK_IDX(c, TS_CARDS, "card") * RS_SORTED + PK_IDX(i, RS_SORTED, "position"); };
+    auto kids = [&](uint32_t node, uint32_t nact, uint32_t (&ch)[4]) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) ch[a] = (uint32_t)a < nact ? uniform((uint32_t)tr.child[PK_IDX(node, TS_MAX_NODES, "child")][a]) : 0u;
+    };
+    auto rows_of = [&](const TsLevel &L, const uint32_t (&ch)[4], uint32_t nact, size_t (&cr)[4]) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) cr[a] = (uint32_t)a < nact ? row_of(L, ch[a]) : 0;
+    };
+    auto kind_of = [&](uint32_t node) -> uint32_t { return uniform((uint32_t)tr.kind[PK_IDX(node, TS_MAX_NODES, "kind")]); };
+    auto is_river = [&](uint32_t node) -> bool { return uniform((uint32_t)tr.river[PK_IDX(node, TS_MAX_NODES, "river")]) != 0u; };
+
+    for (uint32_t spot = blockIdx.x; spot < m; spot += gridDim.x) {
+        __syncthreads();                              // (the table and the tree; the spot before: its pool is done with)
+        const uint64_t *d = desc + (size_t)spot * RS_DESC_WORDS;
+        const uint64_t known = uniform(d[0]), meta = uniform(d[2]);
+        const bool good = ((uint32_t)meta & 1u) != 0u;
+        const uint64_t avail = good ? uniform(d[1]) : 0ull;     // (a refused spot: no holding is valid, every output is 0)
+        const uint32_t P = (uint32_t)(meta >> 56);
+        // ---- zeros: every output at the holdings that are not in the pool, by the lanes of the fixed index h = tid + 512 j
+        for (uint32_t h = tid; h < (uint32_t)RS_HOLDINGS; h += RS_BLOCK) {
+            uint32_t ca = 0, cb = 1;
+            unpair(h, ca, cb);
+            if ((avail >> ca) & (avail >> cb) & 1ull) continue;
+            for (uint32_t p = 0; p < 2u; ++p) {
+                if (out.value) out.value[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
+                if (out.br) out.br[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
+            }
+            if (out.strategy)
+                for (uint32_t r = 0; r < Dt * 4u; ++r) out.strategy[((size_t)spot * Dt * 4 + r) * RS_HOLDINGS + h] = 0;
+        }
+        // ... and of river_strategy every (card, holding) no pass writes: the card or the holding is not in the pool, or the holding has the card
+        if (out.river_strategy)
+            for (uint32_t e = tid; e < 52u * (uint32_t)RS_HOLDINGS; e += RS_BLOCK) {
+                const uint32_t k = e / (uint32_t)RS_HOLDINGS, h = e - k * (uint32_t)RS_HOLDINGS;
+                uint32_t ca = 0, cb = 1;
+                unpair(h, ca, cb);
+                if (((avail >> ca) & (avail >> cb) & (avail >> k) & 1ull) && k != ca && k != cb) continue;
+                for (uint32_t r = 0; r < Dr; ++r)
+                    for (uint32_t a = 0; a < 4u; ++a) out.river_strategy[((((size_t)spot * Dr + r) * 52 + k) * 4 + a) * RS_HOLDINGS + h] = 0;
+            }
+        if (!good) continue;
+        fill_pool(pool, canon, avail, tid);
+        const uint32_t nT = tri(P), nh = tri(P - 1u), K = P - 4u;
+        uint32_t npad = 64;
+        while (npad < nT) npad <<= 1;                 // (the P - 1 holdings with the card are all ones: a pad slot always exists)
+        // ---- once per river card: rank, sort, and the card's tables
+        for (uint32_t cs = 0; cs < P; ++cs) {
+            __syncthreads();                          // (the pool; the card before: its slots have been read)
+            for (uint32_t ph = tid; ph < npad; ph += RS_BLOCK) {
+                uint64_t s = ~0ull;
+                if (ph < nT) {
+                    uint32_t ea, eb;
+                    unpair(ph, ea, eb);
+                    if (ea != cs && eb != cs) {
+                        const uint64_t bits = known | pool[PK_IDX(cs, 64, "pool")] | pool[PK_IDX(ea, 64, "pool")] | pool[PK_IDX(eb, 64, "pool")];
+                        s = ((uint64_t)order_key(eval7_tab_back(eval7_tab_front_bits(bits, T), T)) << 11) | ph;
+                    }
+                }
+                slot[PK_IDX(ph, RS_SLOTS, "slot")] = s;
+            }
+            __syncthreads();
+            for (uint32_t kk = 2; kk <= npad; kk <<= 1) {
+                for (uint32_t jj = kk >> 1; jj > 0; jj >>= 1) {
+                    for (uint32_t t = tid; t < (npad >> 1); t += RS_BLOCK) {
+                        const uint32_t lo = ((t & ~(jj - 1u)) << 1) | (t & (jj - 1u)), hi = lo | jj;
+                        const uint64_t a = slot[PK_IDX(lo, RS_SLOTS, "slot")], b = slot[PK_IDX(hi, RS_SLOTS, "slot")];
+                        const bool up = (lo & kk) == 0u;
+                        if ((a > b) == up) { slot[PK_IDX(lo, RS_SLOTS, "slot")] = b; slot[PK_IDX(hi, RS_SLOTS, "slot")] = a; }
+                    }
+                    __syncthreads();
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                if (i >= nh) continue;
+                const uint64_t s = slot[PK_IDX(i, RS_SLOTS, "slot")];
+                const uint32_t kh = (uint32_t)(s >> 11), ph = (uint32_t)s & 2047u;
+                uint32_t l = 0, u = 0;                                          // sorted positions with a key < kh, <= kh
+                for (uint32_t step = npad >> 1; step > 0; step >>= 1) {
+                    const uint32_t kl = (uint32_t)(slot[PK_IDX(l + step - 1u, RS_SLOTS, "slot")] >> 11);
+                    const uint32_t ku = (uint32_t)(slot[PK_IDX(u + step - 1u, RS_SLOTS, "slot")] >> 11);
+                    l += kl < kh ? step : 0u;
+                    u += ku <= kh ? step : 0u;
+                }
+                slotof[tab_at(cs, i)] = (uint16_t)ph;
+                bounds[tab_at(cs, i)] = l | (u << 16);
+                posofg[(size_t)cs * TS_TURN + PK_IDX(ph, TS_TURN, "turn slot")] = (uint16_t)i;
+            }
+        }
+        // ---- the turn slots this lane owns: their fixed indices
+        uint32_t gh[RS_PER_LANE];
+        auto fixed = [&](uint32_t s) -> uint32_t {
+            uint32_t a, b;
+            unpair(s, a, b);
+            return tri(canon[PK_IDX(b, 64, "canon")]) + canon[PK_IDX(a, 64, "canon")];
+        };
+#pragma unroll
+        for (int j = 0; j < RS_PER_LANE; ++j) {
+            const uint32_t s = tid + (uint32_t)j * RS_BLOCK;
+            gh[j] = s < nT ? fixed(s) : 0u;
+        }
+        auto river_level = [&](uint32_t cs) -> TsLevel {
+            const size_t o = (size_t)PK_IDX(cs, TS_CARDS, "card") * rplane;
+            return TsLevel{Rr + o, Ar + o, U0r, U1r, RRr, SGr, (uint32_t)RS_SORTED, nh};
+        };
+        TsLevel Lturn = Lt;
+        Lturn.cnt = nT;
+        // ---- the root's reaches; regrets and accumulators start at 0
+        const uint16_t *w0 = spots.ranges + (size_t)spot * 2 * RS_HOLDINGS, *w1 = w0 + RS_HOLDINGS;
+#pragma unroll
+        for (int j = 0; j < RS_PER_LANE; ++j) {
+            const uint32_t s = tid + (uint32_t)j * RS_BLOCK;
+            if (s < nT) {
+                RRt[at(Lturn, 0, s)] = ((uint64_t)w0[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 1) | ((uint64_t)w1[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 33);
+                for (uint32_t v = 0; v < nt; ++v) { Rt[(size_t)v * TS_TURN + s] = 0; At[(size_t)v * TS_TURN + s] = 0; }
+            }
+            if (s < nh)
+                for (uint32_t cs = 0; cs < P; ++cs)
+                    for (uint32_t v = 0; v < nr; ++v) { Rr[((size_t)cs * nr + v) * RS_SORTED + s] = 0; Ar[((size_t)cs * nr + v) * RS_SORTED + s] = 0; }
+        }
+        __syncthreads();                              // (the last card's slots have been read: their memory becomes rs and posof)
+
+        // A river-level terminal under card cs (every lane of the workgroup comes here): k_river_solve's, the lane's positions from the tables
+        auto terminal = [&](const TsLevel &L, uint32_t cs, uint32_t node, uint32_t kind) {
+            const size_t nrow = row_of(L, node);
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                if (i < nh) rs[PK_IDX(i, RS_SORTED, "rs")] = L.RR[at(L, nrow, i)];
+            }
+            __syncthreads();
+            uint64_t v[RS_PER_LANE], mine = 0;
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid * RS_PER_LANE + (uint32_t)j;
+                v[j] = i < nh ? rs[PK_IDX(i, RS_SORTED, "rs")] : 0ull;
+                mine += v[j];
+            }
+            uint64_t inc = mine;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint64_t y = __shfl_up(inc, off);
+                inc += lane >= (uint32_t)off ? y : 0ull;
+            }
+            if (lane == 63u) wsum[PK_IDX(wave, RS_WAVES, "wsum")] = inc;
+            __syncthreads();
+            uint64_t run = inc - mine, all = 0;
+#pragma unroll
+            for (int w = 0; w < RS_WAVES; ++w) {
+                const uint64_t s = wsum[PK_IDX(w, RS_WAVES, "wsum")];
+                run += (uint32_t)w < wave ? s : 0ull;
+                all += s;
+            }
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid * RS_PER_LANE + (uint32_t)j;
+                if (i < (uint32_t)RS_PREFIX) pre[PK_IDX(i, RS_PREFIX, "pre")] = run;
+                run += v[j];
+            }
+            __syncthreads();
+            const uint32_t f = kind - RS_FOLD0, pf = tr.put[PK_IDX(node, TS_MAX_NODES, "put")][f & 1u], c = tr.put[PK_IDX(node, TS_MAX_NODES, "put")][0];
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                if (i >= nh) continue;
+                const uint32_t hph = slotof[tab_at(cs, i)], lu = bounds[tab_at(cs, i)], lb = lu & 0xFFFFu, ub = lu >> 16;
+                uint32_t ha, hb;
+                unpair(hph, ha, hb);
+                const uint64_t below0 = pre[PK_IDX(lb, RS_PREFIX, "pre")], self = rs[PK_IDX(i, RS_SORTED, "rs")];
+                uint64_t below = below0, equal = pre[PK_IDX(ub, RS_PREFIX, "pre")] - below0 - self, conf = self;
+                // card removal: every holding {ha, x}, {hb, x} without the river card, by its own sorted position
+                const uint32_t ta = tri(ha), tb = tri(hb);
+#pragma unroll 4
+                for (uint32_t x = 0; x < P; ++x) {
+                    const bool own = x == ha || x == hb || x == cs;
+                    const uint32_t tx = tri(x);
+                    const uint32_t i0 = own ? hph : pair(ha, ta, x, tx), i1 = own ? hph : pair(hb, tb, x, tx);
+                    const uint32_t p0 = posof[PK_IDX(i0, TS_TURN, "posof")], p1 = posof[PK_IDX(i1, TS_TURN, "posof")];
+                    const uint64_t r0 = own ? 0ull : rs[PK_IDX(p0, RS_SORTED, "rs")], r1 = own ? 0ull : rs[PK_IDX(p1, RS_SORTED, "rs")];
+                    conf += r0 + r1;
+                    below -= (p0 < lb ? r0 : 0ull) + (p1 < lb ? r1 : 0ull);
+                    equal -= ((p0 >= lb && p0 < ub) ? r0 : 0ull) + ((p1 >= lb && p1 < ub) ? r1 : 0ull);
+                }
+                const uint64_t S = all - conf, above = S - below - equal;
+                int64_t u0, u1;                       // player 0 meets player 1's reach (the high halves), player 1 the low ones
+                if (kind == RS_SHOWDOWN) {
+                    u0 = (int64_t)(2u * (pot + c)) * (int64_t)(below >> 32) + (int64_t)pot * (int64_t)(equal >> 32) - (int64_t)(2u * c) * (int64_t)(above >> 32);
+                    u1 = (int64_t)(2u * (pot + c)) * (int64_t)(uint32_t)below + (int64_t)pot * (int64_t)(uint32_t)equal - (int64_t)(2u * c) * (int64_t)(uint32_t)above;
+                } else {
+                    const int64_t lose = -(int64_t)(2u * pf), gain = (int64_t)(2u * (pot + pf));
+                    u0 = (f == 0u ? lose : gain) * (int64_t)(S >> 32);
+                    u1 = (f == 1u ? lose : gain) * (int64_t)(uint32_t)S;
+                }
+                L.U0[at(L, nrow, i)] = u0;
+                L.U1[at(L, nrow, i)] = u1;
+            }
+            __syncthreads();                          // (rs, pre and the totals are rewritten by the next terminal)
+        };
+
+        // A turn-level fold (every lane comes here): S_q(h) = the total - the sums of h's two cards + h's own entry, times the P - 4 river cards
+        auto turn_fold = [&](uint32_t node, uint32_t kind) {
+            const size_t nrow = row_of(Lturn, node);
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t s = tid + (uint32_t)j * RS_BLOCK;
+                if (s < nT) slot[PK_IDX(s, RS_SLOTS, "slot")] = RRt[at(Lturn, nrow, s)];
+            }
+            __syncthreads();
+            if (tid < P) {
+                uint64_t sum = 0;
+                const uint32_t tt = tri(tid);
+                for (uint32_t x = 0; x < P; ++x) sum += x == tid ? 0ull : slot[PK_IDX(pair(tid, tt, x, tri(x)), RS_SLOTS, "slot")];
+                pre[PK_IDX(tid, RS_PREFIX, "pre")] = sum;
+            }
+            __syncthreads();
+            uint64_t twice = 0;
+            for (uint32_t x = 0; x < P; ++x) twice += pre[PK_IDX(x, RS_PREFIX, "pre")];
+            const uint64_t all = ((uint64_t)((uint32_t)twice >> 1)) | ((twice >> 33) << 32);       // (each half is even)
+            const uint32_t f = kind - RS_FOLD0, pf = tr.put[PK_IDX(node, TS_MAX_NODES, "put")][f & 1u];
+            const int64_t lose = -(int64_t)(2u * pf * K), gain = (int64_t)(2u * (pot + pf) * K);
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t s = tid + (uint32_t)j * RS_BLOCK;
+                if (s >= nT) continue;
+                uint32_t a, b;
+                unpair(s, a, b);
+                const uint64_t S = all - pre[PK_IDX(a, RS_PREFIX, "pre")] - pre[PK_IDX(b, RS_PREFIX, "pre")] + slot[PK_IDX(s, RS_SLOTS, "slot")];
+                U0t[at(Lturn, nrow, s)] = (f == 0u ? lose : gain) * (int64_t)(S >> 32);
+                U1t[at(Lturn, nrow, s)] = (f == 1u ? lose : gain) * (int64_t)(uint32_t)S;
+            }
+            __syncthreads();
+        };
+
+        // A decision node on the way down, at either level.  FROM_R: the probabilities come from the regrets and are kept in SG;
+        // otherwise SG is played as it stands.
+        auto decide_down = [&](const TsLevel &L, uint32_t node, uint32_t kind, bool from_r) {
+            const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, TS_MAX_NODES, "nact")]);
+            uint32_t ch[4];
+            kids(node, nact, ch);
+            size_t cr[4];
+            rows_of(L, ch, nact, cr);
+            const size_t nrow = row_of(L, node);
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                if (i >= L.cnt) continue;
+                uint32_t sig[4];
+                if (from_r) {
+                    int64_t X[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) X[a] = (uint32_t)a < nact ? L.R[at(L, cr[a], i)] : 0;
+                    rs_sigma(X, nact, sig);
+                }
+                const uint64_t rr = L.RR[at(L, nrow, i)];
+                const uint32_t r0 = (uint32_t)rr, r1 = (uint32_t)(rr >> 32);
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    if ((uint32_t)a >= nact) continue;
+                    const size_t e = at(L, cr[a], i);
+                    if (from_r) L.SG[e] = sig[a]; else sig[a] = L.SG[e];
+                    const uint32_t mine = (uint32_t)(((uint64_t)(kind == RS_P0 ? r0 : r1) * sig[a]) >> 15);
+                    L.RR[e] = kind == RS_P0 ? ((uint64_t)mine | ((uint64_t)r1 << 32)) : ((uint64_t)r0 | ((uint64_t)mine << 32));
+                }
+            }
+        };
+        // ... and on the way up of iteration t, with the regret and accumulator updates
+        auto decide_up = [&](const TsLevel &L, uint32_t node, uint32_t kind, uint32_t t) {
+            const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, TS_MAX_NODES, "nact")]);
+            int64_t *const Up = kind == RS_P0 ? L.U0 : L.U1, *const Uq = kind == RS_P0 ? L.U1 : L.U0;
+            uint32_t ch[4];
+            kids(node, nact, ch);
+            size_t cr[4];
+            rows_of(L, ch, nact, cr);
+            const size_t nrow = row_of(L, node);
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                if (i >= L.cnt) continue;
+                int64_t up[4], acc = 0, uq = 0;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    up[a] = 0;
+                    if ((uint32_t)a >= nact) continue;
+                    const size_t e = at(L, cr[a], i);
+                    up[a] = Up[e];
+                    acc += (int64_t)L.SG[e] * up[a];
+                    uq += Uq[e];
+                }
+                const int64_t un = acc >> 15;         // (the sum first, the floor once)
+                Up[at(L, nrow, i)] = un;
+                Uq[at(L, nrow, i)] = uq;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    if ((uint32_t)a >= nact) continue;
+                    const size_t e = at(L, cr[a], i);
+                    const int64_t r = L.R[e] + up[a] - un;
+                    L.R[e] = r > 0 ? r : 0;
+                    const uint64_t rr = L.RR[e];
+                    L.A[e] += (int64_t)((uint64_t)t * (uint64_t)(kind == RS_P0 ? (uint32_t)rr : (uint32_t)(rr >> 32)));
+                }
+            }
+        };
+        // ... of the last pass: beside each player's value, the value of the player who plays the maximum at its own nodes (B0 / B1, in
+        // the memory of R / A; a terminal's is its value)
+        auto decide_up_best = [&](const TsLevel &L, uint32_t node, uint32_t kind) {
+            const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, TS_MAX_NODES, "nact")]);
+            int64_t *const Up = kind == RS_P0 ? L.U0 : L.U1, *const Uq = kind == RS_P0 ? L.U1 : L.U0;
+            int64_t *const Bp = kind == RS_P0 ? L.R : L.A, *const Bq = kind == RS_P0 ? L.A : L.R;
+            uint32_t ch[4];
+            bool leaf[4];
+            kids(node, nact, ch);
+            size_t cr[4];
+            rows_of(L, ch, nact, cr);
+            const size_t nrow = row_of(L, node);
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const uint32_t k = kind_of(ch[a]);
+                leaf[a] = k > RS_P1 && k != (uint32_t)TS_CHANCE;
+            }
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                if (i >= L.cnt) continue;
+                int64_t acc = 0, uq = 0, bp = 0, bq = 0;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    if ((uint32_t)a >= nact) continue;
+                    const size_t e = at(L, cr[a], i);
+                    const int64_t up = Up[e], uqa = Uq[e], bpa = leaf[a] ? up : Bp[e], bqa = leaf[a] ? uqa : Bq[e];
+                    acc += (int64_t)L.SG[e] * up;
+                    uq += uqa;
+                    bp = (a == 0 || bpa > bp) ? bpa : bp;
+                    bq += bqa;
+                }
+                Up[at(L, nrow, i)] = acc >> 15;
+                Uq[at(L, nrow, i)] = uq;
+                Bp[at(L, nrow, i)] = bp;
+                Bq[at(L, nrow, i)] = bq;
+            }
+        };
+        // The turn-level walk down: reaches, the folds' values; a chance node's sums start at 0 (BEST: those of the best responses too)
+        auto turn_down = [&](bool from_r, bool best) {
+            for (uint32_t node = 0; node < n; ++node) {
+                if (is_river(node)) continue;
+                const uint32_t kind = kind_of(node);
+                if (kind <= RS_P1) { decide_down(Lturn, node, kind, from_r); continue; }
+                if (kind != (uint32_t)TS_CHANCE) { turn_fold(node, kind); continue; }
+                const size_t nrow = row_of(Lturn, node);
+#pragma unroll
+                for (int j = 0; j < RS_PER_LANE; ++j) {
+                    const uint32_t s = tid + (uint32_t)j * RS_BLOCK;
+                    if (s >= nT) continue;
+                    U0t[at(Lturn, nrow, s)] = 0; U1t[at(Lturn, nrow, s)] = 0;
+                    if (best) { Rt[at(Lturn, nrow, s)] = 0; At[at(Lturn, nrow, s)] = 0; }
+                }
+            }
+        };
+        // A card's pass begins: its positions into LDS (the barrier also orders the card before: its sums into the chance nodes)
+        auto card_begin = [&](uint32_t cs) {
+            for (uint32_t s = tid; s < nT; s += RS_BLOCK) posof[PK_IDX(s, TS_TURN, "posof")] = posofg[(size_t)cs * TS_TURN + s];
+            __syncthreads();
+        };
+        // The river-level walk down under card cs: a chance node hands its reaches to its child through the card's table
+        auto river_down = [&](const TsLevel &L, uint32_t cs, bool from_r) {
+            for (uint32_t node = 0; node < n; ++node) {
+                const uint32_t kind = kind_of(node);
+                if (kind == (uint32_t)TS_CHANCE) {
+                    const uint32_t ch = uniform((uint32_t)tr.child[PK_IDX(node, TS_MAX_NODES, "child")][0]);
+                    const size_t nrow = row_of(Lturn, node), crow = row_of(L, ch);
+#pragma unroll
+                    for (int j = 0; j < RS_PER_LANE; ++j) {
+                        const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                        if (i < nh) L.RR[at(L, crow, i)] = RRt[at(Lturn, nrow, slotof[tab_at(cs, i)])];
+                    }
+                    continue;
+                }
+                if (!is_river(node)) continue;
+                if (kind <= RS_P1) decide_down(L, node, kind, from_r);
+                else terminal(L, cs, node, kind);
+            }
+        };
+
+        // ---- the iterations
+        for (uint32_t t = 1; t <= iters; ++t) {
+            turn_down(true, false);
+            for (uint32_t cs = 0; cs < P; ++cs) {
+                const TsLevel L = river_level(cs);
+                card_begin(cs);
+                river_down(L, cs, true);
+                for (uint32_t node = n; node-- > 0u;) {
+                    const uint32_t kind = kind_of(node);
+                    if (kind == (uint32_t)TS_CHANCE) {
+                        const uint32_t ch = uniform((uint32_t)tr.child[PK_IDX(node, TS_MAX_NODES, "child")][0]);
+                        const size_t nrow = row_of(Lturn, node), crow = row_of(L, ch);
+#pragma unroll
+                        for (int j = 0; j < RS_PER_LANE; ++j) {
+                            const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                            if (i >= nh) continue;
+                            const size_t e = at(Lturn, nrow, slotof[tab_at(cs, i)]);
+                            U0t[e] += L.U0[at(L, crow, i)];
+                            U1t[e] += L.U1[at(L, crow, i)];
+                        }
+                    } else if (is_river(node) && kind <= RS_P1) decide_up(L, node, kind, t);
+                }
+            }
+            __syncthreads();                          // (the last card's sums)
+            for (uint32_t node = n; node-- > 0u;) {
+                const uint32_t kind = kind_of(node);
+                if (!is_river(node) && kind <= RS_P1) decide_up(Lturn, node, kind, t);
+            }
+        }
+
+        // ---- the average strategy: the rule applied to the accumulators; it stays in SG for the last walk
+        auto average = [&](const TsLevel &L, uint32_t node, uint32_t cs, bool river) {
+            const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, TS_MAX_NODES, "nact")]), row = uniform((uint32_t)tr.row[PK_IDX(node, TS_MAX_NODES, "row")]);
+            uint32_t ch[4];
+            kids(node, nact, ch);
+            size_t cr[4];
+            rows_of(L, ch, nact, cr);
+            const size_t nrow = row_of(L, node);
+#pragma unroll
+            for (int j = 0; j < RS_PER_LANE; ++j) {
+                const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                if (i >= L.cnt) continue;
+                int64_t X[4];
+                uint32_t sig[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) X[a] = (uint32_t)a < nact ? L.A[at(L, cr[a], i)] : 0;
+                rs_sigma(X, nact, sig);
+                uint16_t *o = nullptr;
+                if (river) {
+                    if (out.river_strategy)
+                        o = out.river_strategy + ((((size_t)spot * Dr + row) * 52 + canon[PK_IDX(cs, 64, "canon")]) * 4) * RS_HOLDINGS + fixed(slotof[tab_at(cs, i)]);
+                } else if (out.strategy) o = out.strategy + (((size_t)spot * Dt + row) * 4) * RS_HOLDINGS + gh[j];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    if ((uint32_t)a < nact) L.SG[at(L, cr[a], i)] = sig[a];
+                    if (o) o[(size_t)a * RS_HOLDINGS] = (uint16_t)sig[a];
+                }
+            }
+        };
+        for (uint32_t node = 0; node < n; ++node)
+            if (!is_river(node) && kind_of(node) <= RS_P1) average(Lturn, node, 0u, false);
+        const bool values = out.value || out.br;
+        if (!(values || out.river_strategy)) continue;
+        // ---- its values and the best responses against it: one walk down serves all three, the walk up carries the maximum beside the value
+        if (values) turn_down(false, true);
+        for (uint32_t cs = 0; cs < P; ++cs) {
+            const TsLevel L = river_level(cs);
+            for (uint32_t node = 0; node < n; ++node)
+                if (is_river(node) && kind_of(node) <= RS_P1) average(L, node, cs, true);
+            if (!values) continue;
+            card_begin(cs);
+            river_down(L, cs, false);
+            for (uint32_t node = n; node-- > 0u;) {
+                const uint32_t kind = kind_of(node);
+                if (kind == (uint32_t)TS_CHANCE) {
+                    const uint32_t ch = uniform((uint32_t)tr.child[PK_IDX(node, TS_MAX_NODES, "child")][0]);
+                    const size_t nrow = row_of(Lturn, node), crow = row_of(L, ch);
+                    const bool leaf = kind_of(ch) > RS_P1;
+#pragma unroll
+                    for (int j = 0; j < RS_PER_LANE; ++j) {
+                        const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                        if (i >= nh) continue;
+                        const size_t e = at(Lturn, nrow, slotof[tab_at(cs, i)]), g = at(L, crow, i);
+                        const int64_t u0 = L.U0[g], u1 = L.U1[g];
+                        U0t[e] += u0;
+                        U1t[e] += u1;
+                        Rt[e] += leaf ? u0 : L.R[g];
+                        At[e] += leaf ? u1 : L.A[g];
+                    }
+                } else if (is_river(node) && kind <= RS_P1) decide_up_best(L, node, kind);
+            }
+        }
+        if (!values) continue;
+        __syncthreads();                              // (the last card's sums)
+        for (uint32_t node = n; node-- > 0u;) {
+            const uint32_t kind = kind_of(node);
+            if (!is_river(node) && kind <= RS_P1) decide_up_best(Lturn, node, kind);
+        }
+#pragma unroll
+        for (int j = 0; j < RS_PER_LANE; ++j) {
+            const uint32_t s = tid + (uint32_t)j * RS_BLOCK;
+            if (s >= nT) continue;
+            const size_t o = (size_t)spot * 2 * RS_HOLDINGS + gh[j];
+            if (out.value) { out.value[o] = U0t[at(Lturn, 0, s)]; out.value[o + RS_HOLDINGS] = U1t[at(Lturn, 0, s)]; }
+            if (out.br) { out.br[o] = Rt[at(Lturn, 0, s)]; out.br[o + RS_HOLDINGS] = At[at(Lturn, 0, s)]; }
+        }
+    }
+}
+
+namespace pk {
+
+hipError_t ts_launch(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTree &tree, uint32_t iters, size_t m, const TsOut &out,
+                     char *work) {
+    if (m == 0) return hipSuccess;
+    const TsPrepArgs a{spots, out.status, (uint64_t *)work, m};
+    hipLaunchKernelGGL(k_ts_prep, dim3((unsigned)((m + TS_PREP_BLOCK - 1) / TS_PREP_BLOCK)), dim3(TS_PREP_BLOCK), 0, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !(out.strategy || out.river_strategy || out.value || out.br)) return e;   // (status alone: the preparation kernel has written it)
+    hipLaunchKernelGGL(k_turn_solve, dim3(ts_grid(m, tree.nt, tree.nr)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, tree, spots, out,
+                       work + rs_desc_bytes(m), iters, (uint32_t)m);
+    return hipGetLastError();
+}
+
+}  // namespace pk

@@ -1,0 +1,67 @@
+// pk_turn_solver.hpp -- the turn subgame solver: heads-up CFR+ on a four-card board through the river card, one subgame per workgroup, in
+// integers (include/pokerl_hip.h "Turn solver"): what the host entry points (pk_api.hip) and the kernels
+// (pk_turn_solver.hip) share.  The table kernels do not include it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "pk_river_solver.hpp"
+
+namespace pk {
+
+constexpr int TS_MAX_NODES = PK_TS_MAX_NODES;
+constexpr int TS_CARDS = 48;                             // river cards of the largest pool
+constexpr int TS_TURN_HOLDINGS = 1128;                   // C(48, 2): holdings of the largest pool on a four-card board
+constexpr int TS_TURN = 1152;                            // ... padded: slots per turn-level node (NOT RS_SORTED: 1088 < 1128)
+constexpr size_t TS_WORK_MAX = (size_t)4 << 30;          // the ceiling of the per-workgroup slices together (not measured: DESIGN.md 3.13)
+static_assert(RS_BLOCK * RS_PER_LANE >= TS_TURN_HOLDINGS && TS_TURN >= TS_TURN_HOLDINGS && TS_TURN % 64 == 0 && TS_TURN_HOLDINGS < 2048, "a lane owns at most RS_PER_LANE slots");
+
+enum { TS_CHANCE = 5 };
+
+// The tree as the kernel takes it (by value).  Derived by the host check: nact, row (a decision node's row of `strategy` or of
+// `river_strategy`), river (1 below a chance node) and idx (the node's number among the nodes of its level: where its arrays are).
+struct TsTree {
+    uint32_t n, pot, nt, nr;                             // nodes, chips in the middle, turn-level and river-level nodes (nt + nr = n)
+    uint32_t put[TS_MAX_NODES][2];
+    uint8_t kind[TS_MAX_NODES], nact[TS_MAX_NODES], row[TS_MAX_NODES], river[TS_MAX_NODES], idx[TS_MAX_NODES];
+    uint8_t child[TS_MAX_NODES][4];
+};
+static_assert(sizeof(TsTree) % 4 == 0 && sizeof(TsTree) <= 3072, "copied into LDS as 32-bit words; travels as a kernel argument (4 KB with the rest)");
+
+struct TsSpots {
+    const uint8_t *board;      // [m][4]
+    const uint64_t *dead;      // [m], NULL: none
+    const uint16_t *ranges;    // [m][2][1326]
+};
+struct TsOut {                 // any may be NULL
+    uint16_t *strategy;        // [m][D_t][4][1326]
+    uint16_t *river_strategy;  // [m][D_r][52][4][1326]
+    int64_t *value, *br;       // [m][2][1326]
+    uint8_t *status;           // [m]
+};
+
+// Work space: the m descriptors, then -- sized by the grid, never by m, and for the largest pool -- per workgroup:
+//   the 48 river cards' tables: per sorted position its turn slot (u16) and the bounds of its key (u16, u16), per turn slot its position (u16);
+//   per turn-level node and slot: regret, accumulator, both values, both reaches (one word), the edge's probability;
+//   per river-level node, card and position: regret and accumulator -- all that outlives a card's pass;
+//   per river-level node and position: both values, both reaches, the probability -- rewritten by every card's pass.
+constexpr size_t TS_TABLE_BYTES = (size_t)TS_CARDS * (RS_SORTED * 6 + TS_TURN * 2);
+constexpr size_t TS_TURN_NODE_BYTES = (size_t)TS_TURN * (5 * 8 + 4);
+constexpr size_t TS_RIVER_NODE_BYTES = (size_t)RS_SORTED * ((size_t)TS_CARDS * 16 + 3 * 8 + 4);
+constexpr size_t ts_group_bytes(uint32_t nt, uint32_t nr) { return TS_TABLE_BYTES + nt * TS_TURN_NODE_BYTES + nr * TS_RIVER_NODE_BYTES; }
+constexpr unsigned ts_grid(size_t m, uint32_t nt, uint32_t nr) {
+    const size_t fit = TS_WORK_MAX / ts_group_bytes(nt, nr), cap = fit < (size_t)RS_GRID_MAX ? fit : (size_t)RS_GRID_MAX;
+    return (unsigned)(m < cap ? m : cap);
+}
+constexpr size_t ts_work_bytes(size_t m, uint32_t nt, uint32_t nr, bool solve) {
+    return rs_desc_bytes(m) + (solve ? (size_t)ts_grid(m, nt, nr) * ts_group_bytes(nt, nr) : 0);
+}
+static_assert(ts_group_bytes(1, TS_MAX_NODES - 1) * 16 < TS_WORK_MAX, "the largest tree still gets a grid");
+
+// Queues the whole call on `stream`: descriptors + status (one lane per spot), then -- where an output beside status is wanted -- the
+// persistent kernel.  tab: the evaluator table (eval7_table).  The tree has passed the host check (pk_api.hip ts_check_tree).
+hipError_t ts_launch(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTree &tree, uint32_t iters, size_t m, const TsOut &out,
+                     char *work);
+
+}  // namespace pk

@@ -1,6 +1,8 @@
 """The river subgame solver (pk_solve_river; the definition: include/pokerl_hip.h "River solver"): heads-up CFR+
 over a caller-supplied betting tree, one subgame per workgroup on the device, in integers -- the same call gives the same bytes whatever
-the grid.  river_tree builds a tree on the host; solve_river / solve_river_batch / solve_river_d run it."""
+the grid.  river_tree builds a tree on the host; solve_river / solve_river_batch / solve_river_d run it.
+The turn solver (pk_solve_turn; "Turn solver") is the same one street earlier, on a four-card board with the river
+card as a chance node: turn_tree, solve_turn / solve_turn_batch / solve_turn_d, at the end of this module."""
 import math
 
 import numpy as np
@@ -46,6 +48,64 @@ class RiverTree:
         return "RiverTree(n=%d, decisions=%d, pot=%d)" % (self.n, len(self.decision_nodes), self.pot)
 
 
+class _Builder:
+    """The node lists of a tree under construction and the betting rule of one street (river_tree's docstring)."""
+
+    def __init__(self, pot, stack, limit):
+        self.pot, self.stack, self.limit = pot, stack, limit
+        self.kind, self.child, self.put, self.actions = [], [], [], []
+
+    def new(self, k, p0, p1, parent, text):
+        self.kind.append(k); self.child.append([NO_CHILD] * 4); self.put.append([p0, p1]); self.actions.append(None if parent is None else (parent, text))
+        if len(self.kind) > self.limit:
+            raise ValueError("the tree has more than %d nodes: fewer bet sizes or raises" % self.limit)
+        return len(self.kind) - 1
+
+    def sizes(self, p, puts, room, bet_fractions):
+        to_call = max(puts) - puts[p]
+        after = self.pot + puts[0] + puts[1] + to_call
+        left = self.stack - puts[p] - to_call
+        out = []
+        for f in bet_fractions:
+            amount = min(max(1, int(math.floor(f * after))), left)
+            if amount > 0 and amount not in out:
+                out.append(amount)
+        return out[:room]
+
+    def betting_round(self, root, bet_fractions, max_raises, end):
+        """One street from the decision node `root` (player 0 to act, nothing to call); end(p0, p1, parent, text) makes the node a call
+        or a check behind leads to."""
+        new, put = self.new, self.put
+        pending = [root]
+        state = {root: (0, False, 0)}                    # node -> (actor, a check has been made, raises so far)
+        while pending:                                   # breadth first: every child index is above its parent's
+            n = pending.pop(0)
+            p, checked, raises = state[n]
+            puts = put[n]
+            facing = max(puts) - puts[p]
+            kids = []
+            if facing:
+                pf = list(puts)
+                kids.append(new(KIND_FOLD0 + p, pf[0], pf[1], n, "%d:fold" % p))
+                pc = list(puts); pc[p] = max(puts)
+                kids.append(end(pc[0], pc[1], n, "%d:call" % p))
+                for amount in (self.sizes(p, puts, 2, bet_fractions) if raises < max_raises else []):
+                    pr = list(puts); pr[p] = max(puts) + amount
+                    c = new(KIND_P0 + (1 - p), pr[0], pr[1], n, "%d:raise %d" % (p, amount))
+                    state[c] = (1 - p, True, raises + 1); pending.append(c); kids.append(c)
+            else:
+                if checked:
+                    kids.append(end(puts[0], puts[1], n, "%d:check" % p))
+                else:
+                    c = new(KIND_P0 + (1 - p), puts[0], puts[1], n, "%d:check" % p)
+                    state[c] = (1 - p, True, raises); pending.append(c); kids.append(c)
+                for amount in (self.sizes(p, puts, 3, bet_fractions) if raises < max_raises else []):
+                    pb = list(puts); pb[p] += amount
+                    c = new(KIND_P0 + (1 - p), pb[0], pb[1], n, "%d:bet %d" % (p, amount))
+                    state[c] = (1 - p, True, raises + 1); pending.append(c); kids.append(c)
+            self.child[n][:len(kids)] = kids
+
+
 def river_tree(pot, stack, bet_fractions=(0.5, 1.0), max_raises=2):
     """The tree of a river betting round: `pot` chips in the middle, `stack` chips behind each player, player 0 first.
     The rule: a player who faces no bet may check or bet; one who faces a bet may fold, call or raise.  max_raises counts the opening bet
@@ -56,54 +116,9 @@ def river_tree(pot, stack, bet_fractions=(0.5, 1.0), max_raises=2):
     pot, stack, max_raises = int(pot), int(stack), int(max_raises)
     if pot < 0 or stack < 0 or max_raises < 0:
         raise ValueError("pot, stack and max_raises must be non-negative")
-    kind, child, put, actions = [], [], [], []
-
-    def new(k, p0, p1, parent, text):
-        kind.append(k); child.append([NO_CHILD] * 4); put.append([p0, p1]); actions.append(None if parent is None else (parent, text))
-        if len(kind) > MAX_NODES:
-            raise ValueError("the tree has more than %d nodes: fewer bet sizes or raises" % MAX_NODES)
-        return len(kind) - 1
-
-    def sizes(p, puts, room):
-        to_call = max(puts) - puts[p]
-        after = pot + puts[0] + puts[1] + to_call
-        left = stack - puts[p] - to_call
-        out = []
-        for f in bet_fractions:
-            amount = min(max(1, int(math.floor(f * after))), left)
-            if amount > 0 and amount not in out:
-                out.append(amount)
-        return out[:room]
-
-    pending = [new(KIND_P0, 0, 0, None, None)]
-    state = {0: (0, False, 0)}                       # node -> (actor, a check has been made, raises so far)
-    while pending:                                   # breadth first: every child index is above its parent's
-        n = pending.pop(0)
-        p, checked, raises = state[n]
-        puts = put[n]
-        facing = max(puts) - puts[p]
-        kids = []
-        if facing:
-            pf = list(puts)
-            kids.append(new(KIND_FOLD0 + p, pf[0], pf[1], n, "%d:fold" % p))
-            pc = list(puts); pc[p] = max(puts)
-            kids.append(new(KIND_SHOWDOWN, pc[0], pc[1], n, "%d:call" % p))
-            for amount in (sizes(p, puts, 2) if raises < max_raises else []):
-                pr = list(puts); pr[p] = max(puts) + amount
-                c = new(KIND_P0 + (1 - p), pr[0], pr[1], n, "%d:raise %d" % (p, amount))
-                state[c] = (1 - p, True, raises + 1); pending.append(c); kids.append(c)
-        else:
-            if checked:
-                kids.append(new(KIND_SHOWDOWN, puts[0], puts[1], n, "%d:check" % p))
-            else:
-                c = new(KIND_P0 + (1 - p), puts[0], puts[1], n, "%d:check" % p)
-                state[c] = (1 - p, True, raises); pending.append(c); kids.append(c)
-            for amount in (sizes(p, puts, 3) if raises < max_raises else []):
-                pb = list(puts); pb[p] += amount
-                c = new(KIND_P0 + (1 - p), pb[0], pb[1], n, "%d:bet %d" % (p, amount))
-                state[c] = (1 - p, True, raises + 1); pending.append(c); kids.append(c)
-        child[n][:len(kids)] = kids
-    return RiverTree(kind, child, put, pot, actions)
+    b = _Builder(pot, stack, MAX_NODES)
+    b.betting_round(b.new(KIND_P0, 0, 0, None, None), bet_fractions, max_raises, lambda p0, p1, n, text: b.new(KIND_SHOWDOWN, p0, p1, n, text))
+    return RiverTree(b.kind, b.child, b.put, pot, b.actions)
 
 
 class RiverSolution:
@@ -207,6 +222,182 @@ def solve_river(board, ranges, tree, iters, dead=(), device=0):
     b = np.array([[_card(c) for c in board]], np.uint8)
     d = np.array([dead if isinstance(dead, (int, np.integer)) else dead_mask(dead)], np.uint64)
     r = solve_river_batch(b, np.asarray(ranges)[None], tree, iters, d, device=device)[0]
+    if r.status:
+        raise ValueError("invalid spot: " + equity_status_text(r.status))
+    return r
+
+
+# ------------------------------------------------------------------------------------------------ the turn solver
+TURN_MAX_NODES = 128
+KIND_CHANCE = 5
+
+
+class TurnTree(RiverTree):
+    """A betting tree on a four-card board: RiverTree's arrays, with kind 5 = chance (the river card is dealt; one child).  Nodes not
+    below a chance node are turn-level, the others river-level.  decision_nodes: the TURN-LEVEL decision nodes in index order (row d of a
+    solution's strategy); river_decision_nodes: the river-level ones (row d of river_strategy)."""
+
+    def __init__(self, kind, child, put, pot, actions=None):
+        super().__init__(kind, child, put, pot, actions)
+        self.river_level = np.zeros(self.n, bool)
+        for v in range(self.n):
+            for c in self.child[v]:
+                if c != NO_CHILD and c < self.n:
+                    self.river_level[c] = self.river_level[v] or self.kind[v] == KIND_CHANCE
+        decisions = self.decision_nodes
+        self.decision_nodes = [v for v in decisions if not self.river_level[v]]
+        self.river_decision_nodes = [v for v in decisions if self.river_level[v]]
+
+    def __repr__(self):
+        return "TurnTree(n=%d, turn decisions=%d, river decisions=%d, pot=%d)" % (self.n, len(self.decision_nodes), len(self.river_decision_nodes), self.pot)
+
+
+def turn_tree(pot, stack, bet_fractions=(0.5, 1.0), max_raises=2, river_bet_fractions=None, river_max_raises=None):
+    """The tree of a turn and a river betting round: `pot` chips in the middle, `stack` chips behind each player, player 0 first on both
+    streets.  river_tree's betting rule on each street (river_bet_fractions / river_max_raises: None = the turn's).  Every turn line that
+    ends in a call or in check-check leads to a chance node and from there to a river round on the chips left -- or straight to a
+    showdown if nothing is left.  At most 128 nodes (ValueError)."""
+    pot, stack, max_raises = int(pot), int(stack), int(max_raises)
+    river_bet_fractions = bet_fractions if river_bet_fractions is None else river_bet_fractions
+    river_max_raises = max_raises if river_max_raises is None else int(river_max_raises)
+    if pot < 0 or stack < 0 or max_raises < 0 or river_max_raises < 0:
+        raise ValueError("pot, stack and max_raises must be non-negative")
+    b = _Builder(pot, stack, TURN_MAX_NODES)
+    chances = []
+
+    def deal(p0, p1, n, text):
+        chances.append(b.new(KIND_CHANCE, p0, p1, n, text))
+        return chances[-1]
+
+    b.betting_round(b.new(KIND_P0, 0, 0, None, None), bet_fractions, max_raises, deal)
+    for c in chances:
+        p0, p1 = b.put[c]
+        if p0 >= stack:
+            b.child[c][0] = b.new(KIND_SHOWDOWN, p0, p1, c, "deal")
+        else:
+            b.child[c][0] = b.new(KIND_P0, p0, p1, c, "deal")
+            b.betting_round(b.child[c][0], river_bet_fractions, river_max_raises, lambda q0, q1, n, text: b.new(KIND_SHOWDOWN, q0, q1, n, text))
+    return TurnTree(b.kind, b.child, b.put, pot, b.actions)
+
+
+class TurnSolution:
+    """What pk_solve_turn returns for one spot or a batch: strategy uint16 [D_t, 4, 1326], river_strategy uint16 [D_r, 52, 4, 1326] (None
+    unless asked for; indexed by the river card's canonical index, 0 for cards outside the pool and holdings with the card), value and br
+    int64 [2, 1326] (half-chips times the opponent's reach, which starts at weight << 1, times the P - 4 river cards), status, and pool
+    (P).  A batch has a leading [m]."""
+
+    def __init__(self, tree, ranges, strategy, river_strategy, value, br, status, valid, pool):
+        self.tree, self.ranges, self.strategy, self.river_strategy = tree, ranges, strategy, river_strategy
+        self.value, self.br, self.status, self.valid, self.pool = value, br, status, valid, pool
+
+    def __getitem__(self, i):
+        return TurnSolution(self.tree, self.ranges[i], self.strategy[i], None if self.river_strategy is None else self.river_strategy[i],
+                            self.value[i], self.br[i], self.status[i], self.valid[i], self.pool[i])
+
+    _pair_weight = RiverSolution._pair_weight
+    _one = RiverSolution._one
+
+    @property
+    def ev(self):
+        """chips per player: sum_h w_p[h] value[p][h] / (4 (P - 4) sum over disjoint pairs of w_0 w_1); Python integers, one division each"""
+        self._one()
+        den = 4 * (int(self.pool) - 4) * self._pair_weight()
+        return tuple(sum(int(w) * int(v) for w, v in zip(self.ranges[p], self.value[p])) / den if den else float("nan") for p in (0, 1))
+
+    @property
+    def exploitability(self):
+        """sum_p (br_p - value_p) reduced the same way, in chips"""
+        self._one()
+        den = 4 * (int(self.pool) - 4) * self._pair_weight()
+        num = sum(int(w) * (int(b) - int(v)) for p in (0, 1) for w, b, v in zip(self.ranges[p], self.br[p], self.value[p]))
+        return num / den if den else float("nan")
+
+    def probabilities(self, node, river_card=None):
+        """float64 [actions, 1326]: the strategy at decision node `node` (a node index of the tree) -- of a river-level node under
+        river_card (a Card-like, 'RS' string or Card.value); nan at invalid holdings and at holdings with the river card"""
+        self._one()
+        node = int(node)
+        nact = self.tree.num_actions(node)
+        valid = self.valid
+        if node in self.tree.decision_nodes:
+            out = self.strategy[self.tree.decision_nodes.index(node), :nact].astype(np.float64) / ONE
+        else:
+            if self.river_strategy is None:
+                raise ValueError("solve with river_strategy=True")
+            if river_card is None:
+                raise ValueError("a river-level node needs river_card")
+            c = int(_card(river_card))
+            k = (c & 15) * 4 + (c >> 4)
+            out = self.river_strategy[self.tree.river_decision_nodes.index(node), k, :nact].astype(np.float64) / ONE
+            a = np.array([a for b in range(52) for a in range(b)])
+            b = np.array([b for b in range(52) for a in range(b)])
+            valid = valid & (a != k) & (b != k)
+        out[:, ~valid] = np.nan
+        return out
+
+    def __repr__(self):
+        return "TurnSolution(status=%r)" % (self.status,)
+
+
+def _turn_levels(tree):
+    nr = int(np.count_nonzero(tree.river_level))
+    return tree.n - nr, nr
+
+
+def turn_grid(tree, m=None):
+    """The number of workgroups a solve of `tree` uses (for m spots; None: for any m that large): min(m, 256, 4 GiB / the work space of
+    one workgroup).  No output depends on it."""
+    nt, nr = _turn_levels(tree)
+    return int(L.lib().pk_turn_grid(GRID_MAX if m is None else int(m), nt, nr))
+
+
+def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False, device=0):
+    """pk_solve_turn on host arrays: board uint8 [m, 4] Card.value, ranges uint16 [m, 2, 1326] over holding_index, one TurnTree for the
+    call, dead uint64 [m] masks over canonical card indices (None: none) -> TurnSolution with a leading [m].  river_strategy=True also
+    returns the river-level strategies (551 616 bytes per river-level decision node and spot)."""
+    board = np.ascontiguousarray(board, np.uint8)
+    if board.ndim != 2 or board.shape[1] != 4:
+        raise ValueError("board must have shape [m, 4]")
+    m = board.shape[0]
+    ranges = np.ascontiguousarray(ranges, np.uint16)
+    if ranges.shape != (m, 2, L.EQ_HOLDINGS):
+        raise ValueError("ranges must have shape [m, 2, 1326]")
+    if dead is not None:
+        dead = np.ascontiguousarray(dead, np.uint64)
+        if dead.shape != (m,):
+            raise ValueError("dead must have shape [m]")
+    Dt, Dr = len(tree.decision_nodes), len(tree.river_decision_nodes)
+    strategy = np.zeros((m, Dt, 4, L.EQ_HOLDINGS), np.uint16)
+    rstrat = np.zeros((m, Dr, 52, 4, L.EQ_HOLDINGS), np.uint16) if river_strategy else None
+    value, br = np.zeros((m, 2, L.EQ_HOLDINGS), np.int64), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64)
+    status = np.zeros(m, np.uint8)
+    L.check(L.lib().pk_solve_turn(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *_tree_args(tree), int(iters), L.ptr(strategy),
+                                  L.ptr(rstrat), L.ptr(value), L.ptr(br), L.ptr(status)))
+    board5 = np.concatenate([board, np.zeros((m, 1), np.uint8)], axis=1)
+    valid = rvr_valid_holdings(board5, np.full(m, 4, np.uint8), dead) & (status == 0)[:, None]
+    pool = np.where(status == 0, valid.sum(axis=1), 0)
+    pool = np.array([int(round((1 + math.sqrt(1 + 8 * int(x))) / 2)) if x else 0 for x in pool])      # C(P, 2) valid holdings -> P
+    return TurnSolution(tree, ranges, strategy, rstrat, value, br, status, valid, pool)
+
+
+def solve_turn_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None, river_strategy_d=None, value_d=None, br_d=None, status_d=None,
+                 device=0, stream=None):
+    """pk_solve_turn_d: the same on device-resident buffers (device pointers as ints / c_void_p; the tree stays a host TurnTree; dead_d and
+    the outputs may be None), asynchronous on `stream`."""
+    L.check(L.lib().pk_solve_turn_d(int(device), int(m), board_d, dead_d, ranges_d, *_tree_args(tree), int(iters), strategy_d, river_strategy_d,
+                                    value_d, br_d, status_d, stream))
+
+
+def solve_turn(board, ranges, tree, iters, dead=(), river_strategy=False, device=0):
+    """One subgame.  board: the four board cards; ranges: [2, 1326] integers 0 .. 65535 over holding_index, player 0 (first to act on
+    both streets) then player 1; dead: cards known to be out of play.  Raises ValueError for an invalid spot.  A reach starts at
+    weight << 1 and every split rounds down: scale a range so that its largest weight uses the sixteen bits."""
+    board = list(board)
+    if len(board) != 4:
+        raise ValueError("four board cards")
+    b = np.array([[_card(c) for c in board]], np.uint8)
+    d = np.array([dead if isinstance(dead, (int, np.integer)) else dead_mask(dead)], np.uint64)
+    r = solve_turn_batch(b, np.asarray(ranges)[None], tree, iters, d, river_strategy=river_strategy, device=device)[0]
     if r.status:
         raise ValueError("invalid spot: " + equity_status_text(r.status))
     return r

@@ -60,6 +60,7 @@ import hist_cluster_spec as CS          # noqa: E402
 import hist_spec as HS                  # noqa: E402
 import preflop_spec as PS               # noqa: E402
 import river_solver_spec as RVS         # noqa: E402
+import turn_solver_spec as TSS          # noqa: E402
 import ranged_ev_spec as XS             # noqa: E402
 import rvr_spec as VS                   # noqa: E402
 from oracle import rng_spec as R        # noqa: E402
@@ -75,7 +76,7 @@ OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("w
            "cluster": ("centroids_out", "label", "dist", "inertia", "changed"),
            "herohist": ("hist", "void", "completions", "status"), "preflop": ("win", "tie"),
            "pfhero": ("agg", "win", "tie", "boards", "status"), "pfrvr": ("win", "tie", "tot"),
-           "riversolve": ("strategy", "value", "br", "status")}
+           "riversolve": ("strategy", "value", "br", "status"), "turnsolve": ("strategy", "river_strategy", "value", "br", "status")}
 
 
 class Case:
@@ -1133,6 +1134,80 @@ def river_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- turn solver
+def turn_case(name, pools, tree, iters, seed, outputs=None, quick=True, edit=None, redit=None, fixture=None):
+    """k_ts_prep + k_turn_solve against tests/turn_solver_spec.py at a grid of 1; int64 value / br are compared as their bit patterns.
+    fixture: the spot and the expected values come from tests/golden/turn_solver/<fixture>.npz (written by the spec: make.py there)."""
+    m = len(pools)
+    if fixture:
+        fx = np.load(os.path.join(ROOT, "tests", "golden", "turn_solver", fixture + ".npz"))
+        board, dead, ranges = fx["board"][None].copy(), np.array([fx["dead"]], np.uint64), fx["ranges"][None].copy()
+    else:
+        board, _, dead = board_spots(seed, [(4, p) for p in pools])
+        board = np.ascontiguousarray(board[:, :4])
+        rng = np.random.default_rng(seed + 1)
+        ranges = rng.integers(0, 65536, (m, 2, HOLDINGS)).astype(np.uint16)
+        for row in ranges.reshape(-1, HOLDINGS):
+            row[rng.integers(0, HOLDINGS, 200)] = 0
+            row[rng.integers(0, HOLDINGS, 100)] = 65535
+    if edit:
+        edit(board, dead)
+    if redit:
+        redit(ranges)
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [1]), "iters": ("u32", [iters]), "n": ("u32", [tree.n]), "pot": ("u32", [tree.pot]),
+              "kind": ("u8", tree.kind), "child": ("u8", tree.child), "put": ("u32", tree.put), "board": ("u8", board), "dead": ("u64", dead),
+              "ranges": ("u16", ranges)}
+
+    def expect():
+        if fixture:
+            return dict(strategy=fx["strategy"][None], value=fx["value"][None].view(np.uint64), br=fx["br"][None].view(np.uint64), status=fx["status"][None])
+        r = TSS.solve_batch(board, ranges, tree, iters, dead)
+        return dict(strategy=r["strategy"], river_strategy=r["river_strategy"], value=r["value"].view(np.uint64), br=r["br"].view(np.uint64), status=r["status"])
+    return Case(name, "turnsolve", arrays, expect, outputs, quick)
+
+
+def turn_feature_tree():
+    """A hand-made tree with a four-action root, a forced node, turn-level folds, river-level folds and an all-in chance -> showdown."""
+    from pokerl_amd.solver import TurnTree
+    FF = 0xFF
+    nodes = [(0, [1, 2, 3, 4], (0, 0)), (1, [5], (0, 0)), (1, [6, 7], (50, 0)), (1, [8, 9], (300, 0)), (1, [10, 11], (100, 0)),
+             (5, [12], (0, 0)), (3, [], (50, 0)), (5, [13], (50, 50)), (3, [], (300, 0)), (5, [14], (300, 300)), (3, [], (100, 0)), (5, [15], (100, 100)),
+             (0, [16, 17], (0, 0)), (4, [], (50, 50)), (4, [], (300, 300)), (0, [18, 19], (100, 100)), (4, [], (0, 0)), (1, [20, 21], (100, 0)),
+             (1, [22, 23, 24], (200, 100)), (4, [], (100, 100)), (3, [], (100, 0)), (4, [], (100, 100)), (3, [], (200, 100)), (4, [], (200, 200)),
+             (0, [25, 26], (200, 300)), (2, [], (200, 300)), (4, [], (300, 300))]
+    return TurnTree([k for k, _, _ in nodes], [ch + [FF] * (4 - len(ch)) for _, ch, _ in nodes], [list(p) for _, _, p in nodes], 100)
+
+
+def turn_cases():
+    """The turn solver's cases (names tsolve-...), every one at a grid of 1: one workgroup takes the spots in turn, so stale LDS or work
+    space of the spot before would show.  NOT part of all_cases()."""
+    from pokerl_amd.solver import turn_tree
+    small, feature = turn_tree(100, 50, (0.5,), 1), turn_feature_tree()
+
+    def straight_flush_board(board, dead):                            # four of the river solver's royal_board, the rest of that suit dead:
+        board[:] = np.array([8, 9, 10, 11], np.uint8)                  # the fifth on the river makes the board play for everyone
+        for i in range(len(dead)):
+            dead[i] = np.uint64((int(dead[i]) & ~sum(1 << (r * 4) for r in range(8, 13))) | sum(1 << (r * 4) for r in range(8)))
+
+    def break_middle_board(board, dead):
+        board[1, 1] = board[1, 0]
+
+    def zero_one(ranges):
+        ranges[0, 1] = 0
+        ranges[1, 0] = 0
+    cs = [turn_case("tsolve-pools-grid1", (5, 9, 20, 33), small, 2, 51),
+          turn_case("tsolve-feature-tree-iters1", (8, 12), feature, 1, 52),
+          turn_case("tsolve-feature-tree-iters3", (6, 10), feature, 3, 53),
+          turn_case("tsolve-refused-between", (9, 8, 7), small, 2, 54, edit=break_middle_board),
+          turn_case("tsolve-board-plays", (14, 16), small, 2, 55, edit=straight_flush_board),
+          turn_case("tsolve-one-range-zero", (10, 12), feature, 2, 56, redit=zero_one),
+          turn_case("tsolve-no-strategy", (7, 8), small, 2, 57, outputs=("value", "br", "status")),
+          turn_case("tsolve-status-only", (9, 9, 9), small, 1, 58, outputs=("status",), edit=break_middle_board),
+          turn_case("tsolve-p48-fixture", (48,), turn_tree(100, 400, (1.0,), 1), 2, 59, outputs=("strategy", "value", "br", "status"), quick=False, fixture="p48")]
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -1147,7 +1222,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

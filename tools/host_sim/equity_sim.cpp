@@ -9,7 +9,8 @@
 //   equity_sim <case file> <out file>
 // Case file: lines "name dtype count" (dtype u8 u16 u32 u64 i32) each followed by a line of `count` decimal values, and
 // "family <name>" / "outputs <name> ..." lines.  Out file: the same array format.
-// -DPK_ES_ONLY=1 .. 12: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist, preflop, rangedev, riversolve), so that a test can compile them side by side.
+// -DPK_ES_ONLY=1 .. 13: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist, preflop, rangedev, riversolve, turnsolve), so that a test can compile them side by side.
+// The turnsolve family (pk_turn_solver.hip: k_ts_prep, k_turn_solve) takes the tree as riversolve does; the driver derives nact, row, river and idx as the host check does.
 // The riversolve family (pk_river_solver.hip: k_rs_prep, k_river_solve) takes the tree's arrays as the C ABI does; the driver derives nact and row as the host check does.  Its
 // int64 outputs (value, br) travel as their bit patterns, dtype u64.
 // The preflop family (pk_preflop.hip) is the partial count: the driver queues k_pfm_rank and k_pfm_count chunk by chunk in the order of
@@ -68,6 +69,9 @@
 #endif
 #if PK_ES_HAS(12)
 #include "../../pokerl_amd/csrc/pk_river_solver.hip"
+#endif
+#if PK_ES_HAS(13)
+#include "../../pokerl_amd/csrc/pk_turn_solver.hip"
 #endif
 #include <chrono>
 #include <climits>
@@ -633,6 +637,44 @@ void run_river(Case &c, const uint32_t *tab) {
 }
 #endif
 
+#if PK_ES_HAS(13)
+void run_turn(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const uint32_t n = (uint32_t)c.num("n"), iters = (uint32_t)c.num("iters");
+    if (n < 1 || n > (uint32_t)TS_MAX_NODES || grid < 1) die("turnsolve: n outside 1 .. 128, or no workgroup");
+    const uint8_t *kind = c.need<uint8_t>("kind", n), *child = c.need<uint8_t>("child", (size_t)n * 4);
+    const uint32_t *put = c.need<uint32_t>("put", (size_t)n * 2);
+    TsTree t{};
+    t.n = n; t.pot = (uint32_t)c.num("pot");
+    size_t D[2] = {0, 0};
+    for (uint32_t v = 0; v < n; ++v) {
+        t.kind[v] = kind[v]; t.put[v][0] = put[v * 2]; t.put[v][1] = put[v * 2 + 1];
+        for (int a = 0; a < 4; ++a) {
+            const uint8_t ch = child[v * 4 + a];
+            t.child[v][a] = ch; t.nact[v] += ch != 0xFF;
+            if (ch != 0xFF && ch < n) t.river[ch] = t.river[v] || kind[v] == TS_CHANCE;
+        }
+        t.idx[v] = (uint8_t)(t.river[v] ? t.nr++ : t.nt++);
+        if (kind[v] <= RS_P1) t.row[v] = (uint8_t)D[t.river[v]]++;
+    }
+    const TsSpots spots{c.need<uint8_t>("board", m * 4), c.arr<uint64_t>("dead", m), c.need<uint16_t>("ranges", m * 2 * RS_HOLDINGS)};
+    TsOut out{};
+    out.strategy = c.output<uint16_t>("strategy", "u16", m * D[0] * 4 * RS_HOLDINGS);
+    out.river_strategy = c.output<uint16_t>("river_strategy", "u16", m * D[1] * 52 * 4 * RS_HOLDINGS);
+    out.value = (int64_t *)c.output<uint64_t>("value", "u64", m * 2 * RS_HOLDINGS);
+    out.br = (int64_t *)c.output<uint64_t>("br", "u64", m * 2 * RS_HOLDINGS);
+    out.status = c.output<uint8_t>("status", "u8", m);
+    Work<uint64_t> desc(m * RS_DESC_WORDS);
+    Work<char> ws((size_t)grid * ts_group_bytes(t.nt, t.nr));       // sized by the grid, as pk::ts_work_bytes sizes it
+    const TsPrepArgs a{spots, out.status, desc.p, m};
+    pk_sim::launch(prep_grid(m, TS_PREP_BLOCK), TS_PREP_BLOCK, [&] { k_ts_prep(a); });
+    const uint64_t *dp = desc.p;
+    char *wp = ws.p;
+    if (out.strategy || out.river_strategy || out.value || out.br) pk_sim::launch(grid, RS_BLOCK, [&] { k_turn_solve(tab, dp, t, spots, out, wp, iters, (uint32_t)m); });
+}
+#endif
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -640,7 +682,7 @@ int main(int argc, char **argv) {
     Case c(argv[1]);
     // the function-local __shared__ arrays of the main kernels (the preparation kernels have none)
     const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "11k_hero_histPKj", "5k_eqwILi", "4k_evILi", "5k_evwILi", "10k_cl_quant", "11k_cl_assign",
-                                        "11k_cl_update", "14k_cl_seed_dist", "14k_cl_seed_pick", "10k_pfm_rank", "11k_pfm_count", "10k_pfm_hero", "9k_pfm_rvr", "13k_river_solvePKj"});
+                                        "11k_cl_update", "14k_cl_seed_dist", "14k_cl_seed_pick", "10k_pfm_rank", "11k_pfm_count", "10k_pfm_hero", "9k_pfm_rvr", "13k_river_solvePKj", "12k_turn_solvePKj"});
     Work<uint32_t> tab(EVAL7_TAB_WORDS);
     for (int i = 0; i < EVAL7_TAB_WORDS; ++i) tab.p[i] = eval7_tab_entry((uint32_t)i);
     const auto t0 = std::chrono::steady_clock::now();
@@ -705,6 +747,9 @@ int main(int argc, char **argv) {
 #endif
 #if PK_ES_HAS(12)
     if (c.family == "riversolve") { run_river(c, tab.p); ran = true; }
+#endif
+#if PK_ES_HAS(13)
+    if (c.family == "turnsolve") { run_turn(c, tab.p); ran = true; }
 #endif
     if (!ran) die("family " + c.family + ": not in this build");
     c.write(argv[2]);

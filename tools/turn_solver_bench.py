@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Timings of the turn solver (pk_solve_turn_d) on one MI355X, printed as ONE JSON line and written to profiles/turn_solver_bench.json
+(stamped with the library's source hash).  Legs: m = 256 and 1 024 full-pool turn subgames (random boards, random ranges with zeros and
+65 535s), turn_tree(100, 400, (1.0,), 1), 64 iterations; outputs strategy, value, br, status (river_strategy is not asked for).  Per leg:
+milliseconds per call (a HIP event pair on the call's stream and the host's clock, every shape warmed up, median of `--samples`),
+microseconds per spot-iteration, the call's work-space bytes -- and the RATIO to the yardstick a user has without the turn solver:
+pk_solve_river_d on the 48 x m river boards (each turn board plus each of its river cards, the same ranges) with the river subtree
+river_tree(100, 400, (1.0,), 1) and the same iteration count, outputs value, br, status.  The yardstick is the cost of the inner work
+alone: it has no chance node, so it computes no turn strategy.
+
+    python tools/turn_solver_bench.py [--samples 3] [--m 256 1024] [--iters 64]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import numpy as np  # noqa: E402
+import pokerl_amd  # noqa: E402
+from pokerl_amd import _lib as L  # noqa: E402
+from pokerl_amd import hipmem, solver  # noqa: E402
+from pokerl_amd.hipmem import DeviceBuffer  # noqa: E402
+from equity_bench import CANON, time_stream  # noqa: E402
+import kernel_meta  # noqa: E402
+
+H = L.EQ_HOLDINGS
+TABLE_BYTES, TURN_NODE_BYTES, RIVER_NODE_BYTES = 423936, 50688, 866048        # pk_turn_solver.hpp
+
+
+def subgames(rng, m):
+    """m turn boards, their 48 river boards each [m * 48, 5], ranges [m, 2, 1326]"""
+    board, river = np.zeros((m, 4), np.uint8), np.zeros((m, 48, 5), np.uint8)
+    for i in range(m):
+        deck = rng.permutation(52)
+        board[i] = [CANON[c] for c in deck[:4]]
+        river[i, :, :4] = board[i]
+        river[i, :, 4] = [CANON[c] for c in sorted(deck[4:])]
+    ranges = rng.integers(0, 65536, (m, 2, H)).astype(np.uint16)
+    for row in ranges.reshape(-1, H):
+        row[rng.integers(0, H, 200)] = 0
+        row[rng.integers(0, H, 100)] = 65535
+    return board, river.reshape(m * 48, 5), ranges
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", type=int, default=3)
+    ap.add_argument("--m", type=int, nargs="+", default=[256, 1024])
+    ap.add_argument("--iters", type=int, default=64)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "turn_solver_bench.json"))
+    args = ap.parse_args()
+    if pokerl_amd.device_count() < 1:
+        sys.exit("turn_solver_bench: no MI355X visible (no fallback)")
+    hip = hipmem._lib()
+    stream = C.c_void_p()
+    assert hip.hipStreamCreateWithFlags(C.byref(stream), 1) == 0
+    rng = np.random.default_rng(0)
+    tree, rtree = solver.turn_tree(100, 400, (1.0,), 1), solver.river_tree(100, 400, (1.0,), 1)
+    Dt = len(tree.decision_nodes)
+    nr = int(tree.river_level.sum())
+    meta = kernel_meta.kernels(L.LIB_PATH)["k_turn_solve"]
+    res = dict(tool="turn_solver_bench", src=L.source_hash(), samples=args.samples, iters=args.iters, tree_nodes=tree.n, turn_level_nodes=tree.n - nr,
+               river_level_nodes=nr, yardstick_tree_nodes=rtree.n, legs={},
+               k_turn_solve=dict(vgprs=meta["vgprs"], sgprs=meta["sgprs"], lds=meta["lds"], scratch=meta["private_segment"], block=512))
+    board, river, ranges = subgames(rng, max(args.m))
+    for m in args.m:
+        grid = solver.turn_grid(tree, m)
+        ins = [DeviceBuffer(x.nbytes).upload(x) for x in (np.ascontiguousarray(board[:m]), np.ascontiguousarray(ranges[:m]))]
+        strategy, value, br, status = DeviceBuffer(m * Dt * 4 * H * 2), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m)
+
+        def run():
+            solver.solve_turn_d(m, ins[0].ptr, ins[1].ptr, tree, args.iters, strategy_d=strategy.ptr, value_d=value.ptr, br_d=br.ptr, status_d=status.ptr,
+                                stream=stream)
+
+        us, each, wall, odd = time_stream(run, stream, args.samples, warmup=1)
+        assert not status.download(np.uint8, m).any()
+        v, b = value.download(np.int64, m * 2 * H), br.download(np.int64, m * 2 * H)
+        assert (b >= v).all() and v.any()
+        for x in ins + [strategy, value, br, status]:
+            x.free()
+        # the yardstick: 48 m river subgames, each spot's ranges repeated for its 48 river boards
+        M = 48 * m
+        rins = [DeviceBuffer(x.nbytes).upload(x) for x in (np.ascontiguousarray(river[:M]), np.ascontiguousarray(np.repeat(ranges[:m], 48, axis=0)))]
+        rvalue, rbr, rstatus = DeviceBuffer(M * 2 * H * 8), DeviceBuffer(M * 2 * H * 8), DeviceBuffer(M)
+
+        def run_river():
+            solver.solve_river_d(M, rins[0].ptr, rins[1].ptr, rtree, args.iters, value_d=rvalue.ptr, br_d=rbr.ptr, status_d=rstatus.ptr, stream=stream)
+
+        rus, reach, rwall, rodd = time_stream(run_river, stream, args.samples, warmup=1)
+        assert not rstatus.download(np.uint8, M).any()
+        for x in rins + [rvalue, rbr, rstatus]:
+            x.free()
+        res["legs"]["m_%d" % m] = dict(ms_per_call=round(us * 1e-3, 3), samples_ms=[round(x * 1e-3, 3) for x in each], host_clock_ms=round(wall * 1e-3, 3),
+                                       event_anomalies=odd + rodd, grid=grid, us_per_spot_iteration=round(us / (m * args.iters), 3),
+                                       work_space_bytes=((m * 24 + 255) & ~255) + grid * (TABLE_BYTES + (tree.n - nr) * TURN_NODE_BYTES + nr * RIVER_NODE_BYTES),
+                                       yardstick_ms_per_call=round(rus * 1e-3, 3), yardstick_samples_ms=[round(x * 1e-3, 3) for x in reach],
+                                       ratio_to_yardstick=round(us / rus, 3))
+    hip.hipStreamDestroy(stream)
+    line = json.dumps(res)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()

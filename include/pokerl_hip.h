@@ -1077,6 +1077,50 @@ int pk_solve_turn(int device, size_t m, const uint8_t *board, const uint64_t *de
                   int64_t *value, int64_t *br, uint8_t *status);
 /* The grid pk_solve_turn uses for m spots of a tree with nt turn-level and nr river-level nodes (no output depends on it). */
 unsigned pk_turn_grid(size_t m, uint32_t nt, uint32_t nr);
+
+/* ---- River and turn solvers: a tree per spot.  The four calls below take `ntrees` trees and, per spot, the index
+ * of its tree: spots of different pots, stacks, bet sizes and raise caps are solved in ONE call.
+ * DEFINITION: spot i's outputs are byte for byte what pk_solve_river / pk_solve_turn give for that spot alone with tree tree_of[i]; only
+ * the row strides of the strategies are the call's (below).
+ * TREES: 1 <= ntrees <= PK_RS_MAX_TREES, in HOST memory in every form.  Tree k is row k of each array -- n u32 [ntrees], kind u8
+ * [ntrees][64] (turn: [ntrees][128]), child u8 [ntrees][64][4], put u32 [ntrees][64][2], pot u32 [ntrees] -- and the entries past n[k] are
+ * ignored.  EVERY tree passes the check of the one-tree call, whether or not a spot names it; a bad tree is PK_E_INVALID_ARG before any
+ * device is looked at, with the one-tree call's text after "tree <k>: ".  ntrees out of range and a NULL n, pot or tree_of are refused the
+ * same way.  The trees are packed on the host and copied to the device with the call: in the _d forms the caller may overwrite the host
+ * tree arrays as soon as the call returns.
+ * tree_of u32 [m]: in DEVICE memory in the _d forms, on the host otherwise.  A spot whose tree_of is >= ntrees reports PK_EQ_BAD_TREE,
+ * gets all-zero outputs and disturbs no neighbour.
+ * STRIDES: Dmax (river), Dtmax and Drmax (turn) are the largest D, D_t and D_r over ALL trees passed (pk_rs_trees_rows / pk_ts_trees_rows
+ * compute them): strategy is u16 [m][Dmax][4][1326] (turn: [m][Dtmax][4][1326]), river_strategy u16 [m][Drmax][52][4][1326]; a spot's
+ * rows at or past its own tree's count are written 0.
+ * WORK SPACE: a workgroup's slice is sized for the largest tree of the call (the turn grid too: pk_turn_grid(m, max nt, max nr)), plus
+ * the packed trees (968 / 2 192 bytes each).  Spots are dealt to workgroups by a fixed stride, whatever their trees' sizes. */
+#define PK_RS_MAX_TREES 65536
+#define PK_EQ_BAD_TREE 32u   /* a tree per spot: tree_of is >= ntrees (the value of PK_EQ_BAD_TABLE, which no spot form reports) */
+int pk_solve_river_trees_d(int device, size_t m, const uint8_t *board_d /*[m][5]*/, const uint64_t *dead_d /*[m]; NULL: none*/,
+                           const uint16_t *ranges_d /*[m][2][1326]*/, uint32_t ntrees, const uint32_t *n /*[ntrees], host*/,
+                           const uint8_t *kind /*[ntrees][64], host*/, const uint8_t *child /*[ntrees][64][4], host*/,
+                           const uint32_t *put /*[ntrees][64][2], host*/, const uint32_t *pot /*[ntrees], host*/,
+                           const uint32_t *tree_of_d /*[m], DEVICE*/, uint32_t iters, uint16_t *strategy_d /*[m][Dmax][4][1326]*/,
+                           int64_t *value_d /*[m][2][1326]*/, int64_t *br_d, uint8_t *status_d, void *stream);
+int pk_solve_river_trees(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees,
+                         const uint32_t *n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot,
+                         const uint32_t *tree_of /*[m], host*/, uint32_t iters, uint16_t *strategy, int64_t *value, int64_t *br, uint8_t *status);
+int pk_solve_turn_trees_d(int device, size_t m, const uint8_t *board_d /*[m][4]*/, const uint64_t *dead_d /*[m]; NULL: none*/,
+                          const uint16_t *ranges_d /*[m][2][1326]*/, uint32_t ntrees, const uint32_t *n /*[ntrees], host*/,
+                          const uint8_t *kind /*[ntrees][128], host*/, const uint8_t *child /*[ntrees][128][4], host*/,
+                          const uint32_t *put /*[ntrees][128][2], host*/, const uint32_t *pot /*[ntrees], host*/,
+                          const uint32_t *tree_of_d /*[m], DEVICE*/, uint32_t iters, uint16_t *strategy_d /*[m][Dtmax][4][1326]*/,
+                          uint16_t *river_strategy_d /*[m][Drmax][52][4][1326]*/, int64_t *value_d /*[m][2][1326]*/, int64_t *br_d,
+                          uint8_t *status_d, void *stream);
+int pk_solve_turn_trees(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees,
+                        const uint32_t *n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot,
+                        const uint32_t *tree_of /*[m], host*/, uint32_t iters, uint16_t *strategy, uint16_t *river_strategy, int64_t *value,
+                        int64_t *br, uint8_t *status);
+/* The row strides of the calls above: the largest number of decision nodes (turn: of turn-level and of river-level ones) over the trees.
+ * They look at kind (and child) only; PK_E_INVALID_ARG for ntrees out of range, a NULL pointer, an n[k] out of range or (turn) a child index <= its parent or >= n[k]. */
+int pk_rs_trees_rows(uint32_t ntrees, const uint32_t *n, const uint8_t *kind, uint32_t *Dmax);
+int pk_ts_trees_rows(uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child, uint32_t *Dtmax, uint32_t *Drmax);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

@@ -24,6 +24,8 @@ EQ_BAD_CARD, EQ_DUP_CARD, EQ_NO_LIVE, EQ_BAD_NBOARD, EQ_IN_FLIGHT, EQ_BAD_TABLE 
 OBSERVER_NONE, OBSERVER_ACTIVE = -1, -2   # pk_clone_tables_d: an exact copy / redeal from each source table's active player
 EQ_PREFLOP, EQ_SMALL_POOL = 64, 128   # ... of pk_equity_range: nb < 3 / fewer pool cards than the board to come plus one holding
 EQ_BAD_BET = 64   # ... of pk_equity_ev: a bet that is negative, NaN or infinite (the value of EQ_PREFLOP, which no EV call reports)
+EQ_BAD_TREE = 32   # PK_EQ_BAD_TREE, of the solvers' tree-per-spot calls: tree_of >= ntrees (the value of EQ_BAD_TABLE, which no spot form reports)
+RS_MAX_TREES = 65536   # PK_RS_MAX_TREES: trees of one pk_solve_river_trees / pk_solve_turn_trees call at most
 EQ_HIST_MAX_BINS = 32   # PK_EQ_HIST_MAX_BINS: the most bins of a strength histogram
 EQ_HOLDINGS = 1326   # PK_EQ_HOLDINGS: unordered pairs of the 52 cards, h = b (b - 1) / 2 + a over canonical indices a < b
 CL_MAX_K, CL_NONE, CL_MAX_ITERS = 4096, 0xFFFF, 1024   # PK_CL_MAX_K, PK_CL_NONE; iterations of one pk_hist_cluster call at most
@@ -57,7 +59,8 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_preflop_count_d", "pk_preflop_count", "pk_preflop_matchups_d", "pk_preflop_matchups",
            "pk_equity_preflop_d", "pk_equity_preflop", "pk_table_equity_preflop_d", "pk_table_equity_preflop",
            "pk_equity_rvr_preflop_d", "pk_equity_rvr_preflop",
-           "pk_solve_river_d", "pk_solve_river", "pk_solve_turn_d", "pk_solve_turn", "pk_turn_grid"]
+           "pk_solve_river_d", "pk_solve_river", "pk_solve_turn_d", "pk_solve_turn", "pk_turn_grid",
+           "pk_solve_river_trees_d", "pk_solve_river_trees", "pk_solve_turn_trees_d", "pk_solve_turn_trees", "pk_rs_trees_rows", "pk_ts_trees_rows"]
 
 
 class PokerlHipError(RuntimeError):
@@ -212,6 +215,12 @@ def lib():
     L.pk_solve_turn_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 3 + [C.c_uint32, C.c_uint32] + [_vp] * 6
     L.pk_solve_turn.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 3 + [C.c_uint32, C.c_uint32] + [_vp] * 5
     L.pk_turn_grid.argtypes = [C.c_size_t, C.c_uint32, C.c_uint32]
+    L.pk_solve_river_trees_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 5
+    L.pk_solve_river_trees.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 4
+    L.pk_solve_turn_trees_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 6
+    L.pk_solve_turn_trees.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 5
+    L.pk_rs_trees_rows.argtypes = [C.c_uint32] + [_vp] * 3
+    L.pk_ts_trees_rows.argtypes = [C.c_uint32] + [_vp] * 5
     for name in SYMBOLS:
         if name not in ("pk_last_error", "pk_build_info", "pk_snapshot_bytes"):
             getattr(L, name).restype = C.c_int

@@ -3055,4 +3055,166 @@ int pk_solve_turn(int device, size_t m, const uint8_t *board, const uint64_t *de
     });
 }
 
+// ---- the river and turn solvers with a tree per spot (pokerl_hip.h "River and turn solvers: a tree per spot").
+// Every tree is checked and packed on the host with the one-tree calls' checks; the packed trees go to the device with the call -- in the
+// host forms as a piece of the staging, in the device forms behind the work space on the caller's stream (the source is this call's own
+// pageable vector: the runtime has finished with it when hipMemcpyAsync returns, so it may go when the call does).
+static_assert(RS_MAX_TREES == 65536u, "the header's text names the limit");
+struct RsPacked { std::vector<RsTree> trees; uint32_t nmax = 0, Dmax = 0; std::string why; };
+struct TsPacked { std::vector<TsTree> trees; uint32_t ntmax = 0, nrmax = 0, Dtmax = 0, Drmax = 0; std::string why; };
+static const char *trees_check(size_t m, bool pointers, uint32_t iters, uint32_t ntrees, bool tree_pointers) {
+    if (const char *why = eq_bad_m(m)) return why;
+    if ((m && !pointers) || !tree_pointers) return ": NULL where a pointer is required (board, ranges, n, kind, child, put, pot, tree_of, status)";
+    if (iters < 1u || iters > (uint32_t)RS_MAX_ITERS) return ": iters outside 1 .. 4096";
+    if (ntrees < 1u || ntrees > RS_MAX_TREES) return ": ntrees outside 1 .. 65536";
+    return nullptr;
+}
+static const char *trees_refusal(std::string &text, uint32_t k, const char *why) {
+    text = ": tree " + std::to_string(k) + why;
+    return text.c_str();
+}
+static const char *rs_pack_trees(size_t m, bool pointers, uint32_t iters, uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child,
+                                 const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, RsPacked &p) {
+    if (const char *why = trees_check(m, pointers, iters, ntrees, n && kind && child && put && pot && tree_of)) return why;
+    p.trees.resize(ntrees);
+    for (uint32_t k = 0; k < ntrees; ++k) {
+        const size_t row = (size_t)k * RS_MAX_NODES;
+        if (const char *why = rs_check_tree(n[k], kind + row, child + row * 4, put + row * 2, pot[k], p.trees[k])) return trees_refusal(p.why, k, why);
+        uint32_t D = 0;
+        for (uint32_t v = 0; v < n[k]; ++v) D += p.trees[k].kind[v] <= RS_P1;
+        p.nmax = n[k] > p.nmax ? n[k] : p.nmax;
+        p.Dmax = D > p.Dmax ? D : p.Dmax;
+    }
+    return nullptr;
+}
+static const char *ts_pack_trees(size_t m, bool pointers, uint32_t iters, uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child,
+                                 const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, TsPacked &p) {
+    if (const char *why = trees_check(m, pointers, iters, ntrees, n && kind && child && put && pot && tree_of)) return why;
+    p.trees.resize(ntrees);
+    for (uint32_t k = 0; k < ntrees; ++k) {
+        const size_t row = (size_t)k * TS_MAX_NODES;
+        TsTree &t = p.trees[k];
+        if (const char *why = ts_check_tree(n[k], kind + row, child + row * 4, put + row * 2, pot[k], t)) return trees_refusal(p.why, k, why);
+        uint32_t D[2] = {0, 0};
+        for (uint32_t v = 0; v < n[k]; ++v) D[t.river[v]] += t.kind[v] <= RS_P1;
+        p.ntmax = t.nt > p.ntmax ? t.nt : p.ntmax;
+        p.nrmax = t.nr > p.nrmax ? t.nr : p.nrmax;
+        p.Dtmax = D[0] > p.Dtmax ? D[0] : p.Dtmax;
+        p.Drmax = D[1] > p.Drmax ? D[1] : p.Drmax;
+    }
+    return nullptr;
+}
+
+int pk_rs_trees_rows(uint32_t ntrees, const uint32_t *n, const uint8_t *kind, uint32_t *Dmax) {
+    const char *call = "pk_rs_trees_rows";
+    if (ntrees < 1u || ntrees > RS_MAX_TREES || !n || !kind || !Dmax) return eq_fail(PK_E_INVALID_ARG, call, ": ntrees outside 1 .. 65536, or a NULL pointer");
+    uint32_t best = 0;
+    for (uint32_t k = 0; k < ntrees; ++k) {
+        if (n[k] < 1u || n[k] > (uint32_t)RS_MAX_NODES) return eq_fail(PK_E_INVALID_ARG, call, (": tree " + std::to_string(k) + ": n outside 1 .. 64").c_str());
+        uint32_t D = 0;
+        for (uint32_t v = 0; v < n[k]; ++v) D += kind[(size_t)k * RS_MAX_NODES + v] <= RS_P1;
+        best = D > best ? D : best;
+    }
+    *Dmax = best;
+    return PK_OK;
+}
+
+int pk_ts_trees_rows(uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child, uint32_t *Dtmax, uint32_t *Drmax) {
+    const char *call = "pk_ts_trees_rows";
+    if (ntrees < 1u || ntrees > RS_MAX_TREES || !n || !kind || !child || !Dtmax || !Drmax)
+        return eq_fail(PK_E_INVALID_ARG, call, ": ntrees outside 1 .. 65536, or a NULL pointer");
+    uint32_t best[2] = {0, 0};
+    for (uint32_t k = 0; k < ntrees; ++k) {
+        if (n[k] < 1u || n[k] > (uint32_t)TS_MAX_NODES) return eq_fail(PK_E_INVALID_ARG, call, (": tree " + std::to_string(k) + ": n outside 1 .. 128").c_str());
+        const uint8_t *kd = kind + (size_t)k * TS_MAX_NODES, *ch = child + (size_t)k * TS_MAX_NODES * 4;
+        uint8_t river[TS_MAX_NODES] = {0};
+        uint32_t D[2] = {0, 0};
+        for (uint32_t v = 0; v < n[k]; ++v) {                 // (every parent comes before its children: the level of v is known here)
+            for (int a = 0; a < 4; ++a) {
+                const uint32_t c = ch[v * 4 + a];
+                if (c == 0xFFu) continue;
+                if (c <= v || c >= n[k]) return eq_fail(PK_E_INVALID_ARG, call, (": tree " + std::to_string(k) + ": a child index is <= its parent or >= n").c_str());
+                river[c] = (uint8_t)(river[v] || kd[v] == TS_CHANCE);
+            }
+            D[river[v]] += kd[v] <= RS_P1;
+        }
+        best[0] = D[0] > best[0] ? D[0] : best[0];
+        best[1] = D[1] > best[1] ? D[1] : best[1];
+    }
+    *Dtmax = best[0]; *Drmax = best[1];
+    return PK_OK;
+}
+
+int pk_solve_river_trees_d(int device, size_t m, const uint8_t *board_d, const uint64_t *dead_d, const uint16_t *ranges_d, uint32_t ntrees, const uint32_t *n,
+                           const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of_d, uint32_t iters,
+                           uint16_t *strategy_d, int64_t *value_d, int64_t *br_d, uint8_t *status_d, void *stream) {
+    const char *call = "pk_solve_river_trees_d";
+    RsPacked p;
+    EQ_REFUSE(g_fail, call, rs_pack_trees(m, board_d && ranges_d && status_d, iters, ntrees, n, kind, child, put, pot, tree_of_d, p));
+    const bool solve = strategy_d || value_d || br_d;
+    const size_t ws = rs_work_bytes(m, p.nmax, solve);
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, ws + (solve ? rs_trees_bytes(ntrees) : 0), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        RsTree *trees_d = (RsTree *)(work + ws);
+        if (solve)
+            if (const hipError_t e = hipMemcpyAsync(trees_d, p.trees.data(), (size_t)ntrees * sizeof(RsTree), hipMemcpyHostToDevice, st)) return e;
+        return rs_launch_trees(st, tab, RsSpots{board_d, dead_d, ranges_d}, RsTrees{trees_d, tree_of_d, p.nmax, p.Dmax}, ntrees, iters, m,
+                               RsOut{strategy_d, value_d, br_d, status_d}, work);
+    });
+}
+
+int pk_solve_river_trees(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees, const uint32_t *n,
+                         const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, uint32_t iters,
+                         uint16_t *strategy, int64_t *value, int64_t *br, uint8_t *status) {
+    const char *call = "pk_solve_river_trees";
+    RsPacked p;
+    EQ_REFUSE(g_fail, call, rs_pack_trees(m, board && ranges && status, iters, ntrees, n, kind, child, put, pot, tree_of, p));
+    const bool solve = strategy || value || br;
+    Stage g;
+    const int bo = g.in(board, m * 5), de = g.in(dead, m * 8), ra = g.in(ranges, m * 2 * RS_HOLDINGS * 2), to = g.in(tree_of, m * 4);
+    const int tr = g.in(solve ? p.trees.data() : nullptr, (size_t)ntrees * sizeof(RsTree));
+    const int sg = g.out(strategy, m * p.Dmax * 4 * RS_HOLDINGS * 2), va = g.out(value, m * 2 * RS_HOLDINGS * 8), be = g.out(br, m * 2 * RS_HOLDINGS * 8);
+    const int su = g.out(status, m);
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, rs_work_bytes(m, p.nmax, solve), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return rs_launch_trees(st, tab, RsSpots{g.at<uint8_t>(bo), g.at<uint64_t>(de), g.at<uint16_t>(ra)},
+                               RsTrees{g.at<RsTree>(tr), g.at<uint32_t>(to), p.nmax, p.Dmax}, ntrees, iters, m,
+                               RsOut{g.at<uint16_t>(sg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
+    });
+}
+
+int pk_solve_turn_trees_d(int device, size_t m, const uint8_t *board_d, const uint64_t *dead_d, const uint16_t *ranges_d, uint32_t ntrees, const uint32_t *n,
+                          const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of_d, uint32_t iters,
+                          uint16_t *strategy_d, uint16_t *river_strategy_d, int64_t *value_d, int64_t *br_d, uint8_t *status_d, void *stream) {
+    const char *call = "pk_solve_turn_trees_d";
+    TsPacked p;
+    EQ_REFUSE(g_fail, call, ts_pack_trees(m, board_d && ranges_d && status_d, iters, ntrees, n, kind, child, put, pot, tree_of_d, p));
+    const bool solve = strategy_d || river_strategy_d || value_d || br_d;
+    const size_t ws = ts_work_bytes(m, p.ntmax, p.nrmax, solve);
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, ws + (solve ? ts_trees_bytes(ntrees) : 0), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        TsTree *trees_d = (TsTree *)(work + ws);
+        if (solve)
+            if (const hipError_t e = hipMemcpyAsync(trees_d, p.trees.data(), (size_t)ntrees * sizeof(TsTree), hipMemcpyHostToDevice, st)) return e;
+        return ts_launch_trees(st, tab, TsSpots{board_d, dead_d, ranges_d}, TsTrees{trees_d, tree_of_d, p.ntmax, p.nrmax, p.Dtmax, p.Drmax}, ntrees, iters, m,
+                               TsOut{strategy_d, river_strategy_d, value_d, br_d, status_d}, work);
+    });
+}
+
+int pk_solve_turn_trees(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees, const uint32_t *n,
+                        const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, uint32_t iters,
+                        uint16_t *strategy, uint16_t *river_strategy, int64_t *value, int64_t *br, uint8_t *status) {
+    const char *call = "pk_solve_turn_trees";
+    TsPacked p;
+    EQ_REFUSE(g_fail, call, ts_pack_trees(m, board && ranges && status, iters, ntrees, n, kind, child, put, pot, tree_of, p));
+    const bool solve = strategy || river_strategy || value || br;
+    Stage g;
+    const int bo = g.in(board, m * 4), de = g.in(dead, m * 8), ra = g.in(ranges, m * 2 * RS_HOLDINGS * 2), to = g.in(tree_of, m * 4);
+    const int tr = g.in(solve ? p.trees.data() : nullptr, (size_t)ntrees * sizeof(TsTree));
+    const int sg = g.out(strategy, m * p.Dtmax * 4 * RS_HOLDINGS * 2), rg = g.out(river_strategy, m * p.Drmax * 52 * 4 * RS_HOLDINGS * 2);
+    const int va = g.out(value, m * 2 * RS_HOLDINGS * 8), be = g.out(br, m * 2 * RS_HOLDINGS * 8), su = g.out(status, m);
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, ts_work_bytes(m, p.ntmax, p.nrmax, solve), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return ts_launch_trees(st, tab, TsSpots{g.at<uint8_t>(bo), g.at<uint64_t>(de), g.at<uint16_t>(ra)},
+                               TsTrees{g.at<TsTree>(tr), g.at<uint32_t>(to), p.ntmax, p.nrmax, p.Dtmax, p.Drmax}, ntrees, iters, m,
+                               TsOut{g.at<uint16_t>(sg), g.at<uint16_t>(rg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
+    });
+}
+
 }  // extern "C"

@@ -1,5 +1,5 @@
 // pk_river_solver.hip -- the river subgame solver (include/pokerl_hip.h "River solver"): simultaneous CFR+ for two
-// players over a caller's betting tree, in 64-bit integers whose sums do not depend on their order.  Two kernels:
+// players over a caller's betting tree, in 64-bit integers whose sums do not depend on their order.  Two kernels, each in two forms:
 //   k_rs_prep       one lane per spot: checks the five board cards and the dead mask, writes the spot's descriptor (range vs range's, k = 0)
 //                   and its status;
 //   k_river_solve   a persistent grid of 512-thread workgroups, the evaluator table and the tree in LDS (staged once per workgroup), ONE
@@ -14,6 +14,11 @@
 //                   The final passes (the average strategy, its values, the best responses) run in the same launch.  A best-response
 //                   pass of p needs only q's reaches, which are those of the value pass: one walk down serves all three, and the walk up
 //                   carries the maximum beside the value.
+//   k_trees_prep / k_trees_river_solve   a call in which every spot names its tree ("River and turn solvers: a tree per spot", DESIGN.md
+//                   section 3.14).  k_trees_prep follows k_rs_prep: it refuses a spot whose tree_of is >= ntrees (PK_EQ_BAD_TREE, folded into
+//                   the descriptor's "good" bit).  k_trees_river_solve is k_river_solve's body (rs_solve_body<PER_SPOT>): it stages
+//                   trees[tree_of[spot]] into LDS at the top of each spot (a refused one: tree 0, unused), lays its slice -- sized for the call's largest tree -- out
+//                   for that tree's n, and writes `strategy` with the call's row stride Dmax, the rows at or past the spot's own D as zeros.
 // Ordinary vector stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_river_solver_host.py reads the code object).
 #include <hip/hip_runtime.h>
 
@@ -59,9 +64,22 @@ __global__ void __launch_bounds__(RS_PREP_BLOCK) k_rs_prep(RsPrepArgs a) {
     if (a.status) a.status[i] = (uint8_t)status;
 }
 
-// registers: one workgroup per CU is two waves per SIMD
-__global__ void __launch_bounds__(RS_BLOCK, 2) k_river_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, RsTree tree, RsSpots spots,
-                                                             RsOut out, char *ws, uint32_t iters, uint32_t m) {
+// The second half of a tree-per-spot call's preparation, queued behind k_rs_prep or k_ts_prep (whose text and code stay as they are): one
+// lane per spot, a tree_of >= ntrees adds PK_EQ_BAD_TREE to the spot's status and clears its descriptor's "good" bit, so that the solver
+// never indexes the trees with it.
+__global__ void __launch_bounds__(RS_PREP_BLOCK) k_trees_prep(const uint32_t *__restrict__ tree_of, uint32_t ntrees, uint64_t *desc, uint8_t *status, size_t m) {
+    const size_t i = (size_t)blockIdx.x * RS_PREP_BLOCK + threadIdx.x;
+    if (i >= m || tree_of[i] < ntrees) return;
+    desc[i * (size_t)RS_DESC_WORDS + 2] &= ~1ull;
+    if (status) status[i] |= (uint8_t)PK_EQ_BAD_TREE;
+}
+
+// The solver's body.  PER_SPOT = false: `tree` is the call's one tree (the kernel's argument), staged once per workgroup.  PER_SPOT = true:
+// `tree` is the call's array of packed trees in device memory, and a spot stages trees[tree_of[spot]] (a refused one tree 0) -- after the barrier at the top
+// of the spot, which the last use of `tr` by the spot before lies behind; nmax and Dmax are the largest n and D of the call.
+template <bool PER_SPOT>
+__device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, const RsTree *tree, const uint32_t *tree_of,
+                                              uint32_t nmax, uint32_t Dmax, const RsSpots &spots, const RsOut &out, char *ws, uint32_t iters, uint32_t m) {
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     __shared__ uint64_t slot[RS_SLOTS];               // key << 11 | pool holding, sorted once per spot; all ones = no holding.  After the
                                                       // sort the same memory holds rs and posof (below)
@@ -75,19 +93,27 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_river_solve(const uint32_t *__r
     static_assert(RS_SORTED * 8 + RS_SORTED * 2 <= RS_SLOTS * 8, "rs and posof fit the sort slots");
     stage_eval7_tab<RS_BLOCK>(T, tab);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
-    for (uint32_t w = tid; w < (uint32_t)(sizeof(RsTree) / 4); w += RS_BLOCK)
-        reinterpret_cast<uint32_t *>(&tr)[PK_IDX(w, sizeof(RsTree) / 4, "tree")] = reinterpret_cast<const uint32_t *>(&tree)[w];
-    __syncthreads();
-    const uint32_t n = uniform(tr.n), pot = uniform(tr.pot);
-    uint32_t D = 0;
-    for (uint32_t v = 0; v < n; ++v) D += tr.kind[PK_IDX(v, RS_MAX_NODES, "kind")] <= RS_P1 ? 1u : 0u;
-    D = uniform(D);
-    // the workgroup's slice of the work space, every array [n][RS_SORTED]
-    char *const base = ws + (size_t)blockIdx.x * rs_group_bytes(n);
-    const size_t plane = (size_t)n * RS_SORTED;
-    int64_t *const R = reinterpret_cast<int64_t *>(base), *const A = R + plane, *const U0 = A + plane, *const U1 = U0 + plane;
-    uint64_t *const RR = reinterpret_cast<uint64_t *>(U1 + plane);
-    uint32_t *const SG = reinterpret_cast<uint32_t *>(RR + plane);
+    uint32_t n = 0, pot = 0, D = 0;
+    int64_t *R = nullptr, *A = nullptr, *U0 = nullptr, *U1 = nullptr;
+    uint64_t *RR = nullptr;
+    uint32_t *SG = nullptr;
+    // A tree into LDS (every lane of the workgroup comes here), and the workgroup's slice of the work space laid out for it
+    auto stage = [&](const RsTree *src) {
+        for (uint32_t w = tid; w < (uint32_t)(sizeof(RsTree) / 4); w += RS_BLOCK)
+            reinterpret_cast<uint32_t *>(&tr)[PK_IDX(w, sizeof(RsTree) / 4, "tree")] = reinterpret_cast<const uint32_t *>(src)[w];
+        __syncthreads();
+        n = uniform(tr.n); pot = uniform(tr.pot);
+        uint32_t dec = 0;
+        for (uint32_t v = 0; v < n; ++v) dec += tr.kind[PK_IDX(v, RS_MAX_NODES, "kind")] <= RS_P1 ? 1u : 0u;
+        D = uniform(dec);
+        // the workgroup's slice of the work space, every array [n][RS_SORTED]
+        char *const base = ws + (size_t)blockIdx.x * rs_group_bytes(PER_SPOT ? nmax : n);
+        const size_t plane = (size_t)n * RS_SORTED;
+        R = reinterpret_cast<int64_t *>(base); A = R + plane; U0 = A + plane; U1 = U0 + plane;
+        RR = reinterpret_cast<uint64_t *>(U1 + plane);
+        SG = reinterpret_cast<uint32_t *>(RR + plane);
+    };
+    if constexpr (!PER_SPOT) stage(tree);
     auto at = [&](uint32_t node, uint32_t i) -> size_t { return (size_t)PK_IDX(node, n, "node") * RS_SORTED + PK_IDX(i, RS_SORTED, "position"); };
     // a decision node's children (every lane of the wave asks together: the answer is wave-uniform); the slots past nact: node 0, never used
     auto kids = [&](uint32_t node, uint32_t nact, uint32_t (&ch)[4]) {
@@ -102,6 +128,13 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_river_solve(const uint32_t *__r
         const bool good = ((uint32_t)meta & 1u) != 0u;
         const uint64_t avail = good ? uniform(d[1]) : 0ull;     // (a refused spot: no holding is valid, every output is 0)
         const uint32_t P = (uint32_t)(meta >> 56);
+        if constexpr (PER_SPOT) {
+            // (good: k_trees_prep has seen tree_of[spot] < ntrees.  A refused spot stages tree 0, which always exists, and uses none of it:
+            // staging on every path keeps n, pot and the slice's pointers plain values of the spot, not merges with the spot before)
+            stage(tree + (good ? PK_IDX(uniform(tree_of[spot]), RS_MAX_TREES, "tree_of") : 0u));
+            if (!good) D = 0;
+        }
+        const uint32_t DS = PER_SPOT ? Dmax : D;      // the row stride of `strategy`
         // ---- zeros: every output at the holdings that are not in the pool, by the lanes of the fixed index h = tid + 512 j
         for (uint32_t h = tid; h < (uint32_t)RS_HOLDINGS; h += RS_BLOCK) {
             uint32_t ca = 0, cb = 1;
@@ -112,8 +145,17 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_river_solve(const uint32_t *__r
                 if (out.br) out.br[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
             }
             if (out.strategy)
-                for (uint32_t r = 0; r < D * 4u; ++r) out.strategy[((size_t)spot * D * 4 + r) * RS_HOLDINGS + h] = 0;
+                for (uint32_t r = 0; r < DS * 4u; ++r) out.strategy[((size_t)spot * DS * 4 + r) * RS_HOLDINGS + h] = 0;
         }
+        // ... and, where the call's stride is wider than the spot's tree, the rows past its own at the holdings of the pool
+        if constexpr (PER_SPOT)
+            if (out.strategy && D < DS)
+                for (uint32_t h = tid; h < (uint32_t)RS_HOLDINGS; h += RS_BLOCK) {
+                    uint32_t ca = 0, cb = 1;
+                    unpair(h, ca, cb);
+                    if (!((avail >> ca) & (avail >> cb) & 1ull)) continue;
+                    for (uint32_t r = D * 4u; r < DS * 4u; ++r) out.strategy[((size_t)spot * DS * 4 + r) * RS_HOLDINGS + h] = 0;
+                }
         if (!good) continue;
         fill_pool(pool, canon, avail, tid);
         __syncthreads();
@@ -351,7 +393,7 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_river_solve(const uint32_t *__r
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     if ((uint32_t)a < nact) SG[at(ch[a], i)] = sig[a];
-                    if (out.strategy) out.strategy[(((size_t)spot * D + row) * 4 + (uint32_t)a) * RS_HOLDINGS + gh[j]] = (uint16_t)sig[a];
+                    if (out.strategy) out.strategy[(((size_t)spot * DS + row) * 4 + (uint32_t)a) * RS_HOLDINGS + gh[j]] = (uint16_t)sig[a];
                 }
             }
         }
@@ -402,6 +444,16 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_river_solve(const uint32_t *__r
     }
 }
 
+// registers: one workgroup per CU is two waves per SIMD
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_river_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, RsTree tree, RsSpots spots,
+                                                             RsOut out, char *ws, uint32_t iters, uint32_t m) {
+    rs_solve_body<false>(tab, desc, &tree, nullptr, 0u, 0u, spots, out, ws, iters, m);
+}
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_trees_river_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, RsTrees trees, RsSpots spots,
+                                                                   RsOut out, char *ws, uint32_t iters, uint32_t m) {
+    rs_solve_body<true>(tab, desc, trees.trees, trees.tree_of, trees.nmax, trees.Dmax, spots, out, ws, iters, m);
+}
+
 namespace pk {
 
 hipError_t rs_launch(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTree &tree, uint32_t iters, size_t m, const RsOut &out,
@@ -413,6 +465,24 @@ hipError_t rs_launch(hipStream_t stream, const uint32_t *tab, const RsSpots &spo
     if (e != hipSuccess || !(out.strategy || out.value || out.br)) return e;   // (status alone: the preparation kernel has written it)
     hipLaunchKernelGGL(k_river_solve, dim3(rs_grid(m)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, tree, spots, out, work + rs_desc_bytes(m),
                        iters, (uint32_t)m);
+    return hipGetLastError();
+}
+
+hipError_t trees_prep_launch(hipStream_t stream, const uint32_t *tree_of, uint32_t ntrees, uint64_t *desc, uint8_t *status, size_t m) {
+    hipLaunchKernelGGL(k_trees_prep, dim3((unsigned)((m + RS_PREP_BLOCK - 1) / RS_PREP_BLOCK)), dim3(RS_PREP_BLOCK), 0, stream, tree_of, ntrees, desc, status, m);
+    return hipGetLastError();
+}
+
+hipError_t rs_launch_trees(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTrees &trees, uint32_t ntrees, uint32_t iters, size_t m,
+                           const RsOut &out, char *work) {
+    if (m == 0) return hipSuccess;
+    const RsPrepArgs a{spots, out.status, (uint64_t *)work, m};
+    hipLaunchKernelGGL(k_rs_prep, dim3((unsigned)((m + RS_PREP_BLOCK - 1) / RS_PREP_BLOCK)), dim3(RS_PREP_BLOCK), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = trees_prep_launch(stream, trees.tree_of, ntrees, (uint64_t *)work, out.status, m);
+    if (e != hipSuccess || !(out.strategy || out.value || out.br)) return e;   // (status alone: the preparation kernel has written it)
+    hipLaunchKernelGGL(k_trees_river_solve, dim3(rs_grid(m)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, spots, out,
+                       work + rs_desc_bytes(m), iters, (uint32_t)m);
     return hipGetLastError();
 }
 

@@ -60,4 +60,18 @@ constexpr size_t rs_work_bytes(size_t m, uint32_t n, bool solve) { return rs_des
 hipError_t rs_launch(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTree &tree, uint32_t iters, size_t m, const RsOut &out,
                      char *work);
 
+// ---- a tree per spot (include/pokerl_hip.h "River and turn solvers: a tree per spot")
+constexpr uint32_t RS_MAX_TREES = PK_RS_MAX_TREES;
+struct RsTrees {
+    const RsTree *trees;       // [ntrees] packed trees, DEVICE memory
+    const uint32_t *tree_of;   // [m], device memory
+    uint32_t nmax, Dmax;       // the largest n and D over the call's trees: a workgroup's slice, the row stride of `strategy`
+};
+constexpr size_t rs_trees_bytes(uint32_t ntrees) { return ((size_t)ntrees * sizeof(RsTree) + 255) & ~(size_t)255; }
+// k_trees_prep on the m descriptors k_rs_prep or k_ts_prep has written (the turn solver's launch calls it too)
+hipError_t trees_prep_launch(hipStream_t stream, const uint32_t *tree_of, uint32_t ntrees, uint64_t *desc, uint8_t *status, size_t m);
+// rs_launch's launches with k_trees_prep between them and k_trees_river_solve; `work` as rs_work_bytes(m, trees.nmax, solve) sizes it.
+hipError_t rs_launch_trees(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTrees &trees, uint32_t ntrees, uint32_t iters, size_t m,
+                           const RsOut &out, char *work);
+
 }  // namespace pk

@@ -15,6 +15,10 @@
 //                   the turn-level nodes.  A turn-level fold needs no order: the total minus the two per-card sums plus the own reach.
 //                   Regrets and accumulators of river-level nodes are kept per card; values, reaches and probabilities of river-level
 //                   nodes are rewritten by every card's pass.  The final passes run in the same launch.
+//   k_trees_turn_solve   the same body (ts_solve_body<PER_SPOT>) for a call in which every spot names its tree: behind
+//                   k_ts_prep comes k_trees_prep (pk_river_solver.hip); a spot stages trees[tree_of[spot]] (a refused one tree 0) into LDS at its top and lays
+//                   the workgroup's slice -- sized for the call's largest nt and nr -- out for its own; `strategy` and `river_strategy`
+//                   have the call's row strides, the rows at or past the spot's own counts are written 0.
 // Ordinary vector stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_turn_solver_host.py reads the code object).
 #include <hip/hip_runtime.h>
 
@@ -72,9 +76,12 @@ struct TsLevel {
 
 }  // namespace
 
-// registers: one workgroup per CU is two waves per SIMD
-__global__ void __launch_bounds__(RS_BLOCK, 2) k_turn_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, TsTree tree, TsSpots spots,
-                                                            TsOut out, char *ws, uint32_t iters, uint32_t m) {
+// The solver's body.  PER_SPOT = false: `tree` is the call's one tree (the kernel's argument), staged once per workgroup.  PER_SPOT = true:
+// `tree` is the call's array of packed trees in device memory, and a spot stages trees[tree_of[spot]] (a refused one tree 0) -- after the barrier at the top
+// of the spot, which the last use of `tr` by the spot before lies behind; ntmax, nrmax, Dtmax and Drmax are the call's largest.
+template <bool PER_SPOT>
+static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, const TsTree *tree, const TsTrees &mx,
+                                                     const TsSpots &spots, const TsOut &out, char *ws, uint32_t iters, uint32_t m) {
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     __shared__ uint64_t slot[RS_SLOTS];               // key << 11 | turn slot, sorted once per spot and card; all ones = no holding.  Between
                                                       // the sorts the same memory holds rs and posof, or a turn-level fold's reaches
@@ -88,30 +95,42 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_turn_solve(const uint32_t *__re
     static_assert(RS_SORTED * 8 + TS_TURN * 2 <= RS_SLOTS * 8 && TS_TURN <= RS_SLOTS && RS_PREFIX >= 64, "rs and posof, or a fold's reaches, fit the sort slots");
     stage_eval7_tab<RS_BLOCK>(T, tab);
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
-    for (uint32_t w = tid; w < (uint32_t)(sizeof(TsTree) / 4); w += RS_BLOCK)
-        reinterpret_cast<uint32_t *>(&tr)[PK_IDX(w, sizeof(TsTree) / 4, "tree")] = reinterpret_cast<const uint32_t *>(&tree)[w];
-    __syncthreads();
-    const uint32_t n = uniform(tr.n), pot = uniform(tr.pot), nt = uniform(tr.nt), nr = uniform(tr.nr);
-    uint32_t Dt = 0, Dr = 0;
-    for (uint32_t v = 0; v < n; ++v) {
-        const bool dec = tr.kind[PK_IDX(v, TS_MAX_NODES, "kind")] <= RS_P1, riv = tr.river[PK_IDX(v, TS_MAX_NODES, "river")] != 0;
-        Dt += (dec && !riv) ? 1u : 0u;
-        Dr += (dec && riv) ? 1u : 0u;
-    }
-    Dt = uniform(Dt); Dr = uniform(Dr);
-    // the workgroup's slice of the work space (pk_turn_solver.hpp): 64-bit arrays first
-    char *const base = ws + (size_t)blockIdx.x * ts_group_bytes(nt, nr);
-    const size_t tplane = (size_t)nt * TS_TURN, rplane = (size_t)nr * RS_SORTED;
-    int64_t *const Rt = reinterpret_cast<int64_t *>(base), *const At = Rt + tplane, *const U0t = At + tplane, *const U1t = U0t + tplane;
-    uint64_t *const RRt = reinterpret_cast<uint64_t *>(U1t + tplane);
-    int64_t *const Rr = reinterpret_cast<int64_t *>(RRt + tplane), *const Ar = Rr + rplane * TS_CARDS;         // [card][river node][position]
-    int64_t *const U0r = Ar + rplane * TS_CARDS, *const U1r = U0r + rplane;
-    uint64_t *const RRr = reinterpret_cast<uint64_t *>(U1r + rplane);
-    uint32_t *const SGt = reinterpret_cast<uint32_t *>(RRr + rplane), *const SGr = SGt + tplane;
-    uint32_t *const bounds = SGr + rplane;                                       // [card][position] lb | ub << 16
-    uint16_t *const slotof = reinterpret_cast<uint16_t *>(bounds + (size_t)TS_CARDS * RS_SORTED);              // [card][position] -> turn slot
-    uint16_t *const posofg = slotof + (size_t)TS_CARDS * RS_SORTED;             // [card][turn slot] -> position
-    const TsLevel Lt{Rt, At, U0t, U1t, RRt, SGt, (uint32_t)TS_TURN, 0u};
+    uint32_t n = 0, pot = 0, nt = 0, nr = 0, Dt = 0, Dr = 0;
+    size_t rplane = 0;
+    int64_t *Rt = nullptr, *At = nullptr, *U0t = nullptr, *U1t = nullptr, *Rr = nullptr, *Ar = nullptr, *U0r = nullptr, *U1r = nullptr;
+    uint64_t *RRt = nullptr, *RRr = nullptr;
+    uint32_t *SGt = nullptr, *SGr = nullptr, *bounds = nullptr;
+    uint16_t *slotof = nullptr, *posofg = nullptr;
+    TsLevel Lt{};
+    // A tree into LDS (every lane of the workgroup comes here), and the workgroup's slice of the work space laid out for it
+    auto stage = [&](const TsTree *src) {
+        for (uint32_t w = tid; w < (uint32_t)(sizeof(TsTree) / 4); w += RS_BLOCK)
+            reinterpret_cast<uint32_t *>(&tr)[PK_IDX(w, sizeof(TsTree) / 4, "tree")] = reinterpret_cast<const uint32_t *>(src)[w];
+        __syncthreads();
+        n = uniform(tr.n); pot = uniform(tr.pot); nt = uniform(tr.nt); nr = uniform(tr.nr);
+        uint32_t dt = 0, dr = 0;
+        for (uint32_t v = 0; v < n; ++v) {
+            const bool dec = tr.kind[PK_IDX(v, TS_MAX_NODES, "kind")] <= RS_P1, riv = tr.river[PK_IDX(v, TS_MAX_NODES, "river")] != 0;
+            dt += (dec && !riv) ? 1u : 0u;
+            dr += (dec && riv) ? 1u : 0u;
+        }
+        Dt = uniform(dt); Dr = uniform(dr);
+        // the workgroup's slice of the work space (pk_turn_solver.hpp): 64-bit arrays first
+        char *const base = ws + (size_t)blockIdx.x * (PER_SPOT ? ts_group_bytes(mx.ntmax, mx.nrmax) : ts_group_bytes(nt, nr));
+        const size_t tplane = (size_t)nt * TS_TURN;
+        rplane = (size_t)nr * RS_SORTED;
+        Rt = reinterpret_cast<int64_t *>(base); At = Rt + tplane; U0t = At + tplane; U1t = U0t + tplane;
+        RRt = reinterpret_cast<uint64_t *>(U1t + tplane);
+        Rr = reinterpret_cast<int64_t *>(RRt + tplane); Ar = Rr + rplane * TS_CARDS;                         // [card][river node][position]
+        U0r = Ar + rplane * TS_CARDS; U1r = U0r + rplane;
+        RRr = reinterpret_cast<uint64_t *>(U1r + rplane);
+        SGt = reinterpret_cast<uint32_t *>(RRr + rplane); SGr = SGt + tplane;
+        bounds = SGr + rplane;                                                   // [card][position] lb | ub << 16
+        slotof = reinterpret_cast<uint16_t *>(bounds + (size_t)TS_CARDS * RS_SORTED);                          // [card][position] -> turn slot
+        posofg = slotof + (size_t)TS_CARDS * RS_SORTED;                         // [card][turn slot] -> position
+        Lt = TsLevel{Rt, At, U0t, U1t, RRt, SGt, (uint32_t)TS_TURN, 0u};
+    };
+    if constexpr (!PER_SPOT) stage(tree);
     auto idx = [&](uint32_t node) -> uint32_t { return uniform((uint32_t)tr.idx[PK_IDX(node, TS_MAX_NODES, "idx")]); };
     // where a node's entries begin in its level's arrays (wave-uniform: asked outside the code that depends on the lane), and entry i there
     auto row_of = [&](const TsLevel &L, uint32_t node) -> size_t { return (size_t)idx(node) * L.stride; };
@@ -135,6 +154,13 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_turn_solve(const uint32_t *__re
         const bool good = ((uint32_t)meta & 1u) != 0u;
         const uint64_t avail = good ? uniform(d[1]) : 0ull;     // (a refused spot: no holding is valid, every output is 0)
         const uint32_t P = (uint32_t)(meta >> 56);
+        if constexpr (PER_SPOT) {
+            // (good: k_trees_prep has seen tree_of[spot] < ntrees.  A refused spot stages tree 0, which always exists, and uses none of it:
+            // staging on every path keeps the tree's counts and the slice's pointers plain values of the spot, not merges with the spot before)
+            stage(tree + (good ? PK_IDX(uniform(mx.tree_of[spot]), RS_MAX_TREES, "tree_of") : 0u));
+            if (!good) { Dt = 0; Dr = 0; }
+        }
+        const uint32_t DtS = PER_SPOT ? mx.Dtmax : Dt, DrS = PER_SPOT ? mx.Drmax : Dr;               // the row strides of the strategies
         // ---- zeros: every output at the holdings that are not in the pool, by the lanes of the fixed index h = tid + 512 j
         for (uint32_t h = tid; h < (uint32_t)RS_HOLDINGS; h += RS_BLOCK) {
             uint32_t ca = 0, cb = 1;
@@ -145,7 +171,7 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_turn_solve(const uint32_t *__re
                 if (out.br) out.br[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
             }
             if (out.strategy)
-                for (uint32_t r = 0; r < Dt * 4u; ++r) out.strategy[((size_t)spot * Dt * 4 + r) * RS_HOLDINGS + h] = 0;
+                for (uint32_t r = 0; r < DtS * 4u; ++r) out.strategy[((size_t)spot * DtS * 4 + r) * RS_HOLDINGS + h] = 0;
         }
         // ... and of river_strategy every (card, holding) no pass writes: the card or the holding is not in the pool, or the holding has the card
         if (out.river_strategy)
@@ -154,9 +180,28 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_turn_solve(const uint32_t *__re
                 uint32_t ca = 0, cb = 1;
                 unpair(h, ca, cb);
                 if (((avail >> ca) & (avail >> cb) & (avail >> k) & 1ull) && k != ca && k != cb) continue;
-                for (uint32_t r = 0; r < Dr; ++r)
-                    for (uint32_t a = 0; a < 4u; ++a) out.river_strategy[((((size_t)spot * Dr + r) * 52 + k) * 4 + a) * RS_HOLDINGS + h] = 0;
+                for (uint32_t r = 0; r < DrS; ++r)
+                    for (uint32_t a = 0; a < 4u; ++a) out.river_strategy[((((size_t)spot * DrS + r) * 52 + k) * 4 + a) * RS_HOLDINGS + h] = 0;
             }
+        // ... and, where the call's strides are wider than the spot's tree, the rows past its own at what the passes write
+        if constexpr (PER_SPOT) {
+            if (out.strategy && Dt < DtS)
+                for (uint32_t h = tid; h < (uint32_t)RS_HOLDINGS; h += RS_BLOCK) {
+                    uint32_t ca = 0, cb = 1;
+                    unpair(h, ca, cb);
+                    if (!((avail >> ca) & (avail >> cb) & 1ull)) continue;
+                    for (uint32_t r = Dt * 4u; r < DtS * 4u; ++r) out.strategy[((size_t)spot * DtS * 4 + r) * RS_HOLDINGS + h] = 0;
+                }
+            if (out.river_strategy && Dr < DrS)
+                for (uint32_t e = tid; e < 52u * (uint32_t)RS_HOLDINGS; e += RS_BLOCK) {
+                    const uint32_t k = e / (uint32_t)RS_HOLDINGS, h = e - k * (uint32_t)RS_HOLDINGS;
+                    uint32_t ca = 0, cb = 1;
+                    unpair(h, ca, cb);
+                    if (!(((avail >> ca) & (avail >> cb) & (avail >> k) & 1ull) && k != ca && k != cb)) continue;
+                    for (uint32_t r = Dr; r < DrS; ++r)
+                        for (uint32_t a = 0; a < 4u; ++a) out.river_strategy[((((size_t)spot * DrS + r) * 52 + k) * 4 + a) * RS_HOLDINGS + h] = 0;
+                }
+        }
         if (!good) continue;
         fill_pool(pool, canon, avail, tid);
         const uint32_t nT = tri(P), nh = tri(P - 1u), K = P - 4u;
@@ -550,8 +595,8 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_turn_solve(const uint32_t *__re
                 uint16_t *o = nullptr;
                 if (river) {
                     if (out.river_strategy)
-                        o = out.river_strategy + ((((size_t)spot * Dr + row) * 52 + canon[PK_IDX(cs, 64, "canon")]) * 4) * RS_HOLDINGS + fixed(slotof[tab_at(cs, i)]);
-                } else if (out.strategy) o = out.strategy + (((size_t)spot * Dt + row) * 4) * RS_HOLDINGS + gh[j];
+                        o = out.river_strategy + ((((size_t)spot * DrS + row) * 52 + canon[PK_IDX(cs, 64, "canon")]) * 4) * RS_HOLDINGS + fixed(slotof[tab_at(cs, i)]);
+                } else if (out.strategy) o = out.strategy + (((size_t)spot * DtS + row) * 4) * RS_HOLDINGS + gh[j];
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     if ((uint32_t)a < nact) L.SG[at(L, cr[a], i)] = sig[a];
@@ -609,6 +654,16 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_turn_solve(const uint32_t *__re
     }
 }
 
+// registers: one workgroup per CU is two waves per SIMD
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_turn_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, TsTree tree, TsSpots spots,
+                                                            TsOut out, char *ws, uint32_t iters, uint32_t m) {
+    ts_solve_body<false>(tab, desc, &tree, TsTrees{}, spots, out, ws, iters, m);
+}
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_trees_turn_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, TsTrees trees, TsSpots spots,
+                                                                  TsOut out, char *ws, uint32_t iters, uint32_t m) {
+    ts_solve_body<true>(tab, desc, trees.trees, trees, spots, out, ws, iters, m);
+}
+
 namespace pk {
 
 hipError_t ts_launch(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTree &tree, uint32_t iters, size_t m, const TsOut &out,
@@ -620,6 +675,19 @@ hipError_t ts_launch(hipStream_t stream, const uint32_t *tab, const TsSpots &spo
     if (e != hipSuccess || !(out.strategy || out.river_strategy || out.value || out.br)) return e;   // (status alone: the preparation kernel has written it)
     hipLaunchKernelGGL(k_turn_solve, dim3(ts_grid(m, tree.nt, tree.nr)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, tree, spots, out,
                        work + rs_desc_bytes(m), iters, (uint32_t)m);
+    return hipGetLastError();
+}
+
+hipError_t ts_launch_trees(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTrees &trees, uint32_t ntrees, uint32_t iters, size_t m,
+                           const TsOut &out, char *work) {
+    if (m == 0) return hipSuccess;
+    const TsPrepArgs a{spots, out.status, (uint64_t *)work, m};
+    hipLaunchKernelGGL(k_ts_prep, dim3((unsigned)((m + TS_PREP_BLOCK - 1) / TS_PREP_BLOCK)), dim3(TS_PREP_BLOCK), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = trees_prep_launch(stream, trees.tree_of, ntrees, (uint64_t *)work, out.status, m);
+    if (e != hipSuccess || !(out.strategy || out.river_strategy || out.value || out.br)) return e;   // (status alone: the preparation kernels have written it)
+    hipLaunchKernelGGL(k_trees_turn_solve, dim3(ts_grid(m, trees.ntmax, trees.nrmax)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, spots,
+                       out, work + rs_desc_bytes(m), iters, (uint32_t)m);
     return hipGetLastError();
 }
 

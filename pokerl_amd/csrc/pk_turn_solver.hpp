@@ -64,4 +64,16 @@ static_assert(ts_group_bytes(1, TS_MAX_NODES - 1) * 16 < TS_WORK_MAX, "the large
 hipError_t ts_launch(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTree &tree, uint32_t iters, size_t m, const TsOut &out,
                      char *work);
 
+// ---- a tree per spot (include/pokerl_hip.h "River and turn solvers: a tree per spot")
+struct TsTrees {
+    const TsTree *trees;               // [ntrees] packed trees, DEVICE memory
+    const uint32_t *tree_of;           // [m], device memory
+    uint32_t ntmax, nrmax;             // the largest nt and nr over the call's trees: a workgroup's slice and the grid
+    uint32_t Dtmax, Drmax;             // the largest D_t and D_r: the row strides of `strategy` and `river_strategy`
+};
+constexpr size_t ts_trees_bytes(uint32_t ntrees) { return ((size_t)ntrees * sizeof(TsTree) + 255) & ~(size_t)255; }
+// ts_launch's launches with k_trees_prep between them and k_trees_turn_solve; `work` as ts_work_bytes(m, trees.ntmax, trees.nrmax, solve) sizes it.
+hipError_t ts_launch_trees(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTrees &trees, uint32_t ntrees, uint32_t iters, size_t m,
+                           const TsOut &out, char *work);
+
 }  // namespace pk

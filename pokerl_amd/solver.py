@@ -2,7 +2,10 @@
 over a caller-supplied betting tree, one subgame per workgroup on the device, in integers -- the same call gives the same bytes whatever
 the grid.  river_tree builds a tree on the host; solve_river / solve_river_batch / solve_river_d run it.
 The turn solver (pk_solve_turn; "Turn solver") is the same one street earlier, on a four-card board with the river
-card as a chance node: turn_tree, solve_turn / solve_turn_batch / solve_turn_d, at the end of this module."""
+card as a chance node: turn_tree, solve_turn / solve_turn_batch / solve_turn_d, at the end of this module.
+A tree per spot (pk_solve_river_trees / pk_solve_turn_trees; "River and turn solvers: a tree per spot"): the batch
+and _d functions also take a SEQUENCE of trees with tree_of, the index of each spot's tree; river_trees / turn_trees build both from
+per-spot pots and stacks."""
 import math
 
 import numpy as np
@@ -126,13 +129,20 @@ class RiverSolution:
     unused action slots and invalid holdings 0; a valid holding of weight 0, like any holding that never reached a node, gets the uniform
     row), value and br int64 [2, 1326] (the counterfactual value of every holding under `strategy`, and against it with the holder
     playing a best response; half-chips times the opponent's reach, which starts at weight << 4), status (PK_EQ_* bits).  A batch has a
-    leading [m]."""
+    leading [m].  A batch solved with a tree per spot has tree = None, trees and tree_of instead, and strategy [m, Dmax, 4, 1326] (Dmax:
+    the most decision nodes of any tree passed); solution[i] is an ordinary single solution with tree trees[tree_of[i]] and the strategy
+    cut to that tree's own rows (no tree and no row where tree_of[i] names none: status PK_EQ_BAD_TREE)."""
 
-    def __init__(self, tree, ranges, strategy, value, br, status, valid):
+    def __init__(self, tree, ranges, strategy, value, br, status, valid, trees=None, tree_of=None):
         self.tree, self.ranges, self.strategy, self.value, self.br, self.status, self.valid = tree, ranges, strategy, value, br, status, valid
+        self.trees, self.tree_of = trees, tree_of
 
     def __getitem__(self, i):
-        return RiverSolution(self.tree, self.ranges[i], self.strategy[i], self.value[i], self.br[i], self.status[i], self.valid[i])
+        tree, strategy = self.tree, self.strategy[i]
+        if self.trees is not None:
+            tree = _spot_tree(self.trees, self.tree_of, i)
+            strategy = strategy[:len(tree.decision_nodes) if tree is not None else 0]
+        return RiverSolution(tree, self.ranges[i], strategy, self.value[i], self.br[i], self.status[i], self.valid[i])
 
     def _pair_weight(self):
         w = self.ranges.astype(np.int64) * self.valid
@@ -179,10 +189,72 @@ def _tree_args(tree):
     return (int(tree.n), L.ptr(tree.kind), L.ptr(tree.child), L.ptr(tree.put), int(tree.pot))
 
 
-def solve_river_batch(board, ranges, tree, iters, dead=None, device=0):
+def _spot_tree(trees, tree_of, i):
+    k = int(tree_of[int(i)])
+    return trees[k] if k < len(trees) else None
+
+
+class _TreeRows:
+    """A sequence of trees as the tree-per-spot calls take it: tree k is row k of n uint32 [K], kind uint8 [K, rows], child uint8
+    [K, rows, 4], put uint32 [K, rows, 2] and pot uint32 [K] (rows = 64 for river trees, 128 for turn trees; the entries past n[k] are
+    ignored by the library)."""
+
+    def __init__(self, trees, rows):
+        self.trees = list(trees)
+        K = len(self.trees)
+        if not 1 <= K <= L.RS_MAX_TREES:
+            raise ValueError("between 1 and %d trees" % L.RS_MAX_TREES)
+        if any(t.n > rows for t in self.trees):
+            raise ValueError("a tree has more than %d nodes" % rows)
+        self.n = np.array([t.n for t in self.trees], np.uint32)
+        self.pot = np.array([t.pot for t in self.trees], np.uint32)
+        self.kind, self.child, self.put = np.zeros((K, rows), np.uint8), np.full((K, rows, 4), NO_CHILD, np.uint8), np.zeros((K, rows, 2), np.uint32)
+        for k, t in enumerate(self.trees):
+            self.kind[k, :t.n], self.child[k, :t.n], self.put[k, :t.n] = t.kind, t.child, t.put
+
+    def args(self):
+        return (len(self.trees), L.ptr(self.n), L.ptr(self.kind), L.ptr(self.child), L.ptr(self.put), L.ptr(self.pot))
+
+
+def _tree_of(tree_of, ntrees, m):
+    """tree_of as uint32 [m]; None: spot i uses tree i, which needs exactly m trees"""
+    if tree_of is None:
+        if ntrees != m:
+            raise ValueError("tree_of=None needs one tree per spot: %d trees, %d spots" % (ntrees, m))
+        return np.arange(m, dtype=np.uint32)
+    tree_of = np.asarray(tree_of)
+    if tree_of.shape != (m,) or tree_of.dtype.kind not in "iu":
+        raise ValueError("tree_of must be an integer array of shape [m]")
+    if m and (int(tree_of.min()) < 0 or int(tree_of.max()) > 0xFFFFFFFF):      # (no wrap-around in the cast: such an index names no tree)
+        raise ValueError("tree_of must lie in 0 .. 2^32 - 1")
+    return np.ascontiguousarray(tree_of, np.uint32)
+
+
+def _trees_by_chips(pots, stacks, build):
+    pots, stacks = np.asarray(pots).reshape(-1), np.asarray(stacks).reshape(-1)
+    if pots.shape != stacks.shape:
+        raise ValueError("pots and stacks must have the same shape [m]")
+    index, trees, tree_of = {}, [], np.zeros(pots.shape[0], np.uint32)
+    for i, key in enumerate(zip(pots.tolist(), stacks.tolist())):
+        if key not in index:
+            index[key] = len(trees)
+            trees.append(build(int(key[0]), int(key[1])))
+        tree_of[i] = index[key]
+    return trees, tree_of
+
+
+def river_trees(pots, stacks, bet_fractions=(0.5, 1.0), max_raises=2):
+    """(trees, tree_of) for spots of per-spot chips: pots and stacks are integer arrays [m]; one river_tree per DISTINCT (pot, stack)
+    pair, in the order the pairs first appear, and tree_of uint32 [m] with the index of each spot's tree -- what solve_river_batch takes."""
+    return _trees_by_chips(pots, stacks, lambda pot, stack: river_tree(pot, stack, bet_fractions, max_raises))
+
+
+def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=None):
     """pk_solve_river on host arrays: board uint8 [m, 5] Card.value, ranges uint16 [m, 2, 1326] over holding_index, one tree for the call,
     dead uint64 [m] masks over canonical card indices (None: none) -> RiverSolution with a leading [m].  A bad spot is reported through
-    its status with all-zero outputs; the others are unaffected."""
+    its status with all-zero outputs; the others are unaffected.
+    tree may also be a SEQUENCE of trees (pk_solve_river_trees): spot i is solved with tree[tree_of[i]], tree_of an integer array [m]
+    (None: spot i uses tree i, which needs m trees); every output of spot i is what the call with that one tree gives for it."""
     board = np.ascontiguousarray(board, np.uint8)
     if board.ndim != 2 or board.shape[1] != 5:
         raise ValueError("board must have shape [m, 5]")
@@ -194,19 +266,39 @@ def solve_river_batch(board, ranges, tree, iters, dead=None, device=0):
         dead = np.ascontiguousarray(dead, np.uint64)
         if dead.shape != (m,):
             raise ValueError("dead must have shape [m]")
-    D = len(tree.decision_nodes)
-    strategy = np.zeros((m, D, 4, L.EQ_HOLDINGS), np.uint16)
     value, br = np.zeros((m, 2, L.EQ_HOLDINGS), np.int64), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64)
     status = np.zeros(m, np.uint8)
-    L.check(L.lib().pk_solve_river(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *_tree_args(tree), int(iters), L.ptr(strategy),
-                                   L.ptr(value), L.ptr(br), L.ptr(status)))
+    if isinstance(tree, RiverTree):
+        if tree_of is not None:
+            raise ValueError("tree_of needs a sequence of trees")
+        strategy = np.zeros((m, len(tree.decision_nodes), 4, L.EQ_HOLDINGS), np.uint16)
+        L.check(L.lib().pk_solve_river(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *_tree_args(tree), int(iters), L.ptr(strategy),
+                                       L.ptr(value), L.ptr(br), L.ptr(status)))
+        trees = None
+    else:
+        rows = _TreeRows(tree, MAX_NODES)
+        trees, tree, tree_of = rows.trees, None, _tree_of(tree_of, len(rows.trees), m)
+        strategy = np.zeros((m, max(len(t.decision_nodes) for t in trees), 4, L.EQ_HOLDINGS), np.uint16)
+        L.check(L.lib().pk_solve_river_trees(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *rows.args(), L.ptr(tree_of), int(iters),
+                                             L.ptr(strategy), L.ptr(value), L.ptr(br), L.ptr(status)))
     valid = rvr_valid_holdings(board, np.full(m, 5, np.uint8), dead) & (status == 0)[:, None]
-    return RiverSolution(tree, ranges, strategy, value, br, status, valid)
+    return RiverSolution(tree, ranges, strategy, value, br, status, valid, trees, tree_of)
 
 
-def solve_river_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None, value_d=None, br_d=None, status_d=None, device=0, stream=None):
+def solve_river_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None, value_d=None, br_d=None, status_d=None, device=0, stream=None,
+                  tree_of=None):
     """pk_solve_river_d: the same on device-resident buffers (device pointers as ints / c_void_p; the tree stays a host RiverTree; dead_d and
-    the outputs may be None), asynchronous on `stream`."""
+    the outputs may be None), asynchronous on `stream`.  With a SEQUENCE of trees (pk_solve_river_trees_d) tree_of is the DEVICE pointer of
+    uint32 [m] and strategy_d holds [m, Dmax, 4, 1326], Dmax the most decision nodes of any tree passed; the trees are packed and queued
+    for upload before the call returns."""
+    if not isinstance(tree, RiverTree):
+        if tree_of is None:
+            raise ValueError("a sequence of trees needs tree_of, the device pointer of uint32 [m]")
+        L.check(L.lib().pk_solve_river_trees_d(int(device), int(m), board_d, dead_d, ranges_d, *_TreeRows(tree, MAX_NODES).args(), tree_of, int(iters),
+                                               strategy_d, value_d, br_d, status_d, stream))
+        return
+    if tree_of is not None:
+        raise ValueError("tree_of needs a sequence of trees")
     L.check(L.lib().pk_solve_river_d(int(device), int(m), board_d, dead_d, ranges_d, *_tree_args(tree), int(iters), strategy_d, value_d, br_d,
                                      status_d, stream))
 
@@ -284,15 +376,23 @@ class TurnSolution:
     """What pk_solve_turn returns for one spot or a batch: strategy uint16 [D_t, 4, 1326], river_strategy uint16 [D_r, 52, 4, 1326] (None
     unless asked for; indexed by the river card's canonical index, 0 for cards outside the pool and holdings with the card), value and br
     int64 [2, 1326] (half-chips times the opponent's reach, which starts at weight << 1, times the P - 4 river cards), status, and pool
-    (P).  A batch has a leading [m]."""
+    (P).  A batch has a leading [m].  A batch solved with a tree per spot has tree = None, trees and tree_of instead, and the strategies
+    have the rows of the largest tree passed; solution[i] is an ordinary single solution with tree trees[tree_of[i]] and both strategies
+    cut to that tree's own rows."""
 
-    def __init__(self, tree, ranges, strategy, river_strategy, value, br, status, valid, pool):
+    def __init__(self, tree, ranges, strategy, river_strategy, value, br, status, valid, pool, trees=None, tree_of=None):
         self.tree, self.ranges, self.strategy, self.river_strategy = tree, ranges, strategy, river_strategy
         self.value, self.br, self.status, self.valid, self.pool = value, br, status, valid, pool
+        self.trees, self.tree_of = trees, tree_of
 
     def __getitem__(self, i):
-        return TurnSolution(self.tree, self.ranges[i], self.strategy[i], None if self.river_strategy is None else self.river_strategy[i],
-                            self.value[i], self.br[i], self.status[i], self.valid[i], self.pool[i])
+        tree, strategy, rstrat = self.tree, self.strategy[i], None if self.river_strategy is None else self.river_strategy[i]
+        if self.trees is not None:
+            tree = _spot_tree(self.trees, self.tree_of, i)
+            strategy = strategy[:len(tree.decision_nodes) if tree is not None else 0]
+            if rstrat is not None:
+                rstrat = rstrat[:len(tree.river_decision_nodes) if tree is not None else 0]
+        return TurnSolution(tree, self.ranges[i], strategy, rstrat, self.value[i], self.br[i], self.status[i], self.valid[i], self.pool[i])
 
     _pair_weight = RiverSolution._pair_weight
     _one = RiverSolution._one
@@ -339,6 +439,11 @@ class TurnSolution:
         return "TurnSolution(status=%r)" % (self.status,)
 
 
+def turn_trees(pots, stacks, bet_fractions=(0.5, 1.0), max_raises=2, river_bet_fractions=None, river_max_raises=None):
+    """(trees, tree_of) for spots of per-spot chips, as river_trees: one turn_tree per distinct (pot, stack) pair."""
+    return _trees_by_chips(pots, stacks, lambda pot, stack: turn_tree(pot, stack, bet_fractions, max_raises, river_bet_fractions, river_max_raises))
+
+
 def _turn_levels(tree):
     nr = int(np.count_nonzero(tree.river_level))
     return tree.n - nr, nr
@@ -346,15 +451,21 @@ def _turn_levels(tree):
 
 def turn_grid(tree, m=None):
     """The number of workgroups a solve of `tree` uses (for m spots; None: for any m that large): min(m, 256, 4 GiB / the work space of
-    one workgroup).  No output depends on it."""
+    one workgroup).  No output depends on it.  A sequence of trees: the grid of a tree-per-spot call, whose workgroups are sized for the
+    most turn-level and the most river-level nodes of any tree."""
+    if not isinstance(tree, RiverTree):
+        levels = [_turn_levels(t) for t in tree]
+        nt, nr = max(a for a, _ in levels), max(b for _, b in levels)
+        return int(L.lib().pk_turn_grid(GRID_MAX if m is None else int(m), nt, nr))
     nt, nr = _turn_levels(tree)
     return int(L.lib().pk_turn_grid(GRID_MAX if m is None else int(m), nt, nr))
 
 
-def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False, device=0):
+def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False, device=0, tree_of=None):
     """pk_solve_turn on host arrays: board uint8 [m, 4] Card.value, ranges uint16 [m, 2, 1326] over holding_index, one TurnTree for the
     call, dead uint64 [m] masks over canonical card indices (None: none) -> TurnSolution with a leading [m].  river_strategy=True also
-    returns the river-level strategies (551 616 bytes per river-level decision node and spot)."""
+    returns the river-level strategies (551 616 bytes per river-level decision node and spot).
+    tree may also be a SEQUENCE of TurnTrees with tree_of (pk_solve_turn_trees), as solve_river_batch takes them."""
     board = np.ascontiguousarray(board, np.uint8)
     if board.ndim != 2 or board.shape[1] != 4:
         raise ValueError("board must have shape [m, 4]")
@@ -366,24 +477,43 @@ def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False
         dead = np.ascontiguousarray(dead, np.uint64)
         if dead.shape != (m,):
             raise ValueError("dead must have shape [m]")
-    Dt, Dr = len(tree.decision_nodes), len(tree.river_decision_nodes)
+    rows = None if isinstance(tree, RiverTree) else _TreeRows(tree, TURN_MAX_NODES)
+    if rows is None and tree_of is not None:
+        raise ValueError("tree_of needs a sequence of trees")
+    trees = None if rows is None else rows.trees
+    Dt = max(len(t.decision_nodes) for t in (trees or [tree]))
+    Dr = max(len(t.river_decision_nodes) for t in (trees or [tree]))
     strategy = np.zeros((m, Dt, 4, L.EQ_HOLDINGS), np.uint16)
     rstrat = np.zeros((m, Dr, 52, 4, L.EQ_HOLDINGS), np.uint16) if river_strategy else None
     value, br = np.zeros((m, 2, L.EQ_HOLDINGS), np.int64), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64)
     status = np.zeros(m, np.uint8)
-    L.check(L.lib().pk_solve_turn(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *_tree_args(tree), int(iters), L.ptr(strategy),
-                                  L.ptr(rstrat), L.ptr(value), L.ptr(br), L.ptr(status)))
+    if rows is None:
+        L.check(L.lib().pk_solve_turn(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *_tree_args(tree), int(iters), L.ptr(strategy),
+                                      L.ptr(rstrat), L.ptr(value), L.ptr(br), L.ptr(status)))
+    else:
+        tree, tree_of = None, _tree_of(tree_of, len(trees), m)
+        L.check(L.lib().pk_solve_turn_trees(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *rows.args(), L.ptr(tree_of), int(iters),
+                                            L.ptr(strategy), L.ptr(rstrat), L.ptr(value), L.ptr(br), L.ptr(status)))
     board5 = np.concatenate([board, np.zeros((m, 1), np.uint8)], axis=1)
     valid = rvr_valid_holdings(board5, np.full(m, 4, np.uint8), dead) & (status == 0)[:, None]
     pool = np.where(status == 0, valid.sum(axis=1), 0)
     pool = np.array([int(round((1 + math.sqrt(1 + 8 * int(x))) / 2)) if x else 0 for x in pool])      # C(P, 2) valid holdings -> P
-    return TurnSolution(tree, ranges, strategy, rstrat, value, br, status, valid, pool)
+    return TurnSolution(tree, ranges, strategy, rstrat, value, br, status, valid, pool, trees, tree_of)
 
 
 def solve_turn_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None, river_strategy_d=None, value_d=None, br_d=None, status_d=None,
-                 device=0, stream=None):
+                 device=0, stream=None, tree_of=None):
     """pk_solve_turn_d: the same on device-resident buffers (device pointers as ints / c_void_p; the tree stays a host TurnTree; dead_d and
-    the outputs may be None), asynchronous on `stream`."""
+    the outputs may be None), asynchronous on `stream`.  With a SEQUENCE of trees (pk_solve_turn_trees_d) tree_of is the DEVICE pointer of
+    uint32 [m], as solve_river_d takes it; the strategies have the rows of the largest tree passed."""
+    if not isinstance(tree, RiverTree):
+        if tree_of is None:
+            raise ValueError("a sequence of trees needs tree_of, the device pointer of uint32 [m]")
+        L.check(L.lib().pk_solve_turn_trees_d(int(device), int(m), board_d, dead_d, ranges_d, *_TreeRows(tree, TURN_MAX_NODES).args(), tree_of, int(iters),
+                                              strategy_d, river_strategy_d, value_d, br_d, status_d, stream))
+        return
+    if tree_of is not None:
+        raise ValueError("tree_of needs a sequence of trees")
     L.check(L.lib().pk_solve_turn_d(int(device), int(m), board_d, dead_d, ranges_d, *_tree_args(tree), int(iters), strategy_d, river_strategy_d,
                                     value_d, br_d, status_d, stream))
 

@@ -60,6 +60,7 @@ import hist_cluster_spec as CS          # noqa: E402
 import hist_spec as HS                  # noqa: E402
 import preflop_spec as PS               # noqa: E402
 import river_solver_spec as RVS         # noqa: E402
+import solver_trees_util as STU         # noqa: E402
 import turn_solver_spec as TSS          # noqa: E402
 import ranged_ev_spec as XS             # noqa: E402
 import rvr_spec as VS                   # noqa: E402
@@ -76,7 +77,8 @@ OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("w
            "cluster": ("centroids_out", "label", "dist", "inertia", "changed"),
            "herohist": ("hist", "void", "completions", "status"), "preflop": ("win", "tie"),
            "pfhero": ("agg", "win", "tie", "boards", "status"), "pfrvr": ("win", "tie", "tot"),
-           "riversolve": ("strategy", "value", "br", "status"), "turnsolve": ("strategy", "river_strategy", "value", "br", "status")}
+           "riversolve": ("strategy", "value", "br", "status"), "turnsolve": ("strategy", "river_strategy", "value", "br", "status"),
+           "rivertrees": ("strategy", "value", "br", "status"), "turntrees": ("strategy", "river_strategy", "value", "br", "status")}
 
 
 class Case:
@@ -1208,6 +1210,76 @@ def turn_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- a tree per spot
+def tree_rows(trees, rows):
+    """The trees as the tree-per-spot calls take them: tree k is row k of every array, `rows` nodes a row"""
+    K = len(trees)
+    kind, child, put = np.zeros((K, rows), np.uint8), np.full((K, rows, 4), 0xFF, np.uint8), np.zeros((K, rows, 2), np.uint32)
+    for k, t in enumerate(trees):
+        kind[k, :t.n], child[k, :t.n], put[k, :t.n] = t.kind, t.child, t.put
+    return {"ntrees": ("u32", [K]), "n": ("u32", [t.n for t in trees]), "pot": ("u32", [t.pot for t in trees]), "kind": ("u8", kind),
+            "child": ("u8", child), "put": ("u32", put)}
+
+
+def trees_case(name, street, pools, trees, tree_of, iters, seed, outputs=None, quick=True, edit=None):
+    """k_rs_prep / k_ts_prep + k_trees_prep + k_trees_river_solve / k_trees_turn_solve at a grid of 1 against the spec run ONE SPOT AT A
+    TIME with that spot's tree (tests/solver_trees_util.py); street: 5 (river) or 4 (turn) board cards."""
+    m = len(pools)
+    board, _, dead = board_spots(seed, [(street, p) for p in pools])
+    board = np.ascontiguousarray(board[:, :street])
+    rng = np.random.default_rng(seed + 1)
+    ranges = rng.integers(0, 65536, (m, 2, HOLDINGS)).astype(np.uint16)
+    for row in ranges.reshape(-1, HOLDINGS):
+        row[rng.integers(0, HOLDINGS, 200)] = 0
+        row[rng.integers(0, HOLDINGS, 100)] = 65535
+    if edit:
+        edit(board, dead)
+    tree_of = np.asarray(tree_of, np.uint32)
+    assert tree_of.shape == (m,)
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [1]), "iters": ("u32", [iters]), **tree_rows(trees, 64 if street == 5 else 128),
+              "tree_of": ("u32", tree_of), "board": ("u8", board), "dead": ("u64", dead), "ranges": ("u16", ranges)}
+
+    def expect():
+        r = (STU.river_expect if street == 5 else STU.turn_expect)(board, ranges, trees, tree_of, iters, dead)
+        return {k: (r[k].view(np.uint64) if k in ("value", "br") else r[k]) for k in OUTPUTS["rivertrees" if street == 5 else "turntrees"]}
+    return Case(name, "rivertrees" if street == 5 else "turntrees", arrays, expect, outputs, quick)
+
+
+def break_second_board(board, dead):
+    board[1, 1] = board[1, 0]
+
+
+def river_trees_cases():
+    """The river solver with a tree per spot (names rtrees-...), every case at a grid of 1: ONE workgroup takes the spots in turn, so a stale
+    tree, stale regrets or stale LDS of the spot before would show.  NOT part of all_cases()."""
+    from pokerl_amd.solver import river_tree
+    forced, four, chain = STU.forced_river_tree(), STU.four_action_river_tree(), STU.chain_river_tree()
+    small, default = river_tree(100, 50), river_tree(100, 400)
+    cs = [trees_case("rtrees-big-after-small-and-back", 5, (9, 7, 12, 6, 10, 8), [forced, default, four, chain], [0, 1, 0, 3, 2, 1], 2, 71),
+          trees_case("rtrees-refused-and-bad-tree-between", 5, (9, 8, 10, 7, 9, 6), [small, default], [1, 0, 2, 0, 0xFFFFFFFF, 1], 2, 72, edit=break_second_board),
+          trees_case("rtrees-one-tree-repeated", 5, (6, 17, 9), [small], [0, 0, 0], 3, 73),
+          trees_case("rtrees-unreferenced-tree-sets-the-stride", 5, (8, 11), [forced, chain, four], [0, 2], 2, 74),
+          trees_case("rtrees-pools-fall-trees-grow", 5, (33, 12, 5), [forced, small, default], [0, 1, 2], 1, 75),
+          trees_case("rtrees-no-strategy", 5, (7, 8), [default, forced], [0, 1], 2, 76, outputs=("value", "br", "status")),
+          trees_case("rtrees-status-only", 5, (9, 9, 9), [small, forced], [0, 1, 5], 1, 77, outputs=("status",), edit=break_second_board)]
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
+def turn_trees_cases():
+    """The turn solver with a tree per spot (names ttrees-...), every case at a grid of 1.  NOT part of all_cases()."""
+    from pokerl_amd.solver import turn_tree
+    allin, small, wide = STU.allin_turn_tree(), turn_tree(30, 20, (1.0,), 1), turn_tree(100, 400, (1.0,), 1)
+    cs = [trees_case("ttrees-big-after-small-and-back", 4, (7, 6, 8, 6, 9), [allin, wide, small], [0, 1, 0, 2, 1], 2, 81),
+          trees_case("ttrees-refused-and-bad-tree-between", 4, (8, 7, 9, 6, 7, 6), [small, allin], [1, 0, 2, 0, 0xFFFFFFFF, 1], 2, 82, edit=break_second_board),
+          trees_case("ttrees-one-tree-repeated", 4, (6, 10, 7), [small], [0, 0, 0], 2, 83),
+          trees_case("ttrees-unreferenced-tree-sets-the-strides", 4, (7, 8), [allin, wide], [0, 0], 1, 84),
+          trees_case("ttrees-no-river-strategy", 4, (9, 7), [wide, allin], [0, 1], 2, 85, outputs=("strategy", "value", "br", "status")),
+          trees_case("ttrees-status-only", 4, (9, 9, 9), [small, allin], [0, 1, 7], 1, 86, outputs=("status",), edit=break_second_board)]
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -1222,7 +1294,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() + river_trees_cases() + turn_trees_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

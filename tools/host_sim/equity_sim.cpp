@@ -9,7 +9,9 @@
 //   equity_sim <case file> <out file>
 // Case file: lines "name dtype count" (dtype u8 u16 u32 u64 i32) each followed by a line of `count` decimal values, and
 // "family <name>" / "outputs <name> ..." lines.  Out file: the same array format.
-// -DPK_ES_ONLY=1 .. 13: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist, preflop, rangedev, riversolve, turnsolve), so that a test can compile them side by side.
+// -DPK_ES_ONLY=1 .. 15: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist, preflop, rangedev, riversolve, turnsolve, rivertrees, turntrees), so that a test can compile them side by side.
+// The rivertrees / turntrees families (k_rs_prep / k_ts_prep, k_trees_prep, k_trees_river_solve / k_trees_turn_solve) take ntrees trees as rows of 64 / 128 nodes, as the
+// C ABI's tree-per-spot calls do, and tree_of per spot; the outputs have the call's row strides.  The work space is sized for the call's largest tree, as the library sizes it.
 // The turnsolve family (pk_turn_solver.hip: k_ts_prep, k_turn_solve) takes the tree as riversolve does; the driver derives nact, row, river and idx as the host check does.
 // The riversolve family (pk_river_solver.hip: k_rs_prep, k_river_solve) takes the tree's arrays as the C ABI does; the driver derives nact and row as the host check does.  Its
 // int64 outputs (value, br) travel as their bit patterns, dtype u64.
@@ -67,10 +69,10 @@
 #if PK_ES_HAS(10)
 #include "../../pokerl_amd/csrc/pk_preflop.hip"
 #endif
-#if PK_ES_HAS(12)
-#include "../../pokerl_amd/csrc/pk_river_solver.hip"
+#if PK_ES_HAS(12) || PK_ES_HAS(14) || PK_ES_HAS(13) || PK_ES_HAS(15)
+#include "../../pokerl_amd/csrc/pk_river_solver.hip"     // (the turn solver's tree-per-spot launch queues k_trees_prep)
 #endif
-#if PK_ES_HAS(13)
+#if PK_ES_HAS(13) || PK_ES_HAS(15)
 #include "../../pokerl_amd/csrc/pk_turn_solver.hip"
 #endif
 #include <chrono>
@@ -605,6 +607,117 @@ void run_preflop_rvr(Case &c) {
 }
 #endif
 
+#if PK_ES_HAS(12) || PK_ES_HAS(14)
+// nact and row as the host check derives them -> the number of decision nodes
+size_t pack_river_tree(RsTree &t, uint32_t n, uint32_t pot, const uint8_t *kind, const uint8_t *child, const uint32_t *put) {
+    t = RsTree{};
+    t.n = n; t.pot = pot;
+    size_t D = 0;
+    for (uint32_t v = 0; v < n; ++v) {
+        t.kind[v] = kind[v]; t.put[v][0] = put[v * 2]; t.put[v][1] = put[v * 2 + 1];
+        for (int a = 0; a < 4; ++a) { t.child[v][a] = child[v * 4 + a]; t.nact[v] += child[v * 4 + a] != 0xFF; }
+        if (kind[v] <= RS_P1) t.row[v] = (uint8_t)D++;
+    }
+    return D;
+}
+#endif
+
+#if PK_ES_HAS(13) || PK_ES_HAS(15)
+// nact, row, river and idx as the host check derives them; D[0] / D[1]: turn-level / river-level decision nodes
+void pack_turn_tree(TsTree &t, uint32_t n, uint32_t pot, const uint8_t *kind, const uint8_t *child, const uint32_t *put, size_t (&D)[2]) {
+    t = TsTree{};
+    t.n = n; t.pot = pot;
+    D[0] = D[1] = 0;
+    for (uint32_t v = 0; v < n; ++v) {
+        t.kind[v] = kind[v]; t.put[v][0] = put[v * 2]; t.put[v][1] = put[v * 2 + 1];
+        for (int a = 0; a < 4; ++a) {
+            const uint8_t ch = child[v * 4 + a];
+            t.child[v][a] = ch; t.nact[v] += ch != 0xFF;
+            if (ch != 0xFF && ch < n) t.river[ch] = t.river[v] || kind[v] == TS_CHANCE;
+        }
+        t.idx[v] = (uint8_t)(t.river[v] ? t.nr++ : t.nt++);
+        if (kind[v] <= RS_P1) t.row[v] = (uint8_t)D[t.river[v]]++;
+    }
+}
+#endif
+
+#if PK_ES_HAS(14)
+void run_river_trees(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const uint32_t ntrees = (uint32_t)c.num("ntrees"), iters = (uint32_t)c.num("iters");
+    if (ntrees < 1 || grid < 1) die("rivertrees: no tree, or no workgroup");
+    const uint32_t *n = c.need<uint32_t>("n", ntrees), *pot = c.need<uint32_t>("pot", ntrees), *tree_of = c.need<uint32_t>("tree_of", m);
+    const uint8_t *kind = c.need<uint8_t>("kind", (size_t)ntrees * RS_MAX_NODES), *child = c.need<uint8_t>("child", (size_t)ntrees * RS_MAX_NODES * 4);
+    const uint32_t *put = c.need<uint32_t>("put", (size_t)ntrees * RS_MAX_NODES * 2);
+    Work<RsTree> trees(ntrees);                                       // exactly ntrees: an index past them is ASan's to see
+    uint32_t nmax = 0;
+    size_t Dmax = 0;
+    for (uint32_t k = 0; k < ntrees; ++k) {
+        if (n[k] < 1 || n[k] > (uint32_t)RS_MAX_NODES) die("rivertrees: n outside 1 .. 64");
+        const size_t row = (size_t)k * RS_MAX_NODES;
+        Dmax = std::max(Dmax, pack_river_tree(trees.p[k], n[k], pot[k], kind + row, child + row * 4, put + row * 2));
+        nmax = std::max(nmax, n[k]);
+    }
+    const RsSpots spots{c.need<uint8_t>("board", m * 5), c.arr<uint64_t>("dead", m), c.need<uint16_t>("ranges", m * 2 * RS_HOLDINGS)};
+    RsOut out{};
+    out.strategy = c.output<uint16_t>("strategy", "u16", m * Dmax * 4 * RS_HOLDINGS);
+    out.value = (int64_t *)c.output<uint64_t>("value", "u64", m * 2 * RS_HOLDINGS);
+    out.br = (int64_t *)c.output<uint64_t>("br", "u64", m * 2 * RS_HOLDINGS);
+    out.status = c.output<uint8_t>("status", "u8", m);
+    Work<uint64_t> desc(m * RS_DESC_WORDS);
+    Work<char> ws((size_t)grid * rs_group_bytes(nmax));              // sized by the grid and the largest tree, as pk_solve_river_trees sizes it
+    const RsPrepArgs a{spots, out.status, desc.p, m};
+    pk_sim::launch(prep_grid(m, RS_PREP_BLOCK), RS_PREP_BLOCK, [&] { k_rs_prep(a); });
+    uint64_t *dw = desc.p;
+    uint8_t *st = out.status;
+    pk_sim::launch(prep_grid(m, RS_PREP_BLOCK), RS_PREP_BLOCK, [&] { k_trees_prep(tree_of, ntrees, dw, st, m); });
+    const uint64_t *dp = desc.p;
+    char *wp = ws.p;
+    const RsTrees tt{trees.p, tree_of, nmax, (uint32_t)Dmax};
+    if (out.strategy || out.value || out.br) pk_sim::launch(grid, RS_BLOCK, [&] { k_trees_river_solve(tab, dp, tt, spots, out, wp, iters, (uint32_t)m); });
+}
+#endif
+
+#if PK_ES_HAS(15)
+void run_turn_trees(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const uint32_t ntrees = (uint32_t)c.num("ntrees"), iters = (uint32_t)c.num("iters");
+    if (ntrees < 1 || grid < 1) die("turntrees: no tree, or no workgroup");
+    const uint32_t *n = c.need<uint32_t>("n", ntrees), *pot = c.need<uint32_t>("pot", ntrees), *tree_of = c.need<uint32_t>("tree_of", m);
+    const uint8_t *kind = c.need<uint8_t>("kind", (size_t)ntrees * TS_MAX_NODES), *child = c.need<uint8_t>("child", (size_t)ntrees * TS_MAX_NODES * 4);
+    const uint32_t *put = c.need<uint32_t>("put", (size_t)ntrees * TS_MAX_NODES * 2);
+    Work<TsTree> trees(ntrees);
+    TsTrees tt{trees.p, tree_of, 0, 0, 0, 0};
+    for (uint32_t k = 0; k < ntrees; ++k) {
+        if (n[k] < 1 || n[k] > (uint32_t)TS_MAX_NODES) die("turntrees: n outside 1 .. 128");
+        const size_t row = (size_t)k * TS_MAX_NODES;
+        size_t D[2];
+        pack_turn_tree(trees.p[k], n[k], pot[k], kind + row, child + row * 4, put + row * 2, D);
+        tt.ntmax = std::max(tt.ntmax, trees.p[k].nt); tt.nrmax = std::max(tt.nrmax, trees.p[k].nr);
+        tt.Dtmax = std::max(tt.Dtmax, (uint32_t)D[0]); tt.Drmax = std::max(tt.Drmax, (uint32_t)D[1]);
+    }
+    const TsSpots spots{c.need<uint8_t>("board", m * 4), c.arr<uint64_t>("dead", m), c.need<uint16_t>("ranges", m * 2 * RS_HOLDINGS)};
+    TsOut out{};
+    out.strategy = c.output<uint16_t>("strategy", "u16", m * tt.Dtmax * 4 * RS_HOLDINGS);
+    out.river_strategy = c.output<uint16_t>("river_strategy", "u16", m * tt.Drmax * 52 * 4 * RS_HOLDINGS);
+    out.value = (int64_t *)c.output<uint64_t>("value", "u64", m * 2 * RS_HOLDINGS);
+    out.br = (int64_t *)c.output<uint64_t>("br", "u64", m * 2 * RS_HOLDINGS);
+    out.status = c.output<uint8_t>("status", "u8", m);
+    Work<uint64_t> desc(m * RS_DESC_WORDS);
+    Work<char> ws((size_t)grid * ts_group_bytes(tt.ntmax, tt.nrmax));  // sized by the grid and the call's largest levels, as pk_solve_turn_trees sizes it
+    const TsPrepArgs a{spots, out.status, desc.p, m};
+    pk_sim::launch(prep_grid(m, TS_PREP_BLOCK), TS_PREP_BLOCK, [&] { k_ts_prep(a); });
+    uint64_t *dw = desc.p;
+    uint8_t *st = out.status;
+    pk_sim::launch(prep_grid(m, RS_PREP_BLOCK), RS_PREP_BLOCK, [&] { k_trees_prep(tree_of, ntrees, dw, st, m); });
+    const uint64_t *dp = desc.p;
+    char *wp = ws.p;
+    if (out.strategy || out.river_strategy || out.value || out.br) pk_sim::launch(grid, RS_BLOCK, [&] { k_trees_turn_solve(tab, dp, tt, spots, out, wp, iters, (uint32_t)m); });
+}
+#endif
+
 #if PK_ES_HAS(12)
 void run_river(Case &c, const uint32_t *tab) {
     const size_t m = (size_t)c.num("m");
@@ -613,14 +726,8 @@ void run_river(Case &c, const uint32_t *tab) {
     if (n < 1 || n > (uint32_t)RS_MAX_NODES || grid < 1) die("riversolve: n outside 1 .. 64, or no workgroup");
     const uint8_t *kind = c.need<uint8_t>("kind", n), *child = c.need<uint8_t>("child", (size_t)n * 4);
     const uint32_t *put = c.need<uint32_t>("put", (size_t)n * 2);
-    RsTree t{};
-    t.n = n; t.pot = (uint32_t)c.num("pot");
-    size_t D = 0;
-    for (uint32_t v = 0; v < n; ++v) {
-        t.kind[v] = kind[v]; t.put[v][0] = put[v * 2]; t.put[v][1] = put[v * 2 + 1];
-        for (int a = 0; a < 4; ++a) { t.child[v][a] = child[v * 4 + a]; t.nact[v] += child[v * 4 + a] != 0xFF; }
-        if (kind[v] <= RS_P1) t.row[v] = (uint8_t)D++;
-    }
+    RsTree t;
+    const size_t D = pack_river_tree(t, n, (uint32_t)c.num("pot"), kind, child, put);
     const RsSpots spots{c.need<uint8_t>("board", m * 5), c.arr<uint64_t>("dead", m), c.need<uint16_t>("ranges", m * 2 * RS_HOLDINGS)};
     RsOut out{};
     out.strategy = c.output<uint16_t>("strategy", "u16", m * D * 4 * RS_HOLDINGS);
@@ -645,19 +752,9 @@ void run_turn(Case &c, const uint32_t *tab) {
     if (n < 1 || n > (uint32_t)TS_MAX_NODES || grid < 1) die("turnsolve: n outside 1 .. 128, or no workgroup");
     const uint8_t *kind = c.need<uint8_t>("kind", n), *child = c.need<uint8_t>("child", (size_t)n * 4);
     const uint32_t *put = c.need<uint32_t>("put", (size_t)n * 2);
-    TsTree t{};
-    t.n = n; t.pot = (uint32_t)c.num("pot");
-    size_t D[2] = {0, 0};
-    for (uint32_t v = 0; v < n; ++v) {
-        t.kind[v] = kind[v]; t.put[v][0] = put[v * 2]; t.put[v][1] = put[v * 2 + 1];
-        for (int a = 0; a < 4; ++a) {
-            const uint8_t ch = child[v * 4 + a];
-            t.child[v][a] = ch; t.nact[v] += ch != 0xFF;
-            if (ch != 0xFF && ch < n) t.river[ch] = t.river[v] || kind[v] == TS_CHANCE;
-        }
-        t.idx[v] = (uint8_t)(t.river[v] ? t.nr++ : t.nt++);
-        if (kind[v] <= RS_P1) t.row[v] = (uint8_t)D[t.river[v]]++;
-    }
+    TsTree t;
+    size_t D[2];
+    pack_turn_tree(t, n, (uint32_t)c.num("pot"), kind, child, put, D);
     const TsSpots spots{c.need<uint8_t>("board", m * 4), c.arr<uint64_t>("dead", m), c.need<uint16_t>("ranges", m * 2 * RS_HOLDINGS)};
     TsOut out{};
     out.strategy = c.output<uint16_t>("strategy", "u16", m * D[0] * 4 * RS_HOLDINGS);
@@ -682,7 +779,7 @@ int main(int argc, char **argv) {
     Case c(argv[1]);
     // the function-local __shared__ arrays of the main kernels (the preparation kernels have none)
     const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "11k_hero_histPKj", "5k_eqwILi", "4k_evILi", "5k_evwILi", "10k_cl_quant", "11k_cl_assign",
-                                        "11k_cl_update", "14k_cl_seed_dist", "14k_cl_seed_pick", "10k_pfm_rank", "11k_pfm_count", "10k_pfm_hero", "9k_pfm_rvr", "13k_river_solvePKj", "12k_turn_solvePKj"});
+                                        "11k_cl_update", "14k_cl_seed_dist", "14k_cl_seed_pick", "10k_pfm_rank", "11k_pfm_count", "10k_pfm_hero", "9k_pfm_rvr", "13rs_solve_bodyILb", "13ts_solve_bodyILb"});
     Work<uint32_t> tab(EVAL7_TAB_WORDS);
     for (int i = 0; i < EVAL7_TAB_WORDS; ++i) tab.p[i] = eval7_tab_entry((uint32_t)i);
     const auto t0 = std::chrono::steady_clock::now();
@@ -750,6 +847,12 @@ int main(int argc, char **argv) {
 #endif
 #if PK_ES_HAS(13)
     if (c.family == "turnsolve") { run_turn(c, tab.p); ran = true; }
+#endif
+#if PK_ES_HAS(14)
+    if (c.family == "rivertrees") { run_river_trees(c, tab.p); ran = true; }
+#endif
+#if PK_ES_HAS(15)
+    if (c.family == "turntrees") { run_turn_trees(c, tab.p); ran = true; }
 #endif
     if (!ran) die("family " + c.family + ": not in this build");
     c.write(argv[2]);

@@ -9,6 +9,12 @@ river_tree(100, 400, (1.0,), 1) and the same iteration count, outputs value, br,
 alone: it has no chance node, so it computes no turn strategy.
 
     python tools/turn_solver_bench.py [--samples 3] [--m 256 1024] [--iters 64]
+
+--trees K measures the tree-per-spot entry (pk_solve_turn_trees_d) instead, as tools/river_solver_bench.py --trees
+does, and merges its legs into profiles/solver_trees_bench.json under "turn": the same spots through K single-tree calls (one per tree, on
+its run of spots) and through ONE tree-per-spot call; K = 1 is the price of the indirection, K > 1 uses turn_tree(60 + 10 k, 400, (1.0,), 1).
+
+    python tools/turn_solver_bench.py --trees 1 --m 256
 """
 import argparse
 import ctypes as C
@@ -46,18 +52,78 @@ def subgames(rng, m):
     return board, river.reshape(m * 48, 5), ranges
 
 
+def at(buf, offset):
+    """a device pointer `offset` bytes into a DeviceBuffer"""
+    return C.c_void_p(buf.ptr.value + offset)
+
+
+def trees_legs(args, stream, res):
+    """--trees K (the module's docstring)"""
+    K = args.trees
+    rng = np.random.default_rng(0)
+    board, _, ranges = subgames(rng, max(args.m))
+    trees = [solver.turn_tree(100, 400, (1.0,), 1)] if K == 1 else [solver.turn_tree(60 + 10 * k, 400, (1.0,), 1) for k in range(K)]
+    D = max(len(t.decision_nodes) for t in trees)
+    for m in args.m:
+        tree_of = (np.arange(m) % K).astype(np.uint32)
+        order = np.argsort(tree_of, kind="stable")                            # the spots grouped by tree: K runs of consecutive spots
+        of = np.ascontiguousarray(tree_of[order])
+        ins = [DeviceBuffer(x.nbytes).upload(x) for x in (np.ascontiguousarray(board[:m][order]), np.ascontiguousarray(ranges[:m][order]), of)]
+        strategy, value, br, status = DeviceBuffer(m * D * 4 * H * 2), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m)
+        starts = [int(np.searchsorted(of, k)) for k in range(K + 1)]
+
+        def per_spot():
+            solver.solve_turn_d(m, ins[0].ptr, ins[1].ptr, trees, args.iters, strategy_d=strategy.ptr, value_d=value.ptr, br_d=br.ptr, status_d=status.ptr,
+                                stream=stream, tree_of=ins[2].ptr)
+
+        def grouped():                                                        # one single-tree call per tree, on its run of spots
+            for k in range(K):
+                lo, n = starts[k], starts[k + 1] - starts[k]
+                solver.solve_turn_d(n, at(ins[0], lo * 4), at(ins[1], lo * 2 * H * 2), trees[k], args.iters, strategy_d=at(strategy, lo * D * 4 * H * 2),
+                                    value_d=at(value, lo * 2 * H * 8), br_d=at(br, lo * 2 * H * 8), status_d=at(status, lo), stream=stream)
+
+        leg = {}
+        for name, run in (("single_tree_calls", grouped), ("tree_per_spot_call", per_spot)):
+            us, each, wall, odd = time_stream(run, stream, args.samples, warmup=1)
+            assert not status.download(np.uint8, m).any()
+            v, bb = value.download(np.int64, m * 2 * H), br.download(np.int64, m * 2 * H)
+            assert (bb >= v).all() and v.any()
+            leg[name] = dict(ms=round(us * 1e-3, 3), samples_ms=[round(x * 1e-3, 3) for x in each], host_clock_ms=round(wall * 1e-3, 3), event_anomalies=odd,
+                             calls=K if run is grouped else 1, spot_iterations_per_s=round(m * args.iters / (us * 1e-6), 0), value_sum=int(v.sum()))
+        assert leg["single_tree_calls"]["value_sum"] == leg["tree_per_spot_call"]["value_sum"]          # the same spots, the same trees: the same values
+        leg["ratio_tree_per_spot_to_single"] = round(leg["tree_per_spot_call"]["ms"] / leg["single_tree_calls"]["ms"], 4)
+        leg["note"] = ("single_tree_calls is THIS library's one-tree entry in the same process; the parent commit's one-tree entry is timed separately, "
+                       "by this tool's ordinary legs on that commit's library")
+        res["trees_%d_m_%d" % (K, m)] = dict(iters=args.iters, trees=K, tree_nodes=sorted({t.n for t in trees}), grid=solver.turn_grid(trees, m), **leg)
+        for x in ins + [strategy, value, br, status]:
+            x.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=3)
     ap.add_argument("--m", type=int, nargs="+", default=[256, 1024])
     ap.add_argument("--iters", type=int, default=64)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "turn_solver_bench.json"))
+    ap.add_argument("--trees", type=int, default=0, help="K: measure the tree-per-spot entry with K trees (1: the indirection alone)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "solver_trees_bench.json" if args.trees else "turn_solver_bench.json")
     if pokerl_amd.device_count() < 1:
         sys.exit("turn_solver_bench: no MI355X visible (no fallback)")
     hip = hipmem._lib()
     stream = C.c_void_p()
     assert hip.hipStreamCreateWithFlags(C.byref(stream), 1) == 0
+    if args.trees:
+        from river_solver_bench import merge_into
+        ks = kernel_meta.kernels(L.LIB_PATH)
+        res = dict(tool="turn_solver_bench --trees", src=L.source_hash(), samples=args.samples)
+        for name in ("k_turn_solve", "k_trees_turn_solve"):
+            res[name] = dict(vgprs=ks[name]["vgprs"], sgprs=ks[name]["sgprs"], lds=ks[name]["lds"], scratch=ks[name]["private_segment"])
+        trees_legs(args, stream, res)
+        hip.hipStreamDestroy(stream)
+        merge_into(args.out, "turn", res)
+        print(json.dumps(res))
+        return
     rng = np.random.default_rng(0)
     tree, rtree = solver.turn_tree(100, 400, (1.0,), 1), solver.river_tree(100, 400, (1.0,), 1)
     Dt = len(tree.decision_nodes)

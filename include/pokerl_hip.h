@@ -1121,6 +1121,60 @@ int pk_solve_turn_trees(int device, size_t m, const uint8_t *board, const uint64
  * They look at kind (and child) only; PK_E_INVALID_ARG for ntrees out of range, a NULL pointer, an n[k] out of range or (turn) a child index <= its parent or >= n[k]. */
 int pk_rs_trees_rows(uint32_t ntrees, const uint32_t *n, const uint8_t *kind, uint32_t *Dmax);
 int pk_ts_trees_rows(uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child, uint32_t *Dtmax, uint32_t *Drmax);
+
+/* ---- Locked nodes: the river and turn solvers with rows of the strategy FIXED by the caller (the numpy restatement:
+ * tests/solver_lock_spec.py).  "How exploitable is my policy here?", "he never bluff-raises; what do I do?", and a solution fed back into a
+ * later call.  Everything of "River solver", "Turn solver" and "a tree per spot" holds except what is said here.
+ * A call carries, beside the arguments of pk_solve_river_trees / pk_solve_turn_trees:
+ *   lock   u8  [m][Dmax]            nonzero: row d of spot i is LOCKED (turn: the turn-level rows, stride Dtmax)
+ *   locked u16 [m][Dmax][4][1326]   the layout and strides of the `strategy` output of the tree-per-spot calls
+ *   river_lock u8 [m][Drmax], river_locked u16 [m][Drmax][52][4][1326] (turn only): the river-level rows, in the layout of river_strategy;
+ *                                   a river-level row is locked for all river cards at once.
+ * lock == NULL: nothing is locked and `locked` is not looked at; the same holds for the river_ pair.
+ * DEFINITION: at a locked decision node n (row d, actor p), for every valid holding h, sigma[n][.][h] = the STRATEGY rule of "River solver"
+ * applied to X[a] = locked[i][d][a][h] for a < nact, in every pass of every iteration and in the final passes: the uniform row where all X
+ * are 0, otherwise sigma_a = (X_a << 15) // sum X for a >= 1 and sigma_0 = ONE - sum_{a >= 1} sigma_a (the rule's shift is 0 for 16-bit X).
+ * So a row of a previous `strategy` output is reproduced unchanged (it sums to ONE), any non-negative weights are accepted, and X and 2X
+ * give the same sigma.  NOT READ: action slots >= nact; invalid holdings; rows whose flag is 0; rows at or past the spot's own D; for the
+ * turn solver, cards outside the pool and holdings that contain the river card.  Neither R nor A is updated at a locked node.  The
+ * `strategy` / `river_strategy` output at a locked row is the sigma played.
+ * value and br are defined as before on the final profile.  br IGNORES the locks: p maximises at all of its own nodes, so the
+ * exploitability is that of the profile as played.
+ * iters may be 0 .. PK_RS_MAX_ITERS in these calls (the calls above keep refusing 0).  With 0 iterations every free row is the uniform
+ * row, because A = 0.  All rows locked with iters = 0 is a pure evaluation of a supplied strategy; all rows of q locked is the
+ * best-response computation against q.  The BOUNDS are unchanged, because a locked sigma sums to ONE.
+ * `locked` must not overlap an output: equal `locked` and `strategy` pointers are PK_E_INVALID_ARG, as is a non-NULL `lock` with a NULL
+ * `locked`; the same for the river_ pair.
+ * ONE FORM, the tree-per-spot form; ntrees = 1 with tree_of == NULL means every spot uses tree 0, which is the one-tree case.  The trees
+ * are checked and packed as in the calls above, with their texts.  In the _d forms the lock arrays are DEVICE memory.  Status values and
+ * the refused-spot rule are unchanged; a refused spot's lock data is never read. */
+int pk_solve_river_locked_d(int device, size_t m, const uint8_t *board_d /*[m][5]*/, const uint64_t *dead_d /*[m]; NULL: none*/,
+                            const uint16_t *ranges_d /*[m][2][1326]*/, uint32_t ntrees, const uint32_t *n /*[ntrees], host*/,
+                            const uint8_t *kind /*[ntrees][64], host*/, const uint8_t *child /*[ntrees][64][4], host*/,
+                            const uint32_t *put /*[ntrees][64][2], host*/, const uint32_t *pot /*[ntrees], host*/,
+                            const uint32_t *tree_of_d /*[m], DEVICE; NULL with ntrees = 1: tree 0*/, uint32_t iters,
+                            const uint8_t *lock_d /*[m][Dmax], DEVICE; NULL: none*/, const uint16_t *locked_d /*[m][Dmax][4][1326], DEVICE*/,
+                            uint16_t *strategy_d /*[m][Dmax][4][1326]*/, int64_t *value_d /*[m][2][1326]*/, int64_t *br_d, uint8_t *status_d,
+                            void *stream);
+int pk_solve_river_locked(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees,
+                          const uint32_t *n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot,
+                          const uint32_t *tree_of /*[m], host; NULL with ntrees = 1: tree 0*/, uint32_t iters, const uint8_t *lock,
+                          const uint16_t *locked, uint16_t *strategy, int64_t *value, int64_t *br, uint8_t *status);
+int pk_solve_turn_locked_d(int device, size_t m, const uint8_t *board_d /*[m][4]*/, const uint64_t *dead_d /*[m]; NULL: none*/,
+                           const uint16_t *ranges_d /*[m][2][1326]*/, uint32_t ntrees, const uint32_t *n /*[ntrees], host*/,
+                           const uint8_t *kind /*[ntrees][128], host*/, const uint8_t *child /*[ntrees][128][4], host*/,
+                           const uint32_t *put /*[ntrees][128][2], host*/, const uint32_t *pot /*[ntrees], host*/,
+                           const uint32_t *tree_of_d /*[m], DEVICE; NULL with ntrees = 1: tree 0*/, uint32_t iters,
+                           const uint8_t *lock_d /*[m][Dtmax], DEVICE; NULL: none*/, const uint16_t *locked_d /*[m][Dtmax][4][1326], DEVICE*/,
+                           const uint8_t *river_lock_d /*[m][Drmax], DEVICE; NULL: none*/,
+                           const uint16_t *river_locked_d /*[m][Drmax][52][4][1326], DEVICE*/, uint16_t *strategy_d /*[m][Dtmax][4][1326]*/,
+                           uint16_t *river_strategy_d /*[m][Drmax][52][4][1326]*/, int64_t *value_d /*[m][2][1326]*/, int64_t *br_d,
+                           uint8_t *status_d, void *stream);
+int pk_solve_turn_locked(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees,
+                         const uint32_t *n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot,
+                         const uint32_t *tree_of /*[m], host; NULL with ntrees = 1: tree 0*/, uint32_t iters, const uint8_t *lock,
+                         const uint16_t *locked, const uint8_t *river_lock, const uint16_t *river_locked, uint16_t *strategy,
+                         uint16_t *river_strategy, int64_t *value, int64_t *br, uint8_t *status);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

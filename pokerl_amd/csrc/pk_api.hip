@@ -3217,4 +3217,119 @@ int pk_solve_turn_trees(int device, size_t m, const uint8_t *board, const uint64
     });
 }
 
+// ---- locked nodes (pokerl_hip.h "Locked nodes"): the tree-per-spot calls with rows of the strategies fixed by the
+// caller.  The trees are checked and packed by the code above, with its texts; iters may be 0; tree_of may be NULL with one tree.
+static const char *lock_check(uint32_t iters, uint32_t ntrees, const void *tree_of) {
+    if (iters > (uint32_t)RS_MAX_ITERS) return ": iters outside 0 .. 4096";
+    if (!tree_of && ntrees != 1u) return ": tree_of is NULL with ntrees != 1";
+    return nullptr;
+}
+static const char *lock_pair(const void *lock, const void *locked, const void *out, const char *missing, const char *overlap) {
+    if (lock && !locked) return missing;
+    if (locked && locked == out) return overlap;
+    return nullptr;
+}
+static const char *rs_lock_pack(size_t m, bool pointers, uint32_t iters, uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child,
+                                const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, const uint8_t *lock, const uint16_t *locked,
+                                const uint16_t *strategy, RsPacked &p) {
+    if (const char *why = lock_check(iters, ntrees, tree_of)) return why;
+    if (const char *why = lock_pair(lock, locked, strategy, ": lock without locked", ": locked and strategy are the same buffer")) return why;
+    // (the existing check refuses 0 iterations and a NULL tree_of: both have been judged above)
+    return rs_pack_trees(m, pointers, iters ? iters : 1u, ntrees, n, kind, child, put, pot, tree_of ? tree_of : n, p);
+}
+static const char *ts_lock_pack(size_t m, bool pointers, uint32_t iters, uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child,
+                                const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, const uint8_t *lock, const uint16_t *locked,
+                                const uint8_t *river_lock, const uint16_t *river_locked, const uint16_t *strategy, const uint16_t *river_strategy,
+                                TsPacked &p) {
+    if (const char *why = lock_check(iters, ntrees, tree_of)) return why;
+    if (const char *why = lock_pair(lock, locked, strategy, ": lock without locked", ": locked and strategy are the same buffer")) return why;
+    if (const char *why = lock_pair(river_lock, river_locked, river_strategy, ": river_lock without river_locked",
+                                    ": river_locked and river_strategy are the same buffer"))
+        return why;
+    return ts_pack_trees(m, pointers, iters ? iters : 1u, ntrees, n, kind, child, put, pot, tree_of ? tree_of : n, p);
+}
+
+int pk_solve_river_locked_d(int device, size_t m, const uint8_t *board_d, const uint64_t *dead_d, const uint16_t *ranges_d, uint32_t ntrees, const uint32_t *n,
+                            const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of_d, uint32_t iters,
+                            const uint8_t *lock_d, const uint16_t *locked_d, uint16_t *strategy_d, int64_t *value_d, int64_t *br_d, uint8_t *status_d,
+                            void *stream) {
+    const char *call = "pk_solve_river_locked_d";
+    RsPacked p;
+    EQ_REFUSE(g_fail, call, rs_lock_pack(m, board_d && ranges_d && status_d, iters, ntrees, n, kind, child, put, pot, tree_of_d, lock_d, locked_d, strategy_d, p));
+    const bool solve = strategy_d || value_d || br_d;
+    const size_t ws = rs_work_bytes(m, p.nmax, solve);
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, ws + (solve ? rs_trees_bytes(ntrees) : 0), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        RsTree *trees_d = (RsTree *)(work + ws);
+        if (solve)
+            if (const hipError_t e = hipMemcpyAsync(trees_d, p.trees.data(), (size_t)ntrees * sizeof(RsTree), hipMemcpyHostToDevice, st)) return e;
+        return rs_launch_locked(st, tab, RsSpots{board_d, dead_d, ranges_d}, RsTrees{trees_d, tree_of_d, p.nmax, p.Dmax}, ntrees, RsLock{lock_d, locked_d},
+                                iters, m, RsOut{strategy_d, value_d, br_d, status_d}, work);
+    });
+}
+
+int pk_solve_river_locked(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees, const uint32_t *n,
+                          const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, uint32_t iters,
+                          const uint8_t *lock, const uint16_t *locked, uint16_t *strategy, int64_t *value, int64_t *br, uint8_t *status) {
+    const char *call = "pk_solve_river_locked";
+    RsPacked p;
+    EQ_REFUSE(g_fail, call, rs_lock_pack(m, board && ranges && status, iters, ntrees, n, kind, child, put, pot, tree_of, lock, locked, strategy, p));
+    const bool solve = strategy || value || br;
+    Stage g;
+    const int bo = g.in(board, m * 5), de = g.in(dead, m * 8), ra = g.in(ranges, m * 2 * RS_HOLDINGS * 2), to = g.in(tree_of, m * 4);
+    const int tr = g.in(solve ? p.trees.data() : nullptr, (size_t)ntrees * sizeof(RsTree));
+    const int lo = g.in(solve ? lock : nullptr, m * p.Dmax), ld = g.in(solve && lock ? locked : nullptr, m * p.Dmax * 4 * RS_HOLDINGS * 2);
+    const int sg = g.out(strategy, m * p.Dmax * 4 * RS_HOLDINGS * 2), va = g.out(value, m * 2 * RS_HOLDINGS * 8), be = g.out(br, m * 2 * RS_HOLDINGS * 8);
+    const int su = g.out(status, m);
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, rs_work_bytes(m, p.nmax, solve), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return rs_launch_locked(st, tab, RsSpots{g.at<uint8_t>(bo), g.at<uint64_t>(de), g.at<uint16_t>(ra)},
+                                RsTrees{g.at<RsTree>(tr), g.at<uint32_t>(to), p.nmax, p.Dmax}, ntrees, RsLock{g.at<uint8_t>(lo), g.at<uint16_t>(ld)}, iters, m,
+                                RsOut{g.at<uint16_t>(sg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
+    });
+}
+
+int pk_solve_turn_locked_d(int device, size_t m, const uint8_t *board_d, const uint64_t *dead_d, const uint16_t *ranges_d, uint32_t ntrees, const uint32_t *n,
+                           const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of_d, uint32_t iters,
+                           const uint8_t *lock_d, const uint16_t *locked_d, const uint8_t *river_lock_d, const uint16_t *river_locked_d, uint16_t *strategy_d,
+                           uint16_t *river_strategy_d, int64_t *value_d, int64_t *br_d, uint8_t *status_d, void *stream) {
+    const char *call = "pk_solve_turn_locked_d";
+    TsPacked p;
+    EQ_REFUSE(g_fail, call, ts_lock_pack(m, board_d && ranges_d && status_d, iters, ntrees, n, kind, child, put, pot, tree_of_d, lock_d, locked_d, river_lock_d,
+                                         river_locked_d, strategy_d, river_strategy_d, p));
+    const bool solve = strategy_d || river_strategy_d || value_d || br_d;
+    const size_t ws = ts_work_bytes(m, p.ntmax, p.nrmax, solve);
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, ws + (solve ? ts_trees_bytes(ntrees) : 0), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        TsTree *trees_d = (TsTree *)(work + ws);
+        if (solve)
+            if (const hipError_t e = hipMemcpyAsync(trees_d, p.trees.data(), (size_t)ntrees * sizeof(TsTree), hipMemcpyHostToDevice, st)) return e;
+        return ts_launch_locked(st, tab, TsSpots{board_d, dead_d, ranges_d}, TsTrees{trees_d, tree_of_d, p.ntmax, p.nrmax, p.Dtmax, p.Drmax}, ntrees,
+                                TsLock{lock_d, locked_d, river_lock_d, river_locked_d}, iters, m,
+                                TsOut{strategy_d, river_strategy_d, value_d, br_d, status_d}, work);
+    });
+}
+
+int pk_solve_turn_locked(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees, const uint32_t *n,
+                         const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, uint32_t iters,
+                         const uint8_t *lock, const uint16_t *locked, const uint8_t *river_lock, const uint16_t *river_locked, uint16_t *strategy,
+                         uint16_t *river_strategy, int64_t *value, int64_t *br, uint8_t *status) {
+    const char *call = "pk_solve_turn_locked";
+    TsPacked p;
+    EQ_REFUSE(g_fail, call, ts_lock_pack(m, board && ranges && status, iters, ntrees, n, kind, child, put, pot, tree_of, lock, locked, river_lock, river_locked,
+                                         strategy, river_strategy, p));
+    const bool solve = strategy || river_strategy || value || br;
+    Stage g;
+    const int bo = g.in(board, m * 4), de = g.in(dead, m * 8), ra = g.in(ranges, m * 2 * RS_HOLDINGS * 2), to = g.in(tree_of, m * 4);
+    const int tr = g.in(solve ? p.trees.data() : nullptr, (size_t)ntrees * sizeof(TsTree));
+    const int lo = g.in(solve ? lock : nullptr, m * p.Dtmax), ld = g.in(solve && lock ? locked : nullptr, m * p.Dtmax * 4 * RS_HOLDINGS * 2);
+    const int ro = g.in(solve ? river_lock : nullptr, m * p.Drmax);
+    const int rd = g.in(solve && river_lock ? river_locked : nullptr, m * p.Drmax * 52 * 4 * RS_HOLDINGS * 2);
+    const int sg = g.out(strategy, m * p.Dtmax * 4 * RS_HOLDINGS * 2), rg = g.out(river_strategy, m * p.Drmax * 52 * 4 * RS_HOLDINGS * 2);
+    const int va = g.out(value, m * 2 * RS_HOLDINGS * 8), be = g.out(br, m * 2 * RS_HOLDINGS * 8), su = g.out(status, m);
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, ts_work_bytes(m, p.ntmax, p.nrmax, solve), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return ts_launch_locked(st, tab, TsSpots{g.at<uint8_t>(bo), g.at<uint64_t>(de), g.at<uint16_t>(ra)},
+                                TsTrees{g.at<TsTree>(tr), g.at<uint32_t>(to), p.ntmax, p.nrmax, p.Dtmax, p.Drmax}, ntrees,
+                                TsLock{g.at<uint8_t>(lo), g.at<uint16_t>(ld), g.at<uint8_t>(ro), g.at<uint16_t>(rd)}, iters, m,
+                                TsOut{g.at<uint16_t>(sg), g.at<uint16_t>(rg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
+    });
+}
+
 }  // extern "C"

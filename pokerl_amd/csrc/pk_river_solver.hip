@@ -19,6 +19,8 @@
 //                   the descriptor's "good" bit).  k_trees_river_solve is k_river_solve's body (rs_solve_body<PER_SPOT>): it stages
 //                   trees[tree_of[spot]] into LDS at the top of each spot (a refused one: tree 0, unused), lays its slice -- sized for the call's largest tree -- out
 //                   for that tree's n, and writes `strategy` with the call's row stride Dmax, the rows at or past the spot's own D as zeros.
+//   k_lock_river_solve   the same body with LOCK ("Locked nodes"): rows of the strategy fixed by the caller.  A locked node's
+//                   probabilities are formed once per spot from the caller's weights and stay in SG; R and A are left alone there.
 // Ordinary vector stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_river_solver_host.py reads the code object).
 #include <hip/hip_runtime.h>
 
@@ -77,9 +79,14 @@ __global__ void __launch_bounds__(RS_PREP_BLOCK) k_trees_prep(const uint32_t *__
 // The solver's body.  PER_SPOT = false: `tree` is the call's one tree (the kernel's argument), staged once per workgroup.  PER_SPOT = true:
 // `tree` is the call's array of packed trees in device memory, and a spot stages trees[tree_of[spot]] (a refused one tree 0) -- after the barrier at the top
 // of the spot, which the last use of `tr` by the spot before lies behind; nmax and Dmax are the largest n and D of the call.
-template <bool PER_SPOT>
+// LOCK (with PER_SPOT; "Locked nodes"): rows of `lk.lock` fix a decision node's probabilities to the strategy rule applied to
+// `lk.locked`.  They are formed once per spot by the owner of each position and stay in SG at the node's edges: the walk down plays SG as it stands
+// there, the walk up leaves R and A alone, the average-strategy stage writes `strategy` from SG.  A NULL tree_of: every spot uses tree 0.
+template <bool PER_SPOT, bool LOCK = false>
 __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, const RsTree *tree, const uint32_t *tree_of,
-                                              uint32_t nmax, uint32_t Dmax, const RsSpots &spots, const RsOut &out, char *ws, uint32_t iters, uint32_t m) {
+                                              uint32_t nmax, uint32_t Dmax, const RsSpots &spots, const RsOut &out, char *ws, uint32_t iters, uint32_t m,
+                                              const RsLock &lk = RsLock{}) {
+    static_assert(PER_SPOT || !LOCK, "the locked call has the tree-per-spot form only");
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     __shared__ uint64_t slot[RS_SLOTS];               // key << 11 | pool holding, sorted once per spot; all ones = no holding.  After the
                                                       // sort the same memory holds rs and posof (below)
@@ -131,7 +138,8 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
         if constexpr (PER_SPOT) {
             // (good: k_trees_prep has seen tree_of[spot] < ntrees.  A refused spot stages tree 0, which always exists, and uses none of it:
             // staging on every path keeps n, pot and the slice's pointers plain values of the spot, not merges with the spot before)
-            stage(tree + (good ? PK_IDX(uniform(tree_of[spot]), RS_MAX_TREES, "tree_of") : 0u));
+            if constexpr (LOCK) stage(tree + ((good && tree_of) ? PK_IDX(uniform(tree_of[spot]), RS_MAX_TREES, "tree_of") : 0u));
+            else stage(tree + (good ? PK_IDX(uniform(tree_of[spot]), RS_MAX_TREES, "tree_of") : 0u));
             if (!good) D = 0;
         }
         const uint32_t DS = PER_SPOT ? Dmax : D;      // the row stride of `strategy`
@@ -223,6 +231,38 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
             RR[at(0, i)] = ((uint64_t)w0[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 4) | ((uint64_t)w1[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 36);
             for (uint32_t v = 1; v < n; ++v) { R[at(v, i)] = 0; A[at(v, i)] = 0; }
         }
+        // ---- the locked nodes of the spot (bit v: decision node v), and their probabilities into SG: the rule on the caller's weights
+        uint64_t lockm = 0;
+        if constexpr (LOCK) {
+            if (lk.lock)
+                for (uint32_t v = 0; v < n; ++v) {
+                    if (tr.kind[PK_IDX(v, RS_MAX_NODES, "kind")] > RS_P1) continue;
+                    const uint32_t row = tr.row[PK_IDX(v, RS_MAX_NODES, "row")];
+                    lockm |= lk.lock[(size_t)spot * Dmax + PK_IDX(row, Dmax, "lock row")] ? 1ull << v : 0ull;
+                }
+            lockm = uniform(lockm);
+            for (uint32_t node = 0; node < n; ++node) {
+                if (!((lockm >> node) & 1ull)) continue;
+                const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, RS_MAX_NODES, "nact")]), row = uniform((uint32_t)tr.row[PK_IDX(node, RS_MAX_NODES, "row")]);
+                uint32_t ch[4];
+                kids(node, nact, ch);
+                const uint16_t *src = lk.locked + ((size_t)spot * Dmax + row) * 4 * RS_HOLDINGS;
+#pragma unroll
+                for (int j = 0; j < RS_PER_LANE; ++j) {
+                    const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                    if (i >= nh) continue;
+                    int64_t X[4];
+                    uint32_t sig[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) X[a] = (uint32_t)a < nact ? (int64_t)src[(size_t)a * RS_HOLDINGS + PK_IDX(gh[j], RS_HOLDINGS, "locked")] : 0;
+                    rs_sigma(X, nact, sig);
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+                        if ((uint32_t)a < nact) SG[at(ch[a], i)] = sig[a];
+                }
+            }
+        }
+        auto locked_at = [&](uint32_t node) -> bool { return LOCK && ((lockm >> node) & 1ull) != 0ull; };
         __syncthreads();                              // (posof)
 
         // A terminal node: both players' values of every holding from the opponent's reaches (every lane of the workgroup comes here)
@@ -302,10 +342,11 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
 
         // One walk down: reaches, and every terminal's values.  FROM_R: the probabilities come from the regrets and are kept in SG;
         // otherwise SG is played as it stands.
-        auto down = [&](bool from_r) {
+        auto down = [&](bool walk_from_r) {
             for (uint32_t node = 0; node < n; ++node) {
                 const uint32_t kind = uniform((uint32_t)tr.kind[PK_IDX(node, RS_MAX_NODES, "kind")]);
                 if (kind > RS_P1) { terminal(node, kind); continue; }
+                const bool from_r = walk_from_r && !locked_at(node);          // (a locked node: SG holds what is played there)
                 const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, RS_MAX_NODES, "nact")]);
                 uint32_t ch[4];
                 kids(node, nact, ch);
@@ -361,6 +402,7 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
                     const int64_t un = acc >> 15;     // (the sum first, the floor once)
                     Up[at(node, i)] = un;
                     Uq[at(node, i)] = uq;
+                    if (locked_at(node)) continue;    // (neither R nor A is updated at a locked node)
 #pragma unroll
                     for (int a = 0; a < 4; ++a) {
                         if ((uint32_t)a >= nact) continue;
@@ -389,7 +431,10 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
                 uint32_t sig[4];
 #pragma unroll
                 for (int a = 0; a < 4; ++a) X[a] = (uint32_t)a < nact ? A[at(ch[a], i)] : 0;
-                rs_sigma(X, nact, sig);
+                if (locked_at(node)) {
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) sig[a] = (uint32_t)a < nact ? SG[at(ch[a], i)] : 0u;
+                } else rs_sigma(X, nact, sig);
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     if ((uint32_t)a < nact) SG[at(ch[a], i)] = sig[a];
@@ -454,6 +499,12 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_trees_river_solve(const uint32_
     rs_solve_body<true>(tab, desc, trees.trees, trees.tree_of, trees.nmax, trees.Dmax, spots, out, ws, iters, m);
 }
 
+// the locked call: k_trees_river_solve's body with LOCK (the name does not begin with k_river_solve or k_trees_: host tests list those)
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_lock_river_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, RsTrees trees, RsLock lk,
+                                                                  RsSpots spots, RsOut out, char *ws, uint32_t iters, uint32_t m) {
+    rs_solve_body<true, true>(tab, desc, trees.trees, trees.tree_of, trees.nmax, trees.Dmax, spots, out, ws, iters, m, lk);
+}
+
 namespace pk {
 
 hipError_t rs_launch(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTree &tree, uint32_t iters, size_t m, const RsOut &out,
@@ -482,6 +533,19 @@ hipError_t rs_launch_trees(hipStream_t stream, const uint32_t *tab, const RsSpot
     if (e == hipSuccess) e = trees_prep_launch(stream, trees.tree_of, ntrees, (uint64_t *)work, out.status, m);
     if (e != hipSuccess || !(out.strategy || out.value || out.br)) return e;   // (status alone: the preparation kernel has written it)
     hipLaunchKernelGGL(k_trees_river_solve, dim3(rs_grid(m)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, spots, out,
+                       work + rs_desc_bytes(m), iters, (uint32_t)m);
+    return hipGetLastError();
+}
+
+hipError_t rs_launch_locked(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTrees &trees, uint32_t ntrees, const RsLock &lk,
+                            uint32_t iters, size_t m, const RsOut &out, char *work) {
+    if (m == 0) return hipSuccess;
+    const RsPrepArgs a{spots, out.status, (uint64_t *)work, m};
+    hipLaunchKernelGGL(k_rs_prep, dim3((unsigned)((m + RS_PREP_BLOCK - 1) / RS_PREP_BLOCK)), dim3(RS_PREP_BLOCK), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && trees.tree_of) e = trees_prep_launch(stream, trees.tree_of, ntrees, (uint64_t *)work, out.status, m);
+    if (e != hipSuccess || !(out.strategy || out.value || out.br)) return e;   // (status alone: the preparation kernels have written it)
+    hipLaunchKernelGGL(k_lock_river_solve, dim3(rs_grid(m)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, lk, spots, out,
                        work + rs_desc_bytes(m), iters, (uint32_t)m);
     return hipGetLastError();
 }

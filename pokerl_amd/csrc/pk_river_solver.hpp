@@ -74,4 +74,14 @@ hipError_t trees_prep_launch(hipStream_t stream, const uint32_t *tree_of, uint32
 hipError_t rs_launch_trees(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTrees &trees, uint32_t ntrees, uint32_t iters, size_t m,
                            const RsOut &out, char *work);
 
+
+// ---- locked nodes (include/pokerl_hip.h "Locked nodes")
+struct RsLock {
+    const uint8_t *lock;       // [m][Dmax], nonzero: the row is locked; NULL: nothing is
+    const uint16_t *locked;    // [m][Dmax][4][1326], the layout of `strategy`
+};
+// rs_launch_trees's launches with k_lock_river_solve; trees.tree_of may be NULL (every spot uses tree 0: k_trees_prep is not queued).
+hipError_t rs_launch_locked(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTrees &trees, uint32_t ntrees, const RsLock &lk,
+                            uint32_t iters, size_t m, const RsOut &out, char *work);
+
 }  // namespace pk

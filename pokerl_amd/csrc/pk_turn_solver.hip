@@ -19,6 +19,8 @@
 //                   k_ts_prep comes k_trees_prep (pk_river_solver.hip); a spot stages trees[tree_of[spot]] (a refused one tree 0) into LDS at its top and lays
 //                   the workgroup's slice -- sized for the call's largest nt and nr -- out for its own; `strategy` and `river_strategy`
 //                   have the call's row strides, the rows at or past the spot's own counts are written 0.
+//   k_lock_turn_solve   the same body with LOCK ("Locked nodes"): a locked turn-level node's probabilities stay in SG; a locked
+//                   river-level node's are packed, per card and position, into the regret word of its first edge, which nothing else uses.
 // Ordinary vector stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_turn_solver_host.py reads the code object).
 #include <hip/hip_runtime.h>
 
@@ -79,9 +81,16 @@ struct TsLevel {
 // The solver's body.  PER_SPOT = false: `tree` is the call's one tree (the kernel's argument), staged once per workgroup.  PER_SPOT = true:
 // `tree` is the call's array of packed trees in device memory, and a spot stages trees[tree_of[spot]] (a refused one tree 0) -- after the barrier at the top
 // of the spot, which the last use of `tr` by the spot before lies behind; ntmax, nrmax, Dtmax and Drmax are the call's largest.
-template <bool PER_SPOT>
+// LOCK (with PER_SPOT; "Locked nodes"): a locked TURN-LEVEL node's probabilities are formed once per spot and stay in SG at its
+// edges, as in the river solver.  A locked RIVER-LEVEL node's are formed once per spot and card and PACKED, four 16-bit fields, into the regret
+// word of its first edge under that card -- a word no pass uses, since a locked node's regrets are never read or updated; every pass of the card unpacks
+// them into SG, which the passes of the other cards rewrite.  The last pass of a card unpacks (the average stage) before the best responses take
+// the memory of R and A.  A NULL tree_of: every spot uses tree 0.
+template <bool PER_SPOT, bool LOCK = false>
 static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, const TsTree *tree, const TsTrees &mx,
-                                                     const TsSpots &spots, const TsOut &out, char *ws, uint32_t iters, uint32_t m) {
+                                                     const TsSpots &spots, const TsOut &out, char *ws, uint32_t iters, uint32_t m,
+                                                     const TsLock &lk = TsLock{}) {
+    static_assert(PER_SPOT || !LOCK, "the locked call has the tree-per-spot form only");
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     __shared__ uint64_t slot[RS_SLOTS];               // key << 11 | turn slot, sorted once per spot and card; all ones = no holding.  Between
                                                       // the sorts the same memory holds rs and posof, or a turn-level fold's reaches
@@ -157,7 +166,8 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
         if constexpr (PER_SPOT) {
             // (good: k_trees_prep has seen tree_of[spot] < ntrees.  A refused spot stages tree 0, which always exists, and uses none of it:
             // staging on every path keeps the tree's counts and the slice's pointers plain values of the spot, not merges with the spot before)
-            stage(tree + (good ? PK_IDX(uniform(mx.tree_of[spot]), RS_MAX_TREES, "tree_of") : 0u));
+            if constexpr (LOCK) stage(tree + ((good && mx.tree_of) ? PK_IDX(uniform(mx.tree_of[spot]), RS_MAX_TREES, "tree_of") : 0u));
+            else stage(tree + (good ? PK_IDX(uniform(mx.tree_of[spot]), RS_MAX_TREES, "tree_of") : 0u));
             if (!good) { Dt = 0; Dr = 0; }
         }
         const uint32_t DtS = PER_SPOT ? mx.Dtmax : Dt, DrS = PER_SPOT ? mx.Drmax : Dr;               // the row strides of the strategies
@@ -283,6 +293,69 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
                 for (uint32_t cs = 0; cs < P; ++cs)
                     for (uint32_t v = 0; v < nr; ++v) { Rr[((size_t)cs * nr + v) * RS_SORTED + s] = 0; Ar[((size_t)cs * nr + v) * RS_SORTED + s] = 0; }
         }
+        // ---- the locked nodes of the spot (bit v of lockm[v >> 6]: decision node v), and their probabilities: the rule on the caller's weights
+        uint64_t lockm[2] = {0, 0};
+        auto locked_at = [&](uint32_t node) -> bool { return LOCK && ((lockm[(node >> 6) & 1u] >> (node & 63u)) & 1ull) != 0ull; };
+        auto packed = [](const uint32_t (&sig)[4]) -> int64_t {
+            return (int64_t)((uint64_t)sig[0] | ((uint64_t)sig[1] << 16) | ((uint64_t)sig[2] << 32) | ((uint64_t)sig[3] << 48));
+        };
+        if constexpr (LOCK) {
+            for (uint32_t v = 0; v < n; ++v) {
+                if (tr.kind[PK_IDX(v, TS_MAX_NODES, "kind")] > RS_P1) continue;
+                const uint32_t row = tr.row[PK_IDX(v, TS_MAX_NODES, "row")];
+                bool on = false;
+                if (tr.river[PK_IDX(v, TS_MAX_NODES, "river")]) on = lk.river_lock && lk.river_lock[(size_t)spot * mx.Drmax + PK_IDX(row, mx.Drmax, "lock row")];
+                else on = lk.lock && lk.lock[(size_t)spot * mx.Dtmax + PK_IDX(row, mx.Dtmax, "lock row")];
+                lockm[v >> 6] |= on ? 1ull << (v & 63u) : 0ull;
+            }
+            lockm[0] = uniform(lockm[0]); lockm[1] = uniform(lockm[1]);
+            for (uint32_t node = 0; node < n; ++node) {
+                if (!locked_at(node)) continue;
+                const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, TS_MAX_NODES, "nact")]), row = uniform((uint32_t)tr.row[PK_IDX(node, TS_MAX_NODES, "row")]);
+                uint32_t ch[4];
+                kids(node, nact, ch);
+                size_t cr[4];
+                if (!is_river(node)) {
+                    rows_of(Lturn, ch, nact, cr);
+                    const uint16_t *src = lk.locked + ((size_t)spot * mx.Dtmax + row) * 4 * RS_HOLDINGS;
+#pragma unroll
+                    for (int j = 0; j < RS_PER_LANE; ++j) {
+                        const uint32_t s = tid + (uint32_t)j * RS_BLOCK;
+                        if (s >= nT) continue;
+                        int64_t X[4];
+                        uint32_t sig[4];
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) X[a] = (uint32_t)a < nact ? (int64_t)src[(size_t)a * RS_HOLDINGS + PK_IDX(gh[j], RS_HOLDINGS, "locked")] : 0;
+                        rs_sigma(X, nact, sig);
+#pragma unroll
+                        for (int a = 0; a < 4; ++a)
+                            if ((uint32_t)a < nact) SGt[at(Lturn, cr[a], s)] = sig[a];
+                    }
+                    continue;
+                }
+                for (uint32_t cs = 0; cs < P; ++cs) {
+                    const TsLevel L = river_level(cs);
+                    rows_of(L, ch, nact, cr);
+                    const uint16_t *src = lk.river_locked + (((size_t)spot * mx.Drmax + row) * 52 + canon[PK_IDX(cs, 64, "canon")]) * 4 * RS_HOLDINGS;
+#pragma unroll
+                    for (int j = 0; j < RS_PER_LANE; ++j) {
+                        const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                        if (i >= nh) continue;
+                        const uint32_t fx = fixed(slotof[tab_at(cs, i)]);
+                        int64_t X[4];
+                        uint32_t sig[4];
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) X[a] = (uint32_t)a < nact ? (int64_t)src[(size_t)a * RS_HOLDINGS + PK_IDX(fx, RS_HOLDINGS, "river_locked")] : 0;
+                        rs_sigma(X, nact, sig);
+                        L.R[at(L, cr[0], i)] = packed(sig);
+                    }
+                }
+            }
+        }
+        auto unpack = [](int64_t w, uint32_t (&sig)[4]) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) sig[a] = (uint32_t)((uint64_t)w >> (16 * a)) & 0xFFFFu;
+        };
         __syncthreads();                              // (the last card's slots have been read: their memory becomes rs and posof)
 
         // A river-level terminal under card cs (every lane of the workgroup comes here): k_river_solve's, the lane's positions from the tables
@@ -398,8 +471,10 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
 
         // A decision node on the way down, at either level.  FROM_R: the probabilities come from the regrets and are kept in SG;
         // otherwise SG is played as it stands.
-        auto decide_down = [&](const TsLevel &L, uint32_t node, uint32_t kind, bool from_r) {
+        auto decide_down = [&](const TsLevel &L, uint32_t node, uint32_t kind, bool walk_from_r) {
             const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, TS_MAX_NODES, "nact")]);
+            // (a locked node: SG holds what is played -- at the river level once the card's packed word has been unpacked into it)
+            const bool from_r = walk_from_r && !locked_at(node), from_word = LOCK && walk_from_r && locked_at(node) && is_river(node);
             uint32_t ch[4];
             kids(node, nact, ch);
             size_t cr[4];
@@ -416,13 +491,15 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
                     for (int a = 0; a < 4; ++a) X[a] = (uint32_t)a < nact ? L.R[at(L, cr[a], i)] : 0;
                     rs_sigma(X, nact, sig);
                 }
+                if constexpr (LOCK)
+                    if (from_word) unpack(L.R[at(L, cr[0], i)], sig);
                 const uint64_t rr = L.RR[at(L, nrow, i)];
                 const uint32_t r0 = (uint32_t)rr, r1 = (uint32_t)(rr >> 32);
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     if ((uint32_t)a >= nact) continue;
                     const size_t e = at(L, cr[a], i);
-                    if (from_r) L.SG[e] = sig[a]; else sig[a] = L.SG[e];
+                    if (from_r || from_word) L.SG[e] = sig[a]; else sig[a] = L.SG[e];
                     const uint32_t mine = (uint32_t)(((uint64_t)(kind == RS_P0 ? r0 : r1) * sig[a]) >> 15);
                     L.RR[e] = kind == RS_P0 ? ((uint64_t)mine | ((uint64_t)r1 << 32)) : ((uint64_t)r0 | ((uint64_t)mine << 32));
                 }
@@ -454,6 +531,7 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
                 const int64_t un = acc >> 15;         // (the sum first, the floor once)
                 Up[at(L, nrow, i)] = un;
                 Uq[at(L, nrow, i)] = uq;
+                if (locked_at(node)) continue;        // (neither R nor A is updated at a locked node)
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     if ((uint32_t)a >= nact) continue;
@@ -591,7 +669,13 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
                 uint32_t sig[4];
 #pragma unroll
                 for (int a = 0; a < 4; ++a) X[a] = (uint32_t)a < nact ? L.A[at(L, cr[a], i)] : 0;
-                rs_sigma(X, nact, sig);
+                if (locked_at(node)) {
+                    if (river) unpack(L.R[at(L, cr[0], i)], sig);
+                    else {
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) sig[a] = (uint32_t)a < nact ? L.SG[at(L, cr[a], i)] : 0u;
+                    }
+                } else rs_sigma(X, nact, sig);
                 uint16_t *o = nullptr;
                 if (river) {
                     if (out.river_strategy)
@@ -664,6 +748,12 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_trees_turn_solve(const uint32_t
     ts_solve_body<true>(tab, desc, trees.trees, trees, spots, out, ws, iters, m);
 }
 
+// the locked call: k_trees_turn_solve's body with LOCK (the name does not begin with k_turn_solve or k_trees_: host tests list those)
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_lock_turn_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, TsTrees trees, TsLock lk,
+                                                                 TsSpots spots, TsOut out, char *ws, uint32_t iters, uint32_t m) {
+    ts_solve_body<true, true>(tab, desc, trees.trees, trees, spots, out, ws, iters, m, lk);
+}
+
 namespace pk {
 
 hipError_t ts_launch(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTree &tree, uint32_t iters, size_t m, const TsOut &out,
@@ -687,6 +777,19 @@ hipError_t ts_launch_trees(hipStream_t stream, const uint32_t *tab, const TsSpot
     if (e == hipSuccess) e = trees_prep_launch(stream, trees.tree_of, ntrees, (uint64_t *)work, out.status, m);
     if (e != hipSuccess || !(out.strategy || out.river_strategy || out.value || out.br)) return e;   // (status alone: the preparation kernels have written it)
     hipLaunchKernelGGL(k_trees_turn_solve, dim3(ts_grid(m, trees.ntmax, trees.nrmax)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, spots,
+                       out, work + rs_desc_bytes(m), iters, (uint32_t)m);
+    return hipGetLastError();
+}
+
+hipError_t ts_launch_locked(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTrees &trees, uint32_t ntrees, const TsLock &lk,
+                            uint32_t iters, size_t m, const TsOut &out, char *work) {
+    if (m == 0) return hipSuccess;
+    const TsPrepArgs a{spots, out.status, (uint64_t *)work, m};
+    hipLaunchKernelGGL(k_ts_prep, dim3((unsigned)((m + TS_PREP_BLOCK - 1) / TS_PREP_BLOCK)), dim3(TS_PREP_BLOCK), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && trees.tree_of) e = trees_prep_launch(stream, trees.tree_of, ntrees, (uint64_t *)work, out.status, m);
+    if (e != hipSuccess || !(out.strategy || out.river_strategy || out.value || out.br)) return e;   // (status alone: the preparation kernels have written it)
+    hipLaunchKernelGGL(k_lock_turn_solve, dim3(ts_grid(m, trees.ntmax, trees.nrmax)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, lk, spots,
                        out, work + rs_desc_bytes(m), iters, (uint32_t)m);
     return hipGetLastError();
 }

@@ -76,4 +76,15 @@ constexpr size_t ts_trees_bytes(uint32_t ntrees) { return ((size_t)ntrees * size
 hipError_t ts_launch_trees(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTrees &trees, uint32_t ntrees, uint32_t iters, size_t m,
                            const TsOut &out, char *work);
 
+// ---- locked nodes (include/pokerl_hip.h "Locked nodes")
+struct TsLock {
+    const uint8_t *lock;            // [m][Dtmax], nonzero: the turn-level row is locked; NULL: none is
+    const uint16_t *locked;         // [m][Dtmax][4][1326], the layout of `strategy`
+    const uint8_t *river_lock;      // [m][Drmax], a river-level row, for all river cards at once; NULL: none is
+    const uint16_t *river_locked;   // [m][Drmax][52][4][1326], the layout of `river_strategy`
+};
+// ts_launch_trees's launches with k_lock_turn_solve; trees.tree_of may be NULL (every spot uses tree 0: k_trees_prep is not queued).
+hipError_t ts_launch_locked(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTrees &trees, uint32_t ntrees, const TsLock &lk,
+                            uint32_t iters, size_t m, const TsOut &out, char *work);
+
 }  // namespace pk

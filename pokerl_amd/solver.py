@@ -5,7 +5,10 @@ The turn solver (pk_solve_turn; "Turn solver") is the sa
 card as a chance node: turn_tree, solve_turn / solve_turn_batch / solve_turn_d, at the end of this module.
 A tree per spot (pk_solve_river_trees / pk_solve_turn_trees; "River and turn solvers: a tree per spot"): the batch
 and _d functions also take a SEQUENCE of trees with tree_of, the index of each spot's tree; river_trees / turn_trees build both from
-per-spot pots and stacks."""
+per-spot pots and stacks.
+Locked nodes (pk_solve_river_locked / pk_solve_turn_locked; "Locked nodes"): every solve function takes lock and
+locked (the turn forms also river_lock and river_locked) -- rows of the strategy fixed by the caller, CFR+ on the rest; iters may then be 0.
+evaluate_river / evaluate_turn lock every row: the value and the exploitability of a supplied strategy."""
 import math
 
 import numpy as np
@@ -36,6 +39,10 @@ class RiverTree:
 
     def num_actions(self, node):
         return int((self.child[node] != NO_CHILD).sum())
+
+    def rows_of(self, player):
+        """bool [D]: the rows of a solution's strategy at which `player` (0 or 1) acts -- a `lock` argument that fixes that player's play"""
+        return np.array([int(self.kind[v]) == int(player) for v in self.decision_nodes], bool)
 
     def label(self, node):
         """The actions that lead to `node`, such as "0:check 1:bet 50" ("" for the root)."""
@@ -243,18 +250,52 @@ def _trees_by_chips(pots, stacks, build):
     return trees, tree_of
 
 
+def _lock_rows(lock, m, D, name):
+    """lock as uint8 [m, D]: bool / integer [D] (every spot the same) or [m, D]"""
+    lock = np.asarray(lock)
+    if lock.dtype.kind not in "biu" or lock.shape not in ((D,), (m, D)):
+        raise ValueError("%s must be a bool or integer array of shape [%d] or [%d, %d]" % (name, D, m, D))
+    return np.ascontiguousarray(np.broadcast_to(lock != 0, (m, D)), np.uint8)
+
+
+def _locked_rows(locked, m, shape, name, attr):
+    """locked as uint16 [m, *shape]: an array of that shape (or of `shape`: every spot the same), or a solution, whose `attr` is taken"""
+    if isinstance(locked, (RiverSolution, TurnSolution)):
+        locked = getattr(locked, attr)
+        if locked is None:
+            raise ValueError("the solution passed as %s has no %s" % (name, attr))
+    locked = np.asarray(locked)
+    if locked.dtype.kind not in "iu" or locked.shape not in (shape, (m,) + shape):
+        raise ValueError("%s must be an integer array of shape %r, with or without a leading [%d]" % (name, list(shape), m))
+    if locked.size and (int(locked.min()) < 0 or int(locked.max()) > 0xFFFF):
+        raise ValueError("%s must lie in 0 .. 65535" % name)
+    return np.ascontiguousarray(np.broadcast_to(locked, (m,) + shape), np.uint16)
+
+
+def _lock_pair(lock, locked, m, D, shape, names, attr):
+    if lock is None and locked is None:
+        return None, None
+    if lock is None or locked is None:
+        raise ValueError("%s and %s come together" % names)
+    return _lock_rows(lock, m, D, names[0]), _locked_rows(locked, m, (D,) + shape, names[1], attr)
+
+
 def river_trees(pots, stacks, bet_fractions=(0.5, 1.0), max_raises=2):
     """(trees, tree_of) for spots of per-spot chips: pots and stacks are integer arrays [m]; one river_tree per DISTINCT (pot, stack)
     pair, in the order the pairs first appear, and tree_of uint32 [m] with the index of each spot's tree -- what solve_river_batch takes."""
     return _trees_by_chips(pots, stacks, lambda pot, stack: river_tree(pot, stack, bet_fractions, max_raises))
 
 
-def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=None):
+def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=None, lock=None, locked=None):
     """pk_solve_river on host arrays: board uint8 [m, 5] Card.value, ranges uint16 [m, 2, 1326] over holding_index, one tree for the call,
     dead uint64 [m] masks over canonical card indices (None: none) -> RiverSolution with a leading [m].  A bad spot is reported through
     its status with all-zero outputs; the others are unaffected.
     tree may also be a SEQUENCE of trees (pk_solve_river_trees): spot i is solved with tree[tree_of[i]], tree_of an integer array [m]
-    (None: spot i uses tree i, which needs m trees); every output of spot i is what the call with that one tree gives for it."""
+    (None: spot i uses tree i, which needs m trees); every output of spot i is what the call with that one tree gives for it.
+    lock, locked (pk_solve_river_locked): lock is a bool / integer [D] (every spot the same) or [m, D], nonzero = that row of the strategy
+    is LOCKED to the strategy rule applied to locked -- an integer array of the strategy's shape (any non-negative weights up to 65535; a
+    row of an earlier solution is reproduced unchanged) or a RiverSolution, whose strategy is taken.  CFR+ runs on the other rows; iters
+    may be 0 (every free row: the uniform row).  br ignores the locks, so exploitability is that of the profile as played."""
     board = np.ascontiguousarray(board, np.uint8)
     if board.ndim != 2 or board.shape[1] != 5:
         raise ValueError("board must have shape [m, 5]")
@@ -268,7 +309,18 @@ def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=N
             raise ValueError("dead must have shape [m]")
     value, br = np.zeros((m, 2, L.EQ_HOLDINGS), np.int64), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64)
     status = np.zeros(m, np.uint8)
-    if isinstance(tree, RiverTree):
+    if lock is not None or locked is not None:
+        one = isinstance(tree, RiverTree)
+        if one and tree_of is not None:
+            raise ValueError("tree_of needs a sequence of trees")
+        rows = _TreeRows([tree] if one else tree, MAX_NODES)
+        D = max(len(t.decision_nodes) for t in rows.trees)
+        trees, tree, tree_of = (None, tree, None) if one else (rows.trees, None, _tree_of(tree_of, len(rows.trees), m))
+        lock, locked = _lock_pair(lock, locked, m, D, (4, L.EQ_HOLDINGS), ("lock", "locked"), "strategy")
+        strategy = np.zeros((m, D, 4, L.EQ_HOLDINGS), np.uint16)
+        L.check(L.lib().pk_solve_river_locked(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *rows.args(), L.ptr(tree_of), int(iters),
+                                              L.ptr(lock), L.ptr(locked), L.ptr(strategy), L.ptr(value), L.ptr(br), L.ptr(status)))
+    elif isinstance(tree, RiverTree):
         if tree_of is not None:
             raise ValueError("tree_of needs a sequence of trees")
         strategy = np.zeros((m, len(tree.decision_nodes), 4, L.EQ_HOLDINGS), np.uint16)
@@ -286,11 +338,19 @@ def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=N
 
 
 def solve_river_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None, value_d=None, br_d=None, status_d=None, device=0, stream=None,
-                  tree_of=None):
+                  tree_of=None, lock=None, locked=None):
     """pk_solve_river_d: the same on device-resident buffers (device pointers as ints / c_void_p; the tree stays a host RiverTree; dead_d and
     the outputs may be None), asynchronous on `stream`.  With a SEQUENCE of trees (pk_solve_river_trees_d) tree_of is the DEVICE pointer of
     uint32 [m] and strategy_d holds [m, Dmax, 4, 1326], Dmax the most decision nodes of any tree passed; the trees are packed and queued
-    for upload before the call returns."""
+    for upload before the call returns.  lock, locked (pk_solve_river_locked_d): DEVICE pointers of uint8 [m, Dmax] and uint16
+    [m, Dmax, 4, 1326]; with one RiverTree Dmax is its own D."""
+    if lock is not None or locked is not None:
+        one = isinstance(tree, RiverTree)
+        if one == (tree_of is not None):
+            raise ValueError("tree_of, the device pointer of uint32 [m], comes with a sequence of trees and only with one")
+        L.check(L.lib().pk_solve_river_locked_d(int(device), int(m), board_d, dead_d, ranges_d, *_TreeRows([tree] if one else tree, MAX_NODES).args(),
+                                                tree_of, int(iters), lock, locked, strategy_d, value_d, br_d, status_d, stream))
+        return
     if not isinstance(tree, RiverTree):
         if tree_of is None:
             raise ValueError("a sequence of trees needs tree_of, the device pointer of uint32 [m]")
@@ -303,20 +363,34 @@ def solve_river_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=Non
                                      status_d, stream))
 
 
-def solve_river(board, ranges, tree, iters, dead=(), device=0):
+def solve_river(board, ranges, tree, iters, dead=(), device=0, lock=None, locked=None):
     """One subgame.  board: the five board cards (Card-likes / 'RS' strings / Card.value ints); ranges: [2, 1326] integers 0 .. 65535 over
     holding_index, player 0 (first to act) then player 1; dead: cards known to be out of play.  Raises ValueError for an invalid spot.
     A reach starts at weight << 4 and every split rounds down, so ranges of small integers (1, 2, ...) lose weight on the way down the
-    tree: scale a range so that its largest weight uses the sixteen bits."""
+    tree: scale a range so that its largest weight uses the sixteen bits.  lock bool [D], locked [D, 4, 1326] or a RiverSolution: as
+    solve_river_batch takes them."""
     board = list(board)
     if len(board) != 5:
         raise ValueError("five board cards")
     b = np.array([[_card(c) for c in board]], np.uint8)
     d = np.array([dead if isinstance(dead, (int, np.integer)) else dead_mask(dead)], np.uint64)
-    r = solve_river_batch(b, np.asarray(ranges)[None], tree, iters, d, device=device)[0]
+    r = solve_river_batch(b, np.asarray(ranges)[None], tree, iters, d, device=device, lock=lock, locked=locked)[0]
     if r.status:
         raise ValueError("invalid spot: " + equity_status_text(r.status))
     return r
+
+
+def evaluate_river_batch(board, ranges, tree, strategy, dead=None, device=0, tree_of=None):
+    """The values and best responses of a SUPPLIED strategy: solve_river_batch with every row locked to `strategy` and no iteration.
+    -> an ordinary RiverSolution (solution[i].ev, .exploitability)."""
+    trees = [tree] if isinstance(tree, RiverTree) else list(tree)
+    return solve_river_batch(board, ranges, tree, 0, dead, device=device, tree_of=tree_of,
+                             lock=np.ones(max(len(t.decision_nodes) for t in trees), bool), locked=strategy)
+
+
+def evaluate_river(board, ranges, tree, strategy, dead=(), device=0):
+    """One subgame: the value of `strategy` (integers [D, 4, 1326] or a RiverSolution) and how exploitable it is."""
+    return solve_river(board, ranges, tree, 0, dead, device=device, lock=np.ones(len(tree.decision_nodes), bool), locked=strategy)
 
 
 # ------------------------------------------------------------------------------------------------ the turn solver
@@ -339,6 +413,11 @@ class TurnTree(RiverTree):
         decisions = self.decision_nodes
         self.decision_nodes = [v for v in decisions if not self.river_level[v]]
         self.river_decision_nodes = [v for v in decisions if self.river_level[v]]
+
+    def rows_of(self, player):
+        """(bool [D_t], bool [D_r]): the turn-level and the river-level rows at which `player` acts -- lock and river_lock for that player"""
+        return (np.array([int(self.kind[v]) == int(player) for v in self.decision_nodes], bool),
+                np.array([int(self.kind[v]) == int(player) for v in self.river_decision_nodes], bool))
 
     def __repr__(self):
         return "TurnTree(n=%d, turn decisions=%d, river decisions=%d, pot=%d)" % (self.n, len(self.decision_nodes), len(self.river_decision_nodes), self.pot)
@@ -461,11 +540,15 @@ def turn_grid(tree, m=None):
     return int(L.lib().pk_turn_grid(GRID_MAX if m is None else int(m), nt, nr))
 
 
-def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False, device=0, tree_of=None):
+def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False, device=0, tree_of=None, lock=None, locked=None, river_lock=None,
+                     river_locked=None):
     """pk_solve_turn on host arrays: board uint8 [m, 4] Card.value, ranges uint16 [m, 2, 1326] over holding_index, one TurnTree for the
     call, dead uint64 [m] masks over canonical card indices (None: none) -> TurnSolution with a leading [m].  river_strategy=True also
     returns the river-level strategies (551 616 bytes per river-level decision node and spot).
-    tree may also be a SEQUENCE of TurnTrees with tree_of (pk_solve_turn_trees), as solve_river_batch takes them."""
+    tree may also be a SEQUENCE of TurnTrees with tree_of (pk_solve_turn_trees), as solve_river_batch takes them.
+    lock, locked (turn-level rows) and river_lock, river_locked (river-level rows, each for all river cards at once; river_locked of
+    river_strategy's shape): pk_solve_turn_locked, as solve_river_batch takes them.  A TurnSolution as locked also serves as river_locked
+    where that is None and river_lock is given.  iters may then be 0."""
     board = np.ascontiguousarray(board, np.uint8)
     if board.ndim != 2 or board.shape[1] != 4:
         raise ValueError("board must have shape [m, 4]")
@@ -487,7 +570,18 @@ def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False
     rstrat = np.zeros((m, Dr, 52, 4, L.EQ_HOLDINGS), np.uint16) if river_strategy else None
     value, br = np.zeros((m, 2, L.EQ_HOLDINGS), np.int64), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64)
     status = np.zeros(m, np.uint8)
-    if rows is None:
+    if any(x is not None for x in (lock, locked, river_lock, river_locked)):
+        if river_locked is None and river_lock is not None and isinstance(locked, TurnSolution):
+            river_locked = locked
+        lrows = rows or _TreeRows([tree], TURN_MAX_NODES)
+        if rows is not None:
+            tree, tree_of = None, _tree_of(tree_of, len(trees), m)
+        lock, locked = _lock_pair(lock, locked, m, Dt, (4, L.EQ_HOLDINGS), ("lock", "locked"), "strategy")
+        river_lock, river_locked = _lock_pair(river_lock, river_locked, m, Dr, (52, 4, L.EQ_HOLDINGS), ("river_lock", "river_locked"), "river_strategy")
+        L.check(L.lib().pk_solve_turn_locked(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *lrows.args(), L.ptr(tree_of), int(iters),
+                                             L.ptr(lock), L.ptr(locked), L.ptr(river_lock), L.ptr(river_locked), L.ptr(strategy), L.ptr(rstrat),
+                                             L.ptr(value), L.ptr(br), L.ptr(status)))
+    elif rows is None:
         L.check(L.lib().pk_solve_turn(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *_tree_args(tree), int(iters), L.ptr(strategy),
                                       L.ptr(rstrat), L.ptr(value), L.ptr(br), L.ptr(status)))
     else:
@@ -502,10 +596,19 @@ def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False
 
 
 def solve_turn_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None, river_strategy_d=None, value_d=None, br_d=None, status_d=None,
-                 device=0, stream=None, tree_of=None):
+                 device=0, stream=None, tree_of=None, lock=None, locked=None, river_lock=None, river_locked=None):
     """pk_solve_turn_d: the same on device-resident buffers (device pointers as ints / c_void_p; the tree stays a host TurnTree; dead_d and
     the outputs may be None), asynchronous on `stream`.  With a SEQUENCE of trees (pk_solve_turn_trees_d) tree_of is the DEVICE pointer of
-    uint32 [m], as solve_river_d takes it; the strategies have the rows of the largest tree passed."""
+    uint32 [m], as solve_river_d takes it; the strategies have the rows of the largest tree passed.  lock, locked, river_lock,
+    river_locked (pk_solve_turn_locked_d): DEVICE pointers, as solve_river_d takes them."""
+    if any(x is not None for x in (lock, locked, river_lock, river_locked)):
+        one = isinstance(tree, RiverTree)
+        if one == (tree_of is not None):
+            raise ValueError("tree_of, the device pointer of uint32 [m], comes with a sequence of trees and only with one")
+        L.check(L.lib().pk_solve_turn_locked_d(int(device), int(m), board_d, dead_d, ranges_d, *_TreeRows([tree] if one else tree, TURN_MAX_NODES).args(),
+                                               tree_of, int(iters), lock, locked, river_lock, river_locked, strategy_d, river_strategy_d, value_d, br_d,
+                                               status_d, stream))
+        return
     if not isinstance(tree, RiverTree):
         if tree_of is None:
             raise ValueError("a sequence of trees needs tree_of, the device pointer of uint32 [m]")
@@ -518,7 +621,7 @@ def solve_turn_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None
                                     value_d, br_d, status_d, stream))
 
 
-def solve_turn(board, ranges, tree, iters, dead=(), river_strategy=False, device=0):
+def solve_turn(board, ranges, tree, iters, dead=(), river_strategy=False, device=0, lock=None, locked=None, river_lock=None, river_locked=None):
     """One subgame.  board: the four board cards; ranges: [2, 1326] integers 0 .. 65535 over holding_index, player 0 (first to act on
     both streets) then player 1; dead: cards known to be out of play.  Raises ValueError for an invalid spot.  A reach starts at
     weight << 1 and every split rounds down: scale a range so that its largest weight uses the sixteen bits."""
@@ -527,7 +630,23 @@ def solve_turn(board, ranges, tree, iters, dead=(), river_strategy=False, device
         raise ValueError("four board cards")
     b = np.array([[_card(c) for c in board]], np.uint8)
     d = np.array([dead if isinstance(dead, (int, np.integer)) else dead_mask(dead)], np.uint64)
-    r = solve_turn_batch(b, np.asarray(ranges)[None], tree, iters, d, river_strategy=river_strategy, device=device)[0]
+    r = solve_turn_batch(b, np.asarray(ranges)[None], tree, iters, d, river_strategy=river_strategy, device=device, lock=lock, locked=locked,
+                         river_lock=river_lock, river_locked=river_locked)[0]
     if r.status:
         raise ValueError("invalid spot: " + equity_status_text(r.status))
     return r
+
+
+def evaluate_turn_batch(board, ranges, tree, strategy, river_strategy, dead=None, device=0, tree_of=None, return_river_strategy=False):
+    """The values and best responses of a SUPPLIED strategy pair: solve_turn_batch with every turn-level and river-level row locked and no
+    iteration -> an ordinary TurnSolution (solution[i].ev, .exploitability)."""
+    trees = [tree] if isinstance(tree, RiverTree) else list(tree)
+    return solve_turn_batch(board, ranges, tree, 0, dead, river_strategy=return_river_strategy, device=device, tree_of=tree_of,
+                            lock=np.ones(max(len(t.decision_nodes) for t in trees), bool), locked=strategy,
+                            river_lock=np.ones(max(len(t.river_decision_nodes) for t in trees), bool), river_locked=river_strategy)
+
+
+def evaluate_turn(board, ranges, tree, strategy, river_strategy, dead=(), device=0):
+    """One subgame: the value of (strategy, river_strategy) -- integer arrays or TurnSolutions -- and how exploitable it is."""
+    return solve_turn(board, ranges, tree, 0, dead, device=device, lock=np.ones(len(tree.decision_nodes), bool), locked=strategy,
+                      river_lock=np.ones(len(tree.river_decision_nodes), bool), river_locked=river_strategy)

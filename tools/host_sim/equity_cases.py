@@ -60,6 +60,7 @@ import hist_cluster_spec as CS          # noqa: E402
 import hist_spec as HS                  # noqa: E402
 import preflop_spec as PS               # noqa: E402
 import river_solver_spec as RVS         # noqa: E402
+import solver_lock_spec as SLS           # noqa: E402
 import solver_trees_util as STU         # noqa: E402
 import turn_solver_spec as TSS          # noqa: E402
 import ranged_ev_spec as XS             # noqa: E402
@@ -78,7 +79,8 @@ OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("w
            "herohist": ("hist", "void", "completions", "status"), "preflop": ("win", "tie"),
            "pfhero": ("agg", "win", "tie", "boards", "status"), "pfrvr": ("win", "tie", "tot"),
            "riversolve": ("strategy", "value", "br", "status"), "turnsolve": ("strategy", "river_strategy", "value", "br", "status"),
-           "rivertrees": ("strategy", "value", "br", "status"), "turntrees": ("strategy", "river_strategy", "value", "br", "status")}
+           "rivertrees": ("strategy", "value", "br", "status"), "turntrees": ("strategy", "river_strategy", "value", "br", "status"),
+           "riverlock": ("strategy", "value", "br", "status"), "turnlock": ("strategy", "river_strategy", "value", "br", "status")}
 
 
 class Case:
@@ -1280,6 +1282,136 @@ def turn_trees_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- locked nodes
+def lock_arrays(seed, trees, tree_of, patterns, river=False):
+    """(lock uint8 [m, Dmax], locked uint16 [m, Dmax, (52,) 4, 1326]) for one level of a call.  patterns[i]: "none", "all", "p1" (the rows
+    player 1 acts at), "zero" (every row locked to all-zero weights: the uniform row), "ffff" (a refused spot: every flag set, every weight
+    0xFFFF) or a list of rows.  The weights are random with zeros among them.  What the definition says is NOT READ is 0xFFFF wherever this
+    function knows it: rows past the spot's own D (their flags set), rows whose flag is 0, and action slots from nact on."""
+    rng = np.random.default_rng(seed)
+    m = len(patterns)
+    rows_of = lambda t: (t.river_decision_nodes if river else t.decision_nodes)
+    Dmax = max(len(rows_of(t)) for t in trees)
+    mid = (52,) if river else ()
+    lock = np.zeros((m, Dmax), np.uint8)
+    locked = rng.integers(0, 65536, (m, Dmax) + mid + (4, HOLDINGS)).astype(np.uint16)
+    locked[rng.random(locked.shape) < 0.1] = 0
+    for i, pat in enumerate(patterns):
+        k = int(tree_of[i]) if tree_of is not None else 0
+        if pat == "ffff" or k >= len(trees):
+            lock[i], locked[i] = 0xFF, 0xFFFF
+            continue
+        t = trees[k]
+        nodes = rows_of(t)
+        D = len(nodes)
+        if pat == "none":
+            rows = []
+        elif pat in ("all", "zero"):
+            rows = list(range(D))
+        elif pat == "p1":
+            rows = [r for r, v in enumerate(nodes) if int(t.kind[v]) == 1]
+        else:
+            rows = [r for r in pat if r < D]
+        lock[i, rows] = 1
+        if pat == "zero":
+            locked[i, :D] = 0
+        lock[i, D:], locked[i, D:] = 1, 0xFFFF
+        for r, v in enumerate(nodes):
+            if not lock[i, r]:
+                locked[i, r] = 0xFFFF
+            locked[i, r, ..., t.num_actions(v):, :] = 0xFFFF
+    return lock, locked
+
+
+def lock_case(name, street, pools, trees, tree_of, iters, seed, patterns, river_patterns=None, outputs=None, quick=True, edit=None, no_lock=False, fixture=None):
+    """k_rs_prep / k_ts_prep (+ k_trees_prep where tree_of is given) + k_lock_river_solve / k_lock_turn_solve at a grid of 1 against
+    tests/solver_lock_spec.py; street: 5 (river) or 4 (turn) board cards.  tree_of None: one tree, no tree_of array.  no_lock: the lock
+    arrays are left out of the call (nothing is locked).  fixture: the expected outputs come from tests/golden/solver_lock/<fixture>.npz
+    (written by the spec alone: make.py there, which also holds the recipe of the inputs)."""
+    m = len(pools)
+    if fixture:
+        import importlib.util
+        mk = importlib.util.spec_from_file_location("solver_lock_make", os.path.join(ROOT, "tests", "golden", "solver_lock", "make.py"))
+        LOCKFX = importlib.util.module_from_spec(mk)
+        mk.loader.exec_module(LOCKFX)
+        x = LOCKFX.inputs(fixture)
+        board, dead, ranges, trees, tree_of = x["board"], x["dead"], x["ranges"], [x["tree"]], None
+        lock, locked, rlock, rlocked = x["lock"], x["locked"], x["river_lock"], x["river_locked"]
+        iters = x["iters"]
+    else:
+        board, _, dead = board_spots(seed, [(street, p) for p in pools])
+        board = np.ascontiguousarray(board[:, :street])
+        rng = np.random.default_rng(seed + 1)
+        ranges = rng.integers(0, 65536, (m, 2, HOLDINGS)).astype(np.uint16)
+        for row in ranges.reshape(-1, HOLDINGS):
+            row[rng.integers(0, HOLDINGS, 200)] = 0
+            row[rng.integers(0, HOLDINGS, 100)] = 65535
+        if edit:
+            edit(board, dead)
+        lock, locked = lock_arrays(seed + 2, trees, tree_of, patterns)
+        rlock, rlocked = lock_arrays(seed + 3, trees, tree_of, river_patterns or patterns, river=True) if street == 4 else (None, None)
+    if tree_of is not None:
+        tree_of = np.asarray(tree_of, np.uint32)
+        assert tree_of.shape == (m,)
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [1]), "iters": ("u32", [iters]), **tree_rows(trees, 64 if street == 5 else 128),
+              "tree_of": ("u32", tree_of), "board": ("u8", board), "dead": ("u64", dead), "ranges": ("u16", ranges)}
+    if not no_lock:
+        arrays.update({"lock": ("u8", lock), "locked": ("u16", locked)})
+        if street == 4:
+            arrays.update({"river_lock": ("u8", rlock), "river_locked": ("u16", rlocked)})
+    family = "riverlock" if street == 5 else "turnlock"
+
+    def expect():
+        of = np.zeros(m, np.uint32) if tree_of is None else tree_of
+        if fixture:
+            fx = np.load(os.path.join(ROOT, "tests", "golden", "solver_lock", fixture + ".npz"))
+            return dict(strategy=fx["strategy"][None], value=fx["value"][None].view(np.uint64), br=fx["br"][None].view(np.uint64), status=fx["status"][None])
+        if street == 5:
+            r = SLS.solve_river_batch(board, ranges, trees, of, iters, None if no_lock else lock, locked, dead)
+        else:
+            r = SLS.solve_turn_batch(board, ranges, trees, of, iters, None if no_lock else lock, locked, None if no_lock else rlock, rlocked, dead)
+        return {k: (r[k].view(np.uint64) if k in ("value", "br") else r[k]) for k in OUTPUTS[family]}
+    return Case(name, family, arrays, expect, outputs, quick)
+
+
+def river_lock_cases():
+    """The river solver with locked nodes (names rlock-...), every case at a grid of 1: ONE workgroup takes the spots in turn, so a stale
+    sigma or stale flags of the spot before would show.  NOT part of all_cases()."""
+    from pokerl_amd.solver import river_tree
+    forced, four, chain = STU.forced_river_tree(), STU.four_action_river_tree(), STU.chain_river_tree()
+    small, default = river_tree(100, 50), river_tree(100, 400)
+    cs = [lock_case("rlock-free-all-p1-all-free", 5, (9, 7, 12, 6, 10), [default], None, 2, 91, ["none", "all", "p1", "all", "none"]),
+          lock_case("rlock-refused-with-ffff-between", 5, (9, 8, 10, 7, 9), [small, four], [1, 0, 2, 0, 1], 2, 92, ["p1", "ffff", "ffff", "all", "none"],
+                    edit=break_second_board),
+          lock_case("rlock-all-zero-rows-are-uniform", 5, (8, 11), [four], None, 2, 93, ["zero", [0]]),
+          lock_case("rlock-iters0", 5, (10, 6, 9), [default, four], [0, 1, 0], 0, 94, ["all", "p1", "none"]),
+          lock_case("rlock-pools-4-9-33", 5, (4, 9, 33), [small], [0, 0, 0], 2, 95, ["p1", [1, 2], "all"]),
+          lock_case("rlock-large-after-small-locks-past-its-rows", 5, (8, 7, 9, 6), [forced, chain, small], [0, 1, 2, 1], 1, 96, [[0, 1, 5, 20], [3, 20, 31], "none", "all"]),
+          lock_case("rlock-lock-null", 5, (7, 9), [default], None, 2, 97, ["all", "all"], no_lock=True),
+          lock_case("rlock-status-only", 5, (9, 9, 9), [small, forced], [0, 1, 5], 1, 98, ["all", "ffff", "all"], outputs=("status",), edit=break_second_board)]
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
+def turn_lock_cases():
+    """The turn solver with locked nodes (names tlock-...), every case at a grid of 1: stale packed regret words of the spot before would
+    show too.  NOT part of all_cases()."""
+    from pokerl_amd.solver import turn_tree
+    allin, small = STU.allin_turn_tree(), turn_tree(30, 20, (1.0,), 1)
+    cs = [lock_case("tlock-free-all-p1-all-free", 4, (7, 6, 8, 6, 7), [small], None, 2, 101, ["none", "all", "p1", "all", "none"]),
+          lock_case("tlock-refused-with-ffff-between", 4, (8, 7, 9, 6, 7), [small, allin], [1, 0, 2, 0, 1], 2, 102, ["p1", "ffff", "ffff", "all", "none"],
+                    edit=break_second_board),
+          lock_case("tlock-all-zero-rows-are-uniform", 4, (7, 8), [small], None, 2, 103, ["zero", [0]], ["zero", [1]]),
+          lock_case("tlock-iters0", 4, (8, 6, 7), [small, allin], [0, 1, 0], 0, 104, ["all", "p1", "none"]),
+          lock_case("tlock-pools-5-9-20", 4, (5, 9, 20), [small], [0, 0, 0], 2, 105, ["p1", [1], "all"], ["none", [0, 2], "p1"]),
+          lock_case("tlock-large-after-small-locks-past-its-rows", 4, (7, 6, 8), [allin, small], [0, 1, 0], 1, 106, [[0, 3], [1, 3], "none"], [[1, 3], [0, 3], "all"]),
+          lock_case("tlock-turn-level-only-and-river-level-only", 4, (7, 8), [small], None, 2, 107, ["all", "none"], ["none", "all"]),
+          lock_case("tlock-lock-null", 4, (7, 6), [small], None, 2, 108, ["all", "all"], no_lock=True),
+          lock_case("tlock-p48-fixture", 4, (48,), None, None, None, 109, None, outputs=("strategy", "value", "br", "status"), quick=False, fixture="turn_p48")]
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -1294,7 +1426,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() + river_trees_cases() + turn_trees_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() + river_trees_cases() + turn_trees_cases() + river_lock_cases() + turn_lock_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

@@ -16,6 +16,13 @@ grouped by pot into K single-tree calls queued back to back on the stream; spot-
 
     python tools/river_solver_bench.py --trees 1 --m 512
     python tools/river_solver_bench.py --trees 64 --m 1024 --iters 64
+
+--lock {none,one,all} measures the locked entry (pk_solve_river_locked_d) on the ordinary legs' spots and tree, and
+merges its legs into profiles/solver_lock_bench.json under "river".  none: nothing locked, against pk_solve_river_trees_d with that one tree
+in the same process -- the price of the LOCK instantiation.  one: player 1's rows locked to a plain solution of the same spots, CFR+ for
+player 0.  all: every row locked, no iteration -- evaluations of a supplied strategy per second.
+
+    python tools/river_solver_bench.py --lock none --m 512
 """
 import argparse
 import ctypes as C
@@ -111,6 +118,48 @@ def trees_legs(args, stream, res):
             x.free()
 
 
+def lock_legs(args, stream, res):
+    """--lock (the module's docstring)"""
+    rng = np.random.default_rng(0)
+    board, ranges = subgames(rng, max(args.m))
+    tree = solver.river_tree(100, 400)
+    D = len(tree.decision_nodes)
+    flags = {"none": np.zeros(D, bool), "one": tree.rows_of(1), "all": np.ones(D, bool)}[args.lock]
+    iters = 0 if args.lock == "all" else args.iters
+    for m in args.m:
+        of = np.zeros(m, np.uint32)
+        lock = np.ascontiguousarray(np.broadcast_to(flags, (m, D)), np.uint8)
+        ins = [DeviceBuffer(x.nbytes).upload(x) for x in (np.ascontiguousarray(board[:m]), np.ascontiguousarray(ranges[:m]), of, lock)]
+        strategy, value, br, status = DeviceBuffer(m * D * 4 * H * 2), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m)
+        locked = DeviceBuffer(m * D * 4 * H * 2)
+
+        def plain():
+            solver.solve_river_d(m, ins[0].ptr, ins[1].ptr, [tree], args.iters, strategy_d=strategy.ptr, value_d=value.ptr, br_d=br.ptr, status_d=status.ptr,
+                                 stream=stream, tree_of=ins[2].ptr)
+
+        def with_locks():
+            solver.solve_river_d(m, ins[0].ptr, ins[1].ptr, [tree], iters, strategy_d=strategy.ptr, value_d=value.ptr, br_d=br.ptr, status_d=status.ptr,
+                                 stream=stream, tree_of=ins[2].ptr, lock=ins[3].ptr, locked=locked.ptr)
+
+        # what the rows are locked to: a plain solution of the same spots (device to device, behind the solve on the same stream)
+        solver.solve_river_d(m, ins[0].ptr, ins[1].ptr, [tree], 16, strategy_d=locked.ptr, status_d=status.ptr, stream=stream, tree_of=ins[2].ptr)
+        assert hipmem._lib().hipStreamSynchronize(stream) == 0
+        leg = {}
+        for name, run in (("tree_per_spot_call", plain), ("locked_call", with_locks)) if args.lock == "none" else (("locked_call", with_locks),):
+            us, each, wall, odd = time_stream(run, stream, args.samples, warmup=1)
+            assert not status.download(np.uint8, m).any()
+            v, bb = value.download(np.int64, m * 2 * H), br.download(np.int64, m * 2 * H)
+            assert (bb >= v).all() and v.any()
+            leg[name] = dict(ms=round(us * 1e-3, 3), samples_ms=[round(x * 1e-3, 3) for x in each], host_clock_ms=round(wall * 1e-3, 3), event_anomalies=odd,
+                             solves_per_s=round(m / (us * 1e-6), 1), value_sum=int(v.sum()))
+        if args.lock == "none":
+            assert leg["tree_per_spot_call"]["value_sum"] == leg["locked_call"]["value_sum"]                # nothing locked: the same values
+            leg["ratio_locked_to_tree_per_spot"] = round(leg["locked_call"]["ms"] / leg["tree_per_spot_call"]["ms"], 4)
+        res["lock_%s_m_%d" % (args.lock, m)] = dict(iters=iters, locked_rows=int(flags.sum()), rows=D, **leg)
+        for x in ins + [strategy, value, br, status, locked]:
+            x.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=3)
@@ -118,14 +167,25 @@ def main():
     ap.add_argument("--iters", type=int, default=256)
     ap.add_argument("--spec-iters", type=int, default=0)
     ap.add_argument("--trees", type=int, default=0, help="K: measure the tree-per-spot entry with K trees (1: the indirection alone)")
+    ap.add_argument("--lock", choices=("none", "one", "all"), default=None, help="measure the locked entry: nothing, player 1 or every row locked")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "solver_trees_bench.json" if args.trees else "river_solver_bench.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "solver_lock_bench.json" if args.lock else "solver_trees_bench.json" if args.trees else "river_solver_bench.json")
     if pokerl_amd.device_count() < 1:
         sys.exit("river_solver_bench: no MI355X visible (no fallback)")
     hip = hipmem._lib()
     stream = C.c_void_p()
     assert hip.hipStreamCreateWithFlags(C.byref(stream), 1) == 0
+    if args.lock:
+        ks = kernel_meta.kernels(L.LIB_PATH)
+        res = dict(tool="river_solver_bench --lock", src=L.source_hash(), samples=args.samples)
+        for name in ("k_trees_river_solve", "k_lock_river_solve"):
+            res[name] = dict(vgprs=ks[name]["vgprs"], sgprs=ks[name]["sgprs"], lds=ks[name]["lds"], scratch=ks[name]["private_segment"])
+        lock_legs(args, stream, res)
+        hip.hipStreamDestroy(stream)
+        merge_into(args.out, "river", res)
+        print(json.dumps(res))
+        return
     if args.trees:
         ks = kernel_meta.kernels(L.LIB_PATH)
         res = dict(tool="river_solver_bench --trees", src=L.source_hash(), samples=args.samples)

@@ -15,6 +15,13 @@ does, and merges its legs into profiles/solver_trees_bench.json under "turn": th
 its run of spots) and through ONE tree-per-spot call; K = 1 is the price of the indirection, K > 1 uses turn_tree(60 + 10 k, 400, (1.0,), 1).
 
     python tools/turn_solver_bench.py --trees 1 --m 256
+
+--lock {none,one,all} measures the locked entry (pk_solve_turn_locked_d) as tools/river_solver_bench.py --lock does,
+on the ordinary legs' spots and tree, and merges its legs into profiles/solver_lock_bench.json under "turn": nothing locked against
+pk_solve_turn_trees_d with that one tree; player 1's rows of both levels locked to a plain solution of the same spots; every row locked
+with no iteration.  river_locked takes 6.6 MB of device memory a spot.
+
+    python tools/turn_solver_bench.py --lock none --m 256
 """
 import argparse
 import ctypes as C
@@ -99,20 +106,76 @@ def trees_legs(args, stream, res):
             x.free()
 
 
+def lock_legs(args, stream, res):
+    """--lock (the module's docstring)"""
+    rng = np.random.default_rng(0)
+    board, _, ranges = subgames(rng, max(args.m))
+    tree = solver.turn_tree(100, 400, (1.0,), 1)
+    Dt, Dr = len(tree.decision_nodes), len(tree.river_decision_nodes)
+    t1, r1 = tree.rows_of(1)
+    tf, rf = {"none": (np.zeros(Dt, bool), np.zeros(Dr, bool)), "one": (t1, r1), "all": (np.ones(Dt, bool), np.ones(Dr, bool))}[args.lock]
+    iters = 0 if args.lock == "all" else args.iters
+    for m in args.m:
+        of = np.zeros(m, np.uint32)
+        lock, rlock = (np.ascontiguousarray(np.broadcast_to(f, (m, len(f))), np.uint8) for f in (tf, rf))
+        ins = [DeviceBuffer(x.nbytes).upload(x) for x in (np.ascontiguousarray(board[:m]), np.ascontiguousarray(ranges[:m]), of, lock, rlock)]
+        strategy, value, br, status = DeviceBuffer(m * Dt * 4 * H * 2), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m)
+        locked, rlocked = DeviceBuffer(m * Dt * 4 * H * 2), DeviceBuffer(m * Dr * 52 * 4 * H * 2)
+
+        def plain():
+            solver.solve_turn_d(m, ins[0].ptr, ins[1].ptr, [tree], args.iters, strategy_d=strategy.ptr, value_d=value.ptr, br_d=br.ptr, status_d=status.ptr,
+                                stream=stream, tree_of=ins[2].ptr)
+
+        def with_locks():
+            solver.solve_turn_d(m, ins[0].ptr, ins[1].ptr, [tree], iters, strategy_d=strategy.ptr, value_d=value.ptr, br_d=br.ptr, status_d=status.ptr,
+                                stream=stream, tree_of=ins[2].ptr, lock=ins[3].ptr, locked=locked.ptr, river_lock=ins[4].ptr, river_locked=rlocked.ptr)
+
+        # what the rows are locked to: a plain solution of the same spots (device to device, behind the solve on the same stream)
+        solver.solve_turn_d(m, ins[0].ptr, ins[1].ptr, [tree], 4, strategy_d=locked.ptr, river_strategy_d=rlocked.ptr, status_d=status.ptr, stream=stream,
+                            tree_of=ins[2].ptr)
+        assert hipmem._lib().hipStreamSynchronize(stream) == 0
+        leg = {}
+        for name, run in (("tree_per_spot_call", plain), ("locked_call", with_locks)) if args.lock == "none" else (("locked_call", with_locks),):
+            us, each, wall, odd = time_stream(run, stream, args.samples, warmup=1)
+            assert not status.download(np.uint8, m).any()
+            v, bb = value.download(np.int64, m * 2 * H), br.download(np.int64, m * 2 * H)
+            assert (bb >= v).all() and v.any()
+            leg[name] = dict(ms=round(us * 1e-3, 3), samples_ms=[round(x * 1e-3, 3) for x in each], host_clock_ms=round(wall * 1e-3, 3), event_anomalies=odd,
+                             solves_per_s=round(m / (us * 1e-6), 1), value_sum=int(v.sum()))
+        if args.lock == "none":
+            assert leg["tree_per_spot_call"]["value_sum"] == leg["locked_call"]["value_sum"]                # nothing locked: the same values
+            leg["ratio_locked_to_tree_per_spot"] = round(leg["locked_call"]["ms"] / leg["tree_per_spot_call"]["ms"], 4)
+        res["lock_%s_m_%d" % (args.lock, m)] = dict(iters=iters, locked_rows=[int(tf.sum()), int(rf.sum())], rows=[Dt, Dr], grid=solver.turn_grid([tree], m), **leg)
+        for x in ins + [strategy, value, br, status, locked, rlocked]:
+            x.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=3)
     ap.add_argument("--m", type=int, nargs="+", default=[256, 1024])
     ap.add_argument("--iters", type=int, default=64)
     ap.add_argument("--trees", type=int, default=0, help="K: measure the tree-per-spot entry with K trees (1: the indirection alone)")
+    ap.add_argument("--lock", choices=("none", "one", "all"), default=None, help="measure the locked entry: nothing, player 1 or every row locked")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "solver_trees_bench.json" if args.trees else "turn_solver_bench.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "solver_lock_bench.json" if args.lock else "solver_trees_bench.json" if args.trees else "turn_solver_bench.json")
     if pokerl_amd.device_count() < 1:
         sys.exit("turn_solver_bench: no MI355X visible (no fallback)")
     hip = hipmem._lib()
     stream = C.c_void_p()
     assert hip.hipStreamCreateWithFlags(C.byref(stream), 1) == 0
+    if args.lock:
+        from river_solver_bench import merge_into
+        ks = kernel_meta.kernels(L.LIB_PATH)
+        res = dict(tool="turn_solver_bench --lock", src=L.source_hash(), samples=args.samples)
+        for name in ("k_trees_turn_solve", "k_lock_turn_solve"):
+            res[name] = dict(vgprs=ks[name]["vgprs"], sgprs=ks[name]["sgprs"], lds=ks[name]["lds"], scratch=ks[name]["private_segment"])
+        lock_legs(args, stream, res)
+        hip.hipStreamDestroy(stream)
+        merge_into(args.out, "turn", res)
+        print(json.dumps(res))
+        return
     if args.trees:
         from river_solver_bench import merge_into
         ks = kernel_meta.kernels(L.LIB_PATH)

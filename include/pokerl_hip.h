@@ -1175,6 +1175,70 @@ int pk_solve_turn_locked(int device, size_t m, const uint8_t *board, const uint6
                          const uint32_t *tree_of /*[m], host; NULL with ntrees = 1: tree 0*/, uint32_t iters, const uint8_t *lock,
                          const uint16_t *locked, const uint8_t *river_lock, const uint16_t *river_locked, uint16_t *strategy,
                          uint16_t *river_strategy, int64_t *value, int64_t *br, uint8_t *status);
+
+/* ---- Re-solving: a subgame re-solved from a node of a solution (the numpy restatement: tests/resolve_spec.py).  A
+ * caller who has solved a turn spot and then sees the river card, or has solved a coarse tree and meets a bet between its sizes, hands what the
+ * first solve computed at that node to the next solve.  Everything of "River solver", "Turn solver", "a tree per spot" and "Locked nodes"
+ * holds except what is said here.  A call carries, beside the arguments of pk_solve_river_locked / pk_solve_turn_locked, before `strategy`:
+ *   reach   u32 [m][2][1326]   the root reaches in the solver's own units
+ *   given   i64 [m][2][1326]   (river only) the values at the spot's GIVEN terminal
+ *   at      u8  [m]            the node of the node outputs
+ *   at_card u8  [m]            (turn only) the river card, a card code as on the board, under which a river-level `at` is reported
+ * and after `br`:
+ *   node_reach u32 [m][2][1326], node_value i64 [m][2][1326], node_br i64 [m][2][1326].
+ * Each of them may be NULL.  PK_ABI_VERSION is unchanged: symbols are added only.
+ * ROOT REACHES.  reach != NULL: `ranges` may be NULL and is not read; for valid h, r_p[root][h] = min(reach[i][p][h], LIM), without a shift,
+ * LIM = 2^20 - 1 (river) and 2^17 - 1 (turn): the per-entry bounds of a shifted 16-bit weight, so every BOUND of the solvers holds
+ * unchanged.  Invalid holdings are not read.  reach = ranges << 4 (turn: << 1) gives the locked call's outputs byte for byte.
+ * NODE OUTPUTS.  `at` is NULL exactly when all three node outputs are (PK_E_INVALID_ARG otherwise).  They come from the final pass -- the
+ * one that gives value and br -- at node at[i] of the spot's own tree: node_reach[p][h] = r_p[at][h], node_value[p][h] = u_p[at][h],
+ * node_br[p][h] = the value the best-response pass of p carries at that node (at a terminal: u_p).  Invalid holdings are 0.  At the root
+ * node_value = value, node_br = br and node_reach is the root reach.  Turn solver: at a turn-level node (a chance node is one) the values
+ * are as they stand there, with the factor P - 4; at a river-level node the outputs are those of river card at_card[i], from that card's
+ * pass (the factor P - 4 enters only when the chance node sums the cards), holdings that contain the card are 0; at_card is not read for a
+ * turn-level `at`.  The sum over the pool's cards c of node_value at a chance node's child under c is node_value at the chance node.
+ * STATUS: at[i] >= n of the spot's tree is PK_EQ_BAD_TREE; a river-level at[i] whose at_card[i] is no card of the pool (or a NULL at_card)
+ * is PK_EQ_BAD_CARD; the spot is refused with all-zero outputs and no neighbour is disturbed.  Both are judged only for a spot that is not
+ * refused for another reason.
+ * GIVEN TERMINAL (pk_solve_river_resolve only).  Node kind 6 is a terminal, at most one per tree ("more than one given node"); its put is
+ * not read for payoffs.  At it u_p[h] = clamp(given[i][p][h], +-(2^45 - 1)) for valid h, whatever the reaches, in every pass, the
+ * best-response passes included -- the "terminate" leaf of the re-solving gadget (Burch, Johanson, Bowling 2014): an opponent node above it
+ * chooses per holding between the value it was promised and playing on.  |u| < 2^45 is what every other terminal obeys, so the BOUNDS
+ * hold.  A tree with a given node needs a non-NULL `given` (PK_E_INVALID_ARG); `given` is not read for a spot whose tree has none.  Every
+ * other entry point, pk_solve_turn_resolve included, refuses kind 6 with its own text.
+ * ROOT PUT: no check requires put[root] = 0 and nothing in the definitions does: a subtree re-rooted at one of its nodes keeps the pot
+ * and every node's put, and its passes are those of the original tree below that node.
+ * `reach` must not be `node_reach`, `given` none of value, br, node_value, node_br (PK_E_INVALID_ARG).  In the _d forms the new arrays
+ * are DEVICE memory. */
+int pk_solve_river_resolve_d(int device, size_t m, const uint8_t *board_d /*[m][5]*/, const uint64_t *dead_d /*[m]; NULL: none*/,
+                             const uint16_t *ranges_d /*[m][2][1326]; may be NULL with reach_d*/, uint32_t ntrees, const uint32_t *n /*[ntrees], host*/,
+                             const uint8_t *kind /*[ntrees][64], host*/, const uint8_t *child /*[ntrees][64][4], host*/,
+                             const uint32_t *put /*[ntrees][64][2], host*/, const uint32_t *pot /*[ntrees], host*/,
+                             const uint32_t *tree_of_d /*[m], DEVICE; NULL with ntrees = 1: tree 0*/, uint32_t iters,
+                             const uint8_t *lock_d /*[m][Dmax], DEVICE; NULL: none*/, const uint16_t *locked_d /*[m][Dmax][4][1326], DEVICE*/,
+                             const uint32_t *reach_d /*[m][2][1326]*/, const int64_t *given_d /*[m][2][1326]*/, const uint8_t *at_d /*[m]*/,
+                             uint16_t *strategy_d /*[m][Dmax][4][1326]*/, int64_t *value_d /*[m][2][1326]*/, int64_t *br_d,
+                             uint32_t *node_reach_d /*[m][2][1326]*/, int64_t *node_value_d, int64_t *node_br_d, uint8_t *status_d, void *stream);
+int pk_solve_river_resolve(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees,
+                           const uint32_t *n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot,
+                           const uint32_t *tree_of /*[m], host; NULL with ntrees = 1: tree 0*/, uint32_t iters, const uint8_t *lock,
+                           const uint16_t *locked, const uint32_t *reach, const int64_t *given, const uint8_t *at, uint16_t *strategy,
+                           int64_t *value, int64_t *br, uint32_t *node_reach, int64_t *node_value, int64_t *node_br, uint8_t *status);
+int pk_solve_turn_resolve_d(int device, size_t m, const uint8_t *board_d /*[m][4]*/, const uint64_t *dead_d /*[m]; NULL: none*/,
+                            const uint16_t *ranges_d /*[m][2][1326]; may be NULL with reach_d*/, uint32_t ntrees, const uint32_t *n /*[ntrees], host*/,
+                            const uint8_t *kind /*[ntrees][128], host*/, const uint8_t *child /*[ntrees][128][4], host*/,
+                            const uint32_t *put /*[ntrees][128][2], host*/, const uint32_t *pot /*[ntrees], host*/,
+                            const uint32_t *tree_of_d /*[m], DEVICE; NULL with ntrees = 1: tree 0*/, uint32_t iters,
+                            const uint8_t *lock_d, const uint16_t *locked_d, const uint8_t *river_lock_d, const uint16_t *river_locked_d,
+                            const uint32_t *reach_d /*[m][2][1326]*/, const uint8_t *at_d /*[m]*/, const uint8_t *at_card_d /*[m]*/,
+                            uint16_t *strategy_d, uint16_t *river_strategy_d, int64_t *value_d /*[m][2][1326]*/, int64_t *br_d,
+                            uint32_t *node_reach_d /*[m][2][1326]*/, int64_t *node_value_d, int64_t *node_br_d, uint8_t *status_d, void *stream);
+int pk_solve_turn_resolve(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees,
+                          const uint32_t *n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot,
+                          const uint32_t *tree_of /*[m], host; NULL with ntrees = 1: tree 0*/, uint32_t iters, const uint8_t *lock,
+                          const uint16_t *locked, const uint8_t *river_lock, const uint16_t *river_locked, const uint32_t *reach,
+                          const uint8_t *at, const uint8_t *at_card, uint16_t *strategy, uint16_t *river_strategy, int64_t *value, int64_t *br,
+                          uint32_t *node_reach, int64_t *node_value, int64_t *node_br, uint8_t *status);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

@@ -61,7 +61,8 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_equity_rvr_preflop_d", "pk_equity_rvr_preflop",
            "pk_solve_river_d", "pk_solve_river", "pk_solve_turn_d", "pk_solve_turn", "pk_turn_grid",
            "pk_solve_river_trees_d", "pk_solve_river_trees", "pk_solve_turn_trees_d", "pk_solve_turn_trees", "pk_rs_trees_rows", "pk_ts_trees_rows",
-           "pk_solve_river_locked_d", "pk_solve_river_locked", "pk_solve_turn_locked_d", "pk_solve_turn_locked"]
+           "pk_solve_river_locked_d", "pk_solve_river_locked", "pk_solve_turn_locked_d", "pk_solve_turn_locked",
+           "pk_solve_river_resolve_d", "pk_solve_river_resolve", "pk_solve_turn_resolve_d", "pk_solve_turn_resolve"]
 
 
 class PokerlHipError(RuntimeError):
@@ -224,6 +225,10 @@ def lib():
     L.pk_solve_river_locked.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 6
     L.pk_solve_turn_locked_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 10
     L.pk_solve_turn_locked.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 9
+    L.pk_solve_river_resolve_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 13
+    L.pk_solve_river_resolve.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 12
+    L.pk_solve_turn_resolve_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 16
+    L.pk_solve_turn_resolve.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 15
     L.pk_rs_trees_rows.argtypes = [C.c_uint32] + [_vp] * 3
     L.pk_ts_trees_rows.argtypes = [C.c_uint32] + [_vp] * 5
     for name in SYMBOLS:

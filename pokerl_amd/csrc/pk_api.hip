@@ -2894,13 +2894,17 @@ int pk_equity_rvr_preflop(int device, size_t m, const uint16_t *weights, uint64_
 // with the launch; the work space is the descriptors plus a slice per resident workgroup.  There is no table form.
 static_assert(RS_HOLDINGS == PK_EQ_HOLDINGS, "pk_river_solver.hpp and the ABI header agree");
 // The tree check: the refusal's text, or NULL with `t` filled (nact and row derived)
-static const char *rs_check_tree(uint32_t n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, uint32_t pot, RsTree &t) {
+// (resolve: the re-solving call's check, which also takes one terminal of kind RS_GIVEN -- pokerl_hip.h "Re-solving"; *given: the tree has one)
+static const char *rs_check_tree(uint32_t n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, uint32_t pot, RsTree &t, bool resolve = false,
+                                 bool *given = nullptr) {
     if (n < 1u || n > (uint32_t)RS_MAX_NODES) return ": n outside 1 .. 64";
     t = RsTree{};
     t.n = n; t.pot = pot;
-    uint32_t parents[RS_MAX_NODES] = {0}, rows = 0;
+    uint32_t parents[RS_MAX_NODES] = {0}, rows = 0, givens = 0;
     for (uint32_t v = 0; v < n; ++v) {
-        if (kind[v] > RS_SHOWDOWN) return ": a node kind outside 0 .. 4";
+        if (resolve && kind[v] == RS_GIVEN) {
+            if (++givens > 1u) return ": more than one given node";
+        } else if (kind[v] > RS_SHOWDOWN) return resolve ? ": a node kind outside 0 .. 4 and not 6" : ": a node kind outside 0 .. 4";
         if (v == 0 && kind[v] > RS_P1) return ": the root is not a decision node";
         t.kind[v] = kind[v];
         t.put[v][0] = put[v * 2]; t.put[v][1] = put[v * 2 + 1];
@@ -2925,6 +2929,7 @@ static const char *rs_check_tree(uint32_t n, const uint8_t *kind, const uint8_t 
     }
     for (uint32_t v = 1; v < n; ++v)
         if (parents[v] != 1u) return ": a non-root node does not have exactly one parent";
+    if (given) *given = givens != 0u;
     return nullptr;
 }
 static const char *rs_check(size_t m, bool pointers, uint32_t iters, uint32_t n, const uint8_t *kind, const uint8_t *child, const uint32_t *put,
@@ -3060,7 +3065,7 @@ int pk_solve_turn(int device, size_t m, const uint8_t *board, const uint64_t *de
 // host forms as a piece of the staging, in the device forms behind the work space on the caller's stream (the source is this call's own
 // pageable vector: the runtime has finished with it when hipMemcpyAsync returns, so it may go when the call does).
 static_assert(RS_MAX_TREES == 65536u, "the header's text names the limit");
-struct RsPacked { std::vector<RsTree> trees; uint32_t nmax = 0, Dmax = 0; std::string why; };
+struct RsPacked { std::vector<RsTree> trees; uint32_t nmax = 0, Dmax = 0; bool given = false; std::string why; };
 struct TsPacked { std::vector<TsTree> trees; uint32_t ntmax = 0, nrmax = 0, Dtmax = 0, Drmax = 0; std::string why; };
 static const char *trees_check(size_t m, bool pointers, uint32_t iters, uint32_t ntrees, bool tree_pointers) {
     if (const char *why = eq_bad_m(m)) return why;
@@ -3074,12 +3079,14 @@ static const char *trees_refusal(std::string &text, uint32_t k, const char *why)
     return text.c_str();
 }
 static const char *rs_pack_trees(size_t m, bool pointers, uint32_t iters, uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child,
-                                 const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, RsPacked &p) {
+                                 const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, RsPacked &p, bool resolve = false) {
     if (const char *why = trees_check(m, pointers, iters, ntrees, n && kind && child && put && pot && tree_of)) return why;
     p.trees.resize(ntrees);
     for (uint32_t k = 0; k < ntrees; ++k) {
         const size_t row = (size_t)k * RS_MAX_NODES;
-        if (const char *why = rs_check_tree(n[k], kind + row, child + row * 4, put + row * 2, pot[k], p.trees[k])) return trees_refusal(p.why, k, why);
+        bool given = false;
+        if (const char *why = rs_check_tree(n[k], kind + row, child + row * 4, put + row * 2, pot[k], p.trees[k], resolve, &given)) return trees_refusal(p.why, k, why);
+        p.given = p.given || given;
         uint32_t D = 0;
         for (uint32_t v = 0; v < n[k]; ++v) D += p.trees[k].kind[v] <= RS_P1;
         p.nmax = n[k] > p.nmax ? n[k] : p.nmax;
@@ -3329,6 +3336,136 @@ int pk_solve_turn_locked(int device, size_t m, const uint8_t *board, const uint6
                                 TsTrees{g.at<TsTree>(tr), g.at<uint32_t>(to), p.ntmax, p.nrmax, p.Dtmax, p.Drmax}, ntrees,
                                 TsLock{g.at<uint8_t>(lo), g.at<uint16_t>(ld), g.at<uint8_t>(ro), g.at<uint16_t>(rd)}, iters, m,
                                 TsOut{g.at<uint16_t>(sg), g.at<uint16_t>(rg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
+    });
+}
+
+// ---- re-solving (pokerl_hip.h "Re-solving"): the locked calls with root reaches in the solver's own units, a terminal
+// of given values (river) and the reaches, values and best-response values at one node of each spot's tree.
+static const char *resolve_check(const void *reach, const void *given, const void *at, const void *node_reach, const void *node_value, const void *node_br,
+                                 const void *value, const void *br) {
+    if ((at != nullptr) != (node_reach || node_value || node_br)) return ": at comes with node_reach, node_value or node_br, and only with one of them";
+    if (reach && reach == node_reach) return ": reach and node_reach are the same buffer";
+    if (given && (given == value || given == br || given == node_value || given == node_br)) return ": given and an output are the same buffer";
+    return nullptr;
+}
+static const char *rs_resolve_pack(size_t m, const uint8_t *board, const uint16_t *ranges, const uint8_t *status, uint32_t iters, uint32_t ntrees, const uint32_t *n,
+                                   const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, const uint8_t *lock,
+                                   const uint16_t *locked, const RsResolve &rz, const RsOut &out, RsPacked &p) {
+    if (const char *why = lock_check(iters, ntrees, tree_of)) return why;
+    if (const char *why = lock_pair(lock, locked, out.strategy, ": lock without locked", ": locked and strategy are the same buffer")) return why;
+    if (const char *why = resolve_check(rz.reach, rz.given, rz.at, rz.node_reach, rz.node_value, rz.node_br, out.value, out.br)) return why;
+    if (const char *why = rs_pack_trees(m, board && (ranges || rz.reach) && status, iters ? iters : 1u, ntrees, n, kind, child, put, pot, tree_of ? tree_of : n, p, true))
+        return why;
+    if (p.given && !rz.given) return ": a tree has a given node and given is NULL";
+    return nullptr;
+}
+static const char *ts_resolve_pack(size_t m, const uint8_t *board, const uint16_t *ranges, const uint8_t *status, uint32_t iters, uint32_t ntrees, const uint32_t *n,
+                                   const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, const TsLock &lk,
+                                   const TsResolve &rz, const TsOut &out, TsPacked &p) {
+    if (const char *why = lock_check(iters, ntrees, tree_of)) return why;
+    if (const char *why = lock_pair(lk.lock, lk.locked, out.strategy, ": lock without locked", ": locked and strategy are the same buffer")) return why;
+    if (const char *why = lock_pair(lk.river_lock, lk.river_locked, out.river_strategy, ": river_lock without river_locked",
+                                    ": river_locked and river_strategy are the same buffer"))
+        return why;
+    if (const char *why = resolve_check(rz.reach, nullptr, rz.at, rz.node_reach, rz.node_value, rz.node_br, out.value, out.br)) return why;
+    return ts_pack_trees(m, board && (ranges || rz.reach) && status, iters ? iters : 1u, ntrees, n, kind, child, put, pot, tree_of ? tree_of : n, p);
+}
+
+int pk_solve_river_resolve_d(int device, size_t m, const uint8_t *board_d, const uint64_t *dead_d, const uint16_t *ranges_d, uint32_t ntrees, const uint32_t *n,
+                             const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of_d, uint32_t iters,
+                             const uint8_t *lock_d, const uint16_t *locked_d, const uint32_t *reach_d, const int64_t *given_d, const uint8_t *at_d,
+                             uint16_t *strategy_d, int64_t *value_d, int64_t *br_d, uint32_t *node_reach_d, int64_t *node_value_d, int64_t *node_br_d,
+                             uint8_t *status_d, void *stream) {
+    const char *call = "pk_solve_river_resolve_d";
+    RsPacked p;
+    const RsResolve rz{reach_d, given_d, at_d, node_reach_d, node_value_d, node_br_d};
+    const RsOut out{strategy_d, value_d, br_d, status_d};
+    EQ_REFUSE(g_fail, call, rs_resolve_pack(m, board_d, ranges_d, status_d, iters, ntrees, n, kind, child, put, pot, tree_of_d, lock_d, locked_d, rz, out, p));
+    const bool solve = strategy_d || value_d || br_d || at_d;
+    const size_t ws = rs_work_bytes(m, p.nmax, solve);
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, ws + (solve ? rs_trees_bytes(ntrees) : 0), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        RsTree *trees_d = (RsTree *)(work + ws);
+        if (solve)
+            if (const hipError_t e = hipMemcpyAsync(trees_d, p.trees.data(), (size_t)ntrees * sizeof(RsTree), hipMemcpyHostToDevice, st)) return e;
+        return rs_launch_resolve(st, tab, RsSpots{board_d, dead_d, ranges_d}, RsTrees{trees_d, tree_of_d, p.nmax, p.Dmax}, ntrees, RsLock{lock_d, locked_d}, rz,
+                                 iters, m, out, work);
+    });
+}
+
+int pk_solve_river_resolve(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees, const uint32_t *n,
+                           const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, uint32_t iters,
+                           const uint8_t *lock, const uint16_t *locked, const uint32_t *reach, const int64_t *given, const uint8_t *at, uint16_t *strategy,
+                           int64_t *value, int64_t *br, uint32_t *node_reach, int64_t *node_value, int64_t *node_br, uint8_t *status) {
+    const char *call = "pk_solve_river_resolve";
+    RsPacked p;
+    EQ_REFUSE(g_fail, call, rs_resolve_pack(m, board, ranges, status, iters, ntrees, n, kind, child, put, pot, tree_of, lock, locked,
+                                            RsResolve{reach, given, at, node_reach, node_value, node_br}, RsOut{strategy, value, br, status}, p));
+    const bool solve = strategy || value || br || at;
+    const size_t row = m * 2 * RS_HOLDINGS;
+    Stage g;
+    const int bo = g.in(board, m * 5), de = g.in(dead, m * 8), ra = g.in(reach ? nullptr : ranges, row * 2), to = g.in(tree_of, m * 4);
+    const int tr = g.in(solve ? p.trees.data() : nullptr, (size_t)ntrees * sizeof(RsTree));
+    const int lo = g.in(solve ? lock : nullptr, m * p.Dmax), ld = g.in(solve && lock ? locked : nullptr, m * p.Dmax * 4 * RS_HOLDINGS * 2);
+    const int re = g.in(solve ? reach : nullptr, row * 4), gi = g.in(solve && p.given ? given : nullptr, row * 8), an = g.in(at, m);
+    const int sg = g.out(strategy, m * p.Dmax * 4 * RS_HOLDINGS * 2), va = g.out(value, row * 8), be = g.out(br, row * 8);
+    const int nr = g.out(node_reach, row * 4), nv = g.out(node_value, row * 8), nb = g.out(node_br, row * 8), su = g.out(status, m);
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, rs_work_bytes(m, p.nmax, solve), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return rs_launch_resolve(st, tab, RsSpots{g.at<uint8_t>(bo), g.at<uint64_t>(de), g.at<uint16_t>(ra)},
+                                 RsTrees{g.at<RsTree>(tr), g.at<uint32_t>(to), p.nmax, p.Dmax}, ntrees, RsLock{g.at<uint8_t>(lo), g.at<uint16_t>(ld)},
+                                 RsResolve{g.at<uint32_t>(re), g.at<int64_t>(gi), g.at<uint8_t>(an), g.at<uint32_t>(nr), g.at<int64_t>(nv), g.at<int64_t>(nb)},
+                                 iters, m, RsOut{g.at<uint16_t>(sg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
+    });
+}
+
+int pk_solve_turn_resolve_d(int device, size_t m, const uint8_t *board_d, const uint64_t *dead_d, const uint16_t *ranges_d, uint32_t ntrees, const uint32_t *n,
+                            const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of_d, uint32_t iters,
+                            const uint8_t *lock_d, const uint16_t *locked_d, const uint8_t *river_lock_d, const uint16_t *river_locked_d, const uint32_t *reach_d,
+                            const uint8_t *at_d, const uint8_t *at_card_d, uint16_t *strategy_d, uint16_t *river_strategy_d, int64_t *value_d, int64_t *br_d,
+                            uint32_t *node_reach_d, int64_t *node_value_d, int64_t *node_br_d, uint8_t *status_d, void *stream) {
+    const char *call = "pk_solve_turn_resolve_d";
+    TsPacked p;
+    const TsLock lk{lock_d, locked_d, river_lock_d, river_locked_d};
+    const TsResolve rz{reach_d, at_d, at_card_d, node_reach_d, node_value_d, node_br_d};
+    const TsOut out{strategy_d, river_strategy_d, value_d, br_d, status_d};
+    EQ_REFUSE(g_fail, call, ts_resolve_pack(m, board_d, ranges_d, status_d, iters, ntrees, n, kind, child, put, pot, tree_of_d, lk, rz, out, p));
+    const bool solve = strategy_d || river_strategy_d || value_d || br_d || at_d;
+    const size_t ws = ts_work_bytes(m, p.ntmax, p.nrmax, solve);
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, ws + (solve ? ts_trees_bytes(ntrees) : 0), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        TsTree *trees_d = (TsTree *)(work + ws);
+        if (solve)
+            if (const hipError_t e = hipMemcpyAsync(trees_d, p.trees.data(), (size_t)ntrees * sizeof(TsTree), hipMemcpyHostToDevice, st)) return e;
+        return ts_launch_resolve(st, tab, TsSpots{board_d, dead_d, ranges_d}, TsTrees{trees_d, tree_of_d, p.ntmax, p.nrmax, p.Dtmax, p.Drmax}, ntrees, lk, rz, iters,
+                                 m, out, work);
+    });
+}
+
+int pk_solve_turn_resolve(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees, const uint32_t *n,
+                          const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, uint32_t iters,
+                          const uint8_t *lock, const uint16_t *locked, const uint8_t *river_lock, const uint16_t *river_locked, const uint32_t *reach,
+                          const uint8_t *at, const uint8_t *at_card, uint16_t *strategy, uint16_t *river_strategy, int64_t *value, int64_t *br,
+                          uint32_t *node_reach, int64_t *node_value, int64_t *node_br, uint8_t *status) {
+    const char *call = "pk_solve_turn_resolve";
+    TsPacked p;
+    EQ_REFUSE(g_fail, call, ts_resolve_pack(m, board, ranges, status, iters, ntrees, n, kind, child, put, pot, tree_of, TsLock{lock, locked, river_lock, river_locked},
+                                            TsResolve{reach, at, at_card, node_reach, node_value, node_br}, TsOut{strategy, river_strategy, value, br, status}, p));
+    const bool solve = strategy || river_strategy || value || br || at;
+    const size_t row = m * 2 * RS_HOLDINGS;
+    Stage g;
+    const int bo = g.in(board, m * 4), de = g.in(dead, m * 8), ra = g.in(reach ? nullptr : ranges, row * 2), to = g.in(tree_of, m * 4);
+    const int tr = g.in(solve ? p.trees.data() : nullptr, (size_t)ntrees * sizeof(TsTree));
+    const int lo = g.in(solve ? lock : nullptr, m * p.Dtmax), ld = g.in(solve && lock ? locked : nullptr, m * p.Dtmax * 4 * RS_HOLDINGS * 2);
+    const int ro = g.in(solve ? river_lock : nullptr, m * p.Drmax);
+    const int rd = g.in(solve && river_lock ? river_locked : nullptr, m * p.Drmax * 52 * 4 * RS_HOLDINGS * 2);
+    const int re = g.in(solve ? reach : nullptr, row * 4), an = g.in(at, m), ac = g.in(at ? at_card : nullptr, m);
+    const int sg = g.out(strategy, m * p.Dtmax * 4 * RS_HOLDINGS * 2), rg = g.out(river_strategy, m * p.Drmax * 52 * 4 * RS_HOLDINGS * 2);
+    const int va = g.out(value, row * 8), be = g.out(br, row * 8);
+    const int nr = g.out(node_reach, row * 4), nv = g.out(node_value, row * 8), nb = g.out(node_br, row * 8), su = g.out(status, m);
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, ts_work_bytes(m, p.ntmax, p.nrmax, solve), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return ts_launch_resolve(st, tab, TsSpots{g.at<uint8_t>(bo), g.at<uint64_t>(de), g.at<uint16_t>(ra)},
+                                 TsTrees{g.at<TsTree>(tr), g.at<uint32_t>(to), p.ntmax, p.nrmax, p.Dtmax, p.Drmax}, ntrees,
+                                 TsLock{g.at<uint8_t>(lo), g.at<uint16_t>(ld), g.at<uint8_t>(ro), g.at<uint16_t>(rd)},
+                                 TsResolve{g.at<uint32_t>(re), g.at<uint8_t>(an), g.at<uint8_t>(ac), g.at<uint32_t>(nr), g.at<int64_t>(nv), g.at<int64_t>(nb)}, iters, m,
+                                 TsOut{g.at<uint16_t>(sg), g.at<uint16_t>(rg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
     });
 }
 

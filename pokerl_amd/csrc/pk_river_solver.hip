@@ -21,6 +21,10 @@
 //                   for that tree's n, and writes `strategy` with the call's row stride Dmax, the rows at or past the spot's own D as zeros.
 //   k_lock_river_solve   the same body with LOCK ("Locked nodes"): rows of the strategy fixed by the caller.  A locked node's
 //                   probabilities are formed once per spot from the caller's weights and stay in SG; R and A are left alone there.
+//   k_resolve_prep / k_resolve_river_solve   the same body with RESOLVE ("Re-solving"): the root's reaches come from the
+//                   caller in the solver's own units, a terminal of kind RS_GIVEN takes its values from the caller, and the owners write both
+//                   players' reaches, values and best-response values at the node the spot names.  k_resolve_prep follows the other
+//                   preparation kernels and refuses a spot whose node (or, in the turn solver, river card) does not exist.
 // Ordinary vector stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_river_solver_host.py reads the code object).
 #include <hip/hip_runtime.h>
 
@@ -82,11 +86,14 @@ __global__ void __launch_bounds__(RS_PREP_BLOCK) k_trees_prep(const uint32_t *__
 // LOCK (with PER_SPOT; "Locked nodes"): rows of `lk.lock` fix a decision node's probabilities to the strategy rule applied to
 // `lk.locked`.  They are formed once per spot by the owner of each position and stay in SG at the node's edges: the walk down plays SG as it stands
 // there, the walk up leaves R and A alone, the average-strategy stage writes `strategy` from SG.  A NULL tree_of: every spot uses tree 0.
-template <bool PER_SPOT, bool LOCK = false>
+// RESOLVE (with LOCK; "Re-solving"): rz.reach, where given, is the root's reaches; an RS_GIVEN terminal's values are rz.given's;
+// after the final walk up the owners write rz.node_reach / node_value / node_br at node rz.at[spot], which k_resolve_prep has seen below n.
+template <bool PER_SPOT, bool LOCK = false, bool RESOLVE = false>
 __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, const RsTree *tree, const uint32_t *tree_of,
                                               uint32_t nmax, uint32_t Dmax, const RsSpots &spots, const RsOut &out, char *ws, uint32_t iters, uint32_t m,
-                                              const RsLock &lk = RsLock{}) {
+                                              const RsLock &lk = RsLock{}, const RsResolve &rz = RsResolve{}) {
     static_assert(PER_SPOT || !LOCK, "the locked call has the tree-per-spot form only");
+    static_assert(LOCK || !RESOLVE, "the re-solving call is the locked call with more arguments");
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     __shared__ uint64_t slot[RS_SLOTS];               // key << 11 | pool holding, sorted once per spot; all ones = no holding.  After the
                                                       // sort the same memory holds rs and posof (below)
@@ -151,6 +158,11 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
             for (uint32_t p = 0; p < 2u; ++p) {
                 if (out.value) out.value[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
                 if (out.br) out.br[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
+                if constexpr (RESOLVE) {
+                    if (rz.node_reach) rz.node_reach[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
+                    if (rz.node_value) rz.node_value[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
+                    if (rz.node_br) rz.node_br[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
+                }
             }
             if (out.strategy)
                 for (uint32_t r = 0; r < DS * 4u; ++r) out.strategy[((size_t)spot * DS * 4 + r) * RS_HOLDINGS + h] = 0;
@@ -228,7 +240,15 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
         for (int j = 0; j < RS_PER_LANE; ++j) {
             const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
             if (i >= nh) continue;
-            RR[at(0, i)] = ((uint64_t)w0[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 4) | ((uint64_t)w1[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 36);
+            if constexpr (RESOLVE) {
+                if (rz.reach) {                       // (the solver's own units: no shift, the bound of a shifted weight)
+                    const uint32_t *q = rz.reach + (size_t)spot * 2 * RS_HOLDINGS + PK_IDX(gh[j], RS_HOLDINGS, "reach");
+                    const uint32_t q0 = q[0], q1 = q[RS_HOLDINGS];
+                    RR[at(0, i)] = (uint64_t)(q0 < RS_REACH_MAX ? q0 : RS_REACH_MAX) | ((uint64_t)(q1 < RS_REACH_MAX ? q1 : RS_REACH_MAX) << 32);
+                } else RR[at(0, i)] = ((uint64_t)w0[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 4) | ((uint64_t)w1[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 36);
+            } else {
+                RR[at(0, i)] = ((uint64_t)w0[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 4) | ((uint64_t)w1[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 36);
+            }
             for (uint32_t v = 1; v < n; ++v) { R[at(v, i)] = 0; A[at(v, i)] = 0; }
         }
         // ---- the locked nodes of the spot (bit v: decision node v), and their probabilities into SG: the rule on the caller's weights
@@ -267,6 +287,19 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
 
         // A terminal node: both players' values of every holding from the opponent's reaches (every lane of the workgroup comes here)
         auto terminal = [&](uint32_t node, uint32_t kind) {
+            if constexpr (RESOLVE)
+                if (kind == (uint32_t)RS_GIVEN) {     // the caller's values, whatever the reaches: no order, no sum, no LDS
+#pragma unroll
+                    for (int j = 0; j < RS_PER_LANE; ++j) {
+                        const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                        if (i >= nh) continue;
+                        const int64_t *g = rz.given + (size_t)spot * 2 * RS_HOLDINGS + PK_IDX(gh[j], RS_HOLDINGS, "given");
+                        const int64_t g0 = g[0], g1 = g[RS_HOLDINGS];
+                        U0[at(node, i)] = g0 > RS_GIVEN_MAX ? RS_GIVEN_MAX : g0 < -RS_GIVEN_MAX ? -RS_GIVEN_MAX : g0;
+                        U1[at(node, i)] = g1 > RS_GIVEN_MAX ? RS_GIVEN_MAX : g1 < -RS_GIVEN_MAX ? -RS_GIVEN_MAX : g1;
+                    }
+                    return;
+                }
 #pragma unroll
             for (int j = 0; j < RS_PER_LANE; ++j) {
                 const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
@@ -442,7 +475,12 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
                 }
             }
         }
-        if (!(out.value || out.br)) continue;
+        // (RESOLVE: written as two statements, and without a flag of its own, so that the other instantiations compile as they did)
+        if constexpr (RESOLVE) {
+            if (!(out.value || out.br || rz.node_reach || rz.node_value || rz.node_br)) continue;
+        } else {
+            if (!(out.value || out.br)) continue;
+        }
         // ---- its values and the best responses against it: the walk up carries, beside each player's value, the value of the player
         // who plays the maximum at its own nodes (B0 / B1, in the memory of R / A; a terminal's is its value)
         down(false);
@@ -486,6 +524,20 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
             if (out.value) { out.value[o] = U0[at(0, i)]; out.value[o + RS_HOLDINGS] = U1[at(0, i)]; }
             if (out.br) { out.br[o] = R[at(0, i)]; out.br[o + RS_HOLDINGS] = A[at(0, i)]; }
         }
+        if constexpr (RESOLVE)
+            if (rz.node_reach || rz.node_value || rz.node_br) {
+                const uint32_t an = uniform((uint32_t)rz.at[spot]);
+                const bool leaf = uniform((uint32_t)tr.kind[PK_IDX(an, RS_MAX_NODES, "kind")]) > RS_P1;      // (a terminal's best response is its value)
+#pragma unroll
+                for (int j = 0; j < RS_PER_LANE; ++j) {
+                    const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                    if (i >= nh) continue;
+                    const size_t o = (size_t)spot * 2 * RS_HOLDINGS + gh[j], e = at(an, i);
+                    if (rz.node_reach) { const uint64_t rr = RR[e]; rz.node_reach[o] = (uint32_t)rr; rz.node_reach[o + RS_HOLDINGS] = (uint32_t)(rr >> 32); }
+                    if (rz.node_value) { rz.node_value[o] = U0[e]; rz.node_value[o + RS_HOLDINGS] = U1[e]; }
+                    if (rz.node_br) { rz.node_br[o] = leaf ? U0[e] : R[e]; rz.node_br[o + RS_HOLDINGS] = leaf ? U1[e] : A[e]; }
+                }
+            }
     }
 }
 
@@ -503,6 +555,40 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_trees_river_solve(const uint32_
 __global__ void __launch_bounds__(RS_BLOCK, 2) k_lock_river_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, RsTrees trees, RsLock lk,
                                                                   RsSpots spots, RsOut out, char *ws, uint32_t iters, uint32_t m) {
     rs_solve_body<true, true>(tab, desc, trees.trees, trees.tree_of, trees.nmax, trees.Dmax, spots, out, ws, iters, m, lk);
+}
+
+// the re-solving call: k_lock_river_solve's body with RESOLVE (the name begins with none of the prefixes host tests list kernels by)
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_resolve_river_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, RsTrees trees, RsLock lk,
+                                                                     RsResolve rz, RsSpots spots, RsOut out, char *ws, uint32_t iters, uint32_t m) {
+    rs_solve_body<true, true, true>(tab, desc, trees.trees, trees.tree_of, trees.nmax, trees.Dmax, spots, out, ws, iters, m, lk, rz);
+}
+
+// The last part of a re-solving call's preparation (pk_river_solver.hpp): one lane per spot, only spots that are still good are judged
+struct ResolvePrepArgs {
+    const char *trees;
+    uint32_t stride, river_off;
+    const uint32_t *tree_of;
+    const uint8_t *at, *at_card;
+    uint64_t *desc;
+    uint8_t *status;
+    size_t m;
+};
+__global__ void __launch_bounds__(RS_PREP_BLOCK) k_resolve_prep(ResolvePrepArgs a) {
+    const size_t i = (size_t)blockIdx.x * RS_PREP_BLOCK + threadIdx.x;
+    if (i >= a.m) return;
+    uint64_t *d = a.desc + i * (size_t)RS_DESC_WORDS;
+    if (!(d[2] & 1ull)) return;                       // (refused before: its tree_of may name no tree)
+    const char *t = a.trees + (size_t)(a.tree_of ? a.tree_of[i] : 0u) * a.stride;
+    const uint32_t n = *reinterpret_cast<const uint32_t *>(t), node = a.at[i];
+    uint32_t bad = 0;
+    if (node >= n) bad = PK_EQ_BAD_TREE;
+    else if (a.river_off && reinterpret_cast<const uint8_t *>(t)[a.river_off + node]) {
+        const uint32_t c = a.at_card ? a.at_card[i] : 0xFFu;
+        if (c >= 0x40u || (c & 15u) >= 13u || !((d[1] >> ((c & 15u) * 4u + (c >> 4))) & 1ull)) bad = PK_EQ_BAD_CARD;
+    }
+    if (!bad) return;
+    d[2] &= ~1ull;
+    if (a.status) a.status[i] |= (uint8_t)bad;
 }
 
 namespace pk {
@@ -546,6 +632,27 @@ hipError_t rs_launch_locked(hipStream_t stream, const uint32_t *tab, const RsSpo
     if (e == hipSuccess && trees.tree_of) e = trees_prep_launch(stream, trees.tree_of, ntrees, (uint64_t *)work, out.status, m);
     if (e != hipSuccess || !(out.strategy || out.value || out.br)) return e;   // (status alone: the preparation kernels have written it)
     hipLaunchKernelGGL(k_lock_river_solve, dim3(rs_grid(m)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, lk, spots, out,
+                       work + rs_desc_bytes(m), iters, (uint32_t)m);
+    return hipGetLastError();
+}
+
+hipError_t resolve_prep_launch(hipStream_t stream, const void *trees, uint32_t stride, uint32_t river_off, const uint32_t *tree_of, const uint8_t *at,
+                               const uint8_t *at_card, uint64_t *desc, uint8_t *status, size_t m) {
+    const ResolvePrepArgs a{(const char *)trees, stride, river_off, tree_of, at, at_card, desc, status, m};
+    hipLaunchKernelGGL(k_resolve_prep, dim3((unsigned)((m + RS_PREP_BLOCK - 1) / RS_PREP_BLOCK)), dim3(RS_PREP_BLOCK), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t rs_launch_resolve(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTrees &trees, uint32_t ntrees, const RsLock &lk,
+                             const RsResolve &rz, uint32_t iters, size_t m, const RsOut &out, char *work) {
+    if (m == 0) return hipSuccess;
+    const RsPrepArgs a{spots, out.status, (uint64_t *)work, m};
+    hipLaunchKernelGGL(k_rs_prep, dim3((unsigned)((m + RS_PREP_BLOCK - 1) / RS_PREP_BLOCK)), dim3(RS_PREP_BLOCK), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && trees.tree_of) e = trees_prep_launch(stream, trees.tree_of, ntrees, (uint64_t *)work, out.status, m);
+    if (e == hipSuccess && rz.at) e = resolve_prep_launch(stream, trees.trees, (uint32_t)sizeof(RsTree), 0u, trees.tree_of, rz.at, nullptr, (uint64_t *)work, out.status, m);
+    if (e != hipSuccess || !(out.strategy || out.value || out.br || rz.at)) return e;   // (status alone: the preparation kernels have written it)
+    hipLaunchKernelGGL(k_resolve_river_solve, dim3(rs_grid(m)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, lk, rz, spots, out,
                        work + rs_desc_bytes(m), iters, (uint32_t)m);
     return hipGetLastError();
 }

@@ -25,6 +25,7 @@ constexpr int RS_DESC_WORDS = 3;                         // a spot's descriptor:
 static_assert(RS_BLOCK * RS_PER_LANE >= RS_POOL_HOLDINGS && RS_SORTED >= RS_POOL_HOLDINGS && RS_SORTED % 8 == 0, "a lane owns at most RS_PER_LANE positions");
 
 enum { RS_P0 = 0, RS_P1 = 1, RS_FOLD0 = 2, RS_FOLD1 = 3, RS_SHOWDOWN = 4 };
+enum { RS_GIVEN = 6 };                                   // a terminal whose values the caller supplies ("Re-solving"; 5 is the turn solver's chance node)
 
 // The tree as the kernel takes it (by value: it travels with the launch, so the caller's host arrays are done with when the call returns).
 // nact and row are derived by the host check: a decision node's number of children, and its row of `strategy`.
@@ -83,5 +84,26 @@ struct RsLock {
 // rs_launch_trees's launches with k_lock_river_solve; trees.tree_of may be NULL (every spot uses tree 0: k_trees_prep is not queued).
 hipError_t rs_launch_locked(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTrees &trees, uint32_t ntrees, const RsLock &lk,
                             uint32_t iters, size_t m, const RsOut &out, char *work);
+
+
+// ---- re-solving (include/pokerl_hip.h "Re-solving"): root reaches in the solver's own units, a terminal of given values,
+// and both players' reaches, values and best-response values at one node of the spot's tree.  Any member may be NULL.
+constexpr uint32_t RS_REACH_MAX = (1u << 20) - 1u;       // a root reach: what a u16 weight << 4 never exceeds
+constexpr int64_t RS_GIVEN_MAX = ((int64_t)1 << 45) - 1; // |a given value|: the bound every other terminal's value obeys
+struct RsResolve {
+    const uint32_t *reach;     // [m][2][1326]; non-NULL: the root reaches, `ranges` is not read
+    const int64_t *given;      // [m][2][1326] the values at the spot's RS_GIVEN node
+    const uint8_t *at;         // [m] the node of the node outputs; NULL exactly when all three are
+    uint32_t *node_reach;      // [m][2][1326]
+    int64_t *node_value, *node_br;
+};
+// k_resolve_prep, queued behind the other preparation kernels: one lane per spot that is still good.  at[i] >= the n of the spot's tree:
+// PK_EQ_BAD_TREE; river_off != 0 (the turn solver: the byte offset of TsTree::river) and a river-level at[i] whose at_card[i] is no card of
+// the pool: PK_EQ_BAD_CARD.  Either clears the descriptor's "good" bit.  trees: the packed trees, `stride` bytes each, n their first word.
+hipError_t resolve_prep_launch(hipStream_t stream, const void *trees, uint32_t stride, uint32_t river_off, const uint32_t *tree_of, const uint8_t *at,
+                               const uint8_t *at_card, uint64_t *desc, uint8_t *status, size_t m);
+// rs_launch_locked's launches with k_resolve_prep (where rz.at is given) and k_resolve_river_solve
+hipError_t rs_launch_resolve(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTrees &trees, uint32_t ntrees, const RsLock &lk,
+                             const RsResolve &rz, uint32_t iters, size_t m, const RsOut &out, char *work);
 
 }  // namespace pk

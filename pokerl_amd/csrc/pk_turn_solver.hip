@@ -21,6 +21,10 @@
 //                   have the call's row strides, the rows at or past the spot's own counts are written 0.
 //   k_lock_turn_solve   the same body with LOCK ("Locked nodes"): a locked turn-level node's probabilities stay in SG; a locked
 //                   river-level node's are packed, per card and position, into the regret word of its first edge, which nothing else uses.
+//   k_resolve_turn_solve   the same body with RESOLVE ("Re-solving"): the root's reaches come from the caller in the solver's
+//                   own units, and the owners write both players' reaches, values and best-response values at the node the spot names: a
+//                   turn-level node's after the last walk up, by turn slot; a river-level node's under the river card the spot names, inside
+//                   the final pass's card loop after that card's walk up, by sorted position (the next card rewrites them).
 // Ordinary vector stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_turn_solver_host.py reads the code object).
 #include <hip/hip_runtime.h>
 
@@ -86,11 +90,14 @@ struct TsLevel {
 // word of its first edge under that card -- a word no pass uses, since a locked node's regrets are never read or updated; every pass of the card unpacks
 // them into SG, which the passes of the other cards rewrite.  The last pass of a card unpacks (the average stage) before the best responses take
 // the memory of R and A.  A NULL tree_of: every spot uses tree 0.
-template <bool PER_SPOT, bool LOCK = false>
+// RESOLVE (with LOCK; "Re-solving"): rz.reach, where given, is the root's reaches; the node outputs of node rz.at[spot], which
+// k_resolve_prep (pk_river_solver.hip) has seen below n, and for a river-level node rz.at_card[spot] in the pool.
+template <bool PER_SPOT, bool LOCK = false, bool RESOLVE = false>
 static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, const TsTree *tree, const TsTrees &mx,
                                                      const TsSpots &spots, const TsOut &out, char *ws, uint32_t iters, uint32_t m,
-                                                     const TsLock &lk = TsLock{}) {
+                                                     const TsLock &lk = TsLock{}, const TsResolve &rz = TsResolve{}) {
     static_assert(PER_SPOT || !LOCK, "the locked call has the tree-per-spot form only");
+    static_assert(LOCK || !RESOLVE, "the re-solving call is the locked call with more arguments");
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     __shared__ uint64_t slot[RS_SLOTS];               // key << 11 | turn slot, sorted once per spot and card; all ones = no holding.  Between
                                                       // the sorts the same memory holds rs and posof, or a turn-level fold's reaches
@@ -171,6 +178,22 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
             if (!good) { Dt = 0; Dr = 0; }
         }
         const uint32_t DtS = PER_SPOT ? mx.Dtmax : Dt, DrS = PER_SPOT ? mx.Drmax : Dr;               // the row strides of the strategies
+        // ---- the node of the node outputs; a river-level one: the pool slot of its river card, whose holdings are no holdings there
+        bool nodes = false, at_river = false;
+        uint32_t an = 0, at_cs = 0;
+        uint64_t at_avail = avail;
+        if constexpr (RESOLVE) {
+            nodes = rz.node_reach || rz.node_value || rz.node_br;
+            if (nodes && good) {
+                an = uniform((uint32_t)rz.at[spot]);
+                at_river = is_river(an);
+                if (at_river) {
+                    const uint32_t c = uniform((uint32_t)rz.at_card[spot]), k = (c & 15u) * 4u + (c >> 4);
+                    at_cs = (uint32_t)__popcll(avail & ((1ull << k) - 1ull));
+                    at_avail = avail & ~(1ull << k);
+                }
+            }
+        }
         // ---- zeros: every output at the holdings that are not in the pool, by the lanes of the fixed index h = tid + 512 j
         for (uint32_t h = tid; h < (uint32_t)RS_HOLDINGS; h += RS_BLOCK) {
             uint32_t ca = 0, cb = 1;
@@ -183,6 +206,18 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
             if (out.strategy)
                 for (uint32_t r = 0; r < DtS * 4u; ++r) out.strategy[((size_t)spot * DtS * 4 + r) * RS_HOLDINGS + h] = 0;
         }
+        if constexpr (RESOLVE)
+            if (nodes)
+                for (uint32_t h = tid; h < (uint32_t)RS_HOLDINGS; h += RS_BLOCK) {
+                    uint32_t ca = 0, cb = 1;
+                    unpair(h, ca, cb);
+                    if ((at_avail >> ca) & (at_avail >> cb) & 1ull) continue;
+                    for (uint32_t p = 0; p < 2u; ++p) {
+                        if (rz.node_reach) rz.node_reach[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
+                        if (rz.node_value) rz.node_value[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
+                        if (rz.node_br) rz.node_br[((size_t)spot * 2 + p) * RS_HOLDINGS + h] = 0;
+                    }
+                }
         // ... and of river_strategy every (card, holding) no pass writes: the card or the holding is not in the pool, or the holding has the card
         if (out.river_strategy)
             for (uint32_t e = tid; e < 52u * (uint32_t)RS_HOLDINGS; e += RS_BLOCK) {
@@ -286,7 +321,16 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
         for (int j = 0; j < RS_PER_LANE; ++j) {
             const uint32_t s = tid + (uint32_t)j * RS_BLOCK;
             if (s < nT) {
-                RRt[at(Lturn, 0, s)] = ((uint64_t)w0[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 1) | ((uint64_t)w1[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 33);
+                bool from_ranges = true;
+                if constexpr (RESOLVE)
+                    if (rz.reach) {                   // (the solver's own units: no shift, the bound of a shifted weight)
+                        const uint32_t *q = rz.reach + (size_t)spot * 2 * RS_HOLDINGS + PK_IDX(gh[j], RS_HOLDINGS, "reach");
+                        const uint32_t q0 = q[0], q1 = q[RS_HOLDINGS];
+                        RRt[at(Lturn, 0, s)] = (uint64_t)(q0 < TS_REACH_MAX ? q0 : TS_REACH_MAX) | ((uint64_t)(q1 < TS_REACH_MAX ? q1 : TS_REACH_MAX) << 32);
+                        from_ranges = false;
+                    }
+                if (from_ranges)
+                    RRt[at(Lturn, 0, s)] = ((uint64_t)w0[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 1) | ((uint64_t)w1[PK_IDX(gh[j], RS_HOLDINGS, "range")] << 33);
                 for (uint32_t v = 0; v < nt; ++v) { Rt[(size_t)v * TS_TURN + s] = 0; At[(size_t)v * TS_TURN + s] = 0; }
             }
             if (s < nh)
@@ -690,7 +734,7 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
         };
         for (uint32_t node = 0; node < n; ++node)
             if (!is_river(node) && kind_of(node) <= RS_P1) average(Lturn, node, 0u, false);
-        const bool values = out.value || out.br;
+        const bool values = out.value || out.br || nodes;
         if (!(values || out.river_strategy)) continue;
         // ---- its values and the best responses against it: one walk down serves all three, the walk up carries the maximum beside the value
         if (values) turn_down(false, true);
@@ -720,6 +764,21 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
                     }
                 } else if (is_river(node) && kind <= RS_P1) decide_up_best(L, node, kind);
             }
+            if constexpr (RESOLVE)
+                if (at_river && cs == at_cs) {        // the node's outputs under this card: the next card rewrites what they are read from
+                    const uint32_t k = kind_of(an);
+                    const bool leaf = k > RS_P1;
+                    const size_t nrow = row_of(L, an);
+#pragma unroll
+                    for (int j = 0; j < RS_PER_LANE; ++j) {
+                        const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                        if (i >= nh) continue;
+                        const size_t o = (size_t)spot * 2 * RS_HOLDINGS + PK_IDX(fixed(slotof[tab_at(cs, i)]), RS_HOLDINGS, "holding"), e = at(L, nrow, i);
+                        if (rz.node_reach) { const uint64_t rr = L.RR[e]; rz.node_reach[o] = (uint32_t)rr; rz.node_reach[o + RS_HOLDINGS] = (uint32_t)(rr >> 32); }
+                        if (rz.node_value) { rz.node_value[o] = L.U0[e]; rz.node_value[o + RS_HOLDINGS] = L.U1[e]; }
+                        if (rz.node_br) { rz.node_br[o] = leaf ? L.U0[e] : L.R[e]; rz.node_br[o + RS_HOLDINGS] = leaf ? L.U1[e] : L.A[e]; }
+                    }
+                }
         }
         if (!values) continue;
         __syncthreads();                              // (the last card's sums)
@@ -735,6 +794,21 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
             if (out.value) { out.value[o] = U0t[at(Lturn, 0, s)]; out.value[o + RS_HOLDINGS] = U1t[at(Lturn, 0, s)]; }
             if (out.br) { out.br[o] = Rt[at(Lturn, 0, s)]; out.br[o + RS_HOLDINGS] = At[at(Lturn, 0, s)]; }
         }
+        if constexpr (RESOLVE)
+            if (nodes && !at_river) {
+                const uint32_t k = kind_of(an);
+                const bool leaf = k > RS_P1 && k != (uint32_t)TS_CHANCE;       // (a fold's best response is its value; a chance node carries its sums)
+                const size_t nrow = row_of(Lturn, an);
+#pragma unroll
+                for (int j = 0; j < RS_PER_LANE; ++j) {
+                    const uint32_t s = tid + (uint32_t)j * RS_BLOCK;
+                    if (s >= nT) continue;
+                    const size_t o = (size_t)spot * 2 * RS_HOLDINGS + gh[j], e = at(Lturn, nrow, s);
+                    if (rz.node_reach) { const uint64_t rr = RRt[e]; rz.node_reach[o] = (uint32_t)rr; rz.node_reach[o + RS_HOLDINGS] = (uint32_t)(rr >> 32); }
+                    if (rz.node_value) { rz.node_value[o] = U0t[e]; rz.node_value[o + RS_HOLDINGS] = U1t[e]; }
+                    if (rz.node_br) { rz.node_br[o] = leaf ? U0t[e] : Rt[e]; rz.node_br[o + RS_HOLDINGS] = leaf ? U1t[e] : At[e]; }
+                }
+            }
     }
 }
 
@@ -752,6 +826,12 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_trees_turn_solve(const uint32_t
 __global__ void __launch_bounds__(RS_BLOCK, 2) k_lock_turn_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, TsTrees trees, TsLock lk,
                                                                  TsSpots spots, TsOut out, char *ws, uint32_t iters, uint32_t m) {
     ts_solve_body<true, true>(tab, desc, trees.trees, trees, spots, out, ws, iters, m, lk);
+}
+
+// the re-solving call: k_lock_turn_solve's body with RESOLVE (the name begins with none of the prefixes host tests list kernels by)
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_resolve_turn_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, TsTrees trees, TsLock lk,
+                                                                    TsResolve rz, TsSpots spots, TsOut out, char *ws, uint32_t iters, uint32_t m) {
+    ts_solve_body<true, true, true>(tab, desc, trees.trees, trees, spots, out, ws, iters, m, lk, rz);
 }
 
 namespace pk {
@@ -791,6 +871,22 @@ hipError_t ts_launch_locked(hipStream_t stream, const uint32_t *tab, const TsSpo
     if (e != hipSuccess || !(out.strategy || out.river_strategy || out.value || out.br)) return e;   // (status alone: the preparation kernels have written it)
     hipLaunchKernelGGL(k_lock_turn_solve, dim3(ts_grid(m, trees.ntmax, trees.nrmax)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, lk, spots,
                        out, work + rs_desc_bytes(m), iters, (uint32_t)m);
+    return hipGetLastError();
+}
+
+hipError_t ts_launch_resolve(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTrees &trees, uint32_t ntrees, const TsLock &lk,
+                             const TsResolve &rz, uint32_t iters, size_t m, const TsOut &out, char *work) {
+    if (m == 0) return hipSuccess;
+    const TsPrepArgs a{spots, out.status, (uint64_t *)work, m};
+    hipLaunchKernelGGL(k_ts_prep, dim3((unsigned)((m + TS_PREP_BLOCK - 1) / TS_PREP_BLOCK)), dim3(TS_PREP_BLOCK), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && trees.tree_of) e = trees_prep_launch(stream, trees.tree_of, ntrees, (uint64_t *)work, out.status, m);
+    if (e == hipSuccess && rz.at)
+        e = resolve_prep_launch(stream, trees.trees, (uint32_t)sizeof(TsTree), (uint32_t)offsetof(TsTree, river), trees.tree_of, rz.at, rz.at_card, (uint64_t *)work,
+                                out.status, m);
+    if (e != hipSuccess || !(out.strategy || out.river_strategy || out.value || out.br || rz.at)) return e;   // (status alone: the preparation kernels have written it)
+    hipLaunchKernelGGL(k_resolve_turn_solve, dim3(ts_grid(m, trees.ntmax, trees.nrmax)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, lk, rz,
+                       spots, out, work + rs_desc_bytes(m), iters, (uint32_t)m);
     return hipGetLastError();
 }
 

@@ -87,4 +87,19 @@ struct TsLock {
 hipError_t ts_launch_locked(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTrees &trees, uint32_t ntrees, const TsLock &lk,
                             uint32_t iters, size_t m, const TsOut &out, char *work);
 
+
+// ---- re-solving (include/pokerl_hip.h "Re-solving"): root reaches in the solver's own units, and both players' reaches,
+// values and best-response values at one node of the spot's tree -- of a river-level node under river card at_card.  Any member may be NULL.
+constexpr uint32_t TS_REACH_MAX = (1u << 17) - 1u;       // a root reach: what a u16 weight << 1 never exceeds
+struct TsResolve {
+    const uint32_t *reach;     // [m][2][1326]; non-NULL: the root reaches, `ranges` is not read
+    const uint8_t *at;         // [m] the node of the node outputs; NULL exactly when all three are
+    const uint8_t *at_card;    // [m] a card code, read for a river-level at
+    uint32_t *node_reach;      // [m][2][1326]
+    int64_t *node_value, *node_br;
+};
+// ts_launch_locked's launches with k_resolve_prep (pk_river_solver.hip; where rz.at is given) and k_resolve_turn_solve
+hipError_t ts_launch_resolve(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTrees &trees, uint32_t ntrees, const TsLock &lk,
+                             const TsResolve &rz, uint32_t iters, size_t m, const TsOut &out, char *work);
+
 }  // namespace pk

@@ -8,7 +8,11 @@ and _d functions also take a SEQUENCE of trees with tree_of, the index of each s
 per-spot pots and stacks.
 Locked nodes (pk_solve_river_locked / pk_solve_turn_locked; "Locked nodes"): every solve function takes lock and
 locked (the turn forms also river_lock and river_locked) -- rows of the strategy fixed by the caller, CFR+ on the rest; iters may then be 0.
-evaluate_river / evaluate_turn lock every row: the value and the exploitability of a supplied strategy."""
+evaluate_river / evaluate_turn lock every row: the value and the exploitability of a supplied strategy.
+Re-solving (pk_solve_river_resolve / pk_solve_turn_resolve; "Re-solving"): every solve function takes reach (the root
+reaches in the solver's own units, instead of ranges), at (a node whose reaches, values and best-response values the solution then carries as
+node_reach / node_value / node_br; the turn forms also at_card) and, on the river, given (the values at a tree's KIND_GIVEN terminal).
+subtree / river_subtree re-root a tree, gadget_tree puts the re-solving gadget on top of one, resolve_river does both kinds of re-solving."""
 import math
 
 import numpy as np
@@ -19,6 +23,9 @@ from .judger import _card, dead_mask, equity_status_text, rvr_valid_holdings
 ONE = 32768                 # a probability of 1 in the strategy's fixed point (Q15)
 MAX_NODES, MAX_ACTIONS, MAX_CHIPS, MAX_ITERS = 64, 4, 8191, 4096
 KIND_P0, KIND_P1, KIND_FOLD0, KIND_FOLD1, KIND_SHOWDOWN = 0, 1, 2, 3, 4
+KIND_GIVEN = 6              # a terminal whose values the caller supplies (pk_solve_river_resolve only)
+REACH_MAX, TURN_REACH_MAX = (1 << 20) - 1, (1 << 17) - 1    # the largest root reach: a 16-bit weight << 4 / << 1 never exceeds it
+GIVEN_MAX = (1 << 45) - 1   # the largest |given value|
 NO_CHILD = 0xFF
 GRID_MAX = 256              # the persistent grid's limit (RS_GRID_MAX): spots beyond it wait for a workgroup to come free
 
@@ -43,6 +50,33 @@ class RiverTree:
     def rows_of(self, player):
         """bool [D]: the rows of a solution's strategy at which `player` (0 or 1) acts -- a `lock` argument that fixes that player's play"""
         return np.array([int(self.kind[v]) == int(player) for v in self.decision_nodes], bool)
+
+    def _cut(self, node):
+        """the nodes of the subtree below `node` in index order, and the arguments of the re-rooted tree (pot and every put kept)"""
+        node = int(node)
+        if not 0 <= node < self.n:
+            raise ValueError("no node %d" % node)
+        keep = [node]
+        for v in keep:                                   # (children have larger indices than their parent: sorted at the end)
+            keep += [int(c) for c in self.child[v] if c != NO_CHILD]
+        keep.sort()
+        new = {v: i for i, v in enumerate(keep)}
+        if len(keep) > NO_CHILD:
+            raise ValueError("the subtree has more than %d nodes" % NO_CHILD)
+        child = np.array([[NO_CHILD if c == NO_CHILD else new[int(c)] for c in self.child[v]] for v in keep], np.uint8).reshape(len(keep), 4)
+        actions = None
+        if self._actions is not None:
+            actions = [None if v == node else (new[self._actions[v][0]], self._actions[v][1]) for v in keep]
+        return keep, (self.kind[keep], child, self.put[keep], self.pot, actions)
+
+    def subtree(self, node):
+        """(tree, rows): the RiverTree re-rooted at decision node `node` -- its nodes renumbered in index order, pot and every put kept, so
+        that its passes are those of this tree below the node -- and rows, the indices [D_sub] of its rows in this tree's strategy."""
+        keep, args = self._cut(node)
+        if self.kind[int(node)] > KIND_P1:
+            raise ValueError("node %d is not a decision node" % int(node))
+        rows = np.array([self.decision_nodes.index(v) for v in keep if self.kind[v] <= KIND_P1], np.int64)
+        return RiverTree(*args), rows
 
     def label(self, node):
         """The actions that lead to `node`, such as "0:check 1:bet 50" ("" for the root)."""
@@ -140,19 +174,30 @@ class RiverSolution:
     the most decision nodes of any tree passed); solution[i] is an ordinary single solution with tree trees[tree_of[i]] and the strategy
     cut to that tree's own rows (no tree and no row where tree_of[i] names none: status PK_EQ_BAD_TREE)."""
 
-    def __init__(self, tree, ranges, strategy, value, br, status, valid, trees=None, tree_of=None):
+    _UNIT = 16                  # a root reach per unit of range weight
+
+    def __init__(self, tree, ranges, strategy, value, br, status, valid, trees=None, tree_of=None, node=None, reach=None):
         self.tree, self.ranges, self.strategy, self.value, self.br, self.status, self.valid = tree, ranges, strategy, value, br, status, valid
         self.trees, self.tree_of = trees, tree_of
+        # re-solving: the root reaches the call was given (None: ranges), and the outputs at the node `at` (None when not asked for)
+        self.reach = reach
+        self.node_reach, self.node_value, self.node_br = node if node is not None else (None, None, None)
 
     def __getitem__(self, i):
         tree, strategy = self.tree, self.strategy[i]
         if self.trees is not None:
             tree = _spot_tree(self.trees, self.tree_of, i)
             strategy = strategy[:len(tree.decision_nodes) if tree is not None else 0]
-        return RiverSolution(tree, self.ranges[i], strategy, self.value[i], self.br[i], self.status[i], self.valid[i])
+        return RiverSolution(tree, _ith(self.ranges, i), strategy, self.value[i], self.br[i], self.status[i], self.valid[i],
+                             node=_ith_node(self, i), reach=_ith(self.reach, i))
+
+    def _weights(self):
+        """(w int64 [2, 1326], unit): the weights ev and exploitability reduce by -- the root reaches where the call was given them
+        (unit 1), the ranges otherwise (a reach is `unit` times a weight)"""
+        return (self.ranges, self._UNIT) if self.reach is None else (self.reach, 1)
 
     def _pair_weight(self):
-        w = self.ranges.astype(np.int64) * self.valid
+        w = self._weights()[0].astype(np.int64) * self.valid
         a = np.array([a for b in range(52) for a in range(b)])
         b = np.array([b for b in range(52) for a in range(b)])
         per_card = np.zeros((2, 52), np.int64)
@@ -167,17 +212,20 @@ class RiverSolution:
 
     @property
     def ev(self):
-        """chips per player: sum_h w_p[h] value[p][h] / (32 sum over disjoint pairs of w_0 w_1); Python integers, one division each"""
+        """chips per player: sum_h w_p[h] value[p][h] / (32 sum over disjoint pairs of w_0 w_1); Python integers, one division each
+        (solved from root reaches: w is the reach and the factor 2)"""
         self._one()
-        den = 32 * self._pair_weight()
-        return tuple(sum(int(w) * int(v) for w, v in zip(self.ranges[p], self.value[p])) / den if den else float("nan") for p in (0, 1))
+        w, unit = self._weights()
+        den = 2 * unit * self._pair_weight()
+        return tuple(sum(int(a) * int(v) for a, v in zip(w[p], self.value[p])) / den if den else float("nan") for p in (0, 1))
 
     @property
     def exploitability(self):
         """sum_p (br_p - value_p) reduced the same way, in chips"""
         self._one()
-        den = 32 * self._pair_weight()
-        num = sum(int(w) * (int(b) - int(v)) for p in (0, 1) for w, b, v in zip(self.ranges[p], self.br[p], self.value[p]))
+        w, unit = self._weights()
+        den = 2 * unit * self._pair_weight()
+        num = sum(int(a) * (int(b) - int(v)) for p in (0, 1) for a, b, v in zip(w[p], self.br[p], self.value[p]))
         return num / den if den else float("nan")
 
     def probabilities(self, node):
@@ -190,6 +238,14 @@ class RiverSolution:
 
     def __repr__(self):
         return "RiverSolution(status=%r)" % (self.status,)
+
+
+def _ith(a, i):
+    return None if a is None else a[i]
+
+
+def _ith_node(sol, i):
+    return None if sol.node_reach is None else (sol.node_reach[i], sol.node_value[i], sol.node_br[i])
 
 
 def _tree_args(tree):
@@ -280,13 +336,80 @@ def _lock_pair(lock, locked, m, D, shape, names, attr):
     return _lock_rows(lock, m, D, names[0]), _locked_rows(locked, m, (D,) + shape, names[1], attr)
 
 
+def _resolve_ranges(ranges, reach, m, limit):
+    """(ranges uint16 [m, 2, 1326] or None, reach uint32 [m, 2, 1326] or None): one of them must be given; a reach above `limit` is refused"""
+    if ranges is None and reach is None:
+        raise ValueError("ranges or reach")
+    if ranges is not None:
+        ranges = np.ascontiguousarray(ranges, np.uint16)
+        if ranges.shape != (m, 2, L.EQ_HOLDINGS):
+            raise ValueError("ranges must have shape [m, 2, 1326]")
+    if reach is not None:
+        reach = np.asarray(reach)
+        if reach.shape != (m, 2, L.EQ_HOLDINGS) or reach.dtype.kind not in "iu":
+            raise ValueError("reach must be an integer array of shape [m, 2, 1326]")
+        if reach.size and (int(reach.min()) < 0 or int(reach.max()) > limit):
+            raise ValueError("reach must lie in 0 .. %d" % limit)
+        reach = np.ascontiguousarray(reach, np.uint32)
+    return ranges, reach
+
+
+def _resolve_at(at, m, name="at"):
+    if at is None:
+        return None
+    at = np.asarray(at)
+    if at.dtype.kind not in "iu" or at.shape not in ((), (m,)):
+        raise ValueError("%s must be an integer or an integer array of shape [m]" % name)
+    if at.size and (int(at.min()) < 0 or int(at.max()) > 255):
+        raise ValueError("%s must lie in 0 .. 255" % name)
+    return np.ascontiguousarray(np.broadcast_to(at, (m,)), np.uint8)
+
+
+def _resolve_given(given, m):
+    if given is None:
+        return None
+    given = np.asarray(given)
+    if given.shape != (m, 2, L.EQ_HOLDINGS) or given.dtype.kind not in "iu":
+        raise ValueError("given must be an integer array of shape [m, 2, 1326]")
+    if given.size and (int(given.min()) < -GIVEN_MAX or int(given.max()) > GIVEN_MAX):
+        raise ValueError("given must lie within +- (2^45 - 1)")
+    return np.ascontiguousarray(given, np.int64)
+
+
+def _node_outputs(at, m):
+    if at is None:
+        return None
+    return (np.zeros((m, 2, L.EQ_HOLDINGS), np.uint32), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64))
+
+
+def gadget_tree(tree, opponent):
+    """The re-solving gadget on top of `tree` (Burch, Johanson, Bowling 2014) -> a RiverTree of tree.n + 2 nodes: node 0 is a decision node
+    of `opponent` with the children [1, 2], node 1 the KIND_GIVEN terminal ("terminate": the opponent takes the value it was promised),
+    node 2 the old root ("follow"); the old nodes are shifted by 2, pot and every put kept.  Row 0 of a solution's strategy is the gadget's,
+    rows 1 .. are `tree`'s."""
+    opponent = int(opponent)
+    if opponent not in (0, 1):
+        raise ValueError("opponent must be 0 or 1")
+    if tree.n + 2 > MAX_NODES:
+        raise ValueError("the gadget tree has more than %d nodes" % MAX_NODES)
+    kind = np.concatenate([np.array([opponent, KIND_GIVEN], np.uint8), tree.kind])
+    child = np.where(tree.child == NO_CHILD, NO_CHILD, tree.child.astype(np.int64) + 2)
+    child = np.concatenate([np.array([[1, 2, NO_CHILD, NO_CHILD], [NO_CHILD] * 4], np.int64), child]).astype(np.uint8)
+    put = np.concatenate([tree.put[:1], tree.put[:1], tree.put])
+    actions = [None, (0, "%d:terminate" % opponent), (0, "%d:follow" % opponent)]
+    actions += [None if a is None else (a[0] + 2, a[1]) for a in (tree._actions or [None] * tree.n)][1:]
+    if tree._actions is None:
+        actions = None
+    return RiverTree(kind, child, put, tree.pot, actions)
+
+
 def river_trees(pots, stacks, bet_fractions=(0.5, 1.0), max_raises=2):
     """(trees, tree_of) for spots of per-spot chips: pots and stacks are integer arrays [m]; one river_tree per DISTINCT (pot, stack)
     pair, in the order the pairs first appear, and tree_of uint32 [m] with the index of each spot's tree -- what solve_river_batch takes."""
     return _trees_by_chips(pots, stacks, lambda pot, stack: river_tree(pot, stack, bet_fractions, max_raises))
 
 
-def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=None, lock=None, locked=None):
+def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=None, lock=None, locked=None, reach=None, given=None, at=None):
     """pk_solve_river on host arrays: board uint8 [m, 5] Card.value, ranges uint16 [m, 2, 1326] over holding_index, one tree for the call,
     dead uint64 [m] masks over canonical card indices (None: none) -> RiverSolution with a leading [m].  A bad spot is reported through
     its status with all-zero outputs; the others are unaffected.
@@ -295,21 +418,26 @@ def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=N
     lock, locked (pk_solve_river_locked): lock is a bool / integer [D] (every spot the same) or [m, D], nonzero = that row of the strategy
     is LOCKED to the strategy rule applied to locked -- an integer array of the strategy's shape (any non-negative weights up to 65535; a
     row of an earlier solution is reproduced unchanged) or a RiverSolution, whose strategy is taken.  CFR+ runs on the other rows; iters
-    may be 0 (every free row: the uniform row).  br ignores the locks, so exploitability is that of the profile as played."""
+    may be 0 (every free row: the uniform row).  br ignores the locks, so exploitability is that of the profile as played.
+    reach, given, at (pk_solve_river_resolve): reach integers [m, 2, 1326] up to 2^20 - 1, the root reaches in the solver's own units
+    (ranges may then be None; ranges << 4 is the same call); given integers [m, 2, 1326] within +- (2^45 - 1), the values at a tree's
+    KIND_GIVEN terminal; at an integer or integers [m], the node whose reaches, values and best-response values the solution carries as
+    node_reach, node_value, node_br.  A value outside those bounds is a ValueError here (the library's device forms clamp)."""
     board = np.ascontiguousarray(board, np.uint8)
     if board.ndim != 2 or board.shape[1] != 5:
         raise ValueError("board must have shape [m, 5]")
     m = board.shape[0]
-    ranges = np.ascontiguousarray(ranges, np.uint16)
-    if ranges.shape != (m, 2, L.EQ_HOLDINGS):
-        raise ValueError("ranges must have shape [m, 2, 1326]")
+    resolve = reach is not None or given is not None or at is not None
+    ranges, reach = _resolve_ranges(ranges, reach, m, REACH_MAX)
+    given, at = _resolve_given(given, m), _resolve_at(at, m)
+    node = _node_outputs(at, m)
     if dead is not None:
         dead = np.ascontiguousarray(dead, np.uint64)
         if dead.shape != (m,):
             raise ValueError("dead must have shape [m]")
     value, br = np.zeros((m, 2, L.EQ_HOLDINGS), np.int64), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64)
     status = np.zeros(m, np.uint8)
-    if lock is not None or locked is not None:
+    if resolve or lock is not None or locked is not None:
         one = isinstance(tree, RiverTree)
         if one and tree_of is not None:
             raise ValueError("tree_of needs a sequence of trees")
@@ -318,8 +446,14 @@ def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=N
         trees, tree, tree_of = (None, tree, None) if one else (rows.trees, None, _tree_of(tree_of, len(rows.trees), m))
         lock, locked = _lock_pair(lock, locked, m, D, (4, L.EQ_HOLDINGS), ("lock", "locked"), "strategy")
         strategy = np.zeros((m, D, 4, L.EQ_HOLDINGS), np.uint16)
-        L.check(L.lib().pk_solve_river_locked(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *rows.args(), L.ptr(tree_of), int(iters),
-                                              L.ptr(lock), L.ptr(locked), L.ptr(strategy), L.ptr(value), L.ptr(br), L.ptr(status)))
+        if resolve:
+            nr, nv, nb = node or (None, None, None)
+            L.check(L.lib().pk_solve_river_resolve(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *rows.args(), L.ptr(tree_of), int(iters),
+                                                   L.ptr(lock), L.ptr(locked), L.ptr(reach), L.ptr(given), L.ptr(at), L.ptr(strategy), L.ptr(value),
+                                                   L.ptr(br), L.ptr(nr), L.ptr(nv), L.ptr(nb), L.ptr(status)))
+        else:
+            L.check(L.lib().pk_solve_river_locked(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *rows.args(), L.ptr(tree_of), int(iters),
+                                                  L.ptr(lock), L.ptr(locked), L.ptr(strategy), L.ptr(value), L.ptr(br), L.ptr(status)))
     elif isinstance(tree, RiverTree):
         if tree_of is not None:
             raise ValueError("tree_of needs a sequence of trees")
@@ -334,16 +468,25 @@ def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=N
         L.check(L.lib().pk_solve_river_trees(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *rows.args(), L.ptr(tree_of), int(iters),
                                              L.ptr(strategy), L.ptr(value), L.ptr(br), L.ptr(status)))
     valid = rvr_valid_holdings(board, np.full(m, 5, np.uint8), dead) & (status == 0)[:, None]
-    return RiverSolution(tree, ranges, strategy, value, br, status, valid, trees, tree_of)
+    return RiverSolution(tree, ranges, strategy, value, br, status, valid, trees, tree_of, node=node, reach=reach)
 
 
 def solve_river_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None, value_d=None, br_d=None, status_d=None, device=0, stream=None,
-                  tree_of=None, lock=None, locked=None):
+                  tree_of=None, lock=None, locked=None, reach=None, given=None, at=None, node_reach_d=None, node_value_d=None, node_br_d=None):
     """pk_solve_river_d: the same on device-resident buffers (device pointers as ints / c_void_p; the tree stays a host RiverTree; dead_d and
     the outputs may be None), asynchronous on `stream`.  With a SEQUENCE of trees (pk_solve_river_trees_d) tree_of is the DEVICE pointer of
     uint32 [m] and strategy_d holds [m, Dmax, 4, 1326], Dmax the most decision nodes of any tree passed; the trees are packed and queued
     for upload before the call returns.  lock, locked (pk_solve_river_locked_d): DEVICE pointers of uint8 [m, Dmax] and uint16
-    [m, Dmax, 4, 1326]; with one RiverTree Dmax is its own D."""
+    [m, Dmax, 4, 1326]; with one RiverTree Dmax is its own D.  reach, given, at and node_reach_d, node_value_d, node_br_d
+    (pk_solve_river_resolve_d): DEVICE pointers of uint32 / int64 [m, 2, 1326] and uint8 [m]; ranges_d may then be None."""
+    if any(x is not None for x in (reach, given, at, node_reach_d, node_value_d, node_br_d)):
+        one = isinstance(tree, RiverTree)
+        if one == (tree_of is not None):
+            raise ValueError("tree_of, the device pointer of uint32 [m], comes with a sequence of trees and only with one")
+        L.check(L.lib().pk_solve_river_resolve_d(int(device), int(m), board_d, dead_d, ranges_d, *_TreeRows([tree] if one else tree, MAX_NODES).args(),
+                                                 tree_of, int(iters), lock, locked, reach, given, at, strategy_d, value_d, br_d, node_reach_d,
+                                                 node_value_d, node_br_d, status_d, stream))
+        return
     if lock is not None or locked is not None:
         one = isinstance(tree, RiverTree)
         if one == (tree_of is not None):
@@ -363,18 +506,23 @@ def solve_river_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=Non
                                      status_d, stream))
 
 
-def solve_river(board, ranges, tree, iters, dead=(), device=0, lock=None, locked=None):
+def _one_spot(a):
+    return None if a is None else np.asarray(a)[None]
+
+
+def solve_river(board, ranges, tree, iters, dead=(), device=0, lock=None, locked=None, reach=None, given=None, at=None):
     """One subgame.  board: the five board cards (Card-likes / 'RS' strings / Card.value ints); ranges: [2, 1326] integers 0 .. 65535 over
     holding_index, player 0 (first to act) then player 1; dead: cards known to be out of play.  Raises ValueError for an invalid spot.
     A reach starts at weight << 4 and every split rounds down, so ranges of small integers (1, 2, ...) lose weight on the way down the
     tree: scale a range so that its largest weight uses the sixteen bits.  lock bool [D], locked [D, 4, 1326] or a RiverSolution: as
-    solve_river_batch takes them."""
+    solve_river_batch takes them; so are reach [2, 1326] (ranges may then be None), given [2, 1326] and at (a node index)."""
     board = list(board)
     if len(board) != 5:
         raise ValueError("five board cards")
     b = np.array([[_card(c) for c in board]], np.uint8)
     d = np.array([dead if isinstance(dead, (int, np.integer)) else dead_mask(dead)], np.uint64)
-    r = solve_river_batch(b, np.asarray(ranges)[None], tree, iters, d, device=device, lock=lock, locked=locked)[0]
+    r = solve_river_batch(b, _one_spot(ranges), tree, iters, d, device=device, lock=lock, locked=locked, reach=_one_spot(reach), given=_one_spot(given),
+                          at=at)[0]
     if r.status:
         raise ValueError("invalid spot: " + equity_status_text(r.status))
     return r
@@ -391,6 +539,26 @@ def evaluate_river_batch(board, ranges, tree, strategy, dead=None, device=0, tre
 def evaluate_river(board, ranges, tree, strategy, dead=(), device=0):
     """One subgame: the value of `strategy` (integers [D, 4, 1326] or a RiverSolution) and how exploitable it is."""
     return solve_river(board, ranges, tree, 0, dead, device=device, lock=np.ones(len(tree.decision_nodes), bool), locked=strategy)
+
+
+def resolve_river(board, tree, reach, iters, hero, opponent_values=None, dead=(), device=0):
+    """Re-solve the river subgame `tree` for player `hero` from the reaches [2, 1326] at its root -- node_reach of the solve that led here.
+    Without opponent_values: UNSAFE re-solving, an ordinary solve from those reaches.  With opponent_values (integers [1326]: the
+    opponent's counterfactual values at the root, such as node_br[1 - hero] of that solve): SAFE re-solving through gadget_tree -- the
+    opponent chooses per holding between the value it was promised and playing on, and enters with the same reach for every holding (the
+    largest entry of its row of `reach`), as the gadget prescribes.  -> a RiverSolution on `tree`: the gadget's row is cut off the
+    strategy; value and br are those at the gadget's root."""
+    hero = int(hero)
+    if hero not in (0, 1):
+        raise ValueError("hero must be 0 or 1")
+    reach = np.array(reach, np.int64).reshape(2, L.EQ_HOLDINGS)
+    if opponent_values is None:
+        return solve_river(board, None, tree, iters, dead, device=device, reach=reach)
+    given = np.zeros((2, L.EQ_HOLDINGS), np.int64)
+    given[1 - hero] = np.asarray(opponent_values).reshape(L.EQ_HOLDINGS)
+    reach[1 - hero] = int(reach[1 - hero].max())
+    r = solve_river(board, None, gadget_tree(tree, 1 - hero), iters, dead, device=device, reach=reach, given=given)
+    return RiverSolution(tree, None, r.strategy[1:], r.value, r.br, r.status, r.valid, reach=r.reach)
 
 
 # ------------------------------------------------------------------------------------------------ the turn solver
@@ -413,6 +581,27 @@ class TurnTree(RiverTree):
         decisions = self.decision_nodes
         self.decision_nodes = [v for v in decisions if not self.river_level[v]]
         self.river_decision_nodes = [v for v in decisions if self.river_level[v]]
+
+    def subtree(self, node):
+        """(tree, rows, river_rows): the TurnTree re-rooted at the turn-level decision node `node` (pot and every put kept), and the indices
+        of its turn-level and river-level rows in this tree's strategy and river_strategy."""
+        node = int(node)
+        keep, args = self._cut(node)
+        if self.river_level[node] or self.kind[node] > KIND_P1:
+            raise ValueError("node %d is not a turn-level decision node" % node)
+        rows = np.array([self.decision_nodes.index(v) for v in keep if v in self.decision_nodes], np.int64)
+        river_rows = np.array([self.river_decision_nodes.index(v) for v in keep if v in self.river_decision_nodes], np.int64)
+        return TurnTree(*args), rows, river_rows
+
+    def river_subtree(self, node):
+        """(tree, rows): the RiverTree below the river-level decision node `node` (pot and every put kept) -- what the river solver takes
+        on the five-card board -- and the indices of its rows in this tree's river_strategy."""
+        node = int(node)
+        keep, args = self._cut(node)
+        if not self.river_level[node] or self.kind[node] > KIND_P1:
+            raise ValueError("node %d is not a river-level decision node" % node)
+        rows = np.array([self.river_decision_nodes.index(v) for v in keep if self.kind[v] <= KIND_P1], np.int64)
+        return RiverTree(*args), rows
 
     def rows_of(self, player):
         """(bool [D_t], bool [D_r]): the turn-level and the river-level rows at which `player` acts -- lock and river_lock for that player"""
@@ -459,10 +648,14 @@ class TurnSolution:
     have the rows of the largest tree passed; solution[i] is an ordinary single solution with tree trees[tree_of[i]] and both strategies
     cut to that tree's own rows."""
 
-    def __init__(self, tree, ranges, strategy, river_strategy, value, br, status, valid, pool, trees=None, tree_of=None):
+    _UNIT = 2                   # a root reach per unit of range weight
+
+    def __init__(self, tree, ranges, strategy, river_strategy, value, br, status, valid, pool, trees=None, tree_of=None, node=None, reach=None):
         self.tree, self.ranges, self.strategy, self.river_strategy = tree, ranges, strategy, river_strategy
         self.value, self.br, self.status, self.valid, self.pool = value, br, status, valid, pool
         self.trees, self.tree_of = trees, tree_of
+        self.reach = reach
+        self.node_reach, self.node_value, self.node_br = node if node is not None else (None, None, None)
 
     def __getitem__(self, i):
         tree, strategy, rstrat = self.tree, self.strategy[i], None if self.river_strategy is None else self.river_strategy[i]
@@ -471,8 +664,10 @@ class TurnSolution:
             strategy = strategy[:len(tree.decision_nodes) if tree is not None else 0]
             if rstrat is not None:
                 rstrat = rstrat[:len(tree.river_decision_nodes) if tree is not None else 0]
-        return TurnSolution(tree, self.ranges[i], strategy, rstrat, self.value[i], self.br[i], self.status[i], self.valid[i], self.pool[i])
+        return TurnSolution(tree, _ith(self.ranges, i), strategy, rstrat, self.value[i], self.br[i], self.status[i], self.valid[i], self.pool[i],
+                            node=_ith_node(self, i), reach=_ith(self.reach, i))
 
+    _weights = RiverSolution._weights
     _pair_weight = RiverSolution._pair_weight
     _one = RiverSolution._one
 
@@ -480,15 +675,17 @@ class TurnSolution:
     def ev(self):
         """chips per player: sum_h w_p[h] value[p][h] / (4 (P - 4) sum over disjoint pairs of w_0 w_1); Python integers, one division each"""
         self._one()
-        den = 4 * (int(self.pool) - 4) * self._pair_weight()
-        return tuple(sum(int(w) * int(v) for w, v in zip(self.ranges[p], self.value[p])) / den if den else float("nan") for p in (0, 1))
+        w, unit = self._weights()
+        den = 2 * unit * (int(self.pool) - 4) * self._pair_weight()
+        return tuple(sum(int(a) * int(v) for a, v in zip(w[p], self.value[p])) / den if den else float("nan") for p in (0, 1))
 
     @property
     def exploitability(self):
         """sum_p (br_p - value_p) reduced the same way, in chips"""
         self._one()
-        den = 4 * (int(self.pool) - 4) * self._pair_weight()
-        num = sum(int(w) * (int(b) - int(v)) for p in (0, 1) for w, b, v in zip(self.ranges[p], self.br[p], self.value[p]))
+        w, unit = self._weights()
+        den = 2 * unit * (int(self.pool) - 4) * self._pair_weight()
+        num = sum(int(a) * (int(b) - int(v)) for p in (0, 1) for a, b, v in zip(w[p], self.br[p], self.value[p]))
         return num / den if den else float("nan")
 
     def probabilities(self, node, river_card=None):
@@ -541,21 +738,24 @@ def turn_grid(tree, m=None):
 
 
 def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False, device=0, tree_of=None, lock=None, locked=None, river_lock=None,
-                     river_locked=None):
+                     river_locked=None, reach=None, at=None, at_card=None):
     """pk_solve_turn on host arrays: board uint8 [m, 4] Card.value, ranges uint16 [m, 2, 1326] over holding_index, one TurnTree for the
     call, dead uint64 [m] masks over canonical card indices (None: none) -> TurnSolution with a leading [m].  river_strategy=True also
     returns the river-level strategies (551 616 bytes per river-level decision node and spot).
     tree may also be a SEQUENCE of TurnTrees with tree_of (pk_solve_turn_trees), as solve_river_batch takes them.
     lock, locked (turn-level rows) and river_lock, river_locked (river-level rows, each for all river cards at once; river_locked of
     river_strategy's shape): pk_solve_turn_locked, as solve_river_batch takes them.  A TurnSolution as locked also serves as river_locked
-    where that is None and river_lock is given.  iters may then be 0."""
+    where that is None and river_lock is given.  iters may then be 0.
+    reach, at, at_card (pk_solve_turn_resolve): as solve_river_batch takes reach (up to 2^17 - 1; ranges << 1 is the same call) and at;
+    at_card, Card.value integers [m] or one, names the river card under which a river-level node is reported."""
     board = np.ascontiguousarray(board, np.uint8)
     if board.ndim != 2 or board.shape[1] != 4:
         raise ValueError("board must have shape [m, 4]")
     m = board.shape[0]
-    ranges = np.ascontiguousarray(ranges, np.uint16)
-    if ranges.shape != (m, 2, L.EQ_HOLDINGS):
-        raise ValueError("ranges must have shape [m, 2, 1326]")
+    resolve = reach is not None or at is not None or at_card is not None
+    ranges, reach = _resolve_ranges(ranges, reach, m, TURN_REACH_MAX)
+    at, at_card = _resolve_at(at, m), _resolve_at(at_card, m, "at_card")
+    node = _node_outputs(at, m)
     if dead is not None:
         dead = np.ascontiguousarray(dead, np.uint64)
         if dead.shape != (m,):
@@ -570,7 +770,7 @@ def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False
     rstrat = np.zeros((m, Dr, 52, 4, L.EQ_HOLDINGS), np.uint16) if river_strategy else None
     value, br = np.zeros((m, 2, L.EQ_HOLDINGS), np.int64), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64)
     status = np.zeros(m, np.uint8)
-    if any(x is not None for x in (lock, locked, river_lock, river_locked)):
+    if resolve or any(x is not None for x in (lock, locked, river_lock, river_locked)):
         if river_locked is None and river_lock is not None and isinstance(locked, TurnSolution):
             river_locked = locked
         lrows = rows or _TreeRows([tree], TURN_MAX_NODES)
@@ -578,9 +778,17 @@ def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False
             tree, tree_of = None, _tree_of(tree_of, len(trees), m)
         lock, locked = _lock_pair(lock, locked, m, Dt, (4, L.EQ_HOLDINGS), ("lock", "locked"), "strategy")
         river_lock, river_locked = _lock_pair(river_lock, river_locked, m, Dr, (52, 4, L.EQ_HOLDINGS), ("river_lock", "river_locked"), "river_strategy")
-        L.check(L.lib().pk_solve_turn_locked(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *lrows.args(), L.ptr(tree_of), int(iters),
-                                             L.ptr(lock), L.ptr(locked), L.ptr(river_lock), L.ptr(river_locked), L.ptr(strategy), L.ptr(rstrat),
-                                             L.ptr(value), L.ptr(br), L.ptr(status)))
+        if resolve:
+            nr, nv, nb = node or (None, None, None)
+            L.check(L.lib().pk_solve_turn_resolve(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *lrows.args(), L.ptr(tree_of), int(iters),
+                                                  L.ptr(lock), L.ptr(locked), L.ptr(river_lock), L.ptr(river_locked), L.ptr(reach), L.ptr(at),
+                                                  L.ptr(at_card), L.ptr(strategy), L.ptr(rstrat), L.ptr(value), L.ptr(br), L.ptr(nr), L.ptr(nv),
+                                                  L.ptr(nb), L.ptr(status)))
+        else:
+            L.check(L.lib().pk_solve_turn_locked(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *lrows.args(), L.ptr(tree_of),
+                                                 int(iters),
+                                                 L.ptr(lock), L.ptr(locked), L.ptr(river_lock), L.ptr(river_locked), L.ptr(strategy), L.ptr(rstrat),
+                                                 L.ptr(value), L.ptr(br), L.ptr(status)))
     elif rows is None:
         L.check(L.lib().pk_solve_turn(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *_tree_args(tree), int(iters), L.ptr(strategy),
                                       L.ptr(rstrat), L.ptr(value), L.ptr(br), L.ptr(status)))
@@ -592,15 +800,25 @@ def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False
     valid = rvr_valid_holdings(board5, np.full(m, 4, np.uint8), dead) & (status == 0)[:, None]
     pool = np.where(status == 0, valid.sum(axis=1), 0)
     pool = np.array([int(round((1 + math.sqrt(1 + 8 * int(x))) / 2)) if x else 0 for x in pool])      # C(P, 2) valid holdings -> P
-    return TurnSolution(tree, ranges, strategy, rstrat, value, br, status, valid, pool, trees, tree_of)
+    return TurnSolution(tree, ranges, strategy, rstrat, value, br, status, valid, pool, trees, tree_of, node=node, reach=reach)
 
 
 def solve_turn_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None, river_strategy_d=None, value_d=None, br_d=None, status_d=None,
-                 device=0, stream=None, tree_of=None, lock=None, locked=None, river_lock=None, river_locked=None):
+                 device=0, stream=None, tree_of=None, lock=None, locked=None, river_lock=None, river_locked=None, reach=None, at=None, at_card=None,
+                 node_reach_d=None, node_value_d=None, node_br_d=None):
     """pk_solve_turn_d: the same on device-resident buffers (device pointers as ints / c_void_p; the tree stays a host TurnTree; dead_d and
     the outputs may be None), asynchronous on `stream`.  With a SEQUENCE of trees (pk_solve_turn_trees_d) tree_of is the DEVICE pointer of
     uint32 [m], as solve_river_d takes it; the strategies have the rows of the largest tree passed.  lock, locked, river_lock,
-    river_locked (pk_solve_turn_locked_d): DEVICE pointers, as solve_river_d takes them."""
+    river_locked (pk_solve_turn_locked_d): DEVICE pointers, as solve_river_d takes them.  reach, at, at_card and node_reach_d,
+    node_value_d, node_br_d (pk_solve_turn_resolve_d): DEVICE pointers, as solve_river_d takes them; ranges_d may then be None."""
+    if any(x is not None for x in (reach, at, at_card, node_reach_d, node_value_d, node_br_d)):
+        one = isinstance(tree, RiverTree)
+        if one == (tree_of is not None):
+            raise ValueError("tree_of, the device pointer of uint32 [m], comes with a sequence of trees and only with one")
+        L.check(L.lib().pk_solve_turn_resolve_d(int(device), int(m), board_d, dead_d, ranges_d, *_TreeRows([tree] if one else tree, TURN_MAX_NODES).args(),
+                                                tree_of, int(iters), lock, locked, river_lock, river_locked, reach, at, at_card, strategy_d,
+                                                river_strategy_d, value_d, br_d, node_reach_d, node_value_d, node_br_d, status_d, stream))
+        return
     if any(x is not None for x in (lock, locked, river_lock, river_locked)):
         one = isinstance(tree, RiverTree)
         if one == (tree_of is not None):
@@ -621,17 +839,20 @@ def solve_turn_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None
                                     value_d, br_d, status_d, stream))
 
 
-def solve_turn(board, ranges, tree, iters, dead=(), river_strategy=False, device=0, lock=None, locked=None, river_lock=None, river_locked=None):
+def solve_turn(board, ranges, tree, iters, dead=(), river_strategy=False, device=0, lock=None, locked=None, river_lock=None, river_locked=None,
+               reach=None, at=None, at_card=None):
     """One subgame.  board: the four board cards; ranges: [2, 1326] integers 0 .. 65535 over holding_index, player 0 (first to act on
     both streets) then player 1; dead: cards known to be out of play.  Raises ValueError for an invalid spot.  A reach starts at
-    weight << 1 and every split rounds down: scale a range so that its largest weight uses the sixteen bits."""
+    weight << 1 and every split rounds down: scale a range so that its largest weight uses the sixteen bits.  reach [2, 1326] (ranges may
+    then be None), at (a node index) and at_card (a Card-like, 'RS' string or Card.value): as solve_turn_batch takes them."""
     board = list(board)
     if len(board) != 4:
         raise ValueError("four board cards")
     b = np.array([[_card(c) for c in board]], np.uint8)
     d = np.array([dead if isinstance(dead, (int, np.integer)) else dead_mask(dead)], np.uint64)
-    r = solve_turn_batch(b, np.asarray(ranges)[None], tree, iters, d, river_strategy=river_strategy, device=device, lock=lock, locked=locked,
-                         river_lock=river_lock, river_locked=river_locked)[0]
+    r = solve_turn_batch(b, _one_spot(ranges), tree, iters, d, river_strategy=river_strategy, device=device, lock=lock, locked=locked,
+                         river_lock=river_lock, river_locked=river_locked, reach=_one_spot(reach), at=at,
+                         at_card=None if at_card is None else int(_card(at_card)))[0]
     if r.status:
         raise ValueError("invalid spot: " + equity_status_text(r.status))
     return r

@@ -60,6 +60,7 @@ import hist_cluster_spec as CS          # noqa: E402
 import hist_spec as HS                  # noqa: E402
 import preflop_spec as PS               # noqa: E402
 import river_solver_spec as RVS         # noqa: E402
+import resolve_spec as RZS              # noqa: E402
 import solver_lock_spec as SLS           # noqa: E402
 import solver_trees_util as STU         # noqa: E402
 import turn_solver_spec as TSS          # noqa: E402
@@ -80,7 +81,9 @@ OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("w
            "pfhero": ("agg", "win", "tie", "boards", "status"), "pfrvr": ("win", "tie", "tot"),
            "riversolve": ("strategy", "value", "br", "status"), "turnsolve": ("strategy", "river_strategy", "value", "br", "status"),
            "rivertrees": ("strategy", "value", "br", "status"), "turntrees": ("strategy", "river_strategy", "value", "br", "status"),
-           "riverlock": ("strategy", "value", "br", "status"), "turnlock": ("strategy", "river_strategy", "value", "br", "status")}
+           "riverlock": ("strategy", "value", "br", "status"), "turnlock": ("strategy", "river_strategy", "value", "br", "status"),
+           "riverresolve": ("strategy", "value", "br", "node_reach", "node_value", "node_br", "status"),
+           "turnresolve": ("strategy", "river_strategy", "value", "br", "node_reach", "node_value", "node_br", "status")}
 
 
 class Case:
@@ -1412,6 +1415,170 @@ def turn_lock_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- re-solving
+def resolve_reach(seed, board, street, dead, limit, over=(), refused=()):
+    """reach uint32 [m, 2, 1326]: random up to `limit` with zeros among them; the spots in `over` also hold entries ABOVE the limit (the
+    kernel takes the minimum); what the definition says is not read -- invalid holdings, every entry of a spot in `refused` -- is
+    0xFFFFFFFF."""
+    rng = np.random.default_rng(seed)
+    m = board.shape[0]
+    reach = rng.integers(0, limit + 1, (m, 2, HOLDINGS)).astype(np.uint32)
+    reach[rng.random(reach.shape) < 0.15] = 0
+    reach[rng.random(reach.shape) < 0.05] = limit
+    for i in range(m):
+        if i in over:
+            pick = rng.random((2, HOLDINGS))
+            reach[i][pick < 0.1] = limit + 1
+            reach[i][pick > 0.9] = 0xFFFFFFFF
+        status, gone = VS.check_spot([int(x) for x in board[i]], street, int(dead[i]))
+        if i in refused:
+            reach[i] = 0xFFFFFFFF
+        elif not status & ~VS.PREFLOP:
+            reach[i][:, [h for h in range(HOLDINGS) if VS.PAIR_A[h] in gone or VS.PAIR_B[h] in gone]] = 0xFFFFFFFF
+    return reach
+
+
+def resolve_given(seed, trees, tree_of, m, beyond=()):
+    """given int64 [m, 2, 1326]: random within +- 2^40; the spots in `beyond` also hold values past the clamp, the extremes of int64 among
+    them; a spot whose tree has no given node (or no tree): all ones, which the kernel never reads."""
+    rng = np.random.default_rng(seed)
+    given = rng.integers(-(1 << 40), 1 << 40, (m, 2, HOLDINGS)).astype(np.int64)
+    for i in range(m):
+        k = int(tree_of[i]) if tree_of is not None else 0
+        if k >= len(trees) or RZS.GIVEN not in [int(x) for x in trees[k].kind]:
+            given[i] = -1
+        elif i in beyond:
+            pick = rng.random((2, HOLDINGS))
+            given[i][pick < 0.05] = (1 << 45)
+            given[i][(pick >= 0.05) & (pick < 0.1)] = -(1 << 45)
+            given[i][pick > 0.97] = np.iinfo(np.int64).max
+            given[i][(pick > 0.94) & (pick <= 0.97)] = np.iinfo(np.int64).min
+    return given
+
+
+def resolve_case(name, street, pools, trees, tree_of, iters, seed, at=None, at_card=None, patterns=None, use_reach=True, use_ranges=False, over=(),
+                 beyond=(), refused=None, outputs=None, quick=True, edit=None, fixture=None):
+    """k_rs_prep / k_ts_prep (+ k_trees_prep) + k_resolve_prep + k_resolve_river_solve / k_resolve_turn_solve at a grid of 1 against
+    tests/resolve_spec.py.  at: per spot a node index, "root", "last", "leaf" (the tree's first terminal) or None for the whole call;
+    at_card (turn): per spot a card code, "first" / "last" (the pool's first / last card), "board" (a board card: no card of the pool) or 0xFF.  refused: {spot: True} for the spots
+    whose reach holds 0xFFFFFFFF throughout (refused by their board, their tree_of, their at or their at_card).  fixture: the expected
+    outputs come from tests/golden/resolve/<fixture>.npz (written by the spec alone: make.py there)."""
+    m = len(pools)
+    family = "riverresolve" if street == 5 else "turnresolve"
+    if fixture:
+        import importlib.util
+        mk = importlib.util.spec_from_file_location("resolve_make", os.path.join(ROOT, "tests", "golden", "resolve", "make.py"))
+        FX = importlib.util.module_from_spec(mk)
+        mk.loader.exec_module(FX)
+        x = FX.inputs(fixture)
+        arrays = {"m": ("u32", [1]), "grid": ("u32", [1]), "iters": ("u32", [x["iters"]]), **tree_rows([x["tree"]], 64 if street == 5 else 128),
+                  "board": ("u8", x["board"]), "dead": ("u64", x["dead"]), "reach": ("u32", x["reach"]), "at": ("u8", x["at"])}
+        if street == 4:
+            arrays["at_card"] = ("u8", x["at_card"])
+
+        def expect_fx():
+            fx = np.load(os.path.join(ROOT, "tests", "golden", "resolve", fixture + ".npz"))
+            return {k: (fx[k][None].view(np.uint64) if fx[k].dtype == np.int64 else fx[k][None]) for k in OUTPUTS[family] if k in fx}
+        return Case(name, family, arrays, expect_fx, outputs, quick)
+    board, _, dead = board_spots(seed, [(street, p) for p in pools])
+    board = np.ascontiguousarray(board[:, :street])
+    rng = np.random.default_rng(seed + 1)
+    ranges = rng.integers(0, 65536, (m, 2, HOLDINGS)).astype(np.uint16)
+    if edit:
+        edit(board, dead)
+    if tree_of is not None:
+        tree_of = np.asarray(tree_of, np.uint32)
+    tree_at = lambda i: trees[min(int(tree_of[i]) if tree_of is not None else 0, len(trees) - 1)]
+    ats = None
+    if at is not None:
+        ats = np.zeros(m, np.uint8)
+        for i, a in enumerate(at):
+            t = tree_at(i)
+            ats[i] = {"root": 0, "last": t.n - 1, "leaf": next(v for v in range(t.n) if t.kind[v] > 1 and t.kind[v] != 5)}.get(a, a)
+    cards = None
+    if at_card is not None:
+        cards = np.zeros(m, np.uint8)
+        for i, c in enumerate(at_card):
+            _, gone = VS.check_spot([int(x) for x in board[i]], street, int(dead[i]))
+            pool = [k for k in range(52) if k not in gone]
+            cards[i] = {"first": int(VS.CANON[pool[0]]), "last": int(VS.CANON[pool[-1]]), "board": int(board[i, 0])}.get(c, c)
+    limit = RZS.RIVER_LIM if street == 5 else RZS.TURN_LIM
+    reach = resolve_reach(seed + 4, board, street, dead, limit, over, refused or {}) if use_reach else None
+    has_given = street == 5 and any(RZS.GIVEN in [int(x) for x in t.kind] for t in trees)
+    given = resolve_given(seed + 5, trees, tree_of, m, beyond) if has_given else None
+    lock = locked = rlock = rlocked = None
+    if patterns is not None:
+        lock, locked = lock_arrays(seed + 2, trees, tree_of, patterns)
+        if street == 4:
+            rlock, rlocked = lock_arrays(seed + 3, trees, tree_of, patterns, river=True)
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [1]), "iters": ("u32", [iters]), **tree_rows(trees, 64 if street == 5 else 128),
+              "tree_of": ("u32", tree_of), "board": ("u8", board), "dead": ("u64", dead),
+              "ranges": ("u16", ranges if use_ranges or not use_reach else None), "reach": ("u32", reach),
+              "given": ("u64", None if given is None else given.view(np.uint64)), "at": ("u8", ats), "at_card": ("u8", cards),
+              "lock": ("u8", lock), "locked": ("u16", locked), "river_lock": ("u8", rlock), "river_locked": ("u16", rlocked)}
+    if outputs is None and ats is None:
+        outputs = tuple(k for k in OUTPUTS[family] if not k.startswith("node_"))
+
+    def expect():
+        if street == 5:
+            r = RZS.solve_river_batch(board, ranges, trees, tree_of, iters, lock, locked, dead, reach, given, ats)
+        else:
+            r = RZS.solve_turn_batch(board, ranges, trees, tree_of, iters, lock, locked, rlock, rlocked, dead, reach, ats, cards)
+        return {k: (r[k].view(np.uint64) if r[k].dtype == np.int64 else r[k]) for k in OUTPUTS[family]}
+    return Case(name, family, arrays, expect, outputs, quick)
+
+
+def gadget_of(tree, opponent):
+    from pokerl_amd.solver import gadget_tree
+    return gadget_tree(tree, opponent)
+
+
+def river_resolve_cases():
+    """The river solver's re-solving call (names rres-...), every case at a grid of 1: ONE workgroup takes the spots in turn, so stale node
+    outputs, stale given values or stale LDS of the spot before would show.  NOT part of all_cases()."""
+    from pokerl_amd.solver import river_tree
+    forced, four, chain = STU.forced_river_tree(), STU.four_action_river_tree(), STU.chain_river_tree()
+    small, default = river_tree(100, 50), river_tree(100, 400)
+    gsmall, gfour = gadget_of(small, 1), gadget_of(four, 0)
+    cs = [resolve_case("rres-at-after-no-given-and-back", 5, (9, 7, 10, 6, 8), [small, gsmall, gfour], [0, 1, 0, 2, 0], 2, 111, at=[3, 2, "root", 1, "last"], beyond=(1,)),
+          resolve_case("rres-refused-bad-at-between", 5, (9, 8, 10, 7, 9, 8), [small, gfour], [1, 0, 2, 0, 0, 1], 2, 112, at=[0, 1, 0, 200, small.n, 4],
+                       refused={1: True, 2: True, 3: True, 4: True}, edit=break_second_board),
+          resolve_case("rres-at-root-leaf-last", 5, (8, 11, 7), [default], None, 2, 113, at=["root", "leaf", "last"]),
+          resolve_case("rres-reach-above-the-limit", 5, (9, 6), [small], None, 2, 114, at=[1, 0], over=(0, 1)),
+          resolve_case("rres-given-beyond-the-clamp", 5, (8, 10), [gsmall], None, 3, 115, at=[1, 0], beyond=(0, 1)),
+          resolve_case("rres-large-after-small", 5, (8, 7, 9, 6), [forced, chain, gsmall], [0, 1, 2, 1], 1, 116, at=["last", "last", 1, 5]),
+          resolve_case("rres-iters0-all-locked", 5, (10, 6, 9), [default, gfour], [0, 1, 0], 0, 117, at=[2, "last", "leaf"], patterns=["all", "p1", "none"]),
+          resolve_case("rres-pools-4-9-33", 5, (4, 9, 33), [gsmall], [0, 0, 0], 2, 118, at=[2, 3, "last"]),
+          resolve_case("rres-ranges-no-reach-no-at", 5, (7, 9), [gsmall], None, 2, 119, use_reach=False),
+          resolve_case("rres-ranges-beside-reach-are-not-read", 5, (7, 9), [small], None, 2, 120, at=[0, 2], use_ranges=True),
+          resolve_case("rres-status-only", 5, (9, 9, 9), [small, forced], [0, 1, 5], 1, 121, refused={1: True, 2: True}, outputs=("status",), edit=break_second_board)]
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
+def turn_resolve_cases():
+    """The turn solver's re-solving call (names tres-...), every case at a grid of 1.  NOT part of all_cases()."""
+    from pokerl_amd.solver import turn_tree
+    allin, small = STU.allin_turn_tree(), turn_tree(30, 20, (1.0,), 1)
+    rnode = small.river_decision_nodes[0]
+    chance = next(v for v in range(small.n) if small.kind[v] == 5)
+    cs = [resolve_case("tres-river-at-first-and-last-card", 4, (7, 6, 8, 7), [small], None, 2, 131, at=[rnode, rnode, chance, "last"],
+                       at_card=["first", "last", 0xFF, "last"]),
+          resolve_case("tres-refused-bad-at-bad-card-between", 4, (8, 7, 9, 6, 7, 6, 7), [small, allin], [1, 0, 2, 0, 0, 0, 1], 2, 132,
+                       at=[0, 1, 0, 200, rnode, rnode, "last"], at_card=[0xFF, 0, 0, 0, 0x3F, "board", "first"],
+                       refused={1: True, 2: True, 3: True, 4: True, 5: True}, edit=break_second_board),
+          resolve_case("tres-at-root-leaf-last", 4, (7, 8, 6), [small], None, 2, 133, at=["root", "leaf", "last"], at_card=[0xFF, 0xFF, "first"]),
+          resolve_case("tres-reach-above-the-limit", 4, (7, 6), [small], None, 2, 134, at=[1, rnode], at_card=[0xFF, "last"], over=(0, 1)),
+          resolve_case("tres-large-after-small", 4, (7, 6, 8), [allin, small], [0, 1, 0], 1, 135, at=["last", "last", "root"], at_card=["first", "first", 0xFF]),
+          resolve_case("tres-iters0-all-locked", 4, (8, 6), [small], None, 0, 136, at=[rnode + 1, chance], at_card=["last", 0xFF], patterns=["all", "p1"]),
+          resolve_case("tres-pools-5-9-20", 4, (5, 9, 20), [small], [0, 0, 0], 2, 137, at=[rnode, chance, "last"], at_card=["first", 0xFF, "last"]),
+          resolve_case("tres-ranges-no-reach-no-at", 4, (7, 6), [small], None, 2, 138, use_reach=False),
+          resolve_case("tres-p48-fixture", 4, (48,), None, None, None, 139, quick=False, fixture="turn_p48",
+                       outputs=("value", "br", "node_reach", "node_value", "node_br", "status"))]
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -1426,7 +1593,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() + river_trees_cases() + turn_trees_cases() + river_lock_cases() + turn_lock_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() + river_trees_cases() + turn_trees_cases() + river_lock_cases() + turn_lock_cases() + river_resolve_cases() + turn_resolve_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

@@ -23,6 +23,14 @@ in the same process -- the price of the LOCK instantiation.  one: player 1's row
 player 0.  all: every row locked, no iteration -- evaluations of a supplied strategy per second.
 
     python tools/river_solver_bench.py --lock none --m 512
+
+--resolve {none,at,gadget} measures the re-solving entry (pk_solve_river_resolve_d) on the ordinary legs' spots and
+tree, and merges its legs into profiles/solver_resolve_bench.json under "river".  none: none of the new arguments, against
+pk_solve_river_locked_d with nothing locked in the same process (k_lock_river_solve: the kernel tools/isa_diff.py shows identical to the
+parent commit's) -- the price of the RESOLVE instantiation.  at: the root reaches from `reach` and the three node outputs at the node after
+player 0's first bet.  gadget: the subtree below that node re-solved through gadget_tree from the node_reach and node_br of a first solve.
+
+    python tools/river_solver_bench.py --resolve none --m 512
 """
 import argparse
 import ctypes as C
@@ -160,6 +168,56 @@ def lock_legs(args, stream, res):
             x.free()
 
 
+def resolve_legs(args, stream, res):
+    """--resolve (the module's docstring)"""
+    rng = np.random.default_rng(0)
+    board, ranges = subgames(rng, max(args.m))
+    tree = solver.river_tree(100, 400)
+    node = int(tree.child[0][1])
+    sub, _ = tree.subtree(node)
+    gadget = solver.gadget_tree(sub, 1)
+    used = gadget if args.resolve == "gadget" else tree
+    D = len(used.decision_nodes)
+    rows = solver._TreeRows([used], solver.MAX_NODES)
+    for m in args.m:
+        b, r = np.ascontiguousarray(board[:m]), np.ascontiguousarray(ranges[:m])
+        ins = [DeviceBuffer(x.nbytes).upload(x) for x in (b, r, r.astype(np.uint32) << 4, np.full(m, node, np.uint8))]
+        strategy, value, br, status = DeviceBuffer(m * D * 4 * H * 2), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m)
+        nreach, nvalue, nbr = DeviceBuffer(m * 2 * H * 4), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m * 2 * H * 8)
+
+        def call(ranges_d=None, reach=None, given=None, at_d=None, nodes=(None, None, None)):
+            L.check(L.lib().pk_solve_river_resolve_d(0, m, ins[0].ptr, None, ranges_d, *rows.args(), None, args.iters, None, None, reach, given, at_d, strategy.ptr,
+                                                     value.ptr, br.ptr, *nodes, status.ptr, stream))
+
+        def locked_entry():
+            solver.solve_river_d(m, ins[0].ptr, ins[1].ptr, tree, args.iters, strategy_d=strategy.ptr, value_d=value.ptr, br_d=br.ptr, status_d=status.ptr,
+                                 stream=stream, lock=None, locked=nvalue.ptr)            # (locked without lock: not looked at; the locked entry point)
+
+        runs = {"none": (("locked_call", locked_entry), ("resolve_call", lambda: call(ranges_d=ins[1].ptr))),
+                "at": (("resolve_call", lambda: call(reach=ins[2].ptr, at_d=ins[3].ptr, nodes=(nreach.ptr, nvalue.ptr, nbr.ptr))),),
+                "gadget": (("resolve_call", lambda: call(reach=nreach.ptr, given=nbr.ptr)),)}[args.resolve]
+        if args.resolve == "gadget":                                          # the first solve: its node_reach and node_br stay on the device
+            solver.solve_river_d(m, ins[0].ptr, ins[1].ptr, tree, args.iters, status_d=status.ptr, stream=stream, at=ins[3].ptr, node_reach_d=nreach.ptr,
+                                 node_br_d=nbr.ptr)
+            assert hipmem._lib().hipStreamSynchronize(stream) == 0 and not status.download(np.uint8, m).any()
+        leg = {}
+        for name, run in runs:
+            us, each, wall, odd = time_stream(run, stream, args.samples, warmup=1)
+            assert not status.download(np.uint8, m).any()
+            v, bb = value.download(np.int64, m * 2 * H), br.download(np.int64, m * 2 * H)
+            assert (bb >= v).all() and v.any()
+            leg[name] = dict(ms=round(us * 1e-3, 3), samples_ms=[round(x * 1e-3, 3) for x in each], host_clock_ms=round(wall * 1e-3, 3), event_anomalies=odd,
+                             solves_per_s=round(m / (us * 1e-6), 1), value_sum=int(v.sum()))
+        if args.resolve == "none":
+            assert leg["locked_call"]["value_sum"] == leg["resolve_call"]["value_sum"]                      # nothing new used: the same values
+            leg["ratio_resolve_to_locked"] = round(leg["resolve_call"]["ms"] / leg["locked_call"]["ms"], 4)
+        if args.resolve == "at":
+            assert nvalue.download(np.int64, m * 2 * H).any() and nreach.download(np.uint32, m * 2 * H).any()
+        res["resolve_%s_m_%d" % (args.resolve, m)] = dict(iters=args.iters, tree_nodes=used.n, at=node if args.resolve == "at" else None, **leg)
+        for x in ins + [strategy, value, br, status, nreach, nvalue, nbr]:
+            x.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=3)
@@ -168,14 +226,25 @@ def main():
     ap.add_argument("--spec-iters", type=int, default=0)
     ap.add_argument("--trees", type=int, default=0, help="K: measure the tree-per-spot entry with K trees (1: the indirection alone)")
     ap.add_argument("--lock", choices=("none", "one", "all"), default=None, help="measure the locked entry: nothing, player 1 or every row locked")
+    ap.add_argument("--resolve", choices=("none", "at", "gadget"), default=None, help="measure the re-solving entry: nothing new, node outputs, a gadget solve")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "solver_lock_bench.json" if args.lock else "solver_trees_bench.json" if args.trees else "river_solver_bench.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "solver_resolve_bench.json" if args.resolve else "solver_lock_bench.json" if args.lock else "solver_trees_bench.json" if args.trees else "river_solver_bench.json")
     if pokerl_amd.device_count() < 1:
         sys.exit("river_solver_bench: no MI355X visible (no fallback)")
     hip = hipmem._lib()
     stream = C.c_void_p()
     assert hip.hipStreamCreateWithFlags(C.byref(stream), 1) == 0
+    if args.resolve:
+        ks = kernel_meta.kernels(L.LIB_PATH)
+        res = dict(tool="river_solver_bench --resolve", src=L.source_hash(), samples=args.samples)
+        for name in ("k_lock_river_solve", "k_resolve_river_solve"):
+            res[name] = dict(vgprs=ks[name]["vgprs"], sgprs=ks[name]["sgprs"], lds=ks[name]["lds"], scratch=ks[name]["private_segment"])
+        resolve_legs(args, stream, res)
+        hip.hipStreamDestroy(stream)
+        merge_into(args.out, "river", res)
+        print(json.dumps(res))
+        return
     if args.lock:
         ks = kernel_meta.kernels(L.LIB_PATH)
         res = dict(tool="river_solver_bench --lock", src=L.source_hash(), samples=args.samples)

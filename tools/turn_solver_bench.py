@@ -22,6 +22,12 @@ pk_solve_turn_trees_d with that one tree; player 1's rows of both levels locked 
 with no iteration.  river_locked takes 6.6 MB of device memory a spot.
 
     python tools/turn_solver_bench.py --lock none --m 256
+
+--resolve {none,at} measures the re-solving entry (pk_solve_turn_resolve_d) as tools/river_solver_bench.py --resolve
+does, and merges its legs into profiles/solver_resolve_bench.json under "turn": none of the new arguments against pk_solve_turn_locked_d
+with nothing locked; the root reaches from `reach` and the node outputs at a river-level node under one river card.
+
+    python tools/turn_solver_bench.py --resolve none --m 256
 """
 import argparse
 import ctypes as C
@@ -150,6 +156,49 @@ def lock_legs(args, stream, res):
             x.free()
 
 
+def resolve_legs(args, stream, res):
+    """--resolve (the module's docstring)"""
+    rng = np.random.default_rng(0)
+    board, river, ranges = subgames(rng, max(args.m))
+    tree = solver.turn_tree(100, 400, (1.0,), 1)
+    Dt = len(tree.decision_nodes)
+    node = tree.river_decision_nodes[1]
+    rows = solver._TreeRows([tree], solver.TURN_MAX_NODES)
+    for m in args.m:
+        b, r = np.ascontiguousarray(board[:m]), np.ascontiguousarray(ranges[:m])
+        cards = np.ascontiguousarray(river.reshape(-1, 48, 5)[:m, 24, 4])     # a river card from the middle of each spot's pool
+        ins = [DeviceBuffer(x.nbytes).upload(x) for x in (b, r, r.astype(np.uint32) << 1, np.full(m, node, np.uint8), cards)]
+        strategy, value, br, status = DeviceBuffer(m * Dt * 4 * H * 2), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m)
+        nreach, nvalue, nbr = DeviceBuffer(m * 2 * H * 4), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m * 2 * H * 8)
+
+        def call(ranges_d=None, reach=None, at_d=None, card_d=None, nodes=(None, None, None)):
+            L.check(L.lib().pk_solve_turn_resolve_d(0, m, ins[0].ptr, None, ranges_d, *rows.args(), None, args.iters, None, None, None, None, reach, at_d, card_d,
+                                                    strategy.ptr, None, value.ptr, br.ptr, *nodes, status.ptr, stream))
+
+        def locked_entry():
+            solver.solve_turn_d(m, ins[0].ptr, ins[1].ptr, tree, args.iters, strategy_d=strategy.ptr, value_d=value.ptr, br_d=br.ptr, status_d=status.ptr,
+                                stream=stream, lock=None, locked=nvalue.ptr)             # (locked without lock: not looked at; the locked entry point)
+
+        runs = {"none": (("locked_call", locked_entry), ("resolve_call", lambda: call(ranges_d=ins[1].ptr))),
+                "at": (("resolve_call", lambda: call(reach=ins[2].ptr, at_d=ins[3].ptr, card_d=ins[4].ptr, nodes=(nreach.ptr, nvalue.ptr, nbr.ptr))),)}[args.resolve]
+        leg = {}
+        for name, run in runs:
+            us, each, wall, odd = time_stream(run, stream, args.samples, warmup=1)
+            assert not status.download(np.uint8, m).any()
+            v, bb = value.download(np.int64, m * 2 * H), br.download(np.int64, m * 2 * H)
+            assert (bb >= v).all() and v.any()
+            leg[name] = dict(ms=round(us * 1e-3, 3), samples_ms=[round(x * 1e-3, 3) for x in each], host_clock_ms=round(wall * 1e-3, 3), event_anomalies=odd,
+                             solves_per_s=round(m / (us * 1e-6), 1), value_sum=int(v.sum()))
+        if args.resolve == "none":
+            assert leg["locked_call"]["value_sum"] == leg["resolve_call"]["value_sum"]                      # nothing new used: the same values
+            leg["ratio_resolve_to_locked"] = round(leg["resolve_call"]["ms"] / leg["locked_call"]["ms"], 4)
+        else:
+            assert nvalue.download(np.int64, m * 2 * H).any() and nreach.download(np.uint32, m * 2 * H).any()
+        res["resolve_%s_m_%d" % (args.resolve, m)] = dict(iters=args.iters, at=node if args.resolve == "at" else None, grid=solver.turn_grid([tree], m), **leg)
+        for x in ins + [strategy, value, br, status, nreach, nvalue, nbr]:
+            x.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=3)
@@ -157,14 +206,26 @@ def main():
     ap.add_argument("--iters", type=int, default=64)
     ap.add_argument("--trees", type=int, default=0, help="K: measure the tree-per-spot entry with K trees (1: the indirection alone)")
     ap.add_argument("--lock", choices=("none", "one", "all"), default=None, help="measure the locked entry: nothing, player 1 or every row locked")
+    ap.add_argument("--resolve", choices=("none", "at"), default=None, help="measure the re-solving entry: nothing new, or node outputs at a river-level node")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "solver_lock_bench.json" if args.lock else "solver_trees_bench.json" if args.trees else "turn_solver_bench.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "solver_resolve_bench.json" if args.resolve else "solver_lock_bench.json" if args.lock else "solver_trees_bench.json" if args.trees else "turn_solver_bench.json")
     if pokerl_amd.device_count() < 1:
         sys.exit("turn_solver_bench: no MI355X visible (no fallback)")
     hip = hipmem._lib()
     stream = C.c_void_p()
     assert hip.hipStreamCreateWithFlags(C.byref(stream), 1) == 0
+    if args.resolve:
+        from river_solver_bench import merge_into
+        ks = kernel_meta.kernels(L.LIB_PATH)
+        res = dict(tool="turn_solver_bench --resolve", src=L.source_hash(), samples=args.samples)
+        for name in ("k_lock_turn_solve", "k_resolve_turn_solve"):
+            res[name] = dict(vgprs=ks[name]["vgprs"], sgprs=ks[name]["sgprs"], lds=ks[name]["lds"], scratch=ks[name]["private_segment"])
+        resolve_legs(args, stream, res)
+        hip.hipStreamDestroy(stream)
+        merge_into(args.out, "turn", res)
+        print(json.dumps(res))
+        return
     if args.lock:
         from river_solver_bench import merge_into
         ks = kernel_meta.kernels(L.LIB_PATH)

@@ -1239,6 +1239,79 @@ int pk_solve_turn_resolve(int device, size_t m, const uint8_t *board, const uint
                           const uint16_t *locked, const uint8_t *river_lock, const uint16_t *river_locked, const uint32_t *reach,
                           const uint8_t *at, const uint8_t *at_card, uint16_t *strategy, uint16_t *river_strategy, int64_t *value, int64_t *br,
                           uint32_t *node_reach, int64_t *node_value, int64_t *node_br, uint8_t *status);
+
+/* ---- Resuming a solve: the regrets R and the average accumulators A returned to the caller and taken back (the numpy
+ * restatement: tests/resume_spec.py).  Solving until a target is met, a checkpoint, a warm start after the inputs moved a little, host work
+ * between iterations.  Everything of the sections above holds except what is said here.  PK_ABI_VERSION is unchanged: symbols are added only.
+ * pk_solve_river_resume(_d) / pk_solve_turn_resume(_d) take the arguments of pk_solve_river_resolve(_d) / pk_solve_turn_resolve(_d) and,
+ * before `strategy`:
+ *   t0       u32 [m]                  the iterations the state already holds; NULL: all 0
+ *   regret   i64 [m][Dmax][4][1326]   R, in the shape and strides of `strategy` (turn: [m][Dtmax][4][1326], the turn-level rows)
+ *   average  i64 [m][Dmax][4][1326]   A, likewise
+ *   river_regret, river_average i64 [m][Drmax][52][4][1326]   (turn only) the river-level rows, in the shape of `river_strategy`: by the
+ *                                     river card's canonical index (4.4 MB per row, spot and array)
+ * The state arrays are IN/OUT, in place: DEVICE memory in the _d forms, host memory otherwise.  They are given all together or not at all
+ * (PK_E_INVALID_ARG otherwise, and for a t0 without them, each with its own text).  With none the call IS the resolve call.  A state array
+ * must be no other argument of the call and no other state array (PK_E_INVALID_ARG).
+ * ITERATIONS: spot i runs t = t0[i] + 1 .. t0[i] + iters; t enters only A += t r_p.  iters may be 0.
+ * LOAD, for a spot with t0[i] > 0, at every decision row d < D of the spot's tree that is not locked, action a < nact, valid h -- on the
+ * turn's river level for every card c of the pool and every valid h without c: R = clamp(regret[i][d][a][h], 0, RMAX), A =
+ * clamp(average[i][d][a][h], 0, AMAX); RMAX = 2^58 - 1, AMAX = 2^44 - 1 (river), RMAX = 2^60 - 1, AMAX = 2^41 - 1 (turn, both levels).  With
+ * t0[i] = 0 nothing of the spot's state is read and R = A = 0.  A state this library wrote never meets the clamp.
+ * STORE: after the last iteration and before the final passes the entries named under LOAD are written with R and A as they stand.  Every
+ * OTHER entry of the spot's slices -- a >= nact, invalid holdings, rows at or past the spot's D, locked rows, cards outside the pool,
+ * holdings that contain the card -- is written 0 by a call with t0[i] = 0 and left exactly as it is by a call with t0[i] > 0: a locked
+ * row's state survives a locked call (the word in which the turn kernel keeps a locked river-level node's probabilities never leaves).
+ * STATUS: PK_EQ_BAD_ITER marks t0[i] + iters > 4096, judged only for a spot that is not refused for another reason.  A refused spot, for
+ * whatever reason, has all-zero outputs as before and ITS STATE IS NOT TOUCHED: a mistake destroys no checkpoint.  No neighbour is disturbed.
+ * IDENTITIES: (i) state given with t0 = 0 leaves every other output what the resolve call gives, byte for byte; (ii) (t0 = 0, iters = a)
+ * followed by (t0 = a, iters = b) on the same inputs leaves the state and every output of (t0 = 0, iters = a + b), whatever the grid, the
+ * batch or the mix of t0 in it.
+ * BOUNDS (river).  A regret moves by u_p[c] - u_p[n], |.| < 2^46, an iteration: from the clamp, 2^58 + 4096 * 2^46 = 2^59 < 2^63.  The
+ * strategy rule shifts by bitlen(max) - 31, so the largest shifted entry is < 2^31 and a numerator < 2^46 whatever the size of X.  A grows
+ * by t * reach with t <= 4096 and reach < 2^20: at most sum_{t <= 4096} t * 2^20 < 2^43 in one call, so A < 2^44 + 2^43 < 2^45.  The bounds
+ * of "River solver" are what a state written by this library obeys, since its t never passes 4096; the clamps only keep a foreign state
+ * inside int64_t.
+ * BOUNDS (turn).  |u| < 2^46.7, so a regret moves by < 2^47.7 an iteration: 2^60 + 4096 * 2^47.7 < 2^60.3 < 2^63; the rule's numerator as
+ * above.  A grows by t * reach, reach < 2^17: < 2^40 in one call, so A < 2^41 + 2^40 < 2^42. */
+#define PK_EQ_BAD_ITER 16u   /* resuming: t0 + iters > 4096 (the value of PK_EQ_IN_FLIGHT, which no spot form reports) */
+int pk_solve_river_resume_d(int device, size_t m, const uint8_t *board_d /*[m][5]*/, const uint64_t *dead_d /*[m]; NULL: none*/,
+                            const uint16_t *ranges_d /*[m][2][1326]; may be NULL with reach_d*/, uint32_t ntrees, const uint32_t *n /*[ntrees], host*/,
+                            const uint8_t *kind /*[ntrees][64], host*/, const uint8_t *child /*[ntrees][64][4], host*/,
+                            const uint32_t *put /*[ntrees][64][2], host*/, const uint32_t *pot /*[ntrees], host*/,
+                            const uint32_t *tree_of_d /*[m], DEVICE; NULL with ntrees = 1: tree 0*/, uint32_t iters,
+                            const uint8_t *lock_d /*[m][Dmax], DEVICE; NULL: none*/, const uint16_t *locked_d /*[m][Dmax][4][1326], DEVICE*/,
+                            const uint32_t *reach_d /*[m][2][1326]*/, const int64_t *given_d /*[m][2][1326]*/, const uint8_t *at_d /*[m]*/,
+                            const uint32_t *t0_d /*[m], DEVICE; NULL: all 0*/, int64_t *regret_d /*[m][Dmax][4][1326], DEVICE, in and out*/,
+                            int64_t *average_d /*as regret_d*/, uint16_t *strategy_d /*[m][Dmax][4][1326]*/, int64_t *value_d /*[m][2][1326]*/,
+                            int64_t *br_d, uint32_t *node_reach_d /*[m][2][1326]*/, int64_t *node_value_d, int64_t *node_br_d, uint8_t *status_d,
+                            void *stream);
+int pk_solve_river_resume(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees,
+                          const uint32_t *n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot,
+                          const uint32_t *tree_of /*[m], host; NULL with ntrees = 1: tree 0*/, uint32_t iters, const uint8_t *lock,
+                          const uint16_t *locked, const uint32_t *reach, const int64_t *given, const uint8_t *at, const uint32_t *t0,
+                          int64_t *regret /*in and out*/, int64_t *average /*in and out*/, uint16_t *strategy, int64_t *value, int64_t *br,
+                          uint32_t *node_reach, int64_t *node_value, int64_t *node_br, uint8_t *status);
+int pk_solve_turn_resume_d(int device, size_t m, const uint8_t *board_d /*[m][4]*/, const uint64_t *dead_d /*[m]; NULL: none*/,
+                           const uint16_t *ranges_d /*[m][2][1326]; may be NULL with reach_d*/, uint32_t ntrees, const uint32_t *n /*[ntrees], host*/,
+                           const uint8_t *kind /*[ntrees][128], host*/, const uint8_t *child /*[ntrees][128][4], host*/,
+                           const uint32_t *put /*[ntrees][128][2], host*/, const uint32_t *pot /*[ntrees], host*/,
+                           const uint32_t *tree_of_d /*[m], DEVICE; NULL with ntrees = 1: tree 0*/, uint32_t iters, const uint8_t *lock_d,
+                           const uint16_t *locked_d, const uint8_t *river_lock_d, const uint16_t *river_locked_d,
+                           const uint32_t *reach_d /*[m][2][1326]*/, const uint8_t *at_d /*[m]*/, const uint8_t *at_card_d /*[m]*/,
+                           const uint32_t *t0_d /*[m], DEVICE; NULL: all 0*/, int64_t *regret_d /*[m][Dtmax][4][1326], DEVICE, in and out*/,
+                           int64_t *average_d /*as regret_d*/, int64_t *river_regret_d /*[m][Drmax][52][4][1326], DEVICE, in and out*/,
+                           int64_t *river_average_d /*as river_regret_d*/, uint16_t *strategy_d, uint16_t *river_strategy_d,
+                           int64_t *value_d /*[m][2][1326]*/, int64_t *br_d, uint32_t *node_reach_d /*[m][2][1326]*/, int64_t *node_value_d,
+                           int64_t *node_br_d, uint8_t *status_d, void *stream);
+int pk_solve_turn_resume(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees,
+                         const uint32_t *n, const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot,
+                         const uint32_t *tree_of /*[m], host; NULL with ntrees = 1: tree 0*/, uint32_t iters, const uint8_t *lock,
+                         const uint16_t *locked, const uint8_t *river_lock, const uint16_t *river_locked, const uint32_t *reach,
+                         const uint8_t *at, const uint8_t *at_card, const uint32_t *t0, int64_t *regret /*in and out*/,
+                         int64_t *average /*in and out*/, int64_t *river_regret /*in and out*/, int64_t *river_average /*in and out*/,
+                         uint16_t *strategy, uint16_t *river_strategy, int64_t *value, int64_t *br, uint32_t *node_reach, int64_t *node_value,
+                         int64_t *node_br, uint8_t *status);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

@@ -19,7 +19,8 @@ from .judger import ShowdownEV, showdown_ev, showdown_ev_batch, showdown_ev_d
 from .judger import RangedEV, ranged_ev, ranged_ev_batch, ranged_ev_d
 from .solver import (RiverSolution, RiverTree, TurnSolution, TurnTree, river_tree, river_trees, solve_river, solve_river_batch, solve_river_d,
                      solve_turn, solve_turn_batch, solve_turn_d, turn_grid, turn_tree, turn_trees, evaluate_river, evaluate_river_batch,
-                     evaluate_turn, evaluate_turn_batch, gadget_tree, resolve_river, KIND_GIVEN)
+                     evaluate_turn, evaluate_turn_batch, gadget_tree, resolve_river, KIND_GIVEN,
+                     SolverState, solver_state_bytes, solve_river_until, solve_river_until_batch, solve_turn_until, solve_turn_until_batch)
 from .sharding import gather_f64, shard_tables
 from .single import Game, PokerGameEnv
 from .state_view import Card, StateView, packed_dtype, unpack_obs
@@ -45,4 +46,5 @@ __all__ = ['Game', 'PokerGameEnv', 'VecGame', 'VecPokerGameEnv', 'VecPokerGameEn
            'preflop_range_vs_range', 'preflop_range_vs_range_batch', 'preflop_range_vs_range_d',
            'RiverTree', 'RiverSolution', 'river_tree', 'solve_river', 'solve_river_batch', 'solve_river_d',
            'TurnTree', 'TurnSolution', 'turn_tree', 'turn_grid', 'solve_turn', 'solve_turn_batch', 'solve_turn_d', 'river_trees', 'turn_trees',
-           'evaluate_river', 'evaluate_river_batch', 'evaluate_turn', 'evaluate_turn_batch', 'gadget_tree', 'resolve_river', 'KIND_GIVEN']
+           'evaluate_river', 'evaluate_river_batch', 'evaluate_turn', 'evaluate_turn_batch', 'gadget_tree', 'resolve_river', 'KIND_GIVEN',
+           'SolverState', 'solver_state_bytes', 'solve_river_until', 'solve_river_until_batch', 'solve_turn_until', 'solve_turn_until_batch']

@@ -24,6 +24,7 @@ EQ_BAD_CARD, EQ_DUP_CARD, EQ_NO_LIVE, EQ_BAD_NBOARD, EQ_IN_FLIGHT, EQ_BAD_TABLE 
 OBSERVER_NONE, OBSERVER_ACTIVE = -1, -2   # pk_clone_tables_d: an exact copy / redeal from each source table's active player
 EQ_PREFLOP, EQ_SMALL_POOL = 64, 128   # ... of pk_equity_range: nb < 3 / fewer pool cards than the board to come plus one holding
 EQ_BAD_BET = 64   # ... of pk_equity_ev: a bet that is negative, NaN or infinite (the value of EQ_PREFLOP, which no EV call reports)
+EQ_BAD_ITER = 16   # PK_EQ_BAD_ITER, of the solvers' resuming calls: t0 + iters > 4096 (the value of EQ_IN_FLIGHT, which no spot form reports)
 EQ_BAD_TREE = 32   # PK_EQ_BAD_TREE, of the solvers' tree-per-spot calls: tree_of >= ntrees (the value of EQ_BAD_TABLE, which no spot form reports)
 RS_MAX_TREES = 65536   # PK_RS_MAX_TREES: trees of one pk_solve_river_trees / pk_solve_turn_trees call at most
 EQ_HIST_MAX_BINS = 32   # PK_EQ_HIST_MAX_BINS: the most bins of a strength histogram
@@ -62,7 +63,8 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_solve_river_d", "pk_solve_river", "pk_solve_turn_d", "pk_solve_turn", "pk_turn_grid",
            "pk_solve_river_trees_d", "pk_solve_river_trees", "pk_solve_turn_trees_d", "pk_solve_turn_trees", "pk_rs_trees_rows", "pk_ts_trees_rows",
            "pk_solve_river_locked_d", "pk_solve_river_locked", "pk_solve_turn_locked_d", "pk_solve_turn_locked",
-           "pk_solve_river_resolve_d", "pk_solve_river_resolve", "pk_solve_turn_resolve_d", "pk_solve_turn_resolve"]
+           "pk_solve_river_resolve_d", "pk_solve_river_resolve", "pk_solve_turn_resolve_d", "pk_solve_turn_resolve",
+           "pk_solve_river_resume_d", "pk_solve_river_resume", "pk_solve_turn_resume_d", "pk_solve_turn_resume"]
 
 
 class PokerlHipError(RuntimeError):
@@ -229,6 +231,10 @@ def lib():
     L.pk_solve_river_resolve.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 12
     L.pk_solve_turn_resolve_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 16
     L.pk_solve_turn_resolve.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 15
+    L.pk_solve_river_resume_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 16
+    L.pk_solve_river_resume.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 15
+    L.pk_solve_turn_resume_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 21
+    L.pk_solve_turn_resume.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 20
     L.pk_rs_trees_rows.argtypes = [C.c_uint32] + [_vp] * 3
     L.pk_ts_trees_rows.argtypes = [C.c_uint32] + [_vp] * 5
     for name in SYMBOLS:

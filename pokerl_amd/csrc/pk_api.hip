@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -104,18 +105,19 @@ struct Stage {
     }
     int in(const void *host, size_t bytes) { return host ? add(bytes, host) : -1; }
     int out(void *host, size_t bytes) { return host ? add(bytes, nullptr, host) : -1; }
+    int inout(void *host, size_t bytes) { return host ? add(bytes, host, host) : -1; }   // uploaded, then downloaded into the same array
     template <typename T> T *at(int piece) const { return piece < 0 ? nullptr : (T *)(base + pieces[(size_t)piece].off); }
     // The copies are queued on `stream` up to the first HIP error; download() then waits for the stream.
     hipError_t upload(hipStream_t stream) const {
         hipError_t e = hipSuccess;
         for (const Piece &c : pieces)
-            if (e == hipSuccess && c.src) e = hipMemcpyAsync(base + c.off, c.src, c.bytes, hipMemcpyHostToDevice, stream);
+            if (e == hipSuccess && c.src && c.bytes) e = hipMemcpyAsync(base + c.off, c.src, c.bytes, hipMemcpyHostToDevice, stream);
         return e;
     }
     hipError_t download(hipStream_t stream) const {
         hipError_t e = hipSuccess;
         for (const Piece &c : pieces)
-            if (e == hipSuccess && c.dst) e = hipMemcpyAsync(c.dst, base + c.off, c.bytes, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess && c.dst && c.bytes) e = hipMemcpyAsync(c.dst, base + c.off, c.bytes, hipMemcpyDeviceToHost, stream);
         return e == hipSuccess ? hipStreamSynchronize(stream) : e;
     }
     template <typename F> hipError_t run(hipStream_t stream, F launch) const {   // launch(): queues the kernels, returns their HIP error
@@ -3466,6 +3468,155 @@ int pk_solve_turn_resolve(int device, size_t m, const uint8_t *board, const uint
                                  TsLock{g.at<uint8_t>(lo), g.at<uint16_t>(ld), g.at<uint8_t>(ro), g.at<uint16_t>(rd)},
                                  TsResolve{g.at<uint32_t>(re), g.at<uint8_t>(an), g.at<uint8_t>(ac), g.at<uint32_t>(nr), g.at<int64_t>(nv), g.at<int64_t>(nb)}, iters, m,
                                  TsOut{g.at<uint16_t>(sg), g.at<uint16_t>(rg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
+    });
+}
+
+// ---- resuming (pokerl_hip.h "Resuming a solve"): the re-solving call with the regrets and the average accumulators in
+// the caller's memory, in and out, and the iterations they hold.  Without state the call is the re-solving call.
+// (state: the call's state arrays -- two on the river, four on the turn; others: every other array of the call)
+static const char *resume_check(const void *t0, std::initializer_list<const void *> state, std::initializer_list<const void *> others, const char *together,
+                                const char *alone) {
+    size_t given = 0;
+    for (const void *a : state) given += a ? 1u : 0u;
+    if (given && given != state.size()) return together;
+    if (t0 && !given) return alone;
+    for (const void *a : state) {
+        if (!a) continue;
+        size_t same = 0;
+        for (const void *b : state) same += a == b ? 1u : 0u;
+        if (same != 1u || a == t0) return ": a state array is another argument of the call";
+        for (const void *o : others)
+            if (o == a) return ": a state array is another argument of the call";
+    }
+    return nullptr;
+}
+
+int pk_solve_river_resume_d(int device, size_t m, const uint8_t *board_d, const uint64_t *dead_d, const uint16_t *ranges_d, uint32_t ntrees, const uint32_t *n,
+                            const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of_d, uint32_t iters,
+                            const uint8_t *lock_d, const uint16_t *locked_d, const uint32_t *reach_d, const int64_t *given_d, const uint8_t *at_d,
+                            const uint32_t *t0_d, int64_t *regret_d, int64_t *average_d, uint16_t *strategy_d, int64_t *value_d, int64_t *br_d,
+                            uint32_t *node_reach_d, int64_t *node_value_d, int64_t *node_br_d, uint8_t *status_d, void *stream) {
+    const char *call = "pk_solve_river_resume_d";
+    EQ_REFUSE(g_fail, call, resume_check(t0_d, {regret_d, average_d}, {board_d, dead_d, ranges_d, tree_of_d, lock_d, locked_d, reach_d, given_d, at_d, strategy_d,
+                                                                       value_d, br_d, node_reach_d, node_value_d, node_br_d, status_d},
+                                         ": regret and average come together", ": t0 without regret and average"));
+    if (!regret_d)
+        return pk_solve_river_resolve_d(device, m, board_d, dead_d, ranges_d, ntrees, n, kind, child, put, pot, tree_of_d, iters, lock_d, locked_d, reach_d,
+                                        given_d, at_d, strategy_d, value_d, br_d, node_reach_d, node_value_d, node_br_d, status_d, stream);
+    RsPacked p;
+    const RsResolve rz{reach_d, given_d, at_d, node_reach_d, node_value_d, node_br_d};
+    const RsOut out{strategy_d, value_d, br_d, status_d};
+    EQ_REFUSE(g_fail, call, rs_resolve_pack(m, board_d, ranges_d, status_d, iters, ntrees, n, kind, child, put, pot, tree_of_d, lock_d, locked_d, rz, out, p));
+    const size_t ws = rs_work_bytes(m, p.nmax, true);
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, ws + rs_trees_bytes(ntrees), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        RsTree *trees_d = (RsTree *)(work + ws);
+        if (const hipError_t e = hipMemcpyAsync(trees_d, p.trees.data(), (size_t)ntrees * sizeof(RsTree), hipMemcpyHostToDevice, st)) return e;
+        return rs_launch_resume(st, tab, RsSpots{board_d, dead_d, ranges_d}, RsTrees{trees_d, tree_of_d, p.nmax, p.Dmax}, ntrees, RsLock{lock_d, locked_d}, rz,
+                                RsResume{t0_d, regret_d, average_d}, iters, m, out, work);
+    });
+}
+
+int pk_solve_river_resume(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees, const uint32_t *n,
+                          const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, uint32_t iters,
+                          const uint8_t *lock, const uint16_t *locked, const uint32_t *reach, const int64_t *given, const uint8_t *at, const uint32_t *t0,
+                          int64_t *regret, int64_t *average, uint16_t *strategy, int64_t *value, int64_t *br, uint32_t *node_reach, int64_t *node_value,
+                          int64_t *node_br, uint8_t *status) {
+    const char *call = "pk_solve_river_resume";
+    EQ_REFUSE(g_fail, call, resume_check(t0, {regret, average}, {board, dead, ranges, tree_of, lock, locked, reach, given, at, strategy, value, br, node_reach,
+                                                                 node_value, node_br, status},
+                                         ": regret and average come together", ": t0 without regret and average"));
+    if (!regret)
+        return pk_solve_river_resolve(device, m, board, dead, ranges, ntrees, n, kind, child, put, pot, tree_of, iters, lock, locked, reach, given, at, strategy,
+                                      value, br, node_reach, node_value, node_br, status);
+    RsPacked p;
+    EQ_REFUSE(g_fail, call, rs_resolve_pack(m, board, ranges, status, iters, ntrees, n, kind, child, put, pot, tree_of, lock, locked,
+                                            RsResolve{reach, given, at, node_reach, node_value, node_br}, RsOut{strategy, value, br, status}, p));
+    const size_t row = m * 2 * RS_HOLDINGS, rows = m * p.Dmax * 4 * RS_HOLDINGS;
+    Stage g;
+    const int bo = g.in(board, m * 5), de = g.in(dead, m * 8), ra = g.in(reach ? nullptr : ranges, row * 2), to = g.in(tree_of, m * 4);
+    const int tr = g.in(p.trees.data(), (size_t)ntrees * sizeof(RsTree));
+    const int lo = g.in(lock, m * p.Dmax), ld = g.in(lock ? locked : nullptr, rows * 2);
+    const int re = g.in(reach, row * 4), gi = g.in(p.given ? given : nullptr, row * 8), an = g.in(at, m);
+    const int tz = g.in(t0, m * 4), rg = g.inout(regret, rows * 8), av = g.inout(average, rows * 8);
+    const int sg = g.out(strategy, rows * 2), va = g.out(value, row * 8), be = g.out(br, row * 8);
+    const int nr = g.out(node_reach, row * 4), nv = g.out(node_value, row * 8), nb = g.out(node_br, row * 8), su = g.out(status, m);
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, rs_work_bytes(m, p.nmax, true), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return rs_launch_resume(st, tab, RsSpots{g.at<uint8_t>(bo), g.at<uint64_t>(de), g.at<uint16_t>(ra)},
+                                RsTrees{g.at<RsTree>(tr), g.at<uint32_t>(to), p.nmax, p.Dmax}, ntrees, RsLock{g.at<uint8_t>(lo), g.at<uint16_t>(ld)},
+                                RsResolve{g.at<uint32_t>(re), g.at<int64_t>(gi), g.at<uint8_t>(an), g.at<uint32_t>(nr), g.at<int64_t>(nv), g.at<int64_t>(nb)},
+                                RsResume{g.at<uint32_t>(tz), g.at<int64_t>(rg), g.at<int64_t>(av)}, iters, m,
+                                RsOut{g.at<uint16_t>(sg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
+    });
+}
+
+static const char *const TS_STATE_TOGETHER = ": regret, average, river_regret and river_average come together";
+static const char *const TS_STATE_ALONE = ": t0 without regret, average, river_regret and river_average";
+
+int pk_solve_turn_resume_d(int device, size_t m, const uint8_t *board_d, const uint64_t *dead_d, const uint16_t *ranges_d, uint32_t ntrees, const uint32_t *n,
+                           const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of_d, uint32_t iters,
+                           const uint8_t *lock_d, const uint16_t *locked_d, const uint8_t *river_lock_d, const uint16_t *river_locked_d, const uint32_t *reach_d,
+                           const uint8_t *at_d, const uint8_t *at_card_d, const uint32_t *t0_d, int64_t *regret_d, int64_t *average_d, int64_t *river_regret_d,
+                           int64_t *river_average_d, uint16_t *strategy_d, uint16_t *river_strategy_d, int64_t *value_d, int64_t *br_d, uint32_t *node_reach_d,
+                           int64_t *node_value_d, int64_t *node_br_d, uint8_t *status_d, void *stream) {
+    const char *call = "pk_solve_turn_resume_d";
+    EQ_REFUSE(g_fail, call, resume_check(t0_d, {regret_d, average_d, river_regret_d, river_average_d},
+                                         {board_d, dead_d, ranges_d, tree_of_d, lock_d, locked_d, river_lock_d, river_locked_d, reach_d, at_d, at_card_d, strategy_d,
+                                          river_strategy_d, value_d, br_d, node_reach_d, node_value_d, node_br_d, status_d},
+                                         TS_STATE_TOGETHER, TS_STATE_ALONE));
+    if (!regret_d)
+        return pk_solve_turn_resolve_d(device, m, board_d, dead_d, ranges_d, ntrees, n, kind, child, put, pot, tree_of_d, iters, lock_d, locked_d, river_lock_d,
+                                       river_locked_d, reach_d, at_d, at_card_d, strategy_d, river_strategy_d, value_d, br_d, node_reach_d, node_value_d, node_br_d,
+                                       status_d, stream);
+    TsPacked p;
+    const TsLock lk{lock_d, locked_d, river_lock_d, river_locked_d};
+    const TsResolve rz{reach_d, at_d, at_card_d, node_reach_d, node_value_d, node_br_d};
+    const TsOut out{strategy_d, river_strategy_d, value_d, br_d, status_d};
+    EQ_REFUSE(g_fail, call, ts_resolve_pack(m, board_d, ranges_d, status_d, iters, ntrees, n, kind, child, put, pot, tree_of_d, lk, rz, out, p));
+    const size_t ws = ts_work_bytes(m, p.ntmax, p.nrmax, true);
+    return eq_call_d(call, device, stream, m, EQ_TAB_EVAL, ws + ts_trees_bytes(ntrees), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        TsTree *trees_d = (TsTree *)(work + ws);
+        if (const hipError_t e = hipMemcpyAsync(trees_d, p.trees.data(), (size_t)ntrees * sizeof(TsTree), hipMemcpyHostToDevice, st)) return e;
+        return ts_launch_resume(st, tab, TsSpots{board_d, dead_d, ranges_d}, TsTrees{trees_d, tree_of_d, p.ntmax, p.nrmax, p.Dtmax, p.Drmax}, ntrees, lk, rz,
+                                TsResume{t0_d, regret_d, average_d, river_regret_d, river_average_d}, iters, m, out, work);
+    });
+}
+
+int pk_solve_turn_resume(int device, size_t m, const uint8_t *board, const uint64_t *dead, const uint16_t *ranges, uint32_t ntrees, const uint32_t *n,
+                         const uint8_t *kind, const uint8_t *child, const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, uint32_t iters,
+                         const uint8_t *lock, const uint16_t *locked, const uint8_t *river_lock, const uint16_t *river_locked, const uint32_t *reach,
+                         const uint8_t *at, const uint8_t *at_card, const uint32_t *t0, int64_t *regret, int64_t *average, int64_t *river_regret,
+                         int64_t *river_average, uint16_t *strategy, uint16_t *river_strategy, int64_t *value, int64_t *br, uint32_t *node_reach,
+                         int64_t *node_value, int64_t *node_br, uint8_t *status) {
+    const char *call = "pk_solve_turn_resume";
+    EQ_REFUSE(g_fail, call, resume_check(t0, {regret, average, river_regret, river_average},
+                                         {board, dead, ranges, tree_of, lock, locked, river_lock, river_locked, reach, at, at_card, strategy, river_strategy, value, br,
+                                          node_reach, node_value, node_br, status},
+                                         TS_STATE_TOGETHER, TS_STATE_ALONE));
+    if (!regret)
+        return pk_solve_turn_resolve(device, m, board, dead, ranges, ntrees, n, kind, child, put, pot, tree_of, iters, lock, locked, river_lock, river_locked, reach, at,
+                                     at_card, strategy, river_strategy, value, br, node_reach, node_value, node_br, status);
+    TsPacked p;
+    EQ_REFUSE(g_fail, call, ts_resolve_pack(m, board, ranges, status, iters, ntrees, n, kind, child, put, pot, tree_of, TsLock{lock, locked, river_lock, river_locked},
+                                            TsResolve{reach, at, at_card, node_reach, node_value, node_br}, TsOut{strategy, river_strategy, value, br, status}, p));
+    const size_t row = m * 2 * RS_HOLDINGS, trows = m * p.Dtmax * 4 * RS_HOLDINGS, rrows = m * p.Drmax * 52 * 4 * RS_HOLDINGS;
+    Stage g;
+    const int bo = g.in(board, m * 4), de = g.in(dead, m * 8), ra = g.in(reach ? nullptr : ranges, row * 2), to = g.in(tree_of, m * 4);
+    const int tr = g.in(p.trees.data(), (size_t)ntrees * sizeof(TsTree));
+    const int lo = g.in(lock, m * p.Dtmax), ld = g.in(lock ? locked : nullptr, trows * 2);
+    const int ro = g.in(river_lock, m * p.Drmax), rd = g.in(river_lock ? river_locked : nullptr, rrows * 2);
+    const int re = g.in(reach, row * 4), an = g.in(at, m), ac = g.in(at ? at_card : nullptr, m);
+    const int tz = g.in(t0, m * 4), rg = g.inout(regret, trows * 8), av = g.inout(average, trows * 8);
+    const int rrg = g.inout(river_regret, rrows * 8), rav = g.inout(river_average, rrows * 8);
+    const int sg = g.out(strategy, trows * 2), rs = g.out(river_strategy, rrows * 2);
+    const int va = g.out(value, row * 8), be = g.out(br, row * 8);
+    const int nr = g.out(node_reach, row * 4), nv = g.out(node_value, row * 8), nb = g.out(node_br, row * 8), su = g.out(status, m);
+    return eq_call_host(call, device, m, EQ_TAB_EVAL, g, ts_work_bytes(m, p.ntmax, p.nrmax, true), [&](hipStream_t st, const uint32_t *tab, char *work) {
+        return ts_launch_resume(st, tab, TsSpots{g.at<uint8_t>(bo), g.at<uint64_t>(de), g.at<uint16_t>(ra)},
+                                TsTrees{g.at<TsTree>(tr), g.at<uint32_t>(to), p.ntmax, p.nrmax, p.Dtmax, p.Drmax}, ntrees,
+                                TsLock{g.at<uint8_t>(lo), g.at<uint16_t>(ld), g.at<uint8_t>(ro), g.at<uint16_t>(rd)},
+                                TsResolve{g.at<uint32_t>(re), g.at<uint8_t>(an), g.at<uint8_t>(ac), g.at<uint32_t>(nr), g.at<int64_t>(nv), g.at<int64_t>(nb)},
+                                TsResume{g.at<uint32_t>(tz), g.at<int64_t>(rg), g.at<int64_t>(av), g.at<int64_t>(rrg), g.at<int64_t>(rav)}, iters, m,
+                                TsOut{g.at<uint16_t>(sg), g.at<uint16_t>(rs), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
     });
 }
 

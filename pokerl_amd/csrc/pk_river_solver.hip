@@ -25,6 +25,9 @@
 //                   caller in the solver's own units, a terminal of kind RS_GIVEN takes its values from the caller, and the owners write both
 //                   players' reaches, values and best-response values at the node the spot names.  k_resolve_prep follows the other
 //                   preparation kernels and refuses a spot whose node (or, in the turn solver, river card) does not exist.
+//   k_resume_prep / k_resume_river_solve   the same body with RESUME ("Resuming a solve"): the regrets and the average
+//                   accumulators come from and go back to the caller's memory, a spot runs iterations t0 + 1 .. t0 + iters.  k_resume_prep refuses a
+//                   spot whose t0 + iters passes 4 096 (PK_EQ_BAD_ITER); a refused spot's state is not touched.
 // Ordinary vector stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_river_solver_host.py reads the code object).
 #include <hip/hip_runtime.h>
 
@@ -88,12 +91,17 @@ __global__ void __launch_bounds__(RS_PREP_BLOCK) k_trees_prep(const uint32_t *__
 // there, the walk up leaves R and A alone, the average-strategy stage writes `strategy` from SG.  A NULL tree_of: every spot uses tree 0.
 // RESOLVE (with LOCK; "Re-solving"): rz.reach, where given, is the root's reaches; an RS_GIVEN terminal's values are rz.given's;
 // after the final walk up the owners write rz.node_reach / node_value / node_br at node rz.at[spot], which k_resolve_prep has seen below n.
-template <bool PER_SPOT, bool LOCK = false, bool RESOLVE = false>
+// RESUME (with RESOLVE; "Resuming a solve"): rm.regret / rm.average are the caller's R and A in the layout of `strategy`,
+// rm.t0[spot] the iterations they already hold (NULL: 0).  A spot with t0 > 0 starts from them (clamped) at its free rows and runs t = t0 + 1 ..
+// t0 + iters; after the last iteration and BEFORE the average-strategy stage -- the final passes take the memory of R and A -- the owners write both
+// back.  A spot with t0 = 0 reads nothing and has every other entry of its slice written 0; a refused spot's slice is not touched.
+template <bool PER_SPOT, bool LOCK = false, bool RESOLVE = false, bool RESUME = false>
 __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, const RsTree *tree, const uint32_t *tree_of,
                                               uint32_t nmax, uint32_t Dmax, const RsSpots &spots, const RsOut &out, char *ws, uint32_t iters, uint32_t m,
-                                              const RsLock &lk = RsLock{}, const RsResolve &rz = RsResolve{}) {
+                                              const RsLock &lk = RsLock{}, const RsResolve &rz = RsResolve{}, const RsResume &rm = RsResume{}) {
     static_assert(PER_SPOT || !LOCK, "the locked call has the tree-per-spot form only");
     static_assert(LOCK || !RESOLVE, "the re-solving call is the locked call with more arguments");
+    static_assert(RESOLVE || !RESUME, "the resuming call is the re-solving call with more arguments");
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     __shared__ uint64_t slot[RS_SLOTS];               // key << 11 | pool holding, sorted once per spot; all ones = no holding.  After the
                                                       // sort the same memory holds rs and posof (below)
@@ -150,6 +158,13 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
             if (!good) D = 0;
         }
         const uint32_t DS = PER_SPOT ? Dmax : D;      // the row stride of `strategy`
+        // ---- the iterations the spot's state holds; fresh: a solved spot that starts from nothing, whose unread state entries become 0
+        uint32_t t0 = 0;
+        bool fresh = false;
+        if constexpr (RESUME) {
+            t0 = (good && rm.t0) ? uniform(rm.t0[spot]) : 0u;
+            fresh = good && t0 == 0u;
+        }
         // ---- zeros: every output at the holdings that are not in the pool, by the lanes of the fixed index h = tid + 512 j
         for (uint32_t h = tid; h < (uint32_t)RS_HOLDINGS; h += RS_BLOCK) {
             uint32_t ca = 0, cb = 1;
@@ -166,6 +181,12 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
             }
             if (out.strategy)
                 for (uint32_t r = 0; r < DS * 4u; ++r) out.strategy[((size_t)spot * DS * 4 + r) * RS_HOLDINGS + h] = 0;
+            if constexpr (RESUME)
+                if (fresh)
+                    for (uint32_t r = 0; r < DS * 4u; ++r) {
+                        rm.regret[((size_t)spot * DS * 4 + r) * RS_HOLDINGS + h] = 0;
+                        rm.average[((size_t)spot * DS * 4 + r) * RS_HOLDINGS + h] = 0;
+                    }
         }
         // ... and, where the call's stride is wider than the spot's tree, the rows past its own at the holdings of the pool
         if constexpr (PER_SPOT)
@@ -175,6 +196,17 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
                     unpair(h, ca, cb);
                     if (!((avail >> ca) & (avail >> cb) & 1ull)) continue;
                     for (uint32_t r = D * 4u; r < DS * 4u; ++r) out.strategy[((size_t)spot * DS * 4 + r) * RS_HOLDINGS + h] = 0;
+                }
+        if constexpr (RESUME)
+            if (fresh && D < DS)
+                for (uint32_t h = tid; h < (uint32_t)RS_HOLDINGS; h += RS_BLOCK) {
+                    uint32_t ca = 0, cb = 1;
+                    unpair(h, ca, cb);
+                    if (!((avail >> ca) & (avail >> cb) & 1ull)) continue;
+                    for (uint32_t r = D * 4u; r < DS * 4u; ++r) {
+                        rm.regret[((size_t)spot * DS * 4 + r) * RS_HOLDINGS + h] = 0;
+                        rm.average[((size_t)spot * DS * 4 + r) * RS_HOLDINGS + h] = 0;
+                    }
                 }
         if (!good) continue;
         fill_pool(pool, canon, avail, tid);
@@ -283,6 +315,29 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
             }
         }
         auto locked_at = [&](uint32_t node) -> bool { return LOCK && ((lockm >> node) & 1ull) != 0ull; };
+        // ---- a resumed spot: R and A of its free rows from the caller's state, by the owner of each position
+        if constexpr (RESUME)
+            if (t0 > 0u)
+                for (uint32_t node = 0; node < n; ++node) {
+                    if (uniform((uint32_t)tr.kind[PK_IDX(node, RS_MAX_NODES, "kind")]) > RS_P1 || locked_at(node)) continue;
+                    const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, RS_MAX_NODES, "nact")]), row = uniform((uint32_t)tr.row[PK_IDX(node, RS_MAX_NODES, "row")]);
+                    uint32_t ch[4];
+                    kids(node, nact, ch);
+                    const size_t o = ((size_t)spot * DS + PK_IDX(row, DS, "state row")) * 4 * RS_HOLDINGS;
+#pragma unroll
+                    for (int j = 0; j < RS_PER_LANE; ++j) {
+                        const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                        if (i >= nh) continue;
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) {
+                            if ((uint32_t)a >= nact) continue;
+                            const size_t g = o + (size_t)a * RS_HOLDINGS + PK_IDX(gh[j], RS_HOLDINGS, "state");
+                            const int64_t r = rm.regret[g], v = rm.average[g];
+                            R[at(ch[a], i)] = r < 0 ? 0 : r > RS_RESUME_RMAX ? RS_RESUME_RMAX : r;
+                            A[at(ch[a], i)] = v < 0 ? 0 : v > RS_RESUME_AMAX ? RS_RESUME_AMAX : v;
+                        }
+                    }
+                }
         __syncthreads();                              // (posof)
 
         // A terminal node: both players' values of every holding from the opponent's reaches (every lane of the workgroup comes here)
@@ -410,6 +465,7 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
 
         // ---- the iterations: one walk down, then the walk up with the regret and accumulator updates of each decision node
         for (uint32_t t = 1; t <= iters; ++t) {
+            const uint32_t tw = RESUME ? t0 + t : t;  // (the iteration's number: all that t enters is the accumulators' weight)
             down(true);
             for (uint32_t node = n; node-- > 0u;) {
                 const uint32_t kind = uniform((uint32_t)tr.kind[PK_IDX(node, RS_MAX_NODES, "kind")]);
@@ -443,11 +499,37 @@ __device__ __forceinline__ void rs_solve_body(const uint32_t *__restrict__ tab, 
                         const int64_t r = R[e] + up[a] - un;
                         R[e] = r > 0 ? r : 0;
                         const uint64_t rr = RR[e];
-                        A[e] += (int64_t)((uint64_t)t * (uint64_t)(kind == RS_P0 ? (uint32_t)rr : (uint32_t)(rr >> 32)));
+                        A[e] += (int64_t)((uint64_t)tw * (uint64_t)(kind == RS_P0 ? (uint32_t)rr : (uint32_t)(rr >> 32)));
                     }
                 }
             }
         }
+
+        // ---- the state goes back to the caller: R and A as they stand at the free rows; at a locked row and at the action slots past nact a
+        // fresh spot writes 0, a resumed one nothing
+        if constexpr (RESUME)
+            for (uint32_t node = 0; node < n; ++node) {
+                if (uniform((uint32_t)tr.kind[PK_IDX(node, RS_MAX_NODES, "kind")]) > RS_P1) continue;
+                const bool locked = locked_at(node);
+                if (locked && !fresh) continue;
+                const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, RS_MAX_NODES, "nact")]), row = uniform((uint32_t)tr.row[PK_IDX(node, RS_MAX_NODES, "row")]);
+                uint32_t ch[4];
+                kids(node, nact, ch);
+                const size_t o = ((size_t)spot * DS + PK_IDX(row, DS, "state row")) * 4 * RS_HOLDINGS;
+#pragma unroll
+                for (int j = 0; j < RS_PER_LANE; ++j) {
+                    const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                    if (i >= nh) continue;
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        const bool live = (uint32_t)a < nact && !locked;
+                        if (!(live || fresh)) continue;
+                        const size_t g = o + (size_t)a * RS_HOLDINGS + PK_IDX(gh[j], RS_HOLDINGS, "state");
+                        rm.regret[g] = live ? R[at(ch[a], i)] : 0;
+                        rm.average[g] = live ? A[at(ch[a], i)] : 0;
+                    }
+                }
+            }
 
         // ---- the average strategy: the rule applied to the accumulators; it stays in SG for the last walk
         for (uint32_t node = 0; node < n; ++node) {
@@ -563,6 +645,22 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_resolve_river_solve(const uint3
     rs_solve_body<true, true, true>(tab, desc, trees.trees, trees.tree_of, trees.nmax, trees.Dmax, spots, out, ws, iters, m, lk, rz);
 }
 
+// the resuming call: k_resolve_river_solve's body with RESUME (the name begins with none of the prefixes host tests list kernels by)
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_resume_river_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, RsTrees trees, RsLock lk,
+                                                                    RsResolve rz, RsResume rm, RsSpots spots, RsOut out, char *ws, uint32_t iters, uint32_t m) {
+    rs_solve_body<true, true, true, true>(tab, desc, trees.trees, trees.tree_of, trees.nmax, trees.Dmax, spots, out, ws, iters, m, lk, rz, rm);
+}
+
+// The last part of a resuming call's preparation (pk_river_solver.hpp): one lane per spot, only spots that are still good are judged
+__global__ void __launch_bounds__(RS_PREP_BLOCK) k_resume_prep(const uint32_t *__restrict__ t0, uint32_t iters, uint64_t *desc, uint8_t *status, size_t m) {
+    const size_t i = (size_t)blockIdx.x * RS_PREP_BLOCK + threadIdx.x;
+    if (i >= m) return;
+    uint64_t *d = desc + i * (size_t)RS_DESC_WORDS;
+    if (!(d[2] & 1ull) || (uint64_t)t0[i] + iters <= (uint64_t)RS_MAX_ITERS) return;
+    d[2] &= ~1ull;
+    if (status) status[i] |= (uint8_t)PK_EQ_BAD_ITER;
+}
+
 // The last part of a re-solving call's preparation (pk_river_solver.hpp): one lane per spot, only spots that are still good are judged
 struct ResolvePrepArgs {
     const char *trees;
@@ -653,6 +751,26 @@ hipError_t rs_launch_resolve(hipStream_t stream, const uint32_t *tab, const RsSp
     if (e == hipSuccess && rz.at) e = resolve_prep_launch(stream, trees.trees, (uint32_t)sizeof(RsTree), 0u, trees.tree_of, rz.at, nullptr, (uint64_t *)work, out.status, m);
     if (e != hipSuccess || !(out.strategy || out.value || out.br || rz.at)) return e;   // (status alone: the preparation kernels have written it)
     hipLaunchKernelGGL(k_resolve_river_solve, dim3(rs_grid(m)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, lk, rz, spots, out,
+                       work + rs_desc_bytes(m), iters, (uint32_t)m);
+    return hipGetLastError();
+}
+
+hipError_t resume_prep_launch(hipStream_t stream, const uint32_t *t0, uint32_t iters, uint64_t *desc, uint8_t *status, size_t m) {
+    hipLaunchKernelGGL(k_resume_prep, dim3((unsigned)((m + RS_PREP_BLOCK - 1) / RS_PREP_BLOCK)), dim3(RS_PREP_BLOCK), 0, stream, t0, iters, desc, status, m);
+    return hipGetLastError();
+}
+
+hipError_t rs_launch_resume(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTrees &trees, uint32_t ntrees, const RsLock &lk,
+                            const RsResolve &rz, const RsResume &rm, uint32_t iters, size_t m, const RsOut &out, char *work) {
+    if (m == 0) return hipSuccess;
+    const RsPrepArgs a{spots, out.status, (uint64_t *)work, m};
+    hipLaunchKernelGGL(k_rs_prep, dim3((unsigned)((m + RS_PREP_BLOCK - 1) / RS_PREP_BLOCK)), dim3(RS_PREP_BLOCK), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && trees.tree_of) e = trees_prep_launch(stream, trees.tree_of, ntrees, (uint64_t *)work, out.status, m);
+    if (e == hipSuccess && rz.at) e = resolve_prep_launch(stream, trees.trees, (uint32_t)sizeof(RsTree), 0u, trees.tree_of, rz.at, nullptr, (uint64_t *)work, out.status, m);
+    if (e == hipSuccess && rm.t0) e = resume_prep_launch(stream, rm.t0, iters, (uint64_t *)work, out.status, m);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_resume_river_solve, dim3(rs_grid(m)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, lk, rz, rm, spots, out,
                        work + rs_desc_bytes(m), iters, (uint32_t)m);
     return hipGetLastError();
 }

@@ -106,4 +106,21 @@ hipError_t resolve_prep_launch(hipStream_t stream, const void *trees, uint32_t s
 hipError_t rs_launch_resolve(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTrees &trees, uint32_t ntrees, const RsLock &lk,
                              const RsResolve &rz, uint32_t iters, size_t m, const RsOut &out, char *work);
 
+
+// ---- resuming (include/pokerl_hip.h "Resuming a solve"): the regrets and the average accumulators of a solve, IN and OUT
+// in the caller's memory, and the number of iterations they hold.  regret and average are given together (the host check); t0 may be NULL (all 0).
+constexpr int64_t RS_RESUME_RMAX = ((int64_t)1 << 58) - 1;   // what a loaded regret / accumulator is clamped to: the header's bounds for 4 096
+constexpr int64_t RS_RESUME_AMAX = ((int64_t)1 << 44) - 1;   // iterations, so that 4 096 further ones still fit (its arithmetic is there)
+struct RsResume {
+    const uint32_t *t0;        // [m]
+    int64_t *regret, *average; // [m][Dmax][4][1326], the layout of `strategy`
+};
+// k_resume_prep, queued behind the other preparation kernels: one lane per spot that is still good; t0[i] + iters > 4 096: PK_EQ_BAD_ITER,
+// which clears the descriptor's "good" bit (the turn solver's launch calls it too)
+hipError_t resume_prep_launch(hipStream_t stream, const uint32_t *t0, uint32_t iters, uint64_t *desc, uint8_t *status, size_t m);
+// rs_launch_resolve's launches with k_resume_prep (where rm.t0 is given) and k_resume_river_solve; rm.regret and rm.average are not NULL.  The
+// solve kernel always runs: the state is an output
+hipError_t rs_launch_resume(hipStream_t stream, const uint32_t *tab, const RsSpots &spots, const RsTrees &trees, uint32_t ntrees, const RsLock &lk,
+                            const RsResolve &rz, const RsResume &rm, uint32_t iters, size_t m, const RsOut &out, char *work);
+
 }  // namespace pk

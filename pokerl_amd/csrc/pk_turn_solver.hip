@@ -25,6 +25,8 @@
 //                   own units, and the owners write both players' reaches, values and best-response values at the node the spot names: a
 //                   turn-level node's after the last walk up, by turn slot; a river-level node's under the river card the spot names, inside
 //                   the final pass's card loop after that card's walk up, by sorted position (the next card rewrites them).
+//   k_resume_turn_solve   the same body with RESUME ("Resuming a solve"): the regrets and the average accumulators of both
+//                   levels come from and go back to the caller's memory, before the final passes take the memory of R and A.
 // Ordinary vector stores and LDS loads / stores only; no atomics, no scratch memory (tests/test_turn_solver_host.py reads the code object).
 #include <hip/hip_runtime.h>
 
@@ -92,12 +94,19 @@ struct TsLevel {
 // the memory of R and A.  A NULL tree_of: every spot uses tree 0.
 // RESOLVE (with LOCK; "Re-solving"): rz.reach, where given, is the root's reaches; the node outputs of node rz.at[spot], which
 // k_resolve_prep (pk_river_solver.hip) has seen below n, and for a river-level node rz.at_card[spot] in the pool.
-template <bool PER_SPOT, bool LOCK = false, bool RESOLVE = false>
+// RESUME (with RESOLVE; "Resuming a solve"): rm.regret / rm.average (turn level, the layout of `strategy`) and rm.river_regret /
+// rm.river_average (river level, the layout of `river_strategy`) are the caller's R and A, rm.t0[spot] the iterations they hold (NULL: 0).  A spot
+// with t0 > 0 starts from them (clamped) at its free rows and runs t = t0 + 1 .. t0 + iters; after the last iteration and BEFORE the average-strategy
+// stage -- the final passes take the memory of R and A -- the owners write both back, a turn-level entry by its turn slot, a river-level one by its
+// sorted position under each card.  A locked river-level node's packed word never leaves: its row is skipped.  A spot with t0 = 0 reads nothing and
+// has every other entry of its slices written 0; a refused spot's slices are not touched.
+template <bool PER_SPOT, bool LOCK = false, bool RESOLVE = false, bool RESUME = false>
 static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, const TsTree *tree, const TsTrees &mx,
                                                      const TsSpots &spots, const TsOut &out, char *ws, uint32_t iters, uint32_t m,
-                                                     const TsLock &lk = TsLock{}, const TsResolve &rz = TsResolve{}) {
+                                                     const TsLock &lk = TsLock{}, const TsResolve &rz = TsResolve{}, const TsResume &rm = TsResume{}) {
     static_assert(PER_SPOT || !LOCK, "the locked call has the tree-per-spot form only");
     static_assert(LOCK || !RESOLVE, "the re-solving call is the locked call with more arguments");
+    static_assert(RESOLVE || !RESUME, "the resuming call is the re-solving call with more arguments");
     __shared__ uint32_t T[EVAL7_TAB_WORDS];
     __shared__ uint64_t slot[RS_SLOTS];               // key << 11 | turn slot, sorted once per spot and card; all ones = no holding.  Between
                                                       // the sorts the same memory holds rs and posof, or a turn-level fold's reaches
@@ -178,6 +187,13 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
             if (!good) { Dt = 0; Dr = 0; }
         }
         const uint32_t DtS = PER_SPOT ? mx.Dtmax : Dt, DrS = PER_SPOT ? mx.Drmax : Dr;               // the row strides of the strategies
+        // ---- the iterations the spot's state holds; fresh: a solved spot that starts from nothing, whose unread state entries become 0
+        uint32_t t0 = 0;
+        bool fresh = false;
+        if constexpr (RESUME) {
+            t0 = (good && rm.t0) ? uniform(rm.t0[spot]) : 0u;
+            fresh = good && t0 == 0u;
+        }
         // ---- the node of the node outputs; a river-level one: the pool slot of its river card, whose holdings are no holdings there
         bool nodes = false, at_river = false;
         uint32_t an = 0, at_cs = 0;
@@ -247,6 +263,30 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
                         for (uint32_t a = 0; a < 4u; ++a) out.river_strategy[((((size_t)spot * DrS + r) * 52 + k) * 4 + a) * RS_HOLDINGS + h] = 0;
                 }
         }
+        // ... and of a fresh spot's state every entry outside the pool's holdings (and cards) and every row past its own tree's
+        if constexpr (RESUME)
+            if (fresh) {
+                for (uint32_t h = tid; h < (uint32_t)RS_HOLDINGS; h += RS_BLOCK) {
+                    uint32_t ca = 0, cb = 1;
+                    unpair(h, ca, cb);
+                    const bool in = ((avail >> ca) & (avail >> cb) & 1ull) != 0ull;
+                    for (uint32_t r = (in ? Dt : 0u) * 4u; r < DtS * 4u; ++r) {
+                        rm.regret[((size_t)spot * DtS * 4 + r) * RS_HOLDINGS + h] = 0;
+                        rm.average[((size_t)spot * DtS * 4 + r) * RS_HOLDINGS + h] = 0;
+                    }
+                }
+                for (uint32_t e = tid; e < 52u * (uint32_t)RS_HOLDINGS; e += RS_BLOCK) {
+                    const uint32_t k = e / (uint32_t)RS_HOLDINGS, h = e - k * (uint32_t)RS_HOLDINGS;
+                    uint32_t ca = 0, cb = 1;
+                    unpair(h, ca, cb);
+                    const bool in = ((avail >> ca) & (avail >> cb) & (avail >> k) & 1ull) && k != ca && k != cb;
+                    for (uint32_t r = in ? Dr : 0u; r < DrS; ++r)
+                        for (uint32_t a = 0; a < 4u; ++a) {
+                            rm.river_regret[((((size_t)spot * DrS + r) * 52 + k) * 4 + a) * RS_HOLDINGS + h] = 0;
+                            rm.river_average[((((size_t)spot * DrS + r) * 52 + k) * 4 + a) * RS_HOLDINGS + h] = 0;
+                        }
+                }
+            }
         if (!good) continue;
         fill_pool(pool, canon, avail, tid);
         const uint32_t nT = tri(P), nh = tri(P - 1u), K = P - 4u;
@@ -396,6 +436,70 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
                 }
             }
         }
+        // ---- a resumed spot: R and A of its free rows from the caller's state, by the owner of each slot and of each card's positions.  The store
+        // after the iterations is the same walk the other way: `load` false, and a fresh spot writes 0 at a locked row and past nact
+        auto state_walk = [&](bool load) {
+            for (uint32_t node = 0; node < n; ++node) {
+                if (kind_of(node) > RS_P1) continue;
+                const bool locked = locked_at(node);
+                if (locked && (load || !fresh)) continue;
+                const uint32_t nact = uniform((uint32_t)tr.nact[PK_IDX(node, TS_MAX_NODES, "nact")]), row = uniform((uint32_t)tr.row[PK_IDX(node, TS_MAX_NODES, "row")]);
+                uint32_t ch[4];
+                kids(node, nact, ch);
+                size_t cr[4];
+                if (!is_river(node)) {
+                    rows_of(Lturn, ch, nact, cr);
+                    const size_t o = ((size_t)spot * DtS + PK_IDX(row, DtS, "state row")) * 4 * RS_HOLDINGS;
+#pragma unroll
+                    for (int j = 0; j < RS_PER_LANE; ++j) {
+                        const uint32_t s = tid + (uint32_t)j * RS_BLOCK;
+                        if (s >= nT) continue;
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) {
+                            const bool live = (uint32_t)a < nact && !locked;
+                            if (!(live || (fresh && !load))) continue;
+                            const size_t g = o + (size_t)a * RS_HOLDINGS + PK_IDX(gh[j], RS_HOLDINGS, "state"), e = live ? at(Lturn, cr[a], s) : 0;
+                            if (load) {
+                                const int64_t r = rm.regret[g], v = rm.average[g];
+                                Rt[e] = r < 0 ? 0 : r > TS_RESUME_RMAX ? TS_RESUME_RMAX : r;
+                                At[e] = v < 0 ? 0 : v > TS_RESUME_AMAX ? TS_RESUME_AMAX : v;
+                            } else {
+                                rm.regret[g] = live ? Rt[e] : 0;
+                                rm.average[g] = live ? At[e] : 0;
+                            }
+                        }
+                    }
+                    continue;
+                }
+                for (uint32_t cs = 0; cs < P; ++cs) {
+                    const TsLevel L = river_level(cs);
+                    rows_of(L, ch, nact, cr);
+                    const size_t o = (((size_t)spot * DrS + PK_IDX(row, DrS, "state row")) * 52 + canon[PK_IDX(cs, 64, "canon")]) * 4 * RS_HOLDINGS;
+#pragma unroll
+                    for (int j = 0; j < RS_PER_LANE; ++j) {
+                        const uint32_t i = tid + (uint32_t)j * RS_BLOCK;
+                        if (i >= nh) continue;
+                        const uint32_t fx = fixed(slotof[tab_at(cs, i)]);
+#pragma unroll
+                        for (int a = 0; a < 4; ++a) {
+                            const bool live = (uint32_t)a < nact && !locked;
+                            if (!(live || (fresh && !load))) continue;
+                            const size_t g = o + (size_t)a * RS_HOLDINGS + PK_IDX(fx, RS_HOLDINGS, "state"), e = live ? at(L, cr[a], i) : 0;
+                            if (load) {
+                                const int64_t r = rm.river_regret[g], v = rm.river_average[g];
+                                L.R[e] = r < 0 ? 0 : r > TS_RESUME_RMAX ? TS_RESUME_RMAX : r;
+                                L.A[e] = v < 0 ? 0 : v > TS_RESUME_AMAX ? TS_RESUME_AMAX : v;
+                            } else {
+                                rm.river_regret[g] = live ? L.R[e] : 0;
+                                rm.river_average[g] = live ? L.A[e] : 0;
+                            }
+                        }
+                    }
+                }
+            }
+        };
+        if constexpr (RESUME)
+            if (t0 > 0u) state_walk(true);
         auto unpack = [](int64_t w, uint32_t (&sig)[4]) {
 #pragma unroll
             for (int a = 0; a < 4; ++a) sig[a] = (uint32_t)((uint64_t)w >> (16 * a)) & 0xFFFFu;
@@ -669,6 +773,7 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
 
         // ---- the iterations
         for (uint32_t t = 1; t <= iters; ++t) {
+            const uint32_t tw = RESUME ? t0 + t : t;  // (the iteration's number: all that t enters is the accumulators' weight)
             turn_down(true, false);
             for (uint32_t cs = 0; cs < P; ++cs) {
                 const TsLevel L = river_level(cs);
@@ -687,15 +792,17 @@ static __device__ __forceinline__ void ts_solve_body(const uint32_t *__restrict_
                             U0t[e] += L.U0[at(L, crow, i)];
                             U1t[e] += L.U1[at(L, crow, i)];
                         }
-                    } else if (is_river(node) && kind <= RS_P1) decide_up(L, node, kind, t);
+                    } else if (is_river(node) && kind <= RS_P1) decide_up(L, node, kind, tw);
                 }
             }
             __syncthreads();                          // (the last card's sums)
             for (uint32_t node = n; node-- > 0u;) {
                 const uint32_t kind = kind_of(node);
-                if (!is_river(node) && kind <= RS_P1) decide_up(Lturn, node, kind, t);
+                if (!is_river(node) && kind <= RS_P1) decide_up(Lturn, node, kind, tw);
             }
         }
+        // ---- the state goes back to the caller, before the final passes take the memory of R and A
+        if constexpr (RESUME) state_walk(false);
 
         // ---- the average strategy: the rule applied to the accumulators; it stays in SG for the last walk
         auto average = [&](const TsLevel &L, uint32_t node, uint32_t cs, bool river) {
@@ -834,6 +941,12 @@ __global__ void __launch_bounds__(RS_BLOCK, 2) k_resolve_turn_solve(const uint32
     ts_solve_body<true, true, true>(tab, desc, trees.trees, trees, spots, out, ws, iters, m, lk, rz);
 }
 
+// the resuming call: k_resolve_turn_solve's body with RESUME (the name begins with none of the prefixes host tests list kernels by)
+__global__ void __launch_bounds__(RS_BLOCK, 2) k_resume_turn_solve(const uint32_t *__restrict__ tab, const uint64_t *__restrict__ desc, TsTrees trees, TsLock lk,
+                                                                   TsResolve rz, TsResume rm, TsSpots spots, TsOut out, char *ws, uint32_t iters, uint32_t m) {
+    ts_solve_body<true, true, true, true>(tab, desc, trees.trees, trees, spots, out, ws, iters, m, lk, rz, rm);
+}
+
 namespace pk {
 
 hipError_t ts_launch(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTree &tree, uint32_t iters, size_t m, const TsOut &out,
@@ -886,6 +999,23 @@ hipError_t ts_launch_resolve(hipStream_t stream, const uint32_t *tab, const TsSp
                                 out.status, m);
     if (e != hipSuccess || !(out.strategy || out.river_strategy || out.value || out.br || rz.at)) return e;   // (status alone: the preparation kernels have written it)
     hipLaunchKernelGGL(k_resolve_turn_solve, dim3(ts_grid(m, trees.ntmax, trees.nrmax)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, lk, rz,
+                       spots, out, work + rs_desc_bytes(m), iters, (uint32_t)m);
+    return hipGetLastError();
+}
+
+hipError_t ts_launch_resume(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTrees &trees, uint32_t ntrees, const TsLock &lk,
+                            const TsResolve &rz, const TsResume &rm, uint32_t iters, size_t m, const TsOut &out, char *work) {
+    if (m == 0) return hipSuccess;
+    const TsPrepArgs a{spots, out.status, (uint64_t *)work, m};
+    hipLaunchKernelGGL(k_ts_prep, dim3((unsigned)((m + TS_PREP_BLOCK - 1) / TS_PREP_BLOCK)), dim3(TS_PREP_BLOCK), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && trees.tree_of) e = trees_prep_launch(stream, trees.tree_of, ntrees, (uint64_t *)work, out.status, m);
+    if (e == hipSuccess && rz.at)
+        e = resolve_prep_launch(stream, trees.trees, (uint32_t)sizeof(TsTree), (uint32_t)offsetof(TsTree, river), trees.tree_of, rz.at, rz.at_card, (uint64_t *)work,
+                                out.status, m);
+    if (e == hipSuccess && rm.t0) e = resume_prep_launch(stream, rm.t0, iters, (uint64_t *)work, out.status, m);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_resume_turn_solve, dim3(ts_grid(m, trees.ntmax, trees.nrmax)), dim3(RS_BLOCK), 0, stream, tab, (const uint64_t *)work, trees, lk, rz, rm,
                        spots, out, work + rs_desc_bytes(m), iters, (uint32_t)m);
     return hipGetLastError();
 }

@@ -102,4 +102,19 @@ struct TsResolve {
 hipError_t ts_launch_resolve(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTrees &trees, uint32_t ntrees, const TsLock &lk,
                              const TsResolve &rz, uint32_t iters, size_t m, const TsOut &out, char *work);
 
+
+// ---- resuming (include/pokerl_hip.h "Resuming a solve"): the regrets and the average accumulators of both levels, IN and
+// OUT in the caller's memory, and the number of iterations they hold.  The four arrays are given together (the host check); t0 may be NULL (all 0).
+constexpr int64_t TS_RESUME_RMAX = ((int64_t)1 << 60) - 1;   // what a loaded regret / accumulator is clamped to: the header's bounds for 4 096
+constexpr int64_t TS_RESUME_AMAX = ((int64_t)1 << 41) - 1;   // iterations, so that 4 096 further ones still fit (its arithmetic is there)
+struct TsResume {
+    const uint32_t *t0;                    // [m]
+    int64_t *regret, *average;             // [m][Dtmax][4][1326], the layout of `strategy`
+    int64_t *river_regret, *river_average; // [m][Drmax][52][4][1326], the layout of `river_strategy`
+};
+// ts_launch_resolve's launches with k_resume_prep (pk_river_solver.hip; where rm.t0 is given) and k_resume_turn_solve; the four state arrays are
+// not NULL.  The solve kernel always runs: the state is an output
+hipError_t ts_launch_resume(hipStream_t stream, const uint32_t *tab, const TsSpots &spots, const TsTrees &trees, uint32_t ntrees, const TsLock &lk,
+                            const TsResolve &rz, const TsResume &rm, uint32_t iters, size_t m, const TsOut &out, char *work);
+
 }  // namespace pk

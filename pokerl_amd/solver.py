@@ -12,7 +12,11 @@ evaluate_river / evaluate_turn lock every row: the value and the exploitability 
 Re-solving (pk_solve_river_resolve / pk_solve_turn_resolve; "Re-solving"): every solve function takes reach (the root
 reaches in the solver's own units, instead of ranges), at (a node whose reaches, values and best-response values the solution then carries as
 node_reach / node_value / node_br; the turn forms also at_card) and, on the river, given (the values at a tree's KIND_GIVEN terminal).
-subtree / river_subtree re-root a tree, gadget_tree puts the re-solving gadget on top of one, resolve_river does both kinds of re-solving."""
+subtree / river_subtree re-root a tree, gadget_tree puts the re-solving gadget on top of one, resolve_river does both kinds of re-solving.
+Resuming (pk_solve_river_resume / pk_solve_turn_resume; "Resuming a solve"): every solve function takes state (a
+SolverState: the regrets, the average accumulators and the iterations they hold) and keep_state; the solution then carries .state, which the
+next call continues from.  solve_river_until / solve_turn_until and their _batch forms run such calls, the state on the device, until the
+exploitability is at or under a target."""
 import math
 
 import numpy as np
@@ -176,9 +180,10 @@ class RiverSolution:
 
     _UNIT = 16                  # a root reach per unit of range weight
 
-    def __init__(self, tree, ranges, strategy, value, br, status, valid, trees=None, tree_of=None, node=None, reach=None):
+    def __init__(self, tree, ranges, strategy, value, br, status, valid, trees=None, tree_of=None, node=None, reach=None, state=None):
         self.tree, self.ranges, self.strategy, self.value, self.br, self.status, self.valid = tree, ranges, strategy, value, br, status, valid
         self.trees, self.tree_of = trees, tree_of
+        self.state = state      # resuming: a SolverState (None unless the call was given state or keep_state)
         # re-solving: the root reaches the call was given (None: ranges), and the outputs at the node `at` (None when not asked for)
         self.reach = reach
         self.node_reach, self.node_value, self.node_br = node if node is not None else (None, None, None)
@@ -188,8 +193,13 @@ class RiverSolution:
         if self.trees is not None:
             tree = _spot_tree(self.trees, self.tree_of, i)
             strategy = strategy[:len(tree.decision_nodes) if tree is not None else 0]
+        state = self.state
+        if state is not None:
+            state = state[i]
+            if self.trees is not None:
+                state.regret, state.average = state.regret[:strategy.shape[0]], state.average[:strategy.shape[0]]
         return RiverSolution(tree, _ith(self.ranges, i), strategy, self.value[i], self.br[i], self.status[i], self.valid[i],
-                             node=_ith_node(self, i), reach=_ith(self.reach, i))
+                             node=_ith_node(self, i), reach=_ith(self.reach, i), state=state)
 
     def _weights(self):
         """(w int64 [2, 1326], unit): the weights ev and exploitability reduce by -- the root reaches where the call was given them
@@ -382,6 +392,69 @@ def _node_outputs(at, m):
     return (np.zeros((m, 2, L.EQ_HOLDINGS), np.uint32), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64))
 
 
+class SolverState:
+    """The state of a solve that can be continued: regret and average int64 [D, 4, 1326] (the strategy's shape: the regrets and the average
+    accumulators of every edge) and t, the iterations they hold.  A batch has a leading [m] and t uint32 [m]; state[i] is spot i's.
+    river_regret / river_average are the turn solver's river-level arrays (None: the river solver has none).  An entry the solver does not
+    use -- an action slot past the node's, an invalid holding, a row past the spot's tree, a locked row -- is 0 after a solve from nothing
+    and keeps what it held through a continued one."""
+
+    def __init__(self, regret, average, t, river_regret=None, river_average=None):
+        self.regret, self.average, self.t, self.river_regret, self.river_average = regret, average, t, river_regret, river_average
+
+    def __getitem__(self, i):
+        return SolverState(self.regret[i], self.average[i], self.t[i], _ith(self.river_regret, i), _ith(self.river_average, i))
+
+    @property
+    def nbytes(self):
+        return sum(a.nbytes for a in (self.regret, self.average, self.river_regret, self.river_average) if a is not None)
+
+    def __repr__(self):
+        return "SolverState(t=%r)" % (self.t,)
+
+
+def solver_state_bytes(tree_or_trees, m=1):
+    """The bytes of the state of m spots: two int64 arrays of the strategy's shape, 42 432 bytes per decision row each (the rows of the
+    largest tree passed) -- and for TurnTrees two of river_strategy's, 2 206 464 bytes per river-level row each."""
+    trees = [tree_or_trees] if isinstance(tree_or_trees, RiverTree) else list(tree_or_trees)
+    rows = max(len(t.decision_nodes) for t in trees) + 52 * max(len(getattr(t, "river_decision_nodes", ())) for t in trees)
+    return 2 * int(m) * rows * 4 * L.EQ_HOLDINGS * 8
+
+
+_STATE_NAMES = ("regret", "average", "river_regret", "river_average")
+
+
+def _state_arrays(state, keep_state, m, D, Dr=None):
+    """(t0 uint32 [m], regret, average int64 [m, D, 4, 1326]) -- with Dr (the turn solver) also river_regret, river_average int64
+    [m, Dr, 52, 4, 1326] -- copies, which the call then works in; None where no state is wanted.  state: a SolverState, or the arrays
+    (regret, average, t) -- (regret, average, river_regret, river_average, t) -- of one spot or of m."""
+    shapes = [(D, 4, L.EQ_HOLDINGS)] * 2 + ([] if Dr is None else [(Dr, 52, 4, L.EQ_HOLDINGS)] * 2)
+    if state is None:
+        if not keep_state:
+            return None
+        return (np.zeros(m, np.uint32),) + tuple(np.zeros((m,) + sh, np.int64) for sh in shapes)
+    if isinstance(state, SolverState):
+        state = tuple(getattr(state, k) for k in _STATE_NAMES[:len(shapes)]) + (state.t,)
+    if len(state) != len(shapes) + 1 or any(a is None for a in state):
+        raise ValueError("state is a SolverState of this solver or (%s, t)" % ", ".join(_STATE_NAMES[:len(shapes)]))
+    out = []
+    for a, name, shape in zip(state, _STATE_NAMES, shapes):
+        a = np.asarray(a)
+        if a.dtype.kind not in "iu" or a.shape not in (shape, (m,) + shape):
+            raise ValueError("state.%s must be an integer array of shape %r, with or without a leading [%d]" % (name, list(shape), m))
+        out.append(np.array(np.broadcast_to(a, (m,) + shape), np.int64, order="C"))
+    t = np.asarray(state[-1])
+    if t.dtype.kind not in "iu" or t.shape not in ((), (m,)) or (t.size and (int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF)):
+        raise ValueError("state.t must be a non-negative integer or an integer array of shape [%d]" % m)
+    return (np.array(np.broadcast_to(t, (m,)), np.uint32),) + tuple(out)
+
+
+def _new_state(st, iters, status):
+    """the SolverState after a call that worked in st's arrays: t = t0 + iters at the solved spots, t0 at the refused ones (whose state the
+    library has not touched)"""
+    return SolverState(st[1], st[2], np.where(status == 0, st[0] + np.uint32(iters), st[0]).astype(np.uint32), *st[3:])
+
+
 def gadget_tree(tree, opponent):
     """The re-solving gadget on top of `tree` (Burch, Johanson, Bowling 2014) -> a RiverTree of tree.n + 2 nodes: node 0 is a decision node
     of `opponent` with the children [1, 2], node 1 the KIND_GIVEN terminal ("terminate": the opponent takes the value it was promised),
@@ -409,7 +482,8 @@ def river_trees(pots, stacks, bet_fractions=(0.5, 1.0), max_raises=2):
     return _trees_by_chips(pots, stacks, lambda pot, stack: river_tree(pot, stack, bet_fractions, max_raises))
 
 
-def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=None, lock=None, locked=None, reach=None, given=None, at=None):
+def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=None, lock=None, locked=None, reach=None, given=None, at=None,
+                      state=None, keep_state=False):
     """pk_solve_river on host arrays: board uint8 [m, 5] Card.value, ranges uint16 [m, 2, 1326] over holding_index, one tree for the call,
     dead uint64 [m] masks over canonical card indices (None: none) -> RiverSolution with a leading [m].  A bad spot is reported through
     its status with all-zero outputs; the others are unaffected.
@@ -422,12 +496,16 @@ def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=N
     reach, given, at (pk_solve_river_resolve): reach integers [m, 2, 1326] up to 2^20 - 1, the root reaches in the solver's own units
     (ranges may then be None; ranges << 4 is the same call); given integers [m, 2, 1326] within +- (2^45 - 1), the values at a tree's
     KIND_GIVEN terminal; at an integer or integers [m], the node whose reaches, values and best-response values the solution carries as
-    node_reach, node_value, node_br.  A value outside those bounds is a ValueError here (the library's device forms clamp)."""
+    node_reach, node_value, node_br.  A value outside those bounds is a ValueError here (the library's device forms clamp).
+    state, keep_state (pk_solve_river_resume): state is a SolverState -- the .state of an earlier solution -- or (regret, average, t); the
+    call runs iterations t + 1 .. t + iters from it (its arrays are copied, not changed) and the solution carries the new one as .state.
+    keep_state=True without state starts from nothing and returns the state; iters may be 0.  t + iters > 4096 is status PK_EQ_BAD_ITER."""
     board = np.ascontiguousarray(board, np.uint8)
     if board.ndim != 2 or board.shape[1] != 5:
         raise ValueError("board must have shape [m, 5]")
     m = board.shape[0]
-    resolve = reach is not None or given is not None or at is not None
+    resume = state is not None or keep_state
+    resolve = resume or reach is not None or given is not None or at is not None
     ranges, reach = _resolve_ranges(ranges, reach, m, REACH_MAX)
     given, at = _resolve_given(given, m), _resolve_at(at, m)
     node = _node_outputs(at, m)
@@ -446,7 +524,14 @@ def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=N
         trees, tree, tree_of = (None, tree, None) if one else (rows.trees, None, _tree_of(tree_of, len(rows.trees), m))
         lock, locked = _lock_pair(lock, locked, m, D, (4, L.EQ_HOLDINGS), ("lock", "locked"), "strategy")
         strategy = np.zeros((m, D, 4, L.EQ_HOLDINGS), np.uint16)
-        if resolve:
+        if resume:
+            nr, nv, nb = node or (None, None, None)
+            st = _state_arrays(state, keep_state, m, D)
+            L.check(L.lib().pk_solve_river_resume(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *rows.args(), L.ptr(tree_of), int(iters),
+                                                  L.ptr(lock), L.ptr(locked), L.ptr(reach), L.ptr(given), L.ptr(at), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]),
+                                                  L.ptr(strategy), L.ptr(value), L.ptr(br), L.ptr(nr), L.ptr(nv), L.ptr(nb), L.ptr(status)))
+            state = _new_state(st, iters, status)
+        elif resolve:
             nr, nv, nb = node or (None, None, None)
             L.check(L.lib().pk_solve_river_resolve(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *rows.args(), L.ptr(tree_of), int(iters),
                                                    L.ptr(lock), L.ptr(locked), L.ptr(reach), L.ptr(given), L.ptr(at), L.ptr(strategy), L.ptr(value),
@@ -468,17 +553,27 @@ def solve_river_batch(board, ranges, tree, iters, dead=None, device=0, tree_of=N
         L.check(L.lib().pk_solve_river_trees(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *rows.args(), L.ptr(tree_of), int(iters),
                                              L.ptr(strategy), L.ptr(value), L.ptr(br), L.ptr(status)))
     valid = rvr_valid_holdings(board, np.full(m, 5, np.uint8), dead) & (status == 0)[:, None]
-    return RiverSolution(tree, ranges, strategy, value, br, status, valid, trees, tree_of, node=node, reach=reach)
+    return RiverSolution(tree, ranges, strategy, value, br, status, valid, trees, tree_of, node=node, reach=reach, state=state)
 
 
 def solve_river_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None, value_d=None, br_d=None, status_d=None, device=0, stream=None,
-                  tree_of=None, lock=None, locked=None, reach=None, given=None, at=None, node_reach_d=None, node_value_d=None, node_br_d=None):
+                  tree_of=None, lock=None, locked=None, reach=None, given=None, at=None, node_reach_d=None, node_value_d=None, node_br_d=None,
+                  t0_d=None, regret_d=None, average_d=None):
     """pk_solve_river_d: the same on device-resident buffers (device pointers as ints / c_void_p; the tree stays a host RiverTree; dead_d and
     the outputs may be None), asynchronous on `stream`.  With a SEQUENCE of trees (pk_solve_river_trees_d) tree_of is the DEVICE pointer of
     uint32 [m] and strategy_d holds [m, Dmax, 4, 1326], Dmax the most decision nodes of any tree passed; the trees are packed and queued
     for upload before the call returns.  lock, locked (pk_solve_river_locked_d): DEVICE pointers of uint8 [m, Dmax] and uint16
     [m, Dmax, 4, 1326]; with one RiverTree Dmax is its own D.  reach, given, at and node_reach_d, node_value_d, node_br_d
-    (pk_solve_river_resolve_d): DEVICE pointers of uint32 / int64 [m, 2, 1326] and uint8 [m]; ranges_d may then be None."""
+    (pk_solve_river_resolve_d): DEVICE pointers of uint32 / int64 [m, 2, 1326] and uint8 [m]; ranges_d may then be None.  t0_d, regret_d,
+    average_d (pk_solve_river_resume_d): DEVICE pointers of uint32 [m] (None: all 0) and int64 [m, Dmax, 4, 1326], the state, worked in place."""
+    if any(x is not None for x in (t0_d, regret_d, average_d)):
+        one = isinstance(tree, RiverTree)
+        if one == (tree_of is not None):
+            raise ValueError("tree_of, the device pointer of uint32 [m], comes with a sequence of trees and only with one")
+        L.check(L.lib().pk_solve_river_resume_d(int(device), int(m), board_d, dead_d, ranges_d, *_TreeRows([tree] if one else tree, MAX_NODES).args(),
+                                                tree_of, int(iters), lock, locked, reach, given, at, t0_d, regret_d, average_d, strategy_d, value_d, br_d,
+                                                node_reach_d, node_value_d, node_br_d, status_d, stream))
+        return
     if any(x is not None for x in (reach, given, at, node_reach_d, node_value_d, node_br_d)):
         one = isinstance(tree, RiverTree)
         if one == (tree_of is not None):
@@ -510,21 +605,110 @@ def _one_spot(a):
     return None if a is None else np.asarray(a)[None]
 
 
-def solve_river(board, ranges, tree, iters, dead=(), device=0, lock=None, locked=None, reach=None, given=None, at=None):
+def solve_river(board, ranges, tree, iters, dead=(), device=0, lock=None, locked=None, reach=None, given=None, at=None, state=None, keep_state=False):
     """One subgame.  board: the five board cards (Card-likes / 'RS' strings / Card.value ints); ranges: [2, 1326] integers 0 .. 65535 over
     holding_index, player 0 (first to act) then player 1; dead: cards known to be out of play.  Raises ValueError for an invalid spot.
     A reach starts at weight << 4 and every split rounds down, so ranges of small integers (1, 2, ...) lose weight on the way down the
     tree: scale a range so that its largest weight uses the sixteen bits.  lock bool [D], locked [D, 4, 1326] or a RiverSolution: as
-    solve_river_batch takes them; so are reach [2, 1326] (ranges may then be None), given [2, 1326] and at (a node index)."""
+    solve_river_batch takes them; so are reach [2, 1326] (ranges may then be None), given [2, 1326], at (a node index), state and keep_state."""
     board = list(board)
     if len(board) != 5:
         raise ValueError("five board cards")
     b = np.array([[_card(c) for c in board]], np.uint8)
     d = np.array([dead if isinstance(dead, (int, np.integer)) else dead_mask(dead)], np.uint64)
     r = solve_river_batch(b, _one_spot(ranges), tree, iters, d, device=device, lock=lock, locked=locked, reach=_one_spot(reach), given=_one_spot(given),
-                          at=at)[0]
+                          at=at, state=state, keep_state=keep_state)[0]
+    if state is not None and r.status == L.EQ_BAD_ITER:
+        raise ValueError("the state's iterations and iters together exceed %d" % MAX_ITERS)
     if r.status:
         raise ValueError("invalid spot: " + equity_status_text(r.status))
+    return r
+
+
+def solve_river_until_batch(board, ranges, tree, target, step=64, max_iters=MAX_ITERS, dead=None, device=0, tree_of=None, lock=None, locked=None,
+                            reach=None, given=None):
+    """Solve until every solved spot's exploitability is at or under `target` chips, or max_iters iterations have run: calls of `step`
+    iterations each (the last one shorter where max_iters is no multiple), every spot the same number, the state in DEVICE memory from the
+    first call to the last (solver_state_bytes(tree, m) of it).  The arguments are solve_river_batch's.  -> the last call's RiverSolution
+    with .iters (the iterations run), .trace (float64 [calls, m]: the exploitability of every spot after each call, nan for a refused
+    spot) and .state on the host.  By identity (ii) of the definition the solution is the one solve_river_batch gives with .iters iterations."""
+    from . import hipmem
+    step, max_iters = int(step), int(max_iters)
+    if step < 1 or not 1 <= max_iters <= MAX_ITERS:
+        raise ValueError("step >= 1 and max_iters in 1 .. %d" % MAX_ITERS)
+    board = np.ascontiguousarray(board, np.uint8)
+    if board.ndim != 2 or board.shape[1] != 5:
+        raise ValueError("board must have shape [m, 5]")
+    m = board.shape[0]
+    ranges, reach = _resolve_ranges(ranges, reach, m, REACH_MAX)
+    given = _resolve_given(given, m)
+    if dead is not None:
+        dead = np.ascontiguousarray(dead, np.uint64)
+        if dead.shape != (m,):
+            raise ValueError("dead must have shape [m]")
+    one = isinstance(tree, RiverTree)
+    if one and tree_of is not None:
+        raise ValueError("tree_of needs a sequence of trees")
+    trees = [tree] if one else list(tree)
+    D = max(len(t.decision_nodes) for t in trees)
+    tree_of = None if one else _tree_of(tree_of, len(trees), m)
+    lock, locked = _lock_pair(lock, locked, m, D, (4, L.EQ_HOLDINGS), ("lock", "locked"), "strategy")
+    rows, pair = m * D * 4 * L.EQ_HOLDINGS, m * 2 * L.EQ_HOLDINGS
+    bufs = []
+
+    def dev(a=None, nbytes=0):
+        if a is None and not nbytes:
+            return None
+        b = hipmem.DeviceBuffer(a.nbytes if a is not None else nbytes, device)
+        bufs.append(b)
+        return b.upload(a) if a is not None else b
+    ptr = lambda b: None if b is None else b.ptr
+    try:
+        ins = [dev(a) for a in (board, dead, ranges, tree_of, lock, locked, reach, given)]
+        t0 = np.zeros(m, np.uint32)
+        t0_d, regret_d, average_d = dev(t0), dev(nbytes=rows * 8), dev(nbytes=rows * 8)
+        strategy_d, value_d, br_d, status_d = dev(nbytes=rows * 2), dev(nbytes=pair * 8), dev(nbytes=pair * 8), dev(nbytes=m)
+        trace, done = [], 0
+        while True:
+            it = min(step, max_iters - done)
+            t0_d.upload(t0)
+            solve_river_d(m, ptr(ins[0]), ptr(ins[2]), tree, it, dead_d=ptr(ins[1]), strategy_d=strategy_d.ptr, value_d=value_d.ptr, br_d=br_d.ptr,
+                          status_d=status_d.ptr, device=device, tree_of=ptr(ins[3]), lock=ptr(ins[4]), locked=ptr(ins[5]), reach=ptr(ins[6]),
+                          given=ptr(ins[7]), t0_d=t0_d.ptr, regret_d=regret_d.ptr, average_d=average_d.ptr)
+            value, br = (b.download(np.int64, pair).reshape(m, 2, L.EQ_HOLDINGS) for b in (value_d, br_d))
+            status = status_d.download(np.uint8, m)
+            valid = rvr_valid_holdings(board, np.full(m, 5, np.uint8), dead) & (status == 0)[:, None]
+            sol = RiverSolution(tree if one else None, ranges, None, value, br, status, valid, None if one else trees, tree_of, reach=reach)
+            done += it
+            t0 += np.uint32(it)
+            trace.append([RiverSolution(None, _ith(ranges, i), None, value[i], br[i], status[i], valid[i], reach=_ith(reach, i)).exploitability
+                          if status[i] == 0 else float("nan") for i in range(m)])
+            if done >= max_iters or all(not e > target for e in trace[-1]):
+                break
+        sol.strategy = strategy_d.download(np.uint16, rows).reshape(m, D, 4, L.EQ_HOLDINGS)
+        regret, average = (b.download(np.int64, rows).reshape(m, D, 4, L.EQ_HOLDINGS) for b in (regret_d, average_d))
+        sol.state = SolverState(regret, average, np.where(status == 0, done, 0).astype(np.uint32))
+        sol.iters, sol.trace = done, np.array(trace, np.float64).reshape(len(trace), m)
+        return sol
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def solve_river_until(board, ranges, tree, target, step=64, max_iters=MAX_ITERS, dead=(), device=0, lock=None, locked=None, reach=None, given=None):
+    """One subgame solved to a target: solve_river's arguments, solve_river_until_batch's rule -> its RiverSolution (.iters, .trace float64
+    [calls], .state).  Raises ValueError for an invalid spot."""
+    board = list(board)
+    if len(board) != 5:
+        raise ValueError("five board cards")
+    b = np.array([[_card(c) for c in board]], np.uint8)
+    d = np.array([dead if isinstance(dead, (int, np.integer)) else dead_mask(dead)], np.uint64)
+    full = solve_river_until_batch(b, _one_spot(ranges), tree, target, step, max_iters, d, device=device, lock=lock, locked=locked, reach=_one_spot(reach),
+                                   given=_one_spot(given))
+    r = full[0]
+    if r.status:
+        raise ValueError("invalid spot: " + equity_status_text(r.status))
+    r.iters, r.trace = full.iters, full.trace[:, 0]
     return r
 
 
@@ -650,7 +834,8 @@ class TurnSolution:
 
     _UNIT = 2                   # a root reach per unit of range weight
 
-    def __init__(self, tree, ranges, strategy, river_strategy, value, br, status, valid, pool, trees=None, tree_of=None, node=None, reach=None):
+    def __init__(self, tree, ranges, strategy, river_strategy, value, br, status, valid, pool, trees=None, tree_of=None, node=None, reach=None, state=None):
+        self.state = state      # resuming: a SolverState (None unless the call was given state or keep_state)
         self.tree, self.ranges, self.strategy, self.river_strategy = tree, ranges, strategy, river_strategy
         self.value, self.br, self.status, self.valid, self.pool = value, br, status, valid, pool
         self.trees, self.tree_of = trees, tree_of
@@ -664,8 +849,15 @@ class TurnSolution:
             strategy = strategy[:len(tree.decision_nodes) if tree is not None else 0]
             if rstrat is not None:
                 rstrat = rstrat[:len(tree.river_decision_nodes) if tree is not None else 0]
+        state = self.state
+        if state is not None:
+            state = state[i]
+            if self.trees is not None:
+                nt, nr = (len(tree.decision_nodes), len(tree.river_decision_nodes)) if tree is not None else (0, 0)
+                state.regret, state.average = state.regret[:nt], state.average[:nt]
+                state.river_regret, state.river_average = state.river_regret[:nr], state.river_average[:nr]
         return TurnSolution(tree, _ith(self.ranges, i), strategy, rstrat, self.value[i], self.br[i], self.status[i], self.valid[i], self.pool[i],
-                            node=_ith_node(self, i), reach=_ith(self.reach, i))
+                            node=_ith_node(self, i), reach=_ith(self.reach, i), state=state)
 
     _weights = RiverSolution._weights
     _pair_weight = RiverSolution._pair_weight
@@ -738,7 +930,7 @@ def turn_grid(tree, m=None):
 
 
 def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False, device=0, tree_of=None, lock=None, locked=None, river_lock=None,
-                     river_locked=None, reach=None, at=None, at_card=None):
+                     river_locked=None, reach=None, at=None, at_card=None, state=None, keep_state=False):
     """pk_solve_turn on host arrays: board uint8 [m, 4] Card.value, ranges uint16 [m, 2, 1326] over holding_index, one TurnTree for the
     call, dead uint64 [m] masks over canonical card indices (None: none) -> TurnSolution with a leading [m].  river_strategy=True also
     returns the river-level strategies (551 616 bytes per river-level decision node and spot).
@@ -747,12 +939,15 @@ def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False
     river_strategy's shape): pk_solve_turn_locked, as solve_river_batch takes them.  A TurnSolution as locked also serves as river_locked
     where that is None and river_lock is given.  iters may then be 0.
     reach, at, at_card (pk_solve_turn_resolve): as solve_river_batch takes reach (up to 2^17 - 1; ranges << 1 is the same call) and at;
-    at_card, Card.value integers [m] or one, names the river card under which a river-level node is reported."""
+    at_card, Card.value integers [m] or one, names the river card under which a river-level node is reported.
+    state, keep_state (pk_solve_turn_resume): as solve_river_batch takes them; the state also holds river_regret and river_average, of
+    river_strategy's shape (solver_state_bytes(tree, m) in all: 4.4 MB per river-level row, spot and array)."""
     board = np.ascontiguousarray(board, np.uint8)
     if board.ndim != 2 or board.shape[1] != 4:
         raise ValueError("board must have shape [m, 4]")
     m = board.shape[0]
-    resolve = reach is not None or at is not None or at_card is not None
+    resume = state is not None or keep_state
+    resolve = resume or reach is not None or at is not None or at_card is not None
     ranges, reach = _resolve_ranges(ranges, reach, m, TURN_REACH_MAX)
     at, at_card = _resolve_at(at, m), _resolve_at(at_card, m, "at_card")
     node = _node_outputs(at, m)
@@ -778,7 +973,15 @@ def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False
             tree, tree_of = None, _tree_of(tree_of, len(trees), m)
         lock, locked = _lock_pair(lock, locked, m, Dt, (4, L.EQ_HOLDINGS), ("lock", "locked"), "strategy")
         river_lock, river_locked = _lock_pair(river_lock, river_locked, m, Dr, (52, 4, L.EQ_HOLDINGS), ("river_lock", "river_locked"), "river_strategy")
-        if resolve:
+        if resume:
+            nr, nv, nb = node or (None, None, None)
+            st = _state_arrays(state, keep_state, m, Dt, Dr)
+            L.check(L.lib().pk_solve_turn_resume(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *lrows.args(), L.ptr(tree_of), int(iters),
+                                                 L.ptr(lock), L.ptr(locked), L.ptr(river_lock), L.ptr(river_locked), L.ptr(reach), L.ptr(at),
+                                                 L.ptr(at_card), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]), L.ptr(st[4]), L.ptr(strategy),
+                                                 L.ptr(rstrat), L.ptr(value), L.ptr(br), L.ptr(nr), L.ptr(nv), L.ptr(nb), L.ptr(status)))
+            state = _new_state(st, iters, status)
+        elif resolve:
             nr, nv, nb = node or (None, None, None)
             L.check(L.lib().pk_solve_turn_resolve(int(device), m, L.ptr(board), L.ptr(dead), L.ptr(ranges), *lrows.args(), L.ptr(tree_of), int(iters),
                                                   L.ptr(lock), L.ptr(locked), L.ptr(river_lock), L.ptr(river_locked), L.ptr(reach), L.ptr(at),
@@ -800,17 +1003,27 @@ def solve_turn_batch(board, ranges, tree, iters, dead=None, river_strategy=False
     valid = rvr_valid_holdings(board5, np.full(m, 4, np.uint8), dead) & (status == 0)[:, None]
     pool = np.where(status == 0, valid.sum(axis=1), 0)
     pool = np.array([int(round((1 + math.sqrt(1 + 8 * int(x))) / 2)) if x else 0 for x in pool])      # C(P, 2) valid holdings -> P
-    return TurnSolution(tree, ranges, strategy, rstrat, value, br, status, valid, pool, trees, tree_of, node=node, reach=reach)
+    return TurnSolution(tree, ranges, strategy, rstrat, value, br, status, valid, pool, trees, tree_of, node=node, reach=reach, state=state)
 
 
 def solve_turn_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None, river_strategy_d=None, value_d=None, br_d=None, status_d=None,
                  device=0, stream=None, tree_of=None, lock=None, locked=None, river_lock=None, river_locked=None, reach=None, at=None, at_card=None,
-                 node_reach_d=None, node_value_d=None, node_br_d=None):
+                 node_reach_d=None, node_value_d=None, node_br_d=None, t0_d=None, regret_d=None, average_d=None, river_regret_d=None, river_average_d=None):
     """pk_solve_turn_d: the same on device-resident buffers (device pointers as ints / c_void_p; the tree stays a host TurnTree; dead_d and
     the outputs may be None), asynchronous on `stream`.  With a SEQUENCE of trees (pk_solve_turn_trees_d) tree_of is the DEVICE pointer of
     uint32 [m], as solve_river_d takes it; the strategies have the rows of the largest tree passed.  lock, locked, river_lock,
     river_locked (pk_solve_turn_locked_d): DEVICE pointers, as solve_river_d takes them.  reach, at, at_card and node_reach_d,
-    node_value_d, node_br_d (pk_solve_turn_resolve_d): DEVICE pointers, as solve_river_d takes them; ranges_d may then be None."""
+    node_value_d, node_br_d (pk_solve_turn_resolve_d): DEVICE pointers, as solve_river_d takes them; ranges_d may then be None.  t0_d,
+    regret_d, average_d, river_regret_d, river_average_d (pk_solve_turn_resume_d): DEVICE pointers, the state, worked in place."""
+    if any(x is not None for x in (t0_d, regret_d, average_d, river_regret_d, river_average_d)):
+        one = isinstance(tree, RiverTree)
+        if one == (tree_of is not None):
+            raise ValueError("tree_of, the device pointer of uint32 [m], comes with a sequence of trees and only with one")
+        L.check(L.lib().pk_solve_turn_resume_d(int(device), int(m), board_d, dead_d, ranges_d, *_TreeRows([tree] if one else tree, TURN_MAX_NODES).args(),
+                                               tree_of, int(iters), lock, locked, river_lock, river_locked, reach, at, at_card, t0_d, regret_d, average_d,
+                                               river_regret_d, river_average_d, strategy_d, river_strategy_d, value_d, br_d, node_reach_d, node_value_d,
+                                               node_br_d, status_d, stream))
+        return
     if any(x is not None for x in (reach, at, at_card, node_reach_d, node_value_d, node_br_d)):
         one = isinstance(tree, RiverTree)
         if one == (tree_of is not None):
@@ -840,7 +1053,7 @@ def solve_turn_d(m, board_d, ranges_d, tree, iters, dead_d=None, strategy_d=None
 
 
 def solve_turn(board, ranges, tree, iters, dead=(), river_strategy=False, device=0, lock=None, locked=None, river_lock=None, river_locked=None,
-               reach=None, at=None, at_card=None):
+               reach=None, at=None, at_card=None, state=None, keep_state=False):
     """One subgame.  board: the four board cards; ranges: [2, 1326] integers 0 .. 65535 over holding_index, player 0 (first to act on
     both streets) then player 1; dead: cards known to be out of play.  Raises ValueError for an invalid spot.  A reach starts at
     weight << 1 and every split rounds down: scale a range so that its largest weight uses the sixteen bits.  reach [2, 1326] (ranges may
@@ -852,9 +1065,109 @@ def solve_turn(board, ranges, tree, iters, dead=(), river_strategy=False, device
     d = np.array([dead if isinstance(dead, (int, np.integer)) else dead_mask(dead)], np.uint64)
     r = solve_turn_batch(b, _one_spot(ranges), tree, iters, d, river_strategy=river_strategy, device=device, lock=lock, locked=locked,
                          river_lock=river_lock, river_locked=river_locked, reach=_one_spot(reach), at=at,
-                         at_card=None if at_card is None else int(_card(at_card)))[0]
+                         at_card=None if at_card is None else int(_card(at_card)), state=state, keep_state=keep_state)[0]
+    if state is not None and r.status == L.EQ_BAD_ITER:
+        raise ValueError("the state's iterations and iters together exceed %d" % MAX_ITERS)
     if r.status:
         raise ValueError("invalid spot: " + equity_status_text(r.status))
+    return r
+
+
+def solve_turn_until_batch(board, ranges, tree, target, step=64, max_iters=MAX_ITERS, dead=None, river_strategy=False, device=0, tree_of=None, lock=None,
+                           locked=None, river_lock=None, river_locked=None, reach=None):
+    """solve_river_until_batch for the turn solver: solve_turn_batch's arguments, calls of `step` iterations with the state in DEVICE memory
+    (solver_state_bytes(tree, m) of it: 4.4 MB per river-level row, spot and array) until every solved spot's exploitability is at or
+    under `target` chips or max_iters iterations have run -> the last call's TurnSolution with .iters, .trace float64 [calls, m] and .state
+    on the host.  river_strategy=True: the river-level strategies too, from the last call."""
+    from . import hipmem
+    step, max_iters = int(step), int(max_iters)
+    if step < 1 or not 1 <= max_iters <= MAX_ITERS:
+        raise ValueError("step >= 1 and max_iters in 1 .. %d" % MAX_ITERS)
+    board = np.ascontiguousarray(board, np.uint8)
+    if board.ndim != 2 or board.shape[1] != 4:
+        raise ValueError("board must have shape [m, 4]")
+    m = board.shape[0]
+    ranges, reach = _resolve_ranges(ranges, reach, m, TURN_REACH_MAX)
+    if dead is not None:
+        dead = np.ascontiguousarray(dead, np.uint64)
+        if dead.shape != (m,):
+            raise ValueError("dead must have shape [m]")
+    one = isinstance(tree, RiverTree)
+    if one and tree_of is not None:
+        raise ValueError("tree_of needs a sequence of trees")
+    trees = [tree] if one else list(tree)
+    Dt, Dr = max(len(t.decision_nodes) for t in trees), max(len(t.river_decision_nodes) for t in trees)
+    tree_of = None if one else _tree_of(tree_of, len(trees), m)
+    if river_locked is None and river_lock is not None and isinstance(locked, TurnSolution):
+        river_locked = locked
+    lock, locked = _lock_pair(lock, locked, m, Dt, (4, L.EQ_HOLDINGS), ("lock", "locked"), "strategy")
+    river_lock, river_locked = _lock_pair(river_lock, river_locked, m, Dr, (52, 4, L.EQ_HOLDINGS), ("river_lock", "river_locked"), "river_strategy")
+    trows, rrows, pair = m * Dt * 4 * L.EQ_HOLDINGS, m * Dr * 52 * 4 * L.EQ_HOLDINGS, m * 2 * L.EQ_HOLDINGS
+    bufs = []
+
+    def dev(a=None, nbytes=0):
+        if a is None and not nbytes:
+            return None
+        b = hipmem.DeviceBuffer(a.nbytes if a is not None else max(nbytes, 8), device)
+        bufs.append(b)
+        return b.upload(a) if a is not None else b
+    ptr = lambda b: None if b is None else b.ptr
+    try:
+        ins = [dev(a) for a in (board, dead, ranges, tree_of, lock, locked, river_lock, river_locked, reach)]
+        t0 = np.zeros(m, np.uint32)
+        t0_d = dev(t0)
+        state_d = [dev(nbytes=max(trows, 1) * 8), dev(nbytes=max(trows, 1) * 8), dev(nbytes=max(rrows, 1) * 8), dev(nbytes=max(rrows, 1) * 8)]
+        strategy_d, rstrat_d = dev(nbytes=trows * 2), dev(nbytes=rrows * 2) if river_strategy else None
+        value_d, br_d, status_d = dev(nbytes=pair * 8), dev(nbytes=pair * 8), dev(nbytes=m)
+        board5 = np.concatenate([board, np.zeros((m, 1), np.uint8)], axis=1)
+        trace, done = [], 0
+        while True:
+            it = min(step, max_iters - done)
+            t0_d.upload(t0)
+            last = done + it >= max_iters
+            solve_turn_d(m, ptr(ins[0]), ptr(ins[2]), tree, it, dead_d=ptr(ins[1]), strategy_d=strategy_d.ptr, river_strategy_d=ptr(rstrat_d), value_d=value_d.ptr,
+                         br_d=br_d.ptr, status_d=status_d.ptr, device=device, tree_of=ptr(ins[3]), lock=ptr(ins[4]), locked=ptr(ins[5]), river_lock=ptr(ins[6]),
+                         river_locked=ptr(ins[7]), reach=ptr(ins[8]), t0_d=t0_d.ptr, regret_d=state_d[0].ptr, average_d=state_d[1].ptr,
+                         river_regret_d=state_d[2].ptr, river_average_d=state_d[3].ptr)
+            value, br = (b.download(np.int64, pair).reshape(m, 2, L.EQ_HOLDINGS) for b in (value_d, br_d))
+            status = status_d.download(np.uint8, m)
+            valid = rvr_valid_holdings(board5, np.full(m, 4, np.uint8), dead) & (status == 0)[:, None]
+            pool = np.array([int(round((1 + math.sqrt(1 + 8 * int(x))) / 2)) if x else 0 for x in np.where(status == 0, valid.sum(axis=1), 0)])
+            sol = TurnSolution(tree if one else None, ranges, None, None, value, br, status, valid, pool, None if one else trees, tree_of, reach=reach)
+            done += it
+            t0 += np.uint32(it)
+            trace.append([TurnSolution(None, _ith(ranges, i), None, None, value[i], br[i], status[i], valid[i], pool[i], reach=_ith(reach, i)).exploitability
+                          if status[i] == 0 else float("nan") for i in range(m)])
+            if last or all(not e > target for e in trace[-1]):
+                break
+        sol.strategy = strategy_d.download(np.uint16, trows).reshape(m, Dt, 4, L.EQ_HOLDINGS)
+        if river_strategy:
+            sol.river_strategy = rstrat_d.download(np.uint16, rrows).reshape(m, Dr, 52, 4, L.EQ_HOLDINGS)
+        regret, average = (b.download(np.int64, trows).reshape(m, Dt, 4, L.EQ_HOLDINGS) for b in state_d[:2])
+        rregret, raverage = (b.download(np.int64, rrows).reshape(m, Dr, 52, 4, L.EQ_HOLDINGS) for b in state_d[2:])
+        sol.state = SolverState(regret, average, np.where(status == 0, done, 0).astype(np.uint32), rregret, raverage)
+        sol.iters, sol.trace = done, np.array(trace, np.float64).reshape(len(trace), m)
+        return sol
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def solve_turn_until(board, ranges, tree, target, step=64, max_iters=MAX_ITERS, dead=(), river_strategy=False, device=0, lock=None, locked=None,
+                     river_lock=None, river_locked=None, reach=None):
+    """One subgame solved to a target: solve_turn's arguments, solve_turn_until_batch's rule -> its TurnSolution (.iters, .trace float64
+    [calls], .state).  Raises ValueError for an invalid spot."""
+    board = list(board)
+    if len(board) != 4:
+        raise ValueError("four board cards")
+    b = np.array([[_card(c) for c in board]], np.uint8)
+    d = np.array([dead if isinstance(dead, (int, np.integer)) else dead_mask(dead)], np.uint64)
+    full = solve_turn_until_batch(b, _one_spot(ranges), tree, target, step, max_iters, d, river_strategy=river_strategy, device=device, lock=lock, locked=locked,
+                                  river_lock=river_lock, river_locked=river_locked, reach=_one_spot(reach))
+    r = full[0]
+    if r.status:
+        raise ValueError("invalid spot: " + equity_status_text(r.status))
+    r.iters, r.trace = full.iters, full.trace[:, 0]
     return r
 
 

@@ -61,6 +61,8 @@ import hist_spec as HS                  # noqa: E402
 import preflop_spec as PS               # noqa: E402
 import river_solver_spec as RVS         # noqa: E402
 import resolve_spec as RZS              # noqa: E402
+import resume_spec as RMS               # noqa: E402
+import solver_resume_util as SMU        # noqa: E402
 import solver_lock_spec as SLS           # noqa: E402
 import solver_trees_util as STU         # noqa: E402
 import turn_solver_spec as TSS          # noqa: E402
@@ -83,7 +85,10 @@ OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("w
            "rivertrees": ("strategy", "value", "br", "status"), "turntrees": ("strategy", "river_strategy", "value", "br", "status"),
            "riverlock": ("strategy", "value", "br", "status"), "turnlock": ("strategy", "river_strategy", "value", "br", "status"),
            "riverresolve": ("strategy", "value", "br", "node_reach", "node_value", "node_br", "status"),
-           "turnresolve": ("strategy", "river_strategy", "value", "br", "node_reach", "node_value", "node_br", "status")}
+           "turnresolve": ("strategy", "river_strategy", "value", "br", "node_reach", "node_value", "node_br", "status"),
+           "riverresume": ("strategy", "value", "br", "node_reach", "node_value", "node_br", "status", "regret", "average"),
+           "turnresume": ("strategy", "river_strategy", "value", "br", "node_reach", "node_value", "node_br", "status", "regret", "average", "river_regret",
+                          "river_average")}
 
 
 class Case:
@@ -1579,6 +1584,119 @@ def turn_resolve_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- resuming
+def resume_case(name, street, pools, trees, tree_of, iters, seed, t0, at=None, at_card=None, patterns=None, beyond=(), edit=None, quick=True):
+    """k_rs_prep / k_ts_prep (+ k_trees_prep, k_resolve_prep) + k_resume_prep + k_resume_river_solve / k_resume_turn_solve at a grid of 1 against
+    tests/resume_spec.py.  t0: per spot.  Every state array is pre-filled with the sentinel; a spot with t0 > 0 holds random regrets and
+    accumulators at the entries the definition reads (the spots in `beyond`: values past both clamps, the extremes of int64 among them) and
+    the sentinel everywhere else, so that an entry that must not be read, or must survive, shows."""
+    m = len(pools)
+    family = "riverresume" if street == 5 else "turnresume"
+    board, _, dead = board_spots(seed, [(street, p) for p in pools])
+    board = np.ascontiguousarray(board[:, :street])
+    if edit:
+        edit(board, dead)
+    if tree_of is not None:
+        tree_of = np.asarray(tree_of, np.uint32)
+    tree_at = lambda i: trees[min(int(tree_of[i]) if tree_of is not None else 0, len(trees) - 1)]
+    ats = None
+    if at is not None:
+        ats = np.array([{"root": 0, "last": tree_at(i).n - 1}.get(a, a) for i, a in enumerate(at)], np.uint8)
+    cards = None
+    if at_card is not None:
+        cards = np.zeros(m, np.uint8)
+        for i, c in enumerate(at_card):
+            _, gone = VS.check_spot([int(x) for x in board[i]], street, int(dead[i]))
+            pool = [k for k in range(52) if k not in gone]
+            cards[i] = {"first": int(VS.CANON[pool[0]]), "last": int(VS.CANON[pool[-1]])}.get(c, c)
+    reach = resolve_reach(seed + 4, board, street, dead, RZS.RIVER_LIM if street == 5 else RZS.TURN_LIM)
+    has_given = street == 5 and any(RZS.GIVEN in [int(x) for x in t.kind] for t in trees)
+    given = resolve_given(seed + 5, trees, tree_of, m) if has_given else None
+    lock = locked = rlock = rlocked = None
+    if patterns is not None:
+        lock, locked = lock_arrays(seed + 2, trees, tree_of, patterns)
+        if street == 4:
+            rlock, rlocked = lock_arrays(seed + 3, trees, tree_of, patterns, river=True)
+    t0 = np.asarray(t0, np.uint32)
+    rng = np.random.default_rng(seed + 6)
+    if street == 5:
+        masks = [SMU.river_read_mask(board, dead, trees, tree_of, lock)] * 2
+        lims = (RMS.RIVER_RMAX, RMS.RIVER_AMAX)
+    else:
+        tm, rm = SMU.turn_read_masks(board, dead, trees, tree_of, lock, rlock)
+        masks, lims = [tm, tm, rm, rm], (RMS.TURN_RMAX, RMS.TURN_AMAX, RMS.TURN_RMAX, RMS.TURN_AMAX)
+    big = np.iinfo(np.int64)
+    state = []
+    for j, mask in enumerate(masks):
+        a = np.full(mask.shape, SMU.SENTINEL, np.int64)
+        lim = lims[j % 2]
+        for i in range(m):
+            if not t0[i]:
+                continue
+            if i in beyond:
+                vals = rng.choice(np.array([big.min, -1, 0, 4242, lim, lim + 1, big.max, lim // 2], np.int64), mask[i].shape)
+            else:
+                vals = rng.integers(0, 1 << (40 if j % 2 == 0 else 30), mask[i].shape).astype(np.int64)
+                vals[rng.random(mask[i].shape) < 0.3] = 0
+            a[i][mask[i]] = vals[mask[i]]
+        state.append(a)
+    names = RMS.STATE_KEYS if street == 5 else RMS.TURN_STATE_KEYS
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [1]), "iters": ("u32", [iters]), **tree_rows(trees, 64 if street == 5 else 128),
+              "tree_of": ("u32", tree_of), "board": ("u8", board), "dead": ("u64", dead), "reach": ("u32", reach),
+              "given": ("u64", None if given is None else given.view(np.uint64)), "at": ("u8", ats), "at_card": ("u8", cards),
+              "lock": ("u8", lock), "locked": ("u16", locked), "river_lock": ("u8", rlock), "river_locked": ("u16", rlocked), "t0": ("u32", t0),
+              **{k: ("u64", a.view(np.uint64)) for k, a in zip(names, state)}}
+    outputs = tuple(k for k in OUTPUTS[family] if ats is not None or not k.startswith("node_"))
+
+    def expect():
+        if street == 5:
+            r = RMS.solve_river_batch(board, None, trees, tree_of, iters, lock, locked, dead, reach, given, ats, t0, *state)
+        else:
+            r = RMS.solve_turn_batch(board, None, trees, tree_of, iters, lock, locked, rlock, rlocked, dead, reach, ats, cards, t0, *state)
+        return {k: (r[k].view(np.uint64) if r[k].dtype == np.int64 else r[k]) for k in OUTPUTS[family]}
+    return Case(name, family, arrays, expect, outputs, quick)
+
+
+def break_board_one(board, dead):
+    board[1, 1] = board[1, 0]
+
+
+def river_resume_cases():
+    """The river solver's resuming call (names rsum-...), every case at a grid of 1: ONE workgroup takes the spots in turn, so the state, the t0
+    or stale R / A of the spot before would show.  NOT part of all_cases()."""
+    from pokerl_amd.solver import river_tree
+    forced, four, chain = STU.forced_river_tree(), STU.four_action_river_tree(), STU.chain_river_tree()
+    small, default = river_tree(100, 50), river_tree(100, 400)
+    gsmall = gadget_of(small, 1)
+    cs = [resume_case("rsum-t0-after-zero-and-back", 5, (9, 7, 10, 6), [small, default], [0, 1, 0, 1], 2, 211, [0, 3, 0, 2], at=[1, "root", "last", 2]),
+          resume_case("rsum-zero-after-t0", 5, (8, 9), [four], None, 3, 212, [5, 0]),
+          resume_case("rsum-refused-bad-iter-dup-card-between", 5, (9, 8, 10, 7, 9, 8), [small, gsmall], [1, 0, 0, 2, 1, 0], 2, 213, [1, 3, 4095, 6, 0xFFFFFFFF, 4094],
+                      at=[0, 1, 0, 0, 2, 3], edit=break_board_one),
+          resume_case("rsum-locked-rows-keep-their-state", 5, (9, 7, 8), [small, four], [0, 1, 0], 2, 214, [2, 0, 0], patterns=["p1", "all", "p1"]),
+          resume_case("rsum-iters0", 5, (7, 9), [gsmall], None, 0, 215, [0, 5]),
+          resume_case("rsum-state-beyond-both-clamps", 5, (8, 10), [small], None, 3, 216, [7, 4000], beyond=(0, 1)),
+          resume_case("rsum-large-after-small", 5, (8, 7, 9, 6), [forced, chain], [0, 1, 0, 1], 1, 217, [1, 1, 0, 0]),
+          resume_case("rsum-pools-4-9-33", 5, (4, 9, 33), [small], [0, 0, 0], 2, 218, [1, 0, 2], at=[2, 3, "last"])]
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
+def turn_resume_cases():
+    """The turn solver's resuming call (names tsum-...), every case at a grid of 1.  NOT part of all_cases()."""
+    from pokerl_amd.solver import turn_tree
+    allin, small = STU.allin_turn_tree(), turn_tree(30, 20, (1.0,), 1)
+    cs = [resume_case("tsum-t0-after-zero-and-back", 4, (7, 6, 8), [allin], None, 2, 231, [0, 3, 0], at=[6, "root", "last"], at_card=["first", 0xFF, "last"]),
+          resume_case("tsum-zero-after-t0", 4, (6, 7), [small], None, 2, 232, [2, 0]),
+          resume_case("tsum-refused-bad-iter-dup-card-between", 4, (8, 7, 9, 6, 7), [allin], [0, 0, 0, 1, 0], 2, 233, [1, 3, 4095, 6, 4094], edit=break_board_one),
+          resume_case("tsum-locked-rows-keep-their-state", 4, (7, 6, 8), [allin], None, 2, 234, [2, 0, 3], patterns=["p1", "all", [1]]),
+          resume_case("tsum-iters0", 4, (7, 6), [allin], None, 0, 235, [0, 5]),
+          resume_case("tsum-state-beyond-both-clamps", 4, (7, 8), [allin], None, 3, 236, [7, 4000], beyond=(0, 1)),
+          resume_case("tsum-large-after-small", 4, (7, 6, 6), [allin, small], [0, 1, 0], 1, 237, [1, 1, 0]),
+          resume_case("tsum-pools-5-9-20", 4, (5, 9, 20), [allin], [0, 0, 0], 2, 238, [1, 0, 2], at=[6, "root", "last"], at_card=["first", 0xFF, "last"])]
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -1593,7 +1711,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() + river_trees_cases() + turn_trees_cases() + river_lock_cases() + turn_lock_cases() + river_resolve_cases() + turn_resolve_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() + river_trees_cases() + turn_trees_cases() + river_lock_cases() + turn_lock_cases() + river_resolve_cases() + turn_resolve_cases() + river_resume_cases() + turn_resume_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

@@ -9,7 +9,9 @@
 //   equity_sim <case file> <out file>
 // Case file: lines "name dtype count" (dtype u8 u16 u32 u64 i32) each followed by a line of `count` decimal values, and
 // "family <name>" / "outputs <name> ..." lines.  Out file: the same array format.
-// -DPK_ES_ONLY=1 .. 19: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist, preflop, rangedev, riversolve, turnsolve, rivertrees, turntrees, riverlock, turnlock, riverresolve, turnresolve), so that a test can compile them side by side.
+// -DPK_ES_ONLY=1 .. 21: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist, preflop, rangedev, riversolve, turnsolve, rivertrees, turntrees, riverlock, turnlock, riverresolve, turnresolve, riverresume, turnresume), so that a test can compile them side by side.
+// The riverresume / turnresume families (k_resume_prep, k_resume_river_solve / k_resume_turn_solve) take what riverresolve / turnresolve take and the state arrays,
+// which go in and come out: allocations of exactly their size, holding what the case put there.
 // The riverresolve / turnresolve families (k_resolve_prep, k_resolve_river_solve / k_resolve_turn_solve) take what riverlock / turnlock take (ranges optional) and
 // the optional reach, given (river), at and at_card (turn) arrays, each in an allocation of exactly its size; the node outputs node_reach (u32), node_value, node_br (i64 as u64).
 // The riverlock / turnlock families (k_lock_river_solve / k_lock_turn_solve) take the trees as rivertrees / turntrees do, an optional tree_of (none: every
@@ -73,10 +75,10 @@
 #if PK_ES_HAS(10)
 #include "../../pokerl_amd/csrc/pk_preflop.hip"
 #endif
-#if PK_ES_HAS(12) || PK_ES_HAS(14) || PK_ES_HAS(13) || PK_ES_HAS(15) || PK_ES_HAS(16) || PK_ES_HAS(17) || PK_ES_HAS(18) || PK_ES_HAS(19)
+#if PK_ES_HAS(12) || PK_ES_HAS(14) || PK_ES_HAS(13) || PK_ES_HAS(15) || PK_ES_HAS(16) || PK_ES_HAS(17) || PK_ES_HAS(18) || PK_ES_HAS(19) || PK_ES_HAS(20) || PK_ES_HAS(21)
 #include "../../pokerl_amd/csrc/pk_river_solver.hip"     // (the turn solver's tree-per-spot launch queues k_trees_prep)
 #endif
-#if PK_ES_HAS(13) || PK_ES_HAS(15) || PK_ES_HAS(17) || PK_ES_HAS(19)
+#if PK_ES_HAS(13) || PK_ES_HAS(15) || PK_ES_HAS(17) || PK_ES_HAS(19) || PK_ES_HAS(21)
 #include "../../pokerl_amd/csrc/pk_turn_solver.hip"
 #endif
 #include <chrono>
@@ -160,6 +162,16 @@ struct Case {
     template <typename T> T *output(const char *name, const char *dt, size_t n) {
         if (std::find(outputs.begin(), outputs.end(), name) == outputs.end()) return nullptr;
         out.emplace_back(name, std::make_unique<Buf>(dt, n, 0xA5));
+        return (T *)out.back().second->p;
+    }
+    // an array that goes in AND comes out (a solver's state): the case's own values, an allocation of exactly its size, written with the outputs
+    template <typename T> T *inout(const char *name, size_t n) {
+        auto it = in.find(name);
+        if (it == in.end()) return nullptr;
+        if (it->second->width != sizeof(T) || it->second->count != n) die(std::string(name) + ": not the size the kernel works in");
+        if (std::find(outputs.begin(), outputs.end(), name) == outputs.end()) die(std::string(name) + " goes in and must come out: name it among the outputs");
+        out.emplace_back(name, std::move(it->second));
+        in.erase(it);
         return (T *)out.back().second->p;
     }
     void write(const char *path) const {
@@ -611,7 +623,7 @@ void run_preflop_rvr(Case &c) {
 }
 #endif
 
-#if PK_ES_HAS(12) || PK_ES_HAS(14) || PK_ES_HAS(16) || PK_ES_HAS(18)
+#if PK_ES_HAS(12) || PK_ES_HAS(14) || PK_ES_HAS(16) || PK_ES_HAS(18) || PK_ES_HAS(20)
 // nact and row as the host check derives them -> the number of decision nodes
 size_t pack_river_tree(RsTree &t, uint32_t n, uint32_t pot, const uint8_t *kind, const uint8_t *child, const uint32_t *put) {
     t = RsTree{};
@@ -626,7 +638,7 @@ size_t pack_river_tree(RsTree &t, uint32_t n, uint32_t pot, const uint8_t *kind,
 }
 #endif
 
-#if PK_ES_HAS(13) || PK_ES_HAS(15) || PK_ES_HAS(17) || PK_ES_HAS(19)
+#if PK_ES_HAS(13) || PK_ES_HAS(15) || PK_ES_HAS(17) || PK_ES_HAS(19) || PK_ES_HAS(21)
 // nact, row, river and idx as the host check derives them; D[0] / D[1]: turn-level / river-level decision nodes
 void pack_turn_tree(TsTree &t, uint32_t n, uint32_t pot, const uint8_t *kind, const uint8_t *child, const uint32_t *put, size_t (&D)[2]) {
     t = TsTree{};
@@ -910,6 +922,123 @@ void run_turn_resolve(Case &c, const uint32_t *tab) {
 }
 #endif
 
+#if PK_ES_HAS(20)
+// The riverresume family (k_resume_prep, k_resume_river_solve): what riverresolve takes, and t0 u32 [m] (optional), regret / average
+// u64 [m][Dmax][4][1326], which go in and come out.  The solve kernel always runs: the state is an output.
+void run_river_resume(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const uint32_t ntrees = (uint32_t)c.num("ntrees"), iters = (uint32_t)c.num("iters");
+    if (ntrees < 1 || grid < 1) die("riverresume: no tree, or no workgroup");
+    const uint32_t *n = c.need<uint32_t>("n", ntrees), *pot = c.need<uint32_t>("pot", ntrees), *tree_of = c.arr<uint32_t>("tree_of", m);
+    if (!tree_of && ntrees != 1) die("riverresume: no tree_of with more than one tree");
+    const uint8_t *kind = c.need<uint8_t>("kind", (size_t)ntrees * RS_MAX_NODES), *child = c.need<uint8_t>("child", (size_t)ntrees * RS_MAX_NODES * 4);
+    const uint32_t *put = c.need<uint32_t>("put", (size_t)ntrees * RS_MAX_NODES * 2);
+    Work<RsTree> trees(ntrees);
+    uint32_t nmax = 0;
+    size_t Dmax = 0;
+    bool given_node = false;
+    for (uint32_t k = 0; k < ntrees; ++k) {
+        if (n[k] < 1 || n[k] > (uint32_t)RS_MAX_NODES) die("riverresume: n outside 1 .. 64");
+        const size_t row = (size_t)k * RS_MAX_NODES;
+        Dmax = std::max(Dmax, pack_river_tree(trees.p[k], n[k], pot[k], kind + row, child + row * 4, put + row * 2));
+        nmax = std::max(nmax, n[k]);
+        for (uint32_t v = 0; v < n[k]; ++v) given_node = given_node || kind[row + v] == RS_GIVEN;
+    }
+    const RsSpots spots{c.need<uint8_t>("board", m * 5), c.arr<uint64_t>("dead", m), c.arr<uint16_t>("ranges", m * 2 * RS_HOLDINGS)};
+    const RsLock lk{c.arr<uint8_t>("lock", m * Dmax), c.arr<uint16_t>("locked", m * Dmax * 4 * RS_HOLDINGS)};
+    if (lk.lock && !lk.locked) die("riverresume: lock without locked");
+    RsResolve rz{c.arr<uint32_t>("reach", m * 2 * RS_HOLDINGS), (const int64_t *)c.arr<uint64_t>("given", m * 2 * RS_HOLDINGS), c.arr<uint8_t>("at", m), nullptr, nullptr, nullptr};
+    if (!spots.ranges && !rz.reach) die("riverresume: neither ranges nor reach");
+    if (given_node && !rz.given) die("riverresume: a given node without given");
+    const RsResume rm{c.arr<uint32_t>("t0", m), (int64_t *)c.inout<uint64_t>("regret", m * Dmax * 4 * RS_HOLDINGS), (int64_t *)c.inout<uint64_t>("average", m * Dmax * 4 * RS_HOLDINGS)};
+    if (!rm.regret || !rm.average) die("riverresume: the case has no state");
+    RsOut out{};
+    out.strategy = c.output<uint16_t>("strategy", "u16", m * Dmax * 4 * RS_HOLDINGS);
+    out.value = (int64_t *)c.output<uint64_t>("value", "u64", m * 2 * RS_HOLDINGS);
+    out.br = (int64_t *)c.output<uint64_t>("br", "u64", m * 2 * RS_HOLDINGS);
+    rz.node_reach = c.output<uint32_t>("node_reach", "u32", m * 2 * RS_HOLDINGS);
+    rz.node_value = (int64_t *)c.output<uint64_t>("node_value", "u64", m * 2 * RS_HOLDINGS);
+    rz.node_br = (int64_t *)c.output<uint64_t>("node_br", "u64", m * 2 * RS_HOLDINGS);
+    out.status = c.output<uint8_t>("status", "u8", m);
+    if ((rz.at != nullptr) != (rz.node_reach || rz.node_value || rz.node_br)) die("riverresume: at comes with a node output, and only with one");
+    Work<uint64_t> desc(m * RS_DESC_WORDS);
+    Work<char> ws((size_t)grid * rs_group_bytes(nmax));
+    const RsPrepArgs a{spots, out.status, desc.p, m};
+    pk_sim::launch(prep_grid(m, RS_PREP_BLOCK), RS_PREP_BLOCK, [&] { k_rs_prep(a); });
+    uint64_t *dw = desc.p;
+    uint8_t *st = out.status;
+    if (tree_of) pk_sim::launch(prep_grid(m, RS_PREP_BLOCK), RS_PREP_BLOCK, [&] { k_trees_prep(tree_of, ntrees, dw, st, m); });
+    const ResolvePrepArgs ra{(const char *)trees.p, (uint32_t)sizeof(RsTree), 0u, tree_of, rz.at, nullptr, dw, st, m};
+    if (rz.at) pk_sim::launch(prep_grid(m, RS_PREP_BLOCK), RS_PREP_BLOCK, [&] { k_resolve_prep(ra); });
+    const uint32_t *t0 = rm.t0;
+    if (t0) pk_sim::launch(prep_grid(m, RS_PREP_BLOCK), RS_PREP_BLOCK, [&] { k_resume_prep(t0, iters, dw, st, m); });
+    const uint64_t *dp = desc.p;
+    char *wp = ws.p;
+    const RsTrees tt{trees.p, tree_of, nmax, (uint32_t)Dmax};
+    pk_sim::launch(grid, RS_BLOCK, [&] { k_resume_river_solve(tab, dp, tt, lk, rz, rm, spots, out, wp, iters, (uint32_t)m); });
+}
+#endif
+
+#if PK_ES_HAS(21)
+// The turnresume family (k_resume_prep, k_resume_turn_solve): what turnresolve takes, and t0, regret / average u64 [m][Dtmax][4][1326], river_regret /
+// river_average u64 [m][Drmax][52][4][1326], which go in and come out.
+void run_turn_resume(Case &c, const uint32_t *tab) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const uint32_t ntrees = (uint32_t)c.num("ntrees"), iters = (uint32_t)c.num("iters");
+    if (ntrees < 1 || grid < 1) die("turnresume: no tree, or no workgroup");
+    const uint32_t *n = c.need<uint32_t>("n", ntrees), *pot = c.need<uint32_t>("pot", ntrees), *tree_of = c.arr<uint32_t>("tree_of", m);
+    if (!tree_of && ntrees != 1) die("turnresume: no tree_of with more than one tree");
+    const uint8_t *kind = c.need<uint8_t>("kind", (size_t)ntrees * TS_MAX_NODES), *child = c.need<uint8_t>("child", (size_t)ntrees * TS_MAX_NODES * 4);
+    const uint32_t *put = c.need<uint32_t>("put", (size_t)ntrees * TS_MAX_NODES * 2);
+    Work<TsTree> trees(ntrees);
+    TsTrees tt{trees.p, tree_of, 0, 0, 0, 0};
+    for (uint32_t k = 0; k < ntrees; ++k) {
+        if (n[k] < 1 || n[k] > (uint32_t)TS_MAX_NODES) die("turnresume: n outside 1 .. 128");
+        const size_t row = (size_t)k * TS_MAX_NODES;
+        size_t D[2];
+        pack_turn_tree(trees.p[k], n[k], pot[k], kind + row, child + row * 4, put + row * 2, D);
+        tt.ntmax = std::max(tt.ntmax, trees.p[k].nt); tt.nrmax = std::max(tt.nrmax, trees.p[k].nr);
+        tt.Dtmax = std::max(tt.Dtmax, (uint32_t)D[0]); tt.Drmax = std::max(tt.Drmax, (uint32_t)D[1]);
+    }
+    const TsSpots spots{c.need<uint8_t>("board", m * 4), c.arr<uint64_t>("dead", m), c.arr<uint16_t>("ranges", m * 2 * RS_HOLDINGS)};
+    const TsLock lk{c.arr<uint8_t>("lock", m * tt.Dtmax), c.arr<uint16_t>("locked", m * tt.Dtmax * 4 * RS_HOLDINGS), c.arr<uint8_t>("river_lock", m * tt.Drmax),
+                    c.arr<uint16_t>("river_locked", m * tt.Drmax * 52 * 4 * RS_HOLDINGS)};
+    if ((lk.lock && !lk.locked) || (lk.river_lock && !lk.river_locked)) die("turnresume: a lock array without its locked array");
+    TsResolve rz{c.arr<uint32_t>("reach", m * 2 * RS_HOLDINGS), c.arr<uint8_t>("at", m), c.arr<uint8_t>("at_card", m), nullptr, nullptr, nullptr};
+    if (!spots.ranges && !rz.reach) die("turnresume: neither ranges nor reach");
+    const size_t trows = m * tt.Dtmax * 4 * RS_HOLDINGS, rrows = m * tt.Drmax * 52 * 4 * RS_HOLDINGS;
+    const TsResume rm{c.arr<uint32_t>("t0", m), (int64_t *)c.inout<uint64_t>("regret", trows), (int64_t *)c.inout<uint64_t>("average", trows),
+                      (int64_t *)c.inout<uint64_t>("river_regret", rrows), (int64_t *)c.inout<uint64_t>("river_average", rrows)};
+    if (!rm.regret || !rm.average || !rm.river_regret || !rm.river_average) die("turnresume: the case has no state");
+    TsOut out{};
+    out.strategy = c.output<uint16_t>("strategy", "u16", trows);
+    out.river_strategy = c.output<uint16_t>("river_strategy", "u16", rrows);
+    out.value = (int64_t *)c.output<uint64_t>("value", "u64", m * 2 * RS_HOLDINGS);
+    out.br = (int64_t *)c.output<uint64_t>("br", "u64", m * 2 * RS_HOLDINGS);
+    rz.node_reach = c.output<uint32_t>("node_reach", "u32", m * 2 * RS_HOLDINGS);
+    rz.node_value = (int64_t *)c.output<uint64_t>("node_value", "u64", m * 2 * RS_HOLDINGS);
+    rz.node_br = (int64_t *)c.output<uint64_t>("node_br", "u64", m * 2 * RS_HOLDINGS);
+    out.status = c.output<uint8_t>("status", "u8", m);
+    if ((rz.at != nullptr) != (rz.node_reach || rz.node_value || rz.node_br)) die("turnresume: at comes with a node output, and only with one");
+    Work<uint64_t> desc(m * RS_DESC_WORDS);
+    Work<char> ws((size_t)grid * ts_group_bytes(tt.ntmax, tt.nrmax));
+    const TsPrepArgs a{spots, out.status, desc.p, m};
+    pk_sim::launch(prep_grid(m, TS_PREP_BLOCK), TS_PREP_BLOCK, [&] { k_ts_prep(a); });
+    uint64_t *dw = desc.p;
+    uint8_t *st = out.status;
+    if (tree_of) pk_sim::launch(prep_grid(m, RS_PREP_BLOCK), RS_PREP_BLOCK, [&] { k_trees_prep(tree_of, ntrees, dw, st, m); });
+    const ResolvePrepArgs ra{(const char *)trees.p, (uint32_t)sizeof(TsTree), (uint32_t)offsetof(TsTree, river), tree_of, rz.at, rz.at_card, dw, st, m};
+    if (rz.at) pk_sim::launch(prep_grid(m, RS_PREP_BLOCK), RS_PREP_BLOCK, [&] { k_resolve_prep(ra); });
+    const uint32_t *t0 = rm.t0;
+    if (t0) pk_sim::launch(prep_grid(m, RS_PREP_BLOCK), RS_PREP_BLOCK, [&] { k_resume_prep(t0, iters, dw, st, m); });
+    const uint64_t *dp = desc.p;
+    char *wp = ws.p;
+    pk_sim::launch(grid, RS_BLOCK, [&] { k_resume_turn_solve(tab, dp, tt, lk, rz, rm, spots, out, wp, iters, (uint32_t)m); });
+}
+#endif
+
 #if PK_ES_HAS(12)
 void run_river(Case &c, const uint32_t *tab) {
     const size_t m = (size_t)c.num("m");
@@ -1057,6 +1186,12 @@ int main(int argc, char **argv) {
 #endif
 #if PK_ES_HAS(19)
     if (c.family == "turnresolve") { run_turn_resolve(c, tab.p); ran = true; }
+#endif
+#if PK_ES_HAS(20)
+    if (c.family == "riverresume") { run_river_resume(c, tab.p); ran = true; }
+#endif
+#if PK_ES_HAS(21)
+    if (c.family == "turnresume") { run_turn_resume(c, tab.p); ran = true; }
 #endif
     if (!ran) die("family " + c.family + ": not in this build");
     c.write(argv[2]);

@@ -28,6 +28,9 @@ does, and merges its legs into profiles/solver_resolve_bench.json under "turn": 
 with nothing locked; the root reaches from `reach` and the node outputs at a river-level node under one river card.
 
     python tools/turn_solver_bench.py --resolve none --m 256
+--resume {none,fresh,chain} measures the resuming entry (pk_solve_turn_resume_d) as tools/river_solver_bench.py --resume
+does, and merges its legs into profiles/solver_resume_bench.json under "turn"; the state is 53 MB a spot on this tree.
+    python tools/turn_solver_bench.py --resume chain --m 256
 """
 import argparse
 import ctypes as C
@@ -199,6 +202,52 @@ def resolve_legs(args, stream, res):
             x.free()
 
 
+def resume_legs(args, stream, res):
+    """--resume (the module's docstring)"""
+    rng = np.random.default_rng(0)
+    board, river, ranges = subgames(rng, max(args.m))
+    tree = solver.turn_tree(100, 400, (1.0,), 1)
+    Dt, Dr = len(tree.decision_nodes), len(tree.river_decision_nodes)
+    rows = solver._TreeRows([tree], solver.TURN_MAX_NODES)
+    q = args.iters // 4
+    for m in args.m:
+        b, r = np.ascontiguousarray(board[:m]), np.ascontiguousarray(ranges[:m])
+        ins = [DeviceBuffer(x.nbytes).upload(x) for x in (b, r)]
+        t0s = [DeviceBuffer(m * 4).upload(np.full(m, k * q, np.uint32)) for k in range(4)]
+        strategy, value, br, status = DeviceBuffer(m * Dt * 4 * H * 2), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m * 2 * H * 8), DeviceBuffer(m)
+        state = [DeviceBuffer(m * Dt * 4 * H * 8), DeviceBuffer(m * Dt * 4 * H * 8), DeviceBuffer(m * Dr * 52 * 4 * H * 8), DeviceBuffer(m * Dr * 52 * 4 * H * 8)]
+
+        def resolve_entry():
+            L.check(L.lib().pk_solve_turn_resolve_d(0, m, ins[0].ptr, None, ins[1].ptr, *rows.args(), None, args.iters, None, None, None, None, None, None, None,
+                                                    strategy.ptr, None, value.ptr, br.ptr, None, None, None, status.ptr, stream))
+
+        def resume_entry(iters=args.iters, t0=None, with_state=True):
+            L.check(L.lib().pk_solve_turn_resume_d(0, m, ins[0].ptr, None, ins[1].ptr, *rows.args(), None, iters, None, None, None, None, None, None, None, t0,
+                                                   *[x.ptr if with_state else None for x in state], strategy.ptr, None, value.ptr, br.ptr, None, None, None,
+                                                   status.ptr, stream))
+
+        def chain():
+            for k in range(4):
+                resume_entry(q, t0s[k].ptr)
+        runs = {"none": (("resolve_call", resolve_entry), ("resume_call", lambda: resume_entry(with_state=False))),
+                "fresh": (("resolve_call", resolve_entry), ("resume_call", resume_entry)),
+                "chain": (("one_call", resume_entry), ("four_calls", chain))}[args.resume]
+        leg = {}
+        for name, run in runs:
+            us, each, wall, odd = time_stream(run, stream, args.samples, warmup=1)
+            assert not status.download(np.uint8, m).any()
+            v, bb = value.download(np.int64, m * 2 * H), br.download(np.int64, m * 2 * H)
+            assert (bb >= v).all() and v.any()
+            leg[name] = dict(ms=round(us * 1e-3, 3), samples_ms=[round(x * 1e-3, 3) for x in each], host_clock_ms=round(wall * 1e-3, 3), event_anomalies=odd,
+                             solves_per_s=round(m / (us * 1e-6), 1), value_sum=int(v.sum()))
+        a, b2 = [n for n, _ in runs]
+        assert leg[a]["value_sum"] == leg[b2]["value_sum"] and q * 4 == args.iters                        # the same solve either way
+        leg["ratio_%s_to_%s" % (b2, a)] = round(leg[b2]["ms"] / leg[a]["ms"], 4)
+        res["resume_%s_m_%d" % (args.resume, m)] = dict(iters=args.iters, grid=solver.turn_grid([tree], m), state_bytes=solver.solver_state_bytes(tree, m), **leg)
+        for x in ins + t0s + state + [strategy, value, br, status]:
+            x.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=3)
@@ -207,14 +256,26 @@ def main():
     ap.add_argument("--trees", type=int, default=0, help="K: measure the tree-per-spot entry with K trees (1: the indirection alone)")
     ap.add_argument("--lock", choices=("none", "one", "all"), default=None, help="measure the locked entry: nothing, player 1 or every row locked")
     ap.add_argument("--resolve", choices=("none", "at"), default=None, help="measure the re-solving entry: nothing new, or node outputs at a river-level node")
+    ap.add_argument("--resume", choices=("none", "fresh", "chain"), default=None, help="measure the resuming entry: no state, state from nothing, a solve in four calls")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "solver_resolve_bench.json" if args.resolve else "solver_lock_bench.json" if args.lock else "solver_trees_bench.json" if args.trees else "turn_solver_bench.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "solver_resume_bench.json" if args.resume else "solver_resolve_bench.json" if args.resolve else "solver_lock_bench.json" if args.lock else "solver_trees_bench.json" if args.trees else "turn_solver_bench.json")
     if pokerl_amd.device_count() < 1:
         sys.exit("turn_solver_bench: no MI355X visible (no fallback)")
     hip = hipmem._lib()
     stream = C.c_void_p()
     assert hip.hipStreamCreateWithFlags(C.byref(stream), 1) == 0
+    if args.resume:
+        from river_solver_bench import merge_into
+        ks = kernel_meta.kernels(L.LIB_PATH)
+        res = dict(tool="turn_solver_bench --resume", src=L.source_hash(), samples=args.samples)
+        for name in ("k_resolve_turn_solve", "k_resume_turn_solve"):
+            res[name] = dict(vgprs=ks[name]["vgprs"], sgprs=ks[name]["sgprs"], lds=ks[name]["lds"], scratch=ks[name]["private_segment"])
+        resume_legs(args, stream, res)
+        hip.hipStreamDestroy(stream)
+        merge_into(args.out, "turn", res)
+        print(json.dumps(res))
+        return
     if args.resolve:
         from river_solver_bench import merge_into
         ks = kernel_meta.kernels(L.LIB_PATH)

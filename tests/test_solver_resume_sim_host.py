@@ -5,7 +5,10 @@ before every workgroup, PK_IDX on every LDS and work-space subscript, every arra
 size).  No GPU.  Every case runs at a grid of 1, so that ONE workgroup takes the spots in turn and the state, the t0 or stale regrets of
 the spot before would show.  Every state array is pre-filled with a sentinel, which must come back wherever the definition says the entry
 is not written.  Every output and the whole state are compared byte for byte with tests/resume_spec.py: nothing expected comes from a
-kernel.  The same cases under ASan + UBSan and TSan: tools/host_sim/sanitize_equity.sh --only sum-."""
+kernel.  The same cases under ASan + UBSan and TSan: tools/host_sim/sanitize_equity.sh --only sum-.
+The ARITHMETIC cases (river_arith_cases / turn_arith_cases, case functions of their own because a state at the clamps holds no sentinel): the
+operand tables of tests/solver_rule_cases.py through the rule and the bounds corner, so that what tests/test_hip_solver_arithmetic.py
+gives the device is never compared with the device only; under UBSan (--only arith-) a signed overflow in the kernel bodies stops the run."""
 import os
 import shutil
 import subprocess
@@ -23,6 +26,8 @@ import solver_resume_util as MU  # noqa: E402
 
 RIVER = [c for c in EC.river_resume_cases() if c.quick]
 TURN = [c for c in EC.turn_resume_cases() if c.quick]
+RIVER_ARITH = [c for c in EC.river_arith_cases() if c.quick]
+TURN_ARITH = [c for c in EC.turn_arith_cases() if c.quick]
 
 
 def build(tmp_path_factory, only, tag):
@@ -96,3 +101,36 @@ def test_turn_kernel_as_512_lane_workgroups_vs_spec(turn_sim, case):
     print("%s: %.2f s in the driver" % (case.name, sec))
     assert not bad, (bad, log[-3000:])
     assert "equity_sim: turnresume done" in log and "LDS bytes" in log
+
+
+def test_the_arithmetic_cases_carry_the_tables_and_the_corner():
+    import solver_rule_cases as RC
+    names = {c.name for c in EC.river_arith_cases() + EC.turn_arith_cases()}
+    assert not names & {c.name for c in EC.all_cases() + EC.river_resume_cases() + EC.turn_resume_cases()} and len(RIVER_ARITH) == 6 and len(TURN_ARITH) >= 2
+    assert "tarith-corner-p48-fixture" in names and all(int(field(c, "grid")[0]) == 1 for c in RIVER_ARITH + TURN_ARITH)
+    by = {c.name: c for c in RIVER_ARITH}
+    avg = field(by["rarith-rule-average"], "average").view(np.int64).reshape(-1, 14, 4, 1326)
+    placed = {tuple(int(v) for v in avg[i, row, :n, h]) for i in range(len(avg)) for row, n in ((0, 1),) for h in range(1326)}
+    assert int(field(by["rarith-rule-average"], "iters")[0]) == 0 and (avg == np.iinfo(np.int64).min).any() and (avg == np.iinfo(np.int64).max).any()
+    assert len(placed) > 1 and (RC.lim_of("river_A"),) in placed
+    top = by["rarith-corner-top"]
+    assert (field(top, "regret").view(np.int64) == RC.lim_of("river_R")).all() and field(top, "t0").tolist() == [4093] and int(field(top, "iters")[0]) == 3
+    assert (field(top, "ranges") == 65535).all() and field(top, "pot").tolist() == [1001] and int(field(top, "put").max()) == 7190
+
+
+@pytest.mark.parametrize("case", RIVER_ARITH, ids=[c.name for c in RIVER_ARITH])
+def test_river_arithmetic_as_512_lane_workgroups_vs_spec_and_exact_rule(river_sim, case):
+    exe, work = river_sim
+    bad, sec, log = EC.run_case(exe, case, work, timeout=300)
+    print("%s: %.2f s in the driver" % (case.name, sec))
+    assert not bad, (bad, log[-3000:])
+    assert "equity_sim: riverresume done" in log
+
+
+@pytest.mark.parametrize("case", TURN_ARITH, ids=[c.name for c in TURN_ARITH])
+def test_turn_arithmetic_as_512_lane_workgroups_vs_spec_and_exact_rule(turn_sim, case):
+    exe, work = turn_sim
+    bad, sec, log = EC.run_case(exe, case, work, timeout=600)
+    print("%s: %.2f s in the driver" % (case.name, sec))
+    assert not bad, (bad, log[-3000:])
+    assert "equity_sim: turnresume done" in log

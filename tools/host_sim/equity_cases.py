@@ -36,6 +36,7 @@ The shapes are the smallest at which each mechanism of the kernels can break (do
   equity_cases.py --exe <equity_sim> [--exe <another build>] [--quick] [--only <substring>] [--list] [--keep <dir>]
 """
 import argparse
+import hashlib
 import math
 import os
 import subprocess
@@ -144,8 +145,12 @@ def run_case(exe, case, workdir, timeout=1800):
     for key in case.outputs:
         if key not in got:
             continue
-        w = np.asarray(want[key]).reshape(-1)
         g = got[key]
+        if isinstance(want[key], str):                                # a fixture that holds the array's SHA-256 only
+            if hashlib.sha256(np.ascontiguousarray(g).tobytes()).hexdigest() != want[key]:
+                bad.append("%s: the SHA-256 of the %d entries is not the fixture's" % (key, g.size))
+            continue
+        w = np.asarray(want[key]).reshape(-1)
         if g.size != w.size:
             bad.append("%s: %d entries, the spec has %d" % (key, g.size, w.size))
             continue
@@ -1697,6 +1702,65 @@ def turn_resume_cases():
     return cs
 
 
+# ---------------------------------------------------------------------------------------------------------------- the solvers' arithmetic
+def arith_case(name, street, call, quick=True, fixture=None):
+    """A call of tests/solver_rule_cases.py (rule_call: the operand tables through the rule; corner_call: the bounds corner) on the resuming
+    kernels at a grid of 1, against tests/resume_spec.py -- and, for the tables, against rule_exact in Python integers, which the spec's
+    result must meet before it is the expected value.  The state arrays hold the tables, the sentinel where nothing is read (rule_call) or the
+    clamps everywhere (corner_call): not every case holds the sentinel, which is why these are not among river_resume_cases().
+    fixture: an .npz of tests/golden/solver_arith (the spec's result at a pool where it takes minutes; digests for the large arrays)."""
+    import solver_rule_cases as SRC      # here, not at the top: every other family's cases load without it
+    family = "riverresume" if street == 5 else "turnresume"
+    names = RMS.STATE_KEYS if street == 5 else RMS.TURN_STATE_KEYS
+    m = len(call["board"])
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [1]), "iters": ("u32", [call["iters"]]), **tree_rows(call["trees"], 64 if street == 5 else 128),
+              "tree_of": ("u32", call["tree_of"]), "board": ("u8", call["board"]), "dead": ("u64", call["dead"]), "ranges": ("u16", call["ranges"]),
+              "t0": ("u32", call["t0"]), **{k: ("u64", a.view(np.uint64)) for k, a in zip(names, call["state"])}}
+    outputs = tuple(k for k in OUTPUTS[family] if not k.startswith("node_"))
+
+    def expect():
+        if fixture is not None:
+            fx = np.load(os.path.join(ROOT, "tests", "golden", "solver_arith", fixture))
+            assert fx["board"].tolist() == call["board"][0].tolist() and int(fx["t0"]) == int(call["t0"][0]) and int(fx["iters"]) == call["iters"]
+            out = {k: (fx[k][None].view(np.uint64) if fx[k].dtype == np.int64 else fx[k][None]) for k in ("strategy", "value", "br", "status")}
+            out.update({k: str(fx["sha256_" + k]) for k in ("river_strategy",) + names})
+            return out
+        r = SRC.spec_of(street, call)
+        assert not r["status"].any() and ("where" not in call or SRC.rule_wanted(call, r) == [])
+        return {k: (r[k].view(np.uint64) if r[k].dtype == np.int64 else r[k]) for k in outputs}
+    return Case(name, family, arrays, expect, outputs, quick)
+
+
+def river_arith_cases():
+    """The river solver's arithmetic (names rarith-...; family riverresume, grid 1): the A tables through `average` (iters = 0), the R tables
+    through `regret` (iters = 1, root reach ONE) at t0 = 1 and 4095, and the bounds corner at the full pool from three states at the clamps.
+    NOT part of all_cases()."""
+    import solver_rule_cases as SRC
+    from pokerl_amd.solver import river_tree
+    forced, four, nine, default = STU.forced_river_tree(), STU.four_action_river_tree(), SRC.nine_node_tree(), river_tree(100, 400)
+    cs = [arith_case("rarith-rule-average", 5, SRC.rule_call(5, [forced, default, four], "average", 7, 47)),
+          arith_case("rarith-rule-regret-t1", 5, SRC.rule_call(5, [forced, nine, default, four], "regret", 1, 47)),
+          arith_case("rarith-rule-regret-t4095", 5, SRC.rule_call(5, [forced, nine, default, four], "regret", 4095, 47))]
+    cs += [arith_case("rarith-corner-" + v, 5, SRC.corner_call(5, 47, v)) for v in ("top", "swing", "mix")]
+    return cs
+
+
+def turn_arith_cases():
+    """The turn solver's arithmetic (names tarith-...; family turnresume, grid 1): the tables at both levels at P = 9, the bounds corner at
+    P = 12 and, from tests/golden/solver_arith/turn_corner_p48.npz, at the full pool (not quick).  The tables are cut to two (A) and three (R) spots
+    a tree (the root row has 36 holdings at this pool and a workgroup takes ten seconds a spot here; the river cases carry them whole).
+    NOT part of all_cases()."""
+    import solver_rule_cases as SRC
+    from pokerl_amd.solver import turn_tree
+    four, small = SRC.four_action_turn_tree(), turn_tree(30, 20, (1.0,), 1)
+    return [arith_case("tarith-rule-average", 4, SRC.rule_call(4, [four], "average", 9, 9, spots=2)),
+            arith_case("tarith-rule-regret-t4095", 4, SRC.rule_call(4, [small], "regret", 4095, 9, spots=3), quick=False),
+            arith_case("tarith-rule-regret-four-t1", 4, SRC.rule_call(4, [four], "regret", 1, 9, spots=3), quick=False),
+            arith_case("tarith-corner-top-p12", 4, SRC.corner_call(4, 12, "top")),
+            arith_case("tarith-corner-swing-p12", 4, SRC.corner_call(4, 12, "swing"), quick=False),
+            arith_case("tarith-corner-p48-fixture", 4, SRC.corner_call(4, 48, "top"), quick=False, fixture="turn_corner_p48.npz")]
+
+
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
     assert len({c.name for c in cs}) == len(cs)
@@ -1711,7 +1775,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() + river_trees_cases() + turn_trees_cases() + river_lock_cases() + turn_lock_cases() + river_resolve_cases() + turn_resolve_cases() + river_resume_cases() + turn_resume_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() + river_trees_cases() + turn_trees_cases() + river_lock_cases() + turn_lock_cases() + river_resolve_cases() + turn_resolve_cases() + river_resume_cases() + turn_resume_cases() + river_arith_cases() + turn_arith_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

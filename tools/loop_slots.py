@@ -71,7 +71,7 @@ def main_loop(body):
         raise SystemExit("no loop found")
     h, end, _ = best
     # blocks of the loop laid out in FRONT of its header (the path round end_block): labels that name this header
-    name = label.match(lines[h]).group(1)[1:]
+    name = label.match(lines[h]).group(1)[2:]       # ".LBB16_13" -> "BB16_13", as the block comments spell it
     start = h
     for j in range(h - 1, -1, -1):
         m = label.match(lines[j])

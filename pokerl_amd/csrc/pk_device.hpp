@@ -154,6 +154,7 @@ template <int N, typename F>
 __device__ __forceinline__ void unroll(F &&f) { unroll_impl(f, std::make_integer_sequence<int, N>{}); }
 #define PK_FOR(p, N) pk::unroll<N>([&](auto p##_c) { constexpr int p = decltype(p##_c)::value;
 #define PK_END });
+enum : int { PK_MONEY_AND = 0, PK_MONEY_SEAT = 1, PK_MONEY_BLOCK = 2 };   // Table::begin_step<MONEY>
 template <int N>
 __device__ __forceinline__ double sel(const double (&a)[N], int i) {
     double r = a[0];
@@ -196,6 +197,16 @@ __device__ __forceinline__ uint32_t rep4(uint32_t x) {
     return (x & 0xffu) * 0x01010101u;
 #else
     return __builtin_amdgcn_perm(x, x, 0u);
+#endif
+}
+// bits [off, off + width) of x, off and width taken modulo 32 (one v_bfe_u32); width in 1 .. 31 here.  The CPU builds restate the builtin by
+// hand, so tools/host_sim checks the algebra of the callers, not the instruction's modulo-32 operands: those are pinned on the device, by the
+// parity tests against the reference restatement (tests/test_hip_betting_pass_forms.py: odd and even serials, serials with a carry in the low word, every seat walk).
+__device__ __forceinline__ uint32_t ubfe(uint32_t x, uint32_t off, uint32_t width) {
+#ifdef PK_HOST_SIM
+    return (x >> (off & 31u)) & ((1u << (width & 31u)) - 1u);
+#else
+    return __builtin_amdgcn_ubfe(x, off, width);
 #endif
 }
 // A pointer that was LOADED from memory (the array bases behind `const State *Sp`) is a flat pointer to the compiler: every
@@ -884,8 +895,8 @@ struct ActionRing {
         const uint32_t s = step_serial;                                                          //  bit 0 tested with a 64-bit compare)
         return lds.act[((s >> 3) & 1) * 4 + ((s & 7) >> 1)][threadIdx.x & (PK_WAVE - 1)];
     }
-    __device__ __forceinline__ static uint32_t half_of(uint32_t word, uint32_t step_serial) {
-        return (step_serial & 1) ? (word >> 16) : (word & 0xffffu);
+    __device__ __forceinline__ static uint32_t half_of(uint32_t word, uint32_t step_serial) {   // odd serial: the high half
+        return ubfe(word, step_serial << 4, 16);    // (the extract takes its offset modulo 32: 0 or 16; a shift and a v_bfe_u32 for and / cmp / shift / and / select)
     }
 };
 // The same through the workgroup's LDS table (k_rollout): one byte read instead of a six-step select chain.
@@ -1048,15 +1059,24 @@ struct Table {
         st_active |= (st == PS_ACTIVE) ? b : 0; st_called |= (st == PS_CALLED) ? b : 0;
         st_allin |= (st == PS_ALL_IN) ? b : 0; st_broken |= (st == PS_BROKEN) ? b : 0;
     }
-    __device__ __forceinline__ static uint32_t rotr(uint32_t m, int a) {  // bit k of result = bit (a+k)%N of m
-        return ((m >> a) | (m << (N - a))) & FULL;
+    // Cyclic seat arithmetic on the mask TWICE over, m | m << N (N <= 16): bits a .. a + N - 1 of it are m rotated right by a, so a
+    // rotation is one shift and a window of it is one bit-field extract (the pair of opposite shifts, their OR and the two ANDs cost five).
+    __device__ __forceinline__ static uint32_t twice(uint32_t m) { return m | (m << N); }
+    __device__ __forceinline__ static uint32_t rotr(uint32_t m, int a) {  // bit k of result = bit (a+k)%N of m; a in [0, N)
+        return ubfe(twice(m), (uint32_t)a, N);
     }
+    // rotr(m, a) cut down to its low d + 1 bits -- the seats a, a + 1, ... a + d (cyclic; d in [0, N)): the width d + 1 <= N keeps the
+    // window inside the rotation, so there is no & FULL.
+    __device__ __forceinline__ static uint32_t window_of(uint32_t m, int a, int d) { return ubfe(twice(m), (uint32_t)a, (uint32_t)d + 1u); }
+    // The two cyclic corrections as an unsigned minimum (an addition and a v_min_u32 each, no compare and select):
+    // wrap: x in [0, 2N) -> x mod N; unwrap: d in (-N, N) -> d mod N.  (wrap(-1), where a walk found no seat, is a value every caller discards.)
+    __device__ __forceinline__ static int wrap(int x) { const uint32_t u = (uint32_t)x, v = u - (uint32_t)N; return (int)(u < v ? u : v); }
+    __device__ __forceinline__ static int unwrap(int d) { const uint32_t u = (uint32_t)d, v = u + (uint32_t)N; return (int)(u < v ? u : v); }
     // Game.get_first_playing, game.py:334-337 (idx in [0, N]; all-BROKEN -> idx % N)
     __device__ __forceinline__ int first_playing(int idx) const {
-        int i = idx >= N ? idx - N : idx;
+        int i = wrap(idx);
         uint32_t nb = ~st_broken & FULL;
-        int r = i + (__ffs(rotr(nb, i)) - 1);
-        r = r >= N ? r - N : r;
+        int r = wrap(i + (__ffs(rotr(nb, i)) - 1));
         return nb ? r : i;
     }
     __device__ __forceinline__ bool game_over() const { return __popc(~st_broken & FULL) == 1; }  // game.py:317-320
@@ -1218,9 +1238,12 @@ struct Table {
 
     // Game.step up to the call of next_player (game.py:656-699) for an action already checked against the mask.
     // Branch-free: every lane of the wave takes a different action, so the three arms are merged into selects.
-    // MONEY_IN_SEAT: `pending[a] = bet` compares the seats with a seat index that is -1 where no money moves -- one select in place of a lane-mask
-    // AND per seat.  For rollout_body's kernels (k_rollout_tab<6> +0.6 %); the PokerGameEnv kernels keep the ANDs (synchronous env.step -1.7 % with it).
-    template <bool MONEY_IN_SEAT = false>
+    // `pending[a] = bet` happens only where money moves.  MONEY = PK_MONEY_AND: a lane-mask AND per seat (the PokerGameEnv and Game.step kernels:
+    // synchronous env.step -1.7 % without them).  PK_MONEY_SEAT: the seats are compared with a seat index that is -1 where no money moves -- one
+    // select in place of the ANDs, six compares of its own (rollout_body's kernels, k_rollout_tab<6> +0.6 % when it came).  PK_MONEY_BLOCK: a block
+    // under the exec mask on the lanes where money moves, whose selects take the `p == a` compares that sel(credits, a) has made (twelve slots less
+    // than PK_MONEY_SEAT at six seats; rollout_body's table-evaluator kernels only: with it k_rollout_occ3<7> spills a register to scratch).
+    template <int MONEY = PK_MONEY_AND>
     __device__ __forceinline__ void begin_step(const Hot &S, int action, double high_bet) {
         const int a = active;
         const uint32_t b = 1u << a;
@@ -1239,8 +1262,11 @@ struct Table {
         st_active &= ~b; st_called &= ~b; st_allin &= ~b; st_broken &= ~b;         // player_states[a] = ...
         st_allin |= (action == MV_ALL_IN) ? b : 0;                                 // :671
         st_called |= (action != MV_FOLD && action != MV_ALL_IN) ? b : 0;           // :660, :667 (FOLD: in no mask, :657)
-        const int a_m = (!MONEY_IN_SEAT || money) ? a : -1;
-        PK_FOR(p, N) pending[p] = ((MONEY_IN_SEAT || money) && p == a_m) ? bet_value : pending[p]; PK_END  // :696
+        if constexpr (MONEY == PK_MONEY_BLOCK) { if (money) { PK_FOR(p, N) pending[p] = (p == a) ? bet_value : pending[p]; PK_END } }   // :696
+        else {
+            const int a_m = (MONEY == PK_MONEY_AND || money) ? a : -1;
+            PK_FOR(p, N) pending[p] = ((MONEY == PK_MONEY_SEAT || money) && p == a_m) ? bet_value : pending[p]; PK_END
+        }
         // next_player's entry (game.py:598-605,616-619)
         const bool many = __popc((st_active | st_called | st_allin) & FULL) > 1;
         current = a;
@@ -1251,9 +1277,9 @@ struct Table {
 
     // The `while states[active] != ACTIVE` walk of next_player (game.py:607-611) for one lane, O(1) with seat bitmasks.
     __device__ __forceinline__ bool scan() {
-        int d = current - active; d = d < 0 ? d + N : d;                           // seats active..current (cyclic)
-        uint32_t window = rotr(st_active, active) & ((2u << d) - 1);
-        int a = active + (__ffs(window) - 1); a = a >= N ? a - N : a;
+        int d = unwrap(current - active);                                          // seats active..current (cyclic)
+        uint32_t window = window_of(st_active, active, d);
+        int a = wrap(active + (__ffs(window) - 1));
         active = window ? a : current;                                             // else: walked up to current_player
         return window != 0;
     }
@@ -1272,9 +1298,9 @@ struct Table {
     // The same in two halves for k_rollout's betting pass: scan_first() is branch-free (nearly every step ends there);
     // cursor_tail() is the divergent rest for the lanes whose walk failed.  cursor_tail() ONLY after scan_first().
     __device__ __forceinline__ void scan_first() {
-        int d = current - active; d = d < 0 ? d + N : d;
-        uint32_t window = rotr(st_active, active) & ((2u << d) - 1);
-        int a = active + (__ffs(window) - 1); a = a >= N ? a - N : a;
+        int d = unwrap(current - active);
+        uint32_t window = window_of(st_active, active, d);
+        int a = wrap(active + (__ffs(window) - 1));
         const bool hit = lstate == LS_SCAN && window != 0;
         active = hit ? a : active;
         lstate = hit ? (int)LS_DONE : lstate;
@@ -1292,9 +1318,9 @@ struct Table {
         const bool merge = more && __popc(st_called) > 1;
         st_active |= merge ? st_called : 0u; st_called = merge ? 0u : st_called;
         const int first = first_playing(dealer + 1);
-        int d = current - first; d = d < 0 ? d + N : d;                            // scan() from `first`
-        const uint32_t window = rotr(st_active, first) & ((2u << d) - 1);
-        int a = first + (__ffs(window) - 1); a = a >= N ? a - N : a;
+        int d = unwrap(current - first);                                           // scan() from `first`
+        const uint32_t window = window_of(st_active, first, d);
+        int a = wrap(first + (__ffs(window) - 1));
         const bool found = more && window != 0;
         active = more ? (window ? a : current) : active;
         flags = more ? (uint32_t)PK_FLAG_TURN_OVER : flags;

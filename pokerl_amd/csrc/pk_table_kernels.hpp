@@ -249,7 +249,7 @@ __device__ __forceinline__ void rollout_body(const State *__restrict__ Sp, const
                 else if constexpr (policy == PK_POLICY_ALLIN) act = (int)MV_ALL_IN;
                 else if constexpr (policy == PK_POLICY_CALL) act = call_action(mask);
                 else act = action_from_draw_lds(lds, ActionRing::half_of(word, (uint32_t)tb.step_serial), mask);
-                tb.template begin_step<true>(H, act, high_bet);
+                tb.template begin_step<TAB ? PK_MONEY_BLOCK : PK_MONEY_SEAT>(H, act, high_bet);
             }
             PK_PROF(tb.prof.lap(PF_ACTION);)
             tb.scan_first();      // every lane in LS_SCAN: the steps just begun and the ones end_block carried into a new hand

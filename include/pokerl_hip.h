@@ -1312,6 +1312,42 @@ int pk_solve_turn_resume(int device, size_t m, const uint8_t *board, const uint6
                          int64_t *average /*in and out*/, int64_t *river_regret /*in and out*/, int64_t *river_average /*in and out*/,
                          uint16_t *strategy, uint16_t *river_strategy, int64_t *value, int64_t *br, uint32_t *node_reach, int64_t *node_value,
                          int64_t *node_br, uint8_t *status);
+
+/* ---- Pre-flop solver: heads-up CFR+ over a betting tree with NO board, a showdown paid by the exact matchup table (DESIGN.md section 3.18;
+ * the numpy restatement: tests/preflop_solver_spec.py).  Everything of "River solver" holds except what is said here.  PK_ABI_VERSION is
+ * unchanged: symbols are added only.
+ * SPOTS: a spot has no board and no dead mask: two ranges, u16 [2][1326], and a tree.  Every holding is valid, P = 52.  Player 0 acts
+ * first, as the small blind does heads-up.  Root reach r_p[root][h] = w_p[h] << 4, as on the river.
+ * TREES: the river solver's packed trees with kinds 0 .. 4 only.  Kind 5 (the turn solver's chance node) and kind 6 (a re-solving call's
+ * given node) are refused, each with a text of its own; the rest of the river solver's host check applies unchanged (pot + max put <= 8191,
+ * iters 1 .. 4096), before any device is looked at.  The root's put may be non-zero: the blinds are put[root] = (sb, bb), antes are pot.
+ * A TREE PER SPOT: ntrees, the per-tree arrays and tree_of are taken as the calls of "a tree per spot" take them (at most PK_RS_MAX_TREES
+ * trees, rows of 64 nodes, strategy strided by Dmax = pk_rs_trees_rows).  tree_of NULL: every spot uses tree 0.  tree_of[i] >= ntrees:
+ * PK_EQ_BAD_TREE in status[i], all-zero outputs, no neighbour disturbed.  No other status exists.
+ * FOLD TERMINALS: as the river solver's, with S_q(h) = the sum of r_q[n][h'] over the h' that share no card with h.
+ * SHOWDOWN TERMINAL, the only new arithmetic.  B = PK_PREFLOP_BOARDS = 1 712 304, c = put[0] = put[1], win and tie the resident matchup table
+ * ("Pre-flop matchups"; a pair that shares a card holds 0 in both, so card removal is in the table):
+ *     E_q(h) = sum over h' of r_q[n][h'] (2 win[h][h'] + tie[h][h'])
+ *     u_p[h] = floor((pot + 2c) E_q(h) / B) - 2c S_q(h), the floor of the exact product.
+ * On the full table win + tie + lose = B for a disjoint pair, so this is the river solver's 2 (pot + c) W + pot T - 2c L with W, T, L the
+ * reach times the share of boards won, tied and lost, floored once; the units are half-chips x opponent reach.  A showdown is paid as if
+ * the hand were checked down to the river, whatever the puts: THERE IS NO POST-FLOP BETTING in this game.
+ * BOUNDS: E < 2^52 (the 1 225 holdings disjoint from h, a reach < 2^20 each, times 2 B: below 2^51.97).  The product (pot + 2c) E can reach 2^66, so it is formed as
+ * (pot + 2c) (E div B) + ((pot + 2c) (E mod B)) div B -- the same integer, every intermediate below 2^46.  |u| <= 2 (pot + c) S < 2^45, hence
+ * |sum sigma u| < 2^60, |R| < 2^58 and A < 2^44 as on the river (measured at the corner: tests/preflop_solver_witness.py).  No sum depends
+ * on its order: the output is bit-identical to the restatement whatever the grid.
+ * OUTPUTS as the river solver's: strategy u16 [m][Dmax][4][1326], value and br i64 [m][2][1326], status u8 [m]; each optional except status.
+ * The matchup table is built on the first call that needs it, as the other pre-flop entry points build it; the work space is sized by the
+ * resident workgroups (59 136 bytes per node of the call's largest tree and workgroup), never by m.
+ * NOT HERE: locks, re-solving (reach, at, given), resuming, a table form, more than two players, dead cards, post-flop play below a call. */
+int pk_solve_preflop_d(int device, size_t m, const uint16_t *ranges_d /*[m][2][1326]*/, uint32_t ntrees, const uint32_t *n /*[ntrees], host*/,
+                       const uint8_t *kind /*[ntrees][64], host*/, const uint8_t *child /*[ntrees][64][4], host*/,
+                       const uint32_t *put /*[ntrees][64][2], host*/, const uint32_t *pot /*[ntrees], host*/,
+                       const uint32_t *tree_of_d /*[m], DEVICE; NULL: tree 0*/, uint32_t iters, uint16_t *strategy_d /*[m][Dmax][4][1326]*/,
+                       int64_t *value_d /*[m][2][1326]*/, int64_t *br_d, uint8_t *status_d, void *stream);
+int pk_solve_preflop(int device, size_t m, const uint16_t *ranges, uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child,
+                     const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of /*[m], host; NULL: tree 0*/, uint32_t iters,
+                     uint16_t *strategy, int64_t *value, int64_t *br, uint8_t *status);
 /* Streams are recycled through a per-device pool when handles are destroyed (a process that opens and closes handles keeps its hardware
  * queues); the sub-batch streams of pk_set_env_batches are created at the HIGHEST stream priority (env PK_ENV_STREAM_PRIO=0: normal), so a
  * learner's normal-priority kernels on the same GPU yield to the env ranges while those run.  pk_stream_pool_drain destroys the pooled (idle)

@@ -21,6 +21,8 @@ from .solver import (RiverSolution, RiverTree, TurnSolution, TurnTree, river_tre
                      solve_turn, solve_turn_batch, solve_turn_d, turn_grid, turn_tree, turn_trees, evaluate_river, evaluate_river_batch,
                      evaluate_turn, evaluate_turn_batch, gadget_tree, resolve_river, KIND_GIVEN,
                      SolverState, solver_state_bytes, solve_river_until, solve_river_until_batch, solve_turn_until, solve_turn_until_batch)
+from .solver import (PreflopSolution, holding_class, preflop_tree, preflop_trees, push_fold_tree, solve_preflop, solve_preflop_batch,
+                     solve_preflop_d)
 from .sharding import gather_f64, shard_tables
 from .single import Game, PokerGameEnv
 from .state_view import Card, StateView, packed_dtype, unpack_obs
@@ -47,4 +49,5 @@ __all__ = ['Game', 'PokerGameEnv', 'VecGame', 'VecPokerGameEnv', 'VecPokerGameEn
            'RiverTree', 'RiverSolution', 'river_tree', 'solve_river', 'solve_river_batch', 'solve_river_d',
            'TurnTree', 'TurnSolution', 'turn_tree', 'turn_grid', 'solve_turn', 'solve_turn_batch', 'solve_turn_d', 'river_trees', 'turn_trees',
            'evaluate_river', 'evaluate_river_batch', 'evaluate_turn', 'evaluate_turn_batch', 'gadget_tree', 'resolve_river', 'KIND_GIVEN',
-           'SolverState', 'solver_state_bytes', 'solve_river_until', 'solve_river_until_batch', 'solve_turn_until', 'solve_turn_until_batch']
+           'SolverState', 'solver_state_bytes', 'solve_river_until', 'solve_river_until_batch', 'solve_turn_until', 'solve_turn_until_batch',
+           'PreflopSolution', 'holding_class', 'push_fold_tree', 'preflop_tree', 'preflop_trees', 'solve_preflop', 'solve_preflop_batch', 'solve_preflop_d']

@@ -64,7 +64,8 @@ SYMBOLS = ["pk_abi_version", "pk_device_count", "pk_last_error", "pk_create", "p
            "pk_solve_river_trees_d", "pk_solve_river_trees", "pk_solve_turn_trees_d", "pk_solve_turn_trees", "pk_rs_trees_rows", "pk_ts_trees_rows",
            "pk_solve_river_locked_d", "pk_solve_river_locked", "pk_solve_turn_locked_d", "pk_solve_turn_locked",
            "pk_solve_river_resolve_d", "pk_solve_river_resolve", "pk_solve_turn_resolve_d", "pk_solve_turn_resolve",
-           "pk_solve_river_resume_d", "pk_solve_river_resume", "pk_solve_turn_resume_d", "pk_solve_turn_resume"]
+           "pk_solve_river_resume_d", "pk_solve_river_resume", "pk_solve_turn_resume_d", "pk_solve_turn_resume",
+           "pk_solve_preflop_d", "pk_solve_preflop"]
 
 
 class PokerlHipError(RuntimeError):
@@ -236,6 +237,8 @@ def lib():
     L.pk_solve_turn_resume_d.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 21
     L.pk_solve_turn_resume.argtypes = [C.c_int, C.c_size_t] + [_vp] * 3 + [C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 20
     L.pk_rs_trees_rows.argtypes = [C.c_uint32] + [_vp] * 3
+    L.pk_solve_preflop_d.argtypes = [C.c_int, C.c_size_t, _vp, C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 5
+    L.pk_solve_preflop.argtypes = [C.c_int, C.c_size_t, _vp, C.c_uint32] + [_vp] * 6 + [C.c_uint32] + [_vp] * 4
     L.pk_ts_trees_rows.argtypes = [C.c_uint32] + [_vp] * 5
     for name in SYMBOLS:
         if name not in ("pk_last_error", "pk_build_info", "pk_snapshot_bytes"):

@@ -8,7 +8,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpokerl_hip.so")
 HEADERS = [os.path.join(CSRC, "pk_device.hpp"), os.path.join(CSRC, "pk_table_kernels.hpp"), os.path.join(CSRC, "pk_util_kernels.hpp"), os.path.join(CSRC, "pk_snapshot.hpp"), os.path.join(CSRC, "pk_equity.hpp"),
            os.path.join(CSRC, "pk_equity_common.hpp"), os.path.join(CSRC, "pk_equity_sampled.hpp"), os.path.join(CSRC, "pk_equity_range.hpp"), os.path.join(CSRC, "pk_equity_rvr.hpp"),
-           os.path.join(CSRC, "pk_equity_hist.hpp"), os.path.join(CSRC, "pk_equity_hist_hero.hpp"), os.path.join(CSRC, "pk_equity_ranged.hpp"), os.path.join(CSRC, "pk_equity_ev.hpp"), os.path.join(CSRC, "pk_ev_ranged.hpp"), os.path.join(CSRC, "pk_hist_cluster.hpp"), os.path.join(CSRC, "pk_preflop.hpp"), os.path.join(CSRC, "pk_river_solver.hpp"), os.path.join(CSRC, "pk_solver_common.hpp"), os.path.join(CSRC, "pk_turn_solver.hpp"),
+           os.path.join(CSRC, "pk_equity_hist.hpp"), os.path.join(CSRC, "pk_equity_hist_hero.hpp"), os.path.join(CSRC, "pk_equity_ranged.hpp"), os.path.join(CSRC, "pk_equity_ev.hpp"), os.path.join(CSRC, "pk_ev_ranged.hpp"), os.path.join(CSRC, "pk_hist_cluster.hpp"), os.path.join(CSRC, "pk_preflop.hpp"), os.path.join(CSRC, "pk_preflop_solver.hpp"), os.path.join(CSRC, "pk_river_solver.hpp"), os.path.join(CSRC, "pk_solver_common.hpp"), os.path.join(CSRC, "pk_turn_solver.hpp"),
            os.path.join(os.path.dirname(HERE), "include", "pokerl_hip.h")]
 # -ffp-contract=off: numpy never fuses multiply-add, so neither may we (bit-exact f64 money).
 # -amdgpu-sched-strategy=max-ilp: the table kernels run ONE wave per SIMD (65 536 tables = 1 024 waves), where issue is bound
@@ -22,7 +22,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-ffp-contract=off", "-fn
 SEATS = list(range(2, 17))   # one object per seat count (pk_tables.hip -DPK_SEATS=N), PK_MIN_PLAYERS .. PK_MAX_PLAYERS
 OBJ = os.path.join(HERE, "_obj")
 EQW_CLASSES = (16, 8, 0)     # pk_equity_ranged.hip -DPK_EQW_CLASS: pk::eqw_class
-SOURCES = ["pk_api.hip", "pk_tables.hip", "pk_snapshot.hip", "pk_equity.hip", "pk_equity_sampled.hip", "pk_equity_range.hip", "pk_equity_rvr.hip", "pk_equity_hist.hip", "pk_equity_hist_hero.hip", "pk_equity_ranged.hip", "pk_equity_ev.hip", "pk_ev_ranged.hip", "pk_hist_cluster.hip", "pk_preflop.hip", "pk_river_solver.hip", "pk_turn_solver.hip"]
+SOURCES = ["pk_api.hip", "pk_tables.hip", "pk_snapshot.hip", "pk_equity.hip", "pk_equity_sampled.hip", "pk_equity_range.hip", "pk_equity_rvr.hip", "pk_equity_hist.hip", "pk_equity_hist_hero.hip", "pk_equity_ranged.hip", "pk_equity_ev.hip", "pk_ev_ranged.hip", "pk_hist_cluster.hip", "pk_preflop.hip", "pk_preflop_solver.hip", "pk_river_solver.hip", "pk_turn_solver.hip"]
 COMPILE_FLAGS = [f for f in FLAGS if f != "-shared"]
 # -enable-post-misched=0 (no post-register-allocation scheduler pass) for the table kernels of the seat counts where it was MEASURED
 #   to pay: six seats (k_rollout<6> +0.6 ... 0.9 %, the all-in kernel +2.5 %) and four (+1.5 %); at every other seat count the default
@@ -111,6 +111,7 @@ def build_variant(out, defines=(), seats=None, tag="", verbose=False, jobs=None)
             ("pk_equity_ev.hip", os.path.join(OBJ, "pk_equity_ev%s.o" % tag), defines, verbose),
             ("pk_hist_cluster.hip", os.path.join(OBJ, "pk_hist_cluster%s.o" % tag), defines, verbose),
             ("pk_preflop.hip", os.path.join(OBJ, "pk_preflop%s.o" % tag), defines, verbose),
+            ("pk_preflop_solver.hip", os.path.join(OBJ, "pk_preflop_solver%s.o" % tag), defines, verbose),
             ("pk_river_solver.hip", os.path.join(OBJ, "pk_river_solver%s.o" % tag), defines, verbose),
             ("pk_turn_solver.hip", os.path.join(OBJ, "pk_turn_solver%s.o" % tag), defines, verbose)]
     # the ranged sampling kernels: one object per LDS size class (0, 8 or 16 cumulative rows beside the evaluator table), 15 seat counts each

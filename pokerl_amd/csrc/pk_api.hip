@@ -29,6 +29,7 @@
 #include "pk_equity_hist_hero.hpp"
 #include "pk_hist_cluster.hpp"
 #include "pk_preflop.hpp"
+#include "pk_preflop_solver.hpp"
 #include "pk_snapshot.hpp"
 
 using namespace pk;
@@ -3617,6 +3618,63 @@ int pk_solve_turn_resume(int device, size_t m, const uint8_t *board, const uint6
                                 TsResolve{g.at<uint32_t>(re), g.at<uint8_t>(an), g.at<uint8_t>(ac), g.at<uint32_t>(nr), g.at<int64_t>(nv), g.at<int64_t>(nb)},
                                 TsResume{g.at<uint32_t>(tz), g.at<int64_t>(rg), g.at<int64_t>(av), g.at<int64_t>(rrg), g.at<int64_t>(rav)}, iters, m,
                                 TsOut{g.at<uint16_t>(sg), g.at<uint16_t>(rs), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
+    });
+}
+
+// ---- the pre-flop solver (pokerl_hip.h "Pre-flop solver"; kernel: pk_preflop_solver.hip).  The trees are the river
+// solver's, checked and packed with its check after the two kinds that mean something elsewhere have been refused by name; they go to the
+// device as the tree-per-spot calls send them.  tree_of may be NULL (every spot: tree 0).  The table is the resident matchup table.
+static const char *ps_pack_trees(size_t m, bool pointers, uint32_t iters, uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child,
+                                 const uint32_t *put, const uint32_t *pot, RsPacked &p) {
+    if (const char *why = eq_bad_m(m)) return why;
+    if ((m && !pointers) || !n || !kind || !child || !put || !pot) return ": NULL where a pointer is required (ranges, n, kind, child, put, pot, status)";
+    if (iters < 1u || iters > (uint32_t)RS_MAX_ITERS) return ": iters outside 1 .. 4096";
+    if (ntrees < 1u || ntrees > RS_MAX_TREES) return ": ntrees outside 1 .. 65536";
+    p.trees.resize(ntrees);
+    for (uint32_t k = 0; k < ntrees; ++k) {
+        const size_t row = (size_t)k * RS_MAX_NODES;
+        for (uint32_t v = 0; v < n[k] && v < (uint32_t)RS_MAX_NODES; ++v) {
+            if (kind[row + v] == TS_CHANCE) return trees_refusal(p.why, k, ": a chance node (kind 5): a pre-flop tree has no later street, a call is a showdown");
+            if (kind[row + v] == RS_GIVEN) return trees_refusal(p.why, k, ": a given node (kind 6): the pre-flop solver does not re-solve");
+        }
+        if (const char *why = rs_check_tree(n[k], kind + row, child + row * 4, put + row * 2, pot[k], p.trees[k])) return trees_refusal(p.why, k, why);
+        uint32_t D = 0;
+        for (uint32_t v = 0; v < n[k]; ++v) D += p.trees[k].kind[v] <= RS_P1;
+        p.nmax = n[k] > p.nmax ? n[k] : p.nmax;
+        p.Dmax = D > p.Dmax ? D : p.Dmax;
+    }
+    return nullptr;
+}
+
+int pk_solve_preflop_d(int device, size_t m, const uint16_t *ranges_d, uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child,
+                       const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of_d, uint32_t iters, uint16_t *strategy_d, int64_t *value_d, int64_t *br_d,
+                       uint8_t *status_d, void *stream) {
+    const char *call = "pk_solve_preflop_d";
+    RsPacked p;
+    EQ_REFUSE(g_fail, call, ps_pack_trees(m, ranges_d && status_d, iters, ntrees, n, kind, child, put, pot, p));
+    const bool solve = strategy_d || value_d || br_d;
+    const size_t ws = (ps_work_bytes(m, p.nmax, solve) + 255) & ~(size_t)255;
+    return eq_call_d(call, device, stream, m, solve ? EQ_TAB_PREFLOP : EQ_TAB_NONE, ws + rs_trees_bytes(ntrees), [&](hipStream_t st, const uint32_t *M, char *work) {
+        RsTree *trees_d = (RsTree *)(work + ws);
+        if (const hipError_t e = hipMemcpyAsync(trees_d, p.trees.data(), (size_t)ntrees * sizeof(RsTree), hipMemcpyHostToDevice, st)) return e;
+        return ps_launch(st, M, ranges_d, RsTrees{trees_d, tree_of_d, p.nmax, p.Dmax}, ntrees, iters, m, RsOut{strategy_d, value_d, br_d, status_d}, work);
+    });
+}
+
+int pk_solve_preflop(int device, size_t m, const uint16_t *ranges, uint32_t ntrees, const uint32_t *n, const uint8_t *kind, const uint8_t *child,
+                     const uint32_t *put, const uint32_t *pot, const uint32_t *tree_of, uint32_t iters, uint16_t *strategy, int64_t *value, int64_t *br,
+                     uint8_t *status) {
+    const char *call = "pk_solve_preflop";
+    RsPacked p;
+    EQ_REFUSE(g_fail, call, ps_pack_trees(m, ranges && status, iters, ntrees, n, kind, child, put, pot, p));
+    const bool solve = strategy || value || br;
+    Stage g;
+    const int ra = g.in(ranges, m * 2 * RS_HOLDINGS * 2), to = g.in(tree_of, m * 4), tr = g.in(p.trees.data(), (size_t)ntrees * sizeof(RsTree));
+    const int sg = g.out(strategy, m * p.Dmax * 4 * RS_HOLDINGS * 2), va = g.out(value, m * 2 * RS_HOLDINGS * 8), be = g.out(br, m * 2 * RS_HOLDINGS * 8);
+    const int su = g.out(status, m);
+    return eq_call_host(call, device, m, solve ? EQ_TAB_PREFLOP : EQ_TAB_NONE, g, ps_work_bytes(m, p.nmax, solve), [&](hipStream_t st, const uint32_t *M, char *work) {
+        return ps_launch(st, M, g.at<uint16_t>(ra), RsTrees{g.at<RsTree>(tr), g.at<uint32_t>(to), p.nmax, p.Dmax}, ntrees, iters, m,
+                         RsOut{g.at<uint16_t>(sg), g.at<int64_t>(va), g.at<int64_t>(be), g.at<uint8_t>(su)}, work);
     });
 }
 

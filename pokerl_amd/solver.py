@@ -16,7 +16,9 @@ subtree / river_subtree re-root a tree, gadget_tree puts the re-solving gadget o
 Resuming (pk_solve_river_resume / pk_solve_turn_resume; "Resuming a solve"): every solve function takes state (a
 SolverState: the regrets, the average accumulators and the iterations they hold) and keep_state; the solution then carries .state, which the
 next call continues from.  solve_river_until / solve_turn_until and their _batch forms run such calls, the state on the device, until the
-exploitability is at or under a target."""
+exploitability is at or under a target.
+The pre-flop solver (pk_solve_preflop; "Pre-flop solver") is the river solver with no board and a showdown paid by the
+exact matchup table: push_fold_tree / preflop_tree / preflop_trees, solve_preflop / solve_preflop_batch / solve_preflop_d, holding_class."""
 import math
 
 import numpy as np
@@ -120,9 +122,10 @@ class _Builder:
                 out.append(amount)
         return out[:room]
 
-    def betting_round(self, root, bet_fractions, max_raises, end):
+    def betting_round(self, root, bet_fractions, max_raises, end, limp=None):
         """One street from the decision node `root` (player 0 to act, nothing to call); end(p0, p1, parent, text) makes the node a call
-        or a check behind leads to."""
+        or a check behind leads to.  limp (preflop_tree: the root faces the big blind): True -- the root's call does not end the street,
+        the other player may check behind or raise; False -- the root has no call; None -- a call at the root ends it like any other."""
         new, put = self.new, self.put
         pending = [root]
         state = {root: (0, False, 0)}                    # node -> (actor, a check has been made, raises so far)
@@ -136,7 +139,12 @@ class _Builder:
                 pf = list(puts)
                 kids.append(new(KIND_FOLD0 + p, pf[0], pf[1], n, "%d:fold" % p))
                 pc = list(puts); pc[p] = max(puts)
-                kids.append(end(pc[0], pc[1], n, "%d:call" % p))
+                if n == root and limp is not None:
+                    if limp:
+                        c = new(KIND_P0 + (1 - p), pc[0], pc[1], n, "%d:call" % p)
+                        state[c] = (1 - p, True, raises); pending.append(c); kids.append(c)
+                else:
+                    kids.append(end(pc[0], pc[1], n, "%d:call" % p))
                 for amount in (self.sizes(p, puts, 2, bet_fractions) if raises < max_raises else []):
                     pr = list(puts); pr[p] = max(puts) + amount
                     c = new(KIND_P0 + (1 - p), pr[0], pr[1], n, "%d:raise %d" % (p, amount))
@@ -1184,3 +1192,151 @@ def evaluate_turn(board, ranges, tree, strategy, river_strategy, dead=(), device
     """One subgame: the value of (strategy, river_strategy) -- integer arrays or TurnSolutions -- and how exploitable it is."""
     return solve_turn(board, ranges, tree, 0, dead, device=device, lock=np.ones(len(tree.decision_nodes), bool), locked=strategy,
                       river_lock=np.ones(len(tree.river_decision_nodes), bool), river_locked=river_strategy)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the pre-flop solver
+def _blinds(stack, sb, bb, ante):
+    stack, sb, bb, ante = int(stack), int(sb), int(bb), int(ante)
+    if not 0 < sb <= bb <= stack or ante < 0:
+        raise ValueError("0 < sb <= bb <= stack and ante >= 0")
+    return stack, sb, bb, ante
+
+
+def push_fold_tree(stack, sb=1, bb=2, ante=0):
+    """The push / fold game as a RiverTree of five nodes: player 0 (the small blind, first to act heads-up) folds or jams; facing the jam,
+    player 1 folds or calls, and a call is a showdown.  stack: the effective stack in chips BEFORE the blinds (after the ante), so a jam
+    puts `stack` in.  put[root] = (sb, bb), pot = 2 * ante.  Nodes: 0 the root, 1 "0:fold", 2 "0:jam" (player 1 to act), 3 "1:fold",
+    4 "1:call" (the showdown).  The showdown is paid by the exact all-in equity: there is no post-flop betting (solve_preflop)."""
+    stack, sb, bb, ante = _blinds(stack, sb, bb, ante)
+    kind = [KIND_P0, KIND_FOLD0, KIND_P1, KIND_FOLD1, KIND_SHOWDOWN]
+    F = NO_CHILD
+    child = [[1, 2, F, F], [F] * 4, [3, 4, F, F], [F] * 4, [F] * 4]
+    put = [[sb, bb], [sb, bb], [stack, bb], [stack, bb], [stack, stack]]
+    actions = [None, (0, "0:fold"), (0, "0:jam"), (2, "1:fold"), (2, "1:call")]
+    return RiverTree(kind, child, put, 2 * ante, actions)
+
+
+def preflop_tree(stack, sb=1, bb=2, ante=0, bet_fractions=(1.0,), max_raises=3, limp=True):
+    """A pre-flop betting round as a RiverTree: river_tree's rule, started with the big blind as an outstanding bet.  put[root] = (sb, bb),
+    pot = 2 * ante; player 0 (the small blind) may fold, call (limp; not offered with limp=False) or raise; after a limp player 1 may
+    check, which is a showdown, or raise; from there on everything is river_tree's: fold, call (a showdown) or raise, sizes = max(1,
+    floor(fraction * pot after calling)) on top of the call.  The blind does not count among max_raises.  Amounts are capped at `stack`,
+    the effective stack in chips before the blinds (after the ante).  At most 64 nodes and four actions a node (ValueError beyond).
+    Every showdown is paid by the exact all-in equity, whatever the puts: there is no post-flop betting (solve_preflop)."""
+    stack, sb, bb, ante = _blinds(stack, sb, bb, ante)
+    max_raises = int(max_raises)
+    if max_raises < 0:
+        raise ValueError("max_raises must be non-negative")
+    b = _Builder(2 * ante, stack, MAX_NODES)
+    b.betting_round(b.new(KIND_P0, sb, bb, None, None), bet_fractions, max_raises, lambda p0, p1, n, text: b.new(KIND_SHOWDOWN, p0, p1, n, text),
+                    limp=bool(limp))
+    return RiverTree(b.kind, b.child, b.put, 2 * ante, b.actions)
+
+
+def preflop_trees(stacks, sb=1, bb=2, ante=0, bet_fractions=(1.0,), max_raises=3, limp=True, push_fold=False):
+    """(trees, tree_of) for spots of per-spot stacks: stacks is an integer array [m]; one preflop_tree (push_fold=True: push_fold_tree) per
+    DISTINCT stack, in the order the stacks first appear, and tree_of uint32 [m] -- what solve_preflop_batch takes."""
+    stacks = np.asarray(stacks).reshape(-1)
+    index, trees, tree_of = {}, [], np.zeros(stacks.shape[0], np.uint32)
+    for i, key in enumerate(stacks.tolist()):
+        if key not in index:
+            index[key] = len(trees)
+            trees.append(push_fold_tree(key, sb, bb, ante) if push_fold else preflop_tree(key, sb, bb, ante, bet_fractions, max_raises, limp))
+        tree_of[i] = index[key]
+    return trees, tree_of
+
+
+_PAIR_A = np.array([a for b in range(52) for a in range(b)])
+_PAIR_B = np.array([b for b in range(52) for a in range(b)])
+
+
+def holding_class(h):
+    """The class 0 .. 168 of holding index h (an integer or an integer array): the cell 13 * row + column of the 13 x 13 chart over
+    ace-high rank indices 0 (deuce) .. 12 (ace).  A pair of rank r is cell (r, r); a suited holding of ranks hi > lo is (hi, lo); an
+    off-suit one is (lo, hi).  6 holdings a pair class, 4 a suited one, 12 an off-suit one."""
+    h = np.asarray(h)
+    a, b = _PAIR_A[h], _PAIR_B[h]
+    ra, rb = (a // 4 + 12) % 13, (b // 4 + 12) % 13          # (canonical index = 4 * rank0 + suit, and rank0 0 is the ace)
+    lo, hi = np.minimum(ra, rb), np.maximum(ra, rb)
+    suited = (a % 4 == b % 4) & (lo != hi)
+    out = np.where(suited, 13 * hi + lo, 13 * lo + hi)
+    return int(out) if out.ndim == 0 else out
+
+
+class PreflopSolution(RiverSolution):
+    """What pk_solve_preflop returns for one spot or a batch: RiverSolution's fields and properties (strategy uint16 [D, 4, 1326], value and
+    br int64 [2, 1326], status, ev, exploitability, probabilities, solution[i]) for a spot without a board: every holding is valid."""
+
+    def __getitem__(self, i):
+        r = RiverSolution.__getitem__(self, i)
+        return PreflopSolution(r.tree, r.ranges, r.strategy, r.value, r.br, r.status, r.valid)
+
+    def by_class(self, node):
+        """float64 [actions, 13, 13]: the action probabilities at decision node `node` averaged over the holdings of each class
+        (holding_class: cell [row, column]), weighted by the ACTOR's range weight; nan where the class has no weight.  A chart for the eye:
+        the counts behind the solution are NOT suit-symmetric (the evaluator's suit quirks are carried by the matchup table: DESIGN.md
+        section 3.10), so the holdings of one class need not play alike, and the solver does not make them."""
+        self._one()
+        p = self.probabilities(node)
+        w = np.asarray(self.ranges, np.float64)[int(self.tree.kind[int(node)])] * self.valid
+        cls = holding_class(np.arange(L.EQ_HOLDINGS))
+        den = np.bincount(cls, w, 169)
+        out = np.full((p.shape[0], 169), np.nan)
+        for a in range(p.shape[0]):
+            num = np.bincount(cls, np.where(w > 0, w * np.nan_to_num(p[a]), 0.0), 169)
+            out[a] = np.divide(num, den, out=out[a], where=den > 0)
+        return out.reshape(-1, 13, 13)
+
+    def __repr__(self):
+        return "PreflopSolution(status=%r)" % (self.status,)
+
+
+def _preflop_ranges(ranges, m=None):
+    ranges = np.ascontiguousarray(ranges, np.uint16)
+    if ranges.ndim != 3 or ranges.shape[1:] != (2, L.EQ_HOLDINGS) or (m is not None and ranges.shape[0] != m):
+        raise ValueError("ranges must have shape [m, 2, 1326]")
+    return ranges
+
+
+def solve_preflop_batch(ranges, tree, iters, tree_of=None, device=0):
+    """pk_solve_preflop on host arrays: ranges uint16 [m, 2, 1326] over holding_index (player 0, the small blind and first to act, then
+    player 1), one tree for the call or a SEQUENCE of trees with tree_of, an integer array [m] (None: spot i uses tree i, which needs m
+    trees) -> PreflopSolution with a leading [m].  A spot whose tree_of names no tree has status PK_EQ_BAD_TREE and all-zero outputs.
+    Showdowns are paid by the exact all-in equity of the two holdings (the resident matchup table, built on the first call): the game has
+    no post-flop betting."""
+    ranges = _preflop_ranges(ranges)
+    m = ranges.shape[0]
+    one = isinstance(tree, RiverTree)
+    if one and tree_of is not None:
+        raise ValueError("tree_of needs a sequence of trees")
+    rows = _TreeRows([tree] if one else tree, MAX_NODES)
+    trees, tree, tree_of = (None, tree, None) if one else (rows.trees, None, _tree_of(tree_of, len(rows.trees), m))
+    D = max(len(t.decision_nodes) for t in rows.trees)
+    strategy = np.zeros((m, D, 4, L.EQ_HOLDINGS), np.uint16)
+    value, br = np.zeros((m, 2, L.EQ_HOLDINGS), np.int64), np.zeros((m, 2, L.EQ_HOLDINGS), np.int64)
+    status = np.zeros(m, np.uint8)
+    L.check(L.lib().pk_solve_preflop(int(device), m, L.ptr(ranges), *rows.args(), L.ptr(tree_of), int(iters), L.ptr(strategy), L.ptr(value), L.ptr(br),
+                                     L.ptr(status)))
+    valid = np.ones((m, L.EQ_HOLDINGS), bool) & (status == 0)[:, None]
+    return PreflopSolution(tree, ranges, strategy, value, br, status, valid, trees, tree_of)
+
+
+def solve_preflop_d(m, ranges_d, tree, iters, tree_of=None, strategy_d=None, value_d=None, br_d=None, status_d=None, device=0, stream=None):
+    """pk_solve_preflop_d: the same on device-resident buffers (device pointers as ints / c_void_p; the trees stay host RiverTrees; the
+    outputs except status_d may be None), asynchronous on `stream`.  With a SEQUENCE of trees tree_of is the DEVICE pointer of uint32 [m]
+    (None: every spot uses tree 0) and strategy_d holds [m, Dmax, 4, 1326], Dmax the most decision nodes of any tree passed."""
+    one = isinstance(tree, RiverTree)
+    if one and tree_of is not None:
+        raise ValueError("tree_of needs a sequence of trees")
+    L.check(L.lib().pk_solve_preflop_d(int(device), int(m), ranges_d, *_TreeRows([tree] if one else tree, MAX_NODES).args(), tree_of, int(iters),
+                                       strategy_d, value_d, br_d, status_d, stream))
+
+
+def solve_preflop(ranges, tree, iters, device=0):
+    """One pre-flop spot.  ranges: [2, 1326] integers 0 .. 65535 over holding_index, player 0 (the small blind, first to act) then player 1;
+    tree: push_fold_tree / preflop_tree, or any RiverTree of kinds 0 .. 4.  A reach starts at weight << 4 and every split rounds down:
+    scale a range so that its largest weight uses the sixteen bits."""
+    r = solve_preflop_batch(_preflop_ranges(np.asarray(ranges)[None], 1), tree, iters, device=device)[0]
+    if r.status:
+        raise ValueError("invalid spot: " + equity_status_text(r.status))
+    return r

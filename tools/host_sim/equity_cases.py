@@ -60,6 +60,7 @@ import hero_hist_spec as HHS             # noqa: E402
 import hist_cluster_spec as CS          # noqa: E402
 import hist_spec as HS                  # noqa: E402
 import preflop_spec as PS               # noqa: E402
+import preflop_solver_spec as PFS       # noqa: E402
 import river_solver_spec as RVS         # noqa: E402
 import resolve_spec as RZS              # noqa: E402
 import resume_spec as RMS               # noqa: E402
@@ -84,6 +85,7 @@ OUTPUTS = {"equity": ("win", "tie", "share", "boards", "status"), "sampled": ("w
            "pfhero": ("agg", "win", "tie", "boards", "status"), "pfrvr": ("win", "tie", "tot"),
            "riversolve": ("strategy", "value", "br", "status"), "turnsolve": ("strategy", "river_strategy", "value", "br", "status"),
            "rivertrees": ("strategy", "value", "br", "status"), "turntrees": ("strategy", "river_strategy", "value", "br", "status"),
+           "pfsolve": ("strategy", "value", "br", "status"),
            "riverlock": ("strategy", "value", "br", "status"), "turnlock": ("strategy", "river_strategy", "value", "br", "status"),
            "riverresolve": ("strategy", "value", "br", "node_reach", "node_value", "node_br", "status"),
            "turnresolve": ("strategy", "river_strategy", "value", "br", "node_reach", "node_value", "node_br", "status"),
@@ -1760,6 +1762,60 @@ def turn_arith_cases():
             arith_case("tarith-corner-swing-p12", 4, SRC.corner_call(4, 12, "swing"), quick=False),
             arith_case("tarith-corner-p48-fixture", 4, SRC.corner_call(4, 48, "top"), quick=False, fixture="turn_corner_p48.npz")]
 
+# ---------------------------------------------------------------------------------------------------------------- pre-flop solver
+def pfsolve_case(name, trees, tree_of, iters, seed, m=None, outputs=None, quick=True, redit=None):
+    """k_preflop_solve at a grid of 1 against tests/preflop_solver_spec.py on the driver's fixed-pattern table (preflop_table());
+    tree_of None: the driver gets none, every spot uses tree 0.  int64 value / br are compared as their bit patterns."""
+    m = len(tree_of) if tree_of is not None else m
+    rng = np.random.default_rng(seed)
+    ranges = rng.integers(0, 65536, (m, 2, HOLDINGS)).astype(np.uint16)
+    for row in ranges.reshape(-1, HOLDINGS):
+        row[rng.integers(0, HOLDINGS, 200)] = 0
+        row[rng.integers(0, HOLDINGS, 100)] = 65535
+    if redit:
+        redit(ranges)
+    arrays = {"m": ("u32", [m]), "grid": ("u32", [1]), "iters": ("u32", [iters]), **tree_rows(trees, 64), "ranges": ("u16", ranges)}
+    if tree_of is not None:
+        tree_of = np.asarray(tree_of, np.uint32)
+        arrays["tree_of"] = ("u32", tree_of)
+
+    def expect():
+        r = PFS.solve_batch(preflop_table(), ranges, trees, iters, tree_of)
+        return {k: (r[k].view(np.uint64) if k in ("value", "br") else r[k]) for k in OUTPUTS["pfsolve"]}
+    return Case(name, "pfsolve", arrays, expect, outputs, quick)
+
+
+def pfsolve_cases():
+    """The pre-flop solver's cases (names pfsolve-...), every one at a grid of 1: ONE workgroup takes the spots in turn, so a stale tree,
+    stale regrets or stale LDS of the spot before would show.  NOT part of all_cases()."""
+    from pokerl_amd.solver import RiverTree, preflop_tree, push_fold_tree
+    FF = 0xFF
+    big = preflop_tree(40, 1, 2, 0, (0.75, 2.0), 3)
+    assert big.n == 64
+    three = RiverTree([0, 1, 4], [[1, FF, FF, FF], [2, FF, FF, FF], [FF] * 4], [[1, 2], [2, 2], [2, 2]], 3)
+    pf, pf_ante, limp = push_fold_tree(20), push_fold_tree(9, 1, 2, 1), preflop_tree(12, 1, 2, 0, (1.0,), 2)
+
+    def empty(ranges):
+        ranges[0, 1] = 0
+        ranges[1, 0] = 0
+
+    def single(ranges):
+        ranges[0, 0] = 0
+        ranges[0, 0, 1325] = 40000
+        ranges[1, 1] = 0
+        ranges[1, 1, 0] = 65535
+    cs = [pfsolve_case("pfsolve-pushfold-after-64-before-3", [big, pf, three], [0, 1, 2, 1], 2, 91),
+          pfsolve_case("pfsolve-bad-tree-between", [pf, limp], [1, 2, 0, 0xFFFFFFFF, 1], 2, 92),
+          pfsolve_case("pfsolve-empty-range", [pf_ante], None, 2, 93, m=2, redit=empty),
+          pfsolve_case("pfsolve-one-holding", [limp], None, 3, 94, m=2, redit=single),
+          pfsolve_case("pfsolve-iters1", [pf, three], [1, 0, 0], 1, 95),
+          pfsolve_case("pfsolve-iters3-limp", [limp, pf_ante], [0, 1], 3, 96),
+          pfsolve_case("pfsolve-no-strategy", [limp, three], [0, 1], 2, 97, outputs=("value", "br", "status")),
+          pfsolve_case("pfsolve-strategy-alone", [pf], None, 2, 98, m=1, outputs=("strategy", "status")),
+          pfsolve_case("pfsolve-status-only", [pf, three], [0, 7, 1], 1, 99, outputs=("status",))]
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
 
 def all_cases():
     cs = rvr_hist_cases() + range_cases() + equity_cases() + sampled_cases()
@@ -1775,7 +1831,7 @@ def main():
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--keep")
     a = ap.parse_args()
-    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() + river_trees_cases() + turn_trees_cases() + river_lock_cases() + turn_lock_cases() + river_resolve_cases() + turn_resolve_cases() + river_resume_cases() + turn_resume_cases() + river_arith_cases() + turn_arith_cases() if (c.quick or not a.quick) and a.only in c.name]
+    cases = [c for c in all_cases() + ranged_cases() + ev_cases() + ranged_ev_cases() + cluster_cases() + hero_hist_cases() + preflop_cases() + river_cases() + turn_cases() + river_trees_cases() + turn_trees_cases() + river_lock_cases() + turn_lock_cases() + river_resolve_cases() + turn_resolve_cases() + river_resume_cases() + turn_resume_cases() + river_arith_cases() + turn_arith_cases() + pfsolve_cases() if (c.quick or not a.quick) and a.only in c.name]
     if a.list:
         for c in cases:
             print("%-34s %-8s %s" % (c.name, c.family, "quick" if c.quick else ""))

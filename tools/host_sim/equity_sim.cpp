@@ -9,7 +9,9 @@
 //   equity_sim <case file> <out file>
 // Case file: lines "name dtype count" (dtype u8 u16 u32 u64 i32) each followed by a line of `count` decimal values, and
 // "family <name>" / "outputs <name> ..." lines.  Out file: the same array format.
-// -DPK_ES_ONLY=1 .. 21: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist, preflop, rangedev, riversolve, turnsolve, rivertrees, turntrees, riverlock, turnlock, riverresolve, turnresolve, riverresume, turnresume), so that a test can compile them side by side.
+// -DPK_ES_ONLY=1 .. 22: a build of ONE family (equity, sampled, range, rvr, hist, ranged, ev, cluster, herohist, preflop, rangedev, riversolve, turnsolve, rivertrees, turntrees, riverlock, turnlock, riverresolve, turnresolve, riverresume, turnresume, pfsolve), so that a test can compile them side by side.
+// The pfsolve family (pk_preflop_solver.hip: k_preflop_solve) takes the trees as rivertrees does, an optional tree_of (none: every spot uses tree 0)
+// and ranges; the table it reads is the readers' fixed pattern (fill_table), which has none of the real table's structure: the kernel must not lean on any.
 // The riverresume / turnresume families (k_resume_prep, k_resume_river_solve / k_resume_turn_solve) take what riverresolve / turnresolve take and the state arrays,
 // which go in and come out: allocations of exactly their size, holding what the case put there.
 // The riverresolve / turnresolve families (k_resolve_prep, k_resolve_river_solve / k_resolve_turn_solve) take what riverlock / turnlock take (ranges optional) and
@@ -80,6 +82,9 @@
 #endif
 #if PK_ES_HAS(13) || PK_ES_HAS(15) || PK_ES_HAS(17) || PK_ES_HAS(19) || PK_ES_HAS(21)
 #include "../../pokerl_amd/csrc/pk_turn_solver.hip"
+#endif
+#if PK_ES_HAS(22)
+#include "../../pokerl_amd/csrc/pk_preflop_solver.hip"
 #endif
 #include <chrono>
 #include <climits>
@@ -581,6 +586,9 @@ void run_preflop(Case &c, const uint32_t *tab) {
     printf("chunks %u (slice %u boards)\n", launches, slice);
 }
 
+#endif
+
+#if PK_ES_HAS(10) || PK_ES_HAS(22)
 // the readers' table: win, then tie, a fixed pattern
 void fill_table(uint32_t *M) {
     for (size_t i = 0; i < PFM_CELLS; ++i) {
@@ -588,6 +596,9 @@ void fill_table(uint32_t *M) {
         M[PFM_CELLS + i] = ((uint32_t)i * 40503u + 7u) & 1023u;
     }
 }
+#endif
+
+#if PK_ES_HAS(10)
 
 // k_pfm_prep<TABLE>, k_pfm_hero
 void run_preflop_hero(Case &c) {
@@ -623,7 +634,7 @@ void run_preflop_rvr(Case &c) {
 }
 #endif
 
-#if PK_ES_HAS(12) || PK_ES_HAS(14) || PK_ES_HAS(16) || PK_ES_HAS(18) || PK_ES_HAS(20)
+#if PK_ES_HAS(12) || PK_ES_HAS(14) || PK_ES_HAS(16) || PK_ES_HAS(18) || PK_ES_HAS(20) || PK_ES_HAS(22)
 // nact and row as the host check derives them -> the number of decision nodes
 size_t pack_river_tree(RsTree &t, uint32_t n, uint32_t pot, const uint8_t *kind, const uint8_t *child, const uint32_t *put) {
     t = RsTree{};
@@ -692,6 +703,42 @@ void run_river_trees(Case &c, const uint32_t *tab) {
     char *wp = ws.p;
     const RsTrees tt{trees.p, tree_of, nmax, (uint32_t)Dmax};
     if (out.strategy || out.value || out.br) pk_sim::launch(grid, RS_BLOCK, [&] { k_trees_river_solve(tab, dp, tt, spots, out, wp, iters, (uint32_t)m); });
+}
+#endif
+
+#if PK_ES_HAS(22)
+// k_preflop_solve: ONE launch, which writes the status too (pk::ps_launch)
+void run_preflop_solve(Case &c) {
+    const size_t m = (size_t)c.num("m");
+    const unsigned grid = (unsigned)c.num("grid");
+    const uint32_t ntrees = (uint32_t)c.num("ntrees"), iters = (uint32_t)c.num("iters");
+    if (ntrees < 1 || grid < 1) die("pfsolve: no tree, or no workgroup");
+    const uint32_t *n = c.need<uint32_t>("n", ntrees), *pot = c.need<uint32_t>("pot", ntrees), *tree_of = c.arr<uint32_t>("tree_of", m);
+    const uint8_t *kind = c.need<uint8_t>("kind", (size_t)ntrees * RS_MAX_NODES), *child = c.need<uint8_t>("child", (size_t)ntrees * RS_MAX_NODES * 4);
+    const uint32_t *put = c.need<uint32_t>("put", (size_t)ntrees * RS_MAX_NODES * 2);
+    Work<RsTree> trees(ntrees);                                       // exactly ntrees: an index past them is ASan's to see
+    uint32_t nmax = 0;
+    size_t Dmax = 0;
+    for (uint32_t k = 0; k < ntrees; ++k) {
+        if (n[k] < 1 || n[k] > (uint32_t)RS_MAX_NODES) die("pfsolve: n outside 1 .. 64");
+        const size_t row = (size_t)k * RS_MAX_NODES;
+        Dmax = std::max(Dmax, pack_river_tree(trees.p[k], n[k], pot[k], kind + row, child + row * 4, put + row * 2));
+        nmax = std::max(nmax, n[k]);
+    }
+    const uint16_t *ranges = c.need<uint16_t>("ranges", m * 2 * RS_HOLDINGS);
+    RsOut out{};
+    out.strategy = c.output<uint16_t>("strategy", "u16", m * Dmax * 4 * RS_HOLDINGS);
+    out.value = (int64_t *)c.output<uint64_t>("value", "u64", m * 2 * RS_HOLDINGS);
+    out.br = (int64_t *)c.output<uint64_t>("br", "u64", m * 2 * RS_HOLDINGS);
+    out.status = c.output<uint8_t>("status", "u8", m);
+    const bool solve = out.strategy || out.value || out.br;
+    Work<char> ws(solve ? (size_t)grid * ps_group_bytes(nmax) : 0);   // sized by the grid and the largest tree, as pk_solve_preflop sizes it
+    Work<uint32_t> M(2 * PFM_CELLS);
+    fill_table(M.p);
+    const uint32_t *mp = M.p;
+    char *wp = ws.p;
+    const RsTrees tt{trees.p, tree_of, nmax, (uint32_t)Dmax};
+    pk_sim::launch(grid, PS_BLOCK, [&] { k_preflop_solve(mp, ranges, tt, ntrees, out, wp, iters, (uint32_t)m); });
 }
 #endif
 
@@ -1100,7 +1147,7 @@ int main(int argc, char **argv) {
     Case c(argv[1]);
     // the function-local __shared__ arrays of the main kernels (the preparation kernels have none)
     const size_t lds = pk_sim::lds_find({"8k_equityILi", "5k_eqsILi", "5k_eqrPKj", "5k_rvrPKj", "6k_histPKj", "11k_hero_histPKj", "5k_eqwILi", "4k_evILi", "5k_evwILi", "10k_cl_quant", "11k_cl_assign",
-                                        "11k_cl_update", "14k_cl_seed_dist", "14k_cl_seed_pick", "10k_pfm_rank", "11k_pfm_count", "10k_pfm_hero", "9k_pfm_rvr", "13rs_solve_bodyILb", "13ts_solve_bodyILb"});
+                                        "11k_cl_update", "14k_cl_seed_dist", "14k_cl_seed_pick", "10k_pfm_rank", "11k_pfm_count", "10k_pfm_hero", "9k_pfm_rvr", "13rs_solve_bodyILb", "13ts_solve_bodyILb", "15k_preflop_solve"});
     Work<uint32_t> tab(EVAL7_TAB_WORDS);
     for (int i = 0; i < EVAL7_TAB_WORDS; ++i) tab.p[i] = eval7_tab_entry((uint32_t)i);
     const auto t0 = std::chrono::steady_clock::now();
@@ -1192,6 +1239,9 @@ int main(int argc, char **argv) {
 #endif
 #if PK_ES_HAS(21)
     if (c.family == "turnresume") { run_turn_resume(c, tab.p); ran = true; }
+#endif
+#if PK_ES_HAS(22)
+    if (c.family == "pfsolve") { run_preflop_solve(c); ran = true; }
 #endif
     if (!ran) die("family " + c.family + ": not in this build");
     c.write(argv[2]);

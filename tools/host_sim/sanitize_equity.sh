@@ -1,9 +1,9 @@
 #!/bin/bash
 # Dev-only: the 8-wave CPU build of the equity kernels (equity_sim.cpp on wg_shim.h) under ASan + UBSan and under TSan, EVERY case of
-# equity_cases.py -- all_cases(), the ranged family's ranged_cases(), the EV family's ev_cases(), the ranged EV's ranged_ev_cases(), the histogram clustering's cluster_cases(), the hero histograms' hero_hist_cases(), the pre-flop count pass's preflop_cases() the river solver's river_cases(), the turn solver's turn_cases() and the tree-per-spot solvers' river_trees_cases() and turn_trees_cases() and the locked solvers' river_lock_cases() and turn_lock_cases() and the re-solving calls' river_resolve_cases() and turn_resolve_cases() -- on both builds, each compared with the numpy specs; exits 0 only if
+# equity_cases.py -- all_cases(), the ranged family's ranged_cases(), the EV family's ev_cases(), the ranged EV's ranged_ev_cases(), the histogram clustering's cluster_cases(), the hero histograms' hero_hist_cases(), the pre-flop count pass's preflop_cases() the river solver's river_cases(), the turn solver's turn_cases() and the tree-per-spot solvers' river_trees_cases() and turn_trees_cases() and the locked solvers' river_lock_cases() and turn_lock_cases() and the re-solving calls' river_resolve_cases() and turn_resolve_cases() and the pre-flop solver's pfsolve_cases() -- on both builds, each compared with the numpy specs; exits 0 only if
 # every case on both builds does.  Stand-alone programs, run directly on the CPU; the two builds are compiled side by side (2 jobs, never more
 # than 16).  The committed outputs: profiles/equity_sim_sanitizers.txt (the five earlier families) and, from `--only ranged`,
-# profiles/equity_ranged_sim_sanitizers.txt, and from `--only ev-` profiles/equity_ev_sim_sanitizers.txt, and from `--only evw-` profiles/ranged_ev_sim_sanitizers.txt, and from `--only cluster` profiles/hist_cluster_sim_sanitizers.txt, and from `--only herohist` profiles/hero_hist_sim_sanitizers.txt, and from `--only preflop` profiles/preflop_sim_sanitizers.txt, and from `--only rsolve` profiles/river_solver_sim_sanitizers.txt, and from `--only tsolve` profiles/turn_solver_sim_sanitizers.txt, and from `--only trees` profiles/solver_trees_sim_sanitizers.txt, and from `--only lock-` profiles/solver_lock_sim_sanitizers.txt, and from `--only res-` profiles/solver_resolve_sim_sanitizers.txt, and from `--only sum-` (the resuming calls' river_resume_cases() and turn_resume_cases()) profiles/solver_resume_sim_sanitizers.txt, and from `--only arith-` (the solvers' arithmetic: river_arith_cases() and turn_arith_cases()) profiles/solver_arith_sim_sanitizers.txt.
+# profiles/equity_ranged_sim_sanitizers.txt, and from `--only ev-` profiles/equity_ev_sim_sanitizers.txt, and from `--only evw-` profiles/ranged_ev_sim_sanitizers.txt, and from `--only cluster` profiles/hist_cluster_sim_sanitizers.txt, and from `--only herohist` profiles/hero_hist_sim_sanitizers.txt, and from `--only preflop` profiles/preflop_sim_sanitizers.txt, and from `--only rsolve` profiles/river_solver_sim_sanitizers.txt, and from `--only tsolve` profiles/turn_solver_sim_sanitizers.txt, and from `--only trees` profiles/solver_trees_sim_sanitizers.txt, and from `--only lock-` profiles/solver_lock_sim_sanitizers.txt, and from `--only res-` profiles/solver_resolve_sim_sanitizers.txt, and from `--only sum-` (the resuming calls' river_resume_cases() and turn_resume_cases()) profiles/solver_resume_sim_sanitizers.txt, and from `--only arith-` (the solvers' arithmetic: river_arith_cases() and turn_arith_cases()) profiles/solver_arith_sim_sanitizers.txt, and from `--only pfsolve` (the pre-flop solver: pfsolve_cases()) profiles/preflop_solver_sim_sanitizers.txt.
 #   tools/host_sim/sanitize_equity.sh [out-dir] [equity_cases.py options, e.g. --only rvr]      (default out-dir /tmp/equity_sim_san)
 set -e -o pipefail
 cd "$(dirname "$0")/../.."
